@@ -9,13 +9,16 @@ x 80 layers, 1 ray, fp64.  Inputs are uploaded before the timed region (HBM resi
 
   python bench.py --gpus N --steps K --warmup W     N > 1 without WORLD_SIZE: starts its own N ranks (launch_ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (the same ranks, from torchrun)
+  python bench.py --full              the headline and everything measured besides it (below)
+  python bench.py --dump-outputs DIR  also write what the last timed step computed to DIR/<name>.npy
   python bench.py --config 2|3|4|lut  extra lines for BASELINE configs[2..4] and the look-up-table build (bench_configs.py;
                                       not the headline)
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline`
-(dominant kernel: EXECUTED flops, counted on the device, over its HIP-event time)
-and `cpu_baseline` (the oracle, i.e. the CPU restatement of the reference, on the
-host cores; N = 1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline: `value`,
+`ms_per_step`, the workload's `config` and a `checksum` of the last spectrum.  With --full, after the timed steps, the
+line also gets `roofline` (dominant kernel: EXECUTED flops, counted on the device, over its HIP-event time), the HBM
+and brute-force figures, the exact-mode kernels' times, `cpu_baseline` (the oracle, i.e. the CPU restatement of the
+reference, on the host cores, with its parity check; N = 1 only) and, for N > 1, the per-rank record `dist`.
 """
 import argparse
 import gc
@@ -50,6 +53,7 @@ FLOP_PER_EVAL = 16             # SURVEY 8-d flop model per (line, layer, grid po
 # The far field's numbers follow the expansion degree the library was built with (flop_model; degree 22 until the end of
 # round 6: 281 / 93 / 233 / 1932; degree 19 since: 253 / 81 / 188 / 1440).
 ASYNC_GATHER = os.environ.get("SR_GATHER_ASYNC", "1") != "0"   # SR_GATHER_ASYNC=0: every step waits for its all-gather
+DUMP_MAX_ELEMS = 1 << 21       # --dump-outputs: at most 16 MB of float64 per array (three arrays: 48 MB)
 
 
 def flop_model(degree=22):
@@ -248,6 +252,20 @@ def cpu_columns(L, scale):
                      for a, b in zip(L["pt_off"][:-1], L["pt_off"][1:])])
 
 
+def dump_outputs(out_dir, arrays, max_elems=DUMP_MAX_ELEMS):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy in float64.  One larger than max_elems elements
+    is written as a fixed sample of max_elems of its entries (flat indices drawn without replacement by
+    numpy.random.default_rng(0), in ascending order): the same entries in every run with the same arguments."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > max_elems:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), max_elems, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float64))
+
+
 def launch_ranks(n, argv=None, build=True):
     """`python bench.py --gpus N` with no WORLD_SIZE in the environment: start the N ranks as fresh child processes of
     this script (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set as torchrun would) and return the job's exit
@@ -313,7 +331,14 @@ def main():
     ap.add_argument("--layers", type=int, default=80)
     ap.add_argument("--rays", type=int, default=1)
     ap.add_argument("--ppl", type=int, default=8, help="grid points per lane in the coefficient kernels")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, measure and check everything besides the "
+                    "headline: per-kernel HIP-event times, rooflines, the exact-mode kernels, the CPU baseline and its "
+                    "parity check, the per-rank record of N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as "
+                    "DIR/<name>.npy (float64): radiance (the step's gathered spectrum), abs_coeff and emi_coeff (this "
+                    "rank's coefficient spectra); an array of more than %d entries as a fixed seeded sample of that many"
+                    % DUMP_MAX_ELEMS)
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget with --full (0 = skip)")
     ap.add_argument("--shard", default="", help="R/W: time only the spectral shard of rank R of W on this GPU "
                     "(tuning aid for the multi-GPU shard size; not a bench line of the metric)")
     ap.add_argument("--3d", dest="three_d", action="store_true", help="--config 3 in its 3-D form: a coefficient row per LOS "
@@ -327,6 +352,10 @@ def main():
                     "pairs (multipole -> local), sparse line sets per line and box; 2: box pairs always; 1: per line and box")
     args = ap.parse_args()
     args.config = args.config if args.config == "lut" else int(args.config)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != 1:
+        ap.error("--dump-outputs writes the headline workload's outputs (--config 1)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:   # the driver's form: python bench.py --gpus N
         sys.exit(launch_ranks(args.gpus))
 
@@ -405,8 +434,7 @@ def main():
     # 60th step of every run).  Collect now and move what exists into the permanent generation.
     gc.collect()
     gc.freeze()
-    kms = np.zeros(5)
-    engine.set_timing(0)          # no per-kernel timing events in the timed steps (diagnostics: the pass below has them)
+    engine.set_timing(0)          # no per-kernel timing events in the timed steps (diagnostics: --full has them)
     step()
     barrier()
     wait_s[0] = 0.0
@@ -417,12 +445,9 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     wait_timed = wait_s[0]
-    engine.set_timing(1)
-    for _ in range(args.steps):   # HIP-event times of this rank's kernels (each query synchronises that step)
-        step()
-        kms += np.array(ls.last_kernel_ms())
-    barrier()
-    dist_rec = None
+    checksum = float(spec.sum().item())
+    if args.dump_outputs and rank == 0:   # what the last timed step computed, before anything else runs on ab / em
+        dump_outputs(args.dump_outputs, {"radiance": spec, "abs_coeff": ab, "emi_coeff": em})
     if world > 1:
         dev_t = "cuda" if torch.distributed.get_backend() == "nccl" else "cpu"
         # every rank's own numbers, for rank 0's line (the first real SCALE run must be diagnosable from
@@ -432,91 +457,54 @@ def main():
         torch.distributed.all_gather(every, mine)
         per_rank = np.array([e.cpu().numpy() for e in every])
         elapsed = float(per_rank[:, 0].max())              # the bench contract: MAX over ranks
-        costs, n_lines_rank = sd.shard_costs(L["freq"], grid, bounds)
-        # what the collective really was, and the asynchronous gather of the last timed step against a blocking one
-        # of the same shard (outside the timed region)
-        dist_rec = dict(sd.dist_info(), async_gather=bool(ASYNC_GATHER), gathers=dict(sd.stats),
-                        shards={"bounds": [list(b) for b in bounds], "balanced": bool(args.balanced),
-                                "points": [hi - lo for lo, hi in bounds], "lines_prepared": n_lines_rank,
-                                "model_cost_max_over_mean": float(max(costs) / (sum(costs) / len(costs)))},
-                        per_rank={"ms_per_step": [float(v) / args.steps * 1e3 for v in per_rank[:, 0]],
-                                  "ms_per_step_min": float(per_rank[:, 0].min()) / args.steps * 1e3,
-                                  "ms_per_step_max": float(per_rank[:, 0].max()) / args.steps * 1e3,
-                                  "host_enqueue_ms_per_step": [float(v) / args.steps * 1e3 for v in per_rank[:, 1]],
-                                  "host_ms_in_wait_gathers": [float(v) * 1e3 for v in per_rank[:, 2]]},
-                        rank0_ms_in_wait_gathers=float(per_rank[0, 2]) * 1e3)
-        rad_chk = engine.limb_rays((ab, em), los, resident=False)   # (the per-call staging route: a second opinion)
-        blocking = sd.all_gather_spectrum(rad_chk, args.grid, world, rank, bounds=bounds, async_op=False)
-        torch.cuda.synchronize()
-        dist_rec["async_equals_blocking"] = bool(torch.equal(blocking, spec))
-    kms /= args.steps
-    prep_ms = float(kms[0])
-    main_ms = float(kms[1:].sum())   # far-field mode: the coefficient op as a whole (its kernels overlap)
-    checksum = float(spec.sum().item())
-    # outside the timed region: the kernels of the coefficient op one after the other (HIP events on the
-    # stream they run on), and the work each one executes (counting instantiations, device counters)
-    serial_kms = counts = None
-    if not args.exact:
-        serial_kms, counts = serial_kernel_times_and_counts(engine, ls, step)
-    # outside the timed region: the brute-force kernels (every evaluation exact) for reference
-    exact_kms = None
-    if not args.exact and world == 1:
-        engine.set_far_field(0)
-        step()
-        exact_kms = np.zeros(5)
-        for _ in range(2):
-            spec_x = step()
-            exact_kms += np.array(ls.last_kernel_ms()) / 2
-        exact_checksum = float(spec_x.sum().item())
-        engine.set_far_field(args.far_field)
+
+    # --full: everything besides the headline, all of it after the timed steps
+    dist_rec = serial_kms = counts = exact_kms = None
+    if args.full:
+        kms = np.zeros(5)
+        engine.set_timing(1)
+        for _ in range(args.steps):   # HIP-event times of this rank's kernels (each query synchronises that step)
+            step()
+            kms += np.array(ls.last_kernel_ms())
+        barrier()
+        if world > 1:
+            costs, n_lines_rank = sd.shard_costs(L["freq"], grid, bounds)
+            # what the collective really was, and the asynchronous gather of the last timed step against a blocking one
+            # of the same shard (outside the timed region)
+            dist_rec = dict(sd.dist_info(), async_gather=bool(ASYNC_GATHER), gathers=dict(sd.stats),
+                            shards={"bounds": [list(b) for b in bounds], "balanced": bool(args.balanced),
+                                    "points": [hi - lo for lo, hi in bounds], "lines_prepared": n_lines_rank,
+                                    "model_cost_max_over_mean": float(max(costs) / (sum(costs) / len(costs)))},
+                            per_rank={"ms_per_step": [float(v) / args.steps * 1e3 for v in per_rank[:, 0]],
+                                      "ms_per_step_min": float(per_rank[:, 0].min()) / args.steps * 1e3,
+                                      "ms_per_step_max": float(per_rank[:, 0].max()) / args.steps * 1e3,
+                                      "host_enqueue_ms_per_step": [float(v) / args.steps * 1e3 for v in per_rank[:, 1]],
+                                      "host_ms_in_wait_gathers": [float(v) * 1e3 for v in per_rank[:, 2]]},
+                            rank0_ms_in_wait_gathers=float(per_rank[0, 2]) * 1e3)
+            rad_chk = engine.limb_rays((ab, em), los, resident=False)   # (the per-call staging route: a second opinion)
+            blocking = sd.all_gather_spectrum(rad_chk, args.grid, world, rank, bounds=bounds, async_op=False)
+            torch.cuda.synchronize()
+            dist_rec["async_equals_blocking"] = bool(torch.equal(blocking, spec))
+        kms /= args.steps
+        main_ms = float(kms[1:].sum())   # far-field mode: the coefficient op as a whole (its kernels overlap)
+        # outside the timed region: the kernels of the coefficient op one after the other (HIP events on the
+        # stream they run on), and the work each one executes (counting instantiations, device counters)
+        if not args.exact:
+            serial_kms, counts = serial_kernel_times_and_counts(engine, ls, step)
+        # outside the timed region: the brute-force kernels (every evaluation exact) for reference
+        if not args.exact and world == 1:
+            engine.set_far_field(0)
+            step()
+            exact_kms = np.zeros(5)
+            for _ in range(2):
+                spec_x = step()
+                exact_kms += np.array(ls.last_kernel_ms()) / 2
+            exact_checksum = float(spec_x.sum().item())
+            engine.set_far_field(args.far_field)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = args.steps / elapsed  # one limb spectrum (x rays) per step, whole job
-        evals = float(args.lines) * 13010.0 * args.layers / world           # SURVEY 8-d, per launch
-        flops_bf = FLOP_PER_EVAL * evals
-        alg_bytes = (8.0 * args.grid * args.layers * 2 + 80.0 * args.lines) / world
-        gbs = alg_bytes / (main_ms * 1e-3) / 1e9
-        # HBM traffic from the PMC counters: only for the build it was measured on (sources hash)
-        traffic, traffic_src = None, None
-        pmc_name = next((f for f in ("r06_pmc_hbm.json", "r05_pmc_hbm.json", "r04_pmc_hbm.json", "r03_pmc_hbm.json")
-                         if os.path.exists(os.path.join(ROOT, "profiles", f))), "r06_pmc_hbm.json")
-        pmc = os.path.join(ROOT, "profiles", pmc_name)
-        if os.path.exists(pmc) and world == 1 and args.lines == 100000 and args.grid == 100000 and not args.shard:
-            try:
-                pj = json.load(open(pmc))
-                if pj.get("kernel_sources_sha256") == kernel_sources_sha256():
-                    traffic = pj.get("coefficient_kernels_hbm_bytes_per_step")
-                    traffic_src = {"file": "profiles/" + pmc_name, "profile_tag": pj.get("profile_tag"),
-                                   "kernel_sources_sha256": pj.get("kernel_sources_sha256")[:16],
-                                   "raw_counter_bytes": pj.get("coefficient_kernels_hbm_bytes_per_step_raw"),
-                                   "note": "FETCH_SIZE doubled for vector reads (calibration: profiles/"
-                                           "r03_fetch_calibration.txt), WRITE_SIZE as reported; per step of the "
-                                           "coefficient kernels"}
-                else:
-                    traffic_src = {"file": "profiles/" + pmc_name, "stale": True,
-                                   "note": "measured on other kernel sources than this build: not reported"}
-            except Exception:
-                traffic = None
-        if args.exact:
-            xm = float(kms[1] + kms[2])
-            roofline = {"bound": "fp64-valu", "achieved": flops_bf / (xm * 1e-3) / 1e12, "peak": FP64_VALU_PEAK_TFLOPS,
-                        "unit": "TFLOP/s", "frac": flops_bf / (xm * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS,
-                        "traffic": None, "kernel": "sr_abscoeff_wings_kernel + sr_abscoeff_cores_kernel",
-                        "kernels_ms": dict(zip(["sr_prep_kernel", "sr_abscoeff_wings_kernel",
-                                                "sr_abscoeff_cores_kernel"], [float(v) for v in kms[:3]])),
-                        "flops_per_launch": flops_bf, "mode": "exact"}
-        else:
-            roofline = coefficient_roofline(serial_kms, counts, args.far_field)
-            roofline.update({
-                "traffic": traffic, "traffic_source": traffic_src,
-                "coefficient_op_ms_in_timed_steps": main_ms,
-                "note": "dominant kernel of the step; achieved = flops it EXECUTES (evaluations counted on the device "
-                        "by the counting instantiations of the same kernels x the per-region flops of SURVEY 8-d; region 3 "
-                        "at its own 70) / its average HIP-event duration over 5 launches with the kernels one after the "
-                        "other on the caller's stream (in the timed steps the zones kernel overlaps the far-field kernel "
-                        "on a second stream); peak 78.6 TFLOP/s = fp64 vector = fp64 MFMA dense peak of MI355X (no MFMA "
-                        "use: not a contraction).  HBM is not the bound: arithmetic intensity ~1e3 flop/B"})
         out = {
             "metric": "limb spectra/sec (1e5 lines x 1e5 nu-grid, 80 layers)",
             "value": value * args.rays, "unit": "spectra/s", "n_gpus": world, "steps": args.steps,
@@ -526,7 +514,7 @@ def main():
                                    "%d ray(s), 12 non-LTE levels" % (args.lines, args.grid, args.layers, args.rays),
                        "n_lines": args.lines, "n_grid": args.grid, "n_layers": args.layers, "n_rays": args.rays,
                        "sharding": ("spectral window / %d, one all-gather per step (backend %s: nccl = RCCL over xGMI)"
-                                    % (world, dist_rec["backend"]) if world > 1 else
+                                    % (world, sd.dist_info()["backend"]) if world > 1 else
                                     ("ONLY shard %s timed (tuning aid)" % args.shard if args.shard else "none")),
                        "mode": "exact" if args.exact else ("far-field, box pairs" if args.far_field in (2, 3) else "far-field, per line"),
                        "far_field": {"theta": 4, "degree": engine.far_field_degree(),
@@ -535,19 +523,64 @@ def main():
                                              "degree 22 = bound 2.6e-13 until the end of round 6 (-DSR_KFD=22)"},
                        "device": info["name"],
                        "cu_count": info["cu_count"]},
-            "roofline": roofline,
-            "roofline_hbm": {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                             "frac": gbs / HBM_PEAK_GBS, "traffic": traffic, "bytes_per_launch": alg_bytes,
-                             "note": "the BASELINE-named figure: algorithmic bytes 8*n_grid*n_layers*2 + 80*n_lines "
-                                     "(SURVEY 8-d) / coefficient-op time; <<1 by construction (compute bound)"},
-            "algorithmic_speedup_vs_brute_force": {
+        }
+        if args.full:
+            evals = float(args.lines) * 13010.0 * args.layers / world           # SURVEY 8-d, per launch
+            flops_bf = FLOP_PER_EVAL * evals
+            alg_bytes = (8.0 * args.grid * args.layers * 2 + 80.0 * args.lines) / world
+            gbs = alg_bytes / (main_ms * 1e-3) / 1e9
+            # HBM traffic from the PMC counters: only for the build it was measured on (sources hash)
+            traffic, traffic_src = None, None
+            pmc_name = next((f for f in ("r06_pmc_hbm.json", "r05_pmc_hbm.json", "r04_pmc_hbm.json", "r03_pmc_hbm.json")
+                             if os.path.exists(os.path.join(ROOT, "profiles", f))), "r06_pmc_hbm.json")
+            pmc = os.path.join(ROOT, "profiles", pmc_name)
+            if os.path.exists(pmc) and world == 1 and args.lines == 100000 and args.grid == 100000 and not args.shard:
+                try:
+                    pj = json.load(open(pmc))
+                    if pj.get("kernel_sources_sha256") == kernel_sources_sha256():
+                        traffic = pj.get("coefficient_kernels_hbm_bytes_per_step")
+                        traffic_src = {"file": "profiles/" + pmc_name, "profile_tag": pj.get("profile_tag"),
+                                       "kernel_sources_sha256": pj.get("kernel_sources_sha256")[:16],
+                                       "raw_counter_bytes": pj.get("coefficient_kernels_hbm_bytes_per_step_raw"),
+                                       "note": "FETCH_SIZE doubled for vector reads (calibration: profiles/"
+                                               "r03_fetch_calibration.txt), WRITE_SIZE as reported; per step of the "
+                                               "coefficient kernels"}
+                    else:
+                        traffic_src = {"file": "profiles/" + pmc_name, "stale": True,
+                                       "note": "measured on other kernel sources than this build: not reported"}
+                except Exception:
+                    traffic = None
+            if args.exact:
+                xm = float(kms[1] + kms[2])
+                roofline = {"bound": "fp64-valu", "achieved": flops_bf / (xm * 1e-3) / 1e12, "peak": FP64_VALU_PEAK_TFLOPS,
+                            "unit": "TFLOP/s", "frac": flops_bf / (xm * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS,
+                            "traffic": None, "kernel": "sr_abscoeff_wings_kernel + sr_abscoeff_cores_kernel",
+                            "kernels_ms": dict(zip(["sr_prep_kernel", "sr_abscoeff_wings_kernel",
+                                                    "sr_abscoeff_cores_kernel"], [float(v) for v in kms[:3]])),
+                            "flops_per_launch": flops_bf, "mode": "exact"}
+            else:
+                roofline = coefficient_roofline(serial_kms, counts, args.far_field)
+                roofline.update({
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "coefficient_op_ms_in_timed_steps": main_ms,
+                    "note": "dominant kernel of the step; achieved = flops it EXECUTES (evaluations counted on the device "
+                            "by the counting instantiations of the same kernels x the per-region flops of SURVEY 8-d; region 3 "
+                            "at its own 70) / its average HIP-event duration over 5 launches with the kernels one after the "
+                            "other on the caller's stream (in the timed steps the zones kernel overlaps the far-field kernel "
+                            "on a second stream); peak 78.6 TFLOP/s = fp64 vector = fp64 MFMA dense peak of MI355X (no MFMA "
+                            "use: not a contraction).  HBM is not the bound: arithmetic intensity ~1e3 flop/B"})
+            out["roofline"] = roofline
+            out["roofline_hbm"] = {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                   "frac": gbs / HBM_PEAK_GBS, "traffic": traffic, "bytes_per_launch": alg_bytes,
+                                   "note": "the BASELINE-named figure: algorithmic bytes 8*n_grid*n_layers*2 + 80*n_lines "
+                                           "(SURVEY 8-d) / coefficient-op time; <<1 by construction (compute bound)"}
+            out["algorithmic_speedup_vs_brute_force"] = {
                 "brute_force_flops": flops_bf, "equivalent_tflops": flops_bf / (main_ms * 1e-3) / 1e12,
                 "ratio_to_fp64_peak": flops_bf / (main_ms * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS,
                 "note": "16 flop x n_lines*13010*n_layers evaluations of the reference formulation / coefficient-op "
                         "time: NOT a roofline fraction -- in far-field mode ~94 % of those evaluations are replaced "
-                        "by per-box Taylor expansions, so this exceeds what brute force could reach"},
-            "checksum": checksum,
-        }
+                        "by per-box Taylor expansions, so this exceeds what brute force could reach"}
+        out["checksum"] = checksum
         if dist_rec is not None:
             out["dist"] = dist_rec
         if exact_kms is not None:
@@ -560,7 +593,7 @@ def main():
                 "kernels_ms": {"sr_prep_kernel": float(exact_kms[0]), "sr_abscoeff_wings_kernel": float(exact_kms[1]),
                                "sr_abscoeff_cores_kernel": float(exact_kms[2])},
                 "checksum": exact_checksum}
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             gpu = None
             if not args.shard:  # ab / em hold the last exact-mode step: recompute the timed mode's result
                 step()

@@ -267,7 +267,7 @@ def test_bench_gpus2_launches_itself(eng):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--lines", "20000", "--grid", "40000", "--layers", "16"], env=env, stdout=subprocess.PIPE,
+                        "--lines", "20000", "--grid", "40000", "--layers", "16", "--full"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
@@ -288,7 +288,7 @@ def test_bench_gpus2_launches_itself(eng):
     assert len(sh["lines_prepared"]) == 2 and min(sh["lines_prepared"]) > 10000 and sh["model_cost_max_over_mean"] >= 1.0
     # --balanced: work-balanced bounds (multiples of 64 points), the gather pads to the widest shard
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--balanced",
-                        "--lines", "20000", "--grid", "40000", "--layers", "8", "--cpu-seconds", "0"], env=env,
+                        "--lines", "20000", "--grid", "40000", "--layers", "8", "--cpu-seconds", "0", "--full"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     rec = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")][-1])
@@ -313,7 +313,7 @@ def test_bench_gpus2_under_torchrun(eng):
     env.update(SR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5",
-                        "--warmup", "2", "--lines", "20000", "--grid", "40000", "--layers", "16"], env=env,
+                        "--warmup", "2", "--lines", "20000", "--grid", "40000", "--layers", "16", "--full"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
@@ -321,6 +321,44 @@ def test_bench_gpus2_under_torchrun(eng):
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["dist"]["world_size"] == 2 and rec["dist"]["async_equals_blocking"] is True
     assert rec["value"] > 0 and rec["steps"] == 5
+
+
+def test_bench_plain_line_dump_outputs_and_full(eng, tmp_path):
+    """`python bench.py --gpus 1`: a plain run prints the headline alone (value, ms_per_step, the workload, a checksum)
+    and with --dump-outputs writes what its last timed step computed -- the spectrum the checksum sums and the
+    coefficient spectra -- in float64; a second plain run writes the same arrays (seeded inputs, deterministic path).
+    --full adds the rooflines, the exact-mode kernels and the CPU baseline with its parity check to the same headline."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    small = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--lines", "20000", "--grid", "40000", "--layers", "16"]
+
+    def run(*extra):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + small + list(extra), stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout.decode()[-2000:]
+        return json.loads(lines[0])
+
+    rec = run("--dump-outputs", str(tmp_path / "a"))
+    assert rec["steps"] == 3 and rec["n_gpus"] == 1 and rec["unit"] == "spectra/s" and rec["dtype"] == "f64"
+    assert rec["higher_is_better"] is True and rec["value"] > 0
+    assert abs(rec["value"] - 1e3 / rec["ms_per_step"]) <= 1e-9 * rec["value"]
+    assert not {"roofline", "roofline_hbm", "roofline_exact_mode", "cpu_baseline", "dist"} & set(rec)
+    out = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("radiance", "abs_coeff", "emi_coeff")}
+    assert out["radiance"].shape == (1, 40000) and out["abs_coeff"].shape == out["emi_coeff"].shape == (16, 40000)
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in out.values())
+    assert abs(out["radiance"].sum() - rec["checksum"]) <= 1e-12 * abs(rec["checksum"])
+    run("--dump-outputs", str(tmp_path / "b"))
+    for n, a in out.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / (n + ".npy"))), n
+    full = run("--full", "--cpu-seconds", "1")
+    assert full["steps"] == 3 and abs(full["checksum"] - rec["checksum"]) <= 1e-12 * abs(rec["checksum"])
+    assert full["roofline"]["achieved"] > 0 and full["roofline_exact_mode"]["achieved"] > 0
+    par = full["cpu_baseline"]["parity_vs_oracle"]
+    assert max(par["max_rel_err_abs"], par["max_rel_err_emi"]) < 1e-6
 
 
 def test_rccl_async_gather_branch_one_rank(eng, tmp_path):

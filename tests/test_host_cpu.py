@@ -256,6 +256,30 @@ def test_eight_ranks_through_the_launcher(tmp_path, capfd):
     assert time.time() - t0 < 60.0
 
 
+def test_bench_dump_outputs_writes_float64_and_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: an array within the budget is written whole, in float64 and its own shape; a larger one
+    as the same seeded sample of its entries in every run (flat indices in ascending order), so that two builds can be
+    compared entry for entry.  And the refusals before any work: --steps 0, --dump-outputs with another --config."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4) / 7.0
+    big = torch.randn(50, 40, dtype=torch.float64, generator=torch.Generator().manual_seed(3))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big}, max_elems=500)
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and s.shape == (3, 4) and np.array_equal(s, small.numpy())
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.shape == (500,) and np.array_equal(a, b)
+    idx = np.sort(np.random.default_rng(0).choice(2000, 500, replace=False))
+    assert np.array_equal(a, big.numpy().reshape(-1)[idx])
+    assert 3 * bench.DUMP_MAX_ELEMS * 8 <= 64 << 20
+    for argv in (["--steps", "0"], ["--config", "2", "--dump-outputs", str(tmp_path / "c")]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, timeout=120)
+        assert p.returncode == 2 and b"error" in p.stderr, argv
+
+
 def test_hardware_queues_default_is_set_before_hip_and_respects_the_caller():
     """The coefficient op runs on six HIP streams; the package asks ROCm for eight hardware queues (GPU_MAX_HW_QUEUES) at
     import -- the runtime reads it at its first HIP call -- unless the caller has set the variable (spectrobot_amd/__init__.py)."""

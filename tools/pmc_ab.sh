@@ -13,7 +13,7 @@ for lib in "$@"; do
               "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS"; do
     p=$(echo $pass | cut -d' ' -f1)
     rm -rf /tmp/pab_${i}_$p
-    SPECTROBOT_HIP_LIB=$lib timeout -k 10 300 rocprofv3 --pmc $pass -d /tmp/pab_${i}_$p -o p -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 > $out/pmc_${i}_$p.log 2>&1
+    SPECTROBOT_HIP_LIB=$lib timeout -k 10 300 rocprofv3 --pmc $pass -d /tmp/pab_${i}_$p -o p -- python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 > $out/pmc_${i}_$p.log 2>&1
     echo "variant $i [$lib] pass $p exit=$?"
     echo "== variant $i [$lib]" >> $out/pmc_ab.txt
     python3 tools/rocprof_summary.py /tmp/pab_${i}_$p/p_results.db 2>/dev/null | grep -i "$pat\|^kernel " >> $out/pmc_ab.txt

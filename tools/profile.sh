@@ -11,7 +11,7 @@ tag=${1:-prof}
 out=gpurun_out/prof_$tag
 mkdir -p "$out"
 cd /tmp 2>/dev/null && export TMPDIR=/tmp && cd - > /dev/null
-B="python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0"
+B="python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0"
 run() { # name, rocprof args...
   local name=$1; shift
   timeout -k 10 300 rocprofv3 "$@" -d "$out/$name" -o "$name" -- $B > "$out/$name.log" 2>&1
@@ -27,6 +27,6 @@ python3 tools/rocprof_summary.py "$out"/kt/kt_results.db > "$out/${tag}_kernel_t
 python3 tools/rocprof_summary.py "$out"/pmc1/pmc1_results.db "$out"/pmc2/pmc2_results.db > "$out/${tag}_pmc_summary.txt"
 python3 tools/rocprof_summary.py "$out"/fetch/fetch_results.db "$out"/write/write_results.db "$out"/tcc/tcc_results.db > "$out/${tag}_pmc_hbm.txt"
 python3 tools/pmc_hbm_json.py "$tag" "$out"/fetch/fetch_results.db "$out"/write/write_results.db > "$out/${tag}_pmc_hbm.json"
-timeout -k 10 300 python3 bench.py > "$out/${tag}_bench.json" 2> "$out/bench.err"
+timeout -k 10 300 python3 bench.py --full > "$out/${tag}_bench.json" 2> "$out/bench.err"
 echo "bench exit=$?"
 tail -c 600 "$out/${tag}_bench.json"

@@ -18,7 +18,7 @@ done
 ROUTE=1 REPS=3 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/kt_mc -o kt -- python3 tools/level_tables_probe.py > /dev/null 2>&1
 python3 tools/rocprof_summary.py /tmp/kt_mc/kt_results.db > $out/level_tables_kernel_trace_stats.txt
 {
-for s in 0/8 1/8 2/8 3/8 4/8 5/8 6/8 7/8 0/4 0/2; do timeout -k 10 120 python bench.py --shard $s --cpu-seconds 0 --steps 100 --warmup 10 2>/dev/null | python -c "
+for s in 0/8 1/8 2/8 3/8 4/8 5/8 6/8 7/8 0/4 0/2; do timeout -k 10 120 python bench.py --full --shard $s --cpu-seconds 0 --steps 100 --warmup 10 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('shard %s: %.3f ms/step  op %.3f  serial: prep %.3f ff %.3f wings %.3f zones %.3f' % (d['config']['sharding'][11:14], d['ms_per_step'], r['coefficient_op_ms_in_timed_steps'], r['sr_prep_kernel_ms'], *[v['ms'] for v in r['kernels'].values()]))"; done
 timeout -k 10 100 python tools/host_overhead.py
 } > $out/shards.txt 2>&1; cat $out/shards.txt
@@ -26,7 +26,7 @@ for c in 2 3 4 lut; do timeout -k 10 400 python bench.py --config $c --cpu-secon
 timeout -k 10 400 python bench.py --config 3 --3d --cpu-seconds 8 > $out/config3_3d.json 2> $out/config3_3d.err; echo "config 3 3d rc=$?"
 for c in 3 lut; do timeout -k 10 400 python bench.py --config $c --cpu-seconds 0 --level-route 0 > $out/config${c}_per_level_route.json 2>/dev/null; done
 timeout -k 10 400 python bench.py --config 3 --3d --cpu-seconds 0 --level-route 0 > $out/config3_3d_per_level_route.json 2>/dev/null
-timeout -k 10 200 python bench.py --rays 64 --cpu-seconds 0 > $out/rays64.json 2>/dev/null
+timeout -k 10 200 python bench.py --full --rays 64 --cpu-seconds 0 > $out/rays64.json 2>/dev/null
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/kt_c3 -o kt -- python3 bench.py --config 3 --steps 4 --warmup 1 --cpu-seconds 0 > /dev/null 2>&1
 python3 tools/rocprof_summary.py /tmp/kt_c3/kt_results.db > $out/config3_kernel_trace_stats.txt
 python3 - <<PY

@@ -13,7 +13,7 @@ for lib in build/variants/*.so; do
     timeout -k 10 300 python -m pytest tests/test_gpu_parity.py -q -x -m gpu -k "far_field_vs_exact or randomized or e2e_ch4" 2>&1 | tail -2 | tee -a $out
   fi
   if [ -n "${SHARD:-}" ]; then
-    timeout -k 10 120 python bench.py --shard $SHARD --cpu-seconds 0 --steps 100 --warmup 10 2>/dev/null | python -c "
+    timeout -k 10 120 python bench.py --full --shard $SHARD --cpu-seconds 0 --steps 100 --warmup 10 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('   shard $SHARD: %.3f ms/step  op %.3f  serial: prep %.3f ff %.3f wings %.3f zones %.3f' % (d['ms_per_step'], r['coefficient_op_ms_in_timed_steps'], r['sr_prep_kernel_ms'], *[v['ms'] for v in r['kernels'].values()]))" | tee -a $out
   fi
   unset SPECTROBOT_HIP_LIB

@@ -18,7 +18,7 @@ for pair in "$@"; do
   timeout -k 10 300 python -m pytest tests/test_gpu_parity.py -q -x -m gpu \
       -k "far_field_vs_exact or randomized or e2e_ch4" 2>&1 | tail -4 | tee -a "$out"
   timeout -k 10 200 python tools/farfield_error.py 2>&1 | tee -a "$out"
-  timeout -k 10 200 python bench.py --steps 5 --warmup 2 --cpu-seconds 0 2>&1 | tail -1 | tee -a "$out"
+  timeout -k 10 200 python bench.py --full --steps 5 --warmup 2 --cpu-seconds 0 2>&1 | tail -1 | tee -a "$out"
   unset SPECTROBOT_HIP_LIB
   rm -f "$lib"
 done
