@@ -194,6 +194,45 @@ int sr_abscoeff_layers_dev(sr_lineset *ls, const sr_layers_desc *atm,
 int sr_abscoeff_layers(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo,
                        int64_t g_hi, double *abs_out, double *emi_out);
 
+/* Line strengths (SpectLine.CalcStrength*, spect_classes.py:115-119, 208-310).  Here b(E, T) = exp(-c2 E / T) and
+ * r_L = b(E_L, Tvib_L) / b(E_L, T) (spect_base_module.vibtemp_to_ratio; 1 for the 'all' set, whose E_vib is 0).
+ *
+ * HITRAN intensities s_ref[n_lines] (cm^-1 / (molecule cm^-2)) at t_ref, in the order the lines were given to
+ * sr_lineset_create (n_lines = that call's ld->n_lines, else SR_ERR_ARG).  iso_ab: the isotopic abundance they include.
+ * q_ref: Q(t_ref), or <= 0 for the library's CalcPartitionSum (evaluated by the calls that need it).  HOST, copied; a
+ * later call replaces the set (after the calls in flight on the handle have finished with it). */
+int sr_lineset_set_strengths(sr_lineset *ls, const double *s_ref, int64_t n_lines, double t_ref, double q_ref,
+                             double iso_ab);
+
+/* Strengths of every (layer, line).  s_ab / s_em: DEVICE [n_layers][n_lines], n_lines and line order as given to
+ * sr_lineset_create; lines the lineset's filter dropped are 0.  s_em may be NULL.  atm->tvib NULL = LTE; atm->q_part as
+ * everywhere (NULL: CalcPartitionSum); atm->press is not read (may be NULL).  Stream contract of the coefficient calls.
+ *   SR_STRENGTH_EINSTEIN  CalcStrength_from_Einstein (spect_classes.py:219-254) times iso_ab, from the G coefficients of
+ *                         the coefficient op (0 where A = 0 or a g = 0):
+ *                           s_ab = iso_ab (G_abs b(E_vlo, Tvib_lo) - G_ind b(E_vup, Tvib_up)) / Q(T)
+ *                           s_em = iso_ab G_sp b(E_vup, Tvib_up) / Q(T)
+ *   SR_STRENGTH_HITRAN    CalcStrength_from_Strength (:256-289) from the intensities of sr_lineset_set_strengths (else
+ *                         SR_ERR_ARG); iso_ab is not used (the intensities include theirs):
+ *                           S(T) = s_ref Q(t_ref)/Q(T) b(E_low, T)/b(E_low, t_ref) (1 - b(nu, T))/(1 - b(nu, t_ref))
+ *                                  (CalcStrength_at_T, :1713-1733)
+ *                           s_ab = S(T) alpha_nlte(nu, T, r_lo, r_up)     (:1485-1488)
+ *                           s_em = S(T) r_up BB_erg(T, nu)                (:2097-2107, with its own constants
+ *                                  rc1 = 1.1904e-5, rhck = 1.4388: s_em is 0.05-0.2 % below the Einstein source's)
+ * SR_ERR_TABLE: (mol, iso) not in the TIPS tables and Q not given (q_ref of the intensities, atm->q_part). */
+enum { SR_STRENGTH_EINSTEIN = 0, SR_STRENGTH_HITRAN = 1 };
+int sr_line_strengths_dev(sr_lineset *ls, const sr_layers_desc *atm, int source, double iso_ab,
+                          double *s_ab, double *s_em, void *stream);
+
+/* sr_abscoeff_layers_dev with every line weighted by the HITRAN source's s_ab / iso_ab and s_em / iso_ab instead of
+ * the folded G weights, iso_ab being the abundance given to sr_lineset_set_strengths: the output keeps the meaning of
+ * sr_abscoeff_layers_dev's (per molecule of the isotopologue; the abundance rides on the LOS col_scale).  Everything
+ * else is that call's: stream contract, shards, far-field and exact modes, outer lines, frozen region boundaries.
+ * For a line list whose Einstein A are missing or rounded; with s_ref from the A (Einstein_A_to_LineStrength_hitran)
+ * abs equals sr_abscoeff_layers_dev's to rounding (the reference's LTE check, spect_main_Titan.py:186).
+ * SR_ERR_ARG without sr_lineset_set_strengths; SR_ERR_UNSUPPORTED with sr_lineset_set_linear_weights(ls, 1). */
+int sr_abscoeff_layers_from_strengths_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi,
+                                          double *abs_out, double *emi_out, void *stream);
+
 /* Per-level, per-ctype G-coefficient spectra: what LutSet.add_PT -> SpectralGcoeff.BuildCoeff(lines,
  * Temp, Pres, preCalc_shapes=True) produce for ONE level at every (P, T) of the layer stack
  * (spect_main_module.py:1122-1168, spect_classes.py:1277-1337; called per level from

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("SPECTROBOT_HIP_LIB") or os.path.join(_HERE, "lib", "l
 SR_OK = 0
 SR_ERR_ARG, SR_ERR_LIMIT, SR_ERR_HIP, SR_ERR_NODEVICE, SR_ERR_UNSUPPORTED, SR_ERR_TABLE = -1, -2, -3, -4, -5, -6
 IMXSIG = 13010
+SR_STRENGTH_EINSTEIN, SR_STRENGTH_HITRAN = 0, 1
 
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int32)
@@ -87,6 +88,11 @@ SYMBOLS = {
     "sr_abscoeff_layers_dev": (C.c_int, [C.c_void_p, C.POINTER(LayersDesc), C.c_int64, C.c_int64, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
     "sr_abscoeff_layers": (C.c_int, [C.c_void_p, C.POINTER(LayersDesc), C.c_int64, C.c_int64, dp, dp]),
+    "sr_lineset_set_strengths": (C.c_int, [C.c_void_p, dp, C.c_int64, C.c_double, C.c_double, C.c_double]),
+    "sr_line_strengths_dev": (C.c_int, [C.c_void_p, C.POINTER(LayersDesc), C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "sr_abscoeff_layers_from_strengths_dev": (C.c_int, [C.c_void_p, C.POINTER(LayersDesc), C.c_int64, C.c_int64,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_glevel_pairs_dev": (C.c_int, [C.c_void_p, C.POINTER(LayersDesc), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "sr_gcoeff_levels_dev": (C.c_int, [C.c_void_p, C.POINTER(LayersDesc), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "sr_set_level_route": (C.c_int, [C.c_int]),

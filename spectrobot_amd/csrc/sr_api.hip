@@ -370,6 +370,16 @@ struct sr_lineset {
   std::vector<double> bounds_temps; // sr_lineset_set_bounds_temps: empty = boundaries at the call's own temperatures
   sr_lineset *parent = nullptr;     // per-level sub-lineset: the handle it was cut from (its bounds_temps apply)
   bool linear_weights = false;      // sr_lineset_set_linear_weights (takes effect with bounds_temps only)
+  // where every line came from: n_in lines were given to sr_lineset_create; in_main / in_outer: the input index of
+  // each main / outer line (device order); d_inpos [n_in]: main position p, -2 - outer position, or -1 (filtered out)
+  int64_t n_in = 0;
+  std::vector<int64_t> in_main, in_outer;
+  DevBuf d_inpos;
+  // sr_lineset_set_strengths: HITRAN intensities in device order (main lines, then the outer ones) -- L.s_ref, Lo.s_ref
+  DevBuf d_sref;
+  bool has_strengths = false;
+  double s_t_ref = 0.0, s_q_ref = 0.0, s_iso_ab = 1.0; // their temperature, Q there (<= 0: the TIPS tables), abundance
+  Stager s_str;                                         // layer stage of sr_line_strengths_dev
 };
 
 extern "C" {
@@ -706,7 +716,22 @@ int sr_lineset_create(const sr_lines_desc *ld, const sr_isomolec_desc *iso, cons
   }
   ls->host = subset(all, sel_main);
   ls->host_outer = subset(all, sel_outer);
-  const int rc = lineset_upload(ls);
+  ls->n_in = n;
+  std::vector<int> inpos((size_t)std::max<int64_t>(n, 1), -1);
+  for (const int64_t q : sel_main) {
+    inpos[(size_t)keep[ord[q]]] = (int)ls->in_main.size();
+    ls->in_main.push_back(keep[ord[q]]);
+  }
+  for (const int64_t q : sel_outer) {
+    inpos[(size_t)keep[ord[q]]] = -2 - (int)ls->in_outer.size();
+    ls->in_outer.push_back(keep[ord[q]]);
+  }
+  int rc = lineset_upload(ls);
+  if (!rc) rc = ls->d_inpos.ensure(sizeof(int) * inpos.size());
+  if (!rc) {
+    const hipError_t e = hipMemcpy(ls->d_inpos.p, inpos.data(), sizeof(int) * inpos.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy(inpos)");
+  }
   if (rc) { sr_lineset_destroy(ls); return rc; }
   if (n_kept) *n_kept = m;
   *out = ls;
@@ -740,6 +765,9 @@ int sr_lineset_destroy(sr_lineset *ls) {
   ls->level_up_sets.clear();
   ls->d_lines_outer.release();
   ls->d_gscratch.release();
+  ls->d_inpos.release();
+  ls->d_sref.release();
+  ls->s_str.release();
   ls->d_lines.release();
   ls->d_first.release();
   if (ls->work == &ls->own_work) ls->own_work.release();
@@ -793,18 +821,20 @@ static int l2l_table_dev(const double **out) {
 }
 
 // Per-layer scalars of a call (host, fp64): T, P [atm], 296/T, sqrt(2 N_A k T ln2 / MM), the same at the boundary
-// temperatures, the level populations, then three int rows: pole margin, source pole radius, widest zone.
+// temperatures, the level populations, Q(t_ref) / Q(T) and the vibrational ratios r_L of the strength weights (filled when
+// q_ref > 0: the calls with HITRAN intensities), then three int rows: pole margin, source pole radius, widest zone.
 //   mar: the lineset whose lines bound the margins -- the handle itself, or its PARENT for the far-only level passes of
 //        the multi-channel route (every kernel of that route must place a (line, slot) pair on the same side of the
 //        near / far split: the pole margin enters the admissibility threshold)
-static size_t layer_stage_doubles(int nl, int npop) { return (size_t)nl * (8 + npop); }
+static size_t layer_stage_doubles(int nl, int npop) { return (size_t)nl * (9 + 2 * npop); }
 static size_t layer_stage_bytes(int nl, int npop) { return sizeof(double) * layer_stage_doubles(nl, npop) + sizeof(int) * 3 * (size_t)nl; }
-static int fill_layer_stage(const sr_lineset *ls, const sr_lineset *mar, const sr_lineset *bown, const sr_layers_desc *atm, double *T) {
+static int fill_layer_stage(const sr_lineset *ls, const sr_lineset *mar, const sr_lineset *bown, const sr_layers_desc *atm, double *T,
+                            double q_ref = 0.0) {
   const int nl = atm->n_layers, nlev = ls->n_levels, npop = nlev > 0 ? nlev : 1;
   const size_t hl_doubles = layer_stage_doubles(nl, npop);
   const bool frozen = !bown->bounds_temps.empty();
   double *pa = T + nl, *tr = pa + nl, *sq = tr + nl, *ltr = sq + nl, *ltrb = ltr + nl, *sqb = ltrb + nl, *tb = sqb + nl,
-         *pop = tb + nl;
+         *pop = tb + nl, *qrat = pop + (size_t)nl * npop, *rvib = qrat + nl;
   std::vector<double> q(nl);
   if (atm->q_part) {
     std::copy(atm->q_part, atm->q_part + nl, q.begin());
@@ -856,6 +886,13 @@ static int fill_layer_stage(const sr_lineset *ls, const sr_lineset *mar, const s
     } else {
       pop[k] = 1 / q[k]; // smm:2054
     }
+    if (q_ref > 0.0) { // the strength weights: Q(t_ref) / Q(T), vibtemp_to_ratio(E_L, Tvib_L, T) (1 for the 'all' set)
+      qrat[k] = q_ref / q[k];
+      for (int lv = 0; lv < npop; ++lv) {
+        const double e = nlev > 0 ? ls->e_lev[lv] : 0.0, vibt = (nlev > 0 && atm->tvib) ? atm->tvib[(size_t)lv * nl + k] : T[k];
+        rvib[(size_t)k * npop + lv] = std::exp(-kC2 * e / vibt) / std::exp(-kC2 * e / T[k]);
+      }
+    }
   }
   return SR_OK;
 }
@@ -864,6 +901,7 @@ static LayersDev layers_dev_of(const double *dl, int nl, int npop, bool frozen, 
   LayersDev A;
   A.temps = dl; A.p_atm = dl + nl; A.trat = dl + 2 * nl; A.sqk = dl + 3 * nl; A.ltrat = dl + 4 * nl;
   A.ltrat_b = dl + 5 * nl; A.sqk_b = dl + 6 * nl; A.temps_b = dl + 7 * nl; A.pop = dl + 8 * nl;
+  A.qrat = A.pop + (size_t)nl * npop; A.rvib = A.qrat + nl;
   A.frozen = frozen ? 1 : 0;
   A.linear_w = frozen && linear_w ? 1 : 0;
   A.n_layers = nl; A.n_pop = npop;
@@ -891,9 +929,11 @@ static void far_hierarchy(size_t n_pts, int nl, FarParams *fp) {
 //   coefficients [n_layers][n_boxes_total][2][kFC] written there and folded down to level 0 (sr_l2l_kernel: wider levels
 //   hold partial sums afterwards, level 0 everything); no near kernels, no outer lines, abs_out / emi_out
 //   untouched (may be null); the margins are the PARENT's (fill_layer_stage); *far_has = whether any line met the shard.
+//   q_ref: Q(t_ref) of the HITRAN intensities, for the strength weights (kWeightStrength); 0 otherwise.
 struct CoefOpt {
   double *far_coef = nullptr;
   bool *far_has = nullptr;
+  double q_ref = 0.0;
 };
 
 // The coefficient op with the output weights of `W` (sr_kernels.hpp); the public entry points below
@@ -977,7 +1017,7 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
         }
         if (!bounds_all.empty()) bown->bounds_temps.assign(bounds_all.begin() + k0, bounds_all.begin() + k0 + sub.n_layers);
         const int rc = coef_op(ls, &sub, g_lo, g_hi, abs_out + (size_t)k0 * n_pts_all,
-                               emi_out + (size_t)k0 * n_pts_all, stream, W);
+                               emi_out + (size_t)k0 * n_pts_all, stream, W, opt);
         if (rc) return rc;
       }
       return SR_OK;
@@ -1017,7 +1057,7 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
   DevBuf &d_fast = w.d_fast[b], &d_cold = w.d_cold[b];
   int rc = SL.prepare(hl_bytes);
   if (rc) return rc;
-  rc = fill_layer_stage(ls, far_only && ls->parent ? ls->parent : ls, bown, atm, SL.host<double>());
+  rc = fill_layer_stage(ls, far_only && ls->parent ? ls->parent : ls, bown, atm, SL.host<double>(), opt.q_ref);
   if (rc) return rc;
   // set b was last read by the kernels of the call before the previous one
   if (overlap && w.free_recorded[b]) HIPCHK(hipStreamWaitEvent(pst, w.ev_tables_free[b], 0));
@@ -1594,6 +1634,104 @@ extern "C" {
 int sr_abscoeff_layers_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi,
                            double *abs_out, double *emi_out, void *stream) {
   return coef_op(ls, atm, g_lo, g_hi, abs_out, emi_out, stream, WeightMode{kWeightFolded, 0});
+}
+
+// ---- line strengths (spect_classes.py:208-310): HITRAN intensities, strengths per (layer, line), spectra weighted by them
+
+int sr_lineset_set_strengths(sr_lineset *ls, const double *s_ref, int64_t n_lines, double t_ref, double q_ref,
+                             double iso_ab) {
+  if (!ls || ls->parent || (!s_ref && n_lines > 0)) return SR_ERR_ARG;
+  if (n_lines != ls->n_in || !(t_ref > 0.0) || !std::isfinite(t_ref) || !(iso_ab > 0.0) || !std::isfinite(iso_ab) ||
+      !std::isfinite(q_ref))
+    return SR_ERR_ARG;
+  for (int64_t i = 0; i < n_lines; ++i)
+    if (!std::isfinite(s_ref[i])) return SR_ERR_ARG;
+  // the previous set may still be read by calls in flight on this handle (every call records ev_last_done last)
+  CoefWork &w = *ls->work;
+  if (w.last_done_recorded) HIPCHK(hipEventSynchronize(w.ev_last_done));
+  const size_t nm = ls->in_main.size(), no = ls->in_outer.size();
+  std::vector<double> dev(std::max<size_t>(nm + no, 1), 0.0); // device order: main lines, then the outer ones
+  for (size_t p = 0; p < nm; ++p) dev[p] = s_ref[ls->in_main[p]];
+  for (size_t p = 0; p < no; ++p) dev[nm + p] = s_ref[ls->in_outer[p]];
+  int rc = ls->d_sref.ensure(sizeof(double) * dev.size());
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(ls->d_sref.p, dev.data(), sizeof(double) * dev.size(), hipMemcpyHostToDevice));
+  ls->L.s_ref = ls->d_sref.as<double>();
+  ls->Lo.s_ref = ls->d_sref.as<double>() + nm;
+  ls->has_strengths = true;
+  ls->s_t_ref = t_ref;
+  ls->s_q_ref = q_ref;
+  ls->s_iso_ab = iso_ab;
+  return SR_OK;
+}
+
+// Q(t_ref) of the intensities: given, or CalcPartitionSum (SR_ERR_TABLE for an iso-molecule the tables lack)
+static int strengths_q_ref(const sr_lineset *ls, double *q_ref) {
+  if (ls->s_q_ref > 0.0) {
+    *q_ref = ls->s_q_ref;
+    return SR_OK;
+  }
+  return sr_calc_partition_sum(ls->mol, ls->iso, &ls->s_t_ref, 1, q_ref);
+}
+
+int sr_line_strengths_dev(sr_lineset *ls, const sr_layers_desc *atm, int source, double iso_ab, double *s_ab,
+                          double *s_em, void *stream) {
+  if (!ls || ls->parent || !atm || !s_ab) return SR_ERR_ARG;
+  if (atm->n_layers <= 0 || atm->n_layers > 65535 || !atm->temps) return SR_ERR_ARG;
+  if (source != SR_STRENGTH_EINSTEIN && source != SR_STRENGTH_HITRAN) return SR_ERR_ARG;
+  if (source == SR_STRENGTH_EINSTEIN && !std::isfinite(iso_ab)) return SR_ERR_ARG;
+  if (source == SR_STRENGTH_HITRAN && !ls->has_strengths) return SR_ERR_ARG;
+  const int nl = atm->n_layers, npop = ls->n_levels > 0 ? ls->n_levels : 1;
+  for (int k = 0; k < nl; ++k)
+    if (!(atm->temps[k] > 0.0)) return SR_ERR_ARG;
+  if (atm->tvib)
+    for (size_t i = 0; i < (size_t)ls->n_levels * nl; ++i)
+      if (!(atm->tvib[i] > 0.0)) return SR_ERR_ARG;
+  double q_ref = 0.0;
+  if (source == SR_STRENGTH_HITRAN) {
+    const int rc = strengths_q_ref(ls, &q_ref);
+    if (rc) return rc;
+  }
+  if (ls->n_in == 0) return SR_OK;
+  // fill_layer_stage reads the pressures for the coefficient op's margins only
+  std::vector<double> press(nl, 0.0);
+  sr_layers_desc a = *atm;
+  if (!a.press) a.press = press.data();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  CoefWork &w = *ls->work;
+  const size_t hl_bytes = layer_stage_bytes(nl, npop);
+  int rc = ls->s_str.prepare(hl_bytes);
+  if (rc) return rc;
+  rc = fill_layer_stage(ls, ls, ls, &a, ls->s_str.host<double>(), source == SR_STRENGTH_HITRAN ? q_ref : 0.0);
+  if (rc) return rc;
+  if (w.last_done_recorded) HIPCHK(hipStreamWaitEvent(st, w.ev_last_done, 0));
+  rc = ls->s_str.push(hl_bytes, st);
+  if (rc) return rc;
+  const int *d_pm = nullptr;
+  const LayersDev A = layers_dev_of(ls->s_str.d.as<double>(), nl, npop, false, false, &d_pm);
+  LAUNCHCHK(launch_line_strengths(ls->L, ls->Lo, ls->d_inpos.as<int>(), (int)ls->n_in, A, source, iso_ab, ls->s_t_ref,
+                                  s_ab, s_em, st));
+  rc = ls->s_str.mark(st);
+  if (rc) return rc;
+  HIPCHK(hipEventRecord(w.ev_last_done, st));
+  w.last_done_recorded = true;
+  return SR_OK;
+}
+
+int sr_abscoeff_layers_from_strengths_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi,
+                                          double *abs_out, double *emi_out, void *stream) {
+  if (!ls || ls->parent || !ls->has_strengths) return SR_ERR_ARG;
+  if (ls->linear_weights) {
+    g_err = "the strength weights have no linearised form (sr_lineset_set_linear_weights)";
+    return SR_ERR_UNSUPPORTED;
+  }
+  CoefOpt opt;
+  int rc = strengths_q_ref(ls, &opt.q_ref);
+  if (rc) return rc;
+  WeightMode W{kWeightStrength, 0};
+  W.t_ref = ls->s_t_ref;
+  W.inv_iso_ab = 1.0 / ls->s_iso_ab;
+  return coef_op(ls, atm, g_lo, g_hi, abs_out, emi_out, stream, W, opt);
 }
 
 int sr_gcoeff_layers_dev(sr_lineset *ls, const sr_layers_desc *atm, int level, int64_t g_lo, int64_t g_hi,

@@ -29,6 +29,51 @@ namespace sr {
 // prep: spect_classes.py:174-206 (MakeShapeLine), 312-343 (Calc_Gcoeffs),
 //       spect_main_module.py:2049-2080 (population weights), lineshape.f:443-490
 // ------------------------------------------------------------------------
+// The three G coefficients of line ln at temperature Tw (spect_classes.py:326-337, 1806-1853): 0 where A, g_up or g_lo
+// is 0 (:332-341).  lin: linearised about Tw and continued by dTl (sr_lineset_set_linear_weights, see line_physics).
+struct LineG {
+  double sp, in, ab;
+};
+__device__ __forceinline__ LineG line_gcoeffs(const LinesDev &L, int ln, double Tw, bool lin, double dTl) {
+  auto ex = [](double u) { return exp_bounded(fmin(fmax(u, -700.0), 700.0)); };
+  LineG G{0., 0., 0.};
+  const double x0 = L.freq[ln];
+  const double a_co = L.a_coeff[ln], gu = L.g_up[ln], gl = L.g_lo[ln];
+  if (a_co != 0.0 && gl != 0.0 && gu != 0.0) {
+    const double four_pi = 4 * kPi;
+    const double el = L.e_lower[ln];
+    const double eps_up = el + x0 - L.evib_up[ln], eps_lo = el - L.evib_lo[ln];
+    double rot_up = gu * ex(-kC2 * eps_up / Tw);
+    double rot_lo = gl * ex(-kC2 * eps_lo / Tw);
+    if (lin) { // d ln(exp(-c2 eps / T) / sqrt(T)) / d T = c2 eps / T^2 - 1 / (2 T)   (fac ~ dw ~ sqrt(T))
+      rot_up *= fma(dTl, fma(kC2 * eps_up, 1.0 / (Tw * Tw), -0.5 / Tw), 1.0);
+      rot_lo *= fma(dTl, fma(kC2 * eps_lo, 1.0 / (Tw * Tw), -0.5 / Tw), 1.0);
+    }
+    const double hcf = L.hcf[ln];
+    G.sp = hcf * rot_up * a_co / four_pi;
+    G.in = hcf * rot_up * L.b21[ln] / four_pi;
+    G.ab = hcf * rot_lo * L.b12[ln] / four_pi;
+  }
+  return G;
+}
+
+// CalcStrength_from_Strength (spect_classes.py:256-289) of one line: S(T) of CalcStrength_at_T (:1713-1733) from the
+// intensity s_ref at t_ref, with qrat = Q(t_ref) / Q(T); s_ab = S alpha_nlte(nu, T, r_lo, r_up) (:1485-1488),
+// s_em = S r_up BB_erg(T, nu) with BB_erg's own constants (:2097-2107: rc1 = 1.1904e-5, rhck = 1.4388 -- not c1 = 2 h c^2
+// and c2, which puts s_em 0.05-0.2 % below the Einstein source's, as in the reference).
+struct LineS {
+  double ab, em;
+};
+__device__ inline LineS hitran_strength(double s_ref, double nu, double e_low, double T, double t_ref, double qrat,
+                                        double r_lo, double r_up) {
+  auto ex = [](double u) { return exp_bounded(fmin(fmax(u, -700.0), 700.0)); };
+  const double gm = ex(-kC2 * nu / T); // Boltz_ratio_nodeg(Freq, Temp)
+  const double S = s_ref * qrat * (ex(-kC2 * e_low / T) / ex(-kC2 * e_low / t_ref)) * ((1.0 - gm) / (1.0 - ex(-kC2 * nu / t_ref)));
+  const double alpha = r_lo * (1.0 - gm * r_up / r_lo) / (1.0 - gm);
+  const double bb = 1.1904e-5 * (nu * nu * nu) / (ex(nu * 1.4388 / T) - 1.0);
+  return LineS{S * alpha, S * r_up * bb};
+}
+
 // Widths, normalisation and the two output weights of line ln in layer k.
 //   lw, dw' (= dw / sqrt(ln2)), fac        spect_classes.py:1972, 1984, 1997-1999
 //   G coefficients                         spect_classes.py:326-337, 1806-1853
@@ -57,23 +102,8 @@ __device__ inline LinePhys line_physics(const LinesDev &L, const LayersDev &A, c
   const double Tw = lin ? A.temps_b[k] : T;
   const double fac = (lin ? x0 / kCcgs * A.sqk_b[k] : dw) * A.sqrt_pi_ln2;
   const double dTl = T - Tw;
-  double g_sp = 0., g_in = 0., g_ab = 0.;
-  const double a_co = L.a_coeff[ln], gu = L.g_up[ln], gl = L.g_lo[ln];
-  if (a_co != 0.0 && gl != 0.0 && gu != 0.0) {
-    const double four_pi = 4 * kPi;
-    const double el = L.e_lower[ln];
-    const double eps_up = el + x0 - L.evib_up[ln], eps_lo = el - L.evib_lo[ln];
-    double rot_up = gu * ex(-kC2 * eps_up / Tw);
-    double rot_lo = gl * ex(-kC2 * eps_lo / Tw);
-    if (lin) { // d ln(exp(-c2 eps / T) / sqrt(T)) / d T = c2 eps / T^2 - 1 / (2 T)   (fac ~ dw ~ sqrt(T))
-      rot_up *= fma(dTl, fma(kC2 * eps_up, 1.0 / (Tw * Tw), -0.5 / Tw), 1.0);
-      rot_lo *= fma(dTl, fma(kC2 * eps_lo, 1.0 / (Tw * Tw), -0.5 / Tw), 1.0);
-    }
-    const double hcf = L.hcf[ln];
-    g_sp = hcf * rot_up * a_co / four_pi;
-    g_in = hcf * rot_up * L.b21[ln] / four_pi;
-    g_ab = hcf * rot_lo * L.b12[ln] / four_pi;
-  }
+  const LineG G = line_gcoeffs(L, ln, Tw, lin, dTl);
+  const double g_sp = G.sp, g_in = G.in, g_ab = G.ab;
   const int lu = L.lev_up[ln], ll = L.lev_lo[ln];
   const double *pop = A.pop + (size_t)k * A.n_pop;
   double wabs, wemi;
@@ -96,6 +126,11 @@ __device__ inline LinePhys line_physics(const LinesDev &L, const LayersDev &A, c
     const bool all = W.level < 0;          // no level table: the 'all' set (smm:2052-2057)
     wabs = ((all || ll == W.level) ? g_ab : 0.0) - ((all || lu == W.level) ? g_in : 0.0);
     wemi = (all || lu == W.level) ? g_sp : 0.0;
+  } else if (W.mode == kWeightStrength) { // the HITRAN intensities' s_ab, s_em per molecule of the isotopologue
+    const double *rv = A.rvib + (size_t)k * A.n_pop;
+    const LineS S = hitran_strength(L.s_ref[ln], x0, L.e_lower[ln], T, W.t_ref, A.qrat[k], rv[ll], rv[lu]);
+    wabs = S.ab * W.inv_iso_ab;
+    wemi = S.em * W.inv_iso_ab;
   } else {                               // kWeightTracked: one level's share of abs / emi (smm:2083-2087)
     const double pu = pop[lu], pl = pop[ll];
     wabs = (ll == W.level ? pl * g_ab : 0.0) - (lu == W.level ? pu * g_in : 0.0);
@@ -337,6 +372,52 @@ int launch_outer(const LinesDev &Lo, int n_out, const LayersDev &A, const GridPa
     hipLaunchKernelGGL(sr_outer_add_kernel, dim3((hi - lo + 255) / 256, A.n_layers), dim3(256), 0, st, recs, n_out,
                        lo, hi, g_lo, g_hi, abs_out, emi_out);
   }
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------
+// Line strengths (sr_line_strengths_dev): one thread per (input line, layer), stored in input order -- consecutive
+// threads, consecutive outputs.  inpos[i]: main-list position p >= 0, outer-list position -2 - p, or -1 for a line the
+// lineset's filter dropped (0).
+//   source 0: CalcStrength_from_Einstein (spect_classes.py:219-254) times iso_ab, from the G coefficients and the
+//             populations b(E_L, Tvib_L) / Q(T) the coefficient op uses
+//   source 1: CalcStrength_from_Strength (:256-289), hitran_strength
+// ------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sr_line_strengths_kernel(LinesDev L, LinesDev Lo, const int *__restrict__ inpos,
+                                                                int n_in, LayersDev A, int source, double iso_ab,
+                                                                double t_ref, double *__restrict__ s_ab,
+                                                                double *__restrict__ s_em) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+  if (i >= n_in) return;
+  const int p = inpos[i];
+  double ab = 0.0, em = 0.0;
+  if (p != -1) {
+    const LinesDev &M = p >= 0 ? L : Lo;
+    const int ln = p >= 0 ? p : -2 - p;
+    const int lu = M.lev_up[ln], ll = M.lev_lo[ln];
+    const double T = A.temps[k];
+    if (source == 0) {
+      const double *pop = A.pop + (size_t)k * A.n_pop;
+      const LineG G = line_gcoeffs(M, ln, T, false, 0.0);
+      ab = iso_ab * (pop[ll] * G.ab - pop[lu] * G.in);
+      em = iso_ab * (pop[lu] * G.sp);
+    } else {
+      const double *rv = A.rvib + (size_t)k * A.n_pop;
+      const LineS S = hitran_strength(M.s_ref[ln], M.freq[ln], M.e_lower[ln], T, t_ref, A.qrat[k], rv[ll], rv[lu]);
+      ab = S.ab;
+      em = S.em;
+    }
+  }
+  const size_t o = (size_t)k * (size_t)n_in + (size_t)i;
+  s_ab[o] = ab;
+  if (s_em) s_em[o] = em;
+}
+
+int launch_line_strengths(const LinesDev &L, const LinesDev &Lo, const int *inpos, int n_in, const LayersDev &A,
+                          int source, double iso_ab, double t_ref, double *s_ab, double *s_em, hipStream_t st) {
+  if (n_in <= 0 || A.n_layers <= 0) return 0;
+  hipLaunchKernelGGL(sr_line_strengths_kernel, dim3((n_in + 255) / 256, A.n_layers), dim3(256), 0, st, L, Lo, inpos,
+                     n_in, A, source, iso_ab, t_ref, s_ab, s_em);
   return (int)hipGetLastError();
 }
 

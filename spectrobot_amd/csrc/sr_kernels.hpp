@@ -11,6 +11,7 @@ struct LinesDev {
   const double *evib_up, *evib_lo;
   const int *ic, *lev_up, *lev_lo;
   int n_lines;
+  const double *s_ref; // sr_lineset_set_strengths: HITRAN intensities at WeightMode::t_ref (kWeightStrength); else null
 };
 
 // Device-resident layer stack; per-layer scalars are evaluated on the host in
@@ -25,11 +26,14 @@ struct LayersDev {
   int linear_w;                             // frozen only: the line weights LINEARISED about temps_b (sr_lineset_set_linear_weights)
   int n_layers, n_pop;
   double sqrt_ln2, sqrt_pi_ln2;
+  const double *qrat;                       // kWeightStrength / line strengths: Q(t_ref) / Q(T) [n_layers]
+  const double *rvib;                       //   r_L = b(E_L, Tvib_L) / b(E_L, T) [n_layers][n_pop] (vibtemp_to_ratio)
 };
 
 // What the two output channels ("abs", "emi") of the coefficient kernels accumulate, chosen per call:
 // the weights of line i in layer k, from its three G coefficients and its levels' populations.
-enum { kWeightFolded = 0, kWeightGabsGsp = 1, kWeightGind = 2, kWeightTracked = 3, kWeightLevelPair = 4, kWeightChannels = 5 };
+enum { kWeightFolded = 0, kWeightGabsGsp = 1, kWeightGind = 2, kWeightTracked = 3, kWeightLevelPair = 4, kWeightChannels = 5,
+       kWeightStrength = 6 };
 struct WeightMode {
   int mode;  // kWeightFolded: abs = pop_lo G_abs - pop_up G_ind, emi = pop_up G_sp (smm:2073-2080)
              // kWeightGabsGsp: abs = [lev_lo == level] G_abs, emi = [lev_up == level] G_sp   (BuildCoeff)
@@ -41,7 +45,10 @@ struct WeightMode {
              // kWeightChannels: the multi-channel pass (sr_glevel_pairs_dev / sr_gcoeff_levels_dev): wabs = G_abs, wemi = G_sp,
              //                 FastRec::w3 = -G_ind (level == 0: pair tables) or +G_ind (level == 1: three ctypes apart);
              //                 which spectrum each goes to follows from the line's levels (McChannels)
+             // kWeightStrength: abs = s_ab / iso_ab, emi = s_em / iso_ab of the HITRAN intensities (LinesDev::s_ref at
+             //                 t_ref; hitran_strength), i.e. the folded weights' meaning with S(T) in place of the G's
   int level;
+  double t_ref = 0.0, inv_iso_ab = 0.0; // kWeightStrength only
 };
 
 // Direct index into the sorted window-centre list: first[x - x0] = number of lines with
@@ -202,6 +209,9 @@ int launch_prep(const LinesDev &L, const LayersDev &A, const GridParams &gp, con
 // records per (line, layer), then one thread per (grid point, layer) adds them in line order.
 int launch_outer(const LinesDev &Lo, int n_out, const LayersDev &A, const GridParams &gp, const WeightMode &W,
                  OuterRec *recs, int g_lo, int g_hi, double *abs_out, double *emi_out, hipStream_t st);
+// Line strengths of every (input line, layer) in input order (sr_line_strengths_dev); inpos: input -> device position
+int launch_line_strengths(const LinesDev &L, const LinesDev &Lo, const int *inpos, int n_in, const LayersDev &A,
+                          int source, double iso_ab, double t_ref, double *s_ab, double *s_em, hipStream_t st);
 int abscoeff_tile_points(int variant);
 // which = 0: wings kernel (writes abs/emi), 1: cores kernel (adds into them)
 int launch_abscoeff(int variant, int which, const FastRec *fast, const ColdRec *cold, const IcIndex &ix,

@@ -101,6 +101,7 @@ class LineSet(object):
               "sr_lineset_create")
         self._h = h
         self.n_kept = kept.value
+        self.n_lines_in = int(ld.n_lines)
         self._step_cache = None
 
     def close(self):
@@ -146,6 +147,53 @@ class LineSet(object):
             assert ab.shape == (n, npts) and em.shape == (n, npts) and ab.is_contiguous() and em.is_contiguous()
         check(lib.sr_abscoeff_layers_dev(self._h, C.byref(desc), int(g_lo), g_hi, C.c_void_p(ab.data_ptr()),
                                          C.c_void_p(em.data_ptr()), _stream_ptr()), "sr_abscoeff_layers_dev")
+        return ab, em
+
+    def set_strengths(self, s_ref, t_ref=296.0, iso_ab=1.0, q_ref=None):
+        """HITRAN intensities of the lines, in the order given to the constructor (SpectLine.Strength:
+        spect_classes.strengths_of): cm^-1 / (molecule cm^-2) at t_ref, abundance iso_ab included.  q_ref: Q(t_ref), None
+        for CalcPartitionSum (sr_lineset_set_strengths).  They feed line_strengths(source="hitran") and
+        abscoeff_layers_from_strengths."""
+        s, sp = _d(s_ref)
+        if s.ndim != 1 or s.size != self.n_lines_in:
+            raise ValueError("s_ref must hold one intensity per input line (%d)" % self.n_lines_in)
+        check(lib.sr_lineset_set_strengths(self._h, sp, int(s.size), float(t_ref), 0.0 if q_ref is None else float(q_ref),
+                                           float(iso_ab)), "sr_lineset_set_strengths")
+
+    def line_strengths(self, temps, tvib=None, q_part=None, source="einstein", iso_ab=1.0):
+        """Strengths of every (layer, line) on the GPU (sr_line_strengths_dev): CUDA float64 (s_ab, s_em), each
+        [n_layers, n_lines_in] in input order, 0 for the lines the filter dropped.  source "einstein":
+        CalcStrength_from_Einstein times iso_ab; "hitran": CalcStrength_from_Strength from set_strengths' intensities
+        (iso_ab unused).  tvib [n_levels, n_layers] or None (LTE)."""
+        src = {"einstein": _lib.SR_STRENGTH_EINSTEIN, "hitran": _lib.SR_STRENGTH_HITRAN}.get(source)
+        if src is None:
+            raise ValueError("source must be 'einstein' or 'hitran'")
+        t = np.atleast_1d(np.asarray(temps, dtype=np.float64))
+        desc, keep, n = self._layers(t, np.zeros_like(t), tvib, q_part)
+        s_ab = torch.empty((n, self.n_lines_in), dtype=torch.float64, device="cuda")
+        s_em = torch.empty((n, self.n_lines_in), dtype=torch.float64, device="cuda")
+        check(lib.sr_line_strengths_dev(self._h, C.byref(desc), src, float(iso_ab), C.c_void_p(s_ab.data_ptr()),
+                                        C.c_void_p(s_em.data_ptr()), _stream_ptr()), "sr_line_strengths_dev")
+        return s_ab, s_em
+
+    def abscoeff_layers_from_strengths(self, temps, press, tvib=None, q_part=None, g_lo=0, g_hi=None, out=None):
+        """abscoeff_layers with the lines weighted by their HITRAN strengths (set_strengths): s_ab / iso_ab and
+        s_em / iso_ab of line_strengths(source="hitran") instead of the G coefficients
+        (sr_abscoeff_layers_from_strengths_dev).  Same shapes, shards and modes as abscoeff_layers."""
+        g_hi = self.n_grid if g_hi is None else int(g_hi)
+        desc, keep, n = self._layers(temps, press, tvib, q_part)
+        npts = g_hi - int(g_lo)
+        if npts <= 0:
+            raise ValueError("empty shard")
+        if out is None:
+            ab = torch.empty((n, npts), dtype=torch.float64, device="cuda")
+            em = torch.empty((n, npts), dtype=torch.float64, device="cuda")
+        else:
+            ab, em = out
+            assert ab.shape == (n, npts) and em.shape == (n, npts) and ab.is_contiguous() and em.is_contiguous()
+        check(lib.sr_abscoeff_layers_from_strengths_dev(self._h, C.byref(desc), int(g_lo), g_hi, C.c_void_p(ab.data_ptr()),
+                                                        C.c_void_p(em.data_ptr()), _stream_ptr()),
+              "sr_abscoeff_layers_from_strengths_dev")
         return ab, em
 
     def limb_step(self, temps, press, los, tvib=None, q_part=None, g_lo=0, g_hi=None, out=None, rad=None, grid=None):

@@ -24,6 +24,19 @@ def weight(x, x1, x2, itype='lin'):
     return 1.0 - w2, w2
 
 
+# c2 = h c / k of spect_classes (CODATA-2018, cgs), written out: this module imports nothing of the package
+_C2 = (6.62607015e-34 * 1.e7) * (299792458.0 * 1.e2) / (1.380649e-23 * 1.e7)
+
+
+def vibtemp_to_ratio(E_vib, T_vib, T):
+    """Population of a vibrational level of energy E_vib (cm-1) at its vibrational temperature T_vib relative to its
+    LTE population at the kinetic temperature T: exp(-c2 E_vib / T_vib) / exp(-c2 E_vib / T) (1 for E_vib = 0 or
+    T_vib = T).  Call sites spect_classes.py:280-281 (CalcStrength_from_Strength) and spect_main.py:265-267; the
+    function itself is in the absent module (unpinned: the build's own definition, from the call sites' use as the
+    r1 / r2 of alpha_nlte)."""
+    return np.exp(-_C2 * E_vib / T_vib) / np.exp(-_C2 * E_vib / T)
+
+
 class Level(object):
     """A vibrational level: .energy (cm-1), .lev_string, .minimal_level_string(),
     .local_vibtemp (one vibrational temperature per LOS step, spect_main_module.py:2065)."""

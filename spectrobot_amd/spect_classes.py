@@ -116,6 +116,66 @@ def Einstein_A_to_LineStrength_hitran(A_coeff, wavenumber, temp, Q_part, g_upper
         8 * np.pi * c_cgs * wavenumber ** 2 * Q_part)
 
 
+def Einstein_B21_to_A(B21, wavenumber, units='cm3ergcm2'):
+    """spect_classes.py:1757-1775 (only the unit system the path uses): the inverse of Einstein_A_to_B"""
+    if units != 'cm3ergcm2':
+        raise ValueError("only units='cm3ergcm2' is supported on this path")
+    return B21 * (2 * h_cgs * c_cgs ** 2 * wavenumber ** 3)
+
+
+def Boltz_pop_at_T(wavenumber, temp, g_level, Q_part):
+    """spect_classes.py:1866-1873: LTE population of a level"""
+    return g_level * Boltz_ratio_nodeg(wavenumber, temp) / Q_part
+
+
+def Einstein_A_to_LineStrength_nonLTE(A_coeff, wavenumber, E_lower, T_vib_lower, T_vib_upper, g_lower, g_upper, Q_part,
+                                      iso_ab=1.0):
+    """spect_classes.py:1788-1803: the line strength with the two levels populated at their own temperatures"""
+    B_21 = Einstein_A_to_B(A_coeff, wavenumber, units='cm3ergcm2')
+    B_12 = Einstein_B21_to_B12(B_21, g_lower, g_upper)
+    E_upper = E_lower + wavenumber
+    fact = g_lower / g_upper * Boltz_pop_at_T(E_upper, T_vib_upper, g_upper, Q_part) / \
+        Boltz_pop_at_T(E_lower, T_vib_lower, g_lower, Q_part)
+    pop_low = Boltz_pop_at_T(E_lower, T_vib_lower, g_lower, Q_part)
+    return iso_ab * h_cgs * wavenumber * c_cgs * pop_low * (1 - fact) * B_12 / (4 * np.pi)
+
+
+def CalcStrength_at_T(mol, iso, S_ref, w, E_low, T, T_ref=296.):
+    """spect_classes.py:1713-1733: the HITRAN intensity S_ref at T_ref continued to T (Q from CalcPartitionSum)"""
+    def fu_exp(mol, iso, E_low, w, T):
+        Q_part = CalcPartitionSum(mol, iso, temp=T)
+        return Boltz_ratio_nodeg(E_low, T) * (1 - Boltz_ratio_nodeg(w, T)) / Q_part
+    return S_ref * fu_exp(mol, iso, E_low, w, T) / fu_exp(mol, iso, E_low, w, T_ref)
+
+
+def alpha_nlte(Freq, Temp, r1, r2):
+    """spect_classes.py:1485-1488: the non-LTE factor of the absorption strength, r1 / r2 the vibrational population
+    ratios (vibtemp_to_ratio) of the lower / upper level"""
+    Gm = Boltz_ratio_nodeg(Freq, Temp)
+    return r1 * (1 - Gm * r2 / r1) / (1 - Gm)
+
+
+def BB(T, w):
+    """spect_classes.py:2080-2092: black body in nW / (cm2 cm-1), the reference's own constants"""
+    rc1 = 1.1904e-3
+    rhck = 1.4388
+    return rc1 * w ** 3 / (np.exp(w * rhck / T) - 1)
+
+
+def BB_erg(T, w):
+    """spect_classes.py:2095-2107: black body in erg / (cm2 cm-1), the reference's own constants (rc1 = 1.1904e-5 and
+    rhck = 1.4388 are not 2 h c^2 and c2: BB_erg is 0.05-0.2 % below Calc_BB_single in the infrared)"""
+    rc1 = 1.1904e-5
+    rhck = 1.4388
+    return rc1 * w ** 3 / (np.exp(w * rhck / T) - 1)
+
+
+def strengths_of(lines):
+    """The HITRAN intensities (SpectLine.Strength) of a line list, in list order: what engine.LineSet.set_strengths takes
+    for the same list's lines_to_soa."""
+    return np.array([float(l.Strength) for l in lines], dtype=np.float64)
+
+
 def ImportPartitionSumTable(mol, iso):
     """spect_classes.py:1680-1689 -> gi, T_grid, Q_grid (library TIPS-2003 tables)"""
     from .compat import fparts_mod
@@ -675,6 +735,79 @@ class SpectLine(object):
             values = [0., 0., 0.]
         self.G_coeffs = dict(zip(ctypes_, values))
         return self.G_coeffs
+
+
+    def _e_vib(self):
+        # (E_vib_lo, E_vib_up): an unlinked line has none, which the reference reads as 0 (its try / except,
+        # spect_classes.py:240-245, 273-278)
+        return (0.0 if self.E_vib_lo is None else self.E_vib_lo), (0.0 if self.E_vib_up is None else self.E_vib_up)
+
+    def CalcStrength(self, T):
+        """spect_classes.py:115-119: the HITRAN intensity at T (LTE)"""
+        return CalcStrength_at_T(self.Mol, self.Iso, self.Strength, self.Freq, self.E_lower, T)
+
+    def CalcStrength_nonLTE(self, Temp, T_vib_lower, T_vib_upper, Q_part=None):
+        """spect_classes.py:208-217"""
+        if Q_part is None:
+            Q_part = CalcPartitionSum(self.Mol, self.Iso, temp=Temp)
+        return Einstein_A_to_LineStrength_nonLTE(self.A_coeff, self.Freq, self.E_lower, T_vib_lower, T_vib_upper,
+                                                 self.g_lo, self.g_up, Q_part)
+
+    def CalcStrength_from_Einstein(self, Temp, Q_part=None, iso_ab=None, isomolec=None, T_vib_lower=None,
+                                   T_vib_upper=None):
+        """spect_classes.py:219-254 -> (S_ab, S_em): iso_ab (G_abs b(E_vib_lo, T_vib_lower) - G_ind b(E_vib_up,
+        T_vib_upper)) / Q and iso_ab G_sp b(E_vib_up, T_vib_upper) / Q (engine: line_strengths(source="einstein"))"""
+        if T_vib_lower is None:
+            T_vib_lower = Temp
+        if T_vib_upper is None:
+            T_vib_upper = Temp
+        if Q_part is None:
+            Q_part = CalcPartitionSum(self.Mol, self.Iso, temp=Temp)
+        if iso_ab is None:
+            from . import spect_base_module as sbm
+            iso_ab = sbm.find_molec_metadata(self.Mol, self.Iso)['iso_ratio']
+        G_coeffs = self.Calc_Gcoeffs(Temp, isomolec=isomolec)
+        E_vib_lo, E_vib_up = self._e_vib()
+        S_ab = (G_coeffs['absorption'] * Boltz_ratio_nodeg(E_vib_lo, T_vib_lower) -
+                G_coeffs['ind_emission'] * Boltz_ratio_nodeg(E_vib_up, T_vib_upper)) / Q_part
+        S_em = G_coeffs['sp_emission'] * Boltz_ratio_nodeg(E_vib_up, T_vib_upper) / Q_part
+        return iso_ab * S_ab, iso_ab * S_em
+
+    def CalcStrength_from_Strength(self, Temp, Q_part=None, iso_ab=None, isomolec=None, T_vib_lower=None,
+                                   T_vib_upper=None, E_vib_lo=None, E_vib_up=None):
+        """spect_classes.py:256-289 -> (S_ab, S_em) = (S(T) alpha_nlte, S(T) r_up BB_erg(T, Freq)) from the HITRAN
+        intensity (engine: line_strengths(source="hitran")).  As in the reference, S(T) takes its partition sums from
+        CalcPartitionSum (Q_part is not used) and iso_ab and isomolec are not used either."""
+        from . import spect_base_module as sbm
+        if T_vib_lower is None:
+            T_vib_lower = Temp
+        if T_vib_upper is None:
+            T_vib_upper = Temp
+        if E_vib_lo is None and E_vib_up is None:
+            E_vib_lo, E_vib_up = self._e_vib()
+        r1 = sbm.vibtemp_to_ratio(E_vib_lo, T_vib_lower, Temp)
+        r2 = sbm.vibtemp_to_ratio(E_vib_up, T_vib_upper, Temp)
+        alpha = alpha_nlte(self.Freq, Temp, r1, r2)
+        S_ab = self.CalcStrength(Temp) * alpha
+        S_em = self.CalcStrength(Temp) * r2 * BB_erg(Temp, self.Freq)
+        return S_ab, S_em
+
+    def calc_A_coeff_from_strength(self, iso_ab=None, Q_part=None, set_attr=False):
+        """spect_classes.py:291-310: the Einstein A of the HITRAN intensity at 296 K (the inverse of
+        Einstein_A_to_LineStrength_hitran); g_up must be set.  set_attr: store it as A_coeff."""
+        Temp = 296.0
+        if Q_part is None:
+            Q_part = CalcPartitionSum(self.Mol, self.Iso, temp=Temp)
+        if iso_ab is None:
+            from . import spect_base_module as sbm
+            iso_ab = sbm.find_molec_metadata(self.Mol, self.Iso)['iso_ratio']
+        B_21 = self.Strength * (4 * np.pi * Q_part) / (
+            (Boltz_ratio_nodeg(self.E_lower, Temp) - Boltz_ratio_nodeg(self.E_lower + self.Freq, Temp)) *
+            h_cgs * c_cgs * self.Freq * self.g_up * iso_ab)
+        A = Einstein_B21_to_A(B_21, self.Freq)
+        if set_attr:
+            self.A_coeff = A
+        return A
 
 
 def MakeShape(wn_arr, wn_0, lw, dw, Strength=1.0):
