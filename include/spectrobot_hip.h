@@ -49,15 +49,28 @@ int sr_abi_version(void);
 /* Device selection / query (one process per GPU: call once per rank). */
 int sr_set_device(int device);
 int sr_device_info(char *name, int name_len, int *cu_count, double *hbm_gib);
-/* Hardware queues.  The coefficient op runs on SIX HIP streams (the caller's + five of its own: table preparation, two
- * for the far-field chain, the zones kernel, a copy stream).  The ROCm runtime maps a process's streams onto
- * GPU_MAX_HW_QUEUES hardware queues (environment variable, default 4, read ONCE when HIP initialises, i.e. at the
- * process's first HIP call): with fewer queues than streams two streams share one and kernels no event orders wait for
- * each other (measured: 5.63 instead of 5.47 ms per BASELINE step with 4; 6.01 with 2).  A host application exports
- * GPU_MAX_HW_QUEUES=8 before its first HIP call (the Python package does so at import unless the caller already set it).
- * *recommended = 8; *configured = what this process runs with (the variable's value, 4 when unset).  Returns SR_OK;
- * either pointer may be NULL.  Results do not depend on the setting, only the schedule does. */
+/* Hardware queues.  The ROCm runtime maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (environment
+ * variable, default 4, read ONCE when HIP initialises, i.e. at the process's first HIP call); streams that share a
+ * queue wait for each other's kernels although no event orders them.  The coefficient op therefore runs on THREE
+ * streams: the caller's (the wings kernel, which writes the output) and two of the handle's own whose stream order is
+ * the order the phased schedule runs their kernels in anyway -- table preparation -> level-0 pass -> S2M, M2M -> M2L ->
+ * next call's preparation on one, the zones kernel on the other.  Per thread and device the library adds ONE staging
+ * stream (early host-to-device copies), so a process with one top-level lineset keeps caller + 3 <= 4 streams and its
+ * pipeline overlaps fully on the runtime's default (measured per BASELINE step, profiles/two_stream_pipeline_ab.txt:
+ * 5.16 ms with 4 queues and 5.16 with 8; the five-stream pipeline before it 5.45 with 4, 5.15 with 8).  The level-table
+ * builds and per-level sub-linesets run on the same two streams.  Every further top-level lineset used CONCURRENTLY
+ * adds two streams of its own: such a process, or one whose own code keeps several streams busy, still wants more
+ * queues -- export GPU_MAX_HW_QUEUES=8 before its first HIP call (the Python package does so at import unless the
+ * caller already set it).  *recommended = 8: that headroom, not a requirement of a single handle; *configured = what
+ * this process runs with (the variable's value, 4 when unset).  Returns SR_OK; either pointer may be NULL.  Results do
+ * not depend on the setting, only the schedule does. */
 int sr_recommended_hw_queues(int *recommended, int *configured);
+/* *live = HIP streams this library has created and not destroyed in this process, *created_total = all it ever created
+ * (every stream it makes is counted where it is made).  A handle's two pipeline streams are destroyed with the handle
+ * (sr_lineset_destroy); the staging stream belongs to the THREAD that first staged on a device, outlives every handle and
+ * is never destroyed, so *live stays >= 1 per such (thread, device) for the rest of the process, also after the thread
+ * has exited.  Needs no GPU; either pointer may be NULL.  Returns SR_OK. */
+int sr_stream_census(int *live, int *created_total);
 
 /* ------------------------------------------------------------------------ *
  * Fine-grained shims: the f2py call shapes, one reference routine each.     *

@@ -77,6 +77,7 @@ SYMBOLS = {
     "sr_set_device": (C.c_int, [C.c_int]),
     "sr_device_info": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), dp]),
     "sr_recommended_hw_queues": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sr_stream_census": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sr_humliv_bb": (C.c_int, [dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp]),
     "sr_sum_all_lines": (C.c_int, [dp, C.c_int64, dp, ip, ip, C.c_int, C.c_int]),
     "sr_bd_tips_2003": (C.c_int, [C.c_int, C.c_int, dp, dp, dp]),

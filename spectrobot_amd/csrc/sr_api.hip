@@ -47,6 +47,35 @@ int hip_fail(hipError_t e, const char *what) {
     if (e__ != 0) return hip_fail((hipError_t)e__, "kernel launch"); \
   } while (0)
 
+// Every stream the library makes or destroys goes through these two: sr_stream_census reports their counts.
+std::atomic<int> g_streams_live{0}, g_streams_total{0};
+int stream_create(hipStream_t *s) {
+  HIPCHK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+  ++g_streams_live;
+  ++g_streams_total;
+  return SR_OK;
+}
+void stream_destroy(hipStream_t &s) {
+  if (!s) return;
+  (void)hipStreamDestroy(s);
+  s = nullptr;
+  --g_streams_live;
+}
+
+// The ONE staging stream of this thread on device `dev` (Stager::push_early / begin_early): early host-to-device copies
+// and the work that depends on them alone.  Thread-local, never destroyed; it is the third of the three streams the
+// library keeps per (thread, device) beside a handle's two pipeline streams (CoefWork).
+int staging_stream(int dev, hipStream_t *out) {
+  static thread_local std::map<int, hipStream_t> streams; // one per device this thread has used
+  hipStream_t &s = streams[dev];
+  if (!s) {
+    const int rc = stream_create(&s);
+    if (rc) return rc;
+  }
+  *out = s;
+  return SR_OK;
+}
+
 // grow-only device buffer
 struct DevBuf {
   void *p = nullptr;
@@ -115,15 +144,15 @@ struct Stager {
     pending = true;
     return SR_OK;
   }
-  // The copy on a dedicated copy stream, `st` only waits for it.  Host-to-device copies of all streams
+  // The copy on the staging stream, `st` only waits for it.  Host-to-device copies of all streams
   // share the DMA queues in issue order: a small staging copy enqueued on `st` BEHIND 8 ms of kernels
   // held back the next call's layer-scalar copy (on the prep stream) and with it the pipelined
   // preparation of the next call's tables (+0.9 ms per step).  prepare() has already waited for the
   // slot's last consumers, so the copy may run at once.
   int push_early(size_t bytes, hipStream_t st) {
-    static thread_local std::map<int, hipStream_t> copy_streams; // one per device this thread has used
-    hipStream_t &copy_st = copy_streams[dev];
-    if (!copy_st) HIPCHK(hipStreamCreateWithFlags(&copy_st, hipStreamNonBlocking));
+    hipStream_t copy_st = nullptr;
+    const int rc = staging_stream(dev, &copy_st);
+    if (rc) return rc;
     if (bytes) HIPCHK(hipMemcpyAsync(d.p, h, bytes, hipMemcpyHostToDevice, copy_st));
     HIPCHK(hipEventRecord(done, copy_st));
     HIPCHK(hipStreamWaitEvent(st, done, 0));
@@ -131,13 +160,13 @@ struct Stager {
     return SR_OK;
   }
   // push_early in two halves, for work that depends on the staged data alone (the LOS column integration): it runs
-  // on the copy stream right behind the copy, i.e. as soon as the host has issued it -- on `st` it queued behind
+  // on the staging stream right behind the copy, i.e. as soon as the host has issued it -- on `st` it queued behind
   // everything the caller had submitted before (on a 1/8 shard: copy, columns kernel and two event hand-overs, ~35 us
   // of a 0.9 ms step, after the coefficient kernels instead of beside them).
   int begin_early(size_t bytes, hipStream_t *copy_stream_out) {
-    static thread_local std::map<int, hipStream_t> work_streams; // one per device this thread has used
-    hipStream_t &cs = work_streams[dev];
-    if (!cs) HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    hipStream_t cs = nullptr;
+    const int rc = staging_stream(dev, &cs);
+    if (rc) return rc;
     if (bytes) HIPCHK(hipMemcpyAsync(d.p, h, bytes, hipMemcpyHostToDevice, cs));
     *copy_stream_out = cs;
     return SR_OK;
@@ -243,23 +272,28 @@ std::atomic<size_t> g_table_budget{(size_t)48 << 30}; // bytes of FastRec + Cold
 // (level_set) SHARE their parent's -- calls on a handle and its children are serialised through ev_last_done anyway,
 // and twelve levels with their own record tables, far-field scratch, streams and events held twelve times the memory.
 struct CoefWork {
-  // [2]: with sr_set_overlap(1) the tables of call c+1 are prepared (on prep_st) while the kernels
+  // [2]: with sr_set_overlap(1) the tables of call c+1 are prepared (on far_st) while the kernels
   // of call c still read theirs
   Stager s_layers[2];
   DevBuf d_fast[2], d_cold[2], d_coef[2], d_zone, d_zone2[2], d_mom[2], d_outer_recs;
-  hipStream_t aux = nullptr;     // second stream: zones kernel beside the far-field kernel
-  hipStream_t prep_st = nullptr; // third stream: staging copy + sr_prep_kernel of the NEXT call
+  // The TWO internal streams of the pipelined schedule.  On each, stream order IS the order the phased schedule runs
+  // its kernels in anyway, so the pair (with the caller's stream) needs three hardware queues, not six:
+  //   far_st:  staging copy + prep(c) -> level-0 pass(c) -> S2M, M2M(c) -> M2L(c) [-> L2L, far-only passes] -> prep(c + 1) ..
+  //   near_st: zones(c), gated by an event behind the level-0 pass and S2M of its own call
+  // (the wings kernel, which writes the caller-visible output, is on the caller's stream).
+  // streams_of: the CoefWork whose pair this one runs on -- the private CoefWorks of a multi-channel pass (McWork::fw)
+  // borrow the handle's; the owner creates the pair on first use and is the only one that destroys it.
+  hipStream_t far_st = nullptr, near_st = nullptr;
+  CoefWork *streams_of = nullptr;
   hipEvent_t ev_prep_done[2] = {nullptr, nullptr}, ev_tables_free[2] = {nullptr, nullptr}, ev_op0 = nullptr;
-  // the far-field chain (level-0 pass, moments, upward pass, translations) of call c + 1 runs on prep_st behind its
+  // the far-field chain (level-0 pass, moments, upward pass, translations) of call c + 1 runs on far_st behind its
   // table preparation, i.e. beside the zones / wings kernels of call c (its own coefficient / moment buffers)
   hipEvent_t ev_far_done[2] = {nullptr, nullptr}, ev_zones_done[2] = {nullptr, nullptr};
-  hipStream_t chain_st = nullptr, chain2_st = nullptr; // the far-field chain (decoupled pipeline): level-0 pass | moments, translations
-  hipEvent_t ev_l0_done[2] = {nullptr, nullptr}, ev_s2m_done[2] = {nullptr, nullptr};
+  hipEvent_t ev_s2m_done[2] = {nullptr, nullptr}; // behind S2M + M2M: what releases the zones kernel (box-pair mode)
   bool free_recorded[2] = {false, false};
   int parity = 0;
   bool overlapped = false;       // last call ran that way (timing hook)
-  bool pipelined = false;        // last call prepared its tables on prep_st
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  bool pipelined = false;        // last call prepared its tables on far_st
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int n_timed = 0; // kernels timed in the last call
   bool timed = false;
@@ -275,6 +309,20 @@ struct CoefWork {
     HIPCHK(hipEventCreateWithFlags(&ev_last_done, hipEventDisableTiming));
     return SR_OK;
   }
+  int pipeline_streams(hipStream_t *far, hipStream_t *near) {
+    CoefWork &o = streams_of ? *streams_of : *this;
+    if (!o.far_st) { // (each on its own: a pair half made by a failed call is completed by the next, never handed out)
+      const int rc = stream_create(&o.far_st);
+      if (rc) return rc;
+    }
+    if (!o.near_st) {
+      const int rc = stream_create(&o.near_st);
+      if (rc) return rc;
+    }
+    *far = o.far_st;
+    *near = o.near_st;
+    return SR_OK;
+  }
   void release() {
     for (int b = 0; b < 2; ++b) {
       s_layers[b].release();
@@ -284,7 +332,6 @@ struct CoefWork {
       if (ev_tables_free[b]) (void)hipEventDestroy(ev_tables_free[b]);
       if (ev_far_done[b]) (void)hipEventDestroy(ev_far_done[b]);
       if (ev_zones_done[b]) (void)hipEventDestroy(ev_zones_done[b]);
-      if (ev_l0_done[b]) (void)hipEventDestroy(ev_l0_done[b]);
       if (ev_s2m_done[b]) (void)hipEventDestroy(ev_s2m_done[b]);
       d_zone2[b].release();
       d_coef[b].release();
@@ -294,28 +341,28 @@ struct CoefWork {
     if (ev_last_done) (void)hipEventDestroy(ev_last_done);
     d_counts.release();
     d_outer_recs.release();
-    if (prep_st) (void)hipStreamDestroy(prep_st);
-    if (chain_st) (void)hipStreamDestroy(chain_st);
-    if (chain2_st) (void)hipStreamDestroy(chain2_st);
+    stream_destroy(far_st); // (its own pair: a borrowed one, streams_of, is the owner's to destroy)
+    stream_destroy(near_st);
     d_zone.release();
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    if (aux) (void)hipStreamDestroy(aux);
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
   }
 };
 
 // Scratch of the multi-channel pass (mc_pass): record tables of the FULL list with the three channel weights, the
-// far-only coefficients of the level passes, its zones stream, and the CoefWorks the far-only passes run through (not
-// the handle's shared one: folded ops on the handle and the passes of one table build do not wait for each other's scratch).
-constexpr int kMcFarLanes = 4; // far-only level passes in flight side by side (each on its own CoefWork: tables, streams, events)
+// far-only coefficients of the level passes, and the CoefWorks the far-only passes run through (not the handle's shared
+// one: folded ops on the handle and the passes of one table build do not wait for each other's scratch).  It makes no
+// streams: the sparse batch runs on the handle's near_st, the dense passes' chains on its far_st (CoefWork::streams_of).
+// kMcFarLanes: CoefWorks the dense far-only level passes rotate through (tables, events; the handle's streams).  They
+// run one after the other on far_st, so the lanes buy no concurrency any more, only that a pass prepares its tables
+// without waiting for the one before it to finish with a shared set: two CoefWorks x two parities cover the one or two
+// dense passes of a build (it was four when each lane had streams of its own).
+constexpr int kMcFarLanes = 2;
 struct McWork {
   CoefWork fw[kMcFarLanes];
   bool fw_init = false, batch_pending = false;
   Stager s_layers, s_far, s_batch;
   DevBuf d_fast, d_cold, d_coef, d_outer_recs, d_bfast;
-  hipStream_t zst = nullptr;
   hipEvent_t ev_prep = nullptr, ev_zones = nullptr;
   hipEvent_t ev_t[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // timing: start, after the tables, after the zones kernel, before / after the wings kernel
   bool timed = false;
@@ -331,12 +378,10 @@ struct McWork {
     d_coef.release();
     d_outer_recs.release();
     d_bfast.release();
-    if (zst) (void)hipStreamDestroy(zst);
     if (ev_prep) (void)hipEventDestroy(ev_prep);
     if (ev_zones) (void)hipEventDestroy(ev_zones);
     for (auto &e : ev_t)
       if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    zst = nullptr;
     ev_prep = ev_zones = nullptr;
   }
 };
@@ -424,12 +469,20 @@ int sr_device_info(char *name, int name_len, int *cu_count, double *hbm_gib) {
 }
 
 int sr_recommended_hw_queues(int *recommended, int *configured) {
+  // 8: headroom for processes with several top-level linesets in flight (two pipeline streams each) or streams of their
+  // own.  ONE handle needs no more than the runtime's default 4: caller + far_st + near_st + the staging stream.
   if (recommended) *recommended = 8;
   if (configured) {
     const char *e = getenv("GPU_MAX_HW_QUEUES");
     const int v = e ? atoi(e) : 0;
     *configured = v > 0 ? v : 4; // the runtime's default
   }
+  return SR_OK;
+}
+
+int sr_stream_census(int *live, int *created_total) {
+  if (live) *live = g_streams_live.load();
+  if (created_total) *created_total = g_streams_total.load();
   return SR_OK;
 }
 
@@ -1032,25 +1085,28 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
   }
   const size_t hl_bytes = layer_stage_bytes(nl, npop);
   // Table set of this call and the stream its preparation runs on.  With overlap, call c + 1
-  // prepares set (c + 1) % 2 on prep_st while the kernels of call c (which the caller's stream is
+  // prepares set (c + 1) % 2 on far_st while the kernels of call c (which the caller's stream is
   // still running) read set c % 2: the HBM-write-bound prep kernel hides behind the VALU-bound ones.
   const int b = overlap ? (w.parity ^= 1) : 0;
   hipStream_t pst = st;
   // Order this call after the previous one on this handle (see ev_last_done): a no-op when both use
   // the same stream.  The next call's table preparation (pst) needs only its own table set to be free.
   if (w.last_done_recorded) HIPCHK(hipStreamWaitEvent(st, w.ev_last_done, 0));
+  hipStream_t far_st = nullptr, near_st = nullptr; // the pipeline's two streams (see CoefWork)
   if (overlap) {
-    if (!w.prep_st) {
-      HIPCHK(hipStreamCreateWithFlags(&w.prep_st, hipStreamNonBlocking));
+    int rcs = w.pipeline_streams(&far_st, &near_st);
+    if (rcs) return rcs;
+    if (!w.ev_op0) {
       HIPCHK(hipEventCreateWithFlags(&w.ev_op0, hipEventDefault));
       for (int i = 0; i < 2; ++i) {
         HIPCHK(hipEventCreateWithFlags(&w.ev_prep_done[i], hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&w.ev_tables_free[i], hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&w.ev_far_done[i], hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&w.ev_zones_done[i], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&w.ev_s2m_done[i], hipEventDisableTiming));
       }
     }
-    pst = w.prep_st;
+    pst = far_st;
   }
   const bool decoupled = overlap == 1; // the decoupled, phased pipeline (see the far-field branch below)
   Stager &SL = w.s_layers[b];
@@ -1184,11 +1240,11 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
       }
       return SR_OK;
     };
-    // Round 4: a decoupled, phased pipeline.  Between consecutive calls only the caller-visible output orders things:
+    // The decoupled, phased pipeline (round 4).  Between consecutive calls only the caller-visible output orders things:
     // the zones kernel (tables -> private sums), the far-field chain (tables -> coefficients) and the preparation of
-    // the tables touch scratch of the call's own parity and nothing of the caller's, so each runs on an internal stream
-    // of its own as soon as ITS inputs are ready; only the wings kernel (zones' sums + near region 1 + polynomials ->
-    // abs / emi) sits on the caller's stream.  Who runs beside whom is decided by what FITS beside whom
+    // the tables touch scratch of the call's own parity and nothing of the caller's, so they run on internal streams,
+    // beside the previous call's kernels; only the wings kernel (zones' sums + near region 1 + polynomials -> abs / emi)
+    // sits on the caller's stream.  Who runs beside whom is decided by what FITS beside whom
     // (tools/r03_timeline.sh, tools/kernel_resources.sh): 16 zones waves fill a CU -- 120 VGPRs each, 4 x 120 of a
     // SIMD's 512, and 16 x 10 KB = all of its LDS -- and a retiring zones wave frees exactly one such slot, which the
     // next zones wave takes unless the other kernel's wave fits it: the wings kernel (80 VGPRs), M2M / M2L (106 / 104)
@@ -1199,20 +1255,14 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
     // phases: B = [wings(c) | level-0 pass(c + 1) | S2M(c + 1)] -- short waves that share the chip fairly --, then
     // A = [zones(c + 1) | M2M, M2L(c + 1) | prep(c + 2)]; the zones kernel is GATED behind the level-0 pass and S2M of
     // its own call (it needs neither), which is what keeps it from flooding the chip before they are through.
+    // These phases come out of TWO internal streams whose own order is the phase order -- not a stream per part, ordered
+    // by events on what each reads alone: that was the layout until profiles/two_stream_pipeline_ab.txt, and its overlap
+    // held only where each of the five streams had a hardware queue of its own, not on the runtime's default of four:
+    //   far_st:  prep(c) -> level-0(c) -> S2M, M2M(c) -> M2L(c) -> prep(c + 1) -> ..   near_st: zones(c)
+    // M2L(c + 1) and prep(c + 2) follow S2M(c + 1) on far_st and so run beside zones(c + 1), which that S2M releases;
+    // the level-0 pass and S2M of a call run one after the other, both beside wings(c).  Every wait below is on an event
+    // recorded earlier in host order, so no two streams can wait for each other.
     if (decoupled) {
-      if (!w.aux) {
-        HIPCHK(hipStreamCreateWithFlags(&w.aux, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&w.ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&w.ev_join, hipEventDisableTiming));
-      }
-      if (!w.chain_st) {
-        HIPCHK(hipStreamCreateWithFlags(&w.chain_st, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&w.chain2_st, hipStreamNonBlocking));
-        for (int i = 0; i < 2; ++i) {
-          HIPCHK(hipEventCreateWithFlags(&w.ev_l0_done[i], hipEventDisableTiming));
-          HIPCHK(hipEventCreateWithFlags(&w.ev_s2m_done[i], hipEventDisableTiming));
-        }
-      }
       double *z_abs = nullptr, *z_emi = nullptr;
       if (!far_only) {
         rc = w.d_zone2[b].ensure(sizeof(double) * 2 * n_pts * nl);
@@ -1221,36 +1271,29 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
         z_emi = z_abs + n_pts * nl;
       }
       // (the buffers of parity b were last read by the wings kernel two calls ago: the preparation waited for that)
-      // far-field chain: level-0 pass on one stream, moments + upward pass on another, translations behind both
-      HIPCHK(hipStreamWaitEvent(w.chain_st, w.ev_prep_done[b], 0));
-      LAUNCHCHK(launch_farfield(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, w.chain_st));
-      HIPCHK(hipEventRecord(w.ev_l0_done[b], w.chain_st));
-      hipStream_t last = w.chain_st;
+      // far-field chain, behind the table preparation on its stream: level-0 pass, moments + upward pass, translations
+      LAUNCHCHK(launch_farfield(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, far_st));
       if (fp.m2l) {
-        HIPCHK(hipStreamWaitEvent(w.chain2_st, w.ev_prep_done[b], 0));
-        LAUNCHCHK(launch_m2l(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, w.chain2_st, 1));
-        HIPCHK(hipEventRecord(w.ev_s2m_done[b], w.chain2_st));
-        HIPCHK(hipStreamWaitEvent(w.chain2_st, w.ev_l0_done[b], 0));
-        LAUNCHCHK(launch_m2l(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, w.chain2_st, 2));
-        last = w.chain2_st;
+        LAUNCHCHK(launch_m2l(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, far_st, 1));
+        HIPCHK(hipEventRecord(w.ev_s2m_done[b], far_st));
+        LAUNCHCHK(launch_m2l(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, far_st, 2));
       }
       if (far_only) { // the downward pass: the wider levels into the level-0 coefficients, behind the chain on its stream
         const double *l2l_tab = nullptr;
         rc = l2l_table_dev(&l2l_tab);
         if (rc) return rc;
-        LAUNCHCHK(launch_l2l(fp.coef, nl, fp, l2l_tab, last));
+        LAUNCHCHK(launch_l2l(fp.coef, nl, fp, l2l_tab, far_st));
       }
-      HIPCHK(hipEventRecord(w.ev_far_done[b], last));
+      HIPCHK(hipEventRecord(w.ev_far_done[b], far_st));
       if (far_only) { // the coefficients are the result: the caller's stream sees them complete
         HIPCHK(hipStreamWaitEvent(st, w.ev_far_done[b], 0));
       } else {
-      // zones: needs the tables only; gated behind the kernels that cannot run beside it
-      HIPCHK(hipStreamWaitEvent(w.aux, w.ev_prep_done[b], 0));
-      HIPCHK(hipStreamWaitEvent(w.aux, w.ev_l0_done[b], 0));
-      if (fp.m2l) HIPCHK(hipStreamWaitEvent(w.aux, w.ev_s2m_done[b], 0));
+      // zones: needs the tables only; gated behind the kernels that cannot run beside it: S2M (on far_st the tables and
+      // the level-0 pass precede it), or, without box pairs, the level-0 pass, which is then the whole chain
+      HIPCHK(hipStreamWaitEvent(near_st, fp.m2l ? w.ev_s2m_done[b] : w.ev_far_done[b], 0));
       LAUNCHCHK(launch_near(2, 0, d_fast.as<FastRec>(), d_cold.as<ColdRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo,
-                            (int)g_hi, ls->gp, fp, z_abs, z_emi, d_cnt, w.aux));
-      HIPCHK(hipEventRecord(w.ev_zones_done[b], w.aux));
+                            (int)g_hi, ls->gp, fp, z_abs, z_emi, d_cnt, near_st));
+      HIPCHK(hipEventRecord(w.ev_zones_done[b], near_st));
       HIPCHK(hipStreamWaitEvent(st, w.ev_far_done[b], 0));
       if (timing) HIPCHK(hipEventRecord(w.ev[2], st));
       HIPCHK(hipStreamWaitEvent(st, w.ev_zones_done[b], 0));
@@ -1295,7 +1338,7 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
     rc = add_outer(); // after the timing events: not part of the per-kernel times
     if (rc) return rc;
   }
-  // a serial call reads table set 0 too: a later pipelined call, which prepares its set on prep_st without waiting for
+  // a serial call reads table set 0 too: a later pipelined call, which prepares its set on far_st without waiting for
   // the caller's stream, must find the event behind THIS call's kernels
   if (w.ev_tables_free[b]) {
     HIPCHK(hipEventRecord(w.ev_tables_free[b], st));
@@ -1402,8 +1445,7 @@ static int mc_pass(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
     sr_lineset *ls; const std::vector<double> &all;
     ~Restore() { ls->bounds_temps = all; }
   } restore{ls, bounds_all};
-  if (!m.zst) {
-    HIPCHK(hipStreamCreateWithFlags(&m.zst, hipStreamNonBlocking));
+  if (!m.ev_prep) {
     HIPCHK(hipEventCreateWithFlags(&m.ev_prep, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&m.ev_zones, hipEventDisableTiming));
     for (auto &e : m.ev_t) HIPCHK(hipEventCreate(&e));
@@ -1468,14 +1510,16 @@ static int mc_pass(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
       rc = m.s_far.prepare(sizeof(McFarPass) * (size_t)n_far);
       if (rc) return rc;
       McFarPass *far = m.s_far.host<McFarPass>();
-      // The passes are independent of each other: kMcFarLanes of them in flight side by side, each through a CoefWork
-      // of its own (tables, streams, events) instead of the handle's shared one -- one after the other on one chain
-      // stream the eleven sparse passes (0.33 ms each, latency-bound) and the dense ground-state pass were 7.7 ms, longer
-      // than the zones kernel they run beside.  Largest sub-lineset first (its chain is the longest).
+      // The passes are independent of each other.  The dense ones (one or two per build) go one after the other on the
+      // handle's far_st, each through a CoefWork of its own (tables, events) instead of the handle's shared one, so that
+      // none waits for another's scratch; the sparse ones in one batch beside them (below) -- one after the other on one
+      // chain stream the eleven sparse passes (0.33 ms each, latency-bound) and the dense ground-state pass were 7.7 ms,
+      // longer than the zones kernel they run beside.  Largest sub-lineset first (its chain is the longest).
       if (!m.fw_init) {
         for (auto &fwk : m.fw) {
           rc = fwk.init();
           if (rc) return rc;
+          fwk.streams_of = &w; // the handle's two streams, not a set each
         }
         m.fw_init = true;
       }
@@ -1493,7 +1537,7 @@ static int mc_pass(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
       };
       // SPARSE sub-linesets (coef_op's rule: far-field mode 3, fewer than 0.35 lines per grid point -- per-line expansions
       // at every level, sr_farfield_rows_kernel): ALL of them in one batch of three launches -- tables, expansions, downward
-      // pass -- on the zones stream, beside the dense passes' chains.  One coefficient op each, they were eleven launches
+      // pass -- on the handle's near_st, beside the dense passes' chains.  One coefficient op each, they were eleven launches
       // of 0.3 ms, latency-bound, each behind ~0.3 ms of host calls: 6 ms of a 13 ms build (gpurun_out/r06/tl_v4.txt).
       // They share this pass's layer stage: their own would hold the same numbers (margins of the parent).
       std::vector<int> dense;
@@ -1536,7 +1580,12 @@ static int mc_pass(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
           if (rc) return rc;
           for (int i = 0; i < n_items; ++i) items[i].fast = m.d_bfast.as<FastRec>() + rec_off[(size_t)i];
           // (serial schedule, sr_set_overlap(0): everything on the caller's stream, one kernel after the other)
-          hipStream_t bst = g_overlap.load() != 0 ? m.zst : st;
+          hipStream_t bst = st;
+          if (g_overlap.load() != 0) { // beside the dense passes' chains (far_st): the handle's near_st
+            hipStream_t fst = nullptr;
+            rc = w.pipeline_streams(&fst, &bst);
+            if (rc) return rc;
+          }
           if (bst != st) HIPCHK(hipStreamWaitEvent(bst, m.ev_prep, 0));
           rc = m.s_batch.push(sizeof(FarBatchItem) * (size_t)n_items, bst);
           if (rc) return rc;
