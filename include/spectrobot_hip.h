@@ -495,6 +495,31 @@ int sr_limb_rays_jacobians_dev(const double *abs_c, const double *emi_c, const d
                                int n_jac_rows, int n_par, const int32_t *par_gas, const double *par_w, double *rad,
                                double *jac_layer, double *jac_par, void *stream);
 
+/* Radiances and their Jacobian with respect to LEVEL parameters of one level-factored gas: gas `gas` of the batch has
+ * abs[r] = sum_L pop[r][L] A_L[row[r]], emi[r] = sum_L pop[r][L] E_L[row[r]] on every coefficient row r (the combine
+ * of sr_glevel_combine_dev on the pair tables `tab` of sr_glevel_pairs_dev, row[r] = coef_row[r]), and parameter p
+ * moves the population of level par_level[p] on row r by d pop[r][par_level[p]] / d x_p = par_c[p][r].  Per segment s
+ * on row r with column u of that gas, for every parameter with par_c[p][r] != 0,
+ *   dtau = u par_c[p][r] A_lev[row[r]],   dE = u par_c[p][r] E_lev[row[r]],
+ *   J_p <- J_p t + (-I_prev t dtau + dE f + E f' dtau)            (solo_absorption: the two source terms drop)
+ * -- the recursion of sr_limb_rays_jac_layer_dev with dabs / demi read from the tables, so no derivative tables and no
+ * per-row Jacobian are written.  Vibrational temperatures, Tvib_L[r] = Tvib0_L[r] + sum_p w[p][r] x_p:
+ *   par_c[p][r] = w[p][r] pop[r][L] c2 E_L / Tvib_L[r]^2   (exact: the coefficients are linear in the populations,
+ * Q(T) does not depend on Tvib); par_c = w differentiates with respect to the populations themselves.
+ * abs_c / emi_c: DEVICE [n_gas][n_layers][n_pts], the combined coefficients of every gas (n_layers = coefficient
+ * rows); tab: DEVICE [n_levels][2][n_tab_rows][n_pts]; coef_row: HOST [n_layers], each in [0, n_tab_rows); par_level:
+ * HOST [n_par], each in [0, n_levels); par_c: HOST [n_par][n_layers]; rad: DEVICE [n_rays][n_pts] or NULL; jac: DEVICE
+ * [n_rays][n_par][n_pts], every element written (a parameter a ray never touches: zeros).  los_order, solo_absorption
+ * and init_mode 0 / 2 as the other ray-batch calls; init_mode 1 is refused (SR_ERR_ARG).  All arguments are checked
+ * before the first copy or launch: a refused call leaves rad and jac untouched.
+ * The reference has no counterpart (it has no derivative code at all): the build's definition, checked
+ * against the composition sr_glevel_combine_dev + sr_limb_rays_jacobians_dev per level and against central differences
+ * of the whole forward chain in Tvib (tests/test_gpu_tvib_jacobian.py). */
+int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                               const sr_los_desc *los, int gas, const double *tab, int n_levels, int n_tab_rows,
+                               const int32_t *coef_row, int n_par, const int32_t *par_level, const double *par_c,
+                               double *rad, double *jac, void *stream);
+
 /* Radiances and their Jacobian with respect to n_par retrieval parameters on which the absorber
  * columns depend linearly, col_s = sum_p dcol_dpar[s][p] * x_p (VMR profile parameters of the
  * reference's RetParam / LinearProfile classes, spect_main_module.py:319-375; the reference's own

@@ -3297,6 +3297,77 @@ int sr_limb_rays_jac_layer_dev(const double *abs_c, const double *emi_c, const d
   return D.slot->mark(st);
 }
 
+int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                               const sr_los_desc *los, int gas, const double *tab, int n_levels, int n_tab_rows,
+                               const int32_t *coef_row, int n_par, const int32_t *par_level, const double *par_c,
+                               double *rad, double *jac, void *stream) {
+  // everything is checked here, before the first copy or launch (the LOS too: stage_los would only find out after this
+  // call's own staging)
+  if (!abs_c || !emi_c || !tab || !coef_row || !par_level || !par_c || !jac) return SR_ERR_ARG;
+  if (n_layers <= 0 || n_pts <= 0 || n_levels <= 0 || n_tab_rows <= 0 || n_par < 1) return SR_ERR_ARG;
+  if (n_pts > 2000000) return SR_ERR_LIMIT;
+  int n_seg = 0, n_pt = 0;
+  int rc = check_los(los, n_layers, &n_seg, &n_pt);
+  if (rc) return rc;
+  if (gas < 0 || gas >= los->n_gas) return SR_ERR_ARG;
+  if (los->init_mode == 1) {
+    g_err = "sr_limb_rays_jac_level_dev: init_mode 1 (intensity read from a buffer) is not supported, use 0 or 2";
+    return SR_ERR_ARG;
+  }
+  for (int r = 0; r < n_layers; ++r)
+    if (coef_row[r] < 0 || coef_row[r] >= n_tab_rows) return SR_ERR_ARG; // would read out of the tables
+  for (int p = 0; p < n_par; ++p)
+    if (par_level[p] < 0 || par_level[p] >= n_levels) return SR_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // parameters in level order (stable), NP per block: a block then touches few levels, and a row's entries come in
+  // level order without a sort of their own
+  const int np = level_jac_np(n_par), n_blocks = (n_par + np - 1) / np;
+  std::vector<int> order(n_par);
+  for (int p = 0; p < n_par; ++p) order[p] = p;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return par_level[a] < par_level[b]; });
+  std::vector<int> ent_off((size_t)n_blocks * (n_layers + 1)), slot_par((size_t)n_blocks * np, -1);
+  std::vector<LevelEnt> ent;
+  for (int b = 0; b < n_blocks; ++b) {
+    const int i0 = b * np, i1 = std::min(n_par, i0 + np);
+    for (int i = i0; i < i1; ++i) slot_par[i] = order[i];
+    for (int r = 0; r < n_layers; ++r) {
+      ent_off[(size_t)b * (n_layers + 1) + r] = (int)ent.size();
+      for (int i = i0; i < i1; ++i) {
+        const double c = par_c[(size_t)order[i] * n_layers + r];
+        if (c != 0.0) ent.push_back(LevelEnt{i - i0, par_level[order[i]], c});
+      }
+    }
+    ent_off[(size_t)b * (n_layers + 1) + n_layers] = (int)ent.size();
+  }
+  static thread_local Stager s_ring[4];
+  static thread_local unsigned s_next = 0;
+  Stager &sg = s_ring[s_next++ & 3];
+  auto al = [](size_t v) { return (v + 15) / 16 * 16; };
+  const size_t b_ent = sizeof(LevelEnt) * ent.size(), o_row = al(b_ent);
+  const size_t o_off = al(o_row + sizeof(int) * (size_t)n_layers), o_slot = al(o_off + sizeof(int) * ent_off.size());
+  const size_t total = al(o_slot + sizeof(int) * slot_par.size());
+  rc = sg.prepare(total);
+  if (rc) return rc;
+  char *h = sg.host<char>();
+  if (b_ent) std::memcpy(h, ent.data(), b_ent);
+  std::memcpy(h + o_row, coef_row, sizeof(int) * (size_t)n_layers);
+  std::memcpy(h + o_off, ent_off.data(), sizeof(int) * ent_off.size());
+  std::memcpy(h + o_slot, slot_par.data(), sizeof(int) * slot_par.size());
+  rc = sg.push_early(total, st);
+  if (rc) return rc;
+  const char *d = sg.d.as<char>();
+  LosDev D;
+  rc = stage_los(los, n_layers, 0, nullptr, nullptr, st, &D);
+  if (rc) return rc;
+  LAUNCHCHK(launch_limb_jac_level(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col,
+                                  limb_opts(los, D.n_seg), gas, tab, n_tab_rows, reinterpret_cast<const int *>(d + o_row),
+                                  n_blocks, reinterpret_cast<const int *>(d + o_off), reinterpret_cast<const LevelEnt *>(d),
+                                  reinterpret_cast<const int *>(d + o_slot), n_par, rad, jac, st));
+  rc = sg.mark(st);
+  if (rc) return rc;
+  return D.slot->mark(st);
+}
+
 // ------------------------------------------------------------------------
 int sr_lut_interp_dev(const double *g_tab, int n_pt, int64_t n_pts, int n_steps, const int32_t *idx4,
                       const double *wgt4, const double *pop, int combine, double *out_a, double *out_e,

@@ -3014,7 +3014,8 @@ __global__ __launch_bounds__(256) void sr_radiance_jac_layer_kernel(
 //                           solo_absorption / initial_intensity (Planck) (radtran_3D_ch4.py:297-315)
 //   sr_limb_jac_kernel      + derivatives w.r.t. VMR-profile parameters (columns linear in them)
 //   sr_limb_jac_layer_kernel  + derivatives w.r.t. one scalar per layer acting through the coefficients
-//   (both: forward sensitivities, NP parameters per thread; many parameters / layers: sr_limb_adjoint_kernel below)
+//   sr_limb_jac_level_kernel  + derivatives w.r.t. level populations / vibrational temperatures of a level-factored gas
+//   (all three: forward sensitivities, NP parameters per thread; many parameters / layers: sr_limb_adjoint_kernel below)
 // Per segment s of a ray, layer k = seg_layer[s], columns u_g = col[g][s]:
 //   tau = sum_g abs_g[k] u_g,  E = sum_g emi_g[k] u_g,  t = e^-tau,  f = (1 - t)/tau
 //   I <- I t + E f          (E f dropped with solo_absorption)
@@ -3311,6 +3312,97 @@ __global__ __launch_bounds__(256) void sr_limb_jac_layer_kernel(
 #pragma unroll
   for (int q = 0; q < NP; ++q)
     if (p0 + q < n_layers) jac[((size_t)ray * n_layers + p0 + q) * n_pts + j] = J[q];
+}
+
+// Derivatives w.r.t. LEVEL parameters of one level-factored gas (sr_limb_rays_jac_level_dev): the gas's coefficients
+// are abs[r] = sum_L pop[r][L] A_L[row[r]], emi[r] likewise with E_L (the pair tables of sr_glevel_pairs_dev), and
+// parameter p moves the population of level lev[p] on coefficient row r by c[p][r].  The per-layer recursion above
+// with dabs / demi replaced by table spectra times a host-side coefficient:
+//   dtau_L = u A_L[row[r]],  dE_L = u E_L[row[r]],  d_L = -I t dtau_L + dE_L f + E f' dtau_L   (once per level touched)
+//   J_p <- J_p t + c[p][r] d_lev[p]
+// NP accumulators per thread, blocks of NP parameters on blockIdx.z; the host sorts the parameters by level and lists,
+// per (parameter block, coefficient row), the entries (slot, level, c) with c != 0 in level order (LevelEnt): a block
+// works on one ray, so the list is wave-uniform -- scalar loads, scalar branches -- and a segment none of the block's
+// parameters touches costs NP multiplications.  Rays and point blocks by limb_block(): all rays of a point block on
+// one XCD, so that the table rows they share are read from HBM once.  The coefficients of the next segment are
+// loaded while the current one is worked on (a ray's segments are a dependent chain).
+template <int NG, int NP>
+__global__ __launch_bounds__(256) void sr_limb_jac_level_kernel(
+    const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
+    const int *__restrict__ seg_off, const int *__restrict__ seg_layer, const double *__restrict__ col, LimbOpts o,
+    int n_rays, int gas, const double *__restrict__ tab, int n_tab_rows, const int *__restrict__ coef_row,
+    const int *__restrict__ ent_off, const LevelEnt *__restrict__ ent, const int *__restrict__ slot_par, int n_par,
+    double *__restrict__ rad, double *__restrict__ jac) {
+  int pb, ray;
+  if (!limb_block((n_pts + 255) / 256, n_rays, pb, ray)) return;
+  const int j = pb * 256 + threadIdx.x;
+  if (j >= n_pts) return;
+  double I = limb_initial(o, jac, 0, j), J[NP]; // init_mode 1 is refused by the host for this kernel
+#pragma unroll
+  for (int q = 0; q < NP; ++q) J[q] = 0.0;
+  const int *eo = ent_off + (size_t)blockIdx.z * (n_layers + 1);
+  const int s0 = seg_off[ray], s1 = seg_off[ray + 1];
+  const size_t gstride = (size_t)n_layers * n_pts, plane = (size_t)n_tab_rows * n_pts;
+  double an[NG], en[NG];
+  if (s0 < s1) {
+    const size_t ofs = (size_t)seg_layer[s0] * n_pts + j;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      an[g] = abs_c[g * gstride + ofs];
+      en[g] = emi_c[g * gstride + ofs];
+    }
+  }
+  for (int s = s0; s < s1; ++s) {
+    const int r = seg_layer[s];
+    double tau = 0.0, E = 0.0, ug = 0.0;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const double u = col[(size_t)g * o.n_seg_total + s];
+      tau = g == 0 ? an[g] * u : tau + an[g] * u;
+      E = g == 0 ? en[g] * u : E + en[g] * u;
+      ug = g == gas ? u : ug;
+    }
+    {
+      const size_t ofs = (size_t)seg_layer[min(s + 1, s1 - 1)] * n_pts + j;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        an[g] = abs_c[g * gstride + ofs];
+        en[g] = emi_c[g * gstride + ofs];
+      }
+    }
+    const Atten A = attenuation(tau);
+    const double t = A.t, em1 = A.em1, f = A.f;
+    const bool thin = A.thin;
+    const double src = o.solo_absorption ? 0.0 : E * f;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) J[q] *= t;
+    const int e0 = eo[r], e1 = eo[r + 1];
+    if (e0 < e1) {
+      const double fp = thin ? -0.5 : (tau * t - em1) * (A.rtau * A.rtau);
+      const double *tr = tab + (size_t)coef_row[r] * n_pts + j;
+      int lev = -1;
+      double d = 0.0;
+      for (int i = e0; i < e1; ++i) {
+        const int slot = ent[i].slot, lv = ent[i].level;
+        if (lv != lev) { // (entries in level order: two loads and one d per distinct level)
+          lev = lv;
+          const double *tl = tr + (size_t)lv * 2 * plane;
+          const double dtau = ug * tl[0], dE = ug * tl[plane];
+          d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
+        }
+        const double v = ent[i].c * d;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) J[q] += q == slot ? v : 0.0;
+      }
+    }
+    I = I * t + src;
+  }
+  if (blockIdx.z == 0 && rad) rad[(size_t)ray * n_pts + j] = I;
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    const int p = slot_par[blockIdx.z * NP + q];
+    if (p >= 0) jac[((size_t)ray * n_par + p) * n_pts + j] = J[q];
+  }
 }
 
 // ------------------------------------------------------------------------
@@ -4490,6 +4582,24 @@ int launch_limb_jac_layer(int forward, const double *abs_c, const double *emi_c,
     SR_BY_NGAS(o.n_gas, SR_L(1, 16), SR_L(2, 16), SR_L(3, 16), SR_L(4, 16))
   } else {
     SR_BY_NGAS(o.n_gas, SR_L(1, 4), SR_L(2, 4), SR_L(3, 4), SR_L(4, 4))
+  }
+#undef SR_L
+  return (int)hipGetLastError();
+}
+
+int launch_limb_jac_level(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
+                          const int *seg_layer, const double *col, const LimbOpts &o, int gas, const double *tab,
+                          int n_tab_rows, const int *coef_row, int n_blocks, const int *ent_off, const LevelEnt *ent,
+                          const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st) {
+  if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0) return 0;
+  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
+#define SR_L(NG, NP) hipLaunchKernelGGL((sr_limb_jac_level_kernel<NG, NP>), grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, \
+                                        seg_off, seg_layer, col, o, n_rays, gas, tab, n_tab_rows, coef_row, ent_off, ent,       \
+                                        slot_par, n_par, rad, jac)
+  if (level_jac_np(n_par) == kLevelJacNPLarge) {
+    SR_BY_NGAS(o.n_gas, SR_L(1, kLevelJacNPLarge), SR_L(2, kLevelJacNPLarge), SR_L(3, kLevelJacNPLarge), SR_L(4, kLevelJacNPLarge))
+  } else {
+    SR_BY_NGAS(o.n_gas, SR_L(1, kLevelJacNPSmall), SR_L(2, kLevelJacNPSmall), SR_L(3, kLevelJacNPSmall), SR_L(4, kLevelJacNPSmall))
   }
 #undef SR_L
   return (int)hipGetLastError();

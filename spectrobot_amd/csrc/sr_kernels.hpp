@@ -238,6 +238,19 @@ int launch_limb_jac(const double *abs_c, const double *emi_c, int n_pts, int n_l
 int launch_limb_jac_layer(int forward, const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
                           int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
                           const LimbOpts &o, double *jac, hipStream_t st);
+// Level-parameter Jacobians of one level-factored gas (sr_limb_jac_level_kernel): blocks of level_jac_np(n_par)
+// parameters; ent_off [n_blocks][n_layers + 1] into ent, the entries of every (parameter block, coefficient row) with a
+// non-zero coefficient, in level order; slot_par [n_blocks][NP] = the parameter an accumulator belongs to, or -1.
+struct __attribute__((aligned(16))) LevelEnt {
+  int slot, level; // accumulator of the block, level of the pair tables
+  double c;        // d pop[row][level] / d x_p
+};
+constexpr int kLevelJacNPSmall = 8, kLevelJacNPLarge = 16;
+inline int level_jac_np(int n_par) { return n_par > kLevelJacNPSmall ? kLevelJacNPLarge : kLevelJacNPSmall; }
+int launch_limb_jac_level(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
+                          const int *seg_layer, const double *col, const LimbOpts &o, int gas, const double *tab,
+                          int n_tab_rows, const int *coef_row, int n_blocks, const int *ent_off, const LevelEnt *ent,
+                          const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st);
 // One pass per ray for radiances, per-layer and column-parameter Jacobians (sr_limb_adjoint_kernel)
 struct SegProg;
 constexpr int kAdjPlanInts = 4 + 2 * 4; // ints per segment of the host plan: layer, flags, n_ent, jrow, ent_p[4], ent_gf[4]

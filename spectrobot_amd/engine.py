@@ -321,6 +321,23 @@ class LineSet(object):
         dpop = pop * (boltz_dT - (dq / Q)[:, None])
         return np.ascontiguousarray(pop), np.ascontiguousarray(dpop)
 
+    def level_populations_dtvib(self, temps, tvib, q_part=None):
+        """d pop_L / d Tvib_L [n_steps, n_levels] = pop_L c2 E_L / Tvib_L^2 (spect_classes.level_populations_dtvib) with
+        Q(T) supplied the way level_populations does.  ValueError for an iso-molecule without levels and in LTE
+        (tvib None): the vibrational temperature is then not a variable."""
+        from . import spect_classes as spcl
+        if self.level_energies.size == 0:
+            raise ValueError("the iso-molecule has no levels: no vibrational temperature to differentiate by")
+        if tvib is None:
+            raise ValueError("tvib is None (LTE): the vibrational temperature is not a variable")
+        T = np.ascontiguousarray(temps, dtype=np.float64)
+        if q_part is not None:
+            Q = np.asarray(q_part, float)
+        else:
+            Tu, inv = np.unique(T, return_inverse=True)
+            Q = np.atleast_1d(spcl.CalcPartitionSum(self.mol, self.iso, Tu))[inv]
+        return spcl.level_populations_dtvib(self.level_energies, tvib, Q)
+
     def abscoeff_level(self, temps, press, level, tvib=None, q_part=None, g_lo=0, g_hi=None):
         """One level's share of abs / emi (track_levels, spect_main_module.py:2083-2087)."""
         g_hi = self.n_grid if g_hi is None else int(g_hi)
@@ -487,6 +504,41 @@ class LevelFactored(object):
             raise ValueError("LevelFactored was built without dT: no temperature derivative")
         pop, dpop = self.ls.level_populations(T, tvib=tvib, q_part=q_part, derivative=True)
         return glevel_combine(self.tab, step_row, pop, tab_dT=self.tab_dT, dpop=dpop, dT=self.dT, out=out)
+
+    def tvib_jacobian(self, coeffs, los, step_row, tvib, par_level, par_w, gas=0, q_part=None, grid=None, want_rad=True):
+        """(rad | None, jac [n_rays, n_par, n_pts]): d rad / d x_p for vibrational-temperature parameters,
+        Tvib_L[r] = tvib[L, r] + sum_p par_w[p, r] x_p with L = par_level[p], on the coefficient rows r of `coeffs` --
+        what steps(step_row, tvib=tvib) returned (one gas) or the stack of all gases with this one at index `gas`.
+        par_w [n_par, n_steps] (level_node_weights on the rows' altitudes).  Exact and from the resident tables: the
+        coefficients are linear in the populations, d pop_L / d Tvib_L = pop_L c2 E_L / Tvib_L^2
+        (LineSet.level_populations_dtvib), Q(T) does not move (limb_rays_level_jacobian).  Honours the object's
+        spectral shard (a Planck initial intensity is taken on grid[g_lo:])."""
+        step_row = np.ascontiguousarray(step_row, dtype=np.int32)
+        par_level = np.ascontiguousarray(par_level, dtype=np.int32).reshape(-1)
+        par_w = np.asarray(par_w, dtype=np.float64)
+        if par_w.shape != (par_level.size, step_row.size):
+            raise ValueError("par_w must be [n_par, n_steps]")
+        n_lev = self.ls.level_energies.size
+        if par_level.size and (par_level.min() < 0 or par_level.max() >= max(n_lev, 1)):
+            raise ValueError("par_level out of range")
+        dpop = self.ls.level_populations_dtvib(self.temps[step_row], tvib, q_part=q_part)      # [n_steps, n_levels]
+        par_c = par_w * dpop.T[par_level]
+        return limb_rays_level_jacobian(coeffs, los, self.tab, step_row, par_level, par_c, gas=gas, grid=grid,
+                                        g_lo=int(self._shard[0]), want_rad=want_rad)
+
+
+def level_node_weights(nodes, alt):
+    """par_w [n_nodes, n_rows] of one level's vibrational-temperature profile on the coefficient rows: the triangular
+    masks of LinearProfile_1D_new (spect_main_module.alt_triangle: 1 at the node, linear to 0 at its neighbours, the
+    first / last node continued with 1 below / above) at the rows' altitudes `alt` -- a profile that is linear between
+    the nodes `nodes` (increasing, at least two).  Inside the node range the weights of a row sum to one."""
+    from . import spect_main_module as smm
+    nodes = [float(v) for v in nodes]
+    if len(nodes) < 2 or any(b <= a for a, b in zip(nodes[:-1], nodes[1:])):
+        raise ValueError("at least two increasing node altitudes")
+    prof = smm.LinearProfile_1D_new("tvib", np.asarray(alt, dtype=float).reshape(-1), nodes, np.zeros(len(nodes)),
+                                    np.ones(len(nodes)))
+    return np.ascontiguousarray(prof.mask_matrix())
 
 
 def set_timing(on):
@@ -972,6 +1024,37 @@ def limb_rays_jacobians(coeffs, los, dcoeffs=None, par_gas=None, par_w=None, gri
                                          0 if sjr is None else int(n_jac_rows), n_par, pg, pw, ptr(rad), ptr(jl), ptr(jp),
                                          _stream_ptr()), "sr_limb_rays_jacobians_dev")
     return rad, jl, jp
+
+
+def limb_rays_level_jacobian(coeffs, los, tab, coef_row, par_level, par_c, gas=0, grid=None, g_lo=0, want_rad=True):
+    """(rad | None, jac [n_rays, n_par, n_pts]): radiances and their derivatives with respect to level parameters of
+    the level-factored gas `gas` (sr_limb_rays_jac_level_dev).  coeffs as limb_rays; tab: that gas's pair tables (CUDA
+    [n_levels, 2, n_tab_rows, n_pts], LineSet.glevel_pairs); coef_row [n_layers]: the table row of every coefficient
+    row; parameter p moves the population of level par_level[p] on coefficient row r by par_c[p, r].  Vibrational
+    temperatures: LevelFactored.tvib_jacobian."""
+    a, e = _gas_stack(coeffs)
+    n_gas, n_layers, n_pts = a.shape
+    if n_gas != los.n_gas:
+        raise ValueError("%d coefficient sets for %d gases" % (n_gas, los.n_gas))
+    assert tab.is_cuda and tab.dtype == torch.float64 and tab.is_contiguous() and tab.dim() == 4 and tab.shape[1] == 2
+    if tab.shape[3] != n_pts:
+        raise ValueError("tables of %d points for coefficients of %d" % (tab.shape[3], n_pts))
+    coef_row, cr = _i(coef_row)
+    par_level, pl = _i(par_level)
+    par_c, pc = _d(par_c)
+    n_par = par_level.size
+    if coef_row.shape != (n_layers,):
+        raise ValueError("coef_row must be [n_layers]")
+    if par_c.shape != (n_par, n_layers):
+        raise ValueError("par_c must be [n_par, n_layers]")
+    rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
+    jac = torch.empty((los.n_rays, n_par, n_pts), dtype=torch.float64, device="cuda")
+    d = los.desc(grid, g_lo)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    check(lib.sr_limb_rays_jac_level_dev(ptr(a), ptr(e), n_layers, n_pts, C.byref(d), int(gas), ptr(tab), int(tab.shape[0]),
+                                         int(tab.shape[2]), cr, n_par, pl, pc, ptr(rad), ptr(jac), _stream_ptr()),
+          "sr_limb_rays_jac_level_dev")
+    return rad, jac
 
 
 def radiance_jacobian(abs_c, emi_c, seg_off, seg_layer, seg_col, dcol_dpar):

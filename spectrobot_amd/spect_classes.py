@@ -72,6 +72,24 @@ def Boltz_ratio_nodeg(wavenumber, temp):
     return np.exp(-c2 * wavenumber / temp)
 
 
+def level_populations_dtvib(level_energies, tvib, q):
+    """d pop_L / d Tvib_L [n_steps, n_levels] of the non-LTE populations pop_L = exp(-c2 E_L / Tvib_L) / Q(T)
+    (spect_main_module.py:2049-2073): pop_L c2 E_L / Tvib_L^2, exact -- Q depends on the kinetic temperature alone --
+    and zero for a level of energy 0.  level_energies [n_levels] (cm-1), tvib [n_levels, n_steps] (K), q [n_steps].
+    The reference has no counterpart (no derivative code at all)."""
+    E = np.asarray(level_energies, dtype=float).reshape(-1)
+    if E.size == 0:
+        raise ValueError("the iso-molecule has no levels: no vibrational temperature to differentiate by")
+    if tvib is None:
+        raise ValueError("tvib is None (LTE): the vibrational temperature is not a variable")
+    tv = np.asarray(tvib, dtype=float)
+    q = np.asarray(q, dtype=float).reshape(-1)
+    if tv.shape != (E.size, q.size):
+        raise ValueError("tvib must be [n_levels, n_steps]")
+    pop = Boltz_ratio_nodeg(E[:, None], tv) / q[None, :]
+    return np.ascontiguousarray((pop * (c2 * E[:, None] / tv ** 2)).T)
+
+
 def Calc_BB_single(nu, T):
     """spect_classes.py:1895-1903, units erg s-1 cm-2 sr-1 (cm-1)-1"""
     return 2 * h_cgs * c_cgs ** 2 * nu ** 3 / (np.exp(c2 * nu / T) - 1)
