@@ -368,8 +368,9 @@ typedef struct {
 int sr_los_columns(const sr_los_desc *los, double *col_out);
 
 /* Radiances of the ray batch.  abs_c / emi_c: DEVICE [n_gas][n_layers][n_pts]; rad: DEVICE [n_rays][n_pts].
- * Per-level partial radiances (single_rad[(gas, iso, lev)], spect_main_module.py:2883-2887): pass the level's
- * emission share (sr_abscoeff_level_dev) as emi_c with the total abs_c. */
+ * Per-gas and per-level partial radiances (single_rads[(gas, iso)], single_rads[(gas, iso, lev)],
+ * spect_main_module.py:2883-2887, 3287): sr_limb_rays_parts_dev below, all of them in one pass.  (An emission share
+ * given as an explicit spectrum: pass it as emi_c with the total abs_c.) */
 int sr_limb_rays_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
                      double *rad, void *stream);
 
@@ -519,6 +520,32 @@ int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_l
                                const sr_los_desc *los, int gas, const double *tab, int n_levels, int n_tab_rows,
                                const int32_t *coef_row, int n_par, const int32_t *par_level, const double *par_c,
                                double *rad, double *jac, void *stream);
+
+/* The radiance budget of the ray batch: which gas, and which level of the level-factored gas `gas`, emits the radiance
+ * that arrives.  The recursion is linear in the emission: with tau = sum_g abs_g[r] u_g, t = exp(-tau), f = (1 - t) / tau
+ * of a segment on coefficient row r,
+ *   I = I0 T(all) + sum_s E_s f_s T(after s),   E_s = sum_g emi_g[r_s] u_{g,s},
+ * and PART k, a share e_k[r] of the emission of one gas g(k), arrives as the same recursion with that share as the only
+ * source and the TOTAL absorption:  C_k <- C_k t + e_k[r] u_{g(k)} f  (from 0);  the background  B <- B t  (from I0).
+ *   part_level[k] = -1: gas part, e_k[r] = emi_c[part_gas[k]][r] (the whole emission of that gas);
+ *   part_level[k] >= 0: level part of gas `gas` (part_gas[k] must equal gas),
+ *                       e_k[r] = part_c[k][r] * E_lev[coef_row[r]], E_L = tab[L][1] of sr_glevel_pairs_dev.
+ * part_c = the populations gives the level's radiance (single_rads[(gas, iso, lev)]); part_c = populations times an
+ * altitude mask the radiance the level emits inside an altitude band.  Several parts may name the same level.  The gas
+ * parts and B add up to I; the level parts of all levels with part_c = pop add up to the gas part; with
+ * solo_absorption every part is exactly zero and B = I.
+ * abs_c / emi_c: DEVICE [n_gas][n_layers][n_pts]; tab: DEVICE [n_levels][2][n_tab_rows][n_pts]; coef_row: HOST
+ * [n_layers], each in [0, n_tab_rows); part_gas, part_level: HOST [n_part]; part_c: HOST [n_part][n_layers] (rows of gas
+ * parts ignored); tab, coef_row and part_c may be NULL when there is no level part.  rad: DEVICE [n_rays][n_pts] or
+ * NULL; parts: DEVICE [n_rays][n_part + 1][n_pts], row n_part is B, every element written.  los_order, solo_absorption
+ * and init_mode 0 / 2 as the other ray-batch calls; init_mode 1 is refused (SR_ERR_ARG).  All arguments are checked
+ * before the first copy or launch: a refused call leaves rad and parts untouched.
+ * The reference's single_rads come from the absent spect_base_module: the build's definition, checked against
+ * sr_glevel_combine_dev + sr_limb_rays_dev per part, closure and the CPU oracle's recursion (tests/test_gpu_parts.py). */
+int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
+                           int gas, const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_part,
+                           const int32_t *part_gas, const int32_t *part_level, const double *part_c, double *rad,
+                           double *parts, void *stream);
 
 /* Radiances and their Jacobian with respect to n_par retrieval parameters on which the absorber
  * columns depend linearly, col_s = sum_p dcol_dpar[s][p] * x_p (VMR profile parameters of the

@@ -3368,6 +3368,99 @@ int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_l
   return D.slot->mark(st);
 }
 
+int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
+                           int gas, const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_part,
+                           const int32_t *part_gas, const int32_t *part_level, const double *part_c, double *rad,
+                           double *parts, void *stream) {
+  // everything is checked here, before the first copy or launch (the LOS too, as sr_limb_rays_jac_level_dev does)
+  if (!abs_c || !emi_c || !part_gas || !part_level || !parts) return SR_ERR_ARG;
+  if (n_layers <= 0 || n_pts <= 0 || n_part < 1) return SR_ERR_ARG;
+  if (n_pts > 2000000) return SR_ERR_LIMIT;
+  if (tab && n_levels > 0 && n_tab_rows > 0 && 2 * (int64_t)n_levels * n_tab_rows > INT_MAX) return SR_ERR_LIMIT; // 32-bit row numbers
+  int n_seg = 0, n_pt = 0;
+  int rc = check_los(los, n_layers, &n_seg, &n_pt);
+  if (rc) return rc;
+  if (los->init_mode == 1) {
+    g_err = "sr_limb_rays_parts_dev: init_mode 1 (intensity read from a buffer) is not supported, use 0 or 2";
+    return SR_ERR_ARG;
+  }
+  bool any_level = false;
+  for (int k = 0; k < n_part; ++k) {
+    if (part_gas[k] < 0 || part_gas[k] >= los->n_gas || part_level[k] < -1) return SR_ERR_ARG;
+    if (part_level[k] < 0) continue;
+    any_level = true;
+    if (part_gas[k] != gas) {
+      g_err = "sr_limb_rays_parts_dev: a level part of another gas than the level-factored one";
+      return SR_ERR_ARG;
+    }
+    if (!tab || !coef_row || !part_c || part_level[k] >= n_levels || n_tab_rows <= 0) return SR_ERR_ARG;
+  }
+  if (any_level)
+    for (int r = 0; r < n_layers; ++r)
+      if (coef_row[r] < 0 || coef_row[r] >= n_tab_rows) return SR_ERR_ARG; // would read out of the tables
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // the parts in level order (stable; gas parts first, the background last), NP slots per block: the slots of one
+  // level are neighbours, so a row's table value is loaded once per distinct level
+  const int n_slot = n_part + 1, np = limb_parts_np(n_part), n_blocks = (n_slot + np - 1) / np;
+  std::vector<int> order(n_part);
+  for (int k = 0; k < n_part; ++k) order[k] = k;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return std::max(part_level[a], -1) < std::max(part_level[b], -1); });
+  order.push_back(n_part);
+  std::vector<int> slot_level((size_t)n_blocks * np, kPartNoSource), slot_part((size_t)n_blocks * np, -1);
+  std::vector<unsigned> words((size_t)n_blocks * n_layers, 0u);
+  std::vector<double> cc((size_t)n_blocks * n_layers * np, 0.0);
+  for (int i = 0; i < n_slot; ++i) {
+    const int k = order[i], b = i / np, q = i % np;
+    slot_part[i] = k;
+    if (k == n_part) continue; // the background: no source
+    slot_level[i] = part_level[k] >= 0 ? (2 * part_level[k] + 1) * n_tab_rows : -1 - part_gas[k];
+    for (int r = 0; r < n_layers; ++r) {
+      unsigned &w = words[(size_t)b * n_layers + r];
+      if (part_level[k] < 0) { // a gas part: active on every row; its coefficient slot carries the gas's index
+        w |= 1u << q;
+        const int64_t g = part_gas[k];
+        std::memcpy(&cc[((size_t)b * n_layers + r) * np + q], &g, sizeof(g));
+        continue;
+      }
+      const double c = part_c[(size_t)k * n_layers + r];
+      if (c == 0.0) continue;
+      cc[((size_t)b * n_layers + r) * np + q] = c;
+      const bool passed_on = q > 0 && slot_level[i - 1] == slot_level[i] && (w >> (q - 1) & 1u);
+      w |= 1u << q | (passed_on ? 0u : 1u << (16 + q));
+    }
+  }
+  static thread_local Stager s_ring[4];
+  static thread_local unsigned s_next = 0;
+  Stager &sg = s_ring[s_next++ & 3];
+  auto al = [](size_t v) { return (v + 15) / 16 * 16; };
+  const size_t b_cc = sizeof(double) * cc.size(), o_word = al(b_cc), o_row = al(o_word + sizeof(unsigned) * words.size());
+  const size_t o_lev = al(o_row + sizeof(int) * (size_t)n_layers), o_slot = al(o_lev + sizeof(int) * slot_level.size());
+  const size_t total = al(o_slot + sizeof(int) * slot_part.size());
+  rc = sg.prepare(total);
+  if (rc) return rc;
+  char *h = sg.host<char>();
+  std::memcpy(h, cc.data(), b_cc);
+  std::memcpy(h + o_word, words.data(), sizeof(unsigned) * words.size());
+  if (any_level) std::memcpy(h + o_row, coef_row, sizeof(int) * (size_t)n_layers);
+  else std::memset(h + o_row, 0, sizeof(int) * (size_t)n_layers);
+  std::memcpy(h + o_lev, slot_level.data(), sizeof(int) * slot_level.size());
+  std::memcpy(h + o_slot, slot_part.data(), sizeof(int) * slot_part.size());
+  rc = sg.push_early(total, st);
+  if (rc) return rc;
+  const char *d = sg.d.as<char>();
+  LosDev D;
+  rc = stage_los(los, n_layers, 0, nullptr, nullptr, st, &D);
+  if (rc) return rc;
+  LAUNCHCHK(launch_limb_parts(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col,
+                              limb_opts(los, D.n_seg), any_level ? gas : 0, tab,
+                              reinterpret_cast<const int *>(d + o_row), n_blocks, reinterpret_cast<const unsigned *>(d + o_word),
+                              reinterpret_cast<const double *>(d), reinterpret_cast<const int *>(d + o_lev),
+                              reinterpret_cast<const int *>(d + o_slot), n_part, rad, parts, st));
+  rc = sg.mark(st);
+  if (rc) return rc;
+  return D.slot->mark(st);
+}
+
 // ------------------------------------------------------------------------
 int sr_lut_interp_dev(const double *g_tab, int n_pt, int64_t n_pts, int n_steps, const int32_t *idx4,
                       const double *wgt4, const double *pop, int combine, double *out_a, double *out_e,

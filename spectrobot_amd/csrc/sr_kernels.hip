@@ -3016,6 +3016,7 @@ __global__ __launch_bounds__(256) void sr_radiance_jac_layer_kernel(
 //   sr_limb_jac_layer_kernel  + derivatives w.r.t. one scalar per layer acting through the coefficients
 //   sr_limb_jac_level_kernel  + derivatives w.r.t. level populations / vibrational temperatures of a level-factored gas
 //   (all three: forward sensitivities, NP parameters per thread; many parameters / layers: sr_limb_adjoint_kernel below)
+//   sr_limb_parts_kernel    the radiance split into the parts single gases / single levels emit, and the background
 // Per segment s of a ray, layer k = seg_layer[s], columns u_g = col[g][s]:
 //   tau = sum_g abs_g[k] u_g,  E = sum_g emi_g[k] u_g,  t = e^-tau,  f = (1 - t)/tau
 //   I <- I t + E f          (E f dropped with solo_absorption)
@@ -3402,6 +3403,156 @@ __global__ __launch_bounds__(256) void sr_limb_jac_level_kernel(
   for (int q = 0; q < NP; ++q) {
     const int p = slot_par[blockIdx.z * NP + q];
     if (p >= 0) jac[((size_t)ray * n_par + p) * n_pts + j] = J[q];
+  }
+}
+
+// The radiance budget of a ray batch (sr_limb_rays_parts_dev): the recursion is linear in the emission, so the share
+// e_k[r] of one gas's emission -- a whole gas, or c[k][r] E_L[row[r]] of one level of the level-factored gas (plane 1 of
+// the pair tables of sr_glevel_pairs_dev) -- reaches the observer as
+//   C_k <- C_k t + e_k[r] u_g(k) f      (C_k starts at 0; t, f of the TOTAL absorption)
+//   B   <- B t                          (B starts at the initial intensity: the background part)
+// and the gas parts and B add up to I.  One segment of one part (limb_parts_segment) and the kernel around it:
+// NP accumulators per thread, blocks of NP parts on blockIdx.z (the host sorts the parts by level, gas parts first, the
+// background last: slot_level >= 0 the row of the tables at which a level's E plane begins, (2 L + 1) n_tab_rows -- a
+// 32-bit row number, the 64-bit offset is formed per load --, -1 - g the gas part of gas g, kPartNoSource B or an unused
+// slot); per (part
+// block, coefficient row) one word, bit q: slot q has a source on this row (c != 0), bit 16 + q: its table value has
+// to be loaded (clear for a gas part and where the slot before it holds the same level and is active: that value is
+// passed on), and NP coefficients c (for a gas part: the gas's index in the low word).  A block works on one ray, so words and levels are wave-uniform -- scalar loads,
+// scalar branches, the accumulators indexed statically -- and a segment none of the block's parts touches costs NP
+// multiplications.  The NP coefficients of a row are loaded by lanes 0 .. NP - 1 (one vector load, two registers
+// instead of 2 NP scalar ones) and read from there when a slot is worked on (lane_value).  The table values and coefficients of segment s + 1 are loaded before segment s
+// is worked on (two register sets that swap roles: the loop is unrolled by two).  Rays and point blocks by
+// limb_block(): the rays of a point block share one XCD's L2 for the table rows.
+template <int NG, int NP>
+__device__ __forceinline__ void limb_parts_segment(
+    int s, int s1, size_t j, const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, size_t gstride,
+    const int *__restrict__ seg_layer, const double *__restrict__ col, const LimbOpts &o, int gas,
+    const double *__restrict__ tab, const int *__restrict__ coef_row, const unsigned *__restrict__ words,
+    const double *__restrict__ cc, const int (&lv)[NP], double (&an)[NG], double (&en)[NG], unsigned &m,
+    const double (&cur)[NP], double (&nxt)[NP], double ccur, double &cnxt, double &I, double (&J)[NP]) {
+  const int r = seg_layer[s];
+  double tau = 0.0, E = 0.0, ug = 0.0, Eg[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const double u = col[(size_t)g * o.n_seg_total + s];
+    tau = g == 0 ? an[g] * u : tau + an[g] * u;
+    Eg[g] = en[g] * u;
+    E = g == 0 ? Eg[g] : E + Eg[g];
+    ug = g == gas ? u : ug;
+  }
+  // what segment s + 1 needs: its coefficients and the table values its word asks for
+  const int rn = seg_layer[min(s + 1, s1 - 1)];
+  const unsigned mn = s + 1 < s1 && !o.solo_absorption ? words[rn] : 0u;
+  {
+    const size_t ofs = (size_t)rn * n_pts + j;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      an[g] = abs_c[g * gstride + ofs];
+      en[g] = emi_c[g * gstride + ofs];
+    }
+    if (NG > 1 && mn) cnxt = cc[(size_t)rn * NP];
+    if (mn >> 16) {
+      if (NG == 1) cnxt = cc[(size_t)rn * NP];
+      const double *tr = tab + j;
+      const int row = coef_row[rn];
+#pragma unroll
+      for (int q = 0; q < NP; ++q)
+        if (mn >> (16 + q) & 1u) nxt[q] = tr[(size_t)(lv[q] + row) * n_pts];
+    }
+  }
+  const Atten A = attenuation(tau);
+  const double t = A.t, f = A.f;
+#pragma unroll
+  for (int q = 0; q < NP; ++q) J[q] *= t;
+  if (m & 0xffffu) {
+    double last = 0.0;
+#pragma unroll
+    for (int q = 0; q < NP; ++q)
+      if (m >> q & 1u) {
+        double e;
+        if (lv[q] < 0) {
+          e = Eg[0];
+          if constexpr (NG > 1) { // (which gas: read with the row's coefficients, not compared slot by slot with lv --
+            // NP (NG - 1) loop-invariant conditions would each be kept in a scalar register pair)
+            const int gi = __builtin_amdgcn_readlane(__double2loint(ccur), q);
+#pragma unroll
+            for (int g = 1; g < NG; ++g) e = gi == g ? Eg[g] : e;
+          }
+        } else {
+          last = m >> (16 + q) & 1u ? cur[q] : last;
+          e = lane_value(ccur, q) * last * ug;
+        }
+        J[q] += e * f;
+      }
+  }
+  I = I * t + (o.solo_absorption ? 0.0 : E * f);
+  m = mn;
+}
+
+template <int NG, int NP>
+__global__ __launch_bounds__(256) void sr_limb_parts_kernel(
+    const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
+    const int *__restrict__ seg_off, const int *__restrict__ seg_layer, const double *__restrict__ col, LimbOpts o,
+    int n_rays, int gas, const double *__restrict__ tab, const int *__restrict__ coef_row,
+    const unsigned *__restrict__ words, const double *__restrict__ cc, const int *__restrict__ slot_level,
+    const int *__restrict__ slot_part, int n_part, double *__restrict__ rad, double *__restrict__ parts) {
+  static_assert(NP <= 16, "a row's word has 16 bits per kind");
+  int pb, ray;
+  if (!limb_block((n_pts + 255) / 256, n_rays, pb, ray)) return;
+  const int j0 = pb * 256 + threadIdx.x;
+  if (j0 - (int)(threadIdx.x & 63) >= n_pts) return; // the whole wave lies beyond the grid
+  // (a wave that straddles the end keeps all its lanes: the coefficients of a row sit in lanes 0 .. NP - 1 and are
+  // read from there, lane_value; the lanes beyond the grid work on its last point and store nothing)
+  const bool live = j0 < n_pts;
+  const int j = min(j0, n_pts - 1);
+  const double I0 = limb_initial(o, parts, 0, j); // init_mode 1 is refused by the host for this kernel
+  double I = I0, J[NP], ta[NP], tb[NP], ca = 0.0, cb = 0.0;
+  int lv[NP];
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    lv[q] = slot_level[blockIdx.z * NP + q];
+    J[q] = slot_part[blockIdx.z * NP + q] == n_part ? I0 : 0.0;
+    ta[q] = tb[q] = 0.0;
+  }
+  words += (size_t)blockIdx.z * n_layers;
+  cc += (size_t)blockIdx.z * n_layers * NP + (threadIdx.x & (NP - 1)); // lane q holds the coefficient of slot q
+  const int s0 = seg_off[ray], s1 = seg_off[ray + 1];
+  const size_t gstride = (size_t)n_layers * n_pts;
+  double an[NG], en[NG];
+  unsigned m = 0u;
+  if (s0 < s1) {
+    const int r = seg_layer[s0];
+    const size_t ofs = (size_t)r * n_pts + j;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      an[g] = abs_c[g * gstride + ofs];
+      en[g] = emi_c[g * gstride + ofs];
+    }
+    m = o.solo_absorption ? 0u : words[r];
+    if (NG > 1 && m) ca = cc[(size_t)r * NP];
+    if (m >> 16) {
+      if (NG == 1) ca = cc[(size_t)r * NP];
+      const double *tr = tab + j;
+      const int row = coef_row[r];
+#pragma unroll
+      for (int q = 0; q < NP; ++q)
+        if (m >> (16 + q) & 1u) ta[q] = tr[(size_t)(lv[q] + row) * n_pts];
+    }
+  }
+#define SR_SEG(S, CUR, NXT, CCUR, CNXT) limb_parts_segment<NG, NP>(S, s1, (size_t)j, abs_c, emi_c, n_pts, gstride, seg_layer, col, o, gas, \
+                                                       tab, coef_row, words, cc, lv, an, en, m, CUR, NXT, CCUR, CNXT, I, J)
+  for (int s = s0; s < s1; s += 2) {
+    SR_SEG(s, ta, tb, ca, cb);
+    if (s + 1 < s1) SR_SEG(s + 1, tb, ta, cb, ca);
+  }
+#undef SR_SEG
+  if (!live) return;
+  if (blockIdx.z == 0 && rad) rad[(size_t)ray * n_pts + j] = I;
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    const int p = slot_part[blockIdx.z * NP + q];
+    if (p >= 0) parts[((size_t)ray * (n_part + 1) + p) * n_pts + j] = J[q];
   }
 }
 
@@ -4597,6 +4748,24 @@ int launch_limb_jac_level(const double *abs_c, const double *emi_c, int n_pts, i
                                         seg_off, seg_layer, col, o, n_rays, gas, tab, n_tab_rows, coef_row, ent_off, ent,       \
                                         slot_par, n_par, rad, jac)
   if (level_jac_np(n_par) == kLevelJacNPLarge) {
+    SR_BY_NGAS(o.n_gas, SR_L(1, kLevelJacNPLarge), SR_L(2, kLevelJacNPLarge), SR_L(3, kLevelJacNPLarge), SR_L(4, kLevelJacNPLarge))
+  } else {
+    SR_BY_NGAS(o.n_gas, SR_L(1, kLevelJacNPSmall), SR_L(2, kLevelJacNPSmall), SR_L(3, kLevelJacNPSmall), SR_L(4, kLevelJacNPSmall))
+  }
+#undef SR_L
+  return (int)hipGetLastError();
+}
+
+int launch_limb_parts(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
+                      const int *seg_layer, const double *col, const LimbOpts &o, int gas, const double *tab,
+                      const int *coef_row, int n_blocks, const unsigned *words, const double *cc, const int *slot_level,
+                      const int *slot_part, int n_part, double *rad, double *parts, hipStream_t st) {
+  if (n_pts <= 0 || n_rays <= 0 || n_part <= 0 || n_blocks <= 0) return 0;
+  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
+#define SR_L(NG, NP) hipLaunchKernelGGL((sr_limb_parts_kernel<NG, NP>), grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, \
+                                        seg_layer, col, o, n_rays, gas, tab, coef_row, words, cc, slot_level, slot_part,               \
+                                        n_part, rad, parts)
+  if (limb_parts_np(n_part) == kLevelJacNPLarge) {
     SR_BY_NGAS(o.n_gas, SR_L(1, kLevelJacNPLarge), SR_L(2, kLevelJacNPLarge), SR_L(3, kLevelJacNPLarge), SR_L(4, kLevelJacNPLarge))
   } else {
     SR_BY_NGAS(o.n_gas, SR_L(1, kLevelJacNPSmall), SR_L(2, kLevelJacNPSmall), SR_L(3, kLevelJacNPSmall), SR_L(4, kLevelJacNPSmall))

@@ -251,6 +251,19 @@ int launch_limb_jac_level(const double *abs_c, const double *emi_c, int n_pts, i
                           const int *seg_layer, const double *col, const LimbOpts &o, int gas, const double *tab,
                           int n_tab_rows, const int *coef_row, int n_blocks, const int *ent_off, const LevelEnt *ent,
                           const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st);
+// Radiance budget (sr_limb_parts_kernel): the n_part parts and the background are n_part + 1 slots in blocks of
+// limb_parts_np(n_part); slot_level [n_blocks][NP]: >= 0 the first row of a level's E plane in the pair tables,
+// (2 L + 1) n_tab_rows, -1 - g the gas part of gas g,
+// kPartNoSource no source (background, unused slot); slot_part [n_blocks][NP]: the row of `parts` a slot is written to
+// (n_part: the background, which starts at the initial intensity) or -1; words [n_blocks][n_layers]: bit q = slot q
+// has a source on the row, bit 16 + q = its table value is loaded (not passed on from slot q - 1);
+// cc [n_blocks][n_layers][NP]: the coefficients of the level parts (a gas part: its gas index as an int64).
+constexpr int kPartNoSource = -2147483647 - 1;
+inline int limb_parts_np(int n_part) { return n_part + 1 > kLevelJacNPSmall ? kLevelJacNPLarge : kLevelJacNPSmall; }
+int launch_limb_parts(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
+                      const int *seg_layer, const double *col, const LimbOpts &o, int gas, const double *tab,
+                      const int *coef_row, int n_blocks, const unsigned *words, const double *cc, const int *slot_level,
+                      const int *slot_part, int n_part, double *rad, double *parts, hipStream_t st);
 // One pass per ray for radiances, per-layer and column-parameter Jacobians (sr_limb_adjoint_kernel)
 struct SegProg;
 constexpr int kAdjPlanInts = 4 + 2 * 4; // ints per segment of the host plan: layer, flags, n_ent, jrow, ent_p[4], ent_gf[4]

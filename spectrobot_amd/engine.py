@@ -526,6 +526,37 @@ class LevelFactored(object):
         return limb_rays_level_jacobian(coeffs, los, self.tab, step_row, par_level, par_c, gas=gas, grid=grid,
                                         g_lo=int(self._shard[0]), want_rad=want_rad)
 
+    def level_radiances(self, coeffs, los, step_row, tvib, levels=None, weights=None, gas=0, q_part=None, grid=None,
+                        gas_parts=True):
+        """(rad, parts [n_rays, n_part + 1, n_pts], labels): the radiance budget of the batch by the levels of this gas
+        (limb_rays_parts) on the coefficient rows of `coeffs` -- what steps(step_row, tvib=tvib) returned (one gas) or the
+        stack of all gases with this one at index `gas`.  Part i is the radiance level levels[i] emits (None: every
+        level), its share of the emission being pop_L[r] E_L[row[r]] with the populations of level_populations (tvib
+        None: LTE); weights [n_steps] or [n_levels_asked, n_steps] multiplies them, e.g. the mask of an altitude band on
+        the rows' altitudes (a level may be asked for several times, once per band).  gas_parts: then a part per gas of
+        the batch (its whole emission).  The last row is the background (the initial intensity, attenuated).  labels:
+        ('level', L) per level part, ('gas', g) per gas part, ('background',).  Honours the object's spectral shard."""
+        step_row = np.ascontiguousarray(step_row, dtype=np.int32)
+        n_lev = max(self.ls.level_energies.size, 1)
+        levels = np.arange(n_lev, dtype=np.int32) if levels is None else np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
+        if levels.size and (levels.min() < 0 or levels.max() >= n_lev):
+            raise ValueError("level out of range")
+        pop = self.ls.level_populations(self.temps[step_row], tvib=tvib, q_part=q_part)       # [n_steps, n_levels]
+        part_c = pop.T[levels]
+        if weights is not None:
+            w = np.asarray(weights, dtype=np.float64)
+            if w.shape not in ((step_row.size,), (levels.size, step_row.size)):
+                raise ValueError("weights must be [n_steps] or [n_levels_asked, n_steps]")
+            part_c = part_c * w
+        n_gp = los.n_gas if gas_parts else 0
+        part_gas = np.concatenate([np.full(levels.size, gas), np.arange(n_gp)]).astype(np.int32)
+        part_level = np.concatenate([levels, np.full(n_gp, -1)]).astype(np.int32)
+        part_c = np.concatenate([part_c, np.zeros((n_gp, step_row.size))])
+        rad, parts = limb_rays_parts(coeffs, los, part_gas, part_level, part_c=part_c, tab=self.tab, coef_row=step_row,
+                                     gas=gas, grid=grid, g_lo=int(self._shard[0]))
+        labels = [("level", int(L)) for L in levels] + [("gas", g) for g in range(n_gp)] + [("background",)]
+        return rad, parts, labels
+
 
 def level_node_weights(nodes, alt):
     """par_w [n_nodes, n_rows] of one level's vibrational-temperature profile on the coefficient rows: the triangular
@@ -1055,6 +1086,53 @@ def limb_rays_level_jacobian(coeffs, los, tab, coef_row, par_level, par_c, gas=0
                                          int(tab.shape[2]), cr, n_par, pl, pc, ptr(rad), ptr(jac), _stream_ptr()),
           "sr_limb_rays_jac_level_dev")
     return rad, jac
+
+
+def limb_rays_parts(coeffs, los, part_gas, part_level, part_c=None, tab=None, coef_row=None, gas=0, grid=None, g_lo=0,
+                    want_rad=True):
+    """(rad | None, parts [n_rays, n_part + 1, n_pts]): the radiances split into the parts single gases and single levels
+    emit (sr_limb_rays_parts_dev): part k is the radiance that arrives from a share of one gas's emission, attenuated by
+    ALL gases.  part_level[k] = -1: the whole emission of gas part_gas[k]; >= 0: level part_level[k] of the
+    level-factored gas `gas` (part_gas[k] must be gas), its share on coefficient row r being part_c[k, r] *
+    tab[level, 1, coef_row[r]] -- part_c the level's populations, or populations times an altitude mask.  The last row of
+    `parts` is the background (the initial intensity, attenuated); the gas parts and the background add up to rad.
+    coeffs as limb_rays; tab: the gas's pair tables (CUDA [n_levels, 2, n_tab_rows, n_pts], LineSet.glevel_pairs);
+    coef_row [n_layers]; part_c [n_part, n_layers] (rows of gas parts ignored); the three are needed for level parts
+    only.  Populations of a gas's levels: LevelFactored.level_radiances."""
+    a, e = _gas_stack(coeffs)
+    n_gas, n_layers, n_pts = a.shape
+    if n_gas != los.n_gas:
+        raise ValueError("%d coefficient sets for %d gases" % (n_gas, los.n_gas))
+    part_gas, pg = _i(np.asarray(part_gas).reshape(-1))
+    part_level, pl = _i(np.asarray(part_level).reshape(-1))
+    n_part = part_level.size
+    if part_gas.size != n_part:
+        raise ValueError("part_gas and part_level must have the same length")
+    n_levels = n_tab_rows = 0
+    cr = pc = None
+    if n_part and part_level.max() >= 0:
+        if tab is None or coef_row is None or part_c is None:
+            raise ValueError("level parts need tab, coef_row and part_c")
+    if tab is not None:
+        assert tab.is_cuda and tab.dtype == torch.float64 and tab.is_contiguous() and tab.dim() == 4 and tab.shape[1] == 2
+        if tab.shape[3] != n_pts:
+            raise ValueError("tables of %d points for coefficients of %d" % (tab.shape[3], n_pts))
+        n_levels, n_tab_rows = int(tab.shape[0]), int(tab.shape[2])
+    if coef_row is not None:
+        coef_row, cr = _i(coef_row)
+        if coef_row.shape != (n_layers,):
+            raise ValueError("coef_row must be [n_layers]")
+    if part_c is not None:
+        part_c, pc = _d(part_c)
+        if part_c.shape != (n_part, n_layers):
+            raise ValueError("part_c must be [n_part, n_layers]")
+    rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
+    parts = torch.empty((los.n_rays, n_part + 1, n_pts), dtype=torch.float64, device="cuda")
+    d = los.desc(grid, g_lo)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    check(lib.sr_limb_rays_parts_dev(ptr(a), ptr(e), n_layers, n_pts, C.byref(d), int(gas), ptr(tab), n_levels, n_tab_rows,
+                                     cr, n_part, pg, pl, pc, ptr(rad), ptr(parts), _stream_ptr()), "sr_limb_rays_parts_dev")
+    return rad, parts
 
 
 def radiance_jacobian(abs_c, emi_c, seg_off, seg_layer, seg_col, dcol_dpar):

@@ -191,7 +191,129 @@ def shard_with_halo(n_grid, g_lo, g_hi):
     return int(g_lo), int(min(g_hi + 1, n_grid))
 
 
-def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, refresh=False, arrays=False, group=None):
+def los_tags(n_los):
+    """Tags of the simulated lines of sight, in the order they are simulated (three per pixel, or the ladder's with
+    group_observations): the keys of radtrans and of every single_rads entry."""
+    return ['LOS%02d' % i for i in range(n_los)]
+
+
+def _level_index(lev):
+    """A tracked level as an index: an integer, or the reference's level name 'lev_NN'."""
+    if isinstance(lev, str):
+        if not lev.startswith('lev_'):
+            raise ValueError("a level is an index or 'lev_NN', not %r" % (lev,))
+        return int(lev[4:])
+    return int(lev)
+
+
+def single_rad_keys(gases, track_levels=None):
+    """[(key, gas index, level index | None)]: the entries of single_rads in the reference's order
+    (spect_main_module.py:3179-3187): (gas.name, 'iso_<n>') for every gas, followed by (gas.name, 'iso_<n>', lev) for
+    each of its tracked levels -- lev as given in track_levels[(gas.name, 'iso_<n>')], an index or 'lev_NN'.
+    ValueError for a track_levels key that names no gas of the scene and for a level the gas does not have."""
+    track_levels = dict(track_levels or {})
+    out = []
+    for gi, g in enumerate(gases):
+        gasiso = (g.name, 'iso_%d' % g.lineset.iso)
+        out.append((gasiso, gi, None))
+        n_lev = len(g.lineset.level_energies)
+        for lev in track_levels.pop(gasiso, ()):
+            L = _level_index(lev)
+            if not 0 <= L < n_lev:
+                raise ValueError('level {} is not a level of gas {}'.format(lev, g.name))
+            out.append((gasiso + (lev,), gi, L))
+    if track_levels:
+        raise ValueError('track_levels names unknown gases: {}'.format(sorted(track_levels)))
+    return out
+
+
+def pack_single_rads(keys, tags, low, bands_nm):
+    """(radtrans, single_rads) of the reference's return (spect_main_module.py:3287) from the low-resolution rows
+    low [1 + n_keys, n_los, n_bands]: row 0 the radiances, row 1 + i the part of keys[i] (single_rad_keys)."""
+    low = np.asarray(low, dtype=float)
+    if low.shape[:2] != (1 + len(keys), len(tags)):
+        raise ValueError("low must be [1 + n_keys, n_los, n_bands]")
+    radtrans = dict((tag, Spectrum(low[0, i], bands_nm)) for i, tag in enumerate(tags))
+    single_rads = dict()
+    for k, (key, _, _) in enumerate(keys):
+        single_rads[key] = dict((tag, Spectrum(low[1 + k, i], bands_nm)) for i, tag in enumerate(tags))
+    return radtrans, single_rads
+
+
+def _simulate_budget(scene, pixels, track_levels, fov_closed_form, shard, refresh, group):
+    """simulate() with the radiance budget: (sims, radtrans, single_rads).  A gas with tracked levels takes the
+    level-factored route (engine.LevelFactored on the scene's layers, kept on the gas per spectral shard; coefficients
+    from its steps()), so that its pair tables serve the level parts; one engine.limb_rays_parts call per such gas -- the
+    first one also carries the gas parts and the radiances --, one instrument step on the stacked buffer and, with a
+    spectral shard, one all-reduce of the partial band integrals of radiances and parts together."""
+    import torch
+    from . import distributed as sd
+    alts = [a for pix in pixels for a in pix.los_alts()]
+    alts_pix = None
+    if group is not None:
+        alts_sim, _ = smm.make_group_observations(list(pixels), alt_step=group[0], alt_first_los=group[1])
+        alts_pix, alts = alts, [float(a) for a in alts_sim]
+    keys = single_rad_keys(scene.gases, track_levels)
+    n_grid, n_layers, n_gas = len(scene.grid), len(scene.temps), len(scene.gases)
+    g_lo, g_hi = (0, n_grid) if shard is None else shard_with_halo(n_grid, *shard)
+    rows = np.arange(n_layers, dtype=np.int32)
+    tracked = sorted(set(gi for _, gi, L in keys if L is not None))
+    coeffs = []
+    for gi, g in enumerate(scene.gases):
+        if gi in tracked:
+            lf = getattr(g, "level_factored", None)
+            if lf is None or refresh or g.level_factored_shard != (g_lo, g_hi):
+                lf = g.level_factored = engine.LevelFactored(g.lineset, scene.temps, scene.press, g_lo=g_lo, g_hi=g_hi)
+                g.level_factored_shard = (g_lo, g_hi)
+            coeffs.append(lf.steps(rows, tvib=g.tvib))
+        else:
+            if g.coeffs is None or refresh or getattr(g, "coeffs_shard", None) != (g_lo, g_hi):
+                g.coeffs = g.lineset.abscoeff_layers(scene.temps, scene.press, tvib=g.tvib, g_lo=g_lo, g_hi=g_hi)
+                g.coeffs_shard = (g_lo, g_hi)
+            coeffs.append(g.coeffs)
+    stack = engine.gas_stack(coeffs)
+    los, _ = scene.los(alts)
+    n_los = len(alts)
+    # row k of the stacked buffer: 0 the radiances, 1 + i the part of keys[i]
+    buf = [None] * (1 + len(keys))
+    gas_rows = [k for k, (_, gi, L) in enumerate(keys) if L is None]
+    calls = tracked if tracked else [None]
+    for num, gi in enumerate(calls):
+        lev_rows = [k for k, (_, gj, L) in enumerate(keys) if L is not None and gj == gi]
+        levels = [keys[k][2] for k in lev_rows]
+        if gi is None:
+            rad, parts = engine.limb_rays_parts(stack, los, np.arange(n_gas), np.full(n_gas, -1), grid=scene.grid, g_lo=g_lo)
+        else:
+            rad, parts, _ = scene.gases[gi].level_factored.level_radiances(
+                stack, los, rows, scene.gases[gi].tvib, levels=levels, gas=gi, grid=scene.grid, gas_parts=num == 0)
+        for i, k in enumerate(lev_rows):
+            buf[1 + k] = parts[:, i]
+        if num == 0:
+            buf[0] = rad
+            for g, k in enumerate(gas_rows):
+                buf[1 + k] = parts[:, len(lev_rows) + g]
+    hires = torch.stack(buf).reshape(len(buf) * n_los, -1)
+    low = engine.hires_to_lowres(hires, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units, g_lo=g_lo)
+    low = np.asarray(low).reshape(len(buf), n_los, -1)
+    if shard is not None:
+        dev = "cuda" if (torch.distributed.is_initialized() and torch.distributed.get_backend() == "nccl") else "cpu"
+        t = torch.from_numpy(np.ascontiguousarray(low)).to(dev)
+        sd.all_reduce_sum(t)
+        low = t.cpu().numpy()
+    radtrans_, single_rads = pack_single_rads(keys, los_tags(n_los), low, scene.bands_nm)
+    at = low[0]
+    if alts_pix is not None:
+        f = smm.make_radtran_spline(alts, np.ascontiguousarray(low[0]))
+        at = np.array([f(a) for a in alts_pix])
+    sims = []
+    for i, pix in enumerate(pixels):
+        three = [Spectrum(at[3 * i + q], scene.bands_nm) for q in range(3)]
+        sims.append(smm.FOV_integr_1D(three, pix.pixel_rot, closed_form=fov_closed_form) if pix.fov_half > 0 else three[1])
+    return sims, radtrans_, single_rads
+
+
+def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, refresh=False, arrays=False, group=None,
+             track_levels=None, full_output=False):
     """One forward-model pass for all pixels (the body of the reference's iteration,
     spect_main_module.py:2736-2940): returns (sims, derivs) with sims[i] the FOV-integrated low-resolution
     spectrum of pixel i (Spectrum) and derivs[i][p] its derivative w.r.t. parameter p of bayes_set.
@@ -210,7 +332,14 @@ def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, re
     group = (alt_step_sims, alt_first_los): the reference's group_observations route (spect_main_module.py:2668-2670,
     2908-2930, 3056-3058, 3263-3273) -- the forward model runs on a regular ladder of tangent altitudes
     (smm.make_group_observations) instead of three LOS per pixel, and the pixels' LOS spectra (and derivatives) are read
-    off quadratic splines in tangent altitude (smm.make_radtran_spline) before the FOV integration."""
+    off quadratic splines in tangent altitude (smm.make_radtran_spline) before the FOV integration.
+
+    track_levels / full_output (simulation only: bayes_set None): returns (sims, radtrans, single_rads) as the
+    reference's radtrans (spect_main_module.py:3287) -- see radtrans below."""
+    if track_levels is not None or full_output:
+        if bayes_set is not None or arrays:
+            raise ValueError("the radiance budget (track_levels / full_output) is a simulation: no bayes_set, no arrays")
+        return _simulate_budget(scene, pixels, track_levels, fov_closed_form, shard, refresh, group)
     from . import distributed as sd
     alts = [a for pix in pixels for a in pix.los_alts()]
     alts_pix = None
@@ -546,9 +675,21 @@ def inversion(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM
     return None
 
 
-def radtrans(scene, pixels, fov_closed_form=True, shard=None, group_observations=False, alt_step_sims=50., alt_first_los=None):
+def radtrans(scene, pixels, fov_closed_form=True, shard=None, group_observations=False, alt_step_sims=50., alt_first_los=None,
+             track_levels=None, full_output=False):
     """Simulation only (spect_main_module.radtrans, :2990-3287): the FOV-integrated low-resolution spectra.
     group_observations / alt_step_sims / alt_first_los as in the reference's signature (:2990): simulate a ladder of
-    tangent altitudes and spline to the pixels' lines of sight (simulate(group=...))."""
+    tangent altitudes and spline to the pixels' lines of sight (simulate(group=...)).
+
+    track_levels ({(gas.name, 'iso_<n>'): levels}, smm.track_all_levels(scene) for all of them; a level is an index or
+    'lev_NN') or full_output=True: returns (sims, radtrans, single_rads) like the reference (:3287).  radtrans[tag] is
+    the low-resolution spectrum of simulated line of sight tag = 'LOS%02d' (three per pixel in the pixels' order; the
+    ladder's with group_observations), single_rads[(gas.name, 'iso_<n>')][tag] the part of it that gas emits and
+    single_rads[(gas.name, 'iso_<n>', lev)][tag] the part a tracked level emits (engine.limb_rays_parts: each attenuated
+    by all gases), without field-of-view integral, as in the reference.  The gases' spectra of a line of sight add up
+    to its radtrans entry (the scene has no background), the levels' spectra of a gas to the gas's."""
     group = (alt_step_sims, alt_first_los) if group_observations else None
+    if track_levels is not None or full_output:
+        return simulate(scene, pixels, None, fov_closed_form=fov_closed_form, shard=shard, group=group,
+                        track_levels=track_levels, full_output=True)
     return simulate(scene, pixels, None, fov_closed_form=fov_closed_form, shard=shard, group=group)[0]

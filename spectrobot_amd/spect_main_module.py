@@ -898,6 +898,25 @@ def _clone_spectrum(obj, spectrum=None):
     return out
 
 
+def track_all_levels(planet):
+    """track_levels of radtrans / inversion_fast_limb that names every level of every gas (spect_main_module.py:151-159):
+    {(gas name, iso tag): level names}.  `planet`: the reference's Planet (gases: a dict of molecules with all_iso and an
+    iso-molecule per tag carrying .levels), or a retrieval.LimbScene (gases: a list, each with .name and a line set): then
+    the iso tag is 'iso_<n>' of the line set's isotopologue and the levels are 'lev_00', 'lev_01', ... of its level
+    energies (none for an iso-molecule without levels)."""
+    track_levels = dict()
+    if hasattr(planet.gases, "keys"):
+        for molnam in planet.gases.keys():
+            mol = planet.gases[molnam]
+            for iso in mol.all_iso:
+                track_levels[(molnam, iso)] = getattr(mol, iso).levels
+        return track_levels
+    for gas in planet.gases:
+        n_lev = len(gas.lineset.level_energies)
+        track_levels[(gas.name, 'iso_%d' % gas.lineset.iso)] = ['lev_%02d' % lev for lev in range(n_lev)]
+    return track_levels
+
+
 def make_group_observations(pixels, alt_step=50., alt_first_los=None):
     """The set of tangent altitudes a group of pixels with similar geometry is simulated on, a regular ladder of
     step alt_step from the lowest pixel's lower LOS to (just beyond) the highest pixel's upper LOS
