@@ -197,6 +197,69 @@ struct Stager {
   template <class T> T *host() const { return static_cast<T *>(h); }
 };
 
+// A call site's small ring of staging buffers (each site declares its own, static thread_local): reusing one buffer
+// would make every call wait for the previous call's copy, i.e. for the GPU to reach it, and keep the host at most one
+// step ahead; with four slots a call waits for the one four calls back.
+struct StagerRing {
+  Stager s[4];
+  unsigned next = 0;
+  Stager &take() { return s[next++ & 3]; }
+};
+
+// The layout of one staged block in a Stager: typed arrays one after the other, each on a 16-byte boundary, then an
+// optional device-only tail.  Two phases: the parts are registered first (copy / zeros / room / tail); prepare() sizes
+// the slot and fills the host side, after it host() and dev() give a part's two addresses and push_early() (or
+// begin_early, then the slot's end_early) sends the host parts up.  An offset and the type read back from it are one
+// Part<T>.
+class StagePack {
+ public:
+  template <class T> struct Part { size_t off; };
+  explicit StagePack(Stager &slot) : sg_(slot) {}
+  Stager &slot() const { return sg_; } // for mark() and end_early()
+  // n elements copied from src; `room` keeps a part that may be empty at least that many elements long
+  template <class T> Part<T> copy(const T *src, size_t n, size_t room = 0) {
+    return {place(src, sizeof(T) * n, sizeof(T) * std::max(n, room), false)};
+  }
+  template <class T> Part<T> zeros(size_t n) { return {place(nullptr, 0, sizeof(T) * n, true)}; }
+  template <class T> Part<T> room(size_t n) { return {place(nullptr, 0, sizeof(T) * n, false)}; } // the caller fills host(part)
+  void tail(size_t bytes) { tail_ = bytes; } // device only, behind the staged parts: never copied
+  int prepare() {
+    const int rc = sg_.prepare(in_bytes() + tail_);
+    if (rc) return rc;
+    for (int i = 0; i < n_; ++i) {
+      if (it_[i].src && it_[i].bytes) std::memcpy(sg_.host<char>() + it_[i].off, it_[i].src, it_[i].bytes);
+      if (it_[i].zero) std::memset(sg_.host<char>() + it_[i].off, 0, it_[i].bytes);
+    }
+    return SR_OK;
+  }
+  int push_early(hipStream_t st) { return sg_.push_early(in_bytes(), st); }
+  int stage(hipStream_t st) { // prepare + push_early, for blocks without parts filled in place
+    const int rc = prepare();
+    return rc ? rc : push_early(st);
+  }
+  int begin_early(hipStream_t *copy_stream_out) { return sg_.begin_early(in_bytes(), copy_stream_out); }
+  template <class T> T *host(Part<T> p) const { return reinterpret_cast<T *>(sg_.host<char>() + p.off); }
+  template <class T> const T *dev(Part<T> p) const { return reinterpret_cast<const T *>(sg_.d.as<char>() + p.off); }
+  template <class T> T *dev_tail() const { return reinterpret_cast<T *>(sg_.d.as<char>() + in_bytes()); }
+
+ private:
+  struct Item { size_t off, bytes; const void *src; bool zero; };
+  static size_t al(size_t v) { return (v + 15) / 16 * 16; }
+  size_t in_bytes() const { return al(end_); }
+  size_t place(const void *src, size_t bytes, size_t room_bytes, bool zero) {
+    if (n_ == kMaxParts) abort(); // (a programming error: raise kMaxParts)
+    const size_t off = al(end_);
+    it_[n_++] = Item{off, zero ? room_bytes : bytes, src, zero};
+    end_ = off + room_bytes;
+    return off;
+  }
+  static constexpr int kMaxParts = 12;
+  Stager &sg_;
+  Item it_[kMaxParts];
+  int n_ = 0;
+  size_t end_ = 0, tail_ = 0;
+};
+
 // ---- TIPS-2003 (fparts_mod.f:33-295) + CalcPartitionSum (spect_classes.py:1692-1710) ----
 int tips_row(int mol, int iso) {
   for (int i = 0; i < kTipsNTab; ++i)
@@ -1876,30 +1939,17 @@ int sr_glevel_combine_dev(const double *tab, const double *tab_dT, int n_levels,
   std::vector<int> step_of((size_t)n_steps), fill(start);
   for (int s = 0; s < n_steps; ++s) step_of[(size_t)fill[(size_t)step_row[s]]++] = s;
   const int n_used = (int)rows_used.size();
-  static thread_local Stager s_ring[4];
-  static thread_local unsigned s_next = 0;
-  Stager &sg = s_ring[s_next++ & 3];
-  auto al = [](size_t v) { return (v + 15) / 16 * 16; };
-  const size_t b_pop = sizeof(double) * (size_t)n_steps * n_levels;
-  const size_t o_dpop = al(b_pop), o_used = al(o_dpop + (tab_dT ? b_pop : 0));
-  const size_t o_off = al(o_used + sizeof(int) * (size_t)n_used), o_step = al(o_off + sizeof(int) * (size_t)(n_used + 1));
-  const size_t total = al(o_step + sizeof(int) * (size_t)n_steps);
-  int rc = sg.prepare(total);
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const size_t n_pop = (size_t)n_steps * n_levels;
+  const auto p_pop = pk.copy(pop, n_pop), p_dpop = pk.copy(dpop, tab_dT ? n_pop : 0);
+  const auto p_used = pk.copy(rows_used.data(), rows_used.size()), p_off = pk.copy(row_off.data(), row_off.size());
+  const auto p_step = pk.copy(step_of.data(), step_of.size());
+  const int rc = pk.stage(st);
   if (rc) return rc;
-  char *h = sg.host<char>();
-  std::memcpy(h, pop, b_pop);
-  if (tab_dT) std::memcpy(h + o_dpop, dpop, b_pop);
-  std::memcpy(h + o_used, rows_used.data(), sizeof(int) * (size_t)n_used);
-  std::memcpy(h + o_off, row_off.data(), sizeof(int) * (size_t)(n_used + 1));
-  std::memcpy(h + o_step, step_of.data(), sizeof(int) * (size_t)n_steps);
-  rc = sg.push_early(total, st);
-  if (rc) return rc;
-  const char *d = sg.d.as<char>();
-  LAUNCHCHK(launch_glevel_combine(tab, tab_dT, n_levels, n_rows, (int)n_pts, n_used, reinterpret_cast<const int *>(d + o_used),
-                                  reinterpret_cast<const int *>(d + o_off), reinterpret_cast<const int *>(d + o_step),
-                                  reinterpret_cast<const double *>(d), reinterpret_cast<const double *>(d + o_dpop), inv_dT,
-                                  abs_out, emi_out, dabs_out, demi_out, st));
-  return sg.mark(st);
+  LAUNCHCHK(launch_glevel_combine(tab, tab_dT, n_levels, n_rows, (int)n_pts, n_used, pk.dev(p_used), pk.dev(p_off), pk.dev(p_step),
+                                  pk.dev(p_pop), pk.dev(p_dpop), inv_dT, abs_out, emi_out, dabs_out, demi_out, st));
+  return pk.slot().mark(st);
 }
 
 int sr_abscoeff_layers(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi,
@@ -1958,117 +2008,98 @@ int sr_last_level_tables_ms(sr_lineset *ls, float *ms4) {
   return SR_OK;
 }
 
-// ------------------------------------------------------------------------
-int sr_radiance_rays_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, int n_rays,
-                         const int32_t *seg_off, const int32_t *seg_layer, const double *seg_col,
-                         int init_from_rad, double *rad, void *stream) {
-  if (!abs_c || !emi_c || !rad || !seg_off || n_layers <= 0 || n_pts <= 0 || n_rays <= 0) return SR_ERR_ARG;
+} // extern "C"
+
+namespace {
+
+// The coefficient tables and the grid of a radiance or limb call; rest_ok: the call's other plain argument conditions,
+// which rank with the pointers (SR_ERR_ARG) before the grid limit.
+int check_limb_call(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, bool rest_ok) {
+  if (!abs_c || !emi_c || n_layers <= 0 || n_pts <= 0 || !rest_ok) return SR_ERR_ARG;
   if (n_pts > 2000000) return SR_ERR_LIMIT;
+  return SR_OK;
+}
+
+// The caller's segment lists of the sr_radiance_*_dev calls.  need_segments: the Jacobian calls refuse a batch
+// without any segment.
+int check_segments(int n_layers, int n_rays, const int32_t *seg_off, const int32_t *seg_layer, const double *seg_col,
+                   bool need_segments, int *n_seg_out) {
   const int n_seg = seg_off[n_rays];
-  if (seg_off[0] != 0 || n_seg < 0) return SR_ERR_ARG;
+  if (seg_off[0] != 0 || n_seg < (need_segments ? 1 : 0)) return SR_ERR_ARG;
   if (n_seg > 0 && (!seg_layer || !seg_col)) return SR_ERR_ARG;
   for (int r = 0; r < n_rays; ++r)
     if (seg_off[r + 1] < seg_off[r]) return SR_ERR_ARG;
   for (int s = 0; s < n_seg; ++s)
     if (seg_layer[s] < 0 || seg_layer[s] >= n_layers) return SR_ERR_ARG; // would read out of bounds
+  *n_seg_out = n_seg;
+  return SR_OK;
+}
+
+// Their staged block -- the three segment arrays and, for the column Jacobian, d col / d par (n_dcol values, or 0) --
+// sent up on a slot of the caller's ring, handed to the caller's launch(seg_off, seg_layer, seg_col, dcol) as device
+// pointers, and the slot marked behind that kernel (it is refilled only after it: the copy does not ride on `st`)
+template <class Launch>
+int with_staged_segments(Stager &slot, int n_rays, int n_seg, const int32_t *seg_off, const int32_t *seg_layer,
+                         const double *seg_col, const double *dcol, size_t n_dcol, hipStream_t st, Launch launch) {
+  StagePack pk(slot);
+  const auto p_off = pk.copy(seg_off, (size_t)n_rays + 1), p_layer = pk.copy(seg_layer, (size_t)n_seg, 1);
+  const auto p_col = pk.copy(seg_col, (size_t)n_seg, 1), p_dcol = pk.copy(dcol, n_dcol);
+  const int rc = pk.stage(st);
+  if (rc) return rc;
+  LAUNCHCHK(launch(pk.dev(p_off), pk.dev(p_layer), pk.dev(p_col), pk.dev(p_dcol)));
+  return slot.mark(st);
+}
+
+} // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------------
+int sr_radiance_rays_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, int n_rays,
+                         const int32_t *seg_off, const int32_t *seg_layer, const double *seg_col,
+                         int init_from_rad, double *rad, void *stream) {
+  int n_seg = 0;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, rad && seg_off && n_rays > 0);
+  if (!rc) rc = check_segments(n_layers, n_rays, seg_off, seg_layer, seg_col, /*need_segments=*/false, &n_seg);
+  if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // a small ring of staging buffers: reusing one would make every call wait for the previous
-  // call's copy, i.e. for the GPU to reach it, and keep the host at most one step ahead
-  static thread_local Stager s_ring[4];
-  static thread_local unsigned s_next = 0;
-  Stager &s_seg = s_ring[s_next++ & 3];
-  const size_t b_off = sizeof(int) * (size_t)(n_rays + 1), b_lay = sizeof(int) * (size_t)std::max(n_seg, 1);
-  const size_t o_lay = (b_off + 15) / 16 * 16, o_col = (o_lay + b_lay + 15) / 16 * 16;
-  const size_t total = o_col + sizeof(double) * (size_t)std::max(n_seg, 1);
-  int rc = s_seg.prepare(total);
-  if (rc) return rc;
-  std::memcpy(s_seg.host<char>(), seg_off, b_off);
-  if (n_seg > 0) {
-    std::memcpy(s_seg.host<char>() + o_lay, seg_layer, sizeof(int) * (size_t)n_seg);
-    std::memcpy(s_seg.host<char>() + o_col, seg_col, sizeof(double) * (size_t)n_seg);
-  }
-  rc = s_seg.push_early(total, st);
-  if (rc) return rc;
-  char *base = s_seg.d.as<char>();
-  LAUNCHCHK(launch_radiance(abs_c, emi_c, (int)n_pts, n_rays, reinterpret_cast<const int *>(base),
-                            reinterpret_cast<const int *>(base + o_lay),
-                            reinterpret_cast<const double *>(base + o_col), init_from_rad, rad, st));
-  return s_seg.mark(st); // the slot is refilled only after this kernel (the copy no longer rides on `st`)
+  static thread_local StagerRing ring;
+  return with_staged_segments(ring.take(), n_rays, n_seg, seg_off, seg_layer, seg_col, nullptr, 0, st,
+                              [&](const int *off, const int *layer, const double *col, const double *) {
+    return launch_radiance(abs_c, emi_c, (int)n_pts, n_rays, off, layer, col, init_from_rad, rad, st);
+  });
 }
 
 // ------------------------------------------------------------------------
 int sr_radiance_jac_layer_dev(const double *abs_c, const double *emi_c, const double *dabs, const double *demi,
                               int n_layers, int64_t n_pts, int n_rays, const int32_t *seg_off,
                               const int32_t *seg_layer, const double *seg_col, double *jac, void *stream) {
-  if (!abs_c || !emi_c || !dabs || !demi || !jac || !seg_off || n_layers <= 0 || n_pts <= 0 || n_rays <= 0)
-    return SR_ERR_ARG;
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
-  const int n_seg = seg_off[n_rays];
-  if (seg_off[0] != 0 || n_seg <= 0 || !seg_layer || !seg_col) return SR_ERR_ARG;
-  for (int r = 0; r < n_rays; ++r)
-    if (seg_off[r + 1] < seg_off[r]) return SR_ERR_ARG;
-  for (int s = 0; s < n_seg; ++s)
-    if (seg_layer[s] < 0 || seg_layer[s] >= n_layers) return SR_ERR_ARG;
+  int n_seg = 0;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, dabs && demi && jac && seg_off && n_rays > 0);
+  if (!rc) rc = check_segments(n_layers, n_rays, seg_off, seg_layer, seg_col, /*need_segments=*/true, &n_seg);
+  if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  static thread_local Stager s_ring[4]; // as in sr_radiance_rays_dev
-  static thread_local unsigned s_next = 0;
-  Stager &s_seg = s_ring[s_next++ & 3];
-  const size_t b_off = sizeof(int) * (size_t)(n_rays + 1), b_lay = sizeof(int) * (size_t)n_seg;
-  const size_t o_lay = (b_off + 15) / 16 * 16, o_col = (o_lay + b_lay + 15) / 16 * 16;
-  const size_t total = o_col + sizeof(double) * (size_t)n_seg;
-  int rc = s_seg.prepare(total);
-  if (rc) return rc;
-  char *h = s_seg.host<char>();
-  std::memcpy(h, seg_off, b_off);
-  std::memcpy(h + o_lay, seg_layer, b_lay);
-  std::memcpy(h + o_col, seg_col, sizeof(double) * (size_t)n_seg);
-  rc = s_seg.push_early(total, st);
-  if (rc) return rc;
-  char *base = s_seg.d.as<char>();
-  LAUNCHCHK(launch_radiance_jac_layer(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, n_rays,
-                                      reinterpret_cast<const int *>(base),
-                                      reinterpret_cast<const int *>(base + o_lay),
-                                      reinterpret_cast<const double *>(base + o_col), jac, st));
-  return s_seg.mark(st);
+  static thread_local StagerRing ring;
+  return with_staged_segments(ring.take(), n_rays, n_seg, seg_off, seg_layer, seg_col, nullptr, 0, st,
+                              [&](const int *off, const int *layer, const double *col, const double *) {
+    return launch_radiance_jac_layer(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, n_rays, off, layer, col, jac, st);
+  });
 }
 
 // ------------------------------------------------------------------------
 int sr_radiance_jac_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, int n_rays,
                         const int32_t *seg_off, const int32_t *seg_layer, const double *seg_col,
                         const double *dcol_dpar, int n_par, double *rad, double *jac, void *stream) {
-  if (!abs_c || !emi_c || !rad || !jac || !seg_off || !dcol_dpar || n_layers <= 0 || n_pts <= 0 || n_rays <= 0 ||
-      n_par <= 0)
-    return SR_ERR_ARG;
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
-  const int n_seg = seg_off[n_rays];
-  if (seg_off[0] != 0 || n_seg <= 0 || !seg_layer || !seg_col) return SR_ERR_ARG;
-  for (int r = 0; r < n_rays; ++r)
-    if (seg_off[r + 1] < seg_off[r]) return SR_ERR_ARG;
-  for (int s = 0; s < n_seg; ++s)
-    if (seg_layer[s] < 0 || seg_layer[s] >= n_layers) return SR_ERR_ARG;
+  int n_seg = 0;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, rad && jac && seg_off && dcol_dpar && n_rays > 0 && n_par > 0);
+  if (!rc) rc = check_segments(n_layers, n_rays, seg_off, seg_layer, seg_col, /*need_segments=*/true, &n_seg);
+  if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  static thread_local Stager s_ring[4]; // as in sr_radiance_rays_dev
-  static thread_local unsigned s_next = 0;
-  Stager &s_seg = s_ring[s_next++ & 3];
-  const size_t b_off = sizeof(int) * (size_t)(n_rays + 1), b_lay = sizeof(int) * (size_t)n_seg;
-  const size_t o_lay = (b_off + 15) / 16 * 16, o_col = (o_lay + b_lay + 15) / 16 * 16;
-  const size_t o_d = o_col + sizeof(double) * (size_t)n_seg;
-  const size_t total = o_d + sizeof(double) * (size_t)n_seg * n_par;
-  int rc = s_seg.prepare(total);
-  if (rc) return rc;
-  char *h = s_seg.host<char>();
-  std::memcpy(h, seg_off, b_off);
-  std::memcpy(h + o_lay, seg_layer, b_lay);
-  std::memcpy(h + o_col, seg_col, sizeof(double) * (size_t)n_seg);
-  std::memcpy(h + o_d, dcol_dpar, sizeof(double) * (size_t)n_seg * n_par);
-  rc = s_seg.push_early(total, st);
-  if (rc) return rc;
-  char *base = s_seg.d.as<char>();
-  LAUNCHCHK(launch_radiance_jac(abs_c, emi_c, (int)n_pts, n_rays, reinterpret_cast<const int *>(base),
-                                reinterpret_cast<const int *>(base + o_lay),
-                                reinterpret_cast<const double *>(base + o_col),
-                                reinterpret_cast<const double *>(base + o_d), n_par, rad, jac, st));
-  return s_seg.mark(st);
+  static thread_local StagerRing ring;
+  return with_staged_segments(ring.take(), n_rays, n_seg, seg_off, seg_layer, seg_col, dcol_dpar, (size_t)n_seg * n_par, st,
+                              [&](const int *off, const int *layer, const double *col, const double *dcol) {
+    return launch_radiance_jac(abs_c, emi_c, (int)n_pts, n_rays, off, layer, col, dcol, n_par, rad, jac, st);
+  });
 }
 
 // ------------------------------------------------------------------------
@@ -2087,7 +2118,35 @@ struct LosDev {
   Stager *slot;
 };
 
-int check_los(const sr_los_desc *los, int n_layers, int *n_seg_out, int *n_pt_out) {
+// The entry points that start every ray from 0 or from the Planck function refuse an initial intensity read from a
+// buffer, each with the status it has always answered.
+int refuse_init_mode_1(const sr_los_desc *los, const char *entry, int status) {
+  if (los->init_mode != 1) return SR_OK;
+  g_err = std::string(entry) + ": init_mode 1 (intensity read from a buffer) is not supported, use 0 or 2";
+  return status;
+}
+
+// coef_row [n_layers] of the level-table calls: rows of tables with n_tab_rows rows
+bool coef_rows_in_range(const int32_t *coef_row, int n_layers, int n_tab_rows) {
+  for (int r = 0; r < n_layers; ++r)
+    if (coef_row[r] < 0 || coef_row[r] >= n_tab_rows) return false; // would read out of the tables
+  return true;
+}
+
+// 0 .. n-1 in level order (stable; a level below 0 counts as -1 and comes first): cut into blocks of NP, a block then
+// touches few levels and the entries of one level are neighbours
+std::vector<int> order_by_level(int n, const int32_t *level) {
+  std::vector<int> order(n);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return std::max(level[a], -1) < std::max(level[b], -1); });
+  return order;
+}
+
+struct LosShape {
+  int n_seg = 0, n_pt = 0;
+};
+
+int check_los(const sr_los_desc *los, int n_layers, LosShape *out) {
   if (!los || los->n_rays <= 0 || los->n_gas <= 0 || !los->seg_off || !los->x || !los->nd || !los->vmr) return SR_ERR_ARG;
   if (los->n_gas > 4) return SR_ERR_LIMIT;
   if (los->init_mode < 0 || los->init_mode > 2) return SR_ERR_ARG;
@@ -2103,47 +2162,41 @@ int check_los(const sr_los_desc *los, int n_layers, int *n_seg_out, int *n_pt_ou
     if (np < 2) return SR_ERR_ARG;
     if (np > 8000) return SR_ERR_LIMIT; // imxstp, parameters.inc:64
   }
-  *n_seg_out = n_seg;
-  *n_pt_out = los->pt_off[n_seg];
+  out->n_seg = n_seg;
+  out->n_pt = los->pt_off[n_seg];
   return SR_OK;
 }
 
-// Stage the LOS on `st` and evaluate the columns of the gases and of n_par profile parameters.
-// own: the staging slot of a device-resident LOS (sr_los_create) instead of the per-call ring.
-int stage_los(const sr_los_desc *los, int n_layers, int n_par, const int32_t *par_gas, const double *par_w,
-              hipStream_t st, LosDev *out, Stager *own = nullptr) {
-  int n_seg = 0, n_pt = 0;
-  int rc = check_los(los, n_layers, &n_seg, &n_pt);
+// check_los + the column parameters staged with the batch
+int check_los_par(const sr_los_desc *los, int n_layers, int n_par, const int32_t *par_gas, const double *par_w, LosShape *out) {
+  const int rc = check_los(los, n_layers, out);
   if (rc) return rc;
   if (n_par < 0 || (n_par > 0 && (!par_gas || !par_w))) return SR_ERR_ARG;
   for (int p = 0; p < n_par; ++p)
     if (par_gas[p] < 0 || par_gas[p] >= los->n_gas) return SR_ERR_ARG;
-  static thread_local Stager s_ring[4];
-  static thread_local unsigned s_next = 0;
-  Stager &sg = own ? *own : s_ring[s_next++ & 3];
-  const int n_prof = los->n_gas + n_par, nr = los->n_rays;
-  auto al = [](size_t v) { return (v + 15) / 16 * 16; };
-  const size_t o_x = 0, o_nd = o_x + sizeof(double) * n_pt, o_prof = o_nd + sizeof(double) * n_pt;
-  const size_t o_scale = o_prof + sizeof(double) * (size_t)n_prof * n_pt;
-  const size_t o_soff = al(o_scale + sizeof(double) * n_prof), o_slay = al(o_soff + sizeof(int) * (nr + 1));
-  const size_t o_poff = al(o_slay + sizeof(int) * n_seg), o_pgas = al(o_poff + sizeof(int) * (n_seg + 1));
-  const size_t in_bytes = al(o_pgas + sizeof(int) * (size_t)std::max(n_par, 1));
-  const size_t total = in_bytes + sizeof(double) * (size_t)n_prof * n_seg; // + the column table (device only)
-  rc = sg.prepare(total);
+  return SR_OK;
+}
+
+// Stage a checked LOS (check_los_par: `shape`) and evaluate the columns of the gases and of n_par profile parameters;
+// `st` waits for them.  own: the staging slot of a device-resident LOS (sr_los_create) instead of the per-call ring.
+int stage_los(const sr_los_desc *los, const LosShape &shape, int n_par, const int32_t *par_gas, const double *par_w,
+              hipStream_t st, LosDev *out, Stager *own = nullptr) {
+  static thread_local StagerRing ring;
+  StagePack pk(own ? *own : ring.take());
+  const int n_seg = shape.n_seg, n_pt = shape.n_pt, n_prof = los->n_gas + n_par, nr = los->n_rays;
+  // (observer order re-lists x, nd, seg_layer and pt_off below)
+  const auto p_x = pk.copy(los->x, (size_t)n_pt), p_nd = pk.copy(los->nd, (size_t)n_pt);
+  const auto p_prof = pk.room<double>((size_t)n_prof * n_pt), p_scale = pk.room<double>((size_t)n_prof);
+  const auto p_soff = pk.copy(los->seg_off, (size_t)nr + 1), p_slay = pk.copy(los->seg_layer, (size_t)n_seg);
+  const auto p_poff = pk.copy(los->pt_off, (size_t)n_seg + 1), p_pgas = pk.copy(par_gas, (size_t)n_par, 1);
+  pk.tail(sizeof(double) * (size_t)n_prof * n_seg); // the column table
+  int rc = pk.prepare();
   if (rc) return rc;
-  char *h = sg.host<char>();
-  std::memcpy(h + o_x, los->x, sizeof(double) * n_pt);
-  std::memcpy(h + o_nd, los->nd, sizeof(double) * n_pt);
-  std::memcpy(h + o_prof, los->vmr, sizeof(double) * (size_t)los->n_gas * n_pt);
-  if (n_par) std::memcpy(h + o_prof + sizeof(double) * (size_t)los->n_gas * n_pt, par_w, sizeof(double) * (size_t)n_par * n_pt);
-  double *sc = reinterpret_cast<double *>(h + o_scale);
+  double *prs = pk.host(p_prof), *sc = pk.host(p_scale);
+  std::memcpy(prs, los->vmr, sizeof(double) * (size_t)los->n_gas * n_pt);
+  if (n_par) std::memcpy(prs + (size_t)los->n_gas * n_pt, par_w, sizeof(double) * (size_t)n_par * n_pt);
   for (int g = 0; g < los->n_gas; ++g) sc[g] = los->col_scale ? los->col_scale[g] : 1.0;
   for (int p = 0; p < n_par; ++p) sc[los->n_gas + p] = sc[par_gas[p]];
-  int *so = reinterpret_cast<int *>(h + o_soff), *sl = reinterpret_cast<int *>(h + o_slay);
-  std::memcpy(so, los->seg_off, sizeof(int) * (nr + 1));
-  if (los->los_order == 0) {
-    std::memcpy(sl, los->seg_layer, sizeof(int) * n_seg);
-  }
   // observer order: the recursion walks every ray's segments backwards.  Segment s keeps its index (and
   // its sample points, whose x must stay increasing); only the walk order changes, through a permutation
   // applied to seg_layer and to the column table's segment axis alike.
@@ -2151,11 +2204,10 @@ int stage_los(const sr_los_desc *los, int n_layers, int n_par, const int32_t *pa
   for (int r = 0; r < nr; ++r)
     for (int s = los->seg_off[r]; s < los->seg_off[r + 1]; ++s)
       perm[s] = los->los_order == 0 ? s : los->seg_off[r] + (los->seg_off[r + 1] - 1 - s);
-  int *po = reinterpret_cast<int *>(h + o_poff);
   if (los->los_order != 0) {
     // re-list the segments in photon order: new segment q = old segment perm[q]; sample points re-packed
     std::vector<double> x2(n_pt), nd2(n_pt), pr2((size_t)n_prof * n_pt);
-    const double *prs = reinterpret_cast<const double *>(h + o_prof);
+    int *sl = pk.host(p_slay), *po = pk.host(p_poff);
     int at = 0;
     for (int q = 0; q < n_seg; ++q) {
       const int s = perm[q], a = los->pt_off[s], b = los->pt_off[s + 1];
@@ -2168,32 +2220,23 @@ int stage_los(const sr_los_desc *los, int n_layers, int n_par, const int32_t *pa
       }
     }
     po[n_seg] = at;
-    std::memcpy(h + o_x, x2.data(), sizeof(double) * n_pt);
-    std::memcpy(h + o_nd, nd2.data(), sizeof(double) * n_pt);
-    std::memcpy(h + o_prof, pr2.data(), sizeof(double) * (size_t)n_prof * n_pt);
-  } else {
-    std::memcpy(po, los->pt_off, sizeof(int) * (n_seg + 1));
+    std::memcpy(pk.host(p_x), x2.data(), sizeof(double) * n_pt);
+    std::memcpy(pk.host(p_nd), nd2.data(), sizeof(double) * n_pt);
+    std::memcpy(prs, pr2.data(), sizeof(double) * (size_t)n_prof * n_pt);
   }
-  if (n_par) std::memcpy(h + o_pgas, par_gas, sizeof(int) * n_par);
   hipStream_t cs = nullptr;
-  rc = sg.begin_early(in_bytes, &cs);
+  rc = pk.begin_early(&cs);
   if (rc) return rc;
-  char *d = sg.d.as<char>();
-  out->x = reinterpret_cast<const double *>(d + o_x);
-  out->nd = reinterpret_cast<const double *>(d + o_nd);
-  out->prof = reinterpret_cast<const double *>(d + o_prof);
-  out->scale = reinterpret_cast<const double *>(d + o_scale);
-  out->seg_off = reinterpret_cast<const int *>(d + o_soff);
-  out->seg_layer = reinterpret_cast<const int *>(d + o_slay);
-  out->pt_off = reinterpret_cast<const int *>(d + o_poff);
-  out->par_gas = reinterpret_cast<const int *>(d + o_pgas);
-  out->col = reinterpret_cast<double *>(d + in_bytes);
-  out->n_seg = n_seg;
-  out->n_pt = n_pt;
-  out->n_prof = n_prof;
-  out->slot = &sg;
+  *out = LosDev{pk.dev(p_soff), pk.dev(p_slay), pk.dev(p_poff), pk.dev(p_pgas), pk.dev(p_x), pk.dev(p_nd), pk.dev(p_prof),
+                pk.dev(p_scale), pk.dev_tail<double>(), n_seg, n_pt, n_prof, &pk.slot()};
   LAUNCHCHK(launch_los_columns(out->nd, out->x, out->prof, out->scale, out->pt_off, n_seg, n_pt, n_prof, out->col, cs));
-  return sg.end_early(cs, st);
+  return pk.slot().end_early(cs, st);
+}
+
+// behind the kernels that read two staged blocks
+int mark_both(Stager &a, Stager &b, hipStream_t st) {
+  const int rc = a.mark(st);
+  return rc ? rc : b.mark(st);
 }
 
 LimbOpts limb_opts(const sr_los_desc *los, int n_seg) {
@@ -2285,13 +2328,13 @@ int stage_fold(const sr_los_desc *los, int n_layers, hipStream_t st, FoldStage *
   }
   if (shells.size() > 2 * longest) return SR_OK;
   const int n_vis = (int)shells.size(), n_rec = nr * n_vis;
-  static thread_local Stager s_ring[4];
-  static thread_local unsigned s_next = 0;
-  Stager &sg = own ? *own : s_ring[s_next++ & 3];
-  const size_t plan_bytes = (sizeof(int) * 4 * (size_t)n_rec + 15) / 16 * 16;
-  int rc = sg.prepare(plan_bytes + fold_dense_bytes(n_rec));
+  static thread_local StagerRing ring;
+  StagePack pk(own ? *own : ring.take());
+  const auto p_plan = pk.room<int>(4 * (size_t)n_rec);
+  pk.tail(fold_dense_bytes(n_rec));
+  int rc = pk.prepare();
   if (rc) return rc;
-  int *pl = sg.host<int>();
+  int *pl = pk.host(p_plan);
   for (int r = 0; r < nr; ++r)
     for (int v = 0; v < n_vis; ++v) {
       int *q = pl + ((size_t)r * n_vis + v) * 4;
@@ -2300,14 +2343,9 @@ int stage_fold(const sr_los_desc *los, int n_layers, hipStream_t st, FoldStage *
       q[2] = near[(size_t)r * n_layers + shells[v]];
       q[3] = 0;
     }
-  rc = sg.push_early(plan_bytes, st);
+  rc = pk.push_early(st);
   if (rc) return rc;
-  char *d = sg.d.as<char>();
-  out->plan = reinterpret_cast<const int *>(d);
-  out->rec = reinterpret_cast<FoldDense *>(d + plan_bytes);
-  out->n_vis = n_vis;
-  out->n_rec = n_rec;
-  out->slot = &sg;
+  *out = FoldStage{pk.dev(p_plan), pk.dev_tail<FoldDense>(), n_vis, n_rec, &pk.slot()};
   return SR_OK;
 }
 
@@ -2317,8 +2355,11 @@ extern "C" {
 
 int sr_los_columns(const sr_los_desc *los, double *col_out) {
   if (!col_out) return SR_ERR_ARG;
+  LosShape shape;
+  int rc = check_los(los, 0, &shape);
+  if (rc) return rc;
   LosDev D;
-  int rc = stage_los(los, 0, 0, nullptr, nullptr, nullptr, &D);
+  rc = stage_los(los, shape, 0, nullptr, nullptr, nullptr, &D);
   if (rc) return rc;
   std::vector<double> tmp((size_t)los->n_gas * D.n_seg);
   HIPCHK(hipMemcpy(tmp.data(), D.col, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
@@ -2357,24 +2398,45 @@ struct sr_los {
   bool k_timed = false;
 };
 
-// Entry of every call on a resident batch: the handle belongs to the device it was made on (its buffers, and the
-// pinned stagers that would rebuild themselves on another current device and then copy into this one's memory).
-static int los_enter(sr_los *h, hipStream_t st) {
-  int cur = -1;
-  HIPCHK(hipGetDevice(&cur));
-  if (cur != h->dev) {
-    g_err = "sr_los handle used on device " + std::to_string(cur) + ", made on device " + std::to_string(h->dev);
-    return SR_ERR_ARG;
+// Every call on a resident batch works inside one LosScope.  enter(): the handle belongs to the device it was made on
+// (its buffers, and the pinned stagers that would rebuild themselves on another current device and then copy into this
+// one's memory), and `st` waits for the handle's last use.  leave() records that use behind the call's work on `st` and
+// returns the status; a call that returns early after enter() -- a failed launch or copy with work already enqueued on
+// the handle -- leaves through the destructor, which records it all the same.
+class LosScope {
+ public:
+  LosScope(sr_los *h, hipStream_t st) : h_(h), st_(st) {}
+  ~LosScope() {
+    if (open_) (void)record();
   }
-  if (h->last_recorded) HIPCHK(hipStreamWaitEvent(st, h->ev_last, 0));
-  return SR_OK;
-}
-static int los_leave(sr_los *h, hipStream_t st) {
-  if (!h->ev_last) HIPCHK(hipEventCreateWithFlags(&h->ev_last, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(h->ev_last, st));
-  h->last_recorded = true;
-  return SR_OK;
-}
+  int enter() {
+    int cur = -1;
+    HIPCHK(hipGetDevice(&cur));
+    if (cur != h_->dev) {
+      g_err = "sr_los handle used on device " + std::to_string(cur) + ", made on device " + std::to_string(h_->dev);
+      return SR_ERR_ARG;
+    }
+    if (h_->last_recorded) HIPCHK(hipStreamWaitEvent(st_, h_->ev_last, 0));
+    open_ = true;
+    return SR_OK;
+  }
+  int leave() {
+    HIPCHK(record());
+    return SR_OK;
+  }
+
+ private:
+  hipError_t record() {
+    open_ = false;
+    hipError_t e = h_->ev_last ? hipSuccess : hipEventCreateWithFlags(&h_->ev_last, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(h_->ev_last, st_);
+    h_->last_recorded = h_->last_recorded || e == hipSuccess;
+    return e;
+  }
+  sr_los *h_;
+  hipStream_t st_;
+  bool open_ = false;
+};
 
 // ------------------------------------------------------------------------
 // The instrument step's per-thread device state (sr_hires_to_lowres_shard_dev, and sr_retrieval_forward_dev whose
@@ -2397,16 +2459,23 @@ struct LowresState {
 };
 static thread_local LowresState t_lowres;
 
-// Arguments checked, buffers for n_rows spectra in place, the weight table valid on `st` (its kernel launched there when
-// the key changed: *fresh).  fused: partial sums per 64-point slot (launch_fold_dense with the scratch).
-static int lowres_prepare(int n_rows, int64_t n_pts, int64_t g_lo, double w0, double step, const double *centers_nm,
-                          const double *widths_nm, int n_bands, double n_sigma, int out_units, bool fused, hipStream_t st,
-                          bool *fresh) {
+// The instrument step's arguments (on their own for sr_retrieval_forward_dev, which checks before it touches its handle)
+static int lowres_check(int n_rows, int64_t n_pts, int64_t g_lo, double w0, double step, const double *centers_nm,
+                        const double *widths_nm, int n_bands, double n_sigma, int out_units) {
   if (!centers_nm || !widths_nm || n_rows <= 0 || n_pts < 2 || n_bands <= 0 || g_lo < 0) return SR_ERR_ARG;
   if (g_lo + n_pts > 2000000) return SR_ERR_LIMIT;
   if (!(step > 0.0) || !(w0 > 0.0) || !(n_sigma > 0.0) || out_units < 0 || out_units > 2) return SR_ERR_ARG;
   for (int b = 0; b < n_bands; ++b)
     if (!(widths_nm[b] > 0.0)) return SR_ERR_ARG;
+  return SR_OK;
+}
+// Arguments checked, buffers for n_rows spectra in place, the weight table valid on `st` (its kernel launched there when
+// the key changed: *fresh).  fused: partial sums per 64-point slot (launch_fold_dense with the scratch).
+static int lowres_prepare(int n_rows, int64_t n_pts, int64_t g_lo, double w0, double step, const double *centers_nm,
+                          const double *widths_nm, int n_bands, double n_sigma, int out_units, bool fused, hipStream_t st,
+                          bool *fresh) {
+  int rc = lowres_check(n_rows, n_pts, g_lo, w0, step, centers_nm, widths_nm, n_bands, n_sigma, out_units);
+  if (rc) return rc;
   LowresState &L = t_lowres;
   const size_t nb = (size_t)n_bands;
   int cur_dev = 0;
@@ -2417,7 +2486,7 @@ static int lowres_prepare(int n_rows, int64_t n_pts, int64_t g_lo, double w0, do
     L.valid = false;
     L.dev = cur_dev;
   }
-  int rc = L.d_out.ensure(sizeof(double) * nb * n_rows);
+  rc = L.d_out.ensure(sizeof(double) * nb * n_rows);
   if (rc) return rc;
   rc = L.d_weights.ensure(lowres_scratch_bytes((int)n_pts, n_bands, n_rows, fused));
   if (rc) return rc;
@@ -2457,10 +2526,18 @@ static int lowres_land(int n_rows, int n_bands, double *out_host, hipStream_t st
   return SR_OK;
 }
 
+// The radiance route of a batch without parameters keeps packed records: packed again from the columns, on `st`
+static int los_repack(const sr_los *h, hipStream_t st) {
+  if (h->n_par != 0 || h->F.n_rec <= 0) return 0;
+  return launch_fold_fwd(h->F.plan, h->D.col, h->D.n_seg, h->F.n_rec, h->F.rec, nullptr, nullptr, 0, h->n_layers, h->opt.n_rays,
+                         h->F.n_vis, limb_opts(&h->opt, h->D.n_seg), nullptr, st);
+}
+
 // the recursion of a resident LOS on `st`: launches only
 static int limb_rays_los(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, sr_los *h, int64_t g_lo,
                          double *rad, hipStream_t st) {
-  const int rc0 = los_enter(h, st);
+  LosScope scope(h, st);
+  const int rc0 = scope.enter();
   if (rc0) return rc0;
   sr_los_desc o = h->opt;
   o.g_lo = g_lo;
@@ -2468,12 +2545,28 @@ static int limb_rays_los(const double *abs_c, const double *emi_c, int n_layers,
     LAUNCHCHK(launch_fold_fwd(h->F.plan, h->D.col, h->D.n_seg, h->F.n_rec, h->F.rec, abs_c, emi_c, (int)n_pts, n_layers, o.n_rays,
                               h->F.n_vis, limb_opts(&o, h->D.n_seg), rad, st, /*pack=*/false));
     g_last_limb_route = 2;
-    return los_leave(h, st);
+    return scope.leave();
   }
   LAUNCHCHK(launch_limb(abs_c, emi_c, (int)n_pts, n_layers, o.n_rays, h->D.seg_off, h->D.seg_layer, h->D.col,
                         limb_opts(&o, h->D.n_seg), rad, st));
   g_last_limb_route = 1;
-  return los_leave(h, st);
+  return scope.leave();
+}
+
+// the launches of sr_limb_rays_jac_los_dev on `st`, inside the caller's LosScope
+static int limb_jac_los(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, sr_los *h, int64_t g_lo, double *rad,
+                        double *jac, hipStream_t st) {
+  sr_los_desc o = h->opt;
+  o.g_lo = g_lo;
+  if (h->n_par <= kFoldDensePar && h->F.n_rec > 0 && g_jac_layer_forward.load() == 0) {
+    LAUNCHCHK(launch_fold_dense(h->F.plan, h->D.col, h->par_gas.data(), h->n_par, h->D.n_seg, h->F.n_rec, h->F.rec, abs_c, emi_c,
+                                (int)n_pts, n_layers, o.n_rays, h->F.n_vis, limb_opts(&o, h->D.n_seg), rad, jac, st));
+    return SR_OK;
+  }
+  LAUNCHCHK(launch_limb_jac(abs_c, emi_c, (int)n_pts, n_layers, o.n_rays, h->D.seg_off, h->D.seg_layer, h->D.col,
+                            h->D.col + (size_t)o.n_gas * h->D.n_seg, h->D.par_gas, h->n_par, limb_opts(&o, h->D.n_seg), rad,
+                            jac, st));
+  return SR_OK;
 }
 
 extern "C" {
@@ -2482,8 +2575,11 @@ int sr_los_create_par(const sr_los_desc *los, int n_layers, int n_par, const int
                       sr_los **out) {
   if (!out || n_layers <= 0 || n_par < 0) return SR_ERR_ARG;
   *out = nullptr;
+  LosShape shape;
+  int rc = check_los_par(los, n_layers, n_par, par_gas, par_w, &shape);
+  if (rc) return rc;
   sr_los *h = new sr_los();
-  int rc = stage_los(los, n_layers, n_par, par_gas, par_w, nullptr, &h->D, &h->s_los);
+  rc = stage_los(los, shape, n_par, par_gas, par_w, nullptr, &h->D, &h->s_los);
   if (!rc) rc = stage_fold(los, n_layers, nullptr, &h->F, &h->s_fold);
   if (!rc && n_par == 0 && h->F.n_rec > 0) { // (with parameters the records are packed per call: the columns change with the VMRs)
     LimbOpts o = limb_opts(los, h->D.n_seg);
@@ -2535,7 +2631,8 @@ int sr_los_set_vmr(sr_los *h, const double *vmr, void *stream) {
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t bytes = sizeof(double) * (size_t)h->opt.n_gas * h->D.n_pt;
-  int rc = los_enter(h, st);
+  LosScope scope(h, st);
+  int rc = scope.enter();
   if (rc) return rc;
   rc = h->s_vmr.prepare(bytes); // (waits for the previous update's copy: the one pinned buffer is being refilled)
   if (rc) return rc;
@@ -2545,12 +2642,8 @@ int sr_los_set_vmr(sr_los *h, const double *vmr, void *stream) {
   rc = h->s_vmr.mark(st);
   if (rc) return rc;
   LAUNCHCHK(launch_los_columns(h->D.nd, h->D.x, h->D.prof, h->D.scale, h->D.pt_off, h->D.n_seg, h->D.n_pt, h->opt.n_gas, h->D.col, st));
-  if (h->n_par == 0 && h->F.n_rec > 0) { // the radiance route keeps packed records: repack them with the new columns
-    LimbOpts o = limb_opts(&h->opt, h->D.n_seg);
-    LAUNCHCHK(launch_fold_fwd(h->F.plan, h->D.col, h->D.n_seg, h->F.n_rec, h->F.rec, nullptr, nullptr, 0, h->n_layers, h->opt.n_rays,
-                              h->F.n_vis, o, nullptr, st));
-  }
-  return los_leave(h, st);
+  LAUNCHCHK(los_repack(h, st));
+  return scope.leave();
 }
 
 // The Curtis-Godson columns of a resident batch integrated again from its staged sample points (and the folded
@@ -2560,36 +2653,25 @@ int sr_los_set_vmr(sr_los *h, const double *vmr, void *stream) {
 int sr_los_refresh_columns(sr_los *h, void *stream) {
   if (!h) return SR_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc0 = los_enter(h, st);
+  LosScope scope(h, st);
+  const int rc0 = scope.enter();
   if (rc0) return rc0;
   LAUNCHCHK(launch_los_columns(h->D.nd, h->D.x, h->D.prof, h->D.scale, h->D.pt_off, h->D.n_seg, h->D.n_pt, h->D.n_prof, h->D.col, st));
-  if (h->n_par == 0 && h->F.n_rec > 0) {
-    LimbOpts o = limb_opts(&h->opt, h->D.n_seg);
-    LAUNCHCHK(launch_fold_fwd(h->F.plan, h->D.col, h->D.n_seg, h->F.n_rec, h->F.rec, nullptr, nullptr, 0, h->n_layers, h->opt.n_rays,
-                              h->F.n_vis, o, nullptr, st));
-  }
-  return los_leave(h, st);
+  LAUNCHCHK(los_repack(h, st));
+  return scope.leave();
 }
 
 // sr_limb_rays_jac_dev on a resident batch made with its column parameters (sr_los_create_par): launches only.
 int sr_limb_rays_jac_los_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, sr_los *h, int64_t g_lo,
                              double *rad, double *jac, void *stream) {
-  if (!abs_c || !emi_c || !rad || !jac || !h || n_layers != h->n_layers || n_pts <= 0 || h->n_par <= 0) return SR_ERR_ARG;
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, rad && jac && h && n_layers == h->n_layers && h->n_par > 0);
+  if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc0 = los_enter(h, st);
-  if (rc0) return rc0;
-  sr_los_desc o = h->opt;
-  o.g_lo = g_lo;
-  if (h->n_par <= kFoldDensePar && h->F.n_rec > 0 && g_jac_layer_forward.load() == 0) {
-    LAUNCHCHK(launch_fold_dense(h->F.plan, h->D.col, h->par_gas.data(), h->n_par, h->D.n_seg, h->F.n_rec, h->F.rec, abs_c, emi_c,
-                                (int)n_pts, n_layers, o.n_rays, h->F.n_vis, limb_opts(&o, h->D.n_seg), rad, jac, st));
-    return los_leave(h, st);
-  }
-  LAUNCHCHK(launch_limb_jac(abs_c, emi_c, (int)n_pts, n_layers, o.n_rays, h->D.seg_off, h->D.seg_layer, h->D.col,
-                            h->D.col + (size_t)o.n_gas * h->D.n_seg, h->D.par_gas, h->n_par, limb_opts(&o, h->D.n_seg), rad,
-                            jac, st));
-  return los_leave(h, st);
+  LosScope scope(h, st);
+  rc = scope.enter();
+  if (rc) return rc;
+  rc = limb_jac_los(abs_c, emi_c, n_layers, n_pts, h, g_lo, rad, jac, st);
+  return rc ? rc : scope.leave();
 }
 
 // The forward model of ONE retrieval iteration on a resident batch made with its parameters, in one call: parameter
@@ -2610,8 +2692,13 @@ int sr_retrieval_forward_dev(const double *abs_c, const double *emi_c, int n_lay
   if (h->opt.init_mode == 1) return SR_ERR_ARG; // (initial radiances from the output buffer: `buf` is scratch here)
   const int n_rays = h->opt.n_rays, n_par = h->n_par, n_row = 1 + n_par;
   if (fov && n_rays % 3 != 0) return SR_ERR_ARG;
+  // the tables, the grid and the bands too, before the handle's profiles and columns are rewritten
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, n_layers == h->n_layers);
+  if (!rc) rc = lowres_check(n_rays * n_row, n_pts, g_lo, w0, step, centers_nm, widths_nm, n_bands, n_sigma, out_units);
+  if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = los_enter(h, st);
+  LosScope scope(h, st);
+  rc = scope.enter();
   if (rc) return rc;
   LAUNCHCHK(launch_los_vmr_from_params(const_cast<double *>(h->D.prof), h->opt.n_gas, n_par, h->D.n_pt, h->D.par_gas, x, st));
   LAUNCHCHK(launch_los_columns(h->D.nd, h->D.x, h->D.prof, h->D.scale, h->D.pt_off, h->D.n_seg, h->D.n_pt, h->opt.n_gas, h->D.col, st));
@@ -2619,8 +2706,6 @@ int sr_retrieval_forward_dev(const double *abs_c, const double *emi_c, int n_lay
   low.resize((size_t)n_rays * n_row * n_bands);
   if (g_band_fusion.load() && n_par <= kFoldDensePar && h->F.n_rec > 0 && g_jac_layer_forward.load() == 0) {
     // the one-sweep kernel integrates the bands in its epilogue: no spectra are written (`buf` stays untouched)
-    if (!abs_c || !emi_c || n_layers != h->n_layers || n_pts <= 0) return SR_ERR_ARG;
-    if (n_pts > 2000000) return SR_ERR_LIMIT;
     bool fresh = false;
     rc = lowres_prepare(n_rays * n_row, n_pts, g_lo, w0, step, centers_nm, widths_nm, n_bands, n_sigma, out_units, /*fused=*/true, st,
                         &fresh);
@@ -2640,7 +2725,7 @@ int sr_retrieval_forward_dev(const double *abs_c, const double *emi_c, int n_lay
                                 st, t_lowres.d_weights.p, n_bands));
     if (timed) HIPCHK(hipEventRecord(h->ev_k1, st));
     h->k_timed = timed;
-    rc = los_leave(h, st);
+    rc = scope.leave();
     if (rc) return rc;
     // the sums go straight into the library's pinned landing buffer (16 KB over the bus from the kernel itself: no copy
     // command behind it)
@@ -2652,7 +2737,8 @@ int sr_retrieval_forward_dev(const double *abs_c, const double *emi_c, int n_lay
     HIPCHK(hipStreamSynchronize(st));
     std::memcpy(low.data(), t_lowres.s_land.h, low_bytes);
   } else {
-    rc = sr_limb_rays_jac_los_dev(abs_c, emi_c, n_layers, n_pts, h, g_lo, buf, buf + (size_t)n_rays * n_pts, stream);
+    rc = limb_jac_los(abs_c, emi_c, n_layers, n_pts, h, g_lo, buf, buf + (size_t)n_rays * n_pts, st);
+    if (!rc) rc = scope.leave();
     if (rc) return rc;
     rc = sr_hires_to_lowres_shard_dev(buf, n_rays * n_row, n_pts, g_lo, w0, step, centers_nm, widths_nm, n_bands, n_sigma, out_units,
                                       low.data(), stream);
@@ -2852,9 +2938,9 @@ int sr_retrieval_loop_dev(const double *abs_c, const double *emi_c, int n_layers
 
 int sr_limb_rays_los_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, sr_los *h, int64_t g_lo,
                          double *rad, void *stream) {
-  if (!abs_c || !emi_c || !rad || !h || n_layers != h->n_layers || n_pts <= 0) return SR_ERR_ARG;
-  if (h->n_par != 0) return SR_ERR_ARG; // a batch made with parameters keeps no packed radiance records: sr_limb_rays_jac_los_dev
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
+  // (a batch made with parameters keeps no packed radiance records: sr_limb_rays_jac_los_dev)
+  const int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, rad && h && n_layers == h->n_layers && h->n_par == 0);
+  if (rc) return rc;
   return limb_rays_los(abs_c, emi_c, n_layers, n_pts, h, g_lo, rad, static_cast<hipStream_t>(stream));
 }
 
@@ -2868,11 +2954,13 @@ int sr_limb_step_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, in
 
 int sr_limb_rays_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
                      double *rad, void *stream) {
-  if (!abs_c || !emi_c || !rad || n_layers <= 0 || n_pts <= 0) return SR_ERR_ARG;
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
+  LosShape shape;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, rad != nullptr);
+  if (!rc) rc = check_los(los, n_layers, &shape);
+  if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   LosDev D;
-  int rc = stage_los(los, n_layers, 0, nullptr, nullptr, st, &D);
+  rc = stage_los(los, shape, 0, nullptr, nullptr, st, &D);
   if (rc) return rc;
   // ray batches of a 1-D atmosphere: the folded sweep (a shell's loads and, the path being symmetric, its attenuation
   // once for the ray's two segments); small launches keep the split kernel, whose time is a chain's latency
@@ -2884,9 +2972,7 @@ int sr_limb_rays_dev(const double *abs_c, const double *emi_c, int n_layers, int
       LAUNCHCHK(launch_fold_fwd(F.plan, D.col, D.n_seg, F.n_rec, F.rec, abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, F.n_vis,
                                 limb_opts(los, D.n_seg), rad, st));
       g_last_limb_route = 2;
-      rc = F.slot->mark(st);
-      if (rc) return rc;
-      return D.slot->mark(st);
+      return mark_both(*F.slot, *D.slot, st);
     }
   }
   LAUNCHCHK(launch_limb(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col,
@@ -2909,13 +2995,54 @@ struct AdjPlan {
   std::vector<int> zero_off; // [n_rays + 1]
   std::vector<int> zero_row; // layer rows (< n_layers) and parameter rows (n_layers + p)
 };
+// The column-parameter entries of a ray's walk, step by step (a segment, or a shell visit of the folded plan): the
+// parameters whose next touch (touch[p]: ascending steps) is this step; runs of consecutive touches are carried in one
+// of four registers while one is free.
+struct RunPlan {
+  bool slot_busy[4] = {false, false, false, false};
+  std::vector<int> slot_of, pos;
+  std::vector<char> seen; // the parameter has been written in this ray
+  explicit RunPlan(int n_par) : slot_of(std::max(n_par, 1), -1), pos(std::max(n_par, 1), 0), seen(std::max(n_par, 1), 0) {}
+  // the step's entries into its four slots (ent_p[4], ent_gf[4]); returns their number, or -1 when more than four touch it
+  int step(int at, const std::vector<std::vector<int>> &touch, const int32_t *par_gas, int *ent_p, int *ent_gf) {
+    int n_ent = 0;
+    for (int p = 0; p < (int)touch.size(); ++p) {
+      if (pos[p] >= (int)touch[p].size() || touch[p][pos[p]] != at) continue;
+      if (n_ent == 4) return -1;
+      const bool next_too = pos[p] + 1 < (int)touch[p].size() && touch[p][pos[p] + 1] == at + 1;
+      int fl = 0, sl = slot_of[p];
+      if (sl < 0) { // no carry in: a run starts here
+        fl |= 1;
+        if (next_too)
+          for (int c = 0; c < 4; ++c)
+            if (!slot_busy[c]) { sl = c; slot_busy[c] = true; break; }
+      }
+      const bool carry_out = next_too && sl >= 0;
+      if (!carry_out) {
+        fl |= 2;                    // written here
+        if (!seen[p]) fl |= 4;      // first write of this parameter in the ray: store
+        seen[p] = 1;
+        if (sl >= 0) slot_busy[sl] = false;
+        slot_of[p] = -1;
+      } else {
+        slot_of[p] = sl;
+      }
+      ent_p[n_ent] = p;
+      ent_gf[n_ent] = par_gas[p] | (std::max(sl, 0) << 8) | (fl << 16);
+      ++n_ent;
+      ++pos[p];
+    }
+    return n_ent;
+  }
+};
+
 bool build_adj_plan(const sr_los_desc *los, int n_layers, const int32_t *seg_jrow, int n_jrows, int n_par,
                     const int32_t *par_gas, const double *par_w, bool want_layer, int n_pt, AdjPlan *out) {
   const int nr = los->n_rays, n_seg = los->seg_off[nr];
   out->seg.assign((size_t)n_seg * kAdjPlanInts, 0);
   out->zero_off.assign(nr + 1, 0);
   out->zero_row.clear();
-  std::vector<char> lay_seen(n_jrows), par_seen(std::max(n_par, 1));
+  std::vector<char> lay_seen(n_jrows);
   std::vector<std::vector<int>> touch(n_par); // walk positions (within the ray) of the segments touching p
   for (int r = 0; r < nr; ++r) {
     const int a = los->seg_off[r], b = los->seg_off[r + 1], m = b - a;
@@ -2939,70 +3066,36 @@ bool build_adj_plan(const sr_los_desc *los, int n_layers, const int32_t *seg_jro
         if (nz) touch[p].push_back(q);
       }
     }
-    // entries per segment; runs of consecutive touches take a register while one is free
-    bool slot_busy[4] = {false, false, false, false};
-    std::vector<int> slot_of(std::max(n_par, 1), -1), run_left(std::max(n_par, 1), 0), pos(std::max(n_par, 1), 0);
-    std::fill(par_seen.begin(), par_seen.end(), 0);
+    RunPlan runs(n_par);
     for (int q = 0; q < m; ++q) {
       int *pl = &out->seg[(size_t)(a + q) * kAdjPlanInts];
-      int n_ent = 0;
-      for (int p = 0; p < n_par; ++p) {
-        if (pos[p] >= (int)touch[p].size() || touch[p][pos[p]] != q) continue;
-        if (n_ent == 4) return false;
-        const bool next_too = pos[p] + 1 < (int)touch[p].size() && touch[p][pos[p] + 1] == q + 1;
-        int fl = 0, sl = slot_of[p];
-        if (sl < 0) { // no carry in: a run starts here
-          fl |= 1;
-          if (next_too)
-            for (int c = 0; c < 4; ++c)
-              if (!slot_busy[c]) { sl = c; slot_busy[c] = true; break; }
-        }
-        const bool carry_out = next_too && sl >= 0;
-        if (!carry_out) {
-          fl |= 2;                        // written here
-          if (!par_seen[p]) fl |= 4;      // first write of this parameter in the ray: store
-          par_seen[p] = 1;
-          if (sl >= 0) slot_busy[sl] = false;
-          slot_of[p] = -1;
-        } else {
-          slot_of[p] = sl;
-        }
-        pl[4 + n_ent] = p;
-        pl[4 + 4 + n_ent] = par_gas[p] | (std::max(sl, 0) << 8) | (fl << 16);
-        ++n_ent;
-        ++pos[p];
-      }
-      pl[2] = n_ent;
+      pl[2] = runs.step(q, touch, par_gas, pl + 4, pl + 8);
+      if (pl[2] < 0) return false;
     }
     if (want_layer)
       for (int k = 0; k < n_jrows; ++k)
         if (!lay_seen[k]) out->zero_row.push_back(k);
     for (int p = 0; p < n_par; ++p)
-      if (!par_seen[p]) out->zero_row.push_back(n_jrows + p);
+      if (!runs.seen[p]) out->zero_row.push_back(n_jrows + p);
     out->zero_off[r + 1] = (int)out->zero_row.size();
   }
   return true;
 }
 
 // Radiances (rad may be NULL) + per-layer Jacobian (dabs / demi / jac_layer may be NULL) + column-parameter Jacobian
-// (n_par may be 0) in one pass.  *done = 0 when the plan does not fit the kernel (nothing launched).
+// (n_par may be 0) in one pass.  *done = 0 when the plan does not fit the kernel (nothing launched).  The callers have
+// checked everything: the LOS and its parameters (check_los_par: `shape`), seg_jrow's range, rad against init_mode 1.
 int limb_adjoint(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_layers,
-                 int64_t n_pts, const sr_los_desc *los, const int32_t *seg_jrow, int n_jrows, int n_par,
+                 int64_t n_pts, const sr_los_desc *los, const LosShape &shape, const int32_t *seg_jrow, int n_jrows, int n_par,
                  const int32_t *par_gas, const double *par_w, double *rad, double *jac_layer, double *jac_par,
                  hipStream_t st, int *done) {
   *done = 0;
-  int n_seg = 0, n_pt = 0;
-  int rc = check_los(los, n_layers, &n_seg, &n_pt);
-  if (rc) return rc;
-  if (!rad && los->init_mode == 1) return SR_ERR_ARG; // limb_initial would read rad
+  const int n_seg = shape.n_seg;
   if (!seg_jrow) n_jrows = n_layers;
-  if (seg_jrow)
-    for (int q = 0; q < n_seg; ++q)
-      if (seg_jrow[q] < 0 || seg_jrow[q] >= n_jrows) return SR_ERR_ARG; // would write out of the Jacobian
   AdjPlan plan;
-  if (!build_adj_plan(los, n_layers, seg_jrow, n_jrows, n_par, par_gas, par_w, jac_layer != nullptr, n_pt, &plan)) return SR_OK;
+  if (!build_adj_plan(los, n_layers, seg_jrow, n_jrows, n_par, par_gas, par_w, jac_layer != nullptr, shape.n_pt, &plan)) return SR_OK;
   LosDev D;
-  rc = stage_los(los, n_layers, n_par, par_gas, par_w, st, &D);
+  int rc = stage_los(los, shape, n_par, par_gas, par_w, st, &D);
   if (rc) return rc;
   // Layer-synchronous schedule (sr_limb_adjoint_sync_kernel): when the rays share their coefficient rows (no per-step
   // rows: seg_jrow == NULL) and every ray walks them monotonically down to a turning shell and monotonically up again
@@ -3037,8 +3130,6 @@ int limb_adjoint(const double *abs_c, const double *emi_c, const double *dabs, c
       fplan.assign((size_t)n_frec * kFoldPlanInts, 0);
       bool fits = true;
       std::vector<std::vector<int>> touch(n_par);
-      std::vector<int> slot_of(std::max(n_par, 1)), pos(std::max(n_par, 1));
-      std::vector<char> par_seen(std::max(n_par, 1));
       for (int rr = 0; rr < nb * fold_rays && fits; ++rr) {
         const int bt = rr / fold_rays, i = rr % fold_rays;
         auto rec_at = [&](int v) { return &fplan[(((size_t)bt * n_fvis + v) * fold_rays + i) * kFoldPlanInts]; };
@@ -3064,40 +3155,11 @@ int limb_adjoint(const double *abs_c, const double *emi_c, const double *dabs, c
               if (touch[sp[4 + e]].empty() || touch[sp[4 + e]].back() != v) touch[sp[4 + e]].push_back(v);
           }
         }
-        bool slot_busy[4] = {false, false, false, false};
-        std::fill(slot_of.begin(), slot_of.end(), -1);
-        std::fill(pos.begin(), pos.end(), 0);
-        std::fill(par_seen.begin(), par_seen.end(), 0);
+        RunPlan runs(n_par);
         for (int v = 0; v < n_fvis && fits; ++v) {
           int *pl = rec_at(v);
-          int n_ent = 0;
-          for (int p = 0; p < n_par; ++p) {
-            if (pos[p] >= (int)touch[p].size() || touch[p][pos[p]] != v) continue;
-            if (n_ent == 4) { fits = false; break; }
-            const bool next_too = pos[p] + 1 < (int)touch[p].size() && touch[p][pos[p] + 1] == v + 1;
-            int fl = 0, sl = slot_of[p];
-            if (sl < 0) { // a run starts here
-              fl |= 1;
-              if (next_too)
-                for (int c = 0; c < 4; ++c)
-                  if (!slot_busy[c]) { sl = c; slot_busy[c] = true; break; }
-            }
-            const bool carry_out = next_too && sl >= 0;
-            if (!carry_out) {
-              fl |= 2;
-              if (!par_seen[p]) fl |= 4;
-              par_seen[p] = 1;
-              if (sl >= 0) slot_busy[sl] = false;
-              slot_of[p] = -1;
-            } else {
-              slot_of[p] = sl;
-            }
-            pl[4 + n_ent] = p;
-            pl[4 + 4 + n_ent] = par_gas[p] | (std::max(sl, 0) << 8) | (fl << 16);
-            ++n_ent;
-            ++pos[p];
-          }
-          pl[3] = n_ent;
+          pl[3] = runs.step(v, touch, par_gas, pl + 4, pl + 8);
+          fits = pl[3] >= 0;
         }
       }
       if (!fits) { // a shell's two segments touch more than four parameters between them: one ray per thread
@@ -3131,52 +3193,33 @@ int limb_adjoint(const double *abs_c, const double *emi_c, const double *dabs, c
         }
     }
   }
-  static thread_local Stager s_ring[4];
-  static thread_local unsigned s_next = 0;
-  Stager &sg = s_ring[s_next++ & 3];
-  auto al = [](size_t v) { return (v + 15) / 16 * 16; };
-  const size_t b_plan = sizeof(int) * plan.seg.size(), o_zo = al(b_plan);
-  const size_t o_zr = al(o_zo + sizeof(int) * plan.zero_off.size());
-  const size_t o_sc = al(o_zr + sizeof(int) * std::max<size_t>(plan.zero_row.size(), 1));
-  const size_t o_fp = al(o_sc + sizeof(int) * std::max<size_t>(sched.size(), 1));
-  const size_t in_bytes = al(o_fp + sizeof(int) * std::max<size_t>(fplan.size(), 1));
-  rc = sg.prepare(in_bytes + std::max(adj_prog_bytes(n_seg), fold_rec_bytes(n_frec)));
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_plan = pk.copy(plan.seg.data(), plan.seg.size()), p_zo = pk.copy(plan.zero_off.data(), plan.zero_off.size());
+  const auto p_zr = pk.copy(plan.zero_row.data(), plan.zero_row.size(), 1), p_sc = pk.copy(sched.data(), sched.size(), 1);
+  const auto p_fp = pk.copy(fplan.data(), fplan.size(), 1);
+  pk.tail(std::max(adj_prog_bytes(n_seg), fold_rec_bytes(n_frec))); // the packed records of the kernel that runs
+  rc = pk.stage(st);
   if (rc) return rc;
-  char *h = sg.host<char>();
-  std::memcpy(h, plan.seg.data(), b_plan);
-  std::memcpy(h + o_zo, plan.zero_off.data(), sizeof(int) * plan.zero_off.size());
-  if (!plan.zero_row.empty()) std::memcpy(h + o_zr, plan.zero_row.data(), sizeof(int) * plan.zero_row.size());
-  if (!sched.empty()) std::memcpy(h + o_sc, sched.data(), sizeof(int) * sched.size());
-  if (!fplan.empty()) std::memcpy(h + o_fp, fplan.data(), sizeof(int) * fplan.size());
-  rc = sg.push_early(in_bytes, st);
-  if (rc) return rc;
-  char *d = sg.d.as<char>();
   if (n_fvis > 0) {
-    FoldRec *frec = reinterpret_cast<FoldRec *>(d + in_bytes);
-    LAUNCHCHK(launch_fold_pack(reinterpret_cast<const int *>(d + o_fp), D.col, los->n_gas, n_seg, n_frec, frec, st));
+    FoldRec *frec = pk.dev_tail<FoldRec>();
+    LAUNCHCHK(launch_fold_pack(pk.dev(p_fp), D.col, los->n_gas, n_seg, n_frec, frec, st));
     LAUNCHCHK(launch_limb_adjoint_fold(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, n_jrows, two_rows ? 1 : 0, nr, frec,
-                                       reinterpret_cast<const int *>(d + o_zo), reinterpret_cast<const int *>(d + o_zr), n_par,
-                                       limb_opts(los, D.n_seg), n_fvis, rad, jac_layer, jac_par, st));
-    rc = sg.mark(st);
-    if (rc) return rc;
-    *done = 1;
-    return D.slot->mark(st);
+                                       pk.dev(p_zo), pk.dev(p_zr), n_par, limb_opts(los, D.n_seg), n_fvis, rad, jac_layer,
+                                       jac_par, st));
+  } else {
+    SegProg *prog = pk.dev_tail<SegProg>();
+    LAUNCHCHK(launch_adj_pack(pk.dev(p_plan), D.col, los->n_gas, n_seg, prog, st));
+    if (n_visits > 0)
+      LAUNCHCHK(launch_limb_adjoint_sync(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, n_jrows, nr, prog, pk.dev(p_zo),
+                                         pk.dev(p_zr), n_par, limb_opts(los, D.n_seg), pk.dev(p_sc), n_visits, rad, jac_layer,
+                                         jac_par, st));
+    else
+      LAUNCHCHK(launch_limb_adjoint(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, n_jrows, los->n_rays, D.seg_off, prog,
+                                    pk.dev(p_zo), pk.dev(p_zr), n_par, limb_opts(los, D.n_seg), rad, jac_layer, jac_par, st));
   }
-  SegProg *prog = reinterpret_cast<SegProg *>(d + in_bytes);
-  LAUNCHCHK(launch_adj_pack(reinterpret_cast<const int *>(d), D.col, los->n_gas, n_seg, prog, st));
-  if (n_visits > 0)
-    LAUNCHCHK(launch_limb_adjoint_sync(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, n_jrows, nr, prog,
-                                       reinterpret_cast<const int *>(d + o_zo), reinterpret_cast<const int *>(d + o_zr), n_par,
-                                       limb_opts(los, D.n_seg), reinterpret_cast<const int *>(d + o_sc), n_visits, rad,
-                                       jac_layer, jac_par, st));
-  else
-  LAUNCHCHK(launch_limb_adjoint(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, n_jrows, los->n_rays, D.seg_off, prog,
-                                reinterpret_cast<const int *>(d + o_zo), reinterpret_cast<const int *>(d + o_zr), n_par,
-                                limb_opts(los, D.n_seg), rad, jac_layer, jac_par, st));
-  rc = sg.mark(st);
-  if (rc) return rc;
   *done = 1;
-  return D.slot->mark(st);
+  return mark_both(pk.slot(), *D.slot, st);
 }
 
 } // namespace
@@ -3187,50 +3230,54 @@ int sr_limb_rays_jacobians_dev(const double *abs_c, const double *emi_c, const d
                                int n_layers, int64_t n_pts, const sr_los_desc *los, const int32_t *seg_jac_row,
                                int n_jac_rows, int n_par, const int32_t *par_gas, const double *par_w, double *rad,
                                double *jac_layer, double *jac_par, void *stream) {
-  if (!abs_c || !emi_c || n_layers <= 0 || n_pts <= 0 || n_par < 0) return SR_ERR_ARG;
-  if (seg_jac_row && n_jac_rows <= 0) return SR_ERR_ARG;
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, n_par >= 0 && !(seg_jac_row && n_jac_rows <= 0));
+  if (rc) return rc;
   const bool want_layer = jac_layer != nullptr, want_par = n_par > 0;
   if (want_layer != (dabs != nullptr && demi != nullptr) || (want_par && (!jac_par || !par_gas || !par_w))) return SR_ERR_ARG;
-  if (!want_layer && !want_par) return SR_ERR_ARG;
-  if (!rad && los && los->init_mode == 1) { // the initial intensity would be read from rad (a NULL read on the device)
+  if ((!want_layer && !want_par) || !los) return SR_ERR_ARG;
+  if (!rad && los->init_mode == 1) { // the initial intensity would be read from rad (a NULL read on the device)
     g_err = "sr_limb_rays_jacobians_dev: init_mode 1 reads the initial intensity from rad, which is NULL";
     return SR_ERR_ARG;
   }
-  if (want_layer && los && los->init_mode == 1) {
-    g_err = "per-layer Jacobians: init_mode 1 (intensity read from a buffer) is not supported, use 0 or 2";
-    return SR_ERR_UNSUPPORTED;
-  }
-  if (want_par && los)
-    for (int p = 0; p < n_par; ++p)
-      if (par_gas[p] < 0 || par_gas[p] >= los->n_gas) return SR_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int done = 0;
-  if (g_jac_layer_forward.load() != 1) {
-    const int rc = limb_adjoint(abs_c, emi_c, dabs, demi, n_layers, n_pts, los, seg_jac_row, n_jac_rows, n_par, par_gas,
-                                par_w, rad, jac_layer, jac_par, st, &done);
-    if (rc || done) return rc;
-  }
-  // forward-sensitivity kernels, one call per kind (a segment touching more than four parameters, or asked for)
-  if (seg_jac_row && want_layer) {
+  if (want_layer) rc = refuse_init_mode_1(los, "sr_limb_rays_jacobians_dev (per-layer Jacobians)", SR_ERR_UNSUPPORTED);
+  if (rc) return rc;
+  for (int p = 0; p < n_par; ++p)
+    if (par_gas[p] < 0 || par_gas[p] >= los->n_gas) return SR_ERR_ARG;
+  const bool one_pass = g_jac_layer_forward.load() != 1;
+  const auto needs_one_pass = [] {
     g_err = "sr_limb_rays_jacobians_dev: Jacobian rows other than the coefficient rows need the one-pass kernel "
             "(sr_set_jac_layer_mode(0) and at most four column parameters per segment)";
     return SR_ERR_UNSUPPORTED;
+  };
+  if (!one_pass && seg_jac_row && want_layer) return needs_one_pass();
+  LosShape shape;
+  rc = check_los(los, n_layers, &shape);
+  if (rc) return rc;
+  if (seg_jac_row && one_pass)
+    for (int q = 0; q < shape.n_seg; ++q)
+      if (seg_jac_row[q] < 0 || seg_jac_row[q] >= n_jac_rows) return SR_ERR_ARG; // would write out of the Jacobian
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int done = 0;
+  if (one_pass) {
+    rc = limb_adjoint(abs_c, emi_c, dabs, demi, n_layers, n_pts, los, shape, seg_jac_row, n_jac_rows, n_par, par_gas, par_w, rad,
+                      jac_layer, jac_par, st, &done);
+    if (rc || done) return rc;
   }
+  // forward-sensitivity kernels, one call per kind (a segment touching more than four parameters, or asked for)
+  if (seg_jac_row && want_layer) return needs_one_pass();
   if (want_par) {
     double *rad_out = rad;
     static thread_local DevBuf scratch_rad; // the forward kernel writes the radiances too: somewhere, if not wanted
     if (!rad_out) {
-      if (los && los->init_mode == 1) return SR_ERR_ARG; // an initial intensity is read from rad
       const int rc0 = scratch_rad.ensure(sizeof(double) * (size_t)los->n_rays * (size_t)n_pts);
       if (rc0) return rc0;
       rad_out = scratch_rad.as<double>();
     }
-    const int rc = sr_limb_rays_jac_dev(abs_c, emi_c, n_layers, n_pts, los, n_par, par_gas, par_w, rad_out, jac_par, stream);
+    rc = sr_limb_rays_jac_dev(abs_c, emi_c, n_layers, n_pts, los, n_par, par_gas, par_w, rad_out, jac_par, stream);
     if (rc) return rc;
   }
   if (want_layer) {
-    const int rc = sr_limb_rays_jac_layer_dev(abs_c, emi_c, dabs, demi, n_layers, n_pts, los, jac_layer, stream);
+    rc = sr_limb_rays_jac_layer_dev(abs_c, emi_c, dabs, demi, n_layers, n_pts, los, jac_layer, stream);
     if (rc) return rc;
     if (rad && !want_par) return sr_limb_rays_dev(abs_c, emi_c, n_layers, n_pts, los, rad, stream);
   }
@@ -3240,19 +3287,21 @@ int sr_limb_rays_jacobians_dev(const double *abs_c, const double *emi_c, const d
 int sr_limb_rays_jac_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
                          const sr_los_desc *los, int n_par, const int32_t *par_gas, const double *par_w, double *rad,
                          double *jac, void *stream) {
-  if (!abs_c || !emi_c || !rad || !jac || n_layers <= 0 || n_pts <= 0 || n_par <= 0) return SR_ERR_ARG;
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
+  LosShape shape;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, rad && jac && n_par > 0);
+  if (!rc) rc = check_los_par(los, n_layers, n_par, par_gas, par_w, &shape);
+  if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // many parameters: one pass per ray (the forward kernel repeats the recursion per 16 parameters); rad0 given
   // (init_mode 1) is read by both kernels before they write
-  if (n_par > 8 && g_jac_layer_forward.load() != 1 && par_gas && par_w) {
+  if (n_par > 8 && g_jac_layer_forward.load() != 1) {
     int done = 0;
-    const int rc = limb_adjoint(abs_c, emi_c, nullptr, nullptr, n_layers, n_pts, los, nullptr, 0, n_par, par_gas, par_w,
-                                rad, nullptr, jac, st, &done);
+    rc = limb_adjoint(abs_c, emi_c, nullptr, nullptr, n_layers, n_pts, los, shape, nullptr, 0, n_par, par_gas, par_w, rad, nullptr,
+                      jac, st, &done);
     if (rc || done) return rc;
   }
   LosDev D;
-  int rc = stage_los(los, n_layers, n_par, par_gas, par_w, st, &D);
+  rc = stage_los(los, shape, n_par, par_gas, par_w, st, &D);
   if (rc) return rc;
   // Few parameters, 1-D limb / slant / nadir rays: the folded recursion with an accumulator per parameter
   // (sr_limb_fold_sens_lds_kernel) instead of the path-order forward sensitivities (which repeat the recursion per four parameters)
@@ -3263,9 +3312,7 @@ int sr_limb_rays_jac_dev(const double *abs_c, const double *emi_c, int n_layers,
     if (F.n_rec > 0) {
       LAUNCHCHK(launch_fold_dense(F.plan, D.col, par_gas, n_par, D.n_seg, F.n_rec, F.rec, abs_c, emi_c, (int)n_pts, n_layers,
                                   los->n_rays, F.n_vis, limb_opts(los, D.n_seg), rad, jac, st));
-      rc = F.slot->mark(st);
-      if (rc) return rc;
-      return D.slot->mark(st);
+      return mark_both(*F.slot, *D.slot, st);
     }
   }
   LAUNCHCHK(launch_limb_jac(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col,
@@ -3276,23 +3323,22 @@ int sr_limb_rays_jac_dev(const double *abs_c, const double *emi_c, int n_layers,
 
 int sr_limb_rays_jac_layer_dev(const double *abs_c, const double *emi_c, const double *dabs, const double *demi,
                                int n_layers, int64_t n_pts, const sr_los_desc *los, double *jac, void *stream) {
-  if (!abs_c || !emi_c || !dabs || !demi || !jac || n_layers <= 0 || n_pts <= 0) return SR_ERR_ARG;
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
-  if (los && los->init_mode == 1) {
-    g_err = "sr_limb_rays_jac_layer_dev: init_mode 1 (intensity read from a buffer) is not supported, use 0 or 2";
-    return SR_ERR_UNSUPPORTED;
-  }
+  LosShape shape;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, dabs && demi && jac);
+  if (!rc && los) rc = refuse_init_mode_1(los, "sr_limb_rays_jac_layer_dev", SR_ERR_UNSUPPORTED);
+  if (!rc) rc = check_los(los, n_layers, &shape);
+  if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (g_jac_layer_forward.load() != 1 && n_layers > 8) {
     int done = 0;
-    const int rc = limb_adjoint(abs_c, emi_c, dabs, demi, n_layers, n_pts, los, nullptr, 0, 0, nullptr, nullptr, nullptr,
-                                jac, nullptr, st, &done);
+    rc = limb_adjoint(abs_c, emi_c, dabs, demi, n_layers, n_pts, los, shape, nullptr, 0, 0, nullptr, nullptr, nullptr, jac, nullptr,
+                      st, &done);
     if (rc || done) return rc;
   }
   LosDev D;
-  int rc = stage_los(los, n_layers, 0, nullptr, nullptr, st, &D);
+  rc = stage_los(los, shape, 0, nullptr, nullptr, st, &D);
   if (rc) return rc;
-  LAUNCHCHK(launch_limb_jac_layer(1, abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer,
+  LAUNCHCHK(launch_limb_jac_layer(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer,
                                   D.col, limb_opts(los, D.n_seg), jac, st));
   return D.slot->mark(st);
 }
@@ -3303,28 +3349,20 @@ int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_l
                                double *rad, double *jac, void *stream) {
   // everything is checked here, before the first copy or launch (the LOS too: stage_los would only find out after this
   // call's own staging)
-  if (!abs_c || !emi_c || !tab || !coef_row || !par_level || !par_c || !jac) return SR_ERR_ARG;
-  if (n_layers <= 0 || n_pts <= 0 || n_levels <= 0 || n_tab_rows <= 0 || n_par < 1) return SR_ERR_ARG;
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
-  int n_seg = 0, n_pt = 0;
-  int rc = check_los(los, n_layers, &n_seg, &n_pt);
+  LosShape shape;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts,
+                           tab && coef_row && par_level && par_c && jac && n_levels > 0 && n_tab_rows > 0 && n_par >= 1);
+  if (!rc) rc = check_los(los, n_layers, &shape);
   if (rc) return rc;
   if (gas < 0 || gas >= los->n_gas) return SR_ERR_ARG;
-  if (los->init_mode == 1) {
-    g_err = "sr_limb_rays_jac_level_dev: init_mode 1 (intensity read from a buffer) is not supported, use 0 or 2";
-    return SR_ERR_ARG;
-  }
-  for (int r = 0; r < n_layers; ++r)
-    if (coef_row[r] < 0 || coef_row[r] >= n_tab_rows) return SR_ERR_ARG; // would read out of the tables
+  if ((rc = refuse_init_mode_1(los, "sr_limb_rays_jac_level_dev", SR_ERR_ARG))) return rc;
+  if (!coef_rows_in_range(coef_row, n_layers, n_tab_rows)) return SR_ERR_ARG;
   for (int p = 0; p < n_par; ++p)
     if (par_level[p] < 0 || par_level[p] >= n_levels) return SR_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // parameters in level order (stable), NP per block: a block then touches few levels, and a row's entries come in
-  // level order without a sort of their own
+  // parameters in level order, NP per block: a row's entries come in level order without a sort of their own
   const int np = level_jac_np(n_par), n_blocks = (n_par + np - 1) / np;
-  std::vector<int> order(n_par);
-  for (int p = 0; p < n_par; ++p) order[p] = p;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return par_level[a] < par_level[b]; });
+  const std::vector<int> order = order_by_level(n_par, par_level);
   std::vector<int> ent_off((size_t)n_blocks * (n_layers + 1)), slot_par((size_t)n_blocks * np, -1);
   std::vector<LevelEnt> ent;
   for (int b = 0; b < n_blocks; ++b) {
@@ -3339,33 +3377,20 @@ int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_l
     }
     ent_off[(size_t)b * (n_layers + 1) + n_layers] = (int)ent.size();
   }
-  static thread_local Stager s_ring[4];
-  static thread_local unsigned s_next = 0;
-  Stager &sg = s_ring[s_next++ & 3];
-  auto al = [](size_t v) { return (v + 15) / 16 * 16; };
-  const size_t b_ent = sizeof(LevelEnt) * ent.size(), o_row = al(b_ent);
-  const size_t o_off = al(o_row + sizeof(int) * (size_t)n_layers), o_slot = al(o_off + sizeof(int) * ent_off.size());
-  const size_t total = al(o_slot + sizeof(int) * slot_par.size());
-  rc = sg.prepare(total);
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_ent = pk.copy(ent.data(), ent.size());
+  const auto p_row = pk.copy(coef_row, (size_t)n_layers), p_off = pk.copy(ent_off.data(), ent_off.size());
+  const auto p_slot = pk.copy(slot_par.data(), slot_par.size());
+  rc = pk.stage(st);
   if (rc) return rc;
-  char *h = sg.host<char>();
-  if (b_ent) std::memcpy(h, ent.data(), b_ent);
-  std::memcpy(h + o_row, coef_row, sizeof(int) * (size_t)n_layers);
-  std::memcpy(h + o_off, ent_off.data(), sizeof(int) * ent_off.size());
-  std::memcpy(h + o_slot, slot_par.data(), sizeof(int) * slot_par.size());
-  rc = sg.push_early(total, st);
-  if (rc) return rc;
-  const char *d = sg.d.as<char>();
   LosDev D;
-  rc = stage_los(los, n_layers, 0, nullptr, nullptr, st, &D);
+  rc = stage_los(los, shape, 0, nullptr, nullptr, st, &D);
   if (rc) return rc;
   LAUNCHCHK(launch_limb_jac_level(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col,
-                                  limb_opts(los, D.n_seg), gas, tab, n_tab_rows, reinterpret_cast<const int *>(d + o_row),
-                                  n_blocks, reinterpret_cast<const int *>(d + o_off), reinterpret_cast<const LevelEnt *>(d),
-                                  reinterpret_cast<const int *>(d + o_slot), n_par, rad, jac, st));
-  rc = sg.mark(st);
-  if (rc) return rc;
-  return D.slot->mark(st);
+                                  limb_opts(los, D.n_seg), gas, tab, n_tab_rows, pk.dev(p_row), n_blocks, pk.dev(p_off),
+                                  pk.dev(p_ent), pk.dev(p_slot), n_par, rad, jac, st));
+  return mark_both(pk.slot(), *D.slot, st);
 }
 
 int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
@@ -3373,17 +3398,13 @@ int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layer
                            const int32_t *part_gas, const int32_t *part_level, const double *part_c, double *rad,
                            double *parts, void *stream) {
   // everything is checked here, before the first copy or launch (the LOS too, as sr_limb_rays_jac_level_dev does)
-  if (!abs_c || !emi_c || !part_gas || !part_level || !parts) return SR_ERR_ARG;
-  if (n_layers <= 0 || n_pts <= 0 || n_part < 1) return SR_ERR_ARG;
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
-  if (tab && n_levels > 0 && n_tab_rows > 0 && 2 * (int64_t)n_levels * n_tab_rows > INT_MAX) return SR_ERR_LIMIT; // 32-bit row numbers
-  int n_seg = 0, n_pt = 0;
-  int rc = check_los(los, n_layers, &n_seg, &n_pt);
+  LosShape shape;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, part_gas && part_level && parts && n_part >= 1);
   if (rc) return rc;
-  if (los->init_mode == 1) {
-    g_err = "sr_limb_rays_parts_dev: init_mode 1 (intensity read from a buffer) is not supported, use 0 or 2";
-    return SR_ERR_ARG;
-  }
+  if (tab && n_levels > 0 && n_tab_rows > 0 && 2 * (int64_t)n_levels * n_tab_rows > INT_MAX) return SR_ERR_LIMIT; // 32-bit row numbers
+  rc = check_los(los, n_layers, &shape);
+  if (!rc) rc = refuse_init_mode_1(los, "sr_limb_rays_parts_dev", SR_ERR_ARG);
+  if (rc) return rc;
   bool any_level = false;
   for (int k = 0; k < n_part; ++k) {
     if (part_gas[k] < 0 || part_gas[k] >= los->n_gas || part_level[k] < -1) return SR_ERR_ARG;
@@ -3395,16 +3416,12 @@ int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layer
     }
     if (!tab || !coef_row || !part_c || part_level[k] >= n_levels || n_tab_rows <= 0) return SR_ERR_ARG;
   }
-  if (any_level)
-    for (int r = 0; r < n_layers; ++r)
-      if (coef_row[r] < 0 || coef_row[r] >= n_tab_rows) return SR_ERR_ARG; // would read out of the tables
+  if (any_level && !coef_rows_in_range(coef_row, n_layers, n_tab_rows)) return SR_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // the parts in level order (stable; gas parts first, the background last), NP slots per block: the slots of one
   // level are neighbours, so a row's table value is loaded once per distinct level
   const int n_slot = n_part + 1, np = limb_parts_np(n_part), n_blocks = (n_slot + np - 1) / np;
-  std::vector<int> order(n_part);
-  for (int k = 0; k < n_part; ++k) order[k] = k;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return std::max(part_level[a], -1) < std::max(part_level[b], -1); });
+  std::vector<int> order = order_by_level(n_part, part_level);
   order.push_back(n_part);
   std::vector<int> slot_level((size_t)n_blocks * np, kPartNoSource), slot_part((size_t)n_blocks * np, -1);
   std::vector<unsigned> words((size_t)n_blocks * n_layers, 0u);
@@ -3429,36 +3446,21 @@ int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layer
       w |= 1u << q | (passed_on ? 0u : 1u << (16 + q));
     }
   }
-  static thread_local Stager s_ring[4];
-  static thread_local unsigned s_next = 0;
-  Stager &sg = s_ring[s_next++ & 3];
-  auto al = [](size_t v) { return (v + 15) / 16 * 16; };
-  const size_t b_cc = sizeof(double) * cc.size(), o_word = al(b_cc), o_row = al(o_word + sizeof(unsigned) * words.size());
-  const size_t o_lev = al(o_row + sizeof(int) * (size_t)n_layers), o_slot = al(o_lev + sizeof(int) * slot_level.size());
-  const size_t total = al(o_slot + sizeof(int) * slot_part.size());
-  rc = sg.prepare(total);
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_cc = pk.copy(cc.data(), cc.size());
+  const auto p_word = pk.copy(words.data(), words.size());
+  const auto p_row = any_level ? pk.copy(coef_row, (size_t)n_layers) : pk.zeros<int32_t>((size_t)n_layers);
+  const auto p_lev = pk.copy(slot_level.data(), slot_level.size()), p_slot = pk.copy(slot_part.data(), slot_part.size());
+  rc = pk.stage(st);
   if (rc) return rc;
-  char *h = sg.host<char>();
-  std::memcpy(h, cc.data(), b_cc);
-  std::memcpy(h + o_word, words.data(), sizeof(unsigned) * words.size());
-  if (any_level) std::memcpy(h + o_row, coef_row, sizeof(int) * (size_t)n_layers);
-  else std::memset(h + o_row, 0, sizeof(int) * (size_t)n_layers);
-  std::memcpy(h + o_lev, slot_level.data(), sizeof(int) * slot_level.size());
-  std::memcpy(h + o_slot, slot_part.data(), sizeof(int) * slot_part.size());
-  rc = sg.push_early(total, st);
-  if (rc) return rc;
-  const char *d = sg.d.as<char>();
   LosDev D;
-  rc = stage_los(los, n_layers, 0, nullptr, nullptr, st, &D);
+  rc = stage_los(los, shape, 0, nullptr, nullptr, st, &D);
   if (rc) return rc;
   LAUNCHCHK(launch_limb_parts(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col,
-                              limb_opts(los, D.n_seg), any_level ? gas : 0, tab,
-                              reinterpret_cast<const int *>(d + o_row), n_blocks, reinterpret_cast<const unsigned *>(d + o_word),
-                              reinterpret_cast<const double *>(d), reinterpret_cast<const int *>(d + o_lev),
-                              reinterpret_cast<const int *>(d + o_slot), n_part, rad, parts, st));
-  rc = sg.mark(st);
-  if (rc) return rc;
-  return D.slot->mark(st);
+                              limb_opts(los, D.n_seg), any_level ? gas : 0, tab, pk.dev(p_row), n_blocks, pk.dev(p_word),
+                              pk.dev(p_cc), pk.dev(p_lev), pk.dev(p_slot), n_part, rad, parts, st));
+  return mark_both(pk.slot(), *D.slot, st);
 }
 
 // ------------------------------------------------------------------------
@@ -3477,24 +3479,15 @@ int sr_lut_interp_dev(const double *g_tab, int n_pt, int64_t n_pts, int n_steps,
     }
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  static thread_local Stager s_ring[4];
-  static thread_local unsigned s_next = 0;
-  Stager &sg = s_ring[s_next++ & 3];
-  const size_t b_w = sizeof(double) * 4 * (size_t)n_steps, b_p = sizeof(double) * (size_t)n_steps;
-  const size_t b_i = sizeof(int) * 4 * (size_t)n_steps;
-  int rc = sg.prepare(b_w + b_p + b_i);
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_wgt = pk.copy(wgt4, 4 * (size_t)n_steps);
+  const auto p_pop = pop ? pk.copy(pop, (size_t)n_steps) : pk.zeros<double>((size_t)n_steps);
+  const auto p_idx = pk.copy(idx4, 4 * (size_t)n_steps);
+  const int rc = pk.stage(st);
   if (rc) return rc;
-  char *h = sg.host<char>();
-  std::memcpy(h, wgt4, b_w);
-  if (pop) std::memcpy(h + b_w, pop, b_p); else std::memset(h + b_w, 0, b_p);
-  std::memcpy(h + b_w + b_p, idx4, b_i);
-  rc = sg.push_early(b_w + b_p + b_i, st);
-  if (rc) return rc;
-  char *d = sg.d.as<char>();
-  LAUNCHCHK(launch_lut(combine, g_tab, n_pt, (int)n_pts, n_steps, reinterpret_cast<const int *>(d + b_w + b_p),
-                       reinterpret_cast<const double *>(d), reinterpret_cast<const double *>(d + b_w), out_a, out_e,
-                       st));
-  return sg.mark(st);
+  LAUNCHCHK(launch_lut(combine, g_tab, n_pt, (int)n_pts, n_steps, pk.dev(p_idx), pk.dev(p_wgt), pk.dev(p_pop), out_a, out_e, st));
+  return pk.slot().mark(st);
 }
 
 // ------------------------------------------------------------------------

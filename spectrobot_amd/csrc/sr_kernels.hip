@@ -3104,6 +3104,26 @@ __device__ inline bool limb_block(int n_pb, int n_rays, int &pb, int &ray) {
 }
 __host__ inline unsigned limb_grid(int n_pb, int n_rays) { return (unsigned)(((n_pb + 7) / 8) * 8) * (unsigned)n_rays; }
 
+// The limb launchers' dispatch on the kernels' compile-time parameters.  by_ngas: f(integral_constant<int, NG>) for a
+// batch of n_gas gases, NG = 1..4 (any other count takes the general NG = 4).
+template <class F>
+inline void by_ngas(int n_gas, F &&f) {
+  switch (n_gas) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+// by_jac_kinds: f(bool_constant<per-layer>, bool_constant<per-parameter>) for the Jacobians a one-pass call asks for.
+// (false, false) does not exist as a kernel: a call without per-layer Jacobians is a per-parameter one.
+template <class F>
+inline void by_jac_kinds(bool layer, bool par, F &&f) {
+  if (layer && par) f(std::true_type{}, std::true_type{});
+  else if (layer) f(std::true_type{}, std::false_type{});
+  else f(std::false_type{}, std::true_type{});
+}
+
 template <int NG>
 __global__ __launch_bounds__(256) void sr_limb_kernel(const double *__restrict__ abs_c, const double *__restrict__ emi_c,
                                                       int n_pts, int n_layers, const int *__restrict__ seg_off,
@@ -3870,18 +3890,13 @@ int launch_limb_adjoint_sync(const double *abs_c, const double *emi_c, const dou
                              double *jac_layer, double *jac_par, hipStream_t st) {
   if (n_pts <= 0 || n_rays <= 0 || n_visits <= 0) return 0;
   const dim3 grid((n_pts + 255) / 256, (n_rays + kAdjSyncRays - 1) / kAdjSyncRays);
-#define SR_AS(NG, L, P) hipLaunchKernelGGL((sr_limb_adjoint_sync_kernel<NG, L, P, kAdjSyncRays>), grid, dim3(256), 0, st, abs_c, emi_c, \
-                                           dabs, demi, n_pts, n_layers, n_jrows, prog, zero_off, zero_row, n_par, o, sched, n_visits,   \
-                                           n_rays, rad, jac_layer, jac_par)
-#define SR_AS3(NG)                                                     \
-  do {                                                                 \
-    if (jac_layer && jac_par) SR_AS(NG, true, true);                   \
-    else if (jac_layer) SR_AS(NG, true, false);                        \
-    else SR_AS(NG, false, true);                                       \
-  } while (0)
-  switch (o.n_gas) { case 1: SR_AS3(1); break; case 2: SR_AS3(2); break; case 3: SR_AS3(3); break; default: SR_AS3(4); break; }
-#undef SR_AS3
-#undef SR_AS
+  by_ngas(o.n_gas, [&](auto ng) {
+    by_jac_kinds(jac_layer, jac_par, [&](auto lay, auto par) {
+      hipLaunchKernelGGL((sr_limb_adjoint_sync_kernel<decltype(ng)::value, decltype(lay)::value, decltype(par)::value, kAdjSyncRays>),
+                         grid, dim3(256), 0, st, abs_c, emi_c, dabs, demi, n_pts, n_layers, n_jrows, prog, zero_off, zero_row, n_par,
+                         o, sched, n_visits, n_rays, rad, jac_layer, jac_par);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -4561,10 +4576,10 @@ int launch_fold_fwd(const int *plan, const double *col, int n_seg, int n_rec, Fo
     hipLaunchKernelGGL(sr_fold_dense_pack_kernel, dim3((n_rec + 63) / 64), dim3(64), 0, st, plan, col, o.n_gas, 0, n_seg, n_rec, rec);
   if (n_pts <= 0) return (int)hipGetLastError(); // (packing only)
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays));
-#define SR_FF(NG) hipLaunchKernelGGL(sr_limb_fold_fwd_kernel<NG>, grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, rec, o, n_visits, \
-                                     n_rays, rad)
-  switch (o.n_gas) { case 1: SR_FF(1); break; case 2: SR_FF(2); break; case 3: SR_FF(3); break; default: SR_FF(4); break; }
-#undef SR_FF
+  by_ngas(o.n_gas, [&](auto ng) {
+    hipLaunchKernelGGL(sr_limb_fold_fwd_kernel<decltype(ng)::value>, grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, rec, o,
+                       n_visits, n_rays, rad);
+  });
   return (int)hipGetLastError();
 }
 
@@ -4583,17 +4598,14 @@ int launch_fold_dense(const int *plan, const double *col, const int *par_gas_hos
     const LowresScratch L = lowres_layout(const_cast<void *>(lowres_scratch), n_pts, n_bands);
     bd = FoldBands{L.Wt, L.range, L.part, n_bands};
   }
-#define SR_FD(NG)                                                                                                                  \
-  do {                                                                                                                             \
-    if (lowres_scratch)                                                                                                            \
-      hipLaunchKernelGGL((sr_limb_fold_sens_lds_kernel<NG, true>), grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, rec, n_par, \
-                         pg, o, n_visits, n_rays, rad, jac_par, bd);                                                               \
-    else                                                                                                                           \
-      hipLaunchKernelGGL((sr_limb_fold_sens_lds_kernel<NG, false>), grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, rec, n_par, \
-                         pg, o, n_visits, n_rays, rad, jac_par, bd);                                                               \
-  } while (0)
-  switch (o.n_gas) { case 1: SR_FD(1); break; case 2: SR_FD(2); break; case 3: SR_FD(3); break; default: SR_FD(4); break; }
-#undef SR_FD
+  by_ngas(o.n_gas, [&](auto ng) {
+    auto launch = [&](auto bands) {
+      hipLaunchKernelGGL((sr_limb_fold_sens_lds_kernel<decltype(ng)::value, decltype(bands)::value>), grid, dim3(256), 0, st, abs_c,
+                         emi_c, n_pts, n_layers, rec, n_par, pg, o, n_visits, n_rays, rad, jac_par, bd);
+    };
+    if (lowres_scratch) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
   return (int)hipGetLastError();
 }
 
@@ -4617,18 +4629,13 @@ int launch_limb_adjoint_fold(const double *abs_c, const double *emi_c, const dou
 #else
     const dim3 grid2((n_pts + 255) / 256, n_rays);
 #endif
-#define SR_AF2(NG, L, P) hipLaunchKernelGGL((sr_limb_adjoint_fold_kernel<NG, L, P, 1, true>), grid2, dim3(256), 0, st, abs_c, emi_c, \
-                                            dabs, demi, n_pts, n_layers, n_jrows, rec, zero_off, zero_row, n_par, o, n_visits, n_rays, \
-                                            rad, jac_layer, jac_par)
-#define SR_AF23(NG)                                                    \
-  do {                                                                 \
-    if (jac_layer && jac_par) SR_AF2(NG, true, true);                  \
-    else if (jac_layer) SR_AF2(NG, true, false);                       \
-    else SR_AF2(NG, false, true);                                      \
-  } while (0)
-    switch (o.n_gas) { case 1: SR_AF23(1); break; case 2: SR_AF23(2); break; case 3: SR_AF23(3); break; default: SR_AF23(4); break; }
-#undef SR_AF23
-#undef SR_AF2
+    by_ngas(o.n_gas, [&](auto ng) {
+      by_jac_kinds(jac_layer, jac_par, [&](auto lay, auto par) {
+        hipLaunchKernelGGL((sr_limb_adjoint_fold_kernel<decltype(ng)::value, decltype(lay)::value, decltype(par)::value, 1, true>),
+                           grid2, dim3(256), 0, st, abs_c, emi_c, dabs, demi, n_pts, n_layers, n_jrows, rec, zero_off, zero_row,
+                           n_par, o, n_visits, n_rays, rad, jac_layer, jac_par);
+      });
+    });
     return (int)hipGetLastError();
   }
 #if SR_FOLD_XCD
@@ -4636,18 +4643,13 @@ int launch_limb_adjoint_fold(const double *abs_c, const double *emi_c, const dou
 #else
   const dim3 grid((n_pts + 255) / 256, (n_rays + kAdjFoldRays - 1) / kAdjFoldRays);
 #endif
-#define SR_AF(NG, L, P) hipLaunchKernelGGL((sr_limb_adjoint_fold_kernel<NG, L, P, kAdjFoldRays, false>), grid, dim3(256), 0, st, abs_c, emi_c, \
-                                           dabs, demi, n_pts, n_layers, n_jrows, rec, zero_off, zero_row, n_par, o, n_visits, n_rays, rad, \
-                                           jac_layer, jac_par)
-#define SR_AF3(NG)                                                     \
-  do {                                                                 \
-    if (jac_layer && jac_par) SR_AF(NG, true, true);                   \
-    else if (jac_layer) SR_AF(NG, true, false);                        \
-    else SR_AF(NG, false, true);                                       \
-  } while (0)
-  switch (o.n_gas) { case 1: SR_AF3(1); break; case 2: SR_AF3(2); break; case 3: SR_AF3(3); break; default: SR_AF3(4); break; }
-#undef SR_AF3
-#undef SR_AF
+  by_ngas(o.n_gas, [&](auto ng) {
+    by_jac_kinds(jac_layer, jac_par, [&](auto lay, auto par) {
+      hipLaunchKernelGGL((sr_limb_adjoint_fold_kernel<decltype(ng)::value, decltype(lay)::value, decltype(par)::value, kAdjFoldRays, false>),
+                         grid, dim3(256), 0, st, abs_c, emi_c, dabs, demi, n_pts, n_layers, n_jrows, rec, zero_off, zero_row, n_par,
+                         o, n_visits, n_rays, rad, jac_layer, jac_par);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -4666,22 +4668,15 @@ int launch_limb_adjoint(const double *abs_c, const double *emi_c, const double *
                         double *jac_par, hipStream_t st) {
   if (n_pts <= 0 || n_rays <= 0) return 0;
   const dim3 grid((n_pts + 255) / 256, n_rays);
-#define SR_A(NG, L, P) hipLaunchKernelGGL((sr_limb_adjoint_kernel<NG, L, P>), grid, dim3(256), 0, st, abs_c, emi_c, dabs, demi, \
-                                          n_pts, n_layers, n_jrows, seg_off, prog, zero_off, zero_row, n_par, o, rad, jac_layer, jac_par)
-#define SR_A3(NG)                                                      \
-  do {                                                                 \
-    if (jac_layer && jac_par) SR_A(NG, true, true);                    \
-    else if (jac_layer) SR_A(NG, true, false);                         \
-    else SR_A(NG, false, true);                                        \
-  } while (0)
-  switch (o.n_gas) { case 1: SR_A3(1); break; case 2: SR_A3(2); break; case 3: SR_A3(3); break; default: SR_A3(4); break; }
-#undef SR_A3
-#undef SR_A
+  by_ngas(o.n_gas, [&](auto ng) {
+    by_jac_kinds(jac_layer, jac_par, [&](auto lay, auto par) {
+      hipLaunchKernelGGL((sr_limb_adjoint_kernel<decltype(ng)::value, decltype(lay)::value, decltype(par)::value>), grid, dim3(256), 0,
+                         st, abs_c, emi_c, dabs, demi, n_pts, n_layers, n_jrows, seg_off, prog, zero_off, zero_row, n_par, o, rad,
+                         jac_layer, jac_par);
+    });
+  });
   return (int)hipGetLastError();
 }
-
-#define SR_BY_NGAS(NGV, CALL1, CALL2, CALL3, CALL4) \
-  switch (NGV) { case 1: CALL1; break; case 2: CALL2; break; case 3: CALL3; break; default: CALL4; break; }
 
 int launch_limb(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
                 const int *seg_layer, const double *col, const LimbOpts &o, double *rad, hipStream_t st) {
@@ -4689,17 +4684,17 @@ int launch_limb(const double *abs_c, const double *emi_c, int n_pts, int n_layer
   // fewer than two waves per SIMD: the latency-bound variant (a function of the launch shape only)
   if (limb_launch_is_small(n_pts, n_rays)) {
     const dim3 gs(limb_grid((n_pts + 63) / 64, n_rays));
-#define SR_LS(NG) hipLaunchKernelGGL(sr_limb_split_kernel<NG>, gs, dim3(64 * kLimbParts), 0, st, abs_c, emi_c, n_pts, n_layers, \
-                                     seg_off, seg_layer, col, o, n_rays, rad)
-    SR_BY_NGAS(o.n_gas, SR_LS(1), SR_LS(2), SR_LS(3), SR_LS(4))
-#undef SR_LS
+    by_ngas(o.n_gas, [&](auto ng) {
+      hipLaunchKernelGGL(sr_limb_split_kernel<decltype(ng)::value>, gs, dim3(64 * kLimbParts), 0, st, abs_c, emi_c, n_pts, n_layers,
+                         seg_off, seg_layer, col, o, n_rays, rad);
+    });
     return (int)hipGetLastError();
   }
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays));
-#define SR_L(NG) hipLaunchKernelGGL(sr_limb_kernel<NG>, grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, \
-                                    seg_layer, col, o, n_rays, rad)
-  SR_BY_NGAS(o.n_gas, SR_L(1), SR_L(2), SR_L(3), SR_L(4))
-#undef SR_L
+  by_ngas(o.n_gas, [&](auto ng) {
+    hipLaunchKernelGGL(sr_limb_kernel<decltype(ng)::value>, grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer,
+                       col, o, n_rays, rad);
+  });
   return (int)hipGetLastError();
 }
 
@@ -4710,31 +4705,31 @@ int launch_limb_jac(const double *abs_c, const double *emi_c, int n_pts, int n_l
   // Every block of NP parameters repeats the recursion (exp, expm1, the coefficient loads): with many parameters
   // (configs[3]: one per layer) 16 per thread instead of 4 cut the kernel's instructions 3.4x (160 segments x
   // (60 + NP) per block of NP).
-#define SR_L(NG, NP) hipLaunchKernelGGL((sr_limb_jac_kernel<NG, NP>), dim3((n_pts + 255) / 256, n_rays, (n_par + NP - 1) / NP), \
-                                        dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol,      \
-                                        par_gas, n_par, o, rad, jac)
-  if (n_par > 8) {
-    SR_BY_NGAS(o.n_gas, SR_L(1, 16), SR_L(2, 16), SR_L(3, 16), SR_L(4, 16))
-  } else {
-    SR_BY_NGAS(o.n_gas, SR_L(1, 4), SR_L(2, 4), SR_L(3, 4), SR_L(4, 4))
-  }
-#undef SR_L
+  auto launch = [&](auto np) {
+    by_ngas(o.n_gas, [&](auto ng) {
+      constexpr int NP = decltype(np)::value;
+      hipLaunchKernelGGL((sr_limb_jac_kernel<decltype(ng)::value, NP>), dim3((n_pts + 255) / 256, n_rays, (n_par + NP - 1) / NP),
+                         dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, par_gas, n_par, o, rad, jac);
+    });
+  };
+  if (n_par > 8) launch(std::integral_constant<int, 16>{});
+  else launch(std::integral_constant<int, 4>{});
   return (int)hipGetLastError();
 }
 
-int launch_limb_jac_layer(int forward, const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
+int launch_limb_jac_layer(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
                           int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
                           const LimbOpts &o, double *jac, hipStream_t st) {
   if (n_pts <= 0 || n_rays <= 0 || n_layers <= 0) return 0;
-#define SR_L(NG, NP) hipLaunchKernelGGL((sr_limb_jac_layer_kernel<NG, NP>), dim3((n_pts + 255) / 256, n_rays, (n_layers + NP - 1) / NP), \
-                                        dim3(256), 0, st, abs_c, emi_c, dabs, demi, n_pts, n_layers, seg_off, seg_layer, col, o, jac)
-  (void)forward; // the one-pass formulation is sr_limb_adjoint_kernel (launch_limb_adjoint)
-  if (n_layers > 8) {
-    SR_BY_NGAS(o.n_gas, SR_L(1, 16), SR_L(2, 16), SR_L(3, 16), SR_L(4, 16))
-  } else {
-    SR_BY_NGAS(o.n_gas, SR_L(1, 4), SR_L(2, 4), SR_L(3, 4), SR_L(4, 4))
-  }
-#undef SR_L
+  auto launch = [&](auto np) { // (the one-pass formulation is sr_limb_adjoint_kernel, launch_limb_adjoint)
+    by_ngas(o.n_gas, [&](auto ng) {
+      constexpr int NP = decltype(np)::value;
+      hipLaunchKernelGGL((sr_limb_jac_layer_kernel<decltype(ng)::value, NP>), dim3((n_pts + 255) / 256, n_rays, (n_layers + NP - 1) / NP),
+                         dim3(256), 0, st, abs_c, emi_c, dabs, demi, n_pts, n_layers, seg_off, seg_layer, col, o, jac);
+    });
+  };
+  if (n_layers > 8) launch(std::integral_constant<int, 16>{});
+  else launch(std::integral_constant<int, 4>{});
   return (int)hipGetLastError();
 }
 
@@ -4744,15 +4739,15 @@ int launch_limb_jac_level(const double *abs_c, const double *emi_c, int n_pts, i
                           const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st) {
   if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0) return 0;
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
-#define SR_L(NG, NP) hipLaunchKernelGGL((sr_limb_jac_level_kernel<NG, NP>), grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, \
-                                        seg_off, seg_layer, col, o, n_rays, gas, tab, n_tab_rows, coef_row, ent_off, ent,       \
-                                        slot_par, n_par, rad, jac)
-  if (level_jac_np(n_par) == kLevelJacNPLarge) {
-    SR_BY_NGAS(o.n_gas, SR_L(1, kLevelJacNPLarge), SR_L(2, kLevelJacNPLarge), SR_L(3, kLevelJacNPLarge), SR_L(4, kLevelJacNPLarge))
-  } else {
-    SR_BY_NGAS(o.n_gas, SR_L(1, kLevelJacNPSmall), SR_L(2, kLevelJacNPSmall), SR_L(3, kLevelJacNPSmall), SR_L(4, kLevelJacNPSmall))
-  }
-#undef SR_L
+  auto launch = [&](auto np) {
+    by_ngas(o.n_gas, [&](auto ng) {
+      hipLaunchKernelGGL((sr_limb_jac_level_kernel<decltype(ng)::value, decltype(np)::value>), grid, dim3(256), 0, st, abs_c, emi_c,
+                         n_pts, n_layers, seg_off, seg_layer, col, o, n_rays, gas, tab, n_tab_rows, coef_row, ent_off, ent, slot_par,
+                         n_par, rad, jac);
+    });
+  };
+  if (level_jac_np(n_par) == kLevelJacNPLarge) launch(std::integral_constant<int, kLevelJacNPLarge>{});
+  else launch(std::integral_constant<int, kLevelJacNPSmall>{});
   return (int)hipGetLastError();
 }
 
@@ -4762,18 +4757,17 @@ int launch_limb_parts(const double *abs_c, const double *emi_c, int n_pts, int n
                       const int *slot_part, int n_part, double *rad, double *parts, hipStream_t st) {
   if (n_pts <= 0 || n_rays <= 0 || n_part <= 0 || n_blocks <= 0) return 0;
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
-#define SR_L(NG, NP) hipLaunchKernelGGL((sr_limb_parts_kernel<NG, NP>), grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, \
-                                        seg_layer, col, o, n_rays, gas, tab, coef_row, words, cc, slot_level, slot_part,               \
-                                        n_part, rad, parts)
-  if (limb_parts_np(n_part) == kLevelJacNPLarge) {
-    SR_BY_NGAS(o.n_gas, SR_L(1, kLevelJacNPLarge), SR_L(2, kLevelJacNPLarge), SR_L(3, kLevelJacNPLarge), SR_L(4, kLevelJacNPLarge))
-  } else {
-    SR_BY_NGAS(o.n_gas, SR_L(1, kLevelJacNPSmall), SR_L(2, kLevelJacNPSmall), SR_L(3, kLevelJacNPSmall), SR_L(4, kLevelJacNPSmall))
-  }
-#undef SR_L
+  auto launch = [&](auto np) {
+    by_ngas(o.n_gas, [&](auto ng) {
+      hipLaunchKernelGGL((sr_limb_parts_kernel<decltype(ng)::value, decltype(np)::value>), grid, dim3(256), 0, st, abs_c, emi_c, n_pts,
+                         n_layers, seg_off, seg_layer, col, o, n_rays, gas, tab, coef_row, words, cc, slot_level, slot_part, n_part,
+                         rad, parts);
+    });
+  };
+  if (limb_parts_np(n_part) == kLevelJacNPLarge) launch(std::integral_constant<int, kLevelJacNPLarge>{});
+  else launch(std::integral_constant<int, kLevelJacNPSmall>{});
   return (int)hipGetLastError();
 }
-#undef SR_BY_NGAS
 
 int launch_radiance_jac_layer(const double *abs_c, const double *emi_c, const double *dabs, const double *demi,
                               int n_pts, int n_layers, int n_rays, const int *seg_off, const int *seg_layer,

@@ -235,7 +235,7 @@ int launch_limb_jac(const double *abs_c, const double *emi_c, int n_pts, int n_l
                     const LimbOpts &o, double *rad, double *jac, hipStream_t st);
 // the forward-sensitivity kernel (16 layers per thread when there are more than 8; `forward` is ignored: the one-pass
 // formulation is launch_limb_adjoint)
-int launch_limb_jac_layer(int forward, const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
+int launch_limb_jac_layer(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
                           int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
                           const LimbOpts &o, double *jac, hipStream_t st);
 // Level-parameter Jacobians of one level-factored gas (sr_limb_jac_level_kernel): blocks of level_jac_np(n_par)
