@@ -521,6 +521,34 @@ int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_l
                                const int32_t *coef_row, int n_par, const int32_t *par_level, const double *par_c,
                                double *rad, double *jac, void *stream);
 
+/* Radiances and their Jacobian with respect to a MIXED state vector in one pass over each ray: n_col column parameters
+ * (VMR-profile parameters, exactly those of sr_limb_rays_jac_dev) and n_lev level parameters of the one level-factored
+ * gas `gas` (exactly those of sr_limb_rays_jac_level_dev).  Both kinds feed the same recursion,
+ *   J_p <- J_p t + (-I_prev t dtau_p + dE_p f + E f' dtau_p)        (solo_absorption: the two source terms drop)
+ * and differ in where dtau_p and dE_p of a segment s on coefficient row r come from:
+ *   column parameter p of gas g = par_gas[p]:  dtau = abs_g[r] D,  dE = emi_g[r] D,  D = d u_g[s] / d x_p, the
+ *     Curtis-Godson column of the mask par_w[p] over the segment's sample points (times col_scale[g]);
+ *   level parameter p of level L = par_level[p]:  dtau = par_c[p][r] u A_L[coef_row[r]],  dE = par_c[p][r] u E_L[coef_row[r]],
+ *     u the column of `gas` on s, A_L / E_L the pair tables `tab` of sr_glevel_pairs_dev.
+ * One call instead of sr_limb_rays_jac_dev + sr_limb_rays_jac_level_dev on the same batch: the LOS is staged once, the
+ * columns are integrated once and the recursion tau, t, f, f' runs once per block of parameters, whatever their kinds.
+ * abs_c / emi_c: DEVICE [n_gas][n_layers][n_pts]; par_gas: HOST [n_col], each in [0, n_gas); par_w: HOST [n_col][n_pt]
+ * at the LOS sample points; tab: DEVICE [n_levels][2][n_tab_rows][n_pts]; coef_row: HOST [n_layers], each in
+ * [0, n_tab_rows); par_level: HOST [n_lev], each in [0, n_levels); par_c: HOST [n_lev][n_layers]; rad: DEVICE
+ * [n_rays][n_pts] or NULL; jac: DEVICE [n_rays][n_col + n_lev][n_pts]: the column parameters in the caller's order, then
+ * the level parameters in the caller's order; every element is written (a parameter a ray never touches: exact zeros).
+ * Either kind may be empty, not both; with n_lev == 0, tab, coef_row, par_level and par_c may be NULL (n_col == 0:
+ * par_gas and par_w).  los_order, solo_absorption and init_mode 0 / 2 as the other ray-batch calls; init_mode 1 is
+ * refused (SR_ERR_ARG).  All arguments are checked before the first copy or launch: a refused call leaves rad and jac
+ * untouched.
+ * The reference has no counterpart (it has no derivative code at all): the build's definition, checked
+ * against the two single-kind calls and against central differences of the whole forward chain
+ * (tests/test_gpu_state_jacobian.py). */
+int sr_limb_rays_jac_state_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                               const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
+                               const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
+                               const int32_t *par_level, const double *par_c, double *rad, double *jac, void *stream);
+
 /* The radiance budget of the ray batch: which gas, and which level of the level-factored gas `gas`, emits the radiance
  * that arrives.  The recursion is linear in the emission: with tau = sum_g abs_g[r] u_g, t = exp(-tau), f = (1 - t) / tau
  * of a segment on coefficient row r,

@@ -3393,6 +3393,64 @@ int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_l
   return mark_both(pk.slot(), *D.slot, st);
 }
 
+int sr_limb_rays_jac_state_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                               const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
+                               const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
+                               const int32_t *par_level, const double *par_c, double *rad, double *jac, void *stream) {
+  // everything is checked here, before the first copy or launch (as sr_limb_rays_jac_level_dev does)
+  LosShape shape;
+  const bool lev_ok = n_lev == 0 || (tab && coef_row && par_level && par_c && n_levels > 0 && n_tab_rows > 0);
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, jac && n_col >= 0 && n_lev >= 0 && n_col + (int64_t)n_lev >= 1 && lev_ok);
+  if (!rc) rc = check_los_par(los, n_layers, n_col, par_gas, par_w, &shape);
+  if (rc) return rc;
+  if (gas < 0 || gas >= los->n_gas) return SR_ERR_ARG;
+  if ((rc = refuse_init_mode_1(los, "sr_limb_rays_jac_state_dev", SR_ERR_ARG))) return rc;
+  if (n_lev > 0 && !coef_rows_in_range(coef_row, n_layers, n_tab_rows)) return SR_ERR_ARG;
+  for (int p = 0; p < n_lev; ++p)
+    if (par_level[p] < 0 || par_level[p] >= n_levels) return SR_ERR_ARG;
+  if ((int64_t)n_col + n_lev > INT_MAX) return SR_ERR_LIMIT;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // the column parameters in the caller's order, then the level parameters in level order, NP per block: a block's
+  // column slots come first and stand for consecutive rows of dcol, a row's level entries come in level order
+  const int n_par = n_col + n_lev, np = level_jac_np(n_par), n_blocks = (n_par + np - 1) / np;
+  const std::vector<int> order = order_by_level(n_lev, par_level);
+  std::vector<int> ent_off((size_t)n_blocks * (n_layers + 1)), slot_par((size_t)n_blocks * np, -1), blk((size_t)n_blocks * 2, 0);
+  std::vector<LevelEnt> ent;
+  for (int b = 0; b < n_blocks; ++b) {
+    const int i0 = b * np, i1 = std::min(n_par, i0 + np), nc = std::max(0, std::min(n_col, i1) - i0);
+    unsigned gases = 0u;
+    for (int i = i0; i < i0 + nc; ++i) gases |= (unsigned)par_gas[i] << (2 * (i - i0));
+    blk[2 * b] = nc;
+    blk[2 * b + 1] = (int)gases;
+    for (int i = i0; i < i1; ++i) slot_par[i] = i < n_col ? i : n_col + order[i - n_col];
+    for (int r = 0; r < n_layers; ++r) {
+      ent_off[(size_t)b * (n_layers + 1) + r] = (int)ent.size();
+      for (int i = std::max(i0, n_col); i < i1; ++i) {
+        const int p = order[i - n_col];
+        const double c = par_c[(size_t)p * n_layers + r];
+        if (c != 0.0) ent.push_back(LevelEnt{i - i0, par_level[p], c});
+      }
+    }
+    ent_off[(size_t)b * (n_layers + 1) + n_layers] = (int)ent.size();
+  }
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_ent = pk.copy(ent.data(), ent.size(), 1);
+  const auto p_row = n_lev > 0 ? pk.copy(coef_row, (size_t)n_layers) : pk.zeros<int32_t>((size_t)n_layers);
+  const auto p_off = pk.copy(ent_off.data(), ent_off.size()), p_slot = pk.copy(slot_par.data(), slot_par.size());
+  const auto p_blk = pk.copy(blk.data(), blk.size());
+  rc = pk.stage(st);
+  if (rc) return rc;
+  LosDev D;
+  rc = stage_los(los, shape, n_col, par_gas, par_w, st, &D);
+  if (rc) return rc;
+  LAUNCHCHK(launch_limb_jac_state(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col,
+                                  D.col + (size_t)los->n_gas * D.n_seg, limb_opts(los, D.n_seg), gas, tab, n_tab_rows,
+                                  pk.dev(p_row), n_blocks, pk.dev(p_blk), pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot), n_par,
+                                  rad, jac, st));
+  return mark_both(pk.slot(), *D.slot, st);
+}
+
 int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
                            int gas, const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_part,
                            const int32_t *part_gas, const int32_t *part_level, const double *part_c, double *rad,

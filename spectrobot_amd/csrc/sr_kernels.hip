@@ -3015,6 +3015,7 @@ __global__ __launch_bounds__(256) void sr_radiance_jac_layer_kernel(
 //   sr_limb_jac_kernel      + derivatives w.r.t. VMR-profile parameters (columns linear in them)
 //   sr_limb_jac_layer_kernel  + derivatives w.r.t. one scalar per layer acting through the coefficients
 //   sr_limb_jac_level_kernel  + derivatives w.r.t. level populations / vibrational temperatures of a level-factored gas
+//   sr_limb_jac_state_kernel  + both of these kinds, column and level parameters, in the accumulators of one pass
 //   (all three: forward sensitivities, NP parameters per thread; many parameters / layers: sr_limb_adjoint_kernel below)
 //   sr_limb_parts_kernel    the radiance split into the parts single gases / single levels emit, and the background
 // Per segment s of a ray, layer k = seg_layer[s], columns u_g = col[g][s]:
@@ -3400,6 +3401,141 @@ __global__ __launch_bounds__(256) void sr_limb_jac_level_kernel(
     const int e0 = eo[r], e1 = eo[r + 1];
     if (e0 < e1) {
       const double fp = thin ? -0.5 : (tau * t - em1) * (A.rtau * A.rtau);
+      const double *tr = tab + (size_t)coef_row[r] * n_pts + j;
+      int lev = -1;
+      double d = 0.0;
+      for (int i = e0; i < e1; ++i) {
+        const int slot = ent[i].slot, lv = ent[i].level;
+        if (lv != lev) { // (entries in level order: two loads and one d per distinct level)
+          lev = lv;
+          const double *tl = tr + (size_t)lv * 2 * plane;
+          const double dtau = ug * tl[0], dE = ug * tl[plane];
+          d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
+        }
+        const double v = ent[i].c * d;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) J[q] += q == slot ? v : 0.0;
+      }
+    }
+    I = I * t + src;
+  }
+  if (blockIdx.z == 0 && rad) rad[(size_t)ray * n_pts + j] = I;
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    const int p = slot_par[blockIdx.z * NP + q];
+    if (p >= 0) jac[((size_t)ray * n_par + p) * n_pts + j] = J[q];
+  }
+}
+
+// Derivatives w.r.t. a MIXED state vector in one pass (sr_limb_rays_jac_state_dev): column parameters as in
+// sr_limb_jac_kernel and level parameters as in sr_limb_jac_level_kernel feed the same recursion,
+//   J_p <- J_p t + (-I t dtau_p + dE_p f + E f' dtau_p),
+// and differ only in where dtau_p and dE_p come from:
+//   column parameter of gas g:  dtau = a_g D,  dE = e_g D,  D = dcol[p][s]
+//   level parameter of level L: dtau = c u A_L[row[r]],  dE = c u E_L[row[r]]   (u the column of `gas`, c = c[p][r])
+// so a ray is walked once per block of NP parameters whatever their kinds.  The host lists the column parameters first
+// (caller's order), then the level parameters in level order, and cuts the list into blocks of NP: in a block the
+// column slots are slots 0 .. nc - 1 and stand for the consecutive parameters blockIdx.z NP + q (their dcol rows need
+// no index table), the level slots follow in level order with their entry lists (LevelEnt, as the level kernel's).
+// blk [n_blocks][2] = nc, and the column slots' gases, two bits each.  A block works on one ray, so nc, the gases, the
+// D and the entry lists are wave-uniform: scalar loads, scalar branches, the accumulators indexed statically.  A
+// column slot costs its D (a scalar load, all of a segment's issued together ahead of the exponential), a multiplication
+// and an FMA on top of one (dsrc - I t a_g) per gas; a segment none of the block's level slots touches costs them J *= t.  The
+// arithmetic of either kind is that of its own kernel, operation for operation.  Coefficients of segment s + 1 are
+// loaded while s is worked on; rays and point blocks by limb_block().
+template <int NG, int NP>
+__global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
+    const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
+    const int *__restrict__ seg_off, const int *__restrict__ seg_layer, const double *__restrict__ col,
+    const double *__restrict__ dcol, LimbOpts o, int n_rays, int gas, const double *__restrict__ tab, int n_tab_rows,
+    const int *__restrict__ coef_row, const int *__restrict__ blk, const int *__restrict__ ent_off,
+    const LevelEnt *__restrict__ ent, const int *__restrict__ slot_par, int n_par, double *__restrict__ rad,
+    double *__restrict__ jac) {
+  static_assert(NP <= 16 && NG <= 4, "blk packs the gases of 16 column slots, two bits each");
+  int pb, ray;
+  if (!limb_block((n_pts + 255) / 256, n_rays, pb, ray)) return;
+  const int j = pb * 256 + threadIdx.x;
+  if (j >= n_pts) return;
+  double I = limb_initial(o, jac, 0, j), J[NP]; // init_mode 1 is refused by the host for this kernel
+#pragma unroll
+  for (int q = 0; q < NP; ++q) J[q] = 0.0;
+  const int nc = blk[2 * blockIdx.z];
+  const unsigned gw = (unsigned)blk[2 * blockIdx.z + 1];
+  const double *dc = dcol + (size_t)blockIdx.z * NP * o.n_seg_total; // (read with nc > 0 only)
+  const int *eo = ent_off + (size_t)blockIdx.z * (n_layers + 1);
+  const int s0 = seg_off[ray], s1 = seg_off[ray + 1];
+  const size_t gstride = (size_t)n_layers * n_pts, plane = (size_t)n_tab_rows * n_pts;
+  double an[NG], en[NG];
+  if (s0 < s1) {
+    const size_t ofs = (size_t)seg_layer[s0] * n_pts + j;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      an[g] = abs_c[g * gstride + ofs];
+      en[g] = emi_c[g * gstride + ofs];
+    }
+  }
+  for (int s = s0; s < s1; ++s) {
+    const int r = seg_layer[s];
+    double a[NG], e[NG], D[NP];
+    double tau = 0.0, E = 0.0, ug = 0.0;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      a[g] = an[g];
+      e[g] = en[g];
+      const double u = col[(size_t)g * o.n_seg_total + s];
+      tau = g == 0 ? a[g] * u : tau + a[g] * u;
+      E = g == 0 ? e[g] * u : E + e[g] * u;
+      ug = g == gas ? u : ug;
+    }
+    if (nc > 0) {
+#pragma unroll
+      for (int q = 0; q < NP; ++q) D[q] = dc[(size_t)min(q, nc - 1) * o.n_seg_total + s];
+    }
+    {
+      const size_t ofs = (size_t)seg_layer[min(s + 1, s1 - 1)] * n_pts + j;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        an[g] = abs_c[g * gstride + ofs];
+        en[g] = emi_c[g * gstride + ofs];
+      }
+    }
+    const Atten A = attenuation(tau);
+    const double t = A.t, em1 = A.em1, f = A.f;
+    const bool thin = A.thin;
+    const double src = o.solo_absorption ? 0.0 : E * f;
+    const int e0 = eo[r], e1 = eo[r + 1];
+    double fp = 0.0, W[NG];
+    if (nc > 0 || e0 < e1) fp = thin ? -0.5 : (tau * t - em1) * (A.rtau * A.rtau);
+    if (nc > 0) { // what a column slot of gas g adds per unit of its D: sr_limb_jac_kernel's (dsrc - I t a_g), once per gas
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const double dsrc = o.solo_absorption ? 0.0 : fma(E * fp, a[g], e[g] * f);
+        W[g] = dsrc - I * t * a[g];
+      }
+    }
+    // (nc and the gases are loop-invariant: left to itself the compiler keeps every slot's comparisons in scalar
+    // register pairs over the whole loop, NP NG of them, and spills; re-read through an empty asm they are formed
+    // where they are used)
+    int ncs = nc;
+    unsigned gws = gw;
+    asm volatile("" : "+s"(ncs), "+s"(gws));
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+      if (q < ncs) { // a column slot: sr_limb_jac_kernel's update
+        if constexpr (NG == 1) {
+          J[q] = fma(J[q], t, W[0] * D[q]);
+        } else { // the gas is chosen on the scalar side: D or 0 per gas, the products with 0 add nothing
+          const unsigned gq = gws >> (2 * q) & 3u;
+          double x = W[0] * (gq == 0u ? D[q] : 0.0);
+#pragma unroll
+          for (int g = 1; g < NG; ++g) x = fma(W[g], gq == (unsigned)g ? D[q] : 0.0, x);
+          J[q] = fma(J[q], t, x);
+        }
+      } else {
+        J[q] *= t;
+      }
+    }
+    if (e0 < e1) { // the level slots: sr_limb_jac_level_kernel's update
       const double *tr = tab + (size_t)coef_row[r] * n_pts + j;
       int lev = -1;
       double d = 0.0;
@@ -4744,6 +4880,25 @@ int launch_limb_jac_level(const double *abs_c, const double *emi_c, int n_pts, i
       hipLaunchKernelGGL((sr_limb_jac_level_kernel<decltype(ng)::value, decltype(np)::value>), grid, dim3(256), 0, st, abs_c, emi_c,
                          n_pts, n_layers, seg_off, seg_layer, col, o, n_rays, gas, tab, n_tab_rows, coef_row, ent_off, ent, slot_par,
                          n_par, rad, jac);
+    });
+  };
+  if (level_jac_np(n_par) == kLevelJacNPLarge) launch(std::integral_constant<int, kLevelJacNPLarge>{});
+  else launch(std::integral_constant<int, kLevelJacNPSmall>{});
+  return (int)hipGetLastError();
+}
+
+int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
+                          const int *seg_layer, const double *col, const double *dcol, const LimbOpts &o, int gas,
+                          const double *tab, int n_tab_rows, const int *coef_row, int n_blocks, const int *blk,
+                          const int *ent_off, const LevelEnt *ent, const int *slot_par, int n_par, double *rad, double *jac,
+                          hipStream_t st) {
+  if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0) return 0;
+  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
+  auto launch = [&](auto np) {
+    by_ngas(o.n_gas, [&](auto ng) {
+      hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value>), grid, dim3(256), 0, st, abs_c, emi_c,
+                         n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas, tab, n_tab_rows, coef_row, blk, ent_off, ent,
+                         slot_par, n_par, rad, jac);
     });
   };
   if (level_jac_np(n_par) == kLevelJacNPLarge) launch(std::integral_constant<int, kLevelJacNPLarge>{});

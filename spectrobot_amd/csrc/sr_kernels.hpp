@@ -251,6 +251,15 @@ int launch_limb_jac_level(const double *abs_c, const double *emi_c, int n_pts, i
                           const int *seg_layer, const double *col, const LimbOpts &o, int gas, const double *tab,
                           int n_tab_rows, const int *coef_row, int n_blocks, const int *ent_off, const LevelEnt *ent,
                           const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st);
+// Mixed state vector (sr_limb_jac_state_kernel): n_par = n_col + n_lev parameters, the column parameters first (rows of
+// dcol, caller's order), then the level parameters in level order, in blocks of level_jac_np(n_par); blk [n_blocks][2] =
+// the number of column slots of a block (its first slots: parameters block NP + q) and their gases, two bits per slot;
+// ent_off / ent / slot_par as launch_limb_jac_level, slot numbers counted over all slots of a block.
+int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
+                          const int *seg_layer, const double *col, const double *dcol, const LimbOpts &o, int gas,
+                          const double *tab, int n_tab_rows, const int *coef_row, int n_blocks, const int *blk,
+                          const int *ent_off, const LevelEnt *ent, const int *slot_par, int n_par, double *rad, double *jac,
+                          hipStream_t st);
 // Radiance budget (sr_limb_parts_kernel): the n_part parts and the background are n_part + 1 slots in blocks of
 // limb_parts_np(n_part); slot_level [n_blocks][NP]: >= 0 the first row of a level's E plane in the pair tables,
 // (2 L + 1) n_tab_rows, -1 - g the gas part of gas g,

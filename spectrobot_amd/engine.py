@@ -526,6 +526,29 @@ class LevelFactored(object):
         return limb_rays_level_jacobian(coeffs, los, self.tab, step_row, par_level, par_c, gas=gas, grid=grid,
                                         g_lo=int(self._shard[0]), want_rad=want_rad)
 
+    def state_jacobian(self, coeffs, los, step_row, tvib, par_level, par_w_level, par_gas=None, par_w_col=None, gas=0,
+                       q_part=None, grid=None, want_rad=True):
+        """(rad | None, jac [n_rays, n_col + n_lev, n_pts]): d rad / d x for a mixed state vector in one pass
+        (limb_rays_state_jacobian): first the VMR-profile parameters par_gas / par_w_col of limb_rays_jacobian (any gas
+        of the batch, this one included; None: no such parameter), then the vibrational-temperature parameters
+        par_level / par_w_level of tvib_jacobian, par_c = par_w_level * d pop / d Tvib formed exactly as there (an empty
+        par_level: only column parameters).  Honours the object's spectral shard."""
+        step_row = np.ascontiguousarray(step_row, dtype=np.int32)
+        par_level = np.ascontiguousarray(par_level, dtype=np.int32).reshape(-1)
+        par_w = np.zeros((0, step_row.size)) if par_level.size == 0 else np.asarray(par_w_level, dtype=np.float64)
+        if par_w.shape != (par_level.size, step_row.size):
+            raise ValueError("par_w_level must be [n_lev, n_steps]")
+        n_lev = self.ls.level_energies.size
+        if par_level.size and (par_level.min() < 0 or par_level.max() >= max(n_lev, 1)):
+            raise ValueError("par_level out of range")
+        par_c = None
+        if par_level.size:
+            dpop = self.ls.level_populations_dtvib(self.temps[step_row], tvib, q_part=q_part)  # [n_steps, n_levels]
+            par_c = par_w * dpop.T[par_level]
+        return limb_rays_state_jacobian(coeffs, los, par_gas=par_gas, par_w=par_w_col, tab=self.tab, coef_row=step_row,
+                                        par_level=par_level, par_c=par_c, gas=gas, grid=grid, g_lo=int(self._shard[0]),
+                                        want_rad=want_rad)
+
     def level_radiances(self, coeffs, los, step_row, tvib, levels=None, weights=None, gas=0, q_part=None, grid=None,
                         gas_parts=True):
         """(rad, parts [n_rays, n_part + 1, n_pts], labels): the radiance budget of the batch by the levels of this gas
@@ -1085,6 +1108,53 @@ def limb_rays_level_jacobian(coeffs, los, tab, coef_row, par_level, par_c, gas=0
     check(lib.sr_limb_rays_jac_level_dev(ptr(a), ptr(e), n_layers, n_pts, C.byref(d), int(gas), ptr(tab), int(tab.shape[0]),
                                          int(tab.shape[2]), cr, n_par, pl, pc, ptr(rad), ptr(jac), _stream_ptr()),
           "sr_limb_rays_jac_level_dev")
+    return rad, jac
+
+
+def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, coef_row=None, par_level=None, par_c=None,
+                             gas=0, grid=None, g_lo=0, want_rad=True):
+    """(rad | None, jac [n_rays, n_col + n_lev, n_pts]): radiances and their derivatives with respect to a mixed state
+    vector in ONE pass over each ray (sr_limb_rays_jac_state_dev): the column parameters par_gas / par_w of
+    limb_rays_jacobian (VMR-profile parameters, par_w [n_col, n_pt] at the LOS sample points) first, then the level
+    parameters tab / coef_row / par_level / par_c of limb_rays_level_jacobian for the level-factored gas `gas`
+    (par_c [n_lev, n_layers] on the coefficient rows).  Either kind may be left out (None), not both.  Vibrational
+    temperatures: LevelFactored.state_jacobian."""
+    a, e = _gas_stack(coeffs)
+    n_gas, n_layers, n_pts = a.shape
+    if n_gas != los.n_gas:
+        raise ValueError("%d coefficient sets for %d gases" % (n_gas, los.n_gas))
+    n_col = n_lev = n_levels = n_tab_rows = 0
+    pg = pw = cr = pl = pc = None
+    if par_gas is not None and np.asarray(par_gas).size:
+        par_gas, pg = _i(np.asarray(par_gas).reshape(-1))
+        par_w, pw = _d(par_w)
+        n_col = par_gas.size
+        if par_w.shape != (n_col, los.n_pt):
+            raise ValueError("par_w must be [n_col, n_pt]")
+    if par_level is not None and np.asarray(par_level).size:
+        if tab is None or coef_row is None or par_c is None:
+            raise ValueError("level parameters need tab, coef_row and par_c")
+        assert tab.is_cuda and tab.dtype == torch.float64 and tab.is_contiguous() and tab.dim() == 4 and tab.shape[1] == 2
+        if tab.shape[3] != n_pts:
+            raise ValueError("tables of %d points for coefficients of %d" % (tab.shape[3], n_pts))
+        n_levels, n_tab_rows = int(tab.shape[0]), int(tab.shape[2])
+        coef_row, cr = _i(coef_row)
+        par_level, pl = _i(np.asarray(par_level).reshape(-1))
+        par_c, pc = _d(par_c)
+        n_lev = par_level.size
+        if coef_row.shape != (n_layers,):
+            raise ValueError("coef_row must be [n_layers]")
+        if par_c.shape != (n_lev, n_layers):
+            raise ValueError("par_c must be [n_lev, n_layers]")
+    if n_col + n_lev == 0:
+        raise ValueError("no parameters: give column parameters, level parameters or both")
+    rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
+    jac = torch.empty((los.n_rays, n_col + n_lev, n_pts), dtype=torch.float64, device="cuda")
+    d = los.desc(grid, g_lo)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    check(lib.sr_limb_rays_jac_state_dev(ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw, int(gas),
+                                         ptr(tab) if n_lev else None, n_levels, n_tab_rows, cr, n_lev, pl, pc, ptr(rad),
+                                         ptr(jac), _stream_ptr()), "sr_limb_rays_jac_state_dev")
     return rad, jac
 
 

@@ -58,6 +58,67 @@ class Gas(object):
         self.vmr = np.asarray(profile, dtype=float)
 
 
+class LevelGas(Gas):
+    """A non-LTE gas on the level-factored route, for retrievals of its vibrational temperatures: it owns an
+    engine.LevelFactored on the scene's (T, P) rows -- the pair tables, built once per scene (and spectral shard) -- and
+    a reference tvib0 [n_levels, n_layers]; its coefficients are lf.steps(rows, tvib), recombined only when tvib was
+    changed (set_tvib): a combine of the resident tables, never a walk of the lines."""
+
+    def __init__(self, name, lineset, vmr, tvib0, iso_ratio=1.0):
+        tvib0 = np.array(tvib0, dtype=float)
+        if tvib0.ndim != 2 or tvib0.shape[0] != max(int(np.size(lineset.level_energies)), 1):
+            raise ValueError("tvib0 must be [n_levels, n_layers] for the line set's levels")
+        Gas.__init__(self, name, lineset, vmr, iso_ratio=iso_ratio, tvib=tvib0.copy())
+        self.tvib0 = tvib0
+        self.lf, self._lf_key, self._combined = None, None, None
+
+    @property
+    def n_levels(self):
+        return self.tvib0.shape[0]
+
+    def set_tvib(self, tvib):
+        tvib = np.array(tvib, dtype=float)
+        if tvib.shape != self.tvib0.shape:
+            raise ValueError("tvib must be [n_levels, n_layers] like tvib0")
+        self.tvib = tvib
+
+    def layer_coefficients(self, temps, press, g_lo=0, g_hi=None):
+        """(abs, emi) on the layer stack from the pair tables (LimbScene.coefficients calls this)."""
+        key = (np.asarray(temps, float).tobytes(), np.asarray(press, float).tobytes(), int(g_lo), g_hi)
+        if self.lf is None or self._lf_key != key:
+            self.lf, self._lf_key, self._combined = engine.LevelFactored(self.lineset, temps, press, g_lo=g_lo, g_hi=g_hi), key, None
+        self.rows = np.arange(len(temps), dtype=np.int32)
+        tv = np.asarray(self.tvib, float).tobytes()
+        if self._combined != tv or self.coeffs is None:
+            self.coeffs, self._combined = self.lf.steps(self.rows, tvib=self.tvib), tv
+        return self.coeffs
+
+
+class TvibProfile(smm.LinearProfile_1D_new):
+    """The retrieval set of one level's vibrational temperatures: named "tvib:<gas>:<level>", its parameters the nodes
+    of an OFFSET profile (K) that is added to the gas's reference, Tvib_L = tvib0[L] + sum_p mask_p x_p, the masks
+    those of alt_triangle on the scene's altitude levels (engine.level_node_weights).  An offset may have either sign:
+    no parameter is constrained positive."""
+
+    def __init__(self, gas, level, alt_grid, alt_nodes, apriori_err, apriori=None, first_guess=None):
+        n = len(list(alt_nodes))
+        smm.LinearProfile_1D_new.__init__(self, "tvib:%s:%d" % (gas, int(level)), alt_grid, alt_nodes,
+                                          np.zeros(n) if apriori is None else apriori, apriori_err, first_guess_prof=first_guess)
+        self.gas, self.level = gas, int(level)
+        for par in self.set:
+            par.constrain_positive = False
+
+
+class StateWeights(object):
+    """LimbScene.state_weights' result: the column block (par_gas [n_col], par_w_col [n_col, n_pt]), the level block
+    (level_gas: the LevelGas or None, gas: its index, par_level [n_lev], par_w_lev [n_lev, n_layers]) and perm [n_par]:
+    the row of the call's Jacobian (column parameters, then level parameters) that belongs to BayesSet parameter i."""
+
+    def __init__(self, par_gas, par_w_col, level_gas, gas, par_level, par_w_lev, perm):
+        self.par_gas, self.par_w_col, self.level_gas, self.gas = par_gas, par_w_col, level_gas, gas
+        self.par_level, self.par_w_lev, self.perm = par_level, par_w_lev, perm
+
+
 class LimbPixel(object):
     """A limb pixel: tangent altitude of its centre LOS, half extent of the FOV in altitude (the lower /
     upper LOS are at alt -+ fov_half: pix.low_LOS() / LOS() / up_LOS(), spect_main_module.py:2704-2706),
@@ -91,6 +152,9 @@ class LimbScene(object):
         between the iterations of a VMR retrieval (refresh=True recomputes, e.g. when temperatures are retrieved)."""
         g_hi = len(self.grid) if g_hi is None else int(g_hi)
         for g in self.gases:
+            if isinstance(g, LevelGas):      # the combine of its resident tables, redone only when its tvib changed
+                g.layer_coefficients(self.temps, self.press, g_lo=g_lo, g_hi=g_hi)
+                continue
             if g.coeffs is None or refresh or getattr(g, "coeffs_shard", None) != (g_lo, g_hi):
                 g.coeffs = g.lineset.abscoeff_layers(self.temps, self.press, tvib=g.tvib, g_lo=g_lo, g_hi=g_hi)
                 g.coeffs_shard = (g_lo, g_hi)
@@ -159,6 +223,49 @@ class LimbScene(object):
             a.setflags(write=False)     # shared with every caller until the masks change: engine keys resident batches on them
         self._weights_cache = (key, out[0], out[1])
         return out
+
+    def state_weights(self, bayes_set, alt):
+        """The parameters of a mixed state vector, split in BayesSet order into the column block -- sets named after a gas:
+        VMR-profile parameters, their masks at the LOS sample altitudes `alt` as in profile_weights -- and the level block
+        -- sets named "tvib:<gas>:<level>" (TvibProfile) of ONE LevelGas: their masks on the coefficient rows, the scene's
+        altitude levels.  Returns a StateWeights (its perm leads back to BayesSet order)."""
+        names = [g.name for g in self.gases]
+        top = self.z[-1] + (self.z[-1] - self.z[-2])
+        zz = np.append(self.z, top)
+        par_gas, par_w_col, par_level, par_w_lev, kind = [], [], [], [], []
+        level_gas = None
+        for name in bayes_set.order:
+            st = bayes_set.sets[name]
+            if name in names:
+                for par in st.set:
+                    m = np.asarray(par.maskgrid.mask, dtype=float)
+                    par_gas.append(names.index(name))
+                    par_w_col.append(np.interp(alt, zz, np.append(m, m[-1])))
+                    kind.append(0)
+                continue
+            parts = name.split(":")
+            ok = len(parts) == 3 and parts[0] == "tvib" and parts[1] in names and parts[2].isdigit()
+            gas = self.gas(parts[1]) if ok else None
+            if not ok or not isinstance(gas, LevelGas) or int(parts[2]) >= gas.n_levels:
+                raise ValueError("retrieval set %r names neither a gas of the scene nor tvib:<LevelGas>:<level> with a level "
+                                 "of that gas" % (name,))
+            if level_gas is not None and gas is not level_gas:
+                raise ValueError("vibrational-temperature sets of more than one gas (%s, %s): one call has one "
+                                 "level-factored gas" % (level_gas.name, gas.name))
+            level_gas = gas
+            for par in st.set:
+                m = np.asarray(par.maskgrid.mask, dtype=float)
+                if m.shape != self.z.shape:
+                    raise ValueError("the masks of %r are not on the scene's altitude levels" % (name,))
+                par_level.append(int(parts[2]))
+                par_w_lev.append(m)
+                kind.append(1)
+        kind = np.array(kind, dtype=int)
+        n_col = int((kind == 0).sum())
+        perm = np.where(kind == 0, np.cumsum(kind == 0) - 1, n_col + np.cumsum(kind == 1) - 1).astype(int)
+        return StateWeights(np.array(par_gas, np.int32), np.array(par_w_col, dtype=float).reshape(n_col, len(alt)), level_gas,
+                            None if level_gas is None else self.gases.index(level_gas), np.array(par_level, np.int32),
+                            np.array(par_w_lev, dtype=float).reshape(len(par_level), len(self.z)), perm)
 
 
 def _one_call_eligible(pixels, bayes_set, fov_closed_form):
@@ -582,6 +689,100 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
         for name in bayes_set.sets.keys():                                     # :2984-2985
             scene.gas(name).add_clim(bayes_set.sets[name].profile())
     return chi, obs, (finish(low, dlow) if fast else sims), bayes_set
+
+
+def _state_into_gases(scene, bayes_set):
+    """The BayesSet's profiles into the gases: add_clim for the VMR sets, tvib = tvib0 + offset for the Tvib sets."""
+    names, tvib = [g.name for g in scene.gases], {}
+    for name in bayes_set.order:
+        st = bayes_set.sets[name]
+        if name in names:
+            scene.gas(name).add_clim(st.profile())
+            continue
+        _, gas, level = name.split(":")
+        g = scene.gas(gas)
+        tv = tvib.setdefault(gas, g.tvib0.copy())
+        tv[int(level)] = g.tvib0[int(level)] + st.profile()
+    for gas, tv in tvib.items():
+        scene.gas(gas).set_tvib(tv)
+
+
+def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM=0.1, L1_reg=False,
+                    fov_closed_form=True):
+    """inversion_fast_limb's loop for a MIXED state vector: VMR-profile sets (named after a gas) together with the
+    vibrational-temperature sets of one LevelGas (TvibProfile).  Per iteration: the profiles into the gases, the
+    coefficient stack (the LevelGas recombines its tables when its Tvib moved), ONE Jacobian call for all LOS of all pixels
+    and both kinds of parameter (LevelFactored.state_jacobian), the instrument bands, the closed-form field of view,
+    chi square, the stopping rule and the Levenberg-Marquardt step (smm.inversion_algebra_arrays).  Returns
+    (chi, obs, sims, bayes_set) with .history, .stop, .jacobian and the stored averaging kernel and covariance, like
+    inversion_fast_limb.  Every pixel has the closed-form field of view, or none has a field of view."""
+    pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)
+    with_fov = sum(pix.fov_half > 0 for pix in pixels)
+    if not (with_fov == 0 or (with_fov == len(pixels) and fov_closed_form)):
+        raise ValueError("inversion_state needs the closed-form field of view for every pixel, or for none")
+    alts = [a for pix in pixels for a in pix.los_alts()]
+    scene.state_weights(bayes_set, np.zeros(1))                 # the sets' names are checked before anything is changed
+    _state_into_gases(scene, bayes_set)
+    obs = [pix.observation for pix in pixels]
+    masks = None if all(pix.mask is None for pix in pixels) else [pix.mask for pix in pixels]
+    noise = [pix.noise for pix in pixels]
+    obs_vec, _, noi_vec = smm.genvec(obs, obs, noise, masks=masks)
+    masktot = None if masks is None else np.concatenate([np.asarray(m, dtype=bool) for m in masks])
+    Sa_inv = np.linalg.inv(np.asarray(bayes_set.VCM_apriori(), dtype=float))
+    grid_lo = _Grid(scene.bands_nm)
+    lowres = lambda r: engine.hires_to_lowres(r, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units)
+    rots = [pix.pixel_rot for pix in pixels]
+    bayes_set.history, bayes_set.stop = [], 'max_it'
+
+    def wrap(v):
+        sp = Spectrum.__new__(Spectrum)
+        sp.spectrum, sp.spectral_grid = np.array(v), grid_lo
+        return sp
+
+    def finish(low, dlow):
+        if low is None:                                            # (max_it = 0: nothing was simulated)
+            return []
+        scene.los(alts)                                            # the batch's VMRs = the final profiles
+        jac = np.transpose(dlow, (1, 0, 2)).reshape(dlow.shape[1], -1)     # build_jacobian's rows, of the last iteration
+        bayes_set.jacobian = (jac if masktot is None else jac[:, masktot]).T
+        for num in range(len(pixels)):
+            for ip, par in enumerate(bayes_set.params()):
+                par.store_deriv(wrap(dlow[num, ip]), num=num)
+        return [wrap(v) for v in low]
+
+    chi_old, chi, low, dlow = None, None, None, None
+    n_los = len(alts)
+    for num_it in range(max_it):
+        coeffs = scene.coefficient_stack()
+        los, alt = scene.los(alts)
+        w = scene.state_weights(bayes_set, alt)
+        if w.level_gas is None:
+            rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col)
+        else:
+            lg = w.level_gas
+            rad, jac = lg.lf.state_jacobian(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, par_gas=w.par_gas,
+                                            par_w_col=w.par_w_col, gas=w.gas)
+        n_par = jac.shape[1]
+        both = np.concatenate([lowres(rad)[:, None, :],
+                               lowres(jac.view(n_los * n_par, -1)).reshape(n_los, n_par, -1)[:, w.perm]], axis=1)
+        fov = smm.fov_closed_form(both[0::3], both[1::3], both[2::3], rots) if with_fov else both[1::3]
+        low, dlow = fov[:, 0, :], fov[:, 1:, :]
+        for par in bayes_set.params():
+            par.set_used()
+        sim_vec = low.reshape(-1) if masktot is None else low.reshape(-1)[masktot]
+        chi = np.sum(((obs_vec - sim_vec) / noi_vec) ** 2) / (len(obs_vec) - bayes_set.n_used_par())   # chicalc
+        bayes_set.history.append(chi)
+        why = smm.retrieval_converged(chi, chi_old, chi_threshold)
+        if why:
+            bayes_set.stop = why
+            return chi, obs, finish(low, dlow), bayes_set
+        chi_old = chi
+        K = np.transpose(dlow, (1, 0, 2)).reshape(n_par, -1)               # build_jacobian's rows
+        K = (K if masktot is None else K[:, masktot]).T
+        bayes_set.jacobian = K
+        smm.inversion_algebra_arrays(K, obs_vec, sim_vec, noi_vec, bayes_set, lambda_LM=lambda_LM, L1_reg=L1_reg, Sa_inv=Sa_inv)
+        _state_into_gases(scene, bayes_set)
+    return chi, obs, finish(low, dlow), bayes_set
 
 
 def lut_coefficients(scene, temp_step=5.0, pres_step_log=1.0, refresh=False, **_unused):
