@@ -1032,6 +1032,7 @@ static void far_hierarchy(size_t n_pts, int nl, FarParams *fp) {
   fp->n_layers = nl;
   fp->n_boxes_total = 0;
   fp->top_first = n_pts <= 16384 ? 1 : 0; // see sr_farfield_kernel
+  fp->folded0 = 0;
   for (int lv = 0; lv < kMaxFarLevels; ++lv) {
     const int W = 64 << lv;
     fp->box_count[lv] = (int)((n_pts + W - 1) / W);
@@ -1267,6 +1268,9 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
     fp.pm = d_pm;
     fp.coef = far_only ? opt.far_coef : w.d_coef[b].as<double>();
     fp.m2l = far_field == 2 ? 1 : 0;
+    // box-pair mode: the downward pass folds every level into level 0 behind M2L (both schedules) and the near-wings
+    // kernel evaluates ONE polynomial per point; the per-line mode of sparse sets keeps a polynomial per level
+    fp.folded0 = fp.m2l && !far_only ? 1 : 0;
     fp.rows = sparse_set ? 1 : 0; // the sparse sets' own kernel (sr_farfield_rows_kernel: a box for eight layers per wave)
     fp.pm_src = d_pm + nl;
     fp.disp_lo_end = (int)std::min<int64_t>(std::max<int64_t>(ls->n_disp_lo - line_lo, 0), n_sub);
@@ -1341,7 +1345,7 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
         HIPCHK(hipEventRecord(w.ev_s2m_done[b], far_st));
         LAUNCHCHK(launch_m2l(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, far_st, 2));
       }
-      if (far_only) { // the downward pass: the wider levels into the level-0 coefficients, behind the chain on its stream
+      if (far_only || fp.folded0) { // the downward pass: the wider levels into the level-0 coefficients, behind the chain on its stream
         const double *l2l_tab = nullptr;
         rc = l2l_table_dev(&l2l_tab);
         if (rc) return rc;
@@ -1370,7 +1374,7 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
       w.overlapped = false;
       rc = far_pass(st);
       if (rc) return rc;
-      if (far_only) {
+      if (far_only || fp.folded0) { // (its time falls into the far-field group's slot)
         const double *l2l_tab = nullptr;
         rc = l2l_table_dev(&l2l_tab);
         if (rc) return rc;

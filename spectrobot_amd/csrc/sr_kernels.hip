@@ -43,16 +43,21 @@ __device__ __forceinline__ LineG line_gcoeffs(const LinesDev &L, int ln, double 
     const double four_pi = 4 * kPi;
     const double el = L.e_lower[ln];
     const double eps_up = el + x0 - L.evib_up[ln], eps_lo = el - L.evib_lo[ln];
-    double rot_up = gu * ex(-kC2 * eps_up / Tw);
-    double rot_lo = gl * ex(-kC2 * eps_lo / Tw);
+    // (one division by Tw, one by 4 pi and, in line_physics, one by fac per record, multiplications after that: an IEEE
+    // fp64 division is ~13 instructions and this kernel had nine per record; the weights move by an ulp or two.  The
+    // widths keep their divisions: dw' places the region boundaries by index.)
+    const double inv_Tw = 1.0 / Tw;
+    double rot_up = gu * ex(-kC2 * eps_up * inv_Tw);
+    double rot_lo = gl * ex(-kC2 * eps_lo * inv_Tw);
     if (lin) { // d ln(exp(-c2 eps / T) / sqrt(T)) / d T = c2 eps / T^2 - 1 / (2 T)   (fac ~ dw ~ sqrt(T))
       rot_up *= fma(dTl, fma(kC2 * eps_up, 1.0 / (Tw * Tw), -0.5 / Tw), 1.0);
       rot_lo *= fma(dTl, fma(kC2 * eps_lo, 1.0 / (Tw * Tw), -0.5 / Tw), 1.0);
     }
     const double hcf = L.hcf[ln];
-    G.sp = hcf * rot_up * a_co / four_pi;
-    G.in = hcf * rot_up * L.b21[ln] / four_pi;
-    G.ab = hcf * rot_lo * L.b12[ln] / four_pi;
+    const double inv_four_pi = 1.0 / four_pi; // (a compile-time constant)
+    G.sp = hcf * rot_up * a_co * inv_four_pi;
+    G.in = hcf * rot_up * L.b21[ln] * inv_four_pi;
+    G.ab = hcf * rot_lo * L.b12[ln] * inv_four_pi;
   }
   return G;
 }
@@ -136,8 +141,9 @@ __device__ inline LinePhys line_physics(const LinesDev &L, const LayersDev &A, c
     wabs = (ll == W.level ? pl * g_ab : 0.0) - (lu == W.level ? pu * g_in : 0.0);
     wemi = lu == W.level ? pu * g_sp : 0.0;
   }
-  P.wabs = wabs / fac;
-  P.wemi = wemi / fac;
+  const double inv_fac = 1.0 / fac;
+  P.wabs = wabs * inv_fac;
+  P.wemi = wemi * inv_fac;
   return P;
 }
 
@@ -1736,12 +1742,13 @@ __global__ __launch_bounds__(64) void sr_abscoeff_near_wings_kernel(
 #ifdef SR_DIAG_WINGS
     count_add(cnt, kCntPolyPoints, lane == 0 ? n_diag >> 8 : 0u, lane);
 #else
-    count_add(cnt, kCntPolyPoints, (wlo + lane <= whi) ? (unsigned)fp.n_levels : 0u, lane);
+    count_add(cnt, kCntPolyPoints, (wlo + lane <= whi) ? (unsigned)(fp.folded0 ? 1 : fp.n_levels) : 0u, lane);
 #endif
   }
-  // far field: one polynomial per level
+  // far field: one polynomial per level, or level 0 alone where sr_l2l_kernel has folded the wider levels into it
   const double *cl = fp.coef + (size_t)layer * fp.n_boxes_total * (2 * kFC);
-  for (int lv = 0; lv < fp.n_levels; ++lv) {
+  const int n_lv = fp.folded0 ? 1 : fp.n_levels;
+  for (int lv = 0; lv < n_lv; ++lv) {
     const int W = 64 << lv;
     const int b = (wlo - g_lo) >> (6 + lv);
     const int blo = g_lo + b * W;
@@ -2141,7 +2148,9 @@ __global__ __launch_bounds__(64 * NW) SR_ZONES_ATTR void sr_abscoeff_near_zones_
 // operator entries exact in fp64 (an integer below 2^53 times a power of two).  After it the level-0 coefficients hold
 // every level's far field and a point evaluates ONE polynomial per output instead of one per hierarchy level.  For the
 // multi-channel pass (n_far x 2 outputs per point: 5 x 12 x 2 Horner chains of 22 fma per point were 2.3 of
-// sr_wings_mc_kernel's 5.2 ms); the folded op keeps its five polynomials (176 fma of a ~4100-instruction wave).
+// sr_wings_mc_kernel's 5.2 ms) and for the folded op in the box-pair mode (FarParams::folded0: 152 fma and four batches of
+// scalar coefficient loads less per wave of the near-wings kernel, -6 % of its instructions; this kernel runs behind M2L,
+// beside the zones kernel).  The per-line mode of sparse sets keeps one polynomial per level.
 // One wave per (layer, widest box) of a far pass: the box's tree of 31 coefficient sets in LDS, levels top down.
 // ------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void sr_l2l_kernel(double *__restrict__ coef_one, const FarBatchItem *__restrict__ items, FarParams fp,

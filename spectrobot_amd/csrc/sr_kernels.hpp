@@ -107,6 +107,7 @@ constexpr int kM2LQ = (kMQ + 3) / 4 * 4;      // rows (kMQ, padded with zeros)
 struct FarParams {
   int n_levels, n_layers, n_boxes_total;
   int top_first; // block order of sr_farfield_kernel: widest two levels of a layer group first
+  int folded0;   // level 0 holds every level's far field (sr_l2l_kernel ran): one polynomial per point
   int box_count[kMaxFarLevels], box_off[kMaxFarLevels];
   const int *pm; // [n_layers] pole margin in grid points
   double *coef;  // [n_layers][n_boxes_total][2][kFC]
