@@ -3347,6 +3347,65 @@ int sr_limb_rays_jac_layer_dev(const double *abs_c, const double *emi_c, const d
   return D.slot->mark(st);
 }
 
+// The host plan of sr_limb_jac_state_kernel: the column parameters in the caller's order, then the level parameters in
+// level order, NP per block: a block's column slots come first and stand for consecutive rows of dcol (blk: their number
+// and gases), a row's level entries come in level order without a sort of their own.
+struct LevelJacPlan {
+  int n_blocks;
+  std::vector<int> blk, ent_off, slot_par;
+  std::vector<LevelEnt> ent;
+};
+static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev, const int32_t *par_level, const double *par_c,
+                                   int n_layers) {
+  const int n_par = n_col + n_lev, np = level_jac_np(n_par), n_blocks = (n_par + np - 1) / np;
+  const std::vector<int> order = order_by_level(n_lev, par_level);
+  LevelJacPlan P{n_blocks, std::vector<int>((size_t)n_blocks * 2, 0), std::vector<int>((size_t)n_blocks * (n_layers + 1)),
+                 std::vector<int>((size_t)n_blocks * np, -1), {}};
+  for (int b = 0; b < n_blocks; ++b) {
+    const int i0 = b * np, i1 = std::min(n_par, i0 + np), nc = std::max(0, std::min(n_col, i1) - i0);
+    unsigned gases = 0u;
+    for (int i = i0; i < i0 + nc; ++i) gases |= (unsigned)par_gas[i] << (2 * (i - i0));
+    P.blk[2 * b] = nc;
+    P.blk[2 * b + 1] = (int)gases;
+    for (int i = i0; i < i1; ++i) P.slot_par[i] = i < n_col ? i : n_col + order[i - n_col];
+    for (int r = 0; r < n_layers; ++r) {
+      P.ent_off[(size_t)b * (n_layers + 1) + r] = (int)P.ent.size();
+      for (int i = std::max(i0, n_col); i < i1; ++i) {
+        const int p = order[i - n_col];
+        const double c = par_c[(size_t)p * n_layers + r];
+        if (c != 0.0) P.ent.push_back(LevelEnt{i - i0, par_level[p], c});
+      }
+    }
+    P.ent_off[(size_t)b * (n_layers + 1) + n_layers] = (int)P.ent.size();
+  }
+  return P;
+}
+
+// What both entries below do once their arguments are checked: plan, stage, launch, mark.  cols: the kernel instance
+// with column slots (the state call, with n_col == 0 too); without it n_col is 0 and neither blk nor dcol exists.
+static int limb_jac_state(bool cols, const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
+                          const LosShape &shape, int n_col, const int32_t *par_gas, const double *par_w, int gas,
+                          const double *tab, int n_tab_rows, const int32_t *coef_row, int n_lev, const int32_t *par_level,
+                          const double *par_c, double *rad, double *jac, hipStream_t st) {
+  const LevelJacPlan P = level_jac_plan(n_col, par_gas, n_lev, par_level, par_c, n_layers);
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_ent = pk.copy(P.ent.data(), P.ent.size(), 1); // (no entries: a valid pointer all the same)
+  const auto p_row = n_lev > 0 ? pk.copy(coef_row, (size_t)n_layers) : pk.zeros<int32_t>((size_t)n_layers);
+  const auto p_off = pk.copy(P.ent_off.data(), P.ent_off.size()), p_slot = pk.copy(P.slot_par.data(), P.slot_par.size());
+  const auto p_blk = pk.copy(P.blk.data(), P.blk.size());
+  int rc = pk.stage(st);
+  if (rc) return rc;
+  LosDev D;
+  rc = stage_los(los, shape, n_col, par_gas, par_w, st, &D);
+  if (rc) return rc;
+  LAUNCHCHK(launch_limb_jac_state(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col,
+                                  cols ? D.col + (size_t)los->n_gas * D.n_seg : nullptr, limb_opts(los, D.n_seg), gas, tab,
+                                  n_tab_rows, pk.dev(p_row), P.n_blocks, cols ? pk.dev(p_blk) : nullptr, pk.dev(p_off),
+                                  pk.dev(p_ent), pk.dev(p_slot), n_col + n_lev, rad, jac, st));
+  return mark_both(pk.slot(), *D.slot, st);
+}
+
 int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
                                const sr_los_desc *los, int gas, const double *tab, int n_levels, int n_tab_rows,
                                const int32_t *coef_row, int n_par, const int32_t *par_level, const double *par_c,
@@ -3363,38 +3422,8 @@ int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_l
   if (!coef_rows_in_range(coef_row, n_layers, n_tab_rows)) return SR_ERR_ARG;
   for (int p = 0; p < n_par; ++p)
     if (par_level[p] < 0 || par_level[p] >= n_levels) return SR_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // parameters in level order, NP per block: a row's entries come in level order without a sort of their own
-  const int np = level_jac_np(n_par), n_blocks = (n_par + np - 1) / np;
-  const std::vector<int> order = order_by_level(n_par, par_level);
-  std::vector<int> ent_off((size_t)n_blocks * (n_layers + 1)), slot_par((size_t)n_blocks * np, -1);
-  std::vector<LevelEnt> ent;
-  for (int b = 0; b < n_blocks; ++b) {
-    const int i0 = b * np, i1 = std::min(n_par, i0 + np);
-    for (int i = i0; i < i1; ++i) slot_par[i] = order[i];
-    for (int r = 0; r < n_layers; ++r) {
-      ent_off[(size_t)b * (n_layers + 1) + r] = (int)ent.size();
-      for (int i = i0; i < i1; ++i) {
-        const double c = par_c[(size_t)order[i] * n_layers + r];
-        if (c != 0.0) ent.push_back(LevelEnt{i - i0, par_level[order[i]], c});
-      }
-    }
-    ent_off[(size_t)b * (n_layers + 1) + n_layers] = (int)ent.size();
-  }
-  static thread_local StagerRing ring;
-  StagePack pk(ring.take());
-  const auto p_ent = pk.copy(ent.data(), ent.size());
-  const auto p_row = pk.copy(coef_row, (size_t)n_layers), p_off = pk.copy(ent_off.data(), ent_off.size());
-  const auto p_slot = pk.copy(slot_par.data(), slot_par.size());
-  rc = pk.stage(st);
-  if (rc) return rc;
-  LosDev D;
-  rc = stage_los(los, shape, 0, nullptr, nullptr, st, &D);
-  if (rc) return rc;
-  LAUNCHCHK(launch_limb_jac_level(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col,
-                                  limb_opts(los, D.n_seg), gas, tab, n_tab_rows, pk.dev(p_row), n_blocks, pk.dev(p_off),
-                                  pk.dev(p_ent), pk.dev(p_slot), n_par, rad, jac, st));
-  return mark_both(pk.slot(), *D.slot, st);
+  return limb_jac_state(false, abs_c, emi_c, n_layers, n_pts, los, shape, 0, nullptr, nullptr, gas, tab, n_tab_rows, coef_row,
+                        n_par, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream));
 }
 
 int sr_limb_rays_jac_state_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
@@ -3413,46 +3442,8 @@ int sr_limb_rays_jac_state_dev(const double *abs_c, const double *emi_c, int n_l
   for (int p = 0; p < n_lev; ++p)
     if (par_level[p] < 0 || par_level[p] >= n_levels) return SR_ERR_ARG;
   if ((int64_t)n_col + n_lev > INT_MAX) return SR_ERR_LIMIT;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // the column parameters in the caller's order, then the level parameters in level order, NP per block: a block's
-  // column slots come first and stand for consecutive rows of dcol, a row's level entries come in level order
-  const int n_par = n_col + n_lev, np = level_jac_np(n_par), n_blocks = (n_par + np - 1) / np;
-  const std::vector<int> order = order_by_level(n_lev, par_level);
-  std::vector<int> ent_off((size_t)n_blocks * (n_layers + 1)), slot_par((size_t)n_blocks * np, -1), blk((size_t)n_blocks * 2, 0);
-  std::vector<LevelEnt> ent;
-  for (int b = 0; b < n_blocks; ++b) {
-    const int i0 = b * np, i1 = std::min(n_par, i0 + np), nc = std::max(0, std::min(n_col, i1) - i0);
-    unsigned gases = 0u;
-    for (int i = i0; i < i0 + nc; ++i) gases |= (unsigned)par_gas[i] << (2 * (i - i0));
-    blk[2 * b] = nc;
-    blk[2 * b + 1] = (int)gases;
-    for (int i = i0; i < i1; ++i) slot_par[i] = i < n_col ? i : n_col + order[i - n_col];
-    for (int r = 0; r < n_layers; ++r) {
-      ent_off[(size_t)b * (n_layers + 1) + r] = (int)ent.size();
-      for (int i = std::max(i0, n_col); i < i1; ++i) {
-        const int p = order[i - n_col];
-        const double c = par_c[(size_t)p * n_layers + r];
-        if (c != 0.0) ent.push_back(LevelEnt{i - i0, par_level[p], c});
-      }
-    }
-    ent_off[(size_t)b * (n_layers + 1) + n_layers] = (int)ent.size();
-  }
-  static thread_local StagerRing ring;
-  StagePack pk(ring.take());
-  const auto p_ent = pk.copy(ent.data(), ent.size(), 1);
-  const auto p_row = n_lev > 0 ? pk.copy(coef_row, (size_t)n_layers) : pk.zeros<int32_t>((size_t)n_layers);
-  const auto p_off = pk.copy(ent_off.data(), ent_off.size()), p_slot = pk.copy(slot_par.data(), slot_par.size());
-  const auto p_blk = pk.copy(blk.data(), blk.size());
-  rc = pk.stage(st);
-  if (rc) return rc;
-  LosDev D;
-  rc = stage_los(los, shape, n_col, par_gas, par_w, st, &D);
-  if (rc) return rc;
-  LAUNCHCHK(launch_limb_jac_state(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col,
-                                  D.col + (size_t)los->n_gas * D.n_seg, limb_opts(los, D.n_seg), gas, tab, n_tab_rows,
-                                  pk.dev(p_row), n_blocks, pk.dev(p_blk), pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot), n_par,
-                                  rad, jac, st));
-  return mark_both(pk.slot(), *D.slot, st);
+  return limb_jac_state(true, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, gas, tab, n_tab_rows, coef_row,
+                        n_lev, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream));
 }
 
 int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,

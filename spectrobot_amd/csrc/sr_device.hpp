@@ -361,6 +361,10 @@ __device__ inline Atten attenuation(double tau) {
   A.f = A.thin ? 1.0 : A.em1 * A.rtau;
   return A;
 }
+// f'(tau) = (tau e^-tau - (1 - e^-tau)) / tau^2 of the same segment (-1/2 where |tau| <= 1e-12)
+__device__ __forceinline__ double atten_fprime(const Atten &A, double tau) {
+  return A.thin ? -0.5 : (tau * A.t - A.em1) * (A.rtau * A.rtau);
+}
 
 // Regions 3 and 4 at c2 = (a, b) = ((double)(float)ry, (double)(float)(-rx)): cmplx() is
 // default kind, both parts are rounded to single (lineshape.f:529).

@@ -2994,11 +2994,10 @@ __global__ __launch_bounds__(256) void sr_radiance_jac_layer_kernel(
     const double u = seg_col[s], a = abs_c[o], e = emi_c[o];
     const double tau = a * u;
     const Atten A = attenuation(tau);
-    const double t = A.t, em1 = A.em1, f = A.f;
-    const bool thin = A.thin;
+    const double t = A.t, f = A.f;
     const double src = (e * u) * f;
     if (k >= p0 && k < p0 + NP) { // this segment's layer is one of this thread's parameters
-      const double fp = thin ? -0.5 : (tau * t - em1) * (A.rtau * A.rtau);
+      const double fp = atten_fprime(A, tau);
       const double da = dabs[o], de = demi[o];
       const double d = I * (-u * t * da) + u * f * de + e * u * u * fp * da;
 #pragma unroll
@@ -3023,8 +3022,8 @@ __global__ __launch_bounds__(256) void sr_radiance_jac_layer_kernel(
 //                           solo_absorption / initial_intensity (Planck) (radtran_3D_ch4.py:297-315)
 //   sr_limb_jac_kernel      + derivatives w.r.t. VMR-profile parameters (columns linear in them)
 //   sr_limb_jac_layer_kernel  + derivatives w.r.t. one scalar per layer acting through the coefficients
-//   sr_limb_jac_level_kernel  + derivatives w.r.t. level populations / vibrational temperatures of a level-factored gas
-//   sr_limb_jac_state_kernel  + both of these kinds, column and level parameters, in the accumulators of one pass
+//   sr_limb_jac_state_kernel  + derivatives w.r.t. level populations / vibrational temperatures of a level-factored gas,
+//                             alone or with column parameters in the accumulators of the same pass
 //   (all three: forward sensitivities, NP parameters per thread; many parameters / layers: sr_limb_adjoint_kernel below)
 //   sr_limb_parts_kernel    the radiance split into the parts single gases / single levels emit, and the background
 // Per segment s of a ray, layer k = seg_layer[s], columns u_g = col[g][s]:
@@ -3125,6 +3124,12 @@ inline void by_ngas(int n_gas, F &&f) {
     default: f(std::integral_constant<int, 4>{}); break;
   }
 }
+// by_level_np: f(integral_constant<int, NP>) for the accumulators per thread level_jac_np() / limb_parts_np() chose.
+template <class F>
+inline void by_level_np(int np, F &&f) {
+  if (np == kLevelJacNPLarge) f(std::integral_constant<int, kLevelJacNPLarge>{});
+  else f(std::integral_constant<int, kLevelJacNPSmall>{});
+}
 // by_jac_kinds: f(bool_constant<per-layer>, bool_constant<per-parameter>) for the Jacobians a one-pass call asks for.
 // (false, false) does not exist as a kernel: a call without per-layer Jacobians is a per-parameter one.
 template <class F>
@@ -3132,6 +3137,18 @@ inline void by_jac_kinds(bool layer, bool par, F &&f) {
   if (layer && par) f(std::true_type{}, std::true_type{});
   else if (layer) f(std::true_type{}, std::false_type{});
   else f(std::false_type{}, std::true_type{});
+}
+
+// abs / emi of every gas at ofs = row n_pts + point: one segment's coefficients in the ray-batch kernels that load a
+// segment ahead (where the loads are interleaved with those of the columns they are written out).
+template <int NG>
+__device__ __forceinline__ void limb_load_coef(const double *__restrict__ abs_c, const double *__restrict__ emi_c, size_t gstride,
+                                               size_t ofs, double (&a)[NG], double (&e)[NG]) {
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    a[g] = abs_c[g * gstride + ofs];
+    e[g] = emi_c[g * gstride + ofs];
+  }
 }
 
 template <int NG>
@@ -3271,9 +3288,8 @@ __global__ __launch_bounds__(256) void sr_limb_jac_kernel(
       E = g == 0 ? e[g] * u : E + e[g] * u;
     }
     const Atten A = attenuation(tau);
-    const double t = A.t, em1 = A.em1, f = A.f;
-    const bool thin = A.thin;
-    const double fp = thin ? -0.5 : (tau * t - em1) * (A.rtau * A.rtau);
+    const double t = A.t, f = A.f;
+    const double fp = atten_fprime(A, tau);
     const double src = o.solo_absorption ? 0.0 : E * f;
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
@@ -3326,11 +3342,10 @@ __global__ __launch_bounds__(256) void sr_limb_jac_layer_kernel(
       }
     }
     const Atten A = attenuation(tau);
-    const double t = A.t, em1 = A.em1, f = A.f;
-    const bool thin = A.thin;
+    const double t = A.t, f = A.f;
     const double src = o.solo_absorption ? 0.0 : E * f;
     if (mine) {
-      const double fp = thin ? -0.5 : (tau * t - em1) * (A.rtau * A.rtau);
+      const double fp = atten_fprime(A, tau);
       const double d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
 #pragma unroll
       for (int q = 0; q < NP; ++q) J[q] = fma(J[q], t, (k == p0 + q) ? d : 0.0);
@@ -3345,114 +3360,32 @@ __global__ __launch_bounds__(256) void sr_limb_jac_layer_kernel(
     if (p0 + q < n_layers) jac[((size_t)ray * n_layers + p0 + q) * n_pts + j] = J[q];
 }
 
-// Derivatives w.r.t. LEVEL parameters of one level-factored gas (sr_limb_rays_jac_level_dev): the gas's coefficients
-// are abs[r] = sum_L pop[r][L] A_L[row[r]], emi[r] likewise with E_L (the pair tables of sr_glevel_pairs_dev), and
-// parameter p moves the population of level lev[p] on coefficient row r by c[p][r].  The per-layer recursion above
-// with dabs / demi replaced by table spectra times a host-side coefficient:
-//   dtau_L = u A_L[row[r]],  dE_L = u E_L[row[r]],  d_L = -I t dtau_L + dE_L f + E f' dtau_L   (once per level touched)
-//   J_p <- J_p t + c[p][r] d_lev[p]
-// NP accumulators per thread, blocks of NP parameters on blockIdx.z; the host sorts the parameters by level and lists,
-// per (parameter block, coefficient row), the entries (slot, level, c) with c != 0 in level order (LevelEnt): a block
-// works on one ray, so the list is wave-uniform -- scalar loads, scalar branches -- and a segment none of the block's
-// parameters touches costs NP multiplications.  Rays and point blocks by limb_block(): all rays of a point block on
-// one XCD, so that the table rows they share are read from HBM once.  The coefficients of the next segment are
-// loaded while the current one is worked on (a ray's segments are a dependent chain).
-template <int NG, int NP>
-__global__ __launch_bounds__(256) void sr_limb_jac_level_kernel(
-    const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
-    const int *__restrict__ seg_off, const int *__restrict__ seg_layer, const double *__restrict__ col, LimbOpts o,
-    int n_rays, int gas, const double *__restrict__ tab, int n_tab_rows, const int *__restrict__ coef_row,
-    const int *__restrict__ ent_off, const LevelEnt *__restrict__ ent, const int *__restrict__ slot_par, int n_par,
-    double *__restrict__ rad, double *__restrict__ jac) {
-  int pb, ray;
-  if (!limb_block((n_pts + 255) / 256, n_rays, pb, ray)) return;
-  const int j = pb * 256 + threadIdx.x;
-  if (j >= n_pts) return;
-  double I = limb_initial(o, jac, 0, j), J[NP]; // init_mode 1 is refused by the host for this kernel
-#pragma unroll
-  for (int q = 0; q < NP; ++q) J[q] = 0.0;
-  const int *eo = ent_off + (size_t)blockIdx.z * (n_layers + 1);
-  const int s0 = seg_off[ray], s1 = seg_off[ray + 1];
-  const size_t gstride = (size_t)n_layers * n_pts, plane = (size_t)n_tab_rows * n_pts;
-  double an[NG], en[NG];
-  if (s0 < s1) {
-    const size_t ofs = (size_t)seg_layer[s0] * n_pts + j;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      an[g] = abs_c[g * gstride + ofs];
-      en[g] = emi_c[g * gstride + ofs];
-    }
-  }
-  for (int s = s0; s < s1; ++s) {
-    const int r = seg_layer[s];
-    double tau = 0.0, E = 0.0, ug = 0.0;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const double u = col[(size_t)g * o.n_seg_total + s];
-      tau = g == 0 ? an[g] * u : tau + an[g] * u;
-      E = g == 0 ? en[g] * u : E + en[g] * u;
-      ug = g == gas ? u : ug;
-    }
-    {
-      const size_t ofs = (size_t)seg_layer[min(s + 1, s1 - 1)] * n_pts + j;
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        an[g] = abs_c[g * gstride + ofs];
-        en[g] = emi_c[g * gstride + ofs];
-      }
-    }
-    const Atten A = attenuation(tau);
-    const double t = A.t, em1 = A.em1, f = A.f;
-    const bool thin = A.thin;
-    const double src = o.solo_absorption ? 0.0 : E * f;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) J[q] *= t;
-    const int e0 = eo[r], e1 = eo[r + 1];
-    if (e0 < e1) {
-      const double fp = thin ? -0.5 : (tau * t - em1) * (A.rtau * A.rtau);
-      const double *tr = tab + (size_t)coef_row[r] * n_pts + j;
-      int lev = -1;
-      double d = 0.0;
-      for (int i = e0; i < e1; ++i) {
-        const int slot = ent[i].slot, lv = ent[i].level;
-        if (lv != lev) { // (entries in level order: two loads and one d per distinct level)
-          lev = lv;
-          const double *tl = tr + (size_t)lv * 2 * plane;
-          const double dtau = ug * tl[0], dE = ug * tl[plane];
-          d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
-        }
-        const double v = ent[i].c * d;
-#pragma unroll
-        for (int q = 0; q < NP; ++q) J[q] += q == slot ? v : 0.0;
-      }
-    }
-    I = I * t + src;
-  }
-  if (blockIdx.z == 0 && rad) rad[(size_t)ray * n_pts + j] = I;
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    const int p = slot_par[blockIdx.z * NP + q];
-    if (p >= 0) jac[((size_t)ray * n_par + p) * n_pts + j] = J[q];
-  }
-}
-
-// Derivatives w.r.t. a MIXED state vector in one pass (sr_limb_rays_jac_state_dev): column parameters as in
-// sr_limb_jac_kernel and level parameters as in sr_limb_jac_level_kernel feed the same recursion,
+// Derivatives w.r.t. LEVEL parameters of one level-factored gas (sr_limb_rays_jac_level_dev, COLS = false) or w.r.t. a
+// MIXED state vector of column and level parameters in one pass (sr_limb_rays_jac_state_dev, COLS = true).  The gas's
+// coefficients are abs[r] = sum_L pop[r][L] A_L[row[r]], emi[r] likewise with E_L (the pair tables of
+// sr_glevel_pairs_dev), and level parameter p moves the population of level lev[p] on coefficient row r by c[p][r].
+// Both kinds feed the same recursion,
 //   J_p <- J_p t + (-I t dtau_p + dE_p f + E f' dtau_p),
 // and differ only in where dtau_p and dE_p come from:
-//   column parameter of gas g:  dtau = a_g D,  dE = e_g D,  D = dcol[p][s]
-//   level parameter of level L: dtau = c u A_L[row[r]],  dE = c u E_L[row[r]]   (u the column of `gas`, c = c[p][r])
-// so a ray is walked once per block of NP parameters whatever their kinds.  The host lists the column parameters first
-// (caller's order), then the level parameters in level order, and cuts the list into blocks of NP: in a block the
-// column slots are slots 0 .. nc - 1 and stand for the consecutive parameters blockIdx.z NP + q (their dcol rows need
-// no index table), the level slots follow in level order with their entry lists (LevelEnt, as the level kernel's).
-// blk [n_blocks][2] = nc, and the column slots' gases, two bits each.  A block works on one ray, so nc, the gases, the
-// D and the entry lists are wave-uniform: scalar loads, scalar branches, the accumulators indexed statically.  A
-// column slot costs its D (a scalar load, all of a segment's issued together ahead of the exponential), a multiplication
-// and an FMA on top of one (dsrc - I t a_g) per gas; a segment none of the block's level slots touches costs them J *= t.  The
-// arithmetic of either kind is that of its own kernel, operation for operation.  Coefficients of segment s + 1 are
-// loaded while s is worked on; rays and point blocks by limb_block().
-template <int NG, int NP>
+//   column parameter of gas g (as sr_limb_jac_kernel):  dtau = a_g D,  dE = e_g D,  D = dcol[p][s]
+//   level parameter of level L:  dtau = c u A_L[row[r]],  dE = c u E_L[row[r]]   (u the column of `gas`, c = c[p][r];
+//                                the per-layer recursion above with dabs / demi replaced by table spectra times c)
+// so a ray is walked once per block of NP parameters whatever their kinds: NP accumulators per thread, blocks of NP
+// parameters on blockIdx.z.  The host lists the column parameters first (caller's order), then the level parameters in
+// level order, and cuts the list into blocks of NP: in a block the column slots are slots 0 .. nc - 1 and stand for the
+// consecutive parameters blockIdx.z NP + q (their dcol rows need no index table), the level slots follow in level order.
+// blk [n_blocks][2] = nc, and the column slots' gases, two bits each.  Per (parameter block, coefficient row) the host
+// lists the entries (slot, level, c) with c != 0 in level order (LevelEnt): one d = -I t dtau_L + dE_L f + E f' dtau_L
+// per level touched, J_slot += c d per entry.  A block works on one ray, so nc, the gases, the D and the entry lists are
+// wave-uniform: scalar loads, scalar branches, the accumulators indexed statically.  A column slot costs its D (a scalar
+// load, all of a segment's issued together ahead of the exponential), a multiplication and an FMA on top of one
+// (dsrc - I t a_g) per gas; a segment none of the block's level slots touches costs them J *= t.
+// COLS = false compiles every column-slot line out: dcol and blk are never read and may be null, all slots are level
+// slots.  The level slots' arithmetic is the same in both instances, operation for operation.
+// Coefficients of segment s + 1 are loaded while s is worked on (a ray's segments are a dependent chain); rays and
+// point blocks by limb_block(): all rays of a point block on one XCD, so that the table rows they share are read from
+// HBM once.
+template <int NG, int NP, bool COLS>
 __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
     const int *__restrict__ seg_off, const int *__restrict__ seg_layer, const double *__restrict__ col,
@@ -3468,21 +3401,14 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
   double I = limb_initial(o, jac, 0, j), J[NP]; // init_mode 1 is refused by the host for this kernel
 #pragma unroll
   for (int q = 0; q < NP; ++q) J[q] = 0.0;
-  const int nc = blk[2 * blockIdx.z];
-  const unsigned gw = (unsigned)blk[2 * blockIdx.z + 1];
+  const int nc = COLS ? blk[2 * blockIdx.z] : 0;
+  const unsigned gw = COLS ? (unsigned)blk[2 * blockIdx.z + 1] : 0u;
   const double *dc = dcol + (size_t)blockIdx.z * NP * o.n_seg_total; // (read with nc > 0 only)
   const int *eo = ent_off + (size_t)blockIdx.z * (n_layers + 1);
   const int s0 = seg_off[ray], s1 = seg_off[ray + 1];
   const size_t gstride = (size_t)n_layers * n_pts, plane = (size_t)n_tab_rows * n_pts;
   double an[NG], en[NG];
-  if (s0 < s1) {
-    const size_t ofs = (size_t)seg_layer[s0] * n_pts + j;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      an[g] = abs_c[g * gstride + ofs];
-      en[g] = emi_c[g * gstride + ofs];
-    }
-  }
+  if (s0 < s1) limb_load_coef<NG>(abs_c, emi_c, gstride, (size_t)seg_layer[s0] * n_pts + j, an, en);
   for (int s = s0; s < s1; ++s) {
     const int r = seg_layer[s];
     double a[NG], e[NG], D[NP];
@@ -3500,14 +3426,7 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
 #pragma unroll
       for (int q = 0; q < NP; ++q) D[q] = dc[(size_t)min(q, nc - 1) * o.n_seg_total + s];
     }
-    {
-      const size_t ofs = (size_t)seg_layer[min(s + 1, s1 - 1)] * n_pts + j;
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        an[g] = abs_c[g * gstride + ofs];
-        en[g] = emi_c[g * gstride + ofs];
-      }
-    }
+    limb_load_coef<NG>(abs_c, emi_c, gstride, (size_t)seg_layer[min(s + 1, s1 - 1)] * n_pts + j, an, en);
     const Atten A = attenuation(tau);
     const double t = A.t, em1 = A.em1, f = A.f;
     const bool thin = A.thin;
@@ -3527,10 +3446,10 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     // where they are used)
     int ncs = nc;
     unsigned gws = gw;
-    asm volatile("" : "+s"(ncs), "+s"(gws));
+    if constexpr (COLS) asm volatile("" : "+s"(ncs), "+s"(gws));
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
-      if (q < ncs) { // a column slot: sr_limb_jac_kernel's update
+      if (COLS && q < ncs) { // a column slot: sr_limb_jac_kernel's update
         if constexpr (NG == 1) {
           J[q] = fma(J[q], t, W[0] * D[q]);
         } else { // the gas is chosen on the scalar side: D or 0 per gas, the products with 0 add nothing
@@ -3544,7 +3463,7 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
         J[q] *= t;
       }
     }
-    if (e0 < e1) { // the level slots: sr_limb_jac_level_kernel's update
+    if (e0 < e1) { // the level slots
       const double *tr = tab + (size_t)coef_row[r] * n_pts + j;
       int lev = -1;
       double d = 0.0;
@@ -3610,12 +3529,7 @@ __device__ __forceinline__ void limb_parts_segment(
   const int rn = seg_layer[min(s + 1, s1 - 1)];
   const unsigned mn = s + 1 < s1 && !o.solo_absorption ? words[rn] : 0u;
   {
-    const size_t ofs = (size_t)rn * n_pts + j;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      an[g] = abs_c[g * gstride + ofs];
-      en[g] = emi_c[g * gstride + ofs];
-    }
+    limb_load_coef<NG>(abs_c, emi_c, gstride, (size_t)rn * n_pts + j, an, en);
     if (NG > 1 && mn) cnxt = cc[(size_t)rn * NP];
     if (mn >> 16) {
       if (NG == 1) cnxt = cc[(size_t)rn * NP];
@@ -3688,12 +3602,7 @@ __global__ __launch_bounds__(256) void sr_limb_parts_kernel(
   unsigned m = 0u;
   if (s0 < s1) {
     const int r = seg_layer[s0];
-    const size_t ofs = (size_t)r * n_pts + j;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      an[g] = abs_c[g * gstride + ofs];
-      en[g] = emi_c[g * gstride + ofs];
-    }
+    limb_load_coef<NG>(abs_c, emi_c, gstride, (size_t)r * n_pts + j, an, en);
     m = o.solo_absorption ? 0u : words[r];
     if (NG > 1 && m) ca = cc[(size_t)r * NP];
     if (m >> 16) {
@@ -3850,7 +3759,7 @@ __global__ __launch_bounds__(256) void sr_limb_adjoint_kernel(
         }
       }
       const Atten A = attenuation(tau);
-      const double fp = A.thin ? -0.5 : (tau * A.t - A.em1) * (A.rtau * A.rtau);
+      const double fp = atten_fprime(A, tau);
       {
         const double sm = rem - tau, bb = sm - rem;
         rem_lo += (rem - (sm - bb)) + (-tau - bb);
@@ -3986,7 +3895,7 @@ __global__ __launch_bounds__(256) void sr_limb_adjoint_sync_kernel(
         }
       }
       const Atten A = attenuation(tau);
-      const double fp = A.thin ? -0.5 : (tau * A.t - A.em1) * (A.rtau * A.rtau);
+      const double fp = atten_fprime(A, tau);
       {
         const double sm = rem[r] - tau, bb = sm - rem[r];
         rem_lo[r] += (rem[r] - (sm - bb)) + (-tau - bb);
@@ -4550,7 +4459,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NG <= 2 ? 4
         }
         if (solo) E = 0.0;
         const Atten A = attenuation_sc(tau);
-        const double fp = A.thin ? -0.5 : (tau * A.t - A.em1) * (A.rtau * A.rtau);
+        const double fp = atten_fprime(A, tau);
         const double Ef = E * A.f, we = solo ? 0.0 : A.f;
         double t_f = 1.0, nEfTn = 0.0, bf[NG], wn[NG];
 #pragma unroll
@@ -4878,24 +4787,6 @@ int launch_limb_jac_layer(const double *abs_c, const double *emi_c, const double
   return (int)hipGetLastError();
 }
 
-int launch_limb_jac_level(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
-                          const int *seg_layer, const double *col, const LimbOpts &o, int gas, const double *tab,
-                          int n_tab_rows, const int *coef_row, int n_blocks, const int *ent_off, const LevelEnt *ent,
-                          const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st) {
-  if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0) return 0;
-  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
-  auto launch = [&](auto np) {
-    by_ngas(o.n_gas, [&](auto ng) {
-      hipLaunchKernelGGL((sr_limb_jac_level_kernel<decltype(ng)::value, decltype(np)::value>), grid, dim3(256), 0, st, abs_c, emi_c,
-                         n_pts, n_layers, seg_off, seg_layer, col, o, n_rays, gas, tab, n_tab_rows, coef_row, ent_off, ent, slot_par,
-                         n_par, rad, jac);
-    });
-  };
-  if (level_jac_np(n_par) == kLevelJacNPLarge) launch(std::integral_constant<int, kLevelJacNPLarge>{});
-  else launch(std::integral_constant<int, kLevelJacNPSmall>{});
-  return (int)hipGetLastError();
-}
-
 int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
                           const int *seg_layer, const double *col, const double *dcol, const LimbOpts &o, int gas,
                           const double *tab, int n_tab_rows, const int *coef_row, int n_blocks, const int *blk,
@@ -4903,15 +4794,17 @@ int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, i
                           hipStream_t st) {
   if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0) return 0;
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
-  auto launch = [&](auto np) {
-    by_ngas(o.n_gas, [&](auto ng) {
-      hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value>), grid, dim3(256), 0, st, abs_c, emi_c,
-                         n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas, tab, n_tab_rows, coef_row, blk, ent_off, ent,
-                         slot_par, n_par, rad, jac);
+  auto launch = [&](auto cols) { // no blk: the instance without column slots
+    by_level_np(level_jac_np(n_par), [&](auto np) {
+      by_ngas(o.n_gas, [&](auto ng) {
+        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value>), grid,
+                           dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas, tab,
+                           n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac);
+      });
     });
   };
-  if (level_jac_np(n_par) == kLevelJacNPLarge) launch(std::integral_constant<int, kLevelJacNPLarge>{});
-  else launch(std::integral_constant<int, kLevelJacNPSmall>{});
+  if (blk) launch(std::true_type{});
+  else launch(std::false_type{});
   return (int)hipGetLastError();
 }
 
@@ -4921,15 +4814,13 @@ int launch_limb_parts(const double *abs_c, const double *emi_c, int n_pts, int n
                       const int *slot_part, int n_part, double *rad, double *parts, hipStream_t st) {
   if (n_pts <= 0 || n_rays <= 0 || n_part <= 0 || n_blocks <= 0) return 0;
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
-  auto launch = [&](auto np) {
+  by_level_np(limb_parts_np(n_part), [&](auto np) {
     by_ngas(o.n_gas, [&](auto ng) {
       hipLaunchKernelGGL((sr_limb_parts_kernel<decltype(ng)::value, decltype(np)::value>), grid, dim3(256), 0, st, abs_c, emi_c, n_pts,
                          n_layers, seg_off, seg_layer, col, o, n_rays, gas, tab, coef_row, words, cc, slot_level, slot_part, n_part,
                          rad, parts);
     });
-  };
-  if (limb_parts_np(n_part) == kLevelJacNPLarge) launch(std::integral_constant<int, kLevelJacNPLarge>{});
-  else launch(std::integral_constant<int, kLevelJacNPSmall>{});
+  });
   return (int)hipGetLastError();
 }
 

@@ -239,23 +239,19 @@ int launch_limb_jac(const double *abs_c, const double *emi_c, int n_pts, int n_l
 int launch_limb_jac_layer(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
                           int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
                           const LimbOpts &o, double *jac, hipStream_t st);
-// Level-parameter Jacobians of one level-factored gas (sr_limb_jac_level_kernel): blocks of level_jac_np(n_par)
-// parameters; ent_off [n_blocks][n_layers + 1] into ent, the entries of every (parameter block, coefficient row) with a
-// non-zero coefficient, in level order; slot_par [n_blocks][NP] = the parameter an accumulator belongs to, or -1.
+// Level-parameter and mixed-state Jacobians (sr_limb_jac_state_kernel): n_par = n_col + n_lev parameters, the column
+// parameters first (rows of dcol, caller's order), then the level parameters of one level-factored gas in level order, in
+// blocks of level_jac_np(n_par); blk [n_blocks][2] = the number of column slots of a block (its first slots: parameters
+// block NP + q) and their gases, two bits per slot; ent_off [n_blocks][n_layers + 1] into ent, the entries of every
+// (parameter block, coefficient row) with a non-zero coefficient, in level order, slot numbers counted over all slots of
+// a block; slot_par [n_blocks][NP] = the parameter an accumulator belongs to, or -1.  blk == nullptr: level parameters
+// only (n_col = 0), the kernel instance without column code; dcol is not read and may be null too.
 struct __attribute__((aligned(16))) LevelEnt {
   int slot, level; // accumulator of the block, level of the pair tables
   double c;        // d pop[row][level] / d x_p
 };
 constexpr int kLevelJacNPSmall = 8, kLevelJacNPLarge = 16;
 inline int level_jac_np(int n_par) { return n_par > kLevelJacNPSmall ? kLevelJacNPLarge : kLevelJacNPSmall; }
-int launch_limb_jac_level(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
-                          const int *seg_layer, const double *col, const LimbOpts &o, int gas, const double *tab,
-                          int n_tab_rows, const int *coef_row, int n_blocks, const int *ent_off, const LevelEnt *ent,
-                          const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st);
-// Mixed state vector (sr_limb_jac_state_kernel): n_par = n_col + n_lev parameters, the column parameters first (rows of
-// dcol, caller's order), then the level parameters in level order, in blocks of level_jac_np(n_par); blk [n_blocks][2] =
-// the number of column slots of a block (its first slots: parameters block NP + q) and their gases, two bits per slot;
-// ent_off / ent / slot_par as launch_limb_jac_level, slot numbers counted over all slots of a block.
 int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
                           const int *seg_layer, const double *col, const double *dcol, const LimbOpts &o, int gas,
                           const double *tab, int n_tab_rows, const int *coef_row, int n_blocks, const int *blk,

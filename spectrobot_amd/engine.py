@@ -1080,6 +1080,22 @@ def limb_rays_jacobians(coeffs, los, dcoeffs=None, par_gas=None, par_w=None, gri
     return rad, jl, jp
 
 
+def _level_table_args(tab, coef_row, par_level, par_c, n_layers, n_pts, count):
+    """(n_levels, n_tab_rows, coef_row pointer, number of level parameters, par_level pointer, par_c pointer): the
+    level-table arguments of the two level Jacobians below, checked; `count` is what the caller's text calls the number."""
+    assert tab.is_cuda and tab.dtype == torch.float64 and tab.is_contiguous() and tab.dim() == 4 and tab.shape[1] == 2
+    if tab.shape[3] != n_pts:
+        raise ValueError("tables of %d points for coefficients of %d" % (tab.shape[3], n_pts))
+    coef_row, cr = _i(coef_row)
+    par_level, pl = _i(np.asarray(par_level).reshape(-1))
+    par_c, pc = _d(par_c)
+    if coef_row.shape != (n_layers,):
+        raise ValueError("coef_row must be [n_layers]")
+    if par_c.shape != (par_level.size, n_layers):
+        raise ValueError("par_c must be [%s, n_layers]" % count)
+    return int(tab.shape[0]), int(tab.shape[2]), cr, par_level.size, pl, pc
+
+
 def limb_rays_level_jacobian(coeffs, los, tab, coef_row, par_level, par_c, gas=0, grid=None, g_lo=0, want_rad=True):
     """(rad | None, jac [n_rays, n_par, n_pts]): radiances and their derivatives with respect to level parameters of
     the level-factored gas `gas` (sr_limb_rays_jac_level_dev).  coeffs as limb_rays; tab: that gas's pair tables (CUDA
@@ -1090,23 +1106,13 @@ def limb_rays_level_jacobian(coeffs, los, tab, coef_row, par_level, par_c, gas=0
     n_gas, n_layers, n_pts = a.shape
     if n_gas != los.n_gas:
         raise ValueError("%d coefficient sets for %d gases" % (n_gas, los.n_gas))
-    assert tab.is_cuda and tab.dtype == torch.float64 and tab.is_contiguous() and tab.dim() == 4 and tab.shape[1] == 2
-    if tab.shape[3] != n_pts:
-        raise ValueError("tables of %d points for coefficients of %d" % (tab.shape[3], n_pts))
-    coef_row, cr = _i(coef_row)
-    par_level, pl = _i(par_level)
-    par_c, pc = _d(par_c)
-    n_par = par_level.size
-    if coef_row.shape != (n_layers,):
-        raise ValueError("coef_row must be [n_layers]")
-    if par_c.shape != (n_par, n_layers):
-        raise ValueError("par_c must be [n_par, n_layers]")
+    n_levels, n_tab_rows, cr, n_par, pl, pc = _level_table_args(tab, coef_row, par_level, par_c, n_layers, n_pts, "n_par")
     rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
     jac = torch.empty((los.n_rays, n_par, n_pts), dtype=torch.float64, device="cuda")
     d = los.desc(grid, g_lo)
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    check(lib.sr_limb_rays_jac_level_dev(ptr(a), ptr(e), n_layers, n_pts, C.byref(d), int(gas), ptr(tab), int(tab.shape[0]),
-                                         int(tab.shape[2]), cr, n_par, pl, pc, ptr(rad), ptr(jac), _stream_ptr()),
+    check(lib.sr_limb_rays_jac_level_dev(ptr(a), ptr(e), n_layers, n_pts, C.byref(d), int(gas), ptr(tab), n_levels, n_tab_rows,
+                                         cr, n_par, pl, pc, ptr(rad), ptr(jac), _stream_ptr()),
           "sr_limb_rays_jac_level_dev")
     return rad, jac
 
@@ -1134,18 +1140,7 @@ def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, co
     if par_level is not None and np.asarray(par_level).size:
         if tab is None or coef_row is None or par_c is None:
             raise ValueError("level parameters need tab, coef_row and par_c")
-        assert tab.is_cuda and tab.dtype == torch.float64 and tab.is_contiguous() and tab.dim() == 4 and tab.shape[1] == 2
-        if tab.shape[3] != n_pts:
-            raise ValueError("tables of %d points for coefficients of %d" % (tab.shape[3], n_pts))
-        n_levels, n_tab_rows = int(tab.shape[0]), int(tab.shape[2])
-        coef_row, cr = _i(coef_row)
-        par_level, pl = _i(np.asarray(par_level).reshape(-1))
-        par_c, pc = _d(par_c)
-        n_lev = par_level.size
-        if coef_row.shape != (n_layers,):
-            raise ValueError("coef_row must be [n_layers]")
-        if par_c.shape != (n_lev, n_layers):
-            raise ValueError("par_c must be [n_lev, n_layers]")
+        n_levels, n_tab_rows, cr, n_lev, pl, pc = _level_table_args(tab, coef_row, par_level, par_c, n_layers, n_pts, "n_lev")
     if n_col + n_lev == 0:
         raise ValueError("no parameters: give column parameters, level parameters or both")
     rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None

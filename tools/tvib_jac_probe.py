@@ -87,5 +87,5 @@ a, b = np.median(res["new_call_ms"]), np.median(res["composition_ms"])
 print(json.dumps(dict(res, n_pts=n, n_rays=n_rays, n_steps=n_steps, table_rows=int(len(T_rows)), n_par=int(len(par_level)),
                       levels=list(levels), ratio_composition_over_new=round(float(b / a), 3),
                       new_vs_composition_row_err=agree,
-                      kernel="sr_limb_jac_level_kernel<1, 16>: 83 VGPRs, no spills (hipcc -Rpass-analysis=kernel-resource-usage)",
+                      kernel="sr_limb_jac_state_kernel<1, 16, false>: 83 VGPRs, no spills (tools/kernel_resources.sh)",
                       device=engine.device_info()["name"])))
