@@ -1312,7 +1312,7 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
     // the tables touch scratch of the call's own parity and nothing of the caller's, so they run on internal streams,
     // beside the previous call's kernels; only the wings kernel (zones' sums + near region 1 + polynomials -> abs / emi)
     // sits on the caller's stream.  Who runs beside whom is decided by what FITS beside whom
-    // (tools/r03_timeline.sh, tools/kernel_resources.sh): 16 zones waves fill a CU -- 120 VGPRs each, 4 x 120 of a
+    // (profiles/r04_timeline_*.txt, tools/kernel_resources.sh): 16 zones waves fill a CU -- 120 VGPRs each, 4 x 120 of a
     // SIMD's 512, and 16 x 10 KB = all of its LDS -- and a retiring zones wave frees exactly one such slot, which the
     // next zones wave takes unless the other kernel's wave fits it: the wings kernel (80 VGPRs), M2M / M2L (106 / 104)
     // and the one-wave blocks of the preparation (104 VGPRs, 5 KB) do, the level-0 pass (140) and S2M (154) do not and
@@ -1467,13 +1467,10 @@ static int level_set(sr_lineset *ls, int level, sr_lineset **out, bool up_only =
 //   ctypes3 = 0: out [n_levels][2][n_rows][n_pts], the pair tables of sr_glevel_pairs_dev
 //   ctypes3 = 1: out [n_levels][3][n_rows][n_pts], sp_emission | ind_emission | absorption (sr_gcoeff_levels_dev)
 // Returns SR_ERR_UNSUPPORTED (and does nothing) where the route does not apply -- exact mode, counting passes, more
-// channels than an LDS image holds, 80-byte records -- the callers then run one coefficient op per level.
+// channels than an LDS image holds -- the callers then run one coefficient op per level.
 // spect_main_module.py:1122-1168 (add_PT per level), spect_classes.py:1304-1321 (which lines a level owns).
 // ------------------------------------------------------------------------
 static int mc_pass(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi, double *out, void *stream, int ctypes3) {
-#if !SR_FASTREC64
-  return SR_ERR_UNSUPPORTED;
-#else
   const int nlev = ls->n_levels, n_rows = atm->n_layers;
   const int far_mode = g_far_field.load();
   if (nlev <= 0 || far_mode == 0 || g_counting.load() != 0 || g_level_route.load() == 0) return SR_ERR_UNSUPPORTED;
@@ -1742,7 +1739,6 @@ static int mc_pass(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
     w.last_done_recorded = true;
   }
   return SR_OK;
-#endif
 }
 
 extern "C" {
@@ -3112,7 +3108,6 @@ int limb_adjoint(const double *abs_c, const double *emi_c, const double *dabs, c
   const int jmode = g_jac_layer_forward.load();
   const bool two_rows = seg_jrow != nullptr;           // 3-D paths: a coefficient row per LOS step, shells = Jacobian rows
   const int n_sh = two_rows ? n_jrows : n_layers;      // shells
-  const int fold_rays = two_rows ? 1 : kAdjFoldRays;   // rays per thread of the folded kernel
   if (jmode == 0 || (jmode == 3 && nr >= 2 && !two_rows)) {
     // per ray: far[shell] / near[shell] = walk-order segment index or -1
     std::vector<int> far, near;
@@ -3129,18 +3124,16 @@ int limb_adjoint(const double *abs_c, const double *emi_c, const double *dabs, c
         if (any) shells.push_back(k);
       }
       n_fvis = (int)shells.size();
-      const int nb = (nr + fold_rays - 1) / fold_rays;
-      n_frec = nb * n_fvis * fold_rays;
+      n_frec = nr * n_fvis;
       fplan.assign((size_t)n_frec * kFoldPlanInts, 0);
       bool fits = true;
       std::vector<std::vector<int>> touch(n_par);
-      for (int rr = 0; rr < nb * fold_rays && fits; ++rr) {
-        const int bt = rr / fold_rays, i = rr % fold_rays;
-        auto rec_at = [&](int v) { return &fplan[(((size_t)bt * n_fvis + v) * fold_rays + i) * kFoldPlanInts]; };
+      auto rec_at = [&](int ray, int v) { return &fplan[((size_t)ray * n_fvis + v) * kFoldPlanInts]; };
+      for (int ray = 0; ray < nr && fits; ++ray) {
         for (int v = 0; v < n_fvis; ++v) {
-          int *pl = rec_at(v);
-          pl[1] = rr < nr ? far[(size_t)rr * n_sh + shells[v]] : -1;
-          pl[2] = rr < nr ? near[(size_t)rr * n_sh + shells[v]] : -1;
+          int *pl = rec_at(ray, v);
+          pl[1] = far[(size_t)ray * n_sh + shells[v]];
+          pl[2] = near[(size_t)ray * n_sh + shells[v]];
           // coefficient rows: the segments' own (a side without a segment takes the other's: its loads are not used)
           const int row_f = pl[1] >= 0 ? plan.seg[(size_t)pl[1] * kAdjPlanInts] : -1;
           const int row_n = pl[2] >= 0 ? plan.seg[(size_t)pl[2] * kAdjPlanInts] : -1;
@@ -3148,10 +3141,10 @@ int limb_adjoint(const double *abs_c, const double *emi_c, const double *dabs, c
           pl[12] = two_rows ? (row_n >= 0 ? row_n : std::max(row_f, 0)) : shells[v];
           pl[13] = shells[v];
         }
-        if (rr >= nr || n_par == 0) continue;
+        if (n_par == 0) continue;
         for (int p = 0; p < n_par; ++p) touch[p].clear();
         for (int v = 0; v < n_fvis; ++v) {
-          const int *pl = rec_at(v);
+          const int *pl = rec_at(ray, v);
           for (int side = 1; side <= 2; ++side) {
             if (pl[side] < 0) continue;
             const int *sp = &plan.seg[(size_t)pl[side] * kAdjPlanInts];
@@ -3161,7 +3154,7 @@ int limb_adjoint(const double *abs_c, const double *emi_c, const double *dabs, c
         }
         RunPlan runs(n_par);
         for (int v = 0; v < n_fvis && fits; ++v) {
-          int *pl = rec_at(v);
+          int *pl = rec_at(ray, v);
           pl[3] = runs.step(v, touch, par_gas, pl + 4, pl + 8);
           fits = pl[3] >= 0;
         }

@@ -190,9 +190,7 @@ __device__ __forceinline__ void prep_body(const LinesDev &L, const LayersDev &A,
   r.xr = B.xr;
   r.xstep = B.xstep;
   r1_set(r, B.ry);
-#if SR_FASTREC64
   r.w3 = ph.w3;
-#endif
   r.wabs = ph.wabs;
   r.wemi = ph.wemi;
   r.j1 = ic - kHalf;
@@ -741,21 +739,9 @@ __device__ inline int lane_reduce_index(int lane, bool &primary) {
 // COUNT: the instantiation sr_set_counting(1) selects; it adds the number of (line, box) expansions
 // this launch performs to cnt[kCntExpansions] (bench.py's executed-work accounting).  The timed
 // instantiation carries no counting code.
-// Tuning knob: waves per SIMD to compile for (4: <= 128 VGPRs; 140 unconstrained, 48 B of scratch at 128).  0 (default):
-// unconstrained.  Round 4 built this kernel and S2M to 128 VGPRs and padded the zones kernel to 128 so that their waves
-// fit the slot a retiring zones wave frees: the pass still ran 4.8 ms beside the zones kernel (the dispatcher serves
-// the OLDER dispatch first whenever its next workgroup fits, whatever the younger one needs) and the spills cost
-// 0.6 ms of the far-field group alone (1.07 -> 1.66 ms): step 6.07 vs 5.61 ms.
-#ifndef SR_FAR_WAVES_PER_EU
-#define SR_FAR_WAVES_PER_EU 0
-#endif
-#if SR_FAR_WAVES_PER_EU > 0
-#define SR_FAR_ATTR __attribute__((amdgpu_waves_per_eu(SR_FAR_WAVES_PER_EU)))
-#else
-#define SR_FAR_ATTR
-#endif
+// (Occupancy unconstrained, 140 VGPRs.  Built for 4 waves per SIMD, with S2M, to fit beside the zones kernel: 48 B of scratch, far-field group 1.07 -> 1.66 ms, step 6.07 vs 5.61 ms.)
 template <bool COUNT, bool M2L>
-__global__ __launch_bounds__(64) SR_FAR_ATTR void sr_farfield_kernel(const FastRec *__restrict__ fast,
+__global__ __launch_bounds__(64) void sr_farfield_kernel(const FastRec *__restrict__ fast,
                                                          IcIndex ix,
                                                          const int *__restrict__ zmax, int n_sub, int g_lo,
                                                          int /*g_hi*/, FarParams fp,
@@ -984,7 +970,7 @@ __global__ __launch_bounds__(64) SR_FAR_ATTR void sr_farfield_kernel(const FastR
 // steps instead of six).  Same expansions, same owner of every (line, box): the coefficients differ from
 // sr_farfield_kernel<., false>'s by the summation order.
 #ifndef SR_FAR_ROWS
-#define SR_FAR_ROWS 16 // layers per wave x 64 / that many lines.  8 x 8 through round 6 (degree 22: 16 x 4 and 4 x 16 lost, tools/r04_ab.sh);
+#define SR_FAR_ROWS 16 // layers per wave x 64 / that many lines.  8 x 8 through round 6 (degree 22: 16 x 4 and 4 x 16 lost);
                        // at degree 19 a table build of 12 levels: 16 x 4 11.94 / 23.92 ms (1e5 / 2e5 lines), 8 x 8 12.27 / 24.42, 4 x 16 13.45 / 26.74
 #endif
 constexpr int kFarRows = SR_FAR_ROWS, kFarLines = 64 / kFarRows; // lanes: kFarRows layers x kFarLines lines of a chunk
@@ -1148,16 +1134,9 @@ __device__ __forceinline__ void farfield_rows_body(const FastRec *__restrict__ f
   }
   if (COUNT) count_add(cnt, kCntExpansions, n_exp, lane);
 }
-#ifndef SR_ROWS_WAVES_PER_EU
-#define SR_ROWS_WAVES_PER_EU 0 // tuning knob: waves per SIMD to compile the sparse sets' kernels for (0: unconstrained, 138 VGPRs = 3; 4: 128 VGPRs + 48 B of scratch in the batch kernel: a table build 13.4 -> 15.1 ms)
-#endif
-#if SR_ROWS_WAVES_PER_EU > 0
-#define SR_ROWS_ATTR __attribute__((amdgpu_waves_per_eu(SR_ROWS_WAVES_PER_EU)))
-#else
-#define SR_ROWS_ATTR
-#endif
+// (The sparse sets' kernels: occupancy unconstrained, 138 VGPRs = 3 waves per SIMD; built for 4: 128 VGPRs + 48 B of scratch in the batch kernel, a table build 13.4 -> 15.1 ms.)
 template <bool COUNT>
-__global__ __launch_bounds__(64) SR_ROWS_ATTR void sr_farfield_rows_kernel(const FastRec *__restrict__ fast, IcIndex ix,
+__global__ __launch_bounds__(64) void sr_farfield_rows_kernel(const FastRec *__restrict__ fast, IcIndex ix,
                                                               const int *__restrict__ zmax, int n_sub, int g_lo, FarParams fp,
                                                               unsigned long long *__restrict__ cnt) {
   farfield_rows_body<COUNT, 1>(fast, ix, zmax, n_sub, g_lo, fp, cnt, xcd_remap_groups((int)blockIdx.x, (int)gridDim.x, 16));
@@ -1168,7 +1147,7 @@ __global__ __launch_bounds__(64) SR_ROWS_ATTR void sr_farfield_rows_kernel(const
 #define SR_ROWS_BATCH_WAVES 4
 #endif
 constexpr int kRowsBatchWaves = SR_ROWS_BATCH_WAVES; // waves (boxes) per workgroup of the batch kernel
-__global__ __launch_bounds__(64 * kRowsBatchWaves) SR_ROWS_ATTR void sr_farfield_rows_batch_kernel(const FarBatchItem *__restrict__ items, const int *__restrict__ zmax,
+__global__ __launch_bounds__(64 * kRowsBatchWaves) void sr_farfield_rows_batch_kernel(const FarBatchItem *__restrict__ items, const int *__restrict__ zmax,
                                                                     int g_lo, FarParams fp, int n_work) {
   const FarBatchItem it = items[blockIdx.y];
   fp.coef = it.coef;
@@ -1205,15 +1184,7 @@ __device__ constexpr double inv_factorial(int n) {
 // of 32 lines at a time, the upper half the left-going ones of the same lines, and each half sums its 2 kMQ values
 // over its own 32 lanes.  (A box holds 64 +- 8 lines on config 2: with 64 lines per step and one wave per side the
 // second step of most boxes ran nearly empty.)
-// as SR_FAR_WAVES_PER_EU (154 VGPRs unconstrained, 104 B of scratch at 128).  0 (default): unconstrained.
-#ifndef SR_S2M_WAVES_PER_EU
-#define SR_S2M_WAVES_PER_EU 0
-#endif
-#if SR_S2M_WAVES_PER_EU > 0
-#define SR_S2M_ATTR __attribute__((amdgpu_waves_per_eu(SR_S2M_WAVES_PER_EU)))
-#else
-#define SR_S2M_ATTR
-#endif
+// (Occupancy unconstrained, 154 VGPRs; built for 4 waves per SIMD like sr_farfield_kernel: 104 B of scratch.)
 // (one convolution per line about the MEAN of its two anchors + first-order corrections; round 3's one-per-side
 // variant is in the history: S2M 0.375 vs 0.31 ms)
 // Round 4: one moment set per line instead of one per side.  The two wings of a line use different anchors (the zero of
@@ -1228,7 +1199,7 @@ __device__ constexpr double inv_factorial(int n) {
 // M2L read what they always read.
 constexpr int kS2MCorr = 4; // corrected orders q = 3 .. 2 + kS2MCorr
 template <bool COUNT>
-__global__ __launch_bounds__(64) SR_S2M_ATTR void sr_s2m_kernel(const FastRec *__restrict__ fast, IcIndex ix, int n_sub, int g_lo,
+__global__ __launch_bounds__(64) void sr_s2m_kernel(const FastRec *__restrict__ fast, IcIndex ix, int n_sub, int g_lo,
                                                     FarParams fp, unsigned long long *__restrict__ cnt) {
   const int wid = xcd_remap(blockIdx.x, gridDim.x);
   const int layer = wid / fp.n_src[0], sb = wid - layer * fp.n_src[0];
@@ -1814,28 +1785,10 @@ __device__ inline void core_eval4(const CorePend &P, bool on, const GridParams &
 #ifndef SR_ZONES_ROW
 #define SR_ZONES_ROW 8 // lanes per row of the region-2 / region-4 walk: eight lines at a time (16: 4.35, 8: 4.1, 4: 4.87, 32: 5.09 ms)
 #endif
-#ifndef SR_RMAX
-#define SR_RMAX 0 // 1: the rows' step counts from the lanes = lines phase (s_rmax) instead of rows_max() per round
-#endif
-#ifndef SR_R2_SPLIT
-#define SR_R2_SPLIT 1 // region 2: the left and the right run of a line in two loops
-#endif
-#ifndef SR_R2_XRUN
-#define SR_R2_XRUN 1 // region 2: x by a running sum (see the row walk): 5.38 vs 5.42 ms per headline step
-#endif
-#if SR_RMAX
-#define SR_RMAX_OR(lds_value, row_value) __builtin_amdgcn_readfirstlane(lds_value)
-#else
-#define SR_RMAX_OR(lds_value, row_value) rows_max(row_value)
-#endif
 // At least four waves per SIMD (<= 128 VGPRs): the kernel sits at 118-127; with 129 (one more feature in the rows)
 // the 8-wave blocks of a small shard went from two per CU to one and the shard's kernel from 0.50 to 0.63 ms.
-#ifndef SR_ZONES_WAVES_PER_EU
-#define SR_ZONES_WAVES_PER_EU 4
-#endif
-#define SR_ZONES_ATTR __attribute__((amdgpu_waves_per_eu(SR_ZONES_WAVES_PER_EU)))
 template <int WT, int NW, bool COUNT>
-__global__ __launch_bounds__(64 * NW) SR_ZONES_ATTR void sr_abscoeff_near_zones_kernel(
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) void sr_abscoeff_near_zones_kernel(
     const FastRec *__restrict__ fast, const ColdRec *__restrict__ cold, IcIndex ix,
     const int *__restrict__ zmax, int n_sub, int n_groups, int g_lo, int g_hi, GridParams gp, int add,
     double *__restrict__ abs_out, double *__restrict__ emi_out, unsigned long long *__restrict__ cnt, int layer0) {
@@ -1843,20 +1796,10 @@ __global__ __launch_bounds__(64 * NW) SR_ZONES_ATTR void sr_abscoeff_near_zones_
   // element p + 1, i.e. element k + (j1 - wlo): the hot loops' address arithmetic carries no "- 1" (it cost a v_add per
   // region-2 point: the offset field of ds_add cannot be negative)
   __shared__ double s_img[NW][2][WT + 2];
-#ifdef SR_ZONES_PAD
-  // Tuning knob (see SR_FAR_WAVES_PER_EU): the wave's register footprint rounded up to a whole quarter of the SIMD's
-  // file (118 -> 128 VGPRs; four waves per SIMD either way, LDS allows no fifth).
-  asm volatile("" ::: "v127");
-#endif
   // per wave and region (2, 4): the chunk's lines with work there, compacted in lane order -- lane id and the two run
   // words -- written by the lanes = lines phase, read by the rows (dealing the lines to the rows with ballots and
   // selects cost 27 VALU instructions per round of eight lines, two bpermutes fetched the run words)
   __shared__ int s_item[NW][2][3][64];
-  // longest run of each round of eight list entries: region-2 left, region-2 right, region 4 (both sides) -- the rows'
-  // step counts, wave-uniform (eight v_readlane + maxima per round when the rows worked them out themselves)
-#if SR_RMAX
-  __shared__ int s_rmax[NW][3][8];
-#endif
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int layer = layer0 + wg / n_groups, grp = wg - (layer - layer0) * n_groups; // layer0: the launch's first layer (layer chunks)
   const int wlo = g_lo + grp * WT;
@@ -1952,29 +1895,17 @@ __global__ __launch_bounds__(64 * NW) SR_ZONES_ATTR void sr_abscoeff_near_zones_
       const unsigned long long m2 = __ballot(w2), m4 = __ballot(w4);
       n_items2 = __builtin_popcountll(m2);
       n_items4 = __builtin_popcountll(m4);
-#if SR_RMAX
-      if (lane < 24) (&s_rmax[wave][0][0])[lane] = 0;
-#endif
       if (w2) {
         const int at = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m2 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m2, 0u));
         s_item[wave][0][0][at] = lane;
         s_item[wave][0][1][at] = (int)run2l;
         s_item[wave][0][2][at] = (int)run2r;
-#if SR_RMAX && SR_R2_SPLIT
-        atomicMax(&s_rmax[wave][0][at >> 3], (int)(run2l >> 16));
-        atomicMax(&s_rmax[wave][1][at >> 3], (int)(run2r >> 16));
-#elif SR_RMAX
-        atomicMax(&s_rmax[wave][0][at >> 3], (int)(run2l >> 16) + (int)(run2r >> 16));
-#endif
       }
       if (w4) {
         const int at = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m4 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m4, 0u));
         s_item[wave][1][0][at] = lane;
         s_item[wave][1][1][at] = (int)run4l;
         s_item[wave][1][2][at] = (int)run4r;
-#if SR_RMAX
-        atomicMax(&s_rmax[wave][2][at >> 3], (int)((run4l >> 16) & 0x3fffu) + (int)(run4r >> 16));
-#endif
       }
     }
     // ---- regions 2 and 4, kRows lines at a time: each row of kRowLanes lanes walks the points of ONE line,
@@ -2006,13 +1937,11 @@ __global__ __launch_bounds__(64 * NW) SR_ZONES_ATTR void sr_abscoeff_near_zones_
         // for ~5 % more steps)
         auto run = [&](const int n, const int n_max, const double c, const int i0) {
           const int n_steps = (n_max + kRowLanes - 1) / kRowLanes; // wave-uniform: a scalar loop counter
-#if SR_R2_XRUN
           // x of the lane's point by a running sum, eight steps of xstep at a time (one add instead of a conversion
-          // and an fma per point; <= 20 steps of a run: <= 20 ulp of x, 1e-14 of the value at most)
+          // and an fma per point; <= 20 steps of a run: <= 20 ulp of x, 1e-14 of the value at most): 5.38 vs 5.42 ms
+          // per headline step
           double xt = fma((double)col, xstep, c);
           const double xs8 = (double)kRowLanes * xstep;
-#endif
-#if SR_R2_XRUN
           // ... and ONE counter per lane: the byte offset of its point in the image, which is the loop's predicate too
           int ab = (col + i0) * 8;
           const int ab_end = (n + i0) * 8;
@@ -2025,44 +1954,10 @@ __global__ __launch_bounds__(64 * NW) SR_ZONES_ATTR void sr_abscoeff_near_zones_
               atomicAdd(reinterpret_cast<double *>(reinterpret_cast<char *>(s_e) + ab), we * y);
             }
           }
-#else
-          for (int st = 0; st < n_steps; ++st) {
-            const int t = col + kRowLanes * st;
-            if (t < n) {
-              const double y = region2_val(q2, fma((double)t, xstep, c));
-              if (COUNT) ++n_r2;
-              atomicAdd(&s_a[t + i0], wa * y); // return-less LDS adds: no wait for a read, runs of different lines overlap
-              atomicAdd(&s_e[t + i0], we * y);
-            }
-          }
-#endif
         };
-#if SR_R2_SPLIT
-        run(live ? na : 0, SR_RMAX_OR(s_rmax[wave][0][g >> 3], live ? na : 0),
-            fma((double)(a0 - r.il()), xstep, -z.xs2l), a0 + base_idx);
-        run(live ? nb : 0, SR_RMAX_OR(s_rmax[wave][1][g >> 3], live ? nb : 0),
-            fma((double)(b0 - z.ir2()), xstep, z.xs2r), b0 + base_idx);
-#else
-        {
-          const int n = live ? na + nb : 0;
-          const double c_left = fma((double)(a0 - r.il()), xstep, -z.xs2l);
-          const double c_right = fma((double)(b0 - na - z.ir2()), xstep, z.xs2r);
-          int i_left = a0 + base_idx, i_right = b0 - na + base_idx;
-          asm volatile("" : "+v"(i_left), "+v"(i_right)); // keep the two sums: re-associated, they cost a v_add per point
-          const int n_steps = (SR_RMAX_OR(s_rmax[wave][0][g >> 3], n) + kRowLanes - 1) / kRowLanes;
-          for (int st = 0; st < n_steps; ++st) {
-            const int t = col + kRowLanes * st;
-            if (t < n) {
-              const bool lf = t < na;
-              const double y = region2_val(q2, fma((double)t, xstep, lf ? c_left : c_right));
-              if (COUNT) ++n_r2;
-              const int idx = t + (lf ? i_left : i_right);
-              atomicAdd(&s_a[idx], wa * y);
-              atomicAdd(&s_e[idx], we * y);
-            }
-          }
-        }
-#endif
+        // (step counts by rows_max() per round; from per-round maxima that the lanes = lines phase wrote to LDS: 3.51 vs 3.50 ms, 128-129 VGPRs)
+        run(live ? na : 0, rows_max(live ? na : 0), fma((double)(a0 - r.il()), xstep, -z.xs2l), a0 + base_idx);
+        run(live ? nb : 0, rows_max(live ? nb : 0), fma((double)(b0 - z.ir2()), xstep, z.xs2r), b0 + base_idx);
       }
       // region 4 (lineshape.f:530-546), on both sides of the region-3 interval
       for (int g = 0; g < n_items4; g += kRows) {
@@ -2089,7 +1984,7 @@ __global__ __launch_bounds__(64 * NW) SR_ZONES_ATTR void sr_abscoeff_near_zones_
         // the cosine's tier of this round: the smallest of its lines' (from the lanes = lines phase)
         const int tier_ = live ? (int)(ul >> 30) : 2;
         const int cos_tier = __all(tier_ == 2) ? 2 : (__all(tier_ >= 1) ? 1 : 0);
-        const int n_steps = (SR_RMAX_OR(s_rmax[wave][2][g >> 3], n) + kRowLanes - 1) / kRowLanes;
+        const int n_steps = (rows_max(n) + kRowLanes - 1) / kRowLanes;
         for (int st = 0; st < n_steps; ++st) {
           const int t = col + kRowLanes * st;
           P.k = t < na ? a0 + t : b0 + (t - na);
@@ -2241,7 +2136,6 @@ int launch_far_batch(const FarBatchItem *items, int n_items, int max_n_sub, cons
   return (int)hipGetLastError();
 }
 
-#if SR_FASTREC64
 __device__ inline int mc_base(const McChannels &mc, int level, int off, int plane) { return (mc.stride * level + off) * plane; }
 
 // The two stages of a 64-point slot's near wings (sr_wings_mc_kernel):
@@ -2400,7 +2294,7 @@ __device__ __forceinline__ void wings_mc_polys(const McFarPass *__restrict__ far
 // ms per build of the pair tables, 24.0 vs 21.5 for the three ctypes.  The wings stages ran at this kernel's 16 waves per
 // CU instead of their own 24, behind barriers, and the zones part no longer ran beside the far passes.  Removed.)
 template <int WT, int NW>
-__global__ __launch_bounds__(64 * NW) SR_ZONES_ATTR void sr_zones_mc_kernel(
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) void sr_zones_mc_kernel(
     const FastRec *__restrict__ fast, const ColdRec *__restrict__ cold, const int *__restrict__ lev_up,
     const int *__restrict__ lev_lo, IcIndex ix, const int *__restrict__ zmax, int n_sub, int n_groups, int g_lo, int g_hi,
     GridParams gp, McChannels mc, double *__restrict__ out, int n_rows_total, int row0) {
@@ -2691,15 +2585,6 @@ int launch_wings_mc(const FastRec *fast, const int *lev_up, const int *lev_lo, c
                      n_g1, g_lo, g_hi, fp, mc, far, n_far, out, n_rows_total, row0);
   return (int)hipGetLastError();
 }
-
-#else // 80-byte records carry no third weight: mc_pass never takes this route then (SR_ERR_UNSUPPORTED)
-int zones_mc_image(int) { return 0; }
-size_t wings_mc_lds(int) { return 0; }
-int launch_zones_mc(const FastRec *, const ColdRec *, const int *, const int *, const IcIndex &, const int *, int, int, int, int,
-                    const GridParams &, const McChannels &, double *, int, int, hipStream_t) { return (int)hipErrorNotSupported; }
-int launch_wings_mc(const FastRec *, const int *, const int *, const IcIndex &, const int *, int, int, int, int, const FarParams &,
-                    const McChannels &, const McFarPass *, int, double *, int, int, hipStream_t) { return (int)hipErrorNotSupported; }
-#endif
 
 // a += za, e += ze (small shards: the zones kernel's private result joins the wings kernel's)
 __global__ __launch_bounds__(256) void sr_add2_kernel(double *__restrict__ a, const double *__restrict__ za,
@@ -3973,9 +3858,6 @@ int launch_limb_adjoint_sync(const double *abs_c, const double *emi_c, const dou
 // of two doubles, so that the difference keeps the relative accuracy of what is still to come (see sweep 2).
 // Segments of one shell with the same columns (a 1-D limb path is symmetric) share one attenuation().
 // ------------------------------------------------------------------------
-#ifndef SR_FOLD_XCD
-#define SR_FOLD_XCD 1 // all rays of a point block on one XCD, one after the other (limb_block): 1.22 vs 1.28 ms per configs[3] set
-#endif
 #ifndef SR_FOLD_WAVES
 #define SR_FOLD_WAVES 4 // waves per SIMD the register allocation of the folded kernel aims at
 #endif
@@ -4024,6 +3906,7 @@ __global__ void sr_fold_pack_kernel(const int *__restrict__ plan, const double *
   out[i] = r;
 }
 
+// Rays per thread, NR: 1 as built (1.28-1.39 ms per configs[3] set; 2: 1.45-1.53, 4: 2.3 (spills); path order: 2.1, tools/adjoint_probe.py).
 // TWO: the two segments of a shell read different coefficient rows (3-D paths: a row per LOS step; one ray per thread)
 template <int NG, bool LAYER, bool PAR, int NR, bool TWO>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SR_FOLD_WAVES, SR_FOLD_WAVES))) void sr_limb_adjoint_fold_kernel(
@@ -4032,13 +3915,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SR_FOLD_WAV
     const int *__restrict__ zero_off, const int *__restrict__ zero_row, int n_par, LimbOpts o, int n_visits, int n_rays,
     double *__restrict__ rad, double *__restrict__ jac_layer, double *__restrict__ jac_par) {
   static_assert(!TWO || NR == 1, "rows per ray: one ray per thread");
-#if SR_FOLD_XCD
-  int pb, batch; // all batches of a point block on one XCD, one after the other (limb_block)
+  int pb, batch; // all batches of a point block on one XCD, one after the other (limb_block): 1.22 vs 1.28 ms per configs[3] set
   if (!limb_block((n_pts + 255) / 256, (n_rays + NR - 1) / NR, pb, batch)) return;
   const int j = pb * 256 + threadIdx.x;
-#else
-  const int j = blockIdx.x * blockDim.x + threadIdx.x, batch = blockIdx.y;
-#endif
   if (j >= n_pts) return;
   const int ray0 = batch * NR;
   const FoldRec *rc = rec + (size_t)batch * n_visits * NR;
@@ -4677,31 +4556,16 @@ int launch_limb_adjoint_fold(const double *abs_c, const double *emi_c, const dou
                              const int *zero_row, int n_par, const LimbOpts &o, int n_visits, double *rad, double *jac_layer,
                              double *jac_par, hipStream_t st) {
   if (n_pts <= 0 || n_rays <= 0 || n_visits <= 0) return 0;
-  if (two_rows) { // one ray per thread, a coefficient row per segment
-#if SR_FOLD_XCD
-    const dim3 grid2(limb_grid((n_pts + 255) / 256, n_rays));
-#else
-    const dim3 grid2((n_pts + 255) / 256, n_rays);
-#endif
-    by_ngas(o.n_gas, [&](auto ng) {
-      by_jac_kinds(jac_layer, jac_par, [&](auto lay, auto par) {
-        hipLaunchKernelGGL((sr_limb_adjoint_fold_kernel<decltype(ng)::value, decltype(lay)::value, decltype(par)::value, 1, true>),
-                           grid2, dim3(256), 0, st, abs_c, emi_c, dabs, demi, n_pts, n_layers, n_jrows, rec, zero_off, zero_row,
-                           n_par, o, n_visits, n_rays, rad, jac_layer, jac_par);
-      });
-    });
-    return (int)hipGetLastError();
-  }
-#if SR_FOLD_XCD
-  const dim3 grid(limb_grid((n_pts + 255) / 256, (n_rays + kAdjFoldRays - 1) / kAdjFoldRays));
-#else
-  const dim3 grid((n_pts + 255) / 256, (n_rays + kAdjFoldRays - 1) / kAdjFoldRays);
-#endif
+  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays));
   by_ngas(o.n_gas, [&](auto ng) {
     by_jac_kinds(jac_layer, jac_par, [&](auto lay, auto par) {
-      hipLaunchKernelGGL((sr_limb_adjoint_fold_kernel<decltype(ng)::value, decltype(lay)::value, decltype(par)::value, kAdjFoldRays, false>),
-                         grid, dim3(256), 0, st, abs_c, emi_c, dabs, demi, n_pts, n_layers, n_jrows, rec, zero_off, zero_row, n_par,
-                         o, n_visits, n_rays, rad, jac_layer, jac_par);
+      auto launch = [&](auto two) { // two_rows: a coefficient row per segment
+        hipLaunchKernelGGL((sr_limb_adjoint_fold_kernel<decltype(ng)::value, decltype(lay)::value, decltype(par)::value, 1, decltype(two)::value>),
+                           grid, dim3(256), 0, st, abs_c, emi_c, dabs, demi, n_pts, n_layers, n_jrows, rec, zero_off, zero_row, n_par,
+                           o, n_visits, n_rays, rad, jac_layer, jac_par);
+      };
+      if (two_rows) launch(std::true_type{});
+      else launch(std::false_type{});
     });
   });
   return (int)hipGetLastError();
