@@ -469,7 +469,10 @@ int sr_limb_step_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, in
 /* + Jacobian w.r.t. n_par VMR-profile parameters: the VMR of gas par_gas[p] at LOS sample point i is
  * sum_p par_w[p][i] x_p (mask values of RetParam / LinearProfile at the point, spect_main_module.py:319-375), so
  * d col_g[s] / d x_p = col_scale[g] curgod_fort_2(nd, par_w[p], x).  par_gas: HOST [n_par]; par_w: HOST
- * [n_par][n_pt]; jac: DEVICE [n_rays][n_par][n_pts].  Checked against finite differences (unpinned). */
+ * [n_par][n_pt]; jac: DEVICE [n_rays][n_par][n_pts].  The build's definition (unpinned): every route of this call and of
+ * the Jacobian calls below is held to an extended-precision CPU reference of the recursion on a panel of regimes
+ * (thin switch, range-reduction boundaries, saturated, zero and negative optical depths) in
+ * tests/test_gpu_limb_reference.py, and checked against finite differences in tests/test_gpu_limb.py. */
 int sr_limb_rays_jac_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
                          const sr_los_desc *los, int n_par, const int32_t *par_gas, const double *par_w, double *rad,
                          double *jac, void *stream);
@@ -579,7 +582,8 @@ int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layer
  * columns depend linearly, col_s = sum_p dcol_dpar[s][p] * x_p (VMR profile parameters of the
  * reference's RetParam / LinearProfile classes, spect_main_module.py:319-375; the reference's own
  * derivative code lives in the absent spect_base_module, call site spect_main_module.py:2874, so this
- * is the build's definition, parity unpinned, checked against finite differences).  Same recursion
+ * is the build's definition, parity unpinned, checked against the extended-precision reference of
+ * tests/test_gpu_limb_reference.py (test_host_column_jacobian) and against finite differences).  Same recursion
  * and layouts as sr_radiance_rays_dev; dcol_dpar: HOST [n_seg][n_par]; rad: DEVICE [n_rays][n_pts];
  * jac: DEVICE [n_rays][n_par][n_pts] = d rad / d x_p. */
 int sr_radiance_jac_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, int n_rays,
@@ -589,7 +593,8 @@ int sr_radiance_jac_dev(const double *abs_c, const double *emi_c, int n_layers, 
 /* Radiance Jacobian with respect to one scalar per layer that acts through the layer's own
  * coefficients -- its temperature (BASELINE configs[3]: "Jacobians w.r.t. T ... per layer"; the
  * reference has no temperature Jacobian, spect_main_module.py:300-306 is commented out: build's
- * definition, parity unpinned, checked against finite differences of the whole chain).
+ * definition, parity unpinned, checked against the extended-precision reference of
+ * tests/test_gpu_limb_reference.py (test_host_layer_jacobian) and against finite differences of the whole chain).
  * dabs / demi: DEVICE [n_layers][n_pts] = d(abs, emi of layer k)/d(parameter of layer k), e.g. central
  * differences of two sr_abscoeff_layers_dev calls at T +- dT; jac: DEVICE [n_rays][n_layers][n_pts]. */
 int sr_radiance_jac_layer_dev(const double *abs_c, const double *emi_c, const double *dabs, const double *demi,
@@ -652,8 +657,8 @@ int sr_set_table_budget(int64_t bytes);
 /* Radiance Jacobians of the device LOS pipeline (sr_limb_rays_jac_dev with more than 8 parameters,
  * sr_limb_rays_jac_layer_dev with more than 8 layers, sr_limb_rays_jacobians_dev).  0 (default): one pass over each
  * ray, every segment's sensitivity times the transmission behind it added to the rows it acts on
- * (sr_limb_adjoint_kernel); where the rays share their coefficient rows (no seg_jac_row) and walk them monotonically
- * inwards and outwards again (limb, slant and nadir paths of a 1-D atmosphere), the FOLDED kernel: the shells are
+ * (sr_limb_adjoint_kernel); where the rays walk their shells -- the coefficient rows, or with seg_jac_row the Jacobian
+ * rows -- monotonically inwards and outwards again (limb, slant and nadir paths), the FOLDED kernel: the shells are
  * walked once per sweep, a ray's far-side and near-side segment of a shell together, two rays per thread, every
  * Jacobian value stored once (sr_limb_adjoint_fold_kernel; what enters a near-side segment is taken as the observed
  * radiance minus what the segments in front of it emit: values agree with mode 2 to ~1e-15 of the radiance x d tau).

@@ -319,7 +319,8 @@ __device__ inline double exp_bounded(double u) {
 // x 1e5 points), sr_limb_kernel 1.5 -> see DESIGN.md.  tau may be negative (stimulated emission).
 struct Atten {
   double t, em1, f, rtau; // rtau = 1 / tau (unspecified where |tau| <= 1e-12)
-  bool thin;
+  double fp0;             // f'(tau) from the polynomial, valid where the reduction left n = 0 (atten_fprime)
+  bool thin, n0;
 };
 __device__ inline Atten attenuation(double tau) {
   const double x = -tau;
@@ -343,11 +344,19 @@ __device__ inline Atten attenuation(double tau) {
   A.thin = !(fabs(tau) > 1e-12);
   A.rtau = fast_rcp<2>(tau);
   A.f = A.thin ? 1.0 : A.em1 * A.rtau;
+  A.n0 = n == 0.0;
+  A.fp0 = fma(fabs(r) < 0x1p-4 ? p - 0x1.6p-50 : p, 1.0 - r, -1.0);
   return A;
 }
-// f'(tau) = (tau e^-tau - (1 - e^-tau)) / tau^2 of the same segment (-1/2 where |tau| <= 1e-12)
+// f'(tau) = (tau e^-tau - (1 - e^-tau)) / tau^2 of the same segment (-1/2 where |tau| <= 1e-12).  The closed form is a
+// difference of nearly equal numbers for small tau (good to ~2^-53 / tau of f').  Where the reduction left n = 0
+// (|tau| < ln2 / 2: r = -tau exactly, e^r = 1 + r + r^2 p) the same polynomial gives it without one:
+// tau t - em1 = r^2 (p - 1 - r p), so f' = p (1 - r) - 1, p ~ 1/2.  The minimax fit's constant term is 11 ulp above 1/2
+// (what the higher coefficients make up for towards |r| = 0.35): taken off below |r| = 1/16, where nothing makes up
+// for it.  <= 3 units of 2^-53 below 1/64, <= 18 anywhere (checked on the host against long double).  Beyond n = 0
+// the closed form loses under three bits.
 __device__ __forceinline__ double atten_fprime(const Atten &A, double tau) {
-  return A.thin ? -0.5 : (tau * A.t - A.em1) * (A.rtau * A.rtau);
+  return A.thin ? -0.5 : (A.n0 ? A.fp0 : (tau * A.t - A.em1) * (A.rtau * A.rtau));
 }
 
 // Regions 3 and 4 at c2 = (a, b) = ((double)(float)ry, (double)(float)(-rx)): cmplx() is

@@ -2807,6 +2807,7 @@ __global__ __launch_bounds__(256) void sr_radiance_kernel(const double *__restri
 // dcol[s][p] * x_p).  Forward sensitivity of the same recursion:
 //   d/dcol [I e^-tau + emi col (1 - e^-tau)/tau] = e^-tau (emi - abs I)
 //   J_p <- J_p e^-tau + e^-tau (emi - abs I_prev) dcol[s][p];   I <- I e^-tau + src
+// (thin segments, |tau| <= 1e-12: the source term by the thin rule's f = 1, f' = -1/2, as everywhere else)
 // Thread = (point, ray, chunk of NP parameters).
 template <int NP>
 __global__ __launch_bounds__(256) void sr_radiance_jac_kernel(const double *__restrict__ abs_c,
@@ -2837,9 +2838,13 @@ __global__ __launch_bounds__(256) void sr_radiance_jac_kernel(const double *__re
       const int s = sb + k;
       if (s < s1) {
         const double u = seg_col[s], a = av[k], e = ev[k];
-        const Atten A = attenuation(a * u);
+        const double tau = a * u;
+        const Atten A = attenuation(tau);
         const double t = A.t, src = (e * u) * A.f;
-        const double g = t * (e - a * I);
+        // f + tau f' = t for the functions themselves; under the thin rule (f = 1, f' = -1/2) it is 1 - tau / 2, and
+        // the source term of every other Jacobian kernel (dE f + E f' dtau) carries that
+        double g = t * (e - a * I);
+        if (A.thin) g = fma(0.5 * tau, e, g);
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
           const double d = (p0 + q < n_par) ? dcol[(size_t)s * n_par + p0 + q] : 0.0;
@@ -3318,7 +3323,7 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     const double src = o.solo_absorption ? 0.0 : E * f;
     const int e0 = eo[r], e1 = eo[r + 1];
     double fp = 0.0, W[NG];
-    if (nc > 0 || e0 < e1) fp = thin ? -0.5 : (tau * t - em1) * (A.rtau * A.rtau);
+    if (nc > 0 || e0 < e1) fp = atten_fprime(A, tau);
     if (nc > 0) { // what a column slot of gas g adds per unit of its D: sr_limb_jac_kernel's (dsrc - I t a_g), once per gas
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
@@ -4059,7 +4064,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SR_FOLD_WAV
           }
         }
         A = attenuation(tau);
-        fp = A.thin ? -0.5 : (tau * A.t - A.em1) * (A.rtau * A.rtau);
+        fp = atten_fprime(A, tau);
         two_sum_add(rem[r], rem_lo[r], -tau);
         const double Ta = exp_bounded(fmin(fmax(-(rem[r] + rem_lo[r]), -700.0), 700.0)); // everything behind: the inner far side and the near side
         wt_f = (o.solo_absorption ? -If[r] * A.t : fma(E, fp, -If[r] * A.t)) * Ta;
@@ -4081,7 +4086,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SR_FOLD_WAV
         }
         if (!(R.has & 4)) {
           A = attenuation(tau);
-          fp = A.thin ? -0.5 : (tau * A.t - A.em1) * (A.rtau * A.rtau);
+          fp = atten_fprime(A, tau);
         }
         const double ETn = o.solo_absorption ? 0.0 : E * Tn[r];
         // I_in t Tn = I_obs - cs.  Both are carried as error-free sums (two doubles) of the SAME rounded terms -- the
@@ -4224,6 +4229,8 @@ __device__ inline Atten attenuation_sc(double tau) {
   A.thin = !(fabs(tau) > 1e-12);
   A.rtau = fast_rcp<2>(tau);
   A.f = A.thin ? 1.0 : A.em1 * A.rtau;
+  A.n0 = n == 0.0;
+  A.fp0 = fma(fabs(r) < 0x1p-4 ? p - 0x1.6p-50 : p, 1.0 - r, -1.0);
   return A;
 }
 
