@@ -552,6 +552,30 @@ int sr_limb_rays_jac_state_dev(const double *abs_c, const double *emi_c, int n_l
                                const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
                                const int32_t *par_level, const double *par_c, double *rad, double *jac, void *stream);
 
+/* sr_limb_rays_jac_state_dev with a third kind of parameter in the same pass: n_row ROW parameters, which act through the
+ * coefficients of every gas with a weight per coefficient row (a layer on a 1-D path, a LOS step on a 3-D path).  With
+ * derivative spectra dabs_c / demi_c of the coefficients' shape, a segment s on row r gives row parameter p
+ *   dtau = par_t[p][r] sum_g u_g[s] dabs_g[r],   dE = par_t[p][r] sum_g u_g[s] demi_g[r]      (u_g the gas columns)
+ * in the recursion above: the per-row Jacobian of sr_limb_rays_jac_layer_dev contracted with the weights inside the
+ * recursion, so [n_rays][n_layers][n_pts] is never written.  Kinetic-temperature nodes: dabs_c / demi_c = d abs / dT,
+ * d emi / dT per row, par_t = the nodes' masks on the rows.  The columns are held fixed (the definition of the
+ * temperature Jacobian here: pressure, columns and vibrational temperatures fixed); the density part of a temperature
+ * change is a set of ordinary column parameters, which a caller who wants it adds to par_gas / par_w.
+ * dabs_c / demi_c: DEVICE [n_gas][n_layers][n_pts]; par_t: HOST [n_row][n_layers]; every other argument as in
+ * sr_limb_rays_jac_state_dev.  jac: DEVICE [n_rays][n_col + n_lev + n_row][n_pts]: the column parameters, then the level
+ * parameters, then the row parameters, each kind in the caller's order; every element is written (exact zeros for a
+ * parameter a ray never touches or whose weights are all zero).  Any kind may be empty, not all; n_row == 0 is
+ * sr_limb_rays_jac_state_dev itself (dabs_c, demi_c and par_t may then be NULL).  init_mode 1 is refused (SR_ERR_ARG),
+ * n_pts above the limit SR_ERR_LIMIT.  All arguments are checked before the first copy or launch: a refused call leaves
+ * rad and jac untouched.
+ * The reference has no counterpart: the build's definition, checked against an extended-precision recursion, against
+ * sr_limb_rays_jac_layer_dev contracted on the host and against central differences (tests/test_gpu_state_rows.py). */
+int sr_limb_rays_jac_state_rows_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                    const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
+                                    const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
+                                    const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c,
+                                    int n_row, const double *par_t, double *rad, double *jac, void *stream);
+
 /* The radiance budget of the ray batch: which gas, and which level of the level-factored gas `gas`, emits the radiance
  * that arrives.  The recursion is linear in the emission: with tau = sum_g abs_g[r] u_g, t = exp(-tau), f = (1 - t) / tau
  * of a segment on coefficient row r,

@@ -3341,16 +3341,17 @@ int sr_limb_rays_jac_layer_dev(const double *abs_c, const double *emi_c, const d
 }
 
 // The host plan of sr_limb_jac_state_kernel: the column parameters in the caller's order, then the level parameters in
-// level order, NP per block: a block's column slots come first and stand for consecutive rows of dcol (blk: their number
-// and gases), a row's level entries come in level order without a sort of their own.
+// level order, then the row parameters in the caller's order, NP per block: a block's column slots come first and stand
+// for consecutive rows of dcol (blk: their number and gases), a row's level entries come in level order without a sort
+// of their own, the entries of its row slots (level kLevelEntRows, c = par_t[p][r]) behind them.
 struct LevelJacPlan {
   int n_blocks;
   std::vector<int> blk, ent_off, slot_par;
   std::vector<LevelEnt> ent;
 };
 static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev, const int32_t *par_level, const double *par_c,
-                                   int n_layers) {
-  const int n_par = n_col + n_lev, np = level_jac_np(n_par), n_blocks = (n_par + np - 1) / np;
+                                   int n_layers, int n_row = 0, const double *par_t = nullptr) {
+  const int n_cl = n_col + n_lev, n_par = n_cl + n_row, np = level_jac_np(n_par), n_blocks = (n_par + np - 1) / np;
   const std::vector<int> order = order_by_level(n_lev, par_level);
   LevelJacPlan P{n_blocks, std::vector<int>((size_t)n_blocks * 2, 0), std::vector<int>((size_t)n_blocks * (n_layers + 1)),
                  std::vector<int>((size_t)n_blocks * np, -1), {}};
@@ -3360,13 +3361,17 @@ static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev,
     for (int i = i0; i < i0 + nc; ++i) gases |= (unsigned)par_gas[i] << (2 * (i - i0));
     P.blk[2 * b] = nc;
     P.blk[2 * b + 1] = (int)gases;
-    for (int i = i0; i < i1; ++i) P.slot_par[i] = i < n_col ? i : n_col + order[i - n_col];
+    for (int i = i0; i < i1; ++i) P.slot_par[i] = i < n_col || i >= n_cl ? i : n_col + order[i - n_col];
     for (int r = 0; r < n_layers; ++r) {
       P.ent_off[(size_t)b * (n_layers + 1) + r] = (int)P.ent.size();
-      for (int i = std::max(i0, n_col); i < i1; ++i) {
+      for (int i = std::max(i0, n_col); i < std::min(i1, n_cl); ++i) {
         const int p = order[i - n_col];
         const double c = par_c[(size_t)p * n_layers + r];
         if (c != 0.0) P.ent.push_back(LevelEnt{i - i0, par_level[p], c});
+      }
+      for (int i = std::max(i0, n_cl); i < i1; ++i) {
+        const double c = par_t[(size_t)(i - n_cl) * n_layers + r];
+        if (c != 0.0) P.ent.push_back(LevelEnt{i - i0, kLevelEntRows, c});
       }
     }
     P.ent_off[(size_t)b * (n_layers + 1) + n_layers] = (int)P.ent.size();
@@ -3374,13 +3379,15 @@ static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev,
   return P;
 }
 
-// What both entries below do once their arguments are checked: plan, stage, launch, mark.  cols: the kernel instance
+// What the entries below do once their arguments are checked: plan, stage, launch, mark.  cols: the kernel instance
 // with column slots (the state call, with n_col == 0 too); without it n_col is 0 and neither blk nor dcol exists.
+// n_row > 0 (sr_limb_rays_jac_state_rows_dev): the instances with row slots, which read dabs / demi.
 static int limb_jac_state(bool cols, const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
                           const LosShape &shape, int n_col, const int32_t *par_gas, const double *par_w, int gas,
                           const double *tab, int n_tab_rows, const int32_t *coef_row, int n_lev, const int32_t *par_level,
-                          const double *par_c, double *rad, double *jac, hipStream_t st) {
-  const LevelJacPlan P = level_jac_plan(n_col, par_gas, n_lev, par_level, par_c, n_layers);
+                          const double *par_c, double *rad, double *jac, hipStream_t st, const double *dabs = nullptr,
+                          const double *demi = nullptr, int n_row = 0, const double *par_t = nullptr) {
+  const LevelJacPlan P = level_jac_plan(n_col, par_gas, n_lev, par_level, par_c, n_layers, n_row, par_t);
   static thread_local StagerRing ring;
   StagePack pk(ring.take());
   const auto p_ent = pk.copy(P.ent.data(), P.ent.size(), 1); // (no entries: a valid pointer all the same)
@@ -3392,10 +3399,16 @@ static int limb_jac_state(bool cols, const double *abs_c, const double *emi_c, i
   LosDev D;
   rc = stage_los(los, shape, n_col, par_gas, par_w, st, &D);
   if (rc) return rc;
-  LAUNCHCHK(launch_limb_jac_state(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col,
-                                  cols ? D.col + (size_t)los->n_gas * D.n_seg : nullptr, limb_opts(los, D.n_seg), gas, tab,
-                                  n_tab_rows, pk.dev(p_row), P.n_blocks, cols ? pk.dev(p_blk) : nullptr, pk.dev(p_off),
-                                  pk.dev(p_ent), pk.dev(p_slot), n_col + n_lev, rad, jac, st));
+  const double *dcol = cols ? D.col + (size_t)los->n_gas * D.n_seg : nullptr;
+  const int *blk = cols ? pk.dev(p_blk) : nullptr;
+  if (n_row > 0)
+    LAUNCHCHK(launch_limb_jac_state_rows(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer,
+                                         D.col, dcol, limb_opts(los, D.n_seg), gas, tab, n_tab_rows, pk.dev(p_row), P.n_blocks,
+                                         blk, pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot), n_col + n_lev + n_row, rad, jac, st));
+  else
+    LAUNCHCHK(launch_limb_jac_state(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col, dcol,
+                                    limb_opts(los, D.n_seg), gas, tab, n_tab_rows, pk.dev(p_row), P.n_blocks, blk,
+                                    pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot), n_col + n_lev, rad, jac, st));
   return mark_both(pk.slot(), *D.slot, st);
 }
 
@@ -3437,6 +3450,33 @@ int sr_limb_rays_jac_state_dev(const double *abs_c, const double *emi_c, int n_l
   if ((int64_t)n_col + n_lev > INT_MAX) return SR_ERR_LIMIT;
   return limb_jac_state(true, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, gas, tab, n_tab_rows, coef_row,
                         n_lev, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream));
+}
+
+int sr_limb_rays_jac_state_rows_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                    const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
+                                    const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
+                                    const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c,
+                                    int n_row, const double *par_t, double *rad, double *jac, void *stream) {
+  if (n_row == 0) // nothing of the third kind: the state call, checks and all
+    return sr_limb_rays_jac_state_dev(abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, gas, tab, n_levels, n_tab_rows,
+                                      coef_row, n_lev, par_level, par_c, rad, jac, stream);
+  // everything is checked here, before the first copy or launch (as sr_limb_rays_jac_state_dev does)
+  LosShape shape;
+  const bool lev_ok = n_lev == 0 || (tab && coef_row && par_level && par_c && n_levels > 0 && n_tab_rows > 0);
+  const bool row_ok = n_row > 0 && dabs_c && demi_c && par_t;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, jac && n_col >= 0 && n_lev >= 0 && lev_ok && row_ok);
+  if (!rc) rc = check_los_par(los, n_layers, n_col, par_gas, par_w, &shape);
+  if (rc) return rc;
+  if (gas < 0 || gas >= los->n_gas) return SR_ERR_ARG;
+  if ((rc = refuse_init_mode_1(los, "sr_limb_rays_jac_state_rows_dev", SR_ERR_ARG))) return rc;
+  if (n_lev > 0 && !coef_rows_in_range(coef_row, n_layers, n_tab_rows)) return SR_ERR_ARG;
+  for (int p = 0; p < n_lev; ++p)
+    if (par_level[p] < 0 || par_level[p] >= n_levels) return SR_ERR_ARG;
+  if ((int64_t)n_col + n_lev + n_row > INT_MAX) return SR_ERR_LIMIT;
+  // (without column parameters the instances without column code: fewer registers, the same arithmetic)
+  return limb_jac_state(n_col > 0, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, gas, tab, n_tab_rows,
+                        coef_row, n_lev, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream), dabs_c, demi_c, n_row,
+                        par_t);
 }
 
 int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,

@@ -3275,15 +3275,27 @@ __global__ __launch_bounds__(256) void sr_limb_jac_layer_kernel(
 // Coefficients of segment s + 1 are loaded while s is worked on (a ray's segments are a dependent chain); rays and
 // point blocks by limb_block(): all rays of a point block on one XCD, so that the table rows they share are read from
 // HBM once.
-template <int NG, int NP, bool COLS>
+// ROWS = true adds a third kind (sr_limb_rays_jac_state_rows_dev): a ROW parameter p acts through the coefficients of
+// every gas, with a weight w[p][r] per coefficient row (kinetic-temperature nodes: dabs / demi = d abs / dT, d emi / dT,
+// [NG][n_layers][n_pts], the columns held fixed),
+//   row parameter:  dtau = w sum_g u_g dabs_g[r],  dE = w sum_g u_g demi_g[r]
+// sr_limb_jac_layer_kernel's expression contracted with the weights inside the recursion.  The row slots ride on the entry
+// lists: behind a row's level entries the host appends one entry per row slot with w != 0, its level kLevelEntRows and
+// c = w, so the sums are formed once per segment (2 NG loads at (g, r, j); the columns u_g are read again there, scalar
+// loads that hit the scalar cache, rather than kept in scalar registers over the exponential) and every row slot costs
+// its one multiply-add; a row no row slot weights costs nothing.  dabs and demi are the kernel's last two arguments and
+// exist with ROWS = true only (row_spectra, empty otherwise): the ROWS = false instances keep their argument block and
+// with it their machine code, instruction for instruction.
+template <int NG, int NP, bool COLS, bool ROWS, class... RowSpectra>
 __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
     const int *__restrict__ seg_off, const int *__restrict__ seg_layer, const double *__restrict__ col,
     const double *__restrict__ dcol, LimbOpts o, int n_rays, int gas, const double *__restrict__ tab, int n_tab_rows,
     const int *__restrict__ coef_row, const int *__restrict__ blk, const int *__restrict__ ent_off,
     const LevelEnt *__restrict__ ent, const int *__restrict__ slot_par, int n_par, double *__restrict__ rad,
-    double *__restrict__ jac) {
+    double *__restrict__ jac, RowSpectra... row_spectra) {
   static_assert(NP <= 16 && NG <= 4, "blk packs the gases of 16 column slots, two bits each");
+  static_assert(sizeof...(RowSpectra) == (ROWS ? 2 : 0), "dabs and demi with ROWS, nothing without");
   int pb, ray;
   if (!limb_block((n_pts + 255) / 256, n_rays, pb, ray)) return;
   const int j = pb * 256 + threadIdx.x;
@@ -3361,9 +3373,26 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
         const int slot = ent[i].slot, lv = ent[i].level;
         if (lv != lev) { // (entries in level order: two loads and one d per distinct level)
           lev = lv;
-          const double *tl = tr + (size_t)lv * 2 * plane;
-          const double dtau = ug * tl[0], dE = ug * tl[plane];
-          d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
+          bool rows = false;
+          if constexpr (ROWS) rows = lv == kLevelEntRows;
+          if (rows) { // the row slots: one d for all of them (sr_limb_jac_layer_kernel's sums)
+            if constexpr (ROWS) {
+              const double *const rs[] = {row_spectra...};
+              const size_t ofs = (size_t)r * n_pts + j;
+              double dtau = 0.0, dE = 0.0;
+#pragma unroll
+              for (int g = 0; g < NG; ++g) {
+                const double u = col[(size_t)g * o.n_seg_total + s];
+                dtau = fma(rs[0][g * gstride + ofs], u, dtau);
+                dE = fma(rs[1][g * gstride + ofs], u, dE);
+              }
+              d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
+            }
+          } else {
+            const double *tl = tr + (size_t)lv * 2 * plane;
+            const double dtau = ug * tl[0], dE = ug * tl[plane];
+            d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
+          }
         }
         const double v = ent[i].c * d;
 #pragma unroll
@@ -4668,9 +4697,31 @@ int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, i
   auto launch = [&](auto cols) { // no blk: the instance without column slots
     by_level_np(level_jac_np(n_par), [&](auto np) {
       by_ngas(o.n_gas, [&](auto ng) {
-        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value>), grid,
+        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, false>), grid,
                            dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas, tab,
                            n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac);
+      });
+    });
+  };
+  if (blk) launch(std::true_type{});
+  else launch(std::false_type{});
+  return (int)hipGetLastError();
+}
+
+int launch_limb_jac_state_rows(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
+                               int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
+                               const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
+                               const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
+                               const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st) {
+  if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0) return 0;
+  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
+  auto launch = [&](auto cols) { // no blk: the instance without column slots
+    by_level_np(level_jac_np(n_par), [&](auto np) {
+      by_ngas(o.n_gas, [&](auto ng) {
+        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, true,
+                                                     const double *, const double *>),
+                           grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas,
+                           tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac, dabs, demi);
       });
     });
   };

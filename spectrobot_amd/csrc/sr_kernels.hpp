@@ -250,6 +250,8 @@ struct __attribute__((aligned(16))) LevelEnt {
   int slot, level; // accumulator of the block, level of the pair tables
   double c;        // d pop[row][level] / d x_p
 };
+// the `level` of an entry that belongs to a row slot (launch_limb_jac_state_rows): its c is the slot's weight on the row
+constexpr int kLevelEntRows = -2;
 constexpr int kLevelJacNPSmall = 8, kLevelJacNPLarge = 16;
 inline int level_jac_np(int n_par) { return n_par > kLevelJacNPSmall ? kLevelJacNPLarge : kLevelJacNPSmall; }
 int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
@@ -257,6 +259,15 @@ int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, i
                           const double *tab, int n_tab_rows, const int *coef_row, int n_blocks, const int *blk,
                           const int *ent_off, const LevelEnt *ent, const int *slot_par, int n_par, double *rad, double *jac,
                           hipStream_t st);
+// The same with ROW parameters as a third kind (the kernel's ROWS = true instances): n_par = n_col + n_lev + n_row, the
+// row parameters last, in the caller's order.  dabs / demi [n_gas][n_layers][n_pts]: the derivative spectra a row
+// parameter acts through.  A row slot has, on every coefficient row it weights, one entry behind that row's level entries:
+// level = kLevelEntRows, c = the weight.
+int launch_limb_jac_state_rows(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
+                               int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
+                               const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
+                               const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
+                               const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st);
 // Radiance budget (sr_limb_parts_kernel): the n_part parts and the background are n_part + 1 slots in blocks of
 // limb_parts_np(n_part); slot_level [n_blocks][NP]: >= 0 the first row of a level's E plane in the pair tables,
 // (2 L + 1) n_tab_rows, -1 - g the gas part of gas g,

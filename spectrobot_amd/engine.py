@@ -527,12 +527,15 @@ class LevelFactored(object):
                                         g_lo=int(self._shard[0]), want_rad=want_rad)
 
     def state_jacobian(self, coeffs, los, step_row, tvib, par_level, par_w_level, par_gas=None, par_w_col=None, gas=0,
-                       q_part=None, grid=None, want_rad=True):
-        """(rad | None, jac [n_rays, n_col + n_lev, n_pts]): d rad / d x for a mixed state vector in one pass
+                       q_part=None, grid=None, want_rad=True, dcoeffs=None, par_w_temp=None):
+        """(rad | None, jac [n_rays, n_col + n_lev (+ n_row), n_pts]): d rad / d x for a mixed state vector in one pass
         (limb_rays_state_jacobian): first the VMR-profile parameters par_gas / par_w_col of limb_rays_jacobian (any gas
         of the batch, this one included; None: no such parameter), then the vibrational-temperature parameters
         par_level / par_w_level of tvib_jacobian, par_c = par_w_level * d pop / d Tvib formed exactly as there (an empty
-        par_level: only column parameters).  Honours the object's spectral shard."""
+        par_level: only column parameters).  dcoeffs and par_w_temp [n_row, n_steps] (both or neither): then the
+        kinetic-temperature parameters, T[r] = T0[r] + sum_p par_w_temp[p, r] x_p, through the derivative spectra
+        dcoeffs of every gas of the batch on the coefficient rows (this gas's: steps(..., derivative=True); the columns
+        held fixed).  Honours the object's spectral shard."""
         step_row = np.ascontiguousarray(step_row, dtype=np.int32)
         par_level = np.ascontiguousarray(par_level, dtype=np.int32).reshape(-1)
         par_w = np.zeros((0, step_row.size)) if par_level.size == 0 else np.asarray(par_w_level, dtype=np.float64)
@@ -547,7 +550,7 @@ class LevelFactored(object):
             par_c = par_w * dpop.T[par_level]
         return limb_rays_state_jacobian(coeffs, los, par_gas=par_gas, par_w=par_w_col, tab=self.tab, coef_row=step_row,
                                         par_level=par_level, par_c=par_c, gas=gas, grid=grid, g_lo=int(self._shard[0]),
-                                        want_rad=want_rad)
+                                        want_rad=want_rad, dcoeffs=dcoeffs, par_t=par_w_temp)
 
     def level_radiances(self, coeffs, los, step_row, tvib, levels=None, weights=None, gas=0, q_part=None, grid=None,
                         gas_parts=True):
@@ -1118,13 +1121,22 @@ def limb_rays_level_jacobian(coeffs, los, tab, coef_row, par_level, par_c, gas=0
 
 
 def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, coef_row=None, par_level=None, par_c=None,
-                             gas=0, grid=None, g_lo=0, want_rad=True):
-    """(rad | None, jac [n_rays, n_col + n_lev, n_pts]): radiances and their derivatives with respect to a mixed state
-    vector in ONE pass over each ray (sr_limb_rays_jac_state_dev): the column parameters par_gas / par_w of
+                             gas=0, grid=None, g_lo=0, want_rad=True, dcoeffs=None, par_t=None):
+    """(rad | None, jac [n_rays, n_col + n_lev (+ n_row), n_pts]): radiances and their derivatives with respect to a
+    mixed state vector in ONE pass over each ray (sr_limb_rays_jac_state_dev): the column parameters par_gas / par_w of
     limb_rays_jacobian (VMR-profile parameters, par_w [n_col, n_pt] at the LOS sample points) first, then the level
     parameters tab / coef_row / par_level / par_c of limb_rays_level_jacobian for the level-factored gas `gas`
     (par_c [n_lev, n_layers] on the coefficient rows).  Either kind may be left out (None), not both.  Vibrational
-    temperatures: LevelFactored.state_jacobian."""
+    temperatures: LevelFactored.state_jacobian.
+    dcoeffs and par_t (both or neither) add ROW parameters as a third kind, behind the other two
+    (sr_limb_rays_jac_state_rows_dev): dcoeffs stacks like coeffs, the derivatives of every gas's (abs, emi) with respect
+    to one scalar per coefficient row (kinetic temperature: coefficients_dT, LevelFactored.steps(derivative=True)), and
+    row parameter p moves that scalar on row r by par_t[p, r] (par_t [n_row, n_layers], node masks).  It is
+    limb_rays_layer_jacobian contracted with par_t inside the recursion.  The columns are held fixed, as in
+    temperature_jacobian; the density part of a temperature change is a set of column parameters, which the caller adds
+    to par_gas / par_w if it is wanted.  With row parameters the other two kinds may both be left out."""
+    if (dcoeffs is None) != (par_t is None):
+        raise ValueError("row parameters need both dcoeffs and par_t")
     a, e = _gas_stack(coeffs)
     n_gas, n_layers, n_pts = a.shape
     if n_gas != los.n_gas:
@@ -1141,12 +1153,29 @@ def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, co
         if tab is None or coef_row is None or par_c is None:
             raise ValueError("level parameters need tab, coef_row and par_c")
         n_levels, n_tab_rows, cr, n_lev, pl, pc = _level_table_args(tab, coef_row, par_level, par_c, n_layers, n_pts, "n_lev")
+    d = los.desc(grid, g_lo)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    if par_t is not None:
+        da, de = _gas_stack(dcoeffs)
+        if da.shape != a.shape:
+            raise ValueError("dcoeffs must stack to the shape of coeffs, [%d, %d, %d]" % tuple(a.shape))
+        par_t, pt = _d(par_t)
+        if par_t.ndim != 2 or par_t.shape[1] != n_layers:
+            raise ValueError("par_t must be [n_row, n_layers]")
+        n_row = par_t.shape[0]
+        if n_col + n_lev + n_row == 0:
+            raise ValueError("no parameters: give column parameters, level parameters or row parameters")
+        rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
+        jac = torch.empty((los.n_rays, n_col + n_lev + n_row, n_pts), dtype=torch.float64, device="cuda")
+        check(lib.sr_limb_rays_jac_state_rows_dev(ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw, int(gas),
+                                                  ptr(tab) if n_lev else None, n_levels, n_tab_rows, cr, n_lev, pl, pc,
+                                                  ptr(da), ptr(de), n_row, pt, ptr(rad), ptr(jac), _stream_ptr()),
+              "sr_limb_rays_jac_state_rows_dev")
+        return rad, jac
     if n_col + n_lev == 0:
         raise ValueError("no parameters: give column parameters, level parameters or both")
     rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
     jac = torch.empty((los.n_rays, n_col + n_lev, n_pts), dtype=torch.float64, device="cuda")
-    d = los.desc(grid, g_lo)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     check(lib.sr_limb_rays_jac_state_dev(ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw, int(gas),
                                          ptr(tab) if n_lev else None, n_levels, n_tab_rows, cr, n_lev, pl, pc, ptr(rad),
                                          ptr(jac), _stream_ptr()), "sr_limb_rays_jac_state_dev")

@@ -64,13 +64,15 @@ class LevelGas(Gas):
     a reference tvib0 [n_levels, n_layers]; its coefficients are lf.steps(rows, tvib), recombined only when tvib was
     changed (set_tvib): a combine of the resident tables, never a walk of the lines."""
 
-    def __init__(self, name, lineset, vmr, tvib0, iso_ratio=1.0):
+    def __init__(self, name, lineset, vmr, tvib0, iso_ratio=1.0, dT=None):
+        """dT: handed to engine.LevelFactored -- the tables also at T + dT, for the temperature derivative of the
+        coefficients (layer_coefficients(derivative=True): a retrieval with a TempProfile needs it)."""
         tvib0 = np.array(tvib0, dtype=float)
         if tvib0.ndim != 2 or tvib0.shape[0] != max(int(np.size(lineset.level_energies)), 1):
             raise ValueError("tvib0 must be [n_levels, n_layers] for the line set's levels")
         Gas.__init__(self, name, lineset, vmr, iso_ratio=iso_ratio, tvib=tvib0.copy())
-        self.tvib0 = tvib0
-        self.lf, self._lf_key, self._combined = None, None, None
+        self.tvib0, self.dT = tvib0, dT
+        self.lf, self._lf_key, self._combined, self.dcoeffs = None, None, None, None
 
     @property
     def n_levels(self):
@@ -82,15 +84,25 @@ class LevelGas(Gas):
             raise ValueError("tvib must be [n_levels, n_layers] like tvib0")
         self.tvib = tvib
 
-    def layer_coefficients(self, temps, press, g_lo=0, g_hi=None):
-        """(abs, emi) on the layer stack from the pair tables (LimbScene.coefficients calls this)."""
+    def layer_coefficients(self, temps, press, g_lo=0, g_hi=None, derivative=False):
+        """(abs, emi) on the layer stack from the pair tables (LimbScene.coefficients calls this).  New temperatures or
+        pressures on the same number of rows and the same shard rebuild the tables in place (LevelFactored.rebuild).
+        derivative=True also leaves (d abs / dT, d emi / dT) in self.dcoeffs (LevelFactored.steps(derivative=True))."""
         key = (np.asarray(temps, float).tobytes(), np.asarray(press, float).tobytes(), int(g_lo), g_hi)
-        if self.lf is None or self._lf_key != key:
-            self.lf, self._lf_key, self._combined = engine.LevelFactored(self.lineset, temps, press, g_lo=g_lo, g_hi=g_hi), key, None
+        if self.lf is None or self._lf_key[2:] != key[2:] or self.lf.temps.size != len(temps) or self.lf.dT != self.dT:
+            self.lf = engine.LevelFactored(self.lineset, temps, press, dT=self.dT, g_lo=g_lo, g_hi=g_hi)
+            self._lf_key, self._combined = key, None
+        elif self._lf_key != key:
+            self.lf.rebuild(temps, press)
+            self._lf_key, self._combined = key, None
         self.rows = np.arange(len(temps), dtype=np.int32)
         tv = np.asarray(self.tvib, float).tobytes()
-        if self._combined != tv or self.coeffs is None:
-            self.coeffs, self._combined = self.lf.steps(self.rows, tvib=self.tvib), tv
+        if self._combined != tv or self.coeffs is None or (derivative and self.dcoeffs is None):
+            if derivative:
+                self.coeffs, self.dcoeffs = self.lf.steps(self.rows, tvib=self.tvib, derivative=True)
+            else:
+                self.coeffs, self.dcoeffs = self.lf.steps(self.rows, tvib=self.tvib), None
+            self._combined = tv
         return self.coeffs
 
 
@@ -109,14 +121,32 @@ class TvibProfile(smm.LinearProfile_1D_new):
             par.constrain_positive = False
 
 
+class TempProfile(smm.LinearProfile_1D_new):
+    """The retrieval set of the kinetic temperature: named "temp", its parameters the nodes of an OFFSET profile (K) that
+    is added to the scene's reference temperatures, T = temps0 + sum_p mask_p x_p, the masks those of alt_triangle on the
+    scene's altitude levels (engine.level_node_weights).  No parameter is constrained positive.  The Jacobian holds
+    pressure, columns and vibrational temperatures fixed (engine.temperature_jacobian's definition): the number densities
+    and the LOS columns do not follow the offset.  Their part of a temperature change is a set of ordinary column
+    parameters, which a caller who wants it adds as VMR sets."""
+
+    def __init__(self, alt_grid, alt_nodes, apriori_err, apriori=None, first_guess=None):
+        n = len(list(alt_nodes))
+        smm.LinearProfile_1D_new.__init__(self, "temp", alt_grid, alt_nodes, np.zeros(n) if apriori is None else apriori,
+                                          apriori_err, first_guess_prof=first_guess)
+        for par in self.set:
+            par.constrain_positive = False
+
+
 class StateWeights(object):
     """LimbScene.state_weights' result: the column block (par_gas [n_col], par_w_col [n_col, n_pt]), the level block
-    (level_gas: the LevelGas or None, gas: its index, par_level [n_lev], par_w_lev [n_lev, n_layers]) and perm [n_par]:
-    the row of the call's Jacobian (column parameters, then level parameters) that belongs to BayesSet parameter i."""
+    (level_gas: the LevelGas or None, gas: its index, par_level [n_lev], par_w_lev [n_lev, n_layers]), the row block
+    (par_w_temp [n_row, n_layers]: the temperature nodes' masks; None: no such parameter) and perm [n_par]: the row of the
+    call's Jacobian (column parameters, then level parameters, then row parameters) that belongs to BayesSet parameter i."""
 
-    def __init__(self, par_gas, par_w_col, level_gas, gas, par_level, par_w_lev, perm):
+    def __init__(self, par_gas, par_w_col, level_gas, gas, par_level, par_w_lev, perm, par_w_temp=None):
         self.par_gas, self.par_w_col, self.level_gas, self.gas = par_gas, par_w_col, level_gas, gas
         self.par_level, self.par_w_lev, self.perm = par_level, par_w_lev, perm
+        self.par_w_temp = np.zeros((0, np.shape(par_w_lev)[1])) if par_w_temp is None else par_w_temp
 
 
 class LimbPixel(object):
@@ -228,11 +258,12 @@ class LimbScene(object):
         """The parameters of a mixed state vector, split in BayesSet order into the column block -- sets named after a gas:
         VMR-profile parameters, their masks at the LOS sample altitudes `alt` as in profile_weights -- and the level block
         -- sets named "tvib:<gas>:<level>" (TvibProfile) of ONE LevelGas: their masks on the coefficient rows, the scene's
-        altitude levels.  Returns a StateWeights (its perm leads back to BayesSet order)."""
+        altitude levels -- and the row block -- the set named "temp" (TempProfile): its masks on the coefficient rows
+        likewise.  Returns a StateWeights (its perm leads back to BayesSet order)."""
         names = [g.name for g in self.gases]
         top = self.z[-1] + (self.z[-1] - self.z[-2])
         zz = np.append(self.z, top)
-        par_gas, par_w_col, par_level, par_w_lev, kind = [], [], [], [], []
+        par_gas, par_w_col, par_level, par_w_lev, par_w_temp, kind = [], [], [], [], [], []
         level_gas = None
         for name in bayes_set.order:
             st = bayes_set.sets[name]
@@ -242,6 +273,14 @@ class LimbScene(object):
                     par_gas.append(names.index(name))
                     par_w_col.append(np.interp(alt, zz, np.append(m, m[-1])))
                     kind.append(0)
+                continue
+            if name == "temp":
+                for par in st.set:
+                    m = np.asarray(par.maskgrid.mask, dtype=float)
+                    if m.shape != self.z.shape:
+                        raise ValueError("the masks of %r are not on the scene's altitude levels" % (name,))
+                    par_w_temp.append(m)
+                    kind.append(2)
                 continue
             parts = name.split(":")
             ok = len(parts) == 3 and parts[0] == "tvib" and parts[1] in names and parts[2].isdigit()
@@ -263,9 +302,32 @@ class LimbScene(object):
         kind = np.array(kind, dtype=int)
         n_col = int((kind == 0).sum())
         perm = np.where(kind == 0, np.cumsum(kind == 0) - 1, n_col + np.cumsum(kind == 1) - 1).astype(int)
+        if par_w_temp:
+            perm = np.where(kind == 2, n_col + len(par_level) + np.cumsum(kind == 2) - 1, perm).astype(int)
         return StateWeights(np.array(par_gas, np.int32), np.array(par_w_col, dtype=float).reshape(n_col, len(alt)), level_gas,
                             None if level_gas is None else self.gases.index(level_gas), np.array(par_level, np.int32),
-                            np.array(par_w_lev, dtype=float).reshape(len(par_level), len(self.z)), perm)
+                            np.array(par_w_lev, dtype=float).reshape(len(par_level), len(self.z)), perm,
+                            np.array(par_w_temp, dtype=float).reshape(len(par_w_temp), len(self.z)))
+
+    def temperature_derivatives(self):
+        """(coeffs, dcoeffs): (abs, emi) of every gas at the CURRENT temperatures and their derivatives with respect to
+        each layer's kinetic temperature (pressure and vibrational temperatures fixed), recomputed for a gas only when
+        the temperatures moved since its last call here.  A LevelGas (built with dT) gives both from its pair tables
+        (layer_coefficients(derivative=True)); a plain Gas costs two coefficient ops (engine.coefficients_dT, scheme
+        "forward", on the coefficients just computed)."""
+        key = (self.temps.tobytes(), self.press.tobytes())
+        for g in self.gases:
+            if isinstance(g, LevelGas):
+                if not g.dT:
+                    raise ValueError("a temperature retrieval needs LevelGas(%r, ..., dT=...): the tables at T + dT" % (g.name,))
+                g.layer_coefficients(self.temps, self.press, g_lo=0, g_hi=len(self.grid), derivative=True)   # (coefficients()' own shard key)
+            elif getattr(g, "_dT_key", None) != key or g.coeffs is None or g.coeffs_shard != (0, len(self.grid)):
+                g.coeffs = g.lineset.abscoeff_layers(self.temps, self.press, tvib=g.tvib)
+                g.coeffs_shard = (0, len(self.grid))
+                _, g.dcoeffs = engine.coefficients_dT(g.lineset, self.temps, self.press, tvib=g.tvib, scheme="forward",
+                                                      coeffs=g.coeffs)
+                g._dT_key = key
+        return [g.coeffs for g in self.gases], [g.dcoeffs for g in self.gases]
 
 
 def _one_call_eligible(pixels, bayes_set, fov_closed_form):
@@ -692,12 +754,19 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
 
 
 def _state_into_gases(scene, bayes_set):
-    """The BayesSet's profiles into the gases: add_clim for the VMR sets, tvib = tvib0 + offset for the Tvib sets."""
+    """The BayesSet's profiles into the gases: add_clim for the VMR sets, tvib = tvib0 + offset for the Tvib sets; the
+    "temp" set into the scene, temps = temps0 + offset (temps0: the temperatures at the first such call; the number
+    densities and the LOS columns stay as they are, see TempProfile)."""
     names, tvib = [g.name for g in scene.gases], {}
     for name in bayes_set.order:
         st = bayes_set.sets[name]
         if name in names:
             scene.gas(name).add_clim(st.profile())
+            continue
+        if name == "temp":
+            if getattr(scene, "temps0", None) is None:
+                scene.temps0 = scene.temps.copy()
+            scene.temps = scene.temps0 + st.profile()
             continue
         _, gas, level = name.split(":")
         g = scene.gas(gas)
@@ -710,7 +779,10 @@ def _state_into_gases(scene, bayes_set):
 def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM=0.1, L1_reg=False,
                     fov_closed_form=True):
     """inversion_fast_limb's loop for a MIXED state vector: VMR-profile sets (named after a gas) together with the
-    vibrational-temperature sets of one LevelGas (TvibProfile).  Per iteration: the profiles into the gases, the
+    vibrational-temperature sets of one LevelGas (TvibProfile) and the kinetic-temperature set (TempProfile; with it the
+    coefficients and their temperature derivatives are recomputed per iteration, LimbScene.temperature_derivatives, and
+    the same call takes the third kind too; after the loop the scene holds the final temperatures while a plain gas's
+    cached coefficients are the last iteration's: coefficients(refresh=True) recomputes them).  Per iteration: the profiles into the gases, the
     coefficient stack (the LevelGas recombines its tables when its Tvib moved), ONE Jacobian call for all LOS of all pixels
     and both kinds of parameter (LevelFactored.state_jacobian), the instrument bands, the closed-form field of view,
     chi square, the stopping rule and the Levenberg-Marquardt step (smm.inversion_algebra_arrays).  Returns
@@ -721,7 +793,8 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     if not (with_fov == 0 or (with_fov == len(pixels) and fov_closed_form)):
         raise ValueError("inversion_state needs the closed-form field of view for every pixel, or for none")
     alts = [a for pix in pixels for a in pix.los_alts()]
-    scene.state_weights(bayes_set, np.zeros(1))                 # the sets' names are checked before anything is changed
+    # the sets' names are checked before anything is changed
+    with_temp = scene.state_weights(bayes_set, np.zeros(1)).par_w_temp.shape[0] > 0
     _state_into_gases(scene, bayes_set)
     obs = [pix.observation for pix in pixels]
     masks = None if all(pix.mask is None for pix in pixels) else [pix.mask for pix in pixels]
@@ -753,10 +826,19 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     chi_old, chi, low, dlow = None, None, None, None
     n_los = len(alts)
     for num_it in range(max_it):
-        coeffs = scene.coefficient_stack()
+        coeffs = None if with_temp else scene.coefficient_stack()
         los, alt = scene.los(alts)
         w = scene.state_weights(bayes_set, alt)
-        if w.level_gas is None:
+        if with_temp:          # coefficients at the current temperatures and their derivatives, then all three kinds at once
+            coeffs, dcoeffs = (engine.gas_stack(c) for c in scene.temperature_derivatives())
+            if w.level_gas is None:
+                rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col, dcoeffs=dcoeffs,
+                                                           par_t=w.par_w_temp)
+            else:
+                lg = w.level_gas
+                rad, jac = lg.lf.state_jacobian(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, par_gas=w.par_gas,
+                                                par_w_col=w.par_w_col, gas=w.gas, dcoeffs=dcoeffs, par_w_temp=w.par_w_temp)
+        elif w.level_gas is None:
             rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col)
         else:
             lg = w.level_gas
