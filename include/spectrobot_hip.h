@@ -576,6 +576,32 @@ int sr_limb_rays_jac_state_rows_dev(const double *abs_c, const double *emi_c, in
                                     const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c,
                                     int n_row, const double *par_t, double *rad, double *jac, void *stream);
 
+/* sr_limb_rays_jac_state_rows_dev on the instrument's bands, in one call: the same recursion for the same mixed state
+ * vector (column, level and row parameters, every argument up to par_t as there), but the hi-res spectra rad
+ * [n_rays][n_pts] and jac [n_rays][n_par][n_pts] are never written: the recursion kernel integrates the bands in its
+ * epilogue (sr_hires_to_lowres_shard_dev's weights, one v_mfma_f64_16x16x4 product per wave and 16-band tile), the
+ * partial sums are added on the device and the closed-form field of view of sr_retrieval_forward_dev is applied to the
+ * few KB that reach the host.  What sr_limb_rays_jac_state_rows_dev + sr_hires_to_lowres_shard_dev on rad and on jac +
+ * the field-of-view integral compute, up to the order of the band sums.
+ * The hi-res grid is the descriptor's: point j of the tables is w0 + (g_lo + j) step with los->w0, los->step, los->g_lo
+ * (as for the Planck background); a descriptor without a grid (step <= 0) is refused.  A spectral shard (g_lo > 0 or
+ * fewer points than the grid) returns PARTIAL band integrals with the semantics of sr_hires_to_lowres_shard_dev: shards
+ * that each hold the next shard's first point add up to the whole.
+ * centers_nm / widths_nm: HOST [n_bands]; n_sigma, out_units as sr_hires_to_lowres_dev; fov: HOST [n_rays / 3][7] as
+ * sr_retrieval_forward_dev's (n_rays a multiple of 3), or NULL: the rays themselves; out: HOST
+ * [n_rays / 3 or n_rays][1 + n_par][n_bands], n_par = n_col + n_lev + n_row: row 0 the radiance, row 1 + p the
+ * derivative to parameter p in the call's order (column, level, row parameters).  A parameter a ray never touches is an
+ * exact 0.0 in every band, a band whose window misses the grid an exact 0.0 in every row.  n_row == 0 needs no dabs_c /
+ * demi_c / par_t.  init_mode 1 is refused (SR_ERR_ARG), n_pts above the limit SR_ERR_LIMIT.  All arguments are checked
+ * before the first copy or launch: a refused call leaves out untouched.  Synchronises the stream.
+ * Checked against the composition of the calls it replaces (tests/test_gpu_state_bands.py). */
+int sr_limb_rays_state_bands_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                 const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
+                                 const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
+                                 const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c,
+                                 int n_row, const double *par_t, const double *centers_nm, const double *widths_nm,
+                                 int n_bands, double n_sigma, int out_units, const double *fov, double *out, void *stream);
+
 /* The radiance budget of the ray batch: which gas, and which level of the level-factored gas `gas`, emits the radiance
  * that arrives.  The recursion is linear in the emission: with tau = sum_g abs_g[r] u_g, t = exp(-tau), f = (1 - t) / tau
  * of a segment on coefficient row r,

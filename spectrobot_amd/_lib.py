@@ -144,6 +144,10 @@ SYMBOLS = {
     "sr_limb_rays_jac_state_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(LosDesc), C.c_int, ip,
                                                   dp, C.c_int, C.c_void_p, C.c_int, C.c_int, ip, C.c_int, ip, dp, C.c_void_p,
                                                   C.c_void_p, C.c_int, dp, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_limb_rays_state_bands_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(LosDesc), C.c_int, ip,
+                                               dp, C.c_int, C.c_void_p, C.c_int, C.c_int, ip, C.c_int, ip, dp, C.c_void_p,
+                                               C.c_void_p, C.c_int, dp, dp, dp, C.c_int, C.c_double, C.c_int, dp, dp,
+                                               C.c_void_p]),
     "sr_limb_rays_parts_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(LosDesc), C.c_int,
                                          C.c_void_p, C.c_int, C.c_int, ip, C.c_int, ip, ip, dp, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),

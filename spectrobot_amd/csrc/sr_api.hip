@@ -2526,6 +2526,37 @@ static int lowres_land(int n_rows, int n_bands, double *out_host, hipStream_t st
   return SR_OK;
 }
 
+// The band spectra of a ray batch and their derivatives on their way out (sr_retrieval_forward_dev,
+// sr_limb_rays_state_bands_dev).  low: [n_rays + n_rays n_par][n_bands], the radiances' rows first, then row
+// n_rays + r n_par + p; out: [n_pix or n_rays][1 + n_par][n_bands].  fov [n_pix][7] (see sr_retrieval_forward_dev): the
+// closed-form field-of-view integral of every pixel's three rays, the operations of the mirror's fov_closed_form in its
+// order; null: the rays themselves.
+static void fov_rows(const double *low, int n_rays, int n_par, int n_bands, const double *fov, double *out) {
+  const int n_row = 1 + n_par;
+  // row of (ray r, quantity q): q = 0 the radiance, q = 1 + p the derivative to parameter p
+  auto row = [&](int r, int q) { return low + (size_t)(q == 0 ? r : n_rays + r * n_par + (q - 1)) * n_bands; };
+  if (!fov) {
+    for (int r = 0; r < n_rays; ++r)
+      for (int q = 0; q < n_row; ++q) std::memcpy(out + ((size_t)r * n_row + q) * n_bands, row(r, q), sizeof(double) * n_bands);
+    return;
+  }
+  for (int px = 0; px < n_rays / 3; ++px) {
+    const double *f = fov + 7 * px;
+    const double delta = f[0], delta3 = f[1], two_dmax2 = f[2], edge = f[3], m2 = f[4], esse = f[5];
+    const bool has_edge = f[6] != 0.0;
+    for (int q = 0; q < n_row; ++q) {
+      const double *s0 = row(3 * px, q), *s1 = row(3 * px + 1, q), *s2 = row(3 * px + 2, q);
+      double *o = out + ((size_t)px * n_row + q) * n_bands;
+      for (int b = 0; b < n_bands; ++b) { // (the operations of fov_closed_form, in its order)
+        const double c = (s0[b] + s2[b] - 2.0 * s1[b]) / two_dmax2;
+        double total = 2.0 * (s1[b] * delta + c * delta3 / 3.0);
+        if (has_edge) total = total + s1[b] * edge + 2.0 * c * m2 / edge;
+        o[b] = esse * total;
+      }
+    }
+  }
+}
+
 // The radiance route of a batch without parameters keeps packed records: packed again from the columns, on `st`
 static int los_repack(const sr_los *h, hipStream_t st) {
   if (h->n_par != 0 || h->F.n_rec <= 0) return 0;
@@ -2744,28 +2775,7 @@ int sr_retrieval_forward_dev(const double *abs_c, const double *emi_c, int n_lay
                                       low.data(), stream);
     if (rc) return rc;
   }
-  // row of (ray r, quantity q): q = 0 the radiance, q = 1 + p the derivative to parameter p
-  auto row = [&](int r, int q) { return low.data() + (size_t)(q == 0 ? r : n_rays + r * n_par + (q - 1)) * n_bands; };
-  if (!fov) {
-    for (int r = 0; r < n_rays; ++r)
-      for (int q = 0; q < n_row; ++q) std::memcpy(out + ((size_t)r * n_row + q) * n_bands, row(r, q), sizeof(double) * n_bands);
-    return SR_OK;
-  }
-  for (int px = 0; px < n_rays / 3; ++px) {
-    const double *f = fov + 7 * px;
-    const double delta = f[0], delta3 = f[1], two_dmax2 = f[2], edge = f[3], m2 = f[4], esse = f[5];
-    const bool has_edge = f[6] != 0.0;
-    for (int q = 0; q < n_row; ++q) {
-      const double *s0 = row(3 * px, q), *s1 = row(3 * px + 1, q), *s2 = row(3 * px + 2, q);
-      double *o = out + ((size_t)px * n_row + q) * n_bands;
-      for (int b = 0; b < n_bands; ++b) { // (the operations of fov_closed_form, in its order)
-        const double c = (s0[b] + s2[b] - 2.0 * s1[b]) / two_dmax2;
-        double total = 2.0 * (s1[b] * delta + c * delta3 / 3.0);
-        if (has_edge) total = total + s1[b] * edge + 2.0 * c * m2 / edge;
-        o[b] = esse * total;
-      }
-    }
-  }
+  fov_rows(low.data(), n_rays, n_par, n_bands, fov, out);
   return SR_OK;
 }
 
@@ -3382,11 +3392,14 @@ static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev,
 // What the entries below do once their arguments are checked: plan, stage, launch, mark.  cols: the kernel instance
 // with column slots (the state call, with n_col == 0 too); without it n_col is 0 and neither blk nor dcol exists.
 // n_row > 0 (sr_limb_rays_jac_state_rows_dev): the instances with row slots, which read dabs / demi.
+// band_scratch (sr_limb_rays_state_bands_dev): the instrument step's scratch with its weight table in place; the
+// instances with the band epilogue then leave their partial sums there, rad and jac are not used.
 static int limb_jac_state(bool cols, const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
                           const LosShape &shape, int n_col, const int32_t *par_gas, const double *par_w, int gas,
                           const double *tab, int n_tab_rows, const int32_t *coef_row, int n_lev, const int32_t *par_level,
                           const double *par_c, double *rad, double *jac, hipStream_t st, const double *dabs = nullptr,
-                          const double *demi = nullptr, int n_row = 0, const double *par_t = nullptr) {
+                          const double *demi = nullptr, int n_row = 0, const double *par_t = nullptr,
+                          const void *band_scratch = nullptr, int n_bands = 0) {
   const LevelJacPlan P = level_jac_plan(n_col, par_gas, n_lev, par_level, par_c, n_layers, n_row, par_t);
   static thread_local StagerRing ring;
   StagePack pk(ring.take());
@@ -3401,7 +3414,12 @@ static int limb_jac_state(bool cols, const double *abs_c, const double *emi_c, i
   if (rc) return rc;
   const double *dcol = cols ? D.col + (size_t)los->n_gas * D.n_seg : nullptr;
   const int *blk = cols ? pk.dev(p_blk) : nullptr;
-  if (n_row > 0)
+  if (band_scratch)
+    LAUNCHCHK(launch_limb_jac_state_bands(abs_c, emi_c, n_row > 0 ? dabs : nullptr, n_row > 0 ? demi : nullptr, (int)n_pts, n_layers,
+                                          los->n_rays, D.seg_off, D.seg_layer, D.col, dcol, limb_opts(los, D.n_seg), gas, tab,
+                                          n_tab_rows, pk.dev(p_row), P.n_blocks, blk, pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot),
+                                          n_col + n_lev + n_row, band_scratch, n_bands, st));
+  else if (n_row > 0)
     LAUNCHCHK(launch_limb_jac_state_rows(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer,
                                          D.col, dcol, limb_opts(los, D.n_seg), gas, tab, n_tab_rows, pk.dev(p_row), P.n_blocks,
                                          blk, pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot), n_col + n_lev + n_row, rad, jac, st));
@@ -3432,22 +3450,38 @@ int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_l
                         n_par, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream));
 }
 
+// The arguments of the mixed-state calls (sr_limb_rays_jac_state_dev, _state_rows_dev, sr_limb_rays_state_bands_dev),
+// all of them before the first copy or launch (as sr_limb_rays_jac_level_dev does).  out_ok: the caller's outputs are
+// there.  Any kind of parameter may be empty, not all; a kind that is empty needs none of its arrays.
+static int check_state_call(const char *entry, const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                            const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
+                            const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
+                            const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
+                            const double *par_t, bool out_ok, LosShape *shape) {
+  const bool lev_ok = n_lev == 0 || (tab && coef_row && par_level && par_c && n_levels > 0 && n_tab_rows > 0);
+  const bool row_ok = n_row == 0 || (dabs_c && demi_c && par_t);
+  const bool counts_ok = n_col >= 0 && n_lev >= 0 && n_row >= 0 && (int64_t)n_col + n_lev + n_row >= 1;
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, out_ok && counts_ok && lev_ok && row_ok);
+  if (!rc) rc = check_los_par(los, n_layers, n_col, par_gas, par_w, shape);
+  if (rc) return rc;
+  if (gas < 0 || gas >= los->n_gas) return SR_ERR_ARG;
+  if ((rc = refuse_init_mode_1(los, entry, SR_ERR_ARG))) return rc;
+  if (n_lev > 0 && !coef_rows_in_range(coef_row, n_layers, n_tab_rows)) return SR_ERR_ARG;
+  for (int p = 0; p < n_lev; ++p)
+    if (par_level[p] < 0 || par_level[p] >= n_levels) return SR_ERR_ARG;
+  if ((int64_t)n_col + n_lev + n_row > INT_MAX) return SR_ERR_LIMIT;
+  return SR_OK;
+}
+
 int sr_limb_rays_jac_state_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
                                const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
                                const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
                                const int32_t *par_level, const double *par_c, double *rad, double *jac, void *stream) {
-  // everything is checked here, before the first copy or launch (as sr_limb_rays_jac_level_dev does)
   LosShape shape;
-  const bool lev_ok = n_lev == 0 || (tab && coef_row && par_level && par_c && n_levels > 0 && n_tab_rows > 0);
-  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, jac && n_col >= 0 && n_lev >= 0 && n_col + (int64_t)n_lev >= 1 && lev_ok);
-  if (!rc) rc = check_los_par(los, n_layers, n_col, par_gas, par_w, &shape);
+  const int rc = check_state_call("sr_limb_rays_jac_state_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, gas, tab,
+                                  n_levels, n_tab_rows, coef_row, n_lev, par_level, par_c, nullptr, nullptr, 0, nullptr, jac != nullptr,
+                                  &shape);
   if (rc) return rc;
-  if (gas < 0 || gas >= los->n_gas) return SR_ERR_ARG;
-  if ((rc = refuse_init_mode_1(los, "sr_limb_rays_jac_state_dev", SR_ERR_ARG))) return rc;
-  if (n_lev > 0 && !coef_rows_in_range(coef_row, n_layers, n_tab_rows)) return SR_ERR_ARG;
-  for (int p = 0; p < n_lev; ++p)
-    if (par_level[p] < 0 || par_level[p] >= n_levels) return SR_ERR_ARG;
-  if ((int64_t)n_col + n_lev > INT_MAX) return SR_ERR_LIMIT;
   return limb_jac_state(true, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, gas, tab, n_tab_rows, coef_row,
                         n_lev, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream));
 }
@@ -3460,23 +3494,54 @@ int sr_limb_rays_jac_state_rows_dev(const double *abs_c, const double *emi_c, in
   if (n_row == 0) // nothing of the third kind: the state call, checks and all
     return sr_limb_rays_jac_state_dev(abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, gas, tab, n_levels, n_tab_rows,
                                       coef_row, n_lev, par_level, par_c, rad, jac, stream);
-  // everything is checked here, before the first copy or launch (as sr_limb_rays_jac_state_dev does)
   LosShape shape;
-  const bool lev_ok = n_lev == 0 || (tab && coef_row && par_level && par_c && n_levels > 0 && n_tab_rows > 0);
-  const bool row_ok = n_row > 0 && dabs_c && demi_c && par_t;
-  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, jac && n_col >= 0 && n_lev >= 0 && lev_ok && row_ok);
-  if (!rc) rc = check_los_par(los, n_layers, n_col, par_gas, par_w, &shape);
+  const int rc = check_state_call("sr_limb_rays_jac_state_rows_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, gas,
+                                  tab, n_levels, n_tab_rows, coef_row, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t,
+                                  jac != nullptr, &shape);
   if (rc) return rc;
-  if (gas < 0 || gas >= los->n_gas) return SR_ERR_ARG;
-  if ((rc = refuse_init_mode_1(los, "sr_limb_rays_jac_state_rows_dev", SR_ERR_ARG))) return rc;
-  if (n_lev > 0 && !coef_rows_in_range(coef_row, n_layers, n_tab_rows)) return SR_ERR_ARG;
-  for (int p = 0; p < n_lev; ++p)
-    if (par_level[p] < 0 || par_level[p] >= n_levels) return SR_ERR_ARG;
-  if ((int64_t)n_col + n_lev + n_row > INT_MAX) return SR_ERR_LIMIT;
   // (without column parameters the instances without column code: fewer registers, the same arithmetic)
   return limb_jac_state(n_col > 0, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, gas, tab, n_tab_rows,
                         coef_row, n_lev, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream), dabs_c, demi_c, n_row,
                         par_t);
+}
+
+// The mixed-state Jacobian on the instrument's bands: the state call's plan and checks, the instrument step's cached
+// weight table (lowres_prepare, fused), the recursion kernel's band epilogue, the partial sums added straight into the
+// pinned landing buffer, the field of view on the host.
+int sr_limb_rays_state_bands_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                 const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
+                                 const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
+                                 const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c,
+                                 int n_row, const double *par_t, const double *centers_nm, const double *widths_nm,
+                                 int n_bands, double n_sigma, int out_units, const double *fov, double *out, void *stream) {
+  LosShape shape;
+  int rc = check_state_call("sr_limb_rays_state_bands_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, gas, tab,
+                            n_levels, n_tab_rows, coef_row, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t,
+                            out && centers_nm && widths_nm && n_bands > 0, &shape);
+  if (rc) return rc;
+  const int n_rays = los->n_rays, n_par = n_col + n_lev + n_row;
+  if (fov && n_rays % 3 != 0) return SR_ERR_ARG;
+  if ((int64_t)n_rays * (1 + (int64_t)n_par) > INT_MAX) return SR_ERR_LIMIT;
+  const int n_spec = n_rays * (1 + n_par);
+  // the grid is the descriptor's (a descriptor without one, step <= 0, is refused here)
+  rc = lowres_check(n_spec, n_pts, los->g_lo, los->w0, los->step, centers_nm, widths_nm, n_bands, n_sigma, out_units);
+  if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  bool fresh = false;
+  rc = lowres_prepare(n_spec, n_pts, los->g_lo, los->w0, los->step, centers_nm, widths_nm, n_bands, n_sigma, out_units,
+                      /*fused=*/true, st, &fresh);
+  if (rc) return rc;
+  rc = limb_jac_state(n_col > 0, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, gas, tab, n_tab_rows, coef_row,
+                      n_lev, par_level, par_c, nullptr, nullptr, st, dabs_c, demi_c, n_row, par_t, t_lowres.d_weights.p, n_bands);
+  if (rc) return rc;
+  const size_t low_bytes = sizeof(double) * (size_t)n_spec * n_bands;
+  rc = t_lowres.s_land.prepare(low_bytes);
+  if (rc) return rc;
+  LAUNCHCHK(launch_lowres_sum_blocks((int)n_pts, n_spec, n_bands, out_units, static_cast<double *>(t_lowres.s_land.h),
+                                     t_lowres.d_weights.p, st));
+  HIPCHK(hipStreamSynchronize(st));
+  fov_rows(static_cast<const double *>(t_lowres.s_land.h), n_rays, n_par, n_bands, fov, out);
+  return SR_OK;
 }
 
 int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,

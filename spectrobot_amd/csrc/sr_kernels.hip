@@ -3250,6 +3250,19 @@ __global__ __launch_bounds__(256) void sr_limb_jac_layer_kernel(
     if (p0 + q < n_layers) jac[((size_t)ray * n_layers + p0 + q) * n_pts + j] = J[q];
 }
 
+// Where the recursion kernels with a band epilogue (BANDS = true: sr_limb_fold_sens_lds_kernel, sr_limb_jac_state_kernel)
+// find the instrument step's weight table and leave their partial sums; see the comment above the former.
+struct FoldBands {
+  const double *Wt;  // [band tiles][n_pts][16]
+  const int *range;  // [n_bands][2]
+  double *part;
+  int n_bands;
+};
+constexpr int kBandRow = 68; // doubles per row of a wave's tile of values (64 + padding: rows 8 banks apart)
+// the buffer limb_initial() reads with init_mode 1 (which the host refuses for the state kernel): none with BANDS
+__device__ inline const double *limb_state_init_src(const double *jac) { return jac; }
+__device__ inline const double *limb_state_init_src(const FoldBands &) { return nullptr; }
+
 // Derivatives w.r.t. LEVEL parameters of one level-factored gas (sr_limb_rays_jac_level_dev, COLS = false) or w.r.t. a
 // MIXED state vector of column and level parameters in one pass (sr_limb_rays_jac_state_dev, COLS = true).  The gas's
 // coefficients are abs[r] = sum_L pop[r][L] A_L[row[r]], emi[r] likewise with E_L (the pair tables of
@@ -3286,21 +3299,36 @@ __global__ __launch_bounds__(256) void sr_limb_jac_layer_kernel(
 // its one multiply-add; a row no row slot weights costs nothing.  dabs and demi are the kernel's last two arguments and
 // exist with ROWS = true only (row_spectra, empty otherwise): the ROWS = false instances keep their argument block and
 // with it their machine code, instruction for instruction.
-template <int NG, int NP, bool COLS, bool ROWS, class... RowSpectra>
+// BANDS = true (sr_limb_rays_state_bands_dev): the instrument bands in the epilogue, as sr_limb_fold_sens_lds_kernel<., true>
+// integrates them.  The recursion is the same, operation for operation; at its end a wave's values -- its NP accumulators,
+// and in parameter block 0 the radiance -- go through the wave's own tile in LDS (row q = slot q, row NP = the radiance) and
+// are multiplied with the 16-band tiles of Wt by v_mfma_f64_16x16x4: ONE partial sum per (spectrum, band, wave) in `part`
+// [(row n_slots + 4 pb + wave) n_tiles + tile][16], rows as sr_retrieval_forward_dev orders them (row ray = the radiance,
+// row n_rays + ray n_par + p = parameter p), which sr_lowres_sum_blocks_kernel adds.  A block writes the rows of its own
+// slots (slot_par >= 0), block 0 the radiance row too.  NP = 16 and the radiance are 17 rows, one more than an MFMA tile:
+// block 0 alone runs a SECOND row tile that holds the radiance (NP = 8: nine rows, one tile).  No lane leaves early: a
+// wave needs its 64 lanes for the product, so lanes beyond the grid work on its last point (`live` false) and put exact
+// zeros into the tile; waves that lie wholly beyond the grid leave (the sum kernel reads only slots inside a band's point
+// range).  An accumulator no segment of the ray touches is an exact 0 and so is every one of its sums.  `jac` is the
+// FoldBands of the call in these instances and rad is not used; the BANDS = false instances keep their argument block,
+// their early exit and their stores: the same machine code as before the parameter existed.
+template <int NG, int NP, bool COLS, bool ROWS, bool BANDS, class... RowSpectra>
 __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
     const int *__restrict__ seg_off, const int *__restrict__ seg_layer, const double *__restrict__ col,
     const double *__restrict__ dcol, LimbOpts o, int n_rays, int gas, const double *__restrict__ tab, int n_tab_rows,
     const int *__restrict__ coef_row, const int *__restrict__ blk, const int *__restrict__ ent_off,
     const LevelEnt *__restrict__ ent, const int *__restrict__ slot_par, int n_par, double *__restrict__ rad,
-    double *__restrict__ jac, RowSpectra... row_spectra) {
+    std::conditional_t<BANDS, FoldBands, double *__restrict__> jac, RowSpectra... row_spectra) {
   static_assert(NP <= 16 && NG <= 4, "blk packs the gases of 16 column slots, two bits each");
   static_assert(sizeof...(RowSpectra) == (ROWS ? 2 : 0), "dabs and demi with ROWS, nothing without");
   int pb, ray;
   if (!limb_block((n_pts + 255) / 256, n_rays, pb, ray)) return;
-  const int j = pb * 256 + threadIdx.x;
-  if (j >= n_pts) return;
-  double I = limb_initial(o, jac, 0, j), J[NP]; // init_mode 1 is refused by the host for this kernel
+  const int jt = pb * 256 + threadIdx.x;
+  if (BANDS ? jt - (int)(threadIdx.x & 63) >= n_pts : jt >= n_pts) return; // BANDS: only whole waves beyond the grid leave
+  [[maybe_unused]] const bool live = jt < n_pts;
+  const int j = BANDS ? min(jt, n_pts - 1) : jt;
+  double I = limb_initial(o, limb_state_init_src(jac), 0, j), J[NP]; // init_mode 1 is refused by the host for this kernel
 #pragma unroll
   for (int q = 0; q < NP; ++q) J[q] = 0.0;
   const int nc = COLS ? blk[2 * blockIdx.z] : 0;
@@ -3401,11 +3429,59 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     }
     I = I * t + src;
   }
-  if (blockIdx.z == 0 && rad) rad[(size_t)ray * n_pts + j] = I;
+  if constexpr (BANDS) {
+    // Wave by wave, no block barrier (sr_limb_fold_sens_lds_kernel's epilogue): a wave's values go through ITS tile, its
+    // sums to its own slot of `part`.
+    constexpr int kV = NP + 1; // rows of a wave's tile: the slots, then the radiance
+    __shared__ double tiles[4 * kV * kBandRow];
+    const FoldBands &bd = jac;
+    const int c_lo = pb * 256, n_slots = 4 * ((n_pts + 255) / 256);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lo = lane & 15, kq = lane >> 4;
+    const int n_tiles = (bd.n_bands + 15) >> 4;
+    const bool first = blockIdx.z == 0;
+    const int n_val = first ? kV : NP; // (the radiance is block 0's)
+    double *vt = tiles + wave * (kV * kBandRow);
 #pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    const int p = slot_par[blockIdx.z * NP + q];
-    if (p >= 0) jac[((size_t)ray * n_par + p) * n_pts + j] = J[q];
+    for (int q = 0; q < NP; ++q) vt[q * kBandRow + lane] = live ? J[q] : 0.0;
+    vt[NP * kBandRow + lane] = live && first ? I : 0.0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // A[row = lane & 15][k = lane >> 4], B[k][col = lane & 15], D[row = (lane >> 4) + 4 r][col]; row tile rt holds the
+    // values 16 rt .. 16 rt + 15 (a second one with NP = 16 in block 0 only: the radiance)
+    for (int rt = 0; 16 * rt < n_val; ++rt) {
+      const int vr = 16 * rt + lo;
+      const double *va = vt + min(vr, kV - 1) * kBandRow + kq;
+      double A[16];
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) A[ks] = vr < n_val ? va[4 * ks] : 0.0;
+      long long orow[4]; // the rows of `part` this lane's four sums belong to, or -1
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int q = 16 * rt + kq + 4 * r;
+        const int p = slot_par[blockIdx.z * NP + min(q, NP - 1)];
+        orow[r] = q < NP ? (p >= 0 ? (long long)n_rays + (long long)ray * n_par + p : -1) : (q == NP && first ? (long long)ray : -1);
+      }
+      for (int tile = 0; tile < n_tiles; ++tile) {
+        const double *wt = bd.Wt + (size_t)tile * n_pts * 16 + lo;
+        double Bv[16]; // a tile's sixteen B operands requested together
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) Bv[ks] = wt[(size_t)min(c_lo + 64 * wave + 4 * ks + kq, n_pts - 1) * 16]; // (beyond the grid A is zero)
+        v4d acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[ks], Bv[ks], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (orow[r] >= 0) bd.part[(((size_t)orow[r] * n_slots + 4 * pb + wave) * n_tiles + tile) * 16 + lo] = acc[r];
+      }
+    }
+  } else {
+    if (blockIdx.z == 0 && rad) rad[(size_t)ray * n_pts + j] = I;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+      const int p = slot_par[blockIdx.z * NP + q];
+      if (p >= 0) jac[((size_t)ray * n_par + p) * n_pts + j] = J[q];
+    }
   }
 }
 
@@ -4281,14 +4357,8 @@ static_assert(sizeof(FoldDense) == kSensRecD * 8, "FoldDense in doubles");
 // value and a lane reduction, 26 ds_bpermute each; configs[4]'s 14 bands all cover its whole grid: +27 us on the kernel's
 // 260.)  part: [n_rays (1 + n_par)][64-point slots][band tiles][16], rows as sr_retrieval_forward_dev orders them;
 // sr_lowres_sum_blocks_kernel adds a band's slots.
-struct FoldBands {
-  const double *Wt;  // [band tiles][n_pts][16]
-  const int *range;  // [n_bands][2]
-  double *part;
-  int n_bands;
-};
+// (FoldBands and kBandRow: above sr_limb_jac_state_kernel, whose BANDS instances use them too)
 constexpr int kBandVals = kFoldDensePar + 1;  // spectra per ray: the radiance and its derivatives
-constexpr int kBandRow = 68;                  // doubles per row of a wave's tile of values (64 + padding: rows 8 banks apart)
 template <int NG, bool BANDS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NG <= 2 ? 4 : 3, NG <= 2 ? 4 : 3))) void sr_limb_fold_sens_lds_kernel(
     const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
@@ -4697,7 +4767,7 @@ int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, i
   auto launch = [&](auto cols) { // no blk: the instance without column slots
     by_level_np(level_jac_np(n_par), [&](auto np) {
       by_ngas(o.n_gas, [&](auto ng) {
-        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, false>), grid,
+        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, false, false>), grid,
                            dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas, tab,
                            n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac);
       });
@@ -4718,10 +4788,40 @@ int launch_limb_jac_state_rows(const double *abs_c, const double *emi_c, const d
   auto launch = [&](auto cols) { // no blk: the instance without column slots
     by_level_np(level_jac_np(n_par), [&](auto np) {
       by_ngas(o.n_gas, [&](auto ng) {
-        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, true,
+        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, true, false,
                                                      const double *, const double *>),
                            grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas,
                            tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac, dabs, demi);
+      });
+    });
+  };
+  if (blk) launch(std::true_type{});
+  else launch(std::false_type{});
+  return (int)hipGetLastError();
+}
+
+int launch_limb_jac_state_bands(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
+                                int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
+                                const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
+                                const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
+                                const int *slot_par, int n_par, const void *lowres_scratch, int n_bands, hipStream_t st) {
+  if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0 || n_bands <= 0 || !lowres_scratch) return 0;
+  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
+  const LowresScratch L = lowres_layout(const_cast<void *>(lowres_scratch), n_pts, n_bands);
+  const FoldBands bd{L.Wt, L.range, L.part, n_bands};
+  double *const no_rad = nullptr;
+  auto launch = [&](auto cols) { // no blk: the instance without column slots
+    by_level_np(level_jac_np(n_par), [&](auto np) {
+      by_ngas(o.n_gas, [&](auto ng) {
+        if (dabs && demi) // row parameters
+          hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, true, true,
+                                                       const double *, const double *>),
+                             grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas,
+                             tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, no_rad, bd, dabs, demi);
+        else
+          hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, false, true>),
+                             grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas,
+                             tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, no_rad, bd);
       });
     });
   };

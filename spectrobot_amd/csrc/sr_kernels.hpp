@@ -268,6 +268,16 @@ int launch_limb_jac_state_rows(const double *abs_c, const double *emi_c, const d
                                const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
                                const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
                                const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st);
+// The same recursion with the instrument bands in its epilogue (the kernel's BANDS = true instances): no spectra are
+// written; the band integrals' partial sums per wave (64 points) go to the instrument step's scratch, whose weight table
+// is in place (launch_lowres_weights; scratch sized for n_rays (1 + n_par) rows, fused), rows as launch_fold_dense orders
+// them: row ray = the radiance, row n_rays + ray n_par + p = parameter p.  launch_lowres_sum_blocks finishes them.
+// dabs / demi null: no row parameters.
+int launch_limb_jac_state_bands(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
+                                int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
+                                const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
+                                const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
+                                const int *slot_par, int n_par, const void *lowres_scratch, int n_bands, hipStream_t st);
 // Radiance budget (sr_limb_parts_kernel): the n_part parts and the background are n_part + 1 slots in blocks of
 // limb_parts_np(n_part); slot_level [n_blocks][NP]: >= 0 the first row of a level's E plane in the pair tables,
 // (2 L + 1) n_tab_rows, -1 - g the gas part of gas g,

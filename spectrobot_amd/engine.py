@@ -536,6 +536,14 @@ class LevelFactored(object):
         kinetic-temperature parameters, T[r] = T0[r] + sum_p par_w_temp[p, r] x_p, through the derivative spectra
         dcoeffs of every gas of the batch on the coefficient rows (this gas's: steps(..., derivative=True); the columns
         held fixed).  Honours the object's spectral shard."""
+        step_row, par_level, par_c = self._state_level_args(step_row, tvib, par_level, par_w_level, q_part)
+        return limb_rays_state_jacobian(coeffs, los, par_gas=par_gas, par_w=par_w_col, tab=self.tab, coef_row=step_row,
+                                        par_level=par_level, par_c=par_c, gas=gas, grid=grid, g_lo=int(self._shard[0]),
+                                        want_rad=want_rad, dcoeffs=dcoeffs, par_t=par_w_temp)
+
+    def _state_level_args(self, step_row, tvib, par_level, par_w_level, q_part):
+        """(step_row, par_level, par_c) of state_jacobian / state_bands: par_c = par_w_level * d pop / d Tvib, formed as in
+        tvib_jacobian (None without level parameters)."""
         step_row = np.ascontiguousarray(step_row, dtype=np.int32)
         par_level = np.ascontiguousarray(par_level, dtype=np.int32).reshape(-1)
         par_w = np.zeros((0, step_row.size)) if par_level.size == 0 else np.asarray(par_w_level, dtype=np.float64)
@@ -548,9 +556,20 @@ class LevelFactored(object):
         if par_level.size:
             dpop = self.ls.level_populations_dtvib(self.temps[step_row], tvib, q_part=q_part)  # [n_steps, n_levels]
             par_c = par_w * dpop.T[par_level]
-        return limb_rays_state_jacobian(coeffs, los, par_gas=par_gas, par_w=par_w_col, tab=self.tab, coef_row=step_row,
-                                        par_level=par_level, par_c=par_c, gas=gas, grid=grid, g_lo=int(self._shard[0]),
-                                        want_rad=want_rad, dcoeffs=dcoeffs, par_t=par_w_temp)
+        return step_row, par_level, par_c
+
+    def state_bands(self, coeffs, los, step_row, tvib, par_level, par_w_level, grid, centers_nm, widths_nm, par_gas=None,
+                    par_w_col=None, gas=0, q_part=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None):
+        """state_jacobian on the instrument's bands in one library call (limb_rays_state_bands): numpy [n_rays | n_rays / 3,
+        1 + n_par, n_bands], row 0 the radiance, row 1 + p the derivative to parameter p (VMR-profile, vibrational-
+        temperature, kinetic-temperature parameters, as state_jacobian orders them); no hi-res spectrum is written.  The
+        parameters' arguments and their errors are state_jacobian's; the bands' (and fov) those of limb_rays_state_bands.
+        Honours the object's spectral shard: partial band integrals then (`grid` is the whole grid)."""
+        step_row, par_level, par_c = self._state_level_args(step_row, tvib, par_level, par_w_level, q_part)
+        return limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=par_gas, par_w=par_w_col, tab=self.tab,
+                                     coef_row=step_row, par_level=par_level, par_c=par_c, gas=gas, dcoeffs=dcoeffs,
+                                     par_t=par_w_temp, out_units=out_units, n_sigma=n_sigma, fov=fov,
+                                     g_lo=int(self._shard[0]))
 
     def level_radiances(self, coeffs, los, step_row, tvib, levels=None, weights=None, gas=0, q_part=None, grid=None,
                         gas_parts=True):
@@ -1135,14 +1154,35 @@ def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, co
     limb_rays_layer_jacobian contracted with par_t inside the recursion.  The columns are held fixed, as in
     temperature_jacobian; the density part of a temperature change is a set of column parameters, which the caller adds
     to par_gas / par_w if it is wanted.  With row parameters the other two kinds may both be left out."""
+    A = _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t)
+    n_pts = A.a.shape[2]
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
+    jac = torch.empty((los.n_rays, A.n_par, n_pts), dtype=torch.float64, device="cuda")
+    if par_t is not None:
+        check(lib.sr_limb_rays_jac_state_rows_dev(*A.head, ptr(rad), ptr(jac), _stream_ptr()), "sr_limb_rays_jac_state_rows_dev")
+        return rad, jac
+    check(lib.sr_limb_rays_jac_state_dev(*A.head[:16], ptr(rad), ptr(jac), _stream_ptr()), "sr_limb_rays_jac_state_dev")
+    return rad, jac
+
+
+class _StateArgs(object):
+    """What _state_args returns: a, e (the stacked coefficients), desc, n_col, n_lev, n_row, n_par, head -- the arguments of
+    sr_limb_rays_jac_state_rows_dev up to par_t, in its order (the first 16 are those of sr_limb_rays_jac_state_dev up to
+    par_c) -- and keep, the arrays and tensors the pointers in head point into."""
+
+
+def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t):
+    """The arguments of a mixed-state call (limb_rays_state_jacobian, limb_rays_state_bands), checked and marshalled: the
+    one place where their shapes are refused."""
     if (dcoeffs is None) != (par_t is None):
         raise ValueError("row parameters need both dcoeffs and par_t")
     a, e = _gas_stack(coeffs)
     n_gas, n_layers, n_pts = a.shape
     if n_gas != los.n_gas:
         raise ValueError("%d coefficient sets for %d gases" % (n_gas, los.n_gas))
-    n_col = n_lev = n_levels = n_tab_rows = 0
-    pg = pw = cr = pl = pc = None
+    n_col = n_lev = n_row = n_levels = n_tab_rows = 0
+    pg = pw = cr = pl = pc = pt = da = de = None
     if par_gas is not None and np.asarray(par_gas).size:
         par_gas, pg = _i(np.asarray(par_gas).reshape(-1))
         par_w, pw = _d(par_w)
@@ -1165,21 +1205,46 @@ def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, co
         n_row = par_t.shape[0]
         if n_col + n_lev + n_row == 0:
             raise ValueError("no parameters: give column parameters, level parameters or row parameters")
-        rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
-        jac = torch.empty((los.n_rays, n_col + n_lev + n_row, n_pts), dtype=torch.float64, device="cuda")
-        check(lib.sr_limb_rays_jac_state_rows_dev(ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw, int(gas),
-                                                  ptr(tab) if n_lev else None, n_levels, n_tab_rows, cr, n_lev, pl, pc,
-                                                  ptr(da), ptr(de), n_row, pt, ptr(rad), ptr(jac), _stream_ptr()),
-              "sr_limb_rays_jac_state_rows_dev")
-        return rad, jac
-    if n_col + n_lev == 0:
+    elif n_col + n_lev == 0:
         raise ValueError("no parameters: give column parameters, level parameters or both")
-    rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
-    jac = torch.empty((los.n_rays, n_col + n_lev, n_pts), dtype=torch.float64, device="cuda")
-    check(lib.sr_limb_rays_jac_state_dev(ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw, int(gas),
-                                         ptr(tab) if n_lev else None, n_levels, n_tab_rows, cr, n_lev, pl, pc, ptr(rad),
-                                         ptr(jac), _stream_ptr()), "sr_limb_rays_jac_state_dev")
-    return rad, jac
+    A = _StateArgs()
+    A.a, A.e, A.desc, A.n_col, A.n_lev, A.n_row, A.n_par = a, e, d, n_col, n_lev, n_row, n_col + n_lev + n_row
+    A.keep = (par_gas, par_w, tab, cr, pl, pc, da, de, par_t)
+    A.head = (ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw, int(gas), ptr(tab) if n_lev else None, n_levels,
+              n_tab_rows, cr, n_lev, pl, pc, ptr(da), ptr(de), n_row, pt)
+    return A
+
+
+def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None, par_w=None, tab=None, coef_row=None,
+                          par_level=None, par_c=None, gas=0, dcoeffs=None, par_t=None, out_units="Wm2", n_sigma=5.0, fov=None,
+                          g_lo=0):
+    """limb_rays_state_jacobian on the instrument's bands in ONE library call (sr_limb_rays_state_bands_dev): the same
+    mixed state vector (column, level, row parameters: the same arguments, the same errors), but no hi-res spectrum is
+    written -- the recursion kernel integrates the bands in its epilogue.  Returns numpy [n_rays | n_rays / 3, 1 + n_par,
+    n_bands] in out_units: row 0 the radiance, row 1 + p its derivative to parameter p (column, level, row parameters, each
+    kind in the caller's order).  What limb_rays_state_jacobian + hires_to_lowres on rad and jac (+ fov_closed_form) give,
+    up to the order of the band sums.  fov: fov_factors of the pixels, three rays each.  A spectral shard (g_lo, the
+    coefficient tables' width; `grid` is always the whole grid) gives its partial band integrals, as hires_to_lowres."""
+    A = _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t)
+    n_pts = A.a.shape[2]
+    w0, step, n = grid_params(grid)
+    A.desc.w0, A.desc.step = w0, step   # (the grid of the bands; with a Planck background desc() has set the same)
+    centers_nm, cp = _d(centers_nm)
+    widths_nm, wp = _d(widths_nm)
+    if widths_nm.size != centers_nm.size:
+        raise ValueError("{} spectral widths for {} grid points".format(widths_nm.size, centers_nm.size))
+    if not (0 <= g_lo and g_lo + n_pts <= n):
+        raise ValueError("the coefficient tables cover grid points outside the grid")
+    n_out, fp = los.n_rays, None
+    if fov is not None:
+        fov, fp = _d(fov)
+        if los.n_rays % 3 or fov.shape != (los.n_rays // 3, 7):
+            raise ValueError("fov must be [n_rays / 3, 7] (three rays per pixel)")
+        n_out = los.n_rays // 3
+    out = np.empty((n_out, 1 + A.n_par, centers_nm.size))
+    check(lib.sr_limb_rays_state_bands_dev(*A.head, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp,
+                                           out.ctypes.data_as(dp), _stream_ptr()), "sr_limb_rays_state_bands_dev")
+    return out
 
 
 def limb_rays_parts(coeffs, los, part_gas, part_level, part_c=None, tab=None, coef_row=None, gas=0, grid=None, g_lo=0,

@@ -777,7 +777,7 @@ def _state_into_gases(scene, bayes_set):
 
 
 def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM=0.1, L1_reg=False,
-                    fov_closed_form=True):
+                    fov_closed_form=True, bands_in_kernel=False):
     """inversion_fast_limb's loop for a MIXED state vector: VMR-profile sets (named after a gas) together with the
     vibrational-temperature sets of one LevelGas (TvibProfile) and the kinetic-temperature set (TempProfile; with it the
     coefficients and their temperature derivatives are recomputed per iteration, LimbScene.temperature_derivatives, and
@@ -787,7 +787,10 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     and both kinds of parameter (LevelFactored.state_jacobian), the instrument bands, the closed-form field of view,
     chi square, the stopping rule and the Levenberg-Marquardt step (smm.inversion_algebra_arrays).  Returns
     (chi, obs, sims, bayes_set) with .history, .stop, .jacobian and the stored averaging kernel and covariance, like
-    inversion_fast_limb.  Every pixel has the closed-form field of view, or none has a field of view."""
+    inversion_fast_limb.  Every pixel has the closed-form field of view, or none has a field of view.
+    bands_in_kernel=True: the Jacobian call, the instrument bands and the field of view of an iteration are ONE library call
+    (LevelFactored.state_bands / engine.limb_rays_state_bands): the recursion kernel integrates the bands itself and no
+    hi-res radiance or Jacobian is written.  The same numbers up to the order of the band sums (1e-12 relative)."""
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)
     with_fov = sum(pix.fov_half > 0 for pix in pixels)
     if not (with_fov == 0 or (with_fov == len(pixels) and fov_closed_form)):
@@ -829,25 +832,40 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
         coeffs = None if with_temp else scene.coefficient_stack()
         los, alt = scene.los(alts)
         w = scene.state_weights(bayes_set, alt)
-        if with_temp:          # coefficients at the current temperatures and their derivatives, then all three kinds at once
+        # with_temp: coefficients at the current temperatures and their derivatives, then all three kinds at once
+        dcoeffs = None
+        if with_temp:
             coeffs, dcoeffs = (engine.gas_stack(c) for c in scene.temperature_derivatives())
-            if w.level_gas is None:
+        par_w_temp = w.par_w_temp if with_temp else None
+        lg = w.level_gas
+        if bands_in_kernel:    # Jacobians, instrument bands and field of view in one call: [n_pix | n_los, 1 + n_par, n_bands]
+            band_args = dict(out_units=scene.out_units, fov=engine.fov_factors(rots) if with_fov else None)
+            if lg is None:
+                both = engine.limb_rays_state_bands(coeffs, los, scene.grid, scene.bands_nm, scene.widths_nm, par_gas=w.par_gas,
+                                                    par_w=w.par_w_col, dcoeffs=dcoeffs, par_t=par_w_temp, **band_args)
+            else:
+                both = lg.lf.state_bands(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, scene.grid, scene.bands_nm,
+                                         scene.widths_nm, par_gas=w.par_gas, par_w_col=w.par_w_col, gas=w.gas, dcoeffs=dcoeffs,
+                                         par_w_temp=par_w_temp, **band_args)
+            n_par = both.shape[1] - 1
+            fov = both if with_fov else both[1::3]
+            fov = np.concatenate([fov[:, :1, :], fov[:, 1:, :][:, w.perm]], axis=1)
+        else:                  # (the calls as they always were: without a temperature set no call names row parameters)
+            if with_temp and lg is None:
                 rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col, dcoeffs=dcoeffs,
                                                            par_t=w.par_w_temp)
-            else:
-                lg = w.level_gas
+            elif with_temp:
                 rad, jac = lg.lf.state_jacobian(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, par_gas=w.par_gas,
                                                 par_w_col=w.par_w_col, gas=w.gas, dcoeffs=dcoeffs, par_w_temp=w.par_w_temp)
-        elif w.level_gas is None:
-            rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col)
-        else:
-            lg = w.level_gas
-            rad, jac = lg.lf.state_jacobian(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, par_gas=w.par_gas,
-                                            par_w_col=w.par_w_col, gas=w.gas)
-        n_par = jac.shape[1]
-        both = np.concatenate([lowres(rad)[:, None, :],
-                               lowres(jac.view(n_los * n_par, -1)).reshape(n_los, n_par, -1)[:, w.perm]], axis=1)
-        fov = smm.fov_closed_form(both[0::3], both[1::3], both[2::3], rots) if with_fov else both[1::3]
+            elif lg is None:
+                rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col)
+            else:
+                rad, jac = lg.lf.state_jacobian(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, par_gas=w.par_gas,
+                                                par_w_col=w.par_w_col, gas=w.gas)
+            n_par = jac.shape[1]
+            both = np.concatenate([lowres(rad)[:, None, :],
+                                   lowres(jac.view(n_los * n_par, -1)).reshape(n_los, n_par, -1)[:, w.perm]], axis=1)
+            fov = smm.fov_closed_form(both[0::3], both[1::3], both[2::3], rots) if with_fov else both[1::3]
         low, dlow = fov[:, 0, :], fov[:, 1:, :]
         for par in bayes_set.params():
             par.set_used()
