@@ -602,6 +602,55 @@ int sr_limb_rays_state_bands_dev(const double *abs_c, const double *emi_c, int n
                                  int n_row, const double *par_t, const double *centers_nm, const double *widths_nm,
                                  int n_bands, double n_sigma, int out_units, const double *fov, double *out, void *stream);
 
+/* sr_limb_rays_jac_state_rows_dev for level parameters of SEVERAL level-factored gases in the same pass: a batch whose
+ * gases lgas[0 .. n_lgas) are each combined from pair tables of their own (two non-LTE emitters in one window) gets the
+ * vibrational-temperature parameters of all of them from ONE walk of each ray, together with the column and the row
+ * parameters.  Level parameter p belongs to level gas k = par_lgas[p] and to its level L = par_level[p]; a segment s on
+ * coefficient row r gives it
+ *   dtau = par_c[p][r] u_g[s] A^k_L[lgas[k].coef_row[r]],   dE = par_c[p][r] u_g[s] E^k_L[lgas[k].coef_row[r]],
+ * g = lgas[k].gas that gas's index in the batch, u_g its column, A^k / E^k its tables -- the term of
+ * sr_limb_rays_jac_state_dev with the gas chosen per parameter; the recursion is unchanged (a parameter of gas A moves
+ * only A's populations).  Column and row parameters exactly as in sr_limb_rays_jac_state_rows_dev.
+ * sr_level_gas: gas in [0, n_gas), no gas twice; tab: DEVICE [n_levels][2][n_tab_rows][n_pts] (sr_glevel_pairs_dev);
+ * coef_row: HOST [n_layers], each in [0, n_tab_rows).  The gases may differ in n_levels, n_tab_rows and coef_row.
+ * lgas: HOST [n_lgas], 1 <= n_lgas <= n_gas; par_lgas: HOST [n_lev], each in [0, n_lgas) (may be NULL with n_lgas == 1);
+ * par_level: HOST [n_lev], each a level of its gas; par_c: HOST [n_lev][n_layers]; every other argument as in
+ * sr_limb_rays_jac_state_rows_dev.  jac: DEVICE [n_rays][n_col + n_lev + n_row][n_pts]: the column parameters, the level
+ * parameters, the row parameters, each kind in the CALLER's order (the level parameters of the gases may be interleaved);
+ * every element is written.  n_lgas == 1 is sr_limb_rays_jac_state_rows_dev itself with that gas (bit for bit); with
+ * n_lev == 0 the tables and row maps are not read and may be NULL.
+ * Refused before the first copy or launch, rad and jac untouched (SR_ERR_ARG unless said otherwise): n_lgas outside
+ * 1 .. n_gas, a gas out of range or named twice, a NULL tab or coef_row, a coef_row value outside its gas's tables,
+ * par_lgas[p] outside [0, n_lgas), par_level[p] not a level of its gas, init_mode 1; n_pts above the limit and n_levels
+ * above 65536 with several gases SR_ERR_LIMIT.
+ * The reference has no counterpart: the build's definition, checked against one sr_limb_rays_jac_state_rows_dev per
+ * level gas, against the extended-precision recursion and against central differences (tests/test_gpu_state_gases.py). */
+typedef struct sr_level_gas {
+  int32_t gas;             /* index of the gas in the batch */
+  int32_t n_levels;        /* levels of its pair tables */
+  int32_t n_tab_rows;      /* (P, T) rows of its pair tables */
+  const double *tab;       /* DEVICE [n_levels][2][n_tab_rows][n_pts] */
+  const int32_t *coef_row; /* HOST [n_layers]: the table row of every coefficient row */
+} sr_level_gas;
+int sr_limb_rays_jac_state_gases_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                     const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
+                                     const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas, const int32_t *par_level,
+                                     const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
+                                     const double *par_t, double *rad, double *jac, void *stream);
+
+/* sr_limb_rays_state_bands_dev for several level-factored gases: the state arguments of
+ * sr_limb_rays_jac_state_gases_dev up to par_t, then the band arguments of sr_limb_rays_state_bands_dev, with their
+ * meaning, limits and refusals (a refused call leaves out untouched).  out: HOST [n_rays / 3 or n_rays][1 + n_par][n_bands],
+ * rows as there with the level parameters in the caller's order.  n_lgas == 1 is sr_limb_rays_state_bands_dev itself.
+ * Synchronises the stream.  Checked against sr_limb_rays_jac_state_gases_dev + the instrument step + the field of view
+ * (tests/test_gpu_state_gases.py). */
+int sr_limb_rays_state_bands_gases_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                       const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
+                                       const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas, const int32_t *par_level,
+                                       const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
+                                       const double *par_t, const double *centers_nm, const double *widths_nm, int n_bands,
+                                       double n_sigma, int out_units, const double *fov, double *out, void *stream);
+
 /* The radiance budget of the ray batch: which gas, and which level of the level-factored gas `gas`, emits the radiance
  * that arrives.  The recursion is linear in the emission: with tau = sum_g abs_g[r] u_g, t = exp(-tau), f = (1 - t) / tau
  * of a segment on coefficient row r,

@@ -3354,14 +3354,23 @@ int sr_limb_rays_jac_layer_dev(const double *abs_c, const double *emi_c, const d
 // level order, then the row parameters in the caller's order, NP per block: a block's column slots come first and stand
 // for consecutive rows of dcol (blk: their number and gases), a row's level entries come in level order without a sort
 // of their own, the entries of its row slots (level kLevelEntRows, c = par_t[p][r]) behind them.
+// par_lgas (several level-factored gases): level parameter p belongs to level gas par_lgas[p]; the level parameters are
+// then listed by (level gas, level) and an entry carries level | level gas << kLevelEntGasShift.  Without it the plan is
+// the one-gas plan, word for word.
 struct LevelJacPlan {
   int n_blocks;
   std::vector<int> blk, ent_off, slot_par;
   std::vector<LevelEnt> ent;
 };
 static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev, const int32_t *par_level, const double *par_c,
-                                   int n_layers, int n_row = 0, const double *par_t = nullptr) {
+                                   int n_layers, int n_row = 0, const double *par_t = nullptr, const int32_t *par_lgas = nullptr) {
   const int n_cl = n_col + n_lev, n_par = n_cl + n_row, np = level_jac_np(n_par), n_blocks = (n_par + np - 1) / np;
+  std::vector<int32_t> packed; // the `level` words of the entries: the level, with several level gases the gas above it
+  if (par_lgas) {
+    packed.resize((size_t)n_lev);
+    for (int p = 0; p < n_lev; ++p) packed[p] = par_level[p] | par_lgas[p] << kLevelEntGasShift;
+    par_level = packed.data();
+  }
   const std::vector<int> order = order_by_level(n_lev, par_level);
   LevelJacPlan P{n_blocks, std::vector<int>((size_t)n_blocks * 2, 0), std::vector<int>((size_t)n_blocks * (n_layers + 1)),
                  std::vector<int>((size_t)n_blocks * np, -1), {}};
@@ -3399,12 +3408,21 @@ static int limb_jac_state(bool cols, const double *abs_c, const double *emi_c, i
                           const double *tab, int n_tab_rows, const int32_t *coef_row, int n_lev, const int32_t *par_level,
                           const double *par_c, double *rad, double *jac, hipStream_t st, const double *dabs = nullptr,
                           const double *demi = nullptr, int n_row = 0, const double *par_t = nullptr,
-                          const void *band_scratch = nullptr, int n_bands = 0) {
-  const LevelJacPlan P = level_jac_plan(n_col, par_gas, n_lev, par_level, par_c, n_layers, n_row, par_t);
+                          const void *band_scratch = nullptr, int n_bands = 0, int n_lgas = 1,
+                          const sr_level_gas *lgas = nullptr, const int32_t *par_lgas = nullptr) {
+  const bool several = n_lgas > 1; // (then gas, tab, n_tab_rows and coef_row are not used: lgas has them per level gas)
+  const LevelJacPlan P = level_jac_plan(n_col, par_gas, n_lev, par_level, par_c, n_layers, n_row, par_t, several ? par_lgas : nullptr);
   static thread_local StagerRing ring;
   StagePack pk(ring.take());
   const auto p_ent = pk.copy(P.ent.data(), P.ent.size(), 1); // (no entries: a valid pointer all the same)
-  const auto p_row = n_lev > 0 ? pk.copy(coef_row, (size_t)n_layers) : pk.zeros<int32_t>((size_t)n_layers);
+  std::vector<int32_t> rows_all; // several level gases: their row maps one behind the other, [n_lgas][n_layers]
+  if (several && n_lev > 0) {
+    rows_all.reserve((size_t)n_lgas * n_layers);
+    for (int k = 0; k < n_lgas; ++k) rows_all.insert(rows_all.end(), lgas[k].coef_row, lgas[k].coef_row + n_layers);
+    coef_row = rows_all.data();
+  }
+  const size_t n_rowmap = (size_t)(several ? n_lgas : 1) * n_layers;
+  const auto p_row = n_lev > 0 ? pk.copy(coef_row, n_rowmap) : pk.zeros<int32_t>(n_rowmap);
   const auto p_off = pk.copy(P.ent_off.data(), P.ent_off.size()), p_slot = pk.copy(P.slot_par.data(), P.slot_par.size());
   const auto p_blk = pk.copy(P.blk.data(), P.blk.size());
   int rc = pk.stage(st);
@@ -3414,7 +3432,18 @@ static int limb_jac_state(bool cols, const double *abs_c, const double *emi_c, i
   if (rc) return rc;
   const double *dcol = cols ? D.col + (size_t)los->n_gas * D.n_seg : nullptr;
   const int *blk = cols ? pk.dev(p_blk) : nullptr;
-  if (band_scratch)
+  if (several) {
+    LevelGasTabs lg{};
+    for (int k = 0; k < n_lgas; ++k) {
+      lg.tab[k] = lgas[k].tab;
+      lg.n_tab_rows[k] = lgas[k].n_tab_rows;
+      lg.gas[k] = lgas[k].gas;
+    }
+    LAUNCHCHK(launch_limb_jac_state_gases(abs_c, emi_c, n_row > 0 ? dabs : nullptr, n_row > 0 ? demi : nullptr, (int)n_pts, n_layers,
+                                          los->n_rays, D.seg_off, D.seg_layer, D.col, dcol, limb_opts(los, D.n_seg), lg,
+                                          pk.dev(p_row), P.n_blocks, blk, pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot),
+                                          n_col + n_lev + n_row, rad, jac, band_scratch, n_bands, st));
+  } else if (band_scratch)
     LAUNCHCHK(launch_limb_jac_state_bands(abs_c, emi_c, n_row > 0 ? dabs : nullptr, n_row > 0 ? demi : nullptr, (int)n_pts, n_layers,
                                           los->n_rays, D.seg_off, D.seg_layer, D.col, dcol, limb_opts(los, D.n_seg), gas, tab,
                                           n_tab_rows, pk.dev(p_row), P.n_blocks, blk, pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot),
@@ -3450,26 +3479,49 @@ int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_l
                         n_par, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream));
 }
 
-// The arguments of the mixed-state calls (sr_limb_rays_jac_state_dev, _state_rows_dev, sr_limb_rays_state_bands_dev),
-// all of them before the first copy or launch (as sr_limb_rays_jac_level_dev does).  out_ok: the caller's outputs are
-// there.  Any kind of parameter may be empty, not all; a kind that is empty needs none of its arrays.
+// The arguments of the mixed-state calls (sr_limb_rays_jac_state_dev, _state_rows_dev, sr_limb_rays_state_bands_dev and
+// their forms for several level gases), all of them before the first copy or launch (as sr_limb_rays_jac_level_dev does).
+// out_ok: the caller's outputs are there.  Any kind of parameter may be empty, not all; a kind that is empty needs none of
+// its arrays.  The level-factored gases come as a list: the one-gas entries hand in their one (one_level_gas), for which
+// the checks and their order are what they always were; par_lgas [n_lev] names a level parameter's level gas (null with
+// one: all 0).
+static sr_level_gas one_level_gas(int gas, const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row) {
+  sr_level_gas g;
+  g.gas = gas; g.n_levels = n_levels; g.n_tab_rows = n_tab_rows; g.tab = tab; g.coef_row = coef_row;
+  return g;
+}
 static int check_state_call(const char *entry, const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
-                            const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
-                            const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
-                            const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
-                            const double *par_t, bool out_ok, LosShape *shape) {
-  const bool lev_ok = n_lev == 0 || (tab && coef_row && par_level && par_c && n_levels > 0 && n_tab_rows > 0);
+                            const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
+                            const sr_level_gas *lgas, const int32_t *par_lgas, int n_lev, const int32_t *par_level,
+                            const double *par_c, const double *dabs_c, const double *demi_c, int n_row, const double *par_t,
+                            bool out_ok, LosShape *shape) {
+  const bool list_ok = lgas && n_lgas >= 1 && n_lgas <= kLevelGasMax;
+  bool lev_ok = n_lev == 0 || (list_ok && par_level && par_c && (n_lgas == 1 || par_lgas));
+  for (int k = 0; list_ok && n_lev > 0 && k < n_lgas; ++k)
+    lev_ok = lev_ok && lgas[k].tab && lgas[k].coef_row && lgas[k].n_levels > 0 && lgas[k].n_tab_rows > 0;
   const bool row_ok = n_row == 0 || (dabs_c && demi_c && par_t);
   const bool counts_ok = n_col >= 0 && n_lev >= 0 && n_row >= 0 && (int64_t)n_col + n_lev + n_row >= 1;
-  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, out_ok && counts_ok && lev_ok && row_ok);
+  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, out_ok && counts_ok && list_ok && lev_ok && row_ok);
   if (!rc) rc = check_los_par(los, n_layers, n_col, par_gas, par_w, shape);
   if (rc) return rc;
-  if (gas < 0 || gas >= los->n_gas) return SR_ERR_ARG;
+  if (n_lgas > los->n_gas) return SR_ERR_ARG;
+  for (int k = 0; k < n_lgas; ++k) {
+    if (lgas[k].gas < 0 || lgas[k].gas >= los->n_gas) return SR_ERR_ARG;
+    for (int i = 0; i < k; ++i)
+      if (lgas[i].gas == lgas[k].gas) return SR_ERR_ARG; // one gas of the batch, one set of tables
+  }
   if ((rc = refuse_init_mode_1(los, entry, SR_ERR_ARG))) return rc;
-  if (n_lev > 0 && !coef_rows_in_range(coef_row, n_layers, n_tab_rows)) return SR_ERR_ARG;
-  for (int p = 0; p < n_lev; ++p)
-    if (par_level[p] < 0 || par_level[p] >= n_levels) return SR_ERR_ARG;
+  for (int k = 0; n_lev > 0 && k < n_lgas; ++k)
+    if (!coef_rows_in_range(lgas[k].coef_row, n_layers, lgas[k].n_tab_rows)) return SR_ERR_ARG;
+  for (int p = 0; p < n_lev; ++p) {
+    const int k = par_lgas ? par_lgas[p] : 0;
+    if (k < 0 || k >= n_lgas) return SR_ERR_ARG;
+    if (par_level[p] < 0 || par_level[p] >= lgas[k].n_levels) return SR_ERR_ARG;
+  }
   if ((int64_t)n_col + n_lev + n_row > INT_MAX) return SR_ERR_LIMIT;
+  if (n_lgas > 1) // (an entry's word holds the level below kLevelEntGasShift)
+    for (int k = 0; n_lev > 0 && k < n_lgas; ++k)
+      if (lgas[k].n_levels > kLevelEntLevelMask + 1) return SR_ERR_LIMIT;
   return SR_OK;
 }
 
@@ -3478,9 +3530,9 @@ int sr_limb_rays_jac_state_dev(const double *abs_c, const double *emi_c, int n_l
                                const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
                                const int32_t *par_level, const double *par_c, double *rad, double *jac, void *stream) {
   LosShape shape;
-  const int rc = check_state_call("sr_limb_rays_jac_state_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, gas, tab,
-                                  n_levels, n_tab_rows, coef_row, n_lev, par_level, par_c, nullptr, nullptr, 0, nullptr, jac != nullptr,
-                                  &shape);
+  const sr_level_gas one = one_level_gas(gas, tab, n_levels, n_tab_rows, coef_row);
+  const int rc = check_state_call("sr_limb_rays_jac_state_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, 1, &one,
+                                  nullptr, n_lev, par_level, par_c, nullptr, nullptr, 0, nullptr, jac != nullptr, &shape);
   if (rc) return rc;
   return limb_jac_state(true, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, gas, tab, n_tab_rows, coef_row,
                         n_lev, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream));
@@ -3495,9 +3547,9 @@ int sr_limb_rays_jac_state_rows_dev(const double *abs_c, const double *emi_c, in
     return sr_limb_rays_jac_state_dev(abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, gas, tab, n_levels, n_tab_rows,
                                       coef_row, n_lev, par_level, par_c, rad, jac, stream);
   LosShape shape;
-  const int rc = check_state_call("sr_limb_rays_jac_state_rows_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, gas,
-                                  tab, n_levels, n_tab_rows, coef_row, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t,
-                                  jac != nullptr, &shape);
+  const sr_level_gas one = one_level_gas(gas, tab, n_levels, n_tab_rows, coef_row);
+  const int rc = check_state_call("sr_limb_rays_jac_state_rows_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, 1,
+                                  &one, nullptr, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, jac != nullptr, &shape);
   if (rc) return rc;
   // (without column parameters the instances without column code: fewer registers, the same arithmetic)
   return limb_jac_state(n_col > 0, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, gas, tab, n_tab_rows,
@@ -3507,17 +3559,17 @@ int sr_limb_rays_jac_state_rows_dev(const double *abs_c, const double *emi_c, in
 
 // The mixed-state Jacobian on the instrument's bands: the state call's plan and checks, the instrument step's cached
 // weight table (lowres_prepare, fused), the recursion kernel's band epilogue, the partial sums added straight into the
-// pinned landing buffer, the field of view on the host.
-int sr_limb_rays_state_bands_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
-                                 const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
-                                 const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
-                                 const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c,
-                                 int n_row, const double *par_t, const double *centers_nm, const double *widths_nm,
-                                 int n_bands, double n_sigma, int out_units, const double *fov, double *out, void *stream) {
+// pinned landing buffer, the field of view on the host.  One body for one level gas (n_lgas == 1: gas, tab, ... of
+// lgas[0], the one-gas instances) and for several.
+static int limb_state_bands(const char *entry, const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                            const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
+                            const sr_level_gas *lgas, const int32_t *par_lgas, int n_lev, const int32_t *par_level,
+                            const double *par_c, const double *dabs_c, const double *demi_c, int n_row, const double *par_t,
+                            const double *centers_nm, const double *widths_nm, int n_bands, double n_sigma, int out_units,
+                            const double *fov, double *out, void *stream) {
   LosShape shape;
-  int rc = check_state_call("sr_limb_rays_state_bands_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, gas, tab,
-                            n_levels, n_tab_rows, coef_row, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t,
-                            out && centers_nm && widths_nm && n_bands > 0, &shape);
+  int rc = check_state_call(entry, abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, n_lgas, lgas, par_lgas, n_lev,
+                            par_level, par_c, dabs_c, demi_c, n_row, par_t, out && centers_nm && widths_nm && n_bands > 0, &shape);
   if (rc) return rc;
   const int n_rays = los->n_rays, n_par = n_col + n_lev + n_row;
   if (fov && n_rays % 3 != 0) return SR_ERR_ARG;
@@ -3531,8 +3583,9 @@ int sr_limb_rays_state_bands_dev(const double *abs_c, const double *emi_c, int n
   rc = lowres_prepare(n_spec, n_pts, los->g_lo, los->w0, los->step, centers_nm, widths_nm, n_bands, n_sigma, out_units,
                       /*fused=*/true, st, &fresh);
   if (rc) return rc;
-  rc = limb_jac_state(n_col > 0, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, gas, tab, n_tab_rows, coef_row,
-                      n_lev, par_level, par_c, nullptr, nullptr, st, dabs_c, demi_c, n_row, par_t, t_lowres.d_weights.p, n_bands);
+  rc = limb_jac_state(n_col > 0, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, lgas[0].gas, lgas[0].tab,
+                      lgas[0].n_tab_rows, lgas[0].coef_row, n_lev, par_level, par_c, nullptr, nullptr, st, dabs_c, demi_c, n_row,
+                      par_t, t_lowres.d_weights.p, n_bands, n_lgas, lgas, par_lgas);
   if (rc) return rc;
   const size_t low_bytes = sizeof(double) * (size_t)n_spec * n_bands;
   rc = t_lowres.s_land.prepare(low_bytes);
@@ -3542,6 +3595,64 @@ int sr_limb_rays_state_bands_dev(const double *abs_c, const double *emi_c, int n
   HIPCHK(hipStreamSynchronize(st));
   fov_rows(static_cast<const double *>(t_lowres.s_land.h), n_rays, n_par, n_bands, fov, out);
   return SR_OK;
+}
+
+int sr_limb_rays_state_bands_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                 const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
+                                 const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
+                                 const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c,
+                                 int n_row, const double *par_t, const double *centers_nm, const double *widths_nm,
+                                 int n_bands, double n_sigma, int out_units, const double *fov, double *out, void *stream) {
+  const sr_level_gas one = one_level_gas(gas, tab, n_levels, n_tab_rows, coef_row);
+  return limb_state_bands("sr_limb_rays_state_bands_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, 1, &one, nullptr,
+                          n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm, n_bands, n_sigma, out_units,
+                          fov, out, stream);
+}
+
+// Several level-factored gases.  One level gas is the existing entry, checks and all (a par_lgas that names another one
+// is refused first: the existing entries have no such argument).
+static bool one_level_gas_call(int n_lgas, const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas, int *rc) {
+  if (n_lgas != 1 || !lgas) return false;
+  *rc = SR_OK;
+  for (int p = 0; par_lgas && p < n_lev; ++p)
+    if (par_lgas[p] != 0) *rc = SR_ERR_ARG;
+  return true;
+}
+
+int sr_limb_rays_jac_state_gases_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                     const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
+                                     const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas, const int32_t *par_level,
+                                     const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
+                                     const double *par_t, double *rad, double *jac, void *stream) {
+  int rc;
+  if (one_level_gas_call(n_lgas, lgas, n_lev, par_lgas, &rc))
+    return rc ? rc : sr_limb_rays_jac_state_rows_dev(abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, lgas[0].gas, lgas[0].tab,
+                                                     lgas[0].n_levels, lgas[0].n_tab_rows, lgas[0].coef_row, n_lev, par_level, par_c,
+                                                     dabs_c, demi_c, n_row, par_t, rad, jac, stream);
+  LosShape shape;
+  rc = check_state_call("sr_limb_rays_jac_state_gases_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, n_lgas, lgas,
+                        par_lgas, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, jac != nullptr, &shape);
+  if (rc) return rc;
+  return limb_jac_state(n_col > 0, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, lgas[0].gas, lgas[0].tab,
+                        lgas[0].n_tab_rows, lgas[0].coef_row, n_lev, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream),
+                        dabs_c, demi_c, n_row, par_t, nullptr, 0, n_lgas, lgas, par_lgas);
+}
+
+int sr_limb_rays_state_bands_gases_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                       const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
+                                       const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas, const int32_t *par_level,
+                                       const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
+                                       const double *par_t, const double *centers_nm, const double *widths_nm, int n_bands,
+                                       double n_sigma, int out_units, const double *fov, double *out, void *stream) {
+  int rc;
+  if (one_level_gas_call(n_lgas, lgas, n_lev, par_lgas, &rc))
+    return rc ? rc : sr_limb_rays_state_bands_dev(abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, lgas[0].gas, lgas[0].tab,
+                                                  lgas[0].n_levels, lgas[0].n_tab_rows, lgas[0].coef_row, n_lev, par_level, par_c,
+                                                  dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm, n_bands, n_sigma, out_units,
+                                                  fov, out, stream);
+  return limb_state_bands("sr_limb_rays_state_bands_gases_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, n_lgas,
+                          lgas, par_lgas, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm, n_bands,
+                          n_sigma, out_units, fov, out, stream);
 }
 
 int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,

@@ -3263,6 +3263,17 @@ constexpr int kBandRow = 68; // doubles per row of a wave's tile of values (64 +
 __device__ inline const double *limb_state_init_src(const double *jac) { return jac; }
 __device__ inline const double *limb_state_init_src(const FoldBands &) { return nullptr; }
 
+// the state kernel's trailing parameter pack: dabs and demi (ROWS), then the LevelGasTabs of a call with several level gases
+template <class... T>
+inline constexpr bool kStateSeveralGases = (std::is_same_v<T, LevelGasTabs> || ...);
+template <class... R>
+__device__ __forceinline__ const double *state_row_spectrum(int which, const double *dabs, const double *demi, const R &...) {
+  return which == 0 ? dabs : demi;
+}
+__device__ __forceinline__ const LevelGasTabs &state_level_gases(const LevelGasTabs &g) { return g; }
+template <class T, class... R>
+__device__ __forceinline__ const LevelGasTabs &state_level_gases(const T &, const R &...r) { return state_level_gases(r...); }
+
 // Derivatives w.r.t. LEVEL parameters of one level-factored gas (sr_limb_rays_jac_level_dev, COLS = false) or w.r.t. a
 // MIXED state vector of column and level parameters in one pass (sr_limb_rays_jac_state_dev, COLS = true).  The gas's
 // coefficients are abs[r] = sum_L pop[r][L] A_L[row[r]], emi[r] likewise with E_L (the pair tables of
@@ -3312,6 +3323,17 @@ __device__ inline const double *limb_state_init_src(const FoldBands &) { return 
 // range).  An accumulator no segment of the ray touches is an exact 0 and so is every one of its sums.  `jac` is the
 // FoldBands of the call in these instances and rad is not used; the BANDS = false instances keep their argument block,
 // their early exit and their stores: the same machine code as before the parameter existed.
+// SEVERAL level-factored gases (sr_limb_rays_jac_state_gases_dev, sr_limb_rays_state_bands_gases_dev): the parameter pack
+// ends in a LevelGasTabs -- the tables, their row counts and the batch gases of up to four level gases, by value in the
+// argument block -- and an entry's `level` is level | level gas << kLevelEntGasShift (the host sorts the level slots by
+// level gas, then level, so "two loads and one d per distinct level" holds as it stands: the comparison of the packed
+// words is the comparison of (level gas, level)).  A level slot of level gas k then reads
+//   dtau = c u_{gas[k]} A^k_L[row_k[r]],  dE = c u_{gas[k]} E^k_L[row_k[r]],  row_k = coef_row + k n_layers,
+// the table pointer, the row count and the gas index by scalar loads from the argument block where the level changes, the
+// column u by a scalar load that hits the scalar cache (as the ROWS branch reads its columns: nothing of this is kept
+// in scalar registers over the exponential; the COLS instances sit at the scalar-register limit).  The recursion term,
+// the row slots, the kLevelEntRows sentinel and the band epilogue are untouched; gas, tab and n_tab_rows are not read.
+// The instances without a LevelGasTabs keep their argument block and their machine code.
 template <int NG, int NP, bool COLS, bool ROWS, bool BANDS, class... RowSpectra>
 __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
@@ -3321,7 +3343,8 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     const LevelEnt *__restrict__ ent, const int *__restrict__ slot_par, int n_par, double *__restrict__ rad,
     std::conditional_t<BANDS, FoldBands, double *__restrict__> jac, RowSpectra... row_spectra) {
   static_assert(NP <= 16 && NG <= 4, "blk packs the gases of 16 column slots, two bits each");
-  static_assert(sizeof...(RowSpectra) == (ROWS ? 2 : 0), "dabs and demi with ROWS, nothing without");
+  constexpr bool GASES = kStateSeveralGases<RowSpectra...>;
+  static_assert(sizeof...(RowSpectra) == (ROWS ? 2 : 0) + (GASES ? 1 : 0), "dabs and demi with ROWS, then the level gases' tables, if several");
   int pb, ray;
   if (!limb_block((n_pts + 255) / 256, n_rays, pb, ray)) return;
   const int jt = pb * 256 + threadIdx.x;
@@ -3394,7 +3417,8 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
       }
     }
     if (e0 < e1) { // the level slots
-      const double *tr = tab + (size_t)coef_row[r] * n_pts + j;
+      [[maybe_unused]] const double *tr = nullptr;
+      if constexpr (!GASES) tr = tab + (size_t)coef_row[r] * n_pts + j;
       int lev = -1;
       double d = 0.0;
       for (int i = e0; i < e1; ++i) {
@@ -3405,7 +3429,7 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
           if constexpr (ROWS) rows = lv == kLevelEntRows;
           if (rows) { // the row slots: one d for all of them (sr_limb_jac_layer_kernel's sums)
             if constexpr (ROWS) {
-              const double *const rs[] = {row_spectra...};
+              const double *const rs[] = {state_row_spectrum(0, row_spectra...), state_row_spectrum(1, row_spectra...)};
               const size_t ofs = (size_t)r * n_pts + j;
               double dtau = 0.0, dE = 0.0;
 #pragma unroll
@@ -3416,6 +3440,14 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
               }
               d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
             }
+          } else if constexpr (GASES) { // a level of level gas k: its table, its row map, its gas's column
+            const LevelGasTabs &lg = state_level_gases(row_spectra...);
+            const int k = lv >> kLevelEntGasShift, L = lv & kLevelEntLevelMask;
+            const size_t pl = (size_t)lg.n_tab_rows[k] * n_pts;
+            const double *tl = lg.tab[k] + (size_t)coef_row[(size_t)k * n_layers + r] * n_pts + j + (size_t)L * 2 * pl;
+            const double u = col[(size_t)lg.gas[k] * o.n_seg_total + s];
+            const double dtau = u * tl[0], dE = u * tl[pl];
+            d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
           } else {
             const double *tl = tr + (size_t)lv * 2 * plane;
             const double dtau = ug * tl[0], dE = ug * tl[plane];
@@ -4822,6 +4854,53 @@ int launch_limb_jac_state_bands(const double *abs_c, const double *emi_c, const 
           hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, false, true>),
                              grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas,
                              tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, no_rad, bd);
+      });
+    });
+  };
+  if (blk) launch(std::true_type{});
+  else launch(std::false_type{});
+  return (int)hipGetLastError();
+}
+
+int launch_limb_jac_state_gases(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
+                                int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
+                                const double *dcol, const LimbOpts &o, const LevelGasTabs &lg, const int *coef_row, int n_blocks,
+                                const int *blk, const int *ent_off, const LevelEnt *ent, const int *slot_par, int n_par,
+                                double *rad, double *jac, const void *lowres_scratch, int n_bands, hipStream_t st) {
+  if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0 || o.n_gas < 2 || o.n_gas > 4) return 0;
+  if (lowres_scratch && n_bands <= 0) return 0;
+  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
+  const bool rows = dabs && demi;
+  const double *const no_tab = nullptr;
+  double *const no_rad = nullptr;
+  constexpr int no_gas = -1; // (gas, tab and n_tab_rows belong to the one-gas instances)
+  auto launch = [&](auto cols) { // no blk: the instances without column slots
+    by_level_np(level_jac_np(n_par), [&](auto np) {
+      by_ngas(o.n_gas, [&](auto ng) {
+        constexpr int NG = decltype(ng)::value, NP = decltype(np)::value;
+        constexpr bool COLS = decltype(cols)::value;
+        if constexpr (NG >= 2) { // (several level gases are several gases of the batch)
+          if (lowres_scratch) {
+            const LowresScratch L = lowres_layout(const_cast<void *>(lowres_scratch), n_pts, n_bands);
+            const FoldBands bd{L.Wt, L.range, L.part, n_bands};
+            if (rows)
+              hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, true, true, const double *, const double *, LevelGasTabs>), grid,
+                                 dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas,
+                                 no_tab, 0, coef_row, blk, ent_off, ent, slot_par, n_par, no_rad, bd, dabs, demi, lg);
+            else
+              hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, false, true, LevelGasTabs>), grid, dim3(256), 0, st, abs_c,
+                                 emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas, no_tab, 0, coef_row, blk,
+                                 ent_off, ent, slot_par, n_par, no_rad, bd, lg);
+          } else if (rows) {
+            hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, true, false, const double *, const double *, LevelGasTabs>), grid,
+                               dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas,
+                               no_tab, 0, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac, dabs, demi, lg);
+          } else {
+            hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, false, false, LevelGasTabs>), grid, dim3(256), 0, st, abs_c,
+                               emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas, no_tab, 0, coef_row, blk,
+                               ent_off, ent, slot_par, n_par, rad, jac, lg);
+          }
+        }
       });
     });
   };

@@ -252,6 +252,15 @@ struct __attribute__((aligned(16))) LevelEnt {
 };
 // the `level` of an entry that belongs to a row slot (launch_limb_jac_state_rows): its c is the slot's weight on the row
 constexpr int kLevelEntRows = -2;
+// several level-factored gases (launch_limb_jac_state_gases below): an entry's `level` is level | level gas << kLevelEntGasShift,
+// and the kernel's last argument holds, per level gas, the tables, their row count and the gas's index in the batch
+constexpr int kLevelEntGasShift = 16, kLevelEntLevelMask = (1 << kLevelEntGasShift) - 1;
+constexpr int kLevelGasMax = 4;
+struct LevelGasTabs {
+  const double *tab[kLevelGasMax];
+  int n_tab_rows[kLevelGasMax];
+  int gas[kLevelGasMax];
+};
 constexpr int kLevelJacNPSmall = 8, kLevelJacNPLarge = 16;
 inline int level_jac_np(int n_par) { return n_par > kLevelJacNPSmall ? kLevelJacNPLarge : kLevelJacNPSmall; }
 int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
@@ -278,6 +287,16 @@ int launch_limb_jac_state_bands(const double *abs_c, const double *emi_c, const 
                                 const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
                                 const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
                                 const int *slot_par, int n_par, const void *lowres_scratch, int n_bands, hipStream_t st);
+// The same three for the level parameters of SEVERAL level-factored gases (the kernel's instances whose parameter pack
+// ends in a LevelGasTabs; batches of two to four gases): level gas k has the tables tab[k] with n_tab_rows[k] rows, is
+// gas gas[k] of the batch, and coef_row [n_lgas][n_layers] holds its row map at k n_layers.  The level slots are sorted
+// by (level gas, level) and an entry's `level` is level | level gas << kLevelEntGasShift.  dabs / demi null: no row
+// parameters; lowres_scratch null: spectra to rad / jac, else the band epilogue as launch_limb_jac_state_bands.
+int launch_limb_jac_state_gases(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
+                                int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
+                                const double *dcol, const LimbOpts &o, const LevelGasTabs &lg, const int *coef_row, int n_blocks,
+                                const int *blk, const int *ent_off, const LevelEnt *ent, const int *slot_par, int n_par,
+                                double *rad, double *jac, const void *lowres_scratch, int n_bands, hipStream_t st);
 // Radiance budget (sr_limb_parts_kernel): the n_part parts and the background are n_part + 1 slots in blocks of
 // limb_parts_np(n_part); slot_level [n_blocks][NP]: >= 0 the first row of a level's E plane in the pair tables,
 // (2 L + 1) n_tab_rows, -1 - g the gas part of gas g,

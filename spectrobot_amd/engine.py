@@ -603,6 +603,66 @@ class LevelFactored(object):
         return rad, parts, labels
 
 
+class LevelFactoredSet(object):
+    """Several LevelFactored of one batch -- two non-LTE emitters in one window -- for the mixed-state calls that take the
+    vibrational-temperature parameters of all of them in ONE pass over each ray (limb_rays_state_jacobian /
+    limb_rays_state_bands with level_gases).  members: [(lf, gas, step_row, tvib), ...] or with a fifth item q_part: a
+    LevelFactored, its gas's index in the batch, the table row of every coefficient row and the vibrational temperatures
+    [n_levels, n_steps] its coefficients in `coeffs` were combined with.  Level parameter p belongs to member par_lgas[p]
+    and to its level par_level[p]; par_c is formed per member exactly as LevelFactored.state_jacobian forms it
+    (_state_level_args: the populations' Tvib derivative times the node weights).  All members share the spectral shard."""
+
+    def __init__(self, members):
+        self.members = [tuple(m) + (None,) * (5 - len(m)) for m in members]
+        if not self.members:
+            raise ValueError("LevelFactoredSet needs at least one (lf, gas, step_row, tvib)")
+        if len({m[0]._shard for m in self.members}) != 1:
+            raise ValueError("the LevelFactored of a set must share their spectral shard")
+        if len({int(m[1]) for m in self.members}) != len(self.members):
+            raise ValueError("a gas is named twice")
+
+    def _args(self, par_lgas, par_level, par_w_level):
+        par_lgas = np.ascontiguousarray(par_lgas, dtype=np.int32).reshape(-1)
+        par_level = np.ascontiguousarray(par_level, dtype=np.int32).reshape(-1)
+        if par_lgas.size != par_level.size:
+            raise ValueError("par_lgas must be [n_lev], one member per level parameter")
+        if par_lgas.size and (par_lgas.min() < 0 or par_lgas.max() >= len(self.members)):
+            raise ValueError("par_lgas out of range")
+        n_steps = np.asarray(self.members[0][2]).size
+        par_w = np.zeros((0, n_steps)) if par_level.size == 0 else np.asarray(par_w_level, dtype=np.float64)
+        if par_w.shape != (par_level.size, n_steps):
+            raise ValueError("par_w_level must be [n_lev, n_steps]")
+        par_c, gases = np.zeros((par_level.size, n_steps)), []
+        for k, (lf, gas, step_row, tvib, q_part) in enumerate(self.members):
+            idx = np.nonzero(par_lgas == k)[0]
+            if np.asarray(step_row).size != n_steps:
+                raise ValueError("the members' step_row must have one length, the coefficient rows of the batch")
+            step_row, _, pc = lf._state_level_args(step_row, tvib, par_level[idx], par_w[idx], q_part)
+            if idx.size:
+                par_c[idx] = pc
+            gases.append((int(gas), lf.tab, step_row))
+        return gases, par_lgas, par_level, par_c
+
+    def state_jacobian(self, coeffs, los, par_lgas, par_level, par_w_level, par_gas=None, par_w_col=None, grid=None,
+                       want_rad=True, dcoeffs=None, par_w_temp=None):
+        """LevelFactored.state_jacobian for the members' vibrational-temperature parameters together: (rad | None, jac
+        [n_rays, n_col + n_lev (+ n_row), n_pts]), the rows in the caller's order."""
+        gases, par_lgas, par_level, par_c = self._args(par_lgas, par_level, par_w_level)
+        return limb_rays_state_jacobian(coeffs, los, par_gas=par_gas, par_w=par_w_col, par_level=par_level, par_c=par_c,
+                                        grid=grid, g_lo=int(self.members[0][0]._shard[0]), want_rad=want_rad, dcoeffs=dcoeffs,
+                                        par_t=par_w_temp, level_gases=gases, par_lgas=par_lgas)
+
+    def state_bands(self, coeffs, los, par_lgas, par_level, par_w_level, grid, centers_nm, widths_nm, par_gas=None,
+                    par_w_col=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None):
+        """LevelFactored.state_bands for the members' vibrational-temperature parameters together: numpy [n_rays | n_rays / 3,
+        1 + n_par, n_bands]."""
+        gases, par_lgas, par_level, par_c = self._args(par_lgas, par_level, par_w_level)
+        return limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=par_gas, par_w=par_w_col,
+                                     par_level=par_level, par_c=par_c, dcoeffs=dcoeffs, par_t=par_w_temp, out_units=out_units,
+                                     n_sigma=n_sigma, fov=fov, g_lo=int(self.members[0][0]._shard[0]), level_gases=gases,
+                                     par_lgas=par_lgas)
+
+
 def level_node_weights(nodes, alt):
     """par_w [n_nodes, n_rows] of one level's vibrational-temperature profile on the coefficient rows: the triangular
     masks of LinearProfile_1D_new (spect_main_module.alt_triangle: 1 at the node, linear to 0 at its neighbours, the
@@ -1140,7 +1200,7 @@ def limb_rays_level_jacobian(coeffs, los, tab, coef_row, par_level, par_c, gas=0
 
 
 def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, coef_row=None, par_level=None, par_c=None,
-                             gas=0, grid=None, g_lo=0, want_rad=True, dcoeffs=None, par_t=None):
+                             gas=0, grid=None, g_lo=0, want_rad=True, dcoeffs=None, par_t=None, level_gases=None, par_lgas=None):
     """(rad | None, jac [n_rays, n_col + n_lev (+ n_row), n_pts]): radiances and their derivatives with respect to a
     mixed state vector in ONE pass over each ray (sr_limb_rays_jac_state_dev): the column parameters par_gas / par_w of
     limb_rays_jacobian (VMR-profile parameters, par_w [n_col, n_pt] at the LOS sample points) first, then the level
@@ -1153,12 +1213,21 @@ def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, co
     row parameter p moves that scalar on row r by par_t[p, r] (par_t [n_row, n_layers], node masks).  It is
     limb_rays_layer_jacobian contracted with par_t inside the recursion.  The columns are held fixed, as in
     temperature_jacobian; the density part of a temperature change is a set of column parameters, which the caller adds
-    to par_gas / par_w if it is wanted.  With row parameters the other two kinds may both be left out."""
-    A = _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t)
+    to par_gas / par_w if it is wanted.  With row parameters the other two kinds may both be left out.
+    level_gases and par_lgas (both or neither; then without tab / coef_row / gas): the level parameters of SEVERAL
+    level-factored gases in the same pass (sr_limb_rays_jac_state_gases_dev): level_gases = [(gas, tab, coef_row), ...],
+    one entry per level-factored gas of the batch (its index there, its pair tables, its row map; tables may differ in
+    levels and rows), and level parameter p belongs to level_gases[par_lgas[p]], to its level par_level[p].  The rows of
+    jac keep the caller's order.  Vibrational temperatures: LevelFactoredSet.state_jacobian."""
+    A = _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t, level_gases,
+                    par_lgas)
     n_pts = A.a.shape[2]
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
     jac = torch.empty((los.n_rays, A.n_par, n_pts), dtype=torch.float64, device="cuda")
+    if level_gases is not None:
+        check(lib.sr_limb_rays_jac_state_gases_dev(*A.head_gases, ptr(rad), ptr(jac), _stream_ptr()), "sr_limb_rays_jac_state_gases_dev")
+        return rad, jac
     if par_t is not None:
         check(lib.sr_limb_rays_jac_state_rows_dev(*A.head, ptr(rad), ptr(jac), _stream_ptr()), "sr_limb_rays_jac_state_rows_dev")
         return rad, jac
@@ -1169,10 +1238,57 @@ def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, co
 class _StateArgs(object):
     """What _state_args returns: a, e (the stacked coefficients), desc, n_col, n_lev, n_row, n_par, head -- the arguments of
     sr_limb_rays_jac_state_rows_dev up to par_t, in its order (the first 16 are those of sr_limb_rays_jac_state_dev up to
-    par_c) -- and keep, the arrays and tensors the pointers in head point into."""
+    par_c) -- and keep, the arrays and tensors the pointers in head point into.  With several level gases head_gases
+    instead: the arguments of sr_limb_rays_jac_state_gases_dev up to par_t."""
 
 
-def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t):
+def _level_gases_args(level_gases, par_lgas, tab, coef_row, par_level, par_c, n_gas, n_layers, n_pts):
+    """The list of level gases of a mixed-state call, checked and marshalled: (LevelGasDesc array, n_lgas, n_lev, pointers to
+    par_lgas, par_level, par_c, what they point into)."""
+    if par_lgas is None:
+        raise ValueError("level_gases needs par_lgas, the level gas of every level parameter")
+    if tab is not None or coef_row is not None:
+        raise ValueError("level_gases carries the tables and row maps: give no tab / coef_row beside it")
+    level_gases = list(level_gases)
+    if not 1 <= len(level_gases) <= n_gas:
+        raise ValueError("%d level gases for a batch of %d gases" % (len(level_gases), n_gas))
+    arr, keep, seen = (_lib.LevelGasDesc * len(level_gases))(), [], set()
+    for k, (g, t, cr) in enumerate(level_gases):
+        g = int(g)
+        if not 0 <= g < n_gas or g in seen:
+            raise ValueError("level gas %d: gas %d is out of range or named twice" % (k, g))
+        seen.add(g)
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 4 and t.shape[1] == 2):
+            raise ValueError("level gas %d: its tables must be a contiguous CUDA float64 [n_levels, 2, n_tab_rows, n_pts]" % k)
+        if t.shape[3] != n_pts:
+            raise ValueError("tables of %d points for coefficients of %d" % (t.shape[3], n_pts))
+        cr, crp = _i(cr)
+        if cr.shape != (n_layers,):
+            raise ValueError("coef_row must be [n_layers]")
+        arr[k].gas, arr[k].n_levels, arr[k].n_tab_rows = g, int(t.shape[0]), int(t.shape[2])
+        arr[k].tab, arr[k].coef_row = t.data_ptr(), crp
+        keep.append((t, cr))
+    par_level, pl = _i(np.asarray([] if par_level is None else par_level).reshape(-1))
+    par_lgas, plg = _i(np.asarray(par_lgas).reshape(-1))
+    if par_lgas.size != par_level.size:
+        raise ValueError("par_lgas must be [n_lev], one level gas per level parameter")
+    if par_lgas.size and (par_lgas.min() < 0 or par_lgas.max() >= len(level_gases)):
+        raise ValueError("par_lgas out of range")
+    pc = None
+    if par_level.size:
+        if par_c is None:
+            raise ValueError("level parameters need par_c")
+        par_c, pc = _d(par_c)
+        if par_c.shape != (par_level.size, n_layers):
+            raise ValueError("par_c must be [n_lev, n_layers]")
+        n_lv = np.array([a.n_levels for a in arr])[par_lgas]
+        if par_level.min() < 0 or np.any(par_level >= n_lv):
+            raise ValueError("par_level out of range for its level gas")
+    return arr, len(level_gases), par_level.size, plg, pl, pc, (keep, par_lgas, par_level, par_c)
+
+
+def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t, level_gases=None,
+                par_lgas=None):
     """The arguments of a mixed-state call (limb_rays_state_jacobian, limb_rays_state_bands), checked and marshalled: the
     one place where their shapes are refused."""
     if (dcoeffs is None) != (par_t is None):
@@ -1189,7 +1305,13 @@ def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, ga
         n_col = par_gas.size
         if par_w.shape != (n_col, los.n_pt):
             raise ValueError("par_w must be [n_col, n_pt]")
-    if par_level is not None and np.asarray(par_level).size:
+    several = None
+    if level_gases is not None:
+        several = _level_gases_args(level_gases, par_lgas, tab, coef_row, par_level, par_c, n_gas, n_layers, n_pts)
+        n_lev = several[2]
+    elif par_lgas is not None:
+        raise ValueError("par_lgas belongs to level_gases")
+    elif par_level is not None and np.asarray(par_level).size:
         if tab is None or coef_row is None or par_c is None:
             raise ValueError("level parameters need tab, coef_row and par_c")
         n_levels, n_tab_rows, cr, n_lev, pl, pc = _level_table_args(tab, coef_row, par_level, par_c, n_layers, n_pts, "n_lev")
@@ -1212,20 +1334,29 @@ def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, ga
     A.keep = (par_gas, par_w, tab, cr, pl, pc, da, de, par_t)
     A.head = (ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw, int(gas), ptr(tab) if n_lev else None, n_levels,
               n_tab_rows, cr, n_lev, pl, pc, ptr(da), ptr(de), n_row, pt)
+    if several is not None:
+        arr, n_lgas, _, plg, pl, pc, keep = several
+        A.keep = A.keep + (arr, keep)
+        A.head = None
+        A.head_gases = (ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw, n_lgas, arr, n_lev, plg, pl, pc, ptr(da),
+                        ptr(de), n_row, pt)
     return A
 
 
 def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None, par_w=None, tab=None, coef_row=None,
                           par_level=None, par_c=None, gas=0, dcoeffs=None, par_t=None, out_units="Wm2", n_sigma=5.0, fov=None,
-                          g_lo=0):
+                          g_lo=0, level_gases=None, par_lgas=None):
     """limb_rays_state_jacobian on the instrument's bands in ONE library call (sr_limb_rays_state_bands_dev): the same
     mixed state vector (column, level, row parameters: the same arguments, the same errors), but no hi-res spectrum is
     written -- the recursion kernel integrates the bands in its epilogue.  Returns numpy [n_rays | n_rays / 3, 1 + n_par,
     n_bands] in out_units: row 0 the radiance, row 1 + p its derivative to parameter p (column, level, row parameters, each
     kind in the caller's order).  What limb_rays_state_jacobian + hires_to_lowres on rad and jac (+ fov_closed_form) give,
     up to the order of the band sums.  fov: fov_factors of the pixels, three rays each.  A spectral shard (g_lo, the
-    coefficient tables' width; `grid` is always the whole grid) gives its partial band integrals, as hires_to_lowres."""
-    A = _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t)
+    coefficient tables' width; `grid` is always the whole grid) gives its partial band integrals, as hires_to_lowres.
+    level_gases / par_lgas: several level-factored gases, as in limb_rays_state_jacobian
+    (sr_limb_rays_state_bands_gases_dev)."""
+    A = _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t, level_gases,
+                    par_lgas)
     n_pts = A.a.shape[2]
     w0, step, n = grid_params(grid)
     A.desc.w0, A.desc.step = w0, step   # (the grid of the bands; with a Planck background desc() has set the same)
@@ -1242,6 +1373,10 @@ def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None
             raise ValueError("fov must be [n_rays / 3, 7] (three rays per pixel)")
         n_out = los.n_rays // 3
     out = np.empty((n_out, 1 + A.n_par, centers_nm.size))
+    if level_gases is not None:
+        check(lib.sr_limb_rays_state_bands_gases_dev(*A.head_gases, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp,
+                                                     out.ctypes.data_as(dp), _stream_ptr()), "sr_limb_rays_state_bands_gases_dev")
+        return out
     check(lib.sr_limb_rays_state_bands_dev(*A.head, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp,
                                            out.ctypes.data_as(dp), _stream_ptr()), "sr_limb_rays_state_bands_dev")
     return out

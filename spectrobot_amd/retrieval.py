@@ -141,12 +141,19 @@ class StateWeights(object):
     """LimbScene.state_weights' result: the column block (par_gas [n_col], par_w_col [n_col, n_pt]), the level block
     (level_gas: the LevelGas or None, gas: its index, par_level [n_lev], par_w_lev [n_lev, n_layers]), the row block
     (par_w_temp [n_row, n_layers]: the temperature nodes' masks; None: no such parameter) and perm [n_par]: the row of the
-    call's Jacobian (column parameters, then level parameters, then row parameters) that belongs to BayesSet parameter i."""
+    call's Jacobian (column parameters, then level parameters, then row parameters) that belongs to BayesSet parameter i.
+    level_gases: every LevelGas with a Tvib set, in the order the BayesSet first names them (state_weights with
+    several_level_gases: any number; otherwise [level_gas] or []), gases: their indices in the scene, par_lgas [n_lev]: the
+    entry of level_gases a level parameter belongs to."""
 
-    def __init__(self, par_gas, par_w_col, level_gas, gas, par_level, par_w_lev, perm, par_w_temp=None):
+    def __init__(self, par_gas, par_w_col, level_gas, gas, par_level, par_w_lev, perm, par_w_temp=None, level_gases=None,
+                 gases=None, par_lgas=None):
         self.par_gas, self.par_w_col, self.level_gas, self.gas = par_gas, par_w_col, level_gas, gas
         self.par_level, self.par_w_lev, self.perm = par_level, par_w_lev, perm
         self.par_w_temp = np.zeros((0, np.shape(par_w_lev)[1])) if par_w_temp is None else par_w_temp
+        self.level_gases = ([] if level_gas is None else [level_gas]) if level_gases is None else list(level_gases)
+        self.gases = ([] if level_gas is None else [gas]) if gases is None else list(gases)
+        self.par_lgas = np.zeros(len(par_level), np.int32) if par_lgas is None else par_lgas
 
 
 class LimbPixel(object):
@@ -254,17 +261,20 @@ class LimbScene(object):
         self._weights_cache = (key, out[0], out[1])
         return out
 
-    def state_weights(self, bayes_set, alt):
+    def state_weights(self, bayes_set, alt, several_level_gases=False):
         """The parameters of a mixed state vector, split in BayesSet order into the column block -- sets named after a gas:
         VMR-profile parameters, their masks at the LOS sample altitudes `alt` as in profile_weights -- and the level block
         -- sets named "tvib:<gas>:<level>" (TvibProfile) of ONE LevelGas: their masks on the coefficient rows, the scene's
         altitude levels -- and the row block -- the set named "temp" (TempProfile): its masks on the coefficient rows
-        likewise.  Returns a StateWeights (its perm leads back to BayesSet order)."""
+        likewise.  Returns a StateWeights (its perm leads back to BayesSet order).
+        several_level_gases=True: Tvib sets of any number of LevelGas (the calls with level_gases take them in one pass);
+        the level block then holds them all in BayesSet order, StateWeights.level_gases / gases / par_lgas say whose each
+        is, level_gas / gas are the first one's.  With one LevelGas the result is the same either way."""
         names = [g.name for g in self.gases]
         top = self.z[-1] + (self.z[-1] - self.z[-2])
         zz = np.append(self.z, top)
         par_gas, par_w_col, par_level, par_w_lev, par_w_temp, kind = [], [], [], [], [], []
-        level_gas = None
+        level_gas, level_gases, par_lgas = None, [], []
         for name in bayes_set.order:
             st = bayes_set.sets[name]
             if name in names:
@@ -288,11 +298,14 @@ class LimbScene(object):
             if not ok or not isinstance(gas, LevelGas) or int(parts[2]) >= gas.n_levels:
                 raise ValueError("retrieval set %r names neither a gas of the scene nor tvib:<LevelGas>:<level> with a level "
                                  "of that gas" % (name,))
-            if level_gas is not None and gas is not level_gas:
+            if level_gas is not None and gas is not level_gas and not several_level_gases:
                 raise ValueError("vibrational-temperature sets of more than one gas (%s, %s): one call has one "
                                  "level-factored gas" % (level_gas.name, gas.name))
-            level_gas = gas
+            level_gas = gas if level_gas is None else level_gas
+            if not any(gas is g for g in level_gases):
+                level_gases.append(gas)
             for par in st.set:
+                par_lgas.append([gas is g for g in level_gases].index(True))
                 m = np.asarray(par.maskgrid.mask, dtype=float)
                 if m.shape != self.z.shape:
                     raise ValueError("the masks of %r are not on the scene's altitude levels" % (name,))
@@ -307,7 +320,8 @@ class LimbScene(object):
         return StateWeights(np.array(par_gas, np.int32), np.array(par_w_col, dtype=float).reshape(n_col, len(alt)), level_gas,
                             None if level_gas is None else self.gases.index(level_gas), np.array(par_level, np.int32),
                             np.array(par_w_lev, dtype=float).reshape(len(par_level), len(self.z)), perm,
-                            np.array(par_w_temp, dtype=float).reshape(len(par_w_temp), len(self.z)))
+                            np.array(par_w_temp, dtype=float).reshape(len(par_w_temp), len(self.z)), level_gases,
+                            [self.gases.index(g) for g in level_gases], np.array(par_lgas, np.int32))
 
     def temperature_derivatives(self):
         """(coeffs, dcoeffs): (abs, emi) of every gas at the CURRENT temperatures and their derivatives with respect to
@@ -779,7 +793,8 @@ def _state_into_gases(scene, bayes_set):
 def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM=0.1, L1_reg=False,
                     fov_closed_form=True, bands_in_kernel=False):
     """inversion_fast_limb's loop for a MIXED state vector: VMR-profile sets (named after a gas) together with the
-    vibrational-temperature sets of one LevelGas (TvibProfile) and the kinetic-temperature set (TempProfile; with it the
+    vibrational-temperature sets of one LevelGas or of several (TvibProfile; several: engine.LevelFactoredSet, the same one
+    call per iteration with the level parameters of all of them) and the kinetic-temperature set (TempProfile; with it the
     coefficients and their temperature derivatives are recomputed per iteration, LimbScene.temperature_derivatives, and
     the same call takes the third kind too; after the loop the scene holds the final temperatures while a plain gas's
     cached coefficients are the last iteration's: coefficients(refresh=True) recomputes them).  Per iteration: the profiles into the gases, the
@@ -797,7 +812,7 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
         raise ValueError("inversion_state needs the closed-form field of view for every pixel, or for none")
     alts = [a for pix in pixels for a in pix.los_alts()]
     # the sets' names are checked before anything is changed
-    with_temp = scene.state_weights(bayes_set, np.zeros(1)).par_w_temp.shape[0] > 0
+    with_temp = scene.state_weights(bayes_set, np.zeros(1), several_level_gases=True).par_w_temp.shape[0] > 0
     _state_into_gases(scene, bayes_set)
     obs = [pix.observation for pix in pixels]
     masks = None if all(pix.mask is None for pix in pixels) else [pix.mask for pix in pixels]
@@ -831,16 +846,23 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     for num_it in range(max_it):
         coeffs = None if with_temp else scene.coefficient_stack()
         los, alt = scene.los(alts)
-        w = scene.state_weights(bayes_set, alt)
+        w = scene.state_weights(bayes_set, alt, several_level_gases=True)
         # with_temp: coefficients at the current temperatures and their derivatives, then all three kinds at once
         dcoeffs = None
         if with_temp:
             coeffs, dcoeffs = (engine.gas_stack(c) for c in scene.temperature_derivatives())
         par_w_temp = w.par_w_temp if with_temp else None
         lg = w.level_gas
+        lfs = None
+        if len(w.level_gases) > 1:     # Tvib sets of several gases: their level parameters in the same one call
+            lfs = engine.LevelFactoredSet([(g.lf, i, g.rows, g.tvib) for g, i in zip(w.level_gases, w.gases)])
         if bands_in_kernel:    # Jacobians, instrument bands and field of view in one call: [n_pix | n_los, 1 + n_par, n_bands]
             band_args = dict(out_units=scene.out_units, fov=engine.fov_factors(rots) if with_fov else None)
-            if lg is None:
+            if lfs is not None:
+                both = lfs.state_bands(coeffs, los, w.par_lgas, w.par_level, w.par_w_lev, scene.grid, scene.bands_nm,
+                                       scene.widths_nm, par_gas=w.par_gas, par_w_col=w.par_w_col, dcoeffs=dcoeffs,
+                                       par_w_temp=par_w_temp, **band_args)
+            elif lg is None:
                 both = engine.limb_rays_state_bands(coeffs, los, scene.grid, scene.bands_nm, scene.widths_nm, par_gas=w.par_gas,
                                                     par_w=w.par_w_col, dcoeffs=dcoeffs, par_t=par_w_temp, **band_args)
             else:
@@ -850,8 +872,11 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             n_par = both.shape[1] - 1
             fov = both if with_fov else both[1::3]
             fov = np.concatenate([fov[:, :1, :], fov[:, 1:, :][:, w.perm]], axis=1)
-        else:                  # (the calls as they always were: without a temperature set no call names row parameters)
-            if with_temp and lg is None:
+        else:                  # (one level gas or none: the calls as they always were -- without a temperature set no call names row parameters)
+            if lfs is not None:
+                rad, jac = lfs.state_jacobian(coeffs, los, w.par_lgas, w.par_level, w.par_w_lev, par_gas=w.par_gas,
+                                              par_w_col=w.par_w_col, dcoeffs=dcoeffs, par_w_temp=par_w_temp)
+            elif with_temp and lg is None:
                 rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col, dcoeffs=dcoeffs,
                                                            par_t=w.par_w_temp)
             elif with_temp:
