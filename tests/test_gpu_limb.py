@@ -469,8 +469,9 @@ def test_band_fusion_equals_the_instrument_step(eng, n, n_par, n_g, n_extra):
     spectra + sr_hires_to_lowres_shard_dev's kernels (sr_set_band_fusion(0)): the same band integrals up to the order of
     the sums.  Grids that do not fill their last 256-point block, one block only; a band outside the grid (exactly zero
     both ways), a band over the whole grid, narrow bands at both ends, overlapping bands, 37 bands (three tiles of 16 in
-    the kernel's MFMA product); with and without the field-of-view integral; the fused call leaves `buf` untouched.  PARITY UNPINNED (product kernels against product
-    kernels: see test_retrieval_forward_against_its_parts)."""
+    the kernel's MFMA product); with and without the field-of-view integral; the fused call leaves `buf` untouched.  Product kernels against product
+    kernels (both sides read the same weight table): the band integrals of both routes are pinned to the extended-precision
+    reference by tests/test_gpu_lowres_reference.py; the recursion's own status: see test_retrieval_forward_against_its_parts."""
     import torch
     from spectrobot_amd import synthetic as syn
     rng = np.random.default_rng(n + n_par)

@@ -4,8 +4,10 @@ kernel integrates the bands in its epilogue and no hi-res spectrum is written.  
 without it, on the same inputs: limb_rays_state_jacobian -> hires_to_lowres on rad and on the flattened jac ->
 smm.fov_closed_form.  Both run the same recursion and differ in the order of the band sums only, so the bound is that of
 tests/test_gpu_limb.py::test_band_fusion_equals_the_instrument_step for the same epilogue: 1e-12 of a quantity row's
-largest element.  The hi-res Jacobian is pinned to the extended-precision reference (tests/test_gpu_limb_reference.py) and
-hires_to_lowres to the reference's Python (tests/golden/lowres_ils.npz): this file ties the new call to their composition."""
+largest element.  The hi-res Jacobian is pinned to the extended-precision reference (tests/test_gpu_limb_reference.py),
+hires_to_lowres to the reference's Python (tests/golden/lowres_ils.npz), and the band integrals of both routes -- weights,
+window ends, ranges, the band epilogue and the field of view -- to the extended-precision reference of the instrument step
+(tests/lowres_reference.py, tests/test_gpu_lowres_reference.py): this file ties the new call to their composition."""
 import copy
 
 import numpy as np
