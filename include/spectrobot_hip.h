@@ -651,6 +651,31 @@ int sr_limb_rays_state_bands_gases_dev(const double *abs_c, const double *emi_c,
                                        const double *par_t, const double *centers_nm, const double *widths_nm, int n_bands,
                                        double n_sigma, int out_units, const double *fov, double *out, void *stream);
 
+/* sr_limb_rays_state_bands_dev / sr_limb_rays_state_bands_gases_dev with the two INSTRUMENT rows: the derivatives of the
+ * radiance's bands to the band centre and to the logarithm of the ILS width (sr_hires_to_lowres_instr_shard_dev's
+ * definition, window membership held fixed), from the same call: in parameter block 0 the recursion kernel multiplies the
+ * wave's radiance row with the 16-band tiles of the two derivative weight tables too (the same v_mfma_f64_16x16x4 chain);
+ * the hi-res radiance is never written.  The arguments, limits and refusals of the two calls; in addition
+ * n_col + n_lev + n_row == 0 is allowed (the radiance and the instrument rows alone).
+ * out: HOST [n_rays / 3 or n_rays][1 + n_par + 2][n_bands]: rows 0 .. n_par as the call without the instrument rows
+ * returns them (bit for bit), row 1 + n_par = d / d centre (per nm), row 2 + n_par = d / d ln width.  The field of view
+ * is linear in the rays' band values and is applied to the two rows as to the others.  A band whose window misses the
+ * grid or holds fewer than two points is an exact 0.0 in every row.  A refused call leaves out untouched.  Synchronises
+ * the stream.  Checked against the extended-precision reference (tests/test_gpu_state_bands_instr.py). */
+int sr_limb_rays_state_bands_instr_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                       const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
+                                       const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
+                                       const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c,
+                                       int n_row, const double *par_t, const double *centers_nm, const double *widths_nm,
+                                       int n_bands, double n_sigma, int out_units, const double *fov, double *out, void *stream);
+int sr_limb_rays_state_bands_instr_gases_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                             const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w,
+                                             int n_lgas, const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas,
+                                             const int32_t *par_level, const double *par_c, const double *dabs_c,
+                                             const double *demi_c, int n_row, const double *par_t, const double *centers_nm,
+                                             const double *widths_nm, int n_bands, double n_sigma, int out_units,
+                                             const double *fov, double *out, void *stream);
+
 /* The radiance budget of the ray batch: which gas, and which level of the level-factored gas `gas`, emits the radiance
  * that arrives.  The recursion is linear in the emission: with tau = sum_g abs_g[r] u_g, t = exp(-tau), f = (1 - t) / tau
  * of a segment on coefficient row r,
@@ -722,6 +747,25 @@ int sr_hires_to_lowres_dev(const double *rad, int n_rays, int64_t n_pts, double 
 int sr_hires_to_lowres_shard_dev(const double *rad, int n_rays, int64_t n_pts, int64_t g_lo, double w0, double step,
                                  const double *centers_nm, const double *widths_nm, int n_bands, double n_sigma,
                                  int out_units, double *out_host, void *stream);
+
+/* sr_hires_to_lowres_shard_dev with the two instrument derivatives of every band.  With x_i = 1e7 / g_i the nm grid,
+ * t_i = (x_i - f_b) / w_b, W_i the trapezoid weights of band b (band_b = k sum_i s_i W_i over the window
+ * f_b - n_sigma w_b <= x_i <= f_b + n_sigma w_b, k the unit factor), and the window's MEMBERSHIP HELD FIXED:
+ *   centre f_b -> f_b + delta (nm):   d band_b / d delta = k sum_i s_i W_i t_i / w_b
+ *   width  w_b -> w_b e^eta:          d band_b / d eta   = k sum_i s_i W_i (t_i^2 - 1)
+ * The membership is piecewise constant in f and w; between its jumps these sums are the exact derivatives of the value,
+ * and a jump (a grid point entering or leaving at +-n_sigma) is of relative size exp(-n_sigma^2 / 2).  The factors are
+ * applied to the weights themselves (two more weight tables from the same pass over the window), and all three tables
+ * are applied in one read of the spectrum.
+ * out_host: HOST [n_rays][3][n_bands]: row 0 the value (sr_hires_to_lowres_shard_dev's, bit for bit), row 1 d / d delta,
+ * row 2 d / d eta.  A band whose window holds fewer than two points or misses the grid: exact 0.0 in all rows; a shard's
+ * rows are partial sums that add up over the shards.  Any parametrisation of the centres and widths (one global shift, an
+ * offset and a slope, ...) is a chain rule on these rows.  Arguments, limits, refusals and status codes as
+ * sr_hires_to_lowres_shard_dev.  Synchronises the stream.  Checked against an extended-precision reference
+ * (tests/test_gpu_lowres_instr.py). */
+int sr_hires_to_lowres_instr_shard_dev(const double *rad, int n_rays, int64_t n_pts, int64_t g_lo, double w0, double step,
+                                       const double *centers_nm, const double *widths_nm, int n_bands, double n_sigma,
+                                       int out_units, double *out_host, void *stream);
 
 /* Evaluation mode of the coefficient op.  Far region-1 wings by local Taylor expansions per box of grid
  * points (truncation <= sr_far_field_truncation_bound() of a line's own contribution: 1.6e-11 as built by default, degree

@@ -159,6 +159,14 @@ SYMBOLS = {
                                                      dp, C.c_int, C.POINTER(LevelGasDesc), C.c_int, ip, ip, dp, C.c_void_p,
                                                      C.c_void_p, C.c_int, dp, dp, dp, C.c_int, C.c_double, C.c_int, dp, dp,
                                                      C.c_void_p]),
+    "sr_limb_rays_state_bands_instr_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(LosDesc), C.c_int, ip,
+                                                     dp, C.c_int, C.c_void_p, C.c_int, C.c_int, ip, C.c_int, ip, dp, C.c_void_p,
+                                                     C.c_void_p, C.c_int, dp, dp, dp, C.c_int, C.c_double, C.c_int, dp, dp,
+                                                     C.c_void_p]),
+    "sr_limb_rays_state_bands_instr_gases_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(LosDesc), C.c_int,
+                                                           ip, dp, C.c_int, C.POINTER(LevelGasDesc), C.c_int, ip, ip, dp, C.c_void_p,
+                                                           C.c_void_p, C.c_int, dp, dp, dp, C.c_int, C.c_double, C.c_int, dp, dp,
+                                                           C.c_void_p]),
     "sr_limb_rays_parts_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(LosDesc), C.c_int,
                                          C.c_void_p, C.c_int, C.c_int, ip, C.c_int, ip, ip, dp, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
@@ -172,6 +180,8 @@ SYMBOLS = {
                                          C.c_double, C.c_int, dp, C.c_void_p]),
     "sr_hires_to_lowres_shard_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, dp, dp,
                                                C.c_int, C.c_double, C.c_int, dp, C.c_void_p]),
+    "sr_hires_to_lowres_instr_shard_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, dp, dp,
+                                                     C.c_int, C.c_double, C.c_int, dp, C.c_void_p]),
     "sr_set_points_per_lane": (C.c_int, [C.c_int]),
     "sr_set_band_fusion": (C.c_int, [C.c_int]),
     "sr_far_field_truncation_bound": (C.c_double, []),

@@ -2453,6 +2453,7 @@ struct LowresState {
   int64_t n_pts = -1, g_lo = 0;
   double w0 = 0, step = 0, n_sigma = 0;
   bool valid = false;
+  bool instr = false;     // the table is the three tables of a call with the instrument derivatives (another layout)
   unsigned gen = 0;
   int dev = -1;
   std::vector<double> bands;
@@ -2470,10 +2471,11 @@ static int lowres_check(int n_rows, int64_t n_pts, int64_t g_lo, double w0, doub
   return SR_OK;
 }
 // Arguments checked, buffers for n_rows spectra in place, the weight table valid on `st` (its kernel launched there when
-// the key changed: *fresh).  fused: partial sums per 64-point slot (launch_fold_dense with the scratch).
+// the key changed: *fresh).  fused: partial sums per 64-point slot (launch_fold_dense with the scratch).  instr: the
+// tables of the two instrument derivatives too (n_rows counts their rows); part of the key, the layouts differ.
 static int lowres_prepare(int n_rows, int64_t n_pts, int64_t g_lo, double w0, double step, const double *centers_nm,
                           const double *widths_nm, int n_bands, double n_sigma, int out_units, bool fused, hipStream_t st,
-                          bool *fresh) {
+                          bool *fresh, bool instr = false) {
   int rc = lowres_check(n_rows, n_pts, g_lo, w0, step, centers_nm, widths_nm, n_bands, n_sigma, out_units);
   if (rc) return rc;
   LowresState &L = t_lowres;
@@ -2488,9 +2490,9 @@ static int lowres_prepare(int n_rows, int64_t n_pts, int64_t g_lo, double w0, do
   }
   rc = L.d_out.ensure(sizeof(double) * nb * n_rows);
   if (rc) return rc;
-  rc = L.d_weights.ensure(lowres_scratch_bytes((int)n_pts, n_bands, n_rows, fused));
+  rc = L.d_weights.ensure(lowres_scratch_bytes((int)n_pts, n_bands, n_rows, fused, instr));
   if (rc) return rc;
-  const bool same = L.valid && L.gen == L.d_weights.gen && L.n_pts == n_pts && L.g_lo == g_lo && L.w0 == w0 && L.step == step &&
+  const bool same = L.valid && L.instr == instr && L.gen == L.d_weights.gen && L.n_pts == n_pts && L.g_lo == g_lo && L.w0 == w0 && L.step == step &&
                     L.n_sigma == n_sigma && L.bands.size() == 2 * nb &&
                     std::memcmp(L.bands.data(), centers_nm, sizeof(double) * nb) == 0 &&
                     std::memcmp(L.bands.data() + nb, widths_nm, sizeof(double) * nb) == 0;
@@ -2504,7 +2506,8 @@ static int lowres_prepare(int n_rows, int64_t n_pts, int64_t g_lo, double w0, do
   rc = L.s_bands.push(sizeof(double) * 2 * nb, st);
   if (rc) return rc;
   LAUNCHCHK(launch_lowres_weights((int)n_pts, (int)g_lo, w0, step, L.s_bands.d.as<double>(), L.s_bands.d.as<double>() + nb, n_bands,
-                                  n_sigma, L.d_weights.p, st));
+                                  n_sigma, L.d_weights.p, st, instr));
+  L.instr = instr;
   L.n_pts = n_pts; L.g_lo = g_lo; L.w0 = w0; L.step = step; L.n_sigma = n_sigma;
   L.bands.assign(centers_nm, centers_nm + nb);
   L.bands.insert(L.bands.end(), widths_nm, widths_nm + nb);
@@ -3364,7 +3367,8 @@ struct LevelJacPlan {
 };
 static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev, const int32_t *par_level, const double *par_c,
                                    int n_layers, int n_row = 0, const double *par_t = nullptr, const int32_t *par_lgas = nullptr) {
-  const int n_cl = n_col + n_lev, n_par = n_cl + n_row, np = level_jac_np(n_par), n_blocks = (n_par + np - 1) / np;
+  const int n_cl = n_col + n_lev, n_par = n_cl + n_row, np = level_jac_np(n_par);
+  const int n_blocks = std::max(1, (n_par + np - 1) / np); // (no parameter at all, the instrument rows alone: one block of unused slots)
   std::vector<int32_t> packed; // the `level` words of the entries: the level, with several level gases the gas above it
   if (par_lgas) {
     packed.resize((size_t)n_lev);
@@ -3402,14 +3406,15 @@ static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev,
 // with column slots (the state call, with n_col == 0 too); without it n_col is 0 and neither blk nor dcol exists.
 // n_row > 0 (sr_limb_rays_jac_state_rows_dev): the instances with row slots, which read dabs / demi.
 // band_scratch (sr_limb_rays_state_bands_dev): the instrument step's scratch with its weight table in place; the
-// instances with the band epilogue then leave their partial sums there, rad and jac are not used.
+// instances with the band epilogue then leave their partial sums there, rad and jac are not used.  instr: the scratch of
+// a call with the instrument derivatives, the INSTR instances; then there may be no parameter at all.
 static int limb_jac_state(bool cols, const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
                           const LosShape &shape, int n_col, const int32_t *par_gas, const double *par_w, int gas,
                           const double *tab, int n_tab_rows, const int32_t *coef_row, int n_lev, const int32_t *par_level,
                           const double *par_c, double *rad, double *jac, hipStream_t st, const double *dabs = nullptr,
                           const double *demi = nullptr, int n_row = 0, const double *par_t = nullptr,
                           const void *band_scratch = nullptr, int n_bands = 0, int n_lgas = 1,
-                          const sr_level_gas *lgas = nullptr, const int32_t *par_lgas = nullptr) {
+                          const sr_level_gas *lgas = nullptr, const int32_t *par_lgas = nullptr, bool instr = false) {
   const bool several = n_lgas > 1; // (then gas, tab, n_tab_rows and coef_row are not used: lgas has them per level gas)
   const LevelJacPlan P = level_jac_plan(n_col, par_gas, n_lev, par_level, par_c, n_layers, n_row, par_t, several ? par_lgas : nullptr);
   static thread_local StagerRing ring;
@@ -3442,12 +3447,12 @@ static int limb_jac_state(bool cols, const double *abs_c, const double *emi_c, i
     LAUNCHCHK(launch_limb_jac_state_gases(abs_c, emi_c, n_row > 0 ? dabs : nullptr, n_row > 0 ? demi : nullptr, (int)n_pts, n_layers,
                                           los->n_rays, D.seg_off, D.seg_layer, D.col, dcol, limb_opts(los, D.n_seg), lg,
                                           pk.dev(p_row), P.n_blocks, blk, pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot),
-                                          n_col + n_lev + n_row, rad, jac, band_scratch, n_bands, st));
+                                          n_col + n_lev + n_row, rad, jac, band_scratch, n_bands, st, instr));
   } else if (band_scratch)
     LAUNCHCHK(launch_limb_jac_state_bands(abs_c, emi_c, n_row > 0 ? dabs : nullptr, n_row > 0 ? demi : nullptr, (int)n_pts, n_layers,
                                           los->n_rays, D.seg_off, D.seg_layer, D.col, dcol, limb_opts(los, D.n_seg), gas, tab,
                                           n_tab_rows, pk.dev(p_row), P.n_blocks, blk, pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot),
-                                          n_col + n_lev + n_row, band_scratch, n_bands, st));
+                                          n_col + n_lev + n_row, band_scratch, n_bands, st, instr));
   else if (n_row > 0)
     LAUNCHCHK(launch_limb_jac_state_rows(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer,
                                          D.col, dcol, limb_opts(los, D.n_seg), gas, tab, n_tab_rows, pk.dev(p_row), P.n_blocks,
@@ -3481,8 +3486,8 @@ int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_l
 
 // The arguments of the mixed-state calls (sr_limb_rays_jac_state_dev, _state_rows_dev, sr_limb_rays_state_bands_dev and
 // their forms for several level gases), all of them before the first copy or launch (as sr_limb_rays_jac_level_dev does).
-// out_ok: the caller's outputs are there.  Any kind of parameter may be empty, not all; a kind that is empty needs none of
-// its arrays.  The level-factored gases come as a list: the one-gas entries hand in their one (one_level_gas), for which
+// out_ok: the caller's outputs are there.  Any kind of parameter may be empty, not all (may_be_empty: all, the calls
+// with the instrument rows, which have something to return without a parameter); a kind that is empty needs none of its arrays.  The level-factored gases come as a list: the one-gas entries hand in their one (one_level_gas), for which
 // the checks and their order are what they always were; par_lgas [n_lev] names a level parameter's level gas (null with
 // one: all 0).
 static sr_level_gas one_level_gas(int gas, const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row) {
@@ -3494,13 +3499,13 @@ static int check_state_call(const char *entry, const double *abs_c, const double
                             const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
                             const sr_level_gas *lgas, const int32_t *par_lgas, int n_lev, const int32_t *par_level,
                             const double *par_c, const double *dabs_c, const double *demi_c, int n_row, const double *par_t,
-                            bool out_ok, LosShape *shape) {
+                            bool out_ok, LosShape *shape, bool may_be_empty = false) {
   const bool list_ok = lgas && n_lgas >= 1 && n_lgas <= kLevelGasMax;
   bool lev_ok = n_lev == 0 || (list_ok && par_level && par_c && (n_lgas == 1 || par_lgas));
   for (int k = 0; list_ok && n_lev > 0 && k < n_lgas; ++k)
     lev_ok = lev_ok && lgas[k].tab && lgas[k].coef_row && lgas[k].n_levels > 0 && lgas[k].n_tab_rows > 0;
   const bool row_ok = n_row == 0 || (dabs_c && demi_c && par_t);
-  const bool counts_ok = n_col >= 0 && n_lev >= 0 && n_row >= 0 && (int64_t)n_col + n_lev + n_row >= 1;
+  const bool counts_ok = n_col >= 0 && n_lev >= 0 && n_row >= 0 && (int64_t)n_col + n_lev + n_row >= (may_be_empty ? 0 : 1);
   int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, out_ok && counts_ok && list_ok && lev_ok && row_ok);
   if (!rc) rc = check_los_par(los, n_layers, n_col, par_gas, par_w, shape);
   if (rc) return rc;
@@ -3566,12 +3571,17 @@ static int limb_state_bands(const char *entry, const double *abs_c, const double
                             const sr_level_gas *lgas, const int32_t *par_lgas, int n_lev, const int32_t *par_level,
                             const double *par_c, const double *dabs_c, const double *demi_c, int n_row, const double *par_t,
                             const double *centers_nm, const double *widths_nm, int n_bands, double n_sigma, int out_units,
-                            const double *fov, double *out, void *stream) {
+                            const double *fov, double *out, void *stream, bool instr = false) {
   LosShape shape;
   int rc = check_state_call(entry, abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, n_lgas, lgas, par_lgas, n_lev,
-                            par_level, par_c, dabs_c, demi_c, n_row, par_t, out && centers_nm && widths_nm && n_bands > 0, &shape);
+                            par_level, par_c, dabs_c, demi_c, n_row, par_t, out && centers_nm && widths_nm && n_bands > 0, &shape,
+                            /*may_be_empty=*/instr);
   if (rc) return rc;
-  const int n_rays = los->n_rays, n_par = n_col + n_lev + n_row;
+  // instr: the two instrument rows are the last two parameter rows of every ray, here and in the kernel; the sum kernel
+  // and the field of view (linear in the rays' band values) take them as they are
+  const int n_rays = los->n_rays, n_state = n_col + n_lev + n_row;
+  if (instr && n_state > INT_MAX - 2) return SR_ERR_LIMIT;
+  const int n_par = n_state + (instr ? 2 : 0);
   if (fov && n_rays % 3 != 0) return SR_ERR_ARG;
   if ((int64_t)n_rays * (1 + (int64_t)n_par) > INT_MAX) return SR_ERR_LIMIT;
   const int n_spec = n_rays * (1 + n_par);
@@ -3581,17 +3591,17 @@ static int limb_state_bands(const char *entry, const double *abs_c, const double
   hipStream_t st = static_cast<hipStream_t>(stream);
   bool fresh = false;
   rc = lowres_prepare(n_spec, n_pts, los->g_lo, los->w0, los->step, centers_nm, widths_nm, n_bands, n_sigma, out_units,
-                      /*fused=*/true, st, &fresh);
+                      /*fused=*/true, st, &fresh, instr);
   if (rc) return rc;
   rc = limb_jac_state(n_col > 0, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, lgas[0].gas, lgas[0].tab,
                       lgas[0].n_tab_rows, lgas[0].coef_row, n_lev, par_level, par_c, nullptr, nullptr, st, dabs_c, demi_c, n_row,
-                      par_t, t_lowres.d_weights.p, n_bands, n_lgas, lgas, par_lgas);
+                      par_t, t_lowres.d_weights.p, n_bands, n_lgas, lgas, par_lgas, instr);
   if (rc) return rc;
   const size_t low_bytes = sizeof(double) * (size_t)n_spec * n_bands;
   rc = t_lowres.s_land.prepare(low_bytes);
   if (rc) return rc;
   LAUNCHCHK(launch_lowres_sum_blocks((int)n_pts, n_spec, n_bands, out_units, static_cast<double *>(t_lowres.s_land.h),
-                                     t_lowres.d_weights.p, st));
+                                     t_lowres.d_weights.p, st, instr));
   HIPCHK(hipStreamSynchronize(st));
   fov_rows(static_cast<const double *>(t_lowres.s_land.h), n_rays, n_par, n_bands, fov, out);
   return SR_OK;
@@ -3653,6 +3663,38 @@ int sr_limb_rays_state_bands_gases_dev(const double *abs_c, const double *emi_c,
   return limb_state_bands("sr_limb_rays_state_bands_gases_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, n_lgas,
                           lgas, par_lgas, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm, n_bands,
                           n_sigma, out_units, fov, out, stream);
+}
+
+// ... with the two instrument rows behind the parameters' (d / d band centre, d / d ln ILS width of the radiance's bands):
+// the same arguments, the same checks, out [n_rays / 3 or n_rays][1 + n_par + 2][n_bands]; no parameter at all is allowed.
+int sr_limb_rays_state_bands_instr_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                       const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
+                                       const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
+                                       const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c,
+                                       int n_row, const double *par_t, const double *centers_nm, const double *widths_nm,
+                                       int n_bands, double n_sigma, int out_units, const double *fov, double *out, void *stream) {
+  const sr_level_gas one = one_level_gas(gas, tab, n_levels, n_tab_rows, coef_row);
+  return limb_state_bands("sr_limb_rays_state_bands_instr_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, 1, &one,
+                          nullptr, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm, n_bands, n_sigma,
+                          out_units, fov, out, stream, /*instr=*/true);
+}
+
+int sr_limb_rays_state_bands_instr_gases_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                             const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w,
+                                             int n_lgas, const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas,
+                                             const int32_t *par_level, const double *par_c, const double *dabs_c,
+                                             const double *demi_c, int n_row, const double *par_t, const double *centers_nm,
+                                             const double *widths_nm, int n_bands, double n_sigma, int out_units,
+                                             const double *fov, double *out, void *stream) {
+  int rc;
+  if (one_level_gas_call(n_lgas, lgas, n_lev, par_lgas, &rc))
+    return rc ? rc : sr_limb_rays_state_bands_instr_dev(abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, lgas[0].gas,
+                                                        lgas[0].tab, lgas[0].n_levels, lgas[0].n_tab_rows, lgas[0].coef_row, n_lev,
+                                                        par_level, par_c, dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm,
+                                                        n_bands, n_sigma, out_units, fov, out, stream);
+  return limb_state_bands("sr_limb_rays_state_bands_instr_gases_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w,
+                          n_lgas, lgas, par_lgas, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm,
+                          n_bands, n_sigma, out_units, fov, out, stream, /*instr=*/true);
 }
 
 int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
@@ -3772,6 +3814,24 @@ int sr_hires_to_lowres_shard_dev(const double *rad, int n_rays, int64_t n_pts, i
   LAUNCHCHK(launch_lowres(rad, (int)n_pts, (int)g_lo, n_rays, w0, step, nullptr, nullptr, n_bands, n_sigma, out_units,
                           L.d_out.as<double>(), L.d_weights.p, st, /*weights=*/false));
   return lowres_land(n_rays, n_bands, out_host, st);
+}
+
+// The instrument step with its two instrument derivatives: out_host [n_rays][3][n_bands] = the value (sr_hires_to_lowres_
+// shard_dev's, bit for bit), d / d band centre (per nm), d / d ln ILS width; arguments, limits, refusals and status codes
+// as sr_hires_to_lowres_shard_dev.
+int sr_hires_to_lowres_instr_shard_dev(const double *rad, int n_rays, int64_t n_pts, int64_t g_lo, double w0, double step,
+                                       const double *centers_nm, const double *widths_nm, int n_bands, double n_sigma,
+                                       int out_units, double *out_host, void *stream) {
+  if (!rad || !out_host) return SR_ERR_ARG;
+  if (n_rays > INT_MAX / 3) return SR_ERR_LIMIT;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  bool fresh = false;
+  int rc = lowres_prepare(n_rays > 0 ? 3 * n_rays : n_rays, n_pts, g_lo, w0, step, centers_nm, widths_nm, n_bands, n_sigma, out_units,
+                          /*fused=*/false, st, &fresh, /*instr=*/true);
+  if (rc) return rc;
+  LowresState &L = t_lowres;
+  LAUNCHCHK(launch_lowres_instr(rad, (int)n_pts, n_rays, n_bands, out_units, L.d_out.as<double>(), L.d_weights.p, st));
+  return lowres_land(3 * n_rays, n_bands, out_host, st);
 }
 
 // ------------------------------------------------------------------------

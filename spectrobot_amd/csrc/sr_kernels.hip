@@ -3258,6 +3258,7 @@ struct FoldBands {
   double *part;
   int n_bands;
 };
+constexpr int kLowresTables = 3; // the weight tables of a call with the instrument derivatives: value, d / d centre, d / d ln width
 constexpr int kBandRow = 68; // doubles per row of a wave's tile of values (64 + padding: rows 8 banks apart)
 // the buffer limb_initial() reads with init_mode 1 (which the host refuses for the state kernel): none with BANDS
 __device__ inline const double *limb_state_init_src(const double *jac) { return jac; }
@@ -3334,7 +3335,15 @@ __device__ __forceinline__ const LevelGasTabs &state_level_gases(const T &, cons
 // in scalar registers over the exponential; the COLS instances sit at the scalar-register limit).  The recursion term,
 // the row slots, the kLevelEntRows sentinel and the band epilogue are untouched; gas, tab and n_tab_rows are not read.
 // The instances without a LevelGasTabs keep their argument block and their machine code.
-template <int NG, int NP, bool COLS, bool ROWS, bool BANDS, class... RowSpectra>
+// INSTR = true (sr_limb_rays_state_bands_instr_dev, BANDS instances only): the two instrument derivatives of the radiance's
+// bands, d / d centre and d / d ln width (sr_lowres_weights_kernel).  They are band integrals of the radiance alone with
+// other weights, and those weights lie in Wt as further band tiles (table k at tile k n_tiles + tile, k = 1, 2): in
+// parameter block 0 the tile loop of the row tile that holds the radiance runs over them too -- the same A operands, the
+// same MFMA chain -- and stores that ONE row, to the rows of parameters n_par - 2 and n_par - 1 (the host counts the two
+// instrument rows into n_par: they are the last two "parameters" of every ray, so the rows of `part`, the sum kernel and
+// the field of view take them as they are).  slot_par never names them.  The recursion, every other row and the
+// INSTR = false instances are untouched: same argument block, same machine code.
+template <int NG, int NP, bool COLS, bool ROWS, bool BANDS, bool INSTR, class... RowSpectra>
 __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
     const int *__restrict__ seg_off, const int *__restrict__ seg_layer, const double *__restrict__ col,
@@ -3343,6 +3352,7 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     const LevelEnt *__restrict__ ent, const int *__restrict__ slot_par, int n_par, double *__restrict__ rad,
     std::conditional_t<BANDS, FoldBands, double *__restrict__> jac, RowSpectra... row_spectra) {
   static_assert(NP <= 16 && NG <= 4, "blk packs the gases of 16 column slots, two bits each");
+  static_assert(BANDS || !INSTR, "the instrument rows are band integrals");
   constexpr bool GASES = kStateSeveralGases<RowSpectra...>;
   static_assert(sizeof...(RowSpectra) == (ROWS ? 2 : 0) + (GASES ? 1 : 0), "dabs and demi with ROWS, then the level gases' tables, if several");
   int pb, ray;
@@ -3494,7 +3504,12 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
         const int p = slot_par[blockIdx.z * NP + min(q, NP - 1)];
         orow[r] = q < NP ? (p >= 0 ? (long long)n_rays + (long long)ray * n_par + p : -1) : (q == NP && first ? (long long)ray : -1);
       }
-      for (int tile = 0; tile < n_tiles; ++tile) {
+      // INSTR: in block 0 the row tile that holds the radiance (value NP: row NP & 15 of row tile NP / 16, held by the lanes
+      // kq == (NP & 3) in acc[(NP & 15) >> 2]) goes on over the tiles of the two derivative tables -- the same loop, the
+      // same operands -- and stores that one row (a second loop of its own cost 36 VGPRs and a wave per SIMD)
+      int n_tl = n_tiles;
+      if constexpr (INSTR) n_tl = first && rt == NP / 16 ? kLowresTables * n_tiles : n_tiles;
+      for (int tile = 0; tile < n_tl; ++tile) {
         const double *wt = bd.Wt + (size_t)tile * n_pts * 16 + lo;
         double Bv[16]; // a tile's sixteen B operands requested together
 #pragma unroll
@@ -3502,6 +3517,14 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
         v4d acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[ks], Bv[ks], acc, 0, 0, 0);
+        if constexpr (INSTR) {
+          if (tile >= n_tiles) { // (wave-uniform) table k = 1, 2, its band tile bt: the instrument row n_par - 3 + k of the ray
+            const int k = tile >= 2 * n_tiles ? 2 : 1, bt = tile - k * n_tiles;
+            const size_t row = (size_t)n_rays + (size_t)ray * n_par + (n_par - kLowresTables + k);
+            if (kq == (NP & 3)) bd.part[((row * n_slots + 4 * pb + wave) * n_tiles + bt) * 16 + lo] = acc[(NP & 15) >> 2];
+            continue;
+          }
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           if (orow[r] >= 0) bd.part[(((size_t)orow[r] * n_slots + 4 * pb + wave) * n_tiles + tile) * 16 + lo] = acc[r];
@@ -4276,18 +4299,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SR_FOLD_WAV
 // segments and every parameter (up to kFoldDensePar) is carried along in ONE sweep: sr_limb_fold_sens_lds_kernel below.
 // ------------------------------------------------------------------------
 // the instrument step's device scratch (launch_lowres): the bands' weight table and point ranges, then partial sums
+// instr (the instrument derivatives, see sr_lowres_weights_kernel): THREE tables one behind the other in W and in Wt -- the
+// weights, then those of d / d centre and of d / d ln width ([3][n_bands][n_pts]; Wt: band tile `tile` of table k is tile
+// k n_tiles + tile) -- and nothing else moves; without it the layout is what it always was.
 struct LowresScratch {
   double *W;   // [n_bands][n_pts]
   int *range;  // [n_bands][2]
   double *Wt;  // [band tiles][n_pts][16]: the same weights, band-minor in tiles of 16 (zero columns beyond n_bands)
   double *part;
 };
-static LowresScratch lowres_layout(void *scratch, int n_pts, int n_bands) {
+static LowresScratch lowres_layout(void *scratch, int n_pts, int n_bands, bool instr = false) {
+  const size_t n_tab = instr ? kLowresTables : 1;
   LowresScratch L;
   L.W = static_cast<double *>(scratch);
-  L.range = reinterpret_cast<int *>(L.W + (size_t)n_bands * n_pts); // (before the partial sums: their size follows n_rays)
+  L.range = reinterpret_cast<int *>(L.W + n_tab * n_bands * n_pts); // (before the partial sums: their size follows n_rays)
   L.Wt = reinterpret_cast<double *>(L.range + 2 * (size_t)n_bands + 2);
-  L.part = L.Wt + (size_t)((n_bands + 15) / 16) * 16 * n_pts;
+  L.part = L.Wt + n_tab * ((n_bands + 15) / 16) * 16 * n_pts;
   return L;
 }
 struct __attribute__((aligned(16))) FoldDense { // one ray in one shell
@@ -4799,7 +4826,7 @@ int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, i
   auto launch = [&](auto cols) { // no blk: the instance without column slots
     by_level_np(level_jac_np(n_par), [&](auto np) {
       by_ngas(o.n_gas, [&](auto ng) {
-        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, false, false>), grid,
+        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, false, false, false>), grid,
                            dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas, tab,
                            n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac);
       });
@@ -4820,7 +4847,7 @@ int launch_limb_jac_state_rows(const double *abs_c, const double *emi_c, const d
   auto launch = [&](auto cols) { // no blk: the instance without column slots
     by_level_np(level_jac_np(n_par), [&](auto np) {
       by_ngas(o.n_gas, [&](auto ng) {
-        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, true, false,
+        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, true, false, false,
                                                      const double *, const double *>),
                            grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas,
                            tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac, dabs, demi);
@@ -4836,29 +4863,35 @@ int launch_limb_jac_state_bands(const double *abs_c, const double *emi_c, const 
                                 int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
                                 const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
                                 const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
-                                const int *slot_par, int n_par, const void *lowres_scratch, int n_bands, hipStream_t st) {
-  if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0 || n_bands <= 0 || !lowres_scratch) return 0;
+                                const int *slot_par, int n_par, const void *lowres_scratch, int n_bands, hipStream_t st, bool instr) {
+  if (n_pts <= 0 || n_rays <= 0 || n_par < (instr ? 0 : 1) || n_blocks <= 0 || n_bands <= 0 || !lowres_scratch) return 0;
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
-  const LowresScratch L = lowres_layout(const_cast<void *>(lowres_scratch), n_pts, n_bands);
+  const LowresScratch L = lowres_layout(const_cast<void *>(lowres_scratch), n_pts, n_bands, instr);
   const FoldBands bd{L.Wt, L.range, L.part, n_bands};
   double *const no_rad = nullptr;
-  auto launch = [&](auto cols) { // no blk: the instance without column slots
+  const int n_row_par = n_par + (instr ? kLowresTables - 1 : 0); // the parameter rows of a ray in `part`
+  auto launch = [&](auto cols, auto ins) { // no blk: the instance without column slots
     by_level_np(level_jac_np(n_par), [&](auto np) {
       by_ngas(o.n_gas, [&](auto ng) {
         if (dabs && demi) // row parameters
           hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, true, true,
-                                                       const double *, const double *>),
+                                                       decltype(ins)::value, const double *, const double *>),
                              grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas,
-                             tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, no_rad, bd, dabs, demi);
+                             tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_row_par, no_rad, bd, dabs, demi);
         else
-          hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, false, true>),
+          hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, false, true,
+                                                       decltype(ins)::value>),
                              grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas,
-                             tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, no_rad, bd);
+                             tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_row_par, no_rad, bd);
       });
     });
   };
-  if (blk) launch(std::true_type{});
-  else launch(std::false_type{});
+  auto by_instr = [&](auto cols) {
+    if (instr) launch(cols, std::true_type{});
+    else launch(cols, std::false_type{});
+  };
+  if (blk) by_instr(std::true_type{});
+  else by_instr(std::false_type{});
   return (int)hipGetLastError();
 }
 
@@ -4866,14 +4899,16 @@ int launch_limb_jac_state_gases(const double *abs_c, const double *emi_c, const 
                                 int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
                                 const double *dcol, const LimbOpts &o, const LevelGasTabs &lg, const int *coef_row, int n_blocks,
                                 const int *blk, const int *ent_off, const LevelEnt *ent, const int *slot_par, int n_par,
-                                double *rad, double *jac, const void *lowres_scratch, int n_bands, hipStream_t st) {
-  if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0 || o.n_gas < 2 || o.n_gas > 4) return 0;
+                                double *rad, double *jac, const void *lowres_scratch, int n_bands, hipStream_t st, bool instr) {
+  if (instr && !lowres_scratch) return 0;
+  if (n_pts <= 0 || n_rays <= 0 || n_par < (instr ? 0 : 1) || n_blocks <= 0 || o.n_gas < 2 || o.n_gas > 4) return 0;
   if (lowres_scratch && n_bands <= 0) return 0;
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
   const bool rows = dabs && demi;
   const double *const no_tab = nullptr;
   double *const no_rad = nullptr;
   constexpr int no_gas = -1; // (gas, tab and n_tab_rows belong to the one-gas instances)
+  const int n_row_par = n_par + (instr ? kLowresTables - 1 : 0); // the parameter rows of a ray in `part`
   auto launch = [&](auto cols) { // no blk: the instances without column slots
     by_level_np(level_jac_np(n_par), [&](auto np) {
       by_ngas(o.n_gas, [&](auto ng) {
@@ -4881,22 +4916,27 @@ int launch_limb_jac_state_gases(const double *abs_c, const double *emi_c, const 
         constexpr bool COLS = decltype(cols)::value;
         if constexpr (NG >= 2) { // (several level gases are several gases of the batch)
           if (lowres_scratch) {
-            const LowresScratch L = lowres_layout(const_cast<void *>(lowres_scratch), n_pts, n_bands);
+            const LowresScratch L = lowres_layout(const_cast<void *>(lowres_scratch), n_pts, n_bands, instr);
             const FoldBands bd{L.Wt, L.range, L.part, n_bands};
-            if (rows)
-              hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, true, true, const double *, const double *, LevelGasTabs>), grid,
-                                 dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas,
-                                 no_tab, 0, coef_row, blk, ent_off, ent, slot_par, n_par, no_rad, bd, dabs, demi, lg);
-            else
-              hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, false, true, LevelGasTabs>), grid, dim3(256), 0, st, abs_c,
-                                 emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas, no_tab, 0, coef_row, blk,
-                                 ent_off, ent, slot_par, n_par, no_rad, bd, lg);
+            auto bands = [&](auto ins) {
+              constexpr bool INSTR = decltype(ins)::value;
+              if (rows)
+                hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, true, true, INSTR, const double *, const double *, LevelGasTabs>),
+                                   grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays,
+                                   no_gas, no_tab, 0, coef_row, blk, ent_off, ent, slot_par, n_row_par, no_rad, bd, dabs, demi, lg);
+              else
+                hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, false, true, INSTR, LevelGasTabs>), grid, dim3(256), 0, st,
+                                   abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas, no_tab, 0, coef_row,
+                                   blk, ent_off, ent, slot_par, n_row_par, no_rad, bd, lg);
+            };
+            if (instr) bands(std::true_type{});
+            else bands(std::false_type{});
           } else if (rows) {
-            hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, true, false, const double *, const double *, LevelGasTabs>), grid,
-                               dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas,
+            hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, true, false, false, const double *, const double *, LevelGasTabs>),
+                               grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas,
                                no_tab, 0, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac, dabs, demi, lg);
           } else {
-            hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, false, false, LevelGasTabs>), grid, dim3(256), 0, st, abs_c,
+            hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, false, false, false, LevelGasTabs>), grid, dim3(256), 0, st, abs_c,
                                emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas, no_tab, 0, coef_row, blk,
                                ent_off, ent, slot_par, n_par, rad, jac, lg);
           }
@@ -5316,6 +5356,17 @@ __global__ void sr_curgod_kernel(int which, const double *__restrict__ nd, const
 // sr_lowres_weights_kernel makes W [n_bands][n_pts] (cm-1 index order) and the bands' point ranges once per call,
 // sr_lowres_apply_kernel is the banded product: a block per (spectrum, chunk of 4096 points, group of 16 bands), the
 // chunks' partial sums added in chunk order by sr_lowres_sum_kernel.
+//
+// INSTR = true: the two instrument derivatives of a band, the window's membership held fixed (it is piecewise constant in
+// f and w; between its jumps, of relative size exp(-n_sigma^2 / 2), these are the exact derivatives of the sum):
+//   centre f -> f + delta (nm):  d band / d delta = sum_i s_i W_i t_i / w
+//   width  w -> w e^eta:         d band / d eta   = sum_i s_i W_i (t_i^2 - 1)
+// (d u / d f = u t / w; d u / d ln w = u (t^2 - 1): the Gaussian's t^2 and the normalisation's -1; c_i does not move.)
+// Linear functionals of the spectrum with weights that differ from W by a polynomial in t: the two tables are written
+// beside W and Wt in the same pass -- the same window search, the same t -- as tables 1 and 2 of the scratch
+// (lowres_layout, instr), each factor applied to the weight itself (moments sum s x W would cancel).  A window of fewer
+// than two points is zero in all three.  INSTR = false: the kernel as it was.
+template <bool INSTR>
 __global__ __launch_bounds__(256) void sr_lowres_weights_kernel(int n_pts, int g_lo, double w0, double gstep,
                                                                 const double *__restrict__ cen, const double *__restrict__ wid,
                                                                 double n_sigma, int n_bands, double *__restrict__ W, // [n_bands][n_pts]
@@ -5324,7 +5375,14 @@ __global__ __launch_bounds__(256) void sr_lowres_weights_kernel(int n_pts, int g
   const int b = blockIdx.y;
   if (b >= n_bands) { // the zero columns that fill the last tile of Wt
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n_pts) Wt[((size_t)(b >> 4) * n_pts + j) * 16 + (b & 15)] = 0.0;
+    if (j < n_pts) {
+      const size_t at = ((size_t)(b >> 4) * n_pts + j) * 16 + (b & 15);
+      Wt[at] = 0.0;
+      if constexpr (INSTR) {
+        const size_t tab_wt = (size_t)(gridDim.y >> 4) * n_pts * 16; // a table of Wt
+        Wt[tab_wt + at] = Wt[2 * tab_wt + at] = 0.0;
+      }
+    }
     return;
   }
   const double f = cen[b], w = wid[b];
@@ -5351,14 +5409,27 @@ __global__ __launch_bounds__(256) void sr_lowres_weights_kernel(int n_pts, int g
   if (j >= n_pts) return;
   const int i = n_pts - 1 - j;
   double wgt = 0.0;
+  [[maybe_unused]] double wgt_f = 0.0, wgt_w = 0.0;
   if (i >= i0 && i < i1 && i1 - i0 >= 2) {
     const double g = gcm(i), x = 1.e7 / g, t = (x - f) / w;
     const double u = ((g * g) * 1.e-7) * (fac * exp(-0.5 * (t * t))); // y = s u (spcl:779-783 the cm-1 -> nm factor, :1926-1934 the Gaussian)
     const double xl = i > i0 ? xnm(i - 1) : x, xr = i + 1 < i1 ? xnm(i + 1) : x;
     wgt = u * ((xr - xl) / 2.0);
+    if constexpr (INSTR) {
+      wgt_f = wgt * (t / w);
+      wgt_w = wgt * (t * t - 1.0);
+    }
   }
-  W[(size_t)b * n_pts + j] = wgt;
-  Wt[((size_t)(b >> 4) * n_pts + j) * 16 + (b & 15)] = wgt;
+  const size_t at = (size_t)b * n_pts + j, at_t = ((size_t)(b >> 4) * n_pts + j) * 16 + (b & 15);
+  W[at] = wgt;
+  Wt[at_t] = wgt;
+  if constexpr (INSTR) {
+    const size_t tab_w = (size_t)n_bands * n_pts, tab_wt = (size_t)(gridDim.y >> 4) * n_pts * 16; // a table of W, of Wt
+    W[tab_w + at] = wgt_f;
+    W[2 * tab_w + at] = wgt_w;
+    Wt[tab_wt + at_t] = wgt_f;
+    Wt[2 * tab_wt + at_t] = wgt_w;
+  }
 }
 
 constexpr int kLowresBands = 16;   // bands per block of the apply kernel
@@ -5367,16 +5438,24 @@ constexpr int kLowresBands = 16;   // bands per block of the apply kernel
 #endif
 constexpr int kLowresChunk = SR_LOWRES_CHUNK; // (2048 / 1024 measured 60 / 80 us against 56 for the 144 spectra of a configs[4] iteration) points per block: 144 spectra x 15 chunks fill the chip (a block per spectrum walked
                                    // its 60 000 points alone: 117 dependent rounds of 15 loads, 0.21 ms)
+// N_TAB = 1: the weights alone, part [n_rays][n_chunks][n_bands].  N_TAB = 3 (sr_hires_to_lowres_instr_shard_dev): the three
+// tables of an instr scratch applied in ONE read of the spectrum -- per band the value's accumulator takes the same
+// operations in the same order (row 0 is the N_TAB = 1 result, bit for bit: one text), the two derivative accumulators
+// beside it; part [n_rays][3][n_chunks][n_bands], i.e. row 3 ray + k of sr_lowres_sum_kernel's [rows][n_chunks][n_bands].
+template <int N_TAB>
 __global__ __launch_bounds__(256) void sr_lowres_apply_kernel(const double *__restrict__ rad, int n_pts,
                                                               const double *__restrict__ W, const int *__restrict__ range,
                                                               int n_bands, int n_chunks,
-                                                              double *__restrict__ part) { // [n_rays][n_chunks][n_bands]
+                                                              double *__restrict__ part) { // [n_rays][N_TAB][n_chunks][n_bands]
   const int ray = blockIdx.x, chunk = blockIdx.y, b0 = blockIdx.z * kLowresBands, nb = min(kLowresBands, n_bands - b0);
   const double *sp = rad + (size_t)ray * n_pts;
+  [[maybe_unused]] const size_t tab = (size_t)n_bands * n_pts; // a table of W
   const int c_lo = chunk * kLowresChunk, c_hi = min(c_lo + kLowresChunk, n_pts);
-  double acc[kLowresBands];
+  double acc[N_TAB][kLowresBands];
 #pragma unroll
-  for (int q = 0; q < kLowresBands; ++q) acc[q] = 0.0;
+  for (int k = 0; k < N_TAB; ++k)
+#pragma unroll
+    for (int q = 0; q < kLowresBands; ++q) acc[k][q] = 0.0;
   // W is zero outside a band's window: no per-point range test, only whole bands that miss the chunk are skipped
   // (block-uniform); the loads of a point's bands are independent of each other
   bool use[kLowresBands];
@@ -5386,28 +5465,38 @@ __global__ __launch_bounds__(256) void sr_lowres_apply_kernel(const double *__re
     use[q] = q < nb && range[2 * (b0 + q)] < c_hi && range[2 * (b0 + q) + 1] > c_lo;
     any_use = any_use || use[q];
   }
+  auto row = [&](int k) { return (((size_t)ray * N_TAB + k) * n_chunks + chunk) * n_bands + b0; };
   if (!any_use) { // none of this block's bands reaches the chunk (block-uniform): zeros, and the spectrum is not read
-    if ((int)threadIdx.x < nb) part[((size_t)ray * n_chunks + chunk) * n_bands + b0 + threadIdx.x] = 0.0;
+    if ((int)threadIdx.x < nb)
+#pragma unroll
+      for (int k = 0; k < N_TAB; ++k) part[row(k) + threadIdx.x] = 0.0;
     return;
   }
   for (int j = c_lo + (int)threadIdx.x; j < c_hi; j += (int)blockDim.x) {
     const double sv = sp[j];
 #pragma unroll
     for (int q = 0; q < kLowresBands; ++q)
-      if (use[q]) acc[q] = fma(sv, W[(size_t)(b0 + q) * n_pts + j], acc[q]);
-  }
-  __shared__ double red[kLowresBands][4];
+      if (use[q]) {
+        const double *w = W + (size_t)(b0 + q) * n_pts + j;
 #pragma unroll
-  for (int q = 0; q < kLowresBands; ++q) {
-    double v = acc[q];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = v;
+        for (int k = 0; k < N_TAB; ++k) acc[k][q] = fma(sv, w[k * tab], acc[k][q]);
+      }
   }
+  __shared__ double red[N_TAB][kLowresBands][4];
+#pragma unroll
+  for (int k = 0; k < N_TAB; ++k)
+#pragma unroll
+    for (int q = 0; q < kLowresBands; ++q) {
+      double v = acc[k][q];
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+      if ((threadIdx.x & 63) == 0) red[k][q][threadIdx.x >> 6] = v;
+    }
   __syncthreads();
   if ((int)threadIdx.x < nb) {
     const int q = threadIdx.x;
-    part[((size_t)ray * n_chunks + chunk) * n_bands + b0 + q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
+#pragma unroll
+    for (int k = 0; k < N_TAB; ++k) part[row(k) + q] = (red[k][q][0] + red[k][q][1]) + (red[k][q][2] + red[k][q][3]);
   }
 }
 __global__ void sr_lowres_sum_kernel(const double *__restrict__ part, int n_rays, int n_chunks, int n_bands, int out_units,
@@ -5450,26 +5539,34 @@ __global__ __launch_bounds__(256) void sr_lowres_sum_blocks_kernel(const double 
 }
 
 static int lowres_chunks(int n_pts) { return (n_pts + kLowresChunk - 1) / kLowresChunk; }
-// fused: the partial sums are per wave of the recursion (launch_fold_dense with the scratch)
-size_t lowres_scratch_bytes(int n_pts, int n_bands, int n_rays, bool fused) {
-  const size_t tiles16 = (size_t)((n_bands + 15) / 16) * 16;
+// fused: the partial sums are per wave of the recursion (launch_fold_dense with the scratch).  n_rays: the rows of partial
+// sums (spectra; with the instrument derivatives, instr, the caller counts their rows in).  The scratch grows by the two
+// derivative tables with instr only.
+size_t lowres_scratch_bytes(int n_pts, int n_bands, int n_rays, bool fused, bool instr) {
+  const size_t tiles16 = (size_t)((n_bands + 15) / 16) * 16, n_tab = instr ? kLowresTables : 1;
   const size_t n_part = fused ? 4 * (size_t)((n_pts + 255) / 256) * tiles16 : (size_t)lowres_chunks(n_pts) * n_bands;
-  return sizeof(double) * ((size_t)n_bands + tiles16) * n_pts + sizeof(double) * (size_t)n_rays * n_part +
+  return sizeof(double) * n_tab * ((size_t)n_bands + tiles16) * n_pts + sizeof(double) * (size_t)n_rays * n_part +
          sizeof(int) * (2 * (size_t)n_bands + 2);
 }
 
 int launch_lowres_weights(int n_pts, int g_lo, double w0, double gstep, const double *cen, const double *wid, int n_bands,
-                          double n_sigma, void *scratch, hipStream_t st) {
+                          double n_sigma, void *scratch, hipStream_t st, bool instr) {
   if (n_bands <= 0) return 0;
-  const LowresScratch L = lowres_layout(scratch, n_pts, n_bands);
-  hipLaunchKernelGGL(sr_lowres_weights_kernel, dim3((n_pts + 255) / 256, (n_bands + 15) / 16 * 16), dim3(256), 0, st, n_pts, g_lo, w0,
-                     gstep, cen, wid, n_sigma, n_bands, L.W, L.range, L.Wt);
+  const LowresScratch L = lowres_layout(scratch, n_pts, n_bands, instr);
+  const dim3 grid((n_pts + 255) / 256, (n_bands + 15) / 16 * 16);
+  if (instr)
+    hipLaunchKernelGGL(sr_lowres_weights_kernel<true>, grid, dim3(256), 0, st, n_pts, g_lo, w0, gstep, cen, wid, n_sigma, n_bands, L.W,
+                       L.range, L.Wt);
+  else
+    hipLaunchKernelGGL(sr_lowres_weights_kernel<false>, grid, dim3(256), 0, st, n_pts, g_lo, w0, gstep, cen, wid, n_sigma, n_bands, L.W,
+                       L.range, L.Wt);
   return (int)hipGetLastError();
 }
 
-int launch_lowres_sum_blocks(int n_pts, int n_rows, int n_bands, int out_units, double *out, void *scratch, hipStream_t st) {
+int launch_lowres_sum_blocks(int n_pts, int n_rows, int n_bands, int out_units, double *out, void *scratch, hipStream_t st,
+                             bool instr) {
   if (n_bands <= 0 || n_rows <= 0) return 0;
-  const LowresScratch L = lowres_layout(scratch, n_pts, n_bands);
+  const LowresScratch L = lowres_layout(scratch, n_pts, n_bands, instr);
   hipLaunchKernelGGL(sr_lowres_sum_blocks_kernel, dim3(n_rows, (n_bands + 15) / 16), dim3(256), 0, st, L.part, L.range,
                      4 * ((n_pts + 255) / 256), n_bands, out_units, out);
   return (int)hipGetLastError();
@@ -5482,9 +5579,23 @@ int launch_lowres(const double *rad, int n_pts, int g_lo, int n_rays, double w0,
   const int n_chunks = lowres_chunks(n_pts);
   const LowresScratch L = lowres_layout(scratch, n_pts, n_bands);
   if (weights) launch_lowres_weights(n_pts, g_lo, w0, gstep, cen, wid, n_bands, n_sigma, scratch, st);
-  hipLaunchKernelGGL(sr_lowres_apply_kernel, dim3(n_rays, n_chunks, (n_bands + kLowresBands - 1) / kLowresBands), dim3(256), 0, st,
+  hipLaunchKernelGGL(sr_lowres_apply_kernel<1>, dim3(n_rays, n_chunks, (n_bands + kLowresBands - 1) / kLowresBands), dim3(256), 0, st,
                      rad, n_pts, L.W, L.range, n_bands, n_chunks, L.part);
   hipLaunchKernelGGL(sr_lowres_sum_kernel, dim3((n_rays * n_bands + 255) / 256), dim3(256), 0, st, L.part, n_rays, n_chunks, n_bands,
+                     out_units, out);
+  return (int)hipGetLastError();
+}
+
+// ... with the instrument derivatives: the scratch of an instr call with its three tables in place (launch_lowres_weights,
+// instr; sized for 3 n_rays rows); out [n_rays][3][n_bands]: the value, d / d centre, d / d ln width
+int launch_lowres_instr(const double *rad, int n_pts, int n_rays, int n_bands, int out_units, double *out, void *scratch,
+                        hipStream_t st) {
+  if (n_bands <= 0 || n_rays <= 0) return 0;
+  const int n_chunks = lowres_chunks(n_pts), n_rows = kLowresTables * n_rays;
+  const LowresScratch L = lowres_layout(scratch, n_pts, n_bands, true);
+  hipLaunchKernelGGL(sr_lowres_apply_kernel<kLowresTables>, dim3(n_rays, n_chunks, (n_bands + kLowresBands - 1) / kLowresBands), dim3(256), 0,
+                     st, rad, n_pts, L.W, L.range, n_bands, n_chunks, L.part);
+  hipLaunchKernelGGL(sr_lowres_sum_kernel, dim3((n_rows * n_bands + 255) / 256), dim3(256), 0, st, L.part, n_rows, n_chunks, n_bands,
                      out_units, out);
   return (int)hipGetLastError();
 }

@@ -286,7 +286,11 @@ int launch_limb_jac_state_bands(const double *abs_c, const double *emi_c, const 
                                 int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
                                 const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
                                 const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
-                                const int *slot_par, int n_par, const void *lowres_scratch, int n_bands, hipStream_t st);
+                                const int *slot_par, int n_par, const void *lowres_scratch, int n_bands, hipStream_t st,
+                                bool instr = false);
+// (instr: the kernel's INSTR = true instances -- the scratch of an instr call, three weight tables; every ray has two more
+// parameter rows in `part`, n_par and n_par + 1 of n_par + 2: the radiance's bands d / d centre and d / d ln width; n_par,
+// here the number of state parameters, may then be 0, with one block whose slots are all unused)
 // The same three for the level parameters of SEVERAL level-factored gases (the kernel's instances whose parameter pack
 // ends in a LevelGasTabs; batches of two to four gases): level gas k has the tables tab[k] with n_tab_rows[k] rows, is
 // gas gas[k] of the batch, and coef_row [n_lgas][n_layers] holds its row map at k n_layers.  The level slots are sorted
@@ -296,7 +300,8 @@ int launch_limb_jac_state_gases(const double *abs_c, const double *emi_c, const 
                                 int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
                                 const double *dcol, const LimbOpts &o, const LevelGasTabs &lg, const int *coef_row, int n_blocks,
                                 const int *blk, const int *ent_off, const LevelEnt *ent, const int *slot_par, int n_par,
-                                double *rad, double *jac, const void *lowres_scratch, int n_bands, hipStream_t st);
+                                double *rad, double *jac, const void *lowres_scratch, int n_bands, hipStream_t st,
+                                bool instr = false);
 // Radiance budget (sr_limb_parts_kernel): the n_part parts and the background are n_part + 1 slots in blocks of
 // limb_parts_np(n_part); slot_level [n_blocks][NP]: >= 0 the first row of a level's E plane in the pair tables,
 // (2 L + 1) n_tab_rows, -1 - g the gas part of gas g,
@@ -376,10 +381,14 @@ int launch_sum_lines(double *spe, long n_spe, const double *rows, const int *ini
 // scratch: lowres_scratch_bytes(...) of device memory (the bands' weight table and point ranges, then the chunks' partial
 // sums).  weights = false: the table and ranges at the head of `scratch` are those of an earlier call with the same
 // grid window and bands (a retrieval's instrument step: every iteration the same bands)
-size_t lowres_scratch_bytes(int n_pts, int n_bands, int n_rays, bool fused = false);
+// instr: the scratch carries the weight tables of the two instrument derivatives behind the weights (three tables in all)
+size_t lowres_scratch_bytes(int n_pts, int n_bands, int n_rays, bool fused = false, bool instr = false);
 int launch_lowres_weights(int n_pts, int g_lo, double w0, double gstep, const double *cen, const double *wid, int n_bands,
-                          double n_sigma, void *scratch, hipStream_t st);
-int launch_lowres_sum_blocks(int n_pts, int n_rows, int n_bands, int out_units, double *out, void *scratch, hipStream_t st);
+                          double n_sigma, void *scratch, hipStream_t st, bool instr = false);
+int launch_lowres_sum_blocks(int n_pts, int n_rows, int n_bands, int out_units, double *out, void *scratch, hipStream_t st,
+                             bool instr = false);
+int launch_lowres_instr(const double *rad, int n_pts, int n_rays, int n_bands, int out_units, double *out, void *scratch,
+                        hipStream_t st);
 int launch_lowres(const double *rad, int n_pts, int g_lo, int n_rays, double w0, double gstep, const double *cen,
                   const double *wid, int n_bands, double n_sigma, int out_units, double *out, void *scratch, hipStream_t st,
                   bool weights = true);

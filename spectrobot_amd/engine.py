@@ -559,17 +559,19 @@ class LevelFactored(object):
         return step_row, par_level, par_c
 
     def state_bands(self, coeffs, los, step_row, tvib, par_level, par_w_level, grid, centers_nm, widths_nm, par_gas=None,
-                    par_w_col=None, gas=0, q_part=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None):
+                    par_w_col=None, gas=0, q_part=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None,
+                    instrument=False):
         """state_jacobian on the instrument's bands in one library call (limb_rays_state_bands): numpy [n_rays | n_rays / 3,
         1 + n_par, n_bands], row 0 the radiance, row 1 + p the derivative to parameter p (VMR-profile, vibrational-
         temperature, kinetic-temperature parameters, as state_jacobian orders them); no hi-res spectrum is written.  The
         parameters' arguments and their errors are state_jacobian's; the bands' (and fov) those of limb_rays_state_bands.
-        Honours the object's spectral shard: partial band integrals then (`grid` is the whole grid)."""
+        Honours the object's spectral shard: partial band integrals then (`grid` is the whole grid).  instrument=True: the
+        two instrument rows behind the parameters' (limb_rays_state_bands)."""
         step_row, par_level, par_c = self._state_level_args(step_row, tvib, par_level, par_w_level, q_part)
         return limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=par_gas, par_w=par_w_col, tab=self.tab,
                                      coef_row=step_row, par_level=par_level, par_c=par_c, gas=gas, dcoeffs=dcoeffs,
                                      par_t=par_w_temp, out_units=out_units, n_sigma=n_sigma, fov=fov,
-                                     g_lo=int(self._shard[0]))
+                                     g_lo=int(self._shard[0]), instrument=instrument)
 
     def level_radiances(self, coeffs, los, step_row, tvib, levels=None, weights=None, gas=0, q_part=None, grid=None,
                         gas_parts=True):
@@ -653,14 +655,14 @@ class LevelFactoredSet(object):
                                         par_t=par_w_temp, level_gases=gases, par_lgas=par_lgas)
 
     def state_bands(self, coeffs, los, par_lgas, par_level, par_w_level, grid, centers_nm, widths_nm, par_gas=None,
-                    par_w_col=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None):
+                    par_w_col=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None, instrument=False):
         """LevelFactored.state_bands for the members' vibrational-temperature parameters together: numpy [n_rays | n_rays / 3,
-        1 + n_par, n_bands]."""
+        1 + n_par, n_bands]; instrument=True: [.., 1 + n_par + 2, n_bands], the two instrument rows last."""
         gases, par_lgas, par_level, par_c = self._args(par_lgas, par_level, par_w_level)
         return limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=par_gas, par_w=par_w_col,
                                      par_level=par_level, par_c=par_c, dcoeffs=dcoeffs, par_t=par_w_temp, out_units=out_units,
                                      n_sigma=n_sigma, fov=fov, g_lo=int(self.members[0][0]._shard[0]), level_gases=gases,
-                                     par_lgas=par_lgas)
+                                     par_lgas=par_lgas, instrument=instrument)
 
 
 def level_node_weights(nodes, alt):
@@ -1288,9 +1290,10 @@ def _level_gases_args(level_gases, par_lgas, tab, coef_row, par_level, par_c, n_
 
 
 def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t, level_gases=None,
-                par_lgas=None):
+                par_lgas=None, may_be_empty=False):
     """The arguments of a mixed-state call (limb_rays_state_jacobian, limb_rays_state_bands), checked and marshalled: the
-    one place where their shapes are refused."""
+    one place where their shapes are refused.  may_be_empty: a call that returns something without any parameter (the
+    bands call with its instrument rows)."""
     if (dcoeffs is None) != (par_t is None):
         raise ValueError("row parameters need both dcoeffs and par_t")
     a, e = _gas_stack(coeffs)
@@ -1325,9 +1328,9 @@ def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, ga
         if par_t.ndim != 2 or par_t.shape[1] != n_layers:
             raise ValueError("par_t must be [n_row, n_layers]")
         n_row = par_t.shape[0]
-        if n_col + n_lev + n_row == 0:
+        if n_col + n_lev + n_row == 0 and not may_be_empty:
             raise ValueError("no parameters: give column parameters, level parameters or row parameters")
-    elif n_col + n_lev == 0:
+    elif n_col + n_lev == 0 and not may_be_empty:
         raise ValueError("no parameters: give column parameters, level parameters or both")
     A = _StateArgs()
     A.a, A.e, A.desc, A.n_col, A.n_lev, A.n_row, A.n_par = a, e, d, n_col, n_lev, n_row, n_col + n_lev + n_row
@@ -1345,7 +1348,7 @@ def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, ga
 
 def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None, par_w=None, tab=None, coef_row=None,
                           par_level=None, par_c=None, gas=0, dcoeffs=None, par_t=None, out_units="Wm2", n_sigma=5.0, fov=None,
-                          g_lo=0, level_gases=None, par_lgas=None):
+                          g_lo=0, level_gases=None, par_lgas=None, instrument=False):
     """limb_rays_state_jacobian on the instrument's bands in ONE library call (sr_limb_rays_state_bands_dev): the same
     mixed state vector (column, level, row parameters: the same arguments, the same errors), but no hi-res spectrum is
     written -- the recursion kernel integrates the bands in its epilogue.  Returns numpy [n_rays | n_rays / 3, 1 + n_par,
@@ -1354,9 +1357,14 @@ def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None
     up to the order of the band sums.  fov: fov_factors of the pixels, three rays each.  A spectral shard (g_lo, the
     coefficient tables' width; `grid` is always the whole grid) gives its partial band integrals, as hires_to_lowres.
     level_gases / par_lgas: several level-factored gases, as in limb_rays_state_jacobian
-    (sr_limb_rays_state_bands_gases_dev)."""
+    (sr_limb_rays_state_bands_gases_dev).
+    instrument=True (sr_limb_rays_state_bands_instr[_gases]_dev): two more rows behind the parameters', [.., 1 + n_par + 2,
+    n_bands]: the derivatives of the radiance's bands to the band centre (per nm) and to the logarithm of the ILS width, as
+    hires_to_lowres_instrument defines them (window membership held fixed); rows 0 .. n_par are those of the call without
+    them, bit for bit, and there may then be no parameter at all."""
+    instrument = bool(instrument)
     A = _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t, level_gases,
-                    par_lgas)
+                    par_lgas, may_be_empty=instrument)
     n_pts = A.a.shape[2]
     w0, step, n = grid_params(grid)
     A.desc.w0, A.desc.step = w0, step   # (the grid of the bands; with a Planck background desc() has set the same)
@@ -1372,7 +1380,12 @@ def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None
         if los.n_rays % 3 or fov.shape != (los.n_rays // 3, 7):
             raise ValueError("fov must be [n_rays / 3, 7] (three rays per pixel)")
         n_out = los.n_rays // 3
-    out = np.empty((n_out, 1 + A.n_par, centers_nm.size))
+    out = np.empty((n_out, 1 + A.n_par + (2 if instrument else 0), centers_nm.size))
+    if instrument:
+        name = "sr_limb_rays_state_bands_instr_gases_dev" if level_gases is not None else "sr_limb_rays_state_bands_instr_dev"
+        check(getattr(lib, name)(*(A.head_gases if level_gases is not None else A.head), cp, wp, centers_nm.size, float(n_sigma),
+                                 _UNITS[out_units], fp, out.ctypes.data_as(dp), _stream_ptr()), name)
+        return out
     if level_gases is not None:
         check(lib.sr_limb_rays_state_bands_gases_dev(*A.head_gases, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp,
                                                      out.ctypes.data_as(dp), _stream_ptr()), "sr_limb_rays_state_bands_gases_dev")
@@ -1652,13 +1665,9 @@ def set_far_field(on):
 _UNITS = {"Wm2": 0, "ergscm2": 1, "nWcm2": 2}
 
 
-def hires_to_lowres(rad, grid, centers_nm, widths_nm, out_units="Wm2", n_sigma=5.0, g_lo=None):
-    """Gaussian-ILS degradation of hi-res spectra (CUDA float64 [n_rays, n_grid], 'ergscm2' on the
-    cm-1 grid) onto low-resolution bands given in nm: SpectralIntensity.hires_to_lowres
-    (spect_classes.py:1180-1191).  Returns numpy [n_rays, n_bands] in out_units.
-    g_lo given: rad holds the grid points g_lo .. g_lo + rad.shape[-1] - 1 only (a spectral shard) and the PARTIAL band
-    integrals over them are returned (sr_hires_to_lowres_shard_dev); `grid` is always the whole grid.  Without g_lo
-    the spectrum must cover the whole grid (a mis-sized spectrum is an error, not a partial integral)."""
+def _lowres_call(entry, n_tab, rad, grid, centers_nm, widths_nm, out_units, n_sigma, g_lo):
+    """The instrument step's arguments, checked and marshalled once for its two entry points: returns numpy
+    [n_rays, n_tab, n_bands] as `entry` (sr_hires_to_lowres_shard_dev: n_tab 1; sr_hires_to_lowres_instr_shard_dev: 3) fills it."""
     w0, step, n = grid_params(grid)
     n_sh = rad.shape[-1]
     if g_lo is None:
@@ -1671,11 +1680,32 @@ def hires_to_lowres(rad, grid, centers_nm, widths_nm, out_units="Wm2", n_sigma=5
     widths_nm, wp = _d(widths_nm)
     if widths_nm.size != centers_nm.size:
         raise ValueError("{} spectral widths for {} grid points".format(widths_nm.size, centers_nm.size))
-    out = np.zeros((rad2.shape[0], centers_nm.size))
-    check(lib.sr_hires_to_lowres_shard_dev(C.c_void_p(rad2.data_ptr()), rad2.shape[0], n_sh, int(g_lo), w0, step, cp, wp,
-                                           centers_nm.size, float(n_sigma), _UNITS[out_units], out.ctypes.data_as(dp),
-                                           _stream_ptr()), "sr_hires_to_lowres_shard_dev")
+    out = np.zeros((rad2.shape[0], n_tab, centers_nm.size))
+    check(getattr(lib, entry)(C.c_void_p(rad2.data_ptr()), rad2.shape[0], n_sh, int(g_lo), w0, step, cp, wp, centers_nm.size,
+                              float(n_sigma), _UNITS[out_units], out.ctypes.data_as(dp), _stream_ptr()), entry)
     return out
+
+
+def hires_to_lowres(rad, grid, centers_nm, widths_nm, out_units="Wm2", n_sigma=5.0, g_lo=None):
+    """Gaussian-ILS degradation of hi-res spectra (CUDA float64 [n_rays, n_grid], 'ergscm2' on the
+    cm-1 grid) onto low-resolution bands given in nm: SpectralIntensity.hires_to_lowres
+    (spect_classes.py:1180-1191).  Returns numpy [n_rays, n_bands] in out_units.
+    g_lo given: rad holds the grid points g_lo .. g_lo + rad.shape[-1] - 1 only (a spectral shard) and the PARTIAL band
+    integrals over them are returned (sr_hires_to_lowres_shard_dev); `grid` is always the whole grid.  Without g_lo
+    the spectrum must cover the whole grid (a mis-sized spectrum is an error, not a partial integral)."""
+    return _lowres_call("sr_hires_to_lowres_shard_dev", 1, rad, grid, centers_nm, widths_nm, out_units, n_sigma, g_lo)[:, 0]
+
+
+def hires_to_lowres_instrument(rad, grid, centers_nm, widths_nm, out_units="Wm2", n_sigma=5.0, g_lo=None):
+    """hires_to_lowres with the two instrument derivatives of every band (sr_hires_to_lowres_instr_shard_dev): returns
+    (low, dlow_dcentre, dlow_dlnwidth), numpy [n_rays, n_bands] each -- the band values (hires_to_lowres's, bit for bit),
+    their derivatives to a shift of the band centre (per nm) and to the logarithm of the ILS width,
+        d low_b / d delta = k sum_i s_i W_i t_i / w_b,     d low_b / d eta = k sum_i s_i W_i (t_i^2 - 1),
+    t_i = (x_i - f_b) / w_b, with the window's membership held fixed (it is piecewise constant in f and w; a jump is of
+    relative size exp(-n_sigma^2 / 2)).  Any parametrisation of the centres and widths is a chain rule on these rows.
+    Arguments as hires_to_lowres; a shard (g_lo) returns partial sums that add up over the shards."""
+    out = _lowres_call("sr_hires_to_lowres_instr_shard_dev", 3, rad, grid, centers_nm, widths_nm, out_units, n_sigma, g_lo)
+    return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
 
 
 def set_table_budget(n_bytes):

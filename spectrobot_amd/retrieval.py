@@ -137,6 +137,58 @@ class TempProfile(smm.LinearProfile_1D_new):
             par.constrain_positive = False
 
 
+INSTR_SET = "instr"    # the name of the retrieval set of the instrument's band calibration (BandCalibration)
+
+
+class BandCalibration(smm.RetSet):
+    """The retrieval set of the instrument's band calibration, named "instr": up to three scalar parameters,
+        shift     (nm)  every band centre moves by it
+        slope     (-)   the shift per nm of distance from the mean band centre
+        ln_width  (-)   the logarithm of a common factor on the ILS widths
+    so that bands_nm = bands_nm0 + shift + slope (bands_nm0 - mean(bands_nm0)) and widths_nm = widths_nm0 exp(ln_width).
+    Each is switched on by giving it (apriori, apriori_err) or (apriori, apriori_err, first_guess); a parameter left None
+    is not retrieved and stands at 0.  No parameter is constrained positive.  The Jacobian columns come from the two
+    instrument rows of the band integrals (engine.hires_to_lowres_instrument: d / d centre, d / d ln width, the windows'
+    membership held fixed) by the chain rule, jacobian_rows."""
+    KEYS = ("shift", "slope", "ln_width")
+
+    def __init__(self, shift=None, slope=None, ln_width=None):
+        self.name, self.set = INSTR_SET, []
+        mask = smm.GridMask([0.0], [1.0], 'box')    # (a scalar: nothing to mask)
+        for key, spec in zip(self.KEYS, (shift, slope, ln_width)):
+            if spec is None:
+                continue
+            spec = tuple(float(v) for v in spec)
+            if len(spec) not in (2, 3):
+                raise ValueError("%s must be (apriori, apriori_err) or (apriori, apriori_err, first_guess)" % key)
+            self.set.append(smm.RetParam(INSTR_SET, key, mask, spec[0], spec[1], first_guess=spec[2] if len(spec) == 3 else None,
+                                         constrain_positive=False))
+        if not self.set:
+            raise ValueError("a BandCalibration with no parameter switched on")
+        self.n_par = len(self.set)
+
+    def value(self, key):
+        """The current value of shift / slope / ln_width; 0 for one that is switched off."""
+        return float(sum(p.value for p in self.set if p.key == key))
+
+    def bands(self, bands_nm0, widths_nm0):
+        """(bands_nm, widths_nm) of the current parameters from the nominal ones."""
+        b0, w0 = np.asarray(bands_nm0, float), np.asarray(widths_nm0, float)
+        return b0 + self.value("shift") + self.value("slope") * (b0 - b0.mean()), w0 * np.exp(self.value("ln_width"))
+
+    def jacobian_rows(self, bands_nm0, d_centre, d_lnwidth):
+        """The derivatives of band values [..., n_bands] to the set's parameters, [..., n_par, n_bands] in the set's order,
+        from their derivatives to the band centres (per nm) and to the logarithm of the widths: the chain rule of bands()."""
+        b0 = np.asarray(bands_nm0, float)
+        rows = dict(shift=d_centre, slope=d_centre * (b0 - b0.mean()), ln_width=d_lnwidth)
+        return np.stack([np.asarray(rows[p.key], float) for p in self.set], axis=-2)
+
+
+def _refuse_instr(bayes_set, who):
+    if bayes_set is not None and INSTR_SET in getattr(bayes_set, "sets", {}):
+        raise ValueError("%s does not take the retrieval set %r (BandCalibration): use inversion_state" % (who, INSTR_SET))
+
+
 class StateWeights(object):
     """LimbScene.state_weights' result: the column block (par_gas [n_col], par_w_col [n_col, n_pt]), the level block
     (level_gas: the LevelGas or None, gas: its index, par_level [n_lev], par_w_lev [n_lev, n_layers]), the row block
@@ -179,6 +231,7 @@ class LimbScene(object):
         self.nd = syn.number_density(self.press, self.temps)
         self.gases = list(gases)
         self.bands_nm, self.widths_nm = np.asarray(bands_nm, float), np.asarray(widths_nm, float)
+        self.bands_nm0, self.widths_nm0 = self.bands_nm.copy(), self.widths_nm.copy()   # the nominal calibration (BandCalibration)
         self.R, self.n_sub, self.out_units = R, n_sub, out_units
 
     def gas(self, name):
@@ -269,7 +322,9 @@ class LimbScene(object):
         likewise.  Returns a StateWeights (its perm leads back to BayesSet order).
         several_level_gases=True: Tvib sets of any number of LevelGas (the calls with level_gases take them in one pass);
         the level block then holds them all in BayesSet order, StateWeights.level_gases / gases / par_lgas say whose each
-        is, level_gas / gas are the first one's.  With one LevelGas the result is the same either way."""
+        is, level_gas / gas are the first one's.  With one LevelGas the result is the same either way.
+        The set named "instr" (BandCalibration) is accepted and has no part in any block: perm then covers the other sets'
+        parameters alone, in BayesSet order."""
         names = [g.name for g in self.gases]
         top = self.z[-1] + (self.z[-1] - self.z[-2])
         zz = np.append(self.z, top)
@@ -277,6 +332,8 @@ class LimbScene(object):
         level_gas, level_gases, par_lgas = None, [], []
         for name in bayes_set.order:
             st = bayes_set.sets[name]
+            if name == INSTR_SET and name not in names:
+                continue
             if name in names:
                 for par in st.set:
                     m = np.asarray(par.maskgrid.mask, dtype=float)
@@ -518,7 +575,11 @@ def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, re
     off quadratic splines in tangent altitude (smm.make_radtran_spline) before the FOV integration.
 
     track_levels / full_output (simulation only: bayes_set None): returns (sims, radtrans, single_rads) as the
-    reference's radtrans (spect_main_module.py:3287) -- see radtrans below."""
+    reference's radtrans (spect_main_module.py:3287) -- see radtrans below.
+
+    A bayes_set with the "instr" set (BandCalibration) is refused: the one-call forward model behind this function
+    (sr_retrieval_forward_dev, and the step and loop calls built on it) has no instrument rows; inversion_state has."""
+    _refuse_instr(bayes_set, "simulate (sr_retrieval_forward_dev / _step_dev / _loop_dev)")
     if track_levels is not None or full_output:
         if bayes_set is not None or arrays:
             raise ValueError("the radiance budget (track_levels / full_output) is a simulation: no bayes_set, no arrays")
@@ -633,6 +694,7 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
     Returns (chi, obs, sims, bayes_set) like the reference, plus .history on bayes_set (chi per iteration)
     and .stop ('converged' | 'raised' | 'max_it').  shard / refresh: see simulate (every rank of a multi-GPU run
     calls this with its own spectral shard; all ranks hold the same chi square history and parameters)."""
+    _refuse_instr(bayes_set, "inversion_fast_limb")
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)                       # :2607
     group = (alt_step_sims, alt_first_los) if group_observations else None     # :2668-2670
     for name in bayes_set.sets.keys():                                         # :2624-2625
@@ -770,12 +832,16 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
 def _state_into_gases(scene, bayes_set):
     """The BayesSet's profiles into the gases: add_clim for the VMR sets, tvib = tvib0 + offset for the Tvib sets; the
     "temp" set into the scene, temps = temps0 + offset (temps0: the temperatures at the first such call; the number
-    densities and the LOS columns stay as they are, see TempProfile)."""
+    densities and the LOS columns stay as they are, see TempProfile); the "instr" set into the scene's bands,
+    bands_nm = bands_nm0 + shift + slope (bands_nm0 - mean), widths_nm = widths_nm0 exp(ln_width)."""
     names, tvib = [g.name for g in scene.gases], {}
     for name in bayes_set.order:
         st = bayes_set.sets[name]
         if name in names:
             scene.gas(name).add_clim(st.profile())
+            continue
+        if name == INSTR_SET:
+            scene.bands_nm, scene.widths_nm = st.bands(scene.bands_nm0, scene.widths_nm0)
             continue
         if name == "temp":
             if getattr(scene, "temps0", None) is None:
@@ -805,7 +871,12 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     inversion_fast_limb.  Every pixel has the closed-form field of view, or none has a field of view.
     bands_in_kernel=True: the Jacobian call, the instrument bands and the field of view of an iteration are ONE library call
     (LevelFactored.state_bands / engine.limb_rays_state_bands): the recursion kernel integrates the bands itself and no
-    hi-res radiance or Jacobian is written.  The same numbers up to the order of the band sums (1e-12 relative)."""
+    hi-res radiance or Jacobian is written.  The same numbers up to the order of the band sums (1e-12 relative).
+    A set named "instr" (BandCalibration: band shift, its slope over the bands, ILS width) is retrieved with the profiles:
+    per iteration its values go into scene.bands_nm / widths_nm, the two instrument rows of the band integrals come from
+    the same fused call (instrument=True) or, on the other route, from engine.hires_to_lowres_instrument on the radiance
+    the Jacobian call wrote, and the set's Jacobian columns follow by the chain rule (BandCalibration.jacobian_rows); they
+    stand where the set stands in the BayesSet.  Without such a set nothing changes."""
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)
     with_fov = sum(pix.fov_half > 0 for pix in pixels)
     if not (with_fov == 0 or (with_fov == len(pixels) and fov_closed_form)):
@@ -824,11 +895,25 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     lowres = lambda r: engine.hires_to_lowres(r, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units)
     rots = [pix.pixel_rot for pix in pixels]
     bayes_set.history, bayes_set.stop = [], 'max_it'
+    instr = bayes_set.sets.get(INSTR_SET) if INSTR_SET not in [g.name for g in scene.gases] else None
+    is_instr = np.array([instr is not None and par.nameset == INSTR_SET for par in bayes_set.params()], dtype=bool)
+
+    def with_instr(fov_rows, n_prof):
+        """[n_pix, 1 + n_prof + 2, n_bands] (radiance, profile parameters in BayesSet order, d / d centre, d / d ln width)
+        -> [n_pix, 1 + n_tot, n_bands] in BayesSet order, the set's columns by the chain rule."""
+        out = np.empty((fov_rows.shape[0], 1 + is_instr.size, fov_rows.shape[2]))
+        out[:, 0] = fov_rows[:, 0]
+        out[:, 1:][:, ~is_instr] = fov_rows[:, 1:1 + n_prof]
+        out[:, 1:][:, is_instr] = instr.jacobian_rows(scene.bands_nm0, fov_rows[:, 1 + n_prof], fov_rows[:, 2 + n_prof])
+        return out
 
     def wrap(v):
         sp = Spectrum.__new__(Spectrum)
-        sp.spectrum, sp.spectral_grid = np.array(v), grid_lo
+        # (an "instr" set moves the band centres: the spectra carry those they were simulated on, the last iteration's)
+        sp.spectrum, sp.spectral_grid = np.array(v), grid_lo if instr is None else grid_sim[0]
         return sp
+
+    grid_sim = [grid_lo]
 
     def finish(low, dlow):
         if low is None:                                            # (max_it = 0: nothing was simulated)
@@ -846,6 +931,8 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     for num_it in range(max_it):
         coeffs = None if with_temp else scene.coefficient_stack()
         los, alt = scene.los(alts)
+        if instr is not None:
+            grid_sim[0] = _Grid(scene.bands_nm.copy())                 # the centres this iteration simulates on
         w = scene.state_weights(bayes_set, alt, several_level_gases=True)
         # with_temp: coefficients at the current temperatures and their derivatives, then all three kinds at once
         dcoeffs = None
@@ -858,6 +945,8 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             lfs = engine.LevelFactoredSet([(g.lf, i, g.rows, g.tvib) for g, i in zip(w.level_gases, w.gases)])
         if bands_in_kernel:    # Jacobians, instrument bands and field of view in one call: [n_pix | n_los, 1 + n_par, n_bands]
             band_args = dict(out_units=scene.out_units, fov=engine.fov_factors(rots) if with_fov else None)
+            if instr is not None:
+                band_args["instrument"] = True
             if lfs is not None:
                 both = lfs.state_bands(coeffs, los, w.par_lgas, w.par_level, w.par_w_lev, scene.grid, scene.bands_nm,
                                        scene.widths_nm, par_gas=w.par_gas, par_w_col=w.par_w_col, dcoeffs=dcoeffs,
@@ -869,11 +958,13 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
                 both = lg.lf.state_bands(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, scene.grid, scene.bands_nm,
                                          scene.widths_nm, par_gas=w.par_gas, par_w_col=w.par_w_col, gas=w.gas, dcoeffs=dcoeffs,
                                          par_w_temp=par_w_temp, **band_args)
-            n_par = both.shape[1] - 1
+            n_par = both.shape[1] - 1 - (0 if instr is None else 2)
             fov = both if with_fov else both[1::3]
-            fov = np.concatenate([fov[:, :1, :], fov[:, 1:, :][:, w.perm]], axis=1)
+            fov = np.concatenate([fov[:, :1, :], fov[:, 1:1 + n_par, :][:, w.perm], fov[:, 1 + n_par:, :]], axis=1)
         else:                  # (one level gas or none: the calls as they always were -- without a temperature set no call names row parameters)
-            if lfs is not None:
+            if instr is not None and len(w.perm) == 0:    # the instrument set alone: the radiances, no Jacobian call
+                rad, jac = engine.limb_rays(coeffs, los, resident=False), None
+            elif lfs is not None:
                 rad, jac = lfs.state_jacobian(coeffs, los, w.par_lgas, w.par_level, w.par_w_lev, par_gas=w.par_gas,
                                               par_w_col=w.par_w_col, dcoeffs=dcoeffs, par_w_temp=par_w_temp)
             elif with_temp and lg is None:
@@ -887,10 +978,17 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             else:
                 rad, jac = lg.lf.state_jacobian(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, par_gas=w.par_gas,
                                                 par_w_col=w.par_w_col, gas=w.gas)
-            n_par = jac.shape[1]
-            both = np.concatenate([lowres(rad)[:, None, :],
-                                   lowres(jac.view(n_los * n_par, -1)).reshape(n_los, n_par, -1)[:, w.perm]], axis=1)
+            n_par = 0 if jac is None else jac.shape[1]
+            rows = [] if jac is None else [lowres(jac.view(n_los * n_par, -1)).reshape(n_los, n_par, -1)[:, w.perm]]
+            if instr is None:
+                both = np.concatenate([lowres(rad)[:, None, :]] + rows, axis=1)
+            else:      # the instrument step once more on the radiance, with its two derivative rows (row 0: lowres(rad))
+                three = engine.hires_to_lowres_instrument(rad, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units)
+                both = np.concatenate([three[0][:, None, :]] + rows + [three[1][:, None, :], three[2][:, None, :]], axis=1)
             fov = smm.fov_closed_form(both[0::3], both[1::3], both[2::3], rots) if with_fov else both[1::3]
+        if instr is not None:
+            fov = with_instr(fov, n_par)
+            n_par = is_instr.size
         low, dlow = fov[:, 0, :], fov[:, 1:, :]
         for par in bayes_set.params():
             par.set_used()
@@ -957,6 +1055,7 @@ def inversion(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM
     n_tot parameters (:2562 -- the fast loop uses the parameters in use), the same stopping rule and
     inversion_algebra.  Coefficients through look-up tables (useLUTs, lut_coefficients) or directly.  Like the
     reference it returns None: the result is the state of bayes_set (.history, .stop are added)."""
+    _refuse_instr(bayes_set, "inversion")
     LUTopt = dict(LUTopt or {})
     for name in bayes_set.sets.keys():                                                    # :2445-2446
         scene.gas(name).add_clim(bayes_set.sets[name].profile())

@@ -22,7 +22,7 @@ out.append(between(ker, "__device__ inline double limb_initial(", "// Block -> (
 out.append(between(ker, "__device__ inline bool limb_block(", "__host__ inline unsigned limb_grid"))
 out.append(between(ker, "template <int NG>\n__device__ __forceinline__ void limb_load_coef", "template <int NG>\n__global__ __launch_bounds__(256) void sr_limb_kernel"))
 out.append(between(ker, "struct FoldBands {", "// Derivatives w.r.t. LEVEL parameters"))
-out.append(between(ker, "template <int NG, int NP, bool COLS, bool ROWS, bool BANDS, class... RowSpectra>", "// The radiance budget of a ray batch"))
+out.append(between(ker, "template <int NG, int NP, bool COLS, bool ROWS, bool BANDS, bool INSTR, class... RowSpectra>", "// The radiance budget of a ray batch"))
 txt = "\n".join(out)
 txt = re.sub(r'if constexpr \(COLS\) asm volatile\(""[^;]*;', "", txt)
 open(os.path.join(out_dir, "kernel_text.inc"), "w").write(txt)

@@ -3,7 +3,9 @@
 // exact division for the reciprocal.  Every case runs the BANDS = false and the BANDS = true instance on the same inputs
 // and reads the partial sums as sr_lowres_sum_blocks_kernel does (`part` starts as NaN: a slot that is read must have
 // been written): |fused - sum_j spectrum_j W_j| <= 1e-12 of the row's largest band, exact zeros for all-zero spectra and
-// the band outside the grid.  Built with AddressSanitizer and UBSan by run.sh: indexing, plan, tile and row mapping on a
+// the band outside the grid.  Then the INSTR = true instance with two more weight tables behind the first (further band
+// tiles of Wt) and two more parameter rows per ray: its value and parameter rows must be the BANDS instance's bit for bit,
+// its two instrument rows the plain sums of the radiance with tables 1 and 2 -- also for no parameter at all.  Built with AddressSanitizer and UBSan by run.sh: indexing, plan, tile and row mapping on a
 // machine without a GPU -- not the compiled gfx950 code.
 #include <algorithm>
 #include <cmath>
@@ -118,6 +120,14 @@ static int run_case(int n_pts, int n_col, int n_lev, int n_row, int n_bands, int
     range[2 * b] = r0; range[2 * b + 1] = r1;
     for (int j = r0; j < r1; ++j) Wt[((size_t)(b >> 4) * n_pts + j) * 16 + (b & 15)] = 0.1 + U(rng);
   }
+  // the instrument tables: tables 1 and 2 behind the weights, on the same ranges
+  std::vector<double> Wt3((size_t)3 * n_tiles * n_pts * 16, 0.0);
+  std::copy(Wt.begin(), Wt.end(), Wt3.begin());
+  for (int k = 1; k < 3; ++k)
+    for (int b = 0; b < n_bands; ++b)
+      for (int j = range[2 * b]; j < range[2 * b + 1]; ++j) Wt3[((size_t)(k * n_tiles + (b >> 4)) * n_pts + j) * 16 + (b & 15)] = U(rng) - 0.5;
+  const int n_par3 = n_par + 2;
+  std::vector<double> part3((size_t)n_rays * (1 + n_par3) * n_slots * n_tiles * 16, NAN);
   const int n_rows_out = n_rays * (1 + n_par);
   std::vector<double> rad((size_t)n_rays * n_pts, NAN), jac((size_t)n_rays * n_par * n_pts, NAN);
   std::vector<double> part((size_t)n_rows_out * n_slots * n_tiles * 16, NAN);
@@ -126,12 +136,21 @@ static int run_case(int n_pts, int n_col, int n_lev, int n_row, int n_bands, int
   auto go = [&](auto np) {
     constexpr int NP = decltype(np)::value;
     const FoldBands bd{Wt.data(), range.data(), part.data(), n_bands};
+    const FoldBands bd3{Wt3.data(), range.data(), part3.data(), n_bands};
+    if constexpr (ROWS)
+      launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, true, true, true, const double *, const double *>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, gas, tab.data(), n_tab_rows, coef_row.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), n_par3, nullptr, bd3, pda, pde); });
+    else
+      launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, false, true, true>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, gas, tab.data(), n_tab_rows, coef_row.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), n_par3, nullptr, bd3); });
+    if (n_par == 0) { // no parameter: there is no other instance to compare with; the radiance from the one-slot-free state call
+      launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, false, false, false>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, gas, tab.data(), n_tab_rows, coef_row.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), n_par, rad.data(), jac.data()); });
+      return;
+    }
     if constexpr (ROWS) {
-      launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, true, false, const double *, const double *>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, gas, tab.data(), n_tab_rows, coef_row.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), n_par, rad.data(), jac.data(), pda, pde); });
-      launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, true, true, const double *, const double *>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, gas, tab.data(), n_tab_rows, coef_row.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), n_par, nullptr, bd, pda, pde); });
+      launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, true, false, false, const double *, const double *>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, gas, tab.data(), n_tab_rows, coef_row.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), n_par, rad.data(), jac.data(), pda, pde); });
+      launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, true, true, false, const double *, const double *>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, gas, tab.data(), n_tab_rows, coef_row.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), n_par, nullptr, bd, pda, pde); });
     } else {
-      launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, false, false>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, gas, tab.data(), n_tab_rows, coef_row.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), n_par, rad.data(), jac.data()); });
-      launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, false, true>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, gas, tab.data(), n_tab_rows, coef_row.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), n_par, nullptr, bd); });
+      launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, false, false, false>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, gas, tab.data(), n_tab_rows, coef_row.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), n_par, rad.data(), jac.data()); });
+      launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, false, true, false>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, gas, tab.data(), n_tab_rows, coef_row.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), n_par, nullptr, bd); });
     }
   };
   if (level_jac_np(n_par) == 16) go(std::integral_constant<int, 16>{});
@@ -139,7 +158,7 @@ static int run_case(int n_pts, int n_col, int n_lev, int n_row, int n_bands, int
   // the sum kernel's reading of `part`, and the plain band sums of the hi-res spectra
   int bad = 0, zeros = 0, nonfinite = 0;
   double worst = 0.0;
-  for (int ray = 0; ray < n_rays; ++ray)
+  for (int ray = 0; ray < (n_par > 0 ? n_rays : 0); ++ray) // (no parameter: only the INSTR instance ran)
     for (int q = 0; q <= n_par; ++q) {
       const size_t row = q == 0 ? (size_t)ray : (size_t)n_rays + (size_t)ray * n_par + (q - 1);
       const double *sp = q == 0 ? &rad[(size_t)ray * n_pts] : &jac[((size_t)ray * n_par + (q - 1)) * n_pts];
@@ -165,6 +184,41 @@ static int run_case(int n_pts, int n_col, int n_lev, int n_row, int n_bands, int
         if ((b == 0) && f[b] != 0.0) ++bad;
       }
     }
+  // the INSTR instance: value and parameter rows bit for bit, the two instrument rows against plain sums of the radiance
+  int bad3 = 0;
+  double worst3 = 0.0;
+  for (int ray = 0; ray < n_rays; ++ray)
+    for (int q = 0; q <= n_par3; ++q) {
+      const size_t row3 = q == 0 ? (size_t)ray : (size_t)n_rays + (size_t)ray * n_par3 + (q - 1);
+      const size_t row = q == 0 ? (size_t)ray : (size_t)n_rays + (size_t)ray * n_par + (q - 1);
+      const int k = q - n_par; // 1, 2: the instrument rows
+      const double *sp = &rad[(size_t)ray * n_pts];
+      double scale = 0.0;
+      std::vector<double> f(n_bands), u(n_bands);
+      for (int b = 0; b < n_bands; ++b) {
+        const int r0 = range[2 * b], r1 = range[2 * b + 1], tile = b >> 4, c16 = b & 15;
+        double v = 0.0, w = 0.0;
+        if (r1 > r0)
+          for (int c = r0 >> 6; c <= (r1 - 1) >> 6; ++c) {
+            const double x = part3[((row3 * n_slots + c) * n_tiles + tile) * 16 + c16];
+            v += x;
+            if (k <= 0 && n_par > 0 && std::memcmp(&x, &part[((row * n_slots + c) * n_tiles + tile) * 16 + c16], sizeof x) != 0) ++bad3;
+          }
+        if (k > 0 || n_par == 0)
+          for (int j = 0; j < n_pts; ++j) w = std::fma(sp[j], Wt3[((size_t)(std::max(k, 0) * n_tiles + tile) * n_pts + j) * 16 + c16], w);
+        f[b] = v; u[b] = w;
+        scale = std::max(scale, std::fabs(w));
+        if (!std::isfinite(v)) ++nonfinite;
+      }
+      if (k > 0 || n_par == 0)
+        for (int b = 0; b < n_bands; ++b) {
+          const double d = std::fabs(f[b] - u[b]) / (scale > 0 ? scale : 1.0);
+          worst3 = std::max(worst3, d);
+          if (!(d <= 1e-12) || (b == 0 && f[b] != 0.0) || (b == 1 && f[b] == 0.0 && solo == 0)) ++bad3;
+        }
+    }
+  std::printf("  with the instrument rows: worst %.2e, bad %d\n", worst3, bad3);
+  bad += bad3;
   std::printf("NG %d COLS %d ROWS %d n_pts %d pars %d+%d+%d bands %d init %d solo %d: worst %.2e, exact-zero entries %d, non-finite %d, bad %d\n",
               NG, (int)COLS, (int)ROWS, n_pts, n_col, n_lev, n_row, n_bands, init_mode, solo, worst, zeros, nonfinite, bad);
   return bad + nonfinite;
@@ -180,6 +234,7 @@ int main() {
   bad += run_case<1, false, false>(257, 0, 17, 0, 7, 2, 1, 6);
   bad += run_case<2, true, true>(300, 5, 12, 3, 37, 0, 0, 7);
   bad += run_case<3, true, true>(700, 5, 12, 3, 20, 2, 0, 8);
+  bad += run_case<1, false, false>(257, 0, 0, 0, 20, 0, 0, 9);   // no parameter: the radiance and the instrument rows alone
   std::printf(bad ? "FAILED\n" : "all cases agree\n");
   return bad != 0;
 }

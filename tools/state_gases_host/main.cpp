@@ -119,15 +119,15 @@ static int run_case(int n_pts, int n_col, std::vector<int> levs, int n_row, int 
       constexpr int NP = decltype(np)::value;
       if (k_only < 0) {
         if constexpr (ROWS)
-          launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, true, false, const double *, const double *, LevelGasTabs>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, -1, nullptr, 0, rows.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), np_all, rad.data(), jac.data(), pda, pde, T); });
+          launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, true, false, false, const double *, const double *, LevelGasTabs>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, -1, nullptr, 0, rows.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), np_all, rad.data(), jac.data(), pda, pde, T); });
         else
-          launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, false, false, LevelGasTabs>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, -1, nullptr, 0, rows.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), np_all, rad.data(), jac.data(), T); });
+          launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, false, false, false, LevelGasTabs>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, -1, nullptr, 0, rows.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), np_all, rad.data(), jac.data(), T); });
       } else {
         const int k = k_only;
         if constexpr (ROWS)
-          launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, true, false, const double *, const double *>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, lgas_gas[k], tabs[k].data(), n_tab[k], rows.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), np_all, rad.data(), jac.data(), pda, pde); });
+          launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, true, false, false, const double *, const double *>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, lgas_gas[k], tabs[k].data(), n_tab[k], rows.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), np_all, rad.data(), jac.data(), pda, pde); });
         else
-          launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, false, false>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, lgas_gas[k], tabs[k].data(), n_tab[k], rows.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), np_all, rad.data(), jac.data()); });
+          launch(gx, P.n_blocks, [&] { sr_limb_jac_state_kernel<NG, NP, COLS, false, false, false>(a.data(), e.data(), n_pts, n_layers, seg_off.data(), seg_layer.data(), col.data(), dcol.data(), o, n_rays, lgas_gas[k], tabs[k].data(), n_tab[k], rows.data(), blk, P.ent_off.data(), ent.data(), P.slot_par.data(), np_all, rad.data(), jac.data()); });
       }
     };
     if (level_jac_np(np_all) == 16) go(std::integral_constant<int, 16>{});
