@@ -3402,122 +3402,148 @@ static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev,
   return P;
 }
 
-// What the entries below do once their arguments are checked: plan, stage, launch, mark.  cols: the kernel instance
-// with column slots (the state call, with n_col == 0 too); without it n_col is 0 and neither blk nor dcol exists.
-// n_row > 0 (sr_limb_rays_jac_state_rows_dev): the instances with row slots, which read dabs / demi.
-// band_scratch (sr_limb_rays_state_bands_dev): the instrument step's scratch with its weight table in place; the
-// instances with the band epilogue then leave their partial sums there, rad and jac are not used.  instr: the scratch of
-// a call with the instrument derivatives, the INSTR instances; then there may be no parameter at all.
-static int limb_jac_state(bool cols, const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
-                          const LosShape &shape, int n_col, const int32_t *par_gas, const double *par_w, int gas,
-                          const double *tab, int n_tab_rows, const int32_t *coef_row, int n_lev, const int32_t *par_level,
-                          const double *par_c, double *rad, double *jac, hipStream_t st, const double *dabs = nullptr,
-                          const double *demi = nullptr, int n_row = 0, const double *par_t = nullptr,
-                          const void *band_scratch = nullptr, int n_bands = 0, int n_lgas = 1,
-                          const sr_level_gas *lgas = nullptr, const int32_t *par_lgas = nullptr, bool instr = false) {
-  const bool several = n_lgas > 1; // (then gas, tab, n_tab_rows and coef_row are not used: lgas has them per level gas)
-  const LevelJacPlan P = level_jac_plan(n_col, par_gas, n_lev, par_level, par_c, n_layers, n_row, par_t, several ? par_lgas : nullptr);
+// What the entries below do once their arguments are checked: plan, stage, launch, mark.  First the record they fill, a
+// mixed-state call as its entry receives it, in blocks of what belongs together.
+struct StateBatch { // the coefficient tables and the rays
+  const double *abs_c, *emi_c;
+  int n_layers;
+  int64_t n_pts;
+  const sr_los_desc *los;
+};
+struct StateCols { // column parameters, staged with the batch
+  int n_col;
+  const int32_t *par_gas;
+  const double *par_w;
+};
+// level parameters: the level-factored gases come as a list -- the one-gas entries hand in their one (one_level_gas) --
+// and par_lgas [n_lev] names a level parameter's level gas (null with one: all 0)
+struct StateLevels {
+  int n_lgas;
+  const sr_level_gas *lgas;
+  int n_lev;
+  const int32_t *par_lgas, *par_level;
+  const double *par_c;
+};
+struct StateRows { // row parameters, which act through dabs / demi
+  const double *dabs_c, *demi_c;
+  int n_row;
+  const double *par_t;
+};
+// the instrument's bands instead of spectra; instr: with the two instrument rows behind the parameters'
+struct StateBands {
+  const double *centers_nm, *widths_nm;
+  int n_bands;
+  double n_sigma;
+  int out_units;
+  const double *fov;
+  double *out;
+  bool instr;
+};
+struct StateCall {
+  const char *entry; // the name its messages carry
+  StateBatch b;
+  StateCols col;
+  StateLevels lev;
+  StateRows row;
+  void *stream;
+  // cols: the kernel instances with column slots (the state call, with n_col == 0 too); without them n_col is 0 and
+  // neither blk nor dcol exists
+  bool cols = false;
+  double *rad = nullptr, *jac = nullptr; // the spectra, or
+  const StateBands *bands = nullptr;     // the bands block
+};
+static sr_level_gas one_level_gas(int gas, const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row) {
+  sr_level_gas g;
+  g.gas = gas; g.n_levels = n_levels; g.n_tab_rows = n_tab_rows; g.tab = tab; g.coef_row = coef_row;
+  return g;
+}
+
+// n_row > 0: the instances with row slots, which read dabs / demi.  band_scratch (a call with a bands block): the
+// instrument step's scratch with its weight table in place; the instances with the band epilogue then leave their partial
+// sums there, rad and jac are not used.  With bands->instr it is the scratch of a call with the instrument derivatives,
+// the INSTR instances; then there may be no parameter at all.
+static int limb_jac_state(const StateCall &c, const LosShape &shape, const void *band_scratch, hipStream_t st) {
+  const StateBatch &b = c.b;
+  const int n_layers = b.n_layers, n_col = c.col.n_col, n_lev = c.lev.n_lev, n_row = c.row.n_row, n_lgas = c.lev.n_lgas;
+  const sr_level_gas *lgas = c.lev.lgas;
+  const bool several = n_lgas > 1;
+  const LevelJacPlan P = level_jac_plan(n_col, c.col.par_gas, n_lev, c.lev.par_level, c.lev.par_c, n_layers, n_row, c.row.par_t,
+                                        several ? c.lev.par_lgas : nullptr);
   static thread_local StagerRing ring;
   StagePack pk(ring.take());
   const auto p_ent = pk.copy(P.ent.data(), P.ent.size(), 1); // (no entries: a valid pointer all the same)
+  const int32_t *coef_row = lgas[0].coef_row;
   std::vector<int32_t> rows_all; // several level gases: their row maps one behind the other, [n_lgas][n_layers]
   if (several && n_lev > 0) {
     rows_all.reserve((size_t)n_lgas * n_layers);
     for (int k = 0; k < n_lgas; ++k) rows_all.insert(rows_all.end(), lgas[k].coef_row, lgas[k].coef_row + n_layers);
     coef_row = rows_all.data();
   }
-  const size_t n_rowmap = (size_t)(several ? n_lgas : 1) * n_layers;
+  const size_t n_rowmap = (size_t)n_lgas * n_layers;
   const auto p_row = n_lev > 0 ? pk.copy(coef_row, n_rowmap) : pk.zeros<int32_t>(n_rowmap);
   const auto p_off = pk.copy(P.ent_off.data(), P.ent_off.size()), p_slot = pk.copy(P.slot_par.data(), P.slot_par.size());
   const auto p_blk = pk.copy(P.blk.data(), P.blk.size());
   int rc = pk.stage(st);
   if (rc) return rc;
   LosDev D;
-  rc = stage_los(los, shape, n_col, par_gas, par_w, st, &D);
+  rc = stage_los(b.los, shape, n_col, c.col.par_gas, c.col.par_w, st, &D);
   if (rc) return rc;
-  const double *dcol = cols ? D.col + (size_t)los->n_gas * D.n_seg : nullptr;
-  const int *blk = cols ? pk.dev(p_blk) : nullptr;
-  if (several) {
-    LevelGasTabs lg{};
-    for (int k = 0; k < n_lgas; ++k) {
-      lg.tab[k] = lgas[k].tab;
-      lg.n_tab_rows[k] = lgas[k].n_tab_rows;
-      lg.gas[k] = lgas[k].gas;
-    }
-    LAUNCHCHK(launch_limb_jac_state_gases(abs_c, emi_c, n_row > 0 ? dabs : nullptr, n_row > 0 ? demi : nullptr, (int)n_pts, n_layers,
-                                          los->n_rays, D.seg_off, D.seg_layer, D.col, dcol, limb_opts(los, D.n_seg), lg,
-                                          pk.dev(p_row), P.n_blocks, blk, pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot),
-                                          n_col + n_lev + n_row, rad, jac, band_scratch, n_bands, st, instr));
-  } else if (band_scratch)
-    LAUNCHCHK(launch_limb_jac_state_bands(abs_c, emi_c, n_row > 0 ? dabs : nullptr, n_row > 0 ? demi : nullptr, (int)n_pts, n_layers,
-                                          los->n_rays, D.seg_off, D.seg_layer, D.col, dcol, limb_opts(los, D.n_seg), gas, tab,
-                                          n_tab_rows, pk.dev(p_row), P.n_blocks, blk, pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot),
-                                          n_col + n_lev + n_row, band_scratch, n_bands, st, instr));
-  else if (n_row > 0)
-    LAUNCHCHK(launch_limb_jac_state_rows(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer,
-                                         D.col, dcol, limb_opts(los, D.n_seg), gas, tab, n_tab_rows, pk.dev(p_row), P.n_blocks,
-                                         blk, pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot), n_col + n_lev + n_row, rad, jac, st));
-  else
-    LAUNCHCHK(launch_limb_jac_state(abs_c, emi_c, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer, D.col, dcol,
-                                    limb_opts(los, D.n_seg), gas, tab, n_tab_rows, pk.dev(p_row), P.n_blocks, blk,
-                                    pk.dev(p_off), pk.dev(p_ent), pk.dev(p_slot), n_col + n_lev, rad, jac, st));
+  LevelGasTabs lg{};
+  for (int k = 0; several && k < n_lgas; ++k) {
+    lg.tab[k] = lgas[k].tab;
+    lg.n_tab_rows[k] = lgas[k].n_tab_rows;
+    lg.gas[k] = lgas[k].gas;
+  }
+  StateLaunch L{};
+  L.abs_c = b.abs_c, L.emi_c = b.emi_c;
+  L.n_pts = (int)b.n_pts, L.n_layers = n_layers, L.n_rays = b.los->n_rays;
+  L.seg_off = D.seg_off, L.seg_layer = D.seg_layer;
+  L.col = D.col, L.dcol = c.cols ? D.col + (size_t)b.los->n_gas * D.n_seg : nullptr;
+  L.o = limb_opts(b.los, D.n_seg);
+  L.gas = lgas[0].gas, L.tab = lgas[0].tab, L.n_tab_rows = lgas[0].n_tab_rows;
+  L.lgas = several ? &lg : nullptr;
+  L.coef_row = pk.dev(p_row);
+  L.n_blocks = P.n_blocks, L.blk = c.cols ? pk.dev(p_blk) : nullptr;
+  L.ent_off = pk.dev(p_off), L.ent = pk.dev(p_ent), L.slot_par = pk.dev(p_slot);
+  L.n_par = n_col + n_lev + n_row;
+  if (n_row > 0) L.dabs = c.row.dabs_c, L.demi = c.row.demi_c;
+  L.rad = c.rad, L.jac = c.jac;
+  if (c.bands) L.lowres_scratch = band_scratch, L.n_bands = c.bands->n_bands, L.instr = c.bands->instr;
+  LAUNCHCHK(launch_limb_jac_state(L, st));
   return mark_both(pk.slot(), *D.slot, st);
 }
 
-int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
-                               const sr_los_desc *los, int gas, const double *tab, int n_levels, int n_tab_rows,
-                               const int32_t *coef_row, int n_par, const int32_t *par_level, const double *par_c,
-                               double *rad, double *jac, void *stream) {
-  // everything is checked here, before the first copy or launch (the LOS too: stage_los would only find out after this
-  // call's own staging)
-  LosShape shape;
-  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts,
-                           tab && coef_row && par_level && par_c && jac && n_levels > 0 && n_tab_rows > 0 && n_par >= 1);
-  if (!rc) rc = check_los(los, n_layers, &shape);
-  if (rc) return rc;
-  if (gas < 0 || gas >= los->n_gas) return SR_ERR_ARG;
-  if ((rc = refuse_init_mode_1(los, "sr_limb_rays_jac_level_dev", SR_ERR_ARG))) return rc;
-  if (!coef_rows_in_range(coef_row, n_layers, n_tab_rows)) return SR_ERR_ARG;
-  for (int p = 0; p < n_par; ++p)
-    if (par_level[p] < 0 || par_level[p] >= n_levels) return SR_ERR_ARG;
-  return limb_jac_state(false, abs_c, emi_c, n_layers, n_pts, los, shape, 0, nullptr, nullptr, gas, tab, n_tab_rows, coef_row,
-                        n_par, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream));
-}
-
-// The arguments of the mixed-state calls (sr_limb_rays_jac_state_dev, _state_rows_dev, sr_limb_rays_state_bands_dev and
-// their forms for several level gases), all of them before the first copy or launch (as sr_limb_rays_jac_level_dev does).
-// out_ok: the caller's outputs are there.  Any kind of parameter may be empty, not all (may_be_empty: all, the calls
-// with the instrument rows, which have something to return without a parameter); a kind that is empty needs none of its arrays.  The level-factored gases come as a list: the one-gas entries hand in their one (one_level_gas), for which
-// the checks and their order are what they always were; par_lgas [n_lev] names a level parameter's level gas (null with
-// one: all 0).
-static sr_level_gas one_level_gas(int gas, const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row) {
-  sr_level_gas g;
-  g.gas = gas; g.n_levels = n_levels; g.n_tab_rows = n_tab_rows; g.tab = tab; g.coef_row = coef_row;
-  return g;
-}
-static int check_state_call(const char *entry, const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
-                            const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
-                            const sr_level_gas *lgas, const int32_t *par_lgas, int n_lev, const int32_t *par_level,
-                            const double *par_c, const double *dabs_c, const double *demi_c, int n_row, const double *par_t,
-                            bool out_ok, LosShape *shape, bool may_be_empty = false) {
+// The arguments of the mixed-state calls (sr_limb_rays_jac_level_dev, sr_limb_rays_jac_state_dev, _state_rows_dev,
+// sr_limb_rays_state_bands_dev and their forms for several level gases), all of them before the first copy or launch
+// (the LOS too: stage_los would only find out after the call's own staging).  The caller's outputs must be there: jac,
+// or out and the bands.  Any kind of parameter may be empty, not all (but for the calls with the instrument rows, which
+// have something to return without a parameter); a kind that is empty needs none of its arrays.  With one level gas the
+// checks and their order are what they always were.
+static int check_state_call(const StateCall &c, LosShape *shape) {
+  const StateBatch &b = c.b;
+  const int n_col = c.col.n_col, n_lev = c.lev.n_lev, n_row = c.row.n_row, n_lgas = c.lev.n_lgas;
+  const sr_level_gas *lgas = c.lev.lgas;
+  const int32_t *par_lgas = c.lev.par_lgas, *par_level = c.lev.par_level;
+  const bool out_ok = c.bands ? c.bands->out && c.bands->centers_nm && c.bands->widths_nm && c.bands->n_bands > 0 : c.jac != nullptr;
+  const bool may_be_empty = c.bands && c.bands->instr;
   const bool list_ok = lgas && n_lgas >= 1 && n_lgas <= kLevelGasMax;
-  bool lev_ok = n_lev == 0 || (list_ok && par_level && par_c && (n_lgas == 1 || par_lgas));
+  bool lev_ok = n_lev == 0 || (list_ok && par_level && c.lev.par_c && (n_lgas == 1 || par_lgas));
   for (int k = 0; list_ok && n_lev > 0 && k < n_lgas; ++k)
     lev_ok = lev_ok && lgas[k].tab && lgas[k].coef_row && lgas[k].n_levels > 0 && lgas[k].n_tab_rows > 0;
-  const bool row_ok = n_row == 0 || (dabs_c && demi_c && par_t);
+  const bool row_ok = n_row == 0 || (c.row.dabs_c && c.row.demi_c && c.row.par_t);
   const bool counts_ok = n_col >= 0 && n_lev >= 0 && n_row >= 0 && (int64_t)n_col + n_lev + n_row >= (may_be_empty ? 0 : 1);
-  int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, out_ok && counts_ok && list_ok && lev_ok && row_ok);
-  if (!rc) rc = check_los_par(los, n_layers, n_col, par_gas, par_w, shape);
+  int rc = check_limb_call(b.abs_c, b.emi_c, b.n_layers, b.n_pts, out_ok && counts_ok && list_ok && lev_ok && row_ok);
+  if (!rc) rc = check_los_par(b.los, b.n_layers, n_col, c.col.par_gas, c.col.par_w, shape);
   if (rc) return rc;
-  if (n_lgas > los->n_gas) return SR_ERR_ARG;
+  if (n_lgas > b.los->n_gas) return SR_ERR_ARG;
   for (int k = 0; k < n_lgas; ++k) {
-    if (lgas[k].gas < 0 || lgas[k].gas >= los->n_gas) return SR_ERR_ARG;
+    if (lgas[k].gas < 0 || lgas[k].gas >= b.los->n_gas) return SR_ERR_ARG;
     for (int i = 0; i < k; ++i)
       if (lgas[i].gas == lgas[k].gas) return SR_ERR_ARG; // one gas of the batch, one set of tables
   }
-  if ((rc = refuse_init_mode_1(los, entry, SR_ERR_ARG))) return rc;
+  if ((rc = refuse_init_mode_1(b.los, c.entry, SR_ERR_ARG))) return rc;
   for (int k = 0; n_lev > 0 && k < n_lgas; ++k)
-    if (!coef_rows_in_range(lgas[k].coef_row, n_layers, lgas[k].n_tab_rows)) return SR_ERR_ARG;
+    if (!coef_rows_in_range(lgas[k].coef_row, b.n_layers, lgas[k].n_tab_rows)) return SR_ERR_ARG;
   for (int p = 0; p < n_lev; ++p) {
     const int k = par_lgas ? par_lgas[p] : 0;
     if (k < 0 || k >= n_lgas) return SR_ERR_ARG;
@@ -3530,17 +3556,97 @@ static int check_state_call(const char *entry, const double *abs_c, const double
   return SR_OK;
 }
 
+// The calls that return spectra: checked, then run.
+static int limb_state_spectra(const StateCall &c) {
+  LosShape shape;
+  const int rc = check_state_call(c, &shape);
+  return rc ? rc : limb_jac_state(c, shape, nullptr, static_cast<hipStream_t>(c.stream));
+}
+// ... of one level gas with a row block.  Nothing of the third kind: the state call, checks and all; else, without
+// column parameters, the instances without column code (fewer registers, the same arithmetic).
+static int limb_state_rows(StateCall &c) {
+  c.cols = c.col.n_col > 0;
+  if (c.row.n_row == 0) {
+    c.entry = "sr_limb_rays_jac_state_dev";
+    c.row = StateRows{};
+    c.cols = true;
+  }
+  return limb_state_spectra(c);
+}
+
+// The mixed-state Jacobian on the instrument's bands: the state call's plan and checks, the instrument step's cached
+// weight table (lowres_prepare, fused), the recursion kernel's band epilogue, the partial sums added straight into the
+// pinned landing buffer, the field of view on the host.  One body for one level gas (the one-gas instances) and for
+// several.
+static int limb_state_bands(StateCall &c) {
+  const StateBands &B = *c.bands;
+  const sr_los_desc *los = c.b.los;
+  const int64_t n_pts = c.b.n_pts;
+  c.cols = c.col.n_col > 0;
+  LosShape shape;
+  int rc = check_state_call(c, &shape);
+  if (rc) return rc;
+  // instr: the two instrument rows are the last two parameter rows of every ray, here and in the kernel; the sum kernel
+  // and the field of view (linear in the rays' band values) take them as they are
+  const int n_rays = los->n_rays, n_state = c.col.n_col + c.lev.n_lev + c.row.n_row;
+  if (B.instr && n_state > INT_MAX - 2) return SR_ERR_LIMIT;
+  const int n_par = n_state + (B.instr ? 2 : 0);
+  if (B.fov && n_rays % 3 != 0) return SR_ERR_ARG;
+  if ((int64_t)n_rays * (1 + (int64_t)n_par) > INT_MAX) return SR_ERR_LIMIT;
+  const int n_spec = n_rays * (1 + n_par);
+  // the grid is the descriptor's (a descriptor without one, step <= 0, is refused here)
+  rc = lowres_check(n_spec, n_pts, los->g_lo, los->w0, los->step, B.centers_nm, B.widths_nm, B.n_bands, B.n_sigma, B.out_units);
+  if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(c.stream);
+  bool fresh = false;
+  rc = lowres_prepare(n_spec, n_pts, los->g_lo, los->w0, los->step, B.centers_nm, B.widths_nm, B.n_bands, B.n_sigma, B.out_units,
+                      /*fused=*/true, st, &fresh, B.instr);
+  if (rc) return rc;
+  rc = limb_jac_state(c, shape, t_lowres.d_weights.p, st);
+  if (rc) return rc;
+  const size_t low_bytes = sizeof(double) * (size_t)n_spec * B.n_bands;
+  rc = t_lowres.s_land.prepare(low_bytes);
+  if (rc) return rc;
+  LAUNCHCHK(launch_lowres_sum_blocks((int)n_pts, n_spec, B.n_bands, B.out_units, static_cast<double *>(t_lowres.s_land.h),
+                                     t_lowres.d_weights.p, st, B.instr));
+  HIPCHK(hipStreamSynchronize(st));
+  fov_rows(static_cast<const double *>(t_lowres.s_land.h), n_rays, n_par, B.n_bands, B.fov, B.out);
+  return SR_OK;
+}
+
+// Several level-factored gases.  One level gas is the one-gas entry `twin`, checks and all: the record becomes the one
+// that entry fills (a par_lgas that names another gas is refused first: the one-gas entries have no such argument).
+static bool one_level_gas_call(StateCall &c, const char *twin, int *rc) {
+  *rc = SR_OK;
+  if (c.lev.n_lgas != 1 || !c.lev.lgas) return false;
+  for (int p = 0; c.lev.par_lgas && p < c.lev.n_lev; ++p)
+    if (c.lev.par_lgas[p] != 0) *rc = SR_ERR_ARG;
+  c.lev.par_lgas = nullptr;
+  c.entry = twin;
+  return true;
+}
+
+int sr_limb_rays_jac_level_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                               const sr_los_desc *los, int gas, const double *tab, int n_levels, int n_tab_rows,
+                               const int32_t *coef_row, int n_par, const int32_t *par_level, const double *par_c,
+                               double *rad, double *jac, void *stream) {
+  // the state call without column parameters, its checks included: the instances without column code
+  const sr_level_gas one = one_level_gas(gas, tab, n_levels, n_tab_rows, coef_row);
+  StateCall c{"sr_limb_rays_jac_level_dev", {abs_c, emi_c, n_layers, n_pts, los}, {0, nullptr, nullptr},
+              {1, &one, n_par, nullptr, par_level, par_c}, {}, stream};
+  c.rad = rad, c.jac = jac;
+  return limb_state_spectra(c);
+}
+
 int sr_limb_rays_jac_state_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
                                const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int gas,
                                const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
                                const int32_t *par_level, const double *par_c, double *rad, double *jac, void *stream) {
-  LosShape shape;
   const sr_level_gas one = one_level_gas(gas, tab, n_levels, n_tab_rows, coef_row);
-  const int rc = check_state_call("sr_limb_rays_jac_state_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, 1, &one,
-                                  nullptr, n_lev, par_level, par_c, nullptr, nullptr, 0, nullptr, jac != nullptr, &shape);
-  if (rc) return rc;
-  return limb_jac_state(true, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, gas, tab, n_tab_rows, coef_row,
-                        n_lev, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream));
+  StateCall c{"sr_limb_rays_jac_state_dev", {abs_c, emi_c, n_layers, n_pts, los}, {n_col, par_gas, par_w},
+              {1, &one, n_lev, nullptr, par_level, par_c}, {}, stream};
+  c.cols = true, c.rad = rad, c.jac = jac;
+  return limb_state_spectra(c);
 }
 
 int sr_limb_rays_jac_state_rows_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
@@ -3548,63 +3654,11 @@ int sr_limb_rays_jac_state_rows_dev(const double *abs_c, const double *emi_c, in
                                     const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_lev,
                                     const int32_t *par_level, const double *par_c, const double *dabs_c, const double *demi_c,
                                     int n_row, const double *par_t, double *rad, double *jac, void *stream) {
-  if (n_row == 0) // nothing of the third kind: the state call, checks and all
-    return sr_limb_rays_jac_state_dev(abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, gas, tab, n_levels, n_tab_rows,
-                                      coef_row, n_lev, par_level, par_c, rad, jac, stream);
-  LosShape shape;
   const sr_level_gas one = one_level_gas(gas, tab, n_levels, n_tab_rows, coef_row);
-  const int rc = check_state_call("sr_limb_rays_jac_state_rows_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, 1,
-                                  &one, nullptr, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, jac != nullptr, &shape);
-  if (rc) return rc;
-  // (without column parameters the instances without column code: fewer registers, the same arithmetic)
-  return limb_jac_state(n_col > 0, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, gas, tab, n_tab_rows,
-                        coef_row, n_lev, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream), dabs_c, demi_c, n_row,
-                        par_t);
-}
-
-// The mixed-state Jacobian on the instrument's bands: the state call's plan and checks, the instrument step's cached
-// weight table (lowres_prepare, fused), the recursion kernel's band epilogue, the partial sums added straight into the
-// pinned landing buffer, the field of view on the host.  One body for one level gas (n_lgas == 1: gas, tab, ... of
-// lgas[0], the one-gas instances) and for several.
-static int limb_state_bands(const char *entry, const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
-                            const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
-                            const sr_level_gas *lgas, const int32_t *par_lgas, int n_lev, const int32_t *par_level,
-                            const double *par_c, const double *dabs_c, const double *demi_c, int n_row, const double *par_t,
-                            const double *centers_nm, const double *widths_nm, int n_bands, double n_sigma, int out_units,
-                            const double *fov, double *out, void *stream, bool instr = false) {
-  LosShape shape;
-  int rc = check_state_call(entry, abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, n_lgas, lgas, par_lgas, n_lev,
-                            par_level, par_c, dabs_c, demi_c, n_row, par_t, out && centers_nm && widths_nm && n_bands > 0, &shape,
-                            /*may_be_empty=*/instr);
-  if (rc) return rc;
-  // instr: the two instrument rows are the last two parameter rows of every ray, here and in the kernel; the sum kernel
-  // and the field of view (linear in the rays' band values) take them as they are
-  const int n_rays = los->n_rays, n_state = n_col + n_lev + n_row;
-  if (instr && n_state > INT_MAX - 2) return SR_ERR_LIMIT;
-  const int n_par = n_state + (instr ? 2 : 0);
-  if (fov && n_rays % 3 != 0) return SR_ERR_ARG;
-  if ((int64_t)n_rays * (1 + (int64_t)n_par) > INT_MAX) return SR_ERR_LIMIT;
-  const int n_spec = n_rays * (1 + n_par);
-  // the grid is the descriptor's (a descriptor without one, step <= 0, is refused here)
-  rc = lowres_check(n_spec, n_pts, los->g_lo, los->w0, los->step, centers_nm, widths_nm, n_bands, n_sigma, out_units);
-  if (rc) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  bool fresh = false;
-  rc = lowres_prepare(n_spec, n_pts, los->g_lo, los->w0, los->step, centers_nm, widths_nm, n_bands, n_sigma, out_units,
-                      /*fused=*/true, st, &fresh, instr);
-  if (rc) return rc;
-  rc = limb_jac_state(n_col > 0, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, lgas[0].gas, lgas[0].tab,
-                      lgas[0].n_tab_rows, lgas[0].coef_row, n_lev, par_level, par_c, nullptr, nullptr, st, dabs_c, demi_c, n_row,
-                      par_t, t_lowres.d_weights.p, n_bands, n_lgas, lgas, par_lgas, instr);
-  if (rc) return rc;
-  const size_t low_bytes = sizeof(double) * (size_t)n_spec * n_bands;
-  rc = t_lowres.s_land.prepare(low_bytes);
-  if (rc) return rc;
-  LAUNCHCHK(launch_lowres_sum_blocks((int)n_pts, n_spec, n_bands, out_units, static_cast<double *>(t_lowres.s_land.h),
-                                     t_lowres.d_weights.p, st, instr));
-  HIPCHK(hipStreamSynchronize(st));
-  fov_rows(static_cast<const double *>(t_lowres.s_land.h), n_rays, n_par, n_bands, fov, out);
-  return SR_OK;
+  StateCall c{"sr_limb_rays_jac_state_rows_dev", {abs_c, emi_c, n_layers, n_pts, los}, {n_col, par_gas, par_w},
+              {1, &one, n_lev, nullptr, par_level, par_c}, {dabs_c, demi_c, n_row, par_t}, stream};
+  c.rad = rad, c.jac = jac;
+  return limb_state_rows(c);
 }
 
 int sr_limb_rays_state_bands_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
@@ -3614,19 +3668,11 @@ int sr_limb_rays_state_bands_dev(const double *abs_c, const double *emi_c, int n
                                  int n_row, const double *par_t, const double *centers_nm, const double *widths_nm,
                                  int n_bands, double n_sigma, int out_units, const double *fov, double *out, void *stream) {
   const sr_level_gas one = one_level_gas(gas, tab, n_levels, n_tab_rows, coef_row);
-  return limb_state_bands("sr_limb_rays_state_bands_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, 1, &one, nullptr,
-                          n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm, n_bands, n_sigma, out_units,
-                          fov, out, stream);
-}
-
-// Several level-factored gases.  One level gas is the existing entry, checks and all (a par_lgas that names another one
-// is refused first: the existing entries have no such argument).
-static bool one_level_gas_call(int n_lgas, const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas, int *rc) {
-  if (n_lgas != 1 || !lgas) return false;
-  *rc = SR_OK;
-  for (int p = 0; par_lgas && p < n_lev; ++p)
-    if (par_lgas[p] != 0) *rc = SR_ERR_ARG;
-  return true;
+  const StateBands bands{centers_nm, widths_nm, n_bands, n_sigma, out_units, fov, out, /*instr=*/false};
+  StateCall c{"sr_limb_rays_state_bands_dev", {abs_c, emi_c, n_layers, n_pts, los}, {n_col, par_gas, par_w},
+              {1, &one, n_lev, nullptr, par_level, par_c}, {dabs_c, demi_c, n_row, par_t}, stream};
+  c.bands = &bands;
+  return limb_state_bands(c);
 }
 
 int sr_limb_rays_jac_state_gases_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
@@ -3634,18 +3680,13 @@ int sr_limb_rays_jac_state_gases_dev(const double *abs_c, const double *emi_c, i
                                      const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas, const int32_t *par_level,
                                      const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
                                      const double *par_t, double *rad, double *jac, void *stream) {
+  StateCall c{"sr_limb_rays_jac_state_gases_dev", {abs_c, emi_c, n_layers, n_pts, los}, {n_col, par_gas, par_w},
+              {n_lgas, lgas, n_lev, par_lgas, par_level, par_c}, {dabs_c, demi_c, n_row, par_t}, stream};
+  c.rad = rad, c.jac = jac;
   int rc;
-  if (one_level_gas_call(n_lgas, lgas, n_lev, par_lgas, &rc))
-    return rc ? rc : sr_limb_rays_jac_state_rows_dev(abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, lgas[0].gas, lgas[0].tab,
-                                                     lgas[0].n_levels, lgas[0].n_tab_rows, lgas[0].coef_row, n_lev, par_level, par_c,
-                                                     dabs_c, demi_c, n_row, par_t, rad, jac, stream);
-  LosShape shape;
-  rc = check_state_call("sr_limb_rays_jac_state_gases_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, n_lgas, lgas,
-                        par_lgas, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, jac != nullptr, &shape);
-  if (rc) return rc;
-  return limb_jac_state(n_col > 0, abs_c, emi_c, n_layers, n_pts, los, shape, n_col, par_gas, par_w, lgas[0].gas, lgas[0].tab,
-                        lgas[0].n_tab_rows, lgas[0].coef_row, n_lev, par_level, par_c, rad, jac, static_cast<hipStream_t>(stream),
-                        dabs_c, demi_c, n_row, par_t, nullptr, 0, n_lgas, lgas, par_lgas);
+  if (one_level_gas_call(c, "sr_limb_rays_jac_state_rows_dev", &rc)) return rc ? rc : limb_state_rows(c);
+  c.cols = n_col > 0;
+  return limb_state_spectra(c);
 }
 
 int sr_limb_rays_state_bands_gases_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
@@ -3654,15 +3695,13 @@ int sr_limb_rays_state_bands_gases_dev(const double *abs_c, const double *emi_c,
                                        const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
                                        const double *par_t, const double *centers_nm, const double *widths_nm, int n_bands,
                                        double n_sigma, int out_units, const double *fov, double *out, void *stream) {
+  const StateBands bands{centers_nm, widths_nm, n_bands, n_sigma, out_units, fov, out, /*instr=*/false};
+  StateCall c{"sr_limb_rays_state_bands_gases_dev", {abs_c, emi_c, n_layers, n_pts, los}, {n_col, par_gas, par_w},
+              {n_lgas, lgas, n_lev, par_lgas, par_level, par_c}, {dabs_c, demi_c, n_row, par_t}, stream};
+  c.bands = &bands;
   int rc;
-  if (one_level_gas_call(n_lgas, lgas, n_lev, par_lgas, &rc))
-    return rc ? rc : sr_limb_rays_state_bands_dev(abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, lgas[0].gas, lgas[0].tab,
-                                                  lgas[0].n_levels, lgas[0].n_tab_rows, lgas[0].coef_row, n_lev, par_level, par_c,
-                                                  dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm, n_bands, n_sigma, out_units,
-                                                  fov, out, stream);
-  return limb_state_bands("sr_limb_rays_state_bands_gases_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, n_lgas,
-                          lgas, par_lgas, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm, n_bands,
-                          n_sigma, out_units, fov, out, stream);
+  one_level_gas_call(c, "sr_limb_rays_state_bands_dev", &rc);
+  return rc ? rc : limb_state_bands(c);
 }
 
 // ... with the two instrument rows behind the parameters' (d / d band centre, d / d ln ILS width of the radiance's bands):
@@ -3674,9 +3713,11 @@ int sr_limb_rays_state_bands_instr_dev(const double *abs_c, const double *emi_c,
                                        int n_row, const double *par_t, const double *centers_nm, const double *widths_nm,
                                        int n_bands, double n_sigma, int out_units, const double *fov, double *out, void *stream) {
   const sr_level_gas one = one_level_gas(gas, tab, n_levels, n_tab_rows, coef_row);
-  return limb_state_bands("sr_limb_rays_state_bands_instr_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, 1, &one,
-                          nullptr, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm, n_bands, n_sigma,
-                          out_units, fov, out, stream, /*instr=*/true);
+  const StateBands bands{centers_nm, widths_nm, n_bands, n_sigma, out_units, fov, out, /*instr=*/true};
+  StateCall c{"sr_limb_rays_state_bands_instr_dev", {abs_c, emi_c, n_layers, n_pts, los}, {n_col, par_gas, par_w},
+              {1, &one, n_lev, nullptr, par_level, par_c}, {dabs_c, demi_c, n_row, par_t}, stream};
+  c.bands = &bands;
+  return limb_state_bands(c);
 }
 
 int sr_limb_rays_state_bands_instr_gases_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
@@ -3686,15 +3727,13 @@ int sr_limb_rays_state_bands_instr_gases_dev(const double *abs_c, const double *
                                              const double *demi_c, int n_row, const double *par_t, const double *centers_nm,
                                              const double *widths_nm, int n_bands, double n_sigma, int out_units,
                                              const double *fov, double *out, void *stream) {
+  const StateBands bands{centers_nm, widths_nm, n_bands, n_sigma, out_units, fov, out, /*instr=*/true};
+  StateCall c{"sr_limb_rays_state_bands_instr_gases_dev", {abs_c, emi_c, n_layers, n_pts, los}, {n_col, par_gas, par_w},
+              {n_lgas, lgas, n_lev, par_lgas, par_level, par_c}, {dabs_c, demi_c, n_row, par_t}, stream};
+  c.bands = &bands;
   int rc;
-  if (one_level_gas_call(n_lgas, lgas, n_lev, par_lgas, &rc))
-    return rc ? rc : sr_limb_rays_state_bands_instr_dev(abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w, lgas[0].gas,
-                                                        lgas[0].tab, lgas[0].n_levels, lgas[0].n_tab_rows, lgas[0].coef_row, n_lev,
-                                                        par_level, par_c, dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm,
-                                                        n_bands, n_sigma, out_units, fov, out, stream);
-  return limb_state_bands("sr_limb_rays_state_bands_instr_gases_dev", abs_c, emi_c, n_layers, n_pts, los, n_col, par_gas, par_w,
-                          n_lgas, lgas, par_lgas, n_lev, par_level, par_c, dabs_c, demi_c, n_row, par_t, centers_nm, widths_nm,
-                          n_bands, n_sigma, out_units, fov, out, stream, /*instr=*/true);
+  one_level_gas_call(c, "sr_limb_rays_state_bands_instr_dev", &rc);
+  return rc ? rc : limb_state_bands(c);
 }
 
 int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,

@@ -3020,6 +3020,12 @@ inline void by_level_np(int np, F &&f) {
   if (np == kLevelJacNPLarge) f(std::integral_constant<int, kLevelJacNPLarge>{});
   else f(std::integral_constant<int, kLevelJacNPSmall>{});
 }
+// by_flag: f(bool_constant<on>) for a kernel's boolean template parameter.
+template <class F>
+inline void by_flag(bool on, F &&f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
 // by_jac_kinds: f(bool_constant<per-layer>, bool_constant<per-parameter>) for the Jacobians a one-pass call asks for.
 // (false, false) does not exist as a kernel: a call without per-layer Jacobians is a per-parameter one.
 template <class F>
@@ -4816,136 +4822,55 @@ int launch_limb_jac_layer(const double *abs_c, const double *emi_c, const double
   return (int)hipGetLastError();
 }
 
-int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
-                          const int *seg_layer, const double *col, const double *dcol, const LimbOpts &o, int gas,
-                          const double *tab, int n_tab_rows, const int *coef_row, int n_blocks, const int *blk,
-                          const int *ent_off, const LevelEnt *ent, const int *slot_par, int n_par, double *rad, double *jac,
-                          hipStream_t st) {
-  if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0) return 0;
-  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
-  auto launch = [&](auto cols) { // no blk: the instance without column slots
-    by_level_np(level_jac_np(n_par), [&](auto np) {
-      by_ngas(o.n_gas, [&](auto ng) {
-        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, false, false, false>), grid,
-                           dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas, tab,
-                           n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac);
+int launch_limb_jac_state(const StateLaunch &L, hipStream_t st) {
+  const bool bands = L.lowres_scratch != nullptr, rows = L.dabs && L.demi;
+  if (L.instr && !bands) return 0;
+  if (L.n_pts <= 0 || L.n_rays <= 0 || L.n_par < (L.instr ? 0 : 1) || L.n_blocks <= 0) return 0;
+  if (bands && L.n_bands <= 0) return 0;
+  if (L.lgas && (L.o.n_gas < 2 || L.o.n_gas > 4)) return 0;
+  const dim3 grid(limb_grid((L.n_pts + 255) / 256, L.n_rays), 1, L.n_blocks);
+  FoldBands bd{};
+  if (bands) {
+    const LowresScratch S = lowres_layout(const_cast<void *>(L.lowres_scratch), L.n_pts, L.n_bands, L.instr);
+    bd = FoldBands{S.Wt, S.range, S.part, L.n_bands};
+  }
+  const int n_row_par = L.n_par + (L.instr ? kLowresTables - 1 : 0); // the parameter rows of a ray in `part`
+  // (gas, tab and n_tab_rows belong to the one-gas instances, rad to those that write spectra)
+  const int gas = L.lgas ? -1 : L.gas, n_tab_rows = L.lgas ? 0 : L.n_tab_rows;
+  const double *const tab = L.lgas ? nullptr : L.tab;
+  double *const rad = bands ? nullptr : L.rad;
+  by_flag(L.blk != nullptr, [&](auto cols) { // no blk: the instances without column slots
+    by_level_np(level_jac_np(L.n_par), [&](auto np) {
+      by_ngas(L.o.n_gas, [&](auto ng) {
+        by_flag(rows, [&](auto rw) {
+          by_flag(bands, [&](auto bn) {
+            by_flag(L.instr, [&](auto ins) {
+              by_flag(L.lgas != nullptr, [&](auto several) {
+                constexpr int NG = decltype(ng)::value, NP = decltype(np)::value;
+                constexpr bool COLS = decltype(cols)::value, ROWS = decltype(rw)::value, BANDS = decltype(bn)::value;
+                constexpr bool INSTR = decltype(ins)::value, SEVERAL = decltype(several)::value;
+                // the instrument rows are band integrals; several level gases are several gases of the batch
+                if constexpr ((BANDS || !INSTR) && (NG >= 2 || !SEVERAL)) {
+                  auto launch = [&](auto... pack) {
+                    std::conditional_t<BANDS, FoldBands, double *> out;
+                    if constexpr (BANDS) out = bd;
+                    else out = L.jac;
+                    hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, ROWS, BANDS, INSTR, decltype(pack)...>), grid, dim3(256), 0,
+                                       st, L.abs_c, L.emi_c, L.n_pts, L.n_layers, L.seg_off, L.seg_layer, L.col, L.dcol, L.o, L.n_rays, gas,
+                                       tab, n_tab_rows, L.coef_row, L.blk, L.ent_off, L.ent, L.slot_par, n_row_par, rad, out, pack...);
+                  };
+                  if constexpr (ROWS && SEVERAL) launch(L.dabs, L.demi, *L.lgas);
+                  else if constexpr (ROWS) launch(L.dabs, L.demi);
+                  else if constexpr (SEVERAL) launch(*L.lgas);
+                  else launch();
+                }
+              });
+            });
+          });
+        });
       });
     });
-  };
-  if (blk) launch(std::true_type{});
-  else launch(std::false_type{});
-  return (int)hipGetLastError();
-}
-
-int launch_limb_jac_state_rows(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
-                               int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
-                               const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
-                               const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
-                               const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st) {
-  if (n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_blocks <= 0) return 0;
-  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
-  auto launch = [&](auto cols) { // no blk: the instance without column slots
-    by_level_np(level_jac_np(n_par), [&](auto np) {
-      by_ngas(o.n_gas, [&](auto ng) {
-        hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, true, false, false,
-                                                     const double *, const double *>),
-                           grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas,
-                           tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac, dabs, demi);
-      });
-    });
-  };
-  if (blk) launch(std::true_type{});
-  else launch(std::false_type{});
-  return (int)hipGetLastError();
-}
-
-int launch_limb_jac_state_bands(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
-                                int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
-                                const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
-                                const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
-                                const int *slot_par, int n_par, const void *lowres_scratch, int n_bands, hipStream_t st, bool instr) {
-  if (n_pts <= 0 || n_rays <= 0 || n_par < (instr ? 0 : 1) || n_blocks <= 0 || n_bands <= 0 || !lowres_scratch) return 0;
-  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
-  const LowresScratch L = lowres_layout(const_cast<void *>(lowres_scratch), n_pts, n_bands, instr);
-  const FoldBands bd{L.Wt, L.range, L.part, n_bands};
-  double *const no_rad = nullptr;
-  const int n_row_par = n_par + (instr ? kLowresTables - 1 : 0); // the parameter rows of a ray in `part`
-  auto launch = [&](auto cols, auto ins) { // no blk: the instance without column slots
-    by_level_np(level_jac_np(n_par), [&](auto np) {
-      by_ngas(o.n_gas, [&](auto ng) {
-        if (dabs && demi) // row parameters
-          hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, true, true,
-                                                       decltype(ins)::value, const double *, const double *>),
-                             grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas,
-                             tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_row_par, no_rad, bd, dabs, demi);
-        else
-          hipLaunchKernelGGL((sr_limb_jac_state_kernel<decltype(ng)::value, decltype(np)::value, decltype(cols)::value, false, true,
-                                                       decltype(ins)::value>),
-                             grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, gas,
-                             tab, n_tab_rows, coef_row, blk, ent_off, ent, slot_par, n_row_par, no_rad, bd);
-      });
-    });
-  };
-  auto by_instr = [&](auto cols) {
-    if (instr) launch(cols, std::true_type{});
-    else launch(cols, std::false_type{});
-  };
-  if (blk) by_instr(std::true_type{});
-  else by_instr(std::false_type{});
-  return (int)hipGetLastError();
-}
-
-int launch_limb_jac_state_gases(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
-                                int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
-                                const double *dcol, const LimbOpts &o, const LevelGasTabs &lg, const int *coef_row, int n_blocks,
-                                const int *blk, const int *ent_off, const LevelEnt *ent, const int *slot_par, int n_par,
-                                double *rad, double *jac, const void *lowres_scratch, int n_bands, hipStream_t st, bool instr) {
-  if (instr && !lowres_scratch) return 0;
-  if (n_pts <= 0 || n_rays <= 0 || n_par < (instr ? 0 : 1) || n_blocks <= 0 || o.n_gas < 2 || o.n_gas > 4) return 0;
-  if (lowres_scratch && n_bands <= 0) return 0;
-  const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
-  const bool rows = dabs && demi;
-  const double *const no_tab = nullptr;
-  double *const no_rad = nullptr;
-  constexpr int no_gas = -1; // (gas, tab and n_tab_rows belong to the one-gas instances)
-  const int n_row_par = n_par + (instr ? kLowresTables - 1 : 0); // the parameter rows of a ray in `part`
-  auto launch = [&](auto cols) { // no blk: the instances without column slots
-    by_level_np(level_jac_np(n_par), [&](auto np) {
-      by_ngas(o.n_gas, [&](auto ng) {
-        constexpr int NG = decltype(ng)::value, NP = decltype(np)::value;
-        constexpr bool COLS = decltype(cols)::value;
-        if constexpr (NG >= 2) { // (several level gases are several gases of the batch)
-          if (lowres_scratch) {
-            const LowresScratch L = lowres_layout(const_cast<void *>(lowres_scratch), n_pts, n_bands, instr);
-            const FoldBands bd{L.Wt, L.range, L.part, n_bands};
-            auto bands = [&](auto ins) {
-              constexpr bool INSTR = decltype(ins)::value;
-              if (rows)
-                hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, true, true, INSTR, const double *, const double *, LevelGasTabs>),
-                                   grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays,
-                                   no_gas, no_tab, 0, coef_row, blk, ent_off, ent, slot_par, n_row_par, no_rad, bd, dabs, demi, lg);
-              else
-                hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, false, true, INSTR, LevelGasTabs>), grid, dim3(256), 0, st,
-                                   abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas, no_tab, 0, coef_row,
-                                   blk, ent_off, ent, slot_par, n_row_par, no_rad, bd, lg);
-            };
-            if (instr) bands(std::true_type{});
-            else bands(std::false_type{});
-          } else if (rows) {
-            hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, true, false, false, const double *, const double *, LevelGasTabs>),
-                               grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas,
-                               no_tab, 0, coef_row, blk, ent_off, ent, slot_par, n_par, rad, jac, dabs, demi, lg);
-          } else {
-            hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, false, false, false, LevelGasTabs>), grid, dim3(256), 0, st, abs_c,
-                               emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, o, n_rays, no_gas, no_tab, 0, coef_row, blk,
-                               ent_off, ent, slot_par, n_par, rad, jac, lg);
-          }
-        }
-      });
-    });
-  };
-  if (blk) launch(std::true_type{});
-  else launch(std::false_type{});
+  });
   return (int)hipGetLastError();
 }
 

@@ -239,21 +239,16 @@ int launch_limb_jac(const double *abs_c, const double *emi_c, int n_pts, int n_l
 int launch_limb_jac_layer(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
                           int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
                           const LimbOpts &o, double *jac, hipStream_t st);
-// Level-parameter and mixed-state Jacobians (sr_limb_jac_state_kernel): n_par = n_col + n_lev parameters, the column
-// parameters first (rows of dcol, caller's order), then the level parameters of one level-factored gas in level order, in
-// blocks of level_jac_np(n_par); blk [n_blocks][2] = the number of column slots of a block (its first slots: parameters
-// block NP + q) and their gases, two bits per slot; ent_off [n_blocks][n_layers + 1] into ent, the entries of every
-// (parameter block, coefficient row) with a non-zero coefficient, in level order, slot numbers counted over all slots of
-// a block; slot_par [n_blocks][NP] = the parameter an accumulator belongs to, or -1.  blk == nullptr: level parameters
-// only (n_col = 0), the kernel instance without column code; dcol is not read and may be null too.
+// Level-parameter and mixed-state Jacobians (sr_limb_jac_state_kernel): one launcher over one record, StateLaunch below.
+// LevelEnt: an entry of its plan.
 struct __attribute__((aligned(16))) LevelEnt {
   int slot, level; // accumulator of the block, level of the pair tables
   double c;        // d pop[row][level] / d x_p
 };
-// the `level` of an entry that belongs to a row slot (launch_limb_jac_state_rows): its c is the slot's weight on the row
+// the `level` of an entry that belongs to a row slot (StateLaunch::dabs / demi): its c is the slot's weight on the row
 constexpr int kLevelEntRows = -2;
-// several level-factored gases (launch_limb_jac_state_gases below): an entry's `level` is level | level gas << kLevelEntGasShift,
-// and the kernel's last argument holds, per level gas, the tables, their row count and the gas's index in the batch
+// several level-factored gases (StateLaunch::lgas): an entry's `level` is level | level gas << kLevelEntGasShift, and the
+// kernel's last argument holds, per level gas, the tables, their row count and the gas's index in the batch
 constexpr int kLevelEntGasShift = 16, kLevelEntLevelMask = (1 << kLevelEntGasShift) - 1;
 constexpr int kLevelGasMax = 4;
 struct LevelGasTabs {
@@ -263,45 +258,55 @@ struct LevelGasTabs {
 };
 constexpr int kLevelJacNPSmall = 8, kLevelJacNPLarge = 16;
 inline int level_jac_np(int n_par) { return n_par > kLevelJacNPSmall ? kLevelJacNPLarge : kLevelJacNPSmall; }
-int launch_limb_jac_state(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
-                          const int *seg_layer, const double *col, const double *dcol, const LimbOpts &o, int gas,
-                          const double *tab, int n_tab_rows, const int *coef_row, int n_blocks, const int *blk,
-                          const int *ent_off, const LevelEnt *ent, const int *slot_par, int n_par, double *rad, double *jac,
-                          hipStream_t st);
-// The same with ROW parameters as a third kind (the kernel's ROWS = true instances): n_par = n_col + n_lev + n_row, the
-// row parameters last, in the caller's order.  dabs / demi [n_gas][n_layers][n_pts]: the derivative spectra a row
-// parameter acts through.  A row slot has, on every coefficient row it weights, one entry behind that row's level entries:
-// level = kLevelEntRows, c = the weight.
-int launch_limb_jac_state_rows(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
-                               int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
-                               const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
-                               const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
-                               const int *slot_par, int n_par, double *rad, double *jac, hipStream_t st);
-// The same recursion with the instrument bands in its epilogue (the kernel's BANDS = true instances): no spectra are
-// written; the band integrals' partial sums per wave (64 points) go to the instrument step's scratch, whose weight table
-// is in place (launch_lowres_weights; scratch sized for n_rays (1 + n_par) rows, fused), rows as launch_fold_dense orders
-// them: row ray = the radiance, row n_rays + ray n_par + p = parameter p.  launch_lowres_sum_blocks finishes them.
-// dabs / demi null: no row parameters.
-int launch_limb_jac_state_bands(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
-                                int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
-                                const double *dcol, const LimbOpts &o, int gas, const double *tab, int n_tab_rows,
-                                const int *coef_row, int n_blocks, const int *blk, const int *ent_off, const LevelEnt *ent,
-                                const int *slot_par, int n_par, const void *lowres_scratch, int n_bands, hipStream_t st,
-                                bool instr = false);
-// (instr: the kernel's INSTR = true instances -- the scratch of an instr call, three weight tables; every ray has two more
-// parameter rows in `part`, n_par and n_par + 1 of n_par + 2: the radiance's bands d / d centre and d / d ln width; n_par,
-// here the number of state parameters, may then be 0, with one block whose slots are all unused)
-// The same three for the level parameters of SEVERAL level-factored gases (the kernel's instances whose parameter pack
-// ends in a LevelGasTabs; batches of two to four gases): level gas k has the tables tab[k] with n_tab_rows[k] rows, is
-// gas gas[k] of the batch, and coef_row [n_lgas][n_layers] holds its row map at k n_layers.  The level slots are sorted
-// by (level gas, level) and an entry's `level` is level | level gas << kLevelEntGasShift.  dabs / demi null: no row
-// parameters; lowres_scratch null: spectra to rad / jac, else the band epilogue as launch_limb_jac_state_bands.
-int launch_limb_jac_state_gases(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
-                                int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
-                                const double *dcol, const LimbOpts &o, const LevelGasTabs &lg, const int *coef_row, int n_blocks,
-                                const int *blk, const int *ent_off, const LevelEnt *ent, const int *slot_par, int n_par,
-                                double *rad, double *jac, const void *lowres_scratch, int n_bands, hipStream_t st,
-                                bool instr = false);
+struct StateLaunch {
+  // The batch, as launch_limb_jac takes it.  dcol: the rows of the column parameters, caller's order (not read, and may
+  // be null, without column slots).
+  const double *abs_c, *emi_c;
+  int n_pts, n_layers, n_rays;
+  const int *seg_off, *seg_layer;
+  const double *col, *dcol;
+  LimbOpts o;
+  // The level tables.  One level-factored gas (lgas null): gas `gas` of the batch, pair tables tab with n_tab_rows rows,
+  // coef_row [n_layers].  SEVERAL (lgas given, batches of two to four gases; the kernel's instances whose parameter
+  // pack ends in a LevelGasTabs): level gas k has the tables lgas->tab[k] with lgas->n_tab_rows[k] rows, is gas
+  // lgas->gas[k] of the batch, and coef_row [n_lgas][n_layers] holds its row map at k n_layers; the level slots are
+  // sorted by (level gas, level) and an entry's `level` is level | level gas << kLevelEntGasShift; gas, tab and
+  // n_tab_rows are not read.
+  int gas;
+  const double *tab;
+  int n_tab_rows;
+  const LevelGasTabs *lgas;
+  const int *coef_row;
+  // The plan of n_par = n_col + n_lev + n_row parameters: the column parameters first (rows of dcol), then the level
+  // parameters in level order, then the row parameters in the caller's order, in blocks of level_jac_np(n_par).
+  // blk [n_blocks][2] = the number of column slots of a block (its first slots: parameters block NP + q) and their
+  // gases, two bits per slot; ent_off [n_blocks][n_layers + 1] into ent, the entries of every (parameter block,
+  // coefficient row) with a non-zero coefficient, in level order, slot numbers counted over all slots of a block;
+  // slot_par [n_blocks][NP] = the parameter an accumulator belongs to, or -1.  blk == nullptr: no column parameters
+  // (n_col = 0), the kernel instances without column code.
+  int n_blocks;
+  const int *blk, *ent_off;
+  const LevelEnt *ent;
+  const int *slot_par;
+  int n_par;
+  // ROW parameters (the kernel's ROWS = true instances; both null: none).  dabs / demi [n_gas][n_layers][n_pts]: the
+  // derivative spectra a row parameter acts through.  A row slot has, on every coefficient row it weights, one entry
+  // behind that row's level entries: level = kLevelEntRows, c = the weight.
+  const double *dabs, *demi;
+  // The output.  Spectra (lowres_scratch null): rad [n_rays][n_pts] (may be null), jac [n_rays][n_par][n_pts].
+  // Or the instrument bands in the epilogue (the kernel's BANDS = true instances): no spectra are written; the band
+  // integrals' partial sums per wave (64 points) go to lowres_scratch, the instrument step's scratch, whose weight table
+  // is in place (launch_lowres_weights; scratch sized for n_rays (1 + n_par) rows, fused), rows as launch_fold_dense
+  // orders them: row ray = the radiance, row n_rays + ray n_par + p = parameter p.  launch_lowres_sum_blocks finishes them.
+  // instr (bands only): the kernel's INSTR = true instances -- the scratch of an instr call, three weight tables; every
+  // ray has two more parameter rows in `part`, n_par and n_par + 1 of n_par + 2: the radiance's bands d / d centre and
+  // d / d ln width; n_par, here the number of state parameters, may then be 0, with one block whose slots are all unused.
+  double *rad, *jac;
+  const void *lowres_scratch;
+  int n_bands;
+  bool instr;
+};
+int launch_limb_jac_state(const StateLaunch &L, hipStream_t st);
 // Radiance budget (sr_limb_parts_kernel): the n_part parts and the background are n_part + 1 slots in blocks of
 // limb_parts_np(n_part); slot_level [n_blocks][NP]: >= 0 the first row of a level's E plane in the pair tables,
 // (2 L + 1) n_tab_rows, -1 - g the gas part of gas g,

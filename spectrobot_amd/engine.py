@@ -1227,21 +1227,30 @@ def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, co
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
     jac = torch.empty((los.n_rays, A.n_par, n_pts), dtype=torch.float64, device="cuda")
-    if level_gases is not None:
-        check(lib.sr_limb_rays_jac_state_gases_dev(*A.head_gases, ptr(rad), ptr(jac), _stream_ptr()), "sr_limb_rays_jac_state_gases_dev")
-        return rad, jac
-    if par_t is not None:
-        check(lib.sr_limb_rays_jac_state_rows_dev(*A.head, ptr(rad), ptr(jac), _stream_ptr()), "sr_limb_rays_jac_state_rows_dev")
-        return rad, jac
-    check(lib.sr_limb_rays_jac_state_dev(*A.head[:16], ptr(rad), ptr(jac), _stream_ptr()), "sr_limb_rays_jac_state_dev")
+    name = _state_entry(False, False, level_gases is not None, par_t is not None)
+    check(getattr(lib, name)(*A.args(name, ptr(rad), ptr(jac), _stream_ptr())), name)
     return rad, jac
 
 
+def _state_entry(bands, instrument, several, rows):
+    """The library entry of a mixed-state call: spectra or the instrument's bands, those with the instrument rows, the
+    level parameters of one level-factored gas or of a list of them; the spectra of one gas with or without row parameters
+    (the bands entries take both)."""
+    if bands:
+        return "sr_limb_rays_state_bands%s%s_dev" % ("_instr" if instrument else "", "_gases" if several else "")
+    return "sr_limb_rays_jac_state%s_dev" % ("_gases" if several else "_rows" if rows else "")
+
+
 class _StateArgs(object):
-    """What _state_args returns: a, e (the stacked coefficients), desc, n_col, n_lev, n_row, n_par, head -- the arguments of
-    sr_limb_rays_jac_state_rows_dev up to par_t, in its order (the first 16 are those of sr_limb_rays_jac_state_dev up to
-    par_c) -- and keep, the arrays and tensors the pointers in head point into.  With several level gases head_gases
-    instead: the arguments of sr_limb_rays_jac_state_gases_dev up to par_t."""
+    """What _state_args returns: a, e (the stacked coefficients), desc, n_col, n_lev, n_row, n_par, args(entry, *tail) --
+    the argument tuple of the named mixed-state entry, `tail` behind the parameters' (outputs or bands, stream) -- and
+    keep, the arrays and tensors its pointers point into."""
+
+    def args(self, entry, *tail):
+        batch, levels, rows = self._blocks
+        if entry == "sr_limb_rays_jac_state_dev":   # the one entry without row parameters
+            rows = ()
+        return batch + levels + rows + tail
 
 
 def _level_gases_args(level_gases, par_lgas, tab, coef_row, par_level, par_c, n_gas, n_layers, n_pts):
@@ -1335,14 +1344,12 @@ def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, ga
     A = _StateArgs()
     A.a, A.e, A.desc, A.n_col, A.n_lev, A.n_row, A.n_par = a, e, d, n_col, n_lev, n_row, n_col + n_lev + n_row
     A.keep = (par_gas, par_w, tab, cr, pl, pc, da, de, par_t)
-    A.head = (ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw, int(gas), ptr(tab) if n_lev else None, n_levels,
-              n_tab_rows, cr, n_lev, pl, pc, ptr(da), ptr(de), n_row, pt)
-    if several is not None:
+    levels = (int(gas), ptr(tab) if n_lev else None, n_levels, n_tab_rows, cr, n_lev, pl, pc)
+    if several is not None:   # (the entries for a list of level gases)
         arr, n_lgas, _, plg, pl, pc, keep = several
         A.keep = A.keep + (arr, keep)
-        A.head = None
-        A.head_gases = (ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw, n_lgas, arr, n_lev, plg, pl, pc, ptr(da),
-                        ptr(de), n_row, pt)
+        levels = (n_lgas, arr, n_lev, plg, pl, pc)
+    A._blocks = ((ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw), levels, (ptr(da), ptr(de), n_row, pt))
     return A
 
 
@@ -1381,17 +1388,9 @@ def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None
             raise ValueError("fov must be [n_rays / 3, 7] (three rays per pixel)")
         n_out = los.n_rays // 3
     out = np.empty((n_out, 1 + A.n_par + (2 if instrument else 0), centers_nm.size))
-    if instrument:
-        name = "sr_limb_rays_state_bands_instr_gases_dev" if level_gases is not None else "sr_limb_rays_state_bands_instr_dev"
-        check(getattr(lib, name)(*(A.head_gases if level_gases is not None else A.head), cp, wp, centers_nm.size, float(n_sigma),
-                                 _UNITS[out_units], fp, out.ctypes.data_as(dp), _stream_ptr()), name)
-        return out
-    if level_gases is not None:
-        check(lib.sr_limb_rays_state_bands_gases_dev(*A.head_gases, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp,
-                                                     out.ctypes.data_as(dp), _stream_ptr()), "sr_limb_rays_state_bands_gases_dev")
-        return out
-    check(lib.sr_limb_rays_state_bands_dev(*A.head, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp,
-                                           out.ctypes.data_as(dp), _stream_ptr()), "sr_limb_rays_state_bands_dev")
+    name = _state_entry(True, instrument, level_gases is not None, par_t is not None)
+    check(getattr(lib, name)(*A.args(name, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp, out.ctypes.data_as(dp),
+                                     _stream_ptr())), name)
     return out
 
 

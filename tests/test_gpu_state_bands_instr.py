@@ -175,8 +175,9 @@ def test_a_refused_call_leaves_out_untouched(eng):
 
     def call(widths=P["widths"], n_bands=17, n_sigma=5.0, units=0, o=out):
         wid = np.ascontiguousarray(widths, dtype=np.float64)
-        return _lib.lib.sr_limb_rays_state_bands_instr_dev(*A.head, cen.ctypes.data_as(_lib.dp), wid.ctypes.data_as(_lib.dp), n_bands,
-                                                           n_sigma, units, None, None if o is None else o.ctypes.data_as(_lib.dp), None)
+        return _lib.lib.sr_limb_rays_state_bands_instr_dev(*A.args("sr_limb_rays_state_bands_instr_dev", cen.ctypes.data_as(_lib.dp),
+                                                                   wid.ctypes.data_as(_lib.dp), n_bands, n_sigma, units, None,
+                                                                   None if o is None else o.ctypes.data_as(_lib.dp), None))
 
     bad_w = P["widths"].copy()
     bad_w[5] = 0.0
