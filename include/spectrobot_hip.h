@@ -769,7 +769,7 @@ int sr_hires_to_lowres_instr_shard_dev(const double *rad, int n_rays, int64_t n_
 
 /* Evaluation mode of the coefficient op.  Far region-1 wings by local Taylor expansions per box of grid
  * points (truncation <= sr_far_field_truncation_bound() of a line's own contribution: 1.6e-11 as built by default, degree
- * 19; 2.6e-13 with -DSR_KFD=22), near field exact, with the expansions built
+ * 19; 2.6e-13 with -DSR_KFD=22; a box takes a line from sr_far_field_min_distance() on), near field exact, with the expansions built
  * 2: from box pairs -- multipole moments of the lines of a source box (sr_s2m_kernel, sr_m2m_kernel)
  *    translated to every well-separated target box of the level (sr_m2l_kernel), per-line expansions only for
  *    the (line, box) pairs no box pair covers;
@@ -813,6 +813,13 @@ int sr_set_jac_layer_mode(int forward);
  * library as built (theta = 4, degree 19: 1.6e-11; -DSR_KFD=22: 2.6e-13).  The exact mode (sr_set_far_field(0)) has none.
  * What the far-field mode may differ by from the exact mode and from the CPU oracle beyond rounding. */
 double sr_far_field_truncation_bound(void);
+/* The admissibility rule that holds that bound, as the kernels apply it: a box of level `level` (64 << level grid points,
+ * 0 <= level < 5) takes a line by its expansion when the box's centre is at least this many grid points from the line's
+ * centre index -- 4 half-widths + pole_margin, the layer's pole margin in grid points (ceil(0.71 dw' / step) + 1 with
+ * the layer's largest Doppler width dw'), and from level 1 upwards a margin of 0.074 half-widths, without which the bound
+ * is missed at the box edge away from the line.  A multiple of 1/2 (box centres sit between two points).  Host arithmetic,
+ * the same expression the kernels compile; -1.0: level or margin out of range.  For tests and error models. */
+double sr_far_field_min_distance(int level, int pole_margin);
 /* sr_retrieval_forward_dev / _step_dev / _loop_dev with up to 8 parameters on a folded batch: 1 (default) the recursion
  * kernel integrates the instrument bands in its epilogue (partial sums per 64 points; the 1 + n_par spectra per ray
  * are never written: `buf` stays untouched); 0: spectra into `buf`, then sr_hires_to_lowres_shard_dev's kernels -- the

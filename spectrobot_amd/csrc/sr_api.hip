@@ -594,6 +594,11 @@ int sr_set_jac_layer_mode(int forward) {
 
 double sr_far_field_truncation_bound(void) { return 18.0 * std::pow((double)kTheta, -(double)(kFD + 1)); }
 
+double sr_far_field_min_distance(int level, int pole_margin) {
+  if (level < 0 || level >= kMaxFarLevels || pole_margin < 0 || pole_margin > (1 << 24)) return -1.0;
+  return 0.5 * (double)ff_thr2(level, pole_margin); // the kernels' own threshold (sr_kernels.hpp)
+}
+
 int sr_set_band_fusion(int on) {
   g_band_fusion.store(on ? 1 : 0);
   return SR_OK;

@@ -663,8 +663,9 @@ __global__ __launch_bounds__(64) void sr_abscoeff_cores_kernel(
 // recurrence (power-series division of a quadratic by a quartic), the
 // coefficients of all such lines are summed per box (lanes = lines), and each
 // point evaluates ONE polynomial per level instead of one rational per line.
-// Truncation at degree kFD = 22 (kTheta = 4) is <= 2.6e-13 of the line's own contribution
-// (worst case, nearest admissible line, box edge).  Boxes are nested (width
+// Truncation at degree kFD = 19 (kTheta = 4) is <= 18 x 4^-20 = 1.6e-11 of the line's own contribution
+// (worst case: nearest admissible line, the box edge AWAY from it; the admissible distance that holds it is
+// ff_thr2, sr_kernels.hpp, with its derivation; -DSR_KFD=22: 2.6e-13).  Boxes are nested (width
 // 64 << level); a (line, slot) pair is owned by the highest admissible level
 // (admissibility is monotone down the hierarchy) or, if none, by the exact
 // near-field kernel.  All ownership tests are integer and shared by the kernels.
@@ -674,21 +675,38 @@ __device__ inline bool ff_admissible(int j1, int il, int ir, int blo, int bhi, i
   const int d2 = blo + bhi - 2 * (j1 + kHalf); // twice (box centre - line centre)
   return (d2 < 0 ? -d2 : d2) >= thr2;
 }
-__device__ inline int ff_thr2(int level, int pm) { return kTheta * (64 << level) + 2 * pm; }
 
 // Box-pair mode (FarParams::m2l).  Source box s and target box t of level l, both counted in boxes of 64 << l
 // points from g_lo, o = t - s: the pair is VALID when every line centred in s sees all of t in one region-1 wing
 // inside its window, far enough for the multipole / local pair of expansions: gap between the boxes >= the widest
-// zone of the layer (zreq) and >= 2 box widths (truncation ratio 1/5: (1/5)^(kFD+1) ~ 1e-16), more where the poles
+// zone of the layer (zreq) and >= 2 box widths, more where the poles
 // of the layer's lines (pms grid points from their centres) are not small against the box (m2l_separated).
 // Validity is monotone down the hierarchy (children of a valid pair are valid), so a pair is TRANSLATED at level
 // l iff it is valid there and its parent pair is not, and a level-0 pair is covered by some level iff it is valid
 // at level 0.  Valid pairs are admissible for every line of s (ff_admissible at level 0), so the near kernels
 // need not know about box pairs at all.
+// The separation ratio rho = (h + pole) / (distance of the centres - h), h = W / 2, in hundredths.  What it bounds is the
+// MULTIPOLE series, which stops at order kFD: a singularity h + pole from the source centre, seen from the nearest target
+// point on the other side of that centre, is sum_m (m + 1) (-rho)^m with the terms m <= kFD - 2 kept; what is dropped is
+// (kFD + (kFD - 1) rho) rho^(kFD-1) of the line's own value there -- 1.44e-11 at rho = 0.21 and degree 19 (1.6e-13 at 22),
+// to which the local expansion of the target box adds (kFD + 2 + (kFD + 1) r) r^(kFD+1), r = h / (distance of the
+// centres - h - pole) <= rho: 7e-13.  (Until the far field was held to one line's own contribution the ratio was 0.27,
+// set when the degree was 22 by 0.27^(kFD+1): at degree 19 a Doppler line on the last point of its source box measured
+// 1.9e-11 at the nearest point of the first valid target box, tests/test_gpu_farfield_lines.py; 0.21: 6.4e-12, and the
+// first valid offset of level 0 is 4 where it was 3 -- headline step 5.055 -> 5.090 ms, +0.7 %, same box, interleaved.)
+constexpr int kM2LRatioPct = 21;
+constexpr long double m2l_dropped_over_bound() {
+  const long double rho = kM2LRatioPct / 100.0L;
+  long double mp = 1.0L, lc = 1.0L, bound = 18.0L;
+  for (int n = 0; n < kFD - 1; ++n) mp *= rho;
+  for (int n = 0; n <= kFD; ++n) { lc *= rho; bound /= kTheta; }
+  return ((kFD + (kFD - 1) * rho) * mp + (kFD + 2 + (kFD + 1) * rho) * lc) / bound;
+}
+static_assert(m2l_dropped_over_bound() <= 1.0L, "the box pairs' separation ratio does not hold the truncation bound at this degree");
 __device__ inline bool m2l_separated(int level, int a, int zreq, int pms) { // a = |o|
   const int W = 64 << level;
-  // gap >= zone and >= two boxes; (h + pole) <= 0.27 (distance of the centres - h), h = W / 2: 0.27^(kFD+1) = 8e-14
-  return a >= 3 && (a - 1) * W >= zreq && 100 * (W + 2 * pms) <= 27 * (2 * a - 1) * W;
+  // gap >= zone and >= two boxes; (h + pole) <= 0.21 (distance of the centres - h)
+  return a >= 3 && (a - 1) * W >= zreq && 100 * (W + 2 * pms) <= kM2LRatioPct * (2 * a - 1) * W;
 }
 __device__ inline bool m2l_valid(int level, int o, int zreq, int pms) {
   const int W = 64 << level, a = o < 0 ? -o : o;
@@ -825,7 +843,7 @@ __global__ __launch_bounds__(64) void sr_farfield_kernel(const FastRec *__restri
 
   // candidate centre intervals [lo, hi] (inclusive), see DESIGN.md
   int clo[4], chi[4], nr, n_extra = 0;
-  const int mid = blo + h, near_in = kTheta * h + pm;
+  const int mid = blo + h, near_in = thr2 / 2; // candidates: no closer than the admissible distance, rounded down
   if (M2L) {
     // the (line, box) pairs no box pair covers: source boxes closer than the first valid offset, and the two
     // source boxes on either side whose lines' windows end inside or just beyond this box (|o| = 101, 102)
@@ -842,7 +860,8 @@ __global__ __launch_bounds__(64) void sr_farfield_kernel(const FastRec *__restri
     clo[1] = mid + near_in - 2; chi[1] = bhi + kHalf + 1;
     nr = 2;
   } else {
-    const int bn = max(2 * kTheta * h + h + pm, zm + 3 * h) + 2;
+    // beyond bn a line is the parent's: the parent's centre is h from this box's, its admissible distance thr2p / 2
+    const int bn = max((thr2p + 1) / 2 + h, zm + 3 * h) + 2;
     clo[0] = plo - kHalf; chi[0] = phi - (kHalf - 1) + 1;       // window end inside the parent
     clo[1] = mid - bn - 1; chi[1] = mid - near_in + 1;           // left near band
     clo[2] = mid + near_in - 2; chi[2] = mid + bn + 1;           // right near band
@@ -1028,14 +1047,14 @@ __device__ __forceinline__ void farfield_rows_body(const FastRec *__restrict__ f
   __shared__ int rs_all[NW][4], re_all[NW][4];
   int *rs = rs_all[threadIdx.x >> 6], *re = re_all[threadIdx.x >> 6];
   int nr;
-  const int mid = blo + h, near_in = kTheta * h + pm_min;
+  const int mid = blo + h, near_in = ff_thr2(level, pm_min) / 2;
   if (top) {
     const int a0 = lower_bound_ic(ix, blo - kHalf - 1), b0 = lower_bound_ic(ix, mid - near_in + 1 + 1);
     const int a1 = lower_bound_ic(ix, mid + near_in - 2), b1 = lower_bound_ic(ix, bhi + kHalf + 1 + 1);
     rs[0] = a0; re[0] = b0; rs[1] = a1; re[1] = b1;
     nr = 2;
   } else {
-    const int bn = max(2 * kTheta * h + h + pm_max, zm_max + 3 * h) + 2;
+    const int bn = max((ff_thr2(level + 1, pm_max) + 1) / 2 + h, zm_max + 3 * h) + 2; // (the parent's margin: see sr_farfield_kernel)
     const int a0 = lower_bound_ic(ix, plo - kHalf), b0 = lower_bound_ic(ix, phi - (kHalf - 1) + 1 + 1); // window end inside the parent
     const int a1 = lower_bound_ic(ix, mid - bn - 1), b1 = lower_bound_ic(ix, mid - near_in + 1 + 1);   // left near band
     const int a2 = lower_bound_ic(ix, mid + near_in - 2), b2 = lower_bound_ic(ix, mid + bn + 1 + 1);   // right near band

@@ -63,7 +63,8 @@ struct IcIndex {
 
 // Far-field (local expansion) hierarchy over one shard: level l has boxes of
 // 64 << l points starting at g_lo.
-// (kTheta, kFD): the truncation bound is 18 * kTheta^-(kFD+1) of a line's own contribution;
+// (kTheta, kFD): the truncation bound is 18 * kTheta^-(kFD+1) of a line's own contribution (what the admissible
+// distance has to be for it: ff_thr2 below);
 // a smaller kTheta shrinks the exactly evaluated near field, a larger kFD costs far-field
 // time and registers.  Config 2, sum of the coefficient kernels (tools/sweep_farfield.sh):
 // (8,14) 18.2 ms and (5,19) 17.2 ms with the first far-field kernel; with the streamed
@@ -87,6 +88,50 @@ constexpr int kTheta = SR_KTHETA; // admissible distance, in box half-widths
 constexpr int kFD = SR_KFD;       // expansion degree
 constexpr int kFC = kFD + 1;   // coefficients per box and output
 constexpr int kMaxFarLevels = 5;
+// The admissible distance.  A (line, box) pair of level l (box of W = 64 << l points, half-width h = W / 2) may be
+// expanded when the box centre is at least  kTheta h + pm (+ the level's margin)  grid points from the line's centre
+// index; ff_thr2 is TWICE that (box centres sit on half points), the one expression every kernel and the host's
+// sr_far_field_min_distance share.  pm: the layer's pole margin (sr_api.hip, fill_layer_stage).
+// What the bound 18 kTheta^-(kFD+1) asks of it.  Beyond pm the wing is ~ 1/x^2; for a line D points from the box centre,
+// t = (j - centre) / h in [-1, 1] and r = h / D:  (D + h t)^-2 = D^-2 sum_n (n + 1) (-r t)^n, and what is left after
+// degree d, relative to the line's own value at the point, sum_(n > d) (n + 1) r^n = r^(d+1) (d + 2 - (d + 1) r) / (1 - r)^2, is
+//   edge facing the line (t = -1):  (d + 2 - (d + 1) r) r^(d+1)     (4, 19) at r = 1/4: 16 x 4^-20
+//   edge away from it   (t = +1):  (d + 2 + (d + 1) r) r^(d+1)                          26 x 4^-20 = 1.44 x the bound
+// (the absolute error is larger at the facing edge, the line itself smaller at the far one).  At r = 1/kTheta the
+// constant 18 holds for the facing edge only; for both it takes r <= r*, the root of
+// (d + 2 + (d + 1) r) (kTheta r)^(d+1) = 18: (4, 19) r* = 0.245488, D >= h / r* = (4 + 0.07352) h; (4, 22) 0.244642,
+// (4 + 0.08761) h.  kFarMarginQ10 is that excess over kTheta in 1/1024 of h, rounded up: 76 and 90 (bisection in long
+// double at compile time, checked against these two below).
+// Levels >= 1 carry the margin.  Level 0 does not: there the "+ 1" of pm and the half-point inset of the outermost
+// points (t = +-(1 - 1/64)) are worth more than the margin's 2.4 points -- 1.36e-11 of 1.64e-11 at degree 19, 2.25e-13
+// of 2.56e-13 at 22, worst over the panel of tests/test_farfield_reference_host.py -- so the near kernels, which know level 0 only, the box
+// pairs ("valid pairs are admissible at level 0") and the default dense path, whose per-line expansions are level 0's,
+// stay as they were.  Ownership stays monotone down the hierarchy: a parent admissible at (2 kTheta + 2 m) h puts its
+// children at >= (2 kTheta - 1 + 2 m) h >= (kTheta + m) h.
+constexpr long double ff_far_edge_over_bound(long double r) {
+  long double p = 1.0L;
+  for (int n = 0; n <= kFD; ++n) p *= kTheta * r;
+  return (kFD + 2 + (kFD + 1) * r) * p / 18.0L;
+}
+constexpr int ff_margin_q10() {
+  long double lo = 0.5L / kTheta, hi = 1.0L / kTheta; // over_bound(lo) < 1 <= over_bound(hi), increasing in r
+  for (int i = 0; i < 80; ++i) {
+    const long double mid = 0.5L * (lo + hi);
+    (ff_far_edge_over_bound(mid) <= 1.0L ? lo : hi) = mid;
+  }
+  const long double q = 1024.0L * (1.0L / lo - kTheta);
+  const int qi = (int)q;
+  return qi + (qi < q ? 1 : 0);
+}
+constexpr int kFarMarginQ10 = ff_margin_q10();
+// kTheta = 5 computes wrong results (profiles/r06_far_field_order.txt); the degrees are those whose level 0 was checked
+static_assert(kTheta == 4, "the far field is built and checked for kTheta = 4 only");
+static_assert((kFD == 19 && kFarMarginQ10 == 76) || (kFD == 22 && kFarMarginQ10 == 90),
+              "far-field degree without a checked admissible distance: 19 (default) or 22");
+__host__ __device__ constexpr int ff_thr2(int level, int pm) {
+  const int W = 64 << level;
+  return kTheta * W + 2 * pm + (level > 0 ? (W * kFarMarginQ10 + 1023) / 1024 : 0);
+}
 #ifndef SR_FAR_SUPER
 #define SR_FAR_SUPER 16384
 #endif

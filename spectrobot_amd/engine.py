@@ -1625,6 +1625,15 @@ def far_field_truncation_bound():
     return float(lib.sr_far_field_truncation_bound())
 
 
+def far_field_min_distance(level, pole_margin):
+    """Grid points between a level-`level` box's centre and a line's centre index from which the box takes the line by
+    its expansion, as the kernels decide it (sr_far_field_min_distance); pole_margin: the layer's, in grid points."""
+    d = float(lib.sr_far_field_min_distance(int(level), int(pole_margin)))
+    if d < 0.0:
+        raise ValueError("far_field_min_distance: level in [0, 5) and pole_margin >= 0")
+    return d
+
+
 def far_field_degree(theta=4):
     """The expansion degree the library was built with (from its truncation bound 18 theta^-(degree + 1))."""
     import math
