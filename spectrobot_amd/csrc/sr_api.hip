@@ -338,7 +338,7 @@ struct CoefWork {
   // [2]: with sr_set_overlap(1) the tables of call c+1 are prepared (on far_st) while the kernels
   // of call c still read theirs
   Stager s_layers[2];
-  DevBuf d_fast[2], d_cold[2], d_coef[2], d_zone, d_zone2[2], d_mom[2], d_outer_recs;
+  DevBuf d_fast[2], d_cold[2], d_coef[2], d_zone2[2], d_mom[2], d_outer_recs;
   // The TWO internal streams of the pipelined schedule.  On each, stream order IS the order the phased schedule runs
   // its kernels in anyway, so the pair (with the caller's stream) needs three hardware queues, not six:
   //   far_st:  staging copy + prep(c) -> level-0 pass(c) -> S2M, M2M(c) -> M2L(c) [-> L2L, far-only passes] -> prep(c + 1) ..
@@ -360,7 +360,7 @@ struct CoefWork {
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int n_timed = 0; // kernels timed in the last call
   bool timed = false;
-  // d_coef / d_zone / d_counts and (without overlap) the single table set are shared by consecutive
+  // d_coef / d_counts and (without overlap) the single table set are shared by consecutive
   // calls: every call first makes its streams wait for the end of the previous call on this handle,
   // whatever stream that one ran on (ev_last_done), so calls on unrelated caller streams are safe.
   hipEvent_t ev_last_done = nullptr;
@@ -370,6 +370,30 @@ struct CoefWork {
   int init() {
     for (auto &e : ev) HIPCHK(hipEventCreate(&e));
     HIPCHK(hipEventCreateWithFlags(&ev_last_done, hipEventDisableTiming));
+    return SR_OK;
+  }
+  // the events of the pipelined schedule, on its first call
+  int pipeline_events() {
+    if (ev_op0) return SR_OK;
+    HIPCHK(hipEventCreateWithFlags(&ev_op0, hipEventDefault));
+    for (int i = 0; i < 2; ++i) {
+      HIPCHK(hipEventCreateWithFlags(&ev_prep_done[i], hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&ev_tables_free[i], hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&ev_far_done[i], hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&ev_zones_done[i], hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&ev_s2m_done[i], hipEventDisableTiming));
+    }
+    return SR_OK;
+  }
+  // The end of a call whose last kernel went to `st`: table set b (-1: none read) is free behind it, where the
+  // pipeline's events exist, and the next call on the handle waits for ev_last_done
+  int end_call(hipStream_t st, int b) {
+    if (b >= 0 && ev_tables_free[b]) {
+      HIPCHK(hipEventRecord(ev_tables_free[b], st));
+      free_recorded[b] = true;
+    }
+    HIPCHK(hipEventRecord(ev_last_done, st));
+    last_done_recorded = true;
     return SR_OK;
   }
   int pipeline_streams(hipStream_t *far, hipStream_t *near) {
@@ -406,7 +430,6 @@ struct CoefWork {
     d_outer_recs.release();
     stream_destroy(far_st); // (its own pair: a borrowed one, streams_of, is the owner's to destroy)
     stream_destroy(near_st);
-    d_zone.release();
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
   }
@@ -899,46 +922,36 @@ int sr_lineset_destroy(sr_lineset *ls) {
 
 } // extern "C"
 
-// Translation operator of the box-pair far field: built once per process and device (0.8 MB).
+// A table computed on the host and uploaded once per process and device (never freed): n doubles, written by fill
+struct HostTableDev {
+  std::mutex mu;
+  std::map<int, double *> tabs;
+  int get(size_t n, void (*fill)(double *), const double **out) {
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = tabs.find(dev);
+    if (it == tabs.end()) {
+      std::vector<double> h(n);
+      fill(h.data());
+      double *d = nullptr;
+      HIPCHK(hipMalloc(reinterpret_cast<void **>(&d), sizeof(double) * n));
+      HIPCHK(hipMemcpy(d, h.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+      it = tabs.emplace(dev, d).first;
+    }
+    *out = it->second;
+    return SR_OK;
+  }
+};
+// Translation operator of the box-pair far field (0.8 MB)
 static int m2l_table_dev(const double **out) {
-  static std::mutex mu;
-  static std::map<int, double *> tabs;
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = tabs.find(dev);
-  if (it == tabs.end()) {
-    const size_t n = (size_t)2 * kM2LOffsets * kM2LQ * kM2LRow;
-    std::vector<double> h(n);
-    m2l_table_host(h.data());
-    double *d = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&d), sizeof(double) * n));
-    HIPCHK(hipMemcpy(d, h.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-    it = tabs.emplace(dev, d).first;
-  }
-  *out = it->second;
-  return SR_OK;
+  static HostTableDev t;
+  return t.get((size_t)2 * kM2LOffsets * kM2LQ * kM2LRow, m2l_table_host, out);
 }
-
-// Downward-pass operator of the hierarchy (sr_l2l_kernel): built once per process and device (8 KB).
+// Downward-pass operator of the hierarchy (sr_l2l_kernel, 8 KB)
 static int l2l_table_dev(const double **out) {
-  static std::mutex mu;
-  static std::map<int, double *> tabs;
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = tabs.find(dev);
-  if (it == tabs.end()) {
-    const size_t n = (size_t)2 * kFC * kFC;
-    std::vector<double> h(n);
-    l2l_table_host(h.data());
-    double *d = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&d), sizeof(double) * n));
-    HIPCHK(hipMemcpy(d, h.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-    it = tabs.emplace(dev, d).first;
-  }
-  *out = it->second;
-  return SR_OK;
+  static HostTableDev t;
+  return t.get((size_t)2 * kFC * kFC, l2l_table_host, out);
 }
 
 // Per-layer scalars of a call (host, fp64): T, P [atm], 296/T, sqrt(2 N_A k T ln2 / MM), the same at the boundary
@@ -1017,19 +1030,40 @@ static int fill_layer_stage(const sr_lineset *ls, const sr_lineset *mar, const s
   }
   return SR_OK;
 }
-// The device view of a pushed layer stage.  d_pm: [3][n_layers] pole margin | source pole radius | widest zone.
-static LayersDev layers_dev_of(const double *dl, int nl, int npop, bool frozen, bool linear_w, const int **d_pm) {
+// The device view of a pushed layer stage: the scalars, and the three int rows behind them by name
+struct LayerStage {
   LayersDev A;
+  const int *pm, *pm_src, *zmax; // [n_layers] each: pole margin | source pole radius | widest zone (host bounds, see fill_layer_stage)
+};
+// A call's layer stage through slot S: prepare, fill (host, fp64), push on `st`.  wait_for: an event `st` waits for
+// between the fill and the copy (what last read the slot's device mirror), or nullptr.  boundaries = false: the call
+// places no region boundaries (sr_line_strengths_dev), so frozen ones do not apply.
+static int stage_layers(Stager &S, const sr_lineset *ls, const sr_lineset *mar, const sr_lineset *bown, const sr_layers_desc *atm,
+                        double q_ref, bool boundaries, hipEvent_t wait_for, hipStream_t st, LayerStage *out) {
+  const int nl = atm->n_layers, npop = ls->n_levels > 0 ? ls->n_levels : 1;
+  const size_t bytes = layer_stage_bytes(nl, npop);
+  int rc = S.prepare(bytes);
+  if (rc) return rc;
+  rc = fill_layer_stage(ls, mar, bown, atm, S.host<double>(), q_ref);
+  if (rc) return rc;
+  if (wait_for) HIPCHK(hipStreamWaitEvent(st, wait_for, 0));
+  rc = S.push(bytes, st);
+  if (rc) return rc;
+  const bool frozen = boundaries && !bown->bounds_temps.empty(); // sr_lineset_set_bounds_temps
+  const double *dl = S.d.as<double>();
+  LayersDev &A = out->A;
   A.temps = dl; A.p_atm = dl + nl; A.trat = dl + 2 * nl; A.sqk = dl + 3 * nl; A.ltrat = dl + 4 * nl;
   A.ltrat_b = dl + 5 * nl; A.sqk_b = dl + 6 * nl; A.temps_b = dl + 7 * nl; A.pop = dl + 8 * nl;
   A.qrat = A.pop + (size_t)nl * npop; A.rvib = A.qrat + nl;
   A.frozen = frozen ? 1 : 0;
-  A.linear_w = frozen && linear_w ? 1 : 0;
+  A.linear_w = frozen && bown->linear_weights ? 1 : 0;
   A.n_layers = nl; A.n_pop = npop;
   A.sqrt_ln2 = std::sqrt(kLn2);            // spect_classes.py:1999
   A.sqrt_pi_ln2 = std::sqrt(kPi / kLn2);   // :1997
-  *d_pm = reinterpret_cast<const int *>(dl + layer_stage_doubles(nl, npop));
-  return A;
+  out->pm = reinterpret_cast<const int *>(dl + layer_stage_doubles(nl, npop));
+  out->pm_src = out->pm + nl;
+  out->zmax = out->pm + 2 * nl;
+  return SR_OK;
 }
 // The far-field box hierarchy of a shard of n_pts points (the part of FarParams every kernel agrees on)
 static void far_hierarchy(size_t n_pts, int nl, FarParams *fp) {
@@ -1045,6 +1079,114 @@ static void far_hierarchy(size_t n_pts, int nl, FarParams *fp) {
     fp->n_boxes_total += fp->box_count[lv];
   }
 }
+// The FarParams of a pass.  kind: per-line expansions at every level, the same by the sparse sets' own kernel
+// (sr_farfield_rows_kernel: a box for eight layers per wave), or box pairs with the layout of their source boxes
+// (*n_src_total of them per layer: the caller sets mom and tab).  folded0 = 0 and no lines beyond the grid ends:
+// coef_op sets those for its own passes.
+enum FarKind { kFarPerLine, kFarPerLineRows, kFarBoxPairs };
+static FarParams far_params(size_t n_pts, const LayerStage &S, FarKind kind, double *coef, int *n_src_total = nullptr) {
+  FarParams fp;
+  far_hierarchy(n_pts, S.A.n_layers, &fp);
+  fp.pm = S.pm; fp.pm_src = S.pm_src; fp.coef = coef;
+  fp.m2l = kind == kFarBoxPairs ? 1 : 0;
+  fp.rows = kind == kFarPerLineRows ? 1 : 0;
+  fp.disp_lo_end = fp.disp_hi_begin = 0;
+  fp.mom = nullptr; fp.tab = nullptr;
+  // level-0 source boxes: kSrcPad left of the shard, the shard, the window half-width right of it; a whole
+  // number of widest boxes, so that every level halves exactly
+  const int top_boxes = fp.m2l ? (int)(((size_t)kSrcPad * 64 + n_pts + kHalf + 64) >> (6 + kMaxFarLevels - 1)) + 1 : 0;
+  int total = 0;
+  for (int lv = 0; lv < kMaxFarLevels; ++lv) {
+    fp.n_src[lv] = top_boxes << (kMaxFarLevels - 1 - lv);
+    fp.src_off[lv] = total;
+    total += fp.n_src[lv];
+  }
+  if (n_src_total) *n_src_total = total;
+  return fp;
+}
+// Sparse line sets (the per-level sub-linesets of the pair tables: 9-15 % of a hot-band list): the box-pair far field
+// has a fixed cost per box and layer -- S2M, M2M, M2L over every box whatever it holds -- that the per-line
+// expansions at every level (mode 1) do not have: below ~0.37 lines per grid point they are the faster route
+// (tools/ff_mode_crossover.py: 0.3: 2.54 vs 2.61 ms, 0.4: 3.07 vs 3.03, 1.0: 6.74 vs 5.62; the 12 pair tables of the
+// configs[1] list 19.1 vs 21.5 ms).  Mode 3 (the default) switches at 0.35.
+static bool is_sparse_set(const sr_lineset *ls, int far_mode) {
+  constexpr double sparse_thr = 0.35;
+  return far_mode == 3 && (double)ls->n_lines < sparse_thr * (double)ls->gp.n_grid;
+}
+// The lines whose window [ic-6505, ic+6504] meets the shard [g_lo, g_hi): line_lo / n_sub of the lineset's centre index
+static IcIndex shard_lines(const sr_lineset *ls, int64_t g_lo, int64_t g_hi) {
+  const auto lo_it = std::lower_bound(ls->ic.begin(), ls->ic.end(), (int)g_lo - (kHalf - 1));
+  const auto hi_it = std::upper_bound(ls->ic.begin(), ls->ic.end(), (int)g_hi - 1 + kHalf);
+  return IcIndex{ls->d_first.as<int>(), ls->first_x0, ls->first_n, (int)(lo_it - ls->ic.begin()), (int)(hi_it - lo_it)};
+}
+
+// The argument checks of a coefficient call: handle, layers, shard and the (T, P) of every layer.  entry_only: what
+// the entry points of the level tables need before they size their scratch -- the rest is answered by coef_op /
+// mc_pass below them, which check in full.
+static int check_coef_call(const sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi, bool entry_only = false) {
+  if (!ls || !atm || atm->n_layers <= 0 || g_lo < 0 || g_lo >= g_hi) return SR_ERR_ARG;
+  if (entry_only) return SR_OK;
+  if (!atm->temps || !atm->press || g_hi > ls->gp.n_grid) return SR_ERR_ARG;
+  for (int k = 0; k < atm->n_layers; ++k)
+    if (!(atm->temps[k] > 0.0) || !(atm->press[k] >= 0.0)) return SR_ERR_ARG;
+  return SR_OK;
+}
+
+// The layers of a call in batches of at most `batch`: fn(sub, k0) for every [k0, k0 + sub.n_layers), with the batch's
+// slice of temps / press / q_part and of the vibrational temperatures (keep_tvib; else none: no populations enter the
+// level spectra), and with bown->bounds_temps (sr_lineset_set_bounds_temps) cut to the batch, restored on every way out.
+template <class Fn>
+static int for_layer_batches(const sr_layers_desc *atm, sr_lineset *bown, int nlev, bool keep_tvib, int batch, Fn fn) {
+  const int nl = atm->n_layers;
+  if (!bown->bounds_temps.empty() && (int)bown->bounds_temps.size() != nl) {
+    g_err = "sr_lineset_set_bounds_temps was given another number of layers than this call";
+    return SR_ERR_ARG;
+  }
+  sr_layers_desc sub = *atm;
+  if (!keep_tvib) sub.tvib = nullptr;
+  if (batch >= nl) return fn(sub, 0);
+  const std::vector<double> bounds_all = bown->bounds_temps;
+  struct Restore {
+    sr_lineset *ls; const std::vector<double> &all;
+    ~Restore() { ls->bounds_temps = all; }
+  } restore{bown, bounds_all};
+  std::vector<double> tv;
+  for (int k0 = 0; k0 < nl; k0 += batch) {
+    const int n = sub.n_layers = std::min(batch, nl - k0);
+    sub.temps = atm->temps + k0;
+    sub.press = atm->press + k0;
+    sub.q_part = atm->q_part ? atm->q_part + k0 : nullptr;
+    if (keep_tvib && atm->tvib) { // [n_levels][n_layers] -> the batch's columns
+      tv.resize((size_t)nlev * n);
+      for (int lv = 0; lv < nlev; ++lv)
+        std::copy(atm->tvib + (size_t)lv * nl + k0, atm->tvib + (size_t)lv * nl + k0 + n, tv.begin() + (size_t)lv * n);
+      sub.tvib = tv.data();
+    }
+    if (!bounds_all.empty()) bown->bounds_temps.assign(bounds_all.begin() + k0, bounds_all.begin() + k0 + n);
+    const int rc = fn(sub, k0);
+    if (rc) return rc;
+  }
+  return SR_OK;
+}
+
+// Bytes per layer of a coefficient op.  The per-(line, layer) record tables cost 128 B each, the far-field scratch of a
+// layer (local coefficients of all levels' target boxes, multipole moments of the source boxes) 1 KB per 64 grid points
+// + 1.3 KB per 64 points of grid and window halo; a long LOS (the reference allows imxstp = 8000 steps) is processed
+// in layer batches that keep them under g_table_budget.
+static size_t coef_bytes_per_layer(const sr_lineset *ls, size_t n_pts, int far_field, int overlap) {
+  const size_t far_per_layer = !far_field ? 0
+      : (2 * (n_pts / 64 + 2)) * (size_t)(2 * kFC) * sizeof(double) +
+        (far_field == 2 ? (2 * ((n_pts + 64 * kSrcPad + kHalf) / 64 + 16)) * (size_t)kMomPerBox * sizeof(double) : 0);
+  return (size_t)std::max<int64_t>(ls->n_lines, 1) * (sizeof(FastRec) + sizeof(ColdRec)) * (overlap ? 2 : 1) + far_per_layer // two table sets with overlap
+         + (overlap ? 2 * sizeof(double) * n_pts : 0)           // the zones kernel's private sums (small shards)
+         + sizeof(OuterRec) * (size_t)std::max(ls->n_outer, 0); // records of the outer lines
+}
+// Bytes per row of a multi-channel pass: the full list's records + every far pass's coefficients (coef_row doubles per
+// pass and row) + what the largest level pass needs of the shared CoefWork (two table sets, far-field scratch)
+static size_t mc_bytes_per_row(const sr_lineset *ls, size_t n_pts, size_t coef_row, int n_far) {
+  return (size_t)std::max<int64_t>(ls->n_lines, 1) * (sizeof(FastRec) + sizeof(ColdRec)) * 4 +
+         sizeof(double) * coef_row * (size_t)(n_far + 2) + 4 * ((n_pts + 64 * kSrcPad + kHalf) / 64 + 16) * (size_t)kMomPerBox * sizeof(double);
+}
 
 // Options of coef_op beyond the public entry points'.
 //   far_coef: a FAR-ONLY pass for the multi-channel route (mc_pass) -- tables and the far-field chain only, the
@@ -1057,102 +1199,133 @@ struct CoefOpt {
   bool *far_has = nullptr;
   double q_ref = 0.0;
 };
-
-// The coefficient op with the output weights of `W` (sr_kernels.hpp); the public entry points below
-// choose W.  abs_out / emi_out: DEVICE [n_layers][g_hi - g_lo].
-static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi, double *abs_out,
-                   double *emi_out, void *stream, const WeightMode W, const CoefOpt opt = CoefOpt()) {
-  const bool far_only = opt.far_coef != nullptr;
-  if (!ls || !atm || (!far_only && (!abs_out || !emi_out))) return SR_ERR_ARG;
-  if (atm->n_layers <= 0 || !atm->temps || !atm->press) return SR_ERR_ARG;
-  if (g_lo < 0 || g_hi > ls->gp.n_grid || g_lo >= g_hi) return SR_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  CoefWork &w = *ls->work;
-  // frozen region boundaries are set on the handle the caller holds: a per-level sub-lineset follows its parent's
-  sr_lineset *const bown = ls->parent ? ls->parent : ls;
-  const int nl = atm->n_layers, nlev = ls->n_levels, npop = nlev > 0 ? nlev : 1;
-  for (int k = 0; k < nl; ++k)
-    if (!(atm->temps[k] > 0.0) || !(atm->press[k] >= 0.0)) return SR_ERR_ARG;
-  // one snapshot of the mode switches per call
-  const int variant = g_variant.load();
-  const bool timing = g_timing.load() != 0;
-  // Sparse line sets (the per-level sub-linesets of the pair tables: 9-15 % of a hot-band list): the box-pair far field
-  // has a fixed cost per box and layer -- S2M, M2M, M2L over every box whatever it holds -- that the per-line
-  // expansions at every level (mode 1) do not have: below ~0.37 lines per grid point they are the faster route
-  // (tools/ff_mode_crossover.py: 0.3: 2.54 vs 2.61 ms, 0.4: 3.07 vs 3.03, 1.0: 6.74 vs 5.62; the 12 pair tables of the
-  // configs[1] list 19.1 vs 21.5 ms).  Mode 3 (the default) switches at 0.35.
-  constexpr double sparse_thr = 0.35;
-  const int far_mode = g_far_field.load();
-  const bool sparse_set = far_mode == 3 && (double)ls->n_lines < sparse_thr * (double)ls->gp.n_grid;
-  const int far_field = far_mode == 3 ? (sparse_set ? 1 : 2) : far_mode;
-  if (far_only && !far_field) return SR_ERR_UNSUPPORTED; // (mc_pass takes the per-level route in the exact mode)
-  const bool counting = g_counting.load() != 0 && far_field;
+// One snapshot of the mode switches per call (coef_op), shared by its layer batches
+struct CoefModes {
+  int variant, far_field; // far_field: 0 exact, 1 per-line expansions, 2 box pairs (mode 3 resolved: is_sparse_set)
+  bool timing, sparse_set, counting;
   // 1: the decoupled, phased pipeline (far-field modes); 0: the kernels one after the other on the caller's stream, on
   // table set 0 -- sr_set_overlap(0), the exact mode and the counting passes (whose counters are zeroed and read on the
   // caller's stream).  (Round 3's order, overlap 2, was the A/B partner of rounds 4-5 and is gone.)
-  const int overlap = (g_overlap.load() != 0 && far_field && !counting) ? 1 : 0;
-  const size_t table_budget = g_table_budget.load();
+  int overlap;
+  int reps[6]; // launches of each kernel (measurement hook, serial schedule only: see g_repeat_kernel)
+};
+// What the kernels of one far-field call share, whichever schedule issues them
+struct CoefKernels {
+  CoefWork &w;
+  int b; // table set
+  ShardTables t;
+  FarParams fp;
+  const GridParams &gp;
+  bool far_only, timing;
+  double *abs_out, *emi_out;
+  unsigned long long *cnt;
+  hipStream_t st;  // the caller's stream
+  const int *reps; // CoefModes::reps
+};
 
-  // The per-(line, layer) record tables cost 128 B each, the far-field scratch of a layer (local coefficients
-  // of all levels' target boxes, multipole moments of the source boxes) 1 KB per 64 grid points + 1.3 KB per 64
-  // points of grid and window halo; a long LOS (the reference allows imxstp = 8000 steps) is processed in layer
-  // batches that keep them under g_table_budget.
-  {
-    const size_t n_pts_b = (size_t)(g_hi - g_lo);
-    const size_t far_per_layer = !far_field ? 0
-        : (2 * (n_pts_b / 64 + 2)) * (size_t)(2 * kFC) * sizeof(double) +
-          (far_field == 2 ? (2 * ((n_pts_b + 64 * kSrcPad + kHalf) / 64 + 16)) * (size_t)kMomPerBox * sizeof(double) : 0);
-    const size_t per_layer = (size_t)std::max<int64_t>(ls->n_lines, 1) * (sizeof(FastRec) + sizeof(ColdRec)) *
-                                 (overlap ? 2 : 1) + far_per_layer // two table sets with overlap
-                             + (overlap ? 2 * sizeof(double) * n_pts_b : 0)          // the zones kernel's private sums (small shards)
-                             + sizeof(OuterRec) * (size_t)std::max(ls->n_outer, 0);  // records of the outer lines
-    const int nl_max = (int)std::max<size_t>(1, table_budget / per_layer);
-    if (nl > nl_max && far_only) {
-      g_err = "far-only pass over more layers than the table budget holds (mc_pass sizes its row batches for the parent)";
-      return SR_ERR_LIMIT;
-    }
-    if (nl > nl_max) {
-      const size_t n_pts_all = (size_t)(g_hi - g_lo);
-      // sr_lineset_set_bounds_temps: every batch sees its own slice of the boundary temperatures
-      const std::vector<double> bounds_all = bown->bounds_temps;
-      if (!bounds_all.empty() && (int)bounds_all.size() != nl) {
-        g_err = "sr_lineset_set_bounds_temps was given another number of layers than this call";
-        return SR_ERR_ARG;
-      }
-      struct Restore {
-        sr_lineset *ls; const std::vector<double> &all;
-        ~Restore() { ls->bounds_temps = all; }
-      } restore{bown, bounds_all};
-      for (int k0 = 0; k0 < nl; k0 += nl_max) {
-        sr_layers_desc sub = *atm;
-        sub.n_layers = std::min(nl_max, nl - k0);
-        sub.temps = atm->temps + k0;
-        sub.press = atm->press + k0;
-        sub.q_part = atm->q_part ? atm->q_part + k0 : nullptr;
-        std::vector<double> tv;
-        if (atm->tvib) { // [n_levels][n_layers] -> the batch's columns
-          tv.resize((size_t)nlev * sub.n_layers);
-          for (int lv = 0; lv < nlev; ++lv)
-            std::copy(atm->tvib + (size_t)lv * nl + k0, atm->tvib + (size_t)lv * nl + k0 + sub.n_layers,
-                      tv.begin() + (size_t)lv * sub.n_layers);
-          sub.tvib = tv.data();
-        }
-        if (!bounds_all.empty()) bown->bounds_temps.assign(bounds_all.begin() + k0, bounds_all.begin() + k0 + sub.n_layers);
-        const int rc = coef_op(ls, &sub, g_lo, g_hi, abs_out + (size_t)k0 * n_pts_all,
-                               emi_out + (size_t)k0 * n_pts_all, stream, W, opt);
-        if (rc) return rc;
-      }
-      return SR_OK;
-    }
+// The far-field chain on stream fs: per-line expansions (all levels, or level 0 of the box-pair mode), then the box
+// pairs -- moments + upward pass, translations --, then the downward pass behind them.  s2m_done: an event to record
+// behind S2M + M2M, or nullptr.
+static int far_chain(const CoefKernels &k, hipStream_t fs, hipEvent_t s2m_done = nullptr) {
+  for (int r = 0; r < k.reps[1]; ++r) LAUNCHCHK(launch_farfield(k.t, k.fp, k.cnt, fs));
+  if (k.fp.m2l) {
+    for (int r = 0; r < k.reps[2]; ++r) LAUNCHCHK(launch_m2l(k.t, k.fp, k.cnt, fs, 1));
+    if (s2m_done) HIPCHK(hipEventRecord(s2m_done, fs));
+    for (int r = 0; r < k.reps[3]; ++r) LAUNCHCHK(launch_m2l(k.t, k.fp, k.cnt, fs, 2));
   }
+  if (k.far_only || k.fp.folded0) { // the downward pass: the wider levels into the level-0 coefficients
+    const double *l2l_tab = nullptr;
+    const int rc = l2l_table_dev(&l2l_tab);
+    if (rc) return rc;
+    LAUNCHCHK(launch_l2l(k.fp.coef, k.t.n_layers, k.fp, l2l_tab, fs));
+  }
+  return SR_OK;
+}
 
-  // per-layer scalars (host, fp64: fill_layer_stage)
-  const bool frozen = !bown->bounds_temps.empty(); // sr_lineset_set_bounds_temps
-  if (frozen && (int)bown->bounds_temps.size() != nl) {
-    g_err = "sr_lineset_set_bounds_temps was given another number of layers than this call";
-    return SR_ERR_ARG;
+// The serial schedule: chain, wings, zones one after the other on the caller's stream
+static int coef_serial(const CoefKernels &k) {
+  CoefWork &w = k.w;
+  w.overlapped = false;
+  const int rc = far_chain(k, k.st); // (the downward pass's time falls into the far-field group's slot)
+  if (rc) return rc;
+  if (k.timing) HIPCHK(hipEventRecord(w.ev[2], k.st));
+  // wings (writes) then zones (adds); the repeat hook's zones launches store instead (idempotent)
+  for (int part = 1; part <= 2 && !k.far_only; ++part) {
+    const int n_rep = k.reps[part == 1 ? 5 : 4];
+    for (int r = 0; r < n_rep; ++r)
+      LAUNCHCHK(launch_near(part, part == 2 && n_rep == 1, k.t, k.gp, k.fp, k.abs_out, k.emi_out, k.cnt, k.st));
+    if (k.timing) HIPCHK(hipEventRecord(w.ev[2 + part], k.st));
   }
-  const size_t hl_bytes = layer_stage_bytes(nl, npop);
+  return SR_OK;
+}
+
+// The decoupled, phased pipeline (round 4).  Between consecutive calls only the caller-visible output orders things:
+// the zones kernel (tables -> private sums), the far-field chain (tables -> coefficients) and the preparation of
+// the tables touch scratch of the call's own parity and nothing of the caller's, so they run on internal streams,
+// beside the previous call's kernels; only the wings kernel (zones' sums + near region 1 + polynomials -> abs / emi)
+// sits on the caller's stream.  Who runs beside whom is decided by what FITS beside whom
+// (profiles/r04_timeline_*.txt, tools/kernel_resources.sh): 16 zones waves fill a CU -- 120 VGPRs each, 4 x 120 of a
+// SIMD's 512, and 16 x 10 KB = all of its LDS -- and a retiring zones wave frees exactly one such slot, which the
+// next zones wave takes unless the other kernel's wave fits it: the wings kernel (80 VGPRs), M2M / M2L (106 / 104)
+// and the one-wave blocks of the preparation (104 VGPRs, 5 KB) do, the level-0 pass (140) and S2M (154) do not and
+// starved beside the zones kernel until it drained -- then S2M -> M2M -> M2L ran alone, latency-bound, for 0.66 ms
+// of every 5.6 ms step (round 3: the zones kernel forked off the caller's stream, the chain on it; the four-wave
+// blocks of the preparation, 20 KB of LDS each, ran only when everything else had drained).  So the step has two
+// phases: B = [wings(c) | level-0 pass(c + 1) | S2M(c + 1)] -- short waves that share the chip fairly --, then
+// A = [zones(c + 1) | M2M, M2L(c + 1) | prep(c + 2)]; the zones kernel is GATED behind the level-0 pass and S2M of
+// its own call (it needs neither), which is what keeps it from flooding the chip before they are through.
+// These phases come out of TWO internal streams whose own order is the phase order -- not a stream per part, ordered
+// by events on what each reads alone: that was the layout until profiles/two_stream_pipeline_ab.txt, and its overlap
+// held only where each of the five streams had a hardware queue of its own, not on the runtime's default of four:
+//   far_st:  prep(c) -> level-0(c) -> S2M, M2M(c) -> M2L(c) -> prep(c + 1) -> ..   near_st: zones(c)
+// M2L(c + 1) and prep(c + 2) follow S2M(c + 1) on far_st and so run beside zones(c + 1), which that S2M releases;
+// the level-0 pass and S2M of a call run one after the other, both beside wings(c).  Every wait below is on an event
+// recorded earlier in host order, so no two streams can wait for each other.
+static int coef_decoupled(const CoefKernels &k, hipStream_t far_st, hipStream_t near_st) {
+  CoefWork &w = k.w;
+  const int b = k.b;
+  const size_t n_out = (size_t)(k.t.g_hi - k.t.g_lo) * k.t.n_layers;
+  double *z_abs = nullptr, *z_emi = nullptr;
+  if (!k.far_only) {
+    const int rc = w.d_zone2[b].ensure(sizeof(double) * 2 * n_out);
+    if (rc) return rc;
+    z_abs = w.d_zone2[b].as<double>();
+    z_emi = z_abs + n_out;
+  }
+  // (the buffers of parity b were last read by the wings kernel two calls ago: the preparation waited for that)
+  // far-field chain, behind the table preparation on its stream: level-0 pass, moments + upward pass, translations, downward pass
+  const int rc = far_chain(k, far_st, w.ev_s2m_done[b]);
+  if (rc) return rc;
+  HIPCHK(hipEventRecord(w.ev_far_done[b], far_st));
+  if (k.far_only) { // the coefficients are the result: the caller's stream sees them complete
+    HIPCHK(hipStreamWaitEvent(k.st, w.ev_far_done[b], 0));
+  } else {
+    // zones: needs the tables only; gated behind the kernels that cannot run beside it: S2M (on far_st the tables and
+    // the level-0 pass precede it), or, without box pairs, the level-0 pass, which is then the whole chain
+    HIPCHK(hipStreamWaitEvent(near_st, k.fp.m2l ? w.ev_s2m_done[b] : w.ev_far_done[b], 0));
+    LAUNCHCHK(launch_near(2, 0, k.t, k.gp, k.fp, z_abs, z_emi, k.cnt, near_st));
+    HIPCHK(hipEventRecord(w.ev_zones_done[b], near_st));
+    HIPCHK(hipStreamWaitEvent(k.st, w.ev_far_done[b], 0));
+    if (k.timing) HIPCHK(hipEventRecord(w.ev[2], k.st));
+    HIPCHK(hipStreamWaitEvent(k.st, w.ev_zones_done[b], 0));
+    LAUNCHCHK(launch_near(1, 0, k.t, k.gp, k.fp, k.abs_out, k.emi_out, k.cnt, k.st, z_abs, z_emi));
+  }
+  if (k.timing) HIPCHK(hipEventRecord(w.ev[3], k.st));
+  if (k.timing) HIPCHK(hipEventRecord(w.ev[4], k.st));
+  w.overlapped = true;
+  return SR_OK;
+}
+
+// One layer batch of coef_op: stage the layers, select the lines, tables, far chain and near kernels in one of the two
+// schedules (or the exact kernels), outer lines, end of call
+static int coef_batch(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi, double *abs_out, double *emi_out,
+                      hipStream_t st, const WeightMode W, const CoefOpt &opt, const CoefModes &m) {
+  const bool far_only = opt.far_coef != nullptr;
+  CoefWork &w = *ls->work;
+  // frozen region boundaries are set on the handle the caller holds: a per-level sub-lineset follows its parent's
+  const sr_lineset *const bown = ls->parent ? ls->parent : ls;
+  const int nl = atm->n_layers, overlap = m.overlap;
+  const size_t n_pts = (size_t)(g_hi - g_lo);
   // Table set of this call and the stream its preparation runs on.  With overlap, call c + 1
   // prepares set (c + 1) % 2 on far_st while the kernels of call c (which the caller's stream is
   // still running) read set c % 2: the HBM-write-bound prep kernel hides behind the VALU-bound ones.
@@ -1164,48 +1337,20 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
   hipStream_t far_st = nullptr, near_st = nullptr; // the pipeline's two streams (see CoefWork)
   if (overlap) {
     int rcs = w.pipeline_streams(&far_st, &near_st);
+    if (!rcs) rcs = w.pipeline_events();
     if (rcs) return rcs;
-    if (!w.ev_op0) {
-      HIPCHK(hipEventCreateWithFlags(&w.ev_op0, hipEventDefault));
-      for (int i = 0; i < 2; ++i) {
-        HIPCHK(hipEventCreateWithFlags(&w.ev_prep_done[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&w.ev_tables_free[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&w.ev_far_done[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&w.ev_zones_done[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&w.ev_s2m_done[i], hipEventDisableTiming));
-      }
-    }
     pst = far_st;
   }
-  const bool decoupled = overlap == 1; // the decoupled, phased pipeline (see the far-field branch below)
-  Stager &SL = w.s_layers[b];
-  DevBuf &d_fast = w.d_fast[b], &d_cold = w.d_cold[b];
-  int rc = SL.prepare(hl_bytes);
+  // per-layer scalars; set b was last read by the kernels of the call before the previous one
+  LayerStage S;
+  int rc = stage_layers(w.s_layers[b], ls, far_only && ls->parent ? ls->parent : ls, bown, atm, opt.q_ref, true,
+                        overlap && w.free_recorded[b] ? w.ev_tables_free[b] : nullptr, pst, &S);
   if (rc) return rc;
-  rc = fill_layer_stage(ls, far_only && ls->parent ? ls->parent : ls, bown, atm, SL.host<double>(), opt.q_ref);
-  if (rc) return rc;
-  // set b was last read by the kernels of the call before the previous one
-  if (overlap && w.free_recorded[b]) HIPCHK(hipStreamWaitEvent(pst, w.ev_tables_free[b], 0));
-  rc = SL.push(hl_bytes, pst);
-  if (rc) return rc;
-  const int *d_pm = nullptr;
-  const LayersDev A = layers_dev_of(SL.d.as<double>(), nl, npop, frozen, bown->linear_weights, &d_pm);
-  const int *zmax_dev = d_pm + 2 * nl; // [n_layers] widest zone (host bound, see fill_layer_stage)
-
-  // lines whose window [ic-6505, ic+6504] meets the shard
-  const auto lo_it = std::lower_bound(ls->ic.begin(), ls->ic.end(), (int)g_lo - (kHalf - 1));
-  const auto hi_it = std::upper_bound(ls->ic.begin(), ls->ic.end(), (int)g_hi - 1 + kHalf);
-  const int line_lo = (int)(lo_it - ls->ic.begin());
-  const int n_sub = (int)(hi_it - lo_it);
-  const size_t n_pts = (size_t)(g_hi - g_lo);
-
-  const IcIndex ix{ls->d_first.as<int>(), ls->first_x0, ls->first_n, line_lo, n_sub};
-
-  w.timed = false;
-  w.overlapped = false;
-  w.counted = false;
+  const IcIndex ix = shard_lines(ls, g_lo, g_hi);
+  const int line_lo = ix.line_lo, n_sub = ix.n_sub;
+  w.timed = w.overlapped = w.counted = false;
   unsigned long long *d_cnt = nullptr;
-  if (counting) {
+  if (m.counting) {
     rc = w.d_counts.ensure(sizeof(unsigned long long) * kCntN);
     if (rc) return rc;
     d_cnt = w.d_counts.as<unsigned long long>();
@@ -1216,7 +1361,7 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
     if (ls->n_outer <= 0) return SR_OK;
     int rc2 = w.d_outer_recs.ensure(sizeof(OuterRec) * (size_t)ls->n_outer * nl);
     if (rc2) return rc2;
-    LAUNCHCHK(launch_outer(ls->Lo, ls->n_outer, A, ls->gp, W, w.d_outer_recs.as<OuterRec>(), (int)g_lo, (int)g_hi,
+    LAUNCHCHK(launch_outer(ls->Lo, ls->n_outer, S.A, ls->gp, W, w.d_outer_recs.as<OuterRec>(), (int)g_lo, (int)g_hi,
                            abs_out, emi_out, st));
     return SR_OK;
   };
@@ -1225,185 +1370,63 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
   if (n_sub <= 0) {
     HIPCHK(hipMemsetAsync(abs_out, 0, sizeof(double) * n_pts * nl, st));
     HIPCHK(hipMemsetAsync(emi_out, 0, sizeof(double) * n_pts * nl, st));
-    if (ls->n_outer > 0) {
-      // the layer scalars were pushed on pst: the caller's stream must see them
-      if (overlap) {
-        HIPCHK(hipEventRecord(w.ev_prep_done[b], pst));
-        HIPCHK(hipStreamWaitEvent(st, w.ev_prep_done[b], 0));
-      }
-      rc = add_outer();
-      if (rc) return rc;
-      if (overlap) {
-        HIPCHK(hipEventRecord(w.ev_tables_free[b], st));
-        w.free_recorded[b] = true;
-      }
-      HIPCHK(hipEventRecord(w.ev_last_done, st));
-      w.last_done_recorded = true;
+    if (ls->n_outer <= 0) return SR_OK;
+    // the layer scalars were pushed on pst: the caller's stream must see them
+    if (overlap) {
+      HIPCHK(hipEventRecord(w.ev_prep_done[b], pst));
+      HIPCHK(hipStreamWaitEvent(st, w.ev_prep_done[b], 0));
     }
-    return SR_OK;
+    rc = add_outer();
+    if (rc) return rc;
+    return w.end_call(st, overlap ? b : -1);
   }
+  DevBuf &d_fast = w.d_fast[b], &d_cold = w.d_cold[b];
   rc = d_fast.ensure(sizeof(FastRec) * ((size_t)n_sub * nl + 1));
+  if (!rc) rc = d_cold.ensure(sizeof(ColdRec) * ((size_t)n_sub * nl + 1));
   if (rc) return rc;
-  rc = d_cold.ensure(sizeof(ColdRec) * ((size_t)n_sub * nl + 1));
-  if (rc) return rc;
-
-
-  // (measurement hook, serial schedule only: see g_repeat_kernel)
-  const int rep_k = overlap ? -1 : g_repeat_kernel.load(), rep_n = g_repeat_n.load();
-  auto reps = [&](int k) { return k == rep_k ? rep_n : 1; };
-  if (timing) HIPCHK(hipEventRecord(w.ev[0], pst));
+  const ShardTables t{d_fast.as<FastRec>(), d_cold.as<ColdRec>(), ix, S.zmax, nl, (int)g_lo, (int)g_hi};
+  if (m.timing) HIPCHK(hipEventRecord(w.ev[0], pst));
   // cold records: far-field mode reads them for zones inside the shard only, exact mode for window ends too
-  for (int r = 0; r < reps(0); ++r)
-  LAUNCHCHK(launch_prep(ls->L, A, ls->gp, W, line_lo, n_sub, far_only ? INT_MAX / 2 : (far_field ? (int)g_lo : INT_MIN / 2),
-                        far_only ? INT_MIN / 2 : (far_field ? (int)g_hi - 1 : INT_MAX / 2), d_fast.as<FastRec>(),
-                        d_cold.as<ColdRec>(), pst)); // (far-only: an empty cold range, no region-2..4 records)
-  if (timing) HIPCHK(hipEventRecord(w.ev[1], pst));
+  for (int r = 0; r < m.reps[0]; ++r)
+    LAUNCHCHK(launch_prep(ls->L, S.A, ls->gp, W, line_lo, n_sub, far_only ? INT_MAX / 2 : (m.far_field ? (int)g_lo : INT_MIN / 2),
+                          far_only ? INT_MIN / 2 : (m.far_field ? (int)g_hi - 1 : INT_MAX / 2), d_fast.as<FastRec>(),
+                          d_cold.as<ColdRec>(), pst)); // (far-only: an empty cold range, no region-2..4 records)
+  if (m.timing) HIPCHK(hipEventRecord(w.ev[1], pst));
   if (overlap) { // the caller's stream takes over once the tables are ready
     HIPCHK(hipEventRecord(w.ev_prep_done[b], pst));
     HIPCHK(hipStreamWaitEvent(st, w.ev_prep_done[b], 0));
-    if (timing) HIPCHK(hipEventRecord(w.ev_op0, st));
+    if (m.timing) HIPCHK(hipEventRecord(w.ev_op0, st));
   }
-  if (far_field) {
-    FarParams fp;
-    far_hierarchy(n_pts, nl, &fp);
-    if (!far_only) {
-      rc = w.d_coef[b].ensure(sizeof(double) * (size_t)nl * fp.n_boxes_total * 2 * kFC);
-      if (rc) return rc;
-    }
-    fp.pm = d_pm;
-    fp.coef = far_only ? opt.far_coef : w.d_coef[b].as<double>();
-    fp.m2l = far_field == 2 ? 1 : 0;
-    // box-pair mode: the downward pass folds every level into level 0 behind M2L (both schedules) and the near-wings
-    // kernel evaluates ONE polynomial per point; the per-line mode of sparse sets keeps a polynomial per level
-    fp.folded0 = fp.m2l && !far_only ? 1 : 0;
-    fp.rows = sparse_set ? 1 : 0; // the sparse sets' own kernel (sr_farfield_rows_kernel: a box for eight layers per wave)
-    fp.pm_src = d_pm + nl;
-    fp.disp_lo_end = (int)std::min<int64_t>(std::max<int64_t>(ls->n_disp_lo - line_lo, 0), n_sub);
-    fp.disp_hi_begin = (int)std::min<int64_t>(std::max<int64_t>(ls->n_lines - ls->n_disp_hi - line_lo, 0), n_sub);
-    fp.mom = nullptr;
-    fp.tab = nullptr;
-    for (int lv = 0; lv < kMaxFarLevels; ++lv) fp.n_src[lv] = fp.src_off[lv] = 0;
+  if (m.far_field) {
+    int n_src = 0;
+    const FarKind kind = m.far_field == 2 ? kFarBoxPairs : m.sparse_set ? kFarPerLineRows : kFarPerLine;
+    CoefKernels k{w, b, t, far_params(n_pts, S, kind, opt.far_coef, &n_src), ls->gp, far_only, m.timing, abs_out, emi_out, d_cnt, st, m.reps};
+    FarParams &fp = k.fp;
     if (fp.m2l) {
-      // level-0 source boxes: kSrcPad left of the shard, the shard, the window half-width right of it; a whole
-      // number of widest boxes, so that every level halves exactly
-      const int top_boxes = (int)(((size_t)kSrcPad * 64 + n_pts + kHalf + 64) >> (6 + kMaxFarLevels - 1)) + 1;
-      int total = 0;
-      for (int lv = 0; lv < kMaxFarLevels; ++lv) {
-        fp.n_src[lv] = top_boxes << (kMaxFarLevels - 1 - lv);
-        fp.src_off[lv] = total;
-        total += fp.n_src[lv];
-      }
-      rc = w.d_mom[b].ensure(sizeof(double) * (size_t)total * nl * kMomPerBox);
+      rc = w.d_mom[b].ensure(sizeof(double) * (size_t)n_src * nl * kMomPerBox);
       if (rc) return rc;
       fp.mom = w.d_mom[b].as<double>();
       rc = m2l_table_dev(&fp.tab);
       if (rc) return rc;
     }
-    // far-field pass(es): per-line expansions (all levels, or level 0 of the box-pair mode), then the box pairs
-    auto far_pass = [&](hipStream_t fs) -> int {
-      for (int r = 0; r < reps(1); ++r)
-        LAUNCHCHK(launch_farfield(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp,
-                                  d_cnt, fs));
-      if (fp.m2l) {
-        for (int r = 0; r < reps(2); ++r)
-          LAUNCHCHK(launch_m2l(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, fs, 1));
-        for (int r = 0; r < reps(3); ++r)
-          LAUNCHCHK(launch_m2l(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, fs, 2));
-      }
-      return SR_OK;
-    };
-    // The decoupled, phased pipeline (round 4).  Between consecutive calls only the caller-visible output orders things:
-    // the zones kernel (tables -> private sums), the far-field chain (tables -> coefficients) and the preparation of
-    // the tables touch scratch of the call's own parity and nothing of the caller's, so they run on internal streams,
-    // beside the previous call's kernels; only the wings kernel (zones' sums + near region 1 + polynomials -> abs / emi)
-    // sits on the caller's stream.  Who runs beside whom is decided by what FITS beside whom
-    // (profiles/r04_timeline_*.txt, tools/kernel_resources.sh): 16 zones waves fill a CU -- 120 VGPRs each, 4 x 120 of a
-    // SIMD's 512, and 16 x 10 KB = all of its LDS -- and a retiring zones wave frees exactly one such slot, which the
-    // next zones wave takes unless the other kernel's wave fits it: the wings kernel (80 VGPRs), M2M / M2L (106 / 104)
-    // and the one-wave blocks of the preparation (104 VGPRs, 5 KB) do, the level-0 pass (140) and S2M (154) do not and
-    // starved beside the zones kernel until it drained -- then S2M -> M2M -> M2L ran alone, latency-bound, for 0.66 ms
-    // of every 5.6 ms step (round 3: the zones kernel forked off the caller's stream, the chain on it; the four-wave
-    // blocks of the preparation, 20 KB of LDS each, ran only when everything else had drained).  So the step has two
-    // phases: B = [wings(c) | level-0 pass(c + 1) | S2M(c + 1)] -- short waves that share the chip fairly --, then
-    // A = [zones(c + 1) | M2M, M2L(c + 1) | prep(c + 2)]; the zones kernel is GATED behind the level-0 pass and S2M of
-    // its own call (it needs neither), which is what keeps it from flooding the chip before they are through.
-    // These phases come out of TWO internal streams whose own order is the phase order -- not a stream per part, ordered
-    // by events on what each reads alone: that was the layout until profiles/two_stream_pipeline_ab.txt, and its overlap
-    // held only where each of the five streams had a hardware queue of its own, not on the runtime's default of four:
-    //   far_st:  prep(c) -> level-0(c) -> S2M, M2M(c) -> M2L(c) -> prep(c + 1) -> ..   near_st: zones(c)
-    // M2L(c + 1) and prep(c + 2) follow S2M(c + 1) on far_st and so run beside zones(c + 1), which that S2M releases;
-    // the level-0 pass and S2M of a call run one after the other, both beside wings(c).  Every wait below is on an event
-    // recorded earlier in host order, so no two streams can wait for each other.
-    if (decoupled) {
-      double *z_abs = nullptr, *z_emi = nullptr;
-      if (!far_only) {
-        rc = w.d_zone2[b].ensure(sizeof(double) * 2 * n_pts * nl);
-        if (rc) return rc;
-        z_abs = w.d_zone2[b].as<double>();
-        z_emi = z_abs + n_pts * nl;
-      }
-      // (the buffers of parity b were last read by the wings kernel two calls ago: the preparation waited for that)
-      // far-field chain, behind the table preparation on its stream: level-0 pass, moments + upward pass, translations
-      LAUNCHCHK(launch_farfield(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, far_st));
-      if (fp.m2l) {
-        LAUNCHCHK(launch_m2l(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, far_st, 1));
-        HIPCHK(hipEventRecord(w.ev_s2m_done[b], far_st));
-        LAUNCHCHK(launch_m2l(d_fast.as<FastRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, fp, d_cnt, far_st, 2));
-      }
-      if (far_only || fp.folded0) { // the downward pass: the wider levels into the level-0 coefficients, behind the chain on its stream
-        const double *l2l_tab = nullptr;
-        rc = l2l_table_dev(&l2l_tab);
-        if (rc) return rc;
-        LAUNCHCHK(launch_l2l(fp.coef, nl, fp, l2l_tab, far_st));
-      }
-      HIPCHK(hipEventRecord(w.ev_far_done[b], far_st));
-      if (far_only) { // the coefficients are the result: the caller's stream sees them complete
-        HIPCHK(hipStreamWaitEvent(st, w.ev_far_done[b], 0));
-      } else {
-      // zones: needs the tables only; gated behind the kernels that cannot run beside it: S2M (on far_st the tables and
-      // the level-0 pass precede it), or, without box pairs, the level-0 pass, which is then the whole chain
-      HIPCHK(hipStreamWaitEvent(near_st, fp.m2l ? w.ev_s2m_done[b] : w.ev_far_done[b], 0));
-      LAUNCHCHK(launch_near(2, 0, d_fast.as<FastRec>(), d_cold.as<ColdRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo,
-                            (int)g_hi, ls->gp, fp, z_abs, z_emi, d_cnt, near_st));
-      HIPCHK(hipEventRecord(w.ev_zones_done[b], near_st));
-      HIPCHK(hipStreamWaitEvent(st, w.ev_far_done[b], 0));
-      if (timing) HIPCHK(hipEventRecord(w.ev[2], st));
-      HIPCHK(hipStreamWaitEvent(st, w.ev_zones_done[b], 0));
-      LAUNCHCHK(launch_near(1, 0, d_fast.as<FastRec>(), d_cold.as<ColdRec>(), ix, zmax_dev, n_sub, nl, (int)g_lo,
-                            (int)g_hi, ls->gp, fp, abs_out, emi_out, d_cnt, st, z_abs, z_emi));
-      }
-      if (timing) HIPCHK(hipEventRecord(w.ev[3], st));
-      if (timing) HIPCHK(hipEventRecord(w.ev[4], st));
-      w.overlapped = true;
-    } else {
-      w.overlapped = false;
-      rc = far_pass(st);
+    if (!far_only) {
+      rc = w.d_coef[b].ensure(sizeof(double) * (size_t)nl * fp.n_boxes_total * 2 * kFC);
       if (rc) return rc;
-      if (far_only || fp.folded0) { // (its time falls into the far-field group's slot)
-        const double *l2l_tab = nullptr;
-        rc = l2l_table_dev(&l2l_tab);
-        if (rc) return rc;
-        LAUNCHCHK(launch_l2l(fp.coef, nl, fp, l2l_tab, st));
-      }
-      if (timing) HIPCHK(hipEventRecord(w.ev[2], st));
-      // wings (writes) then zones (adds); the repeat hook's zones launches store instead (idempotent)
-      for (int part = 1; part <= 2 && !far_only; ++part) {
-        const int n_rep = reps(part == 1 ? 5 : 4);
-        for (int r = 0; r < n_rep; ++r)
-          LAUNCHCHK(launch_near(part, part == 2 && n_rep == 1, d_fast.as<FastRec>(), d_cold.as<ColdRec>(), ix,
-                                zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, ls->gp, fp, abs_out, emi_out,
-                                d_cnt, st));
-        if (timing) HIPCHK(hipEventRecord(w.ev[2 + part], st));
-      }
+      fp.coef = w.d_coef[b].as<double>();
     }
+    // box-pair mode: the downward pass folds every level into level 0 behind M2L (both schedules) and the near-wings
+    // kernel evaluates ONE polynomial per point; the per-line mode of sparse sets keeps a polynomial per level
+    fp.folded0 = fp.m2l && !far_only ? 1 : 0;
+    fp.disp_lo_end = (int)std::min<int64_t>(std::max<int64_t>(ls->n_disp_lo - line_lo, 0), n_sub);
+    fp.disp_hi_begin = (int)std::min<int64_t>(std::max<int64_t>(ls->n_lines - ls->n_disp_hi - line_lo, 0), n_sub);
+    rc = overlap ? coef_decoupled(k, far_st, near_st) : coef_serial(k);
+    if (rc) return rc;
     w.n_timed = 4;
   } else {
     w.n_timed = 3;
     for (int which = 0; which < 2; ++which) {
-      LAUNCHCHK(launch_abscoeff(variant, which, d_fast.as<FastRec>(), d_cold.as<ColdRec>(),
-                                ix, zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, ls->gp,
-                                abs_out, emi_out, st));
-      if (timing) HIPCHK(hipEventRecord(w.ev[2 + which], st));
+      LAUNCHCHK(launch_abscoeff(m.variant, which, t, ls->gp, abs_out, emi_out, st));
+      if (m.timing) HIPCHK(hipEventRecord(w.ev[2 + which], st));
     }
   }
   if (!far_only) {
@@ -1412,16 +1435,45 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
   }
   // a serial call reads table set 0 too: a later pipelined call, which prepares its set on far_st without waiting for
   // the caller's stream, must find the event behind THIS call's kernels
-  if (w.ev_tables_free[b]) {
-    HIPCHK(hipEventRecord(w.ev_tables_free[b], st));
-    w.free_recorded[b] = true;
-  }
-  HIPCHK(hipEventRecord(w.ev_last_done, st));
-  w.last_done_recorded = true;
+  rc = w.end_call(st, b);
+  if (rc) return rc;
   w.pipelined = overlap != 0;
-  w.timed = timing;
-  w.counted = counting;
+  w.timed = m.timing;
+  w.counted = m.counting;
   return SR_OK;
+}
+
+// The coefficient op with the output weights of `W` (sr_kernels.hpp); the public entry points below
+// choose W.  abs_out / emi_out: DEVICE [n_layers][g_hi - g_lo].
+static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi, double *abs_out,
+                   double *emi_out, void *stream, const WeightMode W, const CoefOpt opt = CoefOpt()) {
+  const bool far_only = opt.far_coef != nullptr;
+  if (!far_only && (!abs_out || !emi_out)) return SR_ERR_ARG;
+  const int rc = check_coef_call(ls, atm, g_lo, g_hi);
+  if (rc) return rc;
+  // one snapshot of the mode switches per call
+  CoefModes m;
+  m.variant = g_variant.load();
+  m.timing = g_timing.load() != 0;
+  const int far_mode = g_far_field.load();
+  m.sparse_set = is_sparse_set(ls, far_mode);
+  m.far_field = far_mode == 3 ? (m.sparse_set ? 1 : 2) : far_mode;
+  if (far_only && !m.far_field) return SR_ERR_UNSUPPORTED; // (mc_pass takes the per-level route in the exact mode)
+  m.counting = g_counting.load() != 0 && m.far_field;
+  m.overlap = (g_overlap.load() != 0 && m.far_field && !m.counting) ? 1 : 0;
+  const int rep_k = m.overlap ? -1 : g_repeat_kernel.load(), rep_n = g_repeat_n.load();
+  for (int i = 0; i < 6; ++i) m.reps[i] = i == rep_k ? rep_n : 1;
+  // layer batches under the table budget
+  const size_t n_pts = (size_t)(g_hi - g_lo);
+  const int nl_max = (int)std::max<size_t>(1, g_table_budget.load() / coef_bytes_per_layer(ls, n_pts, m.far_field, m.overlap));
+  if (atm->n_layers > nl_max && far_only) {
+    g_err = "far-only pass over more layers than the table budget holds (mc_pass sizes its row batches for the parent)";
+    return SR_ERR_LIMIT;
+  }
+  return for_layer_batches(atm, ls->parent ? ls->parent : ls, ls->n_levels, true, nl_max, [&](const sr_layers_desc &sub, int k0) {
+    return coef_batch(ls, &sub, g_lo, g_hi, abs_out + (size_t)k0 * n_pts, emi_out + (size_t)k0 * n_pts,
+                      static_cast<hipStream_t>(stream), W, opt, m);
+  });
 }
 
 // Sub-lineset of the lines whose upper or lower level is `level` (same grid, iso-molecule and level
@@ -1465,6 +1517,219 @@ static int level_set(sr_lineset *ls, int level, sr_lineset **out, bool up_only =
   return SR_OK;
 }
 
+// Far pass f of a multi-channel pass: the level whose sub-lineset it runs over (ind: its ind_emission lines, those whose
+// UPPER level is lv only), the weights of that sub-lineset's own coefficient op, and the channels its two outputs
+// belong to (-1: none -- the unused second channel of the ind_emission weights)
+struct McFarMap {
+  int level, ch_a, ch_e;
+  bool ind;
+  WeightMode W;
+};
+static McFarMap mc_far_pass(int ctypes3, int f) {
+  if (!ctypes3) return McFarMap{f, 2 * f, 2 * f + 1, false, WeightMode{kWeightLevelPair, f}};
+  const int lv = f / 2;
+  if (f & 1) return McFarMap{lv, 3 * lv + 1, -1, true, WeightMode{kWeightGind, lv}};
+  return McFarMap{lv, 3 * lv + 2, 3 * lv, false, WeightMode{kWeightGabsGsp, lv}};
+}
+
+// What the row batches of one multi-channel pass share
+struct McCall {
+  sr_lineset *ls;
+  int64_t g_lo, g_hi;
+  double *out;
+  void *stream;
+  int ctypes3, far_mode, n_rows, n_far;
+  McChannels mc;
+  size_t coef_row; // doubles per (far pass, row)
+  bool timing;
+};
+
+// The SPARSE sub-linesets of a row batch (is_sparse_set -- per-line expansions at every level,
+// sr_farfield_rows_kernel): ALL of them in one batch of three launches -- tables, expansions, downward
+// pass -- on the handle's near_st, beside the dense passes' chains.  One coefficient op each, they were eleven launches
+// of 0.3 ms, latency-bound, each behind ~0.3 ms of host calls: 6 ms of a 13 ms build (gpurun_out/r06/tl_v4.txt).
+// They share this pass's layer stage: their own would hold the same numbers (margins of the parent).
+// far[f].coef of every sparse pass is set (nullptr: no line of it meets the shard); the others are left in `dense`.
+static int mc_sparse_passes(const McCall &c, const LayerStage &S, const std::vector<sr_lineset *> &child, const std::vector<int> &order,
+                            const std::vector<McFarMap> &pass, McFarPass *far, std::vector<int> *dense) {
+  sr_lineset *ls = c.ls;
+  McWork &m = ls->mc;
+  hipStream_t st = static_cast<hipStream_t>(c.stream);
+  const int nl = S.A.n_layers;
+  const size_t n_pts = (size_t)(c.g_hi - c.g_lo);
+  int rc = m.s_batch.prepare(sizeof(FarBatchItem) * (size_t)c.n_far);
+  if (rc) return rc;
+  FarBatchItem *items = m.s_batch.host<FarBatchItem>();
+  int n_items = 0, max_sub = 0;
+  size_t rec_total = 0;
+  std::vector<size_t> rec_off;
+  for (int q = 0; q < c.n_far; ++q) {
+    const int f = order[(size_t)q];
+    sr_lineset *ch = child[(size_t)f];
+    if (!is_sparse_set(ch, c.far_mode)) { dense->push_back(f); continue; }
+    const IcIndex cx = shard_lines(ch, c.g_lo, c.g_hi);
+    if (cx.n_sub <= 0) continue;
+    FarBatchItem &it = items[n_items++];
+    it.L = ch->L;
+    it.first = cx.first;
+    it.first_x0 = cx.x0;
+    it.first_n = cx.n_tab;
+    it.line_lo = cx.line_lo;
+    it.n_sub = cx.n_sub;
+    it.W = pass[(size_t)f].W;
+    it.coef = m.d_coef.as<double>() + c.coef_row * (size_t)nl * f;
+    far[f].coef = it.coef;
+    rec_off.push_back(rec_total);
+    rec_total += (size_t)cx.n_sub * nl;
+    max_sub = std::max(max_sub, cx.n_sub);
+  }
+  m.batch_pending = n_items > 0;
+  if (n_items <= 0) return SR_OK;
+  rc = m.d_bfast.ensure(sizeof(FastRec) * (rec_total + 1));
+  if (rc) return rc;
+  for (int i = 0; i < n_items; ++i) items[i].fast = m.d_bfast.as<FastRec>() + rec_off[(size_t)i];
+  // (serial schedule, sr_set_overlap(0): everything on the caller's stream, one kernel after the other)
+  hipStream_t bst = st;
+  if (g_overlap.load() != 0) { // beside the dense passes' chains (far_st): the handle's near_st
+    hipStream_t fst = nullptr;
+    rc = ls->work->pipeline_streams(&fst, &bst);
+    if (rc) return rc;
+  }
+  if (bst != st) HIPCHK(hipStreamWaitEvent(bst, m.ev_prep, 0));
+  rc = m.s_batch.push(sizeof(FarBatchItem) * (size_t)n_items, bst);
+  if (rc) return rc;
+  const double *l2l_tab = nullptr;
+  rc = l2l_table_dev(&l2l_tab);
+  if (rc) return rc;
+  LAUNCHCHK(launch_far_batch(m.s_batch.d.as<FarBatchItem>(), n_items, max_sub, S.A, ls->gp, S.zmax, (int)c.g_lo,
+                             far_params(n_pts, S, kFarPerLineRows, nullptr), l2l_tab, bst));
+  HIPCHK(hipEventRecord(m.ev_zones, bst));
+  return m.s_batch.mark(bst);
+}
+
+// One row batch [k0, k0 + sub.n_layers) of a multi-channel pass
+static int mc_rows(const McCall &c, const sr_layers_desc &sub, int k0) {
+  sr_lineset *ls = c.ls;
+  CoefWork &w = *ls->work;
+  McWork &m = ls->mc;
+  hipStream_t st = static_cast<hipStream_t>(c.stream);
+  const int nl = sub.n_layers, n_far = c.n_far;
+  const size_t n_pts = (size_t)(c.g_hi - c.g_lo);
+  // this batch after everything earlier on the handle (the previous batch's kernels read the tables refilled below)
+  if (w.last_done_recorded) HIPCHK(hipStreamWaitEvent(st, w.ev_last_done, 0));
+  // (prepare() waits on the HOST for the mark behind the previous batch's -- or build's -- last kernel: nothing of this
+  // batch is enqueued before the previous one has finished with the pass's scratch.  That is what keeps the far passes
+  // below, whose internal streams are not ordered after the caller's, from writing m.d_coef under the wings kernel of
+  // the batch before.)
+  LayerStage S;
+  int rc = stage_layers(m.s_layers, ls, ls, ls, &sub, 0.0, true, nullptr, st, &S);
+  if (rc) return rc;
+  const IcIndex ix = shard_lines(ls, c.g_lo, c.g_hi);
+  const int line_lo = ix.line_lo, n_sub = ix.n_sub;
+  auto chan_rows = [&](int ch) { return c.out + ((size_t)ch * c.n_rows + (size_t)k0) * n_pts; };
+  std::vector<McFarMap> pass((size_t)n_far);
+  for (int f = 0; f < n_far; ++f) pass[(size_t)f] = mc_far_pass(c.ctypes3, f);
+  if (n_sub <= 0) {
+    for (int ch = 0; ch < c.mc.n_ch; ++ch) HIPCHK(hipMemsetAsync(chan_rows(ch), 0, sizeof(double) * n_pts * nl, st));
+  } else {
+    rc = m.d_fast.ensure(sizeof(FastRec) * ((size_t)n_sub * nl + 1));
+    if (!rc) rc = m.d_cold.ensure(sizeof(ColdRec) * ((size_t)n_sub * nl + 1));
+    if (!rc) rc = m.d_coef.ensure(sizeof(double) * c.coef_row * (size_t)nl * n_far);
+    if (rc) return rc;
+    const ShardTables t{m.d_fast.as<FastRec>(), m.d_cold.as<ColdRec>(), ix, S.zmax, nl, (int)c.g_lo, (int)c.g_hi};
+    if (c.timing) HIPCHK(hipEventRecord(m.ev_t[0], st));
+    LAUNCHCHK(launch_prep(ls->L, S.A, ls->gp, WeightMode{kWeightChannels, c.ctypes3 ? 1 : 0}, line_lo, n_sub, (int)c.g_lo, (int)c.g_hi - 1,
+                          m.d_fast.as<FastRec>(), m.d_cold.as<ColdRec>(), st));
+    if (c.timing) HIPCHK(hipEventRecord(m.ev_t[1], st));
+    HIPCHK(hipEventRecord(m.ev_prep, st)); // the layer stage, the tables and everything earlier on the caller's stream
+    // The zones kernel beside the far passes, the wings kernel after both.  The build is bound by its kernels' WORK, not
+    // their order -- 13.25 / 13.32 ms with the zones kernel gated behind the far passes, 13.06 / 13.13 beside them; the
+    // sparse passes' single batched launch no longer starves beside it as their twelve small chains did
+    // (profiles/r06_mc_timeline_v3 / v5).
+    LAUNCHCHK(launch_zones_mc(t, ls->L.lev_up + line_lo, ls->L.lev_lo + line_lo, ls->gp, c.mc, c.out, c.n_rows, k0, st));
+    if (c.timing) HIPCHK(hipEventRecord(m.ev_t[2], st));
+    // far-only passes of the level sub-linesets
+    rc = m.s_far.prepare(sizeof(McFarPass) * (size_t)n_far);
+    if (rc) return rc;
+    McFarPass *far = m.s_far.host<McFarPass>();
+    // The passes are independent of each other.  The dense ones (one or two per build) go one after the other on the
+    // handle's far_st, each through a CoefWork of its own (tables, events) instead of the handle's shared one, so that
+    // none waits for another's scratch; the sparse ones in one batch beside them (mc_sparse_passes) -- one after the
+    // other on one chain stream the eleven sparse passes (0.33 ms each, latency-bound) and the dense ground-state pass
+    // were 7.7 ms, longer than the zones kernel they run beside.  Largest sub-lineset first (its chain is the longest).
+    if (!m.fw_init) {
+      for (auto &fwk : m.fw) {
+        rc = fwk.init();
+        if (rc) return rc;
+        fwk.streams_of = &w; // the handle's two streams, not a set each
+      }
+      m.fw_init = true;
+    }
+    std::vector<sr_lineset *> child((size_t)n_far, nullptr);
+    std::vector<int> order((size_t)n_far), dense;
+    for (int f = 0; f < n_far; ++f) {
+      rc = level_set(ls, pass[(size_t)f].level, &child[(size_t)f], pass[(size_t)f].ind);
+      if (rc) return rc;
+      order[(size_t)f] = f;
+      far[f] = McFarPass{nullptr, pass[(size_t)f].ch_a, pass[(size_t)f].ch_e};
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return child[(size_t)x]->n_lines > child[(size_t)y]->n_lines; });
+    rc = mc_sparse_passes(c, S, child, order, pass, far, &dense);
+    if (rc) return rc;
+    // the dense passes (the ground state's, typically), each through a CoefWork of its own
+    for (size_t q = 0; q < dense.size(); ++q) {
+      const int f = dense[q];
+      sr_lineset *ch = child[(size_t)f];
+      bool has = false;
+      CoefOpt o;
+      o.far_coef = m.d_coef.as<double>() + c.coef_row * (size_t)nl * f;
+      o.far_has = &has;
+      CoefWork *const shared = ch->work;
+      ch->work = &m.fw[q % kMcFarLanes];
+      rc = coef_op(ch, &sub, c.g_lo, c.g_hi, nullptr, nullptr, c.stream, pass[(size_t)f].W, o);
+      ch->work = shared;
+      if (rc) return rc;
+      if (has) far[f].coef = o.far_coef;
+    }
+    if (m.batch_pending) HIPCHK(hipStreamWaitEvent(st, m.ev_zones, 0));
+    rc = m.s_far.push(sizeof(McFarPass) * (size_t)n_far, st);
+    if (rc) return rc;
+    if (c.timing) HIPCHK(hipEventRecord(m.ev_t[3], st));
+    LAUNCHCHK(launch_wings_mc(t, ls->L.lev_up + line_lo, ls->L.lev_lo + line_lo, far_params(n_pts, S, kFarPerLine, nullptr), c.mc,
+                              m.s_far.d.as<McFarPass>(), n_far, c.out, c.n_rows, k0, st));
+    if (c.timing) {
+      HIPCHK(hipEventRecord(m.ev_t[4], st));
+      m.timed = true;
+    }
+    rc = m.s_far.mark(st);
+    if (rc) return rc;
+  }
+  // lines whose centre lies outside their window (humliv_bb's outer branches): per level, as the per-level route
+  if (ls->n_outer > 0) {
+    // (one record buffer for the largest level: sized per level, a growing buffer was freed -- a device synchronisation --
+    // between the levels' launches)
+    rc = m.d_outer_recs.ensure(sizeof(OuterRec) * (size_t)ls->n_outer * nl);
+    if (rc) return rc;
+    for (const McFarMap &p : pass) {
+      sr_lineset *ch = nullptr;
+      rc = level_set(ls, p.level, &ch, p.ind);
+      if (rc) return rc;
+      if (ch->n_outer <= 0) continue;
+      double *o_e = p.ch_e >= 0 ? chan_rows(p.ch_e) : nullptr;
+      if (!o_e) {
+        rc = ls->d_gscratch.ensure(sizeof(double) * n_pts * nl); // the unused second channel of the ind_emission weights
+        if (rc) return rc;
+        o_e = ls->d_gscratch.as<double>();
+      }
+      LAUNCHCHK(launch_outer(ch->Lo, ch->n_outer, S.A, ls->gp, p.W, m.d_outer_recs.as<OuterRec>(), (int)c.g_lo, (int)c.g_hi,
+                             chan_rows(p.ch_a), o_e, st));
+    }
+  }
+  rc = m.s_layers.mark(st);
+  if (rc) return rc;
+  return w.end_call(st, -1);
+}
+
 // ------------------------------------------------------------------------
 // The multi-channel pass: all level spectra of a (P, T) row stack from ONE walk of the full line list (near field:
 // sr_zones_mc_kernel, sr_wings_mc_kernel) + one far-only pass per level sub-lineset (the far field is linear per output
@@ -1476,274 +1741,29 @@ static int level_set(sr_lineset *ls, int level, sr_lineset **out, bool up_only =
 // spect_main_module.py:1122-1168 (add_PT per level), spect_classes.py:1304-1321 (which lines a level owns).
 // ------------------------------------------------------------------------
 static int mc_pass(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi, double *out, void *stream, int ctypes3) {
-  const int nlev = ls->n_levels, n_rows = atm->n_layers;
-  const int far_mode = g_far_field.load();
-  if (nlev <= 0 || far_mode == 0 || g_counting.load() != 0 || g_level_route.load() == 0) return SR_ERR_UNSUPPORTED;
-  if (!atm->temps || !atm->press) return SR_ERR_ARG;
-  if (g_lo < 0 || g_hi > ls->gp.n_grid || g_lo >= g_hi) return SR_ERR_ARG;
-  for (int k = 0; k < n_rows; ++k)
-    if (!(atm->temps[k] > 0.0) || !(atm->press[k] >= 0.0)) return SR_ERR_ARG;
-  McChannels mc;
-  mc.stride = ctypes3 ? 3 : 2;
-  mc.o_lo = ctypes3 ? 2 : 0;
-  mc.o_up_e = ctypes3 ? 0 : 1;
-  mc.o_up_a = ctypes3 ? 1 : 0;
-  mc.n_ch = mc.stride * nlev;
+  const int nlev = ls->n_levels;
+  McCall c{ls, g_lo, g_hi, out, stream, ctypes3, g_far_field.load(), atm->n_layers, ctypes3 ? 2 * nlev : nlev};
+  if (nlev <= 0 || c.far_mode == 0 || g_counting.load() != 0 || g_level_route.load() == 0) return SR_ERR_UNSUPPORTED;
+  const int rc = check_coef_call(ls, atm, g_lo, g_hi);
+  if (rc) return rc;
+  const McChannels &mc = c.mc = ctypes3 ? McChannels{3, 2, 0, 1, 3 * nlev} : McChannels{2, 0, 1, 0, 2 * nlev}; // stride, o_lo, o_up_e, o_up_a, n_ch
   if (mc.n_ch > 1023) return SR_ERR_UNSUPPORTED; // (10 bits per channel in the zones kernel's packed item word)
-  if (zones_mc_image(mc.n_ch) == 0 || wings_mc_lds(mc.n_ch) > (size_t)160 * 1024)
-    return SR_ERR_UNSUPPORTED;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  CoefWork &w = *ls->work;
+  if (zones_mc_image(mc.n_ch) == 0 || wings_mc_lds(mc.n_ch) > (size_t)160 * 1024) return SR_ERR_UNSUPPORTED;
   McWork &m = ls->mc;
   const size_t n_pts = (size_t)(g_hi - g_lo);
-  const int n_far = ctypes3 ? 2 * nlev : nlev;
   FarParams fp0;
   far_hierarchy(n_pts, 1, &fp0);
-  const size_t coef_row = (size_t)fp0.n_boxes_total * 2 * kFC; // doubles per (far pass, row)
-  // Row batches: the full list's records + every far pass's coefficients + what the largest level pass needs of the
-  // shared CoefWork (two table sets, far-field scratch) stay under the table budget
-  const size_t per_row = (size_t)std::max<int64_t>(ls->n_lines, 1) * (sizeof(FastRec) + sizeof(ColdRec)) * 4 +
-                         sizeof(double) * coef_row * (size_t)(n_far + 2) + 4 * ((n_pts + 64 * kSrcPad + kHalf) / 64 + 16) * (size_t)kMomPerBox * sizeof(double);
-  const int rows_max = (int)std::max<size_t>(1, g_table_budget.load() / per_row);
-  const std::vector<double> bounds_all = ls->bounds_temps;
-  if (!bounds_all.empty() && (int)bounds_all.size() != n_rows) {
-    g_err = "sr_lineset_set_bounds_temps was given another number of layers than this call";
-    return SR_ERR_ARG;
-  }
-  struct Restore {
-    sr_lineset *ls; const std::vector<double> &all;
-    ~Restore() { ls->bounds_temps = all; }
-  } restore{ls, bounds_all};
+  c.coef_row = (size_t)fp0.n_boxes_total * 2 * kFC;
+  // row batches under the table budget
+  const int rows_max = (int)std::max<size_t>(1, g_table_budget.load() / mc_bytes_per_row(ls, n_pts, c.coef_row, c.n_far));
   if (!m.ev_prep) {
     HIPCHK(hipEventCreateWithFlags(&m.ev_prep, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&m.ev_zones, hipEventDisableTiming));
     for (auto &e : m.ev_t) HIPCHK(hipEventCreate(&e));
   }
-  const bool timing = g_timing.load() != 0; // (the events of the LAST row batch stay readable: sr_last_level_tables_ms)
+  c.timing = g_timing.load() != 0; // (the events of the LAST row batch stay readable: sr_last_level_tables_ms)
   m.timed = false;
-  const int npop = nlev;
-  for (int k0 = 0; k0 < n_rows; k0 += rows_max) {
-    const int nl = std::min(rows_max, n_rows - k0);
-    sr_layers_desc sub = *atm;
-    sub.n_layers = nl;
-    sub.temps = atm->temps + k0;
-    sub.press = atm->press + k0;
-    sub.q_part = atm->q_part ? atm->q_part + k0 : nullptr;
-    sub.tvib = nullptr; // (no populations enter the level spectra)
-    if (!bounds_all.empty()) ls->bounds_temps.assign(bounds_all.begin() + k0, bounds_all.begin() + k0 + nl);
-    const bool frozen = !ls->bounds_temps.empty();
-    // this batch after everything earlier on the handle (the previous batch's kernels read the tables refilled below)
-    if (w.last_done_recorded) HIPCHK(hipStreamWaitEvent(st, w.ev_last_done, 0));
-    const size_t hl_bytes = layer_stage_bytes(nl, npop);
-    // (prepare() waits on the HOST for the mark behind the previous batch's -- or build's -- last kernel: nothing of this
-    // batch is enqueued before the previous one has finished with the pass's scratch.  That is what keeps the far passes
-    // below, whose internal streams are not ordered after the caller's, from writing m.d_coef under the wings kernel of
-    // the batch before.)
-    int rc = m.s_layers.prepare(hl_bytes);
-    if (rc) return rc;
-    rc = fill_layer_stage(ls, ls, ls, &sub, m.s_layers.host<double>());
-    if (rc) return rc;
-    rc = m.s_layers.push(hl_bytes, st);
-    if (rc) return rc;
-    const int *d_pm = nullptr;
-    const LayersDev A = layers_dev_of(m.s_layers.d.as<double>(), nl, npop, frozen, ls->linear_weights, &d_pm);
-    const int *zmax_dev = d_pm + 2 * nl;
-    const auto lo_it = std::lower_bound(ls->ic.begin(), ls->ic.end(), (int)g_lo - (kHalf - 1));
-    const auto hi_it = std::upper_bound(ls->ic.begin(), ls->ic.end(), (int)g_hi - 1 + kHalf);
-    const int line_lo = (int)(lo_it - ls->ic.begin());
-    const int n_sub = (int)(hi_it - lo_it);
-    const IcIndex ix{ls->d_first.as<int>(), ls->first_x0, ls->first_n, line_lo, n_sub};
-    auto chan_rows = [&](int c) { return out + ((size_t)c * n_rows + (size_t)k0) * n_pts; };
-    if (n_sub <= 0) {
-      for (int c = 0; c < mc.n_ch; ++c) HIPCHK(hipMemsetAsync(chan_rows(c), 0, sizeof(double) * n_pts * nl, st));
-    } else {
-      rc = m.d_fast.ensure(sizeof(FastRec) * ((size_t)n_sub * nl + 1));
-      if (rc) return rc;
-      rc = m.d_cold.ensure(sizeof(ColdRec) * ((size_t)n_sub * nl + 1));
-      if (rc) return rc;
-      rc = m.d_coef.ensure(sizeof(double) * coef_row * (size_t)nl * n_far);
-      if (rc) return rc;
-      if (timing) HIPCHK(hipEventRecord(m.ev_t[0], st));
-      LAUNCHCHK(launch_prep(ls->L, A, ls->gp, WeightMode{kWeightChannels, ctypes3 ? 1 : 0}, line_lo, n_sub, (int)g_lo, (int)g_hi - 1,
-                            m.d_fast.as<FastRec>(), m.d_cold.as<ColdRec>(), st));
-      if (timing) HIPCHK(hipEventRecord(m.ev_t[1], st));
-      HIPCHK(hipEventRecord(m.ev_prep, st)); // the layer stage, the tables and everything earlier on the caller's stream
-      // The zones kernel beside the far passes, the wings kernel after both.  The build is bound by its kernels' WORK, not
-      // their order -- 13.25 / 13.32 ms with the zones kernel gated behind the far passes, 13.06 / 13.13 beside them; the
-      // sparse passes' single batched launch no longer starves beside it as their twelve small chains did
-      // (profiles/r06_mc_timeline_v3 / v5).
-      LAUNCHCHK(launch_zones_mc(m.d_fast.as<FastRec>(), m.d_cold.as<ColdRec>(), ls->L.lev_up + line_lo, ls->L.lev_lo + line_lo, ix,
-                                zmax_dev, n_sub, nl, (int)g_lo, (int)g_hi, ls->gp, mc, out, n_rows, k0, st));
-      if (timing) HIPCHK(hipEventRecord(m.ev_t[2], st));
-      // far-only passes of the level sub-linesets
-      rc = m.s_far.prepare(sizeof(McFarPass) * (size_t)n_far);
-      if (rc) return rc;
-      McFarPass *far = m.s_far.host<McFarPass>();
-      // The passes are independent of each other.  The dense ones (one or two per build) go one after the other on the
-      // handle's far_st, each through a CoefWork of its own (tables, events) instead of the handle's shared one, so that
-      // none waits for another's scratch; the sparse ones in one batch beside them (below) -- one after the other on one
-      // chain stream the eleven sparse passes (0.33 ms each, latency-bound) and the dense ground-state pass were 7.7 ms,
-      // longer than the zones kernel they run beside.  Largest sub-lineset first (its chain is the longest).
-      if (!m.fw_init) {
-        for (auto &fwk : m.fw) {
-          rc = fwk.init();
-          if (rc) return rc;
-          fwk.streams_of = &w; // the handle's two streams, not a set each
-        }
-        m.fw_init = true;
-      }
-      std::vector<sr_lineset *> child((size_t)n_far, nullptr);
-      std::vector<int> order((size_t)n_far);
-      for (int f = 0; f < n_far; ++f) {
-        rc = level_set(ls, ctypes3 ? f / 2 : f, &child[(size_t)f], ctypes3 && (f & 1)); // ind_emission: the lines whose UPPER level is lv only
-        if (rc) return rc;
-        order[(size_t)f] = f;
-      }
-      std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return child[(size_t)x]->n_lines > child[(size_t)y]->n_lines; });
-      auto pass_of = [&](int f, int *lv, bool *ind) { *lv = ctypes3 ? f / 2 : f; *ind = ctypes3 && (f & 1); };
-      auto weights_of = [&](int lv, bool ind) {
-        return !ctypes3 ? WeightMode{kWeightLevelPair, lv} : (ind ? WeightMode{kWeightGind, lv} : WeightMode{kWeightGabsGsp, lv});
-      };
-      // SPARSE sub-linesets (coef_op's rule: far-field mode 3, fewer than 0.35 lines per grid point -- per-line expansions
-      // at every level, sr_farfield_rows_kernel): ALL of them in one batch of three launches -- tables, expansions, downward
-      // pass -- on the handle's near_st, beside the dense passes' chains.  One coefficient op each, they were eleven launches
-      // of 0.3 ms, latency-bound, each behind ~0.3 ms of host calls: 6 ms of a 13 ms build (gpurun_out/r06/tl_v4.txt).
-      // They share this pass's layer stage: their own would hold the same numbers (margins of the parent).
-      std::vector<int> dense;
-      {
-        rc = m.s_batch.prepare(sizeof(FarBatchItem) * (size_t)n_far);
-        if (rc) return rc;
-        FarBatchItem *items = m.s_batch.host<FarBatchItem>();
-        int n_items = 0, max_sub = 0;
-        size_t rec_total = 0;
-        std::vector<size_t> rec_off;
-        for (int q = 0; q < n_far; ++q) {
-          const int f = order[(size_t)q];
-          sr_lineset *c = child[(size_t)f];
-          const bool sparse = far_mode == 3 && (double)c->n_lines < 0.35 * (double)c->gp.n_grid;
-          if (!sparse) { dense.push_back(f); continue; }
-          int lv; bool ind;
-          pass_of(f, &lv, &ind);
-          far[f].ch_a = !ctypes3 ? 2 * lv : (ind ? 3 * lv + 1 : 3 * lv + 2);
-          far[f].ch_e = !ctypes3 ? 2 * lv + 1 : (ind ? -1 : 3 * lv);
-          const auto lo_c = std::lower_bound(c->ic.begin(), c->ic.end(), (int)g_lo - (kHalf - 1));
-          const auto hi_c = std::upper_bound(c->ic.begin(), c->ic.end(), (int)g_hi - 1 + kHalf);
-          const int c_sub = (int)(hi_c - lo_c);
-          if (c_sub <= 0) { far[f].coef = nullptr; continue; }
-          FarBatchItem &it = items[n_items++];
-          it.L = c->L;
-          it.first = c->d_first.as<int>();
-          it.first_x0 = c->first_x0;
-          it.first_n = c->first_n;
-          it.line_lo = (int)(lo_c - c->ic.begin());
-          it.n_sub = c_sub;
-          it.W = weights_of(lv, ind);
-          it.coef = m.d_coef.as<double>() + coef_row * (size_t)nl * f;
-          far[f].coef = it.coef;
-          rec_off.push_back(rec_total);
-          rec_total += (size_t)c_sub * nl;
-          max_sub = std::max(max_sub, c_sub);
-        }
-        if (n_items > 0) {
-          rc = m.d_bfast.ensure(sizeof(FastRec) * (rec_total + 1));
-          if (rc) return rc;
-          for (int i = 0; i < n_items; ++i) items[i].fast = m.d_bfast.as<FastRec>() + rec_off[(size_t)i];
-          // (serial schedule, sr_set_overlap(0): everything on the caller's stream, one kernel after the other)
-          hipStream_t bst = st;
-          if (g_overlap.load() != 0) { // beside the dense passes' chains (far_st): the handle's near_st
-            hipStream_t fst = nullptr;
-            rc = w.pipeline_streams(&fst, &bst);
-            if (rc) return rc;
-          }
-          if (bst != st) HIPCHK(hipStreamWaitEvent(bst, m.ev_prep, 0));
-          rc = m.s_batch.push(sizeof(FarBatchItem) * (size_t)n_items, bst);
-          if (rc) return rc;
-          FarParams fpb;
-          far_hierarchy(n_pts, nl, &fpb);
-          fpb.pm = d_pm;
-          fpb.coef = nullptr;
-          fpb.m2l = 0; fpb.rows = 1; fpb.pm_src = d_pm + nl; fpb.disp_lo_end = 0; fpb.disp_hi_begin = 0; fpb.mom = nullptr; fpb.tab = nullptr;
-          for (int lv = 0; lv < kMaxFarLevels; ++lv) fpb.n_src[lv] = fpb.src_off[lv] = 0;
-          const double *l2l_tab = nullptr;
-          rc = l2l_table_dev(&l2l_tab);
-          if (rc) return rc;
-          LAUNCHCHK(launch_far_batch(m.s_batch.d.as<FarBatchItem>(), n_items, max_sub, A, ls->gp, zmax_dev, (int)g_lo, fpb, l2l_tab, bst));
-          HIPCHK(hipEventRecord(m.ev_zones, bst));
-          rc = m.s_batch.mark(bst);
-          if (rc) return rc;
-        }
-        m.batch_pending = n_items > 0;
-      }
-      // the dense passes (the ground state's, typically), each through a CoefWork of its own
-      for (size_t q = 0; q < dense.size(); ++q) {
-        const int f = dense[q];
-        int lv; bool ind;
-        pass_of(f, &lv, &ind);
-        sr_lineset *c = child[(size_t)f];
-        double *coef = m.d_coef.as<double>() + coef_row * (size_t)nl * f;
-        bool has = false;
-        CoefOpt o;
-        o.far_coef = coef;
-        o.far_has = &has;
-        CoefWork *const shared = c->work;
-        c->work = &m.fw[q % kMcFarLanes];
-        rc = coef_op(c, &sub, g_lo, g_hi, nullptr, nullptr, stream, weights_of(lv, ind), o);
-        c->work = shared;
-        if (rc) return rc;
-        far[f].coef = has ? coef : nullptr;
-        far[f].ch_a = !ctypes3 ? 2 * lv : (ind ? 3 * lv + 1 : 3 * lv + 2);
-        far[f].ch_e = !ctypes3 ? 2 * lv + 1 : (ind ? -1 : 3 * lv);
-      }
-      if (m.batch_pending) HIPCHK(hipStreamWaitEvent(st, m.ev_zones, 0));
-      rc = m.s_far.push(sizeof(McFarPass) * (size_t)n_far, st);
-      if (rc) return rc;
-      FarParams fp;
-      far_hierarchy(n_pts, nl, &fp);
-      fp.pm = d_pm;
-      fp.coef = nullptr;
-      fp.m2l = 0; fp.rows = 0; fp.pm_src = d_pm + nl; fp.disp_lo_end = 0; fp.disp_hi_begin = 0; fp.mom = nullptr; fp.tab = nullptr;
-      for (int lv = 0; lv < kMaxFarLevels; ++lv) fp.n_src[lv] = fp.src_off[lv] = 0;
-      if (timing) HIPCHK(hipEventRecord(m.ev_t[3], st));
-      LAUNCHCHK(launch_wings_mc(m.d_fast.as<FastRec>(), ls->L.lev_up + line_lo, ls->L.lev_lo + line_lo, ix, zmax_dev, n_sub, nl,
-                                (int)g_lo, (int)g_hi, fp, mc, m.s_far.d.as<McFarPass>(), n_far, out, n_rows, k0, st));
-      if (timing) {
-        HIPCHK(hipEventRecord(m.ev_t[4], st));
-        m.timed = true;
-      }
-      rc = m.s_far.mark(st);
-      if (rc) return rc;
-    }
-    // lines whose centre lies outside their window (humliv_bb's outer branches): per level, as the per-level route
-    if (ls->n_outer > 0) {
-      // (one record buffer for the largest level: sized per level, a growing buffer was freed -- a device synchronisation --
-      // between the levels' launches)
-      rc = m.d_outer_recs.ensure(sizeof(OuterRec) * (size_t)ls->n_outer * nl);
-      if (rc) return rc;
-      for (int f = 0; f < n_far; ++f) {
-        const int lv = ctypes3 ? f / 2 : f;
-        const bool ind = ctypes3 && (f & 1);
-        sr_lineset *c = nullptr;
-        rc = level_set(ls, lv, &c, ind);
-        if (rc) return rc;
-        if (c->n_outer <= 0) continue;
-        double *o_a, *o_e;
-        if (!ctypes3) { o_a = chan_rows(2 * lv); o_e = chan_rows(2 * lv + 1); }
-        else if (!ind) { o_a = chan_rows(3 * lv + 2); o_e = chan_rows(3 * lv); }
-        else {
-          rc = ls->d_gscratch.ensure(sizeof(double) * n_pts * nl); // the unused second channel of the ind_emission weights
-          if (rc) return rc;
-          o_a = chan_rows(3 * lv + 1); o_e = ls->d_gscratch.as<double>();
-        }
-        const WeightMode W = !ctypes3 ? WeightMode{kWeightLevelPair, lv} : (ind ? WeightMode{kWeightGind, lv} : WeightMode{kWeightGabsGsp, lv});
-        LAUNCHCHK(launch_outer(c->Lo, c->n_outer, A, ls->gp, W, m.d_outer_recs.as<OuterRec>(), (int)g_lo, (int)g_hi, o_a, o_e, st));
-      }
-    }
-    rc = m.s_layers.mark(st);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(w.ev_last_done, st));
-    w.last_done_recorded = true;
-  }
-  return SR_OK;
+  return for_layer_batches(atm, ls, nlev, false, rows_max, [&](const sr_layers_desc &sub, int k0) { return mc_rows(c, sub, k0); });
 }
 
 extern "C" {
@@ -1798,7 +1818,7 @@ int sr_line_strengths_dev(sr_lineset *ls, const sr_layers_desc *atm, int source,
   if (source != SR_STRENGTH_EINSTEIN && source != SR_STRENGTH_HITRAN) return SR_ERR_ARG;
   if (source == SR_STRENGTH_EINSTEIN && !std::isfinite(iso_ab)) return SR_ERR_ARG;
   if (source == SR_STRENGTH_HITRAN && !ls->has_strengths) return SR_ERR_ARG;
-  const int nl = atm->n_layers, npop = ls->n_levels > 0 ? ls->n_levels : 1;
+  const int nl = atm->n_layers;
   for (int k = 0; k < nl; ++k)
     if (!(atm->temps[k] > 0.0)) return SR_ERR_ARG;
   if (atm->tvib)
@@ -1816,23 +1836,15 @@ int sr_line_strengths_dev(sr_lineset *ls, const sr_layers_desc *atm, int source,
   if (!a.press) a.press = press.data();
   hipStream_t st = static_cast<hipStream_t>(stream);
   CoefWork &w = *ls->work;
-  const size_t hl_bytes = layer_stage_bytes(nl, npop);
-  int rc = ls->s_str.prepare(hl_bytes);
+  LayerStage S;
+  int rc = stage_layers(ls->s_str, ls, ls, ls, &a, source == SR_STRENGTH_HITRAN ? q_ref : 0.0, false,
+                        w.last_done_recorded ? w.ev_last_done : nullptr, st, &S);
   if (rc) return rc;
-  rc = fill_layer_stage(ls, ls, ls, &a, ls->s_str.host<double>(), source == SR_STRENGTH_HITRAN ? q_ref : 0.0);
-  if (rc) return rc;
-  if (w.last_done_recorded) HIPCHK(hipStreamWaitEvent(st, w.ev_last_done, 0));
-  rc = ls->s_str.push(hl_bytes, st);
-  if (rc) return rc;
-  const int *d_pm = nullptr;
-  const LayersDev A = layers_dev_of(ls->s_str.d.as<double>(), nl, npop, false, false, &d_pm);
-  LAUNCHCHK(launch_line_strengths(ls->L, ls->Lo, ls->d_inpos.as<int>(), (int)ls->n_in, A, source, iso_ab, ls->s_t_ref,
+  LAUNCHCHK(launch_line_strengths(ls->L, ls->Lo, ls->d_inpos.as<int>(), (int)ls->n_in, S.A, source, iso_ab, ls->s_t_ref,
                                   s_ab, s_em, st));
   rc = ls->s_str.mark(st);
   if (rc) return rc;
-  HIPCHK(hipEventRecord(w.ev_last_done, st));
-  w.last_done_recorded = true;
-  return SR_OK;
+  return w.end_call(st, -1);
 }
 
 int sr_abscoeff_layers_from_strengths_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi,
@@ -1853,7 +1865,7 @@ int sr_abscoeff_layers_from_strengths_dev(sr_lineset *ls, const sr_layers_desc *
 
 int sr_gcoeff_layers_dev(sr_lineset *ls, const sr_layers_desc *atm, int level, int64_t g_lo, int64_t g_hi,
                          double *g_out, void *stream) {
-  if (!ls || !atm || !g_out || atm->n_layers <= 0 || g_lo < 0 || g_lo >= g_hi) return SR_ERR_ARG;
+  if (!g_out || check_coef_call(ls, atm, g_lo, g_hi, true)) return SR_ERR_ARG;
   sr_lineset *c = nullptr;
   int rc = level_set(ls, level, &c);
   if (rc) return rc;
@@ -1885,7 +1897,7 @@ int sr_abscoeff_level_dev(sr_lineset *ls, const sr_layers_desc *atm, int level, 
 }
 
 int sr_glevel_pairs_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi, double *out, void *stream) {
-  if (!ls || !atm || !out || atm->n_layers <= 0 || g_lo < 0 || g_lo >= g_hi) return SR_ERR_ARG;
+  if (!out || check_coef_call(ls, atm, g_lo, g_hi, true)) return SR_ERR_ARG;
   const size_t plane = (size_t)atm->n_layers * (size_t)(g_hi - g_lo);
   if (ls->n_levels == 0) // the 'all' set: every line, pop = 1 / Q in the combine (smm:2052-2057)
     return coef_op(ls, atm, g_lo, g_hi, out, out + plane, stream, WeightMode{kWeightLevelPair, -1});
@@ -1907,7 +1919,7 @@ int sr_glevel_pairs_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo,
 }
 
 int sr_gcoeff_levels_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi, double *g_out, void *stream) {
-  if (!ls || !atm || !g_out || atm->n_layers <= 0 || g_lo < 0 || g_lo >= g_hi) return SR_ERR_ARG;
+  if (!g_out || check_coef_call(ls, atm, g_lo, g_hi, true)) return SR_ERR_ARG;
   if (ls->n_levels == 0) return sr_gcoeff_layers_dev(ls, atm, 0, g_lo, g_hi, g_out, stream);
   {
     const int rc = mc_pass(ls, atm, g_lo, g_hi, g_out, stream, 1);

@@ -2555,11 +2555,10 @@ int zones_mc_image(int n_ch) {
   return zones_mc_lds(n_ch, 128) <= (size_t)160 * 1024 ? 128 : 0;
 }
 template <int WT>
-static int launch_zones_mc_wt(const FastRec *fast, const ColdRec *cold, const int *lev_up, const int *lev_lo, const IcIndex &ix,
-                              const int *zmax, int n_sub, int n_layers, int g_lo, int g_hi, const GridParams &gp, const McChannels &mc,
+static int launch_zones_mc_wt(const ShardTables &t, const int *lev_up, const int *lev_lo, const GridParams &gp, const McChannels &mc,
                               double *out, int n_rows_total, int row0, hipStream_t st) {
   constexpr int NW = kMcWaves;
-  const int n_t = (g_hi - g_lo + WT - 1) / WT;
+  const int n_t = (t.g_hi - t.g_lo + WT - 1) / WT;
   // (more than 64 KB of dynamic LDS needs the attribute once per kernel and DEVICE: a process that moves to another
   // device sets it there too)
   static unsigned long long attr_set = 0;
@@ -2569,28 +2568,24 @@ static int launch_zones_mc_wt(const FastRec *fast, const ColdRec *cold, const in
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sr_zones_mc_kernel<WT, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set |= 1ull << (dev & 63);
   }
-  hipLaunchKernelGGL((sr_zones_mc_kernel<WT, NW>), dim3((unsigned)(n_t * n_layers)), dim3(64 * NW), zones_mc_lds(mc.n_ch, WT), st, fast, cold,
-                     lev_up, lev_lo, ix, zmax, n_sub, n_t, g_lo, g_hi, gp, mc, out, n_rows_total, row0);
+  hipLaunchKernelGGL((sr_zones_mc_kernel<WT, NW>), dim3((unsigned)(n_t * t.n_layers)), dim3(64 * NW), zones_mc_lds(mc.n_ch, WT), st, t.fast, t.cold,
+                     lev_up, lev_lo, t.ix, t.zmax, t.ix.n_sub, n_t, t.g_lo, t.g_hi, gp, mc, out, n_rows_total, row0);
   return (int)hipGetLastError();
 }
-int launch_zones_mc(const FastRec *fast, const ColdRec *cold, const int *lev_up, const int *lev_lo, const IcIndex &ix,
-                    const int *zmax, int n_sub, int n_layers, int g_lo, int g_hi, const GridParams &gp, const McChannels &mc,
+int launch_zones_mc(const ShardTables &t, const int *lev_up, const int *lev_lo, const GridParams &gp, const McChannels &mc,
                     double *out, int n_rows_total, int row0, hipStream_t st) {
-  if (g_hi <= g_lo || n_layers <= 0) return 0;
+  if (t.g_hi <= t.g_lo || t.n_layers <= 0) return 0;
   const int wt = zones_mc_image(mc.n_ch);
-  if (wt == kMcImage)
-    return launch_zones_mc_wt<kMcImage>(fast, cold, lev_up, lev_lo, ix, zmax, n_sub, n_layers, g_lo, g_hi, gp, mc, out, n_rows_total, row0, st);
-  if (wt == 128)
-    return launch_zones_mc_wt<128>(fast, cold, lev_up, lev_lo, ix, zmax, n_sub, n_layers, g_lo, g_hi, gp, mc, out, n_rows_total, row0, st);
+  if (wt == kMcImage) return launch_zones_mc_wt<kMcImage>(t, lev_up, lev_lo, gp, mc, out, n_rows_total, row0, st);
+  if (wt == 128) return launch_zones_mc_wt<128>(t, lev_up, lev_lo, gp, mc, out, n_rows_total, row0, st);
   return (int)hipErrorInvalidValue;
 }
 
 size_t wings_mc_lds(int n_ch) { return sizeof(double) * ((size_t)n_ch * 64 + 64 * kMcWingWaves); }
-int launch_wings_mc(const FastRec *fast, const int *lev_up, const int *lev_lo, const IcIndex &ix, const int *zmax, int n_sub,
-                    int n_layers, int g_lo, int g_hi, const FarParams &fp, const McChannels &mc, const McFarPass *far, int n_far,
-                    double *out, int n_rows_total, int row0, hipStream_t st) {
-  if (g_hi <= g_lo || n_layers <= 0) return 0;
-  const int n_g1 = (g_hi - g_lo + 63) / 64;
+int launch_wings_mc(const ShardTables &t, const int *lev_up, const int *lev_lo, const FarParams &fp, const McChannels &mc,
+                    const McFarPass *far, int n_far, double *out, int n_rows_total, int row0, hipStream_t st) {
+  if (t.g_hi <= t.g_lo || t.n_layers <= 0) return 0;
+  const int n_g1 = (t.g_hi - t.g_lo + 63) / 64;
   const size_t lds = wings_mc_lds(mc.n_ch); // the image + the polynomial stage's staging rows
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
   static unsigned long long attr_set = 0; // (per kernel and device, see launch_zones_mc_wt)
@@ -2600,39 +2595,25 @@ int launch_wings_mc(const FastRec *fast, const int *lev_up, const int *lev_lo, c
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sr_wings_mc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set |= 1ull << (dev & 63);
   }
-  hipLaunchKernelGGL(sr_wings_mc_kernel, dim3((unsigned)(n_g1 * n_layers)), dim3(64 * kMcWingWaves), lds, st, fast, lev_up, lev_lo, ix, zmax, n_sub,
-                     n_g1, g_lo, g_hi, fp, mc, far, n_far, out, n_rows_total, row0);
+  hipLaunchKernelGGL(sr_wings_mc_kernel, dim3((unsigned)(n_g1 * t.n_layers)), dim3(64 * kMcWingWaves), lds, st, t.fast, lev_up, lev_lo, t.ix, t.zmax,
+                     t.ix.n_sub, n_g1, t.g_lo, t.g_hi, fp, mc, far, n_far, out, n_rows_total, row0);
   return (int)hipGetLastError();
 }
 
-// a += za, e += ze (small shards: the zones kernel's private result joins the wings kernel's)
-__global__ __launch_bounds__(256) void sr_add2_kernel(double *__restrict__ a, const double *__restrict__ za,
-                                                      double *__restrict__ e, const double *__restrict__ ze, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    a[i] += za[i];
-    e[i] += ze[i];
-  }
-}
-int launch_add2(double *a, const double *za, double *e, const double *ze, size_t n, hipStream_t st) {
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(sr_add2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, za, e, ze, n);
-  return (int)hipGetLastError();
-}
-
-int launch_farfield(const FastRec *fast, const IcIndex &ix, const int *zmax, int n_sub, int n_layers, int g_lo,
-                    int g_hi, const FarParams &fp, unsigned long long *cnt, hipStream_t st) {
+int launch_farfield(const ShardTables &t, const FarParams &fp, unsigned long long *cnt, hipStream_t st) {
+  const IcIndex &ix = t.ix;
+  const int n_sub = ix.n_sub, n_layers = t.n_layers, g_lo = t.g_lo, g_hi = t.g_hi;
   if (g_hi <= g_lo || n_layers <= 0) return 0;
   if (!fp.m2l && fp.rows) { // sparse line set: a box for kFarRows layers per wave
     const dim3 gr((unsigned)(fp.n_boxes_total * ((n_layers + kFarRows - 1) / kFarRows)));
     if (cnt)
-      hipLaunchKernelGGL(sr_farfield_rows_kernel<true>, gr, dim3(64), 0, st, fast, ix, zmax, n_sub, g_lo, fp, cnt);
+      hipLaunchKernelGGL(sr_farfield_rows_kernel<true>, gr, dim3(64), 0, st, t.fast, ix, t.zmax, n_sub, g_lo, fp, cnt);
     else
-      hipLaunchKernelGGL(sr_farfield_rows_kernel<false>, gr, dim3(64), 0, st, fast, ix, zmax, n_sub, g_lo, fp, cnt);
+      hipLaunchKernelGGL(sr_farfield_rows_kernel<false>, gr, dim3(64), 0, st, t.fast, ix, t.zmax, n_sub, g_lo, fp, cnt);
     return (int)hipGetLastError();
   }
   const dim3 grid((unsigned)((fp.m2l ? fp.box_count[0] : fp.n_boxes_total) * n_layers));
-#define SR_FAR(C, M) hipLaunchKernelGGL((sr_farfield_kernel<C, M>), grid, dim3(64), 0, st, fast, ix, zmax, n_sub, g_lo, g_hi, fp, cnt)
+#define SR_FAR(C, M) hipLaunchKernelGGL((sr_farfield_kernel<C, M>), grid, dim3(64), 0, st, t.fast, ix, t.zmax, n_sub, g_lo, g_hi, fp, cnt)
   if (fp.m2l) {
     if (cnt) SR_FAR(true, true); else SR_FAR(false, true);
   } else {
@@ -2642,15 +2623,16 @@ int launch_farfield(const FastRec *fast, const IcIndex &ix, const int *zmax, int
   return (int)hipGetLastError();
 }
 
-int launch_m2l(const FastRec *fast, const IcIndex &ix, const int *zmax, int n_sub, int n_layers, int g_lo, int g_hi,
-               const FarParams &fp, unsigned long long *cnt, hipStream_t st, int which) {
+int launch_m2l(const ShardTables &t, const FarParams &fp, unsigned long long *cnt, hipStream_t st, int which) {
+  const IcIndex &ix = t.ix;
+  const int n_sub = ix.n_sub, n_layers = t.n_layers, g_lo = t.g_lo, g_hi = t.g_hi;
   if (g_hi <= g_lo || n_layers <= 0) return 0;
   if (which & 1) {
   const dim3 g1((unsigned)(fp.n_src[0] * n_layers));
   if (cnt)
-    hipLaunchKernelGGL(sr_s2m_kernel<true>, g1, dim3(64), 0, st, fast, ix, n_sub, g_lo, fp, cnt);
+    hipLaunchKernelGGL(sr_s2m_kernel<true>, g1, dim3(64), 0, st, t.fast, ix, n_sub, g_lo, fp, cnt);
   else
-    hipLaunchKernelGGL(sr_s2m_kernel<false>, g1, dim3(64), 0, st, fast, ix, n_sub, g_lo, fp, cnt);
+    hipLaunchKernelGGL(sr_s2m_kernel<false>, g1, dim3(64), 0, st, t.fast, ix, n_sub, g_lo, fp, cnt);
   for (int l = 1; l < fp.n_levels; ++l) { // upward pass, level by level
     const int n2 = fp.n_src[l] * n_layers * 4;
     hipLaunchKernelGGL(sr_m2m_kernel, dim3((unsigned)((n2 + 63) / 64)), dim3(64), 0, st, fp, l);
@@ -2660,9 +2642,9 @@ int launch_m2l(const FastRec *fast, const IcIndex &ix, const int *zmax, int n_su
   int chunks = 0;
   for (int lv = 0; lv < fp.n_levels; ++lv) chunks += (fp.box_count[lv] * n_layers + 15) / 16;
   if (cnt)
-    hipLaunchKernelGGL(sr_m2l_kernel<true>, dim3((unsigned)chunks), dim3(64), 0, st, zmax, fp, cnt);
+    hipLaunchKernelGGL(sr_m2l_kernel<true>, dim3((unsigned)chunks), dim3(64), 0, st, t.zmax, fp, cnt);
   else
-    hipLaunchKernelGGL(sr_m2l_kernel<false>, dim3((unsigned)chunks), dim3(64), 0, st, zmax, fp, cnt);
+    hipLaunchKernelGGL(sr_m2l_kernel<false>, dim3((unsigned)chunks), dim3(64), 0, st, t.zmax, fp, cnt);
   return (int)hipGetLastError();
 }
 
@@ -2700,10 +2682,10 @@ static void launch_zones(dim3 gz, const FastRec *fast, const ColdRec *cold, cons
                      n_t, g_lo, g_hi, gp, add, abs_out, emi_out, cnt, 0);
 }
 
-int launch_near(int part, int add, const FastRec *fast, const ColdRec *cold, const IcIndex &ix, const int *zmax,
-                int n_sub, int n_layers, int g_lo, int g_hi, const GridParams &gp, const FarParams &fp,
-                double *abs_out, double *emi_out, unsigned long long *cnt, hipStream_t st, const double *z_abs,
-                const double *z_emi) {
+int launch_near(int part, int add, const ShardTables &t, const GridParams &gp, const FarParams &fp, double *abs_out,
+                double *emi_out, unsigned long long *cnt, hipStream_t st, const double *z_abs, const double *z_emi) {
+  const IcIndex &ix = t.ix;
+  const int n_sub = ix.n_sub, n_layers = t.n_layers, g_lo = t.g_lo, g_hi = t.g_hi;
   if (g_hi <= g_lo || n_layers <= 0) return 0;
   const int n_groups = (g_hi - g_lo + kGroup - 1) / kGroup;
   const dim3 grid((unsigned)(n_groups * n_layers));
@@ -2712,10 +2694,10 @@ int launch_near(int part, int add, const FastRec *fast, const ColdRec *cold, con
     const int n_g1 = (g_hi - g_lo + 63) / 64;
     if (cnt)
       hipLaunchKernelGGL(sr_abscoeff_near_wings_kernel<true>, dim3((unsigned)(n_g1 * n_layers)), dim3(64), 0, st,
-                         fast, ix, zmax, n_sub, n_g1, g_lo, g_hi, fp, add, z_abs, z_emi, abs_out, emi_out, cnt);
+                         t.fast, ix, t.zmax, n_sub, n_g1, g_lo, g_hi, fp, add, z_abs, z_emi, abs_out, emi_out, cnt);
     else
       hipLaunchKernelGGL(sr_abscoeff_near_wings_kernel<false>, dim3((unsigned)(n_g1 * n_layers)), dim3(64), 0, st,
-                         fast, ix, zmax, n_sub, n_g1, g_lo, g_hi, fp, add, z_abs, z_emi, abs_out, emi_out, cnt);
+                         t.fast, ix, t.zmax, n_sub, n_g1, g_lo, g_hi, fp, add, z_abs, z_emi, abs_out, emi_out, cnt);
   } else {
     // Image width: wider images cut fewer zones in two (fewer (line, group) pairs: 7.1 -> 6.7 ms on
     // 1e5 points x 80 layers with 512 instead of 256) as long as the waves still fill the chip
@@ -2724,8 +2706,8 @@ int launch_near(int part, int add, const FastRec *fast, const ColdRec *cold, con
     const int n_t = (g_hi - g_lo + kZoneImage - 1) / kZoneImage;
     const dim3 gz((unsigned)(n_t * n_layers));
 #define SR_ZONES(NW)                                                                                         \
-  (cnt ? launch_zones<NW, true>(gz, fast, cold, ix, zmax, n_sub, n_t, g_lo, g_hi, gp, add, abs_out, emi_out, cnt, st) \
-       : launch_zones<NW, false>(gz, fast, cold, ix, zmax, n_sub, n_t, g_lo, g_hi, gp, add, abs_out, emi_out, cnt, st))
+  (cnt ? launch_zones<NW, true>(gz, t.fast, t.cold, ix, t.zmax, n_sub, n_t, g_lo, g_hi, gp, add, abs_out, emi_out, cnt, st) \
+       : launch_zones<NW, false>(gz, t.fast, t.cold, ix, t.zmax, n_sub, n_t, g_lo, g_hi, gp, add, abs_out, emi_out, cnt, st))
     if (waves512 >= 3 * 4096)
       SR_ZONES(1);
     else if (waves512 >= 3 * 2048)
@@ -2758,24 +2740,25 @@ int launch_prep(const LinesDev &L, const LayersDev &A, const GridParams &gp, con
 
 int abscoeff_tile_points(int variant) { return 64 * (variant == 4 ? 4 : 8); }
 
-int launch_abscoeff(int variant, int which, const FastRec *fast, const ColdRec *cold, const IcIndex &ix,
-                    const int *zmax, int n_sub, int n_layers, int g_lo, int g_hi, const GridParams &gp,
-                    double *abs_out, double *emi_out, hipStream_t st) {
+int launch_abscoeff(int variant, int which, const ShardTables &t, const GridParams &gp, double *abs_out, double *emi_out,
+                    hipStream_t st) {
+  const IcIndex &ix = t.ix;
+  const int n_sub = ix.n_sub, n_layers = t.n_layers, g_lo = t.g_lo, g_hi = t.g_hi;
   if (g_hi <= g_lo || n_layers <= 0) return 0;
   if (which == 0) {
     const int tp = abscoeff_tile_points(variant);
     const int n_tiles = (g_hi - g_lo + tp - 1) / tp;
     dim3 grid((unsigned)(n_tiles * n_layers));
     if (variant == 4)
-      hipLaunchKernelGGL((sr_abscoeff_wings_kernel<4>), grid, dim3(64), 0, st, fast, ix, n_sub, n_tiles,
+      hipLaunchKernelGGL((sr_abscoeff_wings_kernel<4>), grid, dim3(64), 0, st, t.fast, ix, n_sub, n_tiles,
                          g_lo, g_hi, abs_out, emi_out);
     else
-      hipLaunchKernelGGL((sr_abscoeff_wings_kernel<8>), grid, dim3(64), 0, st, fast, ix, n_sub, n_tiles,
+      hipLaunchKernelGGL((sr_abscoeff_wings_kernel<8>), grid, dim3(64), 0, st, t.fast, ix, n_sub, n_tiles,
                          g_lo, g_hi, abs_out, emi_out);
   } else {
     const int n_groups = (g_hi - g_lo + kGroup - 1) / kGroup;
     dim3 grid((unsigned)(n_groups * n_layers));
-    hipLaunchKernelGGL(sr_abscoeff_cores_kernel, grid, dim3(64), 0, st, fast, cold, ix, zmax, n_sub, n_groups,
+    hipLaunchKernelGGL(sr_abscoeff_cores_kernel, grid, dim3(64), 0, st, t.fast, t.cold, ix, t.zmax, n_sub, n_groups,
                        g_lo, g_hi, gp, abs_out, emi_out);
   }
   return (int)hipGetLastError();

@@ -60,6 +60,15 @@ struct IcIndex {
   const int *first;
   int x0, n_tab, line_lo, n_sub;
 };
+// What the kernels of a call read of its shard [g_lo, g_hi): the record tables [n_layers][ix.n_sub] of the lines that
+// meet it, the centre index and the layers' widest zones (zmax [n_layers], host bound: sr_api.hip, fill_layer_stage)
+struct ShardTables {
+  const FastRec *fast;
+  const ColdRec *cold;
+  IcIndex ix;
+  const int *zmax;
+  int n_layers, g_lo, g_hi;
+};
 
 // Far-field (local expansion) hierarchy over one shard: level l has boxes of
 // 64 << l points starting at g_lo.
@@ -168,7 +177,6 @@ struct FarParams {
   double *mom;       // [sum n_src][n_layers][kMomPerBox]
   const double *tab; // [2: o > 0, o < 0][kM2LOffsets][kM2LQ][kM2LRow] translation operator (host, long double)
 };
-int launch_add2(double *a, const double *za, double *e, const double *ze, size_t n, hipStream_t st);
 // Executed-work counters of the counting instantiations (sr_set_counting): index into cnt[kCntN].
 enum {
   kCntExpansions = 0, // (line, box) far-field expansions          sr_farfield_kernel
@@ -183,19 +191,16 @@ enum {
   kCntN = 10
 };
 // cnt: device counters [kCntN] or nullptr (the timed instantiations: no counting code)
-int launch_farfield(const FastRec *fast, const IcIndex &ix, const int *zmax, int n_sub, int n_layers, int g_lo,
-                    int g_hi, const FarParams &fp, unsigned long long *cnt, hipStream_t st);
+int launch_farfield(const ShardTables &t, const FarParams &fp, unsigned long long *cnt, hipStream_t st);
 // box-pair mode: moments of the level-0 source boxes, the wider levels, the translations (after the level-0 pass
 // of launch_farfield, which stores; the translations add at level 0 and store above)
 // which: bit 0 = moments + upward pass (sr_s2m_kernel, sr_m2m_kernel), bit 1 = translations (sr_m2l_kernel)
-int launch_m2l(const FastRec *fast, const IcIndex &ix, const int *zmax, int n_sub, int n_layers, int g_lo, int g_hi,
-               const FarParams &fp, unsigned long long *cnt, hipStream_t st, int which = 3);
+int launch_m2l(const ShardTables &t, const FarParams &fp, unsigned long long *cnt, hipStream_t st, int which = 3);
 void m2l_table_host(double *tab); // [2][kM2LOffsets][kM2LQ][kM2LRow]
 // part 1: wing-only pairs + far-field polynomials (writes); part 2: general pairs (adds)
 // z_abs / z_emi (part 1 only): the zones kernel's sums in a buffer of their own; the wings kernel writes z + its sums
-int launch_near(int part, int add, const FastRec *fast, const ColdRec *cold, const IcIndex &ix, const int *zmax,
-                int n_sub, int n_layers, int g_lo, int g_hi, const GridParams &gp, const FarParams &fp,
-                double *abs_out, double *emi_out, unsigned long long *cnt, hipStream_t st, const double *z_abs = nullptr,
+int launch_near(int part, int add, const ShardTables &t, const GridParams &gp, const FarParams &fp, double *abs_out,
+                double *emi_out, unsigned long long *cnt, hipStream_t st, const double *z_abs = nullptr,
                 const double *z_emi = nullptr);
 
 // ---- the multi-channel pass (sr_zones_mc_kernel, sr_wings_mc_kernel) ----
@@ -242,12 +247,10 @@ void l2l_table_host(double *tab); // [2][kFC][kFC]
 int launch_l2l(double *coef, int n_layers, const FarParams &fp, const double *tab, hipStream_t st);
 int zones_mc_image(int n_ch);     // points per image sr_zones_mc_kernel takes for n_ch planes (0: they do not fit the LDS)
 size_t wings_mc_lds(int n_ch);    // bytes of LDS of a sr_wings_mc_kernel workgroup
-int launch_zones_mc(const FastRec *fast, const ColdRec *cold, const int *lev_up, const int *lev_lo, const IcIndex &ix,
-                    const int *zmax, int n_sub, int n_layers, int g_lo, int g_hi, const GridParams &gp, const McChannels &mc,
+int launch_zones_mc(const ShardTables &t, const int *lev_up, const int *lev_lo, const GridParams &gp, const McChannels &mc,
                     double *out, int n_rows_total, int row0, hipStream_t st);
-int launch_wings_mc(const FastRec *fast, const int *lev_up, const int *lev_lo, const IcIndex &ix, const int *zmax, int n_sub,
-                    int n_layers, int g_lo, int g_hi, const FarParams &fp, const McChannels &mc, const McFarPass *far, int n_far,
-                    double *out, int n_rows_total, int row0, hipStream_t st);
+int launch_wings_mc(const ShardTables &t, const int *lev_up, const int *lev_lo, const FarParams &fp, const McChannels &mc,
+                    const McFarPass *far, int n_far, double *out, int n_rows_total, int row0, hipStream_t st);
 
 int launch_prep(const LinesDev &L, const LayersDev &A, const GridParams &gp, const WeightMode &W, int line_lo,
                 int n_sub, int cold_lo, int cold_hi, FastRec *fast, ColdRec *cold, hipStream_t st);
@@ -260,9 +263,8 @@ int launch_line_strengths(const LinesDev &L, const LinesDev &Lo, const int *inpo
                           int source, double iso_ab, double t_ref, double *s_ab, double *s_em, hipStream_t st);
 int abscoeff_tile_points(int variant);
 // which = 0: wings kernel (writes abs/emi), 1: cores kernel (adds into them)
-int launch_abscoeff(int variant, int which, const FastRec *fast, const ColdRec *cold, const IcIndex &ix,
-                    const int *zmax, int n_sub, int n_layers, int g_lo, int g_hi, const GridParams &gp,
-                    double *abs_out, double *emi_out, hipStream_t st);
+int launch_abscoeff(int variant, int which, const ShardTables &t, const GridParams &gp, double *abs_out, double *emi_out,
+                    hipStream_t st);
 // Options of the device LOS pipeline (include/spectrobot_hip.h: sr_los_desc)
 struct LimbOpts {
   int n_gas, n_seg_total, solo_absorption, init_mode, g_lo;

@@ -200,7 +200,8 @@ def _plane_err(a, b):
     return float(((a - b).abs() / s).max())
 
 
-@pytest.mark.parametrize("case", ["dense", "sparse_shard", "frozen_linear", "outer_lines", "low_pressure", "forty_levels"])
+@pytest.mark.parametrize("case", ["dense", "sparse_shard", "frozen_linear", "outer_lines", "low_pressure", "forty_levels",
+                                  "empty_levels", "shard_past_the_lines"])
 def test_multichannel_route_equals_the_per_level_route(eng, case):
     """Round 6: the level tables by the multi-channel pass (every line ONCE: sr_zones_mc_kernel / sr_wings_mc_kernel add
     its three weighted contributions to the LDS planes of its two levels; far field by far-only passes of the level
@@ -208,8 +209,10 @@ def test_multichannel_route_equals_the_per_level_route(eng, case):
     to the reference's add_PT -> BuildCoeff run by test_gcoeff_levels_golden).  Pair tables AND the three ctypes; whole
     grids and shards whose lines reach beyond the grid; frozen boundaries with linearised weights (the T + dT build of
     configs[3]); lines whose centre lies outside their window; Doppler-dominated rows (wide region-3 cores); an
-    iso-molecule with forty levels (80 / 120 planes: the zones kernel's 128-point images).  The two routes differ by the
-    order of summation only: <= 2e-12 of a spectrum's largest value."""
+    iso-molecule with forty levels (80 / 120 planes: the zones kernel's 128-point images); levels that own no line (a far
+    pass without coefficients); a shard that no main line's window meets, reached by outer lines only (the tables are
+    zeroed, then the outer lines added).  The two routes differ by the order of summation only: <= 2e-12 of a spectrum's
+    largest value."""
     import torch
     from spectrobot_amd import synthetic as syn
     n_grid, n_lines, nl, lo, hi, w0 = 40000, 30000, 6, 0, None, 2985.0
@@ -222,8 +225,17 @@ def test_multichannel_route_equals_the_per_level_route(eng, case):
     if case == "forty_levels":
         n_grid, n_lines, nl, n_lev = 12000, 9000, 3, 40
         e_lev = np.concatenate([[0.0], np.linspace(1300.0, 6000.0, 39)])
+    n_lev_lines, n_line_pts, p_scale = n_lev, None, 1e-3 if case == "low_pressure" else 1.0
+    if case == "empty_levels":   # levels 7..11 own no line
+        n_grid, n_lines, nl, n_lev_lines = 12000, 4000, 3, 7
+    elif case == "shard_past_the_lines":   # the lines sit on the first 6000 points, the shard starts at point 20000
+        n_grid, n_lines, nl, n_lev_lines, n_line_pts, lo, hi, p_scale = 30000, 400, 3, 7, 6000, 20000, 30000, 20.0
     grid = syn.make_grid(w0, 5e-4, n_grid)
-    L = syn.make_lines(n_lines, grid, seed=61, n_levels=n_lev, config_id=2)
+    L = syn.make_lines(n_lines, grid[:n_line_pts], seed=61, n_levels=n_lev_lines, config_id=2)
+    if case == "shard_past_the_lines":
+        # eight lines 3.3 .. 9 cm-1 beyond the upper grid end, further out than the window half-width: outer lines,
+        # whose wide Lorentz wings (20 x the pressure) reach the shard
+        L["freq"][-8:] = grid[-1] + np.linspace(3.3, 9.0, 8)
     if case == "outer_lines":   # some lines up to 6 cm-1 beyond the grid ends: their windows sit on the end points
         rng = np.random.default_rng(4)
         k = rng.choice(n_lines, 400, replace=False)
@@ -232,7 +244,7 @@ def test_multichannel_route_equals_the_per_level_route(eng, case):
         L["freq"][k[:200]] = grid[0] - rng.uniform(0.0, 6.0, 200)
         L["freq"][k[200:]] = grid[-1] + rng.uniform(0.0, 6.0, 200)
     atm = syn.make_atmosphere(nl, 12)
-    T, P = atm["temps"], atm["press"] * (1e-3 if case == "low_pressure" else 1.0)
+    T, P = atm["temps"], atm["press"] * p_scale
     ls = eng.LineSet(L, grid, 6, 1, syn.CH4_MM, e_lev)
     try:
         if case == "frozen_linear":
