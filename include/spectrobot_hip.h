@@ -367,6 +367,29 @@ typedef struct {
  * (curgods.f:24-45), evaluated on the device.  Synchronises. */
 int sr_los_columns(const sr_los_desc *los, double *col_out);
 
+/* The path of LIMB rays as a function of each ray's own tangent altitude z_t [km], the crossed shells held fixed
+ * (geometry.limb_los(path=True)): per sample point its altitude and the derivatives of its path coordinate and of its
+ * altitude.  With r_t = R + z_t and a shell end at radius hi > r_t, s_hi = sqrt(hi^2 - r_t^2), d s_hi / d z_t =
+ * -r_t / s_hi (s = 0 with derivative 0 at the tangent point); sample point i of a segment [a, b] blends the ends
+ * linearly, alt_i = sqrt(s_i^2 + r_t^2) - R, d alt_i / d z_t = (s_i d s_i + r_t) / (alt_i + R): 0 on a shell boundary, 1
+ * at the tangent point.  The derivative is one-sided where z_t lies on a level (the tangent shell is the one above).
+ * Not defined for 3-D paths, slant / nadir paths, adaptive stepping, observer order, the resident handles, refraction. */
+typedef struct {
+  const double *alt;     /* HOST [n_pt] altitude of the sample points, km */
+  const double *dx_dz;   /* HOST [n_pt] d x / d z_t, cm per km */
+  const double *dalt_dz; /* HOST [n_pt] d alt / d z_t */
+} sr_los_path;
+
+/* d col_g[s] / d z_t, the twin of sr_los_columns: dcol_out HOST [n_gas][n_seg] = col_scale[g] times the forward-mode
+ * derivative of curgod_fort_2's sum over the segment, with d x from the path and, ln nd and every VMR being linear in
+ * altitude inside a segment (slopes from its first and last sample point; zero where their altitudes coincide),
+ *   d nd_i = nd_i slope_ln_nd dalt_dz[i],   d vmr_i = slope_vmr dalt_dz[i].
+ * A segment whose path derivatives are all zero gives an exact 0.0.  path or one of its arrays NULL: SR_ERR_ARG;
+ * los_order != 0: SR_ERR_UNSUPPORTED (observer-order batches re-list their sample points).  Synchronises.
+ * The reference has no counterpart: checked against an extended-precision restatement and against differences of
+ * rebuilt geometry (tests/pointing_reference.py, tests/test_gpu_pointing.py). */
+int sr_los_columns_dz(const sr_los_desc *los, const sr_los_path *path, double *dcol_out);
+
 /* Radiances of the ray batch.  abs_c / emi_c: DEVICE [n_gas][n_layers][n_pts]; rad: DEVICE [n_rays][n_pts].
  * Per-gas and per-level partial radiances (single_rads[(gas, iso)], single_rads[(gas, iso, lev)],
  * spect_main_module.py:2883-2887, 3287): sr_limb_rays_parts_dev below, all of them in one pass.  (An emission share
@@ -675,6 +698,35 @@ int sr_limb_rays_state_bands_instr_gases_dev(const double *abs_c, const double *
                                              const double *demi_c, int n_row, const double *par_t, const double *centers_nm,
                                              const double *widths_nm, int n_bands, double n_sigma, int out_units,
                                              const double *fov, double *out, void *stream);
+
+/* The mixed-state calls with the POINTING derivative: d I / d z_t of every ray's own tangent altitude (for a batch:
+ * d / d delta with every z_t -> z_t + delta), the crossed shells held fixed.  In a 1-D scene a ray's radiance depends on
+ * z_t through its columns only, d I / d z_t = sum_g sum_s d I / d u_g[s] d u_g[s] / d z_t: n_gas more column slots of the
+ * same pass, slot g of gas g with D = d col_g / d z_t (sr_los_columns_dz's kernel, staged with the batch), added up
+ * afterwards; the recursion kernel is the one of the calls without.
+ * sr_limb_rays_jac_state_path_dev: the arguments of sr_limb_rays_jac_state_gases_dev with `path` in front of rad;
+ * n_state = n_col + n_lev + n_row may be 0.  jac: DEVICE [n_rays][n_state + n_gas][n_pts]: rows 0 .. n_state - 1 what
+ * the call without returns (bit for bit), row n_state the pointing derivative; the rows behind it are workspace.
+ * sr_limb_rays_state_bands_path_dev: the arguments of sr_limb_rays_state_bands_gases_dev, then instrument (!= 0: with
+ * the two instrument rows) and path.  out: HOST [n_rays / 3 or n_rays][1 + n_state + 1 (+ 2)][n_bands]: the radiance,
+ * the state rows, the pointing row, the instrument rows; the per-gas rows are added on the host, before the field of
+ * view (which is linear in the rays' band values).  Synchronises the stream.
+ * Refused before the first copy or launch, outputs untouched: path or one of its arrays NULL (SR_ERR_ARG), los_order
+ * != 0 (SR_ERR_UNSUPPORTED), and whatever the twin entries refuse.
+ * The reference has no counterpart: checked against the extended-precision recursion and against central differences
+ * of rebuilt batches (tests/test_gpu_pointing.py). */
+int sr_limb_rays_jac_state_path_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                    const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
+                                    const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas, const int32_t *par_level,
+                                    const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
+                                    const double *par_t, const sr_los_path *path, double *rad, double *jac, void *stream);
+int sr_limb_rays_state_bands_path_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                      const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
+                                      const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas, const int32_t *par_level,
+                                      const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
+                                      const double *par_t, const double *centers_nm, const double *widths_nm, int n_bands,
+                                      double n_sigma, int out_units, const double *fov, double *out, void *stream,
+                                      int instrument, const sr_los_path *path);
 
 /* The radiance budget of the ray batch: which gas, and which level of the level-factored gas `gas`, emits the radiance
  * that arrives.  The recursion is linear in the emission: with tau = sum_g abs_g[r] u_g, t = exp(-tau), f = (1 - t) / tau

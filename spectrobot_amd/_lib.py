@@ -73,6 +73,10 @@ class LevelGasDesc(C.Structure):
     _fields_ = [("gas", C.c_int32), ("n_levels", C.c_int32), ("n_tab_rows", C.c_int32), ("tab", C.c_void_p), ("coef_row", ip)]
 
 
+class LosPath(C.Structure):
+    _fields_ = [("alt", dp), ("dx_dz", dp), ("dalt_dz", dp)]
+
+
 # every symbol include/spectrobot_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     "sr_strerror": (C.c_char_p, [C.c_int]),
@@ -167,6 +171,15 @@ SYMBOLS = {
                                                            ip, dp, C.c_int, C.POINTER(LevelGasDesc), C.c_int, ip, ip, dp, C.c_void_p,
                                                            C.c_void_p, C.c_int, dp, dp, dp, C.c_int, C.c_double, C.c_int, dp, dp,
                                                            C.c_void_p]),
+    "sr_los_columns_dz": (C.c_int, [C.POINTER(LosDesc), C.POINTER(LosPath), dp]),
+    "sr_limb_rays_jac_state_path_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(LosDesc), C.c_int, ip,
+                                                  dp, C.c_int, C.POINTER(LevelGasDesc), C.c_int, ip, ip, dp, C.c_void_p,
+                                                  C.c_void_p, C.c_int, dp, C.POINTER(LosPath), C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
+    "sr_limb_rays_state_bands_path_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(LosDesc), C.c_int, ip,
+                                                    dp, C.c_int, C.POINTER(LevelGasDesc), C.c_int, ip, ip, dp, C.c_void_p,
+                                                    C.c_void_p, C.c_int, dp, dp, dp, C.c_int, C.c_double, C.c_int, dp, dp,
+                                                    C.c_void_p, C.c_int, C.POINTER(LosPath)]),
     "sr_limb_rays_parts_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(LosDesc), C.c_int,
                                          C.c_void_p, C.c_int, C.c_int, ip, C.c_int, ip, ip, dp, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),

@@ -2196,8 +2196,11 @@ int check_los_par(const sr_los_desc *los, int n_layers, int n_par, const int32_t
 
 // Stage a checked LOS (check_los_par: `shape`) and evaluate the columns of the gases and of n_par profile parameters;
 // `st` waits for them.  own: the staging slot of a device-resident LOS (sr_los_create) instead of the per-call ring.
+// path (photon order only, the caller has checked): the sample points' derivatives to the ray's tangent altitude join
+// the pack, and n_gas more rows behind the column table, rows n_gas + n_par .., take d col_g / d z_t
+// (sr_los_columns_dz_kernel).
 int stage_los(const sr_los_desc *los, const LosShape &shape, int n_par, const int32_t *par_gas, const double *par_w,
-              hipStream_t st, LosDev *out, Stager *own = nullptr) {
+              hipStream_t st, LosDev *out, Stager *own = nullptr, const sr_los_path *path = nullptr) {
   static thread_local StagerRing ring;
   StagePack pk(own ? *own : ring.take());
   const int n_seg = shape.n_seg, n_pt = shape.n_pt, n_prof = los->n_gas + n_par, nr = los->n_rays;
@@ -2206,7 +2209,9 @@ int stage_los(const sr_los_desc *los, const LosShape &shape, int n_par, const in
   const auto p_prof = pk.room<double>((size_t)n_prof * n_pt), p_scale = pk.room<double>((size_t)n_prof);
   const auto p_soff = pk.copy(los->seg_off, (size_t)nr + 1), p_slay = pk.copy(los->seg_layer, (size_t)n_seg);
   const auto p_poff = pk.copy(los->pt_off, (size_t)n_seg + 1), p_pgas = pk.copy(par_gas, (size_t)n_par, 1);
-  pk.tail(sizeof(double) * (size_t)n_prof * n_seg); // the column table
+  StagePack::Part<double> p_alt{0}, p_dx{0}, p_dalt{0}; // (registered with a path only: the pack without is what it was)
+  if (path) p_alt = pk.copy(path->alt, (size_t)n_pt), p_dx = pk.copy(path->dx_dz, (size_t)n_pt), p_dalt = pk.copy(path->dalt_dz, (size_t)n_pt);
+  pk.tail(sizeof(double) * (size_t)(n_prof + (path ? los->n_gas : 0)) * n_seg); // the column table
   int rc = pk.prepare();
   if (rc) return rc;
   double *prs = pk.host(p_prof), *sc = pk.host(p_scale);
@@ -2247,6 +2252,9 @@ int stage_los(const sr_los_desc *los, const LosShape &shape, int n_par, const in
   *out = LosDev{pk.dev(p_soff), pk.dev(p_slay), pk.dev(p_poff), pk.dev(p_pgas), pk.dev(p_x), pk.dev(p_nd), pk.dev(p_prof),
                 pk.dev(p_scale), pk.dev_tail<double>(), n_seg, n_pt, n_prof, &pk.slot()};
   LAUNCHCHK(launch_los_columns(out->nd, out->x, out->prof, out->scale, out->pt_off, n_seg, n_pt, n_prof, out->col, cs));
+  if (path)
+    LAUNCHCHK(launch_los_columns_dz(out->nd, out->x, out->prof, out->scale, out->pt_off, pk.dev(p_alt), pk.dev(p_dx),
+                                    pk.dev(p_dalt), n_seg, n_pt, los->n_gas, out->col + (size_t)n_prof * n_seg, cs));
   return pk.slot().end_early(cs, st);
 }
 
@@ -2387,6 +2395,23 @@ int sr_los_columns(const sr_los_desc *los, double *col_out) {
         const int q = los->los_order == 0 ? s : los->seg_off[r] + (los->seg_off[r + 1] - 1 - s);
         col_out[(size_t)g * D.n_seg + s] = tmp[(size_t)g * D.n_seg + q];
       }
+  return SR_OK;
+}
+
+int sr_los_columns_dz(const sr_los_desc *los, const sr_los_path *path, double *dcol_out) {
+  if (!dcol_out || !path || !path->alt || !path->dx_dz || !path->dalt_dz) return SR_ERR_ARG;
+  LosShape shape;
+  int rc = check_los(los, 0, &shape);
+  if (rc) return rc;
+  if (los->los_order != 0) {
+    g_err = "sr_los_columns_dz: the pointing derivative needs the batch in photon order (observer order re-lists the sample points)";
+    return SR_ERR_UNSUPPORTED;
+  }
+  LosDev D;
+  rc = stage_los(los, shape, 0, nullptr, nullptr, nullptr, &D, nullptr, path);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(dcol_out, D.col + (size_t)los->n_gas * D.n_seg, sizeof(double) * (size_t)los->n_gas * D.n_seg,
+                   hipMemcpyDeviceToHost));
   return SR_OK;
 }
 
@@ -3377,14 +3402,18 @@ int sr_limb_rays_jac_layer_dev(const double *abs_c, const double *emi_c, const d
 // par_lgas (several level-factored gases): level parameter p belongs to level gas par_lgas[p]; the level parameters are
 // then listed by (level gas, level) and an entry carries level | level gas << kLevelEntGasShift.  Without it the plan is
 // the one-gas plan, word for word.
+// n_hid (the pointing derivative): n_hid more column slots behind the caller's, slot g of gas g, whose rows of dcol follow
+// the caller's; their rows of jac come LAST, n_col + n_lev + n_row + g, the other kinds keep the rows they have without.
 struct LevelJacPlan {
   int n_blocks;
   std::vector<int> blk, ent_off, slot_par;
   std::vector<LevelEnt> ent;
 };
 static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev, const int32_t *par_level, const double *par_c,
-                                   int n_layers, int n_row = 0, const double *par_t = nullptr, const int32_t *par_lgas = nullptr) {
-  const int n_cl = n_col + n_lev, n_par = n_cl + n_row, np = level_jac_np(n_par);
+                                   int n_layers, int n_row = 0, const double *par_t = nullptr, const int32_t *par_lgas = nullptr,
+                                   int n_hid = 0) {
+  const int n_state = n_col + n_lev + n_row;
+  const int nc_all = n_col + n_hid, n_cl = nc_all + n_lev, n_par = n_cl + n_row, np = level_jac_np(n_par);
   const int n_blocks = std::max(1, (n_par + np - 1) / np); // (no parameter at all, the instrument rows alone: one block of unused slots)
   std::vector<int32_t> packed; // the `level` words of the entries: the level, with several level gases the gas above it
   if (par_lgas) {
@@ -3396,16 +3425,17 @@ static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev,
   LevelJacPlan P{n_blocks, std::vector<int>((size_t)n_blocks * 2, 0), std::vector<int>((size_t)n_blocks * (n_layers + 1)),
                  std::vector<int>((size_t)n_blocks * np, -1), {}};
   for (int b = 0; b < n_blocks; ++b) {
-    const int i0 = b * np, i1 = std::min(n_par, i0 + np), nc = std::max(0, std::min(n_col, i1) - i0);
+    const int i0 = b * np, i1 = std::min(n_par, i0 + np), nc = std::max(0, std::min(nc_all, i1) - i0);
     unsigned gases = 0u;
-    for (int i = i0; i < i0 + nc; ++i) gases |= (unsigned)par_gas[i] << (2 * (i - i0));
+    for (int i = i0; i < i0 + nc; ++i) gases |= (unsigned)(i < n_col ? par_gas[i] : i - n_col) << (2 * (i - i0));
     P.blk[2 * b] = nc;
     P.blk[2 * b + 1] = (int)gases;
-    for (int i = i0; i < i1; ++i) P.slot_par[i] = i < n_col || i >= n_cl ? i : n_col + order[i - n_col];
+    for (int i = i0; i < i1; ++i)
+      P.slot_par[i] = i < n_col ? i : i < nc_all ? n_state + (i - n_col) : i < n_cl ? n_col + order[i - nc_all] : i - n_hid;
     for (int r = 0; r < n_layers; ++r) {
       P.ent_off[(size_t)b * (n_layers + 1) + r] = (int)P.ent.size();
-      for (int i = std::max(i0, n_col); i < std::min(i1, n_cl); ++i) {
-        const int p = order[i - n_col];
+      for (int i = std::max(i0, nc_all); i < std::min(i1, n_cl); ++i) {
+        const int p = order[i - nc_all];
         const double c = par_c[(size_t)p * n_layers + r];
         if (c != 0.0) P.ent.push_back(LevelEnt{i - i0, par_level[p], c});
       }
@@ -3468,6 +3498,8 @@ struct StateCall {
   bool cols = false;
   double *rad = nullptr, *jac = nullptr; // the spectra, or
   const StateBands *bands = nullptr;     // the bands block
+  // the pointing derivative: n_gas hidden column slots behind the caller's, their rows behind the state's (cols is set)
+  const sr_los_path *path = nullptr;
 };
 static sr_level_gas one_level_gas(int gas, const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row) {
   sr_level_gas g;
@@ -3484,8 +3516,9 @@ static int limb_jac_state(const StateCall &c, const LosShape &shape, const void 
   const int n_layers = b.n_layers, n_col = c.col.n_col, n_lev = c.lev.n_lev, n_row = c.row.n_row, n_lgas = c.lev.n_lgas;
   const sr_level_gas *lgas = c.lev.lgas;
   const bool several = n_lgas > 1;
+  const int n_hid = c.path ? b.los->n_gas : 0;
   const LevelJacPlan P = level_jac_plan(n_col, c.col.par_gas, n_lev, c.lev.par_level, c.lev.par_c, n_layers, n_row, c.row.par_t,
-                                        several ? c.lev.par_lgas : nullptr);
+                                        several ? c.lev.par_lgas : nullptr, n_hid);
   static thread_local StagerRing ring;
   StagePack pk(ring.take());
   const auto p_ent = pk.copy(P.ent.data(), P.ent.size(), 1); // (no entries: a valid pointer all the same)
@@ -3503,7 +3536,7 @@ static int limb_jac_state(const StateCall &c, const LosShape &shape, const void 
   int rc = pk.stage(st);
   if (rc) return rc;
   LosDev D;
-  rc = stage_los(b.los, shape, n_col, c.col.par_gas, c.col.par_w, st, &D);
+  rc = stage_los(b.los, shape, n_col, c.col.par_gas, c.col.par_w, st, &D, nullptr, c.path);
   if (rc) return rc;
   LevelGasTabs lg{};
   for (int k = 0; several && k < n_lgas; ++k) {
@@ -3522,11 +3555,12 @@ static int limb_jac_state(const StateCall &c, const LosShape &shape, const void 
   L.coef_row = pk.dev(p_row);
   L.n_blocks = P.n_blocks, L.blk = c.cols ? pk.dev(p_blk) : nullptr;
   L.ent_off = pk.dev(p_off), L.ent = pk.dev(p_ent), L.slot_par = pk.dev(p_slot);
-  L.n_par = n_col + n_lev + n_row;
+  L.n_par = n_col + n_lev + n_row + n_hid;
   if (n_row > 0) L.dabs = c.row.dabs_c, L.demi = c.row.demi_c;
   L.rad = c.rad, L.jac = c.jac;
   if (c.bands) L.lowres_scratch = band_scratch, L.n_bands = c.bands->n_bands, L.instr = c.bands->instr;
   LAUNCHCHK(launch_limb_jac_state(L, st));
+  if (n_hid && !c.bands) LAUNCHCHK(launch_jac_rows_sum(c.jac, L.n_rays, L.n_par - n_hid, n_hid, L.n_pts, st));
   return mark_both(pk.slot(), *D.slot, st);
 }
 
@@ -3542,7 +3576,7 @@ static int check_state_call(const StateCall &c, LosShape *shape) {
   const sr_level_gas *lgas = c.lev.lgas;
   const int32_t *par_lgas = c.lev.par_lgas, *par_level = c.lev.par_level;
   const bool out_ok = c.bands ? c.bands->out && c.bands->centers_nm && c.bands->widths_nm && c.bands->n_bands > 0 : c.jac != nullptr;
-  const bool may_be_empty = c.bands && c.bands->instr;
+  const bool may_be_empty = (c.bands && c.bands->instr) || c.path;
   const bool list_ok = lgas && n_lgas >= 1 && n_lgas <= kLevelGasMax;
   bool lev_ok = n_lev == 0 || (list_ok && par_level && c.lev.par_c && (n_lgas == 1 || par_lgas));
   for (int k = 0; list_ok && n_lev > 0 && k < n_lgas; ++k)
@@ -3566,7 +3600,11 @@ static int check_state_call(const StateCall &c, LosShape *shape) {
     if (k < 0 || k >= n_lgas) return SR_ERR_ARG;
     if (par_level[p] < 0 || par_level[p] >= lgas[k].n_levels) return SR_ERR_ARG;
   }
-  if ((int64_t)n_col + n_lev + n_row > INT_MAX) return SR_ERR_LIMIT;
+  if ((int64_t)n_col + n_lev + n_row + (c.path ? b.los->n_gas : 0) > INT_MAX) return SR_ERR_LIMIT;
+  if (c.path && b.los->los_order != 0) {
+    g_err = std::string(c.entry) + ": the pointing derivative needs the batch in photon order (observer order re-lists the sample points)";
+    return SR_ERR_UNSUPPORTED;
+  }
   if (n_lgas > 1) // (an entry's word holds the level below kLevelEntGasShift)
     for (int k = 0; n_lev > 0 && k < n_lgas; ++k)
       if (lgas[k].n_levels > kLevelEntLevelMask + 1) return SR_ERR_LIMIT;
@@ -3582,7 +3620,7 @@ static int limb_state_spectra(const StateCall &c) {
 // ... of one level gas with a row block.  Nothing of the third kind: the state call, checks and all; else, without
 // column parameters, the instances without column code (fewer registers, the same arithmetic).
 static int limb_state_rows(StateCall &c) {
-  c.cols = c.col.n_col > 0;
+  c.cols = c.col.n_col > 0 || c.path;
   if (c.row.n_row == 0) {
     c.entry = "sr_limb_rays_jac_state_dev";
     c.row = StateRows{};
@@ -3599,15 +3637,16 @@ static int limb_state_bands(StateCall &c) {
   const StateBands &B = *c.bands;
   const sr_los_desc *los = c.b.los;
   const int64_t n_pts = c.b.n_pts;
-  c.cols = c.col.n_col > 0;
+  c.cols = c.col.n_col > 0 || c.path;
   LosShape shape;
   int rc = check_state_call(c, &shape);
   if (rc) return rc;
   // instr: the two instrument rows are the last two parameter rows of every ray, here and in the kernel; the sum kernel
   // and the field of view (linear in the rays' band values) take them as they are
   const int n_rays = los->n_rays, n_state = c.col.n_col + c.lev.n_lev + c.row.n_row;
-  if (B.instr && n_state > INT_MAX - 2) return SR_ERR_LIMIT;
-  const int n_par = n_state + (B.instr ? 2 : 0);
+  const int n_hid = c.path ? los->n_gas : 0, n_instr = B.instr ? 2 : 0;
+  if (n_state > INT_MAX - 2 - n_hid) return SR_ERR_LIMIT;
+  const int n_par = n_state + n_hid + n_instr;
   if (B.fov && n_rays % 3 != 0) return SR_ERR_ARG;
   if ((int64_t)n_rays * (1 + (int64_t)n_par) > INT_MAX) return SR_ERR_LIMIT;
   const int n_spec = n_rays * (1 + n_par);
@@ -3627,7 +3666,27 @@ static int limb_state_bands(StateCall &c) {
   LAUNCHCHK(launch_lowres_sum_blocks((int)n_pts, n_spec, B.n_bands, B.out_units, static_cast<double *>(t_lowres.s_land.h),
                                      t_lowres.d_weights.p, st, B.instr));
   HIPCHK(hipStreamSynchronize(st));
-  fov_rows(static_cast<const double *>(t_lowres.s_land.h), n_rays, n_par, B.n_bands, B.fov, B.out);
+  const double *low = static_cast<const double *>(t_lowres.s_land.h);
+  if (!n_hid) {
+    fov_rows(low, n_rays, n_par, B.n_bands, B.fov, B.out);
+    return SR_OK;
+  }
+  // the pointing row: the hidden per-gas rows added up, in gas order, on the band values that reached the host; the
+  // state rows and the instrument rows move as they are
+  const int n_out = n_state + 1 + n_instr, nb = B.n_bands;
+  std::vector<double> packed((size_t)n_rays * (1 + n_out) * nb);
+  std::memcpy(packed.data(), low, sizeof(double) * (size_t)n_rays * nb);
+  for (int r = 0; r < n_rays; ++r) {
+    const double *src = low + ((size_t)n_rays + (size_t)r * n_par) * nb;
+    double *dst = packed.data() + ((size_t)n_rays + (size_t)r * n_out) * nb;
+    std::memcpy(dst, src, sizeof(double) * (size_t)n_state * nb);
+    double *pt = dst + (size_t)n_state * nb;
+    std::memcpy(pt, src + (size_t)n_state * nb, sizeof(double) * nb);
+    for (int g = 1; g < n_hid; ++g)
+      for (int k = 0; k < nb; ++k) pt[k] = pt[k] + src[(size_t)(n_state + g) * nb + k];
+    if (n_instr) std::memcpy(pt + nb, src + (size_t)(n_state + n_hid) * nb, sizeof(double) * (size_t)n_instr * nb);
+  }
+  fov_rows(packed.data(), n_rays, n_out, nb, B.fov, B.out);
   return SR_OK;
 }
 
@@ -3753,8 +3812,49 @@ int sr_limb_rays_state_bands_instr_gases_dev(const double *abs_c, const double *
   return rc ? rc : limb_state_bands(c);
 }
 
+// ... with the POINTING derivative, d / d z_t of every ray's own tangent altitude: n_gas hidden column slots whose D rows
+// are d col_g / d z_t (stage_los with the path), added up behind the recursion.  The twin entries' records and checks.
+static bool path_ok(const sr_los_path *path) { return path && path->alt && path->dx_dz && path->dalt_dz; }
+
+int sr_limb_rays_jac_state_path_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                    const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
+                                    const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas, const int32_t *par_level,
+                                    const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
+                                    const double *par_t, const sr_los_path *path, double *rad, double *jac, void *stream) {
+  if (!path_ok(path)) return SR_ERR_ARG;
+  StateCall c{"sr_limb_rays_jac_state_path_dev", {abs_c, emi_c, n_layers, n_pts, los}, {n_col, par_gas, par_w},
+              {n_lgas, lgas, n_lev, par_lgas, par_level, par_c}, {dabs_c, demi_c, n_row, par_t}, stream};
+  c.rad = rad, c.jac = jac, c.path = path;
+  int rc;
+  if (one_level_gas_call(c, "sr_limb_rays_jac_state_path_dev", &rc)) {
+    if (rc) return rc;
+    c.cols = true;
+    if (n_row == 0) c.row = StateRows{};
+    return limb_state_spectra(c);
+  }
+  c.cols = true;
+  return limb_state_spectra(c);
+}
+
+int sr_limb_rays_state_bands_path_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts,
+                                      const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lgas,
+                                      const sr_level_gas *lgas, int n_lev, const int32_t *par_lgas, const int32_t *par_level,
+                                      const double *par_c, const double *dabs_c, const double *demi_c, int n_row,
+                                      const double *par_t, const double *centers_nm, const double *widths_nm, int n_bands,
+                                      double n_sigma, int out_units, const double *fov, double *out, void *stream,
+                                      int instrument, const sr_los_path *path) {
+  if (!path_ok(path)) return SR_ERR_ARG;
+  const StateBands bands{centers_nm, widths_nm, n_bands, n_sigma, out_units, fov, out, /*instr=*/instrument != 0};
+  StateCall c{"sr_limb_rays_state_bands_path_dev", {abs_c, emi_c, n_layers, n_pts, los}, {n_col, par_gas, par_w},
+              {n_lgas, lgas, n_lev, par_lgas, par_level, par_c}, {dabs_c, demi_c, n_row, par_t}, stream};
+  c.bands = &bands, c.path = path;
+  int rc;
+  one_level_gas_call(c, "sr_limb_rays_state_bands_path_dev", &rc);
+  return rc ? rc : limb_state_bands(c);
+}
+
 int sr_limb_rays_parts_dev(const double *abs_c, const double *emi_c, int n_layers, int64_t n_pts, const sr_los_desc *los,
-                           int gas, const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_part,
+                           int gas,const double *tab, int n_levels, int n_tab_rows, const int32_t *coef_row, int n_part,
                            const int32_t *part_gas, const int32_t *part_level, const double *part_c, double *rad,
                            double *parts, void *stream) {
   // everything is checked here, before the first copy or launch (the LOS too, as sr_limb_rays_jac_level_dev does)

@@ -2983,6 +2983,76 @@ int launch_los_columns(const double *nd, const double *x, const double *prof, co
   return (int)hipGetLastError();
 }
 
+// d col_g[s] / d z_t of limb rays, the crossed shells held fixed (sr_los_columns_dz): the forward-mode derivative of
+// sr_los_columns_kernel's term.  Inside a segment ln nd and the VMR are linear in altitude (geometry.limb_los), their
+// slopes taken from the segment's first and last sample point (zero where the two altitudes coincide), so with
+// dx_dz = d x_i / d z_t [cm / km] and dalt_dz = d alt_i / d z_t of the path:
+//   d nd_i = nd_i slope_ln_nd dalt_dz[i],   d vmr_i = slope_vmr dalt_dz[i].
+// One thread per (segment, gas); row g of dcol, [n_gas][n_seg].  Zero path derivatives give an exact 0.0.
+__global__ void sr_los_columns_dz_kernel(const double *__restrict__ nd, const double *__restrict__ x,
+                                         const double *__restrict__ prof, // [.][n_pt]: the gases' VMRs first
+                                         const double *__restrict__ scale, const int *__restrict__ pt_off,
+                                         const double *__restrict__ alt, const double *__restrict__ dx_dz,
+                                         const double *__restrict__ dalt_dz, int n_seg, int n_pt,
+                                         double *__restrict__ dcol) {     // [n_gas][n_seg]
+  const int s = blockIdx.x * blockDim.x + threadIdx.x, g = blockIdx.y;
+  if (s >= n_seg) return;
+  const double *vmr = prof + (size_t)g * n_pt;
+  const int i0 = pt_off[s], i1 = pt_off[s + 1] - 1;
+  const double dal = alt[i1] - alt[i0];
+  const double sl_nd = dal != 0.0 ? log(nd[i1] / nd[i0]) / dal : 0.0;
+  const double sl_v = dal != 0.0 ? (vmr[i1] - vmr[i0]) / dal : 0.0;
+  double acc = 0.0;
+  for (int i = i0; i < i1; ++i) {
+    const double dx = x[i + 1] - x[i], ddx = dx_dz[i + 1] - dx_dz[i];
+    const double n0 = nd[i], n1 = nd[i + 1], v0 = vmr[i], v1 = vmr[i + 1];
+    const double dn0 = n0 * sl_nd * dalt_dz[i], dn1 = n1 * sl_nd * dalt_dz[i + 1];
+    const double dv0 = sl_v * dalt_dz[i], dv1 = sl_v * dalt_dz[i + 1];
+    const double A = n0 * v0, dA = dn0 * v0 + n0 * dv0;
+    const double B = n0 * (v1 - v0) / dx;
+    const double dB = (dn0 * (v1 - v0) + n0 * (dv1 - dv0)) / dx - B * ddx / dx;
+    const double fu = n1 / n0, dfu = (dn1 - fu * dn0) / n0;
+    const double L = log(fu), dL = dfu / fu; // L = D dx
+    const double D = L / dx, dD = (dL - D * ddx) / dx;
+    const double N = A * D * (fu - 1.) + B * fu * (L - 1.) + B;
+    const double dN = dA * D * (fu - 1.) + A * dD * (fu - 1.) + A * D * dfu + dB * fu * (L - 1.) + B * dfu * (L - 1.) +
+                      B * fu * dL + dB;
+    const double T = N / (D * D);
+    acc = acc + (dN - 2. * T * D * dD) / (D * D);
+  }
+  dcol[(size_t)g * n_seg + s] = scale[g] * acc;
+}
+
+int launch_los_columns_dz(const double *nd, const double *x, const double *prof, const double *scale, const int *pt_off,
+                          const double *alt, const double *dx_dz, const double *dalt_dz, int n_seg, int n_pt, int n_gas,
+                          double *dcol, hipStream_t st) {
+  if (n_seg <= 0 || n_gas <= 0) return 0;
+  hipLaunchKernelGGL(sr_los_columns_dz_kernel, dim3((n_seg + 63) / 64, n_gas), dim3(64), 0, st, nd, x, prof, scale, pt_off,
+                     alt, dx_dz, dalt_dz, n_seg, n_pt, dcol);
+  return (int)hipGetLastError();
+}
+
+// jac[ray][n_state][j] = sum over the n_hid rows behind it, in row order (the pointing row of
+// sr_limb_rays_jac_state_path_dev from its per-gas rows); rows of n_row_tot = n_state + n_hid.
+__global__ void sr_jac_rows_sum_kernel(double *__restrict__ jac, int n_rays, int n_state, int n_hid, int n_pts) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_pts) return;
+  for (int ray = blockIdx.y; ray < n_rays; ray += gridDim.y) {
+    double *row = jac + ((size_t)ray * (n_state + n_hid) + n_state) * n_pts + j;
+    double v = row[0];
+    for (int g = 1; g < n_hid; ++g) v = v + row[(size_t)g * n_pts];
+    row[0] = v;
+  }
+}
+
+int launch_jac_rows_sum(double *jac, int n_rays, int n_state, int n_hid, int n_pts, hipStream_t st) {
+  if (n_rays <= 0 || n_pts <= 0 || n_hid <= 1) return 0;
+  hipLaunchKernelGGL(sr_jac_rows_sum_kernel, dim3((n_pts + 255) / 256, n_rays < 65535 ? n_rays : 65535), dim3(256), 0, st, jac, n_rays, n_state,
+                     n_hid,
+                     n_pts);
+  return (int)hipGetLastError();
+}
+
 __device__ inline double limb_initial(const LimbOpts &o, const double *rad, size_t at, int j) {
   if (o.init_mode == 1) return rad[at];
   if (o.init_mode == 2) { // Calc_BB, spect_classes.py:1886

@@ -276,6 +276,12 @@ constexpr int kVmrParArg = 32;
 int launch_los_vmr_from_params(double *prof, int n_gas, int n_par, int n_pt, const int *par_gas, const double *x_host, hipStream_t st);
 int launch_los_columns(const double *nd, const double *x, const double *prof, const double *scale, const int *pt_off,
                        int n_seg, int n_pt, int n_prof, double *col, hipStream_t st);
+// d col / d z_t of the gases (rows [n_gas][n_seg] at dcol) from the path derivatives of the sample points
+int launch_los_columns_dz(const double *nd, const double *x, const double *prof, const double *scale, const int *pt_off,
+                          const double *alt, const double *dx_dz, const double *dalt_dz, int n_seg, int n_pt, int n_gas,
+                          double *dcol, hipStream_t st);
+// row n_state of jac [n_rays][n_state + n_hid][n_pts] += the rows behind it
+int launch_jac_rows_sum(double *jac, int n_rays, int n_state, int n_hid, int n_pts, hipStream_t st);
 int launch_limb(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
                 const int *seg_layer, const double *col, const LimbOpts &o, double *rad, hipStream_t st);
 int launch_limb_jac(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,

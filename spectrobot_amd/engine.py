@@ -444,6 +444,11 @@ def glevel_combine(tab, step_row, pop, tab_dT=None, dpop=None, dT=None, out=None
     return ((out[0], out[1]), (out[2], out[3])) if want_dT else (out[0], out[1])
 
 
+def _pointing_kw(pointing):
+    """pointing=True for the mixed-state calls, or nothing: without the pointing row a call is made as it always was."""
+    return dict(pointing=True) if pointing else {}
+
+
 class LevelFactored(object):
     """The level-factored route as one object: the pair tables of a LineSet on a set of (P, T) rows (LineSet.glevel_pairs;
     with dT also at T + dT, region boundaries frozen at T) and the combine for any number of LOS steps on those rows
@@ -527,7 +532,7 @@ class LevelFactored(object):
                                         g_lo=int(self._shard[0]), want_rad=want_rad)
 
     def state_jacobian(self, coeffs, los, step_row, tvib, par_level, par_w_level, par_gas=None, par_w_col=None, gas=0,
-                       q_part=None, grid=None, want_rad=True, dcoeffs=None, par_w_temp=None):
+                       q_part=None, grid=None, want_rad=True, dcoeffs=None, par_w_temp=None, pointing=False):
         """(rad | None, jac [n_rays, n_col + n_lev (+ n_row), n_pts]): d rad / d x for a mixed state vector in one pass
         (limb_rays_state_jacobian): first the VMR-profile parameters par_gas / par_w_col of limb_rays_jacobian (any gas
         of the batch, this one included; None: no such parameter), then the vibrational-temperature parameters
@@ -535,11 +540,12 @@ class LevelFactored(object):
         par_level: only column parameters).  dcoeffs and par_w_temp [n_row, n_steps] (both or neither): then the
         kinetic-temperature parameters, T[r] = T0[r] + sum_p par_w_temp[p, r] x_p, through the derivative spectra
         dcoeffs of every gas of the batch on the coefficient rows (this gas's: steps(..., derivative=True); the columns
-        held fixed).  Honours the object's spectral shard."""
+        held fixed).  Honours the object's spectral shard.  pointing=True: the pointing row behind the state's
+        (limb_rays_state_jacobian)."""
         step_row, par_level, par_c = self._state_level_args(step_row, tvib, par_level, par_w_level, q_part)
         return limb_rays_state_jacobian(coeffs, los, par_gas=par_gas, par_w=par_w_col, tab=self.tab, coef_row=step_row,
                                         par_level=par_level, par_c=par_c, gas=gas, grid=grid, g_lo=int(self._shard[0]),
-                                        want_rad=want_rad, dcoeffs=dcoeffs, par_t=par_w_temp)
+                                        want_rad=want_rad, dcoeffs=dcoeffs, par_t=par_w_temp, **_pointing_kw(pointing))
 
     def _state_level_args(self, step_row, tvib, par_level, par_w_level, q_part):
         """(step_row, par_level, par_c) of state_jacobian / state_bands: par_c = par_w_level * d pop / d Tvib, formed as in
@@ -560,18 +566,18 @@ class LevelFactored(object):
 
     def state_bands(self, coeffs, los, step_row, tvib, par_level, par_w_level, grid, centers_nm, widths_nm, par_gas=None,
                     par_w_col=None, gas=0, q_part=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None,
-                    instrument=False):
+                    instrument=False, pointing=False):
         """state_jacobian on the instrument's bands in one library call (limb_rays_state_bands): numpy [n_rays | n_rays / 3,
         1 + n_par, n_bands], row 0 the radiance, row 1 + p the derivative to parameter p (VMR-profile, vibrational-
         temperature, kinetic-temperature parameters, as state_jacobian orders them); no hi-res spectrum is written.  The
         parameters' arguments and their errors are state_jacobian's; the bands' (and fov) those of limb_rays_state_bands.
         Honours the object's spectral shard: partial band integrals then (`grid` is the whole grid).  instrument=True: the
-        two instrument rows behind the parameters' (limb_rays_state_bands)."""
+        two instrument rows behind the parameters' (limb_rays_state_bands); pointing=True: the pointing row in front of them."""
         step_row, par_level, par_c = self._state_level_args(step_row, tvib, par_level, par_w_level, q_part)
         return limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=par_gas, par_w=par_w_col, tab=self.tab,
                                      coef_row=step_row, par_level=par_level, par_c=par_c, gas=gas, dcoeffs=dcoeffs,
                                      par_t=par_w_temp, out_units=out_units, n_sigma=n_sigma, fov=fov,
-                                     g_lo=int(self._shard[0]), instrument=instrument)
+                                     g_lo=int(self._shard[0]), instrument=instrument, **_pointing_kw(pointing))
 
     def level_radiances(self, coeffs, los, step_row, tvib, levels=None, weights=None, gas=0, q_part=None, grid=None,
                         gas_parts=True):
@@ -646,23 +652,25 @@ class LevelFactoredSet(object):
         return gases, par_lgas, par_level, par_c
 
     def state_jacobian(self, coeffs, los, par_lgas, par_level, par_w_level, par_gas=None, par_w_col=None, grid=None,
-                       want_rad=True, dcoeffs=None, par_w_temp=None):
+                       want_rad=True, dcoeffs=None, par_w_temp=None, pointing=False):
         """LevelFactored.state_jacobian for the members' vibrational-temperature parameters together: (rad | None, jac
-        [n_rays, n_col + n_lev (+ n_row), n_pts]), the rows in the caller's order."""
+        [n_rays, n_col + n_lev (+ n_row), n_pts]), the rows in the caller's order; pointing=True: the pointing row behind."""
         gases, par_lgas, par_level, par_c = self._args(par_lgas, par_level, par_w_level)
         return limb_rays_state_jacobian(coeffs, los, par_gas=par_gas, par_w=par_w_col, par_level=par_level, par_c=par_c,
                                         grid=grid, g_lo=int(self.members[0][0]._shard[0]), want_rad=want_rad, dcoeffs=dcoeffs,
-                                        par_t=par_w_temp, level_gases=gases, par_lgas=par_lgas)
+                                        par_t=par_w_temp, level_gases=gases, par_lgas=par_lgas, **_pointing_kw(pointing))
 
     def state_bands(self, coeffs, los, par_lgas, par_level, par_w_level, grid, centers_nm, widths_nm, par_gas=None,
-                    par_w_col=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None, instrument=False):
+                    par_w_col=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None, instrument=False,
+                    pointing=False):
         """LevelFactored.state_bands for the members' vibrational-temperature parameters together: numpy [n_rays | n_rays / 3,
-        1 + n_par, n_bands]; instrument=True: [.., 1 + n_par + 2, n_bands], the two instrument rows last."""
+        1 + n_par, n_bands]; instrument=True: [.., 1 + n_par + 2, n_bands], the two instrument rows last; pointing=True:
+        the pointing row behind the parameters'."""
         gases, par_lgas, par_level, par_c = self._args(par_lgas, par_level, par_w_level)
         return limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=par_gas, par_w=par_w_col,
                                      par_level=par_level, par_c=par_c, dcoeffs=dcoeffs, par_t=par_w_temp, out_units=out_units,
                                      n_sigma=n_sigma, fov=fov, g_lo=int(self.members[0][0]._shard[0]), level_gases=gases,
-                                     par_lgas=par_lgas, instrument=instrument)
+                                     par_lgas=par_lgas, instrument=instrument, **_pointing_kw(pointing))
 
 
 def level_node_weights(nodes, alt):
@@ -748,10 +756,13 @@ class LimbLOS(object):
 
     seg_off [n_rays+1], seg_layer [n_seg], pt_off [n_seg+1], x / nd [n_pt], vmr [n_gas, n_pt].
     Options as at the reference's call sites: LOS_order ('photon' | 'observer'), solo_absorption,
-    initial_intensity: None, a temperature (Planck source, Calc_BB) or 'rad0' (given per call)."""
+    initial_intensity: None, a temperature (Planck source, Calc_BB) or 'rad0' (given per call).
+    path (optional, limb rays of geometry.limb_los(path=True) only): dict(alt=, dx=, dalt=), [n_pt] each -- the sample
+    points' altitudes [km] and the derivatives of x [cm / km] and of the altitude to the ray's own tangent altitude; kept
+    with the geometry, it is what the calls with pointing=True and los_columns_dz need."""
 
     def __init__(self, seg_off, seg_layer, pt_off, x, nd, vmr, col_scale=None, LOS_order='photon',
-                 solo_absorption=False, initial_temperature=None):
+                 solo_absorption=False, initial_temperature=None, path=None):
         # (copies: the object is the geometry as given -- its device-resident form is built once, see handle())
         self.seg_off, self._so = _i(np.array(seg_off))
         self.seg_layer, self._sl = _i(np.array(seg_layer))
@@ -768,6 +779,11 @@ class LimbLOS(object):
             raise ValueError("LOS_order must be 'photon' or 'observer'")
         self.LOS_order, self.solo_absorption, self.initial_temperature = LOS_order, bool(solo_absorption), initial_temperature
         self._handles = {}      # insertion-ordered: least recently used first (see _keep)
+        self.path = None
+        if path is not None:
+            self.path = tuple(_d(np.array(path[k])) for k in ("alt", "dx", "dalt"))
+            if any(a.shape != (self.n_pt,) for a, _ in self.path):
+                raise ValueError("path arrays must be [n_pt]")
 
     MAX_HANDLES = 8   # resident forms kept per batch: each holds pinned and device memory until it is destroyed
 
@@ -867,12 +883,31 @@ class LimbLOS(object):
             d.init_mode, d.t_init, d.w0, d.step = 2, float(self.initial_temperature), w0, step
         return d
 
+    def path_desc(self):
+        """The sr_los_path of the batch; ValueError for a batch built without `path`."""
+        if self.path is None:
+            raise ValueError("the pointing derivative needs a LimbLOS built with path= (geometry.limb_los(path=True))")
+        p = _lib.LosPath()
+        p.alt, p.dx_dz, p.dalt_dz = (ptr for _, ptr in self.path)
+        return p
+
     def columns(self):
         """[n_gas, n_seg] Curtis-Godson columns (curgod_fort_2 per segment, on the device)."""
         out = np.zeros((self.n_gas, self.n_seg))
         d = self.desc()
         check(lib.sr_los_columns(C.byref(d), out.ctypes.data_as(dp)), "sr_los_columns")
         return out
+
+
+def los_columns_dz(los):
+    """[n_gas, n_seg] d column / d z_t of a limb batch built with path= (sr_los_columns_dz): the derivative of
+    LimbLOS.columns() to every ray's own tangent altitude [per km], the crossed shells held fixed, on the device.
+    Photon order only; a batch without path raises ValueError."""
+    p = los.path_desc()
+    out = np.zeros((los.n_gas, los.n_seg))
+    d = los.desc()
+    check(lib.sr_los_columns_dz(C.byref(d), C.byref(p), out.ctypes.data_as(dp)), "sr_los_columns_dz")
+    return out
 
 
 def gas_stack(coeffs):
@@ -1202,7 +1237,8 @@ def limb_rays_level_jacobian(coeffs, los, tab, coef_row, par_level, par_c, gas=0
 
 
 def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, coef_row=None, par_level=None, par_c=None,
-                             gas=0, grid=None, g_lo=0, want_rad=True, dcoeffs=None, par_t=None, level_gases=None, par_lgas=None):
+                             gas=0, grid=None, g_lo=0, want_rad=True, dcoeffs=None, par_t=None, level_gases=None, par_lgas=None,
+                             pointing=False):
     """(rad | None, jac [n_rays, n_col + n_lev (+ n_row), n_pts]): radiances and their derivatives with respect to a
     mixed state vector in ONE pass over each ray (sr_limb_rays_jac_state_dev): the column parameters par_gas / par_w of
     limb_rays_jacobian (VMR-profile parameters, par_w [n_col, n_pt] at the LOS sample points) first, then the level
@@ -1220,12 +1256,24 @@ def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, co
     level-factored gases in the same pass (sr_limb_rays_jac_state_gases_dev): level_gases = [(gas, tab, coef_row), ...],
     one entry per level-factored gas of the batch (its index there, its pair tables, its row map; tables may differ in
     levels and rows), and level parameter p belongs to level_gases[par_lgas[p]], to its level par_level[p].  The rows of
-    jac keep the caller's order.  Vibrational temperatures: LevelFactoredSet.state_jacobian."""
+    jac keep the caller's order.  Vibrational temperatures: LevelFactoredSet.state_jacobian.
+    pointing=True (sr_limb_rays_jac_state_path_dev; the batch needs path=, else ValueError): one more row behind the
+    state's, jac [n_rays, n_par + 1, n_pts] (a view), d rad / d z_t of every ray's own tangent altitude [per km] with the
+    crossed shells held fixed; the other rows and rad are those of the call without, bit for bit, and there may be no
+    other parameter.  Limb rays of geometry.limb_los only: 3-D paths, slant / nadir paths, adaptive stepping, observer
+    order, the resident-handle routes and refraction are not supported."""
+    if pointing:
+        path = los.path_desc()
     A = _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t, level_gases,
-                    par_lgas)
+                    par_lgas, may_be_empty=bool(pointing), as_list=bool(pointing))
     n_pts = A.a.shape[2]
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     rad = torch.empty((los.n_rays, n_pts), dtype=torch.float64, device="cuda") if want_rad else None
+    if pointing:
+        jac = torch.empty((los.n_rays, A.n_par + los.n_gas, n_pts), dtype=torch.float64, device="cuda")
+        name = "sr_limb_rays_jac_state_path_dev"
+        check(getattr(lib, name)(*A.args(name, C.byref(path), ptr(rad), ptr(jac), _stream_ptr())), name)
+        return rad, jac[:, :A.n_par + 1]
     jac = torch.empty((los.n_rays, A.n_par, n_pts), dtype=torch.float64, device="cuda")
     name = _state_entry(False, False, level_gases is not None, par_t is not None)
     check(getattr(lib, name)(*A.args(name, ptr(rad), ptr(jac), _stream_ptr())), name)
@@ -1299,10 +1347,11 @@ def _level_gases_args(level_gases, par_lgas, tab, coef_row, par_level, par_c, n_
 
 
 def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t, level_gases=None,
-                par_lgas=None, may_be_empty=False):
+                par_lgas=None, may_be_empty=False, as_list=False):
     """The arguments of a mixed-state call (limb_rays_state_jacobian, limb_rays_state_bands), checked and marshalled: the
     one place where their shapes are refused.  may_be_empty: a call that returns something without any parameter (the
-    bands call with its instrument rows)."""
+    bands call with its instrument rows, the calls with the pointing row).  as_list: the one level gas of tab / coef_row
+    / gas as a list of one (the entries with the pointing row take the list form only)."""
     if (dcoeffs is None) != (par_t is None):
         raise ValueError("row parameters need both dcoeffs and par_t")
     a, e = _gas_stack(coeffs)
@@ -1349,13 +1398,19 @@ def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, ga
         arr, n_lgas, _, plg, pl, pc, keep = several
         A.keep = A.keep + (arr, keep)
         levels = (n_lgas, arr, n_lev, plg, pl, pc)
+    elif as_list:
+        arr = (_lib.LevelGasDesc * 1)()
+        arr[0].gas, arr[0].n_levels, arr[0].n_tab_rows = int(gas), n_levels, n_tab_rows
+        arr[0].tab, arr[0].coef_row = (tab.data_ptr() if n_lev else None), cr
+        A.keep = A.keep + (arr,)
+        levels = (1, arr, n_lev, None, pl, pc)
     A._blocks = ((ptr(a), ptr(e), n_layers, n_pts, C.byref(d), n_col, pg, pw), levels, (ptr(da), ptr(de), n_row, pt))
     return A
 
 
 def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None, par_w=None, tab=None, coef_row=None,
                           par_level=None, par_c=None, gas=0, dcoeffs=None, par_t=None, out_units="Wm2", n_sigma=5.0, fov=None,
-                          g_lo=0, level_gases=None, par_lgas=None, instrument=False):
+                          g_lo=0, level_gases=None, par_lgas=None, instrument=False, pointing=False):
     """limb_rays_state_jacobian on the instrument's bands in ONE library call (sr_limb_rays_state_bands_dev): the same
     mixed state vector (column, level, row parameters: the same arguments, the same errors), but no hi-res spectrum is
     written -- the recursion kernel integrates the bands in its epilogue.  Returns numpy [n_rays | n_rays / 3, 1 + n_par,
@@ -1368,10 +1423,15 @@ def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None
     instrument=True (sr_limb_rays_state_bands_instr[_gases]_dev): two more rows behind the parameters', [.., 1 + n_par + 2,
     n_bands]: the derivatives of the radiance's bands to the band centre (per nm) and to the logarithm of the ILS width, as
     hires_to_lowres_instrument defines them (window membership held fixed); rows 0 .. n_par are those of the call without
-    them, bit for bit, and there may then be no parameter at all."""
-    instrument = bool(instrument)
+    them, bit for bit, and there may then be no parameter at all.
+    pointing=True (sr_limb_rays_state_bands_path_dev; the batch needs path=, else ValueError): the pointing row of
+    limb_rays_state_jacobian behind the parameters' and in front of the instrument rows, [.., 1 + n_par + 1 (+ 2),
+    n_bands]; the other rows are those of the call without, bit for bit."""
+    instrument, pointing = bool(instrument), bool(pointing)
+    if pointing:
+        path = los.path_desc()
     A = _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t, level_gases,
-                    par_lgas, may_be_empty=instrument)
+                    par_lgas, may_be_empty=instrument or pointing, as_list=pointing)
     n_pts = A.a.shape[2]
     w0, step, n = grid_params(grid)
     A.desc.w0, A.desc.step = w0, step   # (the grid of the bands; with a Planck background desc() has set the same)
@@ -1387,7 +1447,12 @@ def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None
         if los.n_rays % 3 or fov.shape != (los.n_rays // 3, 7):
             raise ValueError("fov must be [n_rays / 3, 7] (three rays per pixel)")
         n_out = los.n_rays // 3
-    out = np.empty((n_out, 1 + A.n_par + (2 if instrument else 0), centers_nm.size))
+    out = np.empty((n_out, 1 + A.n_par + (1 if pointing else 0) + (2 if instrument else 0), centers_nm.size))
+    if pointing:
+        name = "sr_limb_rays_state_bands_path_dev"
+        check(getattr(lib, name)(*A.args(name, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp,
+                                         out.ctypes.data_as(dp), _stream_ptr(), int(instrument), C.byref(path))), name)
+        return out
     name = _state_entry(True, instrument, level_gases is not None, par_t is not None)
     check(getattr(lib, name)(*A.args(name, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp, out.ctypes.data_as(dp),
                                      _stream_ptr())), name)

@@ -70,13 +70,54 @@ def _sample(a, b, n_sub):
 
 
 _LOS_GEOMETRY = {}   # (levels, tangent heights, R, n_sub) -> segment / sample-point geometry of limb_los
+_LOS_PATH = {}       # the same key -> (dx_dzt, dalt_dzt) of limb_los(path=True)
 
 
-def limb_los(z, nd_levels, vmr_levels, z_tans, R=TITAN_RADIUS_KM, n_sub=3):
+def _limb_path_derivatives(zz, zt, R, n_sub):
+    """(d s_i / d z_t [km / km], d alt_i / d z_t) at the sample points of one limb ray, [n_seg, n_sub + 1] each, the
+    crossed shells held fixed.  A shell end at radius hi > r_t lies at s = sqrt(hi^2 - r_t^2) with d s / d z_t = -r_t / s
+    (the tangent point: s = 0, derivative 0; far side mirrored), sample point i blends the ends a, b with f = i / n_sub,
+    and d alt_i / d z_t = (s_i d s_i + r_t) / (alt_i + R).  With a da = b db = -r_t the numerator is
+        -r_t f (1 - f) (b - a)^2 / (a b)            in a shell above the tangent shell,
+        r_t (1 - f^2)  /  r_t (1 - (1 - f)^2)       in the tangent shell (near / far side),
+    forms without cancellation: exactly 0 on a shell boundary, 1 at the tangent point.  The ends' distances come from
+    (hi - r_t)(hi + r_t) with hi - r_t = zz - z_t, which keeps its digits where a level lies just above the ray."""
+    rt = R + zt
+    k = np.nonzero(R + zz[1:] > rt)[0]
+    hi, lo = zz[1:][k], zz[:-1][k]
+    s_hi = np.sqrt((hi - zt) * ((R + hi) + rt))
+    above = (R + lo) > rt
+    s_lo = np.where(above, np.sqrt(np.where(above, (lo - zt) * ((R + lo) + rt), 0.0)), 0.0)
+    with np.errstate(divide="ignore"):
+        d_hi, d_lo = -rt / s_hi, np.where(above, -rt / np.where(above, s_lo, 1.0), 0.0)
+    # photon order: far side (a = -s_hi, b = -s_lo, outermost shell first), then near side (a = s_lo, b = s_hi)
+    a = np.concatenate([-s_hi[::-1], s_lo])[:, None]
+    b = np.concatenate([-s_lo[::-1], s_hi])[:, None]
+    da = np.concatenate([-d_hi[::-1], d_lo])[:, None]
+    db = np.concatenate([-d_lo[::-1], d_hi])[:, None]
+    i = np.arange(n_sub + 1)[None, :]
+    f, g = i / n_sub, (n_sub - i) / n_sub                       # f and 1 - f
+    s = a * g + b * f
+    ds = da * g + db * f
+    tangent = np.concatenate([~above[::-1], ~above])[:, None]
+    far = (np.arange(2 * len(k)) < len(k))[:, None]
+    # b - a of a shell above the tangent shell from b^2 - a^2 = (hi - lo)(hi + lo): the difference of two long paths
+    span = (hi - lo) * ((R + hi) + (R + lo)) / (s_hi + s_lo)
+    span = np.concatenate([span[::-1], span])[:, None]
+    num_above = -rt * f * g * span * span / np.where(tangent, 1.0, a * b)
+    num = np.where(tangent, np.where(far, rt * f * (1.0 + g), rt * g * (1.0 + f)), num_above)
+    return ds, num / np.sqrt(s * s + rt * rt)
+
+
+def limb_los(z, nd_levels, vmr_levels, z_tans, R=TITAN_RADIUS_KM, n_sub=3, path=False):
     """Lines of sight of limb rays through spherical shells (fixed stepping: one step per shell crossing): per ray the
     crossings in photon order, per crossing n_sub + 1 sample points with the number density interpolated exponentially
     and every VMR linearly in altitude between the levels z.  vmr_levels: [n_gas, n_levels].  Returns the LimbLOS
-    arguments dict(seg_off, seg_layer, pt_off, x [cm], nd, vmr [n_gas, n_pt]) plus `alt` [n_pt] (km)."""
+    arguments dict(seg_off, seg_layer, pt_off, x [cm], nd, vmr [n_gas, n_pt]) plus `alt` [n_pt] (km).
+    path=True: also `dx_dzt` [n_pt] (cm per km) and `dalt_dzt` [n_pt], the derivatives of x and alt to the ray's own
+    tangent altitude with the set of crossed shells held fixed (one-sided where z_t lies on a level: the tangent shell
+    is the one above) -- LimbLOS(path=dict(alt=, dx=, dalt=)), the pointing derivative.  No refraction; the other
+    builders of this module (3-D, slant / nadir, adaptive stepping) have no such derivative."""
     z, zz, ln, vv = _profiles(z, nd_levels, vmr_levels)
     z_tans = np.atleast_1d(np.asarray(z_tans, float))
     # the geometry depends on the levels and the tangent heights only: a retrieval loop asks for the same rays with
@@ -102,7 +143,17 @@ def limb_los(z, nd_levels, vmr_levels, z_tans, R=TITAN_RADIUS_KM, n_sub=3):
     seg_off, seg_layer, pt_off, x_cm, alts = geo
     nd = np.exp(np.interp(alts, zz, ln))
     vmr = np.array([np.interp(alts, zz, v) for v in vv])
-    return dict(seg_off=seg_off, seg_layer=seg_layer, pt_off=pt_off, x=x_cm, nd=nd, vmr=vmr, alt=alts)
+    out = dict(seg_off=seg_off, seg_layer=seg_layer, pt_off=pt_off, x=x_cm, nd=nd, vmr=vmr, alt=alts)
+    if path:
+        der = _LOS_PATH.get(key)
+        if der is None:
+            per_ray = [_limb_path_derivatives(zz, zt, float(R), int(n_sub)) for zt in z_tans]
+            der = (np.concatenate([d[0].ravel() for d in per_ray]) * 1e5, np.concatenate([d[1].ravel() for d in per_ray]))
+            if len(_LOS_PATH) >= 8:
+                _LOS_PATH.pop(next(iter(_LOS_PATH)))
+            _LOS_PATH[key] = der
+        out["dx_dzt"], out["dalt_dzt"] = der
+    return out
 
 
 def sun_in_local_frame(tangent_lat_deg, subsolar_lat_deg, sza_tangent_deg):

@@ -184,9 +184,40 @@ class BandCalibration(smm.RetSet):
         return np.stack([np.asarray(rows[p.key], float) for p in self.set], axis=-2)
 
 
+POINTING_SET = "pointing"    # the name of the retrieval set of the pointing offset (Pointing)
+
+
+class Pointing(smm.RetSet):
+    """The retrieval set of the pointing, named "pointing": one scalar `offset` [km] common to all pixels, added to every
+    line of sight's tangent altitude (LimbPixel.los_alts() + offset).  Given as (apriori, apriori_err) or (apriori,
+    apriori_err, first_guess); not constrained positive.  Its Jacobian column is the pointing row of the mixed-state calls
+    (engine.limb_rays_state_jacobian / limb_rays_state_bands with pointing=True): d / d z_t of every ray's own tangent
+    altitude with the crossed shells held fixed, through the field of view like any other row.  Limb rays of
+    geometry.limb_los in a 1-D scene only: 3-D paths, slant / nadir paths, adaptive stepping, observer order, the
+    resident-handle routes and refraction have no such row; per-pixel offsets are not part of this set.  Retrieved by
+    inversion_state; the other drivers refuse the set."""
+
+    def __init__(self, offset):
+        spec = tuple(float(v) for v in offset)
+        if len(spec) not in (2, 3):
+            raise ValueError("offset must be (apriori, apriori_err) or (apriori, apriori_err, first_guess)")
+        mask = smm.GridMask([0.0], [1.0], 'box')    # (a scalar: nothing to mask)
+        self.name = POINTING_SET
+        self.set = [smm.RetParam(POINTING_SET, "offset", mask, spec[0], spec[1], first_guess=spec[2] if len(spec) == 3 else None,
+                                 constrain_positive=False)]
+        self.n_par = 1
+
+    def offset(self):
+        """The current offset [km]."""
+        return float(self.set[0].value)
+
+
 def _refuse_instr(bayes_set, who):
-    if bayes_set is not None and INSTR_SET in getattr(bayes_set, "sets", {}):
+    sets = getattr(bayes_set, "sets", {}) if bayes_set is not None else {}
+    if INSTR_SET in sets:
         raise ValueError("%s does not take the retrieval set %r (BandCalibration): use inversion_state" % (who, INSTR_SET))
+    if POINTING_SET in sets:
+        raise ValueError("%s does not take the retrieval set %r (Pointing): use inversion_state" % (who, POINTING_SET))
 
 
 class StateWeights(object):
@@ -260,17 +291,19 @@ class LimbScene(object):
             self._stack_of = co          # keeps the ids alive
         return self._stack
 
-    def los(self, tangent_alts, update=True, **opts):
+    def los(self, tangent_alts, update=True, path=False, **opts):
         """engine.LimbLOS of rays with the given tangent altitudes (photon order) + the sample altitudes.  The geometry
         (paths, sample points, densities) depends on the altitudes alone and is kept; between the iterations of a
-        retrieval only the VMRs at the sample points change."""
+        retrieval only the VMRs at the sample points change.  path=True: the batch carries the path derivatives to the
+        rays' tangent altitudes (geometry.limb_los(path=True)), which the calls with pointing=True need."""
         # (the key holds everything the geometry is made from: altitudes of the rays, the level grid, the densities, the
         # sub-stepping and the radius -- by content; ADVICE round 5)
         key = (tuple(float(a) for a in tangent_alts), np.asarray(self.z, float).tobytes(), np.asarray(self.nd, float).tobytes(),
-               int(self.n_sub), float(self.R))
+               int(self.n_sub), float(self.R)) + ((True,) if path else ())
         geo = getattr(self, "_los_geo", None)
         if geo is None or geo[0] != key:
-            L = syn.limb_los(self.z, self.nd, [g.vmr for g in self.gases], tangent_alts, R=self.R, n_sub=self.n_sub)
+            L = syn.limb_los(self.z, self.nd, [g.vmr for g in self.gases], tangent_alts, R=self.R, n_sub=self.n_sub,
+                             **(dict(path=True) if path else {}))
             top = self.z[-1] + (self.z[-1] - self.z[-2])
             geo = self._los_geo = (key, L, np.append(self.z, top))
         _, L, zz = geo
@@ -286,7 +319,8 @@ class LimbScene(object):
             kept[1].set_vmr(vmr)
             return kept[1], L["alt"]
         los = engine.LimbLOS(L["seg_off"], L["seg_layer"], L["pt_off"], L["x"], L["nd"], vmr,
-                             col_scale=[g.iso_ratio for g in self.gases], **opts)
+                             col_scale=[g.iso_ratio for g in self.gases],
+                             path=dict(alt=L["alt"], dx=L["dx_dzt"], dalt=L["dalt_dzt"]) if path else None, **opts)
         if not opts:
             self._los_obj = (key, los)
         return los, L["alt"]
@@ -323,8 +357,8 @@ class LimbScene(object):
         several_level_gases=True: Tvib sets of any number of LevelGas (the calls with level_gases take them in one pass);
         the level block then holds them all in BayesSet order, StateWeights.level_gases / gases / par_lgas say whose each
         is, level_gas / gas are the first one's.  With one LevelGas the result is the same either way.
-        The set named "instr" (BandCalibration) is accepted and has no part in any block: perm then covers the other sets'
-        parameters alone, in BayesSet order."""
+        The sets named "instr" (BandCalibration) and "pointing" (Pointing) are accepted and have no part in any block: perm
+        then covers the other sets' parameters alone, in BayesSet order."""
         names = [g.name for g in self.gases]
         top = self.z[-1] + (self.z[-1] - self.z[-2])
         zz = np.append(self.z, top)
@@ -332,7 +366,7 @@ class LimbScene(object):
         level_gas, level_gases, par_lgas = None, [], []
         for name in bayes_set.order:
             st = bayes_set.sets[name]
-            if name == INSTR_SET and name not in names:
+            if name in (INSTR_SET, POINTING_SET) and name not in names:
                 continue
             if name in names:
                 for par in st.set:
@@ -829,6 +863,23 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
     return chi, obs, (finish(low, dlow) if fast else sims), bayes_set
 
 
+def _rows_in_bayes_order(fov_rows, n_prof, is_point, is_instr, instr, bands_nm0):
+    """[n_pix, 1 + n_prof (+ 1) (+ 2), n_bands] -- the radiance, the profile parameters in BayesSet order, the pointing
+    row if any BayesSet parameter is the pointing's, d / d centre and d / d ln width if any is the instrument's -> [n_pix,
+    1 + n_tot, n_bands] with every set's columns where the set stands (is_point, is_instr [n_tot]: whose each parameter
+    is); the "instr" set's by the chain rule (BandCalibration.jacobian_rows)."""
+    out = np.empty((fov_rows.shape[0], 1 + is_instr.size, fov_rows.shape[2]))
+    out[:, 0] = fov_rows[:, 0]
+    out[:, 1:][:, ~(is_instr | is_point)] = fov_rows[:, 1:1 + n_prof]
+    at = 1 + n_prof
+    if is_point.any():
+        out[:, 1:][:, is_point] = fov_rows[:, at:at + 1]
+        at += 1
+    if is_instr.any():
+        out[:, 1:][:, is_instr] = instr.jacobian_rows(bands_nm0, fov_rows[:, at], fov_rows[:, at + 1])
+    return out
+
+
 def _state_into_gases(scene, bayes_set):
     """The BayesSet's profiles into the gases: add_clim for the VMR sets, tvib = tvib0 + offset for the Tvib sets; the
     "temp" set into the scene, temps = temps0 + offset (temps0: the temperatures at the first such call; the number
@@ -842,6 +893,8 @@ def _state_into_gases(scene, bayes_set):
             continue
         if name == INSTR_SET:
             scene.bands_nm, scene.widths_nm = st.bands(scene.bands_nm0, scene.widths_nm0)
+            continue
+        if name == POINTING_SET:      # (the driver adds the offset to its lines of sight)
             continue
         if name == "temp":
             if getattr(scene, "temps0", None) is None:
@@ -876,7 +929,12 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     per iteration its values go into scene.bands_nm / widths_nm, the two instrument rows of the band integrals come from
     the same fused call (instrument=True) or, on the other route, from engine.hires_to_lowres_instrument on the radiance
     the Jacobian call wrote, and the set's Jacobian columns follow by the chain rule (BandCalibration.jacobian_rows); they
-    stand where the set stands in the BayesSet.  Without such a set nothing changes."""
+    stand where the set stands in the BayesSet.  Without such a set nothing changes.
+    A set named "pointing" (Pointing: one tangent-altitude offset [km] common to all pixels) is retrieved with them: per
+    iteration the lines of sight are the pixels' los_alts() plus the current offset, the calls are made with pointing=True
+    on both routes and the pointing row (through the field of view like the others) is the set's Jacobian column, where
+    the set stands in the BayesSet; it can stand beside an "instr" set.  The crossed shells are held fixed within an
+    iteration and rebuilt between iterations.  Without such a set nothing changes."""
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)
     with_fov = sum(pix.fov_half > 0 for pix in pixels)
     if not (with_fov == 0 or (with_fov == len(pixels) and fov_closed_form)):
@@ -897,15 +955,17 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     bayes_set.history, bayes_set.stop = [], 'max_it'
     instr = bayes_set.sets.get(INSTR_SET) if INSTR_SET not in [g.name for g in scene.gases] else None
     is_instr = np.array([instr is not None and par.nameset == INSTR_SET for par in bayes_set.params()], dtype=bool)
+    point = bayes_set.sets.get(POINTING_SET) if POINTING_SET not in [g.name for g in scene.gases] else None
+    is_point = np.array([point is not None and par.nameset == POINTING_SET for par in bayes_set.params()], dtype=bool)
+    point_kw = {} if point is None else dict(pointing=True)
+    los_kw = {} if point is None else dict(path=True)
+    alts0 = list(alts)
 
     def with_instr(fov_rows, n_prof):
-        """[n_pix, 1 + n_prof + 2, n_bands] (radiance, profile parameters in BayesSet order, d / d centre, d / d ln width)
-        -> [n_pix, 1 + n_tot, n_bands] in BayesSet order, the set's columns by the chain rule."""
-        out = np.empty((fov_rows.shape[0], 1 + is_instr.size, fov_rows.shape[2]))
-        out[:, 0] = fov_rows[:, 0]
-        out[:, 1:][:, ~is_instr] = fov_rows[:, 1:1 + n_prof]
-        out[:, 1:][:, is_instr] = instr.jacobian_rows(scene.bands_nm0, fov_rows[:, 1 + n_prof], fov_rows[:, 2 + n_prof])
-        return out
+        """[n_pix, 1 + n_prof (+ 1) (+ 2), n_bands] (radiance, profile parameters in BayesSet order, the pointing row,
+        d / d centre, d / d ln width) -> [n_pix, 1 + n_tot, n_bands] in BayesSet order, the "instr" set's columns by the
+        chain rule."""
+        return _rows_in_bayes_order(fov_rows, n_prof, is_point, is_instr, instr, scene.bands_nm0)
 
     def wrap(v):
         sp = Spectrum.__new__(Spectrum)
@@ -918,7 +978,7 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     def finish(low, dlow):
         if low is None:                                            # (max_it = 0: nothing was simulated)
             return []
-        scene.los(alts)                                            # the batch's VMRs = the final profiles
+        scene.los(alts, **los_kw)                                  # the batch's VMRs = the final profiles
         jac = np.transpose(dlow, (1, 0, 2)).reshape(dlow.shape[1], -1)     # build_jacobian's rows, of the last iteration
         bayes_set.jacobian = (jac if masktot is None else jac[:, masktot]).T
         for num in range(len(pixels)):
@@ -930,7 +990,9 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     n_los = len(alts)
     for num_it in range(max_it):
         coeffs = None if with_temp else scene.coefficient_stack()
-        los, alt = scene.los(alts)
+        if point is not None:
+            alts = [a + point.offset() for a in alts0]                 # the rays this iteration simulates
+        los, alt = scene.los(alts, **los_kw)
         if instr is not None:
             grid_sim[0] = _Grid(scene.bands_nm.copy())                 # the centres this iteration simulates on
         w = scene.state_weights(bayes_set, alt, several_level_gases=True)
@@ -947,6 +1009,7 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             band_args = dict(out_units=scene.out_units, fov=engine.fov_factors(rots) if with_fov else None)
             if instr is not None:
                 band_args["instrument"] = True
+            band_args.update(point_kw)
             if lfs is not None:
                 both = lfs.state_bands(coeffs, los, w.par_lgas, w.par_level, w.par_w_lev, scene.grid, scene.bands_nm,
                                        scene.widths_nm, par_gas=w.par_gas, par_w_col=w.par_w_col, dcoeffs=dcoeffs,
@@ -958,35 +1021,38 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
                 both = lg.lf.state_bands(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, scene.grid, scene.bands_nm,
                                          scene.widths_nm, par_gas=w.par_gas, par_w_col=w.par_w_col, gas=w.gas, dcoeffs=dcoeffs,
                                          par_w_temp=par_w_temp, **band_args)
-            n_par = both.shape[1] - 1 - (0 if instr is None else 2)
+            n_par = both.shape[1] - 1 - (0 if instr is None else 2) - (0 if point is None else 1)
             fov = both if with_fov else both[1::3]
             fov = np.concatenate([fov[:, :1, :], fov[:, 1:1 + n_par, :][:, w.perm], fov[:, 1 + n_par:, :]], axis=1)
         else:                  # (one level gas or none: the calls as they always were -- without a temperature set no call names row parameters)
-            if instr is not None and len(w.perm) == 0:    # the instrument set alone: the radiances, no Jacobian call
+            if instr is not None and point is None and len(w.perm) == 0:    # the instrument set alone: the radiances, no Jacobian call
                 rad, jac = engine.limb_rays(coeffs, los, resident=False), None
             elif lfs is not None:
                 rad, jac = lfs.state_jacobian(coeffs, los, w.par_lgas, w.par_level, w.par_w_lev, par_gas=w.par_gas,
-                                              par_w_col=w.par_w_col, dcoeffs=dcoeffs, par_w_temp=par_w_temp)
+                                              par_w_col=w.par_w_col, dcoeffs=dcoeffs, par_w_temp=par_w_temp, **point_kw)
             elif with_temp and lg is None:
                 rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col, dcoeffs=dcoeffs,
-                                                           par_t=w.par_w_temp)
+                                                           par_t=w.par_w_temp, **point_kw)
             elif with_temp:
                 rad, jac = lg.lf.state_jacobian(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, par_gas=w.par_gas,
-                                                par_w_col=w.par_w_col, gas=w.gas, dcoeffs=dcoeffs, par_w_temp=w.par_w_temp)
+                                                par_w_col=w.par_w_col, gas=w.gas, dcoeffs=dcoeffs, par_w_temp=w.par_w_temp,
+                                                **point_kw)
             elif lg is None:
-                rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col)
+                rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col, **point_kw)
             else:
                 rad, jac = lg.lf.state_jacobian(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, par_gas=w.par_gas,
-                                                par_w_col=w.par_w_col, gas=w.gas)
-            n_par = 0 if jac is None else jac.shape[1]
-            rows = [] if jac is None else [lowres(jac.view(n_los * n_par, -1)).reshape(n_los, n_par, -1)[:, w.perm]]
+                                                par_w_col=w.par_w_col, gas=w.gas, **point_kw)
+            n_rows = 0 if jac is None else jac.shape[1]
+            n_par = n_rows - (0 if point is None else 1)               # (the pointing row stands behind the state's)
+            order = np.concatenate([w.perm, np.arange(n_par, n_rows)]).astype(int)
+            rows = [] if jac is None else [lowres(jac.contiguous().view(n_los * n_rows, -1)).reshape(n_los, n_rows, -1)[:, order]]
             if instr is None:
                 both = np.concatenate([lowres(rad)[:, None, :]] + rows, axis=1)
             else:      # the instrument step once more on the radiance, with its two derivative rows (row 0: lowres(rad))
                 three = engine.hires_to_lowres_instrument(rad, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units)
                 both = np.concatenate([three[0][:, None, :]] + rows + [three[1][:, None, :], three[2][:, None, :]], axis=1)
             fov = smm.fov_closed_form(both[0::3], both[1::3], both[2::3], rots) if with_fov else both[1::3]
-        if instr is not None:
+        if instr is not None or point is not None:
             fov = with_instr(fov, n_par)
             n_par = is_instr.size
         low, dlow = fov[:, 0, :], fov[:, 1:, :]
