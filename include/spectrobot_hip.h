@@ -176,6 +176,49 @@ int sr_lineset_set_bounds_temps(sr_lineset *ls, const double *temps_bounds, int 
  * 0.002 to 0.05 K and the reference's single-precision staircase (1e-7 |c| / dT) shrinks with it.  0: exact weights. */
 int sr_lineset_set_linear_weights(sr_lineset *ls, int on);
 
+/* Pressure shift of the line centres and self-broadening (what spect_classes.py:161-206 and 1967-1972 intend: the
+ * reference computes wn_0 = Freq + P_shift Pres_atm at :187 and then hands Freq to MakeShape at :197, and no caller
+ * passes Self_broad / Self_pres_atm to Lorenz_width).  Opt-in per line set; a line set that was never given the data,
+ * or was given it and had it taken back, computes exactly what it did before, bit for bit.
+ *
+ * For line i in layer k, with P_atm = convert_to_atm(P_k) and Ps_atm = convert_to_atm(p_self_k):
+ *   shape centre    x0' = Freq_i + p_shift_i P_atm
+ *   Lorentz width   lw  = (296 / T)^n_i (gamma_air,i (P_atm - Ps_atm) + gamma_self,i Ps_atm)
+ * x0' replaces Freq_i wherever the centre POSITIONS the shape (the running x of every region, the region boundaries,
+ * the outer branches' x).  Still taken at Freq_i: the Doppler width, the normalisation fac, the G coefficients and the
+ * strengths, the window (ic = closest_grid(Freq_i), grid indices ic - 6505 .. ic + 6504), the sort order and the
+ * candidate selection of tiles and shards.  Frozen boundaries (sr_lineset_set_bounds_temps) place their indices with
+ * the same x0' and with lw at the boundary temperature.
+ *
+ * sr_lineset_set_line_shape: p_shift[n_lines] (cm^-1 / atm) and self_broad[n_lines] (cm^-1 / atm), in the order the
+ * lines were given to sr_lineset_create (n_lines = that call's, else SR_ERR_ARG).  HOST, copied.  Either may be NULL
+ * (that quantity keeps its default: no shift / air broadening only); both NULL restores the default.  SR_ERR_ARG for a
+ * non-finite value, self_broad < 0, or the handle of a per-level sub-lineset.  The per-level sub-linesets cut earlier
+ * are dropped and rebuilt on their next use.
+ *
+ * sr_lineset_set_self_pressure: the partial pressure of the gas itself, p_self_hpa[n_layers] (hPa; HOST, copied), for
+ * the following coefficient calls with that many layers; a call with another layer count, or with a p_self outside
+ * [0, P] of its layer, is refused with SR_ERR_ARG.  NULL or n_layers == 0 restores p_self = 0.  Without self_broad it
+ * has no effect.  SR_ERR_ARG for a negative or non-finite value.
+ *
+ * Limits, checked per call before anything is copied or launched (outputs stay untouched):
+ *   SR_ERR_LIMIT        max_i |p_shift_i| P_atm,k > SR_MAX_SHIFT_POINTS grid steps in some layer.  A main line's centre
+ *                       lies within half a step of its window centre ic; shifted it stays within 1024.5 points of it,
+ *                       of the window's 6505 to either side.  What the limit keeps: the window-end expansions (degree
+ *                       5 over 64 points) see the centre >= 5417 points away, ratio 32 / 5417 (6441 unshifted: 2.8
+ *                       times the truncation, of a term that is itself ~1e-8 of the line's peak), and the short series of
+ *                       the far field's window bands (8 terms beyond 4096 points of ic) a ratio <= 32 / 3072, 1.4e-16.
+ *                       HITRAN's largest shifts (~0.1 cm^-1 / atm) at 1.5 atm and a step of 5e-4 cm^-1 are 300 points.
+ *   SR_ERR_UNSUPPORTED  a line changes humliv_bb's branch in some layer: an outer line (centre outside its own window,
+ *                       sequential branches lineshape.f:272-442) whose shifted centre lies strictly inside its window,
+ *                       or a main line centred beyond a grid end whose shifted centre leaves it.
+ *
+ * The VMR Jacobians of the limb calls hold the coefficients fixed: the dependence of lw on the gas's own VMR through
+ * p_self is not differentiated; a retrieval refreshes p_self between its iterations. */
+#define SR_MAX_SHIFT_POINTS 1024
+int sr_lineset_set_line_shape(sr_lineset *ls, const double *p_shift, const double *self_broad, int64_t n_lines);
+int sr_lineset_set_self_pressure(sr_lineset *ls, const double *p_self_hpa, int n_layers);
+
 /* Layer stack (the Temps / Press lists of make_abscoeff_isomolec,
  * spect_main_module.py:1880, plus level.local_vibtemp, :2065). Host pointers.
  * tvib: [n_levels][n_layers] or NULL for LTE (:2062-2063).  q_part: [n_layers]

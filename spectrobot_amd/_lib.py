@@ -211,6 +211,8 @@ SYMBOLS = {
     "sr_set_timing": (C.c_int, [C.c_int]),
     "sr_lineset_set_bounds_temps": (C.c_int, [C.c_void_p, dp, C.c_int]),
     "sr_lineset_set_linear_weights": (C.c_int, [C.c_void_p, C.c_int]),
+    "sr_lineset_set_line_shape": (C.c_int, [C.c_void_p, dp, dp, C.c_int64]),
+    "sr_lineset_set_self_pressure": (C.c_int, [C.c_void_p, dp, C.c_int]),
     "sr_last_eval_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 

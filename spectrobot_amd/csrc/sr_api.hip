@@ -309,6 +309,7 @@ struct HostLines {
   int64_t m = 0;   // lines
   std::vector<double> d;
   std::vector<int> i;
+  std::vector<double> p_shift, self_broad; // sr_lineset_set_line_shape: [md] each, or empty (unset)
 };
 
 // Process-wide mode switches (sr_set_*).  Atomic: a call reads each ONCE at entry and works with that
@@ -489,7 +490,9 @@ struct sr_lineset {
   std::vector<double> e_lev;
   std::vector<int> ic; // host copy, sorted
   double freq_max = 0.0;
-  double gamma_max = 0.0, ndep_min = 0.0, ndep_max = 0.0; // air broadening / its temperature exponent over the lines
+  double gamma_max = 0.0, ndep_min = 0.0, ndep_max = 0.0; // air (and self) broadening / its temperature exponent over the lines
+  double shift_max = 0.0;           // sr_lineset_set_line_shape: largest |p_shift| over the lines, cm^-1 / atm (0: unset)
+  std::vector<double> self_press;   // sr_lineset_set_self_pressure: hPa per layer of the next calls; empty = 0
   int64_t n_disp_lo = 0, n_disp_hi = 0; // leading / trailing lines centred beyond the grid ends (window clamped to the end point)
   DevBuf d_lines;      // one allocation, carved below
   LinesDev L{};
@@ -658,11 +661,22 @@ namespace {
 
 int upload_soa(const HostLines &H, DevBuf &buf, LinesDev &L) {
   const size_t bytes_d = H.d.size() * sizeof(double), bytes_i = H.i.size() * sizeof(int);
-  int rc = buf.ensure(bytes_d + bytes_i);
+  // the line-shape arrays, when set, behind the int arrays (at a multiple of 8 bytes)
+  const size_t off_x = bytes_d + (bytes_i + 7) / 8 * 8, bytes_x = H.md * sizeof(double);
+  int rc = buf.ensure(off_x + 2 * bytes_x);
   if (rc) return rc;
   char *base = buf.as<char>();
   HIPCHK(hipMemcpy(base, H.d.data(), bytes_d, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(base + bytes_d, H.i.data(), bytes_i, hipMemcpyHostToDevice));
+  L.p_shift = L.self_broad = nullptr;
+  if (!H.p_shift.empty()) {
+    HIPCHK(hipMemcpy(base + off_x, H.p_shift.data(), bytes_x, hipMemcpyHostToDevice));
+    L.p_shift = reinterpret_cast<const double *>(base + off_x);
+  }
+  if (!H.self_broad.empty()) {
+    HIPCHK(hipMemcpy(base + off_x + bytes_x, H.self_broad.data(), bytes_x, hipMemcpyHostToDevice));
+    L.self_broad = reinterpret_cast<const double *>(base + off_x + bytes_x);
+  }
   const double *dd = reinterpret_cast<const double *>(base);
   const int *di = reinterpret_cast<const int *>(base + bytes_d);
   const size_t md = H.md;
@@ -685,6 +699,14 @@ HostLines subset(const HostLines &H, const std::vector<int64_t> &sel) {
     for (int a = 0; a < 12; ++a) S.d[a * S.md + q] = H.d[a * H.md + sel[q]];
     for (int a = 0; a < 3; ++a) S.i[a * S.md + q] = H.i[a * H.md + sel[q]];
   }
+  if (!H.p_shift.empty()) {
+    S.p_shift.assign(S.md, 0.0);
+    for (int64_t q = 0; q < S.m; ++q) S.p_shift[q] = H.p_shift[sel[q]];
+  }
+  if (!H.self_broad.empty()) {
+    S.self_broad.assign(S.md, 0.0);
+    for (int64_t q = 0; q < S.m; ++q) S.self_broad[q] = H.self_broad[sel[q]];
+  }
   return S;
 }
 
@@ -705,6 +727,13 @@ static int lineset_upload(sr_lineset *ls) {
     ls->ndep_min = std::min(ls->ndep_min, H.d[9 * H.md + q]);
     ls->ndep_max = std::max(ls->ndep_max, H.d[9 * H.md + q]);
   }
+  // sr_lineset_set_line_shape: lw <= (296/T)^n max(gamma_air, gamma_self) P for 0 <= Ps <= P; the largest |shift| over
+  // main and outer lines
+  if (!H.self_broad.empty())
+    for (int64_t q = 0; q < H.m; ++q) ls->gamma_max = std::max(ls->gamma_max, H.self_broad[q]);
+  ls->shift_max = 0.0;
+  for (const HostLines *S : {&H, static_cast<const HostLines *>(&ls->host_outer)})
+    for (int64_t q = 0; q < S->m && !S->p_shift.empty(); ++q) ls->shift_max = std::max(ls->shift_max, std::fabs(S->p_shift[q]));
   ls->n_disp_lo = ls->n_disp_hi = 0;
   if (H.m > 0) {
     const double g0 = grid_at(ls->gp, 0), g1 = grid_at(ls->gp, (int)ls->gp.n_grid - 1), tol = 0.75 * ls->gp.gstep;
@@ -900,6 +929,49 @@ int sr_lineset_set_linear_weights(sr_lineset *ls, int on) {
   return SR_OK;
 }
 
+int sr_lineset_set_line_shape(sr_lineset *ls, const double *p_shift, const double *self_broad, int64_t n_lines) {
+  if (!ls || ls->parent) return SR_ERR_ARG;
+  if ((p_shift || self_broad) && n_lines != ls->n_in) return SR_ERR_ARG;
+  for (int64_t i = 0; i < n_lines; ++i) {
+    if (p_shift && !std::isfinite(p_shift[i])) return SR_ERR_ARG;
+    if (self_broad && (!std::isfinite(self_broad[i]) || self_broad[i] < 0.0)) return SR_ERR_ARG;
+  }
+  // calls in flight on the handle and its sub-linesets read the arrays replaced below
+  (void)hipDeviceSynchronize();
+  // the per-level sub-linesets carry copies of the old data: dropped, cut again on their next use (level_set)
+  for (std::vector<sr_lineset *> *sets : {&ls->level_sets, &ls->level_up_sets}) {
+    for (sr_lineset *child : *sets) sr_lineset_destroy(child);
+    sets->clear();
+  }
+  for (int which = 0; which < 2; ++which) {
+    HostLines &H = which ? ls->host_outer : ls->host;
+    const std::vector<int64_t> &in = which ? ls->in_outer : ls->in_main;
+    H.p_shift.clear();
+    H.self_broad.clear();
+    if (p_shift) {
+      H.p_shift.assign(H.md, 0.0);
+      for (size_t p = 0; p < in.size(); ++p) H.p_shift[p] = p_shift[in[p]];
+    }
+    if (self_broad) {
+      H.self_broad.assign(H.md, 0.0);
+      for (size_t p = 0; p < in.size(); ++p) H.self_broad[p] = self_broad[in[p]];
+    }
+  }
+  return lineset_upload(ls); // the arrays, and the bounds over the lines that depend on them (gamma_max, shift_max)
+}
+
+int sr_lineset_set_self_pressure(sr_lineset *ls, const double *p_self_hpa, int n_layers) {
+  if (!ls || ls->parent || n_layers < 0) return SR_ERR_ARG;
+  if (!p_self_hpa || n_layers == 0) {
+    ls->self_press.clear();
+    return SR_OK;
+  }
+  for (int k = 0; k < n_layers; ++k)
+    if (!(p_self_hpa[k] >= 0.0) || !std::isfinite(p_self_hpa[k])) return SR_ERR_ARG;
+  ls->self_press.assign(p_self_hpa, p_self_hpa + n_layers);
+  return SR_OK;
+}
+
 int sr_lineset_destroy(sr_lineset *ls) {
   if (!ls) return SR_OK;
   (void)hipDeviceSynchronize(); // work of the last calls may still be in flight on the internal streams
@@ -960,7 +1032,11 @@ static int l2l_table_dev(const double **out) {
 //   mar: the lineset whose lines bound the margins -- the handle itself, or its PARENT for the far-only level passes of
 //        the multi-channel route (every kernel of that route must place a (line, slot) pair on the same side of the
 //        near / far split: the pole margin enters the admissibility threshold)
-static size_t layer_stage_doubles(int nl, int npop) { return (size_t)nl * (9 + 2 * npop); }
+static size_t layer_stage_doubles(int nl, int npop) { return (size_t)nl * (10 + 2 * npop); }
+// Grid points the centres of the lines of `mar` move by in a layer of p_atm, rounded up (sr_lineset_set_line_shape)
+static int shift_points(const sr_lineset *mar, double p_atm, double gstep) {
+  return mar->shift_max > 0.0 ? (int)std::ceil(std::min(mar->shift_max * p_atm / gstep, 1e6)) : 0;
+}
 static size_t layer_stage_bytes(int nl, int npop) { return sizeof(double) * layer_stage_doubles(nl, npop) + sizeof(int) * 3 * (size_t)nl; }
 static int fill_layer_stage(const sr_lineset *ls, const sr_lineset *mar, const sr_lineset *bown, const sr_layers_desc *atm, double *T,
                             double q_ref = 0.0) {
@@ -968,7 +1044,9 @@ static int fill_layer_stage(const sr_lineset *ls, const sr_lineset *mar, const s
   const size_t hl_doubles = layer_stage_doubles(nl, npop);
   const bool frozen = !bown->bounds_temps.empty();
   double *pa = T + nl, *tr = pa + nl, *sq = tr + nl, *ltr = sq + nl, *ltrb = ltr + nl, *sqb = ltrb + nl, *tb = sqb + nl,
-         *pop = tb + nl, *qrat = pop + (size_t)nl * npop, *rvib = qrat + nl;
+         *pop = tb + nl, *qrat = pop + (size_t)nl * npop, *rvib = qrat + nl, *ps = rvib + (size_t)nl * npop;
+  // sr_lineset_set_self_pressure (on the handle the caller holds, like the frozen boundaries): 0 when unset
+  const bool self_p = !bown->self_press.empty() && (int)bown->self_press.size() == nl;
   std::vector<double> q(nl);
   if (atm->q_part) {
     std::copy(atm->q_part, atm->q_part + nl, q.begin());
@@ -982,6 +1060,7 @@ static int fill_layer_stage(const sr_lineset *ls, const sr_lineset *mar, const s
     tr[k] = kTref / T[k];                                                     // :1972
     sq[k] = std::sqrt(2 * kAvogadro * kKcgs * T[k] * kLn2 / ls->mm);          // :1984
     ltr[k] = std::log(tr[k]);
+    ps[k] = self_p ? bown->self_press[k] * kHpaToAtm : 0.0;
     {
       const double Tb = frozen ? bown->bounds_temps[k] : T[k]; // where the region boundaries are placed
       tb[k] = Tb;
@@ -997,7 +1076,18 @@ static int fill_layer_stage(const sr_lineset *ls, const sr_lineset *mar, const s
       const double sq_w = std::max(sq[k], sqb[k]);
       const double dwp_max = mar->freq_max / kCcgs * sq_w / std::sqrt(kLn2);
       int *pmh = reinterpret_cast<int *>(T + hl_doubles);
-      pmh[k] = (int)std::ceil(0.71 * dwp_max / ls->gp.gstep) + 1;
+      // Pressure shift (sr_lineset_set_line_shape).  The three bounds below are distances in grid points from a line's
+      // window centre ic -- what every candidate range and ownership test of the kernels is written in -- and each
+      // assumed the centre within half a cell of grid[ic].  The shifted centre x0' = Freq + p_shift P lies within
+      // 1/2 + |p_shift| P / step <= 1/2 + sk of it, so each grows by sk (0 without shifts):
+      //   pole margin: the poles sit within 0.71 dw' of x0', i.e. within 0.71 dw' / step + 1/2 + sk of ic; a box
+      //     admissible at kTheta h + pm from ic is then still kTheta h from the nearest pole, which is what the
+      //     truncation bound is written for (sr_kernels.hpp, ff_thr2);
+      //   source pole radius: the multipole series of a source box converges outside the largest distance of a pole
+      //     of its lines from the box centre, h + 1/2 + sk + |pole| (m2l_separated compares h + pm_src);
+      //   widest zone: region 1 starts (lw + 15 dw') / step from x0', i.e. that + 1/2 + sk from ic.
+      const int sk = shift_points(mar, pa[k], ls->gp.gstep);
+      pmh[k] = (int)std::ceil(0.71 * dwp_max / ls->gp.gstep) + 1 + sk;
       // box-pair mode: the multipole series of a source box converges outside the largest |pole| =
       // sqrt(1/2 + ry^2) dw' = sqrt(dw'^2 / 2 + lw^2) of its lines (bound over the lines of the layer)
       const double trb = frozen ? kTref / bown->bounds_temps[k] : tr[k];
@@ -1005,12 +1095,12 @@ static int fill_layer_stage(const sr_lineset *ls, const sr_lineset *mar, const s
                             std::max(std::max(std::pow(tr[k], mar->ndep_min), std::pow(tr[k], mar->ndep_max)),
                                      std::max(std::pow(trb, mar->ndep_min), std::pow(trb, mar->ndep_max)));
       const double pole = std::sqrt(0.5 * dwp_max * dwp_max + lw_max * lw_max) / ls->gp.gstep;
-      pmh[nl + k] = (int)std::ceil(std::min(pole, 1e6));
+      pmh[nl + k] = (int)std::ceil(std::min(pole, 1e6)) + sk;
       // widest region-2/3/4 zone of the layer, in grid points from the line centre: region 1 starts where
       // |x| - ry >= 15 (lineshape.f:447-454), i.e. (lw + 15 dw') / step points out, +-1 for the nint and the
       // centre's offset inside its grid cell.  A bound over the lines (every kernel reads this one value, so they
       // agree on who evaluates what); kernels clamp it to the window half-width.
-      pmh[2 * nl + k] = (int)std::min(std::ceil((lw_max + 15.0 * dwp_max) / ls->gp.gstep) + 2.0, (double)kHalf);
+      pmh[2 * nl + k] = (int)std::min(std::ceil((lw_max + 15.0 * dwp_max) / ls->gp.gstep) + 2.0 + sk, (double)kHalf);
     }
     if (nlev > 0) {
       for (int lv = 0; lv < nlev; ++lv) {
@@ -1054,7 +1144,7 @@ static int stage_layers(Stager &S, const sr_lineset *ls, const sr_lineset *mar, 
   LayersDev &A = out->A;
   A.temps = dl; A.p_atm = dl + nl; A.trat = dl + 2 * nl; A.sqk = dl + 3 * nl; A.ltrat = dl + 4 * nl;
   A.ltrat_b = dl + 5 * nl; A.sqk_b = dl + 6 * nl; A.temps_b = dl + 7 * nl; A.pop = dl + 8 * nl;
-  A.qrat = A.pop + (size_t)nl * npop; A.rvib = A.qrat + nl;
+  A.qrat = A.pop + (size_t)nl * npop; A.rvib = A.qrat + nl; A.ps_atm = A.rvib + (size_t)nl * npop;
   A.frozen = frozen ? 1 : 0;
   A.linear_w = frozen && bown->linear_weights ? 1 : 0;
   A.n_layers = nl; A.n_pop = npop;
@@ -1132,6 +1222,57 @@ static int check_coef_call(const sr_lineset *ls, const sr_layers_desc *atm, int6
   return SR_OK;
 }
 
+// What a coefficient call on a handle with sr_lineset_set_line_shape / sr_lineset_set_self_pressure data must hold
+// (include/spectrobot_hip.h), on the host, before anything is copied or launched.  root: the handle the caller holds
+// (a sub-lineset's parent).  Nothing to check, and SR_OK, for a handle without the data.
+static int check_line_shape(const sr_lineset *root, const sr_layers_desc *atm) {
+  const int nl = atm->n_layers;
+  if (!atm->press || !atm->temps) return SR_OK; // (refused by check_coef_call)
+  if (!root->self_press.empty()) {
+    if ((int)root->self_press.size() != nl) {
+      g_err = "sr_lineset_set_self_pressure was given another number of layers than this call";
+      return SR_ERR_ARG;
+    }
+    for (int k = 0; k < nl; ++k)
+      if (!(root->self_press[k] <= atm->press[k])) {
+        g_err = "sr_lineset_set_self_pressure: p_self above the layer's pressure";
+        return SR_ERR_ARG;
+      }
+  }
+  if (!(root->shift_max > 0.0)) return SR_OK;
+  const GridParams &gp = root->gp;
+  for (int k = 0; k < nl; ++k)
+    if (root->shift_max * (atm->press[k] * kHpaToAtm) > (double)SR_MAX_SHIFT_POINTS * gp.gstep) {
+      g_err = "pressure shift beyond SR_MAX_SHIFT_POINTS grid steps";
+      return SR_ERR_LIMIT;
+    }
+  // humliv_bb's branch must stay the one the line was sorted into: the outer lines, and the main lines centred beyond
+  // a grid end (the only ones whose centre is not within half a step of their window centre) -- few of either
+  auto inside = [&](const HostLines &H, int64_t q, double p_atm) {
+    const WinX xf{gp.lin_start, gp.lin_delta, grid_at(gp, H.i[q])};
+    const double x0 = H.d[q] + H.p_shift[q] * p_atm;
+    return xf(1) < x0 && x0 < xf(kImxsig);
+  };
+  const HostLines &Ho = root->host_outer, &Hm = root->host;
+  for (int k = 0; k < nl; ++k) {
+    const double p_atm = atm->press[k] * kHpaToAtm;
+    for (int64_t q = 0; q < Ho.m && !Ho.p_shift.empty(); ++q)
+      if (inside(Ho, q, p_atm)) {
+        g_err = "pressure shift moves an outer line's centre into its own window";
+        return SR_ERR_UNSUPPORTED;
+      }
+    for (int64_t q = 0; q < Hm.m; ++q) {
+      if (q == root->n_disp_lo) q = std::max(q, Hm.m - root->n_disp_hi);
+      if (q >= Hm.m) break;
+      if (!inside(Hm, q, p_atm)) {
+        g_err = "pressure shift moves a line's centre out of its own window";
+        return SR_ERR_UNSUPPORTED;
+      }
+    }
+  }
+  return SR_OK;
+}
+
 // The layers of a call in batches of at most `batch`: fn(sub, k0) for every [k0, k0 + sub.n_layers), with the batch's
 // slice of temps / press / q_part and of the vibrational temperatures (keep_tvib; else none: no populations enter the
 // level spectra), and with bown->bounds_temps (sr_lineset_set_bounds_temps) cut to the batch, restored on every way out.
@@ -1145,11 +1286,11 @@ static int for_layer_batches(const sr_layers_desc *atm, sr_lineset *bown, int nl
   sr_layers_desc sub = *atm;
   if (!keep_tvib) sub.tvib = nullptr;
   if (batch >= nl) return fn(sub, 0);
-  const std::vector<double> bounds_all = bown->bounds_temps;
+  const std::vector<double> bounds_all = bown->bounds_temps, self_all = bown->self_press;
   struct Restore {
-    sr_lineset *ls; const std::vector<double> &all;
-    ~Restore() { ls->bounds_temps = all; }
-  } restore{bown, bounds_all};
+    sr_lineset *ls; const std::vector<double> &all, &self;
+    ~Restore() { ls->bounds_temps = all; ls->self_press = self; }
+  } restore{bown, bounds_all, self_all};
   std::vector<double> tv;
   for (int k0 = 0; k0 < nl; k0 += batch) {
     const int n = sub.n_layers = std::min(batch, nl - k0);
@@ -1163,6 +1304,7 @@ static int for_layer_batches(const sr_layers_desc *atm, sr_lineset *bown, int nl
       sub.tvib = tv.data();
     }
     if (!bounds_all.empty()) bown->bounds_temps.assign(bounds_all.begin() + k0, bounds_all.begin() + k0 + n);
+    if (!self_all.empty()) bown->self_press.assign(self_all.begin() + k0, self_all.begin() + k0 + n);
     const int rc = fn(sub, k0);
     if (rc) return rc;
   }
@@ -1449,7 +1591,8 @@ static int coef_op(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
                    double *emi_out, void *stream, const WeightMode W, const CoefOpt opt = CoefOpt()) {
   const bool far_only = opt.far_coef != nullptr;
   if (!far_only && (!abs_out || !emi_out)) return SR_ERR_ARG;
-  const int rc = check_coef_call(ls, atm, g_lo, g_hi);
+  int rc = check_coef_call(ls, atm, g_lo, g_hi);
+  if (!rc) rc = check_line_shape(ls->parent ? ls->parent : ls, atm);
   if (rc) return rc;
   // one snapshot of the mode switches per call
   CoefModes m;
@@ -1744,7 +1887,8 @@ static int mc_pass(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int6
   const int nlev = ls->n_levels;
   McCall c{ls, g_lo, g_hi, out, stream, ctypes3, g_far_field.load(), atm->n_layers, ctypes3 ? 2 * nlev : nlev};
   if (nlev <= 0 || c.far_mode == 0 || g_counting.load() != 0 || g_level_route.load() == 0) return SR_ERR_UNSUPPORTED;
-  const int rc = check_coef_call(ls, atm, g_lo, g_hi);
+  int rc = check_coef_call(ls, atm, g_lo, g_hi);
+  if (!rc) rc = check_line_shape(ls->parent ? ls->parent : ls, atm);
   if (rc) return rc;
   const McChannels &mc = c.mc = ctypes3 ? McChannels{3, 2, 0, 1, 3 * nlev} : McChannels{2, 0, 1, 0, 2 * nlev}; // stride, o_lo, o_up_e, o_up_a, n_ch
   if (mc.n_ch > 1023) return SR_ERR_UNSUPPORTED; // (10 bits per channel in the zones kernel's packed item word)
@@ -1866,6 +2010,7 @@ int sr_abscoeff_layers_from_strengths_dev(sr_lineset *ls, const sr_layers_desc *
 int sr_gcoeff_layers_dev(sr_lineset *ls, const sr_layers_desc *atm, int level, int64_t g_lo, int64_t g_hi,
                          double *g_out, void *stream) {
   if (!g_out || check_coef_call(ls, atm, g_lo, g_hi, true)) return SR_ERR_ARG;
+  if (const int rcs = check_line_shape(ls->parent ? ls->parent : ls, atm)) return rcs; // before any sub-lineset is cut
   sr_lineset *c = nullptr;
   int rc = level_set(ls, level, &c);
   if (rc) return rc;
@@ -1898,6 +2043,7 @@ int sr_abscoeff_level_dev(sr_lineset *ls, const sr_layers_desc *atm, int level, 
 
 int sr_glevel_pairs_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi, double *out, void *stream) {
   if (!out || check_coef_call(ls, atm, g_lo, g_hi, true)) return SR_ERR_ARG;
+  if (const int rcs = check_line_shape(ls->parent ? ls->parent : ls, atm)) return rcs; // before any sub-lineset is cut
   const size_t plane = (size_t)atm->n_layers * (size_t)(g_hi - g_lo);
   if (ls->n_levels == 0) // the 'all' set: every line, pop = 1 / Q in the combine (smm:2052-2057)
     return coef_op(ls, atm, g_lo, g_hi, out, out + plane, stream, WeightMode{kWeightLevelPair, -1});
@@ -1920,6 +2066,7 @@ int sr_glevel_pairs_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo,
 
 int sr_gcoeff_levels_dev(sr_lineset *ls, const sr_layers_desc *atm, int64_t g_lo, int64_t g_hi, double *g_out, void *stream) {
   if (!g_out || check_coef_call(ls, atm, g_lo, g_hi, true)) return SR_ERR_ARG;
+  if (const int rcs = check_line_shape(ls->parent ? ls->parent : ls, atm)) return rcs; // before any sub-lineset is cut
   if (ls->n_levels == 0) return sr_gcoeff_layers_dev(ls, atm, 0, g_lo, g_hi, g_out, stream);
   {
     const int rc = mc_pass(ls, atm, g_lo, g_hi, g_out, stream, 1);

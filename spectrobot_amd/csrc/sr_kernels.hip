@@ -87,6 +87,20 @@ struct LinePhys {
   double lw, dwp, wabs, wemi;
   double w3; // kWeightChannels only: the third weight (0 otherwise)
 };
+// sr_lineset_set_line_shape (include/spectrobot_hip.h): what multiplies (296/T)^n in the Lorentz width of line ln in
+// layer k, gamma_air (P - Ps) + gamma_self Ps (spcl:1972 with its Self_broad / Self_pres_atm passed), and the centre
+// that positions the shape, x0' = Freq + P_shift P (spcl:187).  Unset data: the expressions as they always were.
+__device__ __forceinline__ double line_gamma_p(const LinesDev &L, const LayersDev &A, int ln, int k) {
+  if (L.self_broad) {
+    const double ps = A.ps_atm[k];
+    return L.air_broad[ln] * (A.p_atm[k] - ps) + L.self_broad[ln] * ps;
+  }
+  return L.air_broad[ln] * A.p_atm[k];
+}
+__device__ __forceinline__ double line_centre(const LinesDev &L, const LayersDev &A, int ln, int k) {
+  const double x0 = L.freq[ln];
+  return L.p_shift ? x0 + L.p_shift[ln] * A.p_atm[k] : x0;
+}
 __device__ inline LinePhys line_physics(const LinesDev &L, const LayersDev &A, const WeightMode W, int ln, int k) {
   LinePhys P;
   const double T = A.temps[k];
@@ -94,7 +108,7 @@ __device__ inline LinePhys line_physics(const LinesDev &L, const LayersDev &A, c
   // exp_bounded: the library routine without its special cases (|argument| clamped to 700: e^-700 = 1e-304 is as good
   // as the 0 the reference's exp underflows to much later); three of them were 12 % of this kernel's instructions
   auto ex = [](double u) { return exp_bounded(fmin(fmax(u, -700.0), 700.0)); };
-  P.lw = ex(L.t_dep[ln] * A.ltrat[k]) * (L.air_broad[ln] * A.p_atm[k]); // (296/T)^n gamma P  (spcl:1972)
+  P.lw = ex(L.t_dep[ln] * A.ltrat[k]) * line_gamma_p(L, A, ln, k); // (296/T)^n gamma P  (spcl:1972)
   const double dw = x0 / kCcgs * A.sqk[k];
   P.dwp = dw / A.sqrt_ln2;
   // Linearised weights (sr_lineset_set_linear_weights, with frozen boundaries): the G coefficients and the
@@ -167,7 +181,8 @@ __device__ __forceinline__ void prep_body(const LinesDev &L, const LayersDev &A,
   const bool valid = i0 < n_sub;
   const int i = valid ? i0 : n_sub - 1;
   const int ln = line_lo + i;
-  const double x0 = L.freq[ln];
+  const double freq = L.freq[ln];
+  const double x0 = line_centre(L, A, ln, k); // positions the shape; the Doppler width and the weights keep Freq
   const LinePhys ph = line_physics(L, A, W, ln, k);
   const double lw = ph.lw, dwp = ph.dwp;
 
@@ -178,8 +193,8 @@ __device__ __forceinline__ void prep_body(const LinesDev &L, const LayersDev &A,
   if (A.frozen) {
     // sr_lineset_set_bounds_temps: the region boundaries (indices) as at the layer's boundary temperature, every
     // width and running x at the call's own -- c(T + dT) and c(T) then share their seams
-    const double lw_b = exp_bounded(fmin(fmax(L.t_dep[ln] * A.ltrat_b[k], -700.0), 700.0)) * (L.air_broad[ln] * A.p_atm[k]);
-    dwp0 = x0 / kCcgs * A.sqk_b[k] / A.sqrt_ln2;
+    const double lw_b = exp_bounded(fmin(fmax(L.t_dep[ln] * A.ltrat_b[k], -700.0), 700.0)) * line_gamma_p(L, A, ln, k);
+    dwp0 = freq / kCcgs * A.sqk_b[k] / A.sqrt_ln2;
     B0 = humliv_bounds(xf, kImxsig, x0, lw_b, dwp0);
     B.il = B0.il; B.ir = B0.ir; B.il2 = B0.il2; B.ir2 = B0.ir2;
     B.xr = div_with(xf(B.ir) - x0, dwp, B.inv_dwp); // lineshape.f:471 at the frozen ir
@@ -266,7 +281,7 @@ __global__ __launch_bounds__(64) void sr_outer_prep_kernel(LinesDev L, int n_out
   const int i = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
   if (i >= n_out) return;
   const LinePhys ph = line_physics(L, A, W, i, k);
-  const double x0 = L.freq[i], dw = ph.dwp;
+  const double x0 = line_centre(L, A, i, k), dw = ph.dwp;
   const int ic = L.ic[i], n = kImxsig;
   const WinX xf{gp.lin_start, gp.lin_delta, grid_at(gp, ic)};
   OuterRec r;

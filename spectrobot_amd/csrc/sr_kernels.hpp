@@ -12,6 +12,9 @@ struct LinesDev {
   const int *ic, *lev_up, *lev_lo;
   int n_lines;
   const double *s_ref; // sr_lineset_set_strengths: HITRAN intensities at WeightMode::t_ref (kWeightStrength); else null
+  // sr_lineset_set_line_shape: pressure shift of the centre and self-broadening, cm^-1 / atm; each null when unset (the
+  // same for every line of a launch: the test is wave-uniform)
+  const double *p_shift, *self_broad;
 };
 
 // Device-resident layer stack; per-layer scalars are evaluated on the host in
@@ -28,6 +31,7 @@ struct LayersDev {
   double sqrt_ln2, sqrt_pi_ln2;
   const double *qrat;                       // kWeightStrength / line strengths: Q(t_ref) / Q(T) [n_layers]
   const double *rvib;                       //   r_L = b(E_L, Tvib_L) / b(E_L, T) [n_layers][n_pop] (vibtemp_to_ratio)
+  const double *ps_atm;                     // sr_lineset_set_self_pressure: the gas's own partial pressure [atm] (0 when unset)
 };
 
 // What the two output channels ("abs", "emi") of the coefficient kernels accumulate, chosen per call:

@@ -243,6 +243,36 @@ class LineSet(object):
             check(lib.sr_lineset_set_bounds_temps(self._h, tp, int(t.size)), "sr_lineset_set_bounds_temps")
             check(lib.sr_lineset_set_linear_weights(self._h, int(bool(linear_weights))), "sr_lineset_set_linear_weights")
 
+    def set_line_shape(self, p_shift=None, self_broad=None):
+        """Pressure shift of the line centres and self-broadening (sr_lineset_set_line_shape): p_shift and self_broad,
+        cm^-1 / atm, one per input line in the constructor's order (SpectLine.P_shift, .Self_broad:
+        spect_classes.line_shape_of).  Either may be None; both None restores the default, which is the reference's
+        behaviour (centres at Freq, air broadening only).  Every later coefficient call on this line set places the
+        shapes at Freq + p_shift P and takes lw = (296/T)^n (gamma_air (P - p_self) + gamma_self p_self), p_self from
+        set_self_pressure."""
+        ps = sb = None
+        pp = sp = None
+        n = 0
+        if p_shift is not None:
+            ps, pp = _d(p_shift)
+            n = ps.size
+        if self_broad is not None:
+            sb, sp = _d(self_broad)
+            n = sb.size
+        for a in (ps, sb):
+            if a is not None and (a.ndim != 1 or a.size != self.n_lines_in):
+                raise ValueError("p_shift / self_broad must hold one value per input line (%d)" % self.n_lines_in)
+        check(lib.sr_lineset_set_line_shape(self._h, pp, sp, int(n)), "sr_lineset_set_line_shape")
+
+    def set_self_pressure(self, p_self=None):
+        """Partial pressure of the gas itself, hPa per layer, for the following coefficient calls with that many layers
+        (sr_lineset_set_self_pressure); None: 0 again.  It acts through set_line_shape's self_broad only."""
+        if p_self is None:
+            check(lib.sr_lineset_set_self_pressure(self._h, None, 0), "sr_lineset_set_self_pressure")
+        else:
+            p, pp = _d(np.atleast_1d(np.asarray(p_self, dtype=np.float64)))
+            check(lib.sr_lineset_set_self_pressure(self._h, pp, int(p.size)), "sr_lineset_set_self_pressure")
+
     def gcoeff_layers(self, temps, press, level=0, g_lo=0, g_hi=None):
         """Per-ctype G-coefficient spectra of one level at every (P, T): CUDA float64
         [3, n_layers, g_hi-g_lo], ctype 0 sp_emission, 1 ind_emission, 2 absorption

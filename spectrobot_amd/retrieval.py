@@ -45,13 +45,23 @@ class _Grid(object):
 
 class Gas(object):
     """One absorber: its line set on the scene's grid, isotopic abundance, VMR profile on the altitude levels
-    and (non-LTE) vibrational temperatures [n_levels, n_layers]."""
+    and (non-LTE) vibrational temperatures [n_levels, n_layers].
+    self_broadening: the line set carries self-broadening coefficients (engine.LineSet.set_line_shape) and the scene
+    hands it the gas's own partial pressure, vmr x press of the layers, before every coefficient build.  The VMR
+    Jacobians hold the coefficients fixed -- the dependence of the Lorentz width on the gas's own VMR is not
+    differentiated; a retrieval refreshes the coefficients between its iterations (coefficients(refresh=True))."""
 
-    def __init__(self, name, lineset, vmr, iso_ratio=1.0, tvib=None):
+    def __init__(self, name, lineset, vmr, iso_ratio=1.0, tvib=None, self_broadening=False):
         self.name, self.lineset, self.iso_ratio = name, lineset, float(iso_ratio)
         self.vmr = np.asarray(vmr, dtype=float)
         self.tvib = tvib
+        self.self_broadening = bool(self_broadening)
         self.coeffs = None      # (abs, emi) CUDA [n_layers, n_grid], computed on demand
+
+    def set_self_pressure(self, press):
+        """The line set's self pressure for the coefficient build that follows: vmr x press (hPa) when self_broadening."""
+        if self.self_broadening:
+            self.lineset.set_self_pressure(self.vmr * np.asarray(press, dtype=float))
 
     def add_clim(self, profile):
         """New VMR profile (planet.gases[gas].add_clim, spect_main_module.py:2625, 2985)."""
@@ -64,13 +74,13 @@ class LevelGas(Gas):
     a reference tvib0 [n_levels, n_layers]; its coefficients are lf.steps(rows, tvib), recombined only when tvib was
     changed (set_tvib): a combine of the resident tables, never a walk of the lines."""
 
-    def __init__(self, name, lineset, vmr, tvib0, iso_ratio=1.0, dT=None):
+    def __init__(self, name, lineset, vmr, tvib0, iso_ratio=1.0, dT=None, self_broadening=False):
         """dT: handed to engine.LevelFactored -- the tables also at T + dT, for the temperature derivative of the
         coefficients (layer_coefficients(derivative=True): a retrieval with a TempProfile needs it)."""
         tvib0 = np.array(tvib0, dtype=float)
         if tvib0.ndim != 2 or tvib0.shape[0] != max(int(np.size(lineset.level_energies)), 1):
             raise ValueError("tvib0 must be [n_levels, n_layers] for the line set's levels")
-        Gas.__init__(self, name, lineset, vmr, iso_ratio=iso_ratio, tvib=tvib0.copy())
+        Gas.__init__(self, name, lineset, vmr, iso_ratio=iso_ratio, tvib=tvib0.copy(), self_broadening=self_broadening)
         self.tvib0, self.dT = tvib0, dT
         self.lf, self._lf_key, self._combined, self.dcoeffs = None, None, None, None
 
@@ -88,7 +98,9 @@ class LevelGas(Gas):
         """(abs, emi) on the layer stack from the pair tables (LimbScene.coefficients calls this).  New temperatures or
         pressures on the same number of rows and the same shard rebuild the tables in place (LevelFactored.rebuild).
         derivative=True also leaves (d abs / dT, d emi / dT) in self.dcoeffs (LevelFactored.steps(derivative=True))."""
-        key = (np.asarray(temps, float).tobytes(), np.asarray(press, float).tobytes(), int(g_lo), g_hi)
+        self.set_self_pressure(press)
+        key = (np.asarray(temps, float).tobytes() + (self.vmr.tobytes() if self.self_broadening else b""),
+               np.asarray(press, float).tobytes(), int(g_lo), g_hi)
         if self.lf is None or self._lf_key[2:] != key[2:] or self.lf.temps.size != len(temps) or self.lf.dT != self.dT:
             self.lf = engine.LevelFactored(self.lineset, temps, press, dT=self.dT, g_lo=g_lo, g_hi=g_hi)
             self._lf_key, self._combined = key, None
@@ -277,6 +289,7 @@ class LimbScene(object):
                 g.layer_coefficients(self.temps, self.press, g_lo=g_lo, g_hi=g_hi)
                 continue
             if g.coeffs is None or refresh or getattr(g, "coeffs_shard", None) != (g_lo, g_hi):
+                g.set_self_pressure(self.press)
                 g.coeffs = g.lineset.abscoeff_layers(self.temps, self.press, tvib=g.tvib, g_lo=g_lo, g_hi=g_hi)
                 g.coeffs_shard = (g_lo, g_hi)
         return [g.coeffs for g in self.gases]
@@ -427,6 +440,7 @@ class LimbScene(object):
                     raise ValueError("a temperature retrieval needs LevelGas(%r, ..., dT=...): the tables at T + dT" % (g.name,))
                 g.layer_coefficients(self.temps, self.press, g_lo=0, g_hi=len(self.grid), derivative=True)   # (coefficients()' own shard key)
             elif getattr(g, "_dT_key", None) != key or g.coeffs is None or g.coeffs_shard != (0, len(self.grid)):
+                g.set_self_pressure(self.press)
                 g.coeffs = g.lineset.abscoeff_layers(self.temps, self.press, tvib=g.tvib)
                 g.coeffs_shard = (0, len(self.grid))
                 _, g.dcoeffs = engine.coefficients_dT(g.lineset, self.temps, self.press, tvib=g.tvib, scheme="forward",
@@ -537,11 +551,13 @@ def _simulate_budget(scene, pixels, track_levels, fov_closed_form, shard, refres
         if gi in tracked:
             lf = getattr(g, "level_factored", None)
             if lf is None or refresh or g.level_factored_shard != (g_lo, g_hi):
+                g.set_self_pressure(scene.press)
                 lf = g.level_factored = engine.LevelFactored(g.lineset, scene.temps, scene.press, g_lo=g_lo, g_hi=g_hi)
                 g.level_factored_shard = (g_lo, g_hi)
             coeffs.append(lf.steps(rows, tvib=g.tvib))
         else:
             if g.coeffs is None or refresh or getattr(g, "coeffs_shard", None) != (g_lo, g_hi):
+                g.set_self_pressure(scene.press)
                 g.coeffs = g.lineset.abscoeff_layers(scene.temps, scene.press, tvib=g.tvib, g_lo=g_lo, g_hi=g_hi)
                 g.coeffs_shard = (g_lo, g_hi)
             coeffs.append(g.coeffs)

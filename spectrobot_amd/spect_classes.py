@@ -194,6 +194,14 @@ def strengths_of(lines):
     return np.array([float(l.Strength) for l in lines], dtype=np.float64)
 
 
+def line_shape_of(lines):
+    """(p_shift, self_broad) of a line list in list order, cm^-1 / atm (SpectLine.P_shift, .Self_broad): what
+    engine.LineSet.set_line_shape takes for the same list's lines_to_soa.  The reference reads both and uses neither
+    (spect_classes.py:187-197, 1967-1972)."""
+    return (np.array([float(l.P_shift) for l in lines], dtype=np.float64),
+            np.array([float(l.Self_broad) for l in lines], dtype=np.float64))
+
+
 def ImportPartitionSumTable(mol, iso):
     """spect_classes.py:1680-1689 -> gi, T_grid, Q_grid (library TIPS-2003 tables)"""
     from .compat import fparts_mod

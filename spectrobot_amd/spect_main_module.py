@@ -421,7 +421,7 @@ def _populations(isomolec, levels, Temps, LTE):
 
 def make_abscoeff_isomolec(wn_range_tot, isomolec, Temps, Press, LTE=True, allLUTs=None, useLUTs=False,
                            lines=None, store_in_memory=False, tagLOS=None, cartDROP=None, track_levels=None,
-                           n_threads=n_threads, lineset=None, to_host=True):
+                           n_threads=n_threads, lineset=None, to_host=True, pressure_shift=False, self_vmr=None):
     """Absorption and emission coefficients of `isomolec` at every (Press[i], Temps[i])
     (spect_main_module.py:1880-2131).  Non-LTE: every level of isomolec.levels carries .local_vibtemp (one
     value per step).
@@ -431,6 +431,13 @@ def make_abscoeff_isomolec(wn_range_tot, isomolec, Temps, Press, LTE=True, allLU
     round trip and the population-weighted combine.  useLUTs=True: allLUTs[(isomolec.mol_name, isomolec.iso)]
     is a LookUpTable; its G spectra are interpolated to every step and combined on the GPU (:1992-2017).
     track_levels: level names whose own share of the coefficients is returned too.
+
+    pressure_shift, self_vmr (useLUTs=False; the defaults are the reference's behaviour, which reads P_shift and
+    Self_broad and uses neither, :187-197 of its spect_classes): pressure_shift=True centres every shape at
+    Freq + P_shift P; self_vmr (a number, or one value per step) broadens with
+    Air_broad (P - p_self) + Self_broad p_self, p_self = self_vmr * Press (engine.LineSet.set_line_shape /
+    set_self_pressure).  The line data come from `lines`; with a `lineset` alone its own set_line_shape data hold and
+    self_vmr only sets the self pressure of this call.
 
     Returns (abs_coeffs, emi_coeffs) or, with track_levels, (abs_coeffs, emi_coeffs, emi_coeffs_tracked,
     abs_coeffs_tracked): AbsSetLOS with .device (CUDA [n_steps, n_grid]) and, when to_host, one
@@ -450,6 +457,9 @@ def make_abscoeff_isomolec(wn_range_tot, isomolec, Temps, Press, LTE=True, allLU
             if lev not in isomolec.levels:
                 raise ValueError('level {} is not a level of mol {} iso {}'.format(lev, isomolec.mol, isomolec.iso))
     tracked = {}
+    if useLUTs and (pressure_shift or self_vmr is not None):
+        raise ValueError('pressure_shift / self_vmr act where the shapes are computed: give them to the run that '
+                         'builds the look-up table (useLUTs=False, or a lineset with set_line_shape)')
     if useLUTs:
         LUTs = allLUTs[(isomolec.mol_name, isomolec.iso)]
         spectral_grid = LUTs.spectral_grid
@@ -475,6 +485,13 @@ def make_abscoeff_isomolec(wn_range_tot, isomolec, Temps, Press, LTE=True, allLU
         spectral_grid = prepare_spe_grid(wn_range_tot).spectral_grid
         if lineset is None:
             lineset = _as_lineset(lines, spectral_grid, isomolec)                  # :1968 filter inside
+            if pressure_shift or self_vmr is not None:
+                own = [lin for lin in lines if lin.Mol == isomolec.mol and lin.Iso == isomolec.iso]
+                p_shift, self_broad = spcl.line_shape_of(own)
+                lineset.set_line_shape(p_shift if pressure_shift else None, self_broad if self_vmr is not None else None)
+        elif pressure_shift:
+            raise ValueError('pressure_shift with a ready lineset: call lineset.set_line_shape(...) on it instead')
+        p_self = None if self_vmr is None else np.asarray(self_vmr, float) * Press   # hPa per step
         tvib = None
         if levels and not LTE:
             tvib = np.array([lv.local_vibtemp for lv in levels], dtype=float)      # :2065
@@ -484,12 +501,22 @@ def make_abscoeff_isomolec(wn_range_tot, isomolec, Temps, Press, LTE=True, allLU
         # level-factored route -- per-level pair spectra on the distinct rows + one population-weighted combine
         # (:2036-2106), engine.LevelFactored -- replaces the folded op over the steps.  Same numbers to ~1e-13.
         T_rows, P_rows, step_row = engine.LevelFactored.unique_rows(Temps, Press)
-        if len(T_rows) * 3 <= len(Temps):
-            ab, em = engine.LevelFactored(lineset, T_rows, P_rows).steps(step_row, tvib=tvib)
-        else:
-            ab, em = lineset.abscoeff_layers(Temps, Press, tvib=tvib)
-        for lev in (track_levels or []):
-            tracked[lev] = lineset.abscoeff_level(Temps, Press, isomolec.levels.index(lev), tvib=tvib)
+        # (a self pressure that differs between steps of one (P, T) row has no place in the rows' tables)
+        by_rows = len(T_rows) * 3 <= len(Temps) and (self_vmr is None or np.ndim(self_vmr) == 0)
+        try:
+            if by_rows:
+                if p_self is not None:
+                    lineset.set_self_pressure(float(self_vmr) * np.asarray(P_rows, float))
+                ab, em = engine.LevelFactored(lineset, T_rows, P_rows).steps(step_row, tvib=tvib)
+            if p_self is not None:
+                lineset.set_self_pressure(p_self)
+            if not by_rows:
+                ab, em = lineset.abscoeff_layers(Temps, Press, tvib=tvib)
+            for lev in (track_levels or []):
+                tracked[lev] = lineset.abscoeff_level(Temps, Press, isomolec.levels.index(lev), tvib=tvib)
+        finally:
+            if p_self is not None:
+                lineset.set_self_pressure(None)
 
     tagLOS = 'LOS' if tagLOS is None else tagLOS
     if store_in_memory and to_host:
