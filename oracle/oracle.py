@@ -45,6 +45,9 @@ def lib():
         for n in ("sro_h_cgs", "sro_c_cgs", "sro_k_cgs", "sro_c2"):
             getattr(L, n).restype = C.c_double
         L.sro_humliv_bb.argtypes = [_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _dp]
+        L.sro_humliv_bb_bounds.argtypes = [_dp, C.c_int, C.c_int] + [C.c_double] * 5 + [C.c_int, _dp]
+        L.sro_humliv_bounds.argtypes = [_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_long)]
+        L.sro_make_shape_bounds.argtypes = [_dp, C.c_int] + [C.c_double] * 5 + [C.c_int, _dp]
         L.sro_humli_bb.restype = C.c_double
         L.sro_humli_bb.argtypes = [C.c_double, C.c_double]
         L.sro_sum_all_lines.argtypes = [_dp, C.c_long, _dp, _ip, _ip, C.c_int, C.c_int]
@@ -110,6 +113,28 @@ def humliv_bb(x, i1, i2, x0, lw, dw):
     return y
 
 
+def humliv_bb_bounds(x, i1, i2, x0, lw, dw, lw_b, dw_b, flags=0):
+    """humliv_bb with the middle branch's region boundaries placed at the widths (lw_b, dw_b) and every value computed
+    with (lw, dw) (sro_humliv_bb_bounds); flags & 1: cmplx(ry, -rx) left in double ("smooth")."""
+    x, xp = _d(x)
+    y = np.zeros_like(x)
+    rc = lib().sro_humliv_bb_bounds(xp, i1, i2, x0, lw, dw, lw_b, dw_b, int(flags), y.ctypes.data_as(_dp))
+    if rc:
+        raise ValueError("humliv_bb_bounds: Fortran would stop (code %d)" % rc)
+    return y
+
+
+def humliv_bounds(x, i1, i2, x0, lw, dw):
+    """(il, ir, il2, ir2, k3lo, k3hi) of humliv_bb's middle branch at (lw, dw) as an int64 array (k3lo > k3hi: no
+    region-3 point), or None where the centre lies outside (x(i1), x(i2)): a sequential branch has no boundaries."""
+    x, xp = _d(x)
+    out = (C.c_long * 6)()
+    rc = lib().sro_humliv_bounds(xp, i1, i2, x0, lw, dw, out)
+    if rc < 0:
+        raise ValueError("humliv_bounds: Fortran would stop (code %d)" % rc)
+    return None if rc else np.array(list(out), dtype=np.int64)
+
+
 def humli_bb(rx, ry):
     return lib().sro_humli_bb(rx, ry)
 
@@ -141,6 +166,16 @@ def make_shape(xwin, wn0, lw, dw):
     rc = lib().sro_make_shape(xp, xwin.size, wn0, lw, dw, s.ctypes.data_as(_dp))
     if rc:
         raise ValueError("make_shape rc=%d" % rc)
+    return s
+
+
+def make_shape_bounds(xwin, wn0, lw, dw, lw_b, dw_b, flags=0):
+    """make_shape with the region boundaries placed at the widths (lw_b, dw_b) (sro_make_shape_bounds)."""
+    xwin, xp = _d(xwin)
+    s = np.zeros_like(xwin)
+    rc = lib().sro_make_shape_bounds(xp, xwin.size, wn0, lw, dw, lw_b, dw_b, int(flags), s.ctypes.data_as(_dp))
+    if rc:
+        raise ValueError("make_shape_bounds rc=%d" % rc)
     return s
 
 

@@ -38,13 +38,20 @@ static long lmin(long a, long b) { return a < b ? a : b; }
 /* ------------------------------------------------------------------ */
 /* Humlicek regions                                                    */
 /* ------------------------------------------------------------------ */
-/* lineshape.f:529-560 (also 277-311, 363-398): one core point.
- * cmplx(ry,-rx) is default-kind => both parts rounded to single; the
- * polynomial literals carry no D0 => rounded to single. */
-static double core_point(double rx, double ry) {
+/* lineshape.f:529-560 (also 277-311, 363-398): one core point, in two parts --
+ * the region test (:528) and the region's value -- so that the variant with
+ * frozen boundaries (sro_humliv_bb_bounds) can take them at different widths.
+ * cmplx(ry,-rx) is default-kind => both parts rounded to single (smooth != 0:
+ * left in double, sro_humliv_bb_bounds' flags & 1); the polynomial literals
+ * carry no D0 => rounded to single either way. */
+static int core_is_region4(double rx, double ry) {
   double r2 = (0.195 * rx) - 0.176;
-  double complex c2 = (double)(float)ry + I * (double)(float)(-rx);
-  if (ry < r2) { /* region 4 */
+  return ry < r2;
+}
+static double core_value(double rx, double ry, int region4, int smooth) {
+  double complex c2 = smooth ? ry + I * (-rx)
+                             : (double)(float)ry + I * (double)(float)(-rx);
+  if (region4) { /* region 4 */
     double complex c1 = c2 * c2;
     double complex num =
         c2 *
@@ -76,6 +83,9 @@ static double core_point(double rx, double ry) {
                      c2 * (F32(21.69274) + c2 * (F32(6.699398) + c2)))));
     return creal(num / den);
   }
+}
+static double core_point(double rx, double ry, int smooth) {
+  return core_value(rx, ry, core_is_region4(rx, ry), smooth);
 }
 
 typedef struct {
@@ -120,13 +130,45 @@ static double region1_val(const r1coef *q, double x2) {
 #define X(k) x[(k)-1]
 #define Y(k) y[(k)-1]
 
-int sro_humliv_bb(const double *x, int i1, int i2, double x0, double lw,
-                  double dw, double *y) {
+/* Region boundaries of the middle branch, lineshape.f:443-490 (il2, ir2 as
+ * computed there, before :524-525 move them off an empty region 2). */
+typedef struct {
+  long il, ir, il2, ir2;
+} mid_bounds;
+static mid_bounds middle_bounds(const double *x, int i1, int i2, double x0,
+                                double lw, double dw) {
+  mid_bounds b;
+  double ry = lw / dw;
+  double xstep = (X(i1 + 1) - X(i1)) / dw;
+  double rx = (x0 - X(i1)) / dw;
+  double tst = 15.;
+  b.il = i1;
+  if (rx + ry >= tst) b.il = lmax(nintl((rx - ry - tst) / xstep), 0) + i1;
+  rx = (X(i2) - x0) / dw;
+  b.ir = i2;
+  if (rx + ry >= tst) b.ir = i2 - lmax(nintl((rx - ry - tst) / xstep), 0);
+  rx = (x0 - X(b.il)) / dw;
+  tst = 5.5;
+  b.il2 = b.il;
+  if (rx + ry >= tst) b.il2 = b.il + lmax(nintl((rx - ry - tst) / xstep), 0);
+  b.ir2 = b.ir;
+  rx = (X(b.ir) - x0) / dw;
+  if (rx + ry >= tst) b.ir2 = b.ir - lmax(nintl((rx - ry - tst) / xstep), 0);
+  return b;
+}
+
+/* humliv_bb and its variant in one body: (lw_b, dw_b) place the middle branch's
+ * boundaries and decide region 3 / 4 of a core point, (lw, dw) give every value;
+ * with lw_b == lw, dw_b == dw and smooth == 0 it is lineshape.f:226-569. */
+static int humliv_impl(const double *x, int i1, int i2, double x0, double lw,
+                       double dw, double lw_b, double dw_b, int smooth,
+                       double *y) {
   long j, k, l, ir, ir2, il, il2;
   double rx, ry, tst, xrun, xstep, x2, ry2;
 
   if (i1 > i2) return -1;   /* lineshape.f:253-256 */
   if (!(dw > 0.0)) return -2; /* lineshape.f:260-264 */
+  if (!(dw_b > 0.0)) return -2;
   ry = lw / dw;
   xstep = (X(i1 + 1) - X(i1)) / dw; /* :265-266 */
   ry2 = ry * ry;
@@ -136,7 +178,7 @@ int sro_humliv_bb(const double *x, int i1, int i2, double x0, double lw,
     j = i1;
     rx = (X(j) - x0) / dw;
     while ((rx + ry < tst) && (j <= i2)) {
-      Y(j) = core_point(rx, ry);
+      Y(j) = core_point(rx, ry, smooth);
       j = j + 1;
       rx = rx + xstep;
     }
@@ -170,7 +212,7 @@ int sro_humliv_bb(const double *x, int i1, int i2, double x0, double lw,
     j = i2;
     rx = (x0 - X(j)) / dw;
     while ((rx + ry < tst) && (j >= i1)) {
-      Y(j) = core_point(rx, ry);
+      Y(j) = core_point(rx, ry, smooth);
       j = j - 1;
       rx = rx + xstep;
     }
@@ -199,13 +241,10 @@ int sro_humliv_bb(const double *x, int i1, int i2, double x0, double lw,
       }
     }
   } else { /* x(i1) < x0 < x(i2), lineshape.f:443-562 */
-    rx = (x0 - X(i1)) / dw;
-    tst = 15.;
-    il = i1;
-    if (rx + ry >= tst) il = lmax(nintl((rx - ry - tst) / xstep), 0) + i1;
-    rx = (X(i2) - x0) / dw;
-    ir = i2;
-    if (rx + ry >= tst) ir = i2 - lmax(nintl((rx - ry - tst) / xstep), 0);
+    /* :444-454, 480-490 at the boundary widths; the fills below at the call's */
+    const mid_bounds b = middle_bounds(x, i1, i2, x0, lw_b, dw_b);
+    const double ry_b = lw_b / dw_b;
+    il = b.il; ir = b.ir; il2 = b.il2; ir2 = b.ir2;
     if (il > i1 || ir < i2) {
       r1coef q = region1_coef(ry, ry2);
       if (il > i1) {
@@ -225,13 +264,6 @@ int sro_humliv_bb(const double *x, int i1, int i2, double x0, double lw,
         }
       }
     }
-    rx = (x0 - X(il)) / dw;
-    tst = 5.5;
-    il2 = il;
-    if (rx + ry >= tst) il2 = il + lmax(nintl((rx - ry - tst) / xstep), 0);
-    ir2 = ir;
-    rx = (X(ir) - x0) / dw;
-    if (rx + ry >= tst) ir2 = ir - lmax(nintl((rx - ry - tst) / xstep), 0);
     if (il2 > il || ir2 < ir) {
       r2coef q = region2_coef(ry, ry2);
       if (il < il2) {
@@ -255,9 +287,41 @@ int sro_humliv_bb(const double *x, int i1, int i2, double x0, double lw,
     if (ir2 == ir) ir2 = ir + 1;
     for (j = il2 + 1; j <= ir2 - 1; j++) {
       rx = fabs(X(j) - x0) / dw;
-      Y(j) = core_point(rx, ry);
+      Y(j) = core_value(rx, ry, core_is_region4(fabs(X(j) - x0) / dw_b, ry_b), smooth);
     }
   }
+  return 0;
+}
+
+int sro_humliv_bb(const double *x, int i1, int i2, double x0, double lw,
+                  double dw, double *y) {
+  return humliv_impl(x, i1, i2, x0, lw, dw, lw, dw, 0, y);
+}
+
+int sro_humliv_bb_bounds(const double *x, int i1, int i2, double x0, double lw,
+                         double dw, double lw_b, double dw_b, int flags,
+                         double *y) {
+  return humliv_impl(x, i1, i2, x0, lw, dw, lw_b, dw_b, flags & 1, y);
+}
+
+int sro_humliv_bounds(const double *x, int i1, int i2, double x0, double lw,
+                      double dw, long out6[6]) {
+  for (int q = 0; q < 6; q++) out6[q] = 0;
+  if (i1 > i2) return -1;
+  if (!(dw > 0.0)) return -2;
+  if (x0 <= X(i1) || x0 >= X(i2)) return 1; /* a sequential branch: no boundaries */
+  const mid_bounds b = middle_bounds(x, i1, i2, x0, lw, dw);
+  const double ry = lw / dw;
+  long il2 = b.il2, ir2 = b.ir2, k3lo = 1, k3hi = 0;
+  if (il2 == b.il) il2 = b.il - 1; /* :524-525 */
+  if (ir2 == b.ir) ir2 = b.ir + 1;
+  for (long j = il2 + 1; j <= ir2 - 1; j++)
+    if (!core_is_region4(fabs(X(j) - x0) / dw, ry)) {
+      if (k3lo > k3hi) k3lo = j;
+      k3hi = j;
+    }
+  out6[0] = b.il; out6[1] = b.ir; out6[2] = b.il2; out6[3] = b.ir2;
+  out6[4] = k3lo; out6[5] = k3hi;
   return 0;
 }
 
@@ -336,6 +400,18 @@ int sro_make_shape(const double *xwin, int n, double wn0, double lw, double dw,
                    double *shape) {
   double fac = dw * sqrt(SRO_PI / log(2.0));
   int rc = sro_humliv_bb(xwin, 1, n, wn0, lw, dw / sqrt(log(2.0)), shape);
+  if (rc) return rc;
+  for (int i = 0; i < n; i++) shape[i] = 1.0 * shape[i] / fac;
+  return 0;
+}
+
+/* make_shape with the boundaries placed at the widths (lw_b, dw_b) */
+int sro_make_shape_bounds(const double *xwin, int n, double wn0, double lw,
+                          double dw, double lw_b, double dw_b, int flags,
+                          double *shape) {
+  double fac = dw * sqrt(SRO_PI / log(2.0));
+  int rc = sro_humliv_bb_bounds(xwin, 1, n, wn0, lw, dw / sqrt(log(2.0)), lw_b,
+                                dw_b / sqrt(log(2.0)), flags, shape);
   if (rc) return rc;
   for (int i = 0; i < n; i++) shape[i] = 1.0 * shape[i] / fac;
   return 0;

@@ -38,6 +38,29 @@ double sro_c2(void);
 int sro_humliv_bb(const double *x, int i1, int i2, double x0, double lw,
                   double dw, double *y);
 
+/* humliv_bb with its region boundaries placed at OTHER widths: the reference of the product's frozen boundaries
+ * (include/spectrobot_hip.h, sr_lineset_set_bounds_temps; build's own definition, the reference has none).
+ * Middle branch (x(i1) < x0 < x(i2), lineshape.f:443-562): il, ir, il2, ir2 are computed as there but from
+ * (lw_b, dw_b) -- ry_b = lw_b / dw_b, xstep_b and every rx of :444-490 with dw_b -- and a core point is region 3 or 4
+ * by the reference's own test (:528) on rx_b = |x(j) - x0| / dw_b and ry_b.  Every VALUE is computed with (lw, dw):
+ * ry, xstep, the running-x starts at the frozen indices ((x0 - x(i1)) / dw, (x(ir) - x0) / dw, (x0 - x(il)) / dw,
+ * (x(ir2) - x0) / dw) and the core's rx = |x(j) - x0| / dw.
+ * The sequential branches (x0 <= x(i1) or x0 >= x(i2), :272-442) freeze NOTHING: they walk with (lw, dw) alone, as
+ * the product's outer-line kernel does (it has no frozen path either); lw_b, dw_b are not read there.
+ * flags & 1 ("smooth"): cmplx(ry, -rx) keeps both parts in double -- the two single-precision casts of :529 (and
+ * :277, :363) are dropped and nothing else; the polynomial literals stay single.  A function of the widths without
+ * the 1e-7 staircase of the casts, for derivatives by difference.
+ * With lw_b == lw, dw_b == dw and flags == 0 it is sro_humliv_bb bit for bit (one body serves both). */
+int sro_humliv_bb_bounds(const double *x, int i1, int i2, double x0, double lw,
+                         double dw, double lw_b, double dw_b, int flags,
+                         double *y);
+
+/* The boundaries of the middle branch at (lw, dw): out6 = il, ir, il2, ir2 (as :443-490 compute them, before
+ * :524-525) and k3lo, k3hi, the first and last core index whose point the test of :528 puts in region 3
+ * (k3lo > k3hi: none).  Returns 0; 1 for a sequential branch (out6 zeroed: no boundaries); -1 / -2 as sro_humliv_bb. */
+int sro_humliv_bounds(const double *x, int i1, int i2, double x0, double lw, double dw,
+                      long out6[6]);
+
 /* lineshape.f:150-205  scalar humli_bb (cross-check only). */
 double sro_humli_bb(double rx, double ry);
 
@@ -56,6 +79,12 @@ double sro_doppler_width(double temp, double mm, double wn0);
 /* spect_classes.py:1990-2008 MakeShape on a 13010-point window. */
 int sro_make_shape(const double *xwin, int n, double wn0, double lw, double dw,
                    double *shape);
+
+/* sro_make_shape through sro_humliv_bb_bounds: boundaries at the widths (lw_b, dw_b) (dw_b a Doppler HWHM like dw:
+ * divided by sqrt(ln 2) here too), values and the normalisation fac at (lw, dw); flags as there. */
+int sro_make_shape_bounds(const double *xwin, int n, double wn0, double lw,
+                          double dw, double lw_b, double dw_b, int flags,
+                          double *shape);
 
 /* spect_classes.py:1937-1943 closest_grid (first arg-min). */
 long sro_closest_grid(const double *grid, long n_grid, double wn0);

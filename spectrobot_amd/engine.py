@@ -495,9 +495,11 @@ class LevelFactored(object):
         """dT: also build the tables at T + dT for the temperature derivative of `steps` -- region boundaries frozen at
         T and (linear_weights, default) the line weights linearised about T, so that (A(T + dT) - A(T)) / dT is
         sum_i w_i' y_i(T + dT) + sum_i w_i (y_i(T + dT) - y_i(T)) / dT: the weights' part exact, only the shapes
-        differenced -- their dependence on T is weak (d ln y / d T ~ 1 / 2T) and smooth, so dT = 0.05 K carries
-        1.5e-4 of truncation where the exact-weight quotient needed 0.002 K and sat on the reference's
-        single-precision staircase (1e-7 |c| / dT = 1e-3 of the derivative)."""
+        differenced -- their dependence on T is weak (d ln y / d T ~ 1 / 2T; ~ n / T where the Lorentz width decides) and
+        smooth, so dT = 0.05 K carries 1e-4 (Doppler layers) to 3.5e-4 (Lorentz layers, 80 hPa and more) of truncation
+        (tests/test_frozen_reference_host.py, against a smooth derivative of the CPU reference) where the exact-weight
+        quotient needed 0.002 K and sat on the reference's single-precision staircase (1e-7 |c| / dT = 1e-3 of the
+        derivative)."""
         self.ls = ls
         self.dT = dT
         self._shard, self._linear = (g_lo, g_hi), linear_weights
@@ -1659,10 +1661,12 @@ def coefficients_dT(ls, temps, press, tvib=None, q_part=None, g_lo=0, g_hi=None,
     ~1e-7 |c| / dT in any quotient -- which is what bounds dT from below.
       scheme "central" (default, THREE coefficient ops): (c(T + dT) - c(T - dT)) / 2 dT, dT = 0.05 K: ~3e-5 of a
         layer's largest derivative (2e-4 with moving boundaries, frozen=False: rounds 1-3's definition).
-      scheme "forward" (TWO ops): (c(T + dT) - c(T)) / dT, dT = 0.002 K: ~5e-4 (truncation dT/2 |c''|, with c'' / c'
-        up to 0.3 / K from level populations and Doppler cores, against the staircase noise): good for a
-        Gauss-Newton step, a third cheaper.
-    tests/test_gpu_configs.py::test_temperature_derivative_schemes measures the three against each other."""
+      scheme "forward" (TWO ops): (c(T + dT) - c(T)) / dT, dT = 0.002 K: ~3e-4, and 1.5e-3 for the emission coefficient
+        of a Doppler layer (truncation dT/2 |c''|, with c'' / c' up to 0.3 / K from level populations and Doppler
+        cores, against the staircase noise): good for a Gauss-Newton step, a third cheaper.
+    tests/test_gpu_configs.py::test_temperature_derivative_schemes measures the three against each other;
+    tests/test_frozen_reference_host.py measures the frozen two against a smooth, extrapolated derivative of the CPU
+    reference (central 1.1e-5 abs | 2.5e-5 emi, forward 3.4e-4 | 1.5e-3 at the worst of four layers, 1e-3 to 1013 hPa)."""
     temps = np.ascontiguousarray(temps, dtype=np.float64)
     kw = dict(tvib=tvib, q_part=q_part, g_lo=g_lo, g_hi=g_hi)
     if scheme not in ("forward", "central"):
