@@ -862,6 +862,42 @@ int sr_hires_to_lowres_instr_shard_dev(const double *rad, int n_rays, int64_t n_
                                        const double *centers_nm, const double *widths_nm, int n_bands, double n_sigma,
                                        int out_units, double *out_host, void *stream);
 
+/* A TABULATED instrument line shape for every band integral of the calling thread.  The instrument model above is a
+ * Gaussian of width w_b around f_b, cut at +-n_sigma; a measured response (an asymmetric grating channel, the lobes of an
+ * FTS with their negative wings) is given as n_tab knots phi_k at the uniformly spaced REDUCED offsets
+ * t_k = t_lo + k h, h = (t_hi - t_lo) / (n_tab - 1), t = (x - f_b) / w_b: one table for all bands (n_shapes = 1) or one per
+ * band (n_shapes = n_bands of the calls that follow, table b for band b).  phi^ is the cubic Hermite interpolant of the
+ * knots -- slopes (phi_(k+1) - phi_(k-1)) / (2 h) inside, the one-sided differences at the two ends; C1 inside
+ * [t_lo, t_hi], identically 0 outside; t = t_hi is the last knot.  With p_i = g_i^2 1e-7 c_i (c_i the trapezoid interval
+ * weights) over the window f_b + t_lo w_b <= x_i <= f_b + t_hi w_b (decided on the fp64 nm values; n_sigma is not used,
+ * but still checked to be > 0):
+ *   value:                 W_i   =  p_i phi^(t_i) / w
+ *   d / d centre (per nm): W^f_i = -p_i phi^'(t_i) / w^2
+ *   d / d ln width:        W^w_i = -p_i (phi^(t_i) + t_i phi^'(t_i)) / w
+ * the window's membership held fixed (a jump at an end is phi^ at the table's end: keep it small).  For
+ * phi = exp(-t^2 / 2) / sqrt(2 pi) these are the Gaussian's three tables.  The values are used AS GIVEN: the library does
+ * not normalise (sr_ils_area gives the interpolant's exact integral to divide by).  Everything that reads the weight table
+ * -- sr_hires_to_lowres[_shard|_instr_shard]_dev, sr_retrieval_forward / _step / _loop_dev, the
+ * sr_limb_rays_state_bands*_dev entries and the recursion kernel's band epilogue -- then integrates with this shape;
+ * their signatures, units, shards and layouts are unchanged.
+ * sr_set_ils copies the table (phi: HOST [n_shapes][n_tab]); it is scoped to the calling thread and costs no launch: the
+ * next band call rebuilds its weight table (the binding is part of the table's key).  NULL: the Gaussian again, as the
+ * library always was.  SR_ERR_ARG for a NULL phi, n_tab < 4, n_shapes < 1, t_lo >= t_hi or not finite, a knot that is
+ * not finite; SR_ERR_LIMIT for n_tab > SR_MAX_ILS_TAB; a refused descriptor leaves the binding as it was.  A band call
+ * whose n_bands matches neither n_shapes == 1 nor n_shapes == n_bands returns SR_ERR_ARG before its first copy or launch.
+ * Checked against an extended-precision reference (tests/test_gpu_ils.py). */
+#define SR_MAX_ILS_TAB 65536
+typedef struct sr_ils_desc {
+  int32_t n_shapes;   /* 1, or n_bands of the calls that follow */
+  int32_t n_tab;      /* 4 .. SR_MAX_ILS_TAB */
+  double t_lo, t_hi;  /* t_lo < t_hi, finite */
+  const double *phi;  /* HOST [n_shapes][n_tab], finite; copied by the call */
+} sr_ils_desc;
+int sr_set_ils(const sr_ils_desc *ils);
+/* area: HOST [n_shapes], the exact integral over t of each table's interpolant,
+ * sum_k h (phi_k + phi_(k+1)) / 2 + h^2 (m_k - m_(k+1)) / 12.  Refusals as sr_set_ils (and a NULL argument). */
+int sr_ils_area(const sr_ils_desc *ils, double *area);
+
 /* Evaluation mode of the coefficient op.  Far region-1 wings by local Taylor expansions per box of grid
  * points (truncation <= sr_far_field_truncation_bound() of a line's own contribution: 1.6e-11 as built by default, degree
  * 19; 2.6e-13 with -DSR_KFD=22; a box takes a line from sr_far_field_min_distance() on), near field exact, with the expansions built

@@ -18,6 +18,7 @@ SR_OK = 0
 SR_ERR_ARG, SR_ERR_LIMIT, SR_ERR_HIP, SR_ERR_NODEVICE, SR_ERR_UNSUPPORTED, SR_ERR_TABLE = -1, -2, -3, -4, -5, -6
 IMXSIG = 13010
 SR_STRENGTH_EINSTEIN, SR_STRENGTH_HITRAN = 0, 1
+SR_MAX_ILS_TAB = 65536
 
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int32)
@@ -75,6 +76,10 @@ class LevelGasDesc(C.Structure):
 
 class LosPath(C.Structure):
     _fields_ = [("alt", dp), ("dx_dz", dp), ("dalt_dz", dp)]
+
+
+class IlsDesc(C.Structure):
+    _fields_ = [("n_shapes", C.c_int32), ("n_tab", C.c_int32), ("t_lo", C.c_double), ("t_hi", C.c_double), ("phi", dp)]
 
 
 # every symbol include/spectrobot_hip.h declares: (restype, argtypes)
@@ -195,6 +200,8 @@ SYMBOLS = {
                                                C.c_int, C.c_double, C.c_int, dp, C.c_void_p]),
     "sr_hires_to_lowres_instr_shard_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, dp, dp,
                                                      C.c_int, C.c_double, C.c_int, dp, C.c_void_p]),
+    "sr_set_ils": (C.c_int, [C.POINTER(IlsDesc)]),
+    "sr_ils_area": (C.c_int, [C.POINTER(IlsDesc), dp]),
     "sr_set_points_per_lane": (C.c_int, [C.c_int]),
     "sr_set_band_fusion": (C.c_int, [C.c_int]),
     "sr_far_field_truncation_bound": (C.c_double, []),

@@ -2646,13 +2646,50 @@ struct LowresState {
   unsigned gen = 0;
   int dev = -1;
   std::vector<double> bands;
+  bool ils = false;       // the table was made from a tabulated line shape: that binding's generation and shape
+  unsigned ils_gen = 0;
+  int ils_shapes = 0, ils_tab = 0;
+  double ils_lo = 0, ils_hi = 0;
 };
 static thread_local LowresState t_lowres;
+
+// The calling thread's instrument line shape (sr_set_ils): off -- the Gaussian over +-n_sigma widths, as the library always
+// was -- or a table of knots.  tab [n_shapes][n_tab][2]: knot k and its slope per knot interval (the central difference
+// (phi_(k+1) - phi_(k-1)) / 2 inside, the one-sided difference at the two ends: h times the slopes of the cubic Hermite
+// interpolant), formed here once in fp64, as sr_lowres_weights_tab_kernel reads them.  gen: a new value with every
+// binding, part of the weight table's key (the same bands under another shape are another table).
+struct IlsState {
+  bool on = false;
+  int n_shapes = 0, n_tab = 0;
+  double t_lo = 0, t_hi = 0;
+  unsigned gen = 0;
+  std::vector<double> tab;
+};
+static thread_local IlsState t_ils;
+static void ils_slopes(const double *phi, int n_tab, double *knots_slopes) {
+  for (int k = 0; k < n_tab; ++k) {
+    knots_slopes[2 * k] = phi[k];
+    knots_slopes[2 * k + 1] = k == 0 ? phi[1] - phi[0] : k == n_tab - 1 ? phi[k] - phi[k - 1] : (phi[k + 1] - phi[k - 1]) / 2.0;
+  }
+}
+static int ils_check(const sr_ils_desc *ils) {
+  if (!ils->phi || ils->n_shapes < 1 || ils->n_tab < 4) return SR_ERR_ARG;
+  if (ils->n_tab > SR_MAX_ILS_TAB) return SR_ERR_LIMIT;
+  if (!std::isfinite(ils->t_lo) || !std::isfinite(ils->t_hi) || !(ils->t_lo < ils->t_hi)) return SR_ERR_ARG;
+  if ((size_t)ils->n_shapes > ((size_t)1 << 28) / (size_t)ils->n_tab) return SR_ERR_LIMIT;
+  for (size_t k = 0; k < (size_t)ils->n_shapes * ils->n_tab; ++k)
+    if (!std::isfinite(ils->phi[k])) return SR_ERR_ARG;
+  return SR_OK;
+}
 
 // The instrument step's arguments (on their own for sr_retrieval_forward_dev, which checks before it touches its handle)
 static int lowres_check(int n_rows, int64_t n_pts, int64_t g_lo, double w0, double step, const double *centers_nm,
                         const double *widths_nm, int n_bands, double n_sigma, int out_units) {
   if (!centers_nm || !widths_nm || n_rows <= 0 || n_pts < 2 || n_bands <= 0 || g_lo < 0) return SR_ERR_ARG;
+  if (t_ils.on && t_ils.n_shapes != 1 && t_ils.n_shapes != n_bands) { // a table per band, and not this many bands
+    g_err = "the bound line shape has " + std::to_string(t_ils.n_shapes) + " tables, the call " + std::to_string(n_bands) + " bands";
+    return SR_ERR_ARG;
+  }
   if (g_lo + n_pts > 2000000) return SR_ERR_LIMIT;
   if (!(step > 0.0) || !(w0 > 0.0) || !(n_sigma > 0.0) || out_units < 0 || out_units > 2) return SR_ERR_ARG;
   for (int b = 0; b < n_bands; ++b)
@@ -2662,6 +2699,8 @@ static int lowres_check(int n_rows, int64_t n_pts, int64_t g_lo, double w0, doub
 // Arguments checked, buffers for n_rows spectra in place, the weight table valid on `st` (its kernel launched there when
 // the key changed: *fresh).  fused: partial sums per 64-point slot (launch_fold_dense with the scratch).  instr: the
 // tables of the two instrument derivatives too (n_rows counts their rows); part of the key, the layouts differ.
+// The one place that reads the thread's line shape (sr_set_ils): a table travels up with the bands, picks
+// sr_lowres_weights_tab_kernel and joins the key with its generation and shape.
 static int lowres_prepare(int n_rows, int64_t n_pts, int64_t g_lo, double w0, double step, const double *centers_nm,
                           const double *widths_nm, int n_bands, double n_sigma, int out_units, bool fused, hipStream_t st,
                           bool *fresh, bool instr = false) {
@@ -2681,21 +2720,32 @@ static int lowres_prepare(int n_rows, int64_t n_pts, int64_t g_lo, double w0, do
   if (rc) return rc;
   rc = L.d_weights.ensure(lowres_scratch_bytes((int)n_pts, n_bands, n_rows, fused, instr));
   if (rc) return rc;
-  const bool same = L.valid && L.instr == instr && L.gen == L.d_weights.gen && L.n_pts == n_pts && L.g_lo == g_lo && L.w0 == w0 && L.step == step &&
+  const IlsState &I = t_ils;
+  const bool same_ils = L.ils == I.on && (!I.on || (L.ils_gen == I.gen && L.ils_shapes == I.n_shapes && L.ils_tab == I.n_tab &&
+                                                    L.ils_lo == I.t_lo && L.ils_hi == I.t_hi));
+  const bool same = L.valid && same_ils && L.instr == instr && L.gen == L.d_weights.gen && L.n_pts == n_pts && L.g_lo == g_lo && L.w0 == w0 && L.step == step &&
                     L.n_sigma == n_sigma && L.bands.size() == 2 * nb &&
                     std::memcmp(L.bands.data(), centers_nm, sizeof(double) * nb) == 0 &&
                     std::memcmp(L.bands.data() + nb, widths_nm, sizeof(double) * nb) == 0;
   *fresh = !same;
   if (same) return SR_OK;
   L.valid = false; // (until the launch below has been issued)
-  rc = L.s_bands.prepare(sizeof(double) * 2 * nb);
+  const size_t n_up = 2 * nb + (I.on ? I.tab.size() : 0); // centres, widths, then the table
+  rc = L.s_bands.prepare(sizeof(double) * n_up);
   if (rc) return rc;
   std::memcpy(L.s_bands.host<double>(), centers_nm, sizeof(double) * nb);
   std::memcpy(L.s_bands.host<double>() + nb, widths_nm, sizeof(double) * nb);
-  rc = L.s_bands.push(sizeof(double) * 2 * nb, st);
+  if (I.on) std::memcpy(L.s_bands.host<double>() + 2 * nb, I.tab.data(), sizeof(double) * I.tab.size());
+  rc = L.s_bands.push(sizeof(double) * n_up, st);
   if (rc) return rc;
-  LAUNCHCHK(launch_lowres_weights((int)n_pts, (int)g_lo, w0, step, L.s_bands.d.as<double>(), L.s_bands.d.as<double>() + nb, n_bands,
-                                  n_sigma, L.d_weights.p, st, instr));
+  if (I.on)
+    LAUNCHCHK(launch_lowres_weights_tab((int)n_pts, (int)g_lo, w0, step, L.s_bands.d.as<double>(), L.s_bands.d.as<double>() + nb,
+                                        n_bands, L.s_bands.d.as<double>() + 2 * nb, I.n_shapes, I.n_tab, I.t_lo, I.t_hi,
+                                        L.d_weights.p, st, instr));
+  else
+    LAUNCHCHK(launch_lowres_weights((int)n_pts, (int)g_lo, w0, step, L.s_bands.d.as<double>(), L.s_bands.d.as<double>() + nb, n_bands,
+                                    n_sigma, L.d_weights.p, st, instr));
+  L.ils = I.on; L.ils_gen = I.gen; L.ils_shapes = I.n_shapes; L.ils_tab = I.n_tab; L.ils_lo = I.t_lo; L.ils_hi = I.t_hi;
   L.instr = instr;
   L.n_pts = n_pts; L.g_lo = g_lo; L.w0 = w0; L.step = step; L.n_sigma = n_sigma;
   L.bands.assign(centers_nm, centers_nm + nb);
@@ -4135,6 +4185,45 @@ int sr_hires_to_lowres_instr_shard_dev(const double *rad, int n_rays, int64_t n_
   LowresState &L = t_lowres;
   LAUNCHCHK(launch_lowres_instr(rad, (int)n_pts, n_rays, n_bands, out_units, L.d_out.as<double>(), L.d_weights.p, st));
   return lowres_land(3 * n_rays, n_bands, out_host, st);
+}
+
+// The calling thread's instrument line shape: a table of knots (copied here, with its slopes formed once) or, with NULL, the
+// Gaussian.  No device call: the next band call's lowres_prepare sends the table up with its bands.  A refused descriptor
+// leaves the binding as it was.
+int sr_set_ils(const sr_ils_desc *ils) {
+  IlsState &I = t_ils;
+  if (ils) {
+    const int rc = ils_check(ils);
+    if (rc) return rc;
+    std::vector<double> tab(2 * (size_t)ils->n_shapes * ils->n_tab);
+    for (int q = 0; q < ils->n_shapes; ++q) ils_slopes(ils->phi + (size_t)q * ils->n_tab, ils->n_tab, tab.data() + 2 * (size_t)q * ils->n_tab);
+    I.tab.swap(tab);
+    I.n_shapes = ils->n_shapes; I.n_tab = ils->n_tab; I.t_lo = ils->t_lo; I.t_hi = ils->t_hi;
+  } else {
+    std::vector<double>().swap(I.tab);
+    I.n_shapes = I.n_tab = 0; I.t_lo = I.t_hi = 0.0;
+  }
+  I.on = ils != nullptr;
+  ++I.gen;
+  return SR_OK;
+}
+
+// The exact integral over t of every table's interpolant: on an interval the cubic Hermite integrates to
+// h (phi_k + phi_(k+1)) / 2 + h^2 (m_k - m_(k+1)) / 12; with d = h m the sum is h (trapezoids + (d_0 - d_(n-1)) / 12).
+int sr_ils_area(const sr_ils_desc *ils, double *area) {
+  if (!ils || !area) return SR_ERR_ARG;
+  const int rc = ils_check(ils);
+  if (rc) return rc;
+  const int n = ils->n_tab;
+  const double h = (ils->t_hi - ils->t_lo) / (double)(n - 1);
+  for (int q = 0; q < ils->n_shapes; ++q) {
+    const double *phi = ils->phi + (size_t)q * n;
+    double sum = 0.0;
+    for (int k = 0; k + 1 < n; ++k) sum += (phi[k] + phi[k + 1]) / 2.0;
+    sum += ((phi[1] - phi[0]) - (phi[n - 1] - phi[n - 2])) / 12.0;
+    area[q] = h * sum;
+  }
+  return SR_OK;
 }
 
 // ------------------------------------------------------------------------

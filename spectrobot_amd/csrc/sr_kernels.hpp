@@ -447,6 +447,11 @@ int launch_sum_lines(double *spe, long n_spe, const double *rows, const int *ini
 size_t lowres_scratch_bytes(int n_pts, int n_bands, int n_rays, bool fused = false, bool instr = false);
 int launch_lowres_weights(int n_pts, int g_lo, double w0, double gstep, const double *cen, const double *wid, int n_bands,
                           double n_sigma, void *scratch, hipStream_t st, bool instr = false);
+// launch_lowres_weights for a tabulated line shape (sr_lowres_weights_tab_kernel): tab, device [n_shapes][n_tab][2], the
+// knots with their slopes per knot interval at the reduced offsets t_lo .. t_hi; n_shapes 1 or n_bands
+int launch_lowres_weights_tab(int n_pts, int g_lo, double w0, double gstep, const double *cen, const double *wid, int n_bands,
+                              const double *tab, int n_shapes, int n_tab, double t_lo, double t_hi, void *scratch, hipStream_t st,
+                              bool instr = false);
 int launch_lowres_sum_blocks(int n_pts, int n_rows, int n_bands, int out_units, double *out, void *scratch, hipStream_t st,
                              bool instr = false);
 int launch_lowres_instr(const double *rad, int n_pts, int n_rays, int n_bands, int out_units, double *out, void *scratch,

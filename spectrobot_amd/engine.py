@@ -598,18 +598,19 @@ class LevelFactored(object):
 
     def state_bands(self, coeffs, los, step_row, tvib, par_level, par_w_level, grid, centers_nm, widths_nm, par_gas=None,
                     par_w_col=None, gas=0, q_part=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None,
-                    instrument=False, pointing=False):
+                    instrument=False, pointing=False, ils=None):
         """state_jacobian on the instrument's bands in one library call (limb_rays_state_bands): numpy [n_rays | n_rays / 3,
         1 + n_par, n_bands], row 0 the radiance, row 1 + p the derivative to parameter p (VMR-profile, vibrational-
         temperature, kinetic-temperature parameters, as state_jacobian orders them); no hi-res spectrum is written.  The
         parameters' arguments and their errors are state_jacobian's; the bands' (and fov) those of limb_rays_state_bands.
         Honours the object's spectral shard: partial band integrals then (`grid` is the whole grid).  instrument=True: the
-        two instrument rows behind the parameters' (limb_rays_state_bands); pointing=True: the pointing row in front of them."""
+        two instrument rows behind the parameters' (limb_rays_state_bands); pointing=True: the pointing row in front of them.
+        ils: an ILS, the bands' tabulated line shape."""
         step_row, par_level, par_c = self._state_level_args(step_row, tvib, par_level, par_w_level, q_part)
         return limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=par_gas, par_w=par_w_col, tab=self.tab,
                                      coef_row=step_row, par_level=par_level, par_c=par_c, gas=gas, dcoeffs=dcoeffs,
                                      par_t=par_w_temp, out_units=out_units, n_sigma=n_sigma, fov=fov,
-                                     g_lo=int(self._shard[0]), instrument=instrument, **_pointing_kw(pointing))
+                                     g_lo=int(self._shard[0]), instrument=instrument, ils=ils, **_pointing_kw(pointing))
 
     def level_radiances(self, coeffs, los, step_row, tvib, levels=None, weights=None, gas=0, q_part=None, grid=None,
                         gas_parts=True):
@@ -694,15 +695,15 @@ class LevelFactoredSet(object):
 
     def state_bands(self, coeffs, los, par_lgas, par_level, par_w_level, grid, centers_nm, widths_nm, par_gas=None,
                     par_w_col=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None, instrument=False,
-                    pointing=False):
+                    pointing=False, ils=None):
         """LevelFactored.state_bands for the members' vibrational-temperature parameters together: numpy [n_rays | n_rays / 3,
         1 + n_par, n_bands]; instrument=True: [.., 1 + n_par + 2, n_bands], the two instrument rows last; pointing=True:
-        the pointing row behind the parameters'."""
+        the pointing row behind the parameters'; ils: an ILS, the bands' tabulated line shape."""
         gases, par_lgas, par_level, par_c = self._args(par_lgas, par_level, par_w_level)
         return limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=par_gas, par_w=par_w_col,
                                      par_level=par_level, par_c=par_c, dcoeffs=dcoeffs, par_t=par_w_temp, out_units=out_units,
                                      n_sigma=n_sigma, fov=fov, g_lo=int(self.members[0][0]._shard[0]), level_gases=gases,
-                                     par_lgas=par_lgas, instrument=instrument, **_pointing_kw(pointing))
+                                     par_lgas=par_lgas, instrument=instrument, ils=ils, **_pointing_kw(pointing))
 
 
 def level_node_weights(nodes, alt):
@@ -1037,14 +1038,15 @@ def fov_factors(pixel_rot):
 
 
 def retrieval_forward(coeffs, los, par_gas, par_w, x, grid, centers_nm, widths_nm, out_units="Wm2", n_sigma=5.0, g_lo=0,
-                      fov=None, buf=None):
+                      fov=None, buf=None, ils=None):
     """The forward model of one retrieval iteration in ONE library call (sr_retrieval_forward_dev) on the batch's
     device-resident form with these parameter arrays (LimbLOS.handle_par): parameter vector x -> VMRs of the retrieved
     gases at the sample points -> columns -> radiances and parameter Jacobians -> instrument bands -> (fov: fov_factors
     of the pixels, three rays each) the closed-form field-of-view integral.  Returns numpy [n_pix or n_rays, 1 + n_par,
     n_bands]: row 0 the radiance, row 1 + p its derivative to x_p; a spectral shard (g_lo, the coefficient tables'
     width) gives its partial band integrals.  The batch's host copy of the VMRs (los.vmr) is NOT updated: call
-    los.set_vmr when the loop ends.  buf: scratch from an earlier call (returned as second value)."""
+    los.set_vmr when the loop ends.  buf: scratch from an earlier call (returned as second value).  ils: an ILS, the
+    bands' tabulated line shape (as hires_to_lowres)."""
     a, e = _gas_stack(coeffs)
     n_gas, n_layers, n_pts = a.shape
     w0, step, n = grid_params(grid)
@@ -1069,9 +1071,10 @@ def retrieval_forward(coeffs, los, par_gas, par_w, x, grid, centers_nm, widths_n
     if buf is None or buf.shape != (los.n_rays * (1 + n_par), n_pts):
         buf = torch.empty((los.n_rays * (1 + n_par), n_pts), dtype=torch.float64, device="cuda")
     out = np.empty((n_out, 1 + n_par, centers_nm.size))
-    check(lib.sr_retrieval_forward_dev(a.data_ptr(), e.data_ptr(), n_layers, n_pts, h, int(g_lo), xp, w0, step, cp, wp,
-                                       centers_nm.size, float(n_sigma), _UNITS[out_units], fp, buf.data_ptr(),
-                                       out.ctypes.data_as(dp), _stream_ptr()), "sr_retrieval_forward_dev")
+    with _IlsBound(ils):
+        check(lib.sr_retrieval_forward_dev(a.data_ptr(), e.data_ptr(), n_layers, n_pts, h, int(g_lo), xp, w0, step, cp, wp,
+                                           centers_nm.size, float(n_sigma), _UNITS[out_units], fp, buf.data_ptr(),
+                                           out.ctypes.data_as(dp), _stream_ptr()), "sr_retrieval_forward_dev")
     return out, buf
 
 
@@ -1096,12 +1099,12 @@ class OeProblem(object):
 
 
 def retrieval_step(coeffs, los, par_gas, par_w, x, grid, centers_nm, widths_nm, oe, out_units="Wm2", n_sigma=5.0, fov=None,
-                   buf=None):
+                   buf=None, ils=None):
     """retrieval_forward + the rest of the iteration in the same library call (sr_retrieval_step_dev): chi square of the
     pixels against the observations and the Levenberg-Marquardt step of the optimal-estimation algebra
     (spect_main_module.inversion_algebra) on the band spectra and Jacobians the call brings to the host.  oe: OeProblem.
     Returns (out [n_pix, 1 + n_par, n_bands], chi_sum, n_used, dx [n_par], S_x, AVK [n_par, n_par], buf).  Single process
-    only (a shard's band integrals are partial)."""
+    only (a shard's band integrals are partial).  ils: as retrieval_forward."""
     a, e = _gas_stack(coeffs)
     n_gas, n_layers, n_pts = a.shape
     w0, step, n = grid_params(grid)
@@ -1125,20 +1128,22 @@ def retrieval_step(coeffs, los, par_gas, par_w, x, grid, centers_nm, widths_nm, 
     out = np.empty((n_pix, 1 + n_par, centers_nm.size))
     chi, n_used = C.c_double(0.0), C.c_int32(0)
     dx, s_x, avk = np.empty(n_par), np.empty((n_par, n_par)), np.empty((n_par, n_par))
-    check(lib.sr_retrieval_step_dev(a.data_ptr(), e.data_ptr(), n_layers, n_pts, h, 0, xp, w0, step, cp, wp, centers_nm.size,
-                                    float(n_sigma), _UNITS[out_units], fp, buf.data_ptr(), out.ctypes.data_as(dp), C.byref(oe.desc),
-                                    C.byref(chi), C.byref(n_used), dx.ctypes.data_as(dp), s_x.ctypes.data_as(dp),
-                                    avk.ctypes.data_as(dp), _stream_ptr()), "sr_retrieval_step_dev")
+    with _IlsBound(ils):
+        check(lib.sr_retrieval_step_dev(a.data_ptr(), e.data_ptr(), n_layers, n_pts, h, 0, xp, w0, step, cp, wp, centers_nm.size,
+                                        float(n_sigma), _UNITS[out_units], fp, buf.data_ptr(), out.ctypes.data_as(dp),
+                                        C.byref(oe.desc), C.byref(chi), C.byref(n_used), dx.ctypes.data_as(dp),
+                                        s_x.ctypes.data_as(dp), avk.ctypes.data_as(dp), _stream_ptr()), "sr_retrieval_step_dev")
     return out, chi.value, n_used.value, dx, s_x, avk, buf
 
 
 def retrieval_loop(coeffs, los, par_gas, par_w, x0, grid, centers_nm, widths_nm, oe, positive, n_dof_par, chi_threshold=0.01,
-                   max_it=10, out_units="Wm2", n_sigma=5.0, fov=None, buf=None):
+                   max_it=10, out_units="Wm2", n_sigma=5.0, fov=None, buf=None, ils=None):
     """The whole loop of a retrieval whose coefficient spectra stay fixed, in one library call (sr_retrieval_loop_dev):
     retrieval_step per iteration, reduced chi square, the stopping rule and the update with the positivity rule of
     spect_main_module.inversion_fast_limb.  positive [n_par] bool: constrain_positive of every parameter; n_dof_par: the
     parameters in use.  Returns (out of the last iteration [n_pix, 1 + n_par, n_bands], chi history [n_it], x history
-    [n_updates + 1, n_par], stop '' | 'converged' | 'raised', S_x, AVK (None when no update was applied), buf)."""
+    [n_updates + 1, n_par], stop '' | 'converged' | 'raised', S_x, AVK (None when no update was applied), buf).  ils: as
+    retrieval_forward."""
     a, e = _gas_stack(coeffs)
     n_gas, n_layers, n_pts = a.shape
     w0, step, n = grid_params(grid)
@@ -1168,11 +1173,12 @@ def retrieval_loop(coeffs, los, par_gas, par_w, x0, grid, centers_nm, widths_nm,
     chi_hist, x_hist = np.zeros(max(max_it, 1)), np.zeros((max_it + 1, n_par))
     n_it, stop = C.c_int32(0), C.c_int32(0)
     s_x, avk = np.zeros((n_par, n_par)), np.zeros((n_par, n_par))
-    check(lib.sr_retrieval_loop_dev(a.data_ptr(), e.data_ptr(), n_layers, n_pts, h, 0, xp, w0, step, cp, wp, centers_nm.size,
-                                    float(n_sigma), _UNITS[out_units], fp, buf.data_ptr(), out.ctypes.data_as(dp), C.byref(oe.desc),
-                                    C.byref(lp), chi_hist.ctypes.data_as(dp), x_hist.ctypes.data_as(dp), C.byref(n_it),
-                                    C.byref(stop), s_x.ctypes.data_as(dp), avk.ctypes.data_as(dp), _stream_ptr()),
-          "sr_retrieval_loop_dev")
+    with _IlsBound(ils):
+        check(lib.sr_retrieval_loop_dev(a.data_ptr(), e.data_ptr(), n_layers, n_pts, h, 0, xp, w0, step, cp, wp, centers_nm.size,
+                                        float(n_sigma), _UNITS[out_units], fp, buf.data_ptr(), out.ctypes.data_as(dp),
+                                        C.byref(oe.desc), C.byref(lp), chi_hist.ctypes.data_as(dp), x_hist.ctypes.data_as(dp),
+                                        C.byref(n_it), C.byref(stop), s_x.ctypes.data_as(dp), avk.ctypes.data_as(dp), _stream_ptr()),
+              "sr_retrieval_loop_dev")
     n_upd = n_it.value if stop.value == 0 else n_it.value - 1
     return (out, chi_hist[:n_it.value].copy(), x_hist[:n_upd + 1].copy(), ["", "converged", "raised"][stop.value],
             s_x if n_upd > 0 else None, avk if n_upd > 0 else None, buf)
@@ -1442,7 +1448,7 @@ def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, ga
 
 def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None, par_w=None, tab=None, coef_row=None,
                           par_level=None, par_c=None, gas=0, dcoeffs=None, par_t=None, out_units="Wm2", n_sigma=5.0, fov=None,
-                          g_lo=0, level_gases=None, par_lgas=None, instrument=False, pointing=False):
+                          g_lo=0, level_gases=None, par_lgas=None, instrument=False, pointing=False, ils=None):
     """limb_rays_state_jacobian on the instrument's bands in ONE library call (sr_limb_rays_state_bands_dev): the same
     mixed state vector (column, level, row parameters: the same arguments, the same errors), but no hi-res spectrum is
     written -- the recursion kernel integrates the bands in its epilogue.  Returns numpy [n_rays | n_rays / 3, 1 + n_par,
@@ -1458,7 +1464,8 @@ def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None
     them, bit for bit, and there may then be no parameter at all.
     pointing=True (sr_limb_rays_state_bands_path_dev; the batch needs path=, else ValueError): the pointing row of
     limb_rays_state_jacobian behind the parameters' and in front of the instrument rows, [.., 1 + n_par + 1 (+ 2),
-    n_bands]; the other rows are those of the call without, bit for bit."""
+    n_bands]; the other rows are those of the call without, bit for bit.
+    ils: an ILS, the bands' tabulated line shape (as hires_to_lowres and, with instrument=True, hires_to_lowres_instrument)."""
     instrument, pointing = bool(instrument), bool(pointing)
     if pointing:
         path = los.path_desc()
@@ -1482,12 +1489,14 @@ def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None
     out = np.empty((n_out, 1 + A.n_par + (1 if pointing else 0) + (2 if instrument else 0), centers_nm.size))
     if pointing:
         name = "sr_limb_rays_state_bands_path_dev"
-        check(getattr(lib, name)(*A.args(name, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp,
-                                         out.ctypes.data_as(dp), _stream_ptr(), int(instrument), C.byref(path))), name)
+        with _IlsBound(ils):
+            check(getattr(lib, name)(*A.args(name, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp,
+                                             out.ctypes.data_as(dp), _stream_ptr(), int(instrument), C.byref(path))), name)
         return out
     name = _state_entry(True, instrument, level_gases is not None, par_t is not None)
-    check(getattr(lib, name)(*A.args(name, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp, out.ctypes.data_as(dp),
-                                     _stream_ptr())), name)
+    with _IlsBound(ils):
+        check(getattr(lib, name)(*A.args(name, cp, wp, centers_nm.size, float(n_sigma), _UNITS[out_units], fp,
+                                         out.ctypes.data_as(dp), _stream_ptr())), name)
     return out
 
 
@@ -1772,7 +1781,106 @@ def set_far_field(on):
 _UNITS = {"Wm2": 0, "ergscm2": 1, "nWcm2": 2}
 
 
-def _lowres_call(entry, n_tab, rad, grid, centers_nm, widths_nm, out_units, n_sigma, g_lo):
+class ILS(object):
+    """A tabulated instrument line shape (sr_set_ils): knots phi at the uniformly spaced reduced offsets
+    t = (x - centre) / width from t_lo to t_hi, interpolated by the cubic Hermite interpolant of include/spectrobot_hip.h
+    (central-difference slopes, one-sided at the ends; zero outside [t_lo, t_hi]).  phi: [n_tab], one table for all bands,
+    or [n_bands, n_tab], table b for band b of the calls it is given to.  normalize: every table is divided by the exact
+    integral of its interpolant over t (computed in numpy.longdouble, rounded once), so that a flat spectrum keeps its
+    level whatever the band's width; a table whose area is not positive raises.  The library itself uses the knots as
+    given.  Pass it as ils= to hires_to_lowres, hires_to_lowres_instrument, retrieval_forward / _step / _loop,
+    limb_rays_state_bands and the state_bands methods: the call binds it, runs and unbinds."""
+
+    def __init__(self, t_lo, t_hi, phi, normalize=True):
+        phi = np.array(phi, dtype=np.float64)
+        if phi.ndim not in (1, 2):
+            raise ValueError("phi must be [n_tab] or [n_bands, n_tab]")
+        per_band = phi.ndim == 2
+        phi = np.atleast_2d(phi)
+        t_lo, t_hi = float(t_lo), float(t_hi)
+        if phi.shape[0] < 1 or phi.shape[1] < 4:
+            raise ValueError("a line shape needs at least 4 knots per table")
+        if phi.shape[1] > _lib.SR_MAX_ILS_TAB:
+            raise ValueError("more than %d knots per table" % _lib.SR_MAX_ILS_TAB)
+        if not (np.isfinite(t_lo) and np.isfinite(t_hi) and t_lo < t_hi):
+            raise ValueError("t_lo < t_hi, both finite")
+        if not np.all(np.isfinite(phi)):
+            raise ValueError("a knot is not finite")
+        if normalize:
+            area = self.interpolant_area(t_lo, t_hi, phi)
+            if not np.all(area > 0):
+                raise ValueError("a table's area is not positive: nothing to normalise by")
+            phi = np.asarray(phi.astype(np.longdouble) / area[:, None], np.float64)
+        self.t_lo, self.t_hi, self.per_band = t_lo, t_hi, per_band
+        self.phi = np.ascontiguousarray(phi)
+        self.n_shapes, self.n_tab = self.phi.shape
+        self.desc = _lib.IlsDesc(self.n_shapes, self.n_tab, t_lo, t_hi, self.phi.ctypes.data_as(dp))
+
+    @staticmethod
+    def interpolant_area(t_lo, t_hi, phi):
+        """The exact integral of each table's interpolant in numpy.longdouble [n_shapes]:
+        h (sum_k (phi_k + phi_(k+1)) / 2 + ((phi_1 - phi_0) - (phi_(n-1) - phi_(n-2))) / 12)."""
+        LD = np.longdouble
+        p = np.atleast_2d(np.asarray(phi, np.float64)).astype(LD)
+        h = (LD(t_hi) - LD(t_lo)) / LD(p.shape[1] - 1)
+        trap = p.sum(axis=1) - (p[:, 0] + p[:, -1]) / LD(2)
+        return h * (trap + ((p[:, 1] - p[:, 0]) - (p[:, -1] - p[:, -2])) / LD(12))
+
+    def area(self):
+        """sr_ils_area of the table as bound: numpy [n_shapes]."""
+        out = np.zeros(self.n_shapes)
+        check(lib.sr_ils_area(C.byref(self.desc), out.ctypes.data_as(dp)), "sr_ils_area")
+        return out
+
+    def knots(self):
+        return np.linspace(self.t_lo, self.t_hi, self.n_tab)
+
+    def select(self, order):
+        """The per-band tables in another band order (a shared table: itself)."""
+        if not self.per_band:
+            return self
+        return ILS(self.t_lo, self.t_hi, self.phi[np.asarray(order)], normalize=False)
+
+    @classmethod
+    def from_function(cls, fn, t_lo, t_hi, n_tab, normalize=True):
+        """fn(t) sampled at the n_tab knots."""
+        return cls(t_lo, t_hi, fn(np.linspace(float(t_lo), float(t_hi), int(n_tab))), normalize=normalize)
+
+    @classmethod
+    def gaussian(cls, n_tab=641, t_max=5.0):
+        """exp(-t^2 / 2) / sqrt(2 pi) on +-t_max, as given (not renormalised): for cross-checks against the built-in
+        Gaussian with n_sigma = t_max."""
+        return cls.from_function(lambda t: np.exp(-0.5 * t * t) / np.sqrt(2.0 * np.pi), -t_max, t_max, n_tab, normalize=False)
+
+    @classmethod
+    def sinc(cls, n_lobes, n_tab, apodisation=None):
+        """sin(pi t) / (pi t) on +-n_lobes (the width is the distance of the first zero; the ends are zeros of the
+        shape), negative side lobes and all.  apodisation: a function of u = t / n_lobes in [-1, 1] that multiplies it."""
+        n_lobes = float(n_lobes)
+        fn = (lambda t: np.sinc(t)) if apodisation is None else (lambda t: np.sinc(t) * apodisation(t / n_lobes))
+        return cls.from_function(fn, -n_lobes, n_lobes, n_tab)
+
+
+class _IlsBound(object):
+    """with _IlsBound(ils): the calling thread's band calls integrate with `ils`; the Gaussian again on the way out.
+    None: nothing is bound or unbound."""
+
+    def __init__(self, ils):
+        if ils is not None and not isinstance(ils, ILS):
+            raise TypeError("ils must be an engine.ILS")
+        self.ils = ils
+
+    def __enter__(self):
+        if self.ils is not None:
+            check(lib.sr_set_ils(C.byref(self.ils.desc)), "sr_set_ils")
+
+    def __exit__(self, *exc):
+        if self.ils is not None:
+            check(lib.sr_set_ils(None), "sr_set_ils")
+        return False
+
+
+def _lowres_call(entry, n_tab, rad, grid, centers_nm, widths_nm, out_units, n_sigma, g_lo, ils=None):
     """The instrument step's arguments, checked and marshalled once for its two entry points: returns numpy
     [n_rays, n_tab, n_bands] as `entry` (sr_hires_to_lowres_shard_dev: n_tab 1; sr_hires_to_lowres_instr_shard_dev: 3) fills it."""
     w0, step, n = grid_params(grid)
@@ -1788,30 +1896,33 @@ def _lowres_call(entry, n_tab, rad, grid, centers_nm, widths_nm, out_units, n_si
     if widths_nm.size != centers_nm.size:
         raise ValueError("{} spectral widths for {} grid points".format(widths_nm.size, centers_nm.size))
     out = np.zeros((rad2.shape[0], n_tab, centers_nm.size))
-    check(getattr(lib, entry)(C.c_void_p(rad2.data_ptr()), rad2.shape[0], n_sh, int(g_lo), w0, step, cp, wp, centers_nm.size,
-                              float(n_sigma), _UNITS[out_units], out.ctypes.data_as(dp), _stream_ptr()), entry)
+    with _IlsBound(ils):
+        check(getattr(lib, entry)(C.c_void_p(rad2.data_ptr()), rad2.shape[0], n_sh, int(g_lo), w0, step, cp, wp, centers_nm.size,
+                                  float(n_sigma), _UNITS[out_units], out.ctypes.data_as(dp), _stream_ptr()), entry)
     return out
 
 
-def hires_to_lowres(rad, grid, centers_nm, widths_nm, out_units="Wm2", n_sigma=5.0, g_lo=None):
+def hires_to_lowres(rad, grid, centers_nm, widths_nm, out_units="Wm2", n_sigma=5.0, g_lo=None, ils=None):
     """Gaussian-ILS degradation of hi-res spectra (CUDA float64 [n_rays, n_grid], 'ergscm2' on the
     cm-1 grid) onto low-resolution bands given in nm: SpectralIntensity.hires_to_lowres
     (spect_classes.py:1180-1191).  Returns numpy [n_rays, n_bands] in out_units.
     g_lo given: rad holds the grid points g_lo .. g_lo + rad.shape[-1] - 1 only (a spectral shard) and the PARTIAL band
     integrals over them are returned (sr_hires_to_lowres_shard_dev); `grid` is always the whole grid.  Without g_lo
-    the spectrum must cover the whole grid (a mis-sized spectrum is an error, not a partial integral)."""
-    return _lowres_call("sr_hires_to_lowres_shard_dev", 1, rad, grid, centers_nm, widths_nm, out_units, n_sigma, g_lo)[:, 0]
+    the spectrum must cover the whole grid (a mis-sized spectrum is an error, not a partial integral).
+    ils: an ILS, the tabulated line shape in the Gaussian's place (widths_nm scale its reduced offsets; n_sigma is not used)."""
+    return _lowres_call("sr_hires_to_lowres_shard_dev", 1, rad, grid, centers_nm, widths_nm, out_units, n_sigma, g_lo, ils)[:, 0]
 
 
-def hires_to_lowres_instrument(rad, grid, centers_nm, widths_nm, out_units="Wm2", n_sigma=5.0, g_lo=None):
+def hires_to_lowres_instrument(rad, grid, centers_nm, widths_nm, out_units="Wm2", n_sigma=5.0, g_lo=None, ils=None):
     """hires_to_lowres with the two instrument derivatives of every band (sr_hires_to_lowres_instr_shard_dev): returns
     (low, dlow_dcentre, dlow_dlnwidth), numpy [n_rays, n_bands] each -- the band values (hires_to_lowres's, bit for bit),
     their derivatives to a shift of the band centre (per nm) and to the logarithm of the ILS width,
         d low_b / d delta = k sum_i s_i W_i t_i / w_b,     d low_b / d eta = k sum_i s_i W_i (t_i^2 - 1),
     t_i = (x_i - f_b) / w_b, with the window's membership held fixed (it is piecewise constant in f and w; a jump is of
     relative size exp(-n_sigma^2 / 2)).  Any parametrisation of the centres and widths is a chain rule on these rows.
-    Arguments as hires_to_lowres; a shard (g_lo) returns partial sums that add up over the shards."""
-    out = _lowres_call("sr_hires_to_lowres_instr_shard_dev", 3, rad, grid, centers_nm, widths_nm, out_units, n_sigma, g_lo)
+    Arguments as hires_to_lowres; a shard (g_lo) returns partial sums that add up over the shards.
+    ils: an ILS; the two rows are then the derivatives of its interpolant, -p phi^' / w^2 and -p (phi^ + t phi^') / w."""
+    out = _lowres_call("sr_hires_to_lowres_instr_shard_dev", 3, rad, grid, centers_nm, widths_nm, out_units, n_sigma, g_lo, ils)
     return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
 
 

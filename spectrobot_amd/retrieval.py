@@ -264,11 +264,18 @@ class LimbPixel(object):
         return [self.limb_tg_alt - self.fov_half, self.limb_tg_alt, self.limb_tg_alt + self.fov_half]
 
 
+def _ils(scene):
+    """The scene's tabulated line shape (None: the Gaussian)."""
+    return getattr(scene, "ils", None)
+
+
 class LimbScene(object):
     """1-D atmosphere on altitude levels z [km] (temps [K], press [hPa]), gases, spectral grid, instrument bands
-    (centres / Gaussian sigmas in nm)."""
+    (centres / Gaussian sigmas in nm).  ils: an engine.ILS, the bands' tabulated line shape in the Gaussian's place
+    (widths_nm then scale its reduced offsets): every band integral of simulate, radtran, inversion_fast_limb, inversion
+    and inversion_state, and BandCalibration's two instrument rows, are taken with it."""
 
-    def __init__(self, grid, z, temps, press, gases, bands_nm, widths_nm, R=2575.0, n_sub=3, out_units="Wm2"):
+    def __init__(self, grid, z, temps, press, gases, bands_nm, widths_nm, R=2575.0, n_sub=3, out_units="Wm2", ils=None):
         self.grid = np.asarray(grid, dtype=float)
         self.z, self.temps, self.press = (np.asarray(v, dtype=float) for v in (z, temps, press))
         self.nd = syn.number_density(self.press, self.temps)
@@ -276,6 +283,7 @@ class LimbScene(object):
         self.bands_nm, self.widths_nm = np.asarray(bands_nm, float), np.asarray(widths_nm, float)
         self.bands_nm0, self.widths_nm0 = self.bands_nm.copy(), self.widths_nm.copy()   # the nominal calibration (BandCalibration)
         self.R, self.n_sub, self.out_units = R, n_sub, out_units
+        self.ils = ils
 
     def gas(self, name):
         return [g for g in self.gases if g.name == name][0]
@@ -583,7 +591,8 @@ def _simulate_budget(scene, pixels, track_levels, fov_closed_form, shard, refres
             for g, k in enumerate(gas_rows):
                 buf[1 + k] = parts[:, len(lev_rows) + g]
     hires = torch.stack(buf).reshape(len(buf) * n_los, -1)
-    low = engine.hires_to_lowres(hires, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units, g_lo=g_lo)
+    low = engine.hires_to_lowres(hires, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units, g_lo=g_lo,
+                                 ils=_ils(scene))
     low = np.asarray(low).reshape(len(buf), n_los, -1)
     if shard is not None:
         dev = "cuda" if (torch.distributed.is_initialized() and torch.distributed.get_backend() == "nccl") else "cpu"
@@ -644,7 +653,8 @@ def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, re
     g_lo, g_hi = (0, n_grid) if shard is None else shard_with_halo(n_grid, *shard)
     coeffs = scene.coefficient_stack(refresh=refresh, g_lo=g_lo, g_hi=g_hi)
     n_los = len(alts)
-    lowres = lambda r: engine.hires_to_lowres(r, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units, g_lo=g_lo)
+    lowres = lambda r: engine.hires_to_lowres(r, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units, g_lo=g_lo,
+                                              ils=_ils(scene))
     with_fov = sum(pix.fov_half > 0 for pix in pixels)
     if arrays and group is None and _one_call_eligible(pixels, bayes_set, fov_closed_form):
         # The iteration in ONE library call (engine.retrieval_forward): the VMRs of the retrieved gases are set on the
@@ -654,7 +664,7 @@ def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, re
         out, scene._fwd_buf = engine.retrieval_forward(coeffs, los, par_gas, par_w, bayes_set.param_vector(), scene.grid,
                                                        scene.bands_nm, scene.widths_nm, out_units=scene.out_units, g_lo=g_lo,
                                                        fov=scene._fov_fac if with_fov else None,
-                                                       buf=getattr(scene, "_fwd_buf", None))
+                                                       buf=getattr(scene, "_fwd_buf", None), ils=_ils(scene))
         if not with_fov:
             out = out[1::3]
         if shard is not None:
@@ -806,7 +816,8 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
         both, hist, xh, why, S_x, AVK, scene._fwd_buf = engine.retrieval_loop(
             coeffs, los_b, par_gas, par_w, bayes_set.param_vector(), scene.grid, scene.bands_nm, scene.widths_nm, oe,
             [bool(par.constrain_positive) for par in params], bayes_set.n_used_par(), chi_threshold=chi_threshold, max_it=max_it,
-            out_units=scene.out_units, fov=scene._fov_fac if with_fov else None, buf=getattr(scene, "_fwd_buf", None))
+            out_units=scene.out_units, fov=scene._fov_fac if with_fov else None, buf=getattr(scene, "_fwd_buf", None),
+            ils=_ils(scene))
         for k in range(1, len(xh)):                                            # update_params / update_par, :616-624
             bayes_set.old_params.append(bayes_set.values())
             for par, v in zip(params, xh[k]):
@@ -831,7 +842,8 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
             los_b, par_gas, par_w = _one_call_batch(scene, pixels, bayes_set, alts_all, with_fov)
             both, chi_sum, n_used, dx, S_x, AVK, scene._fwd_buf = engine.retrieval_step(
                 coeffs, los_b, par_gas, par_w, bayes_set.param_vector(), scene.grid, scene.bands_nm, scene.widths_nm, oe,
-                out_units=scene.out_units, fov=scene._fov_fac if with_fov else None, buf=getattr(scene, "_fwd_buf", None))
+                out_units=scene.out_units, fov=scene._fov_fac if with_fov else None, buf=getattr(scene, "_fwd_buf", None),
+                ils=_ils(scene))
             low, dlow = both[:, 0, :], both[:, 1:, :]
             for par in bayes_set.params():
                 par.set_used()
@@ -966,7 +978,7 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     masktot = None if masks is None else np.concatenate([np.asarray(m, dtype=bool) for m in masks])
     Sa_inv = np.linalg.inv(np.asarray(bayes_set.VCM_apriori(), dtype=float))
     grid_lo = _Grid(scene.bands_nm)
-    lowres = lambda r: engine.hires_to_lowres(r, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units)
+    lowres = lambda r: engine.hires_to_lowres(r, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units, ils=_ils(scene))
     rots = [pix.pixel_rot for pix in pixels]
     bayes_set.history, bayes_set.stop = [], 'max_it'
     instr = bayes_set.sets.get(INSTR_SET) if INSTR_SET not in [g.name for g in scene.gases] else None
@@ -1023,6 +1035,8 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             lfs = engine.LevelFactoredSet([(g.lf, i, g.rows, g.tvib) for g, i in zip(w.level_gases, w.gases)])
         if bands_in_kernel:    # Jacobians, instrument bands and field of view in one call: [n_pix | n_los, 1 + n_par, n_bands]
             band_args = dict(out_units=scene.out_units, fov=engine.fov_factors(rots) if with_fov else None)
+            if _ils(scene) is not None:
+                band_args["ils"] = scene.ils
             if instr is not None:
                 band_args["instrument"] = True
             band_args.update(point_kw)
@@ -1065,7 +1079,8 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             if instr is None:
                 both = np.concatenate([lowres(rad)[:, None, :]] + rows, axis=1)
             else:      # the instrument step once more on the radiance, with its two derivative rows (row 0: lowres(rad))
-                three = engine.hires_to_lowres_instrument(rad, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units)
+                three = engine.hires_to_lowres_instrument(rad, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units,
+                                                          ils=_ils(scene))
                 both = np.concatenate([three[0][:, None, :]] + rows + [three[1][:, None, :], three[2][:, None, :]], axis=1)
             fov = smm.fov_closed_form(both[0::3], both[1::3], both[2::3], rots) if with_fov else both[1::3]
         if instr is not None or point is not None:
@@ -1153,9 +1168,9 @@ def inversion(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM
             los, alt = scene.los(pix.los_alts())                                           # low_LOS, LOS, up_LOS
             par_gas, par_w = scene.profile_weights(bayes_set, alt)
             rad, jac = engine.limb_rays_jacobian(coeffs, los, par_gas, par_w)
-            low = engine.hires_to_lowres(rad, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units)
+            low = engine.hires_to_lowres(rad, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units, ils=_ils(scene))
             dlow = engine.hires_to_lowres(jac.reshape(3 * len(par_gas), -1), scene.grid, scene.bands_nm, scene.widths_nm,
-                                          out_units=scene.out_units).reshape(3, len(par_gas), -1)
+                                          out_units=scene.out_units, ils=_ils(scene)).reshape(3, len(par_gas), -1)
             three = [Spectrum(low[q], scene.bands_nm) for q in range(3)]
             sims[num] = smm.FOV_integr_1D(three, pix.pixel_rot, closed_form=fov_closed_form) if pix.fov_half > 0 else three[1]
             for p, par in enumerate(bayes_set.params()):

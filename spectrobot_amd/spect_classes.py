@@ -565,10 +565,12 @@ class SpectralIntensity(SpectralObject):
     def add_bands(self, bands):
         self.bands = copy.deepcopy(bands)
 
-    def hires_to_lowres(self, lowres_obs, spectral_widths=None, keep_original_hires=True):
+    def hires_to_lowres(self, lowres_obs, spectral_widths=None, keep_original_hires=True, ils=None):
         """spect_classes.py:1180-1191.  self: hi-res on a cm_1 np.arange grid in 'ergscm2';
         lowres_obs: object with .spectral_grid (units 'nm') and .units; spectral_widths: Gaussian
-        sigma per band (nm); default = the low-res grid step, as in the reference (spcl:890-892)."""
+        sigma per band (nm); default = the low-res grid step, as in the reference (spcl:890-892).
+        ils: an engine.ILS, a tabulated line shape in the Gaussian's place (the reference's conv_type is ignored there,
+        spcl:832, 883); spectral_widths then scale its reduced offsets."""
         import torch
         from . import engine
         if self.spectral_grid.units != 'cm_1' or self.units != 'ergscm2':
@@ -584,7 +586,7 @@ class SpectralIntensity(SpectralObject):
             raise ValueError('{} spectral widths for {} grid points'.format(len(spectral_widths), new_len))
         dev = torch.as_tensor(np.ascontiguousarray(self.spectrum, dtype=np.float64), device="cuda")
         low = engine.hires_to_lowres(dev, self.spectral_grid.grid, lowres_obs.spectral_grid.grid, spectral_widths,
-                                     out_units=lowres_obs.units)[0]
+                                     out_units=lowres_obs.units, ils=ils)[0]
         return SpectralIntensity(low, lowres_obs.spectral_grid, units=lowres_obs.units)
 
 
