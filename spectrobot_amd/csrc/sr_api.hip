@@ -2290,57 +2290,6 @@ int refuse_init_mode_1(const sr_los_desc *los, const char *entry, int status) {
   return status;
 }
 
-// coef_row [n_layers] of the level-table calls: rows of tables with n_tab_rows rows
-bool coef_rows_in_range(const int32_t *coef_row, int n_layers, int n_tab_rows) {
-  for (int r = 0; r < n_layers; ++r)
-    if (coef_row[r] < 0 || coef_row[r] >= n_tab_rows) return false; // would read out of the tables
-  return true;
-}
-
-// 0 .. n-1 in level order (stable; a level below 0 counts as -1 and comes first): cut into blocks of NP, a block then
-// touches few levels and the entries of one level are neighbours
-std::vector<int> order_by_level(int n, const int32_t *level) {
-  std::vector<int> order(n);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return std::max(level[a], -1) < std::max(level[b], -1); });
-  return order;
-}
-
-struct LosShape {
-  int n_seg = 0, n_pt = 0;
-};
-
-int check_los(const sr_los_desc *los, int n_layers, LosShape *out) {
-  if (!los || los->n_rays <= 0 || los->n_gas <= 0 || !los->seg_off || !los->x || !los->nd || !los->vmr) return SR_ERR_ARG;
-  if (los->n_gas > 4) return SR_ERR_LIMIT;
-  if (los->init_mode < 0 || los->init_mode > 2) return SR_ERR_ARG;
-  if (los->init_mode == 2 && !(los->t_init > 0.0 && los->step > 0.0)) return SR_ERR_ARG;
-  const int n_seg = los->seg_off[los->n_rays];
-  if (los->seg_off[0] != 0 || n_seg <= 0 || !los->seg_layer || !los->pt_off) return SR_ERR_ARG;
-  for (int r = 0; r < los->n_rays; ++r)
-    if (los->seg_off[r + 1] < los->seg_off[r]) return SR_ERR_ARG;
-  if (los->pt_off[0] != 0) return SR_ERR_ARG;
-  for (int s = 0; s < n_seg; ++s) {
-    if (n_layers > 0 && (los->seg_layer[s] < 0 || los->seg_layer[s] >= n_layers)) return SR_ERR_ARG; // out-of-bounds read
-    const int np = los->pt_off[s + 1] - los->pt_off[s];
-    if (np < 2) return SR_ERR_ARG;
-    if (np > 8000) return SR_ERR_LIMIT; // imxstp, parameters.inc:64
-  }
-  out->n_seg = n_seg;
-  out->n_pt = los->pt_off[n_seg];
-  return SR_OK;
-}
-
-// check_los + the column parameters staged with the batch
-int check_los_par(const sr_los_desc *los, int n_layers, int n_par, const int32_t *par_gas, const double *par_w, LosShape *out) {
-  const int rc = check_los(los, n_layers, out);
-  if (rc) return rc;
-  if (n_par < 0 || (n_par > 0 && (!par_gas || !par_w))) return SR_ERR_ARG;
-  for (int p = 0; p < n_par; ++p)
-    if (par_gas[p] < 0 || par_gas[p] >= los->n_gas) return SR_ERR_ARG;
-  return SR_OK;
-}
-
 // Stage a checked LOS (check_los_par: `shape`) and evaluate the columns of the gases and of n_par profile parameters;
 // `st` waits for them.  own: the staging slot of a device-resident LOS (sr_los_create) instead of the per-call ring.
 // path (photon order only, the caller has checked): the sample points' derivatives to the ray's tangent altitude join
@@ -2428,46 +2377,6 @@ LimbOpts limb_opts(const sr_los_desc *los, int n_seg) {
 
 namespace {
 
-// The two sides of rays that walk the shells strictly inwards down to a turning shell and strictly outwards again (limb
-// rays; slant / nadir rays are the outward half, their first segment counted as the inward one): far / near
-// [n_rays][n_layers] = the segment's index in WALK order (LOS_order 'observer' reverses every ray, as stage_los lists the
-// columns) or -1, and the range of shells touched.  false: some ray is not of that shape.
-// row_of_seg (caller's segment order, or NULL: seg_layer): the SHELL of a segment where that is not its coefficient row
-// (3-D paths: seg_jac_row).
-bool fold_sides(const sr_los_desc *los, int n_layers, const int32_t *row_of_seg, std::vector<int> *far_out,
-                std::vector<int> *near_out, int *l_min_out, int *l_max_out) {
-  const int nr = los->n_rays;
-  std::vector<int> &far = *far_out, &near = *near_out;
-  far.assign((size_t)nr * n_layers, -1);
-  near.assign((size_t)nr * n_layers, -1);
-  int l_min = n_layers, l_max = -1;
-  bool ok = true;
-  for (int r = 0; r < nr && ok; ++r) {
-    const int a = los->seg_off[r], m = los->seg_off[r + 1] - a;
-    auto lay = [&](int q) { return (row_of_seg ? row_of_seg : los->seg_layer)[los->los_order == 0 ? a + q : a + (m - 1 - q)]; };
-    int q = 0, prev = INT_MAX;
-    for (; q < m; ++q) { // far side: strictly inwards
-      const int k = lay(q);
-      if (k >= prev) break;
-      far[(size_t)r * n_layers + k] = a + q;
-      prev = k;
-      l_min = std::min(l_min, k); l_max = std::max(l_max, k);
-    }
-    prev = q < m ? lay(q) - 1 : prev;
-    if (q < m && q > 0 && lay(q) < lay(q - 1)) ok = false;
-    for (; q < m && ok; ++q) { // near side: strictly outwards (its first shell may be the far side's last)
-      const int k = lay(q);
-      if (k <= prev) { ok = false; break; }
-      near[(size_t)r * n_layers + k] = a + q;
-      prev = k;
-      l_min = std::min(l_min, k); l_max = std::max(l_max, k);
-    }
-  }
-  *l_min_out = l_min;
-  *l_max_out = l_max;
-  return ok && l_max >= l_min;
-}
-
 // The folded kernels' plan on the device: per ray and visited shell (outermost first) the layer and the ray's two
 // segments there, + room for the packed records.  n_rec = 0: some ray is not V-shaped (nothing staged).
 struct FoldStage {
@@ -2481,12 +2390,7 @@ int stage_fold(const sr_los_desc *los, int n_layers, hipStream_t st, FoldStage *
   int l_min = 0, l_max = -1;
   if (!fold_sides(los, n_layers, nullptr, &far, &near, &l_min, &l_max)) return SR_OK;
   const int nr = los->n_rays;
-  std::vector<int> shells;
-  for (int k = l_max; k >= l_min; --k) {
-    bool any = false;
-    for (int r = 0; r < nr && !any; ++r) any = far[(size_t)r * n_layers + k] >= 0 || near[(size_t)r * n_layers + k] >= 0;
-    if (any) shells.push_back(k);
-  }
+  const std::vector<int> shells = fold_shells(far, near, nr, n_layers, l_min, l_max);
   if ((size_t)nr * shells.size() > ((size_t)1 << 21)) return SR_OK; // (2M records = 436 MB of plan: such batches keep the path-order kernels)
   // The fold pays when the rays SHARE shells.  A 3-D batch lists a row per LOS step (seg_layer = arange): every ray then
   // looks like a slant ray through rows of its own, the union of the shells is the steps of ALL rays and a ray's plan is
@@ -3237,103 +3141,6 @@ int sr_limb_rays_dev(const double *abs_c, const double *emi_c, int n_layers, int
 
 namespace {
 
-// Plan of the one-pass Jacobian kernel (sr_limb_adjoint_kernel): per segment, in the order the recursion walks
-// them, the layer with its first-touch flag and the column parameters the segment touches (d col / d x_p != 0 iff
-// the parameter's weight is non-zero at one of the segment's sample points), runs of consecutive touches carried
-// in one of four registers; per ray the rows it never touches.  Returns false when a segment touches more than
-// kAdjEnt parameters (the forward-sensitivity kernel takes those calls).
-struct AdjPlan {
-  std::vector<int> seg;      // [n_seg][kAdjPlanInts]
-  std::vector<int> zero_off; // [n_rays + 1]
-  std::vector<int> zero_row; // layer rows (< n_layers) and parameter rows (n_layers + p)
-};
-// The column-parameter entries of a ray's walk, step by step (a segment, or a shell visit of the folded plan): the
-// parameters whose next touch (touch[p]: ascending steps) is this step; runs of consecutive touches are carried in one
-// of four registers while one is free.
-struct RunPlan {
-  bool slot_busy[4] = {false, false, false, false};
-  std::vector<int> slot_of, pos;
-  std::vector<char> seen; // the parameter has been written in this ray
-  explicit RunPlan(int n_par) : slot_of(std::max(n_par, 1), -1), pos(std::max(n_par, 1), 0), seen(std::max(n_par, 1), 0) {}
-  // the step's entries into its four slots (ent_p[4], ent_gf[4]); returns their number, or -1 when more than four touch it
-  int step(int at, const std::vector<std::vector<int>> &touch, const int32_t *par_gas, int *ent_p, int *ent_gf) {
-    int n_ent = 0;
-    for (int p = 0; p < (int)touch.size(); ++p) {
-      if (pos[p] >= (int)touch[p].size() || touch[p][pos[p]] != at) continue;
-      if (n_ent == 4) return -1;
-      const bool next_too = pos[p] + 1 < (int)touch[p].size() && touch[p][pos[p] + 1] == at + 1;
-      int fl = 0, sl = slot_of[p];
-      if (sl < 0) { // no carry in: a run starts here
-        fl |= 1;
-        if (next_too)
-          for (int c = 0; c < 4; ++c)
-            if (!slot_busy[c]) { sl = c; slot_busy[c] = true; break; }
-      }
-      const bool carry_out = next_too && sl >= 0;
-      if (!carry_out) {
-        fl |= 2;                    // written here
-        if (!seen[p]) fl |= 4;      // first write of this parameter in the ray: store
-        seen[p] = 1;
-        if (sl >= 0) slot_busy[sl] = false;
-        slot_of[p] = -1;
-      } else {
-        slot_of[p] = sl;
-      }
-      ent_p[n_ent] = p;
-      ent_gf[n_ent] = par_gas[p] | (std::max(sl, 0) << 8) | (fl << 16);
-      ++n_ent;
-      ++pos[p];
-    }
-    return n_ent;
-  }
-};
-
-bool build_adj_plan(const sr_los_desc *los, int n_layers, const int32_t *seg_jrow, int n_jrows, int n_par,
-                    const int32_t *par_gas, const double *par_w, bool want_layer, int n_pt, AdjPlan *out) {
-  const int nr = los->n_rays, n_seg = los->seg_off[nr];
-  out->seg.assign((size_t)n_seg * kAdjPlanInts, 0);
-  out->zero_off.assign(nr + 1, 0);
-  out->zero_row.clear();
-  std::vector<char> lay_seen(n_jrows);
-  std::vector<std::vector<int>> touch(n_par); // walk positions (within the ray) of the segments touching p
-  for (int r = 0; r < nr; ++r) {
-    const int a = los->seg_off[r], b = los->seg_off[r + 1], m = b - a;
-    std::fill(lay_seen.begin(), lay_seen.end(), 0);
-    auto orig = [&](int q) { return los->los_order == 0 ? a + q : a + (m - 1 - q); }; // walk position -> caller's segment
-    for (int q = 0; q < m; ++q) {
-      int *pl = &out->seg[(size_t)(a + q) * kAdjPlanInts];
-      const int k = los->seg_layer[orig(q)], jr = seg_jrow ? seg_jrow[orig(q)] : k;
-      pl[0] = k;
-      pl[1] = lay_seen[jr] ? 0 : 1;
-      pl[3] = jr;
-      lay_seen[jr] = 1;
-    }
-    for (int p = 0; p < n_par; ++p) {
-      touch[p].clear();
-      const double *w = par_w + (size_t)p * n_pt;
-      for (int q = 0; q < m; ++q) {
-        const int s = orig(q);
-        bool nz = false;
-        for (int i = los->pt_off[s]; i < los->pt_off[s + 1] && !nz; ++i) nz = w[i] != 0.0;
-        if (nz) touch[p].push_back(q);
-      }
-    }
-    RunPlan runs(n_par);
-    for (int q = 0; q < m; ++q) {
-      int *pl = &out->seg[(size_t)(a + q) * kAdjPlanInts];
-      pl[2] = runs.step(q, touch, par_gas, pl + 4, pl + 8);
-      if (pl[2] < 0) return false;
-    }
-    if (want_layer)
-      for (int k = 0; k < n_jrows; ++k)
-        if (!lay_seen[k]) out->zero_row.push_back(k);
-    for (int p = 0; p < n_par; ++p)
-      if (!runs.seen[p]) out->zero_row.push_back(n_jrows + p);
-    out->zero_off[r + 1] = (int)out->zero_row.size();
-  }
-  return true;
-}
-
 // Radiances (rad may be NULL) + per-layer Jacobian (dabs / demi / jac_layer may be NULL) + column-parameter Jacobian
 // (n_par may be 0) in one pass.  *done = 0 when the plan does not fit the kernel (nothing launched).  The callers have
 // checked everything: the LOS and its parameters (check_los_par: `shape`), seg_jrow's range, rad against init_mode 1.
@@ -3349,99 +3156,29 @@ int limb_adjoint(const double *abs_c, const double *emi_c, const double *dabs, c
   LosDev D;
   int rc = stage_los(los, shape, n_par, par_gas, par_w, st, &D);
   if (rc) return rc;
-  // Layer-synchronous schedule (sr_limb_adjoint_sync_kernel): when the rays share their coefficient rows (no per-step
-  // rows: seg_jrow == NULL) and every ray walks them monotonically down to a turning shell and monotonically up again
-  // (limb rays; slant / nadir rays are the upward half alone), the shells are listed once -- far side from the
-  // outermost shell inwards, near side outwards -- with every ray's segment in each: the kernel then loads a shell's
-  // coefficients once for kAdjSyncRays rays.  Anything else (3-D paths, unordered LOS) keeps one ray per thread.
+  // The route (sr_set_jac_layer_mode).  Rays that walk the shells down to a turning shell and up again (fold_sides) take
+  // the folded kernel by default (mode 0; 3-D paths with their shells = Jacobian rows, a coefficient row per LOS step)
+  // or, in mode 3 and when they share their coefficient rows, the layer-synchronous one.  Anything else -- an unordered
+  // LOS, a folded plan that does not fit, modes 1 and 2 -- keeps one ray per thread in path order.
   std::vector<int> sched, fplan;
-  int n_visits = 0, n_fvis = 0, n_frec = 0;
-  const int nr = los->n_rays, n_batches = (nr + kAdjSyncRays - 1) / kAdjSyncRays;
+  int n_visits = 0, n_fvis = 0;
+  const int nr = los->n_rays;
   const int jmode = g_jac_layer_forward.load();
-  const bool two_rows = seg_jrow != nullptr;           // 3-D paths: a coefficient row per LOS step, shells = Jacobian rows
-  const int n_sh = two_rows ? n_jrows : n_layers;      // shells
+  const bool two_rows = seg_jrow != nullptr;
+  const int n_sh = two_rows ? n_jrows : n_layers; // shells
   if (jmode == 0 || (jmode == 3 && nr >= 2 && !two_rows)) {
-    // per ray: far[shell] / near[shell] = walk-order segment index or -1
     std::vector<int> far, near;
     int l_min = n_sh, l_max = -1;
-    const bool ok = fold_sides(los, n_sh, seg_jrow, &far, &near, &l_min, &l_max);
-    // The folded plan (sr_limb_adjoint_fold_kernel, the default): one visit per shell, outermost first, with every
-    // ray's far-side and near-side segment there; a column parameter's touches -- read off the per-segment plan -- are
-    // planned over the VISITS (a level acts on the same shells on both sides: one run, one register, one store).
-    if (ok && l_max >= l_min && jmode == 0) {
-      std::vector<int> shells;
-      for (int k = l_max; k >= l_min; --k) {
-        bool any = false;
-        for (int r = 0; r < nr && !any; ++r) any = far[(size_t)r * n_sh + k] >= 0 || near[(size_t)r * n_sh + k] >= 0;
-        if (any) shells.push_back(k);
+    if (fold_sides(los, n_sh, seg_jrow, &far, &near, &l_min, &l_max)) {
+      if (jmode == 0) {
+        const std::vector<int> shells = fold_shells(far, near, nr, n_sh, l_min, l_max);
+        if (build_fold_plan(plan, far, near, shells, nr, n_sh, two_rows, n_par, par_gas, &fplan)) n_fvis = (int)shells.size();
+      } else {
+        build_sync_schedule(far, near, nr, n_layers, l_min, l_max, &sched, &n_visits);
       }
-      n_fvis = (int)shells.size();
-      n_frec = nr * n_fvis;
-      fplan.assign((size_t)n_frec * kFoldPlanInts, 0);
-      bool fits = true;
-      std::vector<std::vector<int>> touch(n_par);
-      auto rec_at = [&](int ray, int v) { return &fplan[((size_t)ray * n_fvis + v) * kFoldPlanInts]; };
-      for (int ray = 0; ray < nr && fits; ++ray) {
-        for (int v = 0; v < n_fvis; ++v) {
-          int *pl = rec_at(ray, v);
-          pl[1] = far[(size_t)ray * n_sh + shells[v]];
-          pl[2] = near[(size_t)ray * n_sh + shells[v]];
-          // coefficient rows: the segments' own (a side without a segment takes the other's: its loads are not used)
-          const int row_f = pl[1] >= 0 ? plan.seg[(size_t)pl[1] * kAdjPlanInts] : -1;
-          const int row_n = pl[2] >= 0 ? plan.seg[(size_t)pl[2] * kAdjPlanInts] : -1;
-          pl[0] = two_rows ? (row_f >= 0 ? row_f : std::max(row_n, 0)) : shells[v];
-          pl[12] = two_rows ? (row_n >= 0 ? row_n : std::max(row_f, 0)) : shells[v];
-          pl[13] = shells[v];
-        }
-        if (n_par == 0) continue;
-        for (int p = 0; p < n_par; ++p) touch[p].clear();
-        for (int v = 0; v < n_fvis; ++v) {
-          const int *pl = rec_at(ray, v);
-          for (int side = 1; side <= 2; ++side) {
-            if (pl[side] < 0) continue;
-            const int *sp = &plan.seg[(size_t)pl[side] * kAdjPlanInts];
-            for (int e = 0; e < sp[2]; ++e)
-              if (touch[sp[4 + e]].empty() || touch[sp[4 + e]].back() != v) touch[sp[4 + e]].push_back(v);
-          }
-        }
-        RunPlan runs(n_par);
-        for (int v = 0; v < n_fvis && fits; ++v) {
-          int *pl = rec_at(ray, v);
-          pl[3] = runs.step(v, touch, par_gas, pl + 4, pl + 8);
-          fits = pl[3] >= 0;
-        }
-      }
-      if (!fits) { // a shell's two segments touch more than four parameters between them: one ray per thread
-        fplan.clear();
-        n_fvis = n_frec = 0;
-      }
-    } else
-    if (ok && l_max >= l_min && !two_rows) {
-      // the visits every batch walks (a batch skips nothing: a visit none of its rays takes costs one load)
-      std::vector<std::pair<int, int>> visits; // (side, layer)
-      for (int k = l_max; k >= l_min; --k) {
-        bool any = false;
-        for (int r = 0; r < nr && !any; ++r) any = far[(size_t)r * n_layers + k] >= 0;
-        if (any) visits.push_back({0, k});
-      }
-      for (int k = l_min; k <= l_max; ++k) {
-        bool any = false;
-        for (int r = 0; r < nr && !any; ++r) any = near[(size_t)r * n_layers + k] >= 0;
-        if (any) visits.push_back({1, k});
-      }
-      n_visits = (int)visits.size();
-      sched.assign((size_t)n_batches * n_visits * (1 + kAdjSyncRays), -1);
-      for (int bt = 0; bt < n_batches; ++bt)
-        for (int v = 0; v < n_visits; ++v) {
-          int *sv = &sched[((size_t)bt * n_visits + v) * (1 + kAdjSyncRays)];
-          sv[0] = visits[v].second;
-          for (int i = 0; i < kAdjSyncRays; ++i) {
-            const int r = bt * kAdjSyncRays + i;
-            if (r < nr) sv[1 + i] = (visits[v].first ? near : far)[(size_t)r * n_layers + visits[v].second];
-          }
-        }
     }
   }
+  const int n_frec = nr * n_fvis;
   static thread_local StagerRing ring;
   StagePack pk(ring.take());
   const auto p_plan = pk.copy(plan.seg.data(), plan.seg.size()), p_zo = pk.copy(plan.zero_off.data(), plan.zero_off.size());
@@ -3590,60 +3327,6 @@ int sr_limb_rays_jac_layer_dev(const double *abs_c, const double *emi_c, const d
   LAUNCHCHK(launch_limb_jac_layer(abs_c, emi_c, dabs, demi, (int)n_pts, n_layers, los->n_rays, D.seg_off, D.seg_layer,
                                   D.col, limb_opts(los, D.n_seg), jac, st));
   return D.slot->mark(st);
-}
-
-// The host plan of sr_limb_jac_state_kernel: the column parameters in the caller's order, then the level parameters in
-// level order, then the row parameters in the caller's order, NP per block: a block's column slots come first and stand
-// for consecutive rows of dcol (blk: their number and gases), a row's level entries come in level order without a sort
-// of their own, the entries of its row slots (level kLevelEntRows, c = par_t[p][r]) behind them.
-// par_lgas (several level-factored gases): level parameter p belongs to level gas par_lgas[p]; the level parameters are
-// then listed by (level gas, level) and an entry carries level | level gas << kLevelEntGasShift.  Without it the plan is
-// the one-gas plan, word for word.
-// n_hid (the pointing derivative): n_hid more column slots behind the caller's, slot g of gas g, whose rows of dcol follow
-// the caller's; their rows of jac come LAST, n_col + n_lev + n_row + g, the other kinds keep the rows they have without.
-struct LevelJacPlan {
-  int n_blocks;
-  std::vector<int> blk, ent_off, slot_par;
-  std::vector<LevelEnt> ent;
-};
-static LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev, const int32_t *par_level, const double *par_c,
-                                   int n_layers, int n_row = 0, const double *par_t = nullptr, const int32_t *par_lgas = nullptr,
-                                   int n_hid = 0) {
-  const int n_state = n_col + n_lev + n_row;
-  const int nc_all = n_col + n_hid, n_cl = nc_all + n_lev, n_par = n_cl + n_row, np = level_jac_np(n_par);
-  const int n_blocks = std::max(1, (n_par + np - 1) / np); // (no parameter at all, the instrument rows alone: one block of unused slots)
-  std::vector<int32_t> packed; // the `level` words of the entries: the level, with several level gases the gas above it
-  if (par_lgas) {
-    packed.resize((size_t)n_lev);
-    for (int p = 0; p < n_lev; ++p) packed[p] = par_level[p] | par_lgas[p] << kLevelEntGasShift;
-    par_level = packed.data();
-  }
-  const std::vector<int> order = order_by_level(n_lev, par_level);
-  LevelJacPlan P{n_blocks, std::vector<int>((size_t)n_blocks * 2, 0), std::vector<int>((size_t)n_blocks * (n_layers + 1)),
-                 std::vector<int>((size_t)n_blocks * np, -1), {}};
-  for (int b = 0; b < n_blocks; ++b) {
-    const int i0 = b * np, i1 = std::min(n_par, i0 + np), nc = std::max(0, std::min(nc_all, i1) - i0);
-    unsigned gases = 0u;
-    for (int i = i0; i < i0 + nc; ++i) gases |= (unsigned)(i < n_col ? par_gas[i] : i - n_col) << (2 * (i - i0));
-    P.blk[2 * b] = nc;
-    P.blk[2 * b + 1] = (int)gases;
-    for (int i = i0; i < i1; ++i)
-      P.slot_par[i] = i < n_col ? i : i < nc_all ? n_state + (i - n_col) : i < n_cl ? n_col + order[i - nc_all] : i - n_hid;
-    for (int r = 0; r < n_layers; ++r) {
-      P.ent_off[(size_t)b * (n_layers + 1) + r] = (int)P.ent.size();
-      for (int i = std::max(i0, nc_all); i < std::min(i1, n_cl); ++i) {
-        const int p = order[i - nc_all];
-        const double c = par_c[(size_t)p * n_layers + r];
-        if (c != 0.0) P.ent.push_back(LevelEnt{i - i0, par_level[p], c});
-      }
-      for (int i = std::max(i0, n_cl); i < i1; ++i) {
-        const double c = par_t[(size_t)(i - n_cl) * n_layers + r];
-        if (c != 0.0) P.ent.push_back(LevelEnt{i - i0, kLevelEntRows, c});
-      }
-    }
-    P.ent_off[(size_t)b * (n_layers + 1) + n_layers] = (int)P.ent.size();
-  }
-  return P;
 }
 
 // What the entries below do once their arguments are checked: plan, stage, launch, mark.  First the record they fill, a

@@ -14,22 +14,12 @@
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "sr_constants.hpp"
 
 namespace sr {
 
 constexpr int kImxsig = 13010;     // parameters.inc:65
 constexpr int kHalf = kImxsig / 2; // window point k=1 sits on grid index ic-6505
-
-// spect_classes.py:39-47 (scipy.constants CODATA-2018)
-constexpr double kTref = 296.0;
-constexpr double kHpaToAtm = 0.00098692326671601;
-constexpr double kHcgs = 6.62607015e-34 * 1.e7;
-constexpr double kCcgs = 299792458.0 * 1.e2;
-constexpr double kKcgs = 1.380649e-23 * 1.e7;
-constexpr double kC2 = kHcgs * kCcgs / kKcgs;
-constexpr double kAvogadro = 6.02214076e23;
-constexpr double kPi = 3.141592653589793;
-constexpr double kLn2 = 0.6931471805599453; // math.log(2.0)
 
 // Grid and line-window arithmetic exactly as numpy builds them
 // (spect_main_module.py:1267, spect_classes.py:1446,1455).
@@ -335,54 +325,6 @@ __device__ inline double exp_core(double u) {
   p = fma(r, p, 1.0);
   p = fma(r, p, 1.0);
   return ldexp(p, (int)n);
-}
-
-// One segment of the radiance recursion: t = exp(-tau), em1 = 1 - exp(-tau) and f = em1 / tau (1 where
-// |tau| <= 1e-12) from ONE range reduction and polynomial: -tau = n ln2 + r, e^r - 1 = r (1 + r P(r)) =: pm1 with
-// exp_bounded's polynomial, s = 2^n, t = s + s pm1, em1 = (1 - s) - s pm1 (n = 0: -pm1, exact for thin segments; no
-// cancellation otherwise: |r| <= 0.35), the quotient by reciprocal + two Newton steps.  ~30 instructions for what
-// exp() + expm1() + an IEEE division spent ~95 on: the recursion kernels are VALU-bound (64 rays x 160 segments
-// x 1e5 points), sr_limb_kernel 1.5 -> see DESIGN.md.  tau may be negative (stimulated emission).
-struct Atten {
-  double t, em1, f, rtau; // rtau = 1 / tau (unspecified where |tau| <= 1e-12)
-  double fp0;             // f'(tau) from the polynomial, valid where the reduction left n = 0 (atten_fprime)
-  bool thin, n0;
-};
-__device__ inline Atten attenuation(double tau) {
-  const double x = -tau;
-  const double n = rint(x * 0x1.71547652b82fep+0);  // log2(e)
-  double r = fma(-n, 0x1.62e42fefa39efp-1, x);      // ln2 hi
-  r = fma(-n, 0x1.abc9e3b39803fp-56, r);            // ln2 lo
-  double p = fma3(r, 0x1.ade156a5dcb37p-26, 0x1.28af3fca7ab0cp-22);
-  p = fma3(r, p, 0x1.71dee623fde64p-19);
-  p = fma3(r, p, 0x1.a01997c89e6b0p-16);
-  p = fma3(r, p, 0x1.a01a014761f6ep-13);
-  p = fma3(r, p, 0x1.6c16c1852b7b0p-10);
-  p = fma3(r, p, 0x1.1111111122322p-7);
-  p = fma3(r, p, 0x1.55555555502a1p-5);
-  p = fma3(r, p, 0x1.5555555555511p-3);
-  p = fma3(r, p, 0x1.000000000000bp-1);
-  const double pm1 = r * fma(r, p, 1.0);
-  const double s = ldexp(1.0, (int)fmin(fmax(n, -1100.0), 1100.0));
-  Atten A;
-  A.t = fma(s, pm1, s);
-  A.em1 = fma(-s, pm1, 1.0 - s);
-  A.thin = !(fabs(tau) > 1e-12);
-  A.rtau = fast_rcp<2>(tau);
-  A.f = A.thin ? 1.0 : A.em1 * A.rtau;
-  A.n0 = n == 0.0;
-  A.fp0 = fma(fabs(r) < 0x1p-4 ? p - 0x1.6p-50 : p, 1.0 - r, -1.0);
-  return A;
-}
-// f'(tau) = (tau e^-tau - (1 - e^-tau)) / tau^2 of the same segment (-1/2 where |tau| <= 1e-12).  The closed form is a
-// difference of nearly equal numbers for small tau (good to ~2^-53 / tau of f').  Where the reduction left n = 0
-// (|tau| < ln2 / 2: r = -tau exactly, e^r = 1 + r + r^2 p) the same polynomial gives it without one:
-// tau t - em1 = r^2 (p - 1 - r p), so f' = p (1 - r) - 1, p ~ 1/2.  The minimax fit's constant term is 11 ulp above 1/2
-// (what the higher coefficients make up for towards |r| = 0.35): taken off below |r| = 1/16, where nothing makes up
-// for it.  <= 3 units of 2^-53 below 1/64, <= 18 anywhere (checked on the host against long double).  Beyond n = 0
-// the closed form loses under three bits.
-__device__ __forceinline__ double atten_fprime(const Atten &A, double tau) {
-  return A.thin ? -0.5 : (A.n0 ? A.fp0 : (tau * A.t - A.em1) * (A.rtau * A.rtau));
 }
 
 // Regions 3 and 4 at c2 = (a, b) = ((double)(float)ry, (double)(float)(-rx)): cmplx() is

@@ -3068,26 +3068,6 @@ int launch_jac_rows_sum(double *jac, int n_rays, int n_state, int n_hid, int n_p
   return (int)hipGetLastError();
 }
 
-__device__ inline double limb_initial(const LimbOpts &o, const double *rad, size_t at, int j) {
-  if (o.init_mode == 1) return rad[at];
-  if (o.init_mode == 2) { // Calc_BB, spect_classes.py:1886
-    const double nu = o.w0 + (double)(o.g_lo + j) * o.gstep;
-    return 2 * kHcgs * (kCcgs * kCcgs) * (nu * nu * nu) / (exp(kC2 * nu / o.t_init) - 1);
-  }
-  return 0.0;
-}
-
-// Block -> (point block, ray) of the ray-batch kernels.  With the rays on the grid's slow axis the resident blocks
-// work on one or two rays at a time and every ray streams the coefficient tables from HBM again (64 rays: 4.0 GB
-// fetched for 0.13 GB of tables, the kernel bound by that).  Here the point blocks are dealt round-robin to the
-// eight XCDs (workgroup ids are) and ALL rays of a point block follow each other on one XCD: the 80 layers x 2 KB
-// of a point block are read from HBM once and by the other rays from that XCD's L2.
-__device__ inline bool limb_block(int n_pb, int n_rays, int &pb, int &ray) {
-  const int id = blockIdx.x, q = id >> 3;
-  ray = q % n_rays;
-  pb = (id & 7) + 8 * (q / n_rays);
-  return pb < n_pb;
-}
 __host__ inline unsigned limb_grid(int n_pb, int n_rays) { return (unsigned)(((n_pb + 7) / 8) * 8) * (unsigned)n_rays; }
 
 // The limb launchers' dispatch on the kernels' compile-time parameters.  by_ngas: f(integral_constant<int, NG>) for a
@@ -3120,18 +3100,6 @@ inline void by_jac_kinds(bool layer, bool par, F &&f) {
   if (layer && par) f(std::true_type{}, std::true_type{});
   else if (layer) f(std::true_type{}, std::false_type{});
   else f(std::false_type{}, std::true_type{});
-}
-
-// abs / emi of every gas at ofs = row n_pts + point: one segment's coefficients in the ray-batch kernels that load a
-// segment ahead (where the loads are interleaved with those of the columns they are written out).
-template <int NG>
-__device__ __forceinline__ void limb_load_coef(const double *__restrict__ abs_c, const double *__restrict__ emi_c, size_t gstride,
-                                               size_t ofs, double (&a)[NG], double (&e)[NG]) {
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    a[g] = abs_c[g * gstride + ofs];
-    e[g] = emi_c[g * gstride + ofs];
-  }
 }
 
 template <int NG>
@@ -3343,295 +3311,9 @@ __global__ __launch_bounds__(256) void sr_limb_jac_layer_kernel(
     if (p0 + q < n_layers) jac[((size_t)ray * n_layers + p0 + q) * n_pts + j] = J[q];
 }
 
-// Where the recursion kernels with a band epilogue (BANDS = true: sr_limb_fold_sens_lds_kernel, sr_limb_jac_state_kernel)
-// find the instrument step's weight table and leave their partial sums; see the comment above the former.
-struct FoldBands {
-  const double *Wt;  // [band tiles][n_pts][16]
-  const int *range;  // [n_bands][2]
-  double *part;
-  int n_bands;
-};
-constexpr int kLowresTables = 3; // the weight tables of a call with the instrument derivatives: value, d / d centre, d / d ln width
-constexpr int kBandRow = 68; // doubles per row of a wave's tile of values (64 + padding: rows 8 banks apart)
-// the buffer limb_initial() reads with init_mode 1 (which the host refuses for the state kernel): none with BANDS
-__device__ inline const double *limb_state_init_src(const double *jac) { return jac; }
-__device__ inline const double *limb_state_init_src(const FoldBands &) { return nullptr; }
-
-// the state kernel's trailing parameter pack: dabs and demi (ROWS), then the LevelGasTabs of a call with several level gases
-template <class... T>
-inline constexpr bool kStateSeveralGases = (std::is_same_v<T, LevelGasTabs> || ...);
-template <class... R>
-__device__ __forceinline__ const double *state_row_spectrum(int which, const double *dabs, const double *demi, const R &...) {
-  return which == 0 ? dabs : demi;
-}
-__device__ __forceinline__ const LevelGasTabs &state_level_gases(const LevelGasTabs &g) { return g; }
-template <class T, class... R>
-__device__ __forceinline__ const LevelGasTabs &state_level_gases(const T &, const R &...r) { return state_level_gases(r...); }
-
-// Derivatives w.r.t. LEVEL parameters of one level-factored gas (sr_limb_rays_jac_level_dev, COLS = false) or w.r.t. a
-// MIXED state vector of column and level parameters in one pass (sr_limb_rays_jac_state_dev, COLS = true).  The gas's
-// coefficients are abs[r] = sum_L pop[r][L] A_L[row[r]], emi[r] likewise with E_L (the pair tables of
-// sr_glevel_pairs_dev), and level parameter p moves the population of level lev[p] on coefficient row r by c[p][r].
-// Both kinds feed the same recursion,
-//   J_p <- J_p t + (-I t dtau_p + dE_p f + E f' dtau_p),
-// and differ only in where dtau_p and dE_p come from:
-//   column parameter of gas g (as sr_limb_jac_kernel):  dtau = a_g D,  dE = e_g D,  D = dcol[p][s]
-//   level parameter of level L:  dtau = c u A_L[row[r]],  dE = c u E_L[row[r]]   (u the column of `gas`, c = c[p][r];
-//                                the per-layer recursion above with dabs / demi replaced by table spectra times c)
-// so a ray is walked once per block of NP parameters whatever their kinds: NP accumulators per thread, blocks of NP
-// parameters on blockIdx.z.  The host lists the column parameters first (caller's order), then the level parameters in
-// level order, and cuts the list into blocks of NP: in a block the column slots are slots 0 .. nc - 1 and stand for the
-// consecutive parameters blockIdx.z NP + q (their dcol rows need no index table), the level slots follow in level order.
-// blk [n_blocks][2] = nc, and the column slots' gases, two bits each.  Per (parameter block, coefficient row) the host
-// lists the entries (slot, level, c) with c != 0 in level order (LevelEnt): one d = -I t dtau_L + dE_L f + E f' dtau_L
-// per level touched, J_slot += c d per entry.  A block works on one ray, so nc, the gases, the D and the entry lists are
-// wave-uniform: scalar loads, scalar branches, the accumulators indexed statically.  A column slot costs its D (a scalar
-// load, all of a segment's issued together ahead of the exponential), a multiplication and an FMA on top of one
-// (dsrc - I t a_g) per gas; a segment none of the block's level slots touches costs them J *= t.
-// COLS = false compiles every column-slot line out: dcol and blk are never read and may be null, all slots are level
-// slots.  The level slots' arithmetic is the same in both instances, operation for operation.
-// Coefficients of segment s + 1 are loaded while s is worked on (a ray's segments are a dependent chain); rays and
-// point blocks by limb_block(): all rays of a point block on one XCD, so that the table rows they share are read from
-// HBM once.
-// ROWS = true adds a third kind (sr_limb_rays_jac_state_rows_dev): a ROW parameter p acts through the coefficients of
-// every gas, with a weight w[p][r] per coefficient row (kinetic-temperature nodes: dabs / demi = d abs / dT, d emi / dT,
-// [NG][n_layers][n_pts], the columns held fixed),
-//   row parameter:  dtau = w sum_g u_g dabs_g[r],  dE = w sum_g u_g demi_g[r]
-// sr_limb_jac_layer_kernel's expression contracted with the weights inside the recursion.  The row slots ride on the entry
-// lists: behind a row's level entries the host appends one entry per row slot with w != 0, its level kLevelEntRows and
-// c = w, so the sums are formed once per segment (2 NG loads at (g, r, j); the columns u_g are read again there, scalar
-// loads that hit the scalar cache, rather than kept in scalar registers over the exponential) and every row slot costs
-// its one multiply-add; a row no row slot weights costs nothing.  dabs and demi are the kernel's last two arguments and
-// exist with ROWS = true only (row_spectra, empty otherwise): the ROWS = false instances keep their argument block and
-// with it their machine code, instruction for instruction.
-// BANDS = true (sr_limb_rays_state_bands_dev): the instrument bands in the epilogue, as sr_limb_fold_sens_lds_kernel<., true>
-// integrates them.  The recursion is the same, operation for operation; at its end a wave's values -- its NP accumulators,
-// and in parameter block 0 the radiance -- go through the wave's own tile in LDS (row q = slot q, row NP = the radiance) and
-// are multiplied with the 16-band tiles of Wt by v_mfma_f64_16x16x4: ONE partial sum per (spectrum, band, wave) in `part`
-// [(row n_slots + 4 pb + wave) n_tiles + tile][16], rows as sr_retrieval_forward_dev orders them (row ray = the radiance,
-// row n_rays + ray n_par + p = parameter p), which sr_lowres_sum_blocks_kernel adds.  A block writes the rows of its own
-// slots (slot_par >= 0), block 0 the radiance row too.  NP = 16 and the radiance are 17 rows, one more than an MFMA tile:
-// block 0 alone runs a SECOND row tile that holds the radiance (NP = 8: nine rows, one tile).  No lane leaves early: a
-// wave needs its 64 lanes for the product, so lanes beyond the grid work on its last point (`live` false) and put exact
-// zeros into the tile; waves that lie wholly beyond the grid leave (the sum kernel reads only slots inside a band's point
-// range).  An accumulator no segment of the ray touches is an exact 0 and so is every one of its sums.  `jac` is the
-// FoldBands of the call in these instances and rad is not used; the BANDS = false instances keep their argument block,
-// their early exit and their stores: the same machine code as before the parameter existed.
-// SEVERAL level-factored gases (sr_limb_rays_jac_state_gases_dev, sr_limb_rays_state_bands_gases_dev): the parameter pack
-// ends in a LevelGasTabs -- the tables, their row counts and the batch gases of up to four level gases, by value in the
-// argument block -- and an entry's `level` is level | level gas << kLevelEntGasShift (the host sorts the level slots by
-// level gas, then level, so "two loads and one d per distinct level" holds as it stands: the comparison of the packed
-// words is the comparison of (level gas, level)).  A level slot of level gas k then reads
-//   dtau = c u_{gas[k]} A^k_L[row_k[r]],  dE = c u_{gas[k]} E^k_L[row_k[r]],  row_k = coef_row + k n_layers,
-// the table pointer, the row count and the gas index by scalar loads from the argument block where the level changes, the
-// column u by a scalar load that hits the scalar cache (as the ROWS branch reads its columns: nothing of this is kept
-// in scalar registers over the exponential; the COLS instances sit at the scalar-register limit).  The recursion term,
-// the row slots, the kLevelEntRows sentinel and the band epilogue are untouched; gas, tab and n_tab_rows are not read.
-// The instances without a LevelGasTabs keep their argument block and their machine code.
-// INSTR = true (sr_limb_rays_state_bands_instr_dev, BANDS instances only): the two instrument derivatives of the radiance's
-// bands, d / d centre and d / d ln width (sr_lowres_weights_kernel).  They are band integrals of the radiance alone with
-// other weights, and those weights lie in Wt as further band tiles (table k at tile k n_tiles + tile, k = 1, 2): in
-// parameter block 0 the tile loop of the row tile that holds the radiance runs over them too -- the same A operands, the
-// same MFMA chain -- and stores that ONE row, to the rows of parameters n_par - 2 and n_par - 1 (the host counts the two
-// instrument rows into n_par: they are the last two "parameters" of every ray, so the rows of `part`, the sum kernel and
-// the field of view take them as they are).  slot_par never names them.  The recursion, every other row and the
-// INSTR = false instances are untouched: same argument block, same machine code.
-template <int NG, int NP, bool COLS, bool ROWS, bool BANDS, bool INSTR, class... RowSpectra>
-__global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
-    const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
-    const int *__restrict__ seg_off, const int *__restrict__ seg_layer, const double *__restrict__ col,
-    const double *__restrict__ dcol, LimbOpts o, int n_rays, int gas, const double *__restrict__ tab, int n_tab_rows,
-    const int *__restrict__ coef_row, const int *__restrict__ blk, const int *__restrict__ ent_off,
-    const LevelEnt *__restrict__ ent, const int *__restrict__ slot_par, int n_par, double *__restrict__ rad,
-    std::conditional_t<BANDS, FoldBands, double *__restrict__> jac, RowSpectra... row_spectra) {
-  static_assert(NP <= 16 && NG <= 4, "blk packs the gases of 16 column slots, two bits each");
-  static_assert(BANDS || !INSTR, "the instrument rows are band integrals");
-  constexpr bool GASES = kStateSeveralGases<RowSpectra...>;
-  static_assert(sizeof...(RowSpectra) == (ROWS ? 2 : 0) + (GASES ? 1 : 0), "dabs and demi with ROWS, then the level gases' tables, if several");
-  int pb, ray;
-  if (!limb_block((n_pts + 255) / 256, n_rays, pb, ray)) return;
-  const int jt = pb * 256 + threadIdx.x;
-  if (BANDS ? jt - (int)(threadIdx.x & 63) >= n_pts : jt >= n_pts) return; // BANDS: only whole waves beyond the grid leave
-  [[maybe_unused]] const bool live = jt < n_pts;
-  const int j = BANDS ? min(jt, n_pts - 1) : jt;
-  double I = limb_initial(o, limb_state_init_src(jac), 0, j), J[NP]; // init_mode 1 is refused by the host for this kernel
-#pragma unroll
-  for (int q = 0; q < NP; ++q) J[q] = 0.0;
-  const int nc = COLS ? blk[2 * blockIdx.z] : 0;
-  const unsigned gw = COLS ? (unsigned)blk[2 * blockIdx.z + 1] : 0u;
-  const double *dc = dcol + (size_t)blockIdx.z * NP * o.n_seg_total; // (read with nc > 0 only)
-  const int *eo = ent_off + (size_t)blockIdx.z * (n_layers + 1);
-  const int s0 = seg_off[ray], s1 = seg_off[ray + 1];
-  const size_t gstride = (size_t)n_layers * n_pts, plane = (size_t)n_tab_rows * n_pts;
-  double an[NG], en[NG];
-  if (s0 < s1) limb_load_coef<NG>(abs_c, emi_c, gstride, (size_t)seg_layer[s0] * n_pts + j, an, en);
-  for (int s = s0; s < s1; ++s) {
-    const int r = seg_layer[s];
-    double a[NG], e[NG], D[NP];
-    double tau = 0.0, E = 0.0, ug = 0.0;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      a[g] = an[g];
-      e[g] = en[g];
-      const double u = col[(size_t)g * o.n_seg_total + s];
-      tau = g == 0 ? a[g] * u : tau + a[g] * u;
-      E = g == 0 ? e[g] * u : E + e[g] * u;
-      ug = g == gas ? u : ug;
-    }
-    if (nc > 0) {
-#pragma unroll
-      for (int q = 0; q < NP; ++q) D[q] = dc[(size_t)min(q, nc - 1) * o.n_seg_total + s];
-    }
-    limb_load_coef<NG>(abs_c, emi_c, gstride, (size_t)seg_layer[min(s + 1, s1 - 1)] * n_pts + j, an, en);
-    const Atten A = attenuation(tau);
-    const double t = A.t, em1 = A.em1, f = A.f;
-    const bool thin = A.thin;
-    const double src = o.solo_absorption ? 0.0 : E * f;
-    const int e0 = eo[r], e1 = eo[r + 1];
-    double fp = 0.0, W[NG];
-    if (nc > 0 || e0 < e1) fp = atten_fprime(A, tau);
-    if (nc > 0) { // what a column slot of gas g adds per unit of its D: sr_limb_jac_kernel's (dsrc - I t a_g), once per gas
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const double dsrc = o.solo_absorption ? 0.0 : fma(E * fp, a[g], e[g] * f);
-        W[g] = dsrc - I * t * a[g];
-      }
-    }
-    // (nc and the gases are loop-invariant: left to itself the compiler keeps every slot's comparisons in scalar
-    // register pairs over the whole loop, NP NG of them, and spills; re-read through an empty asm they are formed
-    // where they are used)
-    int ncs = nc;
-    unsigned gws = gw;
-    if constexpr (COLS) asm volatile("" : "+s"(ncs), "+s"(gws));
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      if (COLS && q < ncs) { // a column slot: sr_limb_jac_kernel's update
-        if constexpr (NG == 1) {
-          J[q] = fma(J[q], t, W[0] * D[q]);
-        } else { // the gas is chosen on the scalar side: D or 0 per gas, the products with 0 add nothing
-          const unsigned gq = gws >> (2 * q) & 3u;
-          double x = W[0] * (gq == 0u ? D[q] : 0.0);
-#pragma unroll
-          for (int g = 1; g < NG; ++g) x = fma(W[g], gq == (unsigned)g ? D[q] : 0.0, x);
-          J[q] = fma(J[q], t, x);
-        }
-      } else {
-        J[q] *= t;
-      }
-    }
-    if (e0 < e1) { // the level slots
-      [[maybe_unused]] const double *tr = nullptr;
-      if constexpr (!GASES) tr = tab + (size_t)coef_row[r] * n_pts + j;
-      int lev = -1;
-      double d = 0.0;
-      for (int i = e0; i < e1; ++i) {
-        const int slot = ent[i].slot, lv = ent[i].level;
-        if (lv != lev) { // (entries in level order: two loads and one d per distinct level)
-          lev = lv;
-          bool rows = false;
-          if constexpr (ROWS) rows = lv == kLevelEntRows;
-          if (rows) { // the row slots: one d for all of them (sr_limb_jac_layer_kernel's sums)
-            if constexpr (ROWS) {
-              const double *const rs[] = {state_row_spectrum(0, row_spectra...), state_row_spectrum(1, row_spectra...)};
-              const size_t ofs = (size_t)r * n_pts + j;
-              double dtau = 0.0, dE = 0.0;
-#pragma unroll
-              for (int g = 0; g < NG; ++g) {
-                const double u = col[(size_t)g * o.n_seg_total + s];
-                dtau = fma(rs[0][g * gstride + ofs], u, dtau);
-                dE = fma(rs[1][g * gstride + ofs], u, dE);
-              }
-              d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
-            }
-          } else if constexpr (GASES) { // a level of level gas k: its table, its row map, its gas's column
-            const LevelGasTabs &lg = state_level_gases(row_spectra...);
-            const int k = lv >> kLevelEntGasShift, L = lv & kLevelEntLevelMask;
-            const size_t pl = (size_t)lg.n_tab_rows[k] * n_pts;
-            const double *tl = lg.tab[k] + (size_t)coef_row[(size_t)k * n_layers + r] * n_pts + j + (size_t)L * 2 * pl;
-            const double u = col[(size_t)lg.gas[k] * o.n_seg_total + s];
-            const double dtau = u * tl[0], dE = u * tl[pl];
-            d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
-          } else {
-            const double *tl = tr + (size_t)lv * 2 * plane;
-            const double dtau = ug * tl[0], dE = ug * tl[plane];
-            d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
-          }
-        }
-        const double v = ent[i].c * d;
-#pragma unroll
-        for (int q = 0; q < NP; ++q) J[q] += q == slot ? v : 0.0;
-      }
-    }
-    I = I * t + src;
-  }
-  if constexpr (BANDS) {
-    // Wave by wave, no block barrier (sr_limb_fold_sens_lds_kernel's epilogue): a wave's values go through ITS tile, its
-    // sums to its own slot of `part`.
-    constexpr int kV = NP + 1; // rows of a wave's tile: the slots, then the radiance
-    __shared__ double tiles[4 * kV * kBandRow];
-    const FoldBands &bd = jac;
-    const int c_lo = pb * 256, n_slots = 4 * ((n_pts + 255) / 256);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lo = lane & 15, kq = lane >> 4;
-    const int n_tiles = (bd.n_bands + 15) >> 4;
-    const bool first = blockIdx.z == 0;
-    const int n_val = first ? kV : NP; // (the radiance is block 0's)
-    double *vt = tiles + wave * (kV * kBandRow);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) vt[q * kBandRow + lane] = live ? J[q] : 0.0;
-    vt[NP * kBandRow + lane] = live && first ? I : 0.0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // A[row = lane & 15][k = lane >> 4], B[k][col = lane & 15], D[row = (lane >> 4) + 4 r][col]; row tile rt holds the
-    // values 16 rt .. 16 rt + 15 (a second one with NP = 16 in block 0 only: the radiance)
-    for (int rt = 0; 16 * rt < n_val; ++rt) {
-      const int vr = 16 * rt + lo;
-      const double *va = vt + min(vr, kV - 1) * kBandRow + kq;
-      double A[16];
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) A[ks] = vr < n_val ? va[4 * ks] : 0.0;
-      long long orow[4]; // the rows of `part` this lane's four sums belong to, or -1
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int q = 16 * rt + kq + 4 * r;
-        const int p = slot_par[blockIdx.z * NP + min(q, NP - 1)];
-        orow[r] = q < NP ? (p >= 0 ? (long long)n_rays + (long long)ray * n_par + p : -1) : (q == NP && first ? (long long)ray : -1);
-      }
-      // INSTR: in block 0 the row tile that holds the radiance (value NP: row NP & 15 of row tile NP / 16, held by the lanes
-      // kq == (NP & 3) in acc[(NP & 15) >> 2]) goes on over the tiles of the two derivative tables -- the same loop, the
-      // same operands -- and stores that one row (a second loop of its own cost 36 VGPRs and a wave per SIMD)
-      int n_tl = n_tiles;
-      if constexpr (INSTR) n_tl = first && rt == NP / 16 ? kLowresTables * n_tiles : n_tiles;
-      for (int tile = 0; tile < n_tl; ++tile) {
-        const double *wt = bd.Wt + (size_t)tile * n_pts * 16 + lo;
-        double Bv[16]; // a tile's sixteen B operands requested together
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) Bv[ks] = wt[(size_t)min(c_lo + 64 * wave + 4 * ks + kq, n_pts - 1) * 16]; // (beyond the grid A is zero)
-        v4d acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[ks], Bv[ks], acc, 0, 0, 0);
-        if constexpr (INSTR) {
-          if (tile >= n_tiles) { // (wave-uniform) table k = 1, 2, its band tile bt: the instrument row n_par - 3 + k of the ray
-            const int k = tile >= 2 * n_tiles ? 2 : 1, bt = tile - k * n_tiles;
-            const size_t row = (size_t)n_rays + (size_t)ray * n_par + (n_par - kLowresTables + k);
-            if (kq == (NP & 3)) bd.part[((row * n_slots + 4 * pb + wave) * n_tiles + bt) * 16 + lo] = acc[(NP & 15) >> 2];
-            continue;
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (orow[r] >= 0) bd.part[(((size_t)orow[r] * n_slots + 4 * pb + wave) * n_tiles + tile) * 16 + lo] = acc[r];
-      }
-    }
-  } else {
-    if (blockIdx.z == 0 && rad) rad[(size_t)ray * n_pts + j] = I;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      const int p = slot_par[blockIdx.z * NP + q];
-      if (p >= 0) jac[((size_t)ray * n_par + p) * n_pts + j] = J[q];
-    }
-  }
-}
+// (the library pins the two scalars to registers through an empty asm; a host build defines the macro to nothing)
+#define SR_PIN_SCALARS(a, b) asm volatile("" : "+s"(a), "+s"(b))
+#include "sr_limb_state.inc"
 
 // The radiance budget of a ray batch (sr_limb_rays_parts_dev): the recursion is linear in the emission, so the share
 // e_k[r] of one gas's emission -- a whole gas, or c[k][r] E_L[row[r]] of one level of the level-factored gas (plane 1 of
@@ -3794,7 +3476,6 @@ __global__ __launch_bounds__(256) void sr_limb_parts_kernel(
 //     way down and again on its way up -- one store, one read-add-store instead of four accesses.
 // Everything in a SegProg is wave-uniform (a block works on one ray): scalar loads and scalar branches.
 // ------------------------------------------------------------------------
-constexpr int kAdjEnt = 4; // column parameters a segment may touch (more: the forward-sensitivity kernel is used)
 struct __attribute__((aligned(16))) SegProg {
   int layer;            // row of the coefficient tables
   int flags;            // bit 0: first touch of the per-layer Jacobian row in this ray (store), else add
@@ -4803,7 +4484,6 @@ int launch_fold_dense(const int *plan, const double *col, const int *par_gas_hos
 size_t fold_rec_bytes(int n_rec) { return sizeof(FoldRec) * (size_t)n_rec; }
 
 int launch_fold_pack(const int *plan, const double *col, int n_gas, int n_seg, int n_rec, FoldRec *out, hipStream_t st) {
-  static_assert(kFoldPlanInts == 4 + 2 * kAdjEnt + 2, "fold plan layout");
   if (n_rec <= 0) return 0;
   hipLaunchKernelGGL(sr_fold_pack_kernel, dim3((n_rec + 63) / 64), dim3(64), 0, st, plan, col, n_gas, n_seg, n_rec, out);
   return (int)hipGetLastError();
@@ -4830,7 +4510,6 @@ int launch_limb_adjoint_fold(const double *abs_c, const double *emi_c, const dou
 }
 
 size_t adj_prog_bytes(int n_seg) { return sizeof(SegProg) * (size_t)n_seg; }
-static_assert(kAdjPlanInts == 4 + 2 * kAdjEnt, "host plan layout");
 
 int launch_adj_pack(const int *plan, const double *col, int n_gas, int n_seg, SegProg *out, hipStream_t st) {
   if (n_seg <= 0) return 0;
@@ -5444,96 +5123,7 @@ __global__ __launch_bounds__(256) void sr_lowres_weights_kernel(int n_pts, int g
   }
 }
 
-// The weights of a TABULATED instrument line shape (sr_set_ils): sr_lowres_weights_kernel with the Gaussian replaced by
-// the cubic Hermite interpolant phi^ of n_tab knots at the reduced offsets t_lo + k h, zero outside [t_lo, t_hi].  The same
-// grid, block, searches, writes (W, Wt with the zero columns of its last tile, range, the three tables with INSTR) and
-// layouts: everything downstream reads the tables as it reads the Gaussian's.
-//   window of band b: f + t_lo w <= x_i <= f + t_hi w on the fp64 nm values (n_sigma plays no part)
-//   p_i = g_i^2 1e-7 c_i:   W_i = p_i phi^(t_i) / w,   W^f_i = -p_i phi^'(t_i) / w^2,   W^w_i = -p_i (phi^ + t_i phi^') / w
-// (d / d centre per nm and d / d ln width of phi^((x - f) / w) / w, the window's membership held fixed; the derivative
-// tables on their own, not W times a factor: phi^ may vanish where phi^' does not).
-// tab [n_shapes][n_tab][2]: the knot phi_k and its slope PER KNOT INTERVAL d_k = h m_k ((phi_(k+1) - phi_(k-1)) / 2 inside,
-// the one-sided difference at the two ends; formed once on the host, sr_set_ils) -- a few KB read with plain loads, resident
-// in L2; n_shapes = 1: every band the same table, else table b for band b.  On interval k, s = (t - t_lo) / h - k:
-//   phi^  = (1 + 2 s)(1 - s)^2 phi_k + s (1 - s)^2 d_k + s^2 (3 - 2 s) phi_(k+1) + s^2 (s - 1) d_(k+1)
-//   phi^' = (6 s (s - 1) (phi_k - phi_(k+1)) + (3 s - 1)(s - 1) d_k + s (3 s - 2) d_(k+1)) / h
-// k is clamped to [0, n_tab - 2]: a point of the window whose rounded t falls a rounding outside the table, and t = t_hi
-// itself (the last knot, s = 1), stay on the table's end intervals.
-template <bool INSTR>
-__global__ __launch_bounds__(256) void sr_lowres_weights_tab_kernel(int n_pts, int g_lo, double w0, double gstep,
-                                                                    const double *__restrict__ cen, const double *__restrict__ wid,
-                                                                    const double *__restrict__ tab, int n_shapes, int n_tab,
-                                                                    double t_lo, double t_hi, int n_bands,
-                                                                    double *__restrict__ W,    // [n_bands][n_pts]
-                                                                    int *__restrict__ range,   // [n_bands][2]: j_lo, j_hi (exclusive)
-                                                                    double *__restrict__ Wt) { // [gridDim.y / 16][n_pts][16]
-  const int b = blockIdx.y;
-  if (b >= n_bands) { // the zero columns that fill the last tile of Wt
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n_pts) {
-      const size_t at = ((size_t)(b >> 4) * n_pts + j) * 16 + (b & 15);
-      Wt[at] = 0.0;
-      if constexpr (INSTR) {
-        const size_t tab_wt = (size_t)(gridDim.y >> 4) * n_pts * 16; // a table of Wt
-        Wt[tab_wt + at] = Wt[2 * tab_wt + at] = 0.0;
-      }
-    }
-    return;
-  }
-  const double f = cen[b], w = wid[b];
-  const double lo = f + t_lo * w, hi = f + t_hi * w;
-  const double h = (t_hi - t_lo) / (double)(n_tab - 1);
-  const double *shape = tab + (n_shapes > 1 ? (size_t)b * n_tab * 2 : 0);
-  auto gcm = [&](int i) { return w0 + (double)(g_lo + n_pts - 1 - i) * gstep; }; // nm index i <-> cm-1 index n-1-i
-  auto xnm = [&](int i) { return 1.e7 / gcm(i); };
-  // first i with x >= lo, first i with x > hi (x ascending in i): the two searches of sr_lowres_weights_kernel
-  int i0, i1;
-  {
-    int a = 0, c = n_pts;
-    while (a < c) { int m = (a + c) >> 1; if (xnm(m) < lo) a = m + 1; else c = m; }
-    i0 = a;
-    a = 0; c = n_pts;
-    while (a < c) { int m = (a + c) >> 1; if (xnm(m) <= hi) a = m + 1; else c = m; }
-    i1 = a; // selected: i0 .. i1-1; fewer than two points: no trapezoid
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    const bool any = i1 - i0 >= 2;
-    range[2 * b] = any ? n_pts - i1 : 0;       // cm-1 indices j = n_pts - 1 - i, i in [i0, i1)
-    range[2 * b + 1] = any ? n_pts - i0 : 0;
-  }
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n_pts) return;
-  const int i = n_pts - 1 - j;
-  double wgt = 0.0;
-  [[maybe_unused]] double wgt_f = 0.0, wgt_w = 0.0;
-  if (i >= i0 && i < i1 && i1 - i0 >= 2) {
-    const double g = gcm(i), x = 1.e7 / g, t = (x - f) / w;
-    const double q = (t - t_lo) / h;
-    const int k = min(max((int)floor(q), 0), n_tab - 2); // the clamp: see above
-    const double s = q - (double)k;
-    const double p0 = shape[2 * k], d0 = shape[2 * k + 1], p1 = shape[2 * k + 2], d1 = shape[2 * k + 3];
-    const double r = 1.0 - s;
-    const double phi = ((1.0 + 2.0 * s) * (r * r)) * p0 + (s * (r * r)) * d0 + ((s * s) * (3.0 - 2.0 * s)) * p1 - ((s * s) * r) * d1;
-    const double xl = i > i0 ? xnm(i - 1) : x, xr = i + 1 < i1 ? xnm(i + 1) : x;
-    const double p = ((g * g) * 1.e-7) * ((xr - xl) / 2.0);
-    wgt = p * phi / w;
-    if constexpr (INSTR) {
-      const double dphi = ((6.0 * s * r) * (p1 - p0) - ((3.0 * s - 1.0) * r) * d0 + (s * (3.0 * s - 2.0)) * d1) / h;
-      wgt_f = -(p * dphi) / (w * w);
-      wgt_w = -(p * (phi + t * dphi)) / w;
-    }
-  }
-  const size_t at = (size_t)b * n_pts + j, at_t = ((size_t)(b >> 4) * n_pts + j) * 16 + (b & 15);
-  W[at] = wgt;
-  Wt[at_t] = wgt;
-  if constexpr (INSTR) {
-    const size_t tab_w = (size_t)n_bands * n_pts, tab_wt = (size_t)(gridDim.y >> 4) * n_pts * 16; // a table of W, of Wt
-    W[tab_w + at] = wgt_f;
-    W[2 * tab_w + at] = wgt_w;
-    Wt[tab_wt + at_t] = wgt_f;
-    Wt[2 * tab_wt + at_t] = wgt_w;
-  }
-}
+#include "sr_lowres_weights_tab.inc"
 
 constexpr int kLowresBands = 16;   // bands per block of the apply kernel
 #ifndef SR_LOWRES_CHUNK

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "sr_device.hpp"
+#include "sr_limb_plan.hpp"
+#include "sr_limb_common.hpp"
 
 namespace sr {
 
@@ -269,11 +271,6 @@ int abscoeff_tile_points(int variant);
 // which = 0: wings kernel (writes abs/emi), 1: cores kernel (adds into them)
 int launch_abscoeff(int variant, int which, const ShardTables &t, const GridParams &gp, double *abs_out, double *emi_out,
                     hipStream_t st);
-// Options of the device LOS pipeline (include/spectrobot_hip.h: sr_los_desc)
-struct LimbOpts {
-  int n_gas, n_seg_total, solo_absorption, init_mode, g_lo;
-  double t_init, w0, gstep;
-};
 // prof[g] = sum_p x_p prof[n_gas + p] over the parameters of gas g (gases without parameters untouched)
 // x_host: HOST [n_par] (passed as kernel arguments, kVmrParArg per launch)
 constexpr int kVmrParArg = 32;
@@ -296,25 +293,8 @@ int launch_limb_jac(const double *abs_c, const double *emi_c, int n_pts, int n_l
 int launch_limb_jac_layer(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
                           int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
                           const LimbOpts &o, double *jac, hipStream_t st);
-// Level-parameter and mixed-state Jacobians (sr_limb_jac_state_kernel): one launcher over one record, StateLaunch below.
-// LevelEnt: an entry of its plan.
-struct __attribute__((aligned(16))) LevelEnt {
-  int slot, level; // accumulator of the block, level of the pair tables
-  double c;        // d pop[row][level] / d x_p
-};
-// the `level` of an entry that belongs to a row slot (StateLaunch::dabs / demi): its c is the slot's weight on the row
-constexpr int kLevelEntRows = -2;
-// several level-factored gases (StateLaunch::lgas): an entry's `level` is level | level gas << kLevelEntGasShift, and the
-// kernel's last argument holds, per level gas, the tables, their row count and the gas's index in the batch
-constexpr int kLevelEntGasShift = 16, kLevelEntLevelMask = (1 << kLevelEntGasShift) - 1;
-constexpr int kLevelGasMax = 4;
-struct LevelGasTabs {
-  const double *tab[kLevelGasMax];
-  int n_tab_rows[kLevelGasMax];
-  int gas[kLevelGasMax];
-};
-constexpr int kLevelJacNPSmall = 8, kLevelJacNPLarge = 16;
-inline int level_jac_np(int n_par) { return n_par > kLevelJacNPSmall ? kLevelJacNPLarge : kLevelJacNPSmall; }
+// Level-parameter and mixed-state Jacobians (sr_limb_jac_state_kernel): one launcher over one record, StateLaunch below
+// (LevelEnt, an entry of its plan, and LevelGasTabs: sr_limb_plan.hpp).
 struct StateLaunch {
   // The batch, as launch_limb_jac takes it.  dcol: the rows of the column parameters, caller's order (not read, and may
   // be null, without column slots).
@@ -379,19 +359,14 @@ int launch_limb_parts(const double *abs_c, const double *emi_c, int n_pts, int n
                       const int *slot_part, int n_part, double *rad, double *parts, hipStream_t st);
 // One pass per ray for radiances, per-layer and column-parameter Jacobians (sr_limb_adjoint_kernel)
 struct SegProg;
-constexpr int kAdjPlanInts = 4 + 2 * 4; // ints per segment of the host plan: layer, flags, n_ent, jrow, ent_p[4], ent_gf[4]
+// plan [n_seg][kAdjPlanInts] (sr_limb_plan.hpp: build_adj_plan)
 int launch_adj_pack(const int *plan, const double *col, int n_gas, int n_seg, SegProg *out, hipStream_t st);
 size_t adj_prog_bytes(int n_seg);
 int launch_limb_adjoint(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
                         int n_layers, int n_jrows, int n_rays, const int *seg_off, const SegProg *prog, const int *zero_off,
                         const int *zero_row, int n_par, const LimbOpts &o, double *rad, double *jac_layer,
                         double *jac_par, hipStream_t st);
-// The layer-synchronous variant for rays that share their coefficient rows (1-D atmospheres): kAdjSyncRays rays per
-// thread, sched [n_batches][n_visits][1 + kAdjSyncRays] = layer, segment of each ray in that shell on that side (or -1)
-#ifndef SR_ADJ_SYNC_RAYS
-#define SR_ADJ_SYNC_RAYS 2 // rays per thread: 2: 1.98 ms per configs[3] set, 4: 2.14-2.19, 8: 3.69; one ray per thread (mode 2): 2.05-2.16 (tools/adjoint_probe.py)
-#endif
-constexpr int kAdjSyncRays = SR_ADJ_SYNC_RAYS;
+// The layer-synchronous variant (sched [n_batches][n_visits][1 + kAdjSyncRays]: sr_limb_plan.hpp, build_sync_schedule)
 int launch_limb_adjoint_sync(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
                              int n_layers, int n_jrows, int n_rays, const SegProg *prog, const int *zero_off,
                              const int *zero_row, int n_par, const LimbOpts &o, const int *sched, int n_visits, double *rad,
@@ -401,7 +376,6 @@ int launch_limb_adjoint_sync(const double *abs_c, const double *emi_c, const dou
 struct FoldRec;
 size_t fold_rec_bytes(int n_rec);
 int launch_fold_pack(const int *plan, const double *col, int n_gas, int n_seg, int n_rec, FoldRec *out, hipStream_t st);
-constexpr int kFoldPlanInts = 4 + 2 * 4 + 2; // layer, far segment, near segment, n_ent, ent_p[4], ent_gf[4], layer_n, jrow
 // two_rows: the two segments of a shell read different coefficient rows (3-D paths)
 int launch_limb_adjoint_fold(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
                              int n_layers, int n_jrows, int two_rows, int n_rays, const FoldRec *rec, const int *zero_off,

@@ -294,10 +294,10 @@ def test_every_band_call_takes_the_keyword_and_unbinds(monkeypatch):
 
 
 def test_the_host_build_of_the_weights_kernel_runs_clean():
-    """tools/ils_host/run.sh: sr_lowres_weights_tab_kernel's own text as a stand-alone program under AddressSanitizer and
+    """tools/host_sim/run.sh ils_host: sr_lowres_weights_tab_kernel's own text as a stand-alone program under AddressSanitizer and
     UBSan, against plain loops (see its main.cpp)."""
     here = os.path.dirname(os.path.abspath(__file__))
-    tool = os.path.join(here, "..", "tools", "ils_host", "run.sh")
-    r = subprocess.run(["bash", tool], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=600)
+    tool = os.path.join(here, "..", "tools", "host_sim", "run.sh")
+    r = subprocess.run(["bash", tool, "ils_host"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=600)
     print(r.stdout[-3000:])
     assert r.returncode == 0 and "all cases ok" in r.stdout and "FAILED" not in r.stdout and "runtime error" not in r.stdout

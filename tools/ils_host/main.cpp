@@ -1,4 +1,4 @@
-// Host build of sr_lowres_weights_tab_kernel's own text (extract.py cuts it out of sr_kernels.hip): the blocks and threads of
+// Host build of sr_lowres_weights_tab_kernel's own text (spectrobot_amd/csrc/sr_lowres_weights_tab.inc, the file the library compiles): the blocks and threads of
 // its launch walked one after the other.  Every buffer has exactly the size the launcher gives it and starts as NaN, so that
 // AddressSanitizer sees an index beyond it and the comparison a place that was not written.  Against plain loops written
 // here (long double, the slopes m_k per unit of t, the window by a linear scan): W, Wt with the zero columns of its last
@@ -7,26 +7,11 @@
 // 19 and 33 bands (a partial last tile of Wt) and 16 (none); a band whose window's lower end is bitwise a grid point
 // (t = t_lo exactly there), one whose upper end is (t = t_hi: the last knot, interval n_tab - 2 with s = 1 by the clamp) and
 // one with a grid point exactly on an interior knot: those three weights are p phi_k / w to a few ulp.  Built with
-// AddressSanitizer and UBSan by run.sh: indexing, clamp, table and tile mapping on a machine without a GPU -- not the
+// AddressSanitizer and UBSan by tools/host_sim/run.sh ils_host: indexing, clamp, table and tile mapping on a machine without a GPU -- not the
 // compiled gfx950 code.
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <random>
-#include <vector>
-#define __device__
-#define __global__
-#define __host__
-#define __restrict__
-#define __launch_bounds__(x)
-using std::max;
-using std::min;
-struct Dim { unsigned x = 1, y = 1, z = 1; };
-static Dim threadIdx, blockIdx, blockDim, gridDim;
+#include "hip_on_host.hpp"
 namespace sr {
-#include "kernel_text.inc"
+#include "sr_lowres_weights_tab.inc"
 }
 
 struct Case { int n_pts, g_lo, n_bands, n_shapes, n_tab; double t_lo, t_hi; };

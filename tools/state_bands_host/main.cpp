@@ -1,81 +1,18 @@
-// Host build of sr_limb_jac_state_kernel's own text (extract.py cuts it out of sr_kernels.hip, with level_jac_plan out of
-// sr_api.hip): a block is 256 threads, a wave's barrier a real barrier, v_mfma_f64_16x16x4 emulated in its operand layout,
+// Host build of sr_limb_jac_state_kernel's own text and of its host plan (sr_limb_state.inc and sr_limb_plan.hpp, the files the library
+// compiles, behind tools/host_sim/hip_on_host.hpp with threaded lanes): a block is 256 threads, a wave's barrier a real barrier, v_mfma_f64_16x16x4 emulated in its operand layout,
 // exact division for the reciprocal.  Every case runs the BANDS = false and the BANDS = true instance on the same inputs
 // and reads the partial sums as sr_lowres_sum_blocks_kernel does (`part` starts as NaN: a slot that is read must have
 // been written): |fused - sum_j spectrum_j W_j| <= 1e-12 of the row's largest band, exact zeros for all-zero spectra and
 // the band outside the grid.  Then the INSTR = true instance with two more weight tables behind the first (further band
 // tiles of Wt) and two more parameter rows per ray: its value and parameter rows must be the BANDS instance's bit for bit,
-// its two instrument rows the plain sums of the radiance with tables 1 and 2 -- also for no parameter at all.  Built with AddressSanitizer and UBSan by run.sh: indexing, plan, tile and row mapping on a
+// its two instrument rows the plain sums of the radiance with tables 1 and 2 -- also for no parameter at all.  Built with AddressSanitizer and UBSan by tools/host_sim/run.sh state_bands_host: indexing, plan, tile and row mapping on a
 // machine without a GPU -- not the compiled gfx950 code.
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <numeric>
-#include <pthread.h>
-#include <random>
-#include <type_traits>
-#include <vector>
-#define __device__
-#define __global__
-#define __host__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __shared__ static
-using std::min;
-struct Dim { unsigned x = 0, y = 0, z = 0; };
-static thread_local Dim threadIdx;
-static Dim blockIdx;
-typedef double v4d __attribute__((ext_vector_type(4)));
-static pthread_barrier_t g_bar[4];
-static double g_opA[4][64], g_opB[4][64];
-#define __builtin_amdgcn_fence(a, b) ((void)0)
-static void wave_barrier() { pthread_barrier_wait(&g_bar[threadIdx.x >> 6]); }
-#define __builtin_amdgcn_wave_barrier wave_barrier
-// D[i][j] += sum_k A[i][k] B[k][j]; A: lane = 16 k + i, B: lane = 16 k + j, D: lane = 16 (i % 4) + j, register i / 4
-static v4d mfma(double a, double b, v4d acc, int, int, int) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  g_opA[w][lane] = a;
-  g_opB[w][lane] = b;
-  wave_barrier();
-  for (int r = 0; r < 4; ++r) {
-    const int i = (lane >> 4) + 4 * r, j = lane & 15;
-    double v = acc[r];
-    for (int k = 0; k < 4; ++k) v = std::fma(g_opA[w][16 * k + i], g_opB[w][16 * k + j], v);
-    acc[r] = v;
-  }
-  wave_barrier();
-  return acc;
-}
-#define __builtin_amdgcn_mfma_f64_16x16x4f64 mfma
-static inline double fma3(double a, double b, double c) { return std::fma(a, b, c); }
-template <int NR> static inline double fast_rcp(double d) { return 1.0 / d; }
+#define HOST_SIM_THREADED_LANES
+#include "hip_on_host.hpp"
 namespace sr {
-#include "kernel_text.inc"
-#include "plan_text.inc"
+#include "sr_limb_state.inc"
 }
 using namespace sr;
-
-template <class F> struct Thunk { F f; unsigned tid; };
-template <class F> static void *run_thread(void *p) {
-  auto *t = static_cast<Thunk<F> *>(p);
-  threadIdx.x = t->tid;
-  t->f();
-  return nullptr;
-}
-template <class F> static void launch(unsigned gx, unsigned gz, F f) {
-  for (unsigned z = 0; z < gz; ++z)
-    for (unsigned x = 0; x < gx; ++x) {
-      blockIdx.x = x; blockIdx.z = z;
-      for (auto &b : g_bar) pthread_barrier_init(&b, nullptr, 64);
-      std::vector<pthread_t> th(256);
-      std::vector<Thunk<F>> tk(256, Thunk<F>{f, 0});
-      for (unsigned t = 0; t < 256; ++t) { tk[t].tid = t; pthread_create(&th[t], nullptr, run_thread<F>, &tk[t]); }
-      for (auto &t : th) pthread_join(t, nullptr);
-      for (auto &b : g_bar) pthread_barrier_destroy(&b);
-    }
-}
 
 template <int NG, bool COLS, bool ROWS>
 static int run_case(int n_pts, int n_col, int n_lev, int n_row, int n_bands, int init_mode, int solo, unsigned seed) {

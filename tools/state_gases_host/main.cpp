@@ -1,52 +1,17 @@
-// Host build of sr_limb_jac_state_kernel's own text with its host plan (tools/state_bands_host/extract.py cuts both out of
-// the sources) for the instances that take the level parameters of SEVERAL level-factored gases: a block is 256 threads
+// Host build of sr_limb_jac_state_kernel's own text with its host plan (sr_limb_state.inc and sr_limb_plan.hpp, the files the
+// library compiles, behind tools/host_sim/hip_on_host.hpp) for the instances that take the level parameters of SEVERAL level-factored gases: a block is 256 threads
 // run one after the other (no band epilogue here, so no barrier is needed), exact division for the reciprocal.  Every case
 // plans and runs ONE pass for two or three level gases -- tables of different levels and rows, row maps of their own,
 // the level parameters interleaved in the caller's order -- and, per level gas, the one-gas instance on the same inputs:
 // the level rows of gas k must be bit for bit those of its own pass, the column and row rows and the radiances bit for
 // bit those of every pass, every element written (outputs start as NaN).  Built with AddressSanitizer and UBSan by
-// run.sh: the plan for mixed blocks and every index the kernel forms from it, on a machine without a GPU -- not the
+// tools/host_sim/run.sh state_gases_host: the plan for mixed blocks and every index the kernel forms from it, on a machine without a GPU -- not the
 // compiled gfx950 code.
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <numeric>
-#include <random>
-#include <type_traits>
-#include <vector>
-#define __device__
-#define __global__
-#define __host__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __shared__ static
-using std::min;
-struct Dim { unsigned x = 0, y = 0, z = 0; };
-static Dim threadIdx, blockIdx;
-typedef double v4d __attribute__((ext_vector_type(4)));
-// (the band epilogue is parsed, never instantiated here)
-#define __builtin_amdgcn_fence(a, b) ((void)0)
-#define __builtin_amdgcn_wave_barrier() ((void)0)
-static v4d no_mfma(double, double, v4d acc, int, int, int) { return acc; }
-#define __builtin_amdgcn_mfma_f64_16x16x4f64 no_mfma
-static inline double fma3(double a, double b, double c) { return std::fma(a, b, c); }
-template <int NR> static inline double fast_rcp(double d) { return 1.0 / d; }
+#include "hip_on_host.hpp"
 namespace sr {
-#include "kernel_text.inc"
-#include "plan_text.inc"
+#include "sr_limb_state.inc"
 }
 using namespace sr;
-
-template <class F> static void launch(unsigned gx, unsigned gz, F f) {
-  for (unsigned z = 0; z < gz; ++z)
-    for (unsigned x = 0; x < gx; ++x)
-      for (unsigned t = 0; t < 256; ++t) {
-        blockIdx.x = x; blockIdx.z = z; threadIdx.x = t;
-        f();
-      }
-}
 
 static bool same(const double *a, const double *b, size_t n) { return std::memcmp(a, b, n * sizeof(double)) == 0; }
 

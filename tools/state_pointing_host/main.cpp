@@ -1,53 +1,18 @@
-// Host build of sr_limb_jac_state_kernel's own text with its host plan (tools/state_bands_host/extract.py cuts both out of
-// the sources) for the HIDDEN column slots of the pointing derivative: level_jac_plan with n_hid = n_gas, slot g of gas g
+// Host build of sr_limb_jac_state_kernel's own text with its host plan (sr_limb_state.inc and sr_limb_plan.hpp, the files the
+// library compiles, behind tools/host_sim/hip_on_host.hpp) for the HIDDEN column slots of the pointing derivative: level_jac_plan with n_hid = n_gas, slot g of gas g
 // behind the caller's column slots, its row of dcol behind theirs, its row of jac behind the state's.  A block is 256
 // threads run one after the other (no band epilogue here), exact division for the reciprocal.  Every case plans and runs
 // ONE pass with the hidden slots and compares it with the pass without them -- the radiance and every state row bit for
 // bit -- and, per gas, with a pass whose only parameter is one column parameter of that gas on the hidden slot's D row:
 // the hidden row bit for bit; every element written (outputs start as NaN), the row sum as the device's small kernel
-// forms it.  Built with AddressSanitizer and UBSan by run.sh: the plan for hidden slots (block boundaries at 8 and 16
+// forms it.  Built with AddressSanitizer and UBSan by tools/host_sim/run.sh state_pointing_host: the plan for hidden slots (block boundaries at 8 and 16
 // slots, row placement) and every index the kernel forms from it, on a machine without a GPU -- not the compiled gfx950
 // code.
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <numeric>
-#include <random>
-#include <type_traits>
-#include <vector>
-#define __device__
-#define __global__
-#define __host__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __shared__ static
-using std::min;
-struct Dim { unsigned x = 0, y = 0, z = 0; };
-static Dim threadIdx, blockIdx;
-typedef double v4d __attribute__((ext_vector_type(4)));
-// (the band epilogue is parsed, never instantiated here)
-#define __builtin_amdgcn_fence(a, b) ((void)0)
-#define __builtin_amdgcn_wave_barrier() ((void)0)
-static v4d no_mfma(double, double, v4d acc, int, int, int) { return acc; }
-#define __builtin_amdgcn_mfma_f64_16x16x4f64 no_mfma
-static inline double fma3(double a, double b, double c) { return std::fma(a, b, c); }
-template <int NR> static inline double fast_rcp(double d) { return 1.0 / d; }
+#include "hip_on_host.hpp"
 namespace sr {
-#include "kernel_text.inc"
-#include "plan_text.inc"
+#include "sr_limb_state.inc"
 }
 using namespace sr;
-
-template <class F> static void launch(unsigned gx, unsigned gz, F f) {
-  for (unsigned z = 0; z < gz; ++z)
-    for (unsigned x = 0; x < gx; ++x)
-      for (unsigned t = 0; t < 256; ++t) {
-        blockIdx.x = x; blockIdx.z = z; threadIdx.x = t;
-        f();
-      }
-}
 
 static bool same(const double *a, const double *b, size_t n) { return std::memcmp(a, b, n * sizeof(double)) == 0; }
 
