@@ -2563,7 +2563,8 @@ __global__ __launch_bounds__(64 * kMcWingWaves) void sr_wings_mc_kernel(
 
 // Image width by what fits: two workgroups of kMcImage points per CU when their planes allow (24 planes x 258 doubles =
 // 49.5 KB), else 128-point images (36 planes -- the three ctypes of twelve levels -- are 74 KB at 256 points: ONE workgroup,
-// eight waves per CU; at 128 points 37 KB: two).  Up to 146 planes (64 levels' pair tables).
+// eight waves per CU; at 128 points 37 KB: two).  Up to 31 planes at 256 points and up to 141 at 128 (64 levels' pair
+// tables are 128 planes, the three ctypes of 47 levels 141; more planes: 0, one coefficient op per level).
 size_t zones_mc_lds(int n_ch, int wt) { return sizeof(double) * (size_t)n_ch * (wt + 2) + sizeof(int) * (size_t)kMcWaves * 2 * 4 * 64; }
 int zones_mc_image(int n_ch) {
   if (2 * zones_mc_lds(n_ch, kMcImage) <= (size_t)160 * 1024) return kMcImage;
