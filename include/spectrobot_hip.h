@@ -960,6 +960,33 @@ int sr_set_band_fusion(int on);
  * (sr_limb_kernel / sr_limb_split_kernel), 2 the folded sweep (sr_limb_fold_fwd_kernel: ray batches that share their
  * shells), 0 none yet.  Diagnostic (tests pin the choice: a 3-D batch with a coefficient row per LOS step must not fold). */
 int sr_last_limb_route(void);
+/* Parameter blocks PER RAY in the mixed-state calls (everything that runs sr_limb_jac_state_kernel:
+ * sr_limb_rays_jac_level_dev, sr_limb_rays_jac_state_dev, _jac_state_rows_dev, sr_limb_rays_state_bands_dev and their
+ * _gases, _instr and _path forms).  0 (default): the parameter list of the BATCH is cut into blocks of 8 or 16 and every
+ * ray is walked once per block, whether or not it touches one of the block's parameters.  1: every ray lists the
+ * parameters that touch it -- a column parameter iff par_w[p] is non-zero at one of the ray's sample points, a level or
+ * row parameter iff par_c[p][r] / par_t[p][r] is non-zero on the coefficient row r of one of its segments, the hidden
+ * pointing slots always -- in the dense plan's order, and cuts its own list into blocks of 8 (no ray is touched by more
+ * than 8) or 16; a ray is walked once per block of ITS list, at least once (the radiance).  The rows of parameters that
+ * do not touch a ray are exact zeros in both settings (with 1 the output is cleared on the stream ahead of the launch);
+ * the other rows and the radiances are the same arithmetic, slot for slot.  Signatures, layouts, limits and refusals
+ * are unchanged.  Process-wide, read once at a call's entry, as sr_set_band_fusion.  Latitude-box states (a ray crosses
+ * two or three of the boxes) and mixed 1-D states with many altitude nodes are what it is for; opt-in.
+ * sr_last_state_route: the plan of the calling thread's most recent such call, 1 dense, 2 per ray, 0 none yet;
+ * sr_last_state_walks: its (ray, block) pairs, the number of times a ray was walked.
+ * sr_state_ray_plan: the per-ray plan itself on the host, for tests and tools -- no device is touched.  The arguments as
+ * the state calls name them (par_lgas NULL: one level gas; n_hid: hidden pointing slots, 0 .. 4).  sizes4: np, the
+ * largest block count of a ray (gridDim.z), the number of ray blocks n_rb, the number of entries n_ent.  The arrays may
+ * each be NULL (a first call for the sizes): ray_blk_off [n_rays + 1], blk [n_rb][2], col_row [n_rb][np],
+ * ent_off [n_rb][n_layers + 1], slot_par [n_rb][np], ent_slot / ent_level / ent_c [n_ent].
+ * Checked against the extended-precision recursion and the dense plan (tests/test_gpu_state_rayblocks.py). */
+int sr_set_state_ray_blocks(int on);
+int sr_last_state_route(void);
+int64_t sr_last_state_walks(void);
+int sr_state_ray_plan(const sr_los_desc *los, int n_layers, int n_col, const int32_t *par_gas, const double *par_w, int n_lev,
+                      const int32_t *par_lgas, const int32_t *par_level, const double *par_c, int n_row, const double *par_t,
+                      int n_hid, int32_t *sizes4, int32_t *ray_blk_off, int32_t *blk, int32_t *col_row, int32_t *ent_off,
+                      int32_t *slot_par, int32_t *ent_slot, int32_t *ent_level, double *ent_c);
 /* Tuning knob of the exact wings kernel: grid points per lane (4 or 8; default 8). */
 int sr_set_points_per_lane(int p);
 

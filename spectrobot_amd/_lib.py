@@ -209,6 +209,11 @@ SYMBOLS = {
     "sr_los_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "sr_set_jac_layer_mode": (C.c_int, [C.c_int]),
     "sr_last_limb_route": (C.c_int, []),
+    "sr_set_state_ray_blocks": (C.c_int, [C.c_int]),
+    "sr_last_state_route": (C.c_int, []),
+    "sr_last_state_walks": (C.c_int64, []),
+    "sr_state_ray_plan": (C.c_int, [C.POINTER(LosDesc), C.c_int, C.c_int, ip, dp, C.c_int, ip, ip, dp, C.c_int, dp, C.c_int,
+                                    ip, ip, ip, ip, ip, ip, ip, ip, dp]),
     "sr_set_far_field": (C.c_int, [C.c_int]),
     "sr_set_overlap": (C.c_int, [C.c_int]),
     "sr_set_kernel_repeat": (C.c_int, [C.c_int, C.c_int]),

@@ -319,6 +319,7 @@ std::atomic<int> g_far_field{3}; // 1: far wings by per-line local expansions, 2
 std::atomic<int> g_overlap{1};   // 1 (default): the decoupled, phased pipeline; 0: kernels one after the other
 // sr_set_jac_layer_mode; SR_JAC_LAYER_MODE (environment, read once at load): its initial value, for A/B runs of whole programs
 std::atomic<int> g_band_fusion{1}; // sr_set_band_fusion
+std::atomic<int> g_state_ray_blocks{0}; // sr_set_state_ray_blocks
 std::atomic<int> g_jac_layer_forward{[] { const char *e = getenv("SR_JAC_LAYER_MODE"); const int v = e ? atoi(e) : 0; return v >= 0 && v <= 3 ? v : 0; }()};
 // sr_set_kernel_repeat: a measurement hook of the SERIAL schedule -- kernel g_repeat_kernel of every call is launched
 // g_repeat_n times back to back (energy per launch: tools/energy_by_kernel.py loops one kernel for seconds beside a power
@@ -627,6 +628,36 @@ double sr_far_field_min_distance(int level, int pole_margin) {
 
 int sr_set_band_fusion(int on) {
   g_band_fusion.store(on ? 1 : 0);
+  return SR_OK;
+}
+
+int sr_set_state_ray_blocks(int on) {
+  g_state_ray_blocks.store(on ? 1 : 0);
+  return SR_OK;
+}
+
+// ray_jac_plan on the host, for tests and tools: no device, no stream
+int sr_state_ray_plan(const sr_los_desc *los, int n_layers, int n_col, const int32_t *par_gas, const double *par_w, int n_lev,
+                      const int32_t *par_lgas, const int32_t *par_level, const double *par_c, int n_row, const double *par_t,
+                      int n_hid, int32_t *sizes4, int32_t *ray_blk_off, int32_t *blk, int32_t *col_row, int32_t *ent_off,
+                      int32_t *slot_par, int32_t *ent_slot, int32_t *ent_level, double *ent_c) {
+  LosShape shape;
+  if (!sizes4 || n_layers <= 0 || n_lev < 0 || n_row < 0 || n_hid < 0 || n_hid > 4) return SR_ERR_ARG;
+  if ((n_lev > 0 && (!par_level || !par_c)) || (n_row > 0 && !par_t)) return SR_ERR_ARG;
+  const int rc = check_los_par(los, n_layers, n_col, par_gas, par_w, &shape);
+  if (rc) return rc;
+  const RayJacPlan R = ray_jac_plan(los, n_col, par_gas, par_w, n_lev, par_level, par_c, n_layers, n_row, par_t, par_lgas, n_hid);
+  sizes4[0] = R.np, sizes4[1] = R.n_blocks, sizes4[2] = R.ray_blk_off.back(), sizes4[3] = (int32_t)R.ent.size();
+  if (ray_blk_off) std::copy(R.ray_blk_off.begin(), R.ray_blk_off.end(), ray_blk_off);
+  if (blk) std::copy(R.blk.begin(), R.blk.end(), blk);
+  if (col_row) std::copy(R.col_row.begin(), R.col_row.end(), col_row);
+  if (ent_off) std::copy(R.ent_off.begin(), R.ent_off.end(), ent_off);
+  if (slot_par) std::copy(R.slot_par.begin(), R.slot_par.end(), slot_par);
+  for (size_t i = 0; i < R.ent.size(); ++i) {
+    if (ent_slot) ent_slot[i] = R.ent[i].slot;
+    if (ent_level) ent_level[i] = R.ent[i].level;
+    if (ent_c) ent_c[i] = R.ent[i].c;
+  }
   return SR_OK;
 }
 
@@ -2468,6 +2499,10 @@ int sr_los_columns_dz(const sr_los_desc *los, const sr_los_path *path, double *d
 
 static thread_local int g_last_limb_route = 0;
 int sr_last_limb_route(void) { return g_last_limb_route; }
+static thread_local int g_last_state_route = 0;     // limb_jac_state: 1 the dense plan, 2 parameter blocks per ray
+static thread_local int64_t g_last_state_walks = 0; // its (ray, block) pairs
+int sr_last_state_route(void) { return g_last_state_route; }
+int64_t sr_last_state_walks(void) { return g_last_state_walks; }
 
 } // extern "C"
 
@@ -3397,11 +3432,23 @@ static int limb_jac_state(const StateCall &c, const LosShape &shape, const void 
   const sr_level_gas *lgas = c.lev.lgas;
   const bool several = n_lgas > 1;
   const int n_hid = c.path ? b.los->n_gas : 0;
-  const LevelJacPlan P = level_jac_plan(n_col, c.col.par_gas, n_lev, c.lev.par_level, c.lev.par_c, n_layers, n_row, c.row.par_t,
-                                        several ? c.lev.par_lgas : nullptr, n_hid);
+  // the dense plan, or (sr_set_state_ray_blocks) every ray's own blocks, whose tables take the dense plan's places
+  const bool per_ray = g_state_ray_blocks.load() != 0;
+  LevelJacPlan P{};
+  RayJacPlan R{};
+  if (per_ray) {
+    R = ray_jac_plan(b.los, n_col, c.col.par_gas, c.col.par_w, n_lev, c.lev.par_level, c.lev.par_c, n_layers, n_row, c.row.par_t,
+                     several ? c.lev.par_lgas : nullptr, n_hid);
+    P.n_blocks = R.n_blocks;
+    P.blk.swap(R.blk), P.ent_off.swap(R.ent_off), P.slot_par.swap(R.slot_par), P.ent.swap(R.ent);
+  } else {
+    P = level_jac_plan(n_col, c.col.par_gas, n_lev, c.lev.par_level, c.lev.par_c, n_layers, n_row, c.row.par_t,
+                       several ? c.lev.par_lgas : nullptr, n_hid);
+  }
   static thread_local StagerRing ring;
   StagePack pk(ring.take());
   const auto p_ent = pk.copy(P.ent.data(), P.ent.size(), 1); // (no entries: a valid pointer all the same)
+  const auto p_rboff = pk.copy(R.ray_blk_off.data(), R.ray_blk_off.size()), p_crow = pk.copy(R.col_row.data(), R.col_row.size());
   const int32_t *coef_row = lgas[0].coef_row;
   std::vector<int32_t> rows_all; // several level gases: their row maps one behind the other, [n_lgas][n_layers]
   if (several && n_lev > 0) {
@@ -3439,6 +3486,9 @@ static int limb_jac_state(const StateCall &c, const LosShape &shape, const void 
   if (n_row > 0) L.dabs = c.row.dabs_c, L.demi = c.row.demi_c;
   L.rad = c.rad, L.jac = c.jac;
   if (c.bands) L.lowres_scratch = band_scratch, L.n_bands = c.bands->n_bands, L.instr = c.bands->instr;
+  if (per_ray) L.ray_blk_off = pk.dev(p_rboff), L.col_row = pk.dev(p_crow), L.np = R.np;
+  g_last_state_route = per_ray ? 2 : 1;
+  g_last_state_walks = per_ray ? (int64_t)R.ray_blk_off.back() : (int64_t)L.n_rays * P.n_blocks;
   LAUNCHCHK(launch_limb_jac_state(L, st));
   if (n_hid && !c.bands) LAUNCHCHK(launch_jac_rows_sum(c.jac, L.n_rays, L.n_par - n_hid, n_hid, L.n_pts, st));
   return mark_both(pk.slot(), *D.slot, st);

@@ -4606,19 +4606,31 @@ int launch_limb_jac_state(const StateLaunch &L, hipStream_t st) {
   const int gas = L.lgas ? -1 : L.gas, n_tab_rows = L.lgas ? 0 : L.n_tab_rows;
   const double *const tab = L.lgas ? nullptr : L.tab;
   double *const rad = bands ? nullptr : L.rad;
+  // blocks per ray: a ray's blocks write the rows of the parameters that touch it, the others read as exact zeros --
+  // cleared here, on the stream, ahead of the launch (the radiance rows of `part`, rows 0 .. n_rays - 1, are block 0's)
+  const bool per_ray = L.ray_blk_off != nullptr;
+  if (per_ray && (L.np != kLevelJacNPSmall && L.np != kLevelJacNPLarge)) return 0;
+  if (per_ray && n_row_par > 0) {
+    const size_t row = bands ? 4 * (size_t)((L.n_pts + 255) / 256) * ((L.n_bands + 15) / 16) * 16 : (size_t)L.n_pts;
+    double *const rows = bands ? bd.part + (size_t)L.n_rays * row : L.jac;
+    const hipError_t e = hipMemsetAsync(rows, 0, sizeof(double) * (size_t)L.n_rays * n_row_par * row, st);
+    if (e != hipSuccess) return (int)e;
+  }
+  const StateRayBlocks rbk{L.ray_blk_off, L.col_row};
   by_flag(L.blk != nullptr, [&](auto cols) { // no blk: the instances without column slots
-    by_level_np(level_jac_np(L.n_par), [&](auto np) {
+    by_level_np(per_ray ? L.np : level_jac_np(L.n_par), [&](auto np) {
       by_ngas(L.o.n_gas, [&](auto ng) {
         by_flag(rows, [&](auto rw) {
           by_flag(bands, [&](auto bn) {
             by_flag(L.instr, [&](auto ins) {
               by_flag(L.lgas != nullptr, [&](auto several) {
+               by_flag(per_ray, [&](auto rayblk) {
                 constexpr int NG = decltype(ng)::value, NP = decltype(np)::value;
                 constexpr bool COLS = decltype(cols)::value, ROWS = decltype(rw)::value, BANDS = decltype(bn)::value;
-                constexpr bool INSTR = decltype(ins)::value, SEVERAL = decltype(several)::value;
+                constexpr bool INSTR = decltype(ins)::value, SEVERAL = decltype(several)::value, RAYBLK = decltype(rayblk)::value;
                 // the instrument rows are band integrals; several level gases are several gases of the batch
                 if constexpr ((BANDS || !INSTR) && (NG >= 2 || !SEVERAL)) {
-                  auto launch = [&](auto... pack) {
+                  auto launch_pack = [&](auto... pack) {
                     std::conditional_t<BANDS, FoldBands, double *> out;
                     if constexpr (BANDS) out = bd;
                     else out = L.jac;
@@ -4626,11 +4638,16 @@ int launch_limb_jac_state(const StateLaunch &L, hipStream_t st) {
                                        st, L.abs_c, L.emi_c, L.n_pts, L.n_layers, L.seg_off, L.seg_layer, L.col, L.dcol, L.o, L.n_rays, gas,
                                        tab, n_tab_rows, L.coef_row, L.blk, L.ent_off, L.ent, L.slot_par, n_row_par, rad, out, pack...);
                   };
+                  auto launch = [&](auto... pack) { // the ray blocks last
+                    if constexpr (RAYBLK) launch_pack(pack..., rbk);
+                    else launch_pack(pack...);
+                  };
                   if constexpr (ROWS && SEVERAL) launch(L.dabs, L.demi, *L.lgas);
                   else if constexpr (ROWS) launch(L.dabs, L.demi);
                   else if constexpr (SEVERAL) launch(*L.lgas);
                   else launch();
                 }
+               });
               });
             });
           });

@@ -342,6 +342,13 @@ struct StateLaunch {
   const void *lowres_scratch;
   int n_bands;
   bool instr;
+  // Parameter blocks PER RAY (ray_jac_plan; the kernel's instances whose pack ends in a StateRayBlocks), ray_blk_off
+  // given: blk, ent_off and slot_par are then indexed by ray_blk_off[ray] + block, n_blocks is the largest block count
+  // of a ray, col_row [ray blocks][np] the dcol row of every column slot, np (8 or 16) the plan's slots per block.  The
+  // launcher clears the parameter rows of jac, or of the partial sums, on the stream first: a ray's blocks write the
+  // rows of its own parameters only.  ray_blk_off null (the default): the dense plan, as above.
+  const int *ray_blk_off, *col_row;
+  int np;
 };
 int launch_limb_jac_state(const StateLaunch &L, hipStream_t st);
 // Radiance budget (sr_limb_parts_kernel): the n_part parts and the background are n_part + 1 slots in blocks of

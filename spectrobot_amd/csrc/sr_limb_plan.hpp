@@ -397,4 +397,117 @@ inline LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev,
   return P;
 }
 
+// The plan PER RAY (sr_set_state_ray_blocks; the kernel's instances whose parameter pack ends in a StateRayBlocks): every
+// ray lists the parameters that touch it -- a column parameter iff par_w[p] is non-zero at one of the ray's sample points,
+// a level or row parameter iff par_c[p][r] / par_t[p][r] is non-zero on the coefficient row r of one of its segments, the
+// n_hid hidden slots always -- in level_jac_plan's order (columns, hidden, levels by (level gas, level), rows), and cuts
+// ITS list into blocks of np: 8 if no ray is touched by more than 8 parameters, else 16.  A ray has at least block 0 (the
+// radiance's), also with an empty list.  The blocks of all rays lie one behind the other: ray_blk_off [n_rays + 1] is the
+// prefix sum of the rays' block counts, and blk [.][2], col_row [.][np], ent_off [.][n_layers + 1] and slot_par [.][np]
+// are indexed by ray_blk_off[ray] + block.  col_row: the row of dcol behind each column slot (p of a caller's parameter,
+// n_col + g of hidden slot g; 0 behind the other slots), since a ray's column slots are no longer consecutive parameters.
+// The entries of (ray block, row) are the dense plan's entries of the block's parameters on that row, in its order, with
+// the block's slot numbers -- on the rows the ray has a segment on; the other rows' lists, which the ray never reads,
+// are empty (with a coefficient row per LOS step they would be n_rays times the dense plan's).  n_blocks: the largest
+// block count of a ray, the launch's gridDim.z.
+struct RayJacPlan {
+  int np, n_blocks;
+  std::vector<int> ray_blk_off, blk, col_row, ent_off, slot_par;
+  std::vector<LevelEnt> ent;
+};
+inline RayJacPlan ray_jac_plan(const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lev,
+                               const int32_t *par_level, const double *par_c, int n_layers, int n_row = 0,
+                               const double *par_t = nullptr, const int32_t *par_lgas = nullptr, int n_hid = 0) {
+  const int n_rays = los->n_rays, n_state = n_col + n_lev + n_row, n_pt = los->pt_off[los->seg_off[n_rays]];
+  std::vector<int32_t> packed;
+  if (par_lgas) {
+    packed.resize((size_t)n_lev);
+    for (int p = 0; p < n_lev; ++p) packed[p] = par_level[p] | par_lgas[p] << kLevelEntGasShift;
+    par_level = packed.data();
+  }
+  const std::vector<int> order = order_by_level(n_lev, par_level);
+  // a ray's list: (kind 0 column / hidden, 1 level, 2 row; index within the kind -- a hidden slot g is column n_col + g)
+  struct Item { int kind, idx; };
+  std::vector<std::vector<Item>> lists(n_rays);
+  std::vector<std::vector<int>> rows_of(n_rays); // the distinct coefficient rows of a ray, ascending
+  std::vector<char> on_ray((size_t)std::max(n_layers, 1));
+  size_t longest = 0;
+  for (int ray = 0; ray < n_rays; ++ray) {
+    const int s0 = los->seg_off[ray], s1 = los->seg_off[ray + 1];
+    std::fill(on_ray.begin(), on_ray.end(), 0);
+    for (int s = s0; s < s1; ++s) on_ray[los->seg_layer[s]] = 1;
+    for (int r = 0; r < n_layers; ++r)
+      if (on_ray[r]) rows_of[ray].push_back(r);
+    auto weighs = [&](const double *c) { // a level or row parameter's coefficients [n_layers]
+      for (int r : rows_of[ray])
+        if (c[r] != 0.0) return true;
+      return false;
+    };
+    std::vector<Item> &lst = lists[ray];
+    for (int p = 0; p < n_col; ++p) {
+      const double *w = par_w + (size_t)p * n_pt;
+      bool nz = false;
+      for (int i = los->pt_off[s0]; i < los->pt_off[s1] && !nz; ++i) nz = w[i] != 0.0;
+      if (nz) lst.push_back(Item{0, p});
+    }
+    for (int g = 0; g < n_hid; ++g) lst.push_back(Item{0, n_col + g});
+    for (int i = 0; i < n_lev; ++i)
+      if (weighs(par_c + (size_t)order[i] * n_layers)) lst.push_back(Item{1, order[i]});
+    for (int p = 0; p < n_row; ++p)
+      if (weighs(par_t + (size_t)p * n_layers)) lst.push_back(Item{2, p});
+    longest = std::max(longest, lst.size());
+  }
+  RayJacPlan P{};
+  P.np = longest > (size_t)kLevelJacNPSmall ? kLevelJacNPLarge : kLevelJacNPSmall;
+  const int np = P.np;
+  P.ray_blk_off.assign((size_t)n_rays + 1, 0);
+  for (int ray = 0; ray < n_rays; ++ray) {
+    const int nb = std::max(1, ((int)lists[ray].size() + np - 1) / np);
+    P.ray_blk_off[ray + 1] = P.ray_blk_off[ray] + nb;
+    P.n_blocks = std::max(P.n_blocks, nb);
+  }
+  const size_t n_rb = (size_t)P.ray_blk_off[n_rays];
+  P.blk.assign(n_rb * 2, 0);
+  P.col_row.assign(n_rb * np, 0);
+  P.slot_par.assign(n_rb * np, -1);
+  P.ent_off.assign(n_rb * (n_layers + 1), 0);
+  for (int ray = 0; ray < n_rays; ++ray) {
+    const std::vector<Item> &lst = lists[ray];
+    for (int rb = P.ray_blk_off[ray]; rb < P.ray_blk_off[ray + 1]; ++rb) {
+      const int i0 = (rb - P.ray_blk_off[ray]) * np, i1 = std::min((int)lst.size(), i0 + np);
+      int nc = 0;
+      unsigned gases = 0u;
+      for (int i = i0; i < i1; ++i) {
+        const Item &it = lst[i];
+        const int q = i - i0;
+        if (it.kind == 0) {
+          gases |= (unsigned)(it.idx < n_col ? par_gas[it.idx] : it.idx - n_col) << (2 * q);
+          P.col_row[(size_t)rb * np + q] = it.idx;
+          ++nc;
+        }
+        P.slot_par[(size_t)rb * np + q] = it.kind == 0   ? (it.idx < n_col ? it.idx : n_state + (it.idx - n_col))
+                                          : it.kind == 1 ? n_col + it.idx
+                                                         : n_col + n_lev + it.idx;
+      }
+      P.blk[2 * (size_t)rb] = nc;
+      P.blk[2 * (size_t)rb + 1] = (int)gases;
+      int *eo = &P.ent_off[(size_t)rb * (n_layers + 1)];
+      size_t next_row = 0;
+      for (int r = 0; r < n_layers; ++r) {
+        eo[r] = (int)P.ent.size();
+        if (next_row == rows_of[ray].size() || rows_of[ray][next_row] != r) continue;
+        ++next_row;
+        for (int i = i0; i < i1; ++i) {
+          const Item &it = lst[i];
+          if (it.kind == 0) continue;
+          const double c = (it.kind == 1 ? par_c : par_t)[(size_t)it.idx * n_layers + r];
+          if (c != 0.0) P.ent.push_back(LevelEnt{i - i0, it.kind == 1 ? par_level[it.idx] : kLevelEntRows, c});
+        }
+      }
+      eo[n_layers] = (int)P.ent.size();
+    }
+  }
+  return P;
+}
+
 } // namespace sr

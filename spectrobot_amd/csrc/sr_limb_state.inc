@@ -23,9 +23,20 @@ template <class... R>
 __device__ __forceinline__ const double *state_row_spectrum(int which, const double *dabs, const double *demi, const R &...) {
   return which == 0 ? dabs : demi;
 }
-__device__ __forceinline__ const LevelGasTabs &state_level_gases(const LevelGasTabs &g) { return g; }
+template <class... R>
+__device__ __forceinline__ const LevelGasTabs &state_level_gases(const LevelGasTabs &g, const R &...) { return g; }
 template <class T, class... R>
 __device__ __forceinline__ const LevelGasTabs &state_level_gases(const T &, const R &...r) { return state_level_gases(r...); }
+// ... and last of all the StateRayBlocks of a launch with the parameter blocks PER RAY (RAYBLK below)
+struct StateRayBlocks {
+  const int *ray_blk_off; // [n_rays + 1]
+  const int *col_row;     // [ray blocks][NP]
+};
+template <class... T>
+inline constexpr bool kStateRayBlocks = (std::is_same_v<T, StateRayBlocks> || ...);
+__device__ __forceinline__ const StateRayBlocks &state_ray_blocks(const StateRayBlocks &b) { return b; }
+template <class T, class... R>
+__device__ __forceinline__ const StateRayBlocks &state_ray_blocks(const T &, const R &...r) { return state_ray_blocks(r...); }
 
 // Derivatives w.r.t. LEVEL parameters of one level-factored gas (sr_limb_rays_jac_level_dev, COLS = false) or w.r.t. a
 // MIXED state vector of column and level parameters in one pass (sr_limb_rays_jac_state_dev, COLS = true).  The gas's
@@ -95,6 +106,19 @@ __device__ __forceinline__ const LevelGasTabs &state_level_gases(const T &, cons
 // instrument rows into n_par: they are the last two "parameters" of every ray, so the rows of `part`, the sum kernel and
 // the field of view take them as they are).  slot_par never names them.  The recursion, every other row and the
 // INSTR = false instances are untouched: same argument block, same machine code.
+// RAYBLK (sr_set_state_ray_blocks: the parameter pack ends in a StateRayBlocks): parameter blocks PER RAY.  The dense plan
+// cuts the batch's parameter list, so every ray is walked gridDim.z times whatever it touches; here every ray has its own
+// list -- the parameters that touch it (ray_jac_plan) -- cut into its own blocks, and the tables blk, ent_off and slot_par
+// are indexed by ray_blk_off[ray] + blockIdx.z.  gridDim.z is the largest block count of a ray; a workgroup beyond its
+// ray's count leaves at once (wave-uniform, two scalar loads).  A ray's column slots are not consecutive parameters:
+// col_row [ray blocks][NP] names the row of dcol behind each, read by scalar loads.  The indices are loop-invariant and
+// left to the compiler, which keeps them over the segment loop: re-read per segment (through SR_PIN_SCALARS, so that
+// they are dead over the exponential) every D load waits for its index load, two dependent scalar loads per segment,
+// and the call was 13 % slower (DESIGN 4.7h); the instances spill fewer scalars than the dense ones either way.  The
+// recursion, the entry loop, the row slots, the level-gas lookup and the band epilogue are the same operations; `first`
+// is still blockIdx.z == 0, the radiance's block of every ray.  Rows of jac / part that no block of a ray writes are
+// cleared by the host on the stream ahead of the launch.  The instances without a StateRayBlocks keep their argument block
+// and their machine code.
 template <int NG, int NP, bool COLS, bool ROWS, bool BANDS, bool INSTR, class... RowSpectra>
 __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
@@ -105,10 +129,18 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     std::conditional_t<BANDS, FoldBands, double *__restrict__> jac, RowSpectra... row_spectra) {
   static_assert(NP <= 16 && NG <= 4, "blk packs the gases of 16 column slots, two bits each");
   static_assert(BANDS || !INSTR, "the instrument rows are band integrals");
-  constexpr bool GASES = kStateSeveralGases<RowSpectra...>;
-  static_assert(sizeof...(RowSpectra) == (ROWS ? 2 : 0) + (GASES ? 1 : 0), "dabs and demi with ROWS, then the level gases' tables, if several");
+  constexpr bool GASES = kStateSeveralGases<RowSpectra...>, RAYBLK = kStateRayBlocks<RowSpectra...>;
+  static_assert(sizeof...(RowSpectra) == (ROWS ? 2 : 0) + (GASES ? 1 : 0) + (RAYBLK ? 1 : 0),
+                "dabs and demi with ROWS, then the level gases' tables, if several, then the ray blocks, if per ray");
   int pb, ray;
   if (!limb_block((n_pts + 255) / 256, n_rays, pb, ray)) return;
+  unsigned rb = blockIdx.z; // the block's row in blk, ent_off and slot_par
+  if constexpr (RAYBLK) {
+    const int *const off = state_ray_blocks(row_spectra...).ray_blk_off;
+    const int b0 = off[ray];
+    if ((int)blockIdx.z >= off[ray + 1] - b0) return; // (the ray has fewer blocks than the longest list)
+    rb = (unsigned)b0 + blockIdx.z;
+  }
   const int jt = pb * 256 + threadIdx.x;
   if (BANDS ? jt - (int)(threadIdx.x & 63) >= n_pts : jt >= n_pts) return; // BANDS: only whole waves beyond the grid leave
   [[maybe_unused]] const bool live = jt < n_pts;
@@ -116,10 +148,10 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
   double I = limb_initial(o, limb_state_init_src(jac), 0, j), J[NP]; // init_mode 1 is refused by the host for this kernel
 #pragma unroll
   for (int q = 0; q < NP; ++q) J[q] = 0.0;
-  const int nc = COLS ? blk[2 * blockIdx.z] : 0;
-  const unsigned gw = COLS ? (unsigned)blk[2 * blockIdx.z + 1] : 0u;
-  const double *dc = dcol + (size_t)blockIdx.z * NP * o.n_seg_total; // (read with nc > 0 only)
-  const int *eo = ent_off + (size_t)blockIdx.z * (n_layers + 1);
+  const int nc = COLS ? blk[2 * rb] : 0;
+  const unsigned gw = COLS ? (unsigned)blk[2 * rb + 1] : 0u;
+  const double *dc = dcol + (RAYBLK ? (size_t)0 : (size_t)rb * NP * o.n_seg_total); // (read with nc > 0 only)
+  const int *eo = ent_off + (size_t)rb * (n_layers + 1);
   const int s0 = seg_off[ray], s1 = seg_off[ray + 1];
   const size_t gstride = (size_t)n_layers * n_pts, plane = (size_t)n_tab_rows * n_pts;
   double an[NG], en[NG];
@@ -138,8 +170,14 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
       ug = g == gas ? u : ug;
     }
     if (nc > 0) {
+      if constexpr (RAYBLK) { // the slots' rows of dcol through col_row (loop-invariant: the compiler keeps the indices)
+        const int *cr = state_ray_blocks(row_spectra...).col_row + (size_t)rb * NP;
 #pragma unroll
-      for (int q = 0; q < NP; ++q) D[q] = dc[(size_t)min(q, nc - 1) * o.n_seg_total + s];
+        for (int q = 0; q < NP; ++q) D[q] = dc[(size_t)cr[min(q, nc - 1)] * o.n_seg_total + s];
+      } else {
+#pragma unroll
+        for (int q = 0; q < NP; ++q) D[q] = dc[(size_t)min(q, nc - 1) * o.n_seg_total + s];
+      }
     }
     limb_load_coef<NG>(abs_c, emi_c, gstride, (size_t)seg_layer[min(s + 1, s1 - 1)] * n_pts + j, an, en);
     const Atten A = attenuation(tau);
@@ -253,7 +291,7 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int q = 16 * rt + kq + 4 * r;
-        const int p = slot_par[blockIdx.z * NP + min(q, NP - 1)];
+        const int p = slot_par[rb * NP + min(q, NP - 1)];
         orow[r] = q < NP ? (p >= 0 ? (long long)n_rays + (long long)ray * n_par + p : -1) : (q == NP && first ? (long long)ray : -1);
       }
       // INSTR: in block 0 the row tile that holds the radiance (value NP: row NP & 15 of row tile NP / 16, held by the lanes
@@ -286,7 +324,7 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     if (blockIdx.z == 0 && rad) rad[(size_t)ray * n_pts + j] = I;
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
-      const int p = slot_par[blockIdx.z * NP + q];
+      const int p = slot_par[rb * NP + q];
       if (p >= 0) jac[((size_t)ray * n_par + p) * n_pts + j] = J[q];
     }
   }

@@ -479,6 +479,11 @@ def _pointing_kw(pointing):
     return dict(pointing=True) if pointing else {}
 
 
+def _ray_blocks_kw(ray_blocks):
+    """ray_blocks= for the mixed-state calls, or nothing: left at None a call is made as it always was."""
+    return {} if ray_blocks is None else dict(ray_blocks=bool(ray_blocks))
+
+
 class LevelFactored(object):
     """The level-factored route as one object: the pair tables of a LineSet on a set of (P, T) rows (LineSet.glevel_pairs;
     with dT also at T + dT, region boundaries frozen at T) and the combine for any number of LOS steps on those rows
@@ -564,7 +569,7 @@ class LevelFactored(object):
                                         g_lo=int(self._shard[0]), want_rad=want_rad)
 
     def state_jacobian(self, coeffs, los, step_row, tvib, par_level, par_w_level, par_gas=None, par_w_col=None, gas=0,
-                       q_part=None, grid=None, want_rad=True, dcoeffs=None, par_w_temp=None, pointing=False):
+                       q_part=None, grid=None, want_rad=True, dcoeffs=None, par_w_temp=None, pointing=False, ray_blocks=None):
         """(rad | None, jac [n_rays, n_col + n_lev (+ n_row), n_pts]): d rad / d x for a mixed state vector in one pass
         (limb_rays_state_jacobian): first the VMR-profile parameters par_gas / par_w_col of limb_rays_jacobian (any gas
         of the batch, this one included; None: no such parameter), then the vibrational-temperature parameters
@@ -577,7 +582,8 @@ class LevelFactored(object):
         step_row, par_level, par_c = self._state_level_args(step_row, tvib, par_level, par_w_level, q_part)
         return limb_rays_state_jacobian(coeffs, los, par_gas=par_gas, par_w=par_w_col, tab=self.tab, coef_row=step_row,
                                         par_level=par_level, par_c=par_c, gas=gas, grid=grid, g_lo=int(self._shard[0]),
-                                        want_rad=want_rad, dcoeffs=dcoeffs, par_t=par_w_temp, **_pointing_kw(pointing))
+                                        want_rad=want_rad, dcoeffs=dcoeffs, par_t=par_w_temp, **_ray_blocks_kw(ray_blocks),
+                                        **_pointing_kw(pointing))
 
     def _state_level_args(self, step_row, tvib, par_level, par_w_level, q_part):
         """(step_row, par_level, par_c) of state_jacobian / state_bands: par_c = par_w_level * d pop / d Tvib, formed as in
@@ -598,7 +604,7 @@ class LevelFactored(object):
 
     def state_bands(self, coeffs, los, step_row, tvib, par_level, par_w_level, grid, centers_nm, widths_nm, par_gas=None,
                     par_w_col=None, gas=0, q_part=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None,
-                    instrument=False, pointing=False, ils=None):
+                    instrument=False, pointing=False, ils=None, ray_blocks=None):
         """state_jacobian on the instrument's bands in one library call (limb_rays_state_bands): numpy [n_rays | n_rays / 3,
         1 + n_par, n_bands], row 0 the radiance, row 1 + p the derivative to parameter p (VMR-profile, vibrational-
         temperature, kinetic-temperature parameters, as state_jacobian orders them); no hi-res spectrum is written.  The
@@ -610,7 +616,8 @@ class LevelFactored(object):
         return limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=par_gas, par_w=par_w_col, tab=self.tab,
                                      coef_row=step_row, par_level=par_level, par_c=par_c, gas=gas, dcoeffs=dcoeffs,
                                      par_t=par_w_temp, out_units=out_units, n_sigma=n_sigma, fov=fov,
-                                     g_lo=int(self._shard[0]), instrument=instrument, ils=ils, **_pointing_kw(pointing))
+                                     g_lo=int(self._shard[0]), instrument=instrument, ils=ils, **_ray_blocks_kw(ray_blocks),
+                                     **_pointing_kw(pointing))
 
     def level_radiances(self, coeffs, los, step_row, tvib, levels=None, weights=None, gas=0, q_part=None, grid=None,
                         gas_parts=True):
@@ -685,17 +692,18 @@ class LevelFactoredSet(object):
         return gases, par_lgas, par_level, par_c
 
     def state_jacobian(self, coeffs, los, par_lgas, par_level, par_w_level, par_gas=None, par_w_col=None, grid=None,
-                       want_rad=True, dcoeffs=None, par_w_temp=None, pointing=False):
+                       want_rad=True, dcoeffs=None, par_w_temp=None, pointing=False, ray_blocks=None):
         """LevelFactored.state_jacobian for the members' vibrational-temperature parameters together: (rad | None, jac
         [n_rays, n_col + n_lev (+ n_row), n_pts]), the rows in the caller's order; pointing=True: the pointing row behind."""
         gases, par_lgas, par_level, par_c = self._args(par_lgas, par_level, par_w_level)
         return limb_rays_state_jacobian(coeffs, los, par_gas=par_gas, par_w=par_w_col, par_level=par_level, par_c=par_c,
                                         grid=grid, g_lo=int(self.members[0][0]._shard[0]), want_rad=want_rad, dcoeffs=dcoeffs,
-                                        par_t=par_w_temp, level_gases=gases, par_lgas=par_lgas, **_pointing_kw(pointing))
+                                        par_t=par_w_temp, level_gases=gases, par_lgas=par_lgas, **_ray_blocks_kw(ray_blocks),
+                                        **_pointing_kw(pointing))
 
     def state_bands(self, coeffs, los, par_lgas, par_level, par_w_level, grid, centers_nm, widths_nm, par_gas=None,
                     par_w_col=None, dcoeffs=None, par_w_temp=None, out_units="Wm2", n_sigma=5.0, fov=None, instrument=False,
-                    pointing=False, ils=None):
+                    pointing=False, ils=None, ray_blocks=None):
         """LevelFactored.state_bands for the members' vibrational-temperature parameters together: numpy [n_rays | n_rays / 3,
         1 + n_par, n_bands]; instrument=True: [.., 1 + n_par + 2, n_bands], the two instrument rows last; pointing=True:
         the pointing row behind the parameters'; ils: an ILS, the bands' tabulated line shape."""
@@ -703,7 +711,8 @@ class LevelFactoredSet(object):
         return limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=par_gas, par_w=par_w_col,
                                      par_level=par_level, par_c=par_c, dcoeffs=dcoeffs, par_t=par_w_temp, out_units=out_units,
                                      n_sigma=n_sigma, fov=fov, g_lo=int(self.members[0][0]._shard[0]), level_gases=gases,
-                                     par_lgas=par_lgas, instrument=instrument, ils=ils, **_pointing_kw(pointing))
+                                     par_lgas=par_lgas, instrument=instrument, ils=ils, **_ray_blocks_kw(ray_blocks),
+                                     **_pointing_kw(pointing))
 
 
 def level_node_weights(nodes, alt):
@@ -1276,7 +1285,7 @@ def limb_rays_level_jacobian(coeffs, los, tab, coef_row, par_level, par_c, gas=0
 
 def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, coef_row=None, par_level=None, par_c=None,
                              gas=0, grid=None, g_lo=0, want_rad=True, dcoeffs=None, par_t=None, level_gases=None, par_lgas=None,
-                             pointing=False):
+                             pointing=False, ray_blocks=None):
     """(rad | None, jac [n_rays, n_col + n_lev (+ n_row), n_pts]): radiances and their derivatives with respect to a
     mixed state vector in ONE pass over each ray (sr_limb_rays_jac_state_dev): the column parameters par_gas / par_w of
     limb_rays_jacobian (VMR-profile parameters, par_w [n_col, n_pt] at the LOS sample points) first, then the level
@@ -1299,7 +1308,15 @@ def limb_rays_state_jacobian(coeffs, los, par_gas=None, par_w=None, tab=None, co
     state's, jac [n_rays, n_par + 1, n_pts] (a view), d rad / d z_t of every ray's own tangent altitude [per km] with the
     crossed shells held fixed; the other rows and rad are those of the call without, bit for bit, and there may be no
     other parameter.  Limb rays of geometry.limb_los only: 3-D paths, slant / nadir paths, adaptive stepping, observer
-    order, the resident-handle routes and refraction are not supported."""
+    order, the resident-handle routes and refraction are not supported.
+    ray_blocks (None: as set_state_ray_blocks left it): parameter blocks per ray, or the dense plan, for this call."""
+    with _RayBlocks(ray_blocks):
+        return _limb_rays_state_jacobian(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, want_rad,
+                                         dcoeffs, par_t, level_gases, par_lgas, pointing)
+
+
+def _limb_rays_state_jacobian(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, want_rad, dcoeffs,
+                              par_t, level_gases, par_lgas, pointing):
     if pointing:
         path = los.path_desc()
     A = _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, gas, grid, g_lo, dcoeffs, par_t, level_gases,
@@ -1448,7 +1465,7 @@ def _state_args(coeffs, los, par_gas, par_w, tab, coef_row, par_level, par_c, ga
 
 def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None, par_w=None, tab=None, coef_row=None,
                           par_level=None, par_c=None, gas=0, dcoeffs=None, par_t=None, out_units="Wm2", n_sigma=5.0, fov=None,
-                          g_lo=0, level_gases=None, par_lgas=None, instrument=False, pointing=False, ils=None):
+                          g_lo=0, level_gases=None, par_lgas=None, instrument=False, pointing=False, ils=None, ray_blocks=None):
     """limb_rays_state_jacobian on the instrument's bands in ONE library call (sr_limb_rays_state_bands_dev): the same
     mixed state vector (column, level, row parameters: the same arguments, the same errors), but no hi-res spectrum is
     written -- the recursion kernel integrates the bands in its epilogue.  Returns numpy [n_rays | n_rays / 3, 1 + n_par,
@@ -1465,7 +1482,15 @@ def limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas=None
     pointing=True (sr_limb_rays_state_bands_path_dev; the batch needs path=, else ValueError): the pointing row of
     limb_rays_state_jacobian behind the parameters' and in front of the instrument rows, [.., 1 + n_par + 1 (+ 2),
     n_bands]; the other rows are those of the call without, bit for bit.
-    ils: an ILS, the bands' tabulated line shape (as hires_to_lowres and, with instrument=True, hires_to_lowres_instrument)."""
+    ils: an ILS, the bands' tabulated line shape (as hires_to_lowres and, with instrument=True, hires_to_lowres_instrument).
+    ray_blocks (None: as set_state_ray_blocks left it): parameter blocks per ray, or the dense plan, for this call."""
+    with _RayBlocks(ray_blocks):
+        return _limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas, par_w, tab, coef_row, par_level, par_c, gas,
+                                      dcoeffs, par_t, out_units, n_sigma, fov, g_lo, level_gases, par_lgas, instrument, pointing, ils)
+
+
+def _limb_rays_state_bands(coeffs, los, grid, centers_nm, widths_nm, par_gas, par_w, tab, coef_row, par_level, par_c, gas, dcoeffs,
+                           par_t, out_units, n_sigma, fov, g_lo, level_gases, par_lgas, instrument, pointing, ils):
     instrument, pointing = bool(instrument), bool(pointing)
     if pointing:
         path = los.path_desc()
@@ -1752,6 +1777,86 @@ def set_band_fusion(on):
     """1 (default): a retrieval iteration's recursion kernel integrates the instrument bands itself; 0: spectra, then the
     instrument step's own kernels (sr_set_band_fusion; the check and the A/B partner)."""
     check(lib.sr_set_band_fusion(int(bool(on))), "sr_set_band_fusion")
+
+
+_state_ray_blocks = False  # what set_state_ray_blocks last set (the library's default: off)
+
+
+def set_state_ray_blocks(on):
+    """False (default): the mixed-state calls cut the parameter list of the batch into blocks and walk every ray once per
+    block; True: every ray has its own list -- the parameters that touch it -- and is walked once per block of that list
+    (sr_set_state_ray_blocks).  The rows of parameters that do not touch a ray are exact zeros either way.  For states
+    whose parameters each act on few rays: latitude boxes, many altitude nodes."""
+    global _state_ray_blocks
+    check(lib.sr_set_state_ray_blocks(int(bool(on))), "sr_set_state_ray_blocks")
+    _state_ray_blocks = bool(on)
+
+
+class _RayBlocks(object):
+    """The ray_blocks= keyword of the mixed-state calls: the switch for one call, then what it was (None: as it is)."""
+
+    def __init__(self, on):
+        self.on = on
+
+    def __enter__(self):
+        self.was = _state_ray_blocks
+        if self.on is not None:
+            set_state_ray_blocks(self.on)
+
+    def __exit__(self, *exc):
+        if self.on is not None:
+            set_state_ray_blocks(self.was)
+        return False
+
+
+def last_state_route():
+    """(route, walks) of this thread's last mixed-state call: route 1 the dense plan, 2 parameter blocks per ray, 0 none
+    yet; walks: its (ray, block) pairs, how often a ray was walked (sr_last_state_route, sr_last_state_walks)."""
+    return int(lib.sr_last_state_route()), int(lib.sr_last_state_walks())
+
+
+def state_ray_plan(los, n_layers, par_gas=None, par_w=None, par_level=None, par_c=None, par_t=None, par_lgas=None, n_hid=0):
+    """The per-ray plan of a mixed-state call on the host (sr_state_ray_plan; no GPU is touched): a dict with np, n_blocks
+    (the largest block count of a ray), ray_blk_off [n_rays + 1], blk [n_rb, 2], col_row [n_rb, np], ent_off [n_rb,
+    n_layers + 1], slot_par [n_rb, np] and the entries ent_slot, ent_level, ent_c.  los: a LimbLOS; the parameter arrays as
+    limb_rays_state_jacobian takes them."""
+    d = los.desc(rad0=True)
+    d.init_mode = 0   # (the plan does not depend on the initial intensity)
+    n_col = n_lev = n_row = 0
+    pg = pw = plg = pl = pc = pt = None
+    if par_gas is not None and np.asarray(par_gas).size:
+        par_gas, pg = _i(np.asarray(par_gas).reshape(-1))
+        par_w, pw = _d(par_w)
+        n_col = par_gas.size
+        if par_w.shape != (n_col, los.n_pt):
+            raise ValueError("par_w must be [n_col, n_pt]")
+    if par_level is not None and np.asarray(par_level).size:
+        par_level, pl = _i(np.asarray(par_level).reshape(-1))
+        par_c, pc = _d(par_c)
+        n_lev = par_level.size
+        if par_c.shape != (n_lev, n_layers):
+            raise ValueError("par_c must be [n_lev, n_layers]")
+        if par_lgas is not None:
+            par_lgas, plg = _i(np.asarray(par_lgas).reshape(-1))
+            if par_lgas.size != n_lev:
+                raise ValueError("par_lgas must be [n_lev]")
+    if par_t is not None:
+        par_t, pt = _d(par_t)
+        if par_t.ndim != 2 or par_t.shape[1] != n_layers:
+            raise ValueError("par_t must be [n_row, n_layers]")
+        n_row = par_t.shape[0]
+    sizes = np.zeros(4, dtype=np.int32)
+    head = (C.byref(d), int(n_layers), n_col, pg, pw, n_lev, plg, pl, pc, n_row, pt, int(n_hid), sizes.ctypes.data_as(ip))
+    check(lib.sr_state_ray_plan(*(head + (None,) * 8)), "sr_state_ray_plan")
+    n_p, n_blocks, n_rb, n_ent = (int(v) for v in sizes)
+    P = dict(np=n_p, n_blocks=n_blocks,
+             ray_blk_off=np.zeros(los.n_rays + 1, dtype=np.int32), blk=np.zeros((n_rb, 2), dtype=np.int32),
+             col_row=np.zeros((n_rb, n_p), dtype=np.int32), ent_off=np.zeros((n_rb, n_layers + 1), dtype=np.int32),
+             slot_par=np.zeros((n_rb, n_p), dtype=np.int32), ent_slot=np.zeros(n_ent, dtype=np.int32),
+             ent_level=np.zeros(n_ent, dtype=np.int32), ent_c=np.zeros(n_ent))
+    ints = tuple(P[k].ctypes.data_as(ip) for k in ("ray_blk_off", "blk", "col_row", "ent_off", "slot_par", "ent_slot", "ent_level"))
+    check(lib.sr_state_ray_plan(*(head + ints + (P["ent_c"].ctypes.data_as(dp),))), "sr_state_ray_plan")
+    return P
 
 
 def set_jac_layer_mode(forward):

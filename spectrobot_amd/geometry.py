@@ -236,6 +236,53 @@ def limb_los_3d(z, nd_levels, vmr_levels, z_tans, sza_tangent_deg, azimuth_deg, 
     return out
 
 
+def lat_box_of_segments(L3, lat_limits):
+    """The latitude box of every LOS step of a batch that knows its steps' latitudes (`seg_lat`: limb_los_3d, or limb_los
+    with path_state_3d's second result put in): 'box' interpolation on the limits of a retrieval set
+    (smm.LinearProfile_2D.lats, smm.lat_box): the boxes START at lat_limits, box j holds lat_limits[j] <= lat <
+    lat_limits[j + 1], the last one is open-ended; a step south of the first limit takes box 0.  It is lat_box_index on
+    the limits closed by +inf.  (smm.lat_box, as the reference, gives a latitude exactly ON the last limit to no box; here
+    it belongs to the last one.)  int32 [n_seg]."""
+    lim = np.asarray(lat_limits, float)
+    return lat_box_index(L3["seg_lat"], np.append(lim, np.inf)).astype(np.int32)
+
+
+def _alt_bracket(L3, z):
+    """Per sample point: the level below (k), and the weights of levels k and k + 1 -- linear in altitude between the
+    levels, constant above the last (k + 1 is then the last level again, with weight 0) and below the first."""
+    z = np.asarray(z, float)
+    alt = np.clip(np.asarray(L3["alt"], float), z[0], z[-1])
+    k = np.clip(np.searchsorted(z, alt, side="right") - 1, 0, len(z) - 1)
+    k1 = np.minimum(k + 1, len(z) - 1)
+    f = np.where(k1 > k, (alt - z[k]) / np.where(k1 > k, z[k1] - z[k], 1.0), 0.0)
+    return k, k1, 1.0 - f, f
+
+
+def _box_of_points(L3, seg_box):
+    return np.repeat(np.asarray(seg_box, int), np.diff(np.asarray(L3["pt_off"])))
+
+
+def box_vmr(L3, z, vmr_boxes, seg_box):
+    """VMR [n_pt] at every LOS sample point of a gas whose profile depends on the latitude box: vmr_boxes [n_box, n_lev]
+    on the levels z, seg_box [n_seg] the box of every step (lat_box_of_segments).  A sample point takes the profile of its
+    STEP's box, linear in altitude between the levels and constant above the last, as _profiles does: sample points are
+    listed per step, so a box boundary falls between two steps and the Curtis-Godson column of a step never mixes boxes."""
+    v = np.asarray(vmr_boxes, float)
+    k, k1, a0, a1 = _alt_bracket(L3, z)
+    b = _box_of_points(L3, seg_box)
+    return a0 * v[b, k] + a1 * v[b, k1]
+
+
+def box_profile_weights(L3, z, masks, seg_box):
+    """[n_par, n_pt]: the masks of the parameters of a latitude-box profile (masks [n_par, n_box, n_lev]: GridMask2D.mask
+    of smm.LinearProfile_2D's parameters) at the LOS sample points, by box_vmr's rule: d vmr(point) / d x_p.  The masks
+    times the parameters' values are box_vmr of the set's profile, to rounding."""
+    m = np.asarray(masks, float)
+    k, k1, a0, a1 = _alt_bracket(L3, z)
+    b = _box_of_points(L3, seg_box)
+    return a0[None, :] * m[:, b, k] + a1[None, :] * m[:, b, k1]
+
+
 def slant_los(z, nd_levels, vmr_levels, zenith_deg, R=TITAN_RADIUS_KM, n_sub=3):
     """Upward-looking-from-below / nadir-viewing paths: rays that leave the lowest level z[0] at the given zenith
     angles (0 = nadir view / vertical path) and cross every shell once, in photon order (bottom -> top, the observer

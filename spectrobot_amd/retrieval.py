@@ -1105,6 +1105,188 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     return chi, obs, finish(low, dlow), bayes_set
 
 
+class BoxPixel(LimbPixel):
+    """A limb pixel in a scene whose composition depends on latitude: LimbPixel plus the latitude of its tangent point
+    [deg] and the heading of its lines of sight there [deg east of north] (geometry.path_state_3d's frame).  The three
+    rays of a pixel share both."""
+
+    def __init__(self, limb_tg_alt, tangent_lat_deg, heading_deg=0.0, fov_half=0.0, pixel_rot=0.0, observation=None, noise=None,
+                 mask=None):
+        LimbPixel.__init__(self, limb_tg_alt, fov_half=fov_half, pixel_rot=pixel_rot, observation=observation, noise=noise, mask=mask)
+        self.tangent_lat_deg, self.heading_deg = float(tangent_lat_deg), float(heading_deg)
+
+
+class BoxBatch(object):
+    """The LOS batch of a latitude-box scene (box_batch): L3 -- geometry.limb_los's dict of all pixels' three rays (low,
+    centre, up; the coefficient rows are the altitude shells) with `seg_lat`, the latitude of every step --, par_gas
+    [n_tot] and par_w [n_tot, n_pt], the weights of every parameter of the BayesSet at the sample points in BayesSet order,
+    seg_box {set name: the box of every step} for the box sets, and touches [n_pix, n_tot]: parameter p has a non-zero
+    weight at a sample point of one of the pixel's three rays (the complement is the reference's not_involved)."""
+
+    def vmr(self, scene, bayes_set):
+        """[n_gas, n_pt]: the VMRs at the sample points for the BayesSet's current values (a box set: geometry.box_vmr of
+        its profile; a 1-D set: its profile, a gas without a set: its vmr, linear in altitude)."""
+        from . import geometry
+        zz, out = self.zz, []
+        for g in scene.gases:
+            st = bayes_set.sets.get(g.name)
+            if isinstance(st, smm.LinearProfile_2D):
+                out.append(geometry.box_vmr(self.L3, scene.z, st.profile(), self.seg_box[g.name]))
+            else:
+                v = np.asarray(g.vmr if st is None else st.profile(), float)
+                out.append(np.interp(self.L3["alt"], zz, np.append(v, v[-1])))
+        return np.array(out)
+
+
+def box_batch(scene, bayes_set, pixels):
+    """The BoxBatch of `pixels` (BoxPixel, taken in the order given) for the sets of bayes_set: smm.LinearProfile_2D sets
+    named after gases of the scene (altitude nodes x latitude boxes) and 1-D profile sets of other gases."""
+    from . import geometry
+    names = [g.name for g in scene.gases]
+    for name in bayes_set.order:
+        if name not in names or not isinstance(bayes_set.sets[name], (smm.LinearProfile_2D, smm.LinearProfile_1D_new)):
+            raise ValueError("retrieval set %r: inversion_boxes takes LinearProfile_2D and 1-D profile sets named after gases of "
+                             "the scene" % (name,))
+    alts = np.array([a for pix in pixels for a in pix.los_alts()])
+    lat_t = np.repeat([pix.tangent_lat_deg for pix in pixels], 3)
+    head = np.repeat([pix.heading_deg for pix in pixels], 3)
+    L3 = dict(geometry.limb_los(scene.z, scene.nd, [g.vmr for g in scene.gases], alts, R=scene.R, n_sub=scene.n_sub))
+    _, L3["seg_lat"] = geometry.path_state_3d(L3, alts, np.array([1.0, 0.0, 0.0]), head, lat_t, R=scene.R)
+    B = BoxBatch()
+    B.L3, B.alts, B.seg_box = L3, alts, {}
+    B.zz = np.append(scene.z, scene.z[-1] + (scene.z[-1] - scene.z[-2]))
+    par_gas, par_w = [], []
+    for name in bayes_set.order:
+        st = bayes_set.sets[name]
+        par_gas += [names.index(name)] * len(st.set)
+        if isinstance(st, smm.LinearProfile_2D):
+            B.seg_box[name] = geometry.lat_box_of_segments(L3, st.lats)
+            par_w.append(geometry.box_profile_weights(L3, scene.z, np.array([p.maskgrid.mask for p in st.set]), B.seg_box[name]))
+        else:
+            par_w.append(np.array([np.interp(L3["alt"], B.zz, np.append(p.maskgrid.mask, p.maskgrid.mask[-1])) for p in st.set]))
+    B.par_gas, B.par_w = np.array(par_gas, np.int32), np.concatenate(par_w, axis=0)
+    pt = np.asarray(L3["pt_off"])[np.asarray(L3["seg_off"])]            # first sample point of every ray
+    B.touches = np.array([(B.par_w[:, pt[3 * i]:pt[3 * i + 3]] != 0).any(axis=1) for i in range(len(pixels))])
+    return B
+
+
+def inversion_boxes(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM=0.1, L1_reg=False, fov_closed_form=True):
+    """The counterpart of the reference's inversion(..., g3D=True) (spect_main_module.py:2422-2595) for VMR sets of class
+    smm.LinearProfile_2D, named after gases of the scene: a gas profile on altitude nodes x latitude boxes, retrieved
+    from limb pixels (BoxPixel) whose lines of sight cross several boxes.  bayes_set may also hold 1-D profile sets of
+    other gases.  T, P and the coefficient tables are the scene's 1-D ones (the rows are the altitude shells); only the
+    composition varies with latitude.
+    Per iteration: the box VMRs into the LOS batch of all pixels' three rays (geometry.box_vmr), ONE
+    engine.limb_rays_state_bands call with the parameters' weights at the sample points (geometry.box_profile_weights),
+    the field of view and ray_blocks=True -- a ray crosses two or three boxes and sees the nodes above its tangent
+    altitude, so every ray is walked for its own parameters only --, chi square with n_tot parameters, the reference's
+    stopping rule (smm.retrieval_converged) and smm.inversion_algebra_arrays.  A parameter that touches no ray of a
+    pixel has exact-zero derivative rows there: the reference's not_involved (bayes_set.touches [n_pix, n_tot] says
+    which; RetParam.not_involved is set for a parameter that touches no pixel at all).
+    Returns (chi, obs, sims, bayes_set) with .history, .stop, .jacobian, .touches and the stored averaging kernel and
+    covariance, as inversion_state.  Every pixel has the closed-form field of view, or none has a field of view.  After
+    the loop a gas with a box set holds the final profiles in gas.vmr_boxes [n_box, n_lev]; its 1-D vmr is untouched."""
+    pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)
+    with_fov = sum(pix.fov_half > 0 for pix in pixels)
+    if not (with_fov == 0 or (with_fov == len(pixels) and fov_closed_form)):
+        raise ValueError("inversion_boxes needs the closed-form field of view for every pixel, or for none")
+    B = box_batch(scene, bayes_set, pixels)
+    L3 = B.L3
+    obs = [pix.observation for pix in pixels]
+    masks = None if all(pix.mask is None for pix in pixels) else [pix.mask for pix in pixels]
+    noise = [pix.noise for pix in pixels]
+    obs_vec, _, noi_vec = smm.genvec(obs, obs, noise, masks=masks)
+    masktot = None if masks is None else np.concatenate([np.asarray(m, dtype=bool) for m in masks])
+    Sa_inv = np.linalg.inv(np.asarray(bayes_set.VCM_apriori(), dtype=float))
+    grid_lo = _Grid(scene.bands_nm)
+    fov = engine.fov_factors([pix.pixel_rot for pix in pixels]) if with_fov else None
+    band_args = dict(out_units=scene.out_units, fov=fov)
+    if _ils(scene) is not None:
+        band_args["ils"] = scene.ils
+    bayes_set.history, bayes_set.stop, bayes_set.touches = [], 'max_it', B.touches
+    for ip, par in enumerate(bayes_set.params()):
+        if B.touches[:, ip].any():
+            par.set_involved()
+        else:
+            par.set_not_involved()
+    n_tot = len(B.par_gas)
+
+    def into_gases():
+        for name in bayes_set.order:
+            st = bayes_set.sets[name]
+            if isinstance(st, smm.LinearProfile_2D):
+                scene.gas(name).vmr_boxes = np.array(st.profile(), dtype=float)
+            else:
+                scene.gas(name).add_clim(st.profile())
+
+    def wrap(v):
+        sp = Spectrum.__new__(Spectrum)
+        sp.spectrum, sp.spectral_grid = np.array(v), grid_lo
+        return sp
+
+    def finish(low, dlow):
+        if low is None:
+            return []
+        jac = np.transpose(dlow, (1, 0, 2)).reshape(dlow.shape[1], -1)
+        bayes_set.jacobian = (jac if masktot is None else jac[:, masktot]).T
+        for num in range(len(pixels)):
+            for ip, par in enumerate(bayes_set.params()):
+                par.store_deriv(wrap(dlow[num, ip]), num=num)
+        return [wrap(v) for v in low]
+
+    into_gases()
+    los = engine.LimbLOS(L3["seg_off"], L3["seg_layer"], L3["pt_off"], L3["x"], L3["nd"], B.vmr(scene, bayes_set),
+                         col_scale=[g.iso_ratio for g in scene.gases])
+    chi_old, chi, low, dlow = None, None, None, None
+    try:
+        for num_it in range(max_it):
+            coeffs = scene.coefficient_stack()
+            if num_it:
+                los.set_vmr(B.vmr(scene, bayes_set))
+            both = engine.limb_rays_state_bands(coeffs, los, scene.grid, scene.bands_nm, scene.widths_nm, par_gas=B.par_gas,
+                                                par_w=B.par_w, ray_blocks=True, **band_args)
+            rows = both if with_fov else both[1::3]
+            low, dlow = rows[:, 0, :], rows[:, 1:, :]
+            for par in bayes_set.params():
+                par.set_used()
+            sim_vec = low.reshape(-1) if masktot is None else low.reshape(-1)[masktot]
+            chi = np.sum(((obs_vec - sim_vec) / noi_vec) ** 2) / (len(obs_vec) - bayes_set.n_used_par())   # chicalc
+            bayes_set.history.append(chi)
+            why = smm.retrieval_converged(chi, chi_old, chi_threshold)
+            if why:
+                bayes_set.stop = why
+                break
+            chi_old = chi
+            K = np.transpose(dlow, (1, 0, 2)).reshape(n_tot, -1)
+            K = (K if masktot is None else K[:, masktot]).T
+            bayes_set.jacobian = K
+            smm.inversion_algebra_arrays(K, obs_vec, sim_vec, noi_vec, bayes_set, lambda_LM=lambda_LM, L1_reg=L1_reg, Sa_inv=Sa_inv)
+            into_gases()
+    finally:
+        los.close()
+    return chi, obs, finish(low, dlow), bayes_set
+
+
+def simulate_boxes(scene, bayes_set, pixels, fov_closed_form=True):
+    """The band spectra [n_pix, n_bands] of `pixels` (BoxPixel, in the order given) for the BayesSet's current values: the
+    forward model of inversion_boxes alone -- twin observations, finite differences."""
+    with_fov = sum(pix.fov_half > 0 for pix in pixels)
+    if not (with_fov == 0 or (with_fov == len(pixels) and fov_closed_form)):
+        raise ValueError("simulate_boxes needs the closed-form field of view for every pixel, or for none")
+    B = box_batch(scene, bayes_set, pixels)
+    L3 = B.L3
+    los = engine.LimbLOS(L3["seg_off"], L3["seg_layer"], L3["pt_off"], L3["x"], L3["nd"], B.vmr(scene, bayes_set),
+                         col_scale=[g.iso_ratio for g in scene.gases])
+    try:
+        rad = engine.limb_rays(scene.coefficient_stack(), los, resident=False)
+        low = engine.hires_to_lowres(rad, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units, ils=_ils(scene))
+    finally:
+        los.close()
+    if not with_fov:
+        return low[1::3]
+    return smm.fov_closed_form(low[0::3, None, :], low[1::3, None, :], low[2::3, None, :], [pix.pixel_rot for pix in pixels])[:, 0, :]
+
+
 def lut_coefficients(scene, temp_step=5.0, pres_step_log=1.0, refresh=False, **_unused):
     """(abs, emi) of every gas at the scene's layer stack through look-up tables, the route of the reference's
     `inversion(..., useLUTs=True)` (spect_main_module.py:2447-2467 -> check_and_build_allluts; per LOS step

@@ -10,8 +10,9 @@ BOTH gases on the level-factored route (an HCN-like gas with 6 levels, CH4 with 
            one_call = LevelFactoredSet.state_bands (sr_limb_rays_state_bands_gases_dev).
 HIP events around blocks of calls (about half a second each), the two routes alternated A B A B ... in one process after a
 warm-up of every shape; per route the median over the blocks of the time per call and the run-to-run spread (largest -
-smallest block).  N=<points>, LAYERS=<layers>, BLOCKS=<blocks per route> (7) for other sizes.  Prints one JSON line per
-case and a last line with the medians."""
+smallest block).  N=<points>, LAYERS=<layers>, BLOCKS=<blocks per route> (7) for other sizes.  RAY_BLOCKS=1: every call
+with the parameter blocks per ray (engine.set_state_ray_blocks; the JSON lines say so and carry the walks of the last
+call).  Prints one JSON line per case and a last line with the medians."""
 import json
 import os
 import sys
@@ -24,6 +25,8 @@ import bench_configs as bc  # noqa: E402
 from spectrobot_amd import engine, synthetic as syn  # noqa: E402
 
 engine.set_device(0)
+ray_blocks = os.environ.get("RAY_BLOCKS", "0") not in ("", "0")
+engine.set_state_ray_blocks(ray_blocks)
 n = int(os.environ.get("N", "100000"))
 n_layers = int(os.environ.get("LAYERS", "55"))
 n_blocks = int(os.environ.get("BLOCKS", "7"))
@@ -128,5 +131,6 @@ for case, routes in (("spectra", (("per_gas", spectra_per_gas), ("one_call", spe
                           per_gas_over_one_call=round(med["per_gas"] / med["one_call"], 3),
                           margin_in_spreads=round((med["per_gas"] - med["one_call"]) / max(spread["per_gas"], spread["one_call"], 1e-9), 1),
                           one_call_vs_per_gas_row_err=agree["spectra" if case == "spectra" else "bands"],
+                          ray_blocks=ray_blocks, last_state_route=engine.last_state_route(),
                           device=engine.device_info()["name"])), flush=True)
 print(json.dumps(dict(summary=summary)))
