@@ -1784,9 +1784,21 @@ __global__ __launch_bounds__(64) void sr_abscoeff_near_wings_kernel(
   }
 }
 
-// One region-3/4 point of a line: the point's window index and the line's data, per lane.  Several lines can
-// hit the same grid point in one step, hence LDS atomics (one wave per image, program order: the sums stay
-// deterministic).
+// ------------------------------------------------------------------------
+// The zones walk: regions 2, 3 and 4 of the lines whose zone meets a group of grid points, summed into an LDS image
+// of the group.  sr_abscoeff_near_zones_kernel and sr_zones_mc_kernel run the SAME walk, one 64-line chunk at a time
+// (zones_chunk); they differ in the SINK, which says where a line's value goes:
+//   kWords            words per entry of the item lists: lane, two run words and, if 4, the sink's own word
+//   Chans             the planes of a line; channels(lv) reads them, pack() / unpack() are the item's fourth word
+//   Line              line(r, ch, ibase): the line's weights and planes; add(k, y) adds weight * y at element
+//                     k + ibase of each plane, add_at_byte(ab, y) at byte ab (ibase = 0).  Several lines can hit the
+//                     same grid point in one step, hence LDS atomics
+//   count(region, on) the executed-work counters
+// Everything is inlined into the two kernels: nothing of it lives in memory that a kernel would hold in registers.
+// ------------------------------------------------------------------------
+#ifndef SR_ZONES_ROW
+#define SR_ZONES_ROW 8 // lanes per row of the region-2 / region-4 walk: eight lines at a time (16: 4.35, 8: 4.1, 4: 4.87, 32: 5.09 ms)
+#endif
 // Largest of a value that is uniform within each row of 8 lanes, as a scalar: eight v_readlane + scalar max.  The
 // row loops then run on a scalar step counter; "while any lane has a step left" costs three VALU instructions per
 // step however it is written (the ballot's mask goes through v_cndmask + v_cmp_ne).
@@ -1796,29 +1808,256 @@ __device__ inline int rows_max(int v) {
   for (int r = 8; r < 64; r += 8) m = max(m, __builtin_amdgcn_readlane(v, r));
   return m;
 }
-struct CorePend {
-  int k, base; // window index; element of the image = k + base
-  double gc, x0, dwp, inv_dwp, ryf, ryf2, two_ryf, wa, we;
+// What a wave's walk needs of its group: the layer's records, the group's first and last grid point, and the wave's
+// item lists [2 regions][kWords][64]: per region (2, 4) the chunk's lines with work there, compacted in lane order --
+// lane id, the two run words, the sink's word -- written by the lanes = lines phase, read by the rows (dealing the
+// lines to the rows with ballots and selects cost 27 VALU instructions per round of eight lines, two bpermutes
+// fetched the run words)
+struct ZoneWalk {
+  const FastRec *frow;
+  const ColdRec *crow;
+  const GridParams &gp;
+  int *items;
+  int wlo, whi, lane;
+  double p6_vgpr; // see core_region4_m
 };
-// cos_tier: see cos_tiered (wave-uniform, from the largest 2 ry rx of the rows' runs)
-__device__ inline void core_eval4(const CorePend &P, bool on, const GridParams &gp, int cos_tier, double p6_vgpr, double *s_a,
-                                  double *s_e) {
-  if (on) {
-    const WinX xf{gp.lin_start, gp.lin_delta, P.gc};
-    const double d = fabs(xf(P.k) - P.x0);
-    double rx = d * P.inv_dwp; // |x(k)-x0|/dw correctly rounded: one residual correction
-    rx = fma(fma(-P.dwp, rx, d), P.inv_dwp, rx);
-    const double y = core_region4_m(P.ryf, P.ryf2, P.two_ryf, (double)(float)rx, cos_tier, p6_vgpr);
-    const int idx = P.k + P.base;
-    atomicAdd(&s_a[idx], P.wa * y);
-    atomicAdd(&s_e[idx], P.we * y);
+// does the zone (inside the window) of the lane's line meet the group: from the FastRec alone
+__device__ __forceinline__ bool zone_meets_group(const FastRec &r, bool in_list, int wlo, int whi) {
+  const int j1 = r.j1, il = r.il(), ir = r.ir();
+  const int zl = max(j1 + il - 1, j1), zh = min(j1 + ir - 1, j1 + (kImxsig - 1));
+  return in_list && zl <= whi && zh >= wlo;
+}
+// runs of the lane's line inside this group, start | count << 16 (window indices <= 13010): region 2 left / right
+// (lineshape.f:503-522), region 4 left / right of the region-3 interval; region 3 = n3 points from e0
+struct ZoneRuns {
+  unsigned run2l, run2r, run4l, run4r;
+  int e0, n3;
+  bool w2, w4; // the line has region-2 / region-4 work here
+};
+__device__ __forceinline__ ZoneRuns zone_runs(const FastRec &r, const ColdRec &z, bool act, int wlo, int whi) {
+  ZoneRuns o;
+  const int j1 = r.j1, il = r.il(), ir = r.ir();
+  const int k3lo = z.k3lo(), k3hi = z.k3hi();
+  const int il2 = z.il2(), ir2 = z.ir2();
+  const int k_lo = max(wlo - j1 + 1, 1), k_hi = min(whi - j1 + 1, kImxsig); // group & window, as k
+  {
+    const int a0 = max(il, k_lo), a1 = il < il2 ? min(il2, k_hi) : a0 - 1;
+    const int b0 = max(ir2, k_lo), b1 = ir2 < ir ? min(ir, k_hi) : b0 - 1;
+    o.run2l = (unsigned)a0 | ((unsigned)max(a1 - a0 + 1, 0) << 16);
+    o.run2r = (unsigned)b0 | ((unsigned)max(b1 - b0 + 1, 0) << 16);
+  }
+  // the core (il2a, ir2a), lineshape.f:524-562: region 3 = [k3lo, k3hi], region 4 on both sides
+  const int c_lo = max(((il2 == il) ? il - 1 : il2) + 1, k_lo), c_hi = min(((ir2 == ir) ? ir + 1 : ir2) - 1, k_hi);
+  const bool has3 = k3lo <= k3hi;
+  {
+    const int a0 = c_lo, a1 = has3 ? min(k3lo - 1, c_hi) : c_hi;
+    const int b0 = has3 ? max(k3hi + 1, c_lo) : c_hi + 1, b1 = c_hi;
+    o.run4l = (unsigned)a0 | ((unsigned)max(a1 - a0 + 1, 0) << 16);
+    o.run4r = (unsigned)b0 | ((unsigned)max(b1 - b0 + 1, 0) << 16);
+  }
+  o.e0 = max(k3lo, c_lo);
+  const int e1 = min(k3hi, c_hi);
+  o.n3 = (act && has3) ? max(e1 - o.e0 + 1, 0) : 0;
+  o.w2 = act && ((o.run2l >> 16) + (o.run2r >> 16)) > 0;
+  o.w4 = act && ((o.run4l >> 16) + (o.run4r >> 16)) > 0;
+  return o;
+}
+// the cosine's argument range over the line's region-4 runs (cos_tiered), for bits 30-31 of run4l (a count is
+// < 2^14): |Im c1| = 2 ry rx is largest at the outer ends of the two runs
+__device__ __forceinline__ unsigned zone_cos_tier(const WinX &xf, unsigned run4l, unsigned run4r, double x0, double inv_dwp,
+                                                  double ryf) {
+  const double rx_max = fmax(fabs(xf((int)(run4l & 0xffffu)) - x0),
+                             fabs(xf((int)(run4r & 0xffffu) + (int)(run4r >> 16) - 1) - x0)) * inv_dwp * 1.001;
+  const double ui_max = (ryf + ryf) * rx_max;
+  return ui_max < 6.5e-3 ? 2u : (ui_max < 0.78 ? 1u : 0u);
+}
+// REGION 3 (lineshape.f:554-560), the ~15 points around the centre, lane = line: all lanes step through their own
+// interval together (the intervals of neighbouring lines are equally long), the line's data sit in the lane's
+// registers and die before the rows; sums by ds_add_f64.  Walked line by line with lanes = points these few points
+// cost a whole 64-lane chunk per line (1.1 of 6.6 ms).  Leaves the cosine's tier in run4l.
+template <class Sink>
+__device__ __forceinline__ void zone_region3(const ZoneWalk &W, Sink &sink, const FastRec &r, const ColdRec &z, ZoneRuns &zr,
+                                             const typename Sink::Chans &ch) {
+  const int j1 = r.j1;
+  const WinX xf{W.gp.lin_start, W.gp.lin_delta, grid_at(W.gp, j1 + kHalf)};
+  const double x0 = z.x0, dwp = z.dwp, inv_dwp = cold_inv_dwp(z.dwp), ryf = cold_ryf(z.ry);
+  const typename Sink::Line to = sink.line(r, ch, j1 - W.wlo); // element = point + 1
+  zr.run4l |= zone_cos_tier(xf, zr.run4l, zr.run4r, x0, inv_dwp, ryf) << 30;
+  const int e0 = zr.e0, n3 = zr.n3;
+  for (int t = 0; __any(t < n3); ++t) {
+    if (t < n3) {
+      const int k = e0 + t;
+      const double d = fabs(xf(k) - x0);
+      double rx = d * inv_dwp; // |x(k)-x0|/dw correctly rounded: one residual correction
+      rx = fma(fma(-dwp, rx, d), inv_dwp, rx);
+      const double y = core_region3(ryf, (double)(float)(-rx));
+      sink.count(3, true);
+      to.add(k, y);
+    }
   }
 }
+// the lines with work in a region (0: region 2, 1: region 4), compacted in lane order; returns their number
+template <class Sink>
+__device__ __forceinline__ int zone_compact(const ZoneWalk &W, int region, bool w, unsigned run_l, unsigned run_r, int word) {
+  const unsigned long long m = __ballot(w);
+  if (w) {
+    const int at = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    int *const it = W.items + region * Sink::kWords * 64 + at;
+    it[0] = W.lane;
+    it[64] = (int)run_l;
+    it[128] = (int)run_r;
+    if (Sink::kWords > 3) it[192] = word;
+  }
+  return __builtin_popcountll(m);
+}
+// ---- regions 2 and 4, kZoneRows lines at a time: each row of kZoneRowLanes lanes walks the points of ONE line,
+// kZoneRowLanes per step, with the line's data in its own registers (per-lane loads of the record fields: the four
+// rows read four records).  History: one line at a time with 64 points per step left the last chunk of each
+// run mostly empty (a line has ~150 region-2 and ~72 region-4 points: 64 + 64 + 22 lanes, 71-78 % lane use)
+// and cost a scalar record fetch + ~40 scalar / vector instructions per line; packing region-4 points of
+// consecutive lines into full chunks fixed its lane use but not the per-line walk.  Rows: lane use 90-94 %, no
+// scalar walk, no pending state: sr_abscoeff_near_zones_kernel 4.9 -> 4.2 ms on config 2.
+constexpr int kZoneRowLanes = SR_ZONES_ROW, kZoneRows = 64 / kZoneRowLanes;
+// the item of this lane's row in round g of a region's list (the last item again, not live, where the list ends)
+struct ZoneItem {
+  bool live;
+  int line; // lane of the line in the chunk
+  unsigned ul, ur;
+  int word;
+};
+template <class Sink>
+__device__ __forceinline__ ZoneItem zone_item(const ZoneWalk &W, int region, int g, int n_items) {
+  const int row = W.lane / kZoneRowLanes;
+  const int *const it = W.items + region * Sink::kWords * 64 + min(g + row, n_items - 1);
+  return {g + row < n_items, it[0], (unsigned)it[64], (unsigned)it[128], Sink::kWords > 3 ? it[192] : 0};
+}
+// region 2 (lineshape.f:503-522): item t of a line: left k = a0 + t, x = xs2l - (k - il) xstep; right
+// k = b0 + (t - na), x = xs2r + (k - ir2) xstep.  Only x^2 enters, so both are t xstep + c with a per-line c.
+template <class Sink>
+__device__ __forceinline__ void zone_rows2(const ZoneWalk &W, Sink &sink, int base, int n_items) {
+  const int col = W.lane % kZoneRowLanes;
+  for (int g = 0; g < n_items; g += kZoneRows) {
+    const ZoneItem I = zone_item<Sink>(W, 0, g, n_items);
+    const FastRec &r = W.frow[base + I.line];
+    const ColdRec &z = W.crow[base + I.line];
+    const int a0 = (int)(I.ul & 0xffffu), na = (int)(I.ul >> 16), b0 = (int)(I.ur & 0xffffu), nb = (int)(I.ur >> 16);
+    const double xstep = r.xstep;
+    const typename Sink::Line to = sink.line(r, Sink::Chans::unpack(I.word), 0);
+    double q2[8];
+    region2_coef_fma(z.ry, q2); // rebuilt per line (ColdRec): 25 flops against ~20 steps of 21 instructions
+    const int base_idx = r.j1 - W.wlo; // element = point + 1
+    // the two runs one after the other, t counted from each run's first point (one loop over both with the
+    // side chosen per point cost a compare and three selects per point: 25 -> 21 VALU instructions per point
+    // for ~5 % more steps)
+    auto run = [&](const int n, const int n_max, const double c, const int i0) {
+      const int n_steps = (n_max + kZoneRowLanes - 1) / kZoneRowLanes; // wave-uniform: a scalar loop counter
+      // x of the lane's point by a running sum, eight steps of xstep at a time (one add instead of a conversion
+      // and an fma per point; <= 20 steps of a run: <= 20 ulp of x, 1e-14 of the value at most): 5.38 vs 5.42 ms
+      // per headline step
+      double xt = fma((double)col, xstep, c);
+      const double xs8 = (double)kZoneRowLanes * xstep;
+      // ... and ONE counter per lane: the byte offset of its point in the image, which is the loop's predicate too
+      int ab = (col + i0) * 8;
+      const int ab_end = (n + i0) * 8;
+      for (int st = 0; st < n_steps; ++st, ab += 8 * kZoneRowLanes) {
+        if (ab < ab_end) {
+          const double y = region2_val(q2, xt);
+          xt += xs8;
+          sink.count(2, true);
+          to.add_at_byte(ab, y); // return-less LDS adds: no wait for a read, runs of different lines overlap
+        }
+      }
+    };
+    // (step counts by rows_max() per round; from per-round maxima that the lanes = lines phase wrote to LDS: 3.51 vs 3.50 ms, 128-129 VGPRs)
+    run(I.live ? na : 0, rows_max(I.live ? na : 0), fma((double)(a0 - r.il()), xstep, -z.xs2l), a0 + base_idx);
+    run(I.live ? nb : 0, rows_max(I.live ? nb : 0), fma((double)(b0 - z.ir2()), xstep, z.xs2r), b0 + base_idx);
+  }
+}
+// region 4 (lineshape.f:530-546), on both sides of the region-3 interval
+template <class Sink>
+__device__ __forceinline__ void zone_rows4(const ZoneWalk &W, Sink &sink, int base, int n_items) {
+  const int col = W.lane % kZoneRowLanes;
+  for (int g = 0; g < n_items; g += kZoneRows) {
+    const ZoneItem I = zone_item<Sink>(W, 1, g, n_items);
+    const FastRec &r = W.frow[base + I.line];
+    const ColdRec &z = W.crow[base + I.line];
+    const unsigned ul = I.ul, ur = I.ur;
+    const int a0 = (int)(ul & 0xffffu), na = (int)((ul >> 16) & 0x3fffu), b0 = (int)(ur & 0xffffu), nb = (int)(ur >> 16);
+    const int n = I.live ? na + nb : 0;
+    const int j1 = r.j1;
+    const double gc = grid_at(W.gp, j1 + kHalf), x0 = z.x0, dwp = z.dwp, inv_dwp = cold_inv_dwp(z.dwp);
+    const double ryf = cold_ryf(z.ry), ryf2 = ryf * ryf, two_ryf = ryf + ryf;
+    const typename Sink::Line to = sink.line(r, Sink::Chans::unpack(I.word), j1 - W.wlo); // element = point + 1
+    // the cosine's tier of this round: the smallest of its lines' (from the lanes = lines phase; cos_tiered)
+    const int tier_ = I.live ? (int)(ul >> 30) : 2;
+    const int cos_tier = __all(tier_ == 2) ? 2 : (__all(tier_ >= 1) ? 1 : 0);
+    const int n_steps = (rows_max(n) + kZoneRowLanes - 1) / kZoneRowLanes;
+    const WinX xf{W.gp.lin_start, W.gp.lin_delta, gc};
+    for (int st = 0; st < n_steps; ++st) {
+      const int t = col + kZoneRowLanes * st;
+      const int k = t < na ? a0 + t : b0 + (t - na);
+      sink.count(4, t < n);
+      if (t < n) {
+        const double d = fabs(xf(k) - x0);
+        double rx = d * inv_dwp; // |x(k)-x0|/dw correctly rounded: one residual correction
+        rx = fma(fma(-dwp, rx, d), inv_dwp, rx);
+        const double y = core_region4_m(ryf, ryf2, two_ryf, (double)(float)rx, cos_tier, W.p6_vgpr);
+        to.add(k, y);
+      }
+    }
+  }
+}
+// One 64-line chunk from record `base` of a list that ends before l1: lane = line for the interval arithmetic of
+// every line (the rows read it back from the item lists: done there it was ~70 scalar instructions per line) and
+// region 3, then the rows.
+template <class Sink>
+__device__ __forceinline__ void zones_chunk(const ZoneWalk &W, Sink &sink, int base, int l1) {
+  const int lv = min(base + W.lane, l1 - 1);
+  const FastRec &r = W.frow[lv];
+  const bool act = zone_meets_group(r, base + W.lane < l1, W.wlo, W.whi);
+  if (__ballot(act) == 0) return; // before the first ColdRec load
+  const ColdRec &z = W.crow[lv];
+  ZoneRuns zr = zone_runs(r, z, act, W.wlo, W.whi);
+  const typename Sink::Chans ch = sink.channels(lv);
+  if (__any(zr.n3 > 0 || zr.w4)) zone_region3(W, sink, r, z, zr, ch);
+  const int n_items2 = zone_compact<Sink>(W, 0, zr.w2, zr.run2l, zr.run2r, ch.pack());
+  const int n_items4 = zone_compact<Sink>(W, 1, zr.w4, zr.run4l, zr.run4r, ch.pack());
+  zone_rows2(W, sink, base, n_items2);
+  zone_rows4(W, sink, base, n_items4);
+}
+
+// The folded op's sink: two sums, wabs and wemi, into the wave's private image (one wave per image, program order:
+// the sums stay deterministic), and the COUNT counters.
+template <bool COUNT>
+struct FoldedSink {
+  static constexpr int kWords = 3;
+  double *s_a, *s_e;
+  unsigned n_r[3]; // COUNT: evaluations of this lane in regions 2, 3, 4
+  struct Chans {
+    __device__ __forceinline__ int pack() const { return 0; }
+    static __device__ __forceinline__ Chans unpack(int) { return {}; }
+  };
+  struct Line {
+    double *s_a, *s_e;
+    double wa, we;
+    int ibase;
+    __device__ __forceinline__ void add(int k, double y) const {
+      atomicAdd(&s_a[k + ibase], wa * y);
+      atomicAdd(&s_e[k + ibase], we * y);
+    }
+    __device__ __forceinline__ void add_at_byte(int ab, double y) const {
+      atomicAdd(reinterpret_cast<double *>(reinterpret_cast<char *>(s_a) + ab), wa * y);
+      atomicAdd(reinterpret_cast<double *>(reinterpret_cast<char *>(s_e) + ab), we * y);
+    }
+  };
+  __device__ __forceinline__ Chans channels(int) const { return {}; }
+  __device__ __forceinline__ Line line(const FastRec &r, Chans, int ibase) const { return {s_a, s_e, r.wabs, r.wemi, ibase}; }
+  __device__ __forceinline__ void count(int region, bool on) {
+    if (COUNT) n_r[region - 2] += on;
+  }
+};
 // WT points per wave (a multiple of 64): the wider the image, the fewer zones are cut in two by
 // its ends (a zone is ~280 points), i.e. the fewer partially filled lane runs.
-#ifndef SR_ZONES_ROW
-#define SR_ZONES_ROW 8 // lanes per row of the region-2 / region-4 walk: eight lines at a time (16: 4.35, 8: 4.1, 4: 4.87, 32: 5.09 ms)
-#endif
 // At least four waves per SIMD (<= 128 VGPRs): the kernel sits at 118-127; with 129 (one more feature in the rows)
 // the 8-wave blocks of a small shard went from two per CU to one and the shard's kernel from 0.50 to 0.63 ms.
 template <int WT, int NW, bool COUNT>
@@ -1830,10 +2069,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
   // element p + 1, i.e. element k + (j1 - wlo): the hot loops' address arithmetic carries no "- 1" (it cost a v_add per
   // region-2 point: the offset field of ds_add cannot be negative)
   __shared__ double s_img[NW][2][WT + 2];
-  // per wave and region (2, 4): the chunk's lines with work there, compacted in lane order -- lane id and the two run
-  // words -- written by the lanes = lines phase, read by the rows (dealing the lines to the rows with ballots and
-  // selects cost 27 VALU instructions per round of eight lines, two bpermutes fetched the run words)
-  __shared__ int s_item[NW][2][3][64];
+  __shared__ int s_item[NW][2][3][64]; // the waves' item lists (ZoneWalk)
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int layer = layer0 + wg / n_groups, grp = wg - (layer - layer0) * n_groups; // layer0: the launch's first layer (layer chunks)
   const int wlo = g_lo + grp * WT;
@@ -1846,7 +2082,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
   const int zm = min(zmax[layer], kHalf - 1);
 #pragma unroll
   for (int p = 0; p < WT / 64; ++p) s_a[1 + lane + 64 * p] = s_e[1 + lane + 64 * p] = 0.;
-  unsigned n_r2 = 0, n_r3 = 0, n_r4 = 0; // COUNT: evaluations of this lane per region
+  FoldedSink<COUNT> sink{s_a, s_e, {0, 0, 0}};
   const double p6_vgpr = vgpr_constant(SR_F32(.56419)); // see core_region4_m
   // lines whose zone [ic - zm, ic + zm] can meet the group
   const int l0 = lower_bound_ic(ix, wlo - zm), l1 = lower_bound_ic(ix, whi + zm + 1);
@@ -1857,181 +2093,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
   // edge -- 45 % more record bytes than the tables hold; swept in opposite directions both reach the shared lines at
   // the same time (start or end of their sweep) and the second one finds them in L2 instead of HBM.
   const int n_chunks = (l1 - l0 + 63) >> 6;
-  for (int ci = wave; ci < n_chunks; ci += NW) {
-    const int base = l0 + 64 * ((grp & 1) ? n_chunks - 1 - ci : ci);
-    const int lv = min(base + lane, l1 - 1);
-    bool act;
-    // runs of the lane's line inside this group, start | count << 16 (window indices <= 13010):
-    // region 2 left / right (lineshape.f:503-522), region 4 left / right of the region-3 interval
-    unsigned run2l, run2r, run4l, run4r;
-    int n_items2, n_items4; // lines of this chunk with region-2 / region-4 work (wave-uniform)
-    {
-      // ---- lane = line: which lines have work here, the interval arithmetic of every line (the walk
-      // below reads it back with v_readlane: done there it was ~70 scalar instructions per line), and
-      // REGION 3 (lineshape.f:554-560), the ~15 points around the centre: all lanes step through
-      // their own interval together (the intervals of neighbouring lines are equally long), the
-      // line's data sit in the lane's registers and die before the walk; sums by ds_add_f64.  Walked
-      // line by line with lanes = points these few points cost a whole 64-lane chunk per line (1.1
-      // of 6.6 ms).
-      const FastRec &r = frow[lv];
-      const int j1 = r.j1, il = r.il(), ir = r.ir();
-      const int zl = max(j1 + il - 1, j1), zh = min(j1 + ir - 1, j1 + (kImxsig - 1));
-      act = base + lane < l1 && zl <= whi && zh >= wlo; // zone (inside the window) meets the group
-      if (__ballot(act) == 0) continue;
-      const ColdRec &z = crow[lv];
-      const int k3lo = z.k3lo(), k3hi = z.k3hi();
-      const int il2 = z.il2(), ir2 = z.ir2();
-      const int k_lo = max(wlo - j1 + 1, 1), k_hi = min(whi - j1 + 1, kImxsig); // group & window, as k
-      {
-        const int a0 = max(il, k_lo), a1 = il < il2 ? min(il2, k_hi) : a0 - 1;
-        const int b0 = max(ir2, k_lo), b1 = ir2 < ir ? min(ir, k_hi) : b0 - 1;
-        run2l = (unsigned)a0 | ((unsigned)max(a1 - a0 + 1, 0) << 16);
-        run2r = (unsigned)b0 | ((unsigned)max(b1 - b0 + 1, 0) << 16);
-      }
-      // the core (il2a, ir2a), lineshape.f:524-562: region 3 = [k3lo, k3hi], region 4 on both sides
-      const int c_lo = max(((il2 == il) ? il - 1 : il2) + 1, k_lo), c_hi = min(((ir2 == ir) ? ir + 1 : ir2) - 1, k_hi);
-      const bool has3 = k3lo <= k3hi;
-      {
-        const int a0 = c_lo, a1 = has3 ? min(k3lo - 1, c_hi) : c_hi;
-        const int b0 = has3 ? max(k3hi + 1, c_lo) : c_hi + 1, b1 = c_hi;
-        run4l = (unsigned)a0 | ((unsigned)max(a1 - a0 + 1, 0) << 16);
-        run4r = (unsigned)b0 | ((unsigned)max(b1 - b0 + 1, 0) << 16);
-      }
-      const int e0 = max(k3lo, c_lo), e1 = min(k3hi, c_hi);
-      const int n3 = (act && has3) ? max(e1 - e0 + 1, 0) : 0;
-      const bool w2 = act && ((run2l >> 16) + (run2r >> 16)) > 0, w4 = act && ((run4l >> 16) + (run4r >> 16)) > 0;
-      if (__any(n3 > 0 || w4)) {
-        const WinX xf{gp.lin_start, gp.lin_delta, grid_at(gp, j1 + kHalf)};
-        const double x0 = z.x0, dwp = z.dwp, inv_dwp = cold_inv_dwp(z.dwp), ryf = cold_ryf(z.ry), wa = r.wabs, we = r.wemi;
-        const int ibase = j1 - wlo; // element = point + 1
-        {
-          // the cosine's argument range over the line's region-4 runs (cos_tiered), bits 30-31 of run4l (a count is
-          // < 2^14): |Im c1| = 2 ry rx is largest at the outer ends of the two runs
-          const double rx_max = fmax(fabs(xf((int)(run4l & 0xffffu)) - x0),
-                                     fabs(xf((int)(run4r & 0xffffu) + (int)(run4r >> 16) - 1) - x0)) * inv_dwp * 1.001;
-          const double ui_max = (ryf + ryf) * rx_max;
-          run4l |= (ui_max < 6.5e-3 ? 2u : (ui_max < 0.78 ? 1u : 0u)) << 30;
-        }
-        for (int t = 0; __any(t < n3); ++t) {
-          if (t < n3) {
-            const int k = e0 + t;
-            const double d = fabs(xf(k) - x0);
-            double rx = d * inv_dwp; // |x(k)-x0|/dw correctly rounded: one residual correction
-            rx = fma(fma(-dwp, rx, d), inv_dwp, rx);
-            const double y = core_region3(ryf, (double)(float)(-rx));
-            if (COUNT) ++n_r3;
-            atomicAdd(&s_a[k + ibase], wa * y);
-            atomicAdd(&s_e[k + ibase], we * y);
-          }
-        }
-      }
-      // the lines with region-2 / region-4 work, compacted in lane order
-      const unsigned long long m2 = __ballot(w2), m4 = __ballot(w4);
-      n_items2 = __builtin_popcountll(m2);
-      n_items4 = __builtin_popcountll(m4);
-      if (w2) {
-        const int at = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m2 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m2, 0u));
-        s_item[wave][0][0][at] = lane;
-        s_item[wave][0][1][at] = (int)run2l;
-        s_item[wave][0][2][at] = (int)run2r;
-      }
-      if (w4) {
-        const int at = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m4 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m4, 0u));
-        s_item[wave][1][0][at] = lane;
-        s_item[wave][1][1][at] = (int)run4l;
-        s_item[wave][1][2][at] = (int)run4r;
-      }
-    }
-    // ---- regions 2 and 4, kRows lines at a time: each row of kRowLanes lanes walks the points of ONE line,
-    // kRowLanes per step, with the line's data in its own registers (per-lane loads of the record fields: the four
-    // rows read four records).  History: one line at a time with 64 points per step left the last chunk of each
-    // run mostly empty (a line has ~150 region-2 and ~72 region-4 points: 64 + 64 + 22 lanes, 71-78 % lane use)
-    // and cost a scalar record fetch + ~40 scalar / vector instructions per line; packing region-4 points of
-    // consecutive lines into full chunks fixed its lane use but not the per-line walk.  Rows: lane use 90-94 %, no
-    // scalar walk, no pending state: sr_abscoeff_near_zones_kernel 4.9 -> 4.2 ms on config 2.
-    {
-      constexpr int kRowLanes = SR_ZONES_ROW, kRows = 64 / kRowLanes;
-      const int row = lane / kRowLanes, col = lane % kRowLanes;
-      // region 2 (lineshape.f:503-522): item t of a line: left k = a0 + t, x = xs2l - (k - il) xstep; right
-      // k = b0 + (t - na), x = xs2r + (k - ir2) xstep.  Only x^2 enters, so both are t xstep + c with a per-line c.
-      for (int g = 0; g < n_items2; g += kRows) {
-        const int it = min(g + row, n_items2 - 1);
-        const bool live = g + row < n_items2;
-        const int ls_ = s_item[wave][0][0][it];
-        const FastRec &r = frow[base + ls_];
-        const ColdRec &z = crow[base + ls_];
-        const unsigned ul = (unsigned)s_item[wave][0][1][it], ur = (unsigned)s_item[wave][0][2][it];
-        const int a0 = (int)(ul & 0xffffu), na = (int)(ul >> 16), b0 = (int)(ur & 0xffffu), nb = (int)(ur >> 16);
-        const double xstep = r.xstep, wa = r.wabs, we = r.wemi;
-        double q2[8];
-        region2_coef_fma(z.ry, q2); // rebuilt per line (ColdRec): 25 flops against ~20 steps of 21 instructions
-        const int base_idx = r.j1 - wlo; // element = point + 1
-        // the two runs one after the other, t counted from each run's first point (one loop over both with the
-        // side chosen per point cost a compare and three selects per point: 25 -> 21 VALU instructions per point
-        // for ~5 % more steps)
-        auto run = [&](const int n, const int n_max, const double c, const int i0) {
-          const int n_steps = (n_max + kRowLanes - 1) / kRowLanes; // wave-uniform: a scalar loop counter
-          // x of the lane's point by a running sum, eight steps of xstep at a time (one add instead of a conversion
-          // and an fma per point; <= 20 steps of a run: <= 20 ulp of x, 1e-14 of the value at most): 5.38 vs 5.42 ms
-          // per headline step
-          double xt = fma((double)col, xstep, c);
-          const double xs8 = (double)kRowLanes * xstep;
-          // ... and ONE counter per lane: the byte offset of its point in the image, which is the loop's predicate too
-          int ab = (col + i0) * 8;
-          const int ab_end = (n + i0) * 8;
-          for (int st = 0; st < n_steps; ++st, ab += 8 * kRowLanes) {
-            if (ab < ab_end) {
-              const double y = region2_val(q2, xt);
-              xt += xs8;
-              if (COUNT) ++n_r2;
-              atomicAdd(reinterpret_cast<double *>(reinterpret_cast<char *>(s_a) + ab), wa * y); // return-less LDS adds: no wait for a read, runs of different lines overlap
-              atomicAdd(reinterpret_cast<double *>(reinterpret_cast<char *>(s_e) + ab), we * y);
-            }
-          }
-        };
-        // (step counts by rows_max() per round; from per-round maxima that the lanes = lines phase wrote to LDS: 3.51 vs 3.50 ms, 128-129 VGPRs)
-        run(live ? na : 0, rows_max(live ? na : 0), fma((double)(a0 - r.il()), xstep, -z.xs2l), a0 + base_idx);
-        run(live ? nb : 0, rows_max(live ? nb : 0), fma((double)(b0 - z.ir2()), xstep, z.xs2r), b0 + base_idx);
-      }
-      // region 4 (lineshape.f:530-546), on both sides of the region-3 interval
-      for (int g = 0; g < n_items4; g += kRows) {
-        const int it = min(g + row, n_items4 - 1);
-        const bool live = g + row < n_items4;
-        const int ls_ = s_item[wave][1][0][it];
-        const FastRec &r = frow[base + ls_];
-        const ColdRec &z = crow[base + ls_];
-        const unsigned ul = (unsigned)s_item[wave][1][1][it], ur = (unsigned)s_item[wave][1][2][it];
-        const int a0 = (int)(ul & 0xffffu), na = (int)((ul >> 16) & 0x3fffu), b0 = (int)(ur & 0xffffu), nb = (int)(ur >> 16);
-        const int n = live ? na + nb : 0;
-        const int j1 = r.j1;
-        CorePend P;
-        P.base = j1 - wlo; // element = point + 1
-        P.gc = grid_at(gp, j1 + kHalf);
-        P.x0 = z.x0;
-        P.dwp = z.dwp;
-        P.inv_dwp = cold_inv_dwp(z.dwp);
-        P.ryf = cold_ryf(z.ry);
-        P.ryf2 = P.ryf * P.ryf;
-        P.two_ryf = P.ryf + P.ryf;
-        P.wa = r.wabs;
-        P.we = r.wemi;
-        // the cosine's tier of this round: the smallest of its lines' (from the lanes = lines phase)
-        const int tier_ = live ? (int)(ul >> 30) : 2;
-        const int cos_tier = __all(tier_ == 2) ? 2 : (__all(tier_ >= 1) ? 1 : 0);
-        const int n_steps = (rows_max(n) + kRowLanes - 1) / kRowLanes;
-        for (int st = 0; st < n_steps; ++st) {
-          const int t = col + kRowLanes * st;
-          P.k = t < na ? a0 + t : b0 + (t - na);
-          if (COUNT) n_r4 += t < n;
-          core_eval4(P, t < n, gp, cos_tier, p6_vgpr, s_a, s_e);
-        }
-      }
-    }
-  }
+  const ZoneWalk W{frow, crow, gp, &s_item[wave][0][0][0], wlo, whi, lane, p6_vgpr};
+  for (int ci = wave; ci < n_chunks; ci += NW) zones_chunk(W, sink, l0 + 64 * ((grp & 1) ? n_chunks - 1 - ci : ci), l1);
   if (COUNT) {
-    count_add(cnt, kCntRegion2, n_r2, lane);
-    count_add(cnt, kCntRegion3, n_r3, lane);
-    count_add(cnt, kCntRegion4, n_r4, lane);
+    count_add(cnt, kCntRegion2, sink.n_r[0], lane);
+    count_add(cnt, kCntRegion3, sink.n_r[1], lane);
+    count_add(cnt, kCntRegion4, sink.n_r[2], lane);
   }
   if (NW > 1) __syncthreads();
   const size_t row = (size_t)layer * (size_t)(g_hi - g_lo);
@@ -2327,22 +2394,63 @@ __device__ __forceinline__ void wings_mc_polys(const McFarPass *__restrict__ far
 // same image, two waves per 64-point slot, the tables stored once instead of stored, read and stored again: 13.5 vs 13.1
 // ms per build of the pair tables, 24.0 vs 21.5 for the three ctypes.  The wings stages ran at this kernel's 16 waves per
 // CU instead of their own 24, behind barriers, and the zones part no longer ran beside the far passes.  Removed.)
+// The multi-channel sink: three sums, wabs, wemi and w3, into the planes of the line's levels (McChannels) in an image
+// [n_ch][kPlane] that the workgroup's waves share; the planes' indices travel in the item's fourth word, 3 x 10 bits.
+template <int kPlane>
+struct McSink {
+  static constexpr int kWords = 4;
+  double *s_img;
+  const int *lev_up, *lev_lo;
+  const McChannels &mc;
+  struct Chans {
+    int lo, ue, ua;
+    __device__ __forceinline__ int pack() const { return lo | (ue << 10) | (ua << 20); }
+    static __device__ __forceinline__ Chans unpack(int w) { return {w & 0x3ff, (w >> 10) & 0x3ff, w >> 20}; }
+  };
+  struct Line {
+    double *s_img;
+    Chans ch;
+    double wa, we, w3;
+    int ibase;
+    __device__ __forceinline__ void add(int k, double y) const {
+      double *const p_lo = s_img + ch.lo * kPlane + ibase, *const p_ue = s_img + ch.ue * kPlane + ibase,
+                   *const p_ua = s_img + ch.ua * kPlane + ibase;
+      atomicAdd(&p_lo[k], wa * y);
+      atomicAdd(&p_ue[k], we * y);
+      atomicAdd(&p_ua[k], w3 * y);
+    }
+    __device__ __forceinline__ void add_at_byte(int ab, double y) const {
+      // byte offsets of the line's second and third plane relative to its first
+      const int d_ue = (ch.ue - ch.lo) * (kPlane * 8), d_ua = (ch.ua - ch.lo) * (kPlane * 8);
+      char *const plane0 = reinterpret_cast<char *>(s_img + ch.lo * kPlane);
+      atomicAdd(reinterpret_cast<double *>(plane0 + ab), wa * y);
+      atomicAdd(reinterpret_cast<double *>(plane0 + ab + d_ue), we * y);
+      atomicAdd(reinterpret_cast<double *>(plane0 + ab + d_ua), w3 * y);
+    }
+  };
+  __device__ __forceinline__ Chans channels(int lv) const {
+    const int lu = lev_up[lv], ll = lev_lo[lv];
+    return {mc.stride * ll + mc.o_lo, mc.stride * lu + mc.o_up_e, mc.stride * lu + mc.o_up_a};
+  }
+  __device__ __forceinline__ Line line(const FastRec &r, const Chans &ch, int ibase) const {
+    return {s_img, ch, r.wabs, r.wemi, r.w3, ibase};
+  }
+  __device__ __forceinline__ void count(int, bool) {}
+};
 template <int WT, int NW>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) void sr_zones_mc_kernel(
     const FastRec *__restrict__ fast, const ColdRec *__restrict__ cold, const int *__restrict__ lev_up,
     const int *__restrict__ lev_lo, IcIndex ix, const int *__restrict__ zmax, int n_sub, int n_groups, int g_lo, int g_hi,
     GridParams gp, McChannels mc, double *__restrict__ out, int n_rows_total, int row0) {
   extern __shared__ double s_dyn[];
-  constexpr int kPlane = WT + 2;             // point p of the group lives at element p + 1 of its plane (see the folded kernel)
+  constexpr int kPlane = WT + 2;             // point p of the group lives at element p + 1 of its plane
   double *const s_img = s_dyn;               // [n_ch][kPlane]
-  int *const s_item_all = reinterpret_cast<int *>(s_dyn + (size_t)mc.n_ch * kPlane); // [NW][2][4][64]
+  int *const s_item_all = reinterpret_cast<int *>(s_dyn + (size_t)mc.n_ch * kPlane); // [NW][2][4][64]: the waves' item lists (ZoneWalk)
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int layer = wg / n_groups, grp = wg - layer * n_groups;
   const int wlo = g_lo + grp * WT;
   const int whi = min(wlo + WT, g_hi) - 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int *const s_item = s_item_all + wave * (2 * 4 * 64);
-  auto item = [&](int region, int field, int at) -> int & { return s_item[(region * 4 + field) * 64 + at]; };
   const int zm = min(zmax[layer], kHalf - 1);
   for (int e = threadIdx.x; e < mc.n_ch * kPlane; e += 64 * NW) s_img[e] = 0.;
   __syncthreads();
@@ -2351,165 +2459,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
   const FastRec *frow = fast + (size_t)layer * n_sub;
   const ColdRec *crow = cold + (size_t)layer * n_sub;
   const int n_chunks = (l1 - l0 + 63) >> 6;
-  for (int ci = wave; ci < n_chunks; ci += NW) {
-    const int base = l0 + 64 * ((grp & 1) ? n_chunks - 1 - ci : ci); // serpentine sweep, see the folded kernel
-    const int lv = min(base + lane, l1 - 1);
-    bool act;
-    unsigned run2l, run2r, run4l, run4r;
-    int n_items2, n_items4;
-    {
-      // ---- lane = line: interval arithmetic of every line, region 3 (see sr_abscoeff_near_zones_kernel)
-      const FastRec &r = frow[lv];
-      const int j1 = r.j1, il = r.il(), ir = r.ir();
-      const int zl = max(j1 + il - 1, j1), zh = min(j1 + ir - 1, j1 + (kImxsig - 1));
-      act = base + lane < l1 && zl <= whi && zh >= wlo;
-      if (__ballot(act) == 0) continue;
-      const ColdRec &z = crow[lv];
-      const int k3lo = z.k3lo(), k3hi = z.k3hi();
-      const int il2 = z.il2(), ir2 = z.ir2();
-      const int k_lo = max(wlo - j1 + 1, 1), k_hi = min(whi - j1 + 1, kImxsig);
-      {
-        const int a0 = max(il, k_lo), a1 = il < il2 ? min(il2, k_hi) : a0 - 1;
-        const int b0 = max(ir2, k_lo), b1 = ir2 < ir ? min(ir, k_hi) : b0 - 1;
-        run2l = (unsigned)a0 | ((unsigned)max(a1 - a0 + 1, 0) << 16);
-        run2r = (unsigned)b0 | ((unsigned)max(b1 - b0 + 1, 0) << 16);
-      }
-      const int c_lo = max(((il2 == il) ? il - 1 : il2) + 1, k_lo), c_hi = min(((ir2 == ir) ? ir + 1 : ir2) - 1, k_hi);
-      const bool has3 = k3lo <= k3hi;
-      {
-        const int a0 = c_lo, a1 = has3 ? min(k3lo - 1, c_hi) : c_hi;
-        const int b0 = has3 ? max(k3hi + 1, c_lo) : c_hi + 1, b1 = c_hi;
-        run4l = (unsigned)a0 | ((unsigned)max(a1 - a0 + 1, 0) << 16);
-        run4r = (unsigned)b0 | ((unsigned)max(b1 - b0 + 1, 0) << 16);
-      }
-      const int e0 = max(k3lo, c_lo), e1 = min(k3hi, c_hi);
-      const int n3 = (act && has3) ? max(e1 - e0 + 1, 0) : 0;
-      const bool w2 = act && ((run2l >> 16) + (run2r >> 16)) > 0, w4 = act && ((run4l >> 16) + (run4r >> 16)) > 0;
-      // the three planes of the lane's line, as element offsets, packed for the rows: 3 x 10 bits of channel index
-      const int lu = lev_up[lv], ll = lev_lo[lv];
-      const int ch_lo = mc.stride * ll + mc.o_lo, ch_ue = mc.stride * lu + mc.o_up_e, ch_ua = mc.stride * lu + mc.o_up_a;
-      const int chans = ch_lo | (ch_ue << 10) | (ch_ua << 20);
-      if (__any(n3 > 0 || w4)) {
-        const WinX xf{gp.lin_start, gp.lin_delta, grid_at(gp, j1 + kHalf)};
-        const double x0 = z.x0, dwp = z.dwp, inv_dwp = cold_inv_dwp(z.dwp), ryf = cold_ryf(z.ry);
-        const double wa = r.wabs, we = r.wemi, w3 = r.w3;
-        const int ibase = j1 - wlo; // element = point + 1
-        {
-          const double rx_max = fmax(fabs(xf((int)(run4l & 0xffffu)) - x0),
-                                     fabs(xf((int)(run4r & 0xffffu) + (int)(run4r >> 16) - 1) - x0)) * inv_dwp * 1.001;
-          const double ui_max = (ryf + ryf) * rx_max;
-          run4l |= (ui_max < 6.5e-3 ? 2u : (ui_max < 0.78 ? 1u : 0u)) << 30;
-        }
-        double *const p_lo = s_img + ch_lo * kPlane + ibase, *const p_ue = s_img + ch_ue * kPlane + ibase,
-                     *const p_ua = s_img + ch_ua * kPlane + ibase;
-        for (int t = 0; __any(t < n3); ++t) {
-          if (t < n3) {
-            const int k = e0 + t;
-            const double d = fabs(xf(k) - x0);
-            double rx = d * inv_dwp;
-            rx = fma(fma(-dwp, rx, d), inv_dwp, rx);
-            const double y = core_region3(ryf, (double)(float)(-rx));
-            atomicAdd(&p_lo[k], wa * y);
-            atomicAdd(&p_ue[k], we * y);
-            atomicAdd(&p_ua[k], w3 * y);
-          }
-        }
-      }
-      const unsigned long long m2 = __ballot(w2), m4 = __ballot(w4);
-      n_items2 = __builtin_popcountll(m2);
-      n_items4 = __builtin_popcountll(m4);
-      if (w2) {
-        const int at = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m2 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m2, 0u));
-        item(0, 0, at) = lane;
-        item(0, 1, at) = (int)run2l;
-        item(0, 2, at) = (int)run2r;
-        item(0, 3, at) = chans;
-      }
-      if (w4) {
-        const int at = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m4 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m4, 0u));
-        item(1, 0, at) = lane;
-        item(1, 1, at) = (int)run4l;
-        item(1, 2, at) = (int)run4r;
-        item(1, 3, at) = chans;
-      }
-    }
-    {
-      constexpr int kRowLanes = SR_ZONES_ROW, kRows = 64 / kRowLanes;
-      const int row = lane / kRowLanes, col = lane % kRowLanes;
-      // region 2 (lineshape.f:503-522), eight lines at a time (see the folded kernel)
-      for (int g = 0; g < n_items2; g += kRows) {
-        const int it = min(g + row, n_items2 - 1);
-        const bool live = g + row < n_items2;
-        const int ls_ = item(0, 0, it);
-        const FastRec &r = frow[base + ls_];
-        const ColdRec &z = crow[base + ls_];
-        const unsigned ul = (unsigned)item(0, 1, it), ur = (unsigned)item(0, 2, it);
-        const int chans = item(0, 3, it);
-        const int a0 = (int)(ul & 0xffffu), na = (int)(ul >> 16), b0 = (int)(ur & 0xffffu), nb = (int)(ur >> 16);
-        const double xstep = r.xstep, wa = r.wabs, we = r.wemi, w3 = r.w3;
-        double q2[8];
-        region2_coef_fma(z.ry, q2);
-        const int base_idx = r.j1 - wlo; // element = point + 1
-        // byte offsets of the line's second and third plane relative to its first
-        const int d_ue = (((chans >> 10) & 0x3ff) - (chans & 0x3ff)) * (kPlane * 8), d_ua = ((chans >> 20) - (chans & 0x3ff)) * (kPlane * 8);
-        char *const plane0 = reinterpret_cast<char *>(s_img + (chans & 0x3ff) * kPlane);
-        auto run = [&](const int n, const int n_max, const double c, const int i0) {
-          const int n_steps = (n_max + kRowLanes - 1) / kRowLanes;
-          double xt = fma((double)col, xstep, c);
-          const double xs8 = (double)kRowLanes * xstep;
-          int ab = (col + i0) * 8;
-          const int ab_end = (n + i0) * 8;
-          for (int st = 0; st < n_steps; ++st, ab += 8 * kRowLanes) {
-            if (ab < ab_end) {
-              const double y = region2_val(q2, xt);
-              xt += xs8;
-              atomicAdd(reinterpret_cast<double *>(plane0 + ab), wa * y);
-              atomicAdd(reinterpret_cast<double *>(plane0 + ab + d_ue), we * y);
-              atomicAdd(reinterpret_cast<double *>(plane0 + ab + d_ua), w3 * y);
-            }
-          }
-        };
-        run(live ? na : 0, rows_max(live ? na : 0), fma((double)(a0 - r.il()), xstep, -z.xs2l), a0 + base_idx);
-        run(live ? nb : 0, rows_max(live ? nb : 0), fma((double)(b0 - z.ir2()), xstep, z.xs2r), b0 + base_idx);
-      }
-      // region 4 (lineshape.f:530-546), on both sides of the region-3 interval
-      for (int g = 0; g < n_items4; g += kRows) {
-        const int it = min(g + row, n_items4 - 1);
-        const bool live = g + row < n_items4;
-        const int ls_ = item(1, 0, it);
-        const FastRec &r = frow[base + ls_];
-        const ColdRec &z = crow[base + ls_];
-        const unsigned ul = (unsigned)item(1, 1, it), ur = (unsigned)item(1, 2, it);
-        const int chans = item(1, 3, it);
-        const int a0 = (int)(ul & 0xffffu), na = (int)((ul >> 16) & 0x3fffu), b0 = (int)(ur & 0xffffu), nb = (int)(ur >> 16);
-        const int n = live ? na + nb : 0;
-        const int j1 = r.j1;
-        const int ebase = j1 - wlo; // element = point + 1
-        const double gc = grid_at(gp, j1 + kHalf), x0 = z.x0, dwp = z.dwp, inv_dwp = cold_inv_dwp(z.dwp);
-        const double ryf = cold_ryf(z.ry), ryf2 = ryf * ryf, two_ryf = ryf + ryf;
-        const double wa = r.wabs, we = r.wemi, w3 = r.w3;
-        double *const p_lo = s_img + (chans & 0x3ff) * kPlane + ebase, *const p_ue = s_img + ((chans >> 10) & 0x3ff) * kPlane + ebase,
-                     *const p_ua = s_img + (chans >> 20) * kPlane + ebase;
-        const int tier_ = live ? (int)(ul >> 30) : 2;
-        const int cos_tier = __all(tier_ == 2) ? 2 : (__all(tier_ >= 1) ? 1 : 0);
-        const int n_steps = (rows_max(n) + kRowLanes - 1) / kRowLanes;
-        const WinX xf{gp.lin_start, gp.lin_delta, gc};
-        for (int st = 0; st < n_steps; ++st) {
-          const int t = col + kRowLanes * st;
-          const int k = t < na ? a0 + t : b0 + (t - na);
-          if (t < n) {
-            const double d = fabs(xf(k) - x0);
-            double rx = d * inv_dwp; // |x(k)-x0|/dw correctly rounded: one residual correction
-            rx = fma(fma(-dwp, rx, d), inv_dwp, rx);
-            const double y = core_region4_m(ryf, ryf2, two_ryf, (double)(float)rx, cos_tier, p6_vgpr);
-            atomicAdd(&p_lo[k], wa * y);
-            atomicAdd(&p_ue[k], we * y);
-            atomicAdd(&p_ua[k], w3 * y);
-          }
-        }
-      }
-    }
-  }
+  McSink<kPlane> sink{s_img, lev_up, lev_lo, mc};
+  const ZoneWalk W{frow, crow, gp, s_item_all + wave * (2 * 4 * 64), wlo, whi, lane, p6_vgpr};
+  // the serpentine sweep of sr_abscoeff_near_zones_kernel
+  for (int ci = wave; ci < n_chunks; ci += NW) zones_chunk(W, sink, l0 + 64 * ((grp & 1) ? n_chunks - 1 - ci : ci), l1);
   __syncthreads();
   // the image's planes to their spectra: out [n_ch][n_rows_total][n_pts], stores (sr_wings_mc_kernel adds)
   const size_t n_pts = (size_t)(g_hi - g_lo);
