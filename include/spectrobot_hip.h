@@ -898,6 +898,44 @@ int sr_set_ils(const sr_ils_desc *ils);
  * sum_k h (phi_k + phi_(k+1)) / 2 + h^2 (m_k - m_(k+1)) / 12.  Refusals as sr_set_ils (and a NULL argument). */
 int sr_ils_area(const sr_ils_desc *ils, double *area);
 
+/* Absorbers without lines: a cross-section, collision-induced-absorption or extinction TABLE as a gas of the coefficient
+ * rows.  The build's own definition (the reference has no counterpart).  A table is n_sets sets; set k has a
+ * temperature set_temp[k] (kept for the caller's plans: the calls below take the plan, not the policy), a regular
+ * wavenumber axis set_v0[k] + i set_dv[k], i < n_k = set_off[k+1] - set_off[k], and the values values[set_off[k] + i],
+ * used as given (negative ones included).  At grid point j, nu_j = w0 + (double)(g_lo + j) step (unfused, as the limb
+ * calls form it), t = (nu_j - v0_k) / dv_k, i = floor(t):
+ *   s_k(j) = a_k[i] + (a_k[i+1] - a_k[i]) (t - i);  a_k[n_k - 1] at t == n_k - 1;  exactly 0 where t < 0 or t > n_k - 1.
+ * Row r with sets (lo, hi) = set2[r], weights w2[r], their temperature derivatives dw2[r], scale c_r (1 without `scale`):
+ *   abs  = c_r (w_lo s_lo + w_hi s_hi)            emi  = source ? abs B(nu_j, temps[r]) : 0
+ *   dabs = c_r (dw_lo s_lo + dw_hi s_hi)          demi = source ? dabs B + abs dB/dT : 0
+ * B = 2 h c^2 nu^3 / (exp(c2 nu / T) - 1), the Planck function of the limb calls' init_mode 2; the scale is held fixed
+ * under d / dT.  accumulate != 0: the four outputs are added to (a point outside both of a row's sets is left as it is;
+ * without a source emi / demi are left as they are).
+ * sr_abs_table_create: all arrays HOST, copied; the handle is device-resident on the current device.  SR_ERR_ARG: a NULL
+ * argument, n_sets <= 0, set_off[0] != 0, a set shorter than 2, dv <= 0 or not finite, v0 not finite, a temperature <= 0 or
+ * not finite; SR_ERR_LIMIT: n_sets > SR_MAX_ABS_SETS or more than SR_MAX_ABS_VALUES values.
+ * sr_abs_table_layers_dev: temps, scale (or NULL), set2, w2, dw2 (or NULL) are HOST arrays of n_rows rows, staged through
+ * the calling thread's pinned ring (no stream is made); abs_out, emi_out, dabs_out, demi_out DEVICE [n_rows][n_pts],
+ * dabs_out / demi_out NULL: no derivative.  Runs on `stream` (hipStream_t), ordered after the handle's creation; the
+ * handle belongs to the device it was made on, and sr_abs_table_destroy waits for its last call.  Every argument is
+ * checked before the first copy or launch and a refused call leaves the outputs untouched:
+ * SR_ERR_ARG for a NULL handle, temps, set2, w2, abs_out or emi_out, n_rows <= 0, n_pts <= 0, g_lo < 0, a set index
+ * outside 0 .. n_sets - 1, a temperature <= 0 or not finite, a scale, weight, w0 or step that is not finite, dabs_out
+ * without dw2, exactly one of dabs_out / demi_out with a source, the handle on another device; SR_ERR_LIMIT for
+ * n_pts > 2000000, g_lo + n_pts > INT32_MAX or n_rows > SR_MAX_ABS_ROWS.
+ * Checked against an extended-precision reference (tests/test_gpu_absorber_table.py). */
+#define SR_MAX_ABS_SETS 4096
+#define SR_MAX_ABS_VALUES 134217728 /* 2^27: 1 GiB of values */
+#define SR_MAX_ABS_ROWS 65536
+typedef struct sr_abs_table sr_abs_table;
+int sr_abs_table_create(int n_sets, const double *set_temp, const double *set_v0, const double *set_dv, const int64_t *set_off,
+                        const double *values, sr_abs_table **out);
+int sr_abs_table_destroy(sr_abs_table *h);
+int sr_abs_table_layers_dev(sr_abs_table *h, int n_rows, const double *temps, const double *scale, const int32_t *set2,
+                            const double *w2, const double *dw2, double w0, double step, int64_t g_lo, int64_t n_pts,
+                            int source, int accumulate, double *abs_out, double *emi_out, double *dabs_out, double *demi_out,
+                            void *stream);
+
 /* Evaluation mode of the coefficient op.  Far region-1 wings by local Taylor expansions per box of grid
  * points (truncation <= sr_far_field_truncation_bound() of a line's own contribution: 1.6e-11 as built by default, degree
  * 19; 2.6e-13 with -DSR_KFD=22; a box takes a line from sr_far_field_min_distance() on), near field exact, with the expansions built

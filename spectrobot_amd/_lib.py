@@ -19,6 +19,7 @@ SR_ERR_ARG, SR_ERR_LIMIT, SR_ERR_HIP, SR_ERR_NODEVICE, SR_ERR_UNSUPPORTED, SR_ER
 IMXSIG = 13010
 SR_STRENGTH_EINSTEIN, SR_STRENGTH_HITRAN = 0, 1
 SR_MAX_ILS_TAB = 65536
+SR_MAX_ABS_SETS, SR_MAX_ABS_VALUES, SR_MAX_ABS_ROWS = 4096, 1 << 27, 65536
 
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int32)
@@ -202,6 +203,11 @@ SYMBOLS = {
                                                      C.c_int, C.c_double, C.c_int, dp, C.c_void_p]),
     "sr_set_ils": (C.c_int, [C.POINTER(IlsDesc)]),
     "sr_ils_area": (C.c_int, [C.POINTER(IlsDesc), dp]),
+    "sr_abs_table_create": (C.c_int, [C.c_int, dp, dp, dp, C.POINTER(C.c_int64), dp, C.POINTER(C.c_void_p)]),
+    "sr_abs_table_destroy": (C.c_int, [C.c_void_p]),
+    "sr_abs_table_layers_dev": (C.c_int, [C.c_void_p, C.c_int, dp, dp, ip, dp, dp, C.c_double, C.c_double, C.c_int64,
+                                          C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "sr_set_points_per_lane": (C.c_int, [C.c_int]),
     "sr_set_band_fusion": (C.c_int, [C.c_int]),
     "sr_far_field_truncation_bound": (C.c_double, []),

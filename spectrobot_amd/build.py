@@ -8,7 +8,8 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libspectrobot_hip.so")
 SOURCES = ["sr_api.hip", "sr_kernels.hip"]
 DEPS = SOURCES + ["sr_device.hpp", "sr_kernels.hpp", "sr_constants.hpp", "sr_limb_plan.hpp", "sr_limb_common.hpp",
-                  "sr_limb_state.inc", "sr_lowres_weights_tab.inc", "tips2003_tables.inc", "../../include/spectrobot_hip.h"]
+                  "sr_limb_state.inc", "sr_lowres_weights_tab.inc", "sr_absorber_table.inc",
+                  "tips2003_tables.inc", "../../include/spectrobot_hip.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-fno-fast-math", "-fgpu-rdc" if False else "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

@@ -2510,6 +2510,7 @@ int64_t sr_last_state_walks(void) { return g_last_state_walks; }
 // the rays share their shells -- the folded sweep's packed records, all made ONCE.  The reference computes a LOS's
 // steps once too (los.calc_radtran_steps, spect_main_module.py:2746-2767) and runs radtran on them many times.
 struct sr_los {
+  static constexpr const char *kName = "sr_los";
   Stager s_los, s_fold, s_vmr, s_x;
   LosDev D{};
   FoldStage F{};
@@ -2526,22 +2527,23 @@ struct sr_los {
   bool k_timed = false;
 };
 
-// Every call on a resident batch works inside one LosScope.  enter(): the handle belongs to the device it was made on
+// Every call on a resident batch works inside one LosScope (a HandleScope; sr_abs_table's calls use the same scope).
+// enter(): the handle belongs to the device it was made on
 // (its buffers, and the pinned stagers that would rebuild themselves on another current device and then copy into this
 // one's memory), and `st` waits for the handle's last use.  leave() records that use behind the call's work on `st` and
 // returns the status; a call that returns early after enter() -- a failed launch or copy with work already enqueued on
 // the handle -- leaves through the destructor, which records it all the same.
-class LosScope {
+template <class H> class HandleScope {
  public:
-  LosScope(sr_los *h, hipStream_t st) : h_(h), st_(st) {}
-  ~LosScope() {
+  HandleScope(H *h, hipStream_t st) : h_(h), st_(st) {}
+  ~HandleScope() {
     if (open_) (void)record();
   }
   int enter() {
     int cur = -1;
     HIPCHK(hipGetDevice(&cur));
     if (cur != h_->dev) {
-      g_err = "sr_los handle used on device " + std::to_string(cur) + ", made on device " + std::to_string(h_->dev);
+      g_err = std::string(H::kName) + " handle used on device " + std::to_string(cur) + ", made on device " + std::to_string(h_->dev);
       return SR_ERR_ARG;
     }
     if (h_->last_recorded) HIPCHK(hipStreamWaitEvent(st_, h_->ev_last, 0));
@@ -2561,10 +2563,11 @@ class LosScope {
     h_->last_recorded = h_->last_recorded || e == hipSuccess;
     return e;
   }
-  sr_los *h_;
+  H *h_;
   hipStream_t st_;
   bool open_ = false;
 };
+using LosScope = HandleScope<sr_los>;
 
 // ------------------------------------------------------------------------
 // The instrument step's per-thread device state (sr_hires_to_lowres_shard_dev, and sr_retrieval_forward_dev whose
@@ -3957,6 +3960,144 @@ int sr_ils_area(const sr_ils_desc *ils, double *area) {
     area[q] = h * sum;
   }
   return SR_OK;
+}
+
+} // extern "C"
+
+// A tabulated absorber resident on the device (sr_abs_table_create): the values of all sets in one block, their axes on
+// the host (a call stages the descriptors of the sets its rows use with the rows' plan).  Read-only after creation.
+struct sr_abs_table {
+  static constexpr const char *kName = "sr_abs_table";
+  DevBuf d_values;
+  std::vector<double> v0, dv;
+  std::vector<int64_t> off; // [n_sets + 1]
+  int n_sets = 0, dev = -1;
+  hipEvent_t ev_last = nullptr; // HandleScope: destroy waits for the last call that reads the values
+  bool last_recorded = false;
+};
+
+extern "C" {
+
+int sr_abs_table_create(int n_sets, const double *set_temp, const double *set_v0, const double *set_dv, const int64_t *set_off,
+                        const double *values, sr_abs_table **out) {
+  if (!set_temp || !set_v0 || !set_dv || !set_off || !values || !out || n_sets <= 0) return SR_ERR_ARG;
+  if (n_sets > SR_MAX_ABS_SETS) return SR_ERR_LIMIT;
+  if (set_off[0] != 0) return SR_ERR_ARG;
+  for (int k = 0; k < n_sets; ++k) {
+    if (set_off[k + 1] < set_off[k] || set_off[k + 1] - set_off[k] < 2) return SR_ERR_ARG;
+    if (set_off[k + 1] > SR_MAX_ABS_VALUES) return SR_ERR_LIMIT;
+    if (!(set_dv[k] > 0.0) || !std::isfinite(set_dv[k]) || !std::isfinite(set_v0[k])) return SR_ERR_ARG;
+    if (!(set_temp[k] > 0.0) || !std::isfinite(set_temp[k])) return SR_ERR_ARG;
+  }
+  sr_abs_table *h = new sr_abs_table;
+  h->n_sets = n_sets;
+  h->v0.assign(set_v0, set_v0 + n_sets);
+  h->dv.assign(set_dv, set_dv + n_sets);
+  h->off.assign(set_off, set_off + n_sets + 1);
+  const size_t bytes = sizeof(double) * (size_t)set_off[n_sets];
+  hipError_t e = hipGetDevice(&h->dev);
+  int rc = e == hipSuccess ? h->d_values.ensure(bytes) : hip_fail(e, "hipGetDevice");
+  if (!rc) {
+    e = hipMemcpy(h->d_values.p, values, bytes, hipMemcpyHostToDevice); // (complete on return: every later call may read)
+    if (e != hipSuccess) rc = hip_fail(e, "sr_abs_table_create: copy");
+  }
+  if (rc) {
+    h->d_values.release();
+    delete h;
+    return rc;
+  }
+  *out = h;
+  return SR_OK;
+}
+
+int sr_abs_table_destroy(sr_abs_table *h) {
+  if (!h) return SR_OK;
+  if (h->last_recorded) (void)hipEventSynchronize(h->ev_last);
+  h->d_values.release();
+  if (h->ev_last) (void)hipEventDestroy(h->ev_last);
+  delete h;
+  return SR_OK;
+}
+
+int sr_abs_table_layers_dev(sr_abs_table *h, int n_rows, const double *temps, const double *scale, const int32_t *set2,
+                            const double *w2, const double *dw2, double w0, double step, int64_t g_lo, int64_t n_pts,
+                            int source, int accumulate, double *abs_out, double *emi_out, double *dabs_out, double *demi_out,
+                            void *stream) {
+  if (!h || !temps || !set2 || !w2 || !abs_out || !emi_out || n_rows <= 0 || n_pts <= 0 || g_lo < 0) return SR_ERR_ARG;
+  if (dabs_out && !dw2) return SR_ERR_ARG;
+  if (source ? (dabs_out != nullptr) != (demi_out != nullptr) : (demi_out && !dabs_out)) return SR_ERR_ARG;
+  if (!std::isfinite(w0) || !std::isfinite(step)) return SR_ERR_ARG;
+  if (n_pts > 2000000 || g_lo + n_pts > INT32_MAX || n_rows > SR_MAX_ABS_ROWS) return SR_ERR_LIMIT;
+  const bool deriv = dabs_out != nullptr;
+  for (int r = 0; r < n_rows; ++r) {
+    if (!(temps[r] > 0.0) || !std::isfinite(temps[r]) || (scale && !std::isfinite(scale[r]))) return SR_ERR_ARG;
+    for (int q = 0; q < 2; ++q) {
+      if (set2[2 * r + q] < 0 || set2[2 * r + q] >= h->n_sets) return SR_ERR_ARG; // would read out of the table
+      if (!std::isfinite(w2[2 * r + q]) || (deriv && !std::isfinite(dw2[2 * r + q]))) return SR_ERR_ARG;
+    }
+  }
+  // the rows in the caller's order, cut into launches whose rows use at most kAbsTabMaxSets sets between them; slot2:
+  // a row's two sets as slots of its launch's list
+  struct Group { int row0, row1, n_used; };
+  std::vector<Group> groups;
+  std::vector<double> g_v0, g_dv;
+  std::vector<long long> g_off;
+  std::vector<int> g_n, slot2(2 * (size_t)n_rows), used;
+  auto close_group = [&](int row0, int row1) {
+    groups.push_back(Group{row0, row1, (int)used.size()});
+    for (int q = 0; q < kAbsTabMaxSets; ++q) {
+      const int k = q < (int)used.size() ? used[(size_t)q] : used[0];
+      g_v0.push_back(h->v0[(size_t)k]);
+      g_dv.push_back(h->dv[(size_t)k]);
+      g_off.push_back((long long)h->off[(size_t)k]);
+      g_n.push_back((int)(h->off[(size_t)k + 1] - h->off[(size_t)k]));
+    }
+    used.clear();
+  };
+  auto slot_of = [&](int k) { return (int)(std::find(used.begin(), used.end(), k) - used.begin()); };
+  int row0 = 0;
+  for (int r = 0; r < n_rows; ++r) {
+    const int lo = set2[2 * r], hi = set2[2 * r + 1];
+    const int fresh = (slot_of(lo) == (int)used.size()) + (hi != lo && slot_of(hi) == (int)used.size());
+    if ((int)used.size() + fresh > kAbsTabMaxSets) {
+      close_group(row0, r);
+      row0 = r;
+    }
+    for (int q = 0; q < 2; ++q) {
+      const int k = set2[2 * r + q];
+      if (slot_of(k) == (int)used.size()) used.push_back(k);
+      slot2[2 * (size_t)r + q] = slot_of(k);
+    }
+  }
+  close_group(row0, n_rows);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  HandleScope<sr_abs_table> scope(h, st);
+  int rc = scope.enter();
+  if (rc) return rc;
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const size_t n2 = 2 * (size_t)n_rows;
+  const auto p_T = pk.copy(temps, (size_t)n_rows), p_c = scale ? pk.copy(scale, (size_t)n_rows) : pk.room<double>((size_t)n_rows);
+  const auto p_slot = pk.copy(slot2.data(), n2);
+  const auto p_w = pk.copy(w2, n2), p_dw = pk.copy(dw2, deriv ? n2 : 0, 1);
+  const auto p_v0 = pk.copy(g_v0.data(), g_v0.size()), p_dv = pk.copy(g_dv.data(), g_dv.size());
+  const auto p_off = pk.copy(g_off.data(), g_off.size());
+  const auto p_n = pk.copy(g_n.data(), g_n.size());
+  rc = pk.prepare();
+  if (rc) return rc;
+  if (!scale) std::fill(pk.host(p_c), pk.host(p_c) + n_rows, 1.0);
+  rc = pk.push_early(st);
+  if (rc) return rc;
+  for (size_t g = 0; g < groups.size(); ++g) {
+    const size_t at = g * kAbsTabMaxSets;
+    LAUNCHCHK(launch_absorber_table(groups[g].n_used, pk.dev(p_v0) + at, pk.dev(p_dv) + at, pk.dev(p_off) + at, pk.dev(p_n) + at,
+                                    h->d_values.as<double>(), groups[g].row0, groups[g].row1, pk.dev(p_T), pk.dev(p_c), pk.dev(p_slot),
+                                    pk.dev(p_w), deriv ? pk.dev(p_dw) : nullptr, w0, step, (int)g_lo, (int)n_pts, source != 0,
+                                    accumulate != 0, abs_out, emi_out, dabs_out, demi_out, st));
+  }
+  rc = pk.slot().mark(st);
+  if (rc) return rc;
+  return scope.leave();
 }
 
 // ------------------------------------------------------------------------

@@ -5288,4 +5288,29 @@ int launch_curgod(int which, const double *nd, const double *vmr, const double *
   return (int)hipGetLastError();
 }
 
+#include "sr_absorber_table.inc"
+static_assert(kAbsTabSets == kAbsTabMaxSets, "the host groups the rows by the kernel's set slots");
+
+int launch_absorber_table(int n_used, const double *set_v0, const double *set_dv, const long long *set_off, const int *set_n,
+                          const double *values, int row0, int row1, const double *temps, const double *scale, const int *slot2,
+                          const double *w2, const double *dw2, double w0, double gstep, int g_lo, int n_pts, bool source,
+                          bool accumulate, double *abs_out, double *emi_out, double *dabs_out, double *demi_out, hipStream_t st) {
+  if (row1 <= row0 || n_pts <= 0) return 0;
+  if (n_used <= 0 || n_used > kAbsTabSets) return (int)hipErrorInvalidValue; // (the kernel's LDS columns rest on it)
+  // 16 rows per block: the sets are interpolated again per row chunk (a few loads and a division per set and point
+  // against 16 rows of stores), and 80 rows x 1e5 points are 5 x 391 blocks for 256 CUs
+  constexpr int kRows = 16;
+  const dim3 grid((n_pts + 255) / 256, (row1 - row0 + kRows - 1) / kRows);
+  const bool deriv = dabs_out != nullptr;
+#define SR_ABT(S, D, A)                                                                                                      \
+  hipLaunchKernelGGL((sr_absorber_table_kernel<S, D, A>), grid, dim3(256), 0, st, n_used, set_v0, set_dv, set_off, set_n, values, \
+                     row0, row1, kRows, temps, scale, slot2, w2, dw2, w0, gstep, g_lo, n_pts, abs_out, emi_out, dabs_out, demi_out)
+#define SR_ABT2(S, D) do { if (accumulate) SR_ABT(S, D, true); else SR_ABT(S, D, false); } while (0)
+  if (source) { if (deriv) SR_ABT2(true, true); else SR_ABT2(true, false); }
+  else { if (deriv) SR_ABT2(false, true); else SR_ABT2(false, false); }
+#undef SR_ABT2
+#undef SR_ABT
+  return (int)hipGetLastError();
+}
+
 } // namespace sr

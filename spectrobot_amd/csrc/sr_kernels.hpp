@@ -450,5 +450,14 @@ int launch_glevel_combine(const double *tab, const double *tab_dT, int n_levels,
                           double *demi_out, hipStream_t st);
 int launch_curgod(int which, const double *nd, const double *vmr, const double *f, const double *x,
                   const int *off, int n_seg, double *res, hipStream_t st);
+// A tabulated absorber on coefficient rows (sr_abs_table_layers_dev, sr_absorber_table.inc).  One launch serves rows
+// row0 .. row1 - 1, which together use n_used <= kAbsTabMaxSets sets: set_v0 / set_dv / set_off / set_n [n_used] describe
+// them (axis, offset into values, length), slot2 [n_rows][2] numbers a row's two sets inside this list.  temps, scale,
+// slot2, w2, dw2 are device arrays indexed by the row; dw2, dabs_out, demi_out may be null (no derivative).
+constexpr int kAbsTabMaxSets = 16;
+int launch_absorber_table(int n_used, const double *set_v0, const double *set_dv, const long long *set_off, const int *set_n,
+                          const double *values, int row0, int row1, const double *temps, const double *scale, const int *slot2,
+                          const double *w2, const double *dw2, double w0, double gstep, int g_lo, int n_pts, bool source,
+                          bool accumulate, double *abs_out, double *emi_out, double *dabs_out, double *demi_out, hipStream_t st);
 
 } // namespace sr

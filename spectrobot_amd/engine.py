@@ -416,6 +416,159 @@ class LineSet(object):
         return dict(zip(names, (int(v) for v in c)))
 
 
+class AbsorberTable(object):
+    """An absorber without lines -- a cross-section, collision-induced-absorption or extinction table -- resident on the
+    device (sr_abs_table_create), put onto coefficient rows by layers().  The build's own definition; the
+    reference has no counterpart.
+
+    sets: a list of (T, v0, dv, values[, P]): a temperature (K), a regular wavenumber axis v0 + i dv (cm^-1) and the
+          values on it, used as given, with an optional pressure label (hPa; all sets or none).  Or a dict of the arrays
+          temp, v0, dv, off [n_sets + 1], values [, press].  One table is one spectral band: two sets of a pressure
+          group may not share a temperature (bands of one species are summed with accumulate=True).
+    """
+
+    def __init__(self, sets):
+        if isinstance(sets, dict):
+            temp, v0, dv = (np.ascontiguousarray(sets[k], dtype=np.float64) for k in ("temp", "v0", "dv"))
+            off = np.ascontiguousarray(sets["off"], dtype=np.int64)
+            values = np.ascontiguousarray(sets["values"], dtype=np.float64)
+            press = sets.get("press")
+        else:
+            sets = [tuple(s) for s in sets]
+            if not sets or any(len(s) not in (4, 5) for s in sets):
+                raise ValueError("a set is (T, v0, dv, values[, P])")
+            if len({len(s) for s in sets}) != 1:
+                raise ValueError("either all sets carry a pressure label or none does")
+            temp = np.array([s[0] for s in sets], dtype=np.float64)
+            v0 = np.array([s[1] for s in sets], dtype=np.float64)
+            dv = np.array([s[2] for s in sets], dtype=np.float64)
+            vals = [np.asarray(s[3], dtype=np.float64).ravel() for s in sets]
+            off = np.concatenate([[0], np.cumsum([v.size for v in vals])]).astype(np.int64)
+            values = np.ascontiguousarray(np.concatenate(vals))
+            press = [s[4] for s in sets] if len(sets[0]) == 5 else None
+        self.set_temp, self.set_v0, self.set_dv, self.set_off, self.values = temp, v0, dv, off, values
+        self.set_press = None if press is None else np.ascontiguousarray(press, dtype=np.float64)
+        self.n_sets = temp.size
+        if not (v0.size == dv.size == self.n_sets and off.size == self.n_sets + 1 and values.size == (off[-1] if off.size else 0)):
+            raise ValueError("the set arrays differ in length")
+        if self.set_press is not None and (self.set_press.size != self.n_sets or not np.all(self.set_press > 0)):
+            raise ValueError("pressure labels must be positive, one per set")
+        self._groups()  # (refuses two sets of one group at one temperature)
+        self._h = None  # made by the first layers(): plan() and the host layers above need no device
+
+    def _handle(self):
+        if self._h is None:
+            h = C.c_void_p()
+            check(lib.sr_abs_table_create(self.n_sets, self.set_temp.ctypes.data_as(dp), self.set_v0.ctypes.data_as(dp),
+                                          self.set_dv.ctypes.data_as(dp), self.set_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          self.values.ctypes.data_as(dp), C.byref(h)), "sr_abs_table_create")
+            self._h = h
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.sr_abs_table_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _groups(self):
+        """[(P label or None, set indices in ascending temperature)], in ascending pressure."""
+        if self.set_press is None:
+            labels = [(None, np.arange(self.n_sets))]
+        else:
+            labels = [(p, np.nonzero(self.set_press == p)[0]) for p in np.unique(self.set_press)]
+        out = []
+        for p, idx in labels:
+            idx = idx[np.argsort(self.set_temp[idx], kind="stable")]
+            if np.any(np.diff(self.set_temp[idx]) == 0):
+                raise ValueError("two sets of one pressure group share a temperature: one AbsorberTable is one band")
+            out.append((p, idx))
+        return out
+
+    def plan(self, temps, press=None):
+        """The rows' interpolation plan as plain arrays (set2 [n, 2] int32, w2 [n, 2], dw2 [n, 2]): which two sets a row
+        at temps[r] (and press[r]) mixes, with which weights, and the weights' temperature derivatives.
+
+        With pressure labels AND press, a row uses the group of sets whose label is nearest to its pressure in ln P (a
+        tie goes to the lower pressure); otherwise all sets.  Inside the group, linear in T between the two bracketing
+        sets, dw = -+1 / (T_hi - T_lo); outside the group's range the nearest set, w = (1, 0), dw = 0.  The larger
+        weight is the quotient, the smaller one minus it (exact), so w_lo + w_hi == 1 and dw_lo + dw_hi == 0 exactly.
+        ONE-SIDED at a set's temperature: a row exactly at T_k takes set k with weight 1 and the derivative of the
+        interval ABOVE it (the right derivative of the piecewise-linear interpolant); at the group's hottest set there
+        is no interval above, and the derivative is 0 as it is beyond it."""
+        temps = np.atleast_1d(np.asarray(temps, dtype=np.float64))
+        n = temps.size
+        groups = self._groups()
+        if press is not None and self.set_press is not None:
+            lnp = np.log(np.broadcast_to(np.asarray(press, dtype=np.float64), (n,)))
+        else:
+            lnp = None
+            if self.set_press is not None:  # no row pressure: every set, whatever its label
+                groups = [(None, np.argsort(self.set_temp, kind="stable"))]
+                if np.any(np.diff(self.set_temp[groups[0][1]]) == 0):
+                    raise ValueError("sets of several pressure groups share temperatures: plan() needs press")
+        set2, w2, dw2 = np.zeros((n, 2), np.int32), np.zeros((n, 2)), np.zeros((n, 2))
+        for r in range(n):
+            idx = groups[0][1]
+            if lnp is not None:
+                best = None
+                for p, cand in groups:  # ascending pressure, strict <: a tie keeps the lower pressure
+                    d = abs(lnp[r] - np.log(p))
+                    if best is None or d < best:
+                        best, idx = d, cand
+            tk, T = self.set_temp[idx], temps[r]
+            if T < tk[0] or idx.size == 1:
+                set2[r], w2[r] = (idx[0], idx[0]), (1.0, 0.0)
+            elif T >= tk[-1]:
+                set2[r], w2[r] = (idx[-1], idx[-1]), (1.0, 0.0)
+            else:
+                k = int(np.searchsorted(tk, T, side="right")) - 1  # tk[k] <= T < tk[k + 1]
+                span = tk[k + 1] - tk[k]
+                if T - tk[k] >= tk[k + 1] - T:
+                    hi = (T - tk[k]) / span
+                    lo = 1.0 - hi
+                else:
+                    lo = (tk[k + 1] - T) / span
+                    hi = 1.0 - lo
+                set2[r], w2[r], dw2[r] = (idx[k], idx[k + 1]), (lo, hi), (-1.0 / span, 1.0 / span)
+        return set2, w2, dw2
+
+    def layers(self, temps, grid, press=None, scale=None, source=True, derivative=False, g_lo=0, g_hi=None, out=None,
+               accumulate=False):
+        """abs / emi (and with derivative=True their analytic d / dT, the scale held fixed) of the table on rows at temps
+        over the grid shard [g_lo, g_hi): abs = scale (w_lo s_lo + w_hi s_hi) with the plan() of (temps, press) and the
+        sets interpolated linearly to the grid, emi = abs B(nu, T) (source=False: 0).  accumulate=True adds to `out`.
+        Returns (abs, emi) or ((abs, emi), (dabs, demi)): CUDA float64 [n_rows, g_hi - g_lo]."""
+        w0, step, n_grid = grid_params(grid)
+        g_hi = n_grid if g_hi is None else int(g_hi)
+        npts = g_hi - int(g_lo)
+        if npts <= 0:
+            raise ValueError("empty shard")
+        temps, tp = _d(np.atleast_1d(temps))
+        n = temps.size
+        set2, w2, dw2 = self.plan(temps, press)
+        sc = scp = None
+        if scale is not None:
+            sc, scp = _d(np.broadcast_to(np.asarray(scale, dtype=np.float64), (n,)))
+        n_out = 4 if derivative else 2
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True adds to out=...")
+            outs = [torch.empty((n, npts), dtype=torch.float64, device="cuda") for _ in range(n_out)]
+        else:
+            outs = list(out[0]) + list(out[1]) if derivative else list(out)
+            for t in outs:
+                assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.shape == (n, npts)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        check(lib.sr_abs_table_layers_dev(self._handle(), n, tp, scp, set2.ctypes.data_as(ip), w2.ctypes.data_as(dp),
+                                          dw2.ctypes.data_as(dp) if derivative else None, w0, step, int(g_lo), npts,
+                                          int(bool(source)), int(bool(accumulate)), ptr(outs[0]), ptr(outs[1]),
+                                          ptr(outs[2]) if derivative else None, ptr(outs[3]) if derivative else None,
+                                          _stream_ptr()), "sr_abs_table_layers_dev")
+        return ((outs[0], outs[1]), (outs[2], outs[3])) if derivative else (outs[0], outs[1])
+
+
 def lut_interp(table, idx4, wgt4, pops=None, out=None):
     """LutSet.calculate for n_steps LOS steps on a G table resident in HBM (sr_lut_interp_dev).
     table: CUDA [3, n_PT, n_grid]; idx4 [n_steps, 4] rows, wgt4 [n_steps, 4] = (wP1, wP2, wT1, wT2).

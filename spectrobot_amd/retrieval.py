@@ -118,6 +118,57 @@ class LevelGas(Gas):
         return self.coeffs
 
 
+class TableGas(Gas):
+    """An absorber without lines: an engine.AbsorberTable (cross-section, CIA or extinction table) as a gas of the scene.
+    Its pair is abs = scale x table(nu, T[, P]) per unit of whatever the VMR counts, emi = abs B(nu, T) (source=False: no
+    emission), and the existing columns apply: a cross-section table (cm^2 per molecule) needs no scale; a CIA pair
+    (cm^5 per molecule^2) takes the partner's number density, scale=lambda scene: scene.nd * x_partner, so that abs is
+    cm^2 per molecule of the gas that carries the VMR; a haze is a TableGas whose "VMR" is extinction per unit density.
+    scale: None, an array per layer, or a callable (scene) -> array; held fixed under d / dT (as TempProfile holds columns
+    and pressure fixed).  A retrieval set named after the gas is an ordinary column set.
+
+    A TableGas takes one of the recursion kernels' four gas slots.  accumulate_into=<name of a plain Gas>: the table is
+    folded into that line gas's pair instead -- added to its (abs, emi) and, in a temperature retrieval, to its analytic
+    row derivatives -- sharing that gas's VMR and iso_ratio; it then has no slot, no VMR and no retrieval set of its
+    own (its vmr and iso_ratio arguments are ignored)."""
+
+    def __init__(self, name, table, vmr, scale=None, source=True, iso_ratio=1.0, accumulate_into=None):
+        Gas.__init__(self, name, None, vmr, iso_ratio=iso_ratio)
+        self.table, self.scale, self.source, self.accumulate_into = table, scale, bool(source), accumulate_into
+        self.dcoeffs, self._key = None, None
+
+    def scale_of(self, scene):
+        """The scale per layer as an array, or None."""
+        sc = self.scale(scene) if callable(self.scale) else self.scale
+        if sc is None:
+            return None
+        sc = np.ascontiguousarray(np.broadcast_to(np.asarray(sc, dtype=float), scene.temps.shape))
+        return sc
+
+    def cache_key(self, scene, g_lo, g_hi):
+        """What the pair depends on, by content: temperatures, pressures, scale, shard (and the source switch)."""
+        sc = self.scale_of(scene)
+        return (scene.temps.tobytes(), scene.press.tobytes(), None if sc is None else sc.tobytes(), int(g_lo), int(g_hi),
+                self.source)
+
+    def layer_coefficients(self, scene, g_lo=0, g_hi=None, derivative=False):
+        """(abs, emi) on the scene's layers over [g_lo, g_hi), recomputed when cache_key moved; derivative=True also leaves
+        the ANALYTIC (d abs / dT, d emi / dT) in self.dcoeffs -- the same launch, no second build."""
+        g_hi = len(scene.grid) if g_hi is None else int(g_hi)
+        key = self.cache_key(scene, g_lo, g_hi)
+        if self._key != key or self.coeffs is None or (derivative and self.dcoeffs is None):
+            res = self.table.layers(scene.temps, scene.grid, press=scene.press, scale=self.scale_of(scene), source=self.source,
+                                    derivative=derivative, g_lo=g_lo, g_hi=g_hi)
+            self.coeffs, self.dcoeffs = res if derivative else (res, None)
+            self._key, self.coeffs_shard = key, (g_lo, g_hi)
+        return self.coeffs
+
+
+def _refuse_table_gas(g, who):
+    if isinstance(g, TableGas):
+        raise ValueError("%s works on line lists: gas %r is a TableGas (a tabulated absorber has no lines and no levels)" % (who, g.name))
+
+
 class TvibProfile(smm.LinearProfile_1D_new):
     """The retrieval set of one level's vibrational temperatures: named "tvib:<gas>:<level>", its parameters the nodes
     of an OFFSET profile (K) that is added to the gas's reference, Tvib_L = tvib0[L] + sum_p mask_p x_p, the masks
@@ -279,7 +330,13 @@ class LimbScene(object):
         self.grid = np.asarray(grid, dtype=float)
         self.z, self.temps, self.press = (np.asarray(v, dtype=float) for v in (z, temps, press))
         self.nd = syn.number_density(self.press, self.temps)
-        self.gases = list(gases)
+        # a TableGas with accumulate_into has no slot: it is folded into a line gas's pair (self.folded)
+        self.gases = [g for g in gases if getattr(g, "accumulate_into", None) is None]
+        self.folded = [g for g in gases if getattr(g, "accumulate_into", None) is not None]
+        for t in self.folded:
+            host = [g for g in self.gases if g.name == t.accumulate_into]
+            if len(host) != 1 or isinstance(host[0], (LevelGas, TableGas)):
+                raise ValueError("TableGas %r: accumulate_into=%r names no plain line Gas of the scene" % (t.name, t.accumulate_into))
         self.bands_nm, self.widths_nm = np.asarray(bands_nm, float), np.asarray(widths_nm, float)
         self.bands_nm0, self.widths_nm0 = self.bands_nm.copy(), self.widths_nm.copy()   # the nominal calibration (BandCalibration)
         self.R, self.n_sub, self.out_units = R, n_sub, out_units
@@ -296,11 +353,26 @@ class LimbScene(object):
             if isinstance(g, LevelGas):      # the combine of its resident tables, redone only when its tvib changed
                 g.layer_coefficients(self.temps, self.press, g_lo=g_lo, g_hi=g_hi)
                 continue
-            if g.coeffs is None or refresh or getattr(g, "coeffs_shard", None) != (g_lo, g_hi):
-                g.set_self_pressure(self.press)
-                g.coeffs = g.lineset.abscoeff_layers(self.temps, self.press, tvib=g.tvib, g_lo=g_lo, g_hi=g_hi)
-                g.coeffs_shard = (g_lo, g_hi)
+            self.gas_coefficients(g, refresh, g_lo, g_hi)
         return [g.coeffs for g in self.gases]
+
+    def folded_into(self, g):
+        return [t for t in self.folded if t.accumulate_into == g.name]
+
+    def gas_coefficients(self, g, refresh, g_lo, g_hi):
+        """(abs, emi) of a TableGas or a plain line Gas over [g_lo, g_hi), kept on the gas; a line gas's pair has the
+        tables folded into it (accumulate_into) added, and is rebuilt when one of them moved."""
+        if isinstance(g, TableGas):
+            return g.layer_coefficients(self, g_lo=g_lo, g_hi=g_hi)
+        fkey = tuple(t.cache_key(self, g_lo, g_hi) for t in self.folded_into(g))
+        if g.coeffs is None or refresh or getattr(g, "coeffs_shard", None) != (g_lo, g_hi) or getattr(g, "_folded_key", ()) != fkey:
+            g.set_self_pressure(self.press)
+            g.coeffs = g.lineset.abscoeff_layers(self.temps, self.press, tvib=g.tvib, g_lo=g_lo, g_hi=g_hi)
+            g.coeffs_shard, g._folded_key = (g_lo, g_hi), fkey
+            for t in self.folded_into(g):
+                t.table.layers(self.temps, self.grid, press=self.press, scale=t.scale_of(self), source=t.source, g_lo=g_lo,
+                               g_hi=g_hi, out=g.coeffs, accumulate=True)
+        return g.coeffs
 
     def coefficient_stack(self, refresh=False, g_lo=0, g_hi=None):
         """coefficients() as the stacked pair the limb_rays* calls work on (engine.gas_stack), re-stacked only when a
@@ -440,10 +512,14 @@ class LimbScene(object):
         each layer's kinetic temperature (pressure and vibrational temperatures fixed), recomputed for a gas only when
         the temperatures moved since its last call here.  A LevelGas (built with dT) gives both from its pair tables
         (layer_coefficients(derivative=True)); a plain Gas costs two coefficient ops (engine.coefficients_dT, scheme
-        "forward", on the coefficients just computed)."""
-        key = (self.temps.tobytes(), self.press.tobytes())
+        "forward", on the coefficients just computed); a TableGas gives its analytic derivatives with its pair, in one
+        launch, and the tables folded into a plain Gas add theirs to that gas's two pairs."""
+        n_grid = len(self.grid)
         for g in self.gases:
-            if isinstance(g, LevelGas):
+            key = (self.temps.tobytes(), self.press.tobytes()) + tuple(t.cache_key(self, 0, n_grid) for t in self.folded_into(g))
+            if isinstance(g, TableGas):
+                g.layer_coefficients(self, g_lo=0, g_hi=n_grid, derivative=True)
+            elif isinstance(g, LevelGas):
                 if not g.dT:
                     raise ValueError("a temperature retrieval needs LevelGas(%r, ..., dT=...): the tables at T + dT" % (g.name,))
                 g.layer_coefficients(self.temps, self.press, g_lo=0, g_hi=len(self.grid), derivative=True)   # (coefficients()' own shard key)
@@ -453,7 +529,10 @@ class LimbScene(object):
                 g.coeffs_shard = (0, len(self.grid))
                 _, g.dcoeffs = engine.coefficients_dT(g.lineset, self.temps, self.press, tvib=g.tvib, scheme="forward",
                                                       coeffs=g.coeffs)
-                g._dT_key = key
+                g._dT_key, g._folded_key = key, key[2:]
+                for t in self.folded_into(g):
+                    t.table.layers(self.temps, self.grid, press=self.press, scale=t.scale_of(self), source=t.source,
+                                   derivative=True, out=(g.coeffs, g.dcoeffs), accumulate=True)
         return [g.coeffs for g in self.gases], [g.dcoeffs for g in self.gases]
 
 
@@ -510,9 +589,11 @@ def single_rad_keys(gases, track_levels=None):
     track_levels = dict(track_levels or {})
     out = []
     for gi, g in enumerate(gases):
-        gasiso = (g.name, 'iso_%d' % g.lineset.iso)
+        # (a TableGas has no isotopologue and no levels: 'iso_0', and any tracked level of it is refused below)
+        table = isinstance(g, TableGas)
+        gasiso = (g.name, 'iso_%d' % (0 if table else g.lineset.iso))
         out.append((gasiso, gi, None))
-        n_lev = len(g.lineset.level_energies)
+        n_lev = 0 if table else len(g.lineset.level_energies)
         for lev in track_levels.pop(gasiso, ()):
             L = _level_index(lev)
             if not 0 <= L < n_lev:
@@ -559,16 +640,13 @@ def _simulate_budget(scene, pixels, track_levels, fov_closed_form, shard, refres
         if gi in tracked:
             lf = getattr(g, "level_factored", None)
             if lf is None or refresh or g.level_factored_shard != (g_lo, g_hi):
+                _refuse_table_gas(g, "the level-factored route of the radiance budget")
                 g.set_self_pressure(scene.press)
                 lf = g.level_factored = engine.LevelFactored(g.lineset, scene.temps, scene.press, g_lo=g_lo, g_hi=g_hi)
                 g.level_factored_shard = (g_lo, g_hi)
             coeffs.append(lf.steps(rows, tvib=g.tvib))
         else:
-            if g.coeffs is None or refresh or getattr(g, "coeffs_shard", None) != (g_lo, g_hi):
-                g.set_self_pressure(scene.press)
-                g.coeffs = g.lineset.abscoeff_layers(scene.temps, scene.press, tvib=g.tvib, g_lo=g_lo, g_hi=g_hi)
-                g.coeffs_shard = (g_lo, g_hi)
-            coeffs.append(g.coeffs)
+            coeffs.append(scene.gas_coefficients(g, refresh, g_lo, g_hi))   # (a TableGas is a ('gas', g) part like any other)
     stack = engine.gas_stack(coeffs)
     los, _ = scene.los(alts)
     n_los = len(alts)
@@ -1301,6 +1379,8 @@ def lut_coefficients(scene, temp_step=5.0, pres_step_log=1.0, refresh=False, **_
     Ts = np.arange(temp_step * np.floor(temps.min() / temp_step) - temp_step, temps.max() + 2 * temp_step, temp_step)
     PT = [[float(P), float(T)] for P in Ps for T in Ts]
     out = []
+    for g in scene.gases + getattr(scene, "folded", []):
+        _refuse_table_gas(g, "lut_coefficients (the look-up tables of G coefficients)")
     for g in scene.gases:
         ls = g.lineset
         n_lev = ls.level_energies.size

@@ -922,6 +922,84 @@ def read_line_database(nome_sp, mol=None, iso=None, up_lev=None, down_lev=None, 
 
 
 # ----------------------------------------------------------------------------
+# absorbers without lines: HITRAN cross-section (.xsc) and collision-induced-absorption (.cia) files -> the set lists
+# of engine.AbsorberTable.  The fixed-width layouts as HITRAN documents them, written from the documentation: the
+# readers have met only the synthetic files of tests/golden (no real file was at hand).  The reference has no reader.
+# ----------------------------------------------------------------------------
+TORR_TO_HPA = 1.333224
+_XSC_WIDTHS = (20, 10, 10, 7, 7, 6, 10, 5, 15, 4, 3, 3)   # molecule, nu_min, nu_max, points, T / K, P / Torr, max value,
+                                                          # resolution, common name, unused, broadener, reference
+_CIA_WIDTHS = (20, 10, 10, 7, 7, 10, 6, 27, 3)            # symbol, nu_min, nu_max, points, T, max value, resolution,
+                                                          # comment, reference
+
+
+def _header_cells(raw, widths):
+    edges = np.concatenate([[0], np.cumsum(widths)])
+    return [raw[a:b] for a, b in zip(edges[:-1], edges[1:])]
+
+
+def read_xsc(path):
+    """A HITRAN cross-section file: per set a 100-character header, then the values ten per line, ten characters each,
+    on the regular axis nu_min .. nu_max.  Returns [(T, v0, dv, values, P / hPa)] (Torr x 1.333224), or 4-tuples without
+    the label when a set's pressure field is empty or not positive."""
+    sets = []
+    with open(path, 'r') as infi:
+        rows = [r.rstrip('\n').rstrip('\r') for r in infi]
+    at = 0
+    while at < len(rows):
+        if not rows[at].strip():
+            at += 1
+            continue
+        cells = _header_cells(rows[at], _XSC_WIDTHS)
+        v_min, v_max, n, temp, p_torr = _num(cells[1], float), _num(cells[2], float), _num(cells[3], int), \
+            _num(cells[4], float), _num(cells[5], float)
+        if not (n >= 2 and v_max > v_min and temp > 0):
+            raise ValueError('%s, line %d: not a cross-section header' % (path, at + 1))
+        at += 1
+        vals = []
+        while len(vals) < n:
+            if at >= len(rows):
+                raise ValueError('%s: the file ends inside a set of %d values' % (path, n))
+            raw = rows[at]
+            vals.extend(float(raw[a:a + 10]) for a in range(0, len(raw), 10) if raw[a:a + 10].strip())
+            at += 1
+        if len(vals) != n:
+            raise ValueError('%s, line %d: %d values where the header announces %d' % (path, at, len(vals), n))
+        sets.append((temp, v_min, (v_max - v_min) / (n - 1), np.array(vals), p_torr * TORR_TO_HPA))
+    if any(not s[4] > 0 for s in sets):
+        sets = [s[:4] for s in sets]
+    return sets
+
+
+def read_cia(path):
+    """A HITRAN collision-induced-absorption file: per set a 100-character header, then one `nu value` pair per line.
+    Returns [(T, v0, dv, values)].  A set whose nu column is not regular to 1e-6 of its step is refused (ValueError):
+    AbsorberTable's axes are regular."""
+    sets = []
+    with open(path, 'r') as infi:
+        rows = [r.rstrip('\n').rstrip('\r') for r in infi]
+    at = 0
+    while at < len(rows):
+        if not rows[at].strip():
+            at += 1
+            continue
+        cells = _header_cells(rows[at], _CIA_WIDTHS)
+        n, temp = _num(cells[3], int), _num(cells[4], float)
+        if not (n >= 2 and temp > 0):
+            raise ValueError('%s, line %d: not a CIA header' % (path, at + 1))
+        if at + n > len(rows) - 1:
+            raise ValueError('%s: the file ends inside a set of %d pairs' % (path, n))
+        pairs = np.array([[float(c) for c in rows[at + 1 + i].split()[:2]] for i in range(n)])
+        at += 1 + n
+        nu, vals = pairs[:, 0], pairs[:, 1]
+        dv = (nu[-1] - nu[0]) / (n - 1)
+        if not dv > 0 or np.max(np.abs(nu - (nu[0] + np.arange(n) * dv))) > 1e-6 * dv:
+            raise ValueError('%s: the set at %g K has an irregular wavenumber column' % (path, temp))
+        sets.append((temp, float(nu[0]), float(dv), vals))
+    return sets
+
+
+# ----------------------------------------------------------------------------
 # line list -> structure of arrays for the engine
 # ----------------------------------------------------------------------------
 def lines_to_soa(lines, isomolec=None):
