@@ -389,7 +389,7 @@ int sr_radiance_rays_dev(const double *abs_c, const double *emi_c, int n_layers,
  * pinned).                                                                                             *
  * ------------------------------------------------------------------------ */
 typedef struct {
-  int n_rays, n_gas;        /* n_gas <= 4 */
+  int n_rays, n_gas;        /* n_gas <= sr_limb_max_gases(.) of the entry, see below the struct */
   const int32_t *seg_off;   /* HOST [n_rays+1]: ray r crosses segments seg_off[r] .. seg_off[r+1]-1 */
   const int32_t *seg_layer; /* HOST [n_seg]: row of abs_c / emi_c (the LOS step's (P, T)) a segment applies */
   const int32_t *pt_off;    /* HOST [n_seg+1]: LOS sample points of segment s: pt_off[s] .. pt_off[s+1]-1 (>= 2) */
@@ -1013,12 +1013,29 @@ int sr_last_limb_route(void);
  * sr_last_state_route: the plan of the calling thread's most recent such call, 1 dense, 2 per ray, 0 none yet;
  * sr_last_state_walks: its (ray, block) pairs, the number of times a ray was walked.
  * sr_state_ray_plan: the per-ray plan itself on the host, for tests and tools -- no device is touched.  The arguments as
- * the state calls name them (par_lgas NULL: one level gas; n_hid: hidden pointing slots, 0 .. 4).  sizes4: np, the
+ * the state calls name them (par_lgas NULL: one level gas; n_hid: hidden pointing slots, 0 .. 4, or 0 .. 8 for a
+ * batch of more than four gases).  sizes4: np, the
  * largest block count of a ray (gridDim.z), the number of ray blocks n_rb, the number of entries n_ent.  The arrays may
  * each be NULL (a first call for the sizes): ray_blk_off [n_rays + 1], blk [n_rb][2], col_row [n_rb][np],
  * ent_off [n_rb][n_layers + 1], slot_par [n_rb][np], ent_slot / ent_level / ent_c [n_ent].
  * Checked against the extended-precision recursion and the dense plan (tests/test_gpu_state_rayblocks.py). */
 int sr_set_state_ray_blocks(int on);
+/* The gases a ray batch may carry, sr_los_desc.n_gas: sr_limb_max_gases(0) = 8 for the entries of the path-order radiance
+ * kernels and of the state kernel, sr_limb_max_gases(1) = 4 for the entries of every kernel that keeps four gas slots in
+ * its packed records (folded, adjoint, forward-sensitivity, parts, retrieval loop).
+ *   8: sr_los_create, sr_los_columns, sr_los_columns_dz, sr_los_set_vmr, sr_limb_rays_dev, sr_limb_rays_los_dev,
+ *      sr_state_ray_plan, and every state entry -- sr_limb_rays_jac_level_dev, sr_limb_rays_jac_state_dev,
+ *      sr_limb_rays_jac_state_rows_dev, sr_limb_rays_jac_state_gases_dev, sr_limb_rays_state_bands_dev,
+ *      sr_limb_rays_state_bands_gases_dev, sr_limb_rays_state_bands_instr_dev, sr_limb_rays_state_bands_instr_gases_dev and
+ *      the pointing forms sr_limb_rays_jac_state_path_dev, sr_limb_rays_state_bands_path_dev.  At most four of the eight
+ *      gases are level-factored (n_lgas <= 4), any of the eight indices.
+ *   4: sr_los_create_par with parameters, sr_limb_rays_jac_los_dev, sr_retrieval_forward_dev, sr_retrieval_step_dev,
+ *      sr_retrieval_loop_dev, sr_limb_rays_jac_dev, sr_limb_rays_jac_layer_dev, sr_limb_rays_jacobians_dev,
+ *      sr_limb_rays_parts_dev.
+ * A batch beyond its entry's limit is refused with SR_ERR_LIMIT before the first copy or launch, outputs untouched.  With
+ * more than four gases the radiance calls take the path-order kernels (sr_last_limb_route() reads 1: no folded records
+ * are made), and the state plan packs a column slot's gas into three bits, eight slots per block. */
+int sr_limb_max_gases(int folded);
 int sr_last_state_route(void);
 int64_t sr_last_state_walks(void);
 int sr_state_ray_plan(const sr_los_desc *los, int n_layers, int n_col, const int32_t *par_gas, const double *par_w, int n_lev,

@@ -216,6 +216,7 @@ SYMBOLS = {
     "sr_set_jac_layer_mode": (C.c_int, [C.c_int]),
     "sr_last_limb_route": (C.c_int, []),
     "sr_set_state_ray_blocks": (C.c_int, [C.c_int]),
+    "sr_limb_max_gases": (C.c_int, [C.c_int]),
     "sr_last_state_route": (C.c_int, []),
     "sr_last_state_walks": (C.c_int64, []),
     "sr_state_ray_plan": (C.c_int, [C.POINTER(LosDesc), C.c_int, C.c_int, ip, dp, C.c_int, ip, ip, dp, C.c_int, dp, C.c_int,

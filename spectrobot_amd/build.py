@@ -6,12 +6,12 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libspectrobot_hip.so")
-SOURCES = ["sr_api.hip", "sr_kernels.hip"]
+SOURCES = ["sr_api.hip", "sr_kernels.hip", "sr_limb_many.hip"]
 DEPS = SOURCES + ["sr_device.hpp", "sr_kernels.hpp", "sr_constants.hpp", "sr_limb_plan.hpp", "sr_limb_common.hpp",
-                  "sr_limb_state.inc", "sr_lowres_weights_tab.inc", "sr_absorber_table.inc",
+                  "sr_limb_state.inc", "sr_limb_state_launch.inc", "sr_limb_forward.inc", "sr_lowres_weights_tab.inc", "sr_absorber_table.inc",
                   "tips2003_tables.inc", "../../include/spectrobot_hip.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-fgpu-rdc" if False else "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 
@@ -35,15 +35,29 @@ def build(force=False, verbose=False, extra=(), out=None):
 
 
 def _compile(OUT, verbose, extra):
+    """The translation units side by side (the build takes as long as the slowest of them, sr_kernels.hip), then one
+    link; objects in a directory of their own beside the library, removed afterwards."""
+    import shutil
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     tmp = "%s.tmp.%d" % (OUT, os.getpid())  # other processes never see a half-written library
-    cmd = [HIPCC] + FLAGS + list(extra) + [os.path.join(CSRC, s) for s in SOURCES] + ["-o", tmp]
+    objdir = tmp + ".obj"
+    os.makedirs(objdir, exist_ok=True)
+    objs = [os.path.join(objdir, os.path.splitext(s)[0] + ".o") for s in SOURCES]
+    cmds = [[HIPCC] + FLAGS + list(extra) + ["-c", os.path.join(CSRC, s), "-o", o] for s, o in zip(SOURCES, objs)]
+    link = [HIPCC] + FLAGS + list(extra) + ["-shared"] + objs + ["-o", tmp]   # (a variant's flags reach the link too)
     if verbose:
-        print(" ".join(cmd).replace(tmp, OUT))
+        for c in cmds + [link]:
+            print(" ".join(c).replace(tmp, OUT))
     try:
-        subprocess.check_call(cmd)
+        procs = [subprocess.Popen(c) for c in cmds]
+        codes = [p.wait() for p in procs]
+        for c, rc in zip(cmds, codes):
+            if rc:
+                raise subprocess.CalledProcessError(rc, c)
+        subprocess.check_call(link)
         os.replace(tmp, OUT)
     finally:
+        shutil.rmtree(objdir, ignore_errors=True)
         if os.path.exists(tmp):
             os.remove(tmp)
     return OUT

@@ -631,6 +631,8 @@ int sr_set_band_fusion(int on) {
   return SR_OK;
 }
 
+int sr_limb_max_gases(int folded) { return folded ? kFoldGasMax : kLimbGasMax; }
+
 int sr_set_state_ray_blocks(int on) {
   g_state_ray_blocks.store(on ? 1 : 0);
   return SR_OK;
@@ -642,11 +644,13 @@ int sr_state_ray_plan(const sr_los_desc *los, int n_layers, int n_col, const int
                       int n_hid, int32_t *sizes4, int32_t *ray_blk_off, int32_t *blk, int32_t *col_row, int32_t *ent_off,
                       int32_t *slot_par, int32_t *ent_slot, int32_t *ent_level, double *ent_c) {
   LosShape shape;
-  if (!sizes4 || n_layers <= 0 || n_lev < 0 || n_row < 0 || n_hid < 0 || n_hid > 4) return SR_ERR_ARG;
+  if (!sizes4 || n_layers <= 0 || n_lev < 0 || n_row < 0 || n_hid < 0) return SR_ERR_ARG;
+  if (n_hid > (los && los->n_gas > kFoldGasMax ? kLimbGasMax : kFoldGasMax)) return SR_ERR_ARG; // (a hidden slot per gas)
   if ((n_lev > 0 && (!par_level || !par_c)) || (n_row > 0 && !par_t)) return SR_ERR_ARG;
-  const int rc = check_los_par(los, n_layers, n_col, par_gas, par_w, &shape);
+  const int rc = check_los_par(los, n_layers, n_col, par_gas, par_w, &shape, kLimbGasMax);
   if (rc) return rc;
-  const RayJacPlan R = ray_jac_plan(los, n_col, par_gas, par_w, n_lev, par_level, par_c, n_layers, n_row, par_t, par_lgas, n_hid);
+  const RayJacPlan R = ray_jac_plan(los, n_col, par_gas, par_w, n_lev, par_level, par_c, n_layers, n_row, par_t, par_lgas, n_hid,
+                                    state_gas_bits(los->n_gas));
   sizes4[0] = R.np, sizes4[1] = R.n_blocks, sizes4[2] = R.ray_blk_off.back(), sizes4[3] = (int32_t)R.ent.size();
   if (ray_blk_off) std::copy(R.ray_blk_off.begin(), R.ray_blk_off.end(), ray_blk_off);
   if (blk) std::copy(R.blk.begin(), R.blk.end(), blk);
@@ -2409,7 +2413,8 @@ LimbOpts limb_opts(const sr_los_desc *los, int n_seg) {
 namespace {
 
 // The folded kernels' plan on the device: per ray and visited shell (outermost first) the layer and the ray's two
-// segments there, + room for the packed records.  n_rec = 0: some ray is not V-shaped (nothing staged).
+// segments there, + room for the packed records.  n_rec = 0: some ray is not V-shaped, or the batch has more than
+// kFoldGasMax gases (nothing staged).
 struct FoldStage {
   const int *plan = nullptr;
   FoldDense *rec = nullptr;
@@ -2417,6 +2422,7 @@ struct FoldStage {
   Stager *slot = nullptr;
 };
 int stage_fold(const sr_los_desc *los, int n_layers, hipStream_t st, FoldStage *out, Stager *own = nullptr) {
+  if (los->n_gas > kFoldGasMax) return SR_OK; // (the folded records hold four columns: such batches keep the path-order kernels)
   std::vector<int> far, near;
   int l_min = 0, l_max = -1;
   if (!fold_sides(los, n_layers, nullptr, &far, &near, &l_min, &l_max)) return SR_OK;
@@ -2463,7 +2469,7 @@ extern "C" {
 int sr_los_columns(const sr_los_desc *los, double *col_out) {
   if (!col_out) return SR_ERR_ARG;
   LosShape shape;
-  int rc = check_los(los, 0, &shape);
+  int rc = check_los(los, 0, &shape, kLimbGasMax);
   if (rc) return rc;
   LosDev D;
   rc = stage_los(los, shape, 0, nullptr, nullptr, nullptr, &D);
@@ -2483,7 +2489,7 @@ int sr_los_columns(const sr_los_desc *los, double *col_out) {
 int sr_los_columns_dz(const sr_los_desc *los, const sr_los_path *path, double *dcol_out) {
   if (!dcol_out || !path || !path->alt || !path->dx_dz || !path->dalt_dz) return SR_ERR_ARG;
   LosShape shape;
-  int rc = check_los(los, 0, &shape);
+  int rc = check_los(los, 0, &shape, kLimbGasMax);
   if (rc) return rc;
   if (los->los_order != 0) {
     g_err = "sr_los_columns_dz: the pointing derivative needs the batch in photon order (observer order re-lists the sample points)";
@@ -2791,7 +2797,9 @@ int sr_los_create_par(const sr_los_desc *los, int n_layers, int n_par, const int
   if (!out || n_layers <= 0 || n_par < 0) return SR_ERR_ARG;
   *out = nullptr;
   LosShape shape;
-  int rc = check_los_par(los, n_layers, n_par, par_gas, par_w, &shape);
+  // (a batch made with parameters serves the entries of the folded and forward-sensitivity kernels only -- sr_limb_rays_jac_los_dev,
+  // sr_retrieval_forward / _step / _loop_dev: refused here, they never see a handle of more than kFoldGasMax gases)
+  int rc = check_los_par(los, n_layers, n_par, par_gas, par_w, &shape, n_par > 0 ? kFoldGasMax : kLimbGasMax);
   if (rc) return rc;
   sr_los *h = new sr_los();
   rc = stage_los(los, shape, n_par, par_gas, par_w, nullptr, &h->D, &h->s_los);
@@ -3150,7 +3158,7 @@ int sr_limb_rays_dev(const double *abs_c, const double *emi_c, int n_layers, int
                      double *rad, void *stream) {
   LosShape shape;
   int rc = check_limb_call(abs_c, emi_c, n_layers, n_pts, rad != nullptr);
-  if (!rc) rc = check_los(los, n_layers, &shape);
+  if (!rc) rc = check_los(los, n_layers, &shape, kLimbGasMax);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   LosDev D;
@@ -3434,19 +3442,19 @@ static int limb_jac_state(const StateCall &c, const LosShape &shape, const void 
   const int n_layers = b.n_layers, n_col = c.col.n_col, n_lev = c.lev.n_lev, n_row = c.row.n_row, n_lgas = c.lev.n_lgas;
   const sr_level_gas *lgas = c.lev.lgas;
   const bool several = n_lgas > 1;
-  const int n_hid = c.path ? b.los->n_gas : 0;
+  const int n_hid = c.path ? b.los->n_gas : 0, gas_bits = state_gas_bits(b.los->n_gas);
   // the dense plan, or (sr_set_state_ray_blocks) every ray's own blocks, whose tables take the dense plan's places
   const bool per_ray = g_state_ray_blocks.load() != 0;
   LevelJacPlan P{};
   RayJacPlan R{};
   if (per_ray) {
     R = ray_jac_plan(b.los, n_col, c.col.par_gas, c.col.par_w, n_lev, c.lev.par_level, c.lev.par_c, n_layers, n_row, c.row.par_t,
-                     several ? c.lev.par_lgas : nullptr, n_hid);
+                     several ? c.lev.par_lgas : nullptr, n_hid, gas_bits);
     P.n_blocks = R.n_blocks;
     P.blk.swap(R.blk), P.ent_off.swap(R.ent_off), P.slot_par.swap(R.slot_par), P.ent.swap(R.ent);
   } else {
     P = level_jac_plan(n_col, c.col.par_gas, n_lev, c.lev.par_level, c.lev.par_c, n_layers, n_row, c.row.par_t,
-                       several ? c.lev.par_lgas : nullptr, n_hid);
+                       several ? c.lev.par_lgas : nullptr, n_hid, gas_bits);
   }
   static thread_local StagerRing ring;
   StagePack pk(ring.take());
@@ -3517,7 +3525,7 @@ static int check_state_call(const StateCall &c, LosShape *shape) {
   const bool row_ok = n_row == 0 || (c.row.dabs_c && c.row.demi_c && c.row.par_t);
   const bool counts_ok = n_col >= 0 && n_lev >= 0 && n_row >= 0 && (int64_t)n_col + n_lev + n_row >= (may_be_empty ? 0 : 1);
   int rc = check_limb_call(b.abs_c, b.emi_c, b.n_layers, b.n_pts, out_ok && counts_ok && list_ok && lev_ok && row_ok);
-  if (!rc) rc = check_los_par(b.los, b.n_layers, n_col, c.col.par_gas, c.col.par_w, shape);
+  if (!rc) rc = check_los_par(b.los, b.n_layers, n_col, c.col.par_gas, c.col.par_w, shape, kLimbGasMax);
   if (rc) return rc;
   if (n_lgas > b.los->n_gas) return SR_ERR_ARG;
   for (int k = 0; k < n_lgas; ++k) {

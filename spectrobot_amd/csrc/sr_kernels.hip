@@ -3022,17 +3022,19 @@ int launch_jac_rows_sum(double *jac, int n_rays, int n_state, int n_hid, int n_p
   return (int)hipGetLastError();
 }
 
-__host__ inline unsigned limb_grid(int n_pb, int n_rays) { return (unsigned)(((n_pb + 7) / 8) * 8) * (unsigned)n_rays; }
-
 // The limb launchers' dispatch on the kernels' compile-time parameters.  by_ngas: f(integral_constant<int, NG>) for a
-// batch of n_gas gases, NG = 1..4 (any other count takes the general NG = 4).
+// batch of n_gas gases, NG = 1..kFoldGasMax.  A larger batch has no instance here: launch_limb and
+// launch_limb_jac_state hand such a batch to sr_limb_many.hip before they come here, and the entries of every other
+// kernel refuse it (check_los with kFoldGasMax).
+// false: no instance for that count -- the launcher answers hipErrorInvalidValue, never a skipped launch.
 template <class F>
-inline void by_ngas(int n_gas, F &&f) {
+inline bool by_ngas(int n_gas, F &&f) {
   switch (n_gas) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 3: f(std::integral_constant<int, 3>{}); break;
-    default: f(std::integral_constant<int, 4>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    case 3: f(std::integral_constant<int, 3>{}); return true;
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    default: return false;
   }
 }
 // by_level_np: f(integral_constant<int, NP>) for the accumulators per thread level_jac_np() / limb_parts_np() chose.
@@ -3056,108 +3058,7 @@ inline void by_jac_kinds(bool layer, bool par, F &&f) {
   else f(std::false_type{}, std::true_type{});
 }
 
-template <int NG>
-__global__ __launch_bounds__(256) void sr_limb_kernel(const double *__restrict__ abs_c, const double *__restrict__ emi_c,
-                                                      int n_pts, int n_layers, const int *__restrict__ seg_off,
-                                                      const int *__restrict__ seg_layer, const double *__restrict__ col,
-                                                      LimbOpts o, int n_rays, double *__restrict__ rad) {
-  int pb, ray;
-  if (!limb_block((n_pts + 255) / 256, n_rays, pb, ray)) return;
-  const int j = pb * 256 + threadIdx.x;
-  if (j >= n_pts) return;
-  double I = limb_initial(o, rad, (size_t)ray * n_pts + j, j);
-  const int s0 = seg_off[ray], s1 = seg_off[ray + 1];
-  constexpr int kB = NG == 1 ? 8 : (NG == 2 ? 4 : 2); // segments whose loads are issued together (see sr_radiance_kernel)
-  const size_t gstride = (size_t)n_layers * n_pts;
-  for (int sb = s0; sb < s1; sb += kB) {
-    double a[kB][NG], e[kB][NG], u[kB][NG];
-#pragma unroll
-    for (int t = 0; t < kB; ++t) {
-      const int s = min(sb + t, s1 - 1);
-      const size_t ofs = (size_t)seg_layer[s] * n_pts + j;
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        a[t][g] = abs_c[g * gstride + ofs];
-        e[t][g] = emi_c[g * gstride + ofs];
-        u[t][g] = col[(size_t)g * o.n_seg_total + s];
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < kB; ++t) {
-      if (sb + t < s1) {
-        double tau = a[t][0] * u[t][0], E = e[t][0] * u[t][0];
-#pragma unroll
-        for (int g = 1; g < NG; ++g) {
-          tau = tau + a[t][g] * u[t][g];
-          E = E + e[t][g] * u[t][g];
-        }
-        const Atten A = attenuation(tau);
-        I = I * A.t + (o.solo_absorption ? 0.0 : E * A.f);
-      }
-    }
-  }
-  rad[(size_t)ray * n_pts + j] = I;
-}
-
-// The same recursion for SMALL launches (one ray on a 1/8 spectral shard: 49 blocks on 256 CUs), where the run time
-// is the latency of one thread's chain of 160 dependent segments: the segments of a ray are cut into kLimbParts
-// consecutive stretches, one wave per stretch and 64 points; a stretch is the affine map I -> I T + S (T = product of
-// its transmissions, S its own emission attenuated by what follows inside the stretch), and maps compose in order.
-constexpr int kLimbParts = 4;
-template <int NG>
-__global__ __launch_bounds__(64 * kLimbParts) void sr_limb_split_kernel(
-    const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
-    const int *__restrict__ seg_off, const int *__restrict__ seg_layer, const double *__restrict__ col, LimbOpts o,
-    int n_rays, double *__restrict__ rad) {
-  __shared__ double s_T[kLimbParts][64], s_S[kLimbParts][64];
-  const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
-  int pb, ray;
-  if (!limb_block((n_pts + 63) / 64, n_rays, pb, ray)) return; // block-uniform: no thread reaches the barrier
-  const int j = pb * 64 + lane;
-  const int jj = min(j, n_pts - 1);
-  const int r0 = seg_off[ray], r1 = seg_off[ray + 1], n = r1 - r0;
-  const int s0 = r0 + (int)(((long)n * part) / kLimbParts), s1 = r0 + (int)(((long)n * (part + 1)) / kLimbParts);
-  constexpr int kB = NG == 1 ? 8 : (NG == 2 ? 4 : 2);
-  const size_t gstride = (size_t)n_layers * n_pts;
-  double T = 1.0, S = 0.0;
-  for (int sb = s0; sb < s1; sb += kB) {
-    double a[kB][NG], e[kB][NG], u[kB][NG];
-#pragma unroll
-    for (int t = 0; t < kB; ++t) {
-      const int s = min(sb + t, s1 - 1);
-      const size_t ofs = (size_t)seg_layer[s] * n_pts + jj;
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        a[t][g] = abs_c[g * gstride + ofs];
-        e[t][g] = emi_c[g * gstride + ofs];
-        u[t][g] = col[(size_t)g * o.n_seg_total + s];
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < kB; ++t) {
-      if (sb + t < s1) {
-        double tau = a[t][0] * u[t][0], E = e[t][0] * u[t][0];
-#pragma unroll
-        for (int g = 1; g < NG; ++g) {
-          tau = tau + a[t][g] * u[t][g];
-          E = E + e[t][g] * u[t][g];
-        }
-        const Atten A = attenuation(tau);
-        T = T * A.t;
-        S = S * A.t + (o.solo_absorption ? 0.0 : E * A.f);
-      }
-    }
-  }
-  s_T[part][lane] = T;
-  s_S[part][lane] = S;
-  __syncthreads();
-  if (part == 0 && j < n_pts) {
-    double I = limb_initial(o, rad, (size_t)ray * n_pts + j, j);
-#pragma unroll
-    for (int p = 0; p < kLimbParts; ++p) I = I * s_T[p][lane] + s_S[p][lane];
-    rad[(size_t)ray * n_pts + j] = I;
-  }
-}
+#include "sr_limb_forward.inc"
 
 // Derivatives w.r.t. NP parameters per thread; parameter p belongs to gas par_gas[p] and moves its columns
 // linearly, d u_g[s] / d x_p = dcol[p][s] (profile parameters of RetParam / LinearProfile, smm:319-375):
@@ -3268,6 +3169,11 @@ __global__ __launch_bounds__(256) void sr_limb_jac_layer_kernel(
 // (the library pins the two scalars to registers through an empty asm; a host build defines the macro to nothing)
 #define SR_PIN_SCALARS(a, b) asm volatile("" : "+s"(a), "+s"(b))
 #include "sr_limb_state.inc"
+// the instances of five to eight gases (sr_limb_many.hip): the same launches from the same prelude
+int launch_limb_many(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
+                     const int *seg_layer, const double *col, const LimbOpts &o, double *rad, hipStream_t st);
+int launch_limb_jac_state_many(const StateLaunch &L, const FoldBands &bd, int n_row_par, hipStream_t st);
+#include "sr_limb_state_launch.inc"
 
 // The radiance budget of a ray batch (sr_limb_rays_parts_dev): the recursion is linear in the emission, so the share
 // e_k[r] of one gas's emission -- a whole gas, or c[k][r] E_L[row[r]] of one level of the level-factored gas (plane 1 of
@@ -3720,16 +3626,17 @@ int launch_limb_adjoint_sync(const double *abs_c, const double *emi_c, const dou
                              int n_layers, int n_jrows, int n_rays, const SegProg *prog, const int *zero_off,
                              const int *zero_row, int n_par, const LimbOpts &o, const int *sched, int n_visits, double *rad,
                              double *jac_layer, double *jac_par, hipStream_t st) {
+  bool found = false; // (an instance for o.n_gas exists and was launched)
   if (n_pts <= 0 || n_rays <= 0 || n_visits <= 0) return 0;
   const dim3 grid((n_pts + 255) / 256, (n_rays + kAdjSyncRays - 1) / kAdjSyncRays);
-  by_ngas(o.n_gas, [&](auto ng) {
+  found = by_ngas(o.n_gas, [&](auto ng) {
     by_jac_kinds(jac_layer, jac_par, [&](auto lay, auto par) {
       hipLaunchKernelGGL((sr_limb_adjoint_sync_kernel<decltype(ng)::value, decltype(lay)::value, decltype(par)::value, kAdjSyncRays>),
                          grid, dim3(256), 0, st, abs_c, emi_c, dabs, demi, n_pts, n_layers, n_jrows, prog, zero_off, zero_row, n_par,
                          o, sched, n_visits, n_rays, rad, jac_layer, jac_par);
     });
   });
-  return (int)hipGetLastError();
+  return found ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------
@@ -4397,16 +4304,17 @@ __global__ __launch_bounds__(256) void sr_limb_fold_fwd_kernel(const double *__r
 int launch_fold_fwd(const int *plan, const double *col, int n_seg, int n_rec, FoldDense *rec, const double *abs_c,
                     const double *emi_c, int n_pts, int n_layers, int n_rays, int n_visits, const LimbOpts &o, double *rad,
                     hipStream_t st, bool pack) {
+  bool found = false; // (an instance for o.n_gas exists and was launched)
   if (n_rec <= 0 || n_rays <= 0) return 0;
   if (pack)
     hipLaunchKernelGGL(sr_fold_dense_pack_kernel, dim3((n_rec + 63) / 64), dim3(64), 0, st, plan, col, o.n_gas, 0, n_seg, n_rec, rec);
   if (n_pts <= 0) return (int)hipGetLastError(); // (packing only)
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays));
-  by_ngas(o.n_gas, [&](auto ng) {
+  found = by_ngas(o.n_gas, [&](auto ng) {
     hipLaunchKernelGGL(sr_limb_fold_fwd_kernel<decltype(ng)::value>, grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, rec, o,
                        n_visits, n_rays, rad);
   });
-  return (int)hipGetLastError();
+  return found ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 size_t fold_dense_bytes(int n_rec) { return sizeof(FoldDense) * (size_t)n_rec; }
@@ -4414,6 +4322,7 @@ size_t fold_dense_bytes(int n_rec) { return sizeof(FoldDense) * (size_t)n_rec; }
 int launch_fold_dense(const int *plan, const double *col, const int *par_gas_host, int n_par, int n_seg, int n_rec, FoldDense *rec,
                       const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, int n_visits,
                       const LimbOpts &o, double *rad, double *jac_par, hipStream_t st, const void *lowres_scratch, int n_bands) {
+  bool found = false; // (an instance for o.n_gas exists and was launched)
   if (n_rec <= 0 || n_pts <= 0 || n_rays <= 0 || n_par <= 0 || n_par > kFoldDensePar) return 0;
   hipLaunchKernelGGL(sr_fold_dense_pack_kernel, dim3((n_rec + 63) / 64), dim3(64), 0, st, plan, col, o.n_gas, n_par, n_seg, n_rec, rec);
   ParGas pg;
@@ -4424,7 +4333,7 @@ int launch_fold_dense(const int *plan, const double *col, const int *par_gas_hos
     const LowresScratch L = lowres_layout(const_cast<void *>(lowres_scratch), n_pts, n_bands);
     bd = FoldBands{L.Wt, L.range, L.part, n_bands};
   }
-  by_ngas(o.n_gas, [&](auto ng) {
+  found = by_ngas(o.n_gas, [&](auto ng) {
     auto launch = [&](auto bands) {
       hipLaunchKernelGGL((sr_limb_fold_sens_lds_kernel<decltype(ng)::value, decltype(bands)::value>), grid, dim3(256), 0, st, abs_c,
                          emi_c, n_pts, n_layers, rec, n_par, pg, o, n_visits, n_rays, rad, jac_par, bd);
@@ -4432,7 +4341,7 @@ int launch_fold_dense(const int *plan, const double *col, const int *par_gas_hos
     if (lowres_scratch) launch(std::true_type{});
     else launch(std::false_type{});
   });
-  return (int)hipGetLastError();
+  return found ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 size_t fold_rec_bytes(int n_rec) { return sizeof(FoldRec) * (size_t)n_rec; }
@@ -4447,9 +4356,10 @@ int launch_limb_adjoint_fold(const double *abs_c, const double *emi_c, const dou
                              int n_layers, int n_jrows, int two_rows, int n_rays, const FoldRec *rec, const int *zero_off,
                              const int *zero_row, int n_par, const LimbOpts &o, int n_visits, double *rad, double *jac_layer,
                              double *jac_par, hipStream_t st) {
+  bool found = false; // (an instance for o.n_gas exists and was launched)
   if (n_pts <= 0 || n_rays <= 0 || n_visits <= 0) return 0;
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays));
-  by_ngas(o.n_gas, [&](auto ng) {
+  found = by_ngas(o.n_gas, [&](auto ng) {
     by_jac_kinds(jac_layer, jac_par, [&](auto lay, auto par) {
       auto launch = [&](auto two) { // two_rows: a coefficient row per segment
         hipLaunchKernelGGL((sr_limb_adjoint_fold_kernel<decltype(ng)::value, decltype(lay)::value, decltype(par)::value, 1, decltype(two)::value>),
@@ -4460,7 +4370,7 @@ int launch_limb_adjoint_fold(const double *abs_c, const double *emi_c, const dou
       else launch(std::false_type{});
     });
   });
-  return (int)hipGetLastError();
+  return found ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 size_t adj_prog_bytes(int n_seg) { return sizeof(SegProg) * (size_t)n_seg; }
@@ -4475,47 +4385,51 @@ int launch_limb_adjoint(const double *abs_c, const double *emi_c, const double *
                         int n_layers, int n_jrows, int n_rays, const int *seg_off, const SegProg *prog, const int *zero_off,
                         const int *zero_row, int n_par, const LimbOpts &o, double *rad, double *jac_layer,
                         double *jac_par, hipStream_t st) {
+  bool found = false; // (an instance for o.n_gas exists and was launched)
   if (n_pts <= 0 || n_rays <= 0) return 0;
   const dim3 grid((n_pts + 255) / 256, n_rays);
-  by_ngas(o.n_gas, [&](auto ng) {
+  found = by_ngas(o.n_gas, [&](auto ng) {
     by_jac_kinds(jac_layer, jac_par, [&](auto lay, auto par) {
       hipLaunchKernelGGL((sr_limb_adjoint_kernel<decltype(ng)::value, decltype(lay)::value, decltype(par)::value>), grid, dim3(256), 0,
                          st, abs_c, emi_c, dabs, demi, n_pts, n_layers, n_jrows, seg_off, prog, zero_off, zero_row, n_par, o, rad,
                          jac_layer, jac_par);
     });
   });
-  return (int)hipGetLastError();
+  return found ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 int launch_limb(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
                 const int *seg_layer, const double *col, const LimbOpts &o, double *rad, hipStream_t st) {
+  bool found = false; // (an instance for o.n_gas exists and was launched)
   if (n_pts <= 0 || n_rays <= 0) return 0;
+  if (o.n_gas > kFoldGasMax) return launch_limb_many(abs_c, emi_c, n_pts, n_layers, n_rays, seg_off, seg_layer, col, o, rad, st);
   // fewer than two waves per SIMD: the latency-bound variant (a function of the launch shape only)
   if (limb_launch_is_small(n_pts, n_rays)) {
     const dim3 gs(limb_grid((n_pts + 63) / 64, n_rays));
-    by_ngas(o.n_gas, [&](auto ng) {
+    found = by_ngas(o.n_gas, [&](auto ng) {
       hipLaunchKernelGGL(sr_limb_split_kernel<decltype(ng)::value>, gs, dim3(64 * kLimbParts), 0, st, abs_c, emi_c, n_pts, n_layers,
                          seg_off, seg_layer, col, o, n_rays, rad);
     });
-    return (int)hipGetLastError();
+    return found ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
   }
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays));
-  by_ngas(o.n_gas, [&](auto ng) {
+  found = by_ngas(o.n_gas, [&](auto ng) {
     hipLaunchKernelGGL(sr_limb_kernel<decltype(ng)::value>, grid, dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer,
                        col, o, n_rays, rad);
   });
-  return (int)hipGetLastError();
+  return found ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 int launch_limb_jac(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
                     const int *seg_layer, const double *col, const double *dcol, const int *par_gas, int n_par,
                     const LimbOpts &o, double *rad, double *jac, hipStream_t st) {
+  bool found = false; // (an instance for o.n_gas exists and was launched)
   if (n_pts <= 0 || n_rays <= 0 || n_par <= 0) return 0;
   // Every block of NP parameters repeats the recursion (exp, expm1, the coefficient loads): with many parameters
   // (configs[3]: one per layer) 16 per thread instead of 4 cut the kernel's instructions 3.4x (160 segments x
   // (60 + NP) per block of NP).
   auto launch = [&](auto np) {
-    by_ngas(o.n_gas, [&](auto ng) {
+    found = by_ngas(o.n_gas, [&](auto ng) {
       constexpr int NP = decltype(np)::value;
       hipLaunchKernelGGL((sr_limb_jac_kernel<decltype(ng)::value, NP>), dim3((n_pts + 255) / 256, n_rays, (n_par + NP - 1) / NP),
                          dim3(256), 0, st, abs_c, emi_c, n_pts, n_layers, seg_off, seg_layer, col, dcol, par_gas, n_par, o, rad, jac);
@@ -4523,15 +4437,16 @@ int launch_limb_jac(const double *abs_c, const double *emi_c, int n_pts, int n_l
   };
   if (n_par > 8) launch(std::integral_constant<int, 16>{});
   else launch(std::integral_constant<int, 4>{});
-  return (int)hipGetLastError();
+  return found ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 int launch_limb_jac_layer(const double *abs_c, const double *emi_c, const double *dabs, const double *demi, int n_pts,
                           int n_layers, int n_rays, const int *seg_off, const int *seg_layer, const double *col,
                           const LimbOpts &o, double *jac, hipStream_t st) {
+  bool found = false; // (an instance for o.n_gas exists and was launched)
   if (n_pts <= 0 || n_rays <= 0 || n_layers <= 0) return 0;
   auto launch = [&](auto np) { // (the one-pass formulation is sr_limb_adjoint_kernel, launch_limb_adjoint)
-    by_ngas(o.n_gas, [&](auto ng) {
+    found = by_ngas(o.n_gas, [&](auto ng) {
       constexpr int NP = decltype(np)::value;
       hipLaunchKernelGGL((sr_limb_jac_layer_kernel<decltype(ng)::value, NP>), dim3((n_pts + 255) / 256, n_rays, (n_layers + NP - 1) / NP),
                          dim3(256), 0, st, abs_c, emi_c, dabs, demi, n_pts, n_layers, seg_off, seg_layer, col, o, jac);
@@ -4539,92 +4454,53 @@ int launch_limb_jac_layer(const double *abs_c, const double *emi_c, const double
   };
   if (n_layers > 8) launch(std::integral_constant<int, 16>{});
   else launch(std::integral_constant<int, 4>{});
-  return (int)hipGetLastError();
+  return found ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 int launch_limb_jac_state(const StateLaunch &L, hipStream_t st) {
-  const bool bands = L.lowres_scratch != nullptr, rows = L.dabs && L.demi;
+  const bool bands = L.lowres_scratch != nullptr;
   if (L.instr && !bands) return 0;
   if (L.n_pts <= 0 || L.n_rays <= 0 || L.n_par < (L.instr ? 0 : 1) || L.n_blocks <= 0) return 0;
   if (bands && L.n_bands <= 0) return 0;
-  if (L.lgas && (L.o.n_gas < 2 || L.o.n_gas > 4)) return 0;
-  const dim3 grid(limb_grid((L.n_pts + 255) / 256, L.n_rays), 1, L.n_blocks);
+  if ((L.lgas && L.o.n_gas < 2) || L.o.n_gas > kLimbGasMax) return (int)hipErrorInvalidValue; // (no such instance)
   FoldBands bd{};
   if (bands) {
     const LowresScratch S = lowres_layout(const_cast<void *>(L.lowres_scratch), L.n_pts, L.n_bands, L.instr);
     bd = FoldBands{S.Wt, S.range, S.part, L.n_bands};
   }
   const int n_row_par = L.n_par + (L.instr ? kLowresTables - 1 : 0); // the parameter rows of a ray in `part`
-  // (gas, tab and n_tab_rows belong to the one-gas instances, rad to those that write spectra)
-  const int gas = L.lgas ? -1 : L.gas, n_tab_rows = L.lgas ? 0 : L.n_tab_rows;
-  const double *const tab = L.lgas ? nullptr : L.tab;
-  double *const rad = bands ? nullptr : L.rad;
   // blocks per ray: a ray's blocks write the rows of the parameters that touch it, the others read as exact zeros --
   // cleared here, on the stream, ahead of the launch (the radiance rows of `part`, rows 0 .. n_rays - 1, are block 0's)
   const bool per_ray = L.ray_blk_off != nullptr;
-  if (per_ray && (L.np != kLevelJacNPSmall && L.np != kLevelJacNPLarge)) return 0;
+  if (per_ray && (L.np != kLevelJacNPSmall && L.np != kLevelJacNPLarge)) return (int)hipErrorInvalidValue;
   if (per_ray && n_row_par > 0) {
     const size_t row = bands ? 4 * (size_t)((L.n_pts + 255) / 256) * ((L.n_bands + 15) / 16) * 16 : (size_t)L.n_pts;
     double *const rows = bands ? bd.part + (size_t)L.n_rays * row : L.jac;
     const hipError_t e = hipMemsetAsync(rows, 0, sizeof(double) * (size_t)L.n_rays * n_row_par * row, st);
     if (e != hipSuccess) return (int)e;
   }
-  const StateRayBlocks rbk{L.ray_blk_off, L.col_row};
-  by_flag(L.blk != nullptr, [&](auto cols) { // no blk: the instances without column slots
-    by_level_np(per_ray ? L.np : level_jac_np(L.n_par), [&](auto np) {
-      by_ngas(L.o.n_gas, [&](auto ng) {
-        by_flag(rows, [&](auto rw) {
-          by_flag(bands, [&](auto bn) {
-            by_flag(L.instr, [&](auto ins) {
-              by_flag(L.lgas != nullptr, [&](auto several) {
-               by_flag(per_ray, [&](auto rayblk) {
-                constexpr int NG = decltype(ng)::value, NP = decltype(np)::value;
-                constexpr bool COLS = decltype(cols)::value, ROWS = decltype(rw)::value, BANDS = decltype(bn)::value;
-                constexpr bool INSTR = decltype(ins)::value, SEVERAL = decltype(several)::value, RAYBLK = decltype(rayblk)::value;
-                // the instrument rows are band integrals; several level gases are several gases of the batch
-                if constexpr ((BANDS || !INSTR) && (NG >= 2 || !SEVERAL)) {
-                  auto launch_pack = [&](auto... pack) {
-                    std::conditional_t<BANDS, FoldBands, double *> out;
-                    if constexpr (BANDS) out = bd;
-                    else out = L.jac;
-                    hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, ROWS, BANDS, INSTR, decltype(pack)...>), grid, dim3(256), 0,
-                                       st, L.abs_c, L.emi_c, L.n_pts, L.n_layers, L.seg_off, L.seg_layer, L.col, L.dcol, L.o, L.n_rays, gas,
-                                       tab, n_tab_rows, L.coef_row, L.blk, L.ent_off, L.ent, L.slot_par, n_row_par, rad, out, pack...);
-                  };
-                  auto launch = [&](auto... pack) { // the ray blocks last
-                    if constexpr (RAYBLK) launch_pack(pack..., rbk);
-                    else launch_pack(pack...);
-                  };
-                  if constexpr (ROWS && SEVERAL) launch(L.dabs, L.demi, *L.lgas);
-                  else if constexpr (ROWS) launch(L.dabs, L.demi);
-                  else if constexpr (SEVERAL) launch(*L.lgas);
-                  else launch();
-                }
-               });
-              });
-            });
-          });
-        });
-      });
-    });
-  });
-  return (int)hipGetLastError();
+  // the instances of five to eight gases are another translation unit's; the launch itself is one body (sr_limb_state_launch.inc)
+  if (L.o.n_gas > kFoldGasMax) return launch_limb_jac_state_many(L, bd, n_row_par, st);
+  const int np = per_ray ? L.np : level_jac_np(L.n_par);
+  return launch_state_instances(L, bd, n_row_par, st, [&](auto &&f) { return by_ngas(L.o.n_gas, f); },
+                                [&](auto &&f) { by_level_np(np, f); });
 }
 
 int launch_limb_parts(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
                       const int *seg_layer, const double *col, const LimbOpts &o, int gas, const double *tab,
                       const int *coef_row, int n_blocks, const unsigned *words, const double *cc, const int *slot_level,
                       const int *slot_part, int n_part, double *rad, double *parts, hipStream_t st) {
+  bool found = false; // (an instance for o.n_gas exists and was launched)
   if (n_pts <= 0 || n_rays <= 0 || n_part <= 0 || n_blocks <= 0) return 0;
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_rays), 1, n_blocks);
   by_level_np(limb_parts_np(n_part), [&](auto np) {
-    by_ngas(o.n_gas, [&](auto ng) {
+    found = by_ngas(o.n_gas, [&](auto ng) {
       hipLaunchKernelGGL((sr_limb_parts_kernel<decltype(ng)::value, decltype(np)::value>), grid, dim3(256), 0, st, abs_c, emi_c, n_pts,
                          n_layers, seg_off, seg_layer, col, o, n_rays, gas, tab, coef_row, words, cc, slot_level, slot_part, n_part,
                          rad, parts);
     });
   });
-  return (int)hipGetLastError();
+  return found ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 int launch_radiance_jac_layer(const double *abs_c, const double *emi_c, const double *dabs, const double *demi,

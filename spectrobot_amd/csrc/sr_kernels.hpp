@@ -405,6 +405,8 @@ int launch_fold_dense(const int *plan, const double *col, const int *par_gas_hos
 int launch_fold_fwd(const int *plan, const double *col, int n_seg, int n_rec, FoldDense *rec, const double *abs_c,
                     const double *emi_c, int n_pts, int n_layers, int n_rays, int n_visits, const LimbOpts &o, double *rad,
                     hipStream_t st, bool pack = true);
+// the grid of the kernels that deal their blocks by limb_block(): the point blocks rounded up to the eight XCDs
+inline unsigned limb_grid(int n_pb, int n_rays) { return (unsigned)(((n_pb + 7) / 8) * 8) * (unsigned)n_rays; }
 // launch_limb takes the latency-bound split kernel below this many waves
 inline bool limb_launch_is_small(int n_pts, int n_rays) { return (long)((n_pts + 63) / 64) * n_rays < 2048; }
 int launch_radiance(const double *abs_c, const double *emi_c, int n_pts, int n_rays, const int *seg_off,

@@ -93,5 +93,17 @@ __device__ __forceinline__ void limb_load_coef(const double *__restrict__ abs_c,
     e[g] = emi_c[g * gstride + ofs];
   }
 }
+// ... of an instance with more gas slots than the batch has gases (the state kernel above four gases: n_live gases in NG
+// slots): a padding slot reads gas 0's rows, so that every load is valid; its column is an exact zero where it is used.
+template <int NG>
+__device__ __forceinline__ void limb_load_coef_padded(const double *__restrict__ abs_c, const double *__restrict__ emi_c,
+                                                      size_t gstride, size_t ofs, int n_live, double (&a)[NG], double (&e)[NG]) {
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const size_t at = (g < n_live ? (size_t)g : (size_t)0) * gstride + ofs;
+    a[g] = abs_c[at];
+    e[g] = emi_c[at];
+  }
+}
 
 } // namespace sr

@@ -39,13 +39,23 @@ constexpr int kLevelEntRows = -2;
 // kernel's last argument holds, per level gas, the tables, their row count and the gas's index in the batch
 constexpr int kLevelEntGasShift = 16, kLevelEntLevelMask = (1 << kLevelEntGasShift) - 1;
 constexpr int kLevelGasMax = 4;
+// Gases of a ray batch.  kLimbGasMax: what the path-order radiance kernels and the state kernel take (check_los of their
+// entries); kFoldGasMax: every kernel with four gas slots in its packed records or registers (the folded, adjoint,
+// forward-sensitivity, parts and retrieval-loop kernels).  At most kLevelGasMax of a batch's gases are level-factored.
+constexpr int kLimbGasMax = 8, kFoldGasMax = 4;
 struct LevelGasTabs {
   const double *tab[kLevelGasMax];
   int n_tab_rows[kLevelGasMax];
   int gas[kLevelGasMax];
 };
 constexpr int kLevelJacNPSmall = 8, kLevelJacNPLarge = 16;
-inline int level_jac_np(int n_par) { return n_par > kLevelJacNPSmall ? kLevelJacNPLarge : kLevelJacNPSmall; }
+// The state plan's gas word (blk[2 b + 1]) holds the gas of every column slot of a block: two bits per slot for a batch
+// of at most four gases (16 slots), three for a batch of five to eight -- 24 bits of the int, so such a batch has blocks
+// of kLevelJacNPSmall slots whatever its parameter count.
+inline int state_gas_bits(int n_gas) { return n_gas > kFoldGasMax ? 3 : 2; }
+inline int level_jac_np(int n_par, int gas_bits = 2) {
+  return gas_bits == 2 && n_par > kLevelJacNPSmall ? kLevelJacNPLarge : kLevelJacNPSmall;
+}
 
 // ---- checks of a call's arguments ----
 
@@ -69,9 +79,10 @@ struct LosShape {
   int n_seg = 0, n_pt = 0;
 };
 
-inline int check_los(const sr_los_desc *los, int n_layers, LosShape *out) {
+// gas_max: the gases the calling entry's kernels take, kLimbGasMax or kFoldGasMax
+inline int check_los(const sr_los_desc *los, int n_layers, LosShape *out, int gas_max = kFoldGasMax) {
   if (!los || los->n_rays <= 0 || los->n_gas <= 0 || !los->seg_off || !los->x || !los->nd || !los->vmr) return SR_ERR_ARG;
-  if (los->n_gas > 4) return SR_ERR_LIMIT;
+  if (los->n_gas > gas_max) return SR_ERR_LIMIT;
   if (los->init_mode < 0 || los->init_mode > 2) return SR_ERR_ARG;
   if (los->init_mode == 2 && !(los->t_init > 0.0 && los->step > 0.0)) return SR_ERR_ARG;
   const int n_seg = los->seg_off[los->n_rays];
@@ -91,8 +102,9 @@ inline int check_los(const sr_los_desc *los, int n_layers, LosShape *out) {
 }
 
 // check_los + the column parameters staged with the batch
-inline int check_los_par(const sr_los_desc *los, int n_layers, int n_par, const int32_t *par_gas, const double *par_w, LosShape *out) {
-  const int rc = check_los(los, n_layers, out);
+inline int check_los_par(const sr_los_desc *los, int n_layers, int n_par, const int32_t *par_gas, const double *par_w, LosShape *out,
+                         int gas_max = kFoldGasMax) {
+  const int rc = check_los(los, n_layers, out, gas_max);
   if (rc) return rc;
   if (n_par < 0 || (n_par > 0 && (!par_gas || !par_w))) return SR_ERR_ARG;
   for (int p = 0; p < n_par; ++p)
@@ -352,6 +364,8 @@ inline void build_sync_schedule(const std::vector<int> &far, const std::vector<i
 // the one-gas plan, word for word.
 // n_hid (the pointing derivative): n_hid more column slots behind the caller's, slot g of gas g, whose rows of dcol follow
 // the caller's; their rows of jac come LAST, n_col + n_lev + n_row + g, the other kinds keep the rows they have without.
+// gas_bits (state_gas_bits of the batch): the bits a column slot's gas takes in the gas word; with 3 the blocks have
+// kLevelJacNPSmall slots.  With 2 the plan is what it always was.
 struct LevelJacPlan {
   int n_blocks;
   std::vector<int> blk, ent_off, slot_par;
@@ -359,9 +373,9 @@ struct LevelJacPlan {
 };
 inline LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev, const int32_t *par_level, const double *par_c,
                                    int n_layers, int n_row = 0, const double *par_t = nullptr, const int32_t *par_lgas = nullptr,
-                                   int n_hid = 0) {
+                                   int n_hid = 0, int gas_bits = 2) {
   const int n_state = n_col + n_lev + n_row;
-  const int nc_all = n_col + n_hid, n_cl = nc_all + n_lev, n_par = n_cl + n_row, np = level_jac_np(n_par);
+  const int nc_all = n_col + n_hid, n_cl = nc_all + n_lev, n_par = n_cl + n_row, np = level_jac_np(n_par, gas_bits);
   const int n_blocks = std::max(1, (n_par + np - 1) / np); // (no parameter at all, the instrument rows alone: one block of unused slots)
   std::vector<int32_t> packed; // the `level` words of the entries: the level, with several level gases the gas above it
   if (par_lgas) {
@@ -375,7 +389,7 @@ inline LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev,
   for (int b = 0; b < n_blocks; ++b) {
     const int i0 = b * np, i1 = std::min(n_par, i0 + np), nc = std::max(0, std::min(nc_all, i1) - i0);
     unsigned gases = 0u;
-    for (int i = i0; i < i0 + nc; ++i) gases |= (unsigned)(i < n_col ? par_gas[i] : i - n_col) << (2 * (i - i0));
+    for (int i = i0; i < i0 + nc; ++i) gases |= (unsigned)(i < n_col ? par_gas[i] : i - n_col) << (gas_bits * (i - i0));
     P.blk[2 * b] = nc;
     P.blk[2 * b + 1] = (int)gases;
     for (int i = i0; i < i1; ++i)
@@ -401,7 +415,7 @@ inline LevelJacPlan level_jac_plan(int n_col, const int32_t *par_gas, int n_lev,
 // ray lists the parameters that touch it -- a column parameter iff par_w[p] is non-zero at one of the ray's sample points,
 // a level or row parameter iff par_c[p][r] / par_t[p][r] is non-zero on the coefficient row r of one of its segments, the
 // n_hid hidden slots always -- in level_jac_plan's order (columns, hidden, levels by (level gas, level), rows), and cuts
-// ITS list into blocks of np: 8 if no ray is touched by more than 8 parameters, else 16.  A ray has at least block 0 (the
+// ITS list into blocks of np: 8 if no ray is touched by more than 8 parameters (or gas_bits is 3), else 16.  A ray has at least block 0 (the
 // radiance's), also with an empty list.  The blocks of all rays lie one behind the other: ray_blk_off [n_rays + 1] is the
 // prefix sum of the rays' block counts, and blk [.][2], col_row [.][np], ent_off [.][n_layers + 1] and slot_par [.][np]
 // are indexed by ray_blk_off[ray] + block.  col_row: the row of dcol behind each column slot (p of a caller's parameter,
@@ -417,7 +431,7 @@ struct RayJacPlan {
 };
 inline RayJacPlan ray_jac_plan(const sr_los_desc *los, int n_col, const int32_t *par_gas, const double *par_w, int n_lev,
                                const int32_t *par_level, const double *par_c, int n_layers, int n_row = 0,
-                               const double *par_t = nullptr, const int32_t *par_lgas = nullptr, int n_hid = 0) {
+                               const double *par_t = nullptr, const int32_t *par_lgas = nullptr, int n_hid = 0, int gas_bits = 2) {
   const int n_rays = los->n_rays, n_state = n_col + n_lev + n_row, n_pt = los->pt_off[los->seg_off[n_rays]];
   std::vector<int32_t> packed;
   if (par_lgas) {
@@ -458,7 +472,7 @@ inline RayJacPlan ray_jac_plan(const sr_los_desc *los, int n_col, const int32_t 
     longest = std::max(longest, lst.size());
   }
   RayJacPlan P{};
-  P.np = longest > (size_t)kLevelJacNPSmall ? kLevelJacNPLarge : kLevelJacNPSmall;
+  P.np = level_jac_np((int)std::min(longest, (size_t)INT_MAX), gas_bits);
   const int np = P.np;
   P.ray_blk_off.assign((size_t)n_rays + 1, 0);
   for (int ray = 0; ray < n_rays; ++ray) {
@@ -481,7 +495,7 @@ inline RayJacPlan ray_jac_plan(const sr_los_desc *los, int n_col, const int32_t 
         const Item &it = lst[i];
         const int q = i - i0;
         if (it.kind == 0) {
-          gases |= (unsigned)(it.idx < n_col ? par_gas[it.idx] : it.idx - n_col) << (2 * q);
+          gases |= (unsigned)(it.idx < n_col ? par_gas[it.idx] : it.idx - n_col) << (gas_bits * q);
           P.col_row[(size_t)rb * np + q] = it.idx;
           ++nc;
         }

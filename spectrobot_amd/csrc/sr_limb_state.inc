@@ -119,6 +119,24 @@ __device__ __forceinline__ const StateRayBlocks &state_ray_blocks(const T &, con
 // is still blockIdx.z == 0, the radiance's block of every ray.  Rows of jac / part that no block of a ray writes are
 // cleared by the host on the stream ahead of the launch.  The instances without a StateRayBlocks keep their argument block
 // and their machine code.
+// MORE THAN FOUR GASES (NG > kFoldGasMax, NP = 8; instantiated by sr_limb_many.hip): blk's gas word holds three bits per
+// column slot, gas of slot q = gws >> 3 q & 7 (state_gas_bits; the host's plans pack them so), and an instance may have
+// more gas slots than the batch has gases -- o.n_gas of them are live, the launcher takes the next instance up.  A
+// padding slot reads gas 0's coefficient rows (limb_load_coef_padded: every load is valid) and column 0 (state_column),
+// and its column counts as an exact 0: tau + a 0, E + e 0 and the row sums' fma(., 0, .) return their other operand for
+// finite a and e, no column slot names the padding gas, so no result depends on it.  The recursion, the entry loop, the
+// row slots, the level-gas lookup and the band epilogue are the same operations; every line of it stands behind a
+// constexpr of NG, and the instances of at most four gases keep their machine code.
+template <bool PAD>
+__device__ __forceinline__ double state_column(const double *__restrict__ col, int g, int n_live, int n_seg_total, int s) {
+  if constexpr (PAD) {
+    const bool on = g < n_live;
+    const double u = col[(size_t)(on ? g : 0) * n_seg_total + s];
+    return on ? u : 0.0;
+  } else {
+    return col[(size_t)g * n_seg_total + s];
+  }
+}
 template <int NG, int NP, bool COLS, bool ROWS, bool BANDS, bool INSTR, class... RowSpectra>
 __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     const double *__restrict__ abs_c, const double *__restrict__ emi_c, int n_pts, int n_layers,
@@ -127,7 +145,11 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     const int *__restrict__ coef_row, const int *__restrict__ blk, const int *__restrict__ ent_off,
     const LevelEnt *__restrict__ ent, const int *__restrict__ slot_par, int n_par, double *__restrict__ rad,
     std::conditional_t<BANDS, FoldBands, double *__restrict__> jac, RowSpectra... row_spectra) {
-  static_assert(NP <= 16 && NG <= 4, "blk packs the gases of 16 column slots, two bits each");
+  static_assert(NG <= kFoldGasMax ? NP <= 16 : (NG <= kLimbGasMax && NP <= kLevelJacNPSmall),
+                "blk packs the gases of a block's column slots: 16 slots of two bits (up to four gases) or 8 of three (up to eight)");
+  constexpr bool PAD = NG > kFoldGasMax; // (the instances that may have more gas slots than the batch has gases)
+  constexpr int kGasBits = PAD ? 3 : 2;
+  constexpr unsigned kGasMask = (1u << kGasBits) - 1u;
   static_assert(BANDS || !INSTR, "the instrument rows are band integrals");
   constexpr bool GASES = kStateSeveralGases<RowSpectra...>, RAYBLK = kStateRayBlocks<RowSpectra...>;
   static_assert(sizeof...(RowSpectra) == (ROWS ? 2 : 0) + (GASES ? 1 : 0) + (RAYBLK ? 1 : 0),
@@ -155,7 +177,10 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
   const int s0 = seg_off[ray], s1 = seg_off[ray + 1];
   const size_t gstride = (size_t)n_layers * n_pts, plane = (size_t)n_tab_rows * n_pts;
   double an[NG], en[NG];
-  if (s0 < s1) limb_load_coef<NG>(abs_c, emi_c, gstride, (size_t)seg_layer[s0] * n_pts + j, an, en);
+  if (s0 < s1) {
+    if constexpr (PAD) limb_load_coef_padded<NG>(abs_c, emi_c, gstride, (size_t)seg_layer[s0] * n_pts + j, o.n_gas, an, en);
+    else limb_load_coef<NG>(abs_c, emi_c, gstride, (size_t)seg_layer[s0] * n_pts + j, an, en);
+  }
   for (int s = s0; s < s1; ++s) {
     const int r = seg_layer[s];
     double a[NG], e[NG], D[NP];
@@ -164,7 +189,7 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
     for (int g = 0; g < NG; ++g) {
       a[g] = an[g];
       e[g] = en[g];
-      const double u = col[(size_t)g * o.n_seg_total + s];
+      const double u = state_column<PAD>(col, g, o.n_gas, o.n_seg_total, s);
       tau = g == 0 ? a[g] * u : tau + a[g] * u;
       E = g == 0 ? e[g] * u : E + e[g] * u;
       ug = g == gas ? u : ug;
@@ -179,7 +204,8 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
         for (int q = 0; q < NP; ++q) D[q] = dc[(size_t)min(q, nc - 1) * o.n_seg_total + s];
       }
     }
-    limb_load_coef<NG>(abs_c, emi_c, gstride, (size_t)seg_layer[min(s + 1, s1 - 1)] * n_pts + j, an, en);
+    if constexpr (PAD) limb_load_coef_padded<NG>(abs_c, emi_c, gstride, (size_t)seg_layer[min(s + 1, s1 - 1)] * n_pts + j, o.n_gas, an, en);
+    else limb_load_coef<NG>(abs_c, emi_c, gstride, (size_t)seg_layer[min(s + 1, s1 - 1)] * n_pts + j, an, en);
     const Atten A = attenuation(tau);
     const double t = A.t, em1 = A.em1, f = A.f;
     const bool thin = A.thin;
@@ -206,7 +232,7 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
         if constexpr (NG == 1) {
           J[q] = fma(J[q], t, W[0] * D[q]);
         } else { // the gas is chosen on the scalar side: D or 0 per gas, the products with 0 add nothing
-          const unsigned gq = gws >> (2 * q) & 3u;
+          const unsigned gq = gws >> (kGasBits * q) & kGasMask;
           double x = W[0] * (gq == 0u ? D[q] : 0.0);
 #pragma unroll
           for (int g = 1; g < NG; ++g) x = fma(W[g], gq == (unsigned)g ? D[q] : 0.0, x);
@@ -234,9 +260,16 @@ __global__ __launch_bounds__(256) void sr_limb_jac_state_kernel(
               double dtau = 0.0, dE = 0.0;
 #pragma unroll
               for (int g = 0; g < NG; ++g) {
-                const double u = col[(size_t)g * o.n_seg_total + s];
-                dtau = fma(rs[0][g * gstride + ofs], u, dtau);
-                dE = fma(rs[1][g * gstride + ofs], u, dE);
+                if constexpr (PAD) { // (a padding slot: gas 0's rows, an exact zero for its column)
+                  const double u = state_column<true>(col, g, o.n_gas, o.n_seg_total, s);
+                  const size_t go = (g < o.n_gas ? (size_t)g : (size_t)0) * gstride + ofs;
+                  dtau = fma(rs[0][go], u, dtau);
+                  dE = fma(rs[1][go], u, dE);
+                } else {
+                  const double u = col[(size_t)g * o.n_seg_total + s];
+                  dtau = fma(rs[0][g * gstride + ofs], u, dtau);
+                  dE = fma(rs[1][g * gstride + ofs], u, dE);
+                }
               }
               d = -I * t * dtau + (o.solo_absorption ? 0.0 : dE * f + E * fp * dtau);
             }

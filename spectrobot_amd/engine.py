@@ -811,12 +811,18 @@ class LevelFactoredSet(object):
     LevelFactored, its gas's index in the batch, the table row of every coefficient row and the vibrational temperatures
     [n_levels, n_steps] its coefficients in `coeffs` were combined with.  Level parameter p belongs to member par_lgas[p]
     and to its level par_level[p]; par_c is formed per member exactly as LevelFactored.state_jacobian forms it
-    (_state_level_args: the populations' Tvib derivative times the node weights).  All members share the spectral shard."""
+    (_state_level_args: the populations' Tvib derivative times the node weights).  All members share the spectral shard.
+    At most MAX_MEMBERS (four) members, whose gases may be any of the batch's up to eight (max_gases())."""
+
+    MAX_MEMBERS = 4   # the level gases of one state call (kLevelGasMax)
 
     def __init__(self, members):
         self.members = [tuple(m) + (None,) * (5 - len(m)) for m in members]
         if not self.members:
             raise ValueError("LevelFactoredSet needs at least one (lf, gas, step_row, tvib)")
+        if len(self.members) > self.MAX_MEMBERS:
+            raise ValueError("LevelFactoredSet: %d members, at most %d gases of a batch are level-factored"
+                             % (len(self.members), self.MAX_MEMBERS))
         if len({m[0]._shard for m in self.members}) != 1:
             raise ValueError("the LevelFactored of a set must share their spectral shard")
         if len({int(m[1]) for m in self.members}) != len(self.members):
@@ -1126,6 +1132,22 @@ def _gas_stack(coeffs):
     return a, e
 
 
+def max_gases(folded=False):
+    """The gases a LimbLOS batch may carry (sr_limb_max_gases): 8 for limb_rays and every state call
+    (limb_rays_state_jacobian, limb_rays_state_bands, limb_rays_level_jacobian, LevelFactored / LevelFactoredSet); with
+    folded=True, 4: limb_rays_jacobian, limb_rays_jacobians, limb_rays_layer_jacobian, limb_rays_parts,
+    retrieval_forward, retrieval_step and retrieval_loop, whose kernels keep four gas slots in their packed records."""
+    return int(lib.sr_limb_max_gases(1 if folded else 0))
+
+
+def _four_gas_call(call, los):
+    """The calls of the folded-limit kernels refuse a larger batch here, before any device call."""
+    limit = max_gases(folded=True)
+    if los.n_gas > limit:
+        raise ValueError("%s: a batch of %d gases, the call takes at most max_gases(folded=True) = %d (limb_rays and the "
+                         "state calls take %d)" % (call, los.n_gas, limit, max_gases()))
+
+
 def limb_rays(coeffs, los, grid=None, g_lo=0, rad0=None, resident=True):
     """Radiances [n_rays, n_pts] of a LimbLOS batch through the gases' coefficients: columns per segment on the device,
     then the recursion.  coeffs: (abs, emi) or [(abs, emi)] per gas, CUDA [n_layers, n_pts] each.  rad0: CUDA
@@ -1155,6 +1177,7 @@ def limb_rays_jacobian(coeffs, los, par_gas, par_w, grid=None, g_lo=0, rad0=None
     as a third value (one hires_to_lowres call, one copy to the host, for a retrieval iteration).
     resident=True: through the batch's device-resident form with these parameter arrays (LimbLOS.handle_par, keyed on
     the arrays' identity) -- a retrieval loop that keeps its LimbLOS and calls los.set_vmr between iterations."""
+    _four_gas_call("limb_rays_jacobian", los)
     a, e = _gas_stack(coeffs)
     n_gas, n_layers, n_pts = a.shape
     par_gas_in, par_w_in = par_gas, par_w
@@ -1209,6 +1232,7 @@ def retrieval_forward(coeffs, los, par_gas, par_w, x, grid, centers_nm, widths_n
     width) gives its partial band integrals.  The batch's host copy of the VMRs (los.vmr) is NOT updated: call
     los.set_vmr when the loop ends.  buf: scratch from an earlier call (returned as second value).  ils: an ILS, the
     bands' tabulated line shape (as hires_to_lowres)."""
+    _four_gas_call("retrieval_forward", los)
     a, e = _gas_stack(coeffs)
     n_gas, n_layers, n_pts = a.shape
     w0, step, n = grid_params(grid)
@@ -1267,6 +1291,7 @@ def retrieval_step(coeffs, los, par_gas, par_w, x, grid, centers_nm, widths_nm, 
     (spect_main_module.inversion_algebra) on the band spectra and Jacobians the call brings to the host.  oe: OeProblem.
     Returns (out [n_pix, 1 + n_par, n_bands], chi_sum, n_used, dx [n_par], S_x, AVK [n_par, n_par], buf).  Single process
     only (a shard's band integrals are partial).  ils: as retrieval_forward."""
+    _four_gas_call("retrieval_step", los)
     a, e = _gas_stack(coeffs)
     n_gas, n_layers, n_pts = a.shape
     w0, step, n = grid_params(grid)
@@ -1306,6 +1331,7 @@ def retrieval_loop(coeffs, los, par_gas, par_w, x0, grid, centers_nm, widths_nm,
     parameters in use.  Returns (out of the last iteration [n_pix, 1 + n_par, n_bands], chi history [n_it], x history
     [n_updates + 1, n_par], stop '' | 'converged' | 'raised', S_x, AVK (None when no update was applied), buf).  ils: as
     retrieval_forward."""
+    _four_gas_call("retrieval_loop", los)
     a, e = _gas_stack(coeffs)
     n_gas, n_layers, n_pts = a.shape
     w0, step, n = grid_params(grid)
@@ -1349,6 +1375,7 @@ def retrieval_loop(coeffs, los, par_gas, par_w, x0, grid, centers_nm, widths_nm,
 def limb_rays_layer_jacobian(coeffs, dcoeffs, los, grid=None, g_lo=0):
     """d rad / d (one scalar per layer) [n_rays, n_layers, n_pts]; dcoeffs like coeffs: d(abs, emi of layer k) /
     d(parameter of layer k) per gas (sr_limb_rays_jac_layer_dev)."""
+    _four_gas_call("limb_rays_layer_jacobian", los)
     a, e = _gas_stack(coeffs)
     da, de = _gas_stack(dcoeffs)
     n_gas, n_layers, n_pts = a.shape
@@ -1368,6 +1395,7 @@ def limb_rays_jacobians(coeffs, los, dcoeffs=None, par_gas=None, par_w=None, gri
     (sr_limb_rays_jacobians_dev).  Returns (rad | None, jac_layer | None, jac_par | None).
     seg_jac_row [n_seg] (with n_jac_rows): the per-layer Jacobian row of every segment when it is not the segment's
     coefficient row (3-D paths: a coefficient row per LOS step, the Jacobian per altitude layer)."""
+    _four_gas_call("limb_rays_jacobians", los)
     a, e = _gas_stack(coeffs)
     n_gas, n_layers, n_pts = a.shape
     if n_gas != los.n_gas:
@@ -1517,8 +1545,9 @@ def _level_gases_args(level_gases, par_lgas, tab, coef_row, par_level, par_c, n_
     if tab is not None or coef_row is not None:
         raise ValueError("level_gases carries the tables and row maps: give no tab / coef_row beside it")
     level_gases = list(level_gases)
-    if not 1 <= len(level_gases) <= n_gas:
-        raise ValueError("%d level gases for a batch of %d gases" % (len(level_gases), n_gas))
+    if not 1 <= len(level_gases) <= min(n_gas, LevelFactoredSet.MAX_MEMBERS):
+        raise ValueError("%d level gases for a batch of %d gases (at most %d are level-factored)"
+                         % (len(level_gases), n_gas, LevelFactoredSet.MAX_MEMBERS))
     arr, keep, seen = (_lib.LevelGasDesc * len(level_gases))(), [], set()
     for k, (g, t, cr) in enumerate(level_gases):
         g = int(g)
@@ -1689,6 +1718,7 @@ def limb_rays_parts(coeffs, los, part_gas, part_level, part_c=None, tab=None, co
     coeffs as limb_rays; tab: the gas's pair tables (CUDA [n_levels, 2, n_tab_rows, n_pts], LineSet.glevel_pairs);
     coef_row [n_layers]; part_c [n_part, n_layers] (rows of gas parts ignored); the three are needed for level parts
     only.  Populations of a gas's levels: LevelFactored.level_radiances."""
+    _four_gas_call("limb_rays_parts", los)
     a, e = _gas_stack(coeffs)
     n_gas, n_layers, n_pts = a.shape
     if n_gas != los.n_gas:

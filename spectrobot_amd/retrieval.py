@@ -49,7 +49,9 @@ class Gas(object):
     self_broadening: the line set carries self-broadening coefficients (engine.LineSet.set_line_shape) and the scene
     hands it the gas's own partial pressure, vmr x press of the layers, before every coefficient build.  The VMR
     Jacobians hold the coefficients fixed -- the dependence of the Lorentz width on the gas's own VMR is not
-    differentiated; a retrieval refreshes the coefficients between its iterations (coefficients(refresh=True))."""
+    differentiated; a retrieval refreshes the coefficients between its iterations (coefficients(refresh=True)).
+    Every Gas -- an isotopologue with its own iso_ratio too -- takes one of the scene's gas slots: eight in inversion_state,
+    inversion_boxes, simulate_boxes and simulate(bayes_set=None), four in the other drivers (see TableGas)."""
 
     def __init__(self, name, lineset, vmr, iso_ratio=1.0, tvib=None, self_broadening=False):
         self.name, self.lineset, self.iso_ratio = name, lineset, float(iso_ratio)
@@ -127,7 +129,9 @@ class TableGas(Gas):
     scale: None, an array per layer, or a callable (scene) -> array; held fixed under d / dT (as TempProfile holds columns
     and pressure fixed).  A retrieval set named after the gas is an ordinary column set.
 
-    A TableGas takes one of the recursion kernels' four gas slots.  accumulate_into=<name of a plain Gas>: the table is
+    A TableGas takes one of the scene's gas slots: eight in inversion_state, inversion_boxes, simulate_boxes and
+    simulate(bayes_set=None) (engine.max_gases()), four in simulate with a bayes_set, inversion_fast_limb, inversion and
+    radtrans, whose kernels keep four gas slots (engine.max_gases(folded=True)).  accumulate_into=<name of a plain Gas>: the table is
     folded into that line gas's pair instead -- added to its (abs, emi) and, in a temperature retrieval, to its analytic
     row derivatives -- sharing that gas's VMR and iso_ratio; it then has no slot, no VMR and no retrieval set of its
     own (its vmr and iso_ratio arguments are ignored)."""
@@ -162,6 +166,15 @@ class TableGas(Gas):
             self.coeffs, self.dcoeffs = res if derivative else (res, None)
             self._key, self.coeffs_shard = key, (g_lo, g_hi)
         return self.coeffs
+
+
+def _refuse_many_slots(scene, who):
+    """The drivers whose kernels keep four gas slots refuse a larger scene before any device call."""
+    limit = engine.max_gases(folded=True)
+    if len(scene.gases) > limit:
+        raise ValueError("%s: a scene of %d gas slots, the call takes at most max_gases(folded=True) = %d (inversion_state, "
+                         "inversion_boxes, simulate_boxes and simulate(bayes_set=None) take %d; TableGas(accumulate_into=...) "
+                         "takes no slot)" % (who, len(scene.gases), limit, engine.max_gases()))
 
 
 def _refuse_table_gas(g, who):
@@ -717,6 +730,8 @@ def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, re
     A bayes_set with the "instr" set (BandCalibration) is refused: the one-call forward model behind this function
     (sr_retrieval_forward_dev, and the step and loop calls built on it) has no instrument rows; inversion_state has."""
     _refuse_instr(bayes_set, "simulate (sr_retrieval_forward_dev / _step_dev / _loop_dev)")
+    if bayes_set is not None or track_levels is not None or full_output:
+        _refuse_many_slots(scene, "simulate with a bayes_set" if bayes_set is not None else "simulate (radiance budget)")
     if track_levels is not None or full_output:
         if bayes_set is not None or arrays:
             raise ValueError("the radiance budget (track_levels / full_output) is a simulation: no bayes_set, no arrays")
@@ -833,6 +848,7 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
     and .stop ('converged' | 'raised' | 'max_it').  shard / refresh: see simulate (every rank of a multi-GPU run
     calls this with its own spectral shard; all ranks hold the same chi square history and parameters)."""
     _refuse_instr(bayes_set, "inversion_fast_limb")
+    _refuse_many_slots(scene, "inversion_fast_limb")
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)                       # :2607
     group = (alt_step_sims, alt_first_los) if group_observations else None     # :2668-2670
     for name in bayes_set.sets.keys():                                         # :2624-2625
@@ -1415,6 +1431,7 @@ def inversion(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM
     inversion_algebra.  Coefficients through look-up tables (useLUTs, lut_coefficients) or directly.  Like the
     reference it returns None: the result is the state of bayes_set (.history, .stop are added)."""
     _refuse_instr(bayes_set, "inversion")
+    _refuse_many_slots(scene, "inversion")
     LUTopt = dict(LUTopt or {})
     for name in bayes_set.sets.keys():                                                    # :2445-2446
         scene.gas(name).add_clim(bayes_set.sets[name].profile())
@@ -1472,6 +1489,7 @@ def radtrans(scene, pixels, fov_closed_form=True, shard=None, group_observations
     single_rads[(gas.name, 'iso_<n>', lev)][tag] the part a tracked level emits (engine.limb_rays_parts: each attenuated
     by all gases), without field-of-view integral, as in the reference.  The gases' spectra of a line of sight add up
     to its radtrans entry (the scene has no background), the levels' spectra of a gas to the gas's."""
+    _refuse_many_slots(scene, "radtrans")
     group = (alt_step_sims, alt_first_los) if group_observations else None
     if track_levels is not None or full_output:
         return simulate(scene, pixels, None, fov_closed_form=fov_closed_form, shard=shard, group=group,

@@ -5,6 +5,7 @@
 # With another version of the source (e.g. `git show HEAD~1:spectrobot_amd/csrc/sr_kernels.hip` in a directory with its
 # headers) every kernel is also compared, instruction for instruction, with the other version's kernel of the same
 # name; old=new pairs rename the other version's kernels first (re.sub on the demangled name).
+# SR_SOURCE=sr_limb_many.hip: another translation unit of spectrobot_amd/csrc instead of sr_kernels.hip.
 set -e
 root=$(cd "$(dirname "$0")/.." && pwd)
 tmp=$(mktemp -d)
@@ -17,7 +18,7 @@ build() { # source, name
   /opt/rocm/lib/llvm/bin/llvm-readelf --notes "$tmp/$2.elf" > "$tmp/$2.notes"
   /opt/rocm/lib/llvm/bin/llvm-objdump -d --no-show-raw-insn --no-leading-addr "$tmp/$2.elf" > "$tmp/$2.dis"
 }
-build "$root/spectrobot_amd/csrc/sr_kernels.hip" k
+build "$root/spectrobot_amd/csrc/${SR_SOURCE:-sr_kernels.hip}" k
 [ -n "$2" ] && build "$2" other
 python3 - "$tmp" "$@" <<'EOF'
 import os, sys, re, subprocess
