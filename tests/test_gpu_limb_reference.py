@@ -7,8 +7,10 @@ the plain fp64 recursion (limb_reference.plain_fp64) measures against the refere
 kernel gives.  F enters only where the call reaches sr_limb_adjoint_fold_kernel (sr_set_jac_layer_mode 0, shared
 shells, more than 8 parameters or layer rows, and sr_limb_rays_jacobians_dev); every other route, the dense fold
 included, is held to A and C alone.  Group A: the host-column calls, one gas, columns of 1, abs_c = tau exactly.
-Group B: the device LOS pipeline on synthetic limb geometry; the reference takes the device's Curtis-Godson columns
-(pinned to curgod_fort_2 by tests/test_gpu_limb.py) as fp64 inputs.  Needs a real MI355X."""
+Group B: the device LOS pipeline on synthetic limb geometry; the reference takes the device's Curtis-Godson columns as
+fp64 inputs.  Their own yardstick is tests/columns_reference.py: tests/test_gpu_columns_reference.py holds the columns
+of every route, those of resident batches and the parameter-mask columns included, to curgod_fort_2 in long double.
+Needs a real MI355X."""
 import functools
 
 import numpy as np
