@@ -630,6 +630,35 @@ def pack_single_rads(keys, tags, low, bands_nm):
     return radtrans, single_rads
 
 
+def _all_reduce_sum(a):
+    """The sum of a numpy array over the ranks of a sharded run (distributed.all_reduce_sum: a no-op without a process
+    group), through the device under NCCL."""
+    import torch
+    from . import distributed as sd
+    dev = "cuda" if (torch.distributed.is_initialized() and torch.distributed.get_backend() == "nccl") else "cpu"
+    t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    sd.all_reduce_sum(t)
+    return t.cpu().numpy()
+
+
+def _ladder(pixels, alts, group):
+    """(the tangent altitudes to simulate, the pixels' own `alts` to spline back to | None): with group = (alt_step_sims,
+    alt_first_los) the ladder of smm.make_group_observations, otherwise `alts` themselves."""
+    if group is None:
+        return alts, None
+    alts_sim, _ = smm.make_group_observations(list(pixels), alt_step=group[0], alt_first_los=group[1])
+    return [float(a) for a in alts_sim], alts
+
+
+def _closed_form_fov(pixels, fov_closed_form, who):
+    """The number of pixels with a field of view; `who` refuses pixels of which only some have one, or any without the
+    closed form."""
+    with_fov = sum(pix.fov_half > 0 for pix in pixels)
+    if not (with_fov == 0 or (with_fov == len(pixels) and fov_closed_form)):
+        raise ValueError("%s needs the closed-form field of view for every pixel, or for none" % who)
+    return with_fov
+
+
 def _simulate_budget(scene, pixels, track_levels, fov_closed_form, shard, refresh, group):
     """simulate() with the radiance budget: (sims, radtrans, single_rads).  A gas with tracked levels takes the
     level-factored route (engine.LevelFactored on the scene's layers, kept on the gas per spectral shard; coefficients
@@ -637,12 +666,7 @@ def _simulate_budget(scene, pixels, track_levels, fov_closed_form, shard, refres
     first one also carries the gas parts and the radiances --, one instrument step on the stacked buffer and, with a
     spectral shard, one all-reduce of the partial band integrals of radiances and parts together."""
     import torch
-    from . import distributed as sd
-    alts = [a for pix in pixels for a in pix.los_alts()]
-    alts_pix = None
-    if group is not None:
-        alts_sim, _ = smm.make_group_observations(list(pixels), alt_step=group[0], alt_first_los=group[1])
-        alts_pix, alts = alts, [float(a) for a in alts_sim]
+    alts, alts_pix = _ladder(pixels, [a for pix in pixels for a in pix.los_alts()], group)
     keys = single_rad_keys(scene.gases, track_levels)
     n_grid, n_layers, n_gas = len(scene.grid), len(scene.temps), len(scene.gases)
     g_lo, g_hi = (0, n_grid) if shard is None else shard_with_halo(n_grid, *shard)
@@ -686,10 +710,7 @@ def _simulate_budget(scene, pixels, track_levels, fov_closed_form, shard, refres
                                  ils=_ils(scene))
     low = np.asarray(low).reshape(len(buf), n_los, -1)
     if shard is not None:
-        dev = "cuda" if (torch.distributed.is_initialized() and torch.distributed.get_backend() == "nccl") else "cpu"
-        t = torch.from_numpy(np.ascontiguousarray(low)).to(dev)
-        sd.all_reduce_sum(t)
-        low = t.cpu().numpy()
+        low = _all_reduce_sum(low)
     radtrans_, single_rads = pack_single_rads(keys, los_tags(n_los), low, scene.bands_nm)
     at = low[0]
     if alts_pix is not None:
@@ -736,12 +757,7 @@ def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, re
         if bayes_set is not None or arrays:
             raise ValueError("the radiance budget (track_levels / full_output) is a simulation: no bayes_set, no arrays")
         return _simulate_budget(scene, pixels, track_levels, fov_closed_form, shard, refresh, group)
-    from . import distributed as sd
-    alts = [a for pix in pixels for a in pix.los_alts()]
-    alts_pix = None
-    if group is not None:
-        alts_sim, _ = smm.make_group_observations(list(pixels), alt_step=group[0], alt_first_los=group[1])
-        alts_pix, alts = alts, [float(a) for a in alts_sim]
+    alts, alts_pix = _ladder(pixels, [a for pix in pixels for a in pix.los_alts()], group)
     n_grid = len(scene.grid)
     g_lo, g_hi = (0, n_grid) if shard is None else shard_with_halo(n_grid, *shard)
     coeffs = scene.coefficient_stack(refresh=refresh, g_lo=g_lo, g_hi=g_hi)
@@ -761,11 +777,7 @@ def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, re
         if not with_fov:
             out = out[1::3]
         if shard is not None:
-            import torch
-            dev = "cuda" if (torch.distributed.is_initialized() and torch.distributed.get_backend() == "nccl") else "cpu"
-            t = torch.from_numpy(np.ascontiguousarray(out)).to(dev)
-            sd.all_reduce_sum(t)
-            out = t.cpu().numpy()
+            out = _all_reduce_sum(out)
         return out[:, 0, :], out[:, 1:, :]
     los, alt = scene.los(alts)
     if bayes_set is None:
@@ -780,12 +792,7 @@ def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, re
         lo_all = lowres(buf)
         both = np.concatenate([lo_all[:n_los, None, :], lo_all[n_los:].reshape(n_los, n_par, -1)], axis=1)
     if shard is not None:
-        # the one exchange of a sharded iteration
-        import torch
-        dev = "cuda" if (torch.distributed.is_initialized() and torch.distributed.get_backend() == "nccl") else "cpu"
-        t = torch.from_numpy(np.ascontiguousarray(both)).to(dev)
-        sd.all_reduce_sum(t)
-        both = t.cpu().numpy()
+        both = _all_reduce_sum(both)     # the one exchange of a sharded iteration
     if alts_pix is not None:
         # group_observations: every quantity (radiance, each derivative) from its spline over the simulated ladder
         at = np.empty((len(alts_pix),) + both.shape[1:])
@@ -811,8 +818,7 @@ def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, re
         fov_all = smm.fov_closed_form(both[0::3], both[1::3], both[2::3], [pix.pixel_rot for pix in pixels])
     if arrays:
         if fov_all is None:
-            if any(pix.fov_half > 0 for pix in pixels):
-                raise ValueError("simulate(arrays=True) needs the closed-form field of view for every pixel, or for none")
+            _closed_form_fov(pixels, fov_closed_form, "simulate(arrays=True)")
             fov_all = both[1::3]
         return fov_all[:, 0, :], fov_all[:, 1:, :]
     for i, pix in enumerate(pixels):
@@ -839,6 +845,82 @@ def simulate(scene, pixels, bayes_set=None, fov_closed_form=True, shard=None, re
     return sims, derivs
 
 
+def _observed(pixels):
+    """(obs, noise, masks) of the pixels, as lists; masks None when no pixel has one."""
+    masks = None if all(pix.mask is None for pix in pixels) else [pix.mask for pix in pixels]
+    return [pix.observation for pix in pixels], [pix.noise for pix in pixels], masks
+
+
+class _Observations(object):
+    """The observation side of a retrieval on arrays: the pixels' obs / noise / masks lists, their masked vectors obs_vec /
+    noi_vec (smm.genvec), masktot (None: no pixel has a mask) and the inverse a-priori covariance Sa_inv of bayes_set --
+    and what a loop does with an iteration's low [n_pix, n_bands] and dlow [n_pix, n_par, n_bands] against them: the same
+    numbers in the same operations as the object path (genvec / build_jacobian concatenate and mask exactly these rows)."""
+
+    def __init__(self, pixels, bayes_set):
+        self.pixels, self.bayes_set = pixels, bayes_set
+        self.obs, self.noise, self.masks = _observed(pixels)
+        self.obs_vec, _, self.noi_vec = smm.genvec(self.obs, self.obs, self.noise, masks=self.masks)
+        self.masktot = None if self.masks is None else np.concatenate([np.asarray(m, dtype=bool) for m in self.masks])
+        self.Sa_inv = np.linalg.inv(np.asarray(bayes_set.VCM_apriori(), dtype=float))
+
+    def chi(self, low):
+        """(sim_vec, chi square over the parameters in use) of the simulated spectra (chicalc, :2949)."""
+        sim_vec = low.reshape(-1) if self.masktot is None else low.reshape(-1)[self.masktot]
+        return sim_vec, np.sum(((self.obs_vec - sim_vec) / self.noi_vec) ** 2) / (len(self.obs_vec) - self.bayes_set.n_used_par())
+
+    def jacobian(self, dlow):
+        """[n_obs, n_par]: build_jacobian's rows, masked."""
+        jac = np.transpose(dlow, (1, 0, 2)).reshape(dlow.shape[1], -1)
+        return (jac if self.masktot is None else jac[:, self.masktot]).T
+
+    def finish(self, low, dlow, grid):
+        """The end of a loop: bayes_set.jacobian and the parameters' stored derivatives (:2929, 2940) are the last
+        iteration's; returns its spectra as objects on `grid` (a _Grid).  low None (max_it = 0: nothing was simulated): []."""
+        if low is None:
+            return []
+
+        def wrap(v):
+            sp = Spectrum.__new__(Spectrum)
+            sp.spectrum, sp.spectral_grid = np.array(v), grid
+            return sp
+
+        self.bayes_set.jacobian = self.jacobian(dlow)
+        for num in range(len(self.pixels)):
+            for ip, par in enumerate(self.bayes_set.params()):
+                par.store_deriv(wrap(dlow[num, ip]), num=num)
+        return [wrap(v) for v in low]
+
+
+def _array_loop(ob, forward, after_update, chi_threshold, max_it, lambda_LM, L1_reg, check_log=None):
+    """The optimal-estimation loop on arrays, shared by the drivers: per iteration forward() -> (low [n_pix, n_bands], dlow
+    [n_pix, n_par, n_bands]), chi square against the _Observations `ob`, the reference's stopping rule (:2963-2973), the
+    Levenberg-Marquardt step (smm.inversion_algebra_arrays, :2977) and after_update(), which carries the new parameters to
+    wherever the next forward() reads them.  Sets .history and .stop on ob.bayes_set; returns (chi, low, dlow) of the last
+    iteration (None each for max_it = 0) for ob.finish."""
+    bayes_set = ob.bayes_set
+    bayes_set.history, bayes_set.stop = [], 'max_it'
+    chi_old, chi, low, dlow = None, None, None, None
+    for num_it in range(max_it):
+        low, dlow = forward()
+        for par in bayes_set.params():
+            par.set_used()
+        sim_vec, chi = ob.chi(low)
+        bayes_set.history.append(chi)
+        if check_log is not None:
+            check_log.write('Iteration {:2d}: chi is {:8.3f}\n'.format(num_it, chi))
+        why = smm.retrieval_converged(chi, chi_old, chi_threshold)
+        if why:
+            bayes_set.stop = why
+            break
+        chi_old = chi
+        bayes_set.jacobian = ob.jacobian(dlow)
+        smm.inversion_algebra_arrays(bayes_set.jacobian, ob.obs_vec, sim_vec, ob.noi_vec, bayes_set, lambda_LM=lambda_LM,
+                                     L1_reg=L1_reg, Sa_inv=ob.Sa_inv)
+        after_update()
+    return chi, low, dlow
+
+
 def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM=0.1, L1_reg=False,
                         solo_simulation=False, check_log=None, fov_closed_form=True, shard=None, refresh=False,
                         group_observations=False, alt_step_sims=50., alt_first_los=None):
@@ -851,52 +933,43 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
     _refuse_many_slots(scene, "inversion_fast_limb")
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)                       # :2607
     group = (alt_step_sims, alt_first_los) if group_observations else None     # :2668-2670
-    for name in bayes_set.sets.keys():                                         # :2624-2625
-        scene.gas(name).add_clim(bayes_set.sets[name].profile())
-    obs = [pix.observation for pix in pixels]
-    masks = None if all(pix.mask is None for pix in pixels) else [pix.mask for pix in pixels]
-    noise = [pix.noise for pix in pixels]
-    bayes_set.history, bayes_set.stop = [], 'max_it'
-    chi_old, chi, sims = None, None, []
+
+    def into_gases():                                                          # :2624-2625, 2984-2985
+        for name in bayes_set.sets.keys():
+            scene.gas(name).add_clim(bayes_set.sets[name].profile())
+
+    into_gases()
+    obs, noise, masks = _observed(pixels)
     # The loop on arrays: when every pixel has the closed-form field of view (or none has one) an
-    # iteration's spectra stay [n_pix, (n_par,) n_bands] arrays -- the same numbers in the same operations as the
-    # object path (genvec / build_jacobian concatenate and mask exactly these rows) -- and become spectrum objects
+    # iteration's spectra stay [n_pix, (n_par,) n_bands] arrays (_Observations) and become spectrum objects
     # once, when the loop ends; otherwise the objects of the reference's loop, iteration by iteration.
     with_fov = sum(pix.fov_half > 0 for pix in pixels)
     fast = not solo_simulation and ((with_fov == len(pixels) and fov_closed_form) or with_fov == 0)
     if fast:
-        obs_vec, _, noi_vec = smm.genvec(obs, obs, noise, masks=masks)
-        masktot = None if masks is None else np.concatenate([np.asarray(m, dtype=bool) for m in masks])
-        Sa_inv = np.linalg.inv(np.asarray(bayes_set.VCM_apriori(), dtype=float))
-        grid_lo = _Grid(scene.bands_nm)
-
-        def wrap(v):
-            sp = Spectrum.__new__(Spectrum)
-            sp.spectrum, sp.spectral_grid = np.array(v), grid_lo
-            return sp
-
-        low = dlow = None
+        ob = _Observations(pixels, bayes_set)
 
         def finish(low, dlow):
-            if low is None:                                            # (max_it = 0: nothing was simulated)
-                return []
-            scene.los([a for pix in pixels for a in pix.los_alts()])   # the batch's VMRs = the final profiles (host copy too)
-            jac = np.transpose(dlow, (1, 0, 2)).reshape(dlow.shape[1], -1)     # build_jacobian's rows, of the last iteration
-            bayes_set.jacobian = (jac if masktot is None else jac[:, masktot]).T
-            for num in range(len(pixels)):
-                for ip, par in enumerate(bayes_set.params()):
-                    par.store_deriv(wrap(dlow[num, ip]), num=num)              # :2929, 2940 (of the last iteration)
-            return [wrap(v) for v in low]
+            if low is not None:
+                scene.los([a for pix in pixels for a in pix.los_alts()])   # the batch's VMRs = the final profiles (host copy too)
+            return ob.finish(low, dlow, _Grid(scene.bands_nm))
     # Round 6: the whole iteration in ONE library call where it can be (engine.retrieval_step: forward model, chi square
     # and the Levenberg-Marquardt algebra -- the n_par x n_par systems in the library's host code -- on one process, the
     # whole grid, no observation grouping); what stays here is the reference's bookkeeping: the positivity rule of the
     # update, the stopping rule, the history.
     one_step = STEP_IN_ONE_CALL and fast and shard is None and group is None and _one_call_eligible(pixels, bayes_set, fov_closed_form)
+    if fast and not one_step:
+        def forward():
+            return simulate(scene, pixels, bayes_set, fov_closed_form=fov_closed_form, shard=shard, refresh=refresh, arrays=True,
+                            group=group)
+
+        chi, low, dlow = _array_loop(ob, forward, into_gases, chi_threshold, max_it, lambda_LM, L1_reg, check_log=check_log)
+        return chi, obs, finish(low, dlow), bayes_set
+    bayes_set.history, bayes_set.stop = [], 'max_it'
     if one_step:
         n_pb = len(pixels) * len(scene.bands_nm)
         obs_all = np.concatenate([np.asarray(o.spectrum, float) for o in obs])
         noi_all = np.concatenate([np.asarray(nz.spectrum, float) for nz in noise])
-        oe = engine.OeProblem(obs_all, noi_all, masktot, Sa_inv, bayes_set.apriori_vector(), lambda_LM)
+        oe = engine.OeProblem(obs_all, noi_all, ob.masktot, ob.Sa_inv, bayes_set.apriori_vector(), lambda_LM)
         assert obs_all.size == n_pb
         alts_all = [a for pix in pixels for a in pix.los_alts()]
     if one_step and LOOP_IN_ONE_CALL and not refresh and max_it > 0:
@@ -924,12 +997,11 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
         if check_log is not None:
             for num_it, c in enumerate(bayes_set.history):
                 check_log.write('Iteration {:2d}: chi is {:8.3f}\n'.format(num_it, c))
-        for name in bayes_set.sets.keys():                                     # :2984-2985
-            scene.gas(name).add_clim(bayes_set.sets[name].profile())
+        into_gases()
         if why:
             bayes_set.stop = why
         return bayes_set.history[-1], obs, finish(both[:, 0, :], both[:, 1:, :]), bayes_set
-    step_out = None
+    chi_old, chi, sims, low, dlow = None, None, [], None, None
     for num_it in range(max_it):
         if one_step:
             coeffs = scene.coefficient_stack(refresh=refresh)
@@ -942,13 +1014,6 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
             for par in bayes_set.params():
                 par.set_used()
             chi = chi_sum / (n_used - bayes_set.n_used_par())                                              # chicalc, :2949
-            step_out = (dx, S_x, AVK)
-        elif fast:
-            low, dlow = simulate(scene, pixels, bayes_set, fov_closed_form=fov_closed_form, shard=shard, refresh=refresh, arrays=True, group=group)
-            for par in bayes_set.params():
-                par.set_used()
-            sim_vec = low.reshape(-1) if masktot is None else low.reshape(-1)[masktot]
-            chi = np.sum(((obs_vec - sim_vec) / noi_vec) ** 2) / (len(obs_vec) - bayes_set.n_used_par())   # chicalc, :2949
         else:
             sims, derivs = simulate(scene, pixels, bayes_set, fov_closed_form=fov_closed_form, shard=shard, refresh=refresh, group=group)
             if solo_simulation:
@@ -964,24 +1029,15 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
         why = smm.retrieval_converged(chi, chi_old, chi_threshold)             # :2963-2973
         if why:
             bayes_set.stop = why
-            return chi, obs, (finish(low, dlow) if fast else sims), bayes_set
+            break
         chi_old = chi
-        if one_step:
-            dx, S_x, AVK = step_out                                            # inversion_algebra's results, :2977
+        if one_step:                                                           # inversion_algebra's results, :2977
             bayes_set.update_params(dx)
             bayes_set.store_avk(AVK)
             bayes_set.store_VCM(S_x)
-        elif fast:
-            n_par = dlow.shape[1]
-            jac = np.transpose(dlow, (1, 0, 2)).reshape(n_par, -1)             # build_jacobian's rows
-            jac = (jac if masktot is None else jac[:, masktot]).T
-            bayes_set.jacobian = jac
-            smm.inversion_algebra_arrays(jac, obs_vec, sim_vec, noi_vec, bayes_set, lambda_LM=lambda_LM, L1_reg=L1_reg,
-                                         Sa_inv=Sa_inv)                        # :2977
         else:
             smm.inversion_algebra(obs, sims, noise, bayes_set, lambda_LM=lambda_LM, L1_reg=L1_reg, masks=masks)  # :2977
-        for name in bayes_set.sets.keys():                                     # :2984-2985
-            scene.gas(name).add_clim(bayes_set.sets[name].profile())
+        into_gases()
     return chi, obs, (finish(low, dlow) if fast else sims), bayes_set
 
 
@@ -1031,6 +1087,32 @@ def _state_into_gases(scene, bayes_set):
         scene.gas(gas).set_tvib(tv)
 
 
+def _state_call(scene, w, coeffs, dcoeffs, los, bands, **kw):
+    """The one mixed-state library call of an inversion_state iteration for the StateWeights `w`: on the spectra (bands
+    False: (rad, jac)) or on the instrument's bands (True: the [.., 1 + n_par (+ ..), n_bands] rows).  Its receiver is the
+    engine.LevelFactoredSet of the level gases when there are several, the one LevelGas's lf, or the engine function when
+    there is none; the row parameters are named only with dcoeffs (a temperature set).  kw: the route's own keywords
+    (pointing, fov, ils, instrument, out_units)."""
+    route = "state_bands" if bands else "state_jacobian"
+    state = dict(par_gas=w.par_gas, par_w_col=w.par_w_col)
+    if dcoeffs is not None:
+        state.update(dcoeffs=dcoeffs, par_w_temp=w.par_w_temp)
+    if len(w.level_gases) > 1:
+        lfs = engine.LevelFactoredSet([(g.lf, i, g.rows, g.tvib) for g, i in zip(w.level_gases, w.gases)])
+        call, head = getattr(lfs, route), (w.par_lgas, w.par_level, w.par_w_lev)
+    elif w.level_gas is not None:
+        lg = w.level_gas
+        call, head = getattr(lg.lf, route), (lg.rows, lg.tvib, w.par_level, w.par_w_lev)
+        state["gas"] = w.gas
+    else:
+        call, head = getattr(engine, "limb_rays_" + route), ()
+        names = dict(par_w_col="par_w", par_w_temp="par_t")     # (what the engine functions call the two weight blocks)
+        state = {names.get(k, k): v for k, v in state.items()}
+    if bands:
+        head += (scene.grid, scene.bands_nm, scene.widths_nm)
+    return call(coeffs, los, *head, **state, **kw)
+
+
 def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM=0.1, L1_reg=False,
                     fov_closed_form=True, bands_in_kernel=False):
     """inversion_fast_limb's loop for a MIXED state vector: VMR-profile sets (named after a gas) together with the
@@ -1058,114 +1140,51 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     the set stands in the BayesSet; it can stand beside an "instr" set.  The crossed shells are held fixed within an
     iteration and rebuilt between iterations.  Without such a set nothing changes."""
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)
-    with_fov = sum(pix.fov_half > 0 for pix in pixels)
-    if not (with_fov == 0 or (with_fov == len(pixels) and fov_closed_form)):
-        raise ValueError("inversion_state needs the closed-form field of view for every pixel, or for none")
-    alts = [a for pix in pixels for a in pix.los_alts()]
+    with_fov = _closed_form_fov(pixels, fov_closed_form, "inversion_state")
+    alts0 = [a for pix in pixels for a in pix.los_alts()]
     # the sets' names are checked before anything is changed
     with_temp = scene.state_weights(bayes_set, np.zeros(1), several_level_gases=True).par_w_temp.shape[0] > 0
     _state_into_gases(scene, bayes_set)
-    obs = [pix.observation for pix in pixels]
-    masks = None if all(pix.mask is None for pix in pixels) else [pix.mask for pix in pixels]
-    noise = [pix.noise for pix in pixels]
-    obs_vec, _, noi_vec = smm.genvec(obs, obs, noise, masks=masks)
-    masktot = None if masks is None else np.concatenate([np.asarray(m, dtype=bool) for m in masks])
-    Sa_inv = np.linalg.inv(np.asarray(bayes_set.VCM_apriori(), dtype=float))
-    grid_lo = _Grid(scene.bands_nm)
+    ob = _Observations(pixels, bayes_set)
     lowres = lambda r: engine.hires_to_lowres(r, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units, ils=_ils(scene))
     rots = [pix.pixel_rot for pix in pixels]
-    bayes_set.history, bayes_set.stop = [], 'max_it'
     instr = bayes_set.sets.get(INSTR_SET) if INSTR_SET not in [g.name for g in scene.gases] else None
     is_instr = np.array([instr is not None and par.nameset == INSTR_SET for par in bayes_set.params()], dtype=bool)
     point = bayes_set.sets.get(POINTING_SET) if POINTING_SET not in [g.name for g in scene.gases] else None
     is_point = np.array([point is not None and par.nameset == POINTING_SET for par in bayes_set.params()], dtype=bool)
     point_kw = {} if point is None else dict(pointing=True)
     los_kw = {} if point is None else dict(path=True)
-    alts0 = list(alts)
+    n_los = len(alts0)
+    # what the last forward() simulated on: its rays (a "pointing" set moves them) and its band centres (an "instr" set
+    # moves those: the spectra carry the centres they were simulated on)
+    alts, grid_sim = alts0, _Grid(scene.bands_nm)
 
-    def with_instr(fov_rows, n_prof):
-        """[n_pix, 1 + n_prof (+ 1) (+ 2), n_bands] (radiance, profile parameters in BayesSet order, the pointing row,
-        d / d centre, d / d ln width) -> [n_pix, 1 + n_tot, n_bands] in BayesSet order, the "instr" set's columns by the
-        chain rule."""
-        return _rows_in_bayes_order(fov_rows, n_prof, is_point, is_instr, instr, scene.bands_nm0)
-
-    def wrap(v):
-        sp = Spectrum.__new__(Spectrum)
-        # (an "instr" set moves the band centres: the spectra carry those they were simulated on, the last iteration's)
-        sp.spectrum, sp.spectral_grid = np.array(v), grid_lo if instr is None else grid_sim[0]
-        return sp
-
-    grid_sim = [grid_lo]
-
-    def finish(low, dlow):
-        if low is None:                                            # (max_it = 0: nothing was simulated)
-            return []
-        scene.los(alts, **los_kw)                                  # the batch's VMRs = the final profiles
-        jac = np.transpose(dlow, (1, 0, 2)).reshape(dlow.shape[1], -1)     # build_jacobian's rows, of the last iteration
-        bayes_set.jacobian = (jac if masktot is None else jac[:, masktot]).T
-        for num in range(len(pixels)):
-            for ip, par in enumerate(bayes_set.params()):
-                par.store_deriv(wrap(dlow[num, ip]), num=num)
-        return [wrap(v) for v in low]
-
-    chi_old, chi, low, dlow = None, None, None, None
-    n_los = len(alts)
-    for num_it in range(max_it):
-        coeffs = None if with_temp else scene.coefficient_stack()
+    def forward():
+        nonlocal alts, grid_sim
+        coeffs, dcoeffs = (None if with_temp else scene.coefficient_stack()), None
         if point is not None:
-            alts = [a + point.offset() for a in alts0]                 # the rays this iteration simulates
+            alts = [a + point.offset() for a in alts0]
         los, alt = scene.los(alts, **los_kw)
         if instr is not None:
-            grid_sim[0] = _Grid(scene.bands_nm.copy())                 # the centres this iteration simulates on
+            grid_sim = _Grid(scene.bands_nm.copy())
         w = scene.state_weights(bayes_set, alt, several_level_gases=True)
-        # with_temp: coefficients at the current temperatures and their derivatives, then all three kinds at once
-        dcoeffs = None
-        if with_temp:
+        if with_temp:    # coefficients at the current temperatures and their derivatives, then all three kinds at once
             coeffs, dcoeffs = (engine.gas_stack(c) for c in scene.temperature_derivatives())
-        par_w_temp = w.par_w_temp if with_temp else None
-        lg = w.level_gas
-        lfs = None
-        if len(w.level_gases) > 1:     # Tvib sets of several gases: their level parameters in the same one call
-            lfs = engine.LevelFactoredSet([(g.lf, i, g.rows, g.tvib) for g, i in zip(w.level_gases, w.gases)])
         if bands_in_kernel:    # Jacobians, instrument bands and field of view in one call: [n_pix | n_los, 1 + n_par, n_bands]
             band_args = dict(out_units=scene.out_units, fov=engine.fov_factors(rots) if with_fov else None)
             if _ils(scene) is not None:
                 band_args["ils"] = scene.ils
             if instr is not None:
                 band_args["instrument"] = True
-            band_args.update(point_kw)
-            if lfs is not None:
-                both = lfs.state_bands(coeffs, los, w.par_lgas, w.par_level, w.par_w_lev, scene.grid, scene.bands_nm,
-                                       scene.widths_nm, par_gas=w.par_gas, par_w_col=w.par_w_col, dcoeffs=dcoeffs,
-                                       par_w_temp=par_w_temp, **band_args)
-            elif lg is None:
-                both = engine.limb_rays_state_bands(coeffs, los, scene.grid, scene.bands_nm, scene.widths_nm, par_gas=w.par_gas,
-                                                    par_w=w.par_w_col, dcoeffs=dcoeffs, par_t=par_w_temp, **band_args)
-            else:
-                both = lg.lf.state_bands(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, scene.grid, scene.bands_nm,
-                                         scene.widths_nm, par_gas=w.par_gas, par_w_col=w.par_w_col, gas=w.gas, dcoeffs=dcoeffs,
-                                         par_w_temp=par_w_temp, **band_args)
+            both = _state_call(scene, w, coeffs, dcoeffs, los, True, **band_args, **point_kw)
             n_par = both.shape[1] - 1 - (0 if instr is None else 2) - (0 if point is None else 1)
             fov = both if with_fov else both[1::3]
             fov = np.concatenate([fov[:, :1, :], fov[:, 1:1 + n_par, :][:, w.perm], fov[:, 1 + n_par:, :]], axis=1)
-        else:                  # (one level gas or none: the calls as they always were -- without a temperature set no call names row parameters)
+        else:
             if instr is not None and point is None and len(w.perm) == 0:    # the instrument set alone: the radiances, no Jacobian call
                 rad, jac = engine.limb_rays(coeffs, los, resident=False), None
-            elif lfs is not None:
-                rad, jac = lfs.state_jacobian(coeffs, los, w.par_lgas, w.par_level, w.par_w_lev, par_gas=w.par_gas,
-                                              par_w_col=w.par_w_col, dcoeffs=dcoeffs, par_w_temp=par_w_temp, **point_kw)
-            elif with_temp and lg is None:
-                rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col, dcoeffs=dcoeffs,
-                                                           par_t=w.par_w_temp, **point_kw)
-            elif with_temp:
-                rad, jac = lg.lf.state_jacobian(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, par_gas=w.par_gas,
-                                                par_w_col=w.par_w_col, gas=w.gas, dcoeffs=dcoeffs, par_w_temp=w.par_w_temp,
-                                                **point_kw)
-            elif lg is None:
-                rad, jac = engine.limb_rays_state_jacobian(coeffs, los, par_gas=w.par_gas, par_w=w.par_w_col, **point_kw)
             else:
-                rad, jac = lg.lf.state_jacobian(coeffs, los, lg.rows, lg.tvib, w.par_level, w.par_w_lev, par_gas=w.par_gas,
-                                                par_w_col=w.par_w_col, gas=w.gas, **point_kw)
+                rad, jac = _state_call(scene, w, coeffs, dcoeffs, los, False, **point_kw)
             n_rows = 0 if jac is None else jac.shape[1]
             n_par = n_rows - (0 if point is None else 1)               # (the pointing row stands behind the state's)
             order = np.concatenate([w.perm, np.arange(n_par, n_rows)]).astype(int)
@@ -1178,25 +1197,13 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
                 both = np.concatenate([three[0][:, None, :]] + rows + [three[1][:, None, :], three[2][:, None, :]], axis=1)
             fov = smm.fov_closed_form(both[0::3], both[1::3], both[2::3], rots) if with_fov else both[1::3]
         if instr is not None or point is not None:
-            fov = with_instr(fov, n_par)
-            n_par = is_instr.size
-        low, dlow = fov[:, 0, :], fov[:, 1:, :]
-        for par in bayes_set.params():
-            par.set_used()
-        sim_vec = low.reshape(-1) if masktot is None else low.reshape(-1)[masktot]
-        chi = np.sum(((obs_vec - sim_vec) / noi_vec) ** 2) / (len(obs_vec) - bayes_set.n_used_par())   # chicalc
-        bayes_set.history.append(chi)
-        why = smm.retrieval_converged(chi, chi_old, chi_threshold)
-        if why:
-            bayes_set.stop = why
-            return chi, obs, finish(low, dlow), bayes_set
-        chi_old = chi
-        K = np.transpose(dlow, (1, 0, 2)).reshape(n_par, -1)               # build_jacobian's rows
-        K = (K if masktot is None else K[:, masktot]).T
-        bayes_set.jacobian = K
-        smm.inversion_algebra_arrays(K, obs_vec, sim_vec, noi_vec, bayes_set, lambda_LM=lambda_LM, L1_reg=L1_reg, Sa_inv=Sa_inv)
-        _state_into_gases(scene, bayes_set)
-    return chi, obs, finish(low, dlow), bayes_set
+            fov = _rows_in_bayes_order(fov, n_par, is_point, is_instr, instr, scene.bands_nm0)
+        return fov[:, 0, :], fov[:, 1:, :]
+
+    chi, low, dlow = _array_loop(ob, forward, lambda: _state_into_gases(scene, bayes_set), chi_threshold, max_it, lambda_LM, L1_reg)
+    if low is not None:
+        scene.los(alts, **los_kw)                                  # the batch's VMRs = the final profiles
+    return chi, ob.obs, ob.finish(low, dlow, grid_sim), bayes_set
 
 
 class BoxPixel(LimbPixel):
@@ -1230,6 +1237,12 @@ class BoxBatch(object):
                 v = np.asarray(g.vmr if st is None else st.profile(), float)
                 out.append(np.interp(self.L3["alt"], zz, np.append(v, v[-1])))
         return np.array(out)
+
+    def los(self, scene, bayes_set):
+        """The engine.LimbLOS of the batch with vmr(scene, bayes_set); the caller closes it."""
+        L3 = self.L3
+        return engine.LimbLOS(L3["seg_off"], L3["seg_layer"], L3["pt_off"], L3["x"], L3["nd"], self.vmr(scene, bayes_set),
+                              col_scale=[g.iso_ratio for g in scene.gases])
 
 
 def box_batch(scene, bayes_set, pixels):
@@ -1281,29 +1294,19 @@ def inversion_boxes(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     covariance, as inversion_state.  Every pixel has the closed-form field of view, or none has a field of view.  After
     the loop a gas with a box set holds the final profiles in gas.vmr_boxes [n_box, n_lev]; its 1-D vmr is untouched."""
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)
-    with_fov = sum(pix.fov_half > 0 for pix in pixels)
-    if not (with_fov == 0 or (with_fov == len(pixels) and fov_closed_form)):
-        raise ValueError("inversion_boxes needs the closed-form field of view for every pixel, or for none")
+    with_fov = _closed_form_fov(pixels, fov_closed_form, "inversion_boxes")
     B = box_batch(scene, bayes_set, pixels)
-    L3 = B.L3
-    obs = [pix.observation for pix in pixels]
-    masks = None if all(pix.mask is None for pix in pixels) else [pix.mask for pix in pixels]
-    noise = [pix.noise for pix in pixels]
-    obs_vec, _, noi_vec = smm.genvec(obs, obs, noise, masks=masks)
-    masktot = None if masks is None else np.concatenate([np.asarray(m, dtype=bool) for m in masks])
-    Sa_inv = np.linalg.inv(np.asarray(bayes_set.VCM_apriori(), dtype=float))
-    grid_lo = _Grid(scene.bands_nm)
+    ob = _Observations(pixels, bayes_set)
     fov = engine.fov_factors([pix.pixel_rot for pix in pixels]) if with_fov else None
     band_args = dict(out_units=scene.out_units, fov=fov)
     if _ils(scene) is not None:
         band_args["ils"] = scene.ils
-    bayes_set.history, bayes_set.stop, bayes_set.touches = [], 'max_it', B.touches
+    bayes_set.touches = B.touches
     for ip, par in enumerate(bayes_set.params()):
         if B.touches[:, ip].any():
             par.set_involved()
         else:
             par.set_not_involved()
-    n_tot = len(B.par_gas)
 
     def into_gases():
         for name in bayes_set.order:
@@ -1313,64 +1316,30 @@ def inversion_boxes(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             else:
                 scene.gas(name).add_clim(st.profile())
 
-    def wrap(v):
-        sp = Spectrum.__new__(Spectrum)
-        sp.spectrum, sp.spectral_grid = np.array(v), grid_lo
-        return sp
-
-    def finish(low, dlow):
-        if low is None:
-            return []
-        jac = np.transpose(dlow, (1, 0, 2)).reshape(dlow.shape[1], -1)
-        bayes_set.jacobian = (jac if masktot is None else jac[:, masktot]).T
-        for num in range(len(pixels)):
-            for ip, par in enumerate(bayes_set.params()):
-                par.store_deriv(wrap(dlow[num, ip]), num=num)
-        return [wrap(v) for v in low]
-
     into_gases()
-    los = engine.LimbLOS(L3["seg_off"], L3["seg_layer"], L3["pt_off"], L3["x"], L3["nd"], B.vmr(scene, bayes_set),
-                         col_scale=[g.iso_ratio for g in scene.gases])
-    chi_old, chi, low, dlow = None, None, None, None
+    los = B.los(scene, bayes_set)
+
+    def forward():
+        coeffs = scene.coefficient_stack()
+        if bayes_set.history:      # (every iteration but the first, whose VMRs the batch was built with)
+            los.set_vmr(B.vmr(scene, bayes_set))
+        both = engine.limb_rays_state_bands(coeffs, los, scene.grid, scene.bands_nm, scene.widths_nm, par_gas=B.par_gas,
+                                            par_w=B.par_w, ray_blocks=True, **band_args)
+        rows = both if with_fov else both[1::3]
+        return rows[:, 0, :], rows[:, 1:, :]
+
     try:
-        for num_it in range(max_it):
-            coeffs = scene.coefficient_stack()
-            if num_it:
-                los.set_vmr(B.vmr(scene, bayes_set))
-            both = engine.limb_rays_state_bands(coeffs, los, scene.grid, scene.bands_nm, scene.widths_nm, par_gas=B.par_gas,
-                                                par_w=B.par_w, ray_blocks=True, **band_args)
-            rows = both if with_fov else both[1::3]
-            low, dlow = rows[:, 0, :], rows[:, 1:, :]
-            for par in bayes_set.params():
-                par.set_used()
-            sim_vec = low.reshape(-1) if masktot is None else low.reshape(-1)[masktot]
-            chi = np.sum(((obs_vec - sim_vec) / noi_vec) ** 2) / (len(obs_vec) - bayes_set.n_used_par())   # chicalc
-            bayes_set.history.append(chi)
-            why = smm.retrieval_converged(chi, chi_old, chi_threshold)
-            if why:
-                bayes_set.stop = why
-                break
-            chi_old = chi
-            K = np.transpose(dlow, (1, 0, 2)).reshape(n_tot, -1)
-            K = (K if masktot is None else K[:, masktot]).T
-            bayes_set.jacobian = K
-            smm.inversion_algebra_arrays(K, obs_vec, sim_vec, noi_vec, bayes_set, lambda_LM=lambda_LM, L1_reg=L1_reg, Sa_inv=Sa_inv)
-            into_gases()
+        chi, low, dlow = _array_loop(ob, forward, into_gases, chi_threshold, max_it, lambda_LM, L1_reg)
     finally:
         los.close()
-    return chi, obs, finish(low, dlow), bayes_set
+    return chi, ob.obs, ob.finish(low, dlow, _Grid(scene.bands_nm)), bayes_set
 
 
 def simulate_boxes(scene, bayes_set, pixels, fov_closed_form=True):
     """The band spectra [n_pix, n_bands] of `pixels` (BoxPixel, in the order given) for the BayesSet's current values: the
     forward model of inversion_boxes alone -- twin observations, finite differences."""
-    with_fov = sum(pix.fov_half > 0 for pix in pixels)
-    if not (with_fov == 0 or (with_fov == len(pixels) and fov_closed_form)):
-        raise ValueError("simulate_boxes needs the closed-form field of view for every pixel, or for none")
-    B = box_batch(scene, bayes_set, pixels)
-    L3 = B.L3
-    los = engine.LimbLOS(L3["seg_off"], L3["seg_layer"], L3["pt_off"], L3["x"], L3["nd"], B.vmr(scene, bayes_set),
-                         col_scale=[g.iso_ratio for g in scene.gases])
+    with_fov = _closed_form_fov(pixels, fov_closed_form, "simulate_boxes")
+    los = box_batch(scene, bayes_set, pixels).los(scene, bayes_set)
     try:
         rad = engine.limb_rays(scene.coefficient_stack(), los, resident=False)
         low = engine.hires_to_lowres(rad, scene.grid, scene.bands_nm, scene.widths_nm, out_units=scene.out_units, ils=_ils(scene))
@@ -1436,9 +1405,7 @@ def inversion(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM
     for name in bayes_set.sets.keys():                                                    # :2445-2446
         scene.gas(name).add_clim(bayes_set.sets[name].profile())
     coeffs = lut_coefficients(scene, **LUTopt) if useLUTs else scene.coefficients()
-    obs = [pix.observation for pix in pixels]
-    masks = None if all(pix.mask is None for pix in pixels) else [pix.mask for pix in pixels]
-    noise = [pix.noise for pix in pixels]
+    obs, noise, masks = _observed(pixels)
     bayes_set.history, bayes_set.stop = [], 'max_it'
     sims = [None] * len(pixels)
     chi_old = None
