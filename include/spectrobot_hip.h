@@ -936,6 +936,46 @@ int sr_abs_table_layers_dev(sr_abs_table *h, int n_rows, const double *temps, co
                             int source, int accumulate, double *abs_out, double *emi_out, double *dabs_out, double *demi_out,
                             void *stream);
 
+/* Single-scattering solar source of coefficient rows: sunlight, attenuated on its way in, scattered once into the line of
+ * sight, as an emission coefficient like any other.  The build's own definition (the reference has no counterpart;
+ * DESIGN.md).  For output row r (a layer of a 1-D scene or a LOS step of a 3-D batch) and grid point j:
+ *   tau[r][j] = sum_{k < n_k} u[r][k] tab_abs[k][j]          n_k = n_gas n_layers, k = g n_layers + l
+ *   S[r][j]   = w[r] sun[j] exp(-tau[r][j])                  exactly 0 where w[r] == 0 or tau >= 700
+ *   emi_out[r][j] (+)= sca_abs[src_row[r]][j] S[r][j]
+ * u[r][k] >= 0: the slant column of gas g in layer l along the straight ray from the row's point towards the sun (dense,
+ * mostly zeros, read as it is); w[r] = albedo x phase function / 4 pi, 0 for a row in shadow: its optical depth is not
+ * evaluated, its output an exact 0, and with accumulate != 0 the row of emi_out is left untouched.  tab_abs DEVICE
+ * [n_k][n_pts] (the stacked absorption rows of the scene), sca_abs DEVICE [n_src][n_pts] (the scatterer's own absorption
+ * rows), sun DEVICE [n_pts] (the solar irradiance on the grid, in units consistent with the scene's emission rows), emi_out
+ * DEVICE [n_rows][n_pts]; trans_out DEVICE [n_rows][n_pts] or NULL: exp(-tau) itself, 1 for a row without columns, 0 in
+ * shadow and where tau >= 700.  accumulate != 0 adds to emi_out.  Every Jacobian of the library treats these rows as
+ * coefficients: the solar attenuation is held fixed under d / d(VMR, T, Tvib) within one linearisation.
+ * The descriptor's arrays are HOST arrays, staged through the calling thread's pinned ring (no stream is made) with the
+ * lists of the chunks of four k in which any lit row of a tile of 16 rows has a column; chunks that are not listed
+ * would only have added exact zeros, so the result does not depend on the lists (sr_set_solar_full_lists(1) lists every
+ * chunk on the calling thread until it is set back: the check of that, not a mode of use).  One fused fp64 kernel (v_mfma_f64_16x16x4 + the exponential) on `stream`; one writer per element, no
+ * atomics, the same call gives the same bits.  Every argument is checked before the first copy or launch and a refused
+ * call leaves the outputs untouched: SR_ERR_ARG for a NULL desc, u, w, src_row, tab_abs, sca_abs, sun or emi_out,
+ * n_rows <= 0, n_k <= 0, n_src <= 0, n_pts <= 0, a u or w that is negative or not finite, a src_row outside
+ * 0 .. n_src - 1; SR_ERR_LIMIT for n_rows > SR_MAX_ABS_ROWS, n_rows n_k > SR_MAX_SOLAR_VALUES (the staged tile of u:
+ * 64 MiB of pinned memory per slot of the ring) or n_pts > 2000000.  The ring has four slots that grow and are kept: a
+ * thread that made calls of the largest size retains up to 256 MiB of pinned host memory and as much device memory.
+ * sr_solar_chunk_lists: the lists alone, on the host (no GPU): tile_off HOST [ceil(n_rows / 16) + 1], chunks HOST
+ * [ceil(n_rows / 16) ceil(n_k / 4)] (room for every chunk), *n_listed the number listed; the descriptor's checks
+ * without src_row's range.  Checked against an extended-precision reference (tests/test_gpu_solar_source.py). */
+#define SR_MAX_SOLAR_VALUES 8388608 /* 2^23 */
+typedef struct {
+  int32_t n_rows;
+  const double *u;        /* [n_rows][n_k] */
+  const double *w;        /* [n_rows] */
+  const int32_t *src_row; /* [n_rows] */
+} sr_solar_desc;
+int sr_set_solar_full_lists(int on);
+int sr_solar_chunk_lists(const sr_solar_desc *desc, int n_k, int32_t *tile_off, int32_t *chunks, int32_t *n_listed);
+int sr_solar_source_rows_dev(const sr_solar_desc *desc, const double *tab_abs, int n_k, const double *sca_abs, int n_src,
+                             const double *sun, int64_t n_pts, int accumulate, double *emi_out, double *trans_out,
+                             void *stream);
+
 /* Evaluation mode of the coefficient op.  Far region-1 wings by local Taylor expansions per box of grid
  * points (truncation <= sr_far_field_truncation_bound() of a line's own contribution: 1.6e-11 as built by default, degree
  * 19; 2.6e-13 with -DSR_KFD=22; a box takes a line from sr_far_field_min_distance() on), near field exact, with the expansions built

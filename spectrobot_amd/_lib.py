@@ -20,6 +20,7 @@ IMXSIG = 13010
 SR_STRENGTH_EINSTEIN, SR_STRENGTH_HITRAN = 0, 1
 SR_MAX_ILS_TAB = 65536
 SR_MAX_ABS_SETS, SR_MAX_ABS_VALUES, SR_MAX_ABS_ROWS = 4096, 1 << 27, 65536
+SR_MAX_SOLAR_VALUES = 1 << 23
 
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int32)
@@ -77,6 +78,10 @@ class LevelGasDesc(C.Structure):
 
 class LosPath(C.Structure):
     _fields_ = [("alt", dp), ("dx_dz", dp), ("dalt_dz", dp)]
+
+
+class SolarDesc(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("u", dp), ("w", dp), ("src_row", ip)]
 
 
 class IlsDesc(C.Structure):
@@ -208,6 +213,10 @@ SYMBOLS = {
     "sr_abs_table_layers_dev": (C.c_int, [C.c_void_p, C.c_int, dp, dp, ip, dp, dp, C.c_double, C.c_double, C.c_int64,
                                           C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "sr_set_solar_full_lists": (C.c_int, [C.c_int]),
+    "sr_solar_chunk_lists": (C.c_int, [C.POINTER(SolarDesc), C.c_int, ip, ip, ip]),
+    "sr_solar_source_rows_dev": (C.c_int, [C.POINTER(SolarDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_set_points_per_lane": (C.c_int, [C.c_int]),
     "sr_set_band_fusion": (C.c_int, [C.c_int]),
     "sr_far_field_truncation_bound": (C.c_double, []),

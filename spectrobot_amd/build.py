@@ -6,9 +6,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libspectrobot_hip.so")
-SOURCES = ["sr_api.hip", "sr_kernels.hip", "sr_limb_many.hip"]
+SOURCES = ["sr_api.hip", "sr_kernels.hip", "sr_limb_many.hip", "sr_solar_source.hip"]
 DEPS = SOURCES + ["sr_device.hpp", "sr_kernels.hpp", "sr_constants.hpp", "sr_limb_plan.hpp", "sr_limb_common.hpp",
                   "sr_limb_state.inc", "sr_limb_state_launch.inc", "sr_limb_forward.inc", "sr_lowres_weights_tab.inc", "sr_absorber_table.inc",
+                  "sr_solar_source.inc", "sr_solar_plan.hpp",
                   "tips2003_tables.inc", "../../include/spectrobot_hip.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

@@ -24,6 +24,7 @@
 
 #include "../../include/spectrobot_hip.h"
 #include "sr_kernels.hpp"
+#include "sr_solar_plan.hpp"
 #include "tips2003_tables.inc"
 
 using namespace sr;
@@ -4106,6 +4107,57 @@ int sr_abs_table_layers_dev(sr_abs_table *h, int n_rows, const double *temps, co
   rc = pk.slot().mark(st);
   if (rc) return rc;
   return scope.leave();
+}
+
+// The single-scattering solar source of coefficient rows (sr_solar_source.hip).  One check of the descriptor for both
+// entries: everything the kernel would index with or multiply by is looked at before the first copy or launch.
+static thread_local int g_solar_full_lists = 0; // sr_set_solar_full_lists: every chunk listed (a check)
+int sr_set_solar_full_lists(int on) {
+  g_solar_full_lists = on != 0;
+  return SR_OK;
+}
+
+static int check_solar_desc(const sr_solar_desc *d, int n_k, int n_src, std::vector<int> *tile_off, std::vector<int> *chunks) {
+  if (!d || !d->u || !d->w || !d->src_row || d->n_rows <= 0 || n_k <= 0) return SR_ERR_ARG;
+  if (d->n_rows > SR_MAX_ABS_ROWS || (int64_t)d->n_rows * n_k > SR_MAX_SOLAR_VALUES) return SR_ERR_LIMIT;
+  for (int r = 0; r < d->n_rows; ++r) {
+    if (!(d->w[r] >= 0.0) || !std::isfinite(d->w[r])) return SR_ERR_ARG;
+    if (n_src >= 0 && (d->src_row[r] < 0 || d->src_row[r] >= n_src)) return SR_ERR_ARG; // would read out of sca_abs
+  }
+  // u is walked once: its check and the chunk lists together (it is the one large array of a call)
+  return solar_chunk_lists(d->u, d->w, d->n_rows, n_k, g_solar_full_lists != 0, *tile_off, *chunks) ? SR_OK : SR_ERR_ARG;
+}
+
+int sr_solar_chunk_lists(const sr_solar_desc *desc, int n_k, int32_t *tile_off, int32_t *chunks, int32_t *n_listed) {
+  if (!tile_off || !chunks || !n_listed) return SR_ERR_ARG;
+  std::vector<int> off, ch;
+  const int rc = check_solar_desc(desc, n_k, -1, &off, &ch);
+  if (rc) return rc;
+  std::copy(off.begin(), off.end(), tile_off);
+  std::copy(ch.begin(), ch.end(), chunks);
+  *n_listed = (int32_t)ch.size();
+  return SR_OK;
+}
+
+int sr_solar_source_rows_dev(const sr_solar_desc *desc, const double *tab_abs, int n_k, const double *sca_abs, int n_src,
+                             const double *sun, int64_t n_pts, int accumulate, double *emi_out, double *trans_out, void *stream) {
+  if (!tab_abs || !sca_abs || !sun || !emi_out || n_src <= 0 || n_pts <= 0) return SR_ERR_ARG;
+  if (n_pts > 2000000) return SR_ERR_LIMIT;
+  std::vector<int> tile_off, chunks;
+  int rc = check_solar_desc(desc, n_k, n_src, &tile_off, &chunks);
+  if (rc) return rc;
+  const int n_rows = desc->n_rows;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_u = pk.copy(desc->u, (size_t)n_rows * n_k), p_w = pk.copy(desc->w, (size_t)n_rows);
+  const auto p_src = pk.copy(desc->src_row, (size_t)n_rows);
+  const auto p_off = pk.copy(tile_off.data(), tile_off.size()), p_ch = pk.copy(chunks.data(), chunks.size(), 1);
+  rc = pk.stage(st);
+  if (rc) return rc;
+  LAUNCHCHK(launch_solar_source(tab_abs, n_k, (int)n_pts, pk.dev(p_u), pk.dev(p_w), pk.dev(p_src), n_rows, pk.dev(p_off),
+                                pk.dev(p_ch), sca_abs, sun, accumulate != 0, emi_out, trans_out, st));
+  return pk.slot().mark(st);
 }
 
 // ------------------------------------------------------------------------

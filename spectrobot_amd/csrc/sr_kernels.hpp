@@ -461,5 +461,11 @@ int launch_absorber_table(int n_used, const double *set_v0, const double *set_dv
                           const double *values, int row0, int row1, const double *temps, const double *scale, const int *slot2,
                           const double *w2, const double *dw2, double w0, double gstep, int g_lo, int n_pts, bool source,
                           bool accumulate, double *abs_out, double *emi_out, double *dabs_out, double *demi_out, hipStream_t st);
+// The single-scattering solar source of coefficient rows (sr_solar_source_rows_dev; sr_solar_source.hip, a unit of its
+// own).  tab_abs [n_k][n_pts], u [n_rows][n_k], w / src_row [n_rows], tile_off / chunks: solar_chunk_lists
+// (sr_solar_plan.hpp), sca_abs [n_src][n_pts], sun [n_pts]: device arrays; trans_out may be null.
+int launch_solar_source(const double *tab_abs, int n_k, int n_pts, const double *u, const double *w, const int *src_row,
+                        int n_rows, const int *tile_off, const int *chunks, const double *sca_abs, const double *sun,
+                        bool accumulate, double *emi_out, double *trans_out, hipStream_t st);
 
 } // namespace sr

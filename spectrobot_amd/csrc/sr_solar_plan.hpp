@@ -1,0 +1,51 @@
+// sr_solar_plan.hpp -- the host plan of sr_solar_source_kernel (sr_solar_source.inc) as a plain function: per tile of
+// kSolarRows rows the chunks of kSolarChunk consecutive k in which any LIT row of the tile (w != 0) has a non-zero
+// column, in ascending order.  Included by sr_api.hip and by the host build tools/solar_source_host; no HIP header.
+// U is read as it is: nothing is sorted, nothing is changed.  full: every chunk of every tile is listed (the check
+// that the result does not depend on the lists: a chunk that is not listed would only have added exact zeros).
+#pragma once
+#include <cstddef>
+#include <vector>
+
+namespace sr {
+
+constexpr int kSolarRows = 16; // rows of a tile: the MFMA's M
+constexpr int kSolarChunk = 4; // k per chunk: the MFMA's K
+
+// tile_off [n_tiles + 1] into chunks; n_tiles = ceil(n_rows / kSolarRows), chunk c covers k = 4 c .. 4 c + 3 (< n_k).
+// Returns false if an element of u is negative or not finite (the entry's check, in the same walk: u is the one large
+// array of a call and is read once); the lists are then unspecified.
+inline bool solar_chunk_lists(const double *u, const double *w, int n_rows, int n_k, bool full, std::vector<int> &tile_off,
+                              std::vector<int> &chunks) {
+  const int n_tiles = (n_rows + kSolarRows - 1) / kSolarRows, n_chunks = (n_k + kSolarChunk - 1) / kSolarChunk;
+  const int n_whole = n_k / kSolarChunk; // chunks with all four k
+  tile_off.assign(1, 0);
+  chunks.clear();
+  std::vector<char> hit((size_t)n_chunks);
+  bool ok = true;
+  for (int t = 0; t < n_tiles; ++t) {
+    hit.assign((size_t)n_chunks, full ? 1 : 0);
+    const int r1 = n_rows < (t + 1) * kSolarRows ? n_rows : (t + 1) * kSolarRows;
+    for (int r = t * kSolarRows; r < r1; ++r) {
+      const char lit = w[r] != 0.0; // in shadow: the row's optical depth is not evaluated, its columns list nothing
+      const double *ur = u + (size_t)r * n_k;
+      for (int c = 0; c < n_whole; ++c) {
+        const double *v = ur + kSolarChunk * c;
+        // (a NaN fails v >= 0, an infinity v <= max)
+        ok &= (v[0] >= 0.0) & (v[1] >= 0.0) & (v[2] >= 0.0) & (v[3] >= 0.0) & (v[0] <= 1.7976931348623157e308) &
+              (v[1] <= 1.7976931348623157e308) & (v[2] <= 1.7976931348623157e308) & (v[3] <= 1.7976931348623157e308);
+        hit[(size_t)c] |= lit & (char)((v[0] != 0.0) | (v[1] != 0.0) | (v[2] != 0.0) | (v[3] != 0.0));
+      }
+      for (int k = kSolarChunk * n_whole; k < n_k; ++k) {
+        ok &= (ur[k] >= 0.0) & (ur[k] <= 1.7976931348623157e308);
+        hit[(size_t)n_whole] |= lit & (char)(ur[k] != 0.0);
+      }
+    }
+    for (int c = 0; c < n_chunks; ++c)
+      if (hit[(size_t)c]) chunks.push_back(c);
+    tile_off.push_back((int)chunks.size());
+  }
+  return ok;
+}
+
+} // namespace sr

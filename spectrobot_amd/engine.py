@@ -569,6 +569,81 @@ class AbsorberTable(object):
         return ((outs[0], outs[1]), (outs[2], outs[3])) if derivative else (outs[0], outs[1])
 
 
+def _solar_desc(U, w, src_row):
+    """(sr_solar_desc, n_k, the arrays it points to) of U [n_rows, n_k] or [n_rows, n_gas, n_layers], w, src_row."""
+    U = np.asarray(U, dtype=np.float64)
+    if U.ndim not in (2, 3):
+        raise ValueError("U must be [n_rows, n_k] or [n_rows, n_gas, n_layers]")
+    u, up = _d(U.reshape(U.shape[0], -1))
+    n_rows, n_k = u.shape
+    wa, wp = _d(np.broadcast_to(np.asarray(w, dtype=np.float64), (n_rows,)))
+    sa, sp = _i(np.arange(n_rows) if src_row is None else src_row)
+    if sa.shape != (n_rows,):
+        raise ValueError("src_row must be [n_rows]")
+    d = _lib.SolarDesc()
+    d.n_rows, d.u, d.w, d.src_row = n_rows, up, wp, sp
+    return d, n_k, (u, wa, sa)
+
+
+def set_solar_full_lists(on):
+    """A check, not a mode of use: True makes solar_source (and solar_chunk_lists) list EVERY chunk of k on this thread
+    until it is set back (sr_set_solar_full_lists) -- the chunks the lists skip only add exact zeros, so the result must
+    come out bit for bit the same."""
+    check(lib.sr_set_solar_full_lists(int(bool(on))), "sr_set_solar_full_lists")
+
+
+def solar_chunk_lists(U, w):
+    """(tile_off [n_tiles + 1], chunks) the solar-source kernel walks (sr_solar_chunk_lists, on the host: no GPU): per
+    tile of 16 rows the chunks of four k in which any lit row (w != 0) of the tile has a non-zero column."""
+    d, n_k, keep = _solar_desc(U, w, None)
+    n_tiles, n_chunks = (d.n_rows + 15) // 16, (n_k + 3) // 4
+    off, ch, n = np.zeros(n_tiles + 1, np.int32), np.zeros(max(n_tiles * n_chunks, 1), np.int32), C.c_int32(0)
+    check(lib.sr_solar_chunk_lists(C.byref(d), n_k, off.ctypes.data_as(ip), ch.ctypes.data_as(ip), C.byref(n)),
+          "sr_solar_chunk_lists")
+    return off, ch[:n.value].copy()
+
+
+def solar_source(A, U, w, sca, sun, src_row=None, out=None, accumulate=False, transmission=False):
+    """The single-scattering solar source of coefficient rows (sr_solar_source_rows_dev; the build's own definition,
+    DESIGN.md): sunlight, attenuated on its way in, scattered once into the line of sight, as emission rows
+
+        tau[r] = sum_k U[r, k] A[k],   S[r] = w[r] sun exp(-tau[r]),   emi[r] (+)= sca[src_row[r]] S[r]
+
+    A: the stacked absorption rows of the scene, CUDA [n_gas, n_layers, n_pts] (the first tensor of gas_stack) or
+    [n_k, n_pts]; U: host [n_rows, n_gas, n_layers] or [n_rows, n_k], the slant columns towards the sun
+    (geometry.solar_columns), >= 0, dense and mostly zeros; w: host [n_rows] = albedo x phase function / 4 pi, 0 for a row
+    in shadow (exact 0 out, its optical depth not evaluated; under accumulate the row is left untouched); sca: CUDA
+    [n_src, n_pts], the scatterer's own absorption rows; sun: CUDA [n_pts], the solar irradiance on the grid in units
+    consistent with the emission rows; src_row [n_rows] (None: row r of sca).  out: CUDA [n_rows, n_pts], required with
+    accumulate=True (thermal + solar).  transmission=True: also exp(-tau) itself [n_rows, n_pts] (1 for a row without
+    columns, 0 in shadow and where tau >= 700).  One fused fp64 kernel; the same call gives the same bits.
+
+    Every Jacobian treats the rows as coefficients: the solar attenuation is HELD FIXED under d / d(VMR, T, Tvib) within
+    one linearisation (as TempProfile holds columns and pressure fixed); the derivative through tau is not built.
+    Returns emi, or (emi, trans)."""
+    d, n_k, keep = _solar_desc(U, w, src_row)
+    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    if not (ok(A) and ok(sca) and ok(sun)) or A.dim() not in (2, 3) or sca.dim() != 2 or sun.dim() != 1:
+        raise ValueError("A, sca and sun must be contiguous CUDA float64 tensors ([n_k or n_gas, n_layers, n_pts], [n_src, n_pts], [n_pts])")
+    n_pts = A.shape[-1]
+    if A.numel() != n_k * n_pts:
+        raise ValueError("U has %d columns per row, A %d rows" % (n_k, A.numel() // max(n_pts, 1)))
+    if sca.shape[1] != n_pts or sun.shape[0] != n_pts:
+        raise ValueError("sca and sun must have A's %d grid points" % n_pts)
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True adds to out=...")
+        out = torch.empty((d.n_rows, n_pts), dtype=torch.float64, device="cuda")
+    elif not ok(out) or out.shape != (d.n_rows, n_pts):
+        raise ValueError("out must be a contiguous CUDA float64 [n_rows, n_pts]")
+    trans = torch.empty((d.n_rows, n_pts), dtype=torch.float64, device="cuda") if transmission else None
+    check(lib.sr_solar_source_rows_dev(C.byref(d), C.c_void_p(A.data_ptr()), n_k, C.c_void_p(sca.data_ptr()), int(sca.shape[0]),
+                                       C.c_void_p(sun.data_ptr()), n_pts, int(bool(accumulate)), C.c_void_p(out.data_ptr()),
+                                       C.c_void_p(trans.data_ptr()) if transmission else None, _stream_ptr()),
+          "sr_solar_source_rows_dev")
+    return (out, trans) if transmission else out
+
+
 def lut_interp(table, idx4, wgt4, pops=None, out=None):
     """LutSet.calculate for n_steps LOS steps on a G table resident in HBM (sr_lut_interp_dev).
     table: CUDA [3, n_PT, n_grid]; idx4 [n_steps, 4] rows, wgt4 [n_steps, 4] = (wP1, wP2, wT1, wT2).

@@ -42,7 +42,11 @@ def _profiles(z, nd_levels, vmr_levels):
 def _limb_crossings(zz, zt, R):
     """Shell crossings of one limb ray in photon order (far side -> tangent point -> observer): shell index k and the
     path coordinates (km from the tangent point, negative on the far side) of its two ends."""
-    rt = R + zt
+    return _crossings_at_radius(zz, R + zt, R)
+
+
+def _crossings_at_radius(zz, rt, R):
+    """_limb_crossings of the ray with the tangent RADIUS rt (solar_columns: a ray given by its impact parameter)."""
     lo, hi = R + zz[:-1], R + zz[1:]
     k = np.nonzero(hi > rt)[0]
     s_hi = np.sqrt(hi[k] * hi[k] - rt * rt)
@@ -394,3 +398,94 @@ def calc_radtran_steps(z, temps, press, nd_levels, vmr_levels, z_tans, R=TITAN_R
                 r["k"], r["a"], r["b"] = r["k"][rep], a2, b2
             L = assemble()
     return L
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the sun's ray: slant columns of the single-scattering solar source (engine.solar_source)
+# ----------------------------------------------------------------------------------------------------------------------
+def _device_columns(L, col_scale):
+    """[n_gas, n_seg] Curtis-Godson columns of a LOS dict by the engine's own routine (engine.LimbLOS.columns: on the
+    device) -- what a line of sight through the same segments gets."""
+    from . import engine
+    return engine.LimbLOS(L["seg_off"], L["seg_layer"], L["pt_off"], L["x"], L["nd"], L["vmr"], col_scale=col_scale).columns()
+
+
+def solar_columns(z, nd_levels, vmr_levels, alt, mu, R=TITAN_RADIUS_KM, n_sub=3, col_scale=None):
+    """Slant columns towards the sun: U [n_rows, n_gas, n_layers] (molecules cm^-2 of gas g in the shell above level l)
+    along the straight ray from the point at altitude alt[r] (km) that sees the sun at mu[r] = cos SZA, and lit [n_rows].
+    The ray has the impact parameter b = (R + alt) sqrt(1 - mu^2); on the limb ray with that tangent radius the point
+    sits at the path coordinate s_p = (R + alt) mu and the sun at + infinity, so the sun's ray is that limb ray from
+    s_p on (_limb_crossings' own arithmetic, the first crossing cut at s_p):
+
+      mu >= 0   outward through the rest of the point's shell and every shell above;
+      mu <  0   down to the tangent radius b and out again: the shells between b and the point are crossed on both
+                sides of the tangent point, the part of the point's own shell below it once per crossing;
+      mu <  0 and b < R + z[0]   the ray passes below the lowest level: in shadow, lit = False and a row of zeros.
+
+    Every crossing carries n_sub + 1 sample points with limb_los's profiles (_sample, _profiles) and its column is the
+    engine's Curtis-Godson column with col_scale -- what a line of sight through the same chord gets; the columns of a
+    shell's crossings are added.  No refraction.  A point above the top boundary has an empty, lit row."""
+    return _solar_columns(z, nd_levels, vmr_levels, alt, mu, R, n_sub, col_scale, _device_columns)
+
+
+def _solar_columns(z, nd_levels, vmr_levels, alt, mu, R, n_sub, col_scale, columns):
+    """solar_columns with the column routine given: columns(L, col_scale) -> [n_gas, n_seg], L limb_los's dict of the rays'
+    crossings (the host tests pass a plain routine, the same on both sides of their comparisons)."""
+    z, zz, ln, vv = _profiles(z, nd_levels, vmr_levels)
+    alt = np.atleast_1d(np.asarray(alt, float))
+    mu = np.broadcast_to(np.asarray(mu, float), alt.shape)
+    if np.any(np.abs(mu) > 1.0):
+        raise ValueError("mu = cos SZA must lie in [-1, 1]")
+    n_rows, n_gas, n_layers = alt.size, vv.shape[0], len(z)
+    U = np.zeros((n_rows, n_gas, n_layers))
+    lit = np.ones(n_rows, bool)
+    seg_off, lay, xs, alts = [0], [], [], []
+    for r_alt, m in zip(alt, mu):
+        rp = R + r_alt
+        b = rp * np.sqrt((1.0 - m) * (1.0 + m))
+        if m < 0.0 and b < R + z[0]:
+            lit[len(seg_off) - 1] = False
+            seg_off.append(seg_off[-1])
+            continue
+        k, a, e = _crossings_at_radius(zz, b, R)
+        s_p = rp * m
+        keep = e - s_p > 1e-12 * rp      # (a point ON a level: the crossing that ends there, to rounding, is not begun)
+        k, a, e = k[keep], np.maximum(a[keep], s_p), e[keep]
+        s = _sample(a, e, n_sub)
+        lay.append(k)
+        xs.append(s.ravel())
+        alts.append((np.sqrt(s * s + b * b) - R).ravel())
+        seg_off.append(seg_off[-1] + len(k))
+    n_seg = seg_off[-1]
+    if n_seg == 0:
+        return U, lit
+    al = np.clip(np.concatenate(alts), z[0], zz[-1])
+    L = dict(seg_off=np.array(seg_off, np.int32), seg_layer=np.concatenate(lay).astype(np.int32),
+             pt_off=(np.arange(n_seg + 1) * (n_sub + 1)).astype(np.int32), x=np.concatenate(xs) * 1e5,
+             nd=np.exp(np.interp(al, zz, ln)), vmr=np.array([np.interp(al, zz, v) for v in vv]), alt=al)
+    col = np.asarray(columns(L, col_scale), float)
+    row = np.repeat(np.arange(n_rows), np.diff(L["seg_off"]))
+    for g in range(n_gas):
+        np.add.at(U[:, g, :], (row, L["seg_layer"]), col[g])
+    return U, lit
+
+
+def hg_phase(cos_theta, g):
+    """Henyey-Greenstein phase function P(Theta) = (1 - g^2) / (1 + g^2 - 2 g cos Theta)^(3/2), normalised so that its
+    mean over the sphere is 1 (int P dOmega = 4 pi); g: the asymmetry parameter, |g| < 1."""
+    g = float(g)
+    if not abs(g) < 1.0:
+        raise ValueError("the asymmetry parameter must lie in (-1, 1)")
+    c = np.asarray(cos_theta, float)
+    return (1.0 - g * g) / (1.0 + g * g - 2.0 * g * c) ** 1.5
+
+
+def solar_irradiance(grid, t_sun=5772.0, r_sun_km=695700.0, dist_km=9.58 * 1.495978707e8):
+    """The irradiance of a black-body sun on the grid (cm^-1) at the planet: pi B(nu, t_sun) (r_sun / dist)^2, with the
+    Planck function of the limb calls' initial intensity, B = 2 h c^2 nu^3 / (exp(c2 nu / T) - 1) in erg s^-1 cm^-2 sr^-1
+    (cm^-1)^-1 -- the units of the emission rows; the result is per unit area, erg s^-1 cm^-2 (cm^-1)^-1.  Defaults: the
+    sun seen from Saturn's mean distance."""
+    h, c, k = 6.62607015e-34 * 1.e7, 299792458.0 * 1.e2, 1.380649e-23 * 1.e7      # sr_constants.hpp
+    nu = np.asarray(grid, float)
+    B = 2 * h * (c * c) * (nu * nu * nu) / (np.exp((h * c / k) * nu / float(t_sun)) - 1)
+    return np.pi * B * (float(r_sun_km) / float(dist_km)) ** 2

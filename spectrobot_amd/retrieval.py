@@ -18,6 +18,7 @@ levels, gases with VMR profiles, limb pixels with three lines of sight each).  W
 import numpy as np
 
 from . import engine
+from . import geometry
 from . import spect_main_module as smm
 from . import synthetic as syn
 
@@ -134,12 +135,25 @@ class TableGas(Gas):
     radtrans, whose kernels keep four gas slots (engine.max_gases(folded=True)).  accumulate_into=<name of a plain Gas>: the table is
     folded into that line gas's pair instead -- added to its (abs, emi) and, in a temperature retrieval, to its analytic
     row derivatives -- sharing that gas's VMR and iso_ratio; it then has no slot, no VMR and no retrieval set of its
-    own (its vmr and iso_ratio arguments are ignored)."""
+    own (its vmr and iso_ratio arguments are ignored).
 
-    def __init__(self, name, table, vmr, scale=None, source=True, iso_ratio=1.0, accumulate_into=None):
+    solar=dict(albedo=, g=): the gas scatters sunlight once into the line of sight (single-scattering albedo, Henyey-
+    Greenstein asymmetry parameter).  In a LimbScene with a sun its emission rows are thermal + solar: the scene adds
+    sca S to a copy of the thermal pair's emi (engine.solar_source; `thermal` keeps the cached pair).  The solar
+    attenuation is held fixed under every Jacobian within one linearisation; multiple scattering is not built."""
+
+    def __init__(self, name, table, vmr, scale=None, source=True, iso_ratio=1.0, accumulate_into=None, solar=None):
         Gas.__init__(self, name, None, vmr, iso_ratio=iso_ratio)
         self.table, self.scale, self.source, self.accumulate_into = table, scale, bool(source), accumulate_into
         self.dcoeffs, self._key = None, None
+        self.solar, self.thermal = None, None
+        if solar is not None:
+            if accumulate_into is not None:
+                raise ValueError("TableGas %r: solar= needs a gas slot of its own (the scatterer's absorption rows are the "
+                                 "source's sca), accumulate_into=%r gives it none" % (name, accumulate_into))
+            if set(solar) != {"albedo", "g"} or not 0.0 <= float(solar["albedo"]) <= 1.0 or not abs(float(solar["g"])) < 1.0:
+                raise ValueError("solar=dict(albedo=<0 .. 1>, g=<asymmetry parameter, |g| < 1>)")
+            self.solar = dict(albedo=float(solar["albedo"]), g=float(solar["g"]))
 
     def scale_of(self, scene):
         """The scale per layer as an array, or None."""
@@ -165,7 +179,31 @@ class TableGas(Gas):
                                     derivative=derivative, g_lo=g_lo, g_hi=g_hi)
             self.coeffs, self.dcoeffs = res if derivative else (res, None)
             self._key, self.coeffs_shard = key, (g_lo, g_hi)
+            self.thermal = self.coeffs      # (a solar gas: the scene puts (abs, thermal emi + solar rows) into coeffs)
         return self.coeffs
+
+
+class Sun(object):
+    """The sun of a LimbScene: solar zenith angle at the tangent point and phase angle (sun - target - observer), in
+    degrees, and the irradiance at the planet on the scene's grid [n_grid] (geometry.solar_irradiance), in units
+    consistent with the scene's emission rows.  The scattering angle is 180 deg - phase."""
+
+    def __init__(self, sza_deg, phase_deg, irradiance):
+        self.sza_deg, self.phase_deg = float(sza_deg), float(phase_deg)
+        self.irradiance = np.ascontiguousarray(irradiance, dtype=float)
+        if self.irradiance.ndim != 1 or not np.all(np.isfinite(self.irradiance)) or np.any(self.irradiance < 0):
+            raise ValueError("the irradiance is a finite, non-negative array on the scene's grid")
+
+    @property
+    def mu(self):
+        return float(np.cos(np.deg2rad(self.sza_deg)))
+
+    @property
+    def cos_scattering(self):
+        return float(np.cos(np.deg2rad(180.0 - self.phase_deg)))
+
+    def key(self):
+        return (self.sza_deg, self.phase_deg, engine._content_key(self.irradiance))
 
 
 def _refuse_many_slots(scene, who):
@@ -337,10 +375,21 @@ class LimbScene(object):
     """1-D atmosphere on altitude levels z [km] (temps [K], press [hPa]), gases, spectral grid, instrument bands
     (centres / Gaussian sigmas in nm).  ils: an engine.ILS, the bands' tabulated line shape in the Gaussian's place
     (widths_nm then scale its reduced offsets): every band integral of simulate, radtran, inversion_fast_limb, inversion
-    and inversion_state, and BandCalibration's two instrument rows, are taken with it."""
+    and inversion_state, and BandCalibration's two instrument rows, are taken with it.
+    sun: a Sun.  With it, the emission rows of every TableGas(solar=...) are thermal + single-scattered sunlight
+    (coefficients() ends with one solar pass over the layer rows, solar_pass); the tangent-SZA approximation -- the
+    reference's use_tangent_sza = True: mu = cos(sza) on every row -- and Theta = 180 deg - phase.  A per-step SZA is
+    the 3-D route: engine.solar_source on geometry.limb_los_3d's rows."""
 
-    def __init__(self, grid, z, temps, press, gases, bands_nm, widths_nm, R=2575.0, n_sub=3, out_units="Wm2", ils=None):
+    def __init__(self, grid, z, temps, press, gases, bands_nm, widths_nm, R=2575.0, n_sub=3, out_units="Wm2", ils=None,
+                 sun=None):
         self.grid = np.asarray(grid, dtype=float)
+        self.sun = sun
+        self.solar_frozen = False   # True: solar rows that exist are kept whatever moves -- the linearisation's own assumption,
+                                    # for finite differences that are to see what the Jacobians see (a rebuilt thermal pair
+                                    # still gets its solar rows again)
+        if sun is not None and sun.irradiance.shape != self.grid.shape:
+            raise ValueError("the sun's irradiance must be given on the scene's grid")
         self.z, self.temps, self.press = (np.asarray(v, dtype=float) for v in (z, temps, press))
         self.nd = syn.number_density(self.press, self.temps)
         # a TableGas with accumulate_into has no slot: it is folded into a line gas's pair (self.folded)
@@ -367,7 +416,56 @@ class LimbScene(object):
                 g.layer_coefficients(self.temps, self.press, g_lo=g_lo, g_hi=g_hi)
                 continue
             self.gas_coefficients(g, refresh, g_lo, g_hi)
+        self.solar_pass(g_lo, g_hi)
         return [g.coeffs for g in self.gases]
+
+    def solar_gases(self):
+        return [g for g in self.gases if getattr(g, "solar", None) is not None] if self.sun is not None else []
+
+    def solar_key(self, g_lo, g_hi):
+        """What the solar rows depend on, by content: every gas's VMR profile (and iso_ratio), the identity of every
+        gas's absorption table -- temperatures, pressures and vibrational temperatures act through them --, the sun and
+        the shard.  A VMR retrieval moves the first and redoes the solar pass each iteration, and nothing else."""
+        tabs = tuple(id((g.thermal if getattr(g, "solar", None) is not None else g.coeffs)[0]) for g in self.gases)
+        return (tuple(np.asarray(g.vmr, float).tobytes() for g in self.gases), tuple(float(g.iso_ratio) for g in self.gases),
+                tabs, self.sun.key(), int(g_lo), int(g_hi))
+
+    def solar_weights(self, g, lit):
+        """w [n_layers] = albedo P(Theta) / 4 pi of a solar gas, 0 on the rows in shadow."""
+        P = geometry.hg_phase(self.sun.cos_scattering, g.solar["g"])
+        return np.where(lit, g.solar["albedo"] * P / (4.0 * np.pi), 0.0)
+
+    def solar_pass(self, g_lo, g_hi):
+        """The emission rows of the solar gases: thermal + sca S on the layer rows (engine.solar_source under
+        accumulate, on a copy of the cached thermal emi).  The point of a row is the middle of its shell, its columns
+        towards the sun geometry.solar_columns with the scene's VMRs.  Held fixed by every Jacobian within one
+        linearisation.  The attenuation is the 1-D scene's: a gas whose profile a driver keeps per latitude box
+        (inversion_boxes: gas.vmr_boxes) enters it with its 1-D vmr."""
+        solar = self.solar_gases()
+        if not solar:
+            return
+        import torch
+        done = all(g.coeffs is not g.thermal for g in solar)
+        if done and self.solar_frozen:
+            return
+        key = self.solar_key(g_lo, g_hi)
+        if done and getattr(self, "_solar_key", None) == key:
+            return
+        top = self.z[-1] + (self.z[-1] - self.z[-2])
+        zz = np.append(self.z, top)
+        U, lit = geometry.solar_columns(self.z, self.nd, [g.vmr for g in self.gases], 0.5 * (zz[:-1] + zz[1:]), self.sun.mu, R=self.R,
+                                   n_sub=self.n_sub, col_scale=[g.iso_ratio for g in self.gases])
+        tabs = [(g.thermal if g in solar else g.coeffs)[0] for g in self.gases]
+        A = torch.stack(tabs).contiguous()
+        sun = torch.as_tensor(self.sun.irradiance[g_lo:g_hi], device="cuda").contiguous()
+        for g in solar:
+            emi = g.thermal[1].clone()
+            engine.solar_source(A, U, self.solar_weights(g, lit), g.thermal[0], sun, out=emi, accumulate=True)
+            g.coeffs = (g.thermal[0], emi)
+        # (the tables themselves are kept beside the key: an id in it stays theirs while they live here.  The key knows a
+        # table by identity, as coefficient_stack does: every rebuild in this package makes new tensors; a caller who
+        # overwrites a table IN PLACE sets scene._solar_key = None)
+        self._solar_key, self._solar_tabs = key, tabs
 
     def folded_into(self, g):
         return [t for t in self.folded if t.accumulate_into == g.name]
@@ -546,6 +644,7 @@ class LimbScene(object):
                 for t in self.folded_into(g):
                     t.table.layers(self.temps, self.grid, press=self.press, scale=t.scale_of(self), source=t.source,
                                    derivative=True, out=(g.coeffs, g.dcoeffs), accumulate=True)
+        self.solar_pass(0, n_grid)      # (the solar rows are held fixed under d / dT: dcoeffs stay the thermal pair's)
         return [g.coeffs for g in self.gases], [g.dcoeffs for g in self.gases]
 
 
@@ -972,7 +1071,9 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
         oe = engine.OeProblem(obs_all, noi_all, ob.masktot, ob.Sa_inv, bayes_set.apriori_vector(), lambda_LM)
         assert obs_all.size == n_pb
         alts_all = [a for pix in pixels for a in pix.los_alts()]
-    if one_step and LOOP_IN_ONE_CALL and not refresh and max_it > 0:
+    # (a sunlit scene's coefficient rows do not stay fixed: the solar attenuation follows the VMRs, and the solar pass is
+    # redone between the iterations -- the loop below, one engine.retrieval_step and one coefficient_stack() per iteration)
+    if one_step and LOOP_IN_ONE_CALL and not refresh and max_it > 0 and not scene.solar_gases():
         # The loop in ONE library call (sr_retrieval_loop_dev): iterations, stopping rule and the updates with their
         # positivity rule run in the library; the objects' bookkeeping is replayed here from the vectors it returns.
         coeffs = scene.coefficient_stack(refresh=False)
@@ -1410,6 +1511,8 @@ def inversion(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM
     sims = [None] * len(pixels)
     chi_old = None
     for num_it in range(max_it):
+        if not useLUTs and scene.solar_gases():     # the solar attenuation follows the VMRs: the solar pass again (nothing else is rebuilt)
+            coeffs = scene.coefficients()
         for num, pix in enumerate(pixels):                                                 # :2487
             los, alt = scene.los(pix.los_alts())                                           # low_LOS, LOS, up_LOS
             par_gas, par_w = scene.profile_weights(bayes_set, alt)
