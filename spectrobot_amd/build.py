@@ -6,11 +6,20 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libspectrobot_hip.so")
-SOURCES = ["sr_api.hip", "sr_kernels.hip", "sr_limb_many.hip", "sr_solar_source.hip"]
-DEPS = SOURCES + ["sr_device.hpp", "sr_kernels.hpp", "sr_constants.hpp", "sr_limb_plan.hpp", "sr_limb_common.hpp",
-                  "sr_limb_state.inc", "sr_limb_state_launch.inc", "sr_limb_forward.inc", "sr_lowres_weights_tab.inc", "sr_absorber_table.inc",
-                  "sr_solar_source.inc", "sr_solar_plan.hpp",
-                  "tips2003_tables.inc", "../../include/spectrobot_hip.h"]
+# the translation units: the host API, the coefficient op, the limb family, the state kernel's instances in units by
+# (gas counts, slots per block), the instances of five to eight gases, the small operators, the solar source
+SOURCES = ["sr_api.hip", "sr_kernels.hip", "sr_limb.hip", "sr_limb_state_12_np8.hip", "sr_limb_state_12_np16.hip",
+           "sr_limb_state_34_np8.hip", "sr_limb_state_34_np16.hip", "sr_limb_many.hip", "sr_ops.hip", "sr_solar_source.hip"]
+MAX_JOBS = 16  # compiles running at a time
+PUBLIC_HEADER = os.path.join(HERE, "..", "include", "spectrobot_hip.h")
+
+
+def deps():
+    """Everything a unit may include: every .hip, .hpp and .inc under csrc/, and the public header."""
+    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))
+            if f.endswith((".hip", ".hpp", ".inc"))] + [PUBLIC_HEADER]
+
+
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-fgpu-rdc" if False else "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
@@ -20,7 +29,7 @@ def up_to_date():
     if not os.path.exists(OUT):
         return False
     t = os.path.getmtime(OUT)
-    return all(os.path.getmtime(os.path.join(CSRC, d)) <= t for d in DEPS) and \
+    return all(os.path.getmtime(d) <= t for d in deps()) and \
         os.path.getmtime(os.path.abspath(__file__)) <= t
 
 
@@ -36,8 +45,10 @@ def build(force=False, verbose=False, extra=(), out=None):
 
 
 def _compile(OUT, verbose, extra):
-    """The translation units side by side (the build takes as long as the slowest of them, sr_kernels.hip), then one
-    link; objects in a directory of their own beside the library, removed afterwards."""
+    """The translation units side by side, at most MAX_JOBS running at a time (the build takes as long as the slowest of
+    them: the widest state unit and sr_limb_many.hip are about level, the coefficient op a third of them), then one link;
+    objects in a directory of their own beside the library, removed afterwards."""
+    from concurrent.futures import ThreadPoolExecutor
     import shutil
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     tmp = "%s.tmp.%d" % (OUT, os.getpid())  # other processes never see a half-written library
@@ -50,8 +61,8 @@ def _compile(OUT, verbose, extra):
         for c in cmds + [link]:
             print(" ".join(c).replace(tmp, OUT))
     try:
-        procs = [subprocess.Popen(c) for c in cmds]
-        codes = [p.wait() for p in procs]
+        with ThreadPoolExecutor(max_workers=MAX_JOBS) as pool:  # (a thread per running compile: it only waits for it)
+            codes = list(pool.map(subprocess.call, cmds))
         for c, rc in zip(cmds, codes):
             if rc:
                 raise subprocess.CalledProcessError(rc, c)

@@ -1,4 +1,4 @@
-// sr_absorber_table.inc -- sr_absorber_table_kernel.  Included by sr_kernels.hip inside namespace sr, and by the host
+// sr_absorber_table.inc -- sr_absorber_table_kernel.  Included by sr_ops.hip inside namespace sr, and by the host
 // build tools/absorber_table_host.
 
 // A tabulated absorber (cross-section, CIA or extinction table: sr_abs_table_create) put onto coefficient rows.  The

@@ -1,5 +1,6 @@
 // sr_api.hip -- host side of libspectrobot_hip.so: the C ABI of
-// include/spectrobot_hip.h on top of the kernels in sr_kernels.hip.
+// include/spectrobot_hip.h on top of the launchers of sr_kernels.hpp (the coefficient op: sr_kernels.hip, the limb
+// family: sr_limb.hip and the state units, the small operators: sr_ops.hip, the solar source: sr_solar_source.hip).
 //
 // Host work is limited to what the reference also does once per call in plain
 // Python: line filtering / window centres (spect_classes.py:1384-1388, 1937-1943),

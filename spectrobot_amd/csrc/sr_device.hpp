@@ -126,6 +126,22 @@ __device__ inline double fast_rcp(double d) {
   return r;
 }
 
+// ---- what the far field and the limb kernels share of the wave ----
+// the accumulator of v_mfma_f64_16x16x4_f64: four doubles per lane
+typedef double v4d __attribute__((ext_vector_type(4)));
+// DPP row move of a double (two dwords): CTRL 0x101..0x10f row_shl:n (lane i reads lane i + n of its row of
+// 16), 0x111..0x11f row_shr:n; lanes whose source lies outside the row get 0.
+template <int CTRL>
+__device__ inline double dpp_move(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+__device__ inline double lane_value(double v, int src_lane) { // wave-uniform: the value lane src_lane holds
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src_lane),
+                          __builtin_amdgcn_readlane(__double2loint(v), src_lane));
+}
+
 // ---- region 1: lineshape.f:456-478 ----
 __device__ inline void region1_coef(double ry, double &a, double &b, double &c, double &d) {
   double ry2 = ry * ry;

@@ -285,6 +285,9 @@ int launch_los_columns_dz(const double *nd, const double *x, const double *prof,
 int launch_jac_rows_sum(double *jac, int n_rays, int n_state, int n_hid, int n_pts, hipStream_t st);
 int launch_limb(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
                 const int *seg_layer, const double *col, const LimbOpts &o, double *rad, hipStream_t st);
+// ... its instances of five to eight gases (sr_limb_many.hip), which launch_limb hands such a batch to
+int launch_limb_many(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
+                     const int *seg_layer, const double *col, const LimbOpts &o, double *rad, hipStream_t st);
 int launch_limb_jac(const double *abs_c, const double *emi_c, int n_pts, int n_layers, int n_rays, const int *seg_off,
                     const int *seg_layer, const double *col, const double *dcol, const int *par_gas, int n_par,
                     const LimbOpts &o, double *rad, double *jac, hipStream_t st);
@@ -351,6 +354,15 @@ struct StateLaunch {
   int np;
 };
 int launch_limb_jac_state(const StateLaunch &L, hipStream_t st);
+// The state units behind it, one translation unit each (sr_limb_state_unit.hpp): the kernel's instances for a pair of gas
+// counts and 8 or 16 slots per block, and those of five to eight gases (sr_limb_many.hip, 8 slots).  From the prelude of
+// launch_limb_jac_state -- the checks made, bd the band scratch's layout, n_row_par the parameter rows of a ray in
+// `part`, the rows of a launch with blocks per ray cleared; a gas count that is not the unit's is hipErrorInvalidValue.
+int launch_limb_jac_state_12_np8(const StateLaunch &L, const FoldBands &bd, int n_row_par, hipStream_t st);
+int launch_limb_jac_state_12_np16(const StateLaunch &L, const FoldBands &bd, int n_row_par, hipStream_t st);
+int launch_limb_jac_state_34_np8(const StateLaunch &L, const FoldBands &bd, int n_row_par, hipStream_t st);
+int launch_limb_jac_state_34_np16(const StateLaunch &L, const FoldBands &bd, int n_row_par, hipStream_t st);
+int launch_limb_jac_state_many(const StateLaunch &L, const FoldBands &bd, int n_row_par, hipStream_t st);
 // Radiance budget (sr_limb_parts_kernel): the n_part parts and the background are n_part + 1 slots in blocks of
 // limb_parts_np(n_part); slot_level [n_blocks][NP]: >= 0 the first row of a level's E plane in the pair tables,
 // (2 L + 1) n_tab_rows, -1 - g the gas part of gas g,
@@ -428,6 +440,26 @@ int launch_sum_lines(double *spe, long n_spe, const double *rows, const int *ini
 // grid window and bands (a retrieval's instrument step: every iteration the same bands)
 // instr: the scratch carries the weight tables of the two instrument derivatives behind the weights (three tables in all)
 size_t lowres_scratch_bytes(int n_pts, int n_bands, int n_rays, bool fused = false, bool instr = false);
+// the scratch's layout: the bands' weight table and point ranges, then the partial sums (the band integrals of sr_ops.hip
+// and the limb launchers with a band epilogue, sr_limb.hip)
+// instr (the instrument derivatives, see sr_lowres_weights_kernel): THREE tables one behind the other in W and in Wt -- the
+// weights, then those of d / d centre and of d / d ln width ([3][n_bands][n_pts]; Wt: band tile `tile` of table k is tile
+// k n_tiles + tile) -- and nothing else moves; without it the layout is what it always was.
+struct LowresScratch {
+  double *W;   // [n_bands][n_pts]
+  int *range;  // [n_bands][2]
+  double *Wt;  // [band tiles][n_pts][16]: the same weights, band-minor in tiles of 16 (zero columns beyond n_bands)
+  double *part;
+};
+inline LowresScratch lowres_layout(void *scratch, int n_pts, int n_bands, bool instr = false) {
+  const size_t n_tab = instr ? kLowresTables : 1;
+  LowresScratch L;
+  L.W = static_cast<double *>(scratch);
+  L.range = reinterpret_cast<int *>(L.W + n_tab * n_bands * n_pts); // (before the partial sums: their size follows n_rays)
+  L.Wt = reinterpret_cast<double *>(L.range + 2 * (size_t)n_bands + 2);
+  L.part = L.Wt + n_tab * ((n_bands + 15) / 16) * 16 * n_pts;
+  return L;
+}
 int launch_lowres_weights(int n_pts, int g_lo, double w0, double gstep, const double *cen, const double *wid, int n_bands,
                           double n_sigma, void *scratch, hipStream_t st, bool instr = false);
 // launch_lowres_weights for a tabulated line shape (sr_lowres_weights_tab_kernel): tab, device [n_shapes][n_tab][2], the

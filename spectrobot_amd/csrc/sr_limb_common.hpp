@@ -1,5 +1,5 @@
 // sr_limb_common.hpp -- what the limb recursion kernels share: a segment's attenuation, the options of a ray batch, the
-// initial intensity, the block order and the coefficient loads.  No HIP header of its own: the includer provides the
+// initial intensity, the band epilogue's record, the block order and the coefficient loads.  No HIP header of its own: the includer provides the
 // qualifiers, blockIdx, fma3 and fast_rcp -- sr_device.hpp in the library, tools/host_sim/hip_on_host.hpp in a host build.
 #pragma once
 #include <cstddef>
@@ -69,6 +69,17 @@ __device__ inline double limb_initial(const LimbOpts &o, const double *rad, size
   }
   return 0.0;
 }
+
+// Where the recursion kernels with a band epilogue (BANDS = true: sr_limb_fold_sens_lds_kernel, sr_limb_jac_state_kernel)
+// find the instrument step's weight table and leave their partial sums; see the comment above the former.
+struct FoldBands {
+  const double *Wt;  // [band tiles][n_pts][16]
+  const int *range;  // [n_bands][2]
+  double *part;
+  int n_bands;
+};
+constexpr int kLowresTables = 3; // the weight tables of a call with the instrument derivatives: value, d / d centre, d / d ln width
+constexpr int kBandRow = 68; // doubles per row of a wave's tile of values (64 + padding: rows 8 banks apart)
 
 // Block -> (point block, ray) of the ray-batch kernels.  With the rays on the grid's slow axis the resident blocks
 // work on one or two rays at a time and every ray streams the coefficient tables from HBM again (64 rays: 4.0 GB

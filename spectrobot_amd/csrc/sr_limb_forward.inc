@@ -1,5 +1,5 @@
 // sr_limb_forward.inc -- the path-order radiance kernels of a ray batch, sr_limb_kernel and sr_limb_split_kernel.
-// Included inside namespace sr by sr_kernels.hip (NG = 1..4), by sr_limb_many.hip (NG = 5..8) and by the host builds under
+// Included inside namespace sr by sr_limb.hip (NG = 1..4), by sr_limb_many.hip (NG = 5..8) and by the host builds under
 // tools/ (tools/host_sim/hip_on_host.hpp) behind sr_limb_common.hpp.
 template <int NG>
 __global__ __launch_bounds__(256) void sr_limb_kernel(const double *__restrict__ abs_c, const double *__restrict__ emi_c,

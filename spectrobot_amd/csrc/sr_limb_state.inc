@@ -1,17 +1,9 @@
-// sr_limb_state.inc -- sr_limb_jac_state_kernel and what only it uses.  Included by sr_kernels.hip inside namespace sr, and
-// by the host builds under tools/ (tools/host_sim/hip_on_host.hpp) behind sr_limb_plan.hpp and sr_limb_common.hpp.
+// sr_limb_state.inc -- sr_limb_jac_state_kernel and what only it uses.  Included inside namespace sr by
+// sr_limb_state_unit.hpp (the library's state units: sr_limb_state_*.hip and sr_limb_many.hip), and by the host builds
+// under tools/ (tools/host_sim/hip_on_host.hpp) behind sr_limb_plan.hpp and sr_limb_common.hpp (FoldBands, kLowresTables,
+// kBandRow).
 // SR_PIN_SCALARS(a, b): the includer's -- pins two wave-uniform ints to scalar registers, or nothing on a host.
 
-// Where the recursion kernels with a band epilogue (BANDS = true: sr_limb_fold_sens_lds_kernel, sr_limb_jac_state_kernel)
-// find the instrument step's weight table and leave their partial sums; see the comment above the former.
-struct FoldBands {
-  const double *Wt;  // [band tiles][n_pts][16]
-  const int *range;  // [n_bands][2]
-  double *part;
-  int n_bands;
-};
-constexpr int kLowresTables = 3; // the weight tables of a call with the instrument derivatives: value, d / d centre, d / d ln width
-constexpr int kBandRow = 68; // doubles per row of a wave's tile of values (64 + padding: rows 8 banks apart)
 // the buffer limb_initial() reads with init_mode 1 (which the host refuses for the state kernel): none with BANDS
 __device__ inline const double *limb_state_init_src(const double *jac) { return jac; }
 __device__ inline const double *limb_state_init_src(const FoldBands &) { return nullptr; }

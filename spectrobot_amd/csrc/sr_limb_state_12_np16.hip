@@ -1,0 +1,10 @@
+// sr_limb_state_12_np16.hip -- sr_limb_jac_state_kernel's instances for batches of 1 or 2 gases with 16 slots per block.
+#include "sr_limb_state_unit.hpp"
+
+namespace sr {
+
+int launch_limb_jac_state_12_np16(const StateLaunch &L, const FoldBands &bd, int n_row_par, hipStream_t st) {
+  return launch_state_instances<kLevelJacNPLarge>(L, bd, n_row_par, st, [&](auto &&f) { return by_ngas_of<1, 2>(L.o.n_gas, f); });
+}
+
+} // namespace sr

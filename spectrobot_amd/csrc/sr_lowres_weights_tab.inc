@@ -1,4 +1,4 @@
-// sr_lowres_weights_tab.inc -- sr_lowres_weights_tab_kernel.  Included by sr_kernels.hip inside namespace sr, and by the host
+// sr_lowres_weights_tab.inc -- sr_lowres_weights_tab_kernel.  Included by sr_ops.hip inside namespace sr, and by the host
 // build tools/ils_host.
 
 // The weights of a TABULATED instrument line shape (sr_set_ils): sr_lowres_weights_kernel with the Gaussian replaced by

@@ -9,8 +9,6 @@
 
 namespace sr {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 #include "sr_solar_source.inc"
 
 int launch_solar_source(const double *tab_abs, int n_k, int n_pts, const double *u, const double *w, const int *src_row,

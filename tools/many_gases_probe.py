@@ -2,8 +2,8 @@
 """What a gas slot above four costs: the state-bands call (engine.limb_rays_state_bands, one column parameter per gas) and
 engine.limb_rays for batches of 4, 5, 6 and 8 gases on the shape of tools/state_bands_probe.py -- 18 pixels x 3 lines of
 sight, 55 layers, 1e5 points, 14 bands, field of view.  The coefficient tables are synthetic (random, thin to thick): the
-recursion kernels' time does not depend on their values.  Four gases run the instances of sr_kernels.hip (the folded sweep
-for limb_rays: route 2), five to eight those of sr_limb_many.hip (path order, route 1; five gases on the six-gas state
+recursion kernels' time does not depend on their values.  Four gases run the instances of sr_limb.hip (the folded sweep
+for limb_rays: route 2) and of sr_limb_state_34_np8.hip, five to eight those of sr_limb_many.hip (path order, route 1; five gases on the six-gas state
 instance).  HIP events around every call, the median of 20 calls after 3, three repeats of that; per gas count the median
 of the repeats, their spread, the ratio to the four-gas call of the same run, and the waves per SIMD the instance's VGPR
 count leaves (512 VGPRs per lane and SIMD, allocated in blocks of 8; the counts are read from
@@ -33,8 +33,8 @@ lam_lo, lam_hi = 1e7 / grid[-1], 1e7 / grid[0]
 margin = min(1.2, 0.1 * (lam_hi - lam_lo))
 bands = (np.linspace(lam_lo + margin, lam_hi - margin, 14), np.full(14, min(1.1, 0.1 * (lam_hi - lam_lo))))
 # VGPRs of the instances the calls run.  Five to eight gases: read from profiles/many_gases_kernel_resources.txt, the output
-# of `SR_SOURCE=sr_limb_many.hip tools/kernel_resources.sh sr_` kept with the code (regenerate it when the kernels change);
-# four gases: the instances of sr_kernels.hip, COPIED from `tools/kernel_resources.sh sr_` of 2026-10-20 -- the JSON says so.
+# of `tools/kernel_resources.sh sr_` for the kernels of sr_limb_many.hip, kept with the code (regenerate it when the kernels
+# change); four gases: COPIED from `tools/kernel_resources.sh sr_` of 2026-10-20 -- the JSON says so.
 RES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "many_gases_kernel_resources.txt")
 VGPR_FOUR = {"state_bands": 116, "limb_rays": 76}    # sr_limb_jac_state_kernel<4, 8, true, false, true, false>, sr_limb_fold_fwd_kernel<4>
 
