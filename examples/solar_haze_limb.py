@@ -9,7 +9,9 @@ coefficient like any other (engine.solar_source).  Three parts:
                 retrieval.TableGas(..., solar=dict(albedo=, g=)): the tangent-SZA approximation, one solar pass over the
                 layer rows inside coefficients()
   retrieval     a twin retrieval of the haze profile (with the CH4 VMR) from sunlit pixels through inversion_state; the
-                Jacobians hold the solar attenuation fixed within an iteration, the pass is redone between iterations
+                Jacobians hold the solar attenuation fixed within an iteration, the pass is redone between iterations.
+                inversion_state(..., solar_attenuation=True) adds the derivative through the solar optical depth to the
+                VMR columns: examples/retrieve_solar_attenuation.py
 
 The haze table is synthetic, the sun a black body at Saturn's distance.  Multiple scattering, refraction and a surface
 term are not built.  Needs an MI355X:  python examples/solar_haze_limb.py

@@ -976,6 +976,38 @@ int sr_solar_source_rows_dev(const sr_solar_desc *desc, const double *tab_abs, i
                              const double *sun, int64_t n_pts, int accumulate, double *emi_out, double *trans_out,
                              void *stream);
 
+/* The solar attenuation in the Jacobians: d radiance / d (column parameter) THROUGH the optical depth of the solar source.
+ * The build's own definition.  For parameter p, ray y and grid point j:
+ *   dtau[p][r][j] = sum_{k < n_k} du[p][r][k] tab_abs[k][j]
+ *   jac[y][par_slot[p]][j] (+)= - sum_{r < n_rows} q[y][r][j] dtau[p][r][j]
+ * du HOST [n_par][n_rows][n_k] = d u[r][k] / d x_p (geometry.solar_column_weights: any finite sign, dense, mostly zeros,
+ * read as it is); tab_abs DEVICE [n_k][n_pts] as above; q DEVICE [n_rays][n_rows][n_pts], finite: d rad[y] / d eps_r for
+ * emi[r] -> emi[r] + eps_r (the solar rows of r alone), i.e. sr_limb_rays_jac_layer_dev with dabs = 0 and demi = those
+ * rows; jac DEVICE [n_rays][n_jac_rows][n_pts], parameter p in row par_slot[p] (HOST [n_par], each row named at most
+ * once), the rows not named are left as they are; accumulate != 0 adds to the rows named (a parameter whose du is all
+ * zero then leaves its row unread).  With a derivative table in tab_abs' place (d abs / d T) the same call gives the
+ * term of a temperature parameter.  du and par_slot are staged through the calling thread's pinned ring (no stream is
+ * made) with the chunk lists per (parameter, tile of 16 rows); chunks and tiles that are not listed would only have added
+ * exact zeros (sr_set_solar_full_lists(1) lists every one: the check of that).  One fused fp64 kernel
+ * (v_mfma_f64_16x16x4, then the product with q and the row sum) on `stream`; one writer per element, no atomics, the same
+ * call gives the same bits.  Every argument is checked before the first copy or launch and a refused call leaves jac
+ * untouched: SR_ERR_ARG for a NULL desc, du, tab_abs, q, par_slot or jac, n_par <= 0, n_rows <= 0, n_k <= 0, n_rays <= 0,
+ * n_pts <= 0, n_jac_rows <= 0, a du that is not finite, a par_slot outside 0 .. n_jac_rows - 1 or named twice;
+ * SR_ERR_LIMIT for n_rows > SR_MAX_ABS_ROWS, n_par n_rows n_k > SR_MAX_SOLAR_VALUES, n_pts > 2000000, or more than
+ * INT32_MAX blocks (8 ceil(n_pts / 2048) n_par ceil(n_rays / 8)).
+ * sr_solar_jacobian_chunk_lists: the lists alone, on the host (no GPU): tile_off HOST [n_par ceil(n_rows / 16) + 1] (the
+ * tiles of parameter p from p ceil(n_rows / 16) on), chunks HOST [n_par ceil(n_rows / 16) ceil(n_k / 4)] (room for every
+ * chunk), *n_listed the number listed.  Checked against an extended-precision reference (tests/test_gpu_solar_jacobian.py). */
+typedef struct {
+  int32_t n_par;
+  int32_t n_rows;
+  const double *du; /* [n_par][n_rows][n_k] */
+} sr_solar_jac_desc;
+int sr_solar_jacobian_chunk_lists(const sr_solar_jac_desc *desc, int n_k, int32_t *tile_off, int32_t *chunks, int32_t *n_listed);
+int sr_solar_jacobian_rows_dev(const sr_solar_jac_desc *desc, const double *tab_abs, int n_k, const double *q, int n_rays,
+                               int64_t n_pts, const int32_t *par_slot, double *jac, int n_jac_rows, int accumulate,
+                               void *stream);
+
 /* Evaluation mode of the coefficient op.  Far region-1 wings by local Taylor expansions per box of grid
  * points (truncation <= sr_far_field_truncation_bound() of a line's own contribution: 1.6e-11 as built by default, degree
  * 19; 2.6e-13 with -DSR_KFD=22; a box takes a line from sr_far_field_min_distance() on), near field exact, with the expansions built

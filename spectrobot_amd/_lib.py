@@ -84,6 +84,10 @@ class SolarDesc(C.Structure):
     _fields_ = [("n_rows", C.c_int32), ("u", dp), ("w", dp), ("src_row", ip)]
 
 
+class SolarJacDesc(C.Structure):
+    _fields_ = [("n_par", C.c_int32), ("n_rows", C.c_int32), ("du", dp)]
+
+
 class IlsDesc(C.Structure):
     _fields_ = [("n_shapes", C.c_int32), ("n_tab", C.c_int32), ("t_lo", C.c_double), ("t_hi", C.c_double), ("phi", dp)]
 
@@ -217,6 +221,9 @@ SYMBOLS = {
     "sr_solar_chunk_lists": (C.c_int, [C.POINTER(SolarDesc), C.c_int, ip, ip, ip]),
     "sr_solar_source_rows_dev": (C.c_int, [C.POINTER(SolarDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                            C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_solar_jacobian_chunk_lists": (C.c_int, [C.POINTER(SolarJacDesc), C.c_int, ip, ip, ip]),
+    "sr_solar_jacobian_rows_dev": (C.c_int, [C.POINTER(SolarJacDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, ip,
+                                             C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "sr_set_points_per_lane": (C.c_int, [C.c_int]),
     "sr_set_band_fusion": (C.c_int, [C.c_int]),
     "sr_far_field_truncation_bound": (C.c_double, []),

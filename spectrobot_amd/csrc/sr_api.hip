@@ -4161,6 +4161,52 @@ int sr_solar_source_rows_dev(const sr_solar_desc *desc, const double *tab_abs, i
   return pk.slot().mark(st);
 }
 
+// The solar attenuation in the Jacobians (sr_solar_jac.inc).  One check of the descriptor for both entries, as above.
+static int check_solar_jac_desc(const sr_solar_jac_desc *d, int n_k, std::vector<int> *tile_off, std::vector<int> *chunks) {
+  if (!d || !d->du || d->n_par <= 0 || d->n_rows <= 0 || n_k <= 0) return SR_ERR_ARG;
+  if (d->n_rows > SR_MAX_ABS_ROWS || (int64_t)d->n_par * d->n_rows * n_k > SR_MAX_SOLAR_VALUES) return SR_ERR_LIMIT;
+  // du is walked once: its check and the chunk lists together
+  return solar_jac_chunk_lists(d->du, d->n_par, d->n_rows, n_k, g_solar_full_lists != 0, *tile_off, *chunks) ? SR_OK : SR_ERR_ARG;
+}
+
+int sr_solar_jacobian_chunk_lists(const sr_solar_jac_desc *desc, int n_k, int32_t *tile_off, int32_t *chunks, int32_t *n_listed) {
+  if (!tile_off || !chunks || !n_listed) return SR_ERR_ARG;
+  std::vector<int> off, ch;
+  const int rc = check_solar_jac_desc(desc, n_k, &off, &ch);
+  if (rc) return rc;
+  std::copy(off.begin(), off.end(), tile_off);
+  std::copy(ch.begin(), ch.end(), chunks);
+  *n_listed = (int32_t)ch.size();
+  return SR_OK;
+}
+
+int sr_solar_jacobian_rows_dev(const sr_solar_jac_desc *desc, const double *tab_abs, int n_k, const double *q, int n_rays,
+                               int64_t n_pts, const int32_t *par_slot, double *jac, int n_jac_rows, int accumulate, void *stream) {
+  if (!tab_abs || !q || !par_slot || !jac || n_rays <= 0 || n_pts <= 0 || n_jac_rows <= 0) return SR_ERR_ARG;
+  if (n_pts > 2000000) return SR_ERR_LIMIT;
+  std::vector<int> tile_off, chunks;
+  int rc = check_solar_jac_desc(desc, n_k, &tile_off, &chunks);
+  if (rc) return rc;
+  const int n_par = desc->n_par, n_rows = desc->n_rows;
+  std::vector<int> slots(par_slot, par_slot + n_par); // one writer per element: a row of jac belongs to one parameter
+  std::sort(slots.begin(), slots.end());
+  if (slots.front() < 0 || slots.back() >= n_jac_rows || std::adjacent_find(slots.begin(), slots.end()) != slots.end()) return SR_ERR_ARG;
+  // the grid: point blocks (rounded up to eight) x parameters x ray groups
+  const int64_t n_blocks = (((n_pts + 255) / 256 + 7) / 8 * 8) * (int64_t)n_par * ((n_rays + kSolarJacRays - 1) / kSolarJacRays);
+  if (n_blocks > 2147483647) return SR_ERR_LIMIT;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_du = pk.copy(desc->du, (size_t)n_par * n_rows * n_k);
+  const auto p_slot = pk.copy(par_slot, (size_t)n_par);
+  const auto p_off = pk.copy(tile_off.data(), tile_off.size()), p_ch = pk.copy(chunks.data(), chunks.size(), 1);
+  rc = pk.stage(st);
+  if (rc) return rc;
+  LAUNCHCHK(launch_solar_jac(tab_abs, n_k, (int)n_pts, pk.dev(p_du), n_par, n_rows, pk.dev(p_off), pk.dev(p_ch), q, n_rays,
+                             pk.dev(p_slot), accumulate != 0, jac, n_jac_rows, st));
+  return pk.slot().mark(st);
+}
+
 // ------------------------------------------------------------------------
 // f2py-shaped shims (host pointers)
 // ------------------------------------------------------------------------

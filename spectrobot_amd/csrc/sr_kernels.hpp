@@ -499,5 +499,9 @@ int launch_absorber_table(int n_used, const double *set_v0, const double *set_dv
 int launch_solar_source(const double *tab_abs, int n_k, int n_pts, const double *u, const double *w, const int *src_row,
                         int n_rows, const int *tile_off, const int *chunks, const double *sca_abs, const double *sun,
                         bool accumulate, double *emi_out, double *trans_out, hipStream_t st);
+// the solar attenuation in the Jacobians (sr_solar_jac.inc); the grid is limb_grid(point blocks, n_par x ray groups)
+int launch_solar_jac(const double *tab_abs, int n_k, int n_pts, const double *du, int n_par, int n_rows, const int *tile_off,
+                     const int *chunks, const double *q, int n_rays, const int *par_slot, bool accumulate, double *jac,
+                     int n_jac_rows, hipStream_t st);
 
 } // namespace sr

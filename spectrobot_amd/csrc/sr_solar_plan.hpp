@@ -3,6 +3,7 @@
 // column, in ascending order.  Included by sr_api.hip and by the host build tools/solar_source_host; no HIP header.
 // U is read as it is: nothing is sorted, nothing is changed.  full: every chunk of every tile is listed (the check
 // that the result does not depend on the lists: a chunk that is not listed would only have added exact zeros).
+// Below it the plan of sr_solar_jac_kernel (sr_solar_jac.inc; tools/solar_jacobian_host): the same lists per parameter.
 #pragma once
 #include <cstddef>
 #include <vector>
@@ -11,6 +12,7 @@ namespace sr {
 
 constexpr int kSolarRows = 16; // rows of a tile: the MFMA's M
 constexpr int kSolarChunk = 4; // k per chunk: the MFMA's K
+constexpr int kSolarJacRays = 8; // NR: rays per block of sr_solar_jac_kernel (profiles/solar_jac_kernel_resources.txt)
 
 // tile_off [n_tiles + 1] into chunks; n_tiles = ceil(n_rows / kSolarRows), chunk c covers k = 4 c .. 4 c + 3 (< n_k).
 // Returns false if an element of u is negative or not finite (the entry's check, in the same walk: u is the one large
@@ -45,6 +47,35 @@ inline bool solar_chunk_lists(const double *u, const double *w, int n_rows, int 
       if (hit[(size_t)c]) chunks.push_back(c);
     tile_off.push_back((int)chunks.size());
   }
+  return ok;
+}
+
+// The plan of sr_solar_jac_kernel (sr_solar_jac.inc): the same lists per (parameter, row tile) of du [n_par][n_rows][n_k],
+// the derivative of the columns to a parameter -- any finite sign, no weights.  tile_off [n_par n_tiles + 1], the tiles of
+// parameter p at p n_tiles ..: a tile never straddles a parameter.  Returns false if an element is not finite.
+inline bool solar_jac_chunk_lists(const double *du, int n_par, int n_rows, int n_k, bool full, std::vector<int> &tile_off,
+                                  std::vector<int> &chunks) {
+  const int n_tiles = (n_rows + kSolarRows - 1) / kSolarRows, n_chunks = (n_k + kSolarChunk - 1) / kSolarChunk;
+  tile_off.assign(1, 0);
+  chunks.clear();
+  std::vector<char> hit((size_t)n_chunks);
+  bool ok = true;
+  for (int p = 0; p < n_par; ++p)
+    for (int t = 0; t < n_tiles; ++t) {
+      hit.assign((size_t)n_chunks, full ? 1 : 0);
+      const int r1 = n_rows < (t + 1) * kSolarRows ? n_rows : (t + 1) * kSolarRows;
+      for (int r = t * kSolarRows; r < r1; ++r) {
+        const double *ur = du + ((size_t)p * n_rows + r) * n_k;
+        for (int k = 0; k < n_k; ++k) {
+          // (a NaN fails both comparisons, an infinity one)
+          ok &= (ur[k] >= -1.7976931348623157e308) & (ur[k] <= 1.7976931348623157e308);
+          hit[(size_t)(k / kSolarChunk)] |= (char)(ur[k] != 0.0);
+        }
+      }
+      for (int c = 0; c < n_chunks; ++c)
+        if (hit[(size_t)c]) chunks.push_back(c);
+      tile_off.push_back((int)chunks.size());
+    }
   return ok;
 }
 

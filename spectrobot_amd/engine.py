@@ -618,9 +618,10 @@ def solar_source(A, U, w, sca, sun, src_row=None, out=None, accumulate=False, tr
     accumulate=True (thermal + solar).  transmission=True: also exp(-tau) itself [n_rows, n_pts] (1 for a row without
     columns, 0 in shadow and where tau >= 700).  One fused fp64 kernel; the same call gives the same bits.
 
-    Every Jacobian treats the rows as coefficients: the solar attenuation is HELD FIXED under d / d(VMR, T, Tvib) within
-    one linearisation (as TempProfile holds columns and pressure fixed); the derivative through tau is not built.
-    Returns emi, or (emi, trans)."""
+    By default every Jacobian treats the rows as coefficients: the solar attenuation is HELD FIXED under d / d(VMR, T, Tvib)
+    within one linearisation (as TempProfile holds columns and pressure fixed).  The derivative through tau for VMR
+    parameters is solar_attenuation_jacobian (retrieval.inversion_state(solar_attenuation=True)); for T and Tvib it is not
+    built.  Returns emi, or (emi, trans)."""
     d, n_k, keep = _solar_desc(U, w, src_row)
     ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
     if not (ok(A) and ok(sca) and ok(sun)) or A.dim() not in (2, 3) or sca.dim() != 2 or sun.dim() != 1:
@@ -642,6 +643,72 @@ def solar_source(A, U, w, sca, sun, src_row=None, out=None, accumulate=False, tr
                                        C.c_void_p(trans.data_ptr()) if transmission else None, _stream_ptr()),
           "sr_solar_source_rows_dev")
     return (out, trans) if transmission else out
+
+
+SOLAR_JAC_RAYS = 8      # rays per block of sr_solar_jac_kernel (kSolarJacRays): where the ray-group edge of a call sits
+
+
+def _solar_jac_desc(dU):
+    """(sr_solar_jac_desc, n_k, the array it points to) of dU [n_par, n_rows, n_k] or [n_par, n_rows, n_gas, n_layers]."""
+    dU = np.asarray(dU, dtype=np.float64)
+    if dU.ndim not in (3, 4) or dU.shape[0] == 0 or dU.shape[1] == 0:
+        raise ValueError("dU must be [n_par, n_rows, n_k] or [n_par, n_rows, n_gas, n_layers]")
+    du, dup = _d(dU.reshape(dU.shape[0], dU.shape[1], -1))
+    d = _lib.SolarJacDesc()
+    d.n_par, d.n_rows, d.du = du.shape[0], du.shape[1], dup
+    return d, du.shape[2], du
+
+
+def solar_jacobian_chunk_lists(dU):
+    """(tile_off [n_par n_tiles + 1], chunks) the solar-attenuation Jacobian kernel walks (sr_solar_jacobian_chunk_lists, on
+    the host: no GPU): per parameter and tile of 16 rows the chunks of four k in which any row of the tile has a non-zero
+    dU; the tiles of parameter p stand at p n_tiles .. (p + 1) n_tiles."""
+    d, n_k, keep = _solar_jac_desc(dU)
+    n_tiles, n_chunks = d.n_par * ((d.n_rows + 15) // 16), (n_k + 3) // 4
+    off, ch, n = np.zeros(n_tiles + 1, np.int32), np.zeros(max(n_tiles * n_chunks, 1), np.int32), C.c_int32(0)
+    check(lib.sr_solar_jacobian_chunk_lists(C.byref(d), n_k, off.ctypes.data_as(ip), ch.ctypes.data_as(ip), C.byref(n)),
+          "sr_solar_jacobian_chunk_lists")
+    return off, ch[:n.value].copy()
+
+
+def solar_attenuation_jacobian(A, dU, Q, out=None, par_slot=None, accumulate=False):
+    """The solar attenuation in the Jacobians (sr_solar_jacobian_rows_dev; the build's own definition):
+    the derivative of limb radiances to column parameters through the optical depth of solar_source's rows,
+
+        dtau[p, r] = sum_k dU[p, r, k] A[k],   jac[ray, par_slot[p]] (+)= - sum_r Q[ray, r] dtau[p, r]
+
+    A: the stacked absorption rows of the scene, CUDA [n_gas, n_layers, n_pts] or [n_k, n_pts], as solar_source takes
+    them; dU: host [n_par, n_rows, n_gas, n_layers] or [n_par, n_rows, n_k] = d U / d x_p
+    (geometry.solar_column_weights), any finite sign, dense and mostly zeros; Q: CUDA [n_rays, n_rows, n_pts], the
+    derivative of the radiances to a factor 1 + eps_r on the solar part of row r's emission:
+    limb_rays_layer_jacobian(coeffs, (zeros, solar rows), los).  out: CUDA [n_rays, n_jac_rows, n_pts], required with
+    accumulate=True; par_slot [n_par]: the row of out of every parameter (None: row p, and out [n_rays, n_par, n_pts]);
+    rows that are not named keep their bits.  One fused fp64 kernel; the same call gives the same bits.  Returns out."""
+    d, n_k, keep = _solar_jac_desc(dU)
+    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    if not (ok(A) and ok(Q)) or A.dim() not in (2, 3) or Q.dim() != 3:
+        raise ValueError("A and Q must be contiguous CUDA float64 tensors ([n_k or n_gas, n_layers, n_pts], [n_rays, n_rows, n_pts])")
+    n_pts = A.shape[-1]
+    if A.numel() != n_k * n_pts:
+        raise ValueError("dU has %d columns per row, A %d rows" % (n_k, A.numel() // max(n_pts, 1)))
+    if Q.shape[0] == 0 or Q.shape[1] != d.n_rows or Q.shape[2] != n_pts:
+        raise ValueError("Q must be [n_rays, %d, %d]: dU's rows and A's grid points" % (d.n_rows, n_pts))
+    n_rays = int(Q.shape[0])
+    slot, sp = _i(np.arange(d.n_par) if par_slot is None else par_slot)
+    if slot.shape != (d.n_par,):
+        raise ValueError("par_slot must be [n_par]")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True adds to out=...")
+        if par_slot is not None:
+            raise ValueError("par_slot places rows in out=...")
+        out = torch.empty((n_rays, d.n_par, n_pts), dtype=torch.float64, device="cuda")
+    elif not ok(out) or out.dim() != 3 or out.shape[0] != n_rays or out.shape[2] != n_pts:
+        raise ValueError("out must be a contiguous CUDA float64 [n_rays, n_jac_rows, n_pts]")
+    check(lib.sr_solar_jacobian_rows_dev(C.byref(d), C.c_void_p(A.data_ptr()), n_k, C.c_void_p(Q.data_ptr()), n_rays, n_pts, sp,
+                                         C.c_void_p(out.data_ptr()), int(out.shape[1]), int(bool(accumulate)), _stream_ptr()),
+          "sr_solar_jacobian_rows_dev")
+    return out
 
 
 def lut_interp(table, idx4, wgt4, pops=None, out=None):

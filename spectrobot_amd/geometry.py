@@ -432,12 +432,27 @@ def _solar_columns(z, nd_levels, vmr_levels, alt, mu, R, n_sub, col_scale, colum
     """solar_columns with the column routine given: columns(L, col_scale) -> [n_gas, n_seg], L limb_los's dict of the rays'
     crossings (the host tests pass a plain routine, the same on both sides of their comparisons)."""
     z, zz, ln, vv = _profiles(z, nd_levels, vmr_levels)
+    n_gas, n_layers = vv.shape[0], len(z)
+    lit, L = _solar_rays(z, zz, ln, alt, mu, R, n_sub)
+    U = np.zeros((lit.size, n_gas, n_layers))
+    if L is None:
+        return U, lit
+    L["vmr"] = np.array([np.interp(L["alt"], zz, v) for v in vv])
+    col = np.asarray(columns(L, col_scale), float)
+    row = np.repeat(np.arange(lit.size), np.diff(L["seg_off"]))
+    for g in range(n_gas):
+        np.add.at(U[:, g, :], (row, L["seg_layer"]), col[g])
+    return U, lit
+
+
+def _solar_rays(z, zz, ln, alt, mu, R, n_sub):
+    """The sun rays of _solar_columns without a profile on them: (lit [n_rows], limb_los's dict of the rays' crossings
+    with x, nd and alt but no vmr -- None when no ray crosses anything).  z, zz, ln: _profiles' levels."""
     alt = np.atleast_1d(np.asarray(alt, float))
     mu = np.broadcast_to(np.asarray(mu, float), alt.shape)
     if np.any(np.abs(mu) > 1.0):
         raise ValueError("mu = cos SZA must lie in [-1, 1]")
-    n_rows, n_gas, n_layers = alt.size, vv.shape[0], len(z)
-    U = np.zeros((n_rows, n_gas, n_layers))
+    n_rows = alt.size
     lit = np.ones(n_rows, bool)
     seg_off, lay, xs, alts = [0], [], [], []
     for r_alt, m in zip(alt, mu):
@@ -458,16 +473,49 @@ def _solar_columns(z, nd_levels, vmr_levels, alt, mu, R, n_sub, col_scale, colum
         seg_off.append(seg_off[-1] + len(k))
     n_seg = seg_off[-1]
     if n_seg == 0:
-        return U, lit
+        return lit, None
     al = np.clip(np.concatenate(alts), z[0], zz[-1])
-    L = dict(seg_off=np.array(seg_off, np.int32), seg_layer=np.concatenate(lay).astype(np.int32),
-             pt_off=(np.arange(n_seg + 1) * (n_sub + 1)).astype(np.int32), x=np.concatenate(xs) * 1e5,
-             nd=np.exp(np.interp(al, zz, ln)), vmr=np.array([np.interp(al, zz, v) for v in vv]), alt=al)
-    col = np.asarray(columns(L, col_scale), float)
-    row = np.repeat(np.arange(n_rows), np.diff(L["seg_off"]))
-    for g in range(n_gas):
-        np.add.at(U[:, g, :], (row, L["seg_layer"]), col[g])
-    return U, lit
+    return lit, dict(seg_off=np.array(seg_off, np.int32), seg_layer=np.concatenate(lay).astype(np.int32),
+                     pt_off=(np.arange(n_seg + 1) * (n_sub + 1)).astype(np.int32), x=np.concatenate(xs) * 1e5,
+                     nd=np.exp(np.interp(al, zz, ln)), alt=al)
+
+
+SOLAR_WEIGHT_BATCH = 8      # masks per column call: what one LOS batch takes as gases
+
+
+def solar_column_weights(z, nd_levels, masks, par_gas, n_gas, alt, mu, R=TITAN_RADIUS_KM, n_sub=3, col_scale=None):
+    """The derivative of solar_columns to column parameters: dU [n_par, n_rows, n_gas, n_layers] = d U / d x_p for
+    d vmr_{par_gas[p]}(z_i) / d x_p = masks[p][i] (as LimbScene.profile_weights assumes), and lit [n_rows].  solar_columns
+    is linear in the VMR profiles, so this is the same crossings, sampling and column routine with the mask in gas
+    par_gas[p]'s place (with that gas's col_scale) and zeros elsewhere; the rays are walked once for all parameters, the
+    column routine takes SOLAR_WEIGHT_BATCH masks per call.  Masks may have either sign; a row in shadow is a row of
+    zeros.  sum_p x_p dU_p is solar_columns of the profiles sum_p x_p masks_p, to rounding."""
+    return _solar_column_weights(z, nd_levels, masks, par_gas, n_gas, alt, mu, R, n_sub, col_scale, _device_columns)
+
+
+def _solar_column_weights(z, nd_levels, masks, par_gas, n_gas, alt, mu, R, n_sub, col_scale, columns):
+    """solar_column_weights with the column routine given, as _solar_columns."""
+    masks = np.atleast_2d(np.asarray(masks, float))
+    par_gas = np.atleast_1d(np.asarray(par_gas, int))
+    n_par, n_gas = masks.shape[0], int(n_gas)
+    if par_gas.shape != (n_par,) or (n_par and (par_gas.min() < 0 or par_gas.max() >= n_gas)):
+        raise ValueError("par_gas must name a gas 0 .. n_gas - 1 for every mask")
+    if masks.shape[1] != len(np.atleast_1d(z)):
+        raise ValueError("the masks must be on the levels z")
+    z, zz, ln, mm = _profiles(z, nd_levels, masks)
+    lit, L = _solar_rays(z, zz, ln, alt, mu, R, n_sub)
+    dU = np.zeros((n_par, lit.size, n_gas, len(z)))
+    if L is None or n_par == 0:
+        return dU, lit
+    scale = np.ones(n_gas) if col_scale is None else np.asarray(col_scale, float)
+    row = np.repeat(np.arange(lit.size), np.diff(L["seg_off"]))
+    for p0 in range(0, n_par, SOLAR_WEIGHT_BATCH):
+        ps = range(p0, min(p0 + SOLAR_WEIGHT_BATCH, n_par))
+        Lb = dict(L, vmr=np.array([np.interp(L["alt"], zz, mm[p]) for p in ps]))
+        col = np.asarray(columns(Lb, [scale[par_gas[p]] for p in ps]), float)
+        for i, p in enumerate(ps):
+            np.add.at(dU[p, :, par_gas[p], :], (row, L["seg_layer"]), col[i])
+    return dU, lit
 
 
 def hg_phase(cos_theta, g):

@@ -388,6 +388,8 @@ class LimbScene(object):
         self.solar_frozen = False   # True: solar rows that exist are kept whatever moves -- the linearisation's own assumption,
                                     # for finite differences that are to see what the Jacobians see (a rebuilt thermal pair
                                     # still gets its solar rows again)
+        self.keep_solar_rows = False  # True: the solar pass keeps every solar gas's solar rows alone (g.solar_rows), what
+                                      # solar_attenuation_jacobian works on (inversion_state(solar_attenuation=True) sets it)
         if sun is not None and sun.irradiance.shape != self.grid.shape:
             raise ValueError("the sun's irradiance must be given on the scene's grid")
         self.z, self.temps, self.press = (np.asarray(v, dtype=float) for v in (z, temps, press))
@@ -445,6 +447,8 @@ class LimbScene(object):
         if not solar:
             return
         import torch
+        if self.keep_solar_rows:
+            return self.solar_pass_with_rows(solar, g_lo, g_hi)
         done = all(g.coeffs is not g.thermal for g in solar)
         if done and self.solar_frozen:
             return
@@ -466,6 +470,58 @@ class LimbScene(object):
         # table by identity, as coefficient_stack does: every rebuild in this package makes new tensors; a caller who
         # overwrites a table IN PLACE sets scene._solar_key = None)
         self._solar_key, self._solar_tabs = key, tabs
+
+    def solar_pass_with_rows(self, solar, g_lo, g_hi):
+        """solar_pass for a scene that was asked for the solar rows alone (keep_solar_rows): every solar gas keeps
+        g.solar_rows = sca S, made by an overwrite call, and its emission rows are thermal + those -- the same sum the
+        accumulating call forms (solar_attenuation_jacobian's input).  The same rule of when nothing is redone."""
+        import torch
+        done = all(g.coeffs is not g.thermal and getattr(g, "solar_rows", None) is not None for g in solar)
+        if done and self.solar_frozen:
+            return
+        key = self.solar_key(g_lo, g_hi) + ("rows",)
+        if done and getattr(self, "_solar_key", None) == key:
+            return
+        top = self.z[-1] + (self.z[-1] - self.z[-2])
+        zz = np.append(self.z, top)
+        U, lit = geometry.solar_columns(self.z, self.nd, [g.vmr for g in self.gases], 0.5 * (zz[:-1] + zz[1:]), self.sun.mu, R=self.R,
+                                        n_sub=self.n_sub, col_scale=[g.iso_ratio for g in self.gases])
+        tabs = [(g.thermal if g in solar else g.coeffs)[0] for g in self.gases]
+        A = torch.stack(tabs).contiguous()
+        sun = torch.as_tensor(self.sun.irradiance[g_lo:g_hi], device="cuda").contiguous()
+        for g in solar:
+            g.solar_rows = engine.solar_source(A, U, self.solar_weights(g, lit), g.thermal[0], sun)
+            g.coeffs = (g.thermal[0], g.thermal[1] + g.solar_rows)
+        self._solar_key, self._solar_tabs = key, tabs
+
+    def solar_attenuation_jacobian(self, los, alt, w, coeffs, jac=None):
+        """The solar attenuation in the column rows of a state Jacobian: d rad / d x_p through tau for the column block
+        of the StateWeights `w` (its level masks w.col_masks and gases w.par_gas), added to rows 0 .. n_col - 1 of jac
+        [n_rays, n_rows, n_pts] (None: returned as its own [n_rays, n_col, n_pts]).  dU from
+        geometry.solar_column_weights at the solar pass's points (the middles of the shells, the tangent-SZA sun), Q by
+        ONE limb_rays_layer_jacobian call with dabs = 0 and demi = every solar gas's solar rows, then one fused call
+        (engine.solar_attenuation_jacobian).  Needs keep_solar_rows and the solar pass of the current state (`coeffs` is
+        coefficient_stack()'s pair); `alt` (the LOS sample altitudes) is not needed: the rows are the scene's layers.
+        limb_rays_layer_jacobian is a four-gas call."""
+        import torch
+        solar = self.solar_gases()
+        if not solar or any(getattr(g, "solar_rows", None) is None for g in solar):
+            raise ValueError("solar_attenuation_jacobian needs a sun, a solar gas and keep_solar_rows = True before the solar pass")
+        n_col = len(w.par_gas)
+        if n_col == 0:
+            return jac
+        top = self.z[-1] + (self.z[-1] - self.z[-2])
+        zz = np.append(self.z, top)
+        dU, _ = geometry.solar_column_weights(self.z, self.nd, w.col_masks, w.par_gas, len(self.gases), 0.5 * (zz[:-1] + zz[1:]),
+                                              self.sun.mu, R=self.R, n_sub=self.n_sub, col_scale=[g.iso_ratio for g in self.gases])
+        a, _ = engine.gas_stack(coeffs)
+        sol = torch.zeros_like(a)
+        for g in solar:
+            sol[self.gases.index(g)] = g.solar_rows
+        Q = engine.limb_rays_layer_jacobian(coeffs, (torch.zeros_like(a), sol), los)
+        if jac is None:
+            return engine.solar_attenuation_jacobian(a, dU, Q)
+        return engine.solar_attenuation_jacobian(a, dU, Q, out=jac, par_slot=np.arange(n_col), accumulate=True)
 
     def folded_into(self, g):
         return [t for t in self.folded if t.accumulate_into == g.name]
@@ -566,7 +622,7 @@ class LimbScene(object):
         names = [g.name for g in self.gases]
         top = self.z[-1] + (self.z[-1] - self.z[-2])
         zz = np.append(self.z, top)
-        par_gas, par_w_col, par_level, par_w_lev, par_w_temp, kind = [], [], [], [], [], []
+        par_gas, par_w_col, par_level, par_w_lev, par_w_temp, kind, col_masks = [], [], [], [], [], [], []
         level_gas, level_gases, par_lgas = None, [], []
         for name in bayes_set.order:
             st = bayes_set.sets[name]
@@ -577,6 +633,7 @@ class LimbScene(object):
                     m = np.asarray(par.maskgrid.mask, dtype=float)
                     par_gas.append(names.index(name))
                     par_w_col.append(np.interp(alt, zz, np.append(m, m[-1])))
+                    col_masks.append(m)
                     kind.append(0)
                 continue
             if name == "temp":
@@ -612,11 +669,13 @@ class LimbScene(object):
         perm = np.where(kind == 0, np.cumsum(kind == 0) - 1, n_col + np.cumsum(kind == 1) - 1).astype(int)
         if par_w_temp:
             perm = np.where(kind == 2, n_col + len(par_level) + np.cumsum(kind == 2) - 1, perm).astype(int)
-        return StateWeights(np.array(par_gas, np.int32), np.array(par_w_col, dtype=float).reshape(n_col, len(alt)), level_gas,
-                            None if level_gas is None else self.gases.index(level_gas), np.array(par_level, np.int32),
-                            np.array(par_w_lev, dtype=float).reshape(len(par_level), len(self.z)), perm,
-                            np.array(par_w_temp, dtype=float).reshape(len(par_w_temp), len(self.z)), level_gases,
-                            [self.gases.index(g) for g in level_gases], np.array(par_lgas, np.int32))
+        sw = StateWeights(np.array(par_gas, np.int32), np.array(par_w_col, dtype=float).reshape(n_col, len(alt)), level_gas,
+                          None if level_gas is None else self.gases.index(level_gas), np.array(par_level, np.int32),
+                          np.array(par_w_lev, dtype=float).reshape(len(par_level), len(self.z)), perm,
+                          np.array(par_w_temp, dtype=float).reshape(len(par_w_temp), len(self.z)), level_gases,
+                          [self.gases.index(g) for g in level_gases], np.array(par_lgas, np.int32))
+        sw.col_masks = np.array(col_masks, dtype=float).reshape(n_col, len(self.z))   # the column block's masks on the levels
+        return sw
 
     def temperature_derivatives(self):
         """(coeffs, dcoeffs): (abs, emi) of every gas at the CURRENT temperatures and their derivatives with respect to
@@ -1215,7 +1274,7 @@ def _state_call(scene, w, coeffs, dcoeffs, los, bands, **kw):
 
 
 def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM=0.1, L1_reg=False,
-                    fov_closed_form=True, bands_in_kernel=False):
+                    fov_closed_form=True, bands_in_kernel=False, solar_attenuation=False):
     """inversion_fast_limb's loop for a MIXED state vector: VMR-profile sets (named after a gas) together with the
     vibrational-temperature sets of one LevelGas or of several (TvibProfile; several: engine.LevelFactoredSet, the same one
     call per iteration with the level parameters of all of them) and the kinetic-temperature set (TempProfile; with it the
@@ -1239,9 +1298,21 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     iteration the lines of sight are the pixels' los_alts() plus the current offset, the calls are made with pointing=True
     on both routes and the pointing row (through the field of view like the others) is the set's Jacobian column, where
     the set stands in the BayesSet; it can stand beside an "instr" set.  The crossed shells are held fixed within an
-    iteration and rebuilt between iterations.  Without such a set nothing changes."""
+    iteration and rebuilt between iterations.  Without such a set nothing changes.
+    solar_attenuation=True, on a scene with solar gases: the VMR columns of every iteration's Jacobian carry the derivative
+    through the solar optical depth too (LimbScene.solar_attenuation_jacobian: the scene keeps its solar rows,
+    keep_solar_rows), added to the hi-res Jacobian before the band step, or, with bands_in_kernel, as hi-res rows of its
+    own through hires_to_lowres and the closed-form field of view (both linear) onto the fused call's band rows.  The
+    term's Q pass is a four-gas call: more gas slots raise ValueError.  False, or a scene without a sun: nothing changes.
+    The temperature, vibrational-temperature, pointing and instrument columns have no such term here."""
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)
     with_fov = _closed_form_fov(pixels, fov_closed_form, "inversion_state")
+    solar_att = bool(solar_attenuation) and bool(scene.solar_gases())
+    if solar_att:
+        if len(scene.gases) > engine.max_gases(folded=True):
+            raise ValueError("inversion_state(solar_attenuation=True): a scene of %d gas slots; the term's Q pass "
+                             "(engine.limb_rays_layer_jacobian) is a four-gas call" % len(scene.gases))
+        scene.keep_solar_rows = True
     alts0 = [a for pix in pixels for a in pix.los_alts()]
     # the sets' names are checked before anything is changed
     with_temp = scene.state_weights(bayes_set, np.zeros(1), several_level_gases=True).par_w_temp.shape[0] > 0
@@ -1278,6 +1349,13 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             if instr is not None:
                 band_args["instrument"] = True
             both = _state_call(scene, w, coeffs, dcoeffs, los, True, **band_args, **point_kw)
+            if solar_att and len(w.par_gas):    # the term as hi-res rows of its own, through the band step and the field of view
+                n_col = len(w.par_gas)
+                extra = lowres(scene.solar_attenuation_jacobian(los, alt, w, coeffs).view(n_los * n_col, -1)).reshape(n_los, n_col, -1)
+                if with_fov:
+                    extra = smm.fov_closed_form(extra[0::3], extra[1::3], extra[2::3], rots)
+                both = np.array(both)
+                both[:, 1:1 + n_col] += extra
             n_par = both.shape[1] - 1 - (0 if instr is None else 2) - (0 if point is None else 1)
             fov = both if with_fov else both[1::3]
             fov = np.concatenate([fov[:, :1, :], fov[:, 1:1 + n_par, :][:, w.perm], fov[:, 1 + n_par:, :]], axis=1)
@@ -1286,6 +1364,8 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
                 rad, jac = engine.limb_rays(coeffs, los, resident=False), None
             else:
                 rad, jac = _state_call(scene, w, coeffs, dcoeffs, los, False, **point_kw)
+                if solar_att:
+                    scene.solar_attenuation_jacobian(los, alt, w, coeffs, jac)
             n_rows = 0 if jac is None else jac.shape[1]
             n_par = n_rows - (0 if point is None else 1)               # (the pointing row stands behind the state's)
             order = np.concatenate([w.perm, np.arange(n_par, n_rows)]).astype(int)
