@@ -13,8 +13,8 @@ coefficient like any other (engine.solar_source).  Three parts:
                 inversion_state(..., solar_attenuation=True) adds the derivative through the solar optical depth to the
                 VMR columns: examples/retrieve_solar_attenuation.py
 
-The haze table is synthetic, the sun a black body at Saturn's distance.  Multiple scattering, refraction and a surface
-term are not built.  Needs an MI355X:  python examples/solar_haze_limb.py
+The haze table is synthetic, the sun a black body at Saturn's distance.  Multiple scattering above a Lambertian
+boundary is examples/multiple_scattering_haze.py; refraction is not built.  Needs an MI355X:  python examples/solar_haze_limb.py
 """
 import os
 import sys

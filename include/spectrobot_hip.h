@@ -1008,6 +1008,50 @@ int sr_solar_jacobian_rows_dev(const sr_solar_jac_desc *desc, const double *tab_
                                int64_t n_pts, const int32_t *par_slot, double *jac, int n_jac_rows, int accumulate,
                                void *stream);
 
+/* Multiple scattering of sunlight: the diffuse field of a plane-parallel two-stream solve per grid point, with delta
+ * scaling and a Lambertian lower boundary, as emission rows of a scatterer.  The build's own definition.
+ * Layers l = 0 .. N-1 bottom to top (N = n_layers), interfaces i = 0 .. N; per layer and grid point j, with
+ * t_g = v[g][l] tab_abs[g N + l][j] and f_g = max(asym_g, 0)^2:
+ *   sigma' = sum ssa_g (1 - f_g) t_g, alpha = sum (1 - ssa_g) t_g, dtau' = sigma' + alpha,
+ *   co = max(alpha / dtau', 2^-52), omega' = 1 - co, g' = sum ssa_g (asym_g - f_g) t_g / sigma' (0 where sigma' == 0)
+ * and the quadrature two-stream equations of Meador & Weaver (1980), tau downward, the source that of the layer's middle:
+ *   dF+/dtau = gamma1 F+ - gamma2 F- - S+,  dF-/dtau = gamma2 F+ - gamma1 F- + S-,
+ *   gamma1 -+ gamma2 = sqrt3 co, sqrt3 (1 - omega' g'),  gamma3 = (1 - sqrt3 g' mu0) / 2,
+ *   S+ = omega' D gamma3, S- = omega' D (1 - gamma3), D = sun[j] beam[l][j]
+ * with F-(top) = 0, F+(bottom) = surface_albedo (F-(bottom) + max(mu0, 0) sun[j] beam[N][j]) and F+- continuous at the
+ * interfaces; a layer with dtau' == 0 passes light through unchanged.  Outputs:
+ *   J_l[j] = sqrt3 (F+_l + F-_l + F+_{l+1} + F-_{l+1}) / (8 pi)          the mean diffuse intensity of layer l
+ *   emi_out[l][j] (+)= ssa_G (1 - f_G) tab_abs[G N + l][j] J_l[j]        G = out_gas
+ * The diffuse field holds light scattered once or more; scattered into the line of sight it is orders two and above
+ * (order one stays sr_solar_source_rows_dev's, with the exact phase function and the unscaled beam).  The direction-
+ * dependent term of the diffuse source is dropped.  Every output is >= 0; emi_out is an exact 0 for ssa_G == 0, every
+ * output where sun beam is 0 on all rows and surface_albedo is 0, or every ssa is 0 and surface_albedo is 0.
+ * desc: v HOST [n_gas][n_layers] >= 0, the vertical column of gas g in layer l; ssa HOST [n_gas] in [0, 1]; asym HOST
+ * [n_gas] in [-0.5, 1); mu0 in [-1, 1]; surface_albedo in [0, 1].  tab_abs DEVICE [n_gas n_layers][n_pts] (the stacked
+ * absorption rows, as sr_solar_source_rows_dev takes them); beam DEVICE [n_layers + 1][n_pts] in [0, 1]: the transmission
+ * of the direct beam at the layers' middle points and, row n_layers, at the lower boundary (the caller makes it, e.g. by
+ * sr_solar_source_rows_dev's trans_out with delta-scaled columns); sun DEVICE [n_pts] >= 0.  emi_out DEVICE
+ * [n_layers][n_pts], or NULL with out_gas = -1; j_out DEVICE [n_layers][n_pts] or NULL; flux_out DEVICE
+ * [2][n_layers + 1][n_pts] or NULL: F+, then F-, at the interfaces.  accumulate != 0 adds to emi_out.
+ * v and the per-gas coefficients are staged through the calling thread's pinned ring (no stream is made).  One thread
+ * per grid point walks the layers up, leaving four doubles per (layer, point) in a workspace of the calling thread (grow-
+ * only, at most 256 MiB per device; a larger call runs in point chunks, one launch after the other), and down again; the
+ * calls of one thread share that workspace, so they belong on one stream at a time.  One writer per element, no atomics,
+ * the same call gives the same bits.  Every argument is checked before the first copy or launch and a refused call
+ * leaves the outputs untouched: SR_ERR_ARG for a NULL desc, v, ssa, asym, tab_abs, beam or sun, n_gas <= 0,
+ * n_layers <= 0, n_pts <= 0, a v, ssa, asym, mu0 or surface_albedo that is not finite or outside its range, an out_gas
+ * outside -1 .. n_gas - 1, emi_out without out_gas or out_gas without emi_out, all three outputs NULL; SR_ERR_LIMIT for
+ * n_gas > 8, n_layers > SR_MAX_ABS_ROWS or n_pts > 2000000.
+ * Checked against an extended-precision reference (tests/test_gpu_diffuse_source.py). */
+typedef struct {
+  int32_t n_gas, n_layers;
+  const double *v, *ssa, *asym; /* [n_gas][n_layers], [n_gas], [n_gas] */
+  double mu0, surface_albedo;
+} sr_diffuse_desc;
+int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_abs, const double *beam, const double *sun,
+                               int64_t n_pts, int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out,
+                               void *stream);
+
 /* Evaluation mode of the coefficient op.  Far region-1 wings by local Taylor expansions per box of grid
  * points (truncation <= sr_far_field_truncation_bound() of a line's own contribution: 1.6e-11 as built by default, degree
  * 19; 2.6e-13 with -DSR_KFD=22; a box takes a line from sr_far_field_min_distance() on), near field exact, with the expansions built

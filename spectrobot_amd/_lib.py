@@ -88,6 +88,11 @@ class SolarJacDesc(C.Structure):
     _fields_ = [("n_par", C.c_int32), ("n_rows", C.c_int32), ("du", dp)]
 
 
+class DiffuseDesc(C.Structure):
+    _fields_ = [("n_gas", C.c_int32), ("n_layers", C.c_int32), ("v", dp), ("ssa", dp), ("asym", dp), ("mu0", C.c_double),
+                ("surface_albedo", C.c_double)]
+
+
 class IlsDesc(C.Structure):
     _fields_ = [("n_shapes", C.c_int32), ("n_tab", C.c_int32), ("t_lo", C.c_double), ("t_hi", C.c_double), ("phi", dp)]
 
@@ -224,6 +229,8 @@ SYMBOLS = {
     "sr_solar_jacobian_chunk_lists": (C.c_int, [C.POINTER(SolarJacDesc), C.c_int, ip, ip, ip]),
     "sr_solar_jacobian_rows_dev": (C.c_int, [C.POINTER(SolarJacDesc), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, ip,
                                              C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "sr_diffuse_source_rows_dev": (C.c_int, [C.POINTER(DiffuseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_set_points_per_lane": (C.c_int, [C.c_int]),
     "sr_set_band_fusion": (C.c_int, [C.c_int]),
     "sr_far_field_truncation_bound": (C.c_double, []),

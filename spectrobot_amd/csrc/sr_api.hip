@@ -4207,6 +4207,56 @@ int sr_solar_jacobian_rows_dev(const sr_solar_jac_desc *desc, const double *tab_
   return pk.slot().mark(st);
 }
 
+// The two-stream diffuse source of coefficient rows (sr_diffuse_source.inc).  The upward sweep's workspace, four doubles
+// per (layer, point), comes from a grow-only buffer per (thread, device); a call whose workspace would pass
+// kDiffuseWsBytes is made in point chunks, one launch after the other on `stream`.
+constexpr size_t kDiffuseWsBytes = (size_t)256 << 20;
+int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_abs, const double *beam, const double *sun,
+                               int64_t n_pts, int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out,
+                               void *stream) {
+  if (!desc || !desc->v || !desc->ssa || !desc->asym || !tab_abs || !beam || !sun) return SR_ERR_ARG;
+  if (desc->n_gas <= 0 || desc->n_layers <= 0 || n_pts <= 0) return SR_ERR_ARG;
+  if (desc->n_gas > kDiffuseGases || desc->n_layers > SR_MAX_ABS_ROWS || n_pts > 2000000) return SR_ERR_LIMIT;
+  const int n_gas = desc->n_gas, n_layers = desc->n_layers;
+  if (out_gas < -1 || out_gas >= n_gas || (out_gas < 0) != (emi_out == nullptr)) return SR_ERR_ARG;
+  if (!emi_out && !j_out && !flux_out) return SR_ERR_ARG;
+  if (!(desc->mu0 >= -1.0 && desc->mu0 <= 1.0) || !(desc->surface_albedo >= 0.0 && desc->surface_albedo <= 1.0)) return SR_ERR_ARG;
+  double coef[3 * kDiffuseGases] = {0.0}; // ssa (1 - f), 1 - ssa, ssa (asym - f): zeros beyond n_gas
+  double w_out = 0.0;
+  for (int g = 0; g < n_gas; ++g) {
+    const double ssa = desc->ssa[g], as = desc->asym[g];
+    if (!(ssa >= 0.0 && ssa <= 1.0) || !(as >= -0.5 && as < 1.0)) return SR_ERR_ARG; // (a NaN fails both)
+    const double f = as > 0.0 ? as * as : 0.0;
+    coef[g] = ssa * (1.0 - f);
+    coef[kDiffuseGases + g] = 1.0 - ssa;
+    coef[2 * kDiffuseGases + g] = ssa * (as - f);
+    if (g == out_gas) w_out = coef[g];
+  }
+  for (size_t i = 0; i < (size_t)n_gas * n_layers; ++i)
+    if (!(desc->v[i] >= 0.0) || !std::isfinite(desc->v[i])) return SR_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int pts_max = (int)std::max<size_t>(256, kDiffuseWsBytes / (32 * (size_t)n_layers) / 256 * 256);
+  const int chunk = (int)std::min<int64_t>(pts_max, (n_pts + 255) / 256 * 256);
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  static thread_local std::map<int, DevBuf> ws_pool; // one per device this thread has used
+  DevBuf &ws = ws_pool[dev];
+  int rc = ws.ensure((size_t)32 * n_layers * chunk);
+  if (rc) return rc;
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_v = pk.copy(desc->v, (size_t)n_gas * n_layers), p_c = pk.copy(coef, (size_t)3 * kDiffuseGases);
+  rc = pk.stage(st);
+  if (rc) return rc;
+  for (int64_t p_lo = 0; p_lo < n_pts; p_lo += chunk) {
+    const int p_hi = (int)std::min<int64_t>(n_pts, p_lo + chunk);
+    LAUNCHCHK(launch_diffuse_source(tab_abs, n_gas, n_layers, (int)n_pts, (int)p_lo, p_hi, pk.dev(p_v), pk.dev(p_c), beam, sun,
+                                    desc->mu0, desc->surface_albedo, out_gas, w_out, ws.as<double>(), chunk, accumulate != 0,
+                                    emi_out, j_out, flux_out, st));
+  }
+  return pk.slot().mark(st);
+}
+
 // ------------------------------------------------------------------------
 // f2py-shaped shims (host pointers)
 // ------------------------------------------------------------------------

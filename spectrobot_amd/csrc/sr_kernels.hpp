@@ -503,5 +503,13 @@ int launch_solar_source(const double *tab_abs, int n_k, int n_pts, const double 
 int launch_solar_jac(const double *tab_abs, int n_k, int n_pts, const double *du, int n_par, int n_rows, const int *tile_off,
                      const int *chunks, const double *q, int n_rays, const int *par_slot, bool accumulate, double *jac,
                      int n_jac_rows, hipStream_t st);
+// the two-stream diffuse source (sr_diffuse_source.inc) on the points [p_lo, p_hi) of the grid: v [n_gas][n_layers] and
+// coef [3][kDiffuseGases] (ssa (1 - f), 1 - ssa, ssa (asym - f); zeros beyond n_gas) staged device arrays, beam
+// [n_layers + 1][n_pts], ws [4][n_layers][ws_stride] with ws_stride >= the points rounded up to 256; emi_out (with out_gas
+// and w_out = ssa (1 - f) of that gas), j_out and flux_out may each be null.
+int launch_diffuse_source(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, const double *v,
+                          const double *coef, const double *beam, const double *sun, double mu0, double albedo, int out_gas,
+                          double w_out, double *ws, int ws_stride, bool accumulate, double *emi_out, double *j_out,
+                          double *flux_out, hipStream_t st);
 
 } // namespace sr

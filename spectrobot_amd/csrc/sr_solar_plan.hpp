@@ -13,6 +13,7 @@ namespace sr {
 constexpr int kSolarRows = 16; // rows of a tile: the MFMA's M
 constexpr int kSolarChunk = 4; // k per chunk: the MFMA's K
 constexpr int kSolarJacRays = 8; // NR: rays per block of sr_solar_jac_kernel (profiles/solar_jac_kernel_resources.txt)
+constexpr int kDiffuseGases = 8; // gas slots of sr_diffuse_source_kernel's loop (sr_diffuse_source.inc): n_gas above is refused
 
 // tile_off [n_tiles + 1] into chunks; n_tiles = ceil(n_rows / kSolarRows), chunk c covers k = 4 c .. 4 c + 3 (< n_k).
 // Returns false if an element of u is negative or not finite (the entry's check, in the same walk: u is the one large

@@ -1,10 +1,12 @@
 // sr_solar_source.hip -- the solar subject's unit: the single-scattering solar source of coefficient rows
 // (sr_solar_source_rows_dev: sr_solar_source.inc) and the solar attenuation in the Jacobians (sr_solar_jacobian_rows_dev:
-// sr_solar_jac.inc), each kernel's text and its launcher.  A translation unit of its own, compiled beside the others: no
+// sr_solar_jac.inc) and the two-stream diffuse source (sr_diffuse_source_rows_dev: sr_diffuse_source.inc), each kernel's
+// text and its launcher.  A translation unit of its own, compiled beside the others: no
 // other unit includes the kernels' text, and this one instantiates no other kernel.
 //
 //   sr_solar_source_kernel<ACC, TRANS>   four instances: overwrite / accumulate, with and without the transmission
 //   sr_solar_jac_kernel<NR, ACC>         two instances: overwrite / accumulate, NR = kSolarJacRays rays per block
+//   sr_diffuse_source_kernel<ACC, WJ, WF> eight instances: overwrite / accumulate, with and without j_out / flux_out
 #include "sr_device.hpp"
 #include "sr_kernels.hpp"
 #include "sr_solar_plan.hpp"
@@ -13,6 +15,7 @@ namespace sr {
 
 #include "sr_solar_source.inc"
 #include "sr_solar_jac.inc"
+#include "sr_diffuse_source.inc"
 
 int launch_solar_source(const double *tab_abs, int n_k, int n_pts, const double *u, const double *w, const int *src_row,
                         int n_rows, const int *tile_off, const int *chunks, const double *sca_abs, const double *sun,
@@ -44,6 +47,30 @@ int launch_solar_jac(const double *tab_abs, int n_k, int n_pts, const double *du
   else
     hipLaunchKernelGGL((sr_solar_jac_kernel<kSolarJacRays, false>), grid, dim3(256), 0, st, tab_abs, n_k, n_pts, du, n_par, n_rows,
                        tile_off, chunks, q, n_rays, par_slot, jac, n_jac_rows);
+  return (int)hipGetLastError();
+}
+
+int launch_diffuse_source(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, const double *v,
+                          const double *coef, const double *beam, const double *sun, double mu0, double albedo, int out_gas,
+                          double w_out, double *ws, int ws_stride, bool accumulate, double *emi_out, double *j_out,
+                          double *flux_out, hipStream_t st) {
+  if (n_layers <= 0 || p_hi <= p_lo) return 0;
+  const dim3 grid(limb_grid((p_hi - p_lo + 255) / 256, 1));
+  auto go = [&](auto acc, auto wj, auto wf) {
+    hipLaunchKernelGGL((sr_diffuse_source_kernel<decltype(acc)::value, decltype(wj)::value, decltype(wf)::value>), grid, dim3(256),
+                       0, st, tab_abs, n_gas, n_layers, n_pts, p_lo, p_hi, v, coef, beam, sun, mu0, albedo, out_gas, w_out, ws,
+                       ws_stride, emi_out, j_out, flux_out);
+  };
+  auto with_f = [&](auto acc, auto wj) {
+    if (flux_out) go(acc, wj, std::true_type{});
+    else go(acc, wj, std::false_type{});
+  };
+  auto with_j = [&](auto acc) {
+    if (j_out) with_f(acc, std::true_type{});
+    else with_f(acc, std::false_type{});
+  };
+  if (accumulate && emi_out) with_j(std::true_type{});
+  else with_j(std::false_type{});
   return (int)hipGetLastError();
 }
 

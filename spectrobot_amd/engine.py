@@ -645,6 +645,64 @@ def solar_source(A, U, w, sca, sun, src_row=None, out=None, accumulate=False, tr
     return (out, trans) if transmission else out
 
 
+def diffuse_source(A, V, ssa, asym, beam, sun, mu0, surface_albedo=0.0, out_gas=None, out=None, accumulate=False,
+                   mean_intensity=False, fluxes=False):
+    """Multiple scattering of sunlight as emission rows (sr_diffuse_source_rows_dev; the build's own definition, DESIGN.md
+    4.11b): per grid point a plane-parallel two-stream solve (Meador & Weaver's quadrature scheme) with delta scaling
+    and a Lambertian lower boundary under the direct beam `beam`, and
+
+        J[l] = sqrt3 (F+[l] + F-[l] + F+[l+1] + F-[l+1]) / (8 pi),   emi[l] (+)= ssa_G (1 - f_G) A[G, l] J[l]
+
+    for the gas G = out_gas, f = max(asym, 0)^2.  The diffuse field holds light scattered once or more, so these rows
+    are scattering orders two and above; order one stays solar_source's.
+
+    A: the stacked absorption rows of the scene, CUDA [n_gas, n_layers, n_pts] (the first tensor of gas_stack); V: host
+    [n_gas, n_layers] >= 0, the layers' vertical columns (geometry.vertical_columns); ssa [n_gas] in [0, 1] (0: an
+    absorber) and asym [n_gas] in [-0.5, 1): host; beam: CUDA [n_layers + 1, n_pts], the direct beam's transmission at the
+    layers' middle points and, last row, at the lower boundary (solar_source(..., transmission=True) with delta-scaled
+    columns); sun: CUDA [n_pts]; mu0 = cos SZA; surface_albedo in [0, 1]: what lies below the lowest level.
+    out_gas: the gas whose rows are made (None: no rows); out: CUDA [n_layers, n_pts], required with accumulate=True.
+    mean_intensity=True: also J [n_layers, n_pts]; fluxes=True: also F [2, n_layers + 1, n_pts], F+ then F- at the
+    interfaces.  One kernel, one writer per element; the same call gives the same bits.  Every Jacobian treats the rows
+    as coefficients.  Returns emi (if out_gas is given), then J, then F, as asked: one tensor or a tuple."""
+    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    if not (ok(A) and ok(beam) and ok(sun)) or A.dim() != 3 or beam.dim() != 2 or sun.dim() != 1:
+        raise ValueError("A, beam and sun must be contiguous CUDA float64 tensors ([n_gas, n_layers, n_pts], "
+                         "[n_layers + 1, n_pts], [n_pts])")
+    n_gas, n_layers, n_pts = (int(s) for s in A.shape)
+    if n_gas == 0 or n_layers == 0 or n_pts == 0:
+        raise ValueError("A must not be empty")
+    va, vp = _d(np.asarray(V, dtype=np.float64))
+    sa, sp = _d(np.broadcast_to(np.asarray(ssa, dtype=np.float64), (n_gas,)))
+    ga, gp = _d(np.broadcast_to(np.asarray(asym, dtype=np.float64), (n_gas,)))
+    if va.shape != (n_gas, n_layers):
+        raise ValueError("V must be [n_gas, n_layers] = [%d, %d]" % (n_gas, n_layers))
+    if beam.shape != (n_layers + 1, n_pts) or sun.shape[0] != n_pts:
+        raise ValueError("beam must be [n_layers + 1, n_pts] and sun [n_pts] on A's %d grid points" % n_pts)
+    if out_gas is None:
+        if out is not None or accumulate:
+            raise ValueError("out= and accumulate= belong to the rows of out_gas=")
+        if not (mean_intensity or fluxes):
+            raise ValueError("nothing asked for: out_gas=, mean_intensity=True or fluxes=True")
+    elif out is None:
+        if accumulate:
+            raise ValueError("accumulate=True adds to out=...")
+        out = torch.empty((n_layers, n_pts), dtype=torch.float64, device="cuda")
+    elif not ok(out) or out.shape != (n_layers, n_pts):
+        raise ValueError("out must be a contiguous CUDA float64 [n_layers, n_pts]")
+    J = torch.empty((n_layers, n_pts), dtype=torch.float64, device="cuda") if mean_intensity else None
+    F = torch.empty((2, n_layers + 1, n_pts), dtype=torch.float64, device="cuda") if fluxes else None
+    d = _lib.DiffuseDesc()
+    d.n_gas, d.n_layers, d.v, d.ssa, d.asym = n_gas, n_layers, vp, sp, gp
+    d.mu0, d.surface_albedo = float(mu0), float(surface_albedo)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    check(lib.sr_diffuse_source_rows_dev(C.byref(d), ptr(A), ptr(beam), ptr(sun), n_pts, -1 if out_gas is None else int(out_gas),
+                                         int(bool(accumulate)), ptr(out), ptr(J), ptr(F), _stream_ptr()),
+          "sr_diffuse_source_rows_dev")
+    res = tuple(t for t in (out, J, F) if t is not None)
+    return res[0] if len(res) == 1 else res
+
+
 SOLAR_JAC_RAYS = 8      # rays per block of sr_solar_jac_kernel (kSolarJacRays): where the ray-group edge of a call sits
 
 

@@ -445,6 +445,20 @@ def _solar_columns(z, nd_levels, vmr_levels, alt, mu, R, n_sub, col_scale, colum
     return U, lit
 
 
+def vertical_columns(z, nd_levels, vmr_levels, R=TITAN_RADIUS_KM, n_sub=3, col_scale=None):
+    """Vertical columns of the layers: V [n_gas, n_layers] (molecules cm^-2 of gas g in the shell above level l), what
+    engine.diffuse_source takes.  solar_columns for the one point at z[0] with mu = 1: a radial ray's column in a shell
+    is that shell's vertical column (the same sampling, profiles and column routine as every other column here)."""
+    return _vertical_columns(z, nd_levels, vmr_levels, R, n_sub, col_scale, _device_columns)
+
+
+def _vertical_columns(z, nd_levels, vmr_levels, R, n_sub, col_scale, columns):
+    """vertical_columns with the column routine given, as _solar_columns."""
+    z0 = float(np.atleast_1d(np.asarray(z, float))[0])
+    U, _ = _solar_columns(z, nd_levels, vmr_levels, [z0], 1.0, R, n_sub, col_scale, columns)
+    return np.ascontiguousarray(U[0])
+
+
 def _solar_rays(z, zz, ln, alt, mu, R, n_sub):
     """The sun rays of _solar_columns without a profile on them: (lit [n_rows], limb_los's dict of the rays' crossings
     with x, nd and alt but no vmr -- None when no ray crosses anything).  z, zz, ln: _profiles' levels."""

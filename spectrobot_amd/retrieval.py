@@ -140,7 +140,9 @@ class TableGas(Gas):
     solar=dict(albedo=, g=): the gas scatters sunlight once into the line of sight (single-scattering albedo, Henyey-
     Greenstein asymmetry parameter).  In a LimbScene with a sun its emission rows are thermal + solar: the scene adds
     sca S to a copy of the thermal pair's emi (engine.solar_source; `thermal` keeps the cached pair).  The solar
-    attenuation is held fixed under every Jacobian within one linearisation; multiple scattering is not built."""
+    attenuation is held fixed under every Jacobian within one linearisation.  Under a Sun(multiple=True) the rows also
+    carry the diffuse field's light (orders two and above, engine.diffuse_source), with `albedo` as the single-scattering
+    albedo and `g` as the asymmetry parameter of a delta-scaled two-stream solve; g must then be >= -0.5."""
 
     def __init__(self, name, table, vmr, scale=None, source=True, iso_ratio=1.0, accumulate_into=None, solar=None):
         Gas.__init__(self, name, None, vmr, iso_ratio=iso_ratio)
@@ -186,13 +188,23 @@ class TableGas(Gas):
 class Sun(object):
     """The sun of a LimbScene: solar zenith angle at the tangent point and phase angle (sun - target - observer), in
     degrees, and the irradiance at the planet on the scene's grid [n_grid] (geometry.solar_irradiance), in units
-    consistent with the scene's emission rows.  The scattering angle is 180 deg - phase."""
+    consistent with the scene's emission rows.  The scattering angle is 180 deg - phase.
 
-    def __init__(self, sza_deg, phase_deg, irradiance):
+    multiple=True: the solar gases' emission rows also carry sunlight scattered twice or more -- the diffuse field of a
+    plane-parallel two-stream solve under the (spherical, delta-scaled) direct beam, engine.diffuse_source, DESIGN.md
+    4.11b; order one stays the single-scattering rows.  surface_albedo (0 .. 1) is the Lambertian albedo of what lies
+    BELOW z[0]: a scene whose grid starts above the ground uses 0, so that everything below absorbs.  It is read with
+    multiple=True only.  The diffuse rows are held fixed under every Jacobian within one linearisation, as the other
+    solar rows are."""
+
+    def __init__(self, sza_deg, phase_deg, irradiance, multiple=False, surface_albedo=0.0):
         self.sza_deg, self.phase_deg = float(sza_deg), float(phase_deg)
         self.irradiance = np.ascontiguousarray(irradiance, dtype=float)
         if self.irradiance.ndim != 1 or not np.all(np.isfinite(self.irradiance)) or np.any(self.irradiance < 0):
             raise ValueError("the irradiance is a finite, non-negative array on the scene's grid")
+        self.multiple, self.surface_albedo = bool(multiple), float(surface_albedo)
+        if not 0.0 <= self.surface_albedo <= 1.0:
+            raise ValueError("surface_albedo is a Lambertian albedo in [0, 1]")
 
     @property
     def mu(self):
@@ -203,7 +215,8 @@ class Sun(object):
         return float(np.cos(np.deg2rad(180.0 - self.phase_deg)))
 
     def key(self):
-        return (self.sza_deg, self.phase_deg, engine._content_key(self.irradiance))
+        key = (self.sza_deg, self.phase_deg, engine._content_key(self.irradiance))
+        return key + (True, self.surface_albedo) if self.multiple else key
 
 
 def _refuse_many_slots(scene, who):
@@ -392,6 +405,10 @@ class LimbScene(object):
                                       # solar_attenuation_jacobian works on (inversion_state(solar_attenuation=True) sets it)
         if sun is not None and sun.irradiance.shape != self.grid.shape:
             raise ValueError("the sun's irradiance must be given on the scene's grid")
+        if sun is not None and getattr(sun, "multiple", False):
+            for g in gases:
+                if getattr(g, "solar", None) is not None and g.solar["g"] < -0.5:
+                    raise ValueError("Sun(multiple=True): gas %r has g = %g, the two-stream solve takes g >= -0.5" % (g.name, g.solar["g"]))
         self.z, self.temps, self.press = (np.asarray(v, dtype=float) for v in (z, temps, press))
         self.nd = syn.number_density(self.press, self.temps)
         # a TableGas with accumulate_into has no slot: it is folded into a line gas's pair (self.folded)
@@ -466,6 +483,8 @@ class LimbScene(object):
             emi = g.thermal[1].clone()
             engine.solar_source(A, U, self.solar_weights(g, lit), g.thermal[0], sun, out=emi, accumulate=True)
             g.coeffs = (g.thermal[0], emi)
+        if self.sun.multiple:
+            self.diffuse_pass(solar, A, sun)
         # (the tables themselves are kept beside the key: an id in it stays theirs while they live here.  The key knows a
         # table by identity, as coefficient_stack does: every rebuild in this package makes new tensors; a caller who
         # overwrites a table IN PLACE sets scene._solar_key = None)
@@ -492,7 +511,43 @@ class LimbScene(object):
         for g in solar:
             g.solar_rows = engine.solar_source(A, U, self.solar_weights(g, lit), g.thermal[0], sun)
             g.coeffs = (g.thermal[0], g.thermal[1] + g.solar_rows)
+        if self.sun.multiple:       # (g.solar_rows stays the single-scattered part alone)
+            self.diffuse_pass(solar, A, sun)
         self._solar_key, self._solar_tabs = key, tabs
+
+    def diffuse_inputs(self, solar, A, sun):
+        """(V, ssa, asym, beam) of engine.diffuse_source for the scene's state: the layers' vertical columns, the solar
+        gases' single-scattering albedos and asymmetry parameters (0 for every other gas) and the direct beam at the
+        middles of the shells and at the level z[0] -- one more engine.solar_source(..., transmission=True) call with
+        every solar gas's columns scaled by 1 - ssa f, f = max(g, 0)^2: the delta-scaled beam, in spherical geometry."""
+        ssa = np.array([g.solar["albedo"] if g in solar else 0.0 for g in self.gases])
+        asym = np.array([g.solar["g"] if g in solar else 0.0 for g in self.gases])
+        iso = np.array([float(g.iso_ratio) for g in self.gases])
+        vmr = [g.vmr for g in self.gases]
+        top = self.z[-1] + (self.z[-1] - self.z[-2])
+        zz = np.append(self.z, top)
+        pts = np.append(0.5 * (zz[:-1] + zz[1:]), self.z[0])
+        Ub, lit = geometry.solar_columns(self.z, self.nd, vmr, pts, self.sun.mu, R=self.R, n_sub=self.n_sub,
+                                         col_scale=iso * (1.0 - ssa * np.maximum(asym, 0.0) ** 2))
+        _, beam = engine.solar_source(A, Ub, np.where(lit, 1.0, 0.0), A[self.gases.index(solar[0])], sun,
+                                      src_row=np.zeros(len(pts), np.int32), transmission=True)
+        V = geometry.vertical_columns(self.z, self.nd, vmr, R=self.R, n_sub=self.n_sub, col_scale=iso)
+        return V, ssa, asym, beam
+
+    def diffuse_pass(self, solar, A, sun):
+        """Adds the diffuse rows (Sun(multiple=True)) to the emission rows the solar pass has just made: one
+        engine.diffuse_source call -- with one solar gas the fused accumulate, with several the mean intensity once and
+        a torch.addcmul per gas."""
+        V, ssa, asym, beam = self.diffuse_inputs(solar, A, sun)
+        kw = dict(surface_albedo=self.sun.surface_albedo)
+        if len(solar) == 1:
+            engine.diffuse_source(A, V, ssa, asym, beam, sun, self.sun.mu, out_gas=self.gases.index(solar[0]),
+                                  out=solar[0].coeffs[1], accumulate=True, **kw)
+            return
+        J = engine.diffuse_source(A, V, ssa, asym, beam, sun, self.sun.mu, mean_intensity=True, **kw)
+        for g in solar:
+            i = self.gases.index(g)
+            g.coeffs[1].addcmul_(A[i], J, value=float(ssa[i] * (1.0 - max(asym[i], 0.0) ** 2)))
 
     def solar_attenuation_jacobian(self, los, alt, w, coeffs, jac=None):
         """The solar attenuation in the column rows of a state Jacobian: d rad / d x_p through tau for the column block
