@@ -1052,6 +1052,49 @@ int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_ab
                                int64_t n_pts, int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out,
                                void *stream);
 
+/* The diffuse rows in the Jacobians: d radiance / d (column parameter) THROUGH the two-stream solve of
+ * sr_diffuse_source_rows_dev.  The build's own definition.  A parameter x_p moves, per layer l and grid
+ * point j, in the notation above,
+ *   d t_g[l] = dv[p][g][l] tab_abs[g N + l][j],   d D_l = D_l dlnbeam[p][l][j],   d Ub_0 = Ub_0 dlnbeam[p][N][j]
+ * (Ub_0 = surface_albedo max(mu0, 0) sun beam[N], the boundary's term) and dJ[p][l][j] is the tangent of J_l along that
+ * direction, of the function AS BUILT: co = max(alpha / dtau', 2^-52) has derivative 0 where the floor holds, g' = 0 where
+ * sigma' == 0 has derivative 0 there, and a layer with dtau' == 0 passes light through whatever dv says (every derivative
+ * of its operators is 0).  Then
+ *   jac[y][par_slot[p]][j] (+)= sum_{l < N} q[y][l][j] dJ[p][l][j]            l ascending, one writer per element
+ * with q[y][l] = d rad[y] / d J_l: sr_limb_rays_jac_layer_dev with dabs = 0 and demi[g] = ssa_g (1 - f_g) tab_abs[g] for
+ * every solar gas (per unit J, so that a row in shadow, J = 0, enters no division).
+ * desc: as sr_diffuse_source_rows_dev takes it, the state the tangent is taken at.  jdesc: dv HOST [n_par][n_gas][n_layers]
+ * = d v / d x_p (geometry.vertical_column_weights: any finite sign, dense, mostly zeros, read as it is).  tab_abs, beam, sun:
+ * as above.  dlnbeam DEVICE [n_par][n_layers + 1][n_pts] = d ln beam / d x_p, finite, row n_layers the boundary's, or NULL:
+ * the beam is held fixed.  q DEVICE [n_rays][n_layers][n_pts], finite, and jac DEVICE [n_rays][n_jac_rows][n_pts] come
+ * together, or both NULL with dj_out; parameter p in row par_slot[p] (HOST [n_par], each row named at most once), the rows
+ * not named are left as they are; accumulate != 0 adds to the rows named.  dj_out DEVICE [n_par][n_layers][n_pts] or NULL:
+ * dJ itself (always overwritten), the counterpart of j_out.
+ * v, dv, the per-gas coefficients, par_slot and per parameter the range of layers with any non-zero dv (made on the host
+ * before any device work; outside it the layer operators stand still and only the sources follow the beam) are staged
+ * through the calling thread's pinned ring (no stream is made).  Two kernels on `stream`: one thread per grid point and
+ * tile of four parameters walks the layers up and down with the tangents beside the base quantities (19 doubles per
+ * (tile, layer, point) in the source's workspace, 23 without dj_out), then the product with q as a register tile of
+ * 8 rays x 4 parameters.  A call whose workspace would pass 256 MiB runs in point chunks and groups of parameter tiles, one
+ * launch after the other: a parameter's rows do not depend on the tile it stands in, a point's not on its chunk.  The
+ * workspace is the one sr_diffuse_source_rows_dev uses, one per (calling thread, device): the calls of one thread to
+ * either entry belong on one stream at a time (two streams would race on it).  No
+ * atomics, the same call gives the same bits.  Every argument is checked before the first copy or launch and a refused
+ * call leaves the outputs untouched, in this order: SR_ERR_ARG for a NULL desc, v, ssa, asym, jdesc, dv, tab_abs, beam or
+ * sun, n_gas <= 0, n_layers <= 0, n_pts <= 0, n_par <= 0, q without jac or jac without q, neither jac nor dj_out, jac
+ * without par_slot or with n_rays <= 0 or n_jac_rows <= 0, a v, ssa, asym, mu0 or surface_albedo that is not finite or
+ * outside its range; SR_ERR_ARG for a dv that is not finite; SR_ERR_LIMIT for n_gas > 8, n_layers > SR_MAX_ABS_ROWS,
+ * n_pts > 2000000 or n_par n_gas n_layers > SR_MAX_SOLAR_VALUES; SR_ERR_ARG for a par_slot outside 0 .. n_jac_rows - 1 or
+ * named twice.  Checked against an extended-precision reference (tests/test_gpu_diffuse_jacobian.py). */
+typedef struct {
+  int32_t n_par;
+  const double *dv; /* [n_par][n_gas][n_layers] */
+} sr_diffuse_jac_desc;
+int sr_diffuse_jacobian_rows_dev(const sr_diffuse_desc *desc, const sr_diffuse_jac_desc *jdesc, const double *tab_abs,
+                                 const double *beam, const double *sun, const double *dlnbeam, const double *q, int n_rays,
+                                 int64_t n_pts, const int32_t *par_slot, double *jac, int n_jac_rows, int accumulate,
+                                 double *dj_out, void *stream);
+
 /* Evaluation mode of the coefficient op.  Far region-1 wings by local Taylor expansions per box of grid
  * points (truncation <= sr_far_field_truncation_bound() of a line's own contribution: 1.6e-11 as built by default, degree
  * 19; 2.6e-13 with -DSR_KFD=22; a box takes a line from sr_far_field_min_distance() on), near field exact, with the expansions built

@@ -93,6 +93,10 @@ class DiffuseDesc(C.Structure):
                 ("surface_albedo", C.c_double)]
 
 
+class DiffuseJacDesc(C.Structure):
+    _fields_ = [("n_par", C.c_int32), ("dv", dp)]
+
+
 class IlsDesc(C.Structure):
     _fields_ = [("n_shapes", C.c_int32), ("n_tab", C.c_int32), ("t_lo", C.c_double), ("t_hi", C.c_double), ("phi", dp)]
 
@@ -231,6 +235,9 @@ SYMBOLS = {
                                              C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "sr_diffuse_source_rows_dev": (C.c_int, [C.POINTER(DiffuseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_diffuse_jacobian_rows_dev": (C.c_int, [C.POINTER(DiffuseDesc), C.POINTER(DiffuseJacDesc), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, ip, C.c_void_p, C.c_int,
+                                               C.c_int, C.c_void_p, C.c_void_p]),
     "sr_set_points_per_lane": (C.c_int, [C.c_int]),
     "sr_set_band_fusion": (C.c_int, [C.c_int]),
     "sr_far_field_truncation_bound": (C.c_double, []),

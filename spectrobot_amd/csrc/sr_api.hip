@@ -4211,6 +4211,11 @@ int sr_solar_jacobian_rows_dev(const sr_solar_jac_desc *desc, const double *tab_
 // per (layer, point), comes from a grow-only buffer per (thread, device); a call whose workspace would pass
 // kDiffuseWsBytes is made in point chunks, one launch after the other on `stream`.
 constexpr size_t kDiffuseWsBytes = (size_t)256 << 20;
+static DevBuf &diffuse_workspace(int dev) { // shared by the source and its Jacobian: one per device this thread has used
+  static thread_local std::map<int, DevBuf> ws_pool;
+  return ws_pool[dev];
+}
+
 int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_abs, const double *beam, const double *sun,
                                int64_t n_pts, int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out,
                                void *stream) {
@@ -4239,8 +4244,7 @@ int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_ab
   const int chunk = (int)std::min<int64_t>(pts_max, (n_pts + 255) / 256 * 256);
   int dev = 0;
   HIPCHK(hipGetDevice(&dev));
-  static thread_local std::map<int, DevBuf> ws_pool; // one per device this thread has used
-  DevBuf &ws = ws_pool[dev];
+  DevBuf &ws = diffuse_workspace(dev);
   int rc = ws.ensure((size_t)32 * n_layers * chunk);
   if (rc) return rc;
   static thread_local StagerRing ring;
@@ -4253,6 +4257,88 @@ int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_ab
     LAUNCHCHK(launch_diffuse_source(tab_abs, n_gas, n_layers, (int)n_pts, (int)p_lo, p_hi, pk.dev(p_v), pk.dev(p_c), beam, sun,
                                     desc->mu0, desc->surface_albedo, out_gas, w_out, ws.as<double>(), chunk, accumulate != 0,
                                     emi_out, j_out, flux_out, st));
+  }
+  return pk.slot().mark(st);
+}
+
+// The diffuse rows in the Jacobians (sr_diffuse_jac.inc).  The workspace is the source's: per (parameter tile, point)
+// 3 + 4 kDiffuseJacPars doubles per layer for the two sweeps and, where the caller takes no dj_out, kDiffuseJacPars more
+// for the dJ rows the contraction reads; a call whose workspace would pass kDiffuseWsBytes is made in point chunks and
+// groups of parameter tiles, a tangent launch and a contraction launch each, one after the other on `stream`.
+int sr_diffuse_jacobian_rows_dev(const sr_diffuse_desc *desc, const sr_diffuse_jac_desc *jdesc, const double *tab_abs,
+                                 const double *beam, const double *sun, const double *dlnbeam, const double *q, int n_rays,
+                                 int64_t n_pts, const int32_t *par_slot, double *jac, int n_jac_rows, int accumulate,
+                                 double *dj_out, void *stream) {
+  if (!desc || !desc->v || !desc->ssa || !desc->asym || !jdesc || !jdesc->dv || !tab_abs || !beam || !sun) return SR_ERR_ARG;
+  if (desc->n_gas <= 0 || desc->n_layers <= 0 || n_pts <= 0 || jdesc->n_par <= 0) return SR_ERR_ARG;
+  if ((q == nullptr) != (jac == nullptr) || (!jac && !dj_out)) return SR_ERR_ARG; // q and jac come together; something is asked for
+  if (jac && (!par_slot || n_rays <= 0 || n_jac_rows <= 0)) return SR_ERR_ARG;
+  if (!(desc->mu0 >= -1.0 && desc->mu0 <= 1.0) || !(desc->surface_albedo >= 0.0 && desc->surface_albedo <= 1.0)) return SR_ERR_ARG;
+  const int64_t n_gas64 = desc->n_gas, n_layers64 = desc->n_layers, n_par64 = jdesc->n_par;
+  // (the sizes are bounded before the arrays they describe are walked; the limits are reported after dv's check)
+  const bool too_large = n_gas64 > kDiffuseGases || n_layers64 > SR_MAX_ABS_ROWS || n_pts > 2000000 ||
+                         n_par64 * n_gas64 * n_layers64 > SR_MAX_SOLAR_VALUES;
+  if (!too_large) {
+    for (int g = 0; g < desc->n_gas; ++g) {
+      const double ssa = desc->ssa[g], as = desc->asym[g];
+      if (!(ssa >= 0.0 && ssa <= 1.0) || !(as >= -0.5 && as < 1.0)) return SR_ERR_ARG; // (a NaN fails both)
+    }
+    for (size_t i = 0; i < (size_t)(n_gas64 * n_layers64); ++i)
+      if (!(desc->v[i] >= 0.0) || !std::isfinite(desc->v[i])) return SR_ERR_ARG;
+  }
+  std::vector<int> mask;
+  if (!too_large && !diffuse_jac_masks(desc->v, jdesc->dv, jdesc->n_par, desc->n_gas, desc->n_layers, mask)) return SR_ERR_ARG;
+  if (too_large) return SR_ERR_LIMIT;
+  const int n_gas = desc->n_gas, n_layers = desc->n_layers, n_par = jdesc->n_par;
+  if (jac) { // one writer per element: a row of jac belongs to one parameter
+    std::vector<int> slots(par_slot, par_slot + n_par);
+    std::sort(slots.begin(), slots.end());
+    if (slots.front() < 0 || slots.back() >= n_jac_rows || std::adjacent_find(slots.begin(), slots.end()) != slots.end()) return SR_ERR_ARG;
+  }
+  double coef[3 * kDiffuseGases] = {0.0}; // ssa (1 - f), 1 - ssa, ssa (asym - f): zeros beyond n_gas
+  for (int g = 0; g < n_gas; ++g) {
+    const double ssa = desc->ssa[g], as = desc->asym[g];
+    const double f = as > 0.0 ? as * as : 0.0;
+    coef[g] = ssa * (1.0 - f);
+    coef[kDiffuseGases + g] = 1.0 - ssa;
+    coef[2 * kDiffuseGases + g] = ssa * (as - f);
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // the workspace: doubles per (tile, layer, point), then points per launch, then tiles per launch
+  const bool dj_ws = jac && !dj_out;
+  const size_t per = (size_t)8 * n_layers * (3 + 4 * kDiffuseJacPars + (dj_ws ? kDiffuseJacPars : 0));
+  const int n_tiles = (n_par + kDiffuseJacPars - 1) / kDiffuseJacPars;
+  const int pts_max = (int)std::max<size_t>(256, kDiffuseWsBytes / per / 256 * 256);
+  const int chunk = (int)std::min<int64_t>(pts_max, (n_pts + 255) / 256 * 256);
+  const int tiles = (int)std::min<size_t>((size_t)n_tiles, std::max<size_t>(1, kDiffuseWsBytes / (per * (size_t)chunk)));
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  DevBuf &ws = diffuse_workspace(dev);
+  int rc = ws.ensure(per * (size_t)chunk * tiles);
+  if (rc) return rc;
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_v = pk.copy(desc->v, (size_t)n_gas * n_layers), p_c = pk.copy(coef, (size_t)3 * kDiffuseGases);
+  const auto p_dv = pk.copy(jdesc->dv, (size_t)n_par * n_gas * n_layers);
+  const auto p_m = pk.copy(mask.data(), mask.size());
+  const auto p_slot = pk.copy(par_slot, jac ? (size_t)n_par : 0, 1);
+  rc = pk.stage(st);
+  if (rc) return rc;
+  double *sweep = ws.as<double>();
+  double *dj_room = sweep + (size_t)tiles * (3 + 4 * kDiffuseJacPars) * n_layers * chunk; // (used with dj_ws only)
+  for (int64_t p_lo = 0; p_lo < n_pts; p_lo += chunk) {
+    const int p_hi = (int)std::min<int64_t>(n_pts, p_lo + chunk);
+    for (int t0 = 0; t0 < n_tiles; t0 += tiles) {
+      const int par_lo = t0 * kDiffuseJacPars, par_hi = std::min(n_par, (t0 + tiles) * kDiffuseJacPars);
+      double *dj = dj_ws ? dj_room : dj_out;
+      const int dj_stride = dj_ws ? chunk : (int)n_pts, dj_joff = dj_ws ? (int)p_lo : 0, dj_par0 = dj_ws ? par_lo : 0;
+      LAUNCHCHK(launch_diffuse_tangent(tab_abs, n_gas, n_layers, (int)n_pts, (int)p_lo, p_hi, par_lo, par_hi, pk.dev(p_v),
+                                       pk.dev(p_dv), pk.dev(p_c), pk.dev(p_m), beam, sun, dlnbeam, desc->mu0, desc->surface_albedo,
+                                       sweep, chunk, dj, dj_stride, dj_joff, dj_par0, st));
+      if (jac)
+        LAUNCHCHK(launch_diffuse_contract(q, n_rays, n_layers, (int)n_pts, (int)p_lo, p_hi, par_lo, par_hi, dj, dj_stride, dj_joff,
+                                          dj_par0, pk.dev(p_slot), accumulate != 0, jac, n_jac_rows, st));
+    }
   }
   return pk.slot().mark(st);
 }

@@ -511,5 +511,18 @@ int launch_diffuse_source(const double *tab_abs, int n_gas, int n_layers, int n_
                           const double *coef, const double *beam, const double *sun, double mu0, double albedo, int out_gas,
                           double w_out, double *ws, int ws_stride, bool accumulate, double *emi_out, double *j_out,
                           double *flux_out, hipStream_t st);
+// the diffuse rows in the Jacobians (sr_diffuse_jac.inc) on the points [p_lo, p_hi) and the parameters [par_lo, par_hi):
+// dv [n_par][n_gas][n_layers], mask [n_par][2] (diffuse_jac_masks, sr_solar_plan.hpp), v and coef as above: staged device
+// arrays; dlnbeam [n_par][n_layers + 1][n_pts] or null; ws [tiles][3 + 4 kDiffuseJacPars][n_layers][ws_stride], tiles =
+// ceil((par_hi - par_lo) / kDiffuseJacPars), ws_stride >= the points rounded up to 256; dJ of (p, l, j) goes to
+// dj[((p - dj_par0) n_layers + l) dj_stride + j - dj_joff].  The contraction reads it from there and q [n_rays][n_layers]
+// [n_pts] and writes jac[ray][par_slot[p]][j]; its grid is limb_grid(point blocks, parameter tiles x ray tiles).
+int launch_diffuse_tangent(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, int par_lo, int par_hi,
+                           const double *v, const double *dv, const double *coef, const int *mask, const double *beam,
+                           const double *sun, const double *dlnbeam, double mu0, double albedo, double *ws, int ws_stride,
+                           double *dj, int dj_stride, int dj_joff, int dj_par0, hipStream_t st);
+int launch_diffuse_contract(const double *q, int n_rays, int n_layers, int n_pts, int p_lo, int p_hi, int par_lo, int par_hi,
+                            const double *dj, int dj_stride, int dj_joff, int dj_par0, const int *par_slot, bool accumulate,
+                            double *jac, int n_jac_rows, hipStream_t st);
 
 } // namespace sr

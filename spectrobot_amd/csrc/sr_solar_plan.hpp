@@ -14,6 +14,8 @@ constexpr int kSolarRows = 16; // rows of a tile: the MFMA's M
 constexpr int kSolarChunk = 4; // k per chunk: the MFMA's K
 constexpr int kSolarJacRays = 8; // NR: rays per block of sr_solar_jac_kernel (profiles/solar_jac_kernel_resources.txt)
 constexpr int kDiffuseGases = 8; // gas slots of sr_diffuse_source_kernel's loop (sr_diffuse_source.inc): n_gas above is refused
+constexpr int kDiffuseJacPars = 4; // NP: parameters per block of sr_diffuse_tangent_kernel and per thread of the contraction
+constexpr int kDiffuseJacRays = 8; // NR: rays per thread of sr_diffuse_contract_kernel (profiles/diffuse_jacobian_kernel_resources.txt)
 
 // tile_off [n_tiles + 1] into chunks; n_tiles = ceil(n_rows / kSolarRows), chunk c covers k = 4 c .. 4 c + 3 (< n_k).
 // Returns false if an element of u is negative or not finite (the entry's check, in the same walk: u is the one large
@@ -77,6 +79,34 @@ inline bool solar_jac_chunk_lists(const double *du, int n_par, int n_rows, int n
         if (hit[(size_t)c]) chunks.push_back(c);
       tile_off.push_back((int)chunks.size());
     }
+  return ok;
+}
+
+// The plan of sr_diffuse_tangent_kernel (sr_diffuse_jac.inc; tools/diffuse_jacobian_host): per parameter the layer range
+// mask[2 p] .. mask[2 p + 1] - 1 that holds every layer with a non-zero dv[p][.][l] (lo = hi = 0: none) of
+// dv [n_par][n_gas][n_layers]; outside it the layer operators have no tangent.  A layer without any column (every
+// v[g][l] == 0) has dtau == 0 at every point and no tangent whatever dv says: it widens no range.  Returns false if an
+// element of dv is not finite.
+inline bool diffuse_jac_masks(const double *v, const double *dv, int n_par, int n_gas, int n_layers, std::vector<int> &mask) {
+  mask.assign((size_t)2 * n_par, 0);
+  bool ok = true;
+  std::vector<char> filled((size_t)n_layers, 0);
+  for (int g = 0; g < n_gas; ++g)
+    for (int l = 0; l < n_layers; ++l) filled[(size_t)l] |= (char)(v[(size_t)g * n_layers + l] != 0.0);
+  for (int p = 0; p < n_par; ++p) {
+    int lo = n_layers, hi = 0;
+    for (int g = 0; g < n_gas; ++g) {
+      const double *row = dv + ((size_t)p * n_gas + g) * n_layers;
+      for (int l = 0; l < n_layers; ++l) {
+        ok &= (row[l] >= -1.7976931348623157e308) & (row[l] <= 1.7976931348623157e308); // (a NaN fails both)
+        if (row[l] != 0.0 && filled[(size_t)l]) {
+          lo = l < lo ? l : lo;
+          hi = l + 1 > hi ? l + 1 : hi;
+        }
+      }
+    }
+    if (hi > lo) mask[(size_t)2 * p] = lo, mask[(size_t)2 * p + 1] = hi;
+  }
   return ok;
 }
 

@@ -1,12 +1,14 @@
 // sr_solar_source.hip -- the solar subject's unit: the single-scattering solar source of coefficient rows
 // (sr_solar_source_rows_dev: sr_solar_source.inc) and the solar attenuation in the Jacobians (sr_solar_jacobian_rows_dev:
-// sr_solar_jac.inc) and the two-stream diffuse source (sr_diffuse_source_rows_dev: sr_diffuse_source.inc), each kernel's
-// text and its launcher.  A translation unit of its own, compiled beside the others: no
+// sr_solar_jac.inc) and the two-stream diffuse source (sr_diffuse_source_rows_dev: sr_diffuse_source.inc) and its tangent
+// in the Jacobians (sr_diffuse_jacobian_rows_dev: sr_diffuse_jac.inc), each kernel's text and its launcher.  A translation unit of its own, compiled beside the others: no
 // other unit includes the kernels' text, and this one instantiates no other kernel.
 //
 //   sr_solar_source_kernel<ACC, TRANS>   four instances: overwrite / accumulate, with and without the transmission
 //   sr_solar_jac_kernel<NR, ACC>         two instances: overwrite / accumulate, NR = kSolarJacRays rays per block
 //   sr_diffuse_source_kernel<ACC, WJ, WF> eight instances: overwrite / accumulate, with and without j_out / flux_out
+//   sr_diffuse_tangent_kernel<NP>         one instance: NP = kDiffuseJacPars parameters per block
+//   sr_diffuse_contract_kernel<NR, NP, ACC> two instances: overwrite / accumulate, kDiffuseJacRays x kDiffuseJacPars per thread
 #include "sr_device.hpp"
 #include "sr_kernels.hpp"
 #include "sr_solar_plan.hpp"
@@ -16,6 +18,7 @@ namespace sr {
 #include "sr_solar_source.inc"
 #include "sr_solar_jac.inc"
 #include "sr_diffuse_source.inc"
+#include "sr_diffuse_jac.inc"
 
 int launch_solar_source(const double *tab_abs, int n_k, int n_pts, const double *u, const double *w, const int *src_row,
                         int n_rows, const int *tile_off, const int *chunks, const double *sca_abs, const double *sun,
@@ -71,6 +74,33 @@ int launch_diffuse_source(const double *tab_abs, int n_gas, int n_layers, int n_
   };
   if (accumulate && emi_out) with_j(std::true_type{});
   else with_j(std::false_type{});
+  return (int)hipGetLastError();
+}
+
+int launch_diffuse_tangent(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, int par_lo, int par_hi,
+                           const double *v, const double *dv, const double *coef, const int *mask, const double *beam,
+                           const double *sun, const double *dlnbeam, double mu0, double albedo, double *ws, int ws_stride,
+                           double *dj, int dj_stride, int dj_joff, int dj_par0, hipStream_t st) {
+  if (n_layers <= 0 || p_hi <= p_lo || par_hi <= par_lo) return 0;
+  const dim3 grid(limb_grid((p_hi - p_lo + 255) / 256, (par_hi - par_lo + kDiffuseJacPars - 1) / kDiffuseJacPars));
+  hipLaunchKernelGGL((sr_diffuse_tangent_kernel<kDiffuseJacPars>), grid, dim3(256), 0, st, tab_abs, n_gas, n_layers, n_pts, p_lo,
+                     p_hi, par_lo, par_hi, v, dv, coef, mask, beam, sun, dlnbeam, mu0, albedo, ws, ws_stride, dj, dj_stride, dj_joff,
+                     dj_par0);
+  return (int)hipGetLastError();
+}
+
+int launch_diffuse_contract(const double *q, int n_rays, int n_layers, int n_pts, int p_lo, int p_hi, int par_lo, int par_hi,
+                            const double *dj, int dj_stride, int dj_joff, int dj_par0, const int *par_slot, bool accumulate,
+                            double *jac, int n_jac_rows, hipStream_t st) {
+  if (n_layers <= 0 || p_hi <= p_lo || par_hi <= par_lo || n_rays <= 0) return 0;
+  const dim3 grid(limb_grid((p_hi - p_lo + 255) / 256, ((par_hi - par_lo + kDiffuseJacPars - 1) / kDiffuseJacPars) *
+                                                           ((n_rays + kDiffuseJacRays - 1) / kDiffuseJacRays)));
+  if (accumulate)
+    hipLaunchKernelGGL((sr_diffuse_contract_kernel<kDiffuseJacRays, kDiffuseJacPars, true>), grid, dim3(256), 0, st, q, n_rays,
+                       n_layers, n_pts, p_lo, p_hi, par_lo, par_hi, dj, dj_stride, dj_joff, dj_par0, par_slot, jac, n_jac_rows);
+  else
+    hipLaunchKernelGGL((sr_diffuse_contract_kernel<kDiffuseJacRays, kDiffuseJacPars, false>), grid, dim3(256), 0, st, q, n_rays,
+                       n_layers, n_pts, p_lo, p_hi, par_lo, par_hi, dj, dj_stride, dj_joff, dj_par0, par_slot, jac, n_jac_rows);
   return (int)hipGetLastError();
 }
 

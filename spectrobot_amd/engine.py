@@ -620,7 +620,8 @@ def solar_source(A, U, w, sca, sun, src_row=None, out=None, accumulate=False, tr
 
     By default every Jacobian treats the rows as coefficients: the solar attenuation is HELD FIXED under d / d(VMR, T, Tvib)
     within one linearisation (as TempProfile holds columns and pressure fixed).  The derivative through tau for VMR
-    parameters is solar_attenuation_jacobian (retrieval.inversion_state(solar_attenuation=True)); for T and Tvib it is not
+    parameters is solar_attenuation_jacobian (retrieval.inversion_state(solar_attenuation=True)), and through the diffuse
+    rows made under this beam diffuse_jacobian (inversion_state(diffuse_jacobian=True)); for T and Tvib neither is
     built.  Returns emi, or (emi, trans)."""
     d, n_k, keep = _solar_desc(U, w, src_row)
     ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
@@ -663,8 +664,9 @@ def diffuse_source(A, V, ssa, asym, beam, sun, mu0, surface_albedo=0.0, out_gas=
     columns); sun: CUDA [n_pts]; mu0 = cos SZA; surface_albedo in [0, 1]: what lies below the lowest level.
     out_gas: the gas whose rows are made (None: no rows); out: CUDA [n_layers, n_pts], required with accumulate=True.
     mean_intensity=True: also J [n_layers, n_pts]; fluxes=True: also F [2, n_layers + 1, n_pts], F+ then F- at the
-    interfaces.  One kernel, one writer per element; the same call gives the same bits.  Every Jacobian treats the rows
-    as coefficients.  Returns emi (if out_gas is given), then J, then F, as asked: one tensor or a tuple."""
+    interfaces.  One kernel, one writer per element; the same call gives the same bits.  By default every Jacobian
+    treats the rows as coefficients; their derivative to VMR parameters is diffuse_jacobian
+    (retrieval.inversion_state(diffuse_jacobian=True)), to T and Tvib it is not built.  Returns emi (if out_gas is given), then J, then F, as asked: one tensor or a tuple."""
     ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
     if not (ok(A) and ok(beam) and ok(sun)) or A.dim() != 3 or beam.dim() != 2 or sun.dim() != 1:
         raise ValueError("A, beam and sun must be contiguous CUDA float64 tensors ([n_gas, n_layers, n_pts], "
@@ -767,6 +769,84 @@ def solar_attenuation_jacobian(A, dU, Q, out=None, par_slot=None, accumulate=Fal
                                          C.c_void_p(out.data_ptr()), int(out.shape[1]), int(bool(accumulate)), _stream_ptr()),
           "sr_solar_jacobian_rows_dev")
     return out
+
+
+DIFFUSE_JAC_PARS = 4    # parameters per tile of sr_diffuse_tangent_kernel (kDiffuseJacPars): where a call's tile edge sits
+DIFFUSE_JAC_RAYS = 8    # rays per thread of sr_diffuse_contract_kernel (kDiffuseJacRays)
+
+
+def diffuse_jacobian(A, V, ssa, asym, beam, sun, mu0, dV, dlnbeam, Q, surface_albedo=0.0, out=None, par_slot=None,
+                     accumulate=False, tangent=False):
+    """The diffuse rows in the Jacobians (sr_diffuse_jacobian_rows_dev; the build's own definition): the
+    derivative of limb radiances to column parameters through diffuse_source's two-stream solve,
+
+        dJ[p, l] = the tangent of J[l] along d t_g[l] = dV[p, g, l] A[g, l], d ln D_l = dlnbeam[p, l],
+                   d ln Ub_0 = dlnbeam[p, n_layers]
+        jac[ray, par_slot[p]] (+)= sum_l Q[ray, l] dJ[p, l]
+
+    of the function as built: the floor of co, g = 0 where nothing scatters and an empty layer have derivative 0.
+    A, V, ssa, asym, beam, sun, mu0, surface_albedo: the state, as diffuse_source takes it.  dV: host [n_par, n_gas,
+    n_layers] = d V / d x_p (geometry.vertical_column_weights), any finite sign, mostly zeros; dlnbeam: CUDA [n_par,
+    n_layers + 1, n_pts] = d ln beam / d x_p, or None: the beam held fixed; Q: CUDA [n_rays, n_layers, n_pts] = d rad /
+    d J_l: limb_rays_layer_jacobian(coeffs, (zeros, W), los) with W[g] = ssa_g (1 - f_g) A[g] for every solar gas, or None
+    with tangent=True (dJ alone).  out: CUDA [n_rays, n_jac_rows, n_pts], required with accumulate=True; par_slot [n_par]:
+    the row of out of every parameter (None: row p, and out [n_rays, n_par, n_pts]); rows that are not named keep their
+    bits.  tangent=True: also dJ [n_par, n_layers, n_pts], the counterpart of diffuse_source(mean_intensity=True).  Two
+    fp64 kernels, one writer per element; the same call gives the same bits.  Returns out, (out, dJ), or dJ (Q None)."""
+    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    if not (ok(A) and ok(beam) and ok(sun)) or A.dim() != 3 or beam.dim() != 2 or sun.dim() != 1:
+        raise ValueError("A, beam and sun must be contiguous CUDA float64 tensors ([n_gas, n_layers, n_pts], "
+                         "[n_layers + 1, n_pts], [n_pts])")
+    n_gas, n_layers, n_pts = (int(s) for s in A.shape)
+    if n_gas == 0 or n_layers == 0 or n_pts == 0:
+        raise ValueError("A must not be empty")
+    va, vp = _d(np.asarray(V, dtype=np.float64))
+    sa, sp = _d(np.broadcast_to(np.asarray(ssa, dtype=np.float64), (n_gas,)))
+    ga, gp = _d(np.broadcast_to(np.asarray(asym, dtype=np.float64), (n_gas,)))
+    if va.shape != (n_gas, n_layers):
+        raise ValueError("V must be [n_gas, n_layers] = [%d, %d]" % (n_gas, n_layers))
+    if beam.shape != (n_layers + 1, n_pts) or sun.shape[0] != n_pts:
+        raise ValueError("beam must be [n_layers + 1, n_pts] and sun [n_pts] on A's %d grid points" % n_pts)
+    dva, dvp = _d(np.asarray(dV, dtype=np.float64))
+    if dva.ndim != 3 or dva.shape[0] == 0 or dva.shape[1:] != (n_gas, n_layers):
+        raise ValueError("dV must be [n_par, n_gas, n_layers] = [n_par, %d, %d]" % (n_gas, n_layers))
+    n_par = int(dva.shape[0])
+    if dlnbeam is not None and (not ok(dlnbeam) or dlnbeam.shape != (n_par, n_layers + 1, n_pts)):
+        raise ValueError("dlnbeam must be a contiguous CUDA float64 [n_par, n_layers + 1, n_pts] or None")
+    slot_p = None
+    if Q is None:
+        if not tangent:
+            raise ValueError("nothing asked for: Q=... or tangent=True")
+        if out is not None or par_slot is not None or accumulate:
+            raise ValueError("out=, par_slot= and accumulate= belong to the product with Q=")
+        n_rays = 0
+    else:
+        if not ok(Q) or Q.dim() != 3 or Q.shape[0] == 0 or Q.shape[1] != n_layers or Q.shape[2] != n_pts:
+            raise ValueError("Q must be a contiguous CUDA float64 [n_rays, %d, %d]: A's layers and grid points" % (n_layers, n_pts))
+        n_rays = int(Q.shape[0])
+        slot, slot_p = _i(np.arange(n_par) if par_slot is None else par_slot)
+        if slot.shape != (n_par,):
+            raise ValueError("par_slot must be [n_par]")
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True adds to out=...")
+            if par_slot is not None:
+                raise ValueError("par_slot places rows in out=...")
+            out = torch.empty((n_rays, n_par, n_pts), dtype=torch.float64, device="cuda")
+        elif not ok(out) or out.dim() != 3 or out.shape[0] != n_rays or out.shape[2] != n_pts:
+            raise ValueError("out must be a contiguous CUDA float64 [n_rays, n_jac_rows, n_pts]")
+    dJ = torch.empty((n_par, n_layers, n_pts), dtype=torch.float64, device="cuda") if tangent else None
+    d = _lib.DiffuseDesc()
+    d.n_gas, d.n_layers, d.v, d.ssa, d.asym = n_gas, n_layers, vp, sp, gp
+    d.mu0, d.surface_albedo = float(mu0), float(surface_albedo)
+    jd = _lib.DiffuseJacDesc()
+    jd.n_par, jd.dv = n_par, dvp
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    check(lib.sr_diffuse_jacobian_rows_dev(C.byref(d), C.byref(jd), ptr(A), ptr(beam), ptr(sun), ptr(dlnbeam), ptr(Q), n_rays, n_pts,
+                                           slot_p, ptr(out), int(out.shape[1]) if out is not None else 0, int(bool(accumulate)),
+                                           ptr(dJ), _stream_ptr()), "sr_diffuse_jacobian_rows_dev")
+    res = tuple(t for t in (out, dJ) if t is not None)
+    return res[0] if len(res) == 1 else res
 
 
 def lut_interp(table, idx4, wgt4, pops=None, out=None):

@@ -532,6 +532,20 @@ def _solar_column_weights(z, nd_levels, masks, par_gas, n_gas, alt, mu, R, n_sub
     return dU, lit
 
 
+def vertical_column_weights(z, nd_levels, masks, par_gas, n_gas, R=TITAN_RADIUS_KM, n_sub=3, col_scale=None):
+    """The derivative of vertical_columns to column parameters: dV [n_par, n_gas, n_layers] = d V / d x_p, what
+    engine.diffuse_jacobian takes.  solar_column_weights for the one point at z[0] with mu = 1, as vertical_columns is to
+    solar_columns; sum_p x_p dV_p is vertical_columns of the profiles sum_p x_p masks_p, to rounding."""
+    return _vertical_column_weights(z, nd_levels, masks, par_gas, n_gas, R, n_sub, col_scale, _device_columns)
+
+
+def _vertical_column_weights(z, nd_levels, masks, par_gas, n_gas, R, n_sub, col_scale, columns):
+    """vertical_column_weights with the column routine given, as _solar_columns."""
+    z0 = float(np.atleast_1d(np.asarray(z, float))[0])
+    dU, _ = _solar_column_weights(z, nd_levels, masks, par_gas, n_gas, [z0], 1.0, R, n_sub, col_scale, columns)
+    return np.ascontiguousarray(dU[:, 0])
+
+
 def hg_phase(cos_theta, g):
     """Henyey-Greenstein phase function P(Theta) = (1 - g^2) / (1 + g^2 - 2 g cos Theta)^(3/2), normalised so that its
     mean over the sphere is 1 (int P dOmega = 4 pi); g: the asymmetry parameter, |g| < 1."""

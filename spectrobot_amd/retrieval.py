@@ -194,8 +194,9 @@ class Sun(object):
     plane-parallel two-stream solve under the (spherical, delta-scaled) direct beam, engine.diffuse_source, DESIGN.md
     4.11b; order one stays the single-scattering rows.  surface_albedo (0 .. 1) is the Lambertian albedo of what lies
     BELOW z[0]: a scene whose grid starts above the ground uses 0, so that everything below absorbs.  It is read with
-    multiple=True only.  The diffuse rows are held fixed under every Jacobian within one linearisation, as the other
-    solar rows are."""
+    multiple=True only.  By default the diffuse rows are held fixed under every Jacobian within one linearisation, as the
+    other solar rows are; their derivative to VMR parameters is LimbScene.diffuse_jacobian
+    (inversion_state(diffuse_jacobian=True)); to T and Tvib it is not built."""
 
     def __init__(self, sza_deg, phase_deg, irradiance, multiple=False, surface_albedo=0.0):
         self.sza_deg, self.phase_deg = float(sza_deg), float(phase_deg)
@@ -403,6 +404,9 @@ class LimbScene(object):
                                     # still gets its solar rows again)
         self.keep_solar_rows = False  # True: the solar pass keeps every solar gas's solar rows alone (g.solar_rows), what
                                       # solar_attenuation_jacobian works on (inversion_state(solar_attenuation=True) sets it)
+        self.keep_diffuse_state = False  # True: the diffuse pass keeps its inputs (self.diffuse_state), what diffuse_jacobian
+                                         # differentiates (inversion_state(diffuse_jacobian=True) sets it)
+        self.diffuse_state = None
         if sun is not None and sun.irradiance.shape != self.grid.shape:
             raise ValueError("the sun's irradiance must be given on the scene's grid")
         if sun is not None and getattr(sun, "multiple", False):
@@ -515,20 +519,26 @@ class LimbScene(object):
             self.diffuse_pass(solar, A, sun)
         self._solar_key, self._solar_tabs = key, tabs
 
+    def diffuse_geometry(self, solar):
+        """(ssa, asym, iso, pts, beam_scale) of the diffuse pass and of its derivative: per gas slot the single-scattering
+        albedo and asymmetry parameter (0 for a gas that is not solar) and the column scale, the points of the direct
+        beam (the middles of the shells, then z[0]) and the delta-scaled column scale iso (1 - ssa f) of its columns."""
+        ssa = np.array([g.solar["albedo"] if g in solar else 0.0 for g in self.gases])
+        asym = np.array([g.solar["g"] if g in solar else 0.0 for g in self.gases])
+        iso = np.array([float(g.iso_ratio) for g in self.gases])
+        top = self.z[-1] + (self.z[-1] - self.z[-2])
+        zz = np.append(self.z, top)
+        pts = np.append(0.5 * (zz[:-1] + zz[1:]), self.z[0])
+        return ssa, asym, iso, pts, iso * (1.0 - ssa * np.maximum(asym, 0.0) ** 2)
+
     def diffuse_inputs(self, solar, A, sun):
         """(V, ssa, asym, beam) of engine.diffuse_source for the scene's state: the layers' vertical columns, the solar
         gases' single-scattering albedos and asymmetry parameters (0 for every other gas) and the direct beam at the
         middles of the shells and at the level z[0] -- one more engine.solar_source(..., transmission=True) call with
         every solar gas's columns scaled by 1 - ssa f, f = max(g, 0)^2: the delta-scaled beam, in spherical geometry."""
-        ssa = np.array([g.solar["albedo"] if g in solar else 0.0 for g in self.gases])
-        asym = np.array([g.solar["g"] if g in solar else 0.0 for g in self.gases])
-        iso = np.array([float(g.iso_ratio) for g in self.gases])
+        ssa, asym, iso, pts, beam_scale = self.diffuse_geometry(solar)
         vmr = [g.vmr for g in self.gases]
-        top = self.z[-1] + (self.z[-1] - self.z[-2])
-        zz = np.append(self.z, top)
-        pts = np.append(0.5 * (zz[:-1] + zz[1:]), self.z[0])
-        Ub, lit = geometry.solar_columns(self.z, self.nd, vmr, pts, self.sun.mu, R=self.R, n_sub=self.n_sub,
-                                         col_scale=iso * (1.0 - ssa * np.maximum(asym, 0.0) ** 2))
+        Ub, lit = geometry.solar_columns(self.z, self.nd, vmr, pts, self.sun.mu, R=self.R, n_sub=self.n_sub, col_scale=beam_scale)
         _, beam = engine.solar_source(A, Ub, np.where(lit, 1.0, 0.0), A[self.gases.index(solar[0])], sun,
                                       src_row=np.zeros(len(pts), np.int32), transmission=True)
         V = geometry.vertical_columns(self.z, self.nd, vmr, R=self.R, n_sub=self.n_sub, col_scale=iso)
@@ -540,6 +550,8 @@ class LimbScene(object):
         a torch.addcmul per gas."""
         V, ssa, asym, beam = self.diffuse_inputs(solar, A, sun)
         kw = dict(surface_albedo=self.sun.surface_albedo)
+        if self.keep_diffuse_state:
+            self.diffuse_state = (A, V, ssa, asym, beam, sun)
         if len(solar) == 1:
             engine.diffuse_source(A, V, ssa, asym, beam, sun, self.sun.mu, out_gas=self.gases.index(solar[0]),
                                   out=solar[0].coeffs[1], accumulate=True, **kw)
@@ -577,6 +589,46 @@ class LimbScene(object):
         if jac is None:
             return engine.solar_attenuation_jacobian(a, dU, Q)
         return engine.solar_attenuation_jacobian(a, dU, Q, out=jac, par_slot=np.arange(n_col), accumulate=True)
+
+    def diffuse_jacobian(self, los, alt, w, coeffs, jac=None):
+        """The diffuse rows in the column rows of a state Jacobian: d rad / d x_p through the two-stream solve of the
+        diffuse pass (Sun(multiple=True)) for the column block of the StateWeights `w`, added to rows 0 .. n_col - 1 of jac
+        [n_rays, n_rows, n_pts] (None: returned as its own [n_rays, n_col, n_pts]).  dV from
+        geometry.vertical_column_weights; the beam's part from geometry.solar_column_weights at diffuse_inputs' points
+        (the middles of the shells and z[0]) with its delta-scaled col_scale, dlnbeam = -(dUb . A) as one torch.matmul
+        (rows in shadow are zero); Q by ONE limb_rays_layer_jacobian call with dabs = 0 and demi[g] = ssa_g (1 - f_g) A[g]
+        of every solar gas -- the radiances' derivative to J; then one engine.diffuse_jacobian call.  Needs
+        keep_diffuse_state and the solar pass of the current state (V, ssa, asym and beam are that pass's own; `coeffs` is
+        coefficient_stack()'s pair); `alt` is not needed: the rows are the scene's layers.  The derivative through the
+        single-scattering rows' own optical depth is solar_attenuation_jacobian's: the full derivative of a sunlit
+        multiple-scattering scene is both.  limb_rays_layer_jacobian is a four-gas call."""
+        import torch
+        solar = self.solar_gases()
+        state = self.diffuse_state
+        if not solar or not getattr(self.sun, "multiple", False) or state is None:
+            raise ValueError("diffuse_jacobian needs a Sun(multiple=True), a solar gas and keep_diffuse_state = True before the solar pass")
+        n_col = len(w.par_gas)
+        if n_col == 0:
+            return jac
+        A, V, ssa, asym, beam, sun = state
+        n_gas, n_layers, n_pts = (int(v) for v in A.shape)
+        _, _, iso, pts, beam_scale = self.diffuse_geometry(solar)
+        f = np.maximum(asym, 0.0) ** 2
+        dV = geometry.vertical_column_weights(self.z, self.nd, w.col_masks, w.par_gas, n_gas, R=self.R, n_sub=self.n_sub, col_scale=iso)
+        dUb, _ = geometry.solar_column_weights(self.z, self.nd, w.col_masks, w.par_gas, n_gas, pts, self.sun.mu, R=self.R,
+                                               n_sub=self.n_sub, col_scale=beam_scale)
+        dub = torch.as_tensor(np.ascontiguousarray(dUb.reshape(n_col * (n_layers + 1), n_gas * n_layers)), device="cuda")
+        dlnbeam = torch.matmul(dub, A.reshape(n_gas * n_layers, n_pts)).neg_().reshape(n_col, n_layers + 1, n_pts)
+        W = torch.zeros_like(A)
+        for g in solar:
+            i = self.gases.index(g)
+            W[i] = A[i] * float(ssa[i] * (1.0 - f[i]))
+        Q = engine.limb_rays_layer_jacobian(coeffs, (torch.zeros_like(A), W), los)
+        kw = dict(surface_albedo=self.sun.surface_albedo)
+        if jac is None:
+            return engine.diffuse_jacobian(A, V, ssa, asym, beam, sun, self.sun.mu, dV, dlnbeam, Q, **kw)
+        return engine.diffuse_jacobian(A, V, ssa, asym, beam, sun, self.sun.mu, dV, dlnbeam, Q, out=jac, par_slot=np.arange(n_col),
+                                       accumulate=True, **kw)
 
     def folded_into(self, g):
         return [t for t in self.folded if t.accumulate_into == g.name]
@@ -1329,7 +1381,7 @@ def _state_call(scene, w, coeffs, dcoeffs, los, bands, **kw):
 
 
 def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lambda_LM=0.1, L1_reg=False,
-                    fov_closed_form=True, bands_in_kernel=False, solar_attenuation=False):
+                    fov_closed_form=True, bands_in_kernel=False, solar_attenuation=False, diffuse_jacobian=False):
     """inversion_fast_limb's loop for a MIXED state vector: VMR-profile sets (named after a gas) together with the
     vibrational-temperature sets of one LevelGas or of several (TvibProfile; several: engine.LevelFactoredSet, the same one
     call per iteration with the level parameters of all of them) and the kinetic-temperature set (TempProfile; with it the
@@ -1359,6 +1411,11 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     keep_solar_rows), added to the hi-res Jacobian before the band step, or, with bands_in_kernel, as hi-res rows of its
     own through hires_to_lowres and the closed-form field of view (both linear) onto the fused call's band rows.  The
     term's Q pass is a four-gas call: more gas slots raise ValueError.  False, or a scene without a sun: nothing changes.
+    diffuse_jacobian=True, on a scene with a Sun(multiple=True) and a solar gas: the VMR columns also carry the derivative
+    through the diffuse rows' two-stream solve (LimbScene.diffuse_jacobian: the scene keeps the diffuse pass's inputs,
+    keep_diffuse_state), added at the same two sites.  Independent of solar_attenuation: the full derivative of a sunlit
+    multiple-scattering scene needs both flags.  The same four-gas Q pass, the same ValueError.  False, or a scene
+    without such a sun: nothing changes.
     The temperature, vibrational-temperature, pointing and instrument columns have no such term here."""
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)
     with_fov = _closed_form_fov(pixels, fov_closed_form, "inversion_state")
@@ -1368,6 +1425,13 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             raise ValueError("inversion_state(solar_attenuation=True): a scene of %d gas slots; the term's Q pass "
                              "(engine.limb_rays_layer_jacobian) is a four-gas call" % len(scene.gases))
         scene.keep_solar_rows = True
+    diffuse_jac = bool(diffuse_jacobian) and bool(scene.solar_gases()) and bool(getattr(scene.sun, "multiple", False))
+    if diffuse_jac:
+        if len(scene.gases) > engine.max_gases(folded=True):
+            raise ValueError("inversion_state(diffuse_jacobian=True): a scene of %d gas slots; the term's Q pass "
+                             "(engine.limb_rays_layer_jacobian) is a four-gas call" % len(scene.gases))
+        scene.keep_diffuse_state = True
+        scene._solar_key = None     # (a solar pass made before the flag kept nothing: the next one is made again)
     alts0 = [a for pix in pixels for a in pix.los_alts()]
     # the sets' names are checked before anything is changed
     with_temp = scene.state_weights(bayes_set, np.zeros(1), several_level_gases=True).par_w_temp.shape[0] > 0
@@ -1404,9 +1468,12 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             if instr is not None:
                 band_args["instrument"] = True
             both = _state_call(scene, w, coeffs, dcoeffs, los, True, **band_args, **point_kw)
-            if solar_att and len(w.par_gas):    # the term as hi-res rows of its own, through the band step and the field of view
+            if (solar_att or diffuse_jac) and len(w.par_gas):    # the terms as hi-res rows of their own, through the band step and the field of view
                 n_col = len(w.par_gas)
-                extra = lowres(scene.solar_attenuation_jacobian(los, alt, w, coeffs).view(n_los * n_col, -1)).reshape(n_los, n_col, -1)
+                term = scene.solar_attenuation_jacobian(los, alt, w, coeffs) if solar_att else None
+                if diffuse_jac:
+                    term = scene.diffuse_jacobian(los, alt, w, coeffs, term)
+                extra = lowres(term.view(n_los * n_col, -1)).reshape(n_los, n_col, -1)
                 if with_fov:
                     extra = smm.fov_closed_form(extra[0::3], extra[1::3], extra[2::3], rots)
                 both = np.array(both)
@@ -1421,6 +1488,8 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
                 rad, jac = _state_call(scene, w, coeffs, dcoeffs, los, False, **point_kw)
                 if solar_att:
                     scene.solar_attenuation_jacobian(los, alt, w, coeffs, jac)
+                if diffuse_jac:
+                    scene.diffuse_jacobian(los, alt, w, coeffs, jac)
             n_rows = 0 if jac is None else jac.shape[1]
             n_par = n_rows - (0 if point is None else 1)               # (the pointing row stands behind the state's)
             order = np.concatenate([w.perm, np.arange(n_par, n_rows)]).astype(int)
