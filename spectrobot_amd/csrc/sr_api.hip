@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <numeric>
@@ -4113,6 +4114,7 @@ int sr_abs_table_layers_dev(sr_abs_table *h, int n_rows, const double *temps, co
 // The single-scattering solar source of coefficient rows (sr_solar_source.hip).  One check of the descriptor for both
 // entries: everything the kernel would index with or multiply by is looked at before the first copy or launch.
 static thread_local int g_solar_full_lists = 0; // sr_set_solar_full_lists: every chunk listed (a check)
+constexpr int64_t kSolarMaxPts = 2000000;         // grid points of a call of the family, solar and diffuse
 int sr_set_solar_full_lists(int on) {
   g_solar_full_lists = on != 0;
   return SR_OK;
@@ -4129,10 +4131,12 @@ static int check_solar_desc(const sr_solar_desc *d, int n_k, int n_src, std::vec
   return solar_chunk_lists(d->u, d->w, d->n_rows, n_k, g_solar_full_lists != 0, *tile_off, *chunks) ? SR_OK : SR_ERR_ARG;
 }
 
-int sr_solar_chunk_lists(const sr_solar_desc *desc, int n_k, int32_t *tile_off, int32_t *chunks, int32_t *n_listed) {
+// The two *_chunk_lists entries: the lists `check` makes of the descriptor, copied out.
+static int export_chunk_lists(int32_t *tile_off, int32_t *chunks, int32_t *n_listed,
+                              const std::function<int(std::vector<int> *, std::vector<int> *)> &check) {
   if (!tile_off || !chunks || !n_listed) return SR_ERR_ARG;
   std::vector<int> off, ch;
-  const int rc = check_solar_desc(desc, n_k, -1, &off, &ch);
+  const int rc = check(&off, &ch);
   if (rc) return rc;
   std::copy(off.begin(), off.end(), tile_off);
   std::copy(ch.begin(), ch.end(), chunks);
@@ -4140,10 +4144,24 @@ int sr_solar_chunk_lists(const sr_solar_desc *desc, int n_k, int32_t *tile_off, 
   return SR_OK;
 }
 
+// One writer per element: a row of jac belongs to one parameter.
+static int check_par_slots(const int32_t *par_slot, int n_par, int n_jac_rows) {
+  std::vector<int> slots(par_slot, par_slot + n_par);
+  std::sort(slots.begin(), slots.end());
+  if (slots.front() < 0 || slots.back() >= n_jac_rows || std::adjacent_find(slots.begin(), slots.end()) != slots.end()) return SR_ERR_ARG;
+  return SR_OK;
+}
+
+int sr_solar_chunk_lists(const sr_solar_desc *desc, int n_k, int32_t *tile_off, int32_t *chunks, int32_t *n_listed) {
+  return export_chunk_lists(tile_off, chunks, n_listed, [&](std::vector<int> *off, std::vector<int> *ch) {
+    return check_solar_desc(desc, n_k, -1, off, ch);
+  });
+}
+
 int sr_solar_source_rows_dev(const sr_solar_desc *desc, const double *tab_abs, int n_k, const double *sca_abs, int n_src,
                              const double *sun, int64_t n_pts, int accumulate, double *emi_out, double *trans_out, void *stream) {
   if (!tab_abs || !sca_abs || !sun || !emi_out || n_src <= 0 || n_pts <= 0) return SR_ERR_ARG;
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
+  if (n_pts > kSolarMaxPts) return SR_ERR_LIMIT;
   std::vector<int> tile_off, chunks;
   int rc = check_solar_desc(desc, n_k, n_src, &tile_off, &chunks);
   if (rc) return rc;
@@ -4170,27 +4188,21 @@ static int check_solar_jac_desc(const sr_solar_jac_desc *d, int n_k, std::vector
 }
 
 int sr_solar_jacobian_chunk_lists(const sr_solar_jac_desc *desc, int n_k, int32_t *tile_off, int32_t *chunks, int32_t *n_listed) {
-  if (!tile_off || !chunks || !n_listed) return SR_ERR_ARG;
-  std::vector<int> off, ch;
-  const int rc = check_solar_jac_desc(desc, n_k, &off, &ch);
-  if (rc) return rc;
-  std::copy(off.begin(), off.end(), tile_off);
-  std::copy(ch.begin(), ch.end(), chunks);
-  *n_listed = (int32_t)ch.size();
-  return SR_OK;
+  return export_chunk_lists(tile_off, chunks, n_listed, [&](std::vector<int> *off, std::vector<int> *ch) {
+    return check_solar_jac_desc(desc, n_k, off, ch);
+  });
 }
 
 int sr_solar_jacobian_rows_dev(const sr_solar_jac_desc *desc, const double *tab_abs, int n_k, const double *q, int n_rays,
                                int64_t n_pts, const int32_t *par_slot, double *jac, int n_jac_rows, int accumulate, void *stream) {
   if (!tab_abs || !q || !par_slot || !jac || n_rays <= 0 || n_pts <= 0 || n_jac_rows <= 0) return SR_ERR_ARG;
-  if (n_pts > 2000000) return SR_ERR_LIMIT;
+  if (n_pts > kSolarMaxPts) return SR_ERR_LIMIT;
   std::vector<int> tile_off, chunks;
   int rc = check_solar_jac_desc(desc, n_k, &tile_off, &chunks);
   if (rc) return rc;
   const int n_par = desc->n_par, n_rows = desc->n_rows;
-  std::vector<int> slots(par_slot, par_slot + n_par); // one writer per element: a row of jac belongs to one parameter
-  std::sort(slots.begin(), slots.end());
-  if (slots.front() < 0 || slots.back() >= n_jac_rows || std::adjacent_find(slots.begin(), slots.end()) != slots.end()) return SR_ERR_ARG;
+  rc = check_par_slots(par_slot, n_par, n_jac_rows);
+  if (rc) return rc;
   // the grid: point blocks (rounded up to eight) x parameters x ray groups
   const int64_t n_blocks = (((n_pts + 255) / 256 + 7) / 8 * 8) * (int64_t)n_par * ((n_rays + kSolarJacRays - 1) / kSolarJacRays);
   if (n_blocks > 2147483647) return SR_ERR_LIMIT;
@@ -4216,36 +4228,57 @@ static DevBuf &diffuse_workspace(int dev) { // shared by the source and its Jaco
   return ws_pool[dev];
 }
 
-int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_abs, const double *beam, const double *sun,
-                               int64_t n_pts, int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out,
-                               void *stream) {
-  if (!desc || !desc->v || !desc->ssa || !desc->asym || !tab_abs || !beam || !sun) return SR_ERR_ARG;
-  if (desc->n_gas <= 0 || desc->n_layers <= 0 || n_pts <= 0) return SR_ERR_ARG;
-  if (desc->n_gas > kDiffuseGases || desc->n_layers > SR_MAX_ABS_ROWS || n_pts > 2000000) return SR_ERR_LIMIT;
-  const int n_gas = desc->n_gas, n_layers = desc->n_layers;
-  if (out_gas < -1 || out_gas >= n_gas || (out_gas < 0) != (emi_out == nullptr)) return SR_ERR_ARG;
-  if (!emi_out && !j_out && !flux_out) return SR_ERR_ARG;
-  if (!(desc->mu0 >= -1.0 && desc->mu0 <= 1.0) || !(desc->surface_albedo >= 0.0 && desc->surface_albedo <= 1.0)) return SR_ERR_ARG;
-  double coef[3 * kDiffuseGases] = {0.0}; // ssa (1 - f), 1 - ssa, ssa (asym - f): zeros beyond n_gas
-  double w_out = 0.0;
-  for (int g = 0; g < n_gas; ++g) {
-    const double ssa = desc->ssa[g], as = desc->asym[g];
+// The state of a two-stream call, for the source and its Jacobian: mu0 and the albedo, then -- `sized`: n_gas and
+// n_layers are inside the limits, so that the arrays may be walked and coef has room -- ssa and asym gas by gas and the
+// columns v >= 0.  coef [3][kDiffuseGases]: ssa (1 - f), 1 - ssa, ssa (asym - f), zeros beyond n_gas; w_out: out_gas's
+// ssa (1 - f) (0 without one).
+static int check_diffuse_desc(const sr_diffuse_desc *d, bool sized, int out_gas, double (&coef)[3 * kDiffuseGases], double *w_out) {
+  if (!(d->mu0 >= -1.0 && d->mu0 <= 1.0) || !(d->surface_albedo >= 0.0 && d->surface_albedo <= 1.0)) return SR_ERR_ARG;
+  std::fill(coef, coef + 3 * kDiffuseGases, 0.0);
+  *w_out = 0.0;
+  if (!sized) return SR_OK;
+  for (int g = 0; g < d->n_gas; ++g) {
+    const double ssa = d->ssa[g], as = d->asym[g];
     if (!(ssa >= 0.0 && ssa <= 1.0) || !(as >= -0.5 && as < 1.0)) return SR_ERR_ARG; // (a NaN fails both)
     const double f = as > 0.0 ? as * as : 0.0;
     coef[g] = ssa * (1.0 - f);
     coef[kDiffuseGases + g] = 1.0 - ssa;
     coef[2 * kDiffuseGases + g] = ssa * (as - f);
-    if (g == out_gas) w_out = coef[g];
+    if (g == out_gas) *w_out = coef[g];
   }
-  for (size_t i = 0; i < (size_t)n_gas * n_layers; ++i)
-    if (!(desc->v[i] >= 0.0) || !std::isfinite(desc->v[i])) return SR_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int pts_max = (int)std::max<size_t>(256, kDiffuseWsBytes / (32 * (size_t)n_layers) / 256 * 256);
+  for (size_t i = 0; i < (size_t)d->n_gas * d->n_layers; ++i)
+    if (!(d->v[i] >= 0.0) || !std::isfinite(d->v[i])) return SR_ERR_ARG;
+  return SR_OK;
+}
+
+// Points per launch and, for the Jacobian, parameter tiles per launch of a call whose workspace takes `per` bytes per
+// (tile, point): whole blocks of 256 points inside kDiffuseWsBytes (one block at the least), then as many tiles as fit.
+struct DiffuseChunks { int chunk, tiles; };
+static DiffuseChunks diffuse_chunks(size_t per, int64_t n_pts, int n_tiles) {
+  const int pts_max = (int)std::max<size_t>(256, kDiffuseWsBytes / per / 256 * 256);
   const int chunk = (int)std::min<int64_t>(pts_max, (n_pts + 255) / 256 * 256);
+  const int tiles = (int)std::min<size_t>((size_t)n_tiles, std::max<size_t>(1, kDiffuseWsBytes / (per * (size_t)chunk)));
+  return DiffuseChunks{chunk, tiles};
+}
+
+int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_abs, const double *beam, const double *sun,
+                               int64_t n_pts, int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out,
+                               void *stream) {
+  if (!desc || !desc->v || !desc->ssa || !desc->asym || !tab_abs || !beam || !sun) return SR_ERR_ARG;
+  if (desc->n_gas <= 0 || desc->n_layers <= 0 || n_pts <= 0) return SR_ERR_ARG;
+  if (desc->n_gas > kDiffuseGases || desc->n_layers > SR_MAX_ABS_ROWS || n_pts > kSolarMaxPts) return SR_ERR_LIMIT;
+  const int n_gas = desc->n_gas, n_layers = desc->n_layers;
+  if (out_gas < -1 || out_gas >= n_gas || (out_gas < 0) != (emi_out == nullptr)) return SR_ERR_ARG;
+  if (!emi_out && !j_out && !flux_out) return SR_ERR_ARG;
+  double coef[3 * kDiffuseGases], w_out;
+  int rc = check_diffuse_desc(desc, true, out_gas, coef, &w_out);
+  if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int chunk = diffuse_chunks((size_t)32 * n_layers, n_pts, 1).chunk;
   int dev = 0;
   HIPCHK(hipGetDevice(&dev));
   DevBuf &ws = diffuse_workspace(dev);
-  int rc = ws.ensure((size_t)32 * n_layers * chunk);
+  rc = ws.ensure((size_t)32 * n_layers * chunk);
   if (rc) return rc;
   static thread_local StagerRing ring;
   StagePack pk(ring.take());
@@ -4273,48 +4306,29 @@ int sr_diffuse_jacobian_rows_dev(const sr_diffuse_desc *desc, const sr_diffuse_j
   if (desc->n_gas <= 0 || desc->n_layers <= 0 || n_pts <= 0 || jdesc->n_par <= 0) return SR_ERR_ARG;
   if ((q == nullptr) != (jac == nullptr) || (!jac && !dj_out)) return SR_ERR_ARG; // q and jac come together; something is asked for
   if (jac && (!par_slot || n_rays <= 0 || n_jac_rows <= 0)) return SR_ERR_ARG;
-  if (!(desc->mu0 >= -1.0 && desc->mu0 <= 1.0) || !(desc->surface_albedo >= 0.0 && desc->surface_albedo <= 1.0)) return SR_ERR_ARG;
   const int64_t n_gas64 = desc->n_gas, n_layers64 = desc->n_layers, n_par64 = jdesc->n_par;
   // (the sizes are bounded before the arrays they describe are walked; the limits are reported after dv's check)
-  const bool too_large = n_gas64 > kDiffuseGases || n_layers64 > SR_MAX_ABS_ROWS || n_pts > 2000000 ||
+  const bool too_large = n_gas64 > kDiffuseGases || n_layers64 > SR_MAX_ABS_ROWS || n_pts > kSolarMaxPts ||
                          n_par64 * n_gas64 * n_layers64 > SR_MAX_SOLAR_VALUES;
-  if (!too_large) {
-    for (int g = 0; g < desc->n_gas; ++g) {
-      const double ssa = desc->ssa[g], as = desc->asym[g];
-      if (!(ssa >= 0.0 && ssa <= 1.0) || !(as >= -0.5 && as < 1.0)) return SR_ERR_ARG; // (a NaN fails both)
-    }
-    for (size_t i = 0; i < (size_t)(n_gas64 * n_layers64); ++i)
-      if (!(desc->v[i] >= 0.0) || !std::isfinite(desc->v[i])) return SR_ERR_ARG;
-  }
+  double coef[3 * kDiffuseGases], w_out;
+  int rc = check_diffuse_desc(desc, !too_large, -1, coef, &w_out);
+  if (rc) return rc;
   std::vector<int> mask;
   if (!too_large && !diffuse_jac_masks(desc->v, jdesc->dv, jdesc->n_par, desc->n_gas, desc->n_layers, mask)) return SR_ERR_ARG;
   if (too_large) return SR_ERR_LIMIT;
   const int n_gas = desc->n_gas, n_layers = desc->n_layers, n_par = jdesc->n_par;
-  if (jac) { // one writer per element: a row of jac belongs to one parameter
-    std::vector<int> slots(par_slot, par_slot + n_par);
-    std::sort(slots.begin(), slots.end());
-    if (slots.front() < 0 || slots.back() >= n_jac_rows || std::adjacent_find(slots.begin(), slots.end()) != slots.end()) return SR_ERR_ARG;
-  }
-  double coef[3 * kDiffuseGases] = {0.0}; // ssa (1 - f), 1 - ssa, ssa (asym - f): zeros beyond n_gas
-  for (int g = 0; g < n_gas; ++g) {
-    const double ssa = desc->ssa[g], as = desc->asym[g];
-    const double f = as > 0.0 ? as * as : 0.0;
-    coef[g] = ssa * (1.0 - f);
-    coef[kDiffuseGases + g] = 1.0 - ssa;
-    coef[2 * kDiffuseGases + g] = ssa * (as - f);
-  }
+  if (jac && (rc = check_par_slots(par_slot, n_par, n_jac_rows)) != 0) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // the workspace: doubles per (tile, layer, point), then points per launch, then tiles per launch
   const bool dj_ws = jac && !dj_out;
   const size_t per = (size_t)8 * n_layers * (3 + 4 * kDiffuseJacPars + (dj_ws ? kDiffuseJacPars : 0));
   const int n_tiles = (n_par + kDiffuseJacPars - 1) / kDiffuseJacPars;
-  const int pts_max = (int)std::max<size_t>(256, kDiffuseWsBytes / per / 256 * 256);
-  const int chunk = (int)std::min<int64_t>(pts_max, (n_pts + 255) / 256 * 256);
-  const int tiles = (int)std::min<size_t>((size_t)n_tiles, std::max<size_t>(1, kDiffuseWsBytes / (per * (size_t)chunk)));
+  const DiffuseChunks dc = diffuse_chunks(per, n_pts, n_tiles);
+  const int chunk = dc.chunk, tiles = dc.tiles;
   int dev = 0;
   HIPCHK(hipGetDevice(&dev));
   DevBuf &ws = diffuse_workspace(dev);
-  int rc = ws.ensure(per * (size_t)chunk * tiles);
+  rc = ws.ensure(per * (size_t)chunk * tiles);
   if (rc) return rc;
   static thread_local StagerRing ring;
   StagePack pk(ring.take());

@@ -1,6 +1,6 @@
 // sr_diffuse_jac.inc -- sr_diffuse_tangent_kernel and sr_diffuse_contract_kernel.  Included by sr_solar_source.hip inside
-// namespace sr, behind sr_diffuse_source.inc (DiffuseLayer, diffuse_layer), and by the host build
-// tools/diffuse_jacobian_host.  Nothing else includes it.
+// namespace sr, behind sr_diffuse_source.inc (DiffuseLayer, diffuse_layer, diffuse_boundary, diffuse_sums), and by the
+// host build tools/diffuse_jacobian_host.  Nothing else includes it.
 
 // The diffuse rows in the Jacobians: the tangent of sr_diffuse_source_kernel's J along column parameters, and its product
 // with the radiances' derivative to J.  The build's own definition -- the reference has no counterpart (DESIGN.md 4.11c).
@@ -151,8 +151,8 @@ __global__ __launch_bounds__(256) void sr_diffuse_tangent_kernel(const double *_
   }
 
   // ---- bottom up ----
-  double Rb = albedo, Cb = 1.0 - albedo;
-  double Ub = albedo * (fmax(mu0, 0.0) * (sj * beam[(size_t)n_layers * np + jj]));
+  double Rb, Cb, Ub;
+  diffuse_boundary(albedo, mu0, sj, beam[(size_t)n_layers * np + jj], Rb, Cb, Ub);
   double dRb[NP], dUb[NP]; // (Cb = 1 - Rb: its tangent is -dRb and is not carried)
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
@@ -164,14 +164,8 @@ __global__ __launch_bounds__(256) void sr_diffuse_tangent_kernel(const double *_
 #pragma unroll
     for (int g = 0; g < kDiffuseGases; ++g) a[g] = tab_abs[((size_t)(g < n_gas ? g : 0) * n_layers + l) * np + jj];
     const double bm = beam[(size_t)l * np + jj];
-    double sp = 0.0, al = 0.0, sg = 0.0;
-#pragma unroll
-    for (int g = 0; g < kDiffuseGases; ++g) {
-      const double t = v[(g < n_gas ? g : 0) * n_layers + l] * a[g];
-      sp += cs[g] * t;
-      al += ca[g] * t;
-      sg += cg[g] * t;
-    }
+    const DiffuseSums s = diffuse_sums(v, coef, n_gas, n_layers, l, a);
+    const double sp = s.sp, al = s.al, sg = s.sg;
     const double D = sj * bm;
     const DiffuseLayer o = diffuse_layer(sp, al, sg, D, mu0);
     const double den = Cb + Rb * o.oneR;

@@ -71,6 +71,31 @@ __device__ __forceinline__ DiffuseLayer diffuse_layer(double sp, double al, doub
   return o;
 }
 
+// The adding's start at the lower boundary, for sr_diffuse_tangent_kernel (sr_diffuse_jac.inc) too: Rb_0 = albedo,
+// Cb_0 = 1 - albedo, Ub_0 = albedo max(mu0, 0) sun beam[N].
+__device__ __forceinline__ void diffuse_boundary(double albedo, double mu0, double sj, double beam_below, double &Rb, double &Cb,
+                                                 double &Ub) {
+  Rb = albedo, Cb = 1.0 - albedo;
+  Ub = albedo * (fmax(mu0, 0.0) * (sj * beam_below));
+}
+
+// The three sums of layer l from its rows a[g] of A, for both kernels: gas by gas in the slots' order, a slot beyond n_gas
+// with gas 0's column and coefficients of zero.  coef [3][kDiffuseGases]: ssa (1 - f), 1 - ssa, ssa (asym - f).
+struct DiffuseSums { double sp, al, sg; };
+__device__ __forceinline__ DiffuseSums diffuse_sums(const double *__restrict__ v, const double *__restrict__ coef, int n_gas,
+                                                    int n_layers, int l, const double (&a)[kDiffuseGases]) {
+  const double *cs = coef, *ca = coef + kDiffuseGases, *cg = coef + 2 * kDiffuseGases;
+  double sp = 0.0, al = 0.0, sg = 0.0;
+#pragma unroll
+  for (int g = 0; g < kDiffuseGases; ++g) {
+    const double t = v[(g < n_gas ? g : 0) * n_layers + l] * a[g];
+    sp += cs[g] * t;
+    al += ca[g] * t;
+    sg += cg[g] * t;
+  }
+  return DiffuseSums{sp, al, sg};
+}
+
 template <bool ACC, bool WJ, bool WF>
 __global__ __launch_bounds__(256) void sr_diffuse_source_kernel(const double *__restrict__ tab_abs, int n_gas, int n_layers, int n_pts,
                                                                 int p_lo, int p_hi, const double *__restrict__ v,
@@ -85,7 +110,6 @@ __global__ __launch_bounds__(256) void sr_diffuse_source_kernel(const double *__
   const bool live = j < p_hi;
   const size_t np = (size_t)n_pts, jj = (size_t)min(j, p_hi - 1);
   const size_t wrow = (size_t)ws_stride, wq = (size_t)n_layers * wrow; // ws [4][n_layers][ws_stride]
-  const double *cs = coef, *ca = coef + kDiffuseGases, *cg = coef + 2 * kDiffuseGases;
   const double sj = sun[jj];
 
   // ---- bottom up ----
@@ -96,23 +120,16 @@ __global__ __launch_bounds__(256) void sr_diffuse_source_kernel(const double *__
     b_nx = beam[(size_t)l * np + jj];
   };
   fetch(0);
-  double Rb = albedo, Cb = 1.0 - albedo;
-  double Ub = albedo * (fmax(mu0, 0.0) * (sj * beam[(size_t)n_layers * np + jj]));
+  double Rb, Cb, Ub;
+  diffuse_boundary(albedo, mu0, sj, beam[(size_t)n_layers * np + jj], Rb, Cb, Ub);
   for (int l = 0; l < n_layers; ++l) {
     double a[kDiffuseGases];
 #pragma unroll
     for (int g = 0; g < kDiffuseGases; ++g) a[g] = a_nx[g];
     const double bm = b_nx;
     if (l + 1 < n_layers) fetch(l + 1); // the next layer's rows in flight under this layer's arithmetic
-    double sp = 0.0, al = 0.0, sg = 0.0;
-#pragma unroll
-    for (int g = 0; g < kDiffuseGases; ++g) {
-      const double t = v[(g < n_gas ? g : 0) * n_layers + l] * a[g];
-      sp += cs[g] * t;
-      al += ca[g] * t;
-      sg += cg[g] * t;
-    }
-    const DiffuseLayer o = diffuse_layer(sp, al, sg, sj * bm, mu0);
+    const DiffuseSums s = diffuse_sums(v, coef, n_gas, n_layers, l, a);
+    const DiffuseLayer o = diffuse_layer(s.sp, s.al, s.sg, sj * bm, mu0);
     const double q = o.live ? 1.0 / (Cb + Rb * o.oneR) : 1.0; // (an empty layer: every quantity keeps its bits)
     const size_t at = (size_t)l * wrow + col;
     ws[at] = o.T * q;

@@ -1,15 +1,15 @@
 // sr_solar_jac.inc -- sr_solar_jac_kernel.  Included by sr_solar_source.hip inside namespace sr, behind
-// sr_solar_source.inc (SolarQuad, kSolarBatch), and by the host build tools/solar_jacobian_host.  Nothing else includes it.
+// sr_solar_tile.inc (the tile product and its lane mapping), and by the host build tools/solar_jacobian_host.  Nothing
+// else includes it.
 
 // The solar attenuation in the Jacobians: the derivative of limb radiances to a column parameter THROUGH the optical depth
 // of the solar source (sr_solar_source.inc).  The build's own definition -- the reference has no counterpart:
 //   dtau[p][r][j] = sum_{k < n_k} du[p][r][k] A[k][j]           (du = d U / d x_p: any finite sign, mostly zeros)
 //   jac[ray][slot[p]][j] (+)= - sum_{r < n_rows} q[ray][r][j] dtau[p][r][j]
 // with q[ray][r] = d rad[ray] / d eps_r for emi[r] -> emi[r] + eps_r (solar rows of r), so that q dtau is the radiance's
-// change through exp(-tau).  The first contraction is sr_solar_source_kernel's product, tile for tile: 16 rows x 256 points
-// per block, a wave's 64 points as four column tiles of v_mfma_f64_16x16x4, the same operand and point layout, the du tile
-// through LDS in operand order, the k axis walked through host chunk lists per (parameter, row tile)
-// (solar_jac_chunk_lists).
+// change through exp(-tau).  The first contraction is sr_solar_source_kernel's product, tile for tile
+// (solar_tile_product<LIT = false> of sr_solar_tile.inc: no weights, every row counts), the k axis walked through host
+// chunk lists per (parameter, row tile) (solar_jac_chunk_lists).
 //
 // A block takes 256 points, ONE parameter and a group of NR rays, and loops over the row tiles; a tile whose list is empty
 // is skipped whole (block-uniform): it would have added exact zeros (q finite).  After a tile's MFMAs a lane holds rows
@@ -37,12 +37,7 @@ __global__ __launch_bounds__(256) void sr_solar_jac_kernel(const double *__restr
   const int par = item % n_par, ray0 = (item / n_par) * NR;
   const int t_lo = par * n_tiles;
   if (ACC && tile_off[t_lo] == tile_off[t_lo + n_tiles]) return; // no column at all: the row is left as it is
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lo = lane & 15, kq = lane >> 4;
-  const int p0 = pb * 256 + wave * 64 + 4 * lo; // the lane's four points: p0 + t
-  const bool whole = p0 + 3 < n_pts;           // (false in the grid's last points only)
-  int pj[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) pj[t] = min(p0 + t, n_pts - 1);
+  const SolarLane ln(pb, n_pts);
   const double *u = du + (size_t)par * n_rows * n_k;
   double sum[NR][4];
 #pragma unroll
@@ -55,70 +50,16 @@ __global__ __launch_bounds__(256) void sr_solar_jac_kernel(const double *__restr
     if (c_lo == c_hi) continue; // (block-uniform)
     const int row0 = tile * kSolarRows;
     v4d acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = v4d{0.0, 0.0, 0.0, 0.0};
-    for (int c0 = c_lo; c0 < c_hi; c0 += kSolarBatch) {
-      const int nb = min(kSolarBatch, c_hi - c0), nb2 = (nb + 1) & ~1; // (walked in pairs: an odd batch ends on a chunk of zeros)
-      __syncthreads();                                                 // (the previous batch has been consumed)
-      for (int e = threadIdx.x; e < nb2 * 64; e += 256) {
-        const int cl = e >> 6, i = (e >> 2) & 15, kk = e & 3; // four lanes read 32 consecutive bytes of a row of du
-        double v = 0.0;
-        if (cl < nb) {
-          const int k = 4 * chunks[c0 + cl] + kk, r = row0 + i;
-          if (k < n_k && r < n_rows) v = u[(size_t)r * n_k + k];
-        }
-        s_u[cl * 64 + kk * 16 + i] = v;
-      }
-      __syncthreads();
-      double bn[2][4];
-      auto fetch = [&](int cl) { // the B operands of the pair of chunks at cl, requested together
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int k = cl + h < nb ? 4 * chunks[c0 + cl + h] + kq : 0;
-          const double *arow = tab_abs + (size_t)(k < n_k ? k : 0) * n_pts;
-          if (whole) { // one 32-byte load: sixteen lanes read 512 consecutive bytes of the row
-            const SolarQuad v = *reinterpret_cast<const SolarQuad *>(arow + p0);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) bn[h][t] = v[t];
-          } else {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) bn[h][t] = arow[pj[t]];
-          }
-        }
-      };
-      fetch(0);
-      for (int cl = 0; cl < nb2; cl += 2) {
-        double b[2][4];
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int t = 0; t < 4; ++t) b[h][t] = bn[h][t];
-        const double a0 = s_u[cl * 64 + lane], a1 = s_u[(cl + 1) * 64 + lane];
-        if (cl + 2 < nb2) fetch(cl + 2); // the next pair in flight under this pair's products
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b[0][t], acc[t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b[1][t], acc[t], 0, 0, 0);
-      }
-    }
+    solar_tile_product<false>(tab_abs, n_k, n_pts, u, nullptr, n_rows, row0, chunks, c_lo, c_hi, ln, s_u, acc);
     // register r4 of a lane is row kq + 4 r4 of the tile, its four column tiles four consecutive points
 #pragma unroll
     for (int r4 = 0; r4 < 4; ++r4) {
-      const int r = row0 + kq + 4 * r4;
+      const int r = row0 + ln.kq + 4 * r4;
       if (r >= n_rows) continue; // (a padded row: its product is 0, its q does not exist)
 #pragma unroll
       for (int y = 0; y < NR; ++y) {
         if (ray0 + y >= n_rays) continue; // (block-uniform)
-        const double *qrow = q + ((size_t)(ray0 + y) * n_rows + r) * n_pts;
-        double qv[4];
-        if (whole) {
-          const SolarQuad v = *reinterpret_cast<const SolarQuad *>(qrow + p0);
-#pragma unroll
-          for (int t = 0; t < 4; ++t) qv[t] = v[t];
-        } else {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) qv[t] = qrow[pj[t]];
-        }
+        const SolarQuad qv = solar_load_quad(q + ((size_t)(ray0 + y) * n_rows + r) * n_pts, ln);
 #pragma unroll
         for (int t = 0; t < 4; ++t) sum[y][t] += qv[t] * acc[t][r4];
       }
@@ -136,23 +77,23 @@ __global__ __launch_bounds__(256) void sr_solar_jac_kernel(const double *__restr
 #pragma unroll
       for (int t = 0; t < 4; ++t) s_u[(y * 256 + threadIdx.x) * 4 + t] = sum[y0 + y][t];
     __syncthreads();
-    const int ray = ray0 + y0 + kq;
+    const int ray = ray0 + y0 + ln.kq;
     if (ray >= n_rays) continue; // (after the pass's last barrier)
-    const double *part = s_u + ((size_t)kq * 256 + wave * 64 + lo) * 4; // + 64 g: lane group g's partial sums of this ray
-    double *out = jac + ((size_t)ray * n_jac_rows + slot) * n_pts + p0;
+    const double *part = s_u + ((size_t)ln.kq * 256 + ln.wave * 64 + ln.lo) * 4; // + 64 g: lane group g's partial sums of this ray
+    double *out = jac + ((size_t)ray * n_jac_rows + slot) * n_pts + ln.p0;
     SolarQuad res;
 #pragma unroll
     for (int t = 0; t < 4; ++t) res[t] = (part[t] + part[64 + t]) + (part[128 + t] + part[192 + t]);
-    if (whole) { // 32-byte stores: sixteen lanes write 512 consecutive bytes of the row
+    if (ln.whole) { // 32-byte stores: sixteen lanes write 512 consecutive bytes of the row
       SolarQuad base = SolarQuad{0.0, 0.0, 0.0, 0.0};
-      if (ACC) base = *reinterpret_cast<const SolarQuad *>(out);
+      if (ACC) base = solar_quad(out);
 #pragma unroll
       for (int t = 0; t < 4; ++t) res[t] = base[t] - res[t];
-      *reinterpret_cast<SolarQuad *>(out) = res;
+      solar_quad(out, res);
     } else {
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        if (p0 + t >= n_pts) continue;
+        if (ln.p0 + t >= n_pts) continue;
         out[t] = (ACC ? out[t] : 0.0) - res[t];
       }
     }

@@ -3,7 +3,7 @@
 // column, in ascending order.  Included by sr_api.hip and by the host build tools/solar_source_host; no HIP header.
 // U is read as it is: nothing is sorted, nothing is changed.  full: every chunk of every tile is listed (the check
 // that the result does not depend on the lists: a chunk that is not listed would only have added exact zeros).
-// Below it the plan of sr_solar_jac_kernel (sr_solar_jac.inc; tools/solar_jacobian_host): the same lists per parameter.
+// The plan of sr_solar_jac_kernel (sr_solar_jac.inc; tools/solar_jacobian_host) is the same walk per parameter.
 #pragma once
 #include <cstddef>
 #include <vector>
@@ -17,62 +17,39 @@ constexpr int kDiffuseGases = 8; // gas slots of sr_diffuse_source_kernel's loop
 constexpr int kDiffuseJacPars = 4; // NP: parameters per block of sr_diffuse_tangent_kernel and per thread of the contraction
 constexpr int kDiffuseJacRays = 8; // NR: rays per thread of sr_diffuse_contract_kernel (profiles/diffuse_jacobian_kernel_resources.txt)
 
-// tile_off [n_tiles + 1] into chunks; n_tiles = ceil(n_rows / kSolarRows), chunk c covers k = 4 c .. 4 c + 3 (< n_k).
-// Returns false if an element of u is negative or not finite (the entry's check, in the same walk: u is the one large
-// array of a call and is read once); the lists are then unspecified.
-inline bool solar_chunk_lists(const double *u, const double *w, int n_rows, int n_k, bool full, std::vector<int> &tile_off,
-                              std::vector<int> &chunks) {
+// The one walk behind both plans: x [n_groups][n_rows][n_k], per (group, row tile) the chunks in which a row of the tile
+// that counts (w == nullptr: every row; else the rows with w[r] != 0) has a non-zero element, ascending; tile_off
+// [n_groups n_tiles + 1] into chunks, the tiles of group p at p n_tiles ..: a tile never straddles a group.  n_tiles =
+// ceil(n_rows / kSolarRows), chunk c covers k = 4 c .. 4 c + 3 (< n_k).  Returns false if an element of x is not finite
+// or, with NONNEG, negative (the entry's check, in the same walk: x is the one large array of a call and is read once);
+// the lists are then unspecified.  A whole chunk is checked and marked without a branch per element.
+template <bool NONNEG>
+inline bool solar_walk_chunk_lists(const double *x, const double *w, int n_groups, int n_rows, int n_k, bool full,
+                                   std::vector<int> &tile_off, std::vector<int> &chunks) {
   const int n_tiles = (n_rows + kSolarRows - 1) / kSolarRows, n_chunks = (n_k + kSolarChunk - 1) / kSolarChunk;
   const int n_whole = n_k / kSolarChunk; // chunks with all four k
+  constexpr double kMax = 1.7976931348623157e308, kMin = NONNEG ? 0.0 : -kMax;
   tile_off.assign(1, 0);
   chunks.clear();
   std::vector<char> hit((size_t)n_chunks);
   bool ok = true;
-  for (int t = 0; t < n_tiles; ++t) {
-    hit.assign((size_t)n_chunks, full ? 1 : 0);
-    const int r1 = n_rows < (t + 1) * kSolarRows ? n_rows : (t + 1) * kSolarRows;
-    for (int r = t * kSolarRows; r < r1; ++r) {
-      const char lit = w[r] != 0.0; // in shadow: the row's optical depth is not evaluated, its columns list nothing
-      const double *ur = u + (size_t)r * n_k;
-      for (int c = 0; c < n_whole; ++c) {
-        const double *v = ur + kSolarChunk * c;
-        // (a NaN fails v >= 0, an infinity v <= max)
-        ok &= (v[0] >= 0.0) & (v[1] >= 0.0) & (v[2] >= 0.0) & (v[3] >= 0.0) & (v[0] <= 1.7976931348623157e308) &
-              (v[1] <= 1.7976931348623157e308) & (v[2] <= 1.7976931348623157e308) & (v[3] <= 1.7976931348623157e308);
-        hit[(size_t)c] |= lit & (char)((v[0] != 0.0) | (v[1] != 0.0) | (v[2] != 0.0) | (v[3] != 0.0));
-      }
-      for (int k = kSolarChunk * n_whole; k < n_k; ++k) {
-        ok &= (ur[k] >= 0.0) & (ur[k] <= 1.7976931348623157e308);
-        hit[(size_t)n_whole] |= lit & (char)(ur[k] != 0.0);
-      }
-    }
-    for (int c = 0; c < n_chunks; ++c)
-      if (hit[(size_t)c]) chunks.push_back(c);
-    tile_off.push_back((int)chunks.size());
-  }
-  return ok;
-}
-
-// The plan of sr_solar_jac_kernel (sr_solar_jac.inc): the same lists per (parameter, row tile) of du [n_par][n_rows][n_k],
-// the derivative of the columns to a parameter -- any finite sign, no weights.  tile_off [n_par n_tiles + 1], the tiles of
-// parameter p at p n_tiles ..: a tile never straddles a parameter.  Returns false if an element is not finite.
-inline bool solar_jac_chunk_lists(const double *du, int n_par, int n_rows, int n_k, bool full, std::vector<int> &tile_off,
-                                  std::vector<int> &chunks) {
-  const int n_tiles = (n_rows + kSolarRows - 1) / kSolarRows, n_chunks = (n_k + kSolarChunk - 1) / kSolarChunk;
-  tile_off.assign(1, 0);
-  chunks.clear();
-  std::vector<char> hit((size_t)n_chunks);
-  bool ok = true;
-  for (int p = 0; p < n_par; ++p)
+  for (int p = 0; p < n_groups; ++p)
     for (int t = 0; t < n_tiles; ++t) {
       hit.assign((size_t)n_chunks, full ? 1 : 0);
       const int r1 = n_rows < (t + 1) * kSolarRows ? n_rows : (t + 1) * kSolarRows;
       for (int r = t * kSolarRows; r < r1; ++r) {
-        const double *ur = du + ((size_t)p * n_rows + r) * n_k;
-        for (int k = 0; k < n_k; ++k) {
-          // (a NaN fails both comparisons, an infinity one)
-          ok &= (ur[k] >= -1.7976931348623157e308) & (ur[k] <= 1.7976931348623157e308);
-          hit[(size_t)(k / kSolarChunk)] |= (char)(ur[k] != 0.0);
+        const char lit = !w || w[r] != 0.0; // in shadow: the row's optical depth is not evaluated, its columns list nothing
+        const double *xr = x + ((size_t)p * n_rows + r) * n_k;
+        for (int c = 0; c < n_whole; ++c) {
+          const double *v = xr + kSolarChunk * c;
+          // (a NaN fails v >= min, an infinity one of the two)
+          ok &= (v[0] >= kMin) & (v[1] >= kMin) & (v[2] >= kMin) & (v[3] >= kMin) & (v[0] <= kMax) & (v[1] <= kMax) &
+                (v[2] <= kMax) & (v[3] <= kMax);
+          hit[(size_t)c] |= lit & (char)((v[0] != 0.0) | (v[1] != 0.0) | (v[2] != 0.0) | (v[3] != 0.0));
+        }
+        for (int k = kSolarChunk * n_whole; k < n_k; ++k) {
+          ok &= (xr[k] >= kMin) & (xr[k] <= kMax);
+          hit[(size_t)n_whole] |= lit & (char)(xr[k] != 0.0);
         }
       }
       for (int c = 0; c < n_chunks; ++c)
@@ -80,6 +57,20 @@ inline bool solar_jac_chunk_lists(const double *du, int n_par, int n_rows, int n
       tile_off.push_back((int)chunks.size());
     }
   return ok;
+}
+
+// The plan of sr_solar_source_kernel: u [n_rows][n_k] >= 0, the lit rows of w.  Returns false if an element of u is
+// negative or not finite.
+inline bool solar_chunk_lists(const double *u, const double *w, int n_rows, int n_k, bool full, std::vector<int> &tile_off,
+                              std::vector<int> &chunks) {
+  return solar_walk_chunk_lists<true>(u, w, 1, n_rows, n_k, full, tile_off, chunks);
+}
+
+// The plan of sr_solar_jac_kernel (sr_solar_jac.inc): the same lists per (parameter, row tile) of du [n_par][n_rows][n_k],
+// the derivative of the columns to a parameter -- any finite sign, no weights.  Returns false if an element is not finite.
+inline bool solar_jac_chunk_lists(const double *du, int n_par, int n_rows, int n_k, bool full, std::vector<int> &tile_off,
+                                  std::vector<int> &chunks) {
+  return solar_walk_chunk_lists<false>(du, nullptr, n_par, n_rows, n_k, full, tile_off, chunks);
 }
 
 // The plan of sr_diffuse_tangent_kernel (sr_diffuse_jac.inc; tools/diffuse_jacobian_host): per parameter the layer range

@@ -1,8 +1,9 @@
 // sr_solar_source.hip -- the solar subject's unit: the single-scattering solar source of coefficient rows
 // (sr_solar_source_rows_dev: sr_solar_source.inc) and the solar attenuation in the Jacobians (sr_solar_jacobian_rows_dev:
-// sr_solar_jac.inc) and the two-stream diffuse source (sr_diffuse_source_rows_dev: sr_diffuse_source.inc) and its tangent
-// in the Jacobians (sr_diffuse_jacobian_rows_dev: sr_diffuse_jac.inc), each kernel's text and its launcher.  A translation unit of its own, compiled beside the others: no
-// other unit includes the kernels' text, and this one instantiates no other kernel.
+// sr_solar_jac.inc), both on the tile product of sr_solar_tile.inc, and the two-stream diffuse source
+// (sr_diffuse_source_rows_dev: sr_diffuse_source.inc) and its tangent in the Jacobians (sr_diffuse_jacobian_rows_dev:
+// sr_diffuse_jac.inc), each kernel's text and its launcher.  A translation unit of its own, compiled beside the others:
+// no other unit includes the kernels' text, and this one instantiates no other kernel.
 //
 //   sr_solar_source_kernel<ACC, TRANS>   four instances: overwrite / accumulate, with and without the transmission
 //   sr_solar_jac_kernel<NR, ACC>         two instances: overwrite / accumulate, NR = kSolarJacRays rays per block
@@ -11,10 +12,12 @@
 //   sr_diffuse_contract_kernel<NR, NP, ACC> two instances: overwrite / accumulate, kDiffuseJacRays x kDiffuseJacPars per thread
 #include "sr_device.hpp"
 #include "sr_kernels.hpp"
+#include "sr_limb_dispatch.hpp"
 #include "sr_solar_plan.hpp"
 
 namespace sr {
 
+#include "sr_solar_tile.inc"
 #include "sr_solar_source.inc"
 #include "sr_solar_jac.inc"
 #include "sr_diffuse_source.inc"
@@ -25,17 +28,12 @@ int launch_solar_source(const double *tab_abs, int n_k, int n_pts, const double 
                         bool accumulate, double *emi_out, double *trans_out, hipStream_t st) {
   if (n_rows <= 0 || n_pts <= 0) return 0;
   const dim3 grid(limb_grid((n_pts + 255) / 256, (n_rows + kSolarRows - 1) / kSolarRows));
-  auto go = [&](auto acc, auto trans) {
-    hipLaunchKernelGGL((sr_solar_source_kernel<decltype(acc)::value, decltype(trans)::value>), grid, dim3(256), 0, st, tab_abs, n_k,
-                       n_pts, u, w, src_row, n_rows, tile_off, chunks, sca_abs, sun, emi_out, trans_out);
-  };
-  if (accumulate) {
-    if (trans_out) go(std::true_type{}, std::true_type{});
-    else go(std::true_type{}, std::false_type{});
-  } else {
-    if (trans_out) go(std::false_type{}, std::true_type{});
-    else go(std::false_type{}, std::false_type{});
-  }
+  by_flag(accumulate, [&](auto acc) {
+    by_flag(trans_out != nullptr, [&](auto trans) {
+      hipLaunchKernelGGL((sr_solar_source_kernel<decltype(acc)::value, decltype(trans)::value>), grid, dim3(256), 0, st, tab_abs,
+                         n_k, n_pts, u, w, src_row, n_rows, tile_off, chunks, sca_abs, sun, emi_out, trans_out);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -44,12 +42,10 @@ int launch_solar_jac(const double *tab_abs, int n_k, int n_pts, const double *du
                      int n_jac_rows, hipStream_t st) {
   if (n_par <= 0 || n_rows <= 0 || n_pts <= 0 || n_rays <= 0) return 0;
   const dim3 grid(limb_grid((n_pts + 255) / 256, n_par * ((n_rays + kSolarJacRays - 1) / kSolarJacRays)));
-  if (accumulate)
-    hipLaunchKernelGGL((sr_solar_jac_kernel<kSolarJacRays, true>), grid, dim3(256), 0, st, tab_abs, n_k, n_pts, du, n_par, n_rows,
-                       tile_off, chunks, q, n_rays, par_slot, jac, n_jac_rows);
-  else
-    hipLaunchKernelGGL((sr_solar_jac_kernel<kSolarJacRays, false>), grid, dim3(256), 0, st, tab_abs, n_k, n_pts, du, n_par, n_rows,
-                       tile_off, chunks, q, n_rays, par_slot, jac, n_jac_rows);
+  by_flag(accumulate, [&](auto acc) {
+    hipLaunchKernelGGL((sr_solar_jac_kernel<kSolarJacRays, decltype(acc)::value>), grid, dim3(256), 0, st, tab_abs, n_k, n_pts, du,
+                       n_par, n_rows, tile_off, chunks, q, n_rays, par_slot, jac, n_jac_rows);
+  });
   return (int)hipGetLastError();
 }
 
@@ -59,21 +55,15 @@ int launch_diffuse_source(const double *tab_abs, int n_gas, int n_layers, int n_
                           double *flux_out, hipStream_t st) {
   if (n_layers <= 0 || p_hi <= p_lo) return 0;
   const dim3 grid(limb_grid((p_hi - p_lo + 255) / 256, 1));
-  auto go = [&](auto acc, auto wj, auto wf) {
-    hipLaunchKernelGGL((sr_diffuse_source_kernel<decltype(acc)::value, decltype(wj)::value, decltype(wf)::value>), grid, dim3(256),
-                       0, st, tab_abs, n_gas, n_layers, n_pts, p_lo, p_hi, v, coef, beam, sun, mu0, albedo, out_gas, w_out, ws,
-                       ws_stride, emi_out, j_out, flux_out);
-  };
-  auto with_f = [&](auto acc, auto wj) {
-    if (flux_out) go(acc, wj, std::true_type{});
-    else go(acc, wj, std::false_type{});
-  };
-  auto with_j = [&](auto acc) {
-    if (j_out) with_f(acc, std::true_type{});
-    else with_f(acc, std::false_type{});
-  };
-  if (accumulate && emi_out) with_j(std::true_type{});
-  else with_j(std::false_type{});
+  by_flag(accumulate && emi_out, [&](auto acc) {
+    by_flag(j_out != nullptr, [&](auto wj) {
+      by_flag(flux_out != nullptr, [&](auto wf) {
+        hipLaunchKernelGGL((sr_diffuse_source_kernel<decltype(acc)::value, decltype(wj)::value, decltype(wf)::value>), grid,
+                           dim3(256), 0, st, tab_abs, n_gas, n_layers, n_pts, p_lo, p_hi, v, coef, beam, sun, mu0, albedo, out_gas,
+                           w_out, ws, ws_stride, emi_out, j_out, flux_out);
+      });
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -95,12 +85,11 @@ int launch_diffuse_contract(const double *q, int n_rays, int n_layers, int n_pts
   if (n_layers <= 0 || p_hi <= p_lo || par_hi <= par_lo || n_rays <= 0) return 0;
   const dim3 grid(limb_grid((p_hi - p_lo + 255) / 256, ((par_hi - par_lo + kDiffuseJacPars - 1) / kDiffuseJacPars) *
                                                            ((n_rays + kDiffuseJacRays - 1) / kDiffuseJacRays)));
-  if (accumulate)
-    hipLaunchKernelGGL((sr_diffuse_contract_kernel<kDiffuseJacRays, kDiffuseJacPars, true>), grid, dim3(256), 0, st, q, n_rays,
-                       n_layers, n_pts, p_lo, p_hi, par_lo, par_hi, dj, dj_stride, dj_joff, dj_par0, par_slot, jac, n_jac_rows);
-  else
-    hipLaunchKernelGGL((sr_diffuse_contract_kernel<kDiffuseJacRays, kDiffuseJacPars, false>), grid, dim3(256), 0, st, q, n_rays,
-                       n_layers, n_pts, p_lo, p_hi, par_lo, par_hi, dj, dj_stride, dj_joff, dj_par0, par_slot, jac, n_jac_rows);
+  by_flag(accumulate, [&](auto acc) {
+    hipLaunchKernelGGL((sr_diffuse_contract_kernel<kDiffuseJacRays, kDiffuseJacPars, decltype(acc)::value>), grid, dim3(256), 0, st,
+                       q, n_rays, n_layers, n_pts, p_lo, p_hi, par_lo, par_hi, dj, dj_stride, dj_joff, dj_par0, par_slot, jac,
+                       n_jac_rows);
+  });
   return (int)hipGetLastError();
 }
 

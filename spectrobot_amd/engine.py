@@ -569,6 +569,58 @@ class AbsorberTable(object):
         return ((outs[0], outs[1]), (outs[2], outs[3])) if derivative else (outs[0], outs[1])
 
 
+def _cuda_f64(t):
+    """A contiguous CUDA float64 tensor: what every device argument of the solar and diffuse calls is."""
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+
+
+def _chunk_lists(entry, name, d, n_k, n_tiles):
+    """(tile_off [n_tiles + 1], chunks) of one of the two *_chunk_lists entries for the descriptor d."""
+    n_chunks = (n_k + 3) // 4
+    off, ch, n = np.zeros(n_tiles + 1, np.int32), np.zeros(max(n_tiles * n_chunks, 1), np.int32), C.c_int32(0)
+    check(entry(C.byref(d), n_k, off.ctypes.data_as(ip), ch.ctypes.data_as(ip), C.byref(n)), name)
+    return off, ch[:n.value].copy()
+
+
+def _jac_target(out, par_slot, accumulate, n_rays, n_par, n_pts):
+    """(out, the host array of par_slot, its pointer) of a Jacobian call that writes row par_slot[p] of out [n_rays,
+    n_jac_rows, n_pts] for parameter p: None for out is a new [n_rays, n_par, n_pts] with row p."""
+    slot, slot_p = _i(np.arange(n_par) if par_slot is None else par_slot)
+    if slot.shape != (n_par,):
+        raise ValueError("par_slot must be [n_par]")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True adds to out=...")
+        if par_slot is not None:
+            raise ValueError("par_slot places rows in out=...")
+        out = torch.empty((n_rays, n_par, n_pts), dtype=torch.float64, device="cuda")
+    elif not _cuda_f64(out) or out.dim() != 3 or out.shape[0] != n_rays or out.shape[2] != n_pts:
+        raise ValueError("out must be a contiguous CUDA float64 [n_rays, n_jac_rows, n_pts]")
+    return out, slot, slot_p
+
+
+def _diffuse_state(A, V, ssa, asym, beam, sun, mu0, surface_albedo):
+    """(sr_diffuse_desc, (n_gas, n_layers, n_pts), the host arrays it points to) of the state diffuse_source and
+    diffuse_jacobian take, checked."""
+    if not (_cuda_f64(A) and _cuda_f64(beam) and _cuda_f64(sun)) or A.dim() != 3 or beam.dim() != 2 or sun.dim() != 1:
+        raise ValueError("A, beam and sun must be contiguous CUDA float64 tensors ([n_gas, n_layers, n_pts], "
+                         "[n_layers + 1, n_pts], [n_pts])")
+    n_gas, n_layers, n_pts = (int(s) for s in A.shape)
+    if n_gas == 0 or n_layers == 0 or n_pts == 0:
+        raise ValueError("A must not be empty")
+    va, vp = _d(np.asarray(V, dtype=np.float64))
+    sa, sp = _d(np.broadcast_to(np.asarray(ssa, dtype=np.float64), (n_gas,)))
+    ga, gp = _d(np.broadcast_to(np.asarray(asym, dtype=np.float64), (n_gas,)))
+    if va.shape != (n_gas, n_layers):
+        raise ValueError("V must be [n_gas, n_layers] = [%d, %d]" % (n_gas, n_layers))
+    if beam.shape != (n_layers + 1, n_pts) or sun.shape[0] != n_pts:
+        raise ValueError("beam must be [n_layers + 1, n_pts] and sun [n_pts] on A's %d grid points" % n_pts)
+    d = _lib.DiffuseDesc()
+    d.n_gas, d.n_layers, d.v, d.ssa, d.asym = n_gas, n_layers, vp, sp, gp
+    d.mu0, d.surface_albedo = float(mu0), float(surface_albedo)
+    return d, (n_gas, n_layers, n_pts), (va, sa, ga)
+
+
 def _solar_desc(U, w, src_row):
     """(sr_solar_desc, n_k, the arrays it points to) of U [n_rows, n_k] or [n_rows, n_gas, n_layers], w, src_row."""
     U = np.asarray(U, dtype=np.float64)
@@ -596,11 +648,7 @@ def solar_chunk_lists(U, w):
     """(tile_off [n_tiles + 1], chunks) the solar-source kernel walks (sr_solar_chunk_lists, on the host: no GPU): per
     tile of 16 rows the chunks of four k in which any lit row (w != 0) of the tile has a non-zero column."""
     d, n_k, keep = _solar_desc(U, w, None)
-    n_tiles, n_chunks = (d.n_rows + 15) // 16, (n_k + 3) // 4
-    off, ch, n = np.zeros(n_tiles + 1, np.int32), np.zeros(max(n_tiles * n_chunks, 1), np.int32), C.c_int32(0)
-    check(lib.sr_solar_chunk_lists(C.byref(d), n_k, off.ctypes.data_as(ip), ch.ctypes.data_as(ip), C.byref(n)),
-          "sr_solar_chunk_lists")
-    return off, ch[:n.value].copy()
+    return _chunk_lists(lib.sr_solar_chunk_lists, "sr_solar_chunk_lists", d, n_k, (d.n_rows + 15) // 16)
 
 
 def solar_source(A, U, w, sca, sun, src_row=None, out=None, accumulate=False, transmission=False):
@@ -624,8 +672,7 @@ def solar_source(A, U, w, sca, sun, src_row=None, out=None, accumulate=False, tr
     rows made under this beam diffuse_jacobian (inversion_state(diffuse_jacobian=True)); for T and Tvib neither is
     built.  Returns emi, or (emi, trans)."""
     d, n_k, keep = _solar_desc(U, w, src_row)
-    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-    if not (ok(A) and ok(sca) and ok(sun)) or A.dim() not in (2, 3) or sca.dim() != 2 or sun.dim() != 1:
+    if not (_cuda_f64(A) and _cuda_f64(sca) and _cuda_f64(sun)) or A.dim() not in (2, 3) or sca.dim() != 2 or sun.dim() != 1:
         raise ValueError("A, sca and sun must be contiguous CUDA float64 tensors ([n_k or n_gas, n_layers, n_pts], [n_src, n_pts], [n_pts])")
     n_pts = A.shape[-1]
     if A.numel() != n_k * n_pts:
@@ -636,7 +683,7 @@ def solar_source(A, U, w, sca, sun, src_row=None, out=None, accumulate=False, tr
         if accumulate:
             raise ValueError("accumulate=True adds to out=...")
         out = torch.empty((d.n_rows, n_pts), dtype=torch.float64, device="cuda")
-    elif not ok(out) or out.shape != (d.n_rows, n_pts):
+    elif not _cuda_f64(out) or out.shape != (d.n_rows, n_pts):
         raise ValueError("out must be a contiguous CUDA float64 [n_rows, n_pts]")
     trans = torch.empty((d.n_rows, n_pts), dtype=torch.float64, device="cuda") if transmission else None
     check(lib.sr_solar_source_rows_dev(C.byref(d), C.c_void_p(A.data_ptr()), n_k, C.c_void_p(sca.data_ptr()), int(sca.shape[0]),
@@ -667,20 +714,7 @@ def diffuse_source(A, V, ssa, asym, beam, sun, mu0, surface_albedo=0.0, out_gas=
     interfaces.  One kernel, one writer per element; the same call gives the same bits.  By default every Jacobian
     treats the rows as coefficients; their derivative to VMR parameters is diffuse_jacobian
     (retrieval.inversion_state(diffuse_jacobian=True)), to T and Tvib it is not built.  Returns emi (if out_gas is given), then J, then F, as asked: one tensor or a tuple."""
-    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-    if not (ok(A) and ok(beam) and ok(sun)) or A.dim() != 3 or beam.dim() != 2 or sun.dim() != 1:
-        raise ValueError("A, beam and sun must be contiguous CUDA float64 tensors ([n_gas, n_layers, n_pts], "
-                         "[n_layers + 1, n_pts], [n_pts])")
-    n_gas, n_layers, n_pts = (int(s) for s in A.shape)
-    if n_gas == 0 or n_layers == 0 or n_pts == 0:
-        raise ValueError("A must not be empty")
-    va, vp = _d(np.asarray(V, dtype=np.float64))
-    sa, sp = _d(np.broadcast_to(np.asarray(ssa, dtype=np.float64), (n_gas,)))
-    ga, gp = _d(np.broadcast_to(np.asarray(asym, dtype=np.float64), (n_gas,)))
-    if va.shape != (n_gas, n_layers):
-        raise ValueError("V must be [n_gas, n_layers] = [%d, %d]" % (n_gas, n_layers))
-    if beam.shape != (n_layers + 1, n_pts) or sun.shape[0] != n_pts:
-        raise ValueError("beam must be [n_layers + 1, n_pts] and sun [n_pts] on A's %d grid points" % n_pts)
+    d, (n_gas, n_layers, n_pts), keep = _diffuse_state(A, V, ssa, asym, beam, sun, mu0, surface_albedo)
     if out_gas is None:
         if out is not None or accumulate:
             raise ValueError("out= and accumulate= belong to the rows of out_gas=")
@@ -690,13 +724,10 @@ def diffuse_source(A, V, ssa, asym, beam, sun, mu0, surface_albedo=0.0, out_gas=
         if accumulate:
             raise ValueError("accumulate=True adds to out=...")
         out = torch.empty((n_layers, n_pts), dtype=torch.float64, device="cuda")
-    elif not ok(out) or out.shape != (n_layers, n_pts):
+    elif not _cuda_f64(out) or out.shape != (n_layers, n_pts):
         raise ValueError("out must be a contiguous CUDA float64 [n_layers, n_pts]")
     J = torch.empty((n_layers, n_pts), dtype=torch.float64, device="cuda") if mean_intensity else None
     F = torch.empty((2, n_layers + 1, n_pts), dtype=torch.float64, device="cuda") if fluxes else None
-    d = _lib.DiffuseDesc()
-    d.n_gas, d.n_layers, d.v, d.ssa, d.asym = n_gas, n_layers, vp, sp, gp
-    d.mu0, d.surface_albedo = float(mu0), float(surface_albedo)
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     check(lib.sr_diffuse_source_rows_dev(C.byref(d), ptr(A), ptr(beam), ptr(sun), n_pts, -1 if out_gas is None else int(out_gas),
                                          int(bool(accumulate)), ptr(out), ptr(J), ptr(F), _stream_ptr()),
@@ -724,11 +755,8 @@ def solar_jacobian_chunk_lists(dU):
     the host: no GPU): per parameter and tile of 16 rows the chunks of four k in which any row of the tile has a non-zero
     dU; the tiles of parameter p stand at p n_tiles .. (p + 1) n_tiles."""
     d, n_k, keep = _solar_jac_desc(dU)
-    n_tiles, n_chunks = d.n_par * ((d.n_rows + 15) // 16), (n_k + 3) // 4
-    off, ch, n = np.zeros(n_tiles + 1, np.int32), np.zeros(max(n_tiles * n_chunks, 1), np.int32), C.c_int32(0)
-    check(lib.sr_solar_jacobian_chunk_lists(C.byref(d), n_k, off.ctypes.data_as(ip), ch.ctypes.data_as(ip), C.byref(n)),
-          "sr_solar_jacobian_chunk_lists")
-    return off, ch[:n.value].copy()
+    return _chunk_lists(lib.sr_solar_jacobian_chunk_lists, "sr_solar_jacobian_chunk_lists", d, n_k,
+                        d.n_par * ((d.n_rows + 15) // 16))
 
 
 def solar_attenuation_jacobian(A, dU, Q, out=None, par_slot=None, accumulate=False):
@@ -745,8 +773,7 @@ def solar_attenuation_jacobian(A, dU, Q, out=None, par_slot=None, accumulate=Fal
     accumulate=True; par_slot [n_par]: the row of out of every parameter (None: row p, and out [n_rays, n_par, n_pts]);
     rows that are not named keep their bits.  One fused fp64 kernel; the same call gives the same bits.  Returns out."""
     d, n_k, keep = _solar_jac_desc(dU)
-    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-    if not (ok(A) and ok(Q)) or A.dim() not in (2, 3) or Q.dim() != 3:
+    if not (_cuda_f64(A) and _cuda_f64(Q)) or A.dim() not in (2, 3) or Q.dim() != 3:
         raise ValueError("A and Q must be contiguous CUDA float64 tensors ([n_k or n_gas, n_layers, n_pts], [n_rays, n_rows, n_pts])")
     n_pts = A.shape[-1]
     if A.numel() != n_k * n_pts:
@@ -754,17 +781,7 @@ def solar_attenuation_jacobian(A, dU, Q, out=None, par_slot=None, accumulate=Fal
     if Q.shape[0] == 0 or Q.shape[1] != d.n_rows or Q.shape[2] != n_pts:
         raise ValueError("Q must be [n_rays, %d, %d]: dU's rows and A's grid points" % (d.n_rows, n_pts))
     n_rays = int(Q.shape[0])
-    slot, sp = _i(np.arange(d.n_par) if par_slot is None else par_slot)
-    if slot.shape != (d.n_par,):
-        raise ValueError("par_slot must be [n_par]")
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate=True adds to out=...")
-        if par_slot is not None:
-            raise ValueError("par_slot places rows in out=...")
-        out = torch.empty((n_rays, d.n_par, n_pts), dtype=torch.float64, device="cuda")
-    elif not ok(out) or out.dim() != 3 or out.shape[0] != n_rays or out.shape[2] != n_pts:
-        raise ValueError("out must be a contiguous CUDA float64 [n_rays, n_jac_rows, n_pts]")
+    out, slot, sp = _jac_target(out, par_slot, accumulate, n_rays, d.n_par, n_pts)
     check(lib.sr_solar_jacobian_rows_dev(C.byref(d), C.c_void_p(A.data_ptr()), n_k, C.c_void_p(Q.data_ptr()), n_rays, n_pts, sp,
                                          C.c_void_p(out.data_ptr()), int(out.shape[1]), int(bool(accumulate)), _stream_ptr()),
           "sr_solar_jacobian_rows_dev")
@@ -793,25 +810,12 @@ def diffuse_jacobian(A, V, ssa, asym, beam, sun, mu0, dV, dlnbeam, Q, surface_al
     the row of out of every parameter (None: row p, and out [n_rays, n_par, n_pts]); rows that are not named keep their
     bits.  tangent=True: also dJ [n_par, n_layers, n_pts], the counterpart of diffuse_source(mean_intensity=True).  Two
     fp64 kernels, one writer per element; the same call gives the same bits.  Returns out, (out, dJ), or dJ (Q None)."""
-    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-    if not (ok(A) and ok(beam) and ok(sun)) or A.dim() != 3 or beam.dim() != 2 or sun.dim() != 1:
-        raise ValueError("A, beam and sun must be contiguous CUDA float64 tensors ([n_gas, n_layers, n_pts], "
-                         "[n_layers + 1, n_pts], [n_pts])")
-    n_gas, n_layers, n_pts = (int(s) for s in A.shape)
-    if n_gas == 0 or n_layers == 0 or n_pts == 0:
-        raise ValueError("A must not be empty")
-    va, vp = _d(np.asarray(V, dtype=np.float64))
-    sa, sp = _d(np.broadcast_to(np.asarray(ssa, dtype=np.float64), (n_gas,)))
-    ga, gp = _d(np.broadcast_to(np.asarray(asym, dtype=np.float64), (n_gas,)))
-    if va.shape != (n_gas, n_layers):
-        raise ValueError("V must be [n_gas, n_layers] = [%d, %d]" % (n_gas, n_layers))
-    if beam.shape != (n_layers + 1, n_pts) or sun.shape[0] != n_pts:
-        raise ValueError("beam must be [n_layers + 1, n_pts] and sun [n_pts] on A's %d grid points" % n_pts)
+    d, (n_gas, n_layers, n_pts), keep = _diffuse_state(A, V, ssa, asym, beam, sun, mu0, surface_albedo)
     dva, dvp = _d(np.asarray(dV, dtype=np.float64))
     if dva.ndim != 3 or dva.shape[0] == 0 or dva.shape[1:] != (n_gas, n_layers):
         raise ValueError("dV must be [n_par, n_gas, n_layers] = [n_par, %d, %d]" % (n_gas, n_layers))
     n_par = int(dva.shape[0])
-    if dlnbeam is not None and (not ok(dlnbeam) or dlnbeam.shape != (n_par, n_layers + 1, n_pts)):
+    if dlnbeam is not None and (not _cuda_f64(dlnbeam) or dlnbeam.shape != (n_par, n_layers + 1, n_pts)):
         raise ValueError("dlnbeam must be a contiguous CUDA float64 [n_par, n_layers + 1, n_pts] or None")
     slot_p = None
     if Q is None:
@@ -821,24 +825,11 @@ def diffuse_jacobian(A, V, ssa, asym, beam, sun, mu0, dV, dlnbeam, Q, surface_al
             raise ValueError("out=, par_slot= and accumulate= belong to the product with Q=")
         n_rays = 0
     else:
-        if not ok(Q) or Q.dim() != 3 or Q.shape[0] == 0 or Q.shape[1] != n_layers or Q.shape[2] != n_pts:
+        if not _cuda_f64(Q) or Q.dim() != 3 or Q.shape[0] == 0 or Q.shape[1] != n_layers or Q.shape[2] != n_pts:
             raise ValueError("Q must be a contiguous CUDA float64 [n_rays, %d, %d]: A's layers and grid points" % (n_layers, n_pts))
         n_rays = int(Q.shape[0])
-        slot, slot_p = _i(np.arange(n_par) if par_slot is None else par_slot)
-        if slot.shape != (n_par,):
-            raise ValueError("par_slot must be [n_par]")
-        if out is None:
-            if accumulate:
-                raise ValueError("accumulate=True adds to out=...")
-            if par_slot is not None:
-                raise ValueError("par_slot places rows in out=...")
-            out = torch.empty((n_rays, n_par, n_pts), dtype=torch.float64, device="cuda")
-        elif not ok(out) or out.dim() != 3 or out.shape[0] != n_rays or out.shape[2] != n_pts:
-            raise ValueError("out must be a contiguous CUDA float64 [n_rays, n_jac_rows, n_pts]")
+        out, slot, slot_p = _jac_target(out, par_slot, accumulate, n_rays, n_par, n_pts)
     dJ = torch.empty((n_par, n_layers, n_pts), dtype=torch.float64, device="cuda") if tangent else None
-    d = _lib.DiffuseDesc()
-    d.n_gas, d.n_layers, d.v, d.ssa, d.asym = n_gas, n_layers, vp, sp, gp
-    d.mu0, d.surface_albedo = float(mu0), float(surface_albedo)
     jd = _lib.DiffuseJacDesc()
     jd.n_par, jd.dv = n_par, dvp
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None

@@ -458,65 +458,50 @@ class LimbScene(object):
         P = geometry.hg_phase(self.sun.cos_scattering, g.solar["g"])
         return np.where(lit, g.solar["albedo"] * P / (4.0 * np.pi), 0.0)
 
+    def shell_midpoints(self):
+        """The middles of the shells above the levels z (the last one as thick as the one below it): the points of the
+        solar pass's rows."""
+        zz = np.append(self.z, self.z[-1] + (self.z[-1] - self.z[-2]))
+        return 0.5 * (zz[:-1] + zz[1:])
+
     def solar_pass(self, g_lo, g_hi):
         """The emission rows of the solar gases: thermal + sca S on the layer rows (engine.solar_source under
         accumulate, on a copy of the cached thermal emi).  The point of a row is the middle of its shell, its columns
         towards the sun geometry.solar_columns with the scene's VMRs.  Held fixed by every Jacobian within one
         linearisation.  The attenuation is the 1-D scene's: a gas whose profile a driver keeps per latitude box
-        (inversion_boxes: gas.vmr_boxes) enters it with its 1-D vmr."""
+        (inversion_boxes: gas.vmr_boxes) enters it with its 1-D vmr.
+        A scene that was asked for the solar rows alone (keep_solar_rows) keeps g.solar_rows = sca S of every solar gas,
+        made by an overwrite call, and its emission rows are thermal + those -- the same sum the accumulating call
+        forms (solar_attenuation_jacobian's input).  The same rule of when nothing is redone."""
         solar = self.solar_gases()
         if not solar:
             return
         import torch
-        if self.keep_solar_rows:
-            return self.solar_pass_with_rows(solar, g_lo, g_hi)
-        done = all(g.coeffs is not g.thermal for g in solar)
+        rows = self.keep_solar_rows
+        done = all(g.coeffs is not g.thermal and (not rows or getattr(g, "solar_rows", None) is not None) for g in solar)
         if done and self.solar_frozen:
             return
-        key = self.solar_key(g_lo, g_hi)
+        key = self.solar_key(g_lo, g_hi) + (("rows",) if rows else ())
         if done and getattr(self, "_solar_key", None) == key:
             return
-        top = self.z[-1] + (self.z[-1] - self.z[-2])
-        zz = np.append(self.z, top)
-        U, lit = geometry.solar_columns(self.z, self.nd, [g.vmr for g in self.gases], 0.5 * (zz[:-1] + zz[1:]), self.sun.mu, R=self.R,
-                                   n_sub=self.n_sub, col_scale=[g.iso_ratio for g in self.gases])
-        tabs = [(g.thermal if g in solar else g.coeffs)[0] for g in self.gases]
-        A = torch.stack(tabs).contiguous()
-        sun = torch.as_tensor(self.sun.irradiance[g_lo:g_hi], device="cuda").contiguous()
-        for g in solar:
-            emi = g.thermal[1].clone()
-            engine.solar_source(A, U, self.solar_weights(g, lit), g.thermal[0], sun, out=emi, accumulate=True)
-            g.coeffs = (g.thermal[0], emi)
-        if self.sun.multiple:
-            self.diffuse_pass(solar, A, sun)
-        # (the tables themselves are kept beside the key: an id in it stays theirs while they live here.  The key knows a
-        # table by identity, as coefficient_stack does: every rebuild in this package makes new tensors; a caller who
-        # overwrites a table IN PLACE sets scene._solar_key = None)
-        self._solar_key, self._solar_tabs = key, tabs
-
-    def solar_pass_with_rows(self, solar, g_lo, g_hi):
-        """solar_pass for a scene that was asked for the solar rows alone (keep_solar_rows): every solar gas keeps
-        g.solar_rows = sca S, made by an overwrite call, and its emission rows are thermal + those -- the same sum the
-        accumulating call forms (solar_attenuation_jacobian's input).  The same rule of when nothing is redone."""
-        import torch
-        done = all(g.coeffs is not g.thermal and getattr(g, "solar_rows", None) is not None for g in solar)
-        if done and self.solar_frozen:
-            return
-        key = self.solar_key(g_lo, g_hi) + ("rows",)
-        if done and getattr(self, "_solar_key", None) == key:
-            return
-        top = self.z[-1] + (self.z[-1] - self.z[-2])
-        zz = np.append(self.z, top)
-        U, lit = geometry.solar_columns(self.z, self.nd, [g.vmr for g in self.gases], 0.5 * (zz[:-1] + zz[1:]), self.sun.mu, R=self.R,
+        U, lit = geometry.solar_columns(self.z, self.nd, [g.vmr for g in self.gases], self.shell_midpoints(), self.sun.mu, R=self.R,
                                         n_sub=self.n_sub, col_scale=[g.iso_ratio for g in self.gases])
         tabs = [(g.thermal if g in solar else g.coeffs)[0] for g in self.gases]
         A = torch.stack(tabs).contiguous()
         sun = torch.as_tensor(self.sun.irradiance[g_lo:g_hi], device="cuda").contiguous()
         for g in solar:
-            g.solar_rows = engine.solar_source(A, U, self.solar_weights(g, lit), g.thermal[0], sun)
-            g.coeffs = (g.thermal[0], g.thermal[1] + g.solar_rows)
+            if rows:
+                g.solar_rows = engine.solar_source(A, U, self.solar_weights(g, lit), g.thermal[0], sun)
+                emi = g.thermal[1] + g.solar_rows
+            else:
+                emi = g.thermal[1].clone()
+                engine.solar_source(A, U, self.solar_weights(g, lit), g.thermal[0], sun, out=emi, accumulate=True)
+            g.coeffs = (g.thermal[0], emi)
         if self.sun.multiple:       # (g.solar_rows stays the single-scattered part alone)
             self.diffuse_pass(solar, A, sun)
+        # (the tables themselves are kept beside the key: an id in it stays theirs while they live here.  The key knows a
+        # table by identity, as coefficient_stack does: every rebuild in this package makes new tensors; a caller who
+        # overwrites a table IN PLACE sets scene._solar_key = None)
         self._solar_key, self._solar_tabs = key, tabs
 
     def diffuse_geometry(self, solar):
@@ -526,9 +511,7 @@ class LimbScene(object):
         ssa = np.array([g.solar["albedo"] if g in solar else 0.0 for g in self.gases])
         asym = np.array([g.solar["g"] if g in solar else 0.0 for g in self.gases])
         iso = np.array([float(g.iso_ratio) for g in self.gases])
-        top = self.z[-1] + (self.z[-1] - self.z[-2])
-        zz = np.append(self.z, top)
-        pts = np.append(0.5 * (zz[:-1] + zz[1:]), self.z[0])
+        pts = np.append(self.shell_midpoints(), self.z[0])
         return ssa, asym, iso, pts, iso * (1.0 - ssa * np.maximum(asym, 0.0) ** 2)
 
     def diffuse_inputs(self, solar, A, sun):
@@ -577,18 +560,14 @@ class LimbScene(object):
         n_col = len(w.par_gas)
         if n_col == 0:
             return jac
-        top = self.z[-1] + (self.z[-1] - self.z[-2])
-        zz = np.append(self.z, top)
-        dU, _ = geometry.solar_column_weights(self.z, self.nd, w.col_masks, w.par_gas, len(self.gases), 0.5 * (zz[:-1] + zz[1:]),
+        dU, _ = geometry.solar_column_weights(self.z, self.nd, w.col_masks, w.par_gas, len(self.gases), self.shell_midpoints(),
                                               self.sun.mu, R=self.R, n_sub=self.n_sub, col_scale=[g.iso_ratio for g in self.gases])
         a, _ = engine.gas_stack(coeffs)
         sol = torch.zeros_like(a)
         for g in solar:
             sol[self.gases.index(g)] = g.solar_rows
-        Q = engine.limb_rays_layer_jacobian(coeffs, (torch.zeros_like(a), sol), los)
-        if jac is None:
-            return engine.solar_attenuation_jacobian(a, dU, Q)
-        return engine.solar_attenuation_jacobian(a, dU, Q, out=jac, par_slot=np.arange(n_col), accumulate=True)
+        Q = self._emission_rows_jacobian(coeffs, sol, los)
+        return self._into_jac(engine.solar_attenuation_jacobian, (a, dU, Q), jac, n_col)
 
     def diffuse_jacobian(self, los, alt, w, coeffs, jac=None):
         """The diffuse rows in the column rows of a state Jacobian: d rad / d x_p through the two-stream solve of the
@@ -623,12 +602,23 @@ class LimbScene(object):
         for g in solar:
             i = self.gases.index(g)
             W[i] = A[i] * float(ssa[i] * (1.0 - f[i]))
-        Q = engine.limb_rays_layer_jacobian(coeffs, (torch.zeros_like(A), W), los)
-        kw = dict(surface_albedo=self.sun.surface_albedo)
+        Q = self._emission_rows_jacobian(coeffs, W, los)
+        return self._into_jac(engine.diffuse_jacobian, (A, V, ssa, asym, beam, sun, self.sun.mu, dV, dlnbeam, Q), jac, n_col,
+                              surface_albedo=self.sun.surface_albedo)
+
+    @staticmethod
+    def _emission_rows_jacobian(coeffs, demi, los):
+        """Q [n_rays, n_layers, n_pts]: the radiances' derivative to a factor on the rows demi [n_gas, n_layers, n_pts] of
+        the emission, the absorption held: ONE limb_rays_layer_jacobian call with dabs = 0."""
+        import torch
+        return engine.limb_rays_layer_jacobian(coeffs, (torch.zeros_like(demi), demi), los)
+
+    @staticmethod
+    def _into_jac(fused, args, jac, n_col, **kw):
+        """fused(*args) as its own [n_rays, n_col, n_pts] (jac None), or added to rows 0 .. n_col - 1 of jac."""
         if jac is None:
-            return engine.diffuse_jacobian(A, V, ssa, asym, beam, sun, self.sun.mu, dV, dlnbeam, Q, **kw)
-        return engine.diffuse_jacobian(A, V, ssa, asym, beam, sun, self.sun.mu, dV, dlnbeam, Q, out=jac, par_slot=np.arange(n_col),
-                                       accumulate=True, **kw)
+            return fused(*args, **kw)
+        return fused(*args, out=jac, par_slot=np.arange(n_col), accumulate=True, **kw)
 
     def folded_into(self, g):
         return [t for t in self.folded if t.accumulate_into == g.name]

@@ -1,8 +1,8 @@
 """The solar attenuation in the Jacobians on the GPU: sr_solar_jac_kernel through engine.solar_attenuation_jacobian
 against the long-double definition of tests/solar_jacobian_reference.py inside its bound on the panel of tile, chunk, store
 and ray-group edges (n_rows 1, 15, 17, 33 x n_k 1, 3, 5, 13, 160 x n_pts 1, 63, 65, 257, (n_rays, n_par) cycling through
-(1, 1), (3, 2), (NR + 1, 5), (9, 17)), the exact cases, every refusal, and the composition it stands for: Q from
-engine.limb_rays_layer_jacobian, dU @ A and the row sum in torch."""
+(1, 1), (3, 2), (NR + 1, 5), (9, 17)), the exact cases, a second batch of chunks (n_k 259), every refusal, and the
+composition it stands for: Q from engine.limb_rays_layer_jacobian, dU @ A and the row sum in torch."""
 import ctypes as C
 
 import numpy as np
@@ -110,6 +110,32 @@ def test_exact_cases(eng):
     w = _np(wide)
     assert np.array_equal(w[:, slots].view(np.uint64), j.view(np.uint64))
     assert np.all(w[:, [2, 5, 7]] == -7.0)
+
+
+def test_a_second_batch_of_chunks(eng):
+    """n_k = 259 is 65 chunks: with every chunk listed a tile walks one whole batch of 64 through LDS, then a batch of one
+    chunk padded to a pair, the last chunk of three k -- on 17 rows (a second row tile of one row), 65 points (a partial
+    quad), NR + 1 rays and two parameters.  Overwrite and accumulate, each inside the bound with full lists and bit for bit
+    the sparse-list call."""
+    import torch
+    key = (17, 259, 65, R.NR + 1, 2)
+    c = _case(*key)
+    base = np.random.default_rng(5).uniform(-1e-8, 1e-8, (R.NR + 1, 2, 65))
+    both = lambda: (_call(eng, c), _call(eng, c, out=_dev(base), accumulate=True))
+    sparse = both()
+    eng.set_solar_full_lists(True)
+    try:
+        full = both()
+        off_f, ch_f = eng.solar_jacobian_chunk_lists(c["dU"])
+    finally:
+        eng.set_solar_full_lists(False)
+    assert list(np.diff(off_f)) == [65] * 4 and ch_f[64] == 64            # (a second batch in every tile of both parameters)
+    jac, acc = (_np(x) for x in full)
+    assert R.ratio(jac, c["jac"], c["b"]) <= 1.0
+    total = base.astype(LD) + c["jac"]
+    assert R.ratio(acc, total, R.bound_accumulated(c["b"], total)) <= 1.0
+    for x, y in zip(sparse, full):
+        assert torch.equal(x, y)
 
 
 def test_every_refusal_leaves_jac_untouched(eng):

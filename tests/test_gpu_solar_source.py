@@ -1,9 +1,9 @@
 """The single-scattering solar source on the GPU: sr_solar_source_kernel through engine.solar_source against the long-double
 definition of tests/solar_source_reference.py inside its bound on the panel of tile, chunk and store edges (n_rows 1, 15,
-17, 33, 65 x n_k 1, 3, 5, 13, 160 x n_pts 1, 63, 65, 257), the exact cases, every refusal, and the plumbing above it: a
-homogeneous segment through engine.limb_rays against S (1 - exp(-tau_los)), the composed torch route, a scene with a sun
-whose scatterer has albedo 0 against the scene without one, and the state Jacobian of a line gas + sunlit haze scene
-against central differences with the solar rows frozen."""
+17, 33, 65 x n_k 1, 3, 5, 13, 160 x n_pts 1, 63, 65, 257), the exact cases, a second batch of chunks (n_k 259), every
+refusal, and the plumbing above it: a homogeneous segment through engine.limb_rays against S (1 - exp(-tau_los)), the
+composed torch route, a scene with a sun whose scatterer has albedo 0 against the scene without one, and the state Jacobian
+of a line gas + sunlit haze scene against central differences with the solar rows frozen."""
 import copy
 import ctypes as C
 
@@ -123,6 +123,36 @@ def test_exact_cases(eng):
     acc2 = base.clone()
     _call(eng, c, out=acc2, accumulate=True)         # ... without the transmission too
     assert np.array_equal(_np(acc2).view(np.uint64), a.view(np.uint64))
+
+
+def test_a_second_batch_of_chunks(eng):
+    """n_k = 259 is 65 chunks: with every chunk listed a tile walks one whole batch of 64 through LDS, then a batch of one
+    chunk padded to a pair, the last chunk of three k -- on 17 rows (a second row tile of one row) and 65 points (a partial
+    quad).  Overwrite with the transmission and accumulate, each inside the bound with full lists and bit for bit the
+    sparse-list call."""
+    import torch
+    c = _case(17, 259, 65)
+    base = np.random.default_rng(5).uniform(-1e-8, 1e-8, (17, 65))
+
+    def both():
+        emi, trans = _call(eng, c, transmission=True)
+        acc = _call(eng, c, out=_dev(base), accumulate=True)
+        return emi, trans, acc
+
+    sparse = both()
+    eng.set_solar_full_lists(True)
+    try:
+        full = both()
+        off_f, ch_f = eng.solar_chunk_lists(c["U"], c["w"])
+    finally:
+        eng.set_solar_full_lists(False)
+    assert list(np.diff(off_f)) == [65, 65] and ch_f[64] == 64            # (a second batch in every tile)
+    e, t, a = (_np(x) for x in full)
+    assert R.ratio(e, c["emi"], c["b_emi"]) <= 1.0 and R.ratio(t, c["trans"], c["b_trans"]) <= 1.0
+    s = base.astype(LD) + e.astype(LD)                                    # the overwrite result plus the base, to one rounding
+    assert np.all(np.abs(a.astype(LD) - s) <= EPS * np.abs(s))
+    for x, y in zip(sparse, full):
+        assert torch.equal(x, y)
 
 
 def test_every_refusal_leaves_the_outputs_untouched(eng):

@@ -29,7 +29,8 @@ def test_abi_surface():
 
 
 def test_reference_against_its_fp64_restatement():
-    """A term-by-term fp64 loop stays inside the bound on 200 random cases (n_k 1 .. 160, about half zeros, both signs)."""
+    """A term-by-term fp64 loop stays inside the bound on 200 random cases (n_k 1 .. 160, about half zeros, both signs) and
+    on the panel case of n_k = 259."""
     rng = np.random.default_rng(20261020)
     worst = 0.0
     for case in range(200):
@@ -40,6 +41,9 @@ def test_reference_against_its_fp64_restatement():
         Q = rng.normal(size=(n_rays, n_rows, n_pts)) * 1e-8
         jac, b = R.reference(A, dU, Q)
         worst = max(worst, R.ratio(R.plain64(A, dU, Q), jac, b))
+    c = R.panel_case(17, 259, 65, R.NR + 1, 2)       # the GPU test's case of a second batch of chunks
+    jac, b = R.reference(c["A"], c["dU"], c["Q"])
+    worst = max(worst, R.ratio(R.plain64(c["A"], c["dU"], c["Q"]), jac, b))
     print("plain fp64 against the reference, in units of the bound: %.3f" % worst)
     assert worst <= 1.0
 
@@ -205,6 +209,21 @@ def test_chunk_lists(n_par, n_rows, n_k):
         off3, ch3 = engine.solar_jacobian_chunk_lists(dU)
         off4, ch4 = engine.solar_jacobian_chunk_lists(dU.reshape(n_par, n_rows, 2, n_k // 2))
         assert np.array_equal(off4, off3) and np.array_equal(ch4, ch3)
+
+
+@pytest.mark.parametrize("n_rows,n_k", [(1, 1), (15, 3), (17, 5), (33, 13), (33, 160), (65, 160)])
+def test_one_parameter_of_non_negative_columns_lists_what_the_source_lists(n_rows, n_k):
+    """The two plans are one walk: dU >= 0 as ONE parameter against the same array as the source's U with every row lit."""
+    from spectrobot_amd import engine
+    dU = np.abs(R.mask_columns(np.random.default_rng([9, n_rows, n_k]), 1, n_rows, n_k))[0]
+    for full in (False, True):
+        engine.set_solar_full_lists(full)
+        try:
+            off_j, ch_j = engine.solar_jacobian_chunk_lists(dU[None])
+            off_s, ch_s = engine.solar_chunk_lists(dU, np.ones(n_rows))
+        finally:
+            engine.set_solar_full_lists(False)
+        assert np.array_equal(off_j, off_s) and np.array_equal(ch_j, ch_s)
 
 
 def test_chunk_lists_refusals():

@@ -26,7 +26,8 @@ def test_abi_surface():
 
 
 def test_reference_against_its_fp64_restatement():
-    """A term-by-term fp64 loop stays inside the bound on 200 random cases (n_k 1 .. 640, tau 0.01 .. 200)."""
+    """A term-by-term fp64 loop stays inside the bound on 200 random cases (n_k 1 .. 640, tau 0.01 .. 200) and on the panel
+    case of n_k = 259."""
     rng = np.random.default_rng(20261020)
     worst_e = worst_t = 0.0
     for case in range(200):
@@ -39,6 +40,11 @@ def test_reference_against_its_fp64_restatement():
         e64, t64 = R.plain64(A, U, w, sca, sun)
         worst_e = max(worst_e, R.ratio(e64, emi, R.bound_emi(emi, tau, K)))
         worst_t = max(worst_t, R.ratio(t64, trans, R.bound_trans(trans, tau, K)))
+    c = R.panel_case(17, 259, 65)                    # the GPU test's case of a second batch of chunks
+    emi, trans, tau, K = R.reference(c["A"], c["U"], c["w"], c["sca"], c["sun"], c["src_row"])
+    e64, t64 = R.plain64(c["A"], c["U"], c["w"], c["sca"], c["sun"], c["src_row"])
+    worst_e = max(worst_e, R.ratio(e64, emi, R.bound_emi(emi, tau, K)))
+    worst_t = max(worst_t, R.ratio(t64, trans, R.bound_trans(trans, tau, K)))
     print("plain fp64 against the reference, in units of the bound: emi %.3f trans %.3f" % (worst_e, worst_t))
     assert worst_e <= 1.0 and worst_t <= 1.0
 

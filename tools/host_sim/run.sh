@@ -7,6 +7,7 @@ name=${1:?usage: tools/host_sim/run.sh <name>}
 root=$(cd "$(dirname "$0")/../.." && pwd)
 tmp=$(mktemp -d)
 trap 'rm -rf "$tmp"' EXIT
+# (-Wno-psabi: sr_solar_tile.inc's helpers return four doubles as a vector, inlined within the one unit: no ABI is crossed)
 ${CXX:-/opt/rocm/lib/llvm/bin/clang++} -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-  -pthread -I"$root/spectrobot_amd/csrc" -I"$root/tools/host_sim" "$root/tools/$name/main.cpp" -o "$tmp/$name"
+  -Wno-psabi -pthread -I"$root/spectrobot_amd/csrc" -I"$root/tools/host_sim" "$root/tools/$name/main.cpp" -o "$tmp/$name"
 "$tmp/$name"

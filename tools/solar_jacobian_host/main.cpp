@@ -1,5 +1,5 @@
-// Host build of sr_solar_jac_kernel's own text (spectrobot_amd/csrc/sr_solar_jac.inc with the chunk lists of
-// sr_solar_plan.hpp, the files the library compiles) behind tools/host_sim/hip_on_host.hpp with threaded lanes: a block is
+// Host build of sr_solar_jac_kernel's own text (spectrobot_amd/csrc/sr_solar_jac.inc on sr_solar_tile.inc with the chunk
+// lists of sr_solar_plan.hpp, the files the library compiles) behind tools/host_sim/hip_on_host.hpp with threaded lanes: a block is
 // 256 threads, its barrier a real barrier, v_mfma_f64_16x16x4 emulated in its operand layout.  Every buffer has exactly
 // the size the entry gives it, so that AddressSanitizer sees an index beyond it; jac starts as a known pattern with more
 // rows than parameters, so that the comparison sees a place that was not written and one that should not have been.
@@ -8,7 +8,9 @@
 // cycling through (1, 1), (3, 2), (NR + 1, 5), (9, 17) -- tile, chunk, store and ray-group edges --, du of both signs laid
 // out as a mask's columns are, a parameter without columns and a ray whose q is zero; the overwrite instance on the whole
 // panel (the widest shape on a diagonal of it, the (3, 2) shape in its place elsewhere), the accumulating one on a fifth
-// of it; sparse lists against full lists, which must agree in every bit.  Built with AddressSanitizer and UBSan by tools/host_sim/run.sh
+// of it; sparse lists against full lists, which must agree in every bit.  Behind the panel n_k = 259 at 17 rows x 63 and 65
+// points, (NR + 1, 2), both instances: with every chunk listed a tile walks 65 chunks -- one whole batch of kSolarBatch,
+// then a batch of one chunk padded to a pair, the last chunk of three k.  Built with AddressSanitizer and UBSan by tools/host_sim/run.sh
 // solar_jacobian_host -- indexing, lists, tile, row and ray mapping on a machine without a GPU, not the compiled gfx950 code.
 #define HOST_SIM_THREADED_LANES
 #include "hip_on_host.hpp"
@@ -17,9 +19,7 @@ static void block_barrier() { pthread_barrier_wait(&g_block_bar); }
 #define __syncthreads block_barrier
 #include "sr_solar_plan.hpp"
 namespace sr {
-// (the two names sr_solar_jac.inc takes from sr_solar_source.inc)
-typedef double SolarQuad __attribute__((ext_vector_type(4), aligned(8)));
-constexpr int kSolarBatch = 64;
+#include "sr_solar_tile.inc"
 #include "sr_solar_jac.inc"
 }
 using namespace sr;
@@ -144,6 +144,13 @@ int main() {
         bad += bc;
         ++n;
       }
+  for (int d = 1; d < 3; ++d) { // a second batch of chunks: 65 with every chunk listed
+    const Case c = make_case(17, 259, pts[d], kSolarJacRays + 1, 2, seed++);
+    const int bc = check_case<false>(c) + check_case<true>(c);
+    if (bc) std::printf("n_rows 17 n_k 259 n_pts %d n_rays %d n_par 2: FAILED\n", pts[d], kSolarJacRays + 1);
+    bad += bc;
+    ++n;
+  }
   std::printf(bad ? "FAILED\n" : "all %d cases ok\n", n);
   return bad ? 1 : 0;
 }

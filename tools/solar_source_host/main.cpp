@@ -1,12 +1,15 @@
-// Host build of sr_solar_source_kernel's own text (spectrobot_amd/csrc/sr_solar_source.inc with the chunk lists of
-// sr_solar_plan.hpp, the files the library compiles) behind tools/host_sim/hip_on_host.hpp with threaded lanes: a block is
+// Host build of sr_solar_source_kernel's own text (spectrobot_amd/csrc/sr_solar_source.inc on sr_solar_tile.inc with the
+// chunk lists of sr_solar_plan.hpp, the files the library compiles) behind tools/host_sim/hip_on_host.hpp with threaded lanes: a block is
 // 256 threads, its barrier a real barrier, v_mfma_f64_16x16x4 emulated in its operand layout.  Every buffer has exactly
 // the size the entry gives it, so that AddressSanitizer sees an index beyond it; the outputs start as NaN (or, accumulating,
 // as a known pattern), so that the comparison sees a place that was not written.  Against plain loops in long double to
 // the bound of tests/solar_source_reference.py, on the panel of tests/test_gpu_solar_source.py: n_rows 1, 15, 17, 33, 65 x
 // n_k 1, 3, 5, 13, 160 x n_pts 1, 63, 65, 257 (tile, chunk and store edges) with columns laid out as a ray's are, rows in
 // shadow, a row without columns and a row beyond tau = 700; the overwrite instance with the transmission on the whole
-// panel, the other three on its corners; sparse lists against full lists, which must agree in every bit.  The
+// panel, the other three on its corners; sparse lists against full lists, which must agree in every bit.  Behind the
+// panel n_k = 259 at 17 rows x 63 and 65 points, overwrite with the transmission and accumulate: with every chunk listed
+// a tile walks 65 chunks -- one whole batch of kSolarBatch, then a batch of one chunk padded to a pair, the last chunk of
+// three k.  The
 // exponential here is the host's (the device routine is pinned on the GPU).  Built with AddressSanitizer and UBSan by
 // tools/host_sim/run.sh solar_source_host -- indexing, lists, tile and row mapping on a machine without a GPU, not the
 // compiled gfx950 code.
@@ -18,6 +21,7 @@ static void block_barrier() { pthread_barrier_wait(&g_block_bar); }
 #include "sr_solar_plan.hpp"
 namespace sr {
 static inline double exp_bounded(double u) { return std::exp(u); }
+#include "sr_solar_tile.inc"
 #include "sr_solar_source.inc"
 }
 using namespace sr;
@@ -128,6 +132,13 @@ int main() {
         bad += bc;
         ++n;
       }
+  for (int d = 1; d < 3; ++d) { // a second batch of chunks: 65 with every chunk listed
+    const Case c = make_case(17, 259, pts[d], seed++);
+    const int bc = check_case<false, true>(c) + check_case<true, false>(c);
+    if (bc) std::printf("n_rows 17 n_k 259 n_pts %d: FAILED\n", pts[d]);
+    bad += bc;
+    ++n;
+  }
   std::printf(bad ? "FAILED\n" : "all %d cases ok\n", n);
   return bad ? 1 : 0;
 }
