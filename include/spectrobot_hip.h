@@ -1095,6 +1095,41 @@ int sr_diffuse_jacobian_rows_dev(const sr_diffuse_desc *desc, const sr_diffuse_j
                                  int64_t n_pts, const int32_t *par_slot, double *jac, int n_jac_rows, int accumulate,
                                  double *dj_out, void *stream);
 
+/* The diffuse rows along a direction in the haze optics: d radiance / d (ssa, asym, surface_albedo) THROUGH the two-stream
+ * solve of sr_diffuse_source_rows_dev.  The build's own definition.  Parameter p moves ssa_g by
+ * dssa[p][g], asym_g by dasym[p][g] and surface_albedo by dalb[p]; the per-gas coefficients as built move by
+ *   f = max(asym, 0)^2, df = 2 max(asym, 0) dasym (0 for asym <= 0)
+ *   d(ssa (1 - f)) = dssa (1 - f) - ssa df,  d(1 - ssa) = -dssa,  d(ssa (asym - f)) = dssa (asym - f) + ssa (dasym - df)
+ * and per layer and grid point the three sums by these times t_g = v[g][l] tab_abs[g N + l][j], the source by
+ * d D_l = D_l dlnbeam[p][l][j], the boundary by
+ *   d Rb_0 = dalb[p],   d Ub_0 = Ub_0 dlnbeam[p][N][j] + dalb[p] max(mu0, 0) sun[j] beam[N][j]
+ * (no division by the albedo: 0 is an ordinary state).  dJ[p][l][j] is the tangent of J_l of the function AS BUILT, with
+ * sr_diffuse_jacobian_rows_dev's three rules (the floor of co, g' = 0 where sigma' == 0, an empty layer), and
+ *   jac[y][par_slot[p]][j] (+)= sum_{l < N} q[y][l][j] dJ[p][l][j]            l ascending, one writer per element
+ * by the contraction kernel of sr_diffuse_jacobian_rows_dev.  desc, tab_abs, beam, sun, dlnbeam, q, n_rays, n_pts,
+ * par_slot, jac, n_jac_rows, accumulate, dj_out, stream: as sr_diffuse_jacobian_rows_dev takes them.  odesc: dssa and
+ * dasym HOST [n_par][n_gas], either may be NULL (zeros: a direction in the albedo only); dalb HOST [n_par] or NULL
+ * (zeros); finite, any sign.  The coefficients' tangents and per parameter the range of layers in which a gas with a
+ * non-zero tangent has a column (empty for a direction in the albedo alone: the operators of every layer stand still and
+ * only the boundary's terms are carried upward) are made on the host and staged through the calling thread's pinned
+ * ring.  Kernels, workspace, chunks, tiles and the one-stream rule: those of sr_diffuse_jacobian_rows_dev, the tangent
+ * kernel in its optics instance (four parameters per tile).  Every argument is checked before the first copy or launch
+ * and a refused call leaves the outputs untouched, in the order of sr_diffuse_jacobian_rows_dev: SR_ERR_ARG for a NULL
+ * desc, v, ssa, asym, odesc, tab_abs, beam or sun or dssa, dasym and dalb all NULL, n_gas <= 0, n_layers <= 0, n_pts <= 0,
+ * n_par <= 0, q without jac or jac without q, neither jac nor dj_out, jac without par_slot or with n_rays <= 0 or
+ * n_jac_rows <= 0, a v, ssa, asym, mu0 or surface_albedo that is not finite or outside its range; SR_ERR_ARG for a dssa,
+ * dasym or dalb that is not finite; SR_ERR_LIMIT for n_gas > 8, n_layers > SR_MAX_ABS_ROWS, n_pts > 2000000 or
+ * n_par n_gas n_layers > SR_MAX_SOLAR_VALUES; SR_ERR_ARG for a par_slot outside 0 .. n_jac_rows - 1 or named twice.
+ * Checked against an extended-precision reference (tests/test_gpu_diffuse_optics.py). */
+typedef struct {
+  int32_t n_par;
+  const double *dssa, *dasym, *dalb; /* [n_par][n_gas] x2, [n_par] */
+} sr_diffuse_optics_desc;
+int sr_diffuse_optics_jacobian_rows_dev(const sr_diffuse_desc *desc, const sr_diffuse_optics_desc *odesc, const double *tab_abs,
+                                        const double *beam, const double *sun, const double *dlnbeam, const double *q, int n_rays,
+                                        int64_t n_pts, const int32_t *par_slot, double *jac, int n_jac_rows, int accumulate,
+                                        double *dj_out, void *stream);
+
 /* Evaluation mode of the coefficient op.  Far region-1 wings by local Taylor expansions per box of grid
  * points (truncation <= sr_far_field_truncation_bound() of a line's own contribution: 1.6e-11 as built by default, degree
  * 19; 2.6e-13 with -DSR_KFD=22; a box takes a line from sr_far_field_min_distance() on), near field exact, with the expansions built

@@ -97,6 +97,10 @@ class DiffuseJacDesc(C.Structure):
     _fields_ = [("n_par", C.c_int32), ("dv", dp)]
 
 
+class DiffuseOpticsDesc(C.Structure):
+    _fields_ = [("n_par", C.c_int32), ("dssa", dp), ("dasym", dp), ("dalb", dp)]
+
+
 class IlsDesc(C.Structure):
     _fields_ = [("n_shapes", C.c_int32), ("n_tab", C.c_int32), ("t_lo", C.c_double), ("t_hi", C.c_double), ("phi", dp)]
 
@@ -238,6 +242,9 @@ SYMBOLS = {
     "sr_diffuse_jacobian_rows_dev": (C.c_int, [C.POINTER(DiffuseDesc), C.POINTER(DiffuseJacDesc), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, ip, C.c_void_p, C.c_int,
                                                C.c_int, C.c_void_p, C.c_void_p]),
+    "sr_diffuse_optics_jacobian_rows_dev": (C.c_int, [C.POINTER(DiffuseDesc), C.POINTER(DiffuseOpticsDesc), C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, ip, C.c_void_p,
+                                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sr_set_points_per_lane": (C.c_int, [C.c_int]),
     "sr_set_band_fusion": (C.c_int, [C.c_int]),
     "sr_far_field_truncation_bound": (C.c_double, []),

@@ -4294,6 +4294,62 @@ int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_ab
   return pk.slot().mark(st);
 }
 
+// What the two Jacobian entries share once their arguments are checked: par_slot's check, the workspace, the staging and
+// the launches (the entry's comment below).  dir is the direction as its kernel instance reads it: dv
+// [n_par][n_gas][n_layers], or -- optics -- dopt [n_par][kDiffuseOpt] (sr_diffuse_optics_jacobian_rows_dev); mask is that
+// direction's plan.
+static int diffuse_jacobian_run(const sr_diffuse_desc *desc, const double (&coef)[3 * kDiffuseGases], int n_par,
+                                const std::vector<int> &mask, const double *dir, bool optics, const double *tab_abs,
+                                const double *beam, const double *sun, const double *dlnbeam, const double *q, int n_rays,
+                                int64_t n_pts, const int32_t *par_slot, double *jac, int n_jac_rows, int accumulate,
+                                double *dj_out, void *stream) {
+  const int n_gas = desc->n_gas, n_layers = desc->n_layers;
+  int rc = jac ? check_par_slots(par_slot, n_par, n_jac_rows) : SR_OK;
+  if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // the workspace: doubles per (tile, layer, point), then points per launch, then tiles per launch
+  const bool dj_ws = jac && !dj_out;
+  const size_t per = (size_t)8 * n_layers * (3 + 4 * kDiffuseJacPars + (dj_ws ? kDiffuseJacPars : 0));
+  const int n_tiles = (n_par + kDiffuseJacPars - 1) / kDiffuseJacPars;
+  const DiffuseChunks dc = diffuse_chunks(per, n_pts, n_tiles);
+  const int chunk = dc.chunk, tiles = dc.tiles;
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  DevBuf &ws = diffuse_workspace(dev);
+  rc = ws.ensure(per * (size_t)chunk * tiles);
+  if (rc) return rc;
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_v = pk.copy(desc->v, (size_t)n_gas * n_layers), p_c = pk.copy(coef, (size_t)3 * kDiffuseGases);
+  const auto p_dir = pk.copy(dir, (size_t)n_par * (optics ? (size_t)kDiffuseOpt : (size_t)n_gas * n_layers));
+  const auto p_m = pk.copy(mask.data(), mask.size());
+  const auto p_slot = pk.copy(par_slot, jac ? (size_t)n_par : 0, 1);
+  rc = pk.stage(st);
+  if (rc) return rc;
+  double *sweep = ws.as<double>();
+  double *dj_room = sweep + (size_t)tiles * (3 + 4 * kDiffuseJacPars) * n_layers * chunk; // (used with dj_ws only)
+  for (int64_t p_lo = 0; p_lo < n_pts; p_lo += chunk) {
+    const int p_hi = (int)std::min<int64_t>(n_pts, p_lo + chunk);
+    for (int t0 = 0; t0 < n_tiles; t0 += tiles) {
+      const int par_lo = t0 * kDiffuseJacPars, par_hi = std::min(n_par, (t0 + tiles) * kDiffuseJacPars);
+      double *dj = dj_ws ? dj_room : dj_out;
+      const int dj_stride = dj_ws ? chunk : (int)n_pts, dj_joff = dj_ws ? (int)p_lo : 0, dj_par0 = dj_ws ? par_lo : 0;
+      if (!optics)
+        LAUNCHCHK(launch_diffuse_tangent(tab_abs, n_gas, n_layers, (int)n_pts, (int)p_lo, p_hi, par_lo, par_hi, pk.dev(p_v),
+                                         pk.dev(p_dir), pk.dev(p_c), pk.dev(p_m), beam, sun, dlnbeam, desc->mu0, desc->surface_albedo,
+                                         sweep, chunk, dj, dj_stride, dj_joff, dj_par0, st));
+      else
+        LAUNCHCHK(launch_diffuse_optics_tangent(tab_abs, n_gas, n_layers, (int)n_pts, (int)p_lo, p_hi, par_lo, par_hi, pk.dev(p_v),
+                                                pk.dev(p_dir), pk.dev(p_c), pk.dev(p_m), beam, sun, dlnbeam, desc->mu0,
+                                                desc->surface_albedo, sweep, chunk, dj, dj_stride, dj_joff, dj_par0, st));
+      if (jac)
+        LAUNCHCHK(launch_diffuse_contract(q, n_rays, n_layers, (int)n_pts, (int)p_lo, p_hi, par_lo, par_hi, dj, dj_stride, dj_joff,
+                                          dj_par0, pk.dev(p_slot), accumulate != 0, jac, n_jac_rows, st));
+    }
+  }
+  return pk.slot().mark(st);
+}
+
 // The diffuse rows in the Jacobians (sr_diffuse_jac.inc).  The workspace is the source's: per (parameter tile, point)
 // 3 + 4 kDiffuseJacPars doubles per layer for the two sweeps and, where the caller takes no dj_out, kDiffuseJacPars more
 // for the dJ rows the contraction reads; a call whose workspace would pass kDiffuseWsBytes is made in point chunks and
@@ -4316,45 +4372,36 @@ int sr_diffuse_jacobian_rows_dev(const sr_diffuse_desc *desc, const sr_diffuse_j
   std::vector<int> mask;
   if (!too_large && !diffuse_jac_masks(desc->v, jdesc->dv, jdesc->n_par, desc->n_gas, desc->n_layers, mask)) return SR_ERR_ARG;
   if (too_large) return SR_ERR_LIMIT;
-  const int n_gas = desc->n_gas, n_layers = desc->n_layers, n_par = jdesc->n_par;
-  if (jac && (rc = check_par_slots(par_slot, n_par, n_jac_rows)) != 0) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // the workspace: doubles per (tile, layer, point), then points per launch, then tiles per launch
-  const bool dj_ws = jac && !dj_out;
-  const size_t per = (size_t)8 * n_layers * (3 + 4 * kDiffuseJacPars + (dj_ws ? kDiffuseJacPars : 0));
-  const int n_tiles = (n_par + kDiffuseJacPars - 1) / kDiffuseJacPars;
-  const DiffuseChunks dc = diffuse_chunks(per, n_pts, n_tiles);
-  const int chunk = dc.chunk, tiles = dc.tiles;
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  DevBuf &ws = diffuse_workspace(dev);
-  rc = ws.ensure(per * (size_t)chunk * tiles);
+  return diffuse_jacobian_run(desc, coef, jdesc->n_par, mask, jdesc->dv, false, tab_abs, beam, sun, dlnbeam, q, n_rays, n_pts,
+                              par_slot, jac, n_jac_rows, accumulate, dj_out, stream);
+}
+
+// The diffuse rows along a direction in the optics (sr_diffuse_tangent_kernel<NP, true>, sr_diffuse_jac.inc): the argument
+// rules, the order of the checks and the limits of sr_diffuse_jacobian_rows_dev, with (dssa, dasym, dalb) in dv's place.
+int sr_diffuse_optics_jacobian_rows_dev(const sr_diffuse_desc *desc, const sr_diffuse_optics_desc *odesc, const double *tab_abs,
+                                        const double *beam, const double *sun, const double *dlnbeam, const double *q, int n_rays,
+                                        int64_t n_pts, const int32_t *par_slot, double *jac, int n_jac_rows, int accumulate,
+                                        double *dj_out, void *stream) {
+  if (!desc || !desc->v || !desc->ssa || !desc->asym || !odesc || (!odesc->dssa && !odesc->dasym && !odesc->dalb) || !tab_abs ||
+      !beam || !sun)
+    return SR_ERR_ARG;
+  if (desc->n_gas <= 0 || desc->n_layers <= 0 || n_pts <= 0 || odesc->n_par <= 0) return SR_ERR_ARG;
+  if ((q == nullptr) != (jac == nullptr) || (!jac && !dj_out)) return SR_ERR_ARG;
+  if (jac && (!par_slot || n_rays <= 0 || n_jac_rows <= 0)) return SR_ERR_ARG;
+  const int64_t n_gas64 = desc->n_gas, n_layers64 = desc->n_layers, n_par64 = odesc->n_par;
+  const bool too_large = n_gas64 > kDiffuseGases || n_layers64 > SR_MAX_ABS_ROWS || n_pts > kSolarMaxPts ||
+                         n_par64 * n_gas64 * n_layers64 > SR_MAX_SOLAR_VALUES;
+  double coef[3 * kDiffuseGases], w_out;
+  int rc = check_diffuse_desc(desc, !too_large, -1, coef, &w_out);
   if (rc) return rc;
-  static thread_local StagerRing ring;
-  StagePack pk(ring.take());
-  const auto p_v = pk.copy(desc->v, (size_t)n_gas * n_layers), p_c = pk.copy(coef, (size_t)3 * kDiffuseGases);
-  const auto p_dv = pk.copy(jdesc->dv, (size_t)n_par * n_gas * n_layers);
-  const auto p_m = pk.copy(mask.data(), mask.size());
-  const auto p_slot = pk.copy(par_slot, jac ? (size_t)n_par : 0, 1);
-  rc = pk.stage(st);
-  if (rc) return rc;
-  double *sweep = ws.as<double>();
-  double *dj_room = sweep + (size_t)tiles * (3 + 4 * kDiffuseJacPars) * n_layers * chunk; // (used with dj_ws only)
-  for (int64_t p_lo = 0; p_lo < n_pts; p_lo += chunk) {
-    const int p_hi = (int)std::min<int64_t>(n_pts, p_lo + chunk);
-    for (int t0 = 0; t0 < n_tiles; t0 += tiles) {
-      const int par_lo = t0 * kDiffuseJacPars, par_hi = std::min(n_par, (t0 + tiles) * kDiffuseJacPars);
-      double *dj = dj_ws ? dj_room : dj_out;
-      const int dj_stride = dj_ws ? chunk : (int)n_pts, dj_joff = dj_ws ? (int)p_lo : 0, dj_par0 = dj_ws ? par_lo : 0;
-      LAUNCHCHK(launch_diffuse_tangent(tab_abs, n_gas, n_layers, (int)n_pts, (int)p_lo, p_hi, par_lo, par_hi, pk.dev(p_v),
-                                       pk.dev(p_dv), pk.dev(p_c), pk.dev(p_m), beam, sun, dlnbeam, desc->mu0, desc->surface_albedo,
-                                       sweep, chunk, dj, dj_stride, dj_joff, dj_par0, st));
-      if (jac)
-        LAUNCHCHK(launch_diffuse_contract(q, n_rays, n_layers, (int)n_pts, (int)p_lo, p_hi, par_lo, par_hi, dj, dj_stride, dj_joff,
-                                          dj_par0, pk.dev(p_slot), accumulate != 0, jac, n_jac_rows, st));
-    }
-  }
-  return pk.slot().mark(st);
+  std::vector<double> dopt;
+  std::vector<int> mask;
+  if (!too_large && !diffuse_optics_plan(desc->v, desc->ssa, desc->asym, odesc->dssa, odesc->dasym, odesc->dalb, odesc->n_par,
+                                         desc->n_gas, desc->n_layers, dopt, mask))
+    return SR_ERR_ARG;
+  if (too_large) return SR_ERR_LIMIT;
+  return diffuse_jacobian_run(desc, coef, odesc->n_par, mask, dopt.data(), true, tab_abs, beam, sun, dlnbeam, q, n_rays, n_pts,
+                              par_slot, jac, n_jac_rows, accumulate, dj_out, stream);
 }
 
 // ------------------------------------------------------------------------

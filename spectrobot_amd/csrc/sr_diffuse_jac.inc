@@ -15,8 +15,10 @@
 // Then   jac[ray][slot[p]][j] (+)= sum_l q[ray][l][j] dJ[p][l][j],   l ascending from 0.0, one product and one addition
 // per layer, the base added last (ACC).
 //
-// sr_diffuse_tangent_kernel<NP>: one thread per grid point, 256 points per block, a block takes a point block and a tile
-// of NP parameters (limb_block deals them; the tiles of a point block follow each other on one XCD and read the same rows).
+// sr_diffuse_tangent_kernel<NP, OPT> (OPT, a direction in ssa, asym and the surface albedo where the text below says dv:
+// at the kernel; tools/diffuse_optics_host is its host build): one thread per grid point, 256 points per block, a block
+// takes a point block and a tile of NP parameters (limb_block deals them; the tiles of a point block follow each other on
+// one XCD and read the same rows).
 // The base quantities of a layer are made once per block (diffuse_layer, unchanged) and held in registers; per parameter
 // of the tile the layer's operator tangents come from
 //   outside the parameter's layer range [mask[2 p], mask[2 p + 1]): d t_g = 0 for every gas, so dR = dT = d(1 - R) =
@@ -124,7 +126,12 @@ __device__ __forceinline__ DiffuseTan diffuse_layer_tangent(double sp, double al
   return t;
 }
 
-template <int NP>
+// OPT false: a direction in the columns, dv [n_par][n_gas][n_layers].  OPT true: a direction in the optics (DESIGN.md
+// 4.11d) -- in dv's place dopt [n_par][kDiffuseOpt]: the per-gas coefficients' tangents [3][kDiffuseGases] (d(ssa (1 - f)),
+// d(1 - ssa), d(ssa (asym - f)), zeros beyond n_gas) and then the albedo's, block-uniform (scalar loads); inside a
+// parameter's layer range the three sums move with the coefficients' tangents on the products t_g = v a that diffuse_sums
+// forms, and the boundary starts with dRb_0 = dalb, dUb_0 = Ub_0 dlnbeam + dalb max(mu0, 0) sun beam[N].
+template <int NP, bool OPT = false>
 __global__ __launch_bounds__(256) void sr_diffuse_tangent_kernel(const double *__restrict__ tab_abs, int n_gas, int n_layers, int n_pts,
                                                                  int p_lo, int p_hi, int par_lo, int par_hi,
                                                                  const double *__restrict__ v, const double *__restrict__ dv,
@@ -158,6 +165,11 @@ __global__ __launch_bounds__(256) void sr_diffuse_tangent_kernel(const double *_
   for (int i = 0; i < NP; ++i) {
     dRb[i] = 0.0;
     dUb[i] = dlnbeam ? Ub * dlnbeam[(size_t)par[i] * brow + (size_t)n_layers * np + jj] : 0.0;
+    if (OPT) { // the albedo's direction: Rb_0 = albedo, Ub_0 = albedo max(mu0, 0) sun beam[N] (diffuse_boundary)
+      const double dalb = dv[(size_t)par[i] * kDiffuseOpt + 3 * kDiffuseGases];
+      dRb[i] = dalb;
+      dUb[i] += dalb * (fmax(mu0, 0.0) * (sj * beam[(size_t)n_layers * np + jj]));
+    }
   }
   for (int l = 0; l < n_layers; ++l) {
     double a[kDiffuseGases];
@@ -166,6 +178,11 @@ __global__ __launch_bounds__(256) void sr_diffuse_tangent_kernel(const double *_
     const double bm = beam[(size_t)l * np + jj];
     const DiffuseSums s = diffuse_sums(v, coef, n_gas, n_layers, l, a);
     const double sp = s.sp, al = s.al, sg = s.sg;
+    double tg[kDiffuseGases]; // (OPT) diffuse_sums' own products
+    if (OPT) {
+#pragma unroll
+      for (int g = 0; g < kDiffuseGases; ++g) tg[g] = v[(g < n_gas ? g : 0) * n_layers + l] * a[g];
+    }
     const double D = sj * bm;
     const DiffuseLayer o = diffuse_layer(sp, al, sg, D, mu0);
     const double den = Cb + Rb * o.oneR;
@@ -182,14 +199,24 @@ __global__ __launch_bounds__(256) void sr_diffuse_tangent_kernel(const double *_
       const double dlb = dlnbeam ? dlnbeam[(size_t)par[i] * brow + (size_t)l * np + jj] : 0.0;
       DiffuseTan t;
       if (l >= m_lo[i] && l < m_hi[i]) { // (block-uniform) inside the parameter's layers: the closed forms' tangent
-        const double *dvp = dv + (size_t)par[i] * n_gas * n_layers;
         double dsp = 0.0, dal = 0.0, dsg = 0.0;
+        if (OPT) {
+          const double *dc = dv + (size_t)par[i] * kDiffuseOpt;
 #pragma unroll
-        for (int g = 0; g < kDiffuseGases; ++g) {
-          const double dt = (g < n_gas ? dvp[g * n_layers + l] : 0.0) * a[g];
-          dsp += cs[g] * dt;
-          dal += ca[g] * dt;
-          dsg += cg[g] * dt;
+          for (int g = 0; g < kDiffuseGases; ++g) {
+            dsp += dc[g] * tg[g];
+            dal += dc[kDiffuseGases + g] * tg[g];
+            dsg += dc[2 * kDiffuseGases + g] * tg[g];
+          }
+        } else {
+          const double *dvp = dv + (size_t)par[i] * n_gas * n_layers;
+#pragma unroll
+          for (int g = 0; g < kDiffuseGases; ++g) {
+            const double dt = (g < n_gas ? dvp[g * n_layers + l] : 0.0) * a[g];
+            dsp += cs[g] * dt;
+            dal += ca[g] * dt;
+            dsg += cg[g] * dt;
+          }
         }
         t = diffuse_layer_tangent(sp, al, sg, D, mu0, dsp, dal, dsg, D * dlb);
       } else { // outside: the operators stand still, the sources follow the beam

@@ -521,6 +521,12 @@ int launch_diffuse_tangent(const double *tab_abs, int n_gas, int n_layers, int n
                            const double *v, const double *dv, const double *coef, const int *mask, const double *beam,
                            const double *sun, const double *dlnbeam, double mu0, double albedo, double *ws, int ws_stride,
                            double *dj, int dj_stride, int dj_joff, int dj_par0, hipStream_t st);
+// the same along a direction in the optics: dopt [n_par][kDiffuseOpt] in dv's place, it and mask from diffuse_optics_plan
+// (sr_solar_plan.hpp); workspace and dJ as above, the contraction is launch_diffuse_contract
+int launch_diffuse_optics_tangent(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, int par_lo,
+                                  int par_hi, const double *v, const double *dopt, const double *coef, const int *mask,
+                                  const double *beam, const double *sun, const double *dlnbeam, double mu0, double albedo,
+                                  double *ws, int ws_stride, double *dj, int dj_stride, int dj_joff, int dj_par0, hipStream_t st);
 int launch_diffuse_contract(const double *q, int n_rays, int n_layers, int n_pts, int p_lo, int p_hi, int par_lo, int par_hi,
                             const double *dj, int dj_stride, int dj_joff, int dj_par0, const int *par_slot, bool accumulate,
                             double *jac, int n_jac_rows, hipStream_t st);

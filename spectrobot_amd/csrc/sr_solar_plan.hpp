@@ -15,6 +15,7 @@ constexpr int kSolarChunk = 4; // k per chunk: the MFMA's K
 constexpr int kSolarJacRays = 8; // NR: rays per block of sr_solar_jac_kernel (profiles/solar_jac_kernel_resources.txt)
 constexpr int kDiffuseGases = 8; // gas slots of sr_diffuse_source_kernel's loop (sr_diffuse_source.inc): n_gas above is refused
 constexpr int kDiffuseJacPars = 4; // NP: parameters per block of sr_diffuse_tangent_kernel and per thread of the contraction
+constexpr int kDiffuseOpt = 3 * kDiffuseGases + 1; // doubles per parameter of an optics direction: the coefficients' tangents, the albedo's
 constexpr int kDiffuseJacRays = 8; // NR: rays per thread of sr_diffuse_contract_kernel (profiles/diffuse_jacobian_kernel_resources.txt)
 
 // The one walk behind both plans: x [n_groups][n_rows][n_k], per (group, row tile) the chunks in which a row of the tile
@@ -95,6 +96,47 @@ inline bool diffuse_jac_masks(const double *v, const double *dv, int n_par, int 
           hi = l + 1 > hi ? l + 1 : hi;
         }
       }
+    }
+    if (hi > lo) mask[(size_t)2 * p] = lo, mask[(size_t)2 * p + 1] = hi;
+  }
+  return ok;
+}
+
+// The plan of sr_diffuse_tangent_kernel's optics instance (sr_diffuse_jac.inc; tools/diffuse_optics_host): per parameter
+// dopt [n_par][kDiffuseOpt] -- the tangents of the per-gas coefficients as built, [3][kDiffuseGases] (zeros beyond n_gas),
+// along dssa and dasym [n_par][n_gas], with f = max(asym, 0)^2, df = 2 max(asym, 0) dasym:
+//   d(ssa (1 - f)) = dssa (1 - f) - ssa df,  d(1 - ssa) = -dssa,  d(ssa (asym - f)) = dssa (asym - f) + ssa (dasym - df)
+// and then dalb[p] -- and the layer range mask[2 p] .. mask[2 p + 1] - 1 that holds every layer in which a gas with a
+// non-zero coefficient tangent has a column (lo = hi = 0: none -- a direction in the albedo alone).  dssa, dasym and dalb
+// may each be null: zeros.  Returns false if an element of them, or a tangent made of them, is not finite.
+inline bool diffuse_optics_plan(const double *v, const double *ssa, const double *asym, const double *dssa, const double *dasym,
+                                const double *dalb, int n_par, int n_gas, int n_layers, std::vector<double> &dopt,
+                                std::vector<int> &mask) {
+  dopt.assign((size_t)n_par * kDiffuseOpt, 0.0);
+  mask.assign((size_t)2 * n_par, 0);
+  bool ok = true;
+  for (int p = 0; p < n_par; ++p) {
+    double *dc = dopt.data() + (size_t)p * kDiffuseOpt;
+    int lo = n_layers, hi = 0;
+    const double db = dalb ? dalb[p] : 0.0;
+    ok &= (db >= -1.7976931348623157e308) & (db <= 1.7976931348623157e308);
+    dc[3 * kDiffuseGases] = db;
+    for (int g = 0; g < n_gas; ++g) {
+      const double ds = dssa ? dssa[(size_t)p * n_gas + g] : 0.0, da = dasym ? dasym[(size_t)p * n_gas + g] : 0.0;
+      ok &= (ds >= -1.7976931348623157e308) & (ds <= 1.7976931348623157e308) & (da >= -1.7976931348623157e308) &
+            (da <= 1.7976931348623157e308); // (a NaN fails both)
+      const double as = asym[g], f = as > 0.0 ? as * as : 0.0, df = as > 0.0 ? 2.0 * as * da : 0.0;
+      dc[g] = ds * (1.0 - f) - ssa[g] * df;
+      dc[kDiffuseGases + g] = -ds;
+      dc[2 * kDiffuseGases + g] = ds * (as - f) + ssa[g] * (da - df);
+      for (int c = 0; c < 3; ++c) // (a direction so large that a coefficient's tangent overflows is refused too)
+        ok &= (dc[c * kDiffuseGases + g] >= -1.7976931348623157e308) & (dc[c * kDiffuseGases + g] <= 1.7976931348623157e308);
+      if (dc[g] == 0.0 && dc[kDiffuseGases + g] == 0.0 && dc[2 * kDiffuseGases + g] == 0.0) continue;
+      for (int l = 0; l < n_layers; ++l)
+        if (v[(size_t)g * n_layers + l] != 0.0) {
+          lo = l < lo ? l : lo;
+          hi = l + 1 > hi ? l + 1 : hi;
+        }
     }
     if (hi > lo) mask[(size_t)2 * p] = lo, mask[(size_t)2 * p + 1] = hi;
   }

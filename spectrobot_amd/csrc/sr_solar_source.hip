@@ -8,7 +8,8 @@
 //   sr_solar_source_kernel<ACC, TRANS>   four instances: overwrite / accumulate, with and without the transmission
 //   sr_solar_jac_kernel<NR, ACC>         two instances: overwrite / accumulate, NR = kSolarJacRays rays per block
 //   sr_diffuse_source_kernel<ACC, WJ, WF> eight instances: overwrite / accumulate, with and without j_out / flux_out
-//   sr_diffuse_tangent_kernel<NP>         one instance: NP = kDiffuseJacPars parameters per block
+//   sr_diffuse_tangent_kernel<NP, OPT>    two instances: NP = kDiffuseJacPars parameters per block; along column parameters,
+//                                         and (OPT) along a direction in ssa, asym and the surface albedo
 //   sr_diffuse_contract_kernel<NR, NP, ACC> two instances: overwrite / accumulate, kDiffuseJacRays x kDiffuseJacPars per thread
 #include "sr_device.hpp"
 #include "sr_kernels.hpp"
@@ -75,6 +76,18 @@ int launch_diffuse_tangent(const double *tab_abs, int n_gas, int n_layers, int n
   const dim3 grid(limb_grid((p_hi - p_lo + 255) / 256, (par_hi - par_lo + kDiffuseJacPars - 1) / kDiffuseJacPars));
   hipLaunchKernelGGL((sr_diffuse_tangent_kernel<kDiffuseJacPars>), grid, dim3(256), 0, st, tab_abs, n_gas, n_layers, n_pts, p_lo,
                      p_hi, par_lo, par_hi, v, dv, coef, mask, beam, sun, dlnbeam, mu0, albedo, ws, ws_stride, dj, dj_stride, dj_joff,
+                     dj_par0);
+  return (int)hipGetLastError();
+}
+
+int launch_diffuse_optics_tangent(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, int par_lo,
+                                  int par_hi, const double *v, const double *dopt, const double *coef, const int *mask,
+                                  const double *beam, const double *sun, const double *dlnbeam, double mu0, double albedo,
+                                  double *ws, int ws_stride, double *dj, int dj_stride, int dj_joff, int dj_par0, hipStream_t st) {
+  if (n_layers <= 0 || p_hi <= p_lo || par_hi <= par_lo) return 0;
+  const dim3 grid(limb_grid((p_hi - p_lo + 255) / 256, (par_hi - par_lo + kDiffuseJacPars - 1) / kDiffuseJacPars));
+  hipLaunchKernelGGL((sr_diffuse_tangent_kernel<kDiffuseJacPars, true>), grid, dim3(256), 0, st, tab_abs, n_gas, n_layers, n_pts, p_lo,
+                     p_hi, par_lo, par_hi, v, dopt, coef, mask, beam, sun, dlnbeam, mu0, albedo, ws, ws_stride, dj, dj_stride, dj_joff,
                      dj_par0);
   return (int)hipGetLastError();
 }

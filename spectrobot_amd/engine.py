@@ -840,6 +840,65 @@ def diffuse_jacobian(A, V, ssa, asym, beam, sun, mu0, dV, dlnbeam, Q, surface_al
     return res[0] if len(res) == 1 else res
 
 
+def diffuse_optics_jacobian(A, V, ssa, asym, beam, sun, mu0, dssa, dasym, dalbedo, dlnbeam, Q, surface_albedo=0.0, out=None,
+                            par_slot=None, accumulate=False, tangent=False):
+    """The diffuse rows along a direction in the haze optics (sr_diffuse_optics_jacobian_rows_dev; the build's own
+    definition): the derivative of limb radiances to ssa, asym and the surface albedo through
+    diffuse_source's two-stream solve,
+
+        dJ[p, l] = the tangent of J[l] along d ssa_g = dssa[p, g], d asym_g = dasym[p, g], d surface_albedo = dalbedo[p],
+                   d ln D_l = dlnbeam[p, l], d ln Ub_0 = dlnbeam[p, n_layers] (the beam's part of the boundary term)
+        jac[ray, par_slot[p]] (+)= sum_l Q[ray, l] dJ[p, l]
+
+    of the function as built (diffuse_jacobian's three rules; f = max(asym, 0)^2 has derivative 0 for asym <= 0).  A, V,
+    ssa, asym, beam, sun, mu0, surface_albedo: the state, as diffuse_source takes it.  dssa, dasym: host [n_par, n_gas],
+    dalbedo: host [n_par]; any finite sign; any of the three may be None (zeros), not all.  dlnbeam, Q, out, par_slot,
+    accumulate, tangent: as diffuse_jacobian takes them.  No division by the albedo: 0 is an ordinary state.  Two fp64
+    kernels, one writer per element; the same call gives the same bits.  Returns out, (out, dJ), or dJ (Q None)."""
+    # (what needs no tensor is refused first, then the state is looked at)
+    given = [np.asarray(x, dtype=np.float64) for x in (dssa, dasym, dalbedo) if x is not None]
+    if not given:
+        raise ValueError("nothing to differentiate along: dssa=, dasym= or dalbedo=")
+    dims = [np.ndim(x) for x in (dssa, dasym) if x is not None] + ([np.ndim(dalbedo) + 1] if dalbedo is not None else [])
+    if any(k != 2 for k in dims) or len({int(x.shape[0]) for x in given}) != 1 or given[0].shape[0] == 0:
+        raise ValueError("dssa and dasym must be [n_par, n_gas] and dalbedo [n_par], one n_par >= 1 for all")
+    n_par = int(given[0].shape[0])
+    if Q is None and not tangent:
+        raise ValueError("nothing asked for: Q=... or tangent=True")
+    if Q is None and (out is not None or par_slot is not None or accumulate):
+        raise ValueError("out=, par_slot= and accumulate= belong to the product with Q=")
+    d, (n_gas, n_layers, n_pts), keep = _diffuse_state(A, V, ssa, asym, beam, sun, mu0, surface_albedo)
+    od = _lib.DiffuseOpticsDesc()
+    od.n_par = n_par
+    held = []
+    for name, x, shape in (("dssa", dssa, (n_par, n_gas)), ("dasym", dasym, (n_par, n_gas)), ("dalb", dalbedo, (n_par,))):
+        if x is None:
+            continue
+        xa, xp = _d(np.asarray(x, dtype=np.float64))
+        if xa.shape != shape:
+            raise ValueError("dssa and dasym must be [n_par, n_gas] = [%d, %d] and dalbedo [%d]" % (n_par, n_gas, n_par))
+        held.append(xa)
+        setattr(od, name, xp)
+    if dlnbeam is not None and (not _cuda_f64(dlnbeam) or dlnbeam.shape != (n_par, n_layers + 1, n_pts)):
+        raise ValueError("dlnbeam must be a contiguous CUDA float64 [n_par, n_layers + 1, n_pts] or None")
+    slot_p = None
+    if Q is None:
+        n_rays = 0
+    else:
+        if not _cuda_f64(Q) or Q.dim() != 3 or Q.shape[0] == 0 or Q.shape[1] != n_layers or Q.shape[2] != n_pts:
+            raise ValueError("Q must be a contiguous CUDA float64 [n_rays, %d, %d]: A's layers and grid points" % (n_layers, n_pts))
+        n_rays = int(Q.shape[0])
+        out, slot, slot_p = _jac_target(out, par_slot, accumulate, n_rays, n_par, n_pts)
+    dJ = torch.empty((n_par, n_layers, n_pts), dtype=torch.float64, device="cuda") if tangent else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    check(lib.sr_diffuse_optics_jacobian_rows_dev(C.byref(d), C.byref(od), ptr(A), ptr(beam), ptr(sun), ptr(dlnbeam), ptr(Q), n_rays,
+                                                  n_pts, slot_p, ptr(out), int(out.shape[1]) if out is not None else 0,
+                                                  int(bool(accumulate)), ptr(dJ), _stream_ptr()),
+          "sr_diffuse_optics_jacobian_rows_dev")
+    res = tuple(t for t in (out, dJ) if t is not None)
+    return res[0] if len(res) == 1 else res
+
+
 def lut_interp(table, idx4, wgt4, pops=None, out=None):
     """LutSet.calculate for n_steps LOS steps on a G table resident in HBM (sr_lut_interp_dev).
     table: CUDA [3, n_PT, n_grid]; idx4 [n_steps, 4] rows, wgt4 [n_steps, 4] = (wP1, wP2, wT1, wT2).

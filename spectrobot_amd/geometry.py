@@ -556,6 +556,17 @@ def hg_phase(cos_theta, g):
     return (1.0 - g * g) / (1.0 + g * g - 2.0 * g * c) ** 1.5
 
 
+def hg_phase_dg(cos_theta, g):
+    """d hg_phase / d g, analytic: with D = 1 + g^2 - 2 g cos Theta, -(2 g D + 3 (1 - g^2)(g - cos Theta)) / D^(5/2) -- what
+    the order-one rows need for a direction in the asymmetry parameter; its mean over the sphere is 0."""
+    g = float(g)
+    if not abs(g) < 1.0:
+        raise ValueError("the asymmetry parameter must lie in (-1, 1)")
+    c = np.asarray(cos_theta, float)
+    D = 1.0 + g * g - 2.0 * g * c
+    return -(2.0 * g * D + 3.0 * (1.0 - g * g) * (g - c)) / D ** 2.5
+
+
 def solar_irradiance(grid, t_sun=5772.0, r_sun_km=695700.0, dist_km=9.58 * 1.495978707e8):
     """The irradiance of a black-body sun on the grid (cm^-1) at the planet: pi B(nu, t_sun) (r_sun / dist)^2, with the
     Planck function of the limb calls' initial intensity, B = 2 h c^2 nu^3 / (exp(c2 nu / T) - 1) in erg s^-1 cm^-2 sr^-1

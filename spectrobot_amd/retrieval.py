@@ -340,8 +340,60 @@ class Pointing(smm.RetSet):
         return float(self.set[0].value)
 
 
+OPTICS_SET = "optics"
+
+
+class HazeOptics(smm.RetSet):
+    """The retrieval set of a sunlit haze's optics, named "optics": scalar parameters only -- the single-scattering albedo
+    and the asymmetry parameter of solar gases (TableGas(solar=dict(albedo=, g=))) and the surface albedo of a
+    Sun(multiple=True).  albedo={gas: spec}, g={gas: spec}, surface_albedo=spec, each spec (apriori, apriori_err) or
+    (apriori, apriori_err, first_guess); none is constrained positive by the algebra.  After every update the values are
+    projected into the library's domain (project(), called where the state goes into the scene): albedo into the CLOSED
+    interval [0, 1], surface_albedo into the CLOSED [0, 1], g into [-0.5, 1) -- closed at -0.5, OPEN at 1, where the
+    projection stops at 1 - 2^-20.  The Jacobian columns are LimbScene.optics_jacobian's, the full derivative of the
+    radiances at the current state.  In thin single scattering ssa x extinction is one number: a state with both a
+    haze's profile and its albedo is degenerate.  Retrieved by inversion_state; the other drivers refuse the set."""
+    G_MAX = 1.0 - 2.0 ** -20
+
+    def __init__(self, albedo=None, g=None, surface_albedo=None):
+        mask = smm.GridMask([0.0], [1.0], 'box')    # (scalars: nothing to mask)
+        self.name, self.set, self.keys = OPTICS_SET, [], []
+        specs = [(("albedo", gas), s) for gas, s in (albedo or {}).items()] + [(("g", gas), s) for gas, s in (g or {}).items()]
+        if surface_albedo is not None:
+            specs.append((("surface_albedo", None), surface_albedo))
+        if not specs:
+            raise ValueError("HazeOptics needs at least one of albedo={gas: spec}, g={gas: spec}, surface_albedo=spec")
+        for key, spec in specs:
+            spec = tuple(float(v) for v in spec)
+            if len(spec) not in (2, 3):
+                raise ValueError("a spec is (apriori, apriori_err) or (apriori, apriori_err, first_guess)")
+            lo, hi = self.domain(key[0])
+            if not (lo <= spec[0] <= hi and lo <= spec[-1] <= hi) or not spec[1] > 0.0:
+                raise ValueError("%s: a priori and first guess lie in [%g, %g], the error is positive" % (key[0], lo, hi))
+            label = key[0] if key[1] is None else "%s:%s" % key
+            self.set.append(smm.RetParam(OPTICS_SET, label, mask, spec[0], spec[1], first_guess=spec[2] if len(spec) == 3 else None,
+                                         constrain_positive=False))
+            self.keys.append(key)
+        self.n_par = len(self.set)
+
+    @classmethod
+    def domain(cls, kind):
+        return (-0.5, cls.G_MAX) if kind == "g" else (0.0, 1.0)
+
+    def project(self):
+        """The values into the library's domain (the class docstring says which ends are closed)."""
+        for key, par in zip(self.keys, self.set):
+            lo, hi = self.domain(key[0])
+            par.value = float(min(max(float(par.value), lo), hi))
+
+    def values(self):
+        return [float(par.value) for par in self.set]
+
+
 def _refuse_instr(bayes_set, who):
     sets = getattr(bayes_set, "sets", {}) if bayes_set is not None else {}
+    if OPTICS_SET in sets:
+        raise ValueError("%s does not take the retrieval set %r (HazeOptics): use inversion_state" % (who, OPTICS_SET))
     if INSTR_SET in sets:
         raise ValueError("%s does not take the retrieval set %r (BandCalibration): use inversion_state" % (who, INSTR_SET))
     if POINTING_SET in sets:
@@ -404,6 +456,9 @@ class LimbScene(object):
                                     # still gets its solar rows again)
         self.keep_solar_rows = False  # True: the solar pass keeps every solar gas's solar rows alone (g.solar_rows), what
                                       # solar_attenuation_jacobian works on (inversion_state(solar_attenuation=True) sets it)
+        self.keep_mean_intensity = False  # True: the diffuse pass also keeps its mean intensity J (self.diffuse_J), from the call it
+                                          # makes anyway (optics_jacobian's direct part; inversion_state sets it for an "optics" set)
+        self.diffuse_J = None
         self.keep_diffuse_state = False  # True: the diffuse pass keeps its inputs (self.diffuse_state), what diffuse_jacobian
                                          # differentiates (inversion_state(diffuse_jacobian=True) sets it)
         self.diffuse_state = None
@@ -450,8 +505,9 @@ class LimbScene(object):
         gas's absorption table -- temperatures, pressures and vibrational temperatures act through them --, the sun and
         the shard.  A VMR retrieval moves the first and redoes the solar pass each iteration, and nothing else."""
         tabs = tuple(id((g.thermal if getattr(g, "solar", None) is not None else g.coeffs)[0]) for g in self.gases)
+        optics = tuple((float(g.solar["albedo"]), float(g.solar["g"])) for g in self.solar_gases())    # (a HazeOptics set moves them)
         return (tuple(np.asarray(g.vmr, float).tobytes() for g in self.gases), tuple(float(g.iso_ratio) for g in self.gases),
-                tabs, self.sun.key(), int(g_lo), int(g_hi))
+                tabs, self.sun.key(), int(g_lo), int(g_hi), optics)
 
     def solar_weights(self, g, lit):
         """w [n_layers] = albedo P(Theta) / 4 pi of a solar gas, 0 on the rows in shadow."""
@@ -536,10 +592,14 @@ class LimbScene(object):
         if self.keep_diffuse_state:
             self.diffuse_state = (A, V, ssa, asym, beam, sun)
         if len(solar) == 1:
-            engine.diffuse_source(A, V, ssa, asym, beam, sun, self.sun.mu, out_gas=self.gases.index(solar[0]),
-                                  out=solar[0].coeffs[1], accumulate=True, **kw)
+            if self.keep_mean_intensity:    # (the same kernel with one more store: the rows keep their bits)
+                kw["mean_intensity"] = True
+            res = engine.diffuse_source(A, V, ssa, asym, beam, sun, self.sun.mu, out_gas=self.gases.index(solar[0]),
+                                        out=solar[0].coeffs[1], accumulate=True, **kw)
+            self.diffuse_J = res[1] if self.keep_mean_intensity else None
             return
         J = engine.diffuse_source(A, V, ssa, asym, beam, sun, self.sun.mu, mean_intensity=True, **kw)
+        self.diffuse_J = J if self.keep_mean_intensity else None
         for g in solar:
             i = self.gases.index(g)
             g.coeffs[1].addcmul_(A[i], J, value=float(ssa[i] * (1.0 - max(asym[i], 0.0) ** 2)))
@@ -605,6 +665,90 @@ class LimbScene(object):
         Q = self._emission_rows_jacobian(coeffs, W, los)
         return self._into_jac(engine.diffuse_jacobian, (A, V, ssa, asym, beam, sun, self.sun.mu, dV, dlnbeam, Q), jac, n_col,
                               surface_albedo=self.sun.surface_albedo)
+
+    def optics_jacobian(self, los, alt, params, coeffs):
+        """[n_rays, n_opt, n_pts]: the complete derivative of the radiances to the optics parameters `params` (HazeOptics.keys:
+        ("albedo", gas), ("g", gas), ("surface_albedo", None)) at the current state, the sum of three parts.
+        Direct: the emission rows' own coefficients move with J and the beam held -- per parameter the order-one rows with
+        d w in place of w (ONE engine.solar_source call: no division by w, rows in shadow stay exact zeros), plus
+        d(ssa (1 - f)) A[g] J of the diffuse rows (keep_mean_intensity: J from the diffuse pass's own call), pushed
+        through one _emission_rows_jacobian call and summed over the layers.  Beam: d ln beam = -(dUb . A), dUb the
+        delta-scaled beam's columns scaled, after solar_columns (the sign is negative), by d(1 - ssa f) / d x of the
+        parameter's gas; one torch.matmul.  Two-stream: ONE engine.diffuse_optics_jacobian call with diffuse_jacobian's Q.
+        With Sun(multiple=False) only the direct part exists and a surface_albedo parameter is refused.  `alt` is not
+        needed.  limb_rays_layer_jacobian is a four-gas call."""
+        import torch
+        solar = self.solar_gases()
+        multiple = bool(getattr(self.sun, "multiple", False))
+        params = list(params)
+        if not solar or not params:
+            raise ValueError("optics_jacobian needs a sun, a solar gas and at least one parameter")
+        for kind, gas in params:
+            if kind == "surface_albedo":
+                if not multiple:
+                    raise ValueError("a surface_albedo parameter needs a Sun(multiple=True): single scattering does not see the ground")
+            elif kind not in ("albedo", "g") or gas not in [g.name for g in solar]:
+                raise ValueError("optics parameter %r: albedo or g of a solar gas, or surface_albedo" % ((kind, gas),))
+        if multiple and (self.diffuse_state is None or self.diffuse_J is None):
+            raise ValueError("optics_jacobian needs keep_diffuse_state = keep_mean_intensity = True before the solar pass")
+        n_gas, n_opt = len(self.gases), len(params)
+        ssa, asym, iso, pts, _ = self.diffuse_geometry(solar)
+        pos = np.maximum(asym, 0.0)
+        f = pos ** 2
+        dssa, dasym, dalb = np.zeros((n_opt, n_gas)), np.zeros((n_opt, n_gas)), np.zeros(n_opt)
+        for p, (kind, gas) in enumerate(params):
+            if kind == "surface_albedo":
+                dalb[p] = 1.0
+            else:
+                (dssa if kind == "albedo" else dasym)[p, self.gases.index(self.gas(gas))] = 1.0
+        dcs = dssa * (1.0 - f) - ssa * 2.0 * pos * dasym                       # d(ssa (1 - f)) [n_opt, n_gas]
+        a, _ = engine.gas_stack(coeffs)
+        n_layers, n_pts = int(a.shape[1]), int(a.shape[2])
+        sun = torch.as_tensor(self.sun.irradiance[self._solar_key[4]:self._solar_key[5]], device="cuda").contiguous()
+        tabs = torch.stack([(g.thermal if g in solar else g.coeffs)[0] for g in self.gases]).contiguous()
+        U, lit = geometry.solar_columns(self.z, self.nd, [g.vmr for g in self.gases], self.shell_midpoints(), self.sun.mu, R=self.R,
+                                        n_sub=self.n_sub, col_scale=[g.iso_ratio for g in self.gases])
+        P = {g.name: (geometry.hg_phase(self.sun.cos_scattering, g.solar["g"]), geometry.hg_phase_dg(self.sun.cos_scattering, g.solar["g"]))
+             for g in solar}
+        direct = []
+        for p, (kind, gas) in enumerate(params):
+            if kind == "surface_albedo":
+                direct.append(None)
+                continue
+            g = self.gas(gas)
+            i = self.gases.index(g)
+            dw = P[gas][0] if kind == "albedo" else g.solar["albedo"] * P[gas][1]
+            demi = torch.zeros_like(a)
+            # (the entry takes weights >= 0 and d P / d g has either sign: the rows are linear in the one weight, so its
+            # magnitude goes in and its sign onto the rows)
+            demi[i] = engine.solar_source(tabs, U, np.where(lit, abs(dw) / (4.0 * np.pi), 0.0), g.thermal[0], sun)
+            if dw < 0.0:
+                demi[i].neg_()
+            if multiple and dcs[p, i] != 0.0:
+                demi[i].addcmul_(tabs[i], self.diffuse_J, value=float(dcs[p, i]))
+            direct.append(self._emission_rows_jacobian(coeffs, demi, los).sum(dim=1))
+        n_rays = next(d.shape[0] for d in direct if d is not None) if any(d is not None for d in direct) else None
+        if multiple:
+            A, V, ssa_s, asym_s, beam, sun_s = self.diffuse_state
+            Ub, litb = geometry.solar_columns(self.z, self.nd, [g.vmr for g in self.gases], pts, self.sun.mu, R=self.R, n_sub=self.n_sub,
+                                              col_scale=iso)
+            dscale = -(dssa * f + ssa * 2.0 * pos * dasym)                     # d(1 - ssa f) / d x_p [n_opt, n_gas]
+            dUb = dscale[:, None, :, None] * (Ub * np.asarray(litb, float)[:, None, None])[None]
+            dub = torch.as_tensor(np.ascontiguousarray(dUb.reshape(n_opt * (n_layers + 1), n_gas * n_layers)), device="cuda")
+            dlnbeam = torch.matmul(dub, A.reshape(n_gas * n_layers, n_pts)).neg_().reshape(n_opt, n_layers + 1, n_pts)
+            W = torch.zeros_like(A)
+            for g in solar:
+                i = self.gases.index(g)
+                W[i] = A[i] * float(ssa[i] * (1.0 - f[i]))
+            Q = self._emission_rows_jacobian(coeffs, W, los)
+            out = engine.diffuse_optics_jacobian(A, V, ssa_s, asym_s, beam, sun_s, self.sun.mu, dssa, dasym, dalb, dlnbeam, Q,
+                                                 surface_albedo=self.sun.surface_albedo)
+        else:
+            out = torch.zeros((n_rays, n_opt, n_pts), dtype=torch.float64, device="cuda")
+        for p, d in enumerate(direct):
+            if d is not None:
+                out[:, p] += d
+        return out
 
     @staticmethod
     def _emission_rows_jacobian(coeffs, demi, los):
@@ -723,7 +867,7 @@ class LimbScene(object):
         level_gas, level_gases, par_lgas = None, [], []
         for name in bayes_set.order:
             st = bayes_set.sets[name]
-            if name in (INSTR_SET, POINTING_SET) and name not in names:
+            if name in (INSTR_SET, POINTING_SET, OPTICS_SET) and name not in names:    # ("optics", HazeOptics, likewise)
                 continue
             if name in names:
                 for par in st.set:
@@ -1298,18 +1442,23 @@ def inversion_fast_limb(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10,
     return chi, obs, (finish(low, dlow) if fast else sims), bayes_set
 
 
-def _rows_in_bayes_order(fov_rows, n_prof, is_point, is_instr, instr, bands_nm0):
+def _rows_in_bayes_order(fov_rows, n_prof, is_point, is_instr, instr, bands_nm0, is_opt=None):
     """[n_pix, 1 + n_prof (+ 1) (+ 2), n_bands] -- the radiance, the profile parameters in BayesSet order, the pointing
     row if any BayesSet parameter is the pointing's, d / d centre and d / d ln width if any is the instrument's -> [n_pix,
     1 + n_tot, n_bands] with every set's columns where the set stands (is_point, is_instr [n_tot]: whose each parameter
     is); the "instr" set's by the chain rule (BandCalibration.jacobian_rows)."""
+    is_opt = np.zeros_like(is_instr) if is_opt is None else is_opt     # (the "optics" set's rows stand behind the pointing row)
     out = np.empty((fov_rows.shape[0], 1 + is_instr.size, fov_rows.shape[2]))
     out[:, 0] = fov_rows[:, 0]
-    out[:, 1:][:, ~(is_instr | is_point)] = fov_rows[:, 1:1 + n_prof]
+    out[:, 1:][:, ~(is_instr | is_point | is_opt)] = fov_rows[:, 1:1 + n_prof]
     at = 1 + n_prof
     if is_point.any():
         out[:, 1:][:, is_point] = fov_rows[:, at:at + 1]
         at += 1
+    if is_opt.any():
+        n_opt = int(is_opt.sum())
+        out[:, 1:][:, is_opt] = fov_rows[:, at:at + n_opt]
+        at += n_opt
     if is_instr.any():
         out[:, 1:][:, is_instr] = instr.jacobian_rows(bands_nm0, fov_rows[:, at], fov_rows[:, at + 1])
     return out
@@ -1319,7 +1468,8 @@ def _state_into_gases(scene, bayes_set):
     """The BayesSet's profiles into the gases: add_clim for the VMR sets, tvib = tvib0 + offset for the Tvib sets; the
     "temp" set into the scene, temps = temps0 + offset (temps0: the temperatures at the first such call; the number
     densities and the LOS columns stay as they are, see TempProfile); the "instr" set into the scene's bands,
-    bands_nm = bands_nm0 + shift + slope (bands_nm0 - mean), widths_nm = widths_nm0 exp(ln_width)."""
+    bands_nm = bands_nm0 + shift + slope (bands_nm0 - mean), widths_nm = widths_nm0 exp(ln_width); the "optics" set
+    (HazeOptics), projected into its domain first, into the solar gases' g.solar and scene.sun.surface_albedo."""
     names, tvib = [g.name for g in scene.gases], {}
     for name in bayes_set.order:
         st = bayes_set.sets[name]
@@ -1330,6 +1480,14 @@ def _state_into_gases(scene, bayes_set):
             scene.bands_nm, scene.widths_nm = st.bands(scene.bands_nm0, scene.widths_nm0)
             continue
         if name == POINTING_SET:      # (the driver adds the offset to its lines of sight)
+            continue
+        if name == OPTICS_SET:        # projected into the domain, then into g.solar and the sun (solar_key sees both)
+            st.project()
+            for (kind, gas), v in zip(st.keys, st.values()):
+                if kind == "surface_albedo":
+                    scene.sun.surface_albedo = v
+                else:
+                    scene.gas(gas).solar[kind] = v
             continue
         if name == "temp":
             if getattr(scene, "temps0", None) is None:
@@ -1406,7 +1564,13 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     keep_diffuse_state), added at the same two sites.  Independent of solar_attenuation: the full derivative of a sunlit
     multiple-scattering scene needs both flags.  The same four-gas Q pass, the same ValueError.  False, or a scene
     without such a sun: nothing changes.
-    The temperature, vibrational-temperature, pointing and instrument columns have no such term here."""
+    The temperature, vibrational-temperature, pointing and instrument columns have no such term here.
+    A set named "optics" (HazeOptics: albedo and g of solar gases, the surface albedo) is retrieved with them: per
+    iteration its projected values go into g.solar and scene.sun.surface_albedo (the solar pass is redone: solar_key sees
+    them), and its columns are LimbScene.optics_jacobian's rows -- always the full derivative, whatever the two flags say
+    -- added as hi-res rows before the band step or, with bands_in_kernel, as rows of their own through hires_to_lowres
+    and the closed-form field of view; they stand where the set stands in the BayesSet.  The same four-gas limit and
+    ValueError.  Without such a set no statement of an iteration changes."""
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)
     with_fov = _closed_form_fov(pixels, fov_closed_form, "inversion_state")
     solar_att = bool(solar_attenuation) and bool(scene.solar_gases())
@@ -1422,6 +1586,17 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
                              "(engine.limb_rays_layer_jacobian) is a four-gas call" % len(scene.gases))
         scene.keep_diffuse_state = True
         scene._solar_key = None     # (a solar pass made before the flag kept nothing: the next one is made again)
+    optics = bayes_set.sets.get(OPTICS_SET) if OPTICS_SET not in [g.name for g in scene.gases] else None
+    is_opt = np.array([optics is not None and par.nameset == OPTICS_SET for par in bayes_set.params()], dtype=bool)
+    if optics is not None:      # its columns are always the full derivative, whatever the two flags above say
+        if not scene.solar_gases():
+            raise ValueError("inversion_state: the retrieval set %r needs a scene with a sun and a solar gas" % OPTICS_SET)
+        if len(scene.gases) > engine.max_gases(folded=True):
+            raise ValueError("inversion_state with the retrieval set %r: a scene of %d gas slots; its Q pass "
+                             "(engine.limb_rays_layer_jacobian) is a four-gas call" % (OPTICS_SET, len(scene.gases)))
+        if getattr(scene.sun, "multiple", False):
+            scene.keep_diffuse_state = scene.keep_mean_intensity = True
+            scene._solar_key = None
     alts0 = [a for pix in pixels for a in pix.los_alts()]
     # the sets' names are checked before anything is changed
     with_temp = scene.state_weights(bayes_set, np.zeros(1), several_level_gases=True).par_w_temp.shape[0] > 0
@@ -1471,8 +1646,14 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             n_par = both.shape[1] - 1 - (0 if instr is None else 2) - (0 if point is None else 1)
             fov = both if with_fov else both[1::3]
             fov = np.concatenate([fov[:, :1, :], fov[:, 1:1 + n_par, :][:, w.perm], fov[:, 1 + n_par:, :]], axis=1)
+            if optics is not None:    # rows of their own through the band step and the field of view, as `extra` above
+                n_opt = optics.n_par
+                opt = lowres(scene.optics_jacobian(los, alt, optics.keys, coeffs).contiguous().view(n_los * n_opt, -1)).reshape(n_los, n_opt, -1)
+                opt = smm.fov_closed_form(opt[0::3], opt[1::3], opt[2::3], rots) if with_fov else opt[1::3]
+                at = 1 + n_par + (0 if point is None else 1)
+                fov = np.concatenate([fov[:, :at, :], opt, fov[:, at:, :]], axis=1)
         else:
-            if instr is not None and point is None and len(w.perm) == 0:    # the instrument set alone: the radiances, no Jacobian call
+            if (instr is not None or optics is not None) and point is None and len(w.perm) == 0:    # the instrument (or optics) set alone: the radiances, no state Jacobian call
                 rad, jac = engine.limb_rays(coeffs, los, resident=False), None
             else:
                 rad, jac = _state_call(scene, w, coeffs, dcoeffs, los, False, **point_kw)
@@ -1484,6 +1665,9 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
             n_par = n_rows - (0 if point is None else 1)               # (the pointing row stands behind the state's)
             order = np.concatenate([w.perm, np.arange(n_par, n_rows)]).astype(int)
             rows = [] if jac is None else [lowres(jac.contiguous().view(n_los * n_rows, -1)).reshape(n_los, n_rows, -1)[:, order]]
+            if optics is not None:    # added as hi-res rows before the band step, behind the pointing row
+                n_opt = optics.n_par
+                rows.append(lowres(scene.optics_jacobian(los, alt, optics.keys, coeffs).contiguous().view(n_los * n_opt, -1)).reshape(n_los, n_opt, -1))
             if instr is None:
                 both = np.concatenate([lowres(rad)[:, None, :]] + rows, axis=1)
             else:      # the instrument step once more on the radiance, with its two derivative rows (row 0: lowres(rad))
@@ -1491,8 +1675,8 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
                                                           ils=_ils(scene))
                 both = np.concatenate([three[0][:, None, :]] + rows + [three[1][:, None, :], three[2][:, None, :]], axis=1)
             fov = smm.fov_closed_form(both[0::3], both[1::3], both[2::3], rots) if with_fov else both[1::3]
-        if instr is not None or point is not None:
-            fov = _rows_in_bayes_order(fov, n_par, is_point, is_instr, instr, scene.bands_nm0)
+        if instr is not None or point is not None or optics is not None:
+            fov = _rows_in_bayes_order(fov, n_par, is_point, is_instr, instr, scene.bands_nm0, is_opt)
         return fov[:, 0, :], fov[:, 1:, :]
 
     chi, low, dlow = _array_loop(ob, forward, lambda: _state_into_gases(scene, bayes_set), chi_threshold, max_it, lambda_LM, L1_reg)
