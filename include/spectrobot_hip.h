@@ -1052,6 +1052,49 @@ int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_ab
                                int64_t n_pts, int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out,
                                void *stream);
 
+/* The diffuse field for several columns of illumination over one atmosphere, and the emission rows of LOS steps that
+ * see it: a 3-D limb batch, whose steps each have their own solar zenith angle.  The build's own definition (DESIGN.md
+ * 4.11e).  For column c < n_col, with mu0[c] and beam[c] [n_layers + 1][n_pts], J[c][l][j] and F+-[c][i][j] are exactly
+ * what sr_diffuse_source_rows_dev defines for (desc's v, ssa, asym, surface_albedo; mu0[c], beam[c]): the atmosphere and
+ * its optics are shared, only the illumination differs, and the columns are independent.  Then for output row r < n_rows
+ *   emi_out[r][j] (+)= ssa_G (1 - f_G) sca_abs[src_row[r]][j] sum_c col_w[r][c] J[c][row_layer[r]][j]      G = out_gas
+ * c ascending, the sum started from its first term; every addend is >= 0.  A row whose weights are all zero is an exact
+ * 0, and under accumulate its row of emi_out keeps its bits; the same holds for every row when ssa_G == 0.
+ * desc: as sr_diffuse_source_rows_dev takes it; its mu0 is not read.  cols: mu0 HOST [n_col], each in [-1, 1]; col_w HOST
+ * [n_rows][n_col], finite and >= 0 (e.g. linear interpolation in mu between the columns); row_layer HOST [n_rows], the
+ * layer 0 .. n_layers - 1 of every row, in any order, a layer any number of times; src_row HOST [n_rows], 0 .. n_src - 1.
+ * tab_abs and sun as the sibling takes them; beam DEVICE [n_col][n_layers + 1][n_pts]; sca_abs DEVICE [n_src][n_pts], the
+ * scatterer's absorption on the rows' own places.  emi_out DEVICE [n_rows][n_pts], or NULL with out_gas = -1 and
+ * n_rows = 0; j_out DEVICE [n_col][n_layers][n_pts] or NULL; flux_out DEVICE [n_col][2][n_layers + 1][n_pts] or NULL.
+ * One thread per grid point walks the layers once for all columns: the layer operators R, T, 1 - R, 1 - R - T and the
+ * elimination are formed once, the sources per column from two shared factors (E+ + E- = D fs, E+ - E- = D mu0 fd), and
+ * the rows are written from the downward sweep, so J goes to memory only where j_out asks for it.  The roundings differ
+ * from sr_diffuse_source_rows_dev's in the sources; both stay inside the reference's bound.  A column's j_out and
+ * flux_out bits do not depend on which other columns share the call.  A call runs the kernel instance of the next
+ * column count of 1, 2, 4, 8.  v, the coefficients, mu0, col_w, src_row and the rows sorted by layer are staged through
+ * the calling thread's pinned ring; the workspace, 2 + 2 x (instance's columns) doubles per (layer, point), is the
+ * sibling's (grow-only, at most 256 MiB per device, a larger call runs in point chunks; one stream at a time per thread).
+ * One writer per element, no atomics, the same call gives the same bits.  Every argument is checked before the first
+ * copy or launch and a refused call leaves the outputs untouched: SR_ERR_ARG for a NULL desc, v, ssa, asym, cols, mu0,
+ * tab_abs, beam or sun, with rows a NULL col_w, row_layer, src_row or sca_abs or n_src <= 0, n_gas <= 0, n_layers <= 0,
+ * n_pts <= 0, n_col <= 0, n_rows < 0, a v, ssa, asym, surface_albedo, mu0, col_w, row_layer or src_row that is not
+ * finite or outside its range, an out_gas outside -1 .. n_gas - 1, emi_out without out_gas or without rows and the
+ * reverse, all three outputs NULL; SR_ERR_LIMIT for n_col > SR_MAX_DIFFUSE_COLUMNS, n_rows > SR_MAX_ABS_ROWS, n_gas > 8,
+ * n_layers > SR_MAX_ABS_ROWS or n_pts > 2000000.
+ * Checked against an extended-precision reference (tests/test_gpu_diffuse_columns.py). */
+#define SR_MAX_DIFFUSE_COLUMNS 8
+typedef struct {
+  int32_t n_col, n_rows;
+  const double *mu0;          /* HOST [n_col], each in [-1, 1] */
+  const double *col_w;        /* HOST [n_rows][n_col], finite, >= 0 */
+  const int32_t *row_layer;   /* HOST [n_rows], 0 .. n_layers-1, any order, a layer any number of times */
+  const int32_t *src_row;     /* HOST [n_rows], 0 .. n_src-1 */
+} sr_diffuse_columns_desc;
+int sr_diffuse_source_columns_dev(const sr_diffuse_desc *desc, const sr_diffuse_columns_desc *cols,
+                                  const double *tab_abs, const double *beam, const double *sun, int64_t n_pts,
+                                  const double *sca_abs, int n_src, int out_gas, int accumulate,
+                                  double *emi_out, double *j_out, double *flux_out, void *stream);
+
 /* The diffuse rows in the Jacobians: d radiance / d (column parameter) THROUGH the two-stream solve of
  * sr_diffuse_source_rows_dev.  The build's own definition.  A parameter x_p moves, per layer l and grid
  * point j, in the notation above,

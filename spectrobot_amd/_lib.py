@@ -21,6 +21,7 @@ SR_STRENGTH_EINSTEIN, SR_STRENGTH_HITRAN = 0, 1
 SR_MAX_ILS_TAB = 65536
 SR_MAX_ABS_SETS, SR_MAX_ABS_VALUES, SR_MAX_ABS_ROWS = 4096, 1 << 27, 65536
 SR_MAX_SOLAR_VALUES = 1 << 23
+SR_MAX_DIFFUSE_COLUMNS = 8
 
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int32)
@@ -91,6 +92,10 @@ class SolarJacDesc(C.Structure):
 class DiffuseDesc(C.Structure):
     _fields_ = [("n_gas", C.c_int32), ("n_layers", C.c_int32), ("v", dp), ("ssa", dp), ("asym", dp), ("mu0", C.c_double),
                 ("surface_albedo", C.c_double)]
+
+
+class DiffuseColumnsDesc(C.Structure):
+    _fields_ = [("n_col", C.c_int32), ("n_rows", C.c_int32), ("mu0", dp), ("col_w", dp), ("row_layer", ip), ("src_row", ip)]
 
 
 class DiffuseJacDesc(C.Structure):
@@ -239,6 +244,9 @@ SYMBOLS = {
                                              C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "sr_diffuse_source_rows_dev": (C.c_int, [C.POINTER(DiffuseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_diffuse_source_columns_dev": (C.c_int, [C.POINTER(DiffuseDesc), C.POINTER(DiffuseColumnsDesc), C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_diffuse_jacobian_rows_dev": (C.c_int, [C.POINTER(DiffuseDesc), C.POINTER(DiffuseJacDesc), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, ip, C.c_void_p, C.c_int,
                                                C.c_int, C.c_void_p, C.c_void_p]),

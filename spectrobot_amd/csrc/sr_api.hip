@@ -4294,6 +4294,56 @@ int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_ab
   return pk.slot().mark(st);
 }
 
+// The same source for several columns of illumination, and the rows of LOS steps (sr_diffuse_columns.inc).  The workspace
+// is the source's, 2 + 2 NC doubles per (layer, point) for the instance NC the call runs; the plan -- mu0 and col_w padded
+// to NC, the rows sorted by layer -- is diffuse_columns_plan's (sr_solar_plan.hpp), staged with v and the coefficients.
+int sr_diffuse_source_columns_dev(const sr_diffuse_desc *desc, const sr_diffuse_columns_desc *cols, const double *tab_abs,
+                                  const double *beam, const double *sun, int64_t n_pts, const double *sca_abs, int n_src,
+                                  int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out, void *stream) {
+  if (!desc || !desc->v || !desc->ssa || !desc->asym || !cols || !cols->mu0 || !tab_abs || !beam || !sun) return SR_ERR_ARG;
+  if (desc->n_gas <= 0 || desc->n_layers <= 0 || n_pts <= 0 || cols->n_col <= 0 || cols->n_rows < 0) return SR_ERR_ARG;
+  if (cols->n_rows > 0 && (!cols->col_w || !cols->row_layer || !cols->src_row || !sca_abs || n_src <= 0)) return SR_ERR_ARG;
+  if (desc->n_gas > kDiffuseGases || desc->n_layers > SR_MAX_ABS_ROWS || n_pts > kSolarMaxPts ||
+      cols->n_col > SR_MAX_DIFFUSE_COLUMNS || cols->n_rows > SR_MAX_ABS_ROWS)
+    return SR_ERR_LIMIT;
+  const int n_gas = desc->n_gas, n_layers = desc->n_layers, n_col = cols->n_col, n_rows = cols->n_rows;
+  if (out_gas < -1 || out_gas >= n_gas || (out_gas < 0) != (emi_out == nullptr) || (n_rows == 0) != (emi_out == nullptr)) return SR_ERR_ARG;
+  if (!emi_out && !j_out && !flux_out) return SR_ERR_ARG;
+  sr_diffuse_desc state = *desc;
+  state.mu0 = 0.0; // (desc->mu0 is not read: the columns bring their own)
+  double coef[3 * kDiffuseGases], w_out;
+  int rc = check_diffuse_desc(&state, true, out_gas, coef, &w_out);
+  if (rc) return rc;
+  std::vector<double> mu0p, wp;
+  std::vector<int> row_off, row_ix;
+  if (!diffuse_columns_plan(cols->mu0, cols->col_w, cols->row_layer, cols->src_row, n_col, n_rows, n_layers, n_src, w_out == 0.0,
+                            accumulate != 0, mu0p, wp, row_off, row_ix))
+    return SR_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t per = (size_t)8 * (2 + 2 * diffuse_columns_instance(n_col)) * n_layers;
+  const int chunk = diffuse_chunks(per, n_pts, 1).chunk;
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  DevBuf &ws = diffuse_workspace(dev);
+  rc = ws.ensure(per * (size_t)chunk);
+  if (rc) return rc;
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_v = pk.copy(desc->v, (size_t)n_gas * n_layers), p_c = pk.copy(coef, (size_t)3 * kDiffuseGases);
+  const auto p_mu = pk.copy(mu0p.data(), mu0p.size()), p_w = pk.copy(wp.data(), wp.size(), 1);
+  const auto p_off = pk.copy(row_off.data(), row_off.size()), p_ix = pk.copy(row_ix.data(), row_ix.size(), 1);
+  const auto p_src = pk.copy(cols->src_row, (size_t)n_rows, 1);
+  rc = pk.stage(st);
+  if (rc) return rc;
+  for (int64_t p_lo = 0; p_lo < n_pts; p_lo += chunk) {
+    const int p_hi = (int)std::min<int64_t>(n_pts, p_lo + chunk);
+    LAUNCHCHK(launch_diffuse_columns(tab_abs, n_gas, n_layers, (int)n_pts, (int)p_lo, p_hi, pk.dev(p_v), pk.dev(p_c), beam, n_col, sun,
+                                     pk.dev(p_mu), desc->surface_albedo, w_out, pk.dev(p_off), pk.dev(p_ix), pk.dev(p_src),
+                                     pk.dev(p_w), sca_abs, ws.as<double>(), chunk, accumulate != 0, emi_out, j_out, flux_out, st));
+  }
+  return pk.slot().mark(st);
+}
+
 // What the two Jacobian entries share once their arguments are checked: par_slot's check, the workspace, the staging and
 // the launches (the entry's comment below).  dir is the direction as its kernel instance reads it: dv
 // [n_par][n_gas][n_layers], or -- optics -- dopt [n_par][kDiffuseOpt] (sr_diffuse_optics_jacobian_rows_dev); mask is that

@@ -530,5 +530,16 @@ int launch_diffuse_optics_tangent(const double *tab_abs, int n_gas, int n_layers
 int launch_diffuse_contract(const double *q, int n_rays, int n_layers, int n_pts, int p_lo, int p_hi, int par_lo, int par_hi,
                             const double *dj, int dj_stride, int dj_joff, int dj_par0, const int *par_slot, bool accumulate,
                             double *jac, int n_jac_rows, hipStream_t st);
+// the two-stream diffuse source for n_col <= kDiffuseColumns columns of illumination and the rows of LOS steps
+// (sr_diffuse_columns.inc) on the points [p_lo, p_hi): v and coef as above, beam [n_col][n_layers + 1][n_pts]; mu0 [NC],
+// col_w [n_rows][NC], row_off [n_layers + 1] and row_ix from diffuse_columns_plan (sr_solar_plan.hpp), NC =
+// diffuse_columns_instance(n_col), and src_row [n_rows]: staged device arrays; ws [2 + 2 NC][n_layers][ws_stride],
+// ws_stride >= the points rounded up to 256; emi_out [n_rows][n_pts] (null: row_off all zero), j_out [n_col][n_layers]
+// [n_pts] and flux_out [n_col][2][n_layers + 1][n_pts] may each be null.
+int launch_diffuse_columns(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, const double *v,
+                           const double *coef, const double *beam, int n_col, const double *sun, const double *mu0, double albedo,
+                           double w_out, const int *row_off, const int *row_ix, const int *src_row, const double *col_w,
+                           const double *sca_abs, double *ws, int ws_stride, bool accumulate, double *emi_out, double *j_out,
+                           double *flux_out, hipStream_t st);
 
 } // namespace sr

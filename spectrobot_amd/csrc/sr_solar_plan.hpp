@@ -17,6 +17,8 @@ constexpr int kDiffuseGases = 8; // gas slots of sr_diffuse_source_kernel's loop
 constexpr int kDiffuseJacPars = 4; // NP: parameters per block of sr_diffuse_tangent_kernel and per thread of the contraction
 constexpr int kDiffuseOpt = 3 * kDiffuseGases + 1; // doubles per parameter of an optics direction: the coefficients' tangents, the albedo's
 constexpr int kDiffuseJacRays = 8; // NR: rays per thread of sr_diffuse_contract_kernel (profiles/diffuse_jacobian_kernel_resources.txt)
+constexpr int kDiffuseColumns = 8; // columns of sr_diffuse_columns_kernel's largest instance (SR_MAX_DIFFUSE_COLUMNS): n_col above is refused
+constexpr int kZeroRow = 1 << 30;  // row_ix flag of sr_diffuse_columns_kernel: the row is an exact 0 (row numbers stay below 2^17)
 
 // The one walk behind both plans: x [n_groups][n_rows][n_k], per (group, row tile) the chunks in which a row of the tile
 // that counts (w == nullptr: every row; else the rows with w[r] != 0) has a non-zero element, ascending; tile_off
@@ -141,6 +143,48 @@ inline bool diffuse_optics_plan(const double *v, const double *ssa, const double
     if (hi > lo) mask[(size_t)2 * p] = lo, mask[(size_t)2 * p + 1] = hi;
   }
   return ok;
+}
+
+// The plan of sr_diffuse_columns_kernel (sr_diffuse_columns.inc; tools/diffuse_columns_host).  nc: the instance a call of
+// n_col columns runs, the next of 1, 2, 4, 8.  mu0p [nc] and wp [n_rows][nc]: mu0 and col_w padded with zeros.  row_ix: the
+// rows in the order of the kernel's downward walk -- layer n_layers - 1 first, a layer's rows ascending --, layer l's at
+// row_off[n_layers - 1 - l] .. row_off[n_layers - l]; a row that is an exact 0 (`dark`: the gas scatters nothing; or
+// every weight is 0) carries kZeroRow, or, accumulating, is not listed at all: its row of the output keeps its bits.
+// Returns false for a mu0 outside [-1, 1], a weight that is negative or not finite, or a row_layer or src_row outside
+// its range; the arrays are then unspecified.
+inline int diffuse_columns_instance(int n_col) { return n_col <= 1 ? 1 : n_col <= 2 ? 2 : n_col <= 4 ? 4 : kDiffuseColumns; }
+inline bool diffuse_columns_plan(const double *mu0, const double *col_w, const int *row_layer, const int *src_row, int n_col,
+                                 int n_rows, int n_layers, int n_src, bool dark, bool accumulate, std::vector<double> &mu0p,
+                                 std::vector<double> &wp, std::vector<int> &row_off, std::vector<int> &row_ix) {
+  const int nc = diffuse_columns_instance(n_col);
+  mu0p.assign((size_t)nc, 0.0);
+  wp.assign((size_t)n_rows * nc, 0.0);
+  row_off.assign((size_t)n_layers + 1, 0);
+  row_ix.clear();
+  bool ok = true;
+  for (int c = 0; c < n_col; ++c) {
+    ok &= (mu0[c] >= -1.0) & (mu0[c] <= 1.0); // (a NaN fails both)
+    mu0p[(size_t)c] = mu0[c];
+  }
+  std::vector<char> zero((size_t)n_rows, 1);
+  std::vector<int> count((size_t)n_layers, 0);
+  for (int r = 0; r < n_rows; ++r) {
+    for (int c = 0; c < n_col; ++c) {
+      const double w = col_w[(size_t)r * n_col + c];
+      ok &= (w >= 0.0) & (w <= 1.7976931348623157e308);
+      wp[(size_t)r * nc + c] = w;
+      if (w != 0.0 && !dark) zero[(size_t)r] = 0;
+    }
+    if (row_layer[r] < 0 || row_layer[r] >= n_layers || src_row[r] < 0 || src_row[r] >= n_src) return false;
+    if (!(zero[(size_t)r] && accumulate)) ++count[(size_t)row_layer[r]];
+  }
+  if (!ok) return false;
+  for (int l = n_layers - 1; l >= 0; --l) row_off[(size_t)(n_layers - l)] = row_off[(size_t)(n_layers - 1 - l)] + count[(size_t)l];
+  row_ix.resize((size_t)row_off[(size_t)n_layers]);
+  std::vector<int> at(row_off.begin(), row_off.end() - 1);
+  for (int r = 0; r < n_rows; ++r)
+    if (!(zero[(size_t)r] && accumulate)) row_ix[(size_t)at[(size_t)(n_layers - 1 - row_layer[r])]++] = r | (zero[(size_t)r] ? kZeroRow : 0);
+  return true;
 }
 
 } // namespace sr

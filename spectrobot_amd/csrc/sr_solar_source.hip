@@ -2,7 +2,8 @@
 // (sr_solar_source_rows_dev: sr_solar_source.inc) and the solar attenuation in the Jacobians (sr_solar_jacobian_rows_dev:
 // sr_solar_jac.inc), both on the tile product of sr_solar_tile.inc, and the two-stream diffuse source
 // (sr_diffuse_source_rows_dev: sr_diffuse_source.inc) and its tangent in the Jacobians (sr_diffuse_jacobian_rows_dev:
-// sr_diffuse_jac.inc), each kernel's text and its launcher.  A translation unit of its own, compiled beside the others:
+// sr_diffuse_jac.inc) and the same source for several columns of illumination with the rows of LOS steps
+// (sr_diffuse_source_columns_dev: sr_diffuse_columns.inc), each kernel's text and its launcher.  A translation unit of its own, compiled beside the others:
 // no other unit includes the kernels' text, and this one instantiates no other kernel.
 //
 //   sr_solar_source_kernel<ACC, TRANS>   four instances: overwrite / accumulate, with and without the transmission
@@ -11,6 +12,7 @@
 //   sr_diffuse_tangent_kernel<NP, OPT>    two instances: NP = kDiffuseJacPars parameters per block; along column parameters,
 //                                         and (OPT) along a direction in ssa, asym and the surface albedo
 //   sr_diffuse_contract_kernel<NR, NP, ACC> two instances: overwrite / accumulate, kDiffuseJacRays x kDiffuseJacPars per thread
+//   sr_diffuse_columns_kernel<NC, ACC>    eight instances: NC = 1, 2, 4, 8 columns, overwrite / accumulate
 #include "sr_device.hpp"
 #include "sr_kernels.hpp"
 #include "sr_limb_dispatch.hpp"
@@ -23,6 +25,7 @@ namespace sr {
 #include "sr_solar_jac.inc"
 #include "sr_diffuse_source.inc"
 #include "sr_diffuse_jac.inc"
+#include "sr_diffuse_columns.inc"
 
 int launch_solar_source(const double *tab_abs, int n_k, int n_pts, const double *u, const double *w, const int *src_row,
                         int n_rows, const int *tile_off, const int *chunks, const double *sca_abs, const double *sun,
@@ -103,6 +106,29 @@ int launch_diffuse_contract(const double *q, int n_rays, int n_layers, int n_pts
                        q, n_rays, n_layers, n_pts, p_lo, p_hi, par_lo, par_hi, dj, dj_stride, dj_joff, dj_par0, par_slot, jac,
                        n_jac_rows);
   });
+  return (int)hipGetLastError();
+}
+
+int launch_diffuse_columns(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, const double *v,
+                           const double *coef, const double *beam, int n_col, const double *sun, const double *mu0, double albedo,
+                           double w_out, const int *row_off, const int *row_ix, const int *src_row, const double *col_w,
+                           const double *sca_abs, double *ws, int ws_stride, bool accumulate, double *emi_out, double *j_out,
+                           double *flux_out, hipStream_t st) {
+  if (n_layers <= 0 || p_hi <= p_lo) return 0;
+  const dim3 grid(limb_grid((p_hi - p_lo + 255) / 256, 1));
+  auto go = [&](auto nc) {
+    by_flag(accumulate && emi_out, [&](auto acc) {
+      hipLaunchKernelGGL((sr_diffuse_columns_kernel<decltype(nc)::value, decltype(acc)::value>), grid, dim3(256), 0, st, tab_abs,
+                         n_gas, n_layers, n_pts, p_lo, p_hi, v, coef, beam, n_col, sun, mu0, albedo, w_out, row_off, row_ix, src_row,
+                         col_w, sca_abs, ws, ws_stride, emi_out, j_out, flux_out);
+    });
+  };
+  switch (diffuse_columns_instance(n_col)) { // (mu0 and col_w are padded to the instance by diffuse_columns_plan)
+  case 1: go(std::integral_constant<int, 1>()); break;
+  case 2: go(std::integral_constant<int, 2>()); break;
+  case 4: go(std::integral_constant<int, 4>()); break;
+  default: go(std::integral_constant<int, kDiffuseColumns>()); break;
+  }
   return (int)hipGetLastError();
 }
 

@@ -736,6 +736,80 @@ def diffuse_source(A, V, ssa, asym, beam, sun, mu0, surface_albedo=0.0, out_gas=
     return res[0] if len(res) == 1 else res
 
 
+def diffuse_source_columns(A, V, ssa, asym, beams, sun, mu0s, col_w, row_layer, sca=None, src_row=None, surface_albedo=0.0,
+                           out_gas=None, out=None, accumulate=False, mean_intensity=False, fluxes=False):
+    """The diffuse field of diffuse_source for several columns of illumination over one atmosphere, and the emission rows
+    of LOS steps that see it (sr_diffuse_source_columns_dev; the build's own definition): the steps of a
+    3-D limb batch each have their own solar zenith angle.  Column c has mu0s[c] and beams[c]; J[c] and F[c] are exactly
+    what diffuse_source defines for them (the atmosphere and its optics are shared, the columns independent), and
+
+        emi[r] (+)= ssa_G (1 - f_G) sca[src_row[r]] sum_c col_w[r, c] J[c, row_layer[r]]
+
+    for the gas G = out_gas.  A, V, ssa, asym, sun, surface_albedo: as diffuse_source takes them.  beams: CUDA [n_col,
+    n_layers + 1, n_pts], n_col <= 8; mu0s: host [n_col]; col_w: host [n_rows, n_col] >= 0 (geometry.sza_columns: linear
+    in mu0 between the columns); row_layer: host [n_rows], the layer of every row, in any order, a layer any number of
+    times; sca: CUDA [n_src, n_pts], the scatterer's absorption on the rows' own places, and src_row [n_rows] (None: row
+    r of sca); sca=None means A[out_gas] with src_row = row_layer.  out: CUDA [n_rows, n_pts], required with
+    accumulate=True; a row whose weights are all zero is an exact 0 and, accumulating, keeps its bits.
+    mean_intensity=True: also J [n_col, n_layers, n_pts]; fluxes=True: also F [n_col, 2, n_layers + 1, n_pts].  One kernel
+    walks the layers once for all columns (the instance of the next column count of 1, 2, 4, 8); one writer per element;
+    the same call gives the same bits, and a column's J and F do not depend on which columns share the call.  Every
+    Jacobian treats these rows as coefficients.  Returns emi (if out_gas is given), then J, then F, as asked."""
+    if not (_cuda_f64(A) and _cuda_f64(beams) and _cuda_f64(sun)) or A.dim() != 3 or beams.dim() != 3 or sun.dim() != 1:
+        raise ValueError("A, beams and sun must be contiguous CUDA float64 tensors ([n_gas, n_layers, n_pts], "
+                         "[n_col, n_layers + 1, n_pts], [n_pts])")
+    if beams.shape[0] == 0:
+        raise ValueError("beams must hold one column at the least")
+    d, (n_gas, n_layers, n_pts), keep = _diffuse_state(A, V, ssa, asym, beams[0], sun, 0.0, surface_albedo)
+    n_col = int(beams.shape[0])
+    ma, mp = _d(np.asarray(mu0s, dtype=np.float64).reshape(-1))
+    if ma.shape != (n_col,):
+        raise ValueError("mu0s must be [n_col] = [%d], one per column of beams" % n_col)
+    cd = _lib.DiffuseColumnsDesc()
+    cd.n_col, cd.n_rows, cd.mu0 = n_col, 0, mp
+    n_src = 0
+    if out_gas is None:
+        if out is not None or accumulate or sca is not None:
+            raise ValueError("out=, accumulate= and sca= belong to the rows of out_gas=")
+        if not (mean_intensity or fluxes):
+            raise ValueError("nothing asked for: out_gas=, mean_intensity=True or fluxes=True")
+    else:
+        la, lp = _i(row_layer)
+        if la.ndim != 1 or la.shape[0] == 0:
+            raise ValueError("row_layer must be [n_rows], one row at the least")
+        n_rows = la.shape[0]
+        wa, wp = _d(np.asarray(col_w, dtype=np.float64))
+        if wa.shape != (n_rows, n_col):
+            raise ValueError("col_w must be [n_rows, n_col] = [%d, %d]" % (n_rows, n_col))
+        if sca is None:
+            if src_row is not None or not 0 <= int(out_gas) < n_gas:
+                raise ValueError("sca=None takes A[out_gas] with src_row = row_layer")
+            sca, src_row = A[int(out_gas)], la
+        elif not _cuda_f64(sca) or sca.dim() != 2 or sca.shape[1] != n_pts:
+            raise ValueError("sca must be a contiguous CUDA float64 [n_src, n_pts] on A's %d grid points" % n_pts)
+        sa, sp = _i(np.arange(n_rows) if src_row is None else src_row)
+        if sa.shape != (n_rows,):
+            raise ValueError("src_row must be [n_rows]")
+        n_src = int(sca.shape[0])
+        cd.n_rows, cd.col_w, cd.row_layer, cd.src_row = n_rows, wp, lp, sp
+        keep = keep + (la, wa, sa)
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True adds to out=...")
+            out = torch.empty((n_rows, n_pts), dtype=torch.float64, device="cuda")
+        elif not _cuda_f64(out) or out.shape != (n_rows, n_pts):
+            raise ValueError("out must be a contiguous CUDA float64 [n_rows, n_pts]")
+    J = torch.empty((n_col, n_layers, n_pts), dtype=torch.float64, device="cuda") if mean_intensity else None
+    F = torch.empty((n_col, 2, n_layers + 1, n_pts), dtype=torch.float64, device="cuda") if fluxes else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    check(lib.sr_diffuse_source_columns_dev(C.byref(d), C.byref(cd), ptr(A), ptr(beams), ptr(sun), n_pts, ptr(sca), n_src,
+                                            -1 if out_gas is None else int(out_gas), int(bool(accumulate)), ptr(out), ptr(J), ptr(F),
+                                            _stream_ptr()),
+          "sr_diffuse_source_columns_dev")
+    res = tuple(t for t in (out, J, F) if t is not None)
+    return res[0] if len(res) == 1 else res
+
+
 SOLAR_JAC_RAYS = 8      # rays per block of sr_solar_jac_kernel (kSolarJacRays): where the ray-group edge of a call sits
 
 

@@ -459,6 +459,28 @@ def _vertical_columns(z, nd_levels, vmr_levels, R, n_sub, col_scale, columns):
     return np.ascontiguousarray(U[0])
 
 
+def sza_columns(seg_mu, n_col):
+    """The solar zenith angles a 3-D batch's diffuse field is solved at, and each step's weights between them:
+    (mu_nodes [n_col], col_w [n_seg, n_col]) for engine.diffuse_source_columns.  The nodes are equally spaced in
+    mu = cos SZA from min(seg_mu) to max(seg_mu); a step's weights are linear in mu: at most two non-zeros, adjacent,
+    summing to 1, with col_w @ mu_nodes = seg_mu.  With n_col == 1, or steps that span less than 1e-12 in mu, there is one
+    node at the mean and every weight is 1."""
+    mu = np.asarray(seg_mu, dtype=float).reshape(-1)
+    n_col = int(n_col)
+    if n_col < 1 or mu.size == 0 or not np.all(np.abs(mu) <= 1.0):
+        raise ValueError("sza_columns takes n_col >= 1 and cosines in [-1, 1], one step at the least")
+    lo, hi = float(mu.min()), float(mu.max())
+    if n_col == 1 or hi - lo < 1e-12:
+        return np.array([lo if hi == lo else float(mu.mean())]), np.ones((mu.size, 1))
+    nodes = np.linspace(lo, hi, n_col)
+    k = np.clip(np.searchsorted(nodes, mu, side="right") - 1, 0, n_col - 2)
+    f = np.clip((mu - nodes[k]) / (nodes[k + 1] - nodes[k]), 0.0, 1.0)
+    w = np.zeros((mu.size, n_col))
+    at = np.arange(mu.size)
+    w[at, k], w[at, k + 1] = 1.0 - f, f
+    return nodes, w
+
+
 def _solar_rays(z, zz, ln, alt, mu, R, n_sub):
     """The sun rays of _solar_columns without a profile on them: (lit [n_rows], limb_los's dict of the rays' crossings
     with x, nd and alt but no vmr -- None when no ray crosses anything).  z, zz, ln: _profiles' levels."""

@@ -445,7 +445,8 @@ class LimbScene(object):
     sun: a Sun.  With it, the emission rows of every TableGas(solar=...) are thermal + single-scattered sunlight
     (coefficients() ends with one solar pass over the layer rows, solar_pass); the tangent-SZA approximation -- the
     reference's use_tangent_sza = True: mu = cos(sza) on every row -- and Theta = 180 deg - phase.  A per-step SZA is
-    the 3-D route: engine.solar_source on geometry.limb_los_3d's rows."""
+    the 3-D route: engine.solar_source on geometry.limb_los_3d's rows, and sunlit_steps(L3) makes those rows -- with the
+    diffuse field under every step's own SZA (engine.diffuse_source_columns) for a Sun(multiple=True)."""
 
     def __init__(self, grid, z, temps, press, gases, bands_nm, widths_nm, R=2575.0, n_sub=3, out_units="Wm2", ils=None,
                  sun=None):
@@ -603,6 +604,57 @@ class LimbScene(object):
         for g in solar:
             i = self.gases.index(g)
             g.coeffs[1].addcmul_(A[i], J, value=float(ssa[i] * (1.0 - max(asym[i], 0.0) ** 2)))
+
+    def sunlit_steps(self, L3, n_columns=4, g_lo=0, g_hi=None):
+        """The per-gas (abs, emi) pairs on the step rows of a 3-D batch L3 (geometry.limb_los_3d), each step under its own
+        solar zenith angle L3["seg_mu"]: what engine.limb_rays takes with an engine.LimbLOS of L3.  The layer rows are
+        gathered by L3["seg_alt_layer"]; the solar gases' emission is thermal + order one with the per-step SZA (one
+        engine.solar_source call per solar gas over the steps, columns towards the sun from the middle of each step).
+        With Sun(multiple=True) the diffuse field is added by one engine.diffuse_source_columns call per solar gas under
+        accumulate: n_columns solar zenith angles equally spaced in mu over the steps' range (geometry.sza_columns), linear
+        in mu between them, the beams of all columns from ONE engine.solar_source(..., transmission=True) call over
+        n_columns x (n_layers + 1) points -- diffuse_inputs' points, delta scaling and V.  The sun's sza_deg is not read;
+        its phase, irradiance, multiple and surface_albedo are.  Nothing of the scene's own 1-D solar pass is used or
+        changed, and no Jacobian is made of these rows."""
+        import torch
+        solar = self.solar_gases()
+        if not solar:
+            raise ValueError("sunlit_steps needs a scene with a Sun and a TableGas(solar=...)")
+        g_hi = len(self.grid) if g_hi is None else int(g_hi)
+        for g in self.gases:        # coefficients() without its solar pass: that one is the tangent-SZA sun's
+            if isinstance(g, LevelGas):
+                g.layer_coefficients(self.temps, self.press, g_lo=g_lo, g_hi=g_hi)
+            else:
+                self.gas_coefficients(g, False, g_lo, g_hi)
+        pairs = [g.thermal if g in solar else g.coeffs for g in self.gases]
+        layer = np.ascontiguousarray(L3["seg_alt_layer"], dtype=np.int32)
+        rows = torch.as_tensor(layer.astype(np.int64), device="cuda")
+        A = torch.stack([p[0] for p in pairs]).contiguous()
+        step_abs = [A[i][rows].contiguous() for i in range(len(pairs))]
+        step_emi = [p[1][rows].contiguous() for p in pairs]
+        lo, hi = L3["pt_off"][:-1], L3["pt_off"][1:] - 1
+        alt_mid = 0.5 * (L3["alt"][(lo + hi) // 2] + L3["alt"][(lo + hi + 1) // 2])
+        vmr, iso = [g.vmr for g in self.gases], [g.iso_ratio for g in self.gases]
+        U, lit = geometry.solar_columns(self.z, self.nd, vmr, alt_mid, L3["seg_mu"], R=self.R, n_sub=self.n_sub, col_scale=iso)
+        sun = torch.as_tensor(self.sun.irradiance[g_lo:g_hi], device="cuda").contiguous()
+        for g in solar:
+            i = self.gases.index(g)
+            engine.solar_source(A, U, self.solar_weights(g, lit), pairs[i][0], sun, src_row=layer, out=step_emi[i], accumulate=True)
+        if self.sun.multiple:
+            mu_nodes, col_w = geometry.sza_columns(L3["seg_mu"], n_columns)
+            ssa, asym, iso_a, pts, beam_scale = self.diffuse_geometry(solar)
+            cols = [geometry.solar_columns(self.z, self.nd, vmr, pts, float(m), R=self.R, n_sub=self.n_sub, col_scale=beam_scale)
+                    for m in mu_nodes]
+            Ub, lit_b = np.concatenate([c[0] for c in cols]), np.concatenate([c[1] for c in cols])
+            _, beams = engine.solar_source(A, Ub, np.where(lit_b, 1.0, 0.0), A[self.gases.index(solar[0])], sun,
+                                           src_row=np.zeros(len(lit_b), np.int32), transmission=True)
+            beams = beams.view(len(mu_nodes), len(pts), -1)
+            V = geometry.vertical_columns(self.z, self.nd, vmr, R=self.R, n_sub=self.n_sub, col_scale=iso_a)
+            for g in solar:
+                i = self.gases.index(g)
+                engine.diffuse_source_columns(A, V, ssa, asym, beams, sun, mu_nodes, col_w, layer, surface_albedo=self.sun.surface_albedo,
+                                              out_gas=i, out=step_emi[i], accumulate=True)
+        return list(zip(step_abs, step_emi))
 
     def solar_attenuation_jacobian(self, los, alt, w, coeffs, jac=None):
         """The solar attenuation in the column rows of a state Jacobian: d rad / d x_p through tau for the column block

@@ -50,8 +50,9 @@ def load_unit(stem):  # demangled name -> (metadata block, [instructions])
             cur = code.setdefault(m[1], [])
         elif cur is not None and line.strip():
             cur.append(re.sub(r"\s+", " ", line.split("//")[0]).strip())
-    for c in code.values():  # (the padding behind a kernel's last instruction; "...": padding objdump left out)
-        while c and c[-1].startswith(("s_nop", "s_code_end", "...")):
+    for c in code.values():  # (the padding behind a kernel's last instruction; "...": padding objdump left out; a zero
+        # word of padding between two kernels decodes as v_cndmask_b32_e32 v0, s0, v0, vcc)
+        while c and (c[-1].startswith(("s_nop", "s_code_end", "...")) or c[-1] == "v_cndmask_b32_e32 v0, s0, v0, vcc"):
             c.pop()
     sym = list(meta)
     return {d: (meta[s], code.get(s, [])) for s, d in zip(sym, demangle(sym))}
