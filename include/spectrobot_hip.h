@@ -1052,6 +1052,45 @@ int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_ab
                                int64_t n_pts, int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out,
                                void *stream);
 
+/* Thermal emission as a source of the same two-stream diffuse field: alone (the night side, thermal windows) or together
+ * with the sun's in one walk of the layers.  The build's own definition; notation, equations, boundary
+ * conditions and outputs are sr_diffuse_source_rows_dev's.  The thermal source of layer l is isotropic and constant over
+ * the layer, at the layer's own temperature:
+ *   S+ = S- = 2 pi co B_l,   B_l = B(nu_j, T_l) = 2 h c^2 nu_j^3 / (exp(c2 nu_j / T_l) - 1),  nu_j = w0 + (g_lo + j) step
+ * so that a layer with nothing coming in sends out E+_th = E-_th = (2 pi / sqrt3) B_l (1 - R - T) (Kirchhoff's law for
+ * the layer; R, T its two-stream reflection and transmission), added to the solar E+- where there is a sun.  A layer with
+ * alpha == 0 at a point has a thermal source of exactly 0 there (the floor of co invents no emission).  A Lambertian
+ * surface of emissivity 1 - surface_albedo at t_surface adds (1 - surface_albedo) (2 pi / sqrt3) B(nu_j, t_surface) to
+ * the upwelling at the lower boundary (the two-stream value: everything at one temperature gives J = B exactly);
+ * t_surface = 0 is no emitting surface.  F-(top) = 0.  The rows:
+ *   own_emission == 0:  emi_out[l][j] (+)= ssa_G (1 - f_G) tab_abs[G N + l][j] J_l[j]
+ *   own_emission != 0:  emi_out[l][j] (+)= tab_abs[G N + l][j] ((1 - ssa_G) B_l + ssa_G (1 - f_G) J_l[j])
+ * the second the scatterer's complete thermal row: its own emission by Kirchhoff's law and the scattered field.  Deep
+ * inside a thick isothermal column it tends to tab_abs B (1 - ssa_G f_G): for asym > 0 the forward peak's share of the
+ * line-of-sight source is left out, as it is for the solar rows.  Every output is >= 0, and an exact 0 where no layer has
+ * an absorber, no surface emits and no sun shines.
+ * desc, tab_abs, n_pts, out_gas, accumulate, emi_out, j_out, flux_out, stream: as sr_diffuse_source_rows_dev takes them.
+ * beam and sun: both given (as the sibling takes them), or both NULL for thermal emission alone; desc->mu0 is not read
+ * when both are NULL.  th: temps HOST [n_layers] > 0, the layers' temperatures; t_surface >= 0; w0, step, g_lo: the
+ * spectral grid of the points; own_emission: the rows' form.  B is evaluated in the kernel as sr_abs_table_layers_dev
+ * evaluates it (no array of Planck values is made); the night call reads tab_abs alone.  Kernel layout, workspace, point
+ * chunks above 256 MiB, staging through the calling thread's pinned ring (temps with v) and the one-stream rule are the
+ * sibling's.  One writer per element, no atomics, the same call gives the same bits.  Every argument is checked before
+ * the first copy or launch and a refused call leaves the outputs untouched: the sibling's refusals (beam and sun as
+ * above), and SR_ERR_ARG for a NULL th or temps, a temperature <= 0 or not finite, t_surface < 0 or not finite, a w0 or
+ * step that is not finite, g_lo < 0, exactly one of beam and sun, own_emission without emi_out; SR_ERR_LIMIT for
+ * g_lo + n_pts > INT32_MAX.
+ * Checked against an extended-precision reference (tests/test_gpu_diffuse_thermal.py). */
+typedef struct {
+  const double *temps; /* HOST [n_layers], > 0 */
+  double t_surface, w0, step;
+  int64_t g_lo;
+  int32_t own_emission;
+} sr_diffuse_thermal_desc;
+int sr_diffuse_thermal_rows_dev(const sr_diffuse_desc *desc, const sr_diffuse_thermal_desc *th, const double *tab_abs,
+                                const double *beam, const double *sun, int64_t n_pts, int out_gas, int accumulate,
+                                double *emi_out, double *j_out, double *flux_out, void *stream);
+
 /* The diffuse field for several columns of illumination over one atmosphere, and the emission rows of LOS steps that
  * see it: a 3-D limb batch, whose steps each have their own solar zenith angle.  The build's own definition (DESIGN.md
  * 4.11e).  For column c < n_col, with mu0[c] and beam[c] [n_layers + 1][n_pts], J[c][l][j] and F+-[c][i][j] are exactly

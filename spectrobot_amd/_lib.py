@@ -94,6 +94,11 @@ class DiffuseDesc(C.Structure):
                 ("surface_albedo", C.c_double)]
 
 
+class DiffuseThermalDesc(C.Structure):
+    _fields_ = [("temps", dp), ("t_surface", C.c_double), ("w0", C.c_double), ("step", C.c_double), ("g_lo", C.c_int64),
+                ("own_emission", C.c_int32)]
+
+
 class DiffuseColumnsDesc(C.Structure):
     _fields_ = [("n_col", C.c_int32), ("n_rows", C.c_int32), ("mu0", dp), ("col_w", dp), ("row_layer", ip), ("src_row", ip)]
 
@@ -244,6 +249,9 @@ SYMBOLS = {
                                              C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "sr_diffuse_source_rows_dev": (C.c_int, [C.POINTER(DiffuseDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_diffuse_thermal_rows_dev": (C.c_int, [C.POINTER(DiffuseDesc), C.POINTER(DiffuseThermalDesc), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
     "sr_diffuse_source_columns_dev": (C.c_int, [C.POINTER(DiffuseDesc), C.POINTER(DiffuseColumnsDesc), C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),

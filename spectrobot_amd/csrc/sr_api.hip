@@ -4294,6 +4294,52 @@ int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_ab
   return pk.slot().mark(st);
 }
 
+// Thermal emission as a source of the same field (sr_diffuse_thermal.inc), alone (beam and sun NULL: desc's mu0 is not
+// read) or with the sun's.  Workspace, point chunks, staging and the one-stream rule are the sibling's; the layers'
+// temperatures are staged with v.
+int sr_diffuse_thermal_rows_dev(const sr_diffuse_desc *desc, const sr_diffuse_thermal_desc *th, const double *tab_abs,
+                                const double *beam, const double *sun, int64_t n_pts, int out_gas, int accumulate,
+                                double *emi_out, double *j_out, double *flux_out, void *stream) {
+  if (!desc || !desc->v || !desc->ssa || !desc->asym || !tab_abs || !th || !th->temps) return SR_ERR_ARG;
+  if ((beam == nullptr) != (sun == nullptr)) return SR_ERR_ARG;
+  if (desc->n_gas <= 0 || desc->n_layers <= 0 || n_pts <= 0 || th->g_lo < 0) return SR_ERR_ARG;
+  if (desc->n_gas > kDiffuseGases || desc->n_layers > SR_MAX_ABS_ROWS || n_pts > kSolarMaxPts || th->g_lo > INT32_MAX - n_pts)
+    return SR_ERR_LIMIT;
+  const int n_gas = desc->n_gas, n_layers = desc->n_layers;
+  if (out_gas < -1 || out_gas >= n_gas || (out_gas < 0) != (emi_out == nullptr)) return SR_ERR_ARG;
+  if (!emi_out && !j_out && !flux_out) return SR_ERR_ARG;
+  if (th->own_emission && !emi_out) return SR_ERR_ARG;
+  if (!(th->t_surface >= 0.0) || !std::isfinite(th->t_surface) || !std::isfinite(th->w0) || !std::isfinite(th->step)) return SR_ERR_ARG;
+  for (int l = 0; l < n_layers; ++l)
+    if (!(th->temps[l] > 0.0) || !std::isfinite(th->temps[l])) return SR_ERR_ARG;
+  sr_diffuse_desc state = *desc;
+  if (!beam) state.mu0 = 0.0;
+  double coef[3 * kDiffuseGases], w_out;
+  int rc = check_diffuse_desc(&state, true, out_gas, coef, &w_out);
+  if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int chunk = diffuse_chunks((size_t)32 * n_layers, n_pts, 1).chunk;
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  DevBuf &ws = diffuse_workspace(dev);
+  rc = ws.ensure((size_t)32 * n_layers * chunk);
+  if (rc) return rc;
+  static thread_local StagerRing ring;
+  StagePack pk(ring.take());
+  const auto p_v = pk.copy(desc->v, (size_t)n_gas * n_layers), p_c = pk.copy(coef, (size_t)3 * kDiffuseGases);
+  const auto p_t = pk.copy(th->temps, (size_t)n_layers);
+  rc = pk.stage(st);
+  if (rc) return rc;
+  for (int64_t p_lo = 0; p_lo < n_pts; p_lo += chunk) {
+    const int p_hi = (int)std::min<int64_t>(n_pts, p_lo + chunk);
+    LAUNCHCHK(launch_diffuse_thermal(tab_abs, n_gas, n_layers, (int)n_pts, (int)p_lo, p_hi, pk.dev(p_v), pk.dev(p_c), pk.dev(p_t),
+                                     beam, sun, state.mu0, state.surface_albedo, th->t_surface, th->w0, th->step, (int)th->g_lo,
+                                     th->own_emission != 0, out_gas, ws.as<double>(), chunk, accumulate != 0,
+                                     emi_out, j_out, flux_out, st));
+  }
+  return pk.slot().mark(st);
+}
+
 // The same source for several columns of illumination, and the rows of LOS steps (sr_diffuse_columns.inc).  The workspace
 // is the source's, 2 + 2 NC doubles per (layer, point) for the instance NC the call runs; the plan -- mu0 and col_w padded
 // to NC, the rows sorted by layer -- is diffuse_columns_plan's (sr_solar_plan.hpp), staged with v and the coefficients.

@@ -36,7 +36,8 @@
 // call's last reads the last point and stores nothing (its workspace column is its own).  One writer per element, no
 // atomics: the same call gives the same bits.
 // (kDiffuseGases: sr_solar_plan.hpp)
-struct DiffuseLayer { double R, T, Ep, Em, oneR, absb; bool live; };
+struct DiffuseLayer { double R, T, Ep, Em, oneR, absb, absq; bool live; }; // absq: 1 - R - T once more, as m u / (1 + Gamma e) --
+// u + Gamma m = 1 - Gamma e cancelled against den, nothing subtracted -- for sr_diffuse_thermal_kernel, whose source it is
 
 // the layer operators from the three sums and the source D of the layer's middle
 __device__ __forceinline__ DiffuseLayer diffuse_layer(double sp, double al, double sg, double D, double mu0) {
@@ -44,7 +45,7 @@ __device__ __forceinline__ DiffuseLayer diffuse_layer(double sp, double al, doub
   DiffuseLayer o;
   const double dtau = sp + al;
   if (!(dtau > 0.0)) {
-    o.R = 0.0, o.T = 1.0, o.Ep = 0.0, o.Em = 0.0, o.oneR = 1.0, o.absb = 0.0, o.live = false;
+    o.R = 0.0, o.T = 1.0, o.Ep = 0.0, o.Em = 0.0, o.oneR = 1.0, o.absb = 0.0, o.absq = 0.0, o.live = false;
     return o;
   }
   o.live = true;
@@ -62,6 +63,7 @@ __device__ __forceinline__ DiffuseLayer diffuse_layer(double sp, double al, doub
   o.T = e * u * (1.0 + Gm) * rden;
   o.oneR = u * (1.0 + Gm * e * e) * rden;
   o.absb = m * u * (1.0 - Gm * e) * rden;
+  o.absq = m * u / ge;
   const double oneT = m * (u + Gm * ge) * rden;
   const double src = om * D;
   const double es = src * (sd + ss) * rg * (m / sd) / ge;

@@ -599,10 +599,12 @@ def _jac_target(out, par_slot, accumulate, n_rays, n_par, n_pts):
     return out, slot, slot_p
 
 
-def _diffuse_state(A, V, ssa, asym, beam, sun, mu0, surface_albedo):
+def _diffuse_state(A, V, ssa, asym, beam, sun, mu0, surface_albedo, night=False):
     """(sr_diffuse_desc, (n_gas, n_layers, n_pts), the host arrays it points to) of the state diffuse_source and
-    diffuse_jacobian take, checked."""
-    if not (_cuda_f64(A) and _cuda_f64(beam) and _cuda_f64(sun)) or A.dim() != 3 or beam.dim() != 2 or sun.dim() != 1:
+    diffuse_jacobian take, checked.  night=True (diffuse_thermal_source without a sun): beam and sun are None and not
+    looked at, mu0 is 0."""
+    lit = not night
+    if not _cuda_f64(A) or A.dim() != 3 or (lit and (not (_cuda_f64(beam) and _cuda_f64(sun)) or beam.dim() != 2 or sun.dim() != 1)):
         raise ValueError("A, beam and sun must be contiguous CUDA float64 tensors ([n_gas, n_layers, n_pts], "
                          "[n_layers + 1, n_pts], [n_pts])")
     n_gas, n_layers, n_pts = (int(s) for s in A.shape)
@@ -613,11 +615,11 @@ def _diffuse_state(A, V, ssa, asym, beam, sun, mu0, surface_albedo):
     ga, gp = _d(np.broadcast_to(np.asarray(asym, dtype=np.float64), (n_gas,)))
     if va.shape != (n_gas, n_layers):
         raise ValueError("V must be [n_gas, n_layers] = [%d, %d]" % (n_gas, n_layers))
-    if beam.shape != (n_layers + 1, n_pts) or sun.shape[0] != n_pts:
+    if lit and (beam.shape != (n_layers + 1, n_pts) or sun.shape[0] != n_pts):
         raise ValueError("beam must be [n_layers + 1, n_pts] and sun [n_pts] on A's %d grid points" % n_pts)
     d = _lib.DiffuseDesc()
     d.n_gas, d.n_layers, d.v, d.ssa, d.asym = n_gas, n_layers, vp, sp, gp
-    d.mu0, d.surface_albedo = float(mu0), float(surface_albedo)
+    d.mu0, d.surface_albedo = float(mu0) if lit else 0.0, float(surface_albedo)
     return d, (n_gas, n_layers, n_pts), (va, sa, ga)
 
 
@@ -732,6 +734,61 @@ def diffuse_source(A, V, ssa, asym, beam, sun, mu0, surface_albedo=0.0, out_gas=
     check(lib.sr_diffuse_source_rows_dev(C.byref(d), ptr(A), ptr(beam), ptr(sun), n_pts, -1 if out_gas is None else int(out_gas),
                                          int(bool(accumulate)), ptr(out), ptr(J), ptr(F), _stream_ptr()),
           "sr_diffuse_source_rows_dev")
+    res = tuple(t for t in (out, J, F) if t is not None)
+    return res[0] if len(res) == 1 else res
+
+
+def diffuse_thermal_source(A, V, ssa, asym, temps, grid, t_surface=0.0, beam=None, sun=None, mu0=0.0, surface_albedo=0.0,
+                           out_gas=None, out=None, accumulate=False, own_emission=False, mean_intensity=False, fluxes=False,
+                           g_lo=0):
+    """Thermal emission as a source of the two-stream diffuse field (sr_diffuse_thermal_rows_dev; the build's own
+    definition): diffuse_source's solve with, per layer, the isotropic source 2 pi co B(nu, T_l) -- the
+    layer emits (2 pi / sqrt3) B (1 - R - T) both ways, Kirchhoff's law; exactly 0 where the layer has no absorber -- and
+    a Lambertian surface of emissivity 1 - surface_albedo at t_surface below (0: none).  beam, sun and mu0 as
+    diffuse_source takes them add the sun's sources to the same solve (one walk of the layers for both); beam=None and
+    sun=None is thermal emission alone, the night side: the call reads A only.
+
+        own_emission=False:  emi[l] (+)= ssa_G (1 - f_G) A[G, l] J[l]
+        own_emission=True:   emi[l] (+)= A[G, l] ((1 - ssa_G) B(nu, T_l) + ssa_G (1 - f_G) J[l])
+
+    the second the scatterer's complete thermal row, in the place of a TableGas's emi = abs B (which emits as if all of
+    the extinction were absorption).  For asym > 0 the forward peak's share of the line-of-sight source is left out, as
+    in diffuse_source.  A, V, ssa, asym, surface_albedo, out_gas, out, accumulate, mean_intensity, fluxes and the result:
+    as diffuse_source.  temps: host [n_layers] > 0; grid: the scene's spectral grid (grid_params), point j of A is grid
+    point g_lo + j.  B is evaluated in the kernel as AbsorberTable.layers evaluates it.  Every Jacobian treats the rows
+    as coefficients: their derivatives are not built."""
+    # the rules among the arguments first, then the grid, then the tensors: what needs no device is refused without one
+    if (beam is None) != (sun is None):
+        raise ValueError("beam and sun: both (sunlight and thermal emission) or neither (thermal emission alone)")
+    if out_gas is None:
+        if out is not None or accumulate or own_emission:
+            raise ValueError("out=, accumulate= and own_emission= belong to the rows of out_gas=")
+        if not (mean_intensity or fluxes):
+            raise ValueError("nothing asked for: out_gas=, mean_intensity=True or fluxes=True")
+    elif out is None and accumulate:
+        raise ValueError("accumulate=True adds to out=...")
+    w0, step, n_grid = grid_params(grid)
+    ta, tp = _d(np.asarray(temps, dtype=np.float64))
+    if ta.ndim != 1 or int(g_lo) < 0 or int(g_lo) >= n_grid:
+        raise ValueError("temps must be [n_layers] and g_lo a point of the grid's %d" % n_grid)
+    d, (n_gas, n_layers, n_pts), keep = _diffuse_state(A, V, ssa, asym, beam, sun, mu0, surface_albedo, night=beam is None)
+    if ta.shape != (n_layers,):
+        raise ValueError("temps must be [n_layers] = [%d]" % n_layers)
+    if int(g_lo) + n_pts > n_grid:
+        raise ValueError("the points g_lo .. g_lo + %d lie outside the grid's %d" % (n_pts, n_grid))
+    th = _lib.DiffuseThermalDesc()
+    th.temps, th.t_surface, th.w0, th.step, th.g_lo, th.own_emission = tp, float(t_surface), w0, step, int(g_lo), int(bool(own_emission))
+    if out_gas is not None:
+        if out is None:
+            out = torch.empty((n_layers, n_pts), dtype=torch.float64, device="cuda")
+        elif not _cuda_f64(out) or out.shape != (n_layers, n_pts):
+            raise ValueError("out must be a contiguous CUDA float64 [n_layers, n_pts]")
+    J = torch.empty((n_layers, n_pts), dtype=torch.float64, device="cuda") if mean_intensity else None
+    F = torch.empty((2, n_layers + 1, n_pts), dtype=torch.float64, device="cuda") if fluxes else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    check(lib.sr_diffuse_thermal_rows_dev(C.byref(d), C.byref(th), ptr(A), ptr(beam), ptr(sun), n_pts,
+                                          -1 if out_gas is None else int(out_gas), int(bool(accumulate)), ptr(out), ptr(J), ptr(F),
+                                          _stream_ptr()), "sr_diffuse_thermal_rows_dev")
     res = tuple(t for t in (out, J, F) if t is not None)
     return res[0] if len(res) == 1 else res
 

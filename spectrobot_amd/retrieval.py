@@ -220,6 +220,37 @@ class Sun(object):
         return key + (True, self.surface_albedo) if self.multiple else key
 
 
+class ThermalScattering(object):
+    """Thermal emission as a source of the diffuse field of a LimbScene (engine.diffuse_thermal_source):
+    with it every TableGas(solar=...) of the scene is a thermal scatterer -- `albedo` its single-scattering albedo, `g` its
+    asymmetry parameter, g >= -0.5 -- with or without a Sun.  Such a gas's emission rows are then its own emission by
+    Kirchhoff's law, (1 - albedo) abs B, and the diffuse field of the layers' thermal emission (and, under a
+    Sun(multiple=True), of the sunlight, in the same solve) scattered into the line of sight; order one of the sunlight
+    stays the single-scattering rows.  Without it such a gas emits abs B, as if all of its extinction were absorption.
+    surface_temperature [K]: a Lambertian surface of emissivity 1 - surface_albedo BELOW z[0] emits at it (None: nothing
+    below emits).  surface_albedo (0 .. 1) is the albedo of that surface; a Sun(multiple=True) of the same scene must
+    carry the same value.  The rows are held fixed under every Jacobian within one linearisation; their derivatives are
+    not built: a scene with it refuses diffuse_jacobian=True, a HazeOptics set and a TempProfile set.  The 3-D route,
+    LimbScene.sunlit_steps, does not look at it: its rows stay thermal abs B + the sun's."""
+
+    def __init__(self, surface_temperature=None, surface_albedo=0.0):
+        self.surface_temperature = None if surface_temperature is None else float(surface_temperature)
+        self.surface_albedo = float(surface_albedo)
+        if self.surface_temperature is not None and not (np.isfinite(self.surface_temperature) and self.surface_temperature > 0.0):
+            raise ValueError("surface_temperature is a temperature in K (> 0), or None for no emitting surface")
+        if not 0.0 <= self.surface_albedo <= 1.0:
+            raise ValueError("surface_albedo is a Lambertian albedo in [0, 1]")
+
+    def key(self):
+        return (self.surface_temperature, self.surface_albedo)
+
+
+def _refuse_thermal_scattering(scene, what):
+    if getattr(scene, "thermal_scattering", None) is not None:
+        raise ValueError("%s on a scene with thermal_scattering: the tangent kernels do not know the thermal source of the "
+                         "diffuse field (its rows are held fixed within a linearisation, their derivatives are not built)" % what)
+
+
 def _refuse_many_slots(scene, who):
     """The drivers whose kernels keep four gas slots refuse a larger scene before any device call."""
     limit = engine.max_gases(folded=True)
@@ -446,12 +477,25 @@ class LimbScene(object):
     (coefficients() ends with one solar pass over the layer rows, solar_pass); the tangent-SZA approximation -- the
     reference's use_tangent_sza = True: mu = cos(sza) on every row -- and Theta = 180 deg - phase.  A per-step SZA is
     the 3-D route: engine.solar_source on geometry.limb_los_3d's rows, and sunlit_steps(L3) makes those rows -- with the
-    diffuse field under every step's own SZA (engine.diffuse_source_columns) for a Sun(multiple=True)."""
+    diffuse field under every step's own SZA (engine.diffuse_source_columns) for a Sun(multiple=True).
+    thermal_scattering: a ThermalScattering.  With it every TableGas(solar=...) is a thermal scatterer, with or without a
+    sun, and its emission rows are made by thermal_pass: [order-one solar rows +] one engine.diffuse_thermal_source call
+    with own_emission=True, which carries beam and sun as well under a Sun(multiple=True).  None runs none of it."""
 
     def __init__(self, grid, z, temps, press, gases, bands_nm, widths_nm, R=2575.0, n_sub=3, out_units="Wm2", ils=None,
-                 sun=None):
+                 sun=None, thermal_scattering=None):
         self.grid = np.asarray(grid, dtype=float)
         self.sun = sun
+        self.thermal_scattering = thermal_scattering    # a ThermalScattering: the solar gases are thermal scatterers (thermal_pass)
+        if thermal_scattering is not None:
+            for g in gases:
+                if getattr(g, "solar", None) is not None and g.solar["g"] < -0.5:
+                    raise ValueError("thermal_scattering: gas %r has g = %g, the two-stream solve takes g >= -0.5" % (g.name, g.solar["g"]))
+                if getattr(g, "solar", None) is not None and not g.source:
+                    raise ValueError("thermal_scattering: gas %r is a thermal scatterer, source=False contradicts it" % g.name)
+            if sun is not None and getattr(sun, "multiple", False) and sun.surface_albedo != thermal_scattering.surface_albedo:
+                raise ValueError("thermal_scattering: its surface_albedo %g and the Sun(multiple=True)'s %g describe one surface"
+                                 % (thermal_scattering.surface_albedo, sun.surface_albedo))
         self.solar_frozen = False   # True: solar rows that exist are kept whatever moves -- the linearisation's own assumption,
                                     # for finite differences that are to see what the Jacobians see (a rebuilt thermal pair
                                     # still gets its solar rows again)
@@ -530,6 +574,8 @@ class LimbScene(object):
         A scene that was asked for the solar rows alone (keep_solar_rows) keeps g.solar_rows = sca S of every solar gas,
         made by an overwrite call, and its emission rows are thermal + those -- the same sum the accumulating call
         forms (solar_attenuation_jacobian's input).  The same rule of when nothing is redone."""
+        if self.thermal_scattering is not None:
+            return self.thermal_pass(g_lo, g_hi)
         solar = self.solar_gases()
         if not solar:
             return
@@ -559,6 +605,73 @@ class LimbScene(object):
         # (the tables themselves are kept beside the key: an id in it stays theirs while they live here.  The key knows a
         # table by identity, as coefficient_stack does: every rebuild in this package makes new tensors; a caller who
         # overwrites a table IN PLACE sets scene._solar_key = None)
+        self._solar_key, self._solar_tabs = key, tabs
+
+    def thermal_scatterers(self):
+        return [g for g in self.gases if getattr(g, "solar", None) is not None] if self.thermal_scattering is not None else []
+
+    def thermal_pass(self, g_lo, g_hi):
+        """The emission rows of the thermal scatterers (thermal_scattering): [order-one solar rows, if a sun] + one
+        engine.diffuse_thermal_source call with own_emission=True -- the gas's own emission (1 - albedo) abs B and the
+        diffuse field scattered into the line of sight; under a Sun(multiple=True) that call carries beam and sun too, so
+        that the layers are walked once for both sources.  With one scatterer the cached thermal emi of the gas is not
+        used: the kernel forms B itself.  With several the field is solved once (mean_intensity=True, no rows) and every
+        gas gets its order-one rows + (1 - albedo) times its cached thermal emi -- the table's own abs B, the same Planck
+        evaluation bit for bit, scaled by Kirchhoff's law: the one place that pair's emi is read -- + one torch.addcmul of
+        J with ssa_G (1 - f_G) of the gas's own slot.  Held fixed by every Jacobian within one
+        linearisation; the rule of when nothing is redone is solar_pass's (solar_frozen, the key -- which here also
+        holds the layer temperatures and the ThermalScattering's values)."""
+        scat = self.thermal_scatterers()
+        if not scat:
+            return
+        import torch
+        ts, sun = self.thermal_scattering, self.sun
+        rows = self.keep_solar_rows and sun is not None
+        done = all(g.coeffs is not g.thermal and (not rows or getattr(g, "solar_rows", None) is not None) for g in scat)
+        if done and self.solar_frozen:
+            return
+        tabs = [(g.thermal if g in scat else g.coeffs)[0] for g in self.gases]
+        optics = tuple((float(g.solar["albedo"]), float(g.solar["g"])) for g in scat)
+        key = (tuple(np.asarray(g.vmr, float).tobytes() for g in self.gases), tuple(float(g.iso_ratio) for g in self.gases),
+               tuple(id(t) for t in tabs), None if sun is None else sun.key(), int(g_lo), int(g_hi), optics, self.temps.tobytes(),
+               ts.key()) + (("rows",) if rows else ())
+        if done and getattr(self, "_solar_key", None) == key:
+            return
+        A = torch.stack(tabs).contiguous()
+        order_one = {}
+        sun_t = None
+        if sun is not None:     # order one: the single-scattering rows, with the exact phase function and the unscaled beam
+            U, lit = geometry.solar_columns(self.z, self.nd, [g.vmr for g in self.gases], self.shell_midpoints(), sun.mu, R=self.R,
+                                            n_sub=self.n_sub, col_scale=[g.iso_ratio for g in self.gases])
+            sun_t = torch.as_tensor(sun.irradiance[g_lo:g_hi], device="cuda").contiguous()
+            for g in scat:
+                order_one[g.name] = engine.solar_source(A, U, self.solar_weights(g, lit), g.thermal[0], sun_t)
+                if rows:
+                    g.solar_rows = order_one[g.name]
+        kw = dict(t_surface=0.0 if ts.surface_temperature is None else ts.surface_temperature, surface_albedo=ts.surface_albedo,
+                  g_lo=g_lo)
+        if sun is not None and sun.multiple:
+            V, ssa, asym, beam = self.diffuse_inputs(scat, A, sun_t)
+            kw.update(beam=beam, sun=sun_t, mu0=sun.mu)
+        else:
+            ssa, asym, iso, _, _ = self.diffuse_geometry(scat)
+            V = geometry.vertical_columns(self.z, self.nd, [g.vmr for g in self.gases], R=self.R, n_sub=self.n_sub, col_scale=iso)
+        if len(scat) == 1:
+            g = scat[0]
+            emi = order_one.get(g.name)
+            if emi is not None and rows:
+                emi = emi.clone()
+            emi = engine.diffuse_thermal_source(A, V, ssa, asym, self.temps, self.grid, out_gas=self.gases.index(g), out=emi,
+                                                accumulate=emi is not None, own_emission=True, **kw)
+            g.coeffs = (g.thermal[0], emi)
+        else:
+            J = engine.diffuse_thermal_source(A, V, ssa, asym, self.temps, self.grid, mean_intensity=True, **kw)
+            for g in scat:
+                i = self.gases.index(g)
+                emi = order_one.get(g.name)
+                emi = g.thermal[1] * float(1.0 - ssa[i]) if emi is None else torch.add(emi, g.thermal[1], alpha=float(1.0 - ssa[i]))
+                emi.addcmul_(A[i], J, value=float(ssa[i] * (1.0 - max(asym[i], 0.0) ** 2)))
+                g.coeffs = (g.thermal[0], emi)
         self._solar_key, self._solar_tabs = key, tabs
 
     def diffuse_geometry(self, solar):
@@ -695,6 +808,7 @@ class LimbScene(object):
         multiple-scattering scene is both.  limb_rays_layer_jacobian is a four-gas call."""
         import torch
         solar = self.solar_gases()
+        _refuse_thermal_scattering(self, "diffuse_jacobian")
         state = self.diffuse_state
         if not solar or not getattr(self.sun, "multiple", False) or state is None:
             raise ValueError("diffuse_jacobian needs a Sun(multiple=True), a solar gas and keep_diffuse_state = True before the solar pass")
@@ -731,6 +845,7 @@ class LimbScene(object):
         needed.  limb_rays_layer_jacobian is a four-gas call."""
         import torch
         solar = self.solar_gases()
+        _refuse_thermal_scattering(self, "optics_jacobian (a HazeOptics set)")
         multiple = bool(getattr(self.sun, "multiple", False))
         params = list(params)
         if not solar or not params:
@@ -977,6 +1092,7 @@ class LimbScene(object):
         (layer_coefficients(derivative=True)); a plain Gas costs two coefficient ops (engine.coefficients_dT, scheme
         "forward", on the coefficients just computed); a TableGas gives its analytic derivatives with its pair, in one
         launch, and the tables folded into a plain Gas add theirs to that gas's two pairs."""
+        _refuse_thermal_scattering(self, "temperature_derivatives (a TempProfile set)")
         n_grid = len(self.grid)
         for g in self.gases:
             key = (self.temps.tobytes(), self.press.tobytes()) + tuple(t.cache_key(self, 0, n_grid) for t in self.folded_into(g))
@@ -1625,6 +1741,14 @@ def inversion_state(scene, bayes_set, pixels, chi_threshold=0.01, max_it=10, lam
     ValueError.  Without such a set no statement of an iteration changes."""
     pixels = sorted(pixels, key=lambda x: x.limb_tg_alt)
     with_fov = _closed_form_fov(pixels, fov_closed_form, "inversion_state")
+    if getattr(scene, "thermal_scattering", None) is not None:
+        if diffuse_jacobian:
+            _refuse_thermal_scattering(scene, "inversion_state(diffuse_jacobian=True)")
+        for name, st in bayes_set.sets.items():
+            if isinstance(st, HazeOptics):
+                _refuse_thermal_scattering(scene, "the HazeOptics set %r" % name)
+            if isinstance(st, TempProfile):
+                _refuse_thermal_scattering(scene, "the TempProfile set %r" % name)
     solar_att = bool(solar_attenuation) and bool(scene.solar_gases())
     if solar_att:
         if len(scene.gases) > engine.max_gases(folded=True):
