@@ -4219,7 +4219,7 @@ int sr_solar_jacobian_rows_dev(const sr_solar_jac_desc *desc, const double *tab_
   return pk.slot().mark(st);
 }
 
-// The two-stream diffuse source of coefficient rows (sr_diffuse_source.inc).  The upward sweep's workspace, four doubles
+// The two-stream diffuse field of coefficient rows (sr_diffuse_source.inc).  The upward sweep's workspace, four doubles
 // per (layer, point), comes from a grow-only buffer per (thread, device); a call whose workspace would pass
 // kDiffuseWsBytes is made in point chunks, one launch after the other on `stream`.
 constexpr size_t kDiffuseWsBytes = (size_t)256 << 20;
@@ -4261,53 +4261,75 @@ static DiffuseChunks diffuse_chunks(size_t per, int64_t n_pts, int n_tiles) {
   return DiffuseChunks{chunk, tiles};
 }
 
-int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_abs, const double *beam, const double *sun,
-                               int64_t n_pts, int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out,
-                               void *stream) {
-  if (!desc || !desc->v || !desc->ssa || !desc->asym || !tab_abs || !beam || !sun) return SR_ERR_ARG;
+// What the three forward entries ask of their arguments alike, in the order of their refusals: the pointers and sizes
+// (with `bad`, the entry's own argument rules), the limits (with `over`, the entry's own), out_gas against emi_out, and
+// that something is asked for.
+static int check_diffuse_field_args(const sr_diffuse_desc *desc, const double *tab_abs, int64_t n_pts, bool bad, bool over,
+                                    int out_gas, const double *emi_out, const double *j_out, const double *flux_out) {
+  if (!desc || !desc->v || !desc->ssa || !desc->asym || !tab_abs || bad) return SR_ERR_ARG;
   if (desc->n_gas <= 0 || desc->n_layers <= 0 || n_pts <= 0) return SR_ERR_ARG;
-  if (desc->n_gas > kDiffuseGases || desc->n_layers > SR_MAX_ABS_ROWS || n_pts > kSolarMaxPts) return SR_ERR_LIMIT;
-  const int n_gas = desc->n_gas, n_layers = desc->n_layers;
-  if (out_gas < -1 || out_gas >= n_gas || (out_gas < 0) != (emi_out == nullptr)) return SR_ERR_ARG;
+  if (desc->n_gas > kDiffuseGases || desc->n_layers > SR_MAX_ABS_ROWS || n_pts > kSolarMaxPts || over) return SR_ERR_LIMIT;
+  if (out_gas < -1 || out_gas >= desc->n_gas || (out_gas < 0) != (emi_out == nullptr)) return SR_ERR_ARG;
   if (!emi_out && !j_out && !flux_out) return SR_ERR_ARG;
-  double coef[3 * kDiffuseGases], w_out;
-  int rc = check_diffuse_desc(desc, true, out_gas, coef, &w_out);
-  if (rc) return rc;
+  return SR_OK;
+}
+
+// What the three forward entries share once their arguments are checked: the workspace of `per` bytes per point, the
+// staging of v and coef with the parts the entry adds (parts(pk)), and the point chunks, one launch after the other on
+// `stream`: launch(pk, p_lo, p_hi, ws, chunk, v, coef, st).  ring is the entry's own, so that no entry waits for
+// another's slots.
+using DiffuseLaunch = std::function<int(StagePack &, int, int, double *, int, const double *, const double *, hipStream_t)>;
+static int diffuse_field_run(const sr_diffuse_desc *desc, const double (&coef)[3 * kDiffuseGases], size_t per, int64_t n_pts,
+                             StagerRing &ring, void *stream, const std::function<void(StagePack &)> &parts,
+                             const DiffuseLaunch &launch) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int chunk = diffuse_chunks((size_t)32 * n_layers, n_pts, 1).chunk;
+  const int chunk = diffuse_chunks(per, n_pts, 1).chunk;
   int dev = 0;
   HIPCHK(hipGetDevice(&dev));
   DevBuf &ws = diffuse_workspace(dev);
-  rc = ws.ensure((size_t)32 * n_layers * chunk);
+  int rc = ws.ensure(per * (size_t)chunk);
   if (rc) return rc;
-  static thread_local StagerRing ring;
   StagePack pk(ring.take());
-  const auto p_v = pk.copy(desc->v, (size_t)n_gas * n_layers), p_c = pk.copy(coef, (size_t)3 * kDiffuseGases);
+  const auto p_v = pk.copy(desc->v, (size_t)desc->n_gas * desc->n_layers), p_c = pk.copy(coef, (size_t)3 * kDiffuseGases);
+  parts(pk);
   rc = pk.stage(st);
   if (rc) return rc;
   for (int64_t p_lo = 0; p_lo < n_pts; p_lo += chunk) {
     const int p_hi = (int)std::min<int64_t>(n_pts, p_lo + chunk);
-    LAUNCHCHK(launch_diffuse_source(tab_abs, n_gas, n_layers, (int)n_pts, (int)p_lo, p_hi, pk.dev(p_v), pk.dev(p_c), beam, sun,
-                                    desc->mu0, desc->surface_albedo, out_gas, w_out, ws.as<double>(), chunk, accumulate != 0,
-                                    emi_out, j_out, flux_out, st));
+    LAUNCHCHK(launch(pk, (int)p_lo, p_hi, ws.as<double>(), chunk, pk.dev(p_v), pk.dev(p_c), st));
   }
   return pk.slot().mark(st);
 }
 
-// Thermal emission as a source of the same field (sr_diffuse_thermal.inc), alone (beam and sun NULL: desc's mu0 is not
-// read) or with the sun's.  Workspace, point chunks, staging and the one-stream rule are the sibling's; the layers'
-// temperatures are staged with v.
+int sr_diffuse_source_rows_dev(const sr_diffuse_desc *desc, const double *tab_abs, const double *beam, const double *sun,
+                               int64_t n_pts, int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out,
+                               void *stream) {
+  int rc = check_diffuse_field_args(desc, tab_abs, n_pts, !beam || !sun, false, out_gas, emi_out, j_out, flux_out);
+  if (rc) return rc;
+  const int n_gas = desc->n_gas, n_layers = desc->n_layers;
+  double coef[3 * kDiffuseGases], w_out;
+  rc = check_diffuse_desc(desc, true, out_gas, coef, &w_out);
+  if (rc) return rc;
+  static thread_local StagerRing ring;
+  return diffuse_field_run(
+      desc, coef, (size_t)32 * n_layers, n_pts, ring, stream, [](StagePack &) {},
+      [&](StagePack &, int p_lo, int p_hi, double *ws, int chunk, const double *v, const double *c, hipStream_t st) {
+        return launch_diffuse_field(tab_abs, n_gas, n_layers, (int)n_pts, p_lo, p_hi, v, c, nullptr, beam, sun, desc->mu0,
+                                    desc->surface_albedo, 0.0, 0.0, 0.0, 0, false, out_gas, ws, chunk, accumulate != 0, emi_out,
+                                    j_out, flux_out, st);
+      });
+}
+
+// Thermal emission as a source of the same field, alone (beam and sun NULL: desc's mu0 is not read) or with the sun's.
+// The layers' temperatures are staged with v.
 int sr_diffuse_thermal_rows_dev(const sr_diffuse_desc *desc, const sr_diffuse_thermal_desc *th, const double *tab_abs,
                                 const double *beam, const double *sun, int64_t n_pts, int out_gas, int accumulate,
                                 double *emi_out, double *j_out, double *flux_out, void *stream) {
-  if (!desc || !desc->v || !desc->ssa || !desc->asym || !tab_abs || !th || !th->temps) return SR_ERR_ARG;
-  if ((beam == nullptr) != (sun == nullptr)) return SR_ERR_ARG;
-  if (desc->n_gas <= 0 || desc->n_layers <= 0 || n_pts <= 0 || th->g_lo < 0) return SR_ERR_ARG;
-  if (desc->n_gas > kDiffuseGases || desc->n_layers > SR_MAX_ABS_ROWS || n_pts > kSolarMaxPts || th->g_lo > INT32_MAX - n_pts)
-    return SR_ERR_LIMIT;
+  const bool bad = !th || !th->temps || (beam == nullptr) != (sun == nullptr) || th->g_lo < 0;
+  int rc = check_diffuse_field_args(desc, tab_abs, n_pts, bad, !bad && th->g_lo > INT32_MAX - n_pts, out_gas, emi_out, j_out,
+                                    flux_out);
+  if (rc) return rc;
   const int n_gas = desc->n_gas, n_layers = desc->n_layers;
-  if (out_gas < -1 || out_gas >= n_gas || (out_gas < 0) != (emi_out == nullptr)) return SR_ERR_ARG;
-  if (!emi_out && !j_out && !flux_out) return SR_ERR_ARG;
   if (th->own_emission && !emi_out) return SR_ERR_ARG;
   if (!(th->t_surface >= 0.0) || !std::isfinite(th->t_surface) || !std::isfinite(th->w0) || !std::isfinite(th->step)) return SR_ERR_ARG;
   for (int l = 0; l < n_layers; ++l)
@@ -4315,79 +4337,57 @@ int sr_diffuse_thermal_rows_dev(const sr_diffuse_desc *desc, const sr_diffuse_th
   sr_diffuse_desc state = *desc;
   if (!beam) state.mu0 = 0.0;
   double coef[3 * kDiffuseGases], w_out;
-  int rc = check_diffuse_desc(&state, true, out_gas, coef, &w_out);
-  if (rc) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int chunk = diffuse_chunks((size_t)32 * n_layers, n_pts, 1).chunk;
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  DevBuf &ws = diffuse_workspace(dev);
-  rc = ws.ensure((size_t)32 * n_layers * chunk);
+  rc = check_diffuse_desc(&state, true, out_gas, coef, &w_out);
   if (rc) return rc;
   static thread_local StagerRing ring;
-  StagePack pk(ring.take());
-  const auto p_v = pk.copy(desc->v, (size_t)n_gas * n_layers), p_c = pk.copy(coef, (size_t)3 * kDiffuseGases);
-  const auto p_t = pk.copy(th->temps, (size_t)n_layers);
-  rc = pk.stage(st);
-  if (rc) return rc;
-  for (int64_t p_lo = 0; p_lo < n_pts; p_lo += chunk) {
-    const int p_hi = (int)std::min<int64_t>(n_pts, p_lo + chunk);
-    LAUNCHCHK(launch_diffuse_thermal(tab_abs, n_gas, n_layers, (int)n_pts, (int)p_lo, p_hi, pk.dev(p_v), pk.dev(p_c), pk.dev(p_t),
-                                     beam, sun, state.mu0, state.surface_albedo, th->t_surface, th->w0, th->step, (int)th->g_lo,
-                                     th->own_emission != 0, out_gas, ws.as<double>(), chunk, accumulate != 0,
-                                     emi_out, j_out, flux_out, st));
-  }
-  return pk.slot().mark(st);
+  StagePack::Part<double> p_t{};
+  return diffuse_field_run(
+      desc, coef, (size_t)32 * n_layers, n_pts, ring, stream, [&](StagePack &pk) { p_t = pk.copy(th->temps, (size_t)n_layers); },
+      [&](StagePack &pk, int p_lo, int p_hi, double *ws, int chunk, const double *v, const double *c, hipStream_t st) {
+        return launch_diffuse_field(tab_abs, n_gas, n_layers, (int)n_pts, p_lo, p_hi, v, c, pk.dev(p_t), beam, sun, state.mu0,
+                                    state.surface_albedo, th->t_surface, th->w0, th->step, (int)th->g_lo, th->own_emission != 0,
+                                    out_gas, ws, chunk, accumulate != 0, emi_out, j_out, flux_out, st);
+      });
 }
 
-// The same source for several columns of illumination, and the rows of LOS steps (sr_diffuse_columns.inc).  The workspace
-// is the source's, 2 + 2 NC doubles per (layer, point) for the instance NC the call runs; the plan -- mu0 and col_w padded
-// to NC, the rows sorted by layer -- is diffuse_columns_plan's (sr_solar_plan.hpp), staged with v and the coefficients.
+// The solar field for several columns of illumination, and the rows of LOS steps (sr_diffuse_columns.inc).  The workspace
+// takes 2 + 2 NC doubles per (layer, point) for the instance NC the call runs; the plan -- mu0 and col_w padded to NC, the
+// rows sorted by layer -- is diffuse_columns_plan's (sr_solar_plan.hpp), staged with v and the coefficients.
 int sr_diffuse_source_columns_dev(const sr_diffuse_desc *desc, const sr_diffuse_columns_desc *cols, const double *tab_abs,
                                   const double *beam, const double *sun, int64_t n_pts, const double *sca_abs, int n_src,
                                   int out_gas, int accumulate, double *emi_out, double *j_out, double *flux_out, void *stream) {
-  if (!desc || !desc->v || !desc->ssa || !desc->asym || !cols || !cols->mu0 || !tab_abs || !beam || !sun) return SR_ERR_ARG;
-  if (desc->n_gas <= 0 || desc->n_layers <= 0 || n_pts <= 0 || cols->n_col <= 0 || cols->n_rows < 0) return SR_ERR_ARG;
-  if (cols->n_rows > 0 && (!cols->col_w || !cols->row_layer || !cols->src_row || !sca_abs || n_src <= 0)) return SR_ERR_ARG;
-  if (desc->n_gas > kDiffuseGases || desc->n_layers > SR_MAX_ABS_ROWS || n_pts > kSolarMaxPts ||
-      cols->n_col > SR_MAX_DIFFUSE_COLUMNS || cols->n_rows > SR_MAX_ABS_ROWS)
-    return SR_ERR_LIMIT;
+  const bool bad = !cols || !cols->mu0 || !beam || !sun || cols->n_col <= 0 || cols->n_rows < 0 ||
+                   (cols->n_rows > 0 && (!cols->col_w || !cols->row_layer || !cols->src_row || !sca_abs || n_src <= 0));
+  const bool over = !bad && (cols->n_col > SR_MAX_DIFFUSE_COLUMNS || cols->n_rows > SR_MAX_ABS_ROWS);
+  int rc = check_diffuse_field_args(desc, tab_abs, n_pts, bad, over, out_gas, emi_out, j_out, flux_out);
+  if (rc) return rc;
   const int n_gas = desc->n_gas, n_layers = desc->n_layers, n_col = cols->n_col, n_rows = cols->n_rows;
-  if (out_gas < -1 || out_gas >= n_gas || (out_gas < 0) != (emi_out == nullptr) || (n_rows == 0) != (emi_out == nullptr)) return SR_ERR_ARG;
-  if (!emi_out && !j_out && !flux_out) return SR_ERR_ARG;
+  if ((n_rows == 0) != (emi_out == nullptr)) return SR_ERR_ARG;
   sr_diffuse_desc state = *desc;
   state.mu0 = 0.0; // (desc->mu0 is not read: the columns bring their own)
   double coef[3 * kDiffuseGases], w_out;
-  int rc = check_diffuse_desc(&state, true, out_gas, coef, &w_out);
+  rc = check_diffuse_desc(&state, true, out_gas, coef, &w_out);
   if (rc) return rc;
   std::vector<double> mu0p, wp;
   std::vector<int> row_off, row_ix;
   if (!diffuse_columns_plan(cols->mu0, cols->col_w, cols->row_layer, cols->src_row, n_col, n_rows, n_layers, n_src, w_out == 0.0,
                             accumulate != 0, mu0p, wp, row_off, row_ix))
     return SR_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t per = (size_t)8 * (2 + 2 * diffuse_columns_instance(n_col)) * n_layers;
-  const int chunk = diffuse_chunks(per, n_pts, 1).chunk;
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  DevBuf &ws = diffuse_workspace(dev);
-  rc = ws.ensure(per * (size_t)chunk);
-  if (rc) return rc;
   static thread_local StagerRing ring;
-  StagePack pk(ring.take());
-  const auto p_v = pk.copy(desc->v, (size_t)n_gas * n_layers), p_c = pk.copy(coef, (size_t)3 * kDiffuseGases);
-  const auto p_mu = pk.copy(mu0p.data(), mu0p.size()), p_w = pk.copy(wp.data(), wp.size(), 1);
-  const auto p_off = pk.copy(row_off.data(), row_off.size()), p_ix = pk.copy(row_ix.data(), row_ix.size(), 1);
-  const auto p_src = pk.copy(cols->src_row, (size_t)n_rows, 1);
-  rc = pk.stage(st);
-  if (rc) return rc;
-  for (int64_t p_lo = 0; p_lo < n_pts; p_lo += chunk) {
-    const int p_hi = (int)std::min<int64_t>(n_pts, p_lo + chunk);
-    LAUNCHCHK(launch_diffuse_columns(tab_abs, n_gas, n_layers, (int)n_pts, (int)p_lo, p_hi, pk.dev(p_v), pk.dev(p_c), beam, n_col, sun,
-                                     pk.dev(p_mu), desc->surface_albedo, w_out, pk.dev(p_off), pk.dev(p_ix), pk.dev(p_src),
-                                     pk.dev(p_w), sca_abs, ws.as<double>(), chunk, accumulate != 0, emi_out, j_out, flux_out, st));
-  }
-  return pk.slot().mark(st);
+  StagePack::Part<double> p_mu{}, p_w{};
+  StagePack::Part<int> p_off{}, p_ix{}, p_src{};
+  return diffuse_field_run(
+      desc, coef, (size_t)8 * (2 + 2 * diffuse_columns_instance(n_col)) * n_layers, n_pts, ring, stream,
+      [&](StagePack &pk) {
+        p_mu = pk.copy(mu0p.data(), mu0p.size()), p_w = pk.copy(wp.data(), wp.size(), 1);
+        p_off = pk.copy(row_off.data(), row_off.size()), p_ix = pk.copy(row_ix.data(), row_ix.size(), 1);
+        p_src = pk.copy(cols->src_row, (size_t)n_rows, 1);
+      },
+      [&](StagePack &pk, int p_lo, int p_hi, double *ws, int chunk, const double *v, const double *c, hipStream_t st) {
+        return launch_diffuse_columns(tab_abs, n_gas, n_layers, (int)n_pts, p_lo, p_hi, v, c, beam, n_col, sun, pk.dev(p_mu),
+                                      desc->surface_albedo, w_out, pk.dev(p_off), pk.dev(p_ix), pk.dev(p_src), pk.dev(p_w), sca_abs,
+                                      ws, chunk, accumulate != 0, emi_out, j_out, flux_out, st);
+      });
 }
 
 // What the two Jacobian entries share once their arguments are checked: par_slot's check, the workspace, the staging and

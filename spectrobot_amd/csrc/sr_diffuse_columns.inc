@@ -1,5 +1,5 @@
 // sr_diffuse_columns.inc -- sr_diffuse_columns_kernel.  Included by sr_solar_source.hip inside namespace sr, behind
-// sr_diffuse_source.inc (whose diffuse_sums and diffuse_boundary it uses), and by the host build
+// sr_diffuse_source.inc (whose diffuse_sums, diffuse_operators and diffuse_boundary it uses), and by the host build
 // tools/diffuse_columns_host.  Nothing else includes it.
 
 // The two-stream diffuse source of sr_diffuse_source.inc for NC columns of illumination -- (mu0_c, beam_c), c < NC -- over
@@ -27,34 +27,14 @@
 // (kZeroRow, kDiffuseColumns and the host's plan diffuse_columns_plan: sr_solar_plan.hpp)
 struct DiffuseShared { double R, T, oneR, absb, fs, fd; bool live; };
 
-// the layer's operators that every column shares, from the three sums: diffuse_layer's without the source
+// the columns' source former: the operators every column shares (diffuse_operators) and the two factors, D left out
 __device__ __forceinline__ DiffuseShared diffuse_layer_shared(double sp, double al, double sg) {
   const double kSqrt3 = 1.7320508075688772;
-  DiffuseShared o;
-  const double dtau = sp + al;
-  if (!(dtau > 0.0)) {
-    o.R = 0.0, o.T = 1.0, o.oneR = 1.0, o.absb = 0.0, o.fs = 0.0, o.fd = 0.0, o.live = false;
-    return o;
-  }
-  o.live = true;
-  const double co = fmax(al / dtau, 0x1p-52), om = 1.0 - co;
-  const double g = sp > 0.0 ? sg / sp : 0.0;
-  const double d = kSqrt3 * co, s = kSqrt3 * (1.0 - om * g);
-  const double sd = sqrt(d), ss = sqrt(s), k = sd * ss, g1 = 0.5 * (s + d);
-  const double g2 = 0.5 * (kSqrt3 * om * (1.0 - g));
-  const double rg = 1.0 / (g1 + k);
-  const double Gm = g2 * rg, u = sd * (sd + ss) * rg;
-  const double x = k * dtau, e = exp(-x), m = -expm1(-x);
-  const double ge = 1.0 + Gm * e;
-  const double rden = 1.0 / ((u + Gm * m) * ge);
-  o.R = Gm * m * (1.0 + e) * rden;
-  o.T = e * u * (1.0 + Gm) * rden;
-  o.oneR = u * (1.0 + Gm * e * e) * rden;
-  o.absb = m * u * (1.0 - Gm * e) * rden;
-  const double oneT = m * (u + Gm * ge) * rden;
-  o.fs = om * (sd + ss) * rg * (m / sd) / ge;
-  o.fd = -(om * (kSqrt3 * g)) / s * (oneT + o.R);
-  return o;
+  if (!(sp + al > 0.0)) return DiffuseShared{0.0, 1.0, 1.0, 0.0, 0.0, 0.0, false};
+  const DiffuseOps p = diffuse_operators(sp, al, sg);
+  const double fs = p.om * (p.sd + p.ss) * p.rg * (p.m / p.sd) / p.ge;
+  const double fd = -(p.om * (kSqrt3 * p.g)) / p.s * (p.oneT + p.R);
+  return DiffuseShared{p.R, p.T, p.oneR, p.absb, fs, fd, true};
 }
 
 template <int NC, bool ACC>

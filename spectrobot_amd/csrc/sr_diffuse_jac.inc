@@ -2,7 +2,7 @@
 // namespace sr, behind sr_diffuse_source.inc (DiffuseLayer, diffuse_layer, diffuse_boundary, diffuse_sums), and by the
 // host build tools/diffuse_jacobian_host.  Nothing else includes it.
 
-// The diffuse rows in the Jacobians: the tangent of sr_diffuse_source_kernel's J along column parameters, and its product
+// The diffuse rows in the Jacobians: the tangent of sr_diffuse_field_kernel's solar J along column parameters, and its product
 // with the radiances' derivative to J.  The build's own definition -- the reference has no counterpart (DESIGN.md 4.11c).
 // In the notation of sr_diffuse_source.inc a parameter x_p moves a layer's three sums and its source through
 //   d t_g[l] = dv[p][g][l] A[g N + l][j],   d D_l = D_l dlnbeam[p][l][j],   d Ub_0 = Ub_0 dlnbeam[p][N][j]

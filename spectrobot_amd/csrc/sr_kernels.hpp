@@ -503,22 +503,17 @@ int launch_solar_source(const double *tab_abs, int n_k, int n_pts, const double 
 int launch_solar_jac(const double *tab_abs, int n_k, int n_pts, const double *du, int n_par, int n_rows, const int *tile_off,
                      const int *chunks, const double *q, int n_rays, const int *par_slot, bool accumulate, double *jac,
                      int n_jac_rows, hipStream_t st);
-// the two-stream diffuse source (sr_diffuse_source.inc) on the points [p_lo, p_hi) of the grid: v [n_gas][n_layers] and
-// coef [3][kDiffuseGases] (ssa (1 - f), 1 - ssa, ssa (asym - f); zeros beyond n_gas) staged device arrays, beam
-// [n_layers + 1][n_pts], ws [4][n_layers][ws_stride] with ws_stride >= the points rounded up to 256; emi_out (with out_gas
-// and w_out = ssa (1 - f) of that gas), j_out and flux_out may each be null.
-int launch_diffuse_source(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, const double *v,
-                          const double *coef, const double *beam, const double *sun, double mu0, double albedo, int out_gas,
-                          double w_out, double *ws, int ws_stride, bool accumulate, double *emi_out, double *j_out,
-                          double *flux_out, hipStream_t st);
-// thermal emission as a source of the same field (sr_diffuse_thermal.inc): the arguments above, temps [n_layers] staged with
-// v, the surface's temperature (0: none), the grid (w0, step, g_lo: point j has nu = w0 + (g_lo + j) step), own: the
-// scatterer's complete thermal row (its weights are coef's of out_gas).  beam and sun both null: the night instance.
-int launch_diffuse_thermal(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, const double *v,
-                           const double *coef, const double *temps, const double *beam, const double *sun, double mu0,
-                           double albedo, double t_surface, double w0, double step, int g_lo, bool own, int out_gas,
-                           double *ws, int ws_stride, bool accumulate, double *emi_out, double *j_out,
-                           double *flux_out, hipStream_t st);
+// the two-stream diffuse field (sr_diffuse_source.inc) on the points [p_lo, p_hi) of the grid: v [n_gas][n_layers], coef
+// [3][kDiffuseGases] (ssa (1 - f), 1 - ssa, ssa (asym - f); zeros beyond n_gas) and temps [n_layers] staged device arrays,
+// beam [n_layers + 1][n_pts], ws [4][n_layers][ws_stride] with ws_stride >= the points rounded up to 256; emi_out (with
+// out_gas, whose weights are coef's), j_out and flux_out may each be null.  temps null: the sun alone (t_surface, the grid
+// and own are not read); else the surface's temperature (0: none), the grid (w0, step, g_lo: point j has nu = w0 +
+// (g_lo + j) step), own: the scatterer's complete thermal row, and beam and sun both null: the night instance.  temps and
+// beam both null is refused.
+int launch_diffuse_field(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, const double *v,
+                         const double *coef, const double *temps, const double *beam, const double *sun, double mu0,
+                         double albedo, double t_surface, double w0, double step, int g_lo, bool own, int out_gas, double *ws,
+                         int ws_stride, bool accumulate, double *emi_out, double *j_out, double *flux_out, hipStream_t st);
 // the diffuse rows in the Jacobians (sr_diffuse_jac.inc) on the points [p_lo, p_hi) and the parameters [par_lo, par_hi):
 // dv [n_par][n_gas][n_layers], mask [n_par][2] (diffuse_jac_masks, sr_solar_plan.hpp), v and coef as above: staged device
 // arrays; dlnbeam [n_par][n_layers + 1][n_pts] or null; ws [tiles][3 + 4 kDiffuseJacPars][n_layers][ws_stride], tiles =

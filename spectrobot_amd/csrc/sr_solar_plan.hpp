@@ -13,7 +13,7 @@ namespace sr {
 constexpr int kSolarRows = 16; // rows of a tile: the MFMA's M
 constexpr int kSolarChunk = 4; // k per chunk: the MFMA's K
 constexpr int kSolarJacRays = 8; // NR: rays per block of sr_solar_jac_kernel (profiles/solar_jac_kernel_resources.txt)
-constexpr int kDiffuseGases = 8; // gas slots of sr_diffuse_source_kernel's loop (sr_diffuse_source.inc): n_gas above is refused
+constexpr int kDiffuseGases = 8; // gas slots of the diffuse kernels' loop (sr_diffuse_source.inc): n_gas above is refused
 constexpr int kDiffuseJacPars = 4; // NP: parameters per block of sr_diffuse_tangent_kernel and per thread of the contraction
 constexpr int kDiffuseOpt = 3 * kDiffuseGases + 1; // doubles per parameter of an optics direction: the coefficients' tangents, the albedo's
 constexpr int kDiffuseJacRays = 8; // NR: rays per thread of sr_diffuse_contract_kernel (profiles/diffuse_jacobian_kernel_resources.txt)

@@ -1,20 +1,20 @@
 // sr_solar_source.hip -- the solar subject's unit: the single-scattering solar source of coefficient rows
 // (sr_solar_source_rows_dev: sr_solar_source.inc) and the solar attenuation in the Jacobians (sr_solar_jacobian_rows_dev:
-// sr_solar_jac.inc), both on the tile product of sr_solar_tile.inc, and the two-stream diffuse source
-// (sr_diffuse_source_rows_dev: sr_diffuse_source.inc) and its tangent in the Jacobians (sr_diffuse_jacobian_rows_dev:
-// sr_diffuse_jac.inc) and the same source for several columns of illumination with the rows of LOS steps
-// (sr_diffuse_source_columns_dev: sr_diffuse_columns.inc), and thermal emission as a source of that field
-// (sr_diffuse_thermal_rows_dev: sr_diffuse_thermal.inc), each kernel's text and its launcher.  A translation unit of its own, compiled beside the others:
-// no other unit includes the kernels' text, and this one instantiates no other kernel.
+// sr_solar_jac.inc), both on the tile product of sr_solar_tile.inc, and the two-stream diffuse field under the sun, from
+// thermal emission or both (sr_diffuse_source_rows_dev, sr_diffuse_thermal_rows_dev: sr_diffuse_source.inc), its tangent in
+// the Jacobians (sr_diffuse_jacobian_rows_dev: sr_diffuse_jac.inc) and the solar field for several columns of illumination
+// with the rows of LOS steps (sr_diffuse_source_columns_dev: sr_diffuse_columns.inc), each kernel's text and its launcher.
+// A translation unit of its own, compiled beside the others: no other unit includes the kernels' text, and this one
+// instantiates no other kernel.
 //
 //   sr_solar_source_kernel<ACC, TRANS>   four instances: overwrite / accumulate, with and without the transmission
 //   sr_solar_jac_kernel<NR, ACC>         two instances: overwrite / accumulate, NR = kSolarJacRays rays per block
-//   sr_diffuse_source_kernel<ACC, WJ, WF> eight instances: overwrite / accumulate, with and without j_out / flux_out
+//   sr_diffuse_field_kernel<SOLAR, THERMAL, ACC, WJ, WF> twenty-four instances: the sun alone, thermal emission alone or
+//                                         both (never neither), each overwrite / accumulate, with and without j_out / flux_out
 //   sr_diffuse_tangent_kernel<NP, OPT>    two instances: NP = kDiffuseJacPars parameters per block; along column parameters,
 //                                         and (OPT) along a direction in ssa, asym and the surface albedo
 //   sr_diffuse_contract_kernel<NR, NP, ACC> two instances: overwrite / accumulate, kDiffuseJacRays x kDiffuseJacPars per thread
 //   sr_diffuse_columns_kernel<NC, ACC>    eight instances: NC = 1, 2, 4, 8 columns, overwrite / accumulate
-//   sr_diffuse_thermal_kernel<SOLAR, ACC, WJ, WF> sixteen instances: thermal alone / with the sun, and the sibling's eight
 #include "sr_device.hpp"
 #include "sr_kernels.hpp"
 #include "sr_limb_dispatch.hpp"
@@ -28,7 +28,6 @@ namespace sr {
 #include "sr_diffuse_source.inc"
 #include "sr_diffuse_jac.inc"
 #include "sr_diffuse_columns.inc"
-#include "sr_diffuse_thermal.inc"
 
 int launch_solar_source(const double *tab_abs, int n_k, int n_pts, const double *u, const double *w, const int *src_row,
                         int n_rows, const int *tile_off, const int *chunks, const double *sca_abs, const double *sun,
@@ -56,44 +55,28 @@ int launch_solar_jac(const double *tab_abs, int n_k, int n_pts, const double *du
   return (int)hipGetLastError();
 }
 
-int launch_diffuse_source(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, const double *v,
-                          const double *coef, const double *beam, const double *sun, double mu0, double albedo, int out_gas,
-                          double w_out, double *ws, int ws_stride, bool accumulate, double *emi_out, double *j_out,
-                          double *flux_out, hipStream_t st) {
+int launch_diffuse_field(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, const double *v,
+                         const double *coef, const double *temps, const double *beam, const double *sun, double mu0,
+                         double albedo, double t_surface, double w0, double step, int g_lo, bool own, int out_gas, double *ws,
+                         int ws_stride, bool accumulate, double *emi_out, double *j_out, double *flux_out, hipStream_t st) {
+  if (!beam && !temps) return (int)hipErrorInvalidValue; // a field without a source: <false, false> is not instantiated
   if (n_layers <= 0 || p_hi <= p_lo) return 0;
   const dim3 grid(limb_grid((p_hi - p_lo + 255) / 256, 1));
-  by_flag(accumulate && emi_out, [&](auto acc) {
-    by_flag(j_out != nullptr, [&](auto wj) {
-      by_flag(flux_out != nullptr, [&](auto wf) {
-        hipLaunchKernelGGL((sr_diffuse_source_kernel<decltype(acc)::value, decltype(wj)::value, decltype(wf)::value>), grid,
-                           dim3(256), 0, st, tab_abs, n_gas, n_layers, n_pts, p_lo, p_hi, v, coef, beam, sun, mu0, albedo, out_gas,
-                           w_out, ws, ws_stride, emi_out, j_out, flux_out);
-      });
-    });
-  });
-  return (int)hipGetLastError();
-}
-
-int launch_diffuse_thermal(const double *tab_abs, int n_gas, int n_layers, int n_pts, int p_lo, int p_hi, const double *v,
-                           const double *coef, const double *temps, const double *beam, const double *sun, double mu0,
-                           double albedo, double t_surface, double w0, double step, int g_lo, bool own, int out_gas,
-                           double *ws, int ws_stride, bool accumulate, double *emi_out, double *j_out,
-                           double *flux_out, hipStream_t st) {
-  if (n_layers <= 0 || p_hi <= p_lo) return 0;
-  const dim3 grid(limb_grid((p_hi - p_lo + 255) / 256, 1));
-  by_flag(beam != nullptr, [&](auto solar) {
+  auto go = [&](auto solar, auto thermal) {
     by_flag(accumulate && emi_out, [&](auto acc) {
       by_flag(j_out != nullptr, [&](auto wj) {
         by_flag(flux_out != nullptr, [&](auto wf) {
-          hipLaunchKernelGGL((sr_diffuse_thermal_kernel<decltype(solar)::value, decltype(acc)::value, decltype(wj)::value,
-                                                        decltype(wf)::value>),
+          hipLaunchKernelGGL((sr_diffuse_field_kernel<decltype(solar)::value, decltype(thermal)::value, decltype(acc)::value,
+                                                      decltype(wj)::value, decltype(wf)::value>),
                              grid, dim3(256), 0, st, tab_abs, n_gas, n_layers, n_pts, p_lo, p_hi, v, coef, temps, beam, sun, mu0,
-                             albedo, t_surface, w0, step, g_lo, (int)own, out_gas, ws, ws_stride, emi_out, j_out,
-                             flux_out);
+                             albedo, t_surface, w0, step, g_lo, (int)own, out_gas, ws, ws_stride, emi_out, j_out, flux_out);
         });
       });
     });
-  });
+  };
+  if (!temps) go(std::true_type{}, std::false_type{});
+  else if (!beam) go(std::false_type{}, std::true_type{});
+  else go(std::true_type{}, std::true_type{});
   return (int)hipGetLastError();
 }
 

@@ -695,6 +695,35 @@ def solar_source(A, U, w, sca, sun, src_row=None, out=None, accumulate=False, tr
     return (out, trans) if transmission else out
 
 
+def _diffuse_rules(out_gas, out, accumulate, asked, extra):
+    """The rules among the arguments of a diffuse call's rows, which need no device: `extra` maps the entry's own row
+    arguments to whether they are given, `asked`: J or F is."""
+    if out_gas is None:
+        if out is not None or accumulate or any(extra.values()):
+            names = ["out", "accumulate"] + list(extra)
+            raise ValueError("%s= and %s= belong to the rows of out_gas=" % ("=, ".join(names[:-1]), names[-1]))
+        if not asked:
+            raise ValueError("nothing asked for: out_gas=, mean_intensity=True or fluxes=True")
+    elif out is None and accumulate:
+        raise ValueError("accumulate=True adds to out=...")
+
+
+def _diffuse_outputs(out_gas, out, accumulate, rows_shape, j_shape, f_shape, extra=None, rows="n_layers"):
+    """The rows and outputs of a diffuse call: _diffuse_rules, then out checked against rows_shape (made where it is None
+    and out_gas given; `rows` names its rows in the refusal) and J and F made where a shape is given.  Returns (out, J, F, result): the three as the C entry
+    takes them, and what the call returns -- emi (if out_gas is given), then J, then F, as asked: one tensor or a tuple."""
+    _diffuse_rules(out_gas, out, accumulate, j_shape is not None or f_shape is not None, extra or {})
+    new = lambda shape: torch.empty(shape, dtype=torch.float64, device="cuda") if shape is not None else None
+    if out_gas is not None:
+        if out is None:
+            out = new(rows_shape)
+        elif not _cuda_f64(out) or out.shape != rows_shape:
+            raise ValueError("out must be a contiguous CUDA float64 [%s, n_pts]" % rows)
+    J, F = new(j_shape), new(f_shape)
+    res = tuple(t for t in (out, J, F) if t is not None)
+    return out, J, F, res[0] if len(res) == 1 else res
+
+
 def diffuse_source(A, V, ssa, asym, beam, sun, mu0, surface_albedo=0.0, out_gas=None, out=None, accumulate=False,
                    mean_intensity=False, fluxes=False):
     """Multiple scattering of sunlight as emission rows (sr_diffuse_source_rows_dev; the build's own definition, DESIGN.md
@@ -717,25 +746,13 @@ def diffuse_source(A, V, ssa, asym, beam, sun, mu0, surface_albedo=0.0, out_gas=
     treats the rows as coefficients; their derivative to VMR parameters is diffuse_jacobian
     (retrieval.inversion_state(diffuse_jacobian=True)), to T and Tvib it is not built.  Returns emi (if out_gas is given), then J, then F, as asked: one tensor or a tuple."""
     d, (n_gas, n_layers, n_pts), keep = _diffuse_state(A, V, ssa, asym, beam, sun, mu0, surface_albedo)
-    if out_gas is None:
-        if out is not None or accumulate:
-            raise ValueError("out= and accumulate= belong to the rows of out_gas=")
-        if not (mean_intensity or fluxes):
-            raise ValueError("nothing asked for: out_gas=, mean_intensity=True or fluxes=True")
-    elif out is None:
-        if accumulate:
-            raise ValueError("accumulate=True adds to out=...")
-        out = torch.empty((n_layers, n_pts), dtype=torch.float64, device="cuda")
-    elif not _cuda_f64(out) or out.shape != (n_layers, n_pts):
-        raise ValueError("out must be a contiguous CUDA float64 [n_layers, n_pts]")
-    J = torch.empty((n_layers, n_pts), dtype=torch.float64, device="cuda") if mean_intensity else None
-    F = torch.empty((2, n_layers + 1, n_pts), dtype=torch.float64, device="cuda") if fluxes else None
+    out, J, F, res = _diffuse_outputs(out_gas, out, accumulate, (n_layers, n_pts), (n_layers, n_pts) if mean_intensity else None,
+                                      (2, n_layers + 1, n_pts) if fluxes else None)
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     check(lib.sr_diffuse_source_rows_dev(C.byref(d), ptr(A), ptr(beam), ptr(sun), n_pts, -1 if out_gas is None else int(out_gas),
                                          int(bool(accumulate)), ptr(out), ptr(J), ptr(F), _stream_ptr()),
           "sr_diffuse_source_rows_dev")
-    res = tuple(t for t in (out, J, F) if t is not None)
-    return res[0] if len(res) == 1 else res
+    return res
 
 
 def diffuse_thermal_source(A, V, ssa, asym, temps, grid, t_surface=0.0, beam=None, sun=None, mu0=0.0, surface_albedo=0.0,
@@ -760,13 +777,7 @@ def diffuse_thermal_source(A, V, ssa, asym, temps, grid, t_surface=0.0, beam=Non
     # the rules among the arguments first, then the grid, then the tensors: what needs no device is refused without one
     if (beam is None) != (sun is None):
         raise ValueError("beam and sun: both (sunlight and thermal emission) or neither (thermal emission alone)")
-    if out_gas is None:
-        if out is not None or accumulate or own_emission:
-            raise ValueError("out=, accumulate= and own_emission= belong to the rows of out_gas=")
-        if not (mean_intensity or fluxes):
-            raise ValueError("nothing asked for: out_gas=, mean_intensity=True or fluxes=True")
-    elif out is None and accumulate:
-        raise ValueError("accumulate=True adds to out=...")
+    _diffuse_rules(out_gas, out, accumulate, mean_intensity or fluxes, {"own_emission": own_emission})
     w0, step, n_grid = grid_params(grid)
     ta, tp = _d(np.asarray(temps, dtype=np.float64))
     if ta.ndim != 1 or int(g_lo) < 0 or int(g_lo) >= n_grid:
@@ -778,19 +789,13 @@ def diffuse_thermal_source(A, V, ssa, asym, temps, grid, t_surface=0.0, beam=Non
         raise ValueError("the points g_lo .. g_lo + %d lie outside the grid's %d" % (n_pts, n_grid))
     th = _lib.DiffuseThermalDesc()
     th.temps, th.t_surface, th.w0, th.step, th.g_lo, th.own_emission = tp, float(t_surface), w0, step, int(g_lo), int(bool(own_emission))
-    if out_gas is not None:
-        if out is None:
-            out = torch.empty((n_layers, n_pts), dtype=torch.float64, device="cuda")
-        elif not _cuda_f64(out) or out.shape != (n_layers, n_pts):
-            raise ValueError("out must be a contiguous CUDA float64 [n_layers, n_pts]")
-    J = torch.empty((n_layers, n_pts), dtype=torch.float64, device="cuda") if mean_intensity else None
-    F = torch.empty((2, n_layers + 1, n_pts), dtype=torch.float64, device="cuda") if fluxes else None
+    out, J, F, res = _diffuse_outputs(out_gas, out, accumulate, (n_layers, n_pts), (n_layers, n_pts) if mean_intensity else None,
+                                      (2, n_layers + 1, n_pts) if fluxes else None)
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     check(lib.sr_diffuse_thermal_rows_dev(C.byref(d), C.byref(th), ptr(A), ptr(beam), ptr(sun), n_pts,
                                           -1 if out_gas is None else int(out_gas), int(bool(accumulate)), ptr(out), ptr(J), ptr(F),
                                           _stream_ptr()), "sr_diffuse_thermal_rows_dev")
-    res = tuple(t for t in (out, J, F) if t is not None)
-    return res[0] if len(res) == 1 else res
+    return res
 
 
 def diffuse_source_columns(A, V, ssa, asym, beams, sun, mu0s, col_w, row_layer, sca=None, src_row=None, surface_albedo=0.0,
@@ -825,12 +830,8 @@ def diffuse_source_columns(A, V, ssa, asym, beams, sun, mu0s, col_w, row_layer, 
     cd = _lib.DiffuseColumnsDesc()
     cd.n_col, cd.n_rows, cd.mu0 = n_col, 0, mp
     n_src = 0
-    if out_gas is None:
-        if out is not None or accumulate or sca is not None:
-            raise ValueError("out=, accumulate= and sca= belong to the rows of out_gas=")
-        if not (mean_intensity or fluxes):
-            raise ValueError("nothing asked for: out_gas=, mean_intensity=True or fluxes=True")
-    else:
+    n_rows = 0
+    if out_gas is not None:
         la, lp = _i(row_layer)
         if la.ndim != 1 or la.shape[0] == 0:
             raise ValueError("row_layer must be [n_rows], one row at the least")
@@ -850,21 +851,14 @@ def diffuse_source_columns(A, V, ssa, asym, beams, sun, mu0s, col_w, row_layer, 
         n_src = int(sca.shape[0])
         cd.n_rows, cd.col_w, cd.row_layer, cd.src_row = n_rows, wp, lp, sp
         keep = keep + (la, wa, sa)
-        if out is None:
-            if accumulate:
-                raise ValueError("accumulate=True adds to out=...")
-            out = torch.empty((n_rows, n_pts), dtype=torch.float64, device="cuda")
-        elif not _cuda_f64(out) or out.shape != (n_rows, n_pts):
-            raise ValueError("out must be a contiguous CUDA float64 [n_rows, n_pts]")
-    J = torch.empty((n_col, n_layers, n_pts), dtype=torch.float64, device="cuda") if mean_intensity else None
-    F = torch.empty((n_col, 2, n_layers + 1, n_pts), dtype=torch.float64, device="cuda") if fluxes else None
+    out, J, F, res = _diffuse_outputs(out_gas, out, accumulate, (n_rows, n_pts), (n_col, n_layers, n_pts) if mean_intensity else None,
+                                      (n_col, 2, n_layers + 1, n_pts) if fluxes else None, {"sca": sca is not None}, "n_rows")
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     check(lib.sr_diffuse_source_columns_dev(C.byref(d), C.byref(cd), ptr(A), ptr(beams), ptr(sun), n_pts, ptr(sca), n_src,
                                             -1 if out_gas is None else int(out_gas), int(bool(accumulate)), ptr(out), ptr(J), ptr(F),
                                             _stream_ptr()),
           "sr_diffuse_source_columns_dev")
-    res = tuple(t for t in (out, J, F) if t is not None)
-    return res[0] if len(res) == 1 else res
+    return res
 
 
 SOLAR_JAC_RAYS = 8      # rays per block of sr_solar_jac_kernel (kSolarJacRays): where the ray-group edge of a call sits

@@ -167,6 +167,21 @@ def test_superposition_on_the_device(eng):
     assert worst <= 1.0
 
 
+@pytest.mark.parametrize("key", [(2, 1, 63), (17, 3, 257)])
+def test_a_thermal_source_of_zero_gives_the_bits_of_diffuse_source(eng, key):
+    """Every ssa = 1 (alpha exactly 0 in every layer), no emitting surface, own_emission off, the sun on: the thermal
+    source is an exact 0, x + 0.0 keeps x and E+- is never -0 (E+ + E- >= +0), so the instance with both sources gives
+    the bits of the sun's alone.  Exact by construction: the two are instances of one kernel text."""
+    import torch
+    c = dict(T.panel_case(*key), ssa=np.ones(key[1]))
+    both = _call(eng, c, True, t_surface=0.0, own_emission=False, mean_intensity=True, fluxes=True)
+    sun = eng.diffuse_source(_dev(c["A"]), c["V"], c["ssa"], c["asym"], _dev(c["beam"]), _dev(c["sun"]), c["mu0"],
+                             surface_albedo=c["albedo"], out_gas=c["out_gas"], mean_intensity=True, fluxes=True)
+    assert bool((sun[1] > 0).any())
+    for k, b, s in zip(KEYS, both, sun):
+        assert torch.equal(b, s), k
+
+
 def test_own_rows_of_an_absorber_are_the_table_emission(eng):
     """ssa = 0: the own_emission rows are A B, what AbsorberTable.layers gives as emi for the same table and temperatures --
     within twice the absorber-table reference's allowance for the emission (the two kernels restate one Planck

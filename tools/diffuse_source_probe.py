@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times engine.diffuse_source (sr_diffuse_source_kernel) at the shape of a scene's solar pass -- 1e5 grid points, 80
+"""Times engine.diffuse_source (sr_diffuse_field_kernel) at the shape of a scene's solar pass -- 1e5 grid points, 80
 layers, the haze scene's two gases (a line gas and the scattering haze), the fused accumulate into the haze's rows -- with
 the two engine.solar_source calls of the same pass beside it (the single-scattering rows of 80 layer points, and the
 direct beam at the 80 layer middles plus the lower boundary, transmission=True), in alternating rounds in the same process

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times engine.diffuse_thermal_source (sr_diffuse_thermal_kernel) at the shape of a scene's pass -- 1e5 grid points, 80
+"""Times engine.diffuse_thermal_source (sr_diffuse_field_kernel) at the shape of a scene's pass -- 1e5 grid points, 80
 layers, the haze scene's two gases, the fused accumulate into the haze's rows with own_emission -- as the call with both
 sources (sun and thermal emission) and as the night call (thermal emission alone), beside engine.diffuse_source on the
 same arrays, in alternating rounds in the same process on the same device.  HIP events, medians of 20 calls after 3

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A host harness (tools/<name>/main.cpp: state_bands_host, state_gases_host, state_pointing_host, ils_host, absorber_table_host, limb_plan_host, many_gases_host, solar_source_host, solar_jacobian_host, diffuse_source_host, diffuse_jacobian_host, diffuse_optics_host, diffuse_columns_host, diffuse_thermal_host)
+# A host harness (tools/<name>/main.cpp: state_bands_host, state_gases_host, state_pointing_host, ils_host, absorber_table_host, limb_plan_host, many_gases_host, solar_source_host, solar_jacobian_host, diffuse_source_host, diffuse_jacobian_host, diffuse_optics_host, diffuse_columns_host)
 # built as a stand-alone program with AddressSanitizer and UBSan against the library's own kernel and plan files, and run.
 # usage: tools/host_sim/run.sh <name>
 set -e
