@@ -362,7 +362,8 @@ int sr_glevel_combine_dev(const double *tab, const double *tab_dT, int n_levels,
  * combine == 0: out_a: DEVICE [3][n_steps][n_pts] receives the interpolated set (out_e unused);
  * combine != 0: the population-weighted combine of make_abscoeff_isomolec (:2073-2080) is applied on the fly,
  * out_a[s] += pop[s] G_abs; out_a[s] -= pop[s] G_ind; out_e[s] += pop[s] G_sp (DEVICE [n_steps][n_pts],
- * zeroed by the caller before the first level).  idx4 / wgt4 / pop: HOST. */
+ * zeroed by the caller before the first level).  idx4 / wgt4 / pop: HOST.  A row outside the table or a weight
+ * that is not finite (any of the four of any step) is refused with SR_ERR_ARG before anything is written. */
 int sr_lut_interp_dev(const double *g_tab, int n_pt, int64_t n_pts, int n_steps, const int32_t *idx4,
                       const double *wgt4, const double *pop, int combine, double *out_a, double *out_e,
                       void *stream);

@@ -3878,6 +3878,7 @@ int sr_lut_interp_dev(const double *g_tab, int n_pt, int64_t n_pts, int n_steps,
     const int32_t *q = idx4 + 4 * s;
     const bool bil = q[2] >= 0;
     for (int i = 0; i < 4; ++i) {
+      if (!std::isfinite(wgt4[4 * s + i])) return SR_ERR_ARG; // (a planner that divided by T2 - T1 == 0)
       if (!bil && i >= 2) { if (q[i] >= 0) return SR_ERR_ARG; continue; }
       if (q[i] < 0 || q[i] >= n_pt) return SR_ERR_ARG; // would read out of the table
     }

@@ -202,18 +202,22 @@ class LutSet(object):
 
     # ---- interpolation (spect_main_module.py:997-1066) ----
     def interp_plan(self, Pres, Temp):
-        """Table rows and weights of LutSet.calculate for one (P, T): ([i1, i2, i3, i4], [wP1, wP2, wT1, wT2])."""
+        """Table rows and weights of LutSet.calculate for one (P, T): ([i1, i2, i3, i4], [wP1, wP2, wT1, wT2]).
+        The nearest node and the nearest of the remaining nodes, ties to the lower index: a stable sort, whose first
+        element is argmin's.  (The reference's default argsort may name argmin's node a second time when (P, T) lies
+        halfway between two nodes: T2 == T1, infinite weights.)"""
         from . import spect_base_module as sbm
         Ps = np.unique(np.array([PT[0] for PT in self.PTcouples]))
         Ts = np.unique(np.array([PT[1] for PT in self.PTcouples]))
-        order_t = np.argsort(np.abs(Ts - Temp))
-        T1, T2 = Ts[np.argmin(np.abs(Ts - Temp))], Ts[order_t[1]]
+        order_t = np.argsort(np.abs(Ts - Temp), kind="stable")
+        T1, T2 = Ts[order_t[0]], Ts[order_t[1]]
         wt = sbm.weight(Temp, T1, T2, itype='lin')
         if Pres <= np.min(Ps):
             P1 = np.min(Ps)
             return [self.find(P1, T1), self.find(P1, T2), -1, -1], [0.0, 0.0, wt[0], wt[1]]
         if Pres <= np.max(Ps):
-            P1, P2 = Ps[np.argmin(np.abs(Ps - Pres))], Ps[np.argsort(np.abs(Ps - Pres))[1]]
+            order_p = np.argsort(np.abs(Ps - Pres), kind="stable")
+            P1, P2 = Ps[order_p[0]], Ps[order_p[1]]
             wp = sbm.weight(Pres, P1, P2, itype='lin')
             return ([self.find(P1, T1), self.find(P1, T2), self.find(P2, T1), self.find(P2, T2)],
                     [wp[0], wp[1], wt[0], wt[1]])
