@@ -1295,7 +1295,13 @@ int sr_last_limb_route(void);
  * largest block count of a ray (gridDim.z), the number of ray blocks n_rb, the number of entries n_ent.  The arrays may
  * each be NULL (a first call for the sizes): ray_blk_off [n_rays + 1], blk [n_rb][2], col_row [n_rb][np],
  * ent_off [n_rb][n_layers + 1], slot_par [n_rb][np], ent_slot / ent_level / ent_c [n_ent].
- * Checked against the extended-precision recursion and the dense plan (tests/test_gpu_state_rayblocks.py). */
+ * Checked against the extended-precision recursion and the dense plan (tests/test_gpu_state_rayblocks.py).
+ * sr_last_state_instance: the census of the state kernel's compiled instances.  out[8] = NG, NP, COLS, ROWS, BANDS, INSTR,
+ * SEVERAL, RAYBLK of the instance the calling thread's most recent such call launched: the template's gas count (6 for a
+ * five-gas batch, 8 for seven), its slots per block (8 or 16), and 0 / 1 for column slots, row slots, the band epilogue,
+ * the instrument rows, several level gases, parameter blocks per ray.  The values are the compile-time constants of the
+ * instantiation that was launched, recorded where it is launched, not what the call asked for.  SR_ERR_ARG for a null
+ * pointer and before the thread's first launch.  tests/test_gpu_state_instances.py holds every instance to the reference. */
 int sr_set_state_ray_blocks(int on);
 /* The gases a ray batch may carry, sr_los_desc.n_gas: sr_limb_max_gases(0) = 8 for the entries of the path-order radiance
  * kernels and of the state kernel, sr_limb_max_gases(1) = 4 for the entries of every kernel that keeps four gas slots in
@@ -1315,6 +1321,7 @@ int sr_set_state_ray_blocks(int on);
 int sr_limb_max_gases(int folded);
 int sr_last_state_route(void);
 int64_t sr_last_state_walks(void);
+int sr_last_state_instance(int32_t out[8]);
 int sr_state_ray_plan(const sr_los_desc *los, int n_layers, int n_col, const int32_t *par_gas, const double *par_w, int n_lev,
                       const int32_t *par_lgas, const int32_t *par_level, const double *par_c, int n_row, const double *par_t,
                       int n_hid, int32_t *sizes4, int32_t *ray_blk_off, int32_t *blk, int32_t *col_row, int32_t *ent_off,

@@ -272,6 +272,7 @@ SYMBOLS = {
     "sr_limb_max_gases": (C.c_int, [C.c_int]),
     "sr_last_state_route": (C.c_int, []),
     "sr_last_state_walks": (C.c_int64, []),
+    "sr_last_state_instance": (C.c_int, [ip]),
     "sr_state_ray_plan": (C.c_int, [C.POINTER(LosDesc), C.c_int, C.c_int, ip, dp, C.c_int, ip, ip, dp, C.c_int, dp, C.c_int,
                                     ip, ip, ip, ip, ip, ip, ip, ip, dp]),
     "sr_set_far_field": (C.c_int, [C.c_int]),

@@ -2512,8 +2512,19 @@ static thread_local int g_last_state_route = 0;     // limb_jac_state: 1 the den
 static thread_local int64_t g_last_state_walks = 0; // its (ray, block) pairs
 int sr_last_state_route(void) { return g_last_state_route; }
 int64_t sr_last_state_walks(void) { return g_last_state_walks; }
+int sr_last_state_instance(int32_t out[8]) {
+  const sr::StateInstance &I = sr::g_last_state_instance;
+  if (!out || I.ng == 0) return SR_ERR_ARG;
+  const int32_t v[8] = {I.ng, I.np, I.cols, I.rows, I.bands, I.instr, I.several, I.rayblk};
+  std::copy(v, v + 8, out);
+  return SR_OK;
+}
 
 } // extern "C"
+
+namespace sr {
+thread_local StateInstance g_last_state_instance{}; // (sr_kernels.hpp: every state unit writes it)
+}
 
 // A LOS batch resident on the device (sr_los_create): the staged description, its Curtis-Godson columns and -- where
 // the rays share their shells -- the folded sweep's packed records, all made ONCE.  The reference computes a LOS's

@@ -354,6 +354,15 @@ struct StateLaunch {
   int np;
 };
 int launch_limb_jac_state(const StateLaunch &L, hipStream_t st);
+// The census of the state kernel's instances: the compile-time parameters of the instance the calling thread launched
+// last, written by launch_state_instances (sr_limb_state_launch.inc) in whichever unit launched it, from the constexpr
+// values of that instantiation -- never from the request.  One record, defined in sr_api.hip beside the last state
+// route; ng == 0: no launch yet.  Read by sr_last_state_instance.
+struct StateInstance {
+  int ng, np;
+  bool cols, rows, bands, instr, several, rayblk;
+};
+extern thread_local StateInstance g_last_state_instance;
 // The state units behind it, one translation unit each (sr_limb_state_unit.hpp): the kernel's instances for a pair of gas
 // counts and 8 or 16 slots per block, and those of five to eight gases (sr_limb_many.hip, 8 slots).  From the prelude of
 // launch_limb_jac_state -- the checks made, bd the band scratch's layout, n_row_par the parameter rows of a ray in

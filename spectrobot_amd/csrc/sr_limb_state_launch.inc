@@ -38,6 +38,7 @@ inline int launch_state_instances(const StateLaunch &L, const FoldBands &bd, int
                     hipLaunchKernelGGL((sr_limb_jac_state_kernel<NG, NP, COLS, ROWS, BANDS, INSTR, decltype(pack)...>), grid, dim3(256), 0,
                                        st, L.abs_c, L.emi_c, L.n_pts, L.n_layers, L.seg_off, L.seg_layer, L.col, L.dcol, L.o, L.n_rays, gas,
                                        tab, n_tab_rows, L.coef_row, L.blk, L.ent_off, L.ent, L.slot_par, n_row_par, rad, out, pack...);
+                    g_last_state_instance = StateInstance{NG, NP, COLS, ROWS, BANDS, INSTR, SEVERAL, RAYBLK}; // the census
                   };
                   auto launch = [&](auto... pack) { // the ray blocks last
                     if constexpr (RAYBLK) launch_pack(pack..., rbk);

@@ -2,6 +2,7 @@
 coefficient spectra, limb radiances.  torch is used for device memory, streams
 and (in distributed.py) the RCCL all-gather only.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -1383,13 +1384,17 @@ class _ParHandle(object):
 
 
 def _array_key(a):
-    """Key of an array for the resident-handle cache: a READ-ONLY ndarray cannot change under its identity (and the cache
-    entry keeps it alive, so the id is not re-used): ("id", id(a)), free; anything else by content (_content_key).
-    retrieval.LimbScene.profile_weights hands out read-only arrays: a retrieval iteration then pays no hashing of its
-    60 000-entry weight table (60-100 us of a 480 us iteration)."""
-    if isinstance(a, np.ndarray) and not a.flags.writeable:
+    """Key of an array for the resident-handle cache: a READ-ONLY ndarray that OWNS its data cannot change under its
+    identity (and the cache entry keeps it alive, so the id is not re-used): ("id", id(a)), free; anything else by content
+    (_content_key) -- a read-only view too: its base may be writable, and an edit through the base changes what the view
+    shows.  retrieval.LimbScene.profile_weights hands out read-only arrays that own their data: a retrieval iteration then
+    pays no hashing of its 60 000-entry weight table (60-100 us of a 480 us iteration)."""
+    if isinstance(a, np.ndarray) and a.base is None and a.flags.owndata and not a.flags.writeable:
         return ("id", id(a))
     return _content_key(a)
+
+
+_KEY_MULT = np.uint64(0x9E3779B97F4A7C15)   # an odd constant (2^64 / the golden ratio): spreads 2 pos + 1 over the word
 
 
 def _content_key(a):
@@ -1399,10 +1404,15 @@ def _content_key(a):
     if a.nbytes <= 4096 or a.nbytes % 8:
         return (a.dtype.str, a.shape, a.tobytes())
     # large tables (a retrieval's parameter weights, every iteration): two vectorised reductions over the 64-bit words
-    # -- xor and a position-weighted wrapped sum -- instead of a cryptographic hash (30 us against 0.5 ms per call)
+    # -- xor and a position-weighted wrapped sum -- instead of a cryptographic hash (0.5 ms per call).  Every position
+    # has its own odd multiplier, (2 pos + 1) K mod 2^64: two words that change places move the sum by
+    # (f(a) - f(b)) 2 (i - j) K, which is 0 only if f(a) - f(b) is a multiple of 2^63 / (i - j)'s power of two.  f folds
+    # a word's upper half into its lower (a bijection), so that x and -x -- words that differ in bit 63 alone -- do not
+    # meet that condition as neighbours.
     w = a.reshape(-1).view(np.uint64)
-    pos = np.arange(1, w.size + 1, dtype=np.uint64)
-    return (a.dtype.str, a.shape, int(np.bitwise_xor.reduce(w)), int((w * (pos | np.uint64(1))).sum(dtype=np.uint64)))
+    mult = (np.arange(w.size, dtype=np.uint64) * np.uint64(2) + np.uint64(1)) * _KEY_MULT
+    f = w ^ (w >> np.uint64(31))
+    return (a.dtype.str, a.shape, int(np.bitwise_xor.reduce(w)), int((f * mult).sum(dtype=np.uint64)))
 
 
 class LimbLOS(object):
@@ -2451,6 +2461,20 @@ def last_state_route():
     """(route, walks) of this thread's last mixed-state call: route 1 the dense plan, 2 parameter blocks per ray, 0 none
     yet; walks: its (ray, block) pairs, how often a ray was walked (sr_last_state_route, sr_last_state_walks)."""
     return int(lib.sr_last_state_route()), int(lib.sr_last_state_walks())
+
+
+StateInstance = collections.namedtuple("StateInstance", "ng np cols rows bands instr several rayblk")
+
+
+def last_state_instance():
+    """StateInstance(ng, np, cols, rows, bands, instr, several, rayblk): the compile-time parameters of the state kernel's
+    instance that the calling thread's most recent mixed-state call launched (sr_last_state_instance) -- the template's
+    gas count (6 for a five-gas batch, 8 for seven), its slots per block, and the flags as bools -- recorded at the
+    launch itself, not what the call asked for.  None before the thread's first launch."""
+    out = (C.c_int32 * 8)()
+    if lib.sr_last_state_instance(out) != _lib.SR_OK:
+        return None
+    return StateInstance(int(out[0]), int(out[1]), *(bool(v) for v in out[2:]))
 
 
 def state_ray_plan(los, n_layers, par_gas=None, par_w=None, par_level=None, par_c=None, par_t=None, par_lgas=None, n_hid=0):
